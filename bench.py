@@ -12,11 +12,14 @@ batch are kept in flight and alternate (the library runs each plan on one of its
 kernels of one pass fill the CUs the next pass's join has not reached or has already left.
 Weak scaling: every rank processes its own batch of the same shape.
 
-Prints ONE JSON line on rank 0.  `value` is the resident-kernel rate (inputs in HBM, window size fixed at 10);
-`inclusive` next to it is the rate when every batch also pays upload + packing, planning and the self dot plots of
-window_size_refine (SF:2030-2046), `sub` repeats the resident measurement on BASELINE configs[2] ("cfg3").
-`roofline` is measured live with HIP events on the library's streams (vapor_plan_timings); `cpu_baseline` times the
-CPU oracle (oracle/, a restatement: kind "port") on a bounded sample of the same pairs, 1 thread.
+Prints ONE JSON line on rank 0.  `value` is the resident-kernel rate (inputs in HBM, window size fixed at 10); a plain run
+does nothing else: set-up, warm-up, the timed steps, the line (and the last step's records with --dump-outputs DIR, as
+DIR/loci_records.npy).  With --full the line also carries what takes work of its own beside the timed steps: the per-pair
+statistics with the device / host finish cross-check, `roofline`, `inclusive` (the rate when every batch also pays upload +
+packing, planning and the self dot plots of window_size_refine, SF:2030-2046), the pipeline and files-path rates, `sub`
+(the resident measurement on BASELINE configs[2], "cfg3"), `cpu_baseline` (the CPU oracle - oracle/, a restatement: kind
+"port" - on a bounded sample of the same pairs, 1 thread) and, for N > 1, the strong-scaling record.  `roofline` is measured
+live with HIP events on the library's streams (vapor_plan_timings).
 """
 from __future__ import annotations
 
@@ -227,6 +230,10 @@ def main() -> None:
     ap.add_argument("--param", action="append", default=[], help="engine parameter name=value (development: A/B of a kernel route)")
     ap.add_argument("--strong-loci", type=int, default=10000, help="N > 1: records of the cfg4 VCF sharded over the ranks (0 = skip)")
     ap.add_argument("--strong-base", type=int, default=300, help="distinct loci of that world (tiled up to --strong-loci)")
+    ap.add_argument("--full", action="store_true", help="also everything beside the headline: statistics cross-check, roofline, "
+                    "inclusive / pipeline / files rates, the --sub record, the CPU baseline, N > 1: the strong-scaling record")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's per-locus records to DIR/loci_records.npy (float64)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -335,7 +342,7 @@ def main() -> None:
     avg = {key: sum(t[0][key] * wt for t, wt in zip(tm, wts)) / max(sum(wts), 1) for key in ("join_ms", "clean_ms", "total_ms", "finish_ms")}
     for key in ("clean_workgroups_per_cu", "remap_in_clean"):      # (the plan's geometry, not a time)
         avg[key] = tm[0][0].get(key)
-    last_rec = tm[(n_passes - 1) % n_plans][1]
+    last_rec = tm[(res.i - 1) % n_plans][1]          # (the plan of the last pass: res.i counts the probe and warm-up passes too)
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -343,31 +350,35 @@ def main() -> None:
         if res.gathered is not None:
             # the last pass of every rank: slot inner - 1 of its share of the gathered step
             last_rec = res.gathered.view(world, inner, w.n_loci, 8)[:, inner - 1].cpu().numpy()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_rec)
 
-    # untimed: per-pair statistics once, for the algorithmic byte count and the oracle cross-check; and the
-    # host-side finish on the same statistics must agree with what the device produced
-    plan = res.plans[0]
-    st = plan.run().copy()
-    host_rec = wl.finish_workload(w, st)
-    dev_rec = plan.run_loci().copy()
-    ok = ~np.isnan(host_rec[:, 0])
-    assert np.array_equal(np.isnan(dev_rec[:, 0]), ~ok) and np.array_equal(dev_rec[ok, 2], host_rec[ok, 2]) \
-        and np.allclose(dev_rec[ok, :2], host_rec[ok, :2], rtol=0, atol=1e-9), "device / host finish mismatch"
-    alg_bytes, cells = plan.algorithmic()
-    n_rec = int(plan.record_counts().sum())
     n_pairs = len(w.pairs)
-    launches = plan.timings()["join_launches"]
+    launches = res.plans[0].timings()["join_launches"]
     ms_per_step = elapsed / max(args.steps, 1) * 1e3
     loci_s = w.n_loci * world * n_passes / elapsed
-    cells_s = cells * world * n_passes / elapsed
-    src_id = kernel_source_id()
-    roof = roofline_record(args.workload, alg_bytes, n_rec, elapsed / n_passes * 1e3,
-                           {"join": avg["join_ms"], "clean": avg["clean_ms"], "finish": avg["finish_ms"]},
-                           {"join": res.alone["join_ms"], "clean": res.alone["clean_ms"]}, src_id)
-
     extras = {}
     cpu = None
-    if rank == 0 and world == 1:
+    if args.full:
+        # untimed: per-pair statistics once, for the algorithmic byte count and the oracle cross-check; and the
+        # host-side finish on the same statistics must agree with what the device produced
+        plan = res.plans[0]
+        st = plan.run().copy()
+        host_rec = wl.finish_workload(w, st)
+        dev_rec = plan.run_loci().copy()
+        ok = ~np.isnan(host_rec[:, 0])
+        assert np.array_equal(np.isnan(dev_rec[:, 0]), ~ok) and np.array_equal(dev_rec[ok, 2], host_rec[ok, 2]) \
+            and np.allclose(dev_rec[ok, :2], host_rec[ok, :2], rtol=0, atol=1e-9), "device / host finish mismatch"
+        alg_bytes, cells = plan.algorithmic()
+        n_rec = int(plan.record_counts().sum())
+        launches = plan.timings()["join_launches"]
+        cells_s = cells * world * n_passes / elapsed
+        src_id = kernel_source_id()
+        roof = roofline_record(args.workload, alg_bytes, n_rec, elapsed / n_passes * 1e3,
+                               {"join": avg["join_ms"], "clean": avg["clean_ms"], "finish": avg["finish_ms"]},
+                               {"join": res.alone["join_ms"], "clean": res.alone["clean_ms"]}, src_id)
+
+    if args.full and rank == 0 and world == 1:
         if not args.no_extras:
             extras["inclusive"] = inclusive_rate(eng, w, wl)
             extras["pipeline"] = pipeline_rate()
@@ -380,7 +391,7 @@ def main() -> None:
     strong = None
     # (VAPOR_BENCH_FORCE_STRONG=1 with VAPOR_BENCH_FORCE_DIST=1: the same leg with a world of one - on a one-GPU box the only way
     # to take the product's gather through RCCL: vapor_amd.dist on CUDA tensors, all_gather_object under nccl)
-    if world > 1 or (dist is not None and os.environ.get("VAPOR_BENCH_FORCE_STRONG") == "1"):
+    if args.full and (world > 1 or (dist is not None and os.environ.get("VAPOR_BENCH_FORCE_STRONG") == "1")):
         # N > 1: the CPU baseline on rank 0 after the timed region (the other ranks wait at the next barrier), and the
         # fixed-size workload north_star's multi-GPU configurations describe: configs[3]'s 10 000-record VCF sharded over
         # the ranks by estimated cost, scored through the product drivers, one gather of the scores (strong scaling)
@@ -419,9 +430,10 @@ def main() -> None:
                        "parallelism": "loci sharded over %d GPU(s)" % world},
             "timed_region_s": round(elapsed, 4),
             "ms_per_pass": round(elapsed / n_passes * 1e3, 5),
-            "cells_per_s": round(cells_s, 1),
-            "hits_per_pass": int(st[:, 0].sum()),
-            "records_per_pass": n_rec,
+        }
+        if args.full:
+            out.update({"cells_per_s": round(cells_s, 1), "hits_per_pass": int(st[:, 0].sum()), "records_per_pass": n_rec})
+        out.update({
             "loci_with_scores": int(np.isfinite(np.asarray(last_rec).reshape(-1, 8)[:, 0]).sum()),
             "kernel_ms": {"join": round(avg["join_ms"], 4), "clean": round(avg["clean_ms"], 4), "finish": round(avg["finish_ms"], 4),
                           "device_total": round(avg["total_ms"], 4), "join_launches": launches,
@@ -433,12 +445,12 @@ def main() -> None:
                                   "share the CUs and their intervals overlap: their sum over the passes exceeds the step), not serial "
                                   "costs; `alone` is each kernel by itself on an otherwise idle device"},
             "upload_pack_s": round(res.upload_s, 4),
+        })
+        if args.full:
             # (roofline_record: the kernel with the largest share of GPU time, its HBM fraction on the algorithmic bytes, the
             # fabric bytes the counters saw, and the fraction of the vector-issue roof the kernels really sit under)
-            "roofline": roof,
-            "kernel_source_id": src_id,
-            "cpu_baseline": cpu,
-        }
+            out.update({"roofline": roof, "kernel_source_id": src_id, "cpu_baseline": cpu})
+        out["full"] = bool(args.full)
         out["gpu_max_hw_queues"] = os.environ.get("GPU_MAX_HW_QUEUES", "unset (HIP default: 4)")
         if strong is not None:
             # N > 1: the fixed call set sharded over the ranks (north_star's multi-GPU configuration) leads the line, right behind
@@ -472,6 +484,14 @@ def main() -> None:
     res.close()
     if dist is not None:
         dist.destroy_process_group()
+
+
+def dump_outputs(d, last_rec):
+    """--dump-outputs: what the timed path hands its caller, from its last step - the per-locus records [QS, GS, GT index,
+    GQ, n scored, n positive, n rounding to <= 0, 0] of the last pass (NaN row = 'NA'), float64, (loci, 8); for N > 1 every
+    rank's, (ranks, loci, 8).  The batch is seeded (1000 + rank), so two builds can be compared record for record."""
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "loci_records.npy"), np.ascontiguousarray(last_rec, dtype=np.float64))
 
 
 def spawn_ranks(n: int) -> int:

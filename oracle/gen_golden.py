@@ -1135,10 +1135,25 @@ def gen_parsers(m):
                              "cases": cases})
 
 
+def gen_parser_files(m):
+    """The whole fixture files gen_parsers read, as data (VCF / BED text keyed by their path in the reference), so that
+    tests/test_parsers_reference_files.py compares whole files on every machine.  xz: the per-chromosome files repeat one
+    another, 10.7 MB of text pack to about 0.2 MB."""
+    import lzma
+    base, files = parser_inputs()
+    out = {"source": "vapor_test/vapor_test.{vcf,bed} and simulate/Structural_Variants_{het,homo}/*.{vcf,bed}, verbatim",
+           "files": {os.path.relpath(f, base): open(f).read() for f in files}}
+    p = os.path.join(OUT, "parser_files.json.xz")
+    with lzma.open(p, "wb", preset=9 | lzma.PRESET_EXTREME) as f:
+        f.write(json.dumps(out, separators=(",", ":")).encode())
+    print("wrote parser_files.json.xz: %d files, %.1f KB" % (len(files), os.path.getsize(p) / 1024))
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     m = load_reference()
-    which = sys.argv[1:] or ["kmerhits", "cleaners", "scorers", "window", "genotype", "io", "locus", "vcf", "other", "config1", "melt", "complex", "deep", "figures", "parsers"]
+    which = sys.argv[1:] or ["kmerhits", "cleaners", "scorers", "window", "genotype", "io", "locus", "vcf", "other", "config1", "melt", "complex", "deep", "figures", "parsers",
+                             "parser_files"]
     for w in which:
         print("== " + w)
         globals()["gen_" + w](m)

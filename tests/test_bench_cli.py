@@ -5,6 +5,7 @@ import json
 import os
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -53,3 +54,24 @@ def test_counter_summaries_carry_the_source_they_were_measured_on():
     for name in ("r03_cfg2_traffic.json", "r03_cfg2_util.json"):
         d = json.load(open(os.path.join(ROOT, "profiles", name)))
         assert "source_id" in d and "join_kernel" in d
+
+
+def test_full_and_dump_outputs_reach_the_ranks(monkeypatch):
+    """--full and --dump-outputs are options of a rank like any other: `--gpus N` hands them on unchanged."""
+    calls = []
+    import subprocess
+    monkeypatch.setattr(subprocess, "call", lambda cmd, env=None: calls.append(cmd) or 0)
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "2", "--steps", "4", "--full", "--dump-outputs", "out"])
+    with pytest.raises(SystemExit) as ei:
+        bench.main()
+    assert ei.value.code == 0 and calls[0][-7:] == ["--gpus", "2", "--steps", "4", "--full", "--dump-outputs", "out"]
+
+
+def test_dump_outputs_writes_float64_records(tmp_path):
+    rec = np.arange(24, dtype=np.float64).reshape(3, 8)
+    rec[1] = np.nan
+    bench.dump_outputs(str(tmp_path / "d"), rec)
+    got = np.load(tmp_path / "d" / "loci_records.npy")
+    assert got.dtype == np.float64 and got.shape == (3, 8)
+    assert np.array_equal(got, rec, equal_nan=True)

@@ -3,19 +3,21 @@ records), vapor_test.bed and every simulate/Structural_Variants_{het,homo}/*.vcf
 vcf_list_readin / bed_info_readin (vapor_vali/vapor:22-50, 127-202) when tests/golden/parsers.json.gz was made
 (oracle/gen_golden.py parsers); here they go through vapor_amd.cli's.  Compared: a digest of the returned structure - bucket
 dict in first-seen order and record-index map for a VCF, the row list for a BED - or the exception type where the reference
-raises (the 4-column BEDs: pin[4], vapor_vali/vapor:31; their 5-column re-expression parses).  The whole files are read where
-/root/reference is mounted (the development container); their first 300 lines (the two vapor_test files whole) are part of
-the fixture and are compared everywhere."""
+raises (the 4-column BEDs: pin[4], vapor_vali/vapor:31; their 5-column re-expression parses).  Both the whole files
+(tests/golden/parser_files.json.xz, the reference's fixture files verbatim, oracle/gen_golden.py parser_files) and their
+first 300 lines (part of parsers.json.gz) are compared."""
 import hashlib
 import json
+import lzma
 import os
 
 import pytest
 
-from conftest import load_golden
+from conftest import GOLDEN, load_golden
 
 GOLD = load_golden("parsers.json.gz")
-REF_ROOT = "/root/reference"
+with lzma.open(os.path.join(GOLDEN, "parser_files.json.xz"), "rt") as _f:
+    FILES = json.load(_f)["files"]
 
 
 def _digest(obj) -> str:
@@ -51,13 +53,11 @@ def test_parsers_on_the_reference_fixture_files(case, tmp_path):
     assert _run(kind, case["slice_text"], tmp_path) == case["slice"]
     if kind == "bed":
         assert _run(kind, _five_columns(case["slice_text"]), tmp_path) == case["slice_5col"]
-    full = os.path.join(REF_ROOT, case["file"])
-    if os.path.exists(full):
-        text = open(full).read()
-        assert hashlib.sha256(text.encode()).hexdigest() == case["input_sha256"]
-        assert _run(kind, text, tmp_path) == case["whole"]
-        if kind == "bed":
-            assert _run(kind, _five_columns(text), tmp_path) == case["whole_5col"]
+    text = FILES[case["file"]]
+    assert hashlib.sha256(text.encode()).hexdigest() == case["input_sha256"]
+    assert _run(kind, text, tmp_path) == case["whole"]
+    if kind == "bed":
+        assert _run(kind, _five_columns(text), tmp_path) == case["whole_5col"]
 
 
 def test_parser_fixture_covers_what_the_survey_names():
