@@ -38,6 +38,7 @@ extern "C" {
 #define VAPOR_E_NOMEM (-5)
 
 #define VAPOR_MAX_SEQ_LEN 65535 /* positions are packed 16+16 bit on the device */
+#define VAPOR_MAX_WIDE_SEQ_LEN 1048575 /* the wide route (vapor_wide_batch, vapor_clean_hits_wide): 2^20 - 1 */
 
 typedef struct vapor_ctx vapor_ctx;
 typedef struct vapor_seqset vapor_seqset;
@@ -263,6 +264,28 @@ int vapor_selfplot_qc(vapor_ctx* ctx, vapor_seqset* set, int32_t n, const int32_
  */
 int vapor_clean_hits(vapor_ctx* ctx, int64_t n_lists, const int32_t* hits_ji, const int64_t* off,
                      const uint32_t* flags, int64_t* stats, uint8_t* hit_flags);
+
+/* ---- the wide route: sequences longer than VAPOR_MAX_SEQ_LEN ------------------------------- */
+/*
+ * The entry points above refuse a sequence longer than VAPOR_MAX_SEQ_LEN (their device records pack positions 16+16 bit).
+ * These two take any pair they accept plus sequences up to VAPOR_MAX_WIDE_SEQ_LEN: one pair at a time, one dot per 8 bytes
+ * (32-bit positions), the dot slot sized by a count pass, the cleaning's value bitmaps in HBM.  The results are those of the
+ * narrow route for every pair both accept.
+ *
+ * vapor_wide_batch: the statistics record of every pair (as vapor_plan_run: VAPOR_ST_STATUS = VAPOR_E_ARG for a bad index,
+ * an unsupported k or a sequence longer than VAPOR_MAX_WIDE_SEQ_LEN, VAPOR_E_KEYERROR as the reference raises it,
+ * VAPOR_E_OVERFLOW for a pair with more than "max_pair_cap" dots - its count pass stops there, VAPOR_ST_RECORDS_NEEDED holds
+ * the dots counted until then, more than the cap; the call itself
+ * returns VAPOR_OK).  hits_ji (may be NULL) receives the dots of pair t as (j, i) int32 pairs at hit_off[t] .. hit_off[t+1]
+ * in unspecified order inside a pair (dotdata's list is these sorted by (j, i)); hit_off (n_pairs + 1 entries, may be NULL
+ * when hits_ji is) is always filled, and VAPOR_E_OVERFLOW is returned, with the statistics complete, when hit_off[n_pairs]
+ * exceeds hits_capacity.
+ * vapor_clean_hits_wide: vapor_clean_hits for lists whose coordinates lie in 0 .. VAPOR_MAX_WIDE_SEQ_LEN.
+ */
+int vapor_wide_batch(vapor_ctx* ctx, vapor_seqset* set, int64_t n_pairs, const vapor_pair* pairs, int64_t* stats,
+                     int32_t* hits_ji, int64_t hits_capacity, int64_t* hit_off);
+int vapor_clean_hits_wide(vapor_ctx* ctx, int64_t n_lists, const int32_t* hits_ji, const int64_t* off,
+                          const uint32_t* flags, int64_t* stats, uint8_t* hit_flags);
 
 /*
  * Host helper of the read extraction (cigar2alignstart_by_pos, SF:309-337; no device involved): walks the CIGAR of

@@ -658,3 +658,18 @@ extern "C" int vapor_row_tails(int32_t n_loci, const int64_t* off, const double*
         return bfail(VAPOR_E_NOMEM, "vapor_row_tails: out of memory");
     }
 }
+
+// The wide route (vapor_wide_batch, vapor_clean_hits_wide) is device code in vapor_hip.hip, whose definitions take precedence
+// over these weak ones in the library.  A build of this file without it - the CPU twin of the C ABI (oracle/, test
+// infrastructure), which has no wide route - answers every call with VAPOR_E_ARG, so that it still exports the whole header.
+extern "C" __attribute__((weak)) int vapor_wide_batch(vapor_ctx*, vapor_seqset*, int64_t, const vapor_pair*, int64_t*, int32_t*,
+                                                      int64_t, int64_t*)
+{
+    return bfail(VAPOR_E_ARG, "vapor_wide_batch: this build has no wide route");
+}
+
+extern "C" __attribute__((weak)) int vapor_clean_hits_wide(vapor_ctx*, int64_t, const int32_t*, const int64_t*, const uint32_t*,
+                                                           int64_t*, uint8_t*)
+{
+    return bfail(VAPOR_E_ARG, "vapor_clean_hits_wide: this build has no wide route");
+}

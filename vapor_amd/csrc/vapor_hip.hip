@@ -6,6 +6,7 @@
 // Everything the GPU touches is resident in HBM between calls: a vapor_seqset holds the packed
 // bit planes, a vapor_plan holds pair/task descriptors, the hit workspace and the statistics.
 #include "vapor_kernels.h"
+#include "vapor_wide.h"
 #include "vapor_bamdev.h"
 #include "vapor_hip.h"
 
@@ -2190,6 +2191,268 @@ extern "C" int vapor_clean_hits(vapor_ctx* ctx, int64_t n_lists, const int32_t* 
     }
     dfree(ctx, d_ov); dfree(ctx, d_big); dfree(ctx, d_dp); dfree(ctx, d_nh); dfree(ctx, d_hits); dfree(ctx, d_fl); dfree(ctx, d_st);
     return rc;
+}
+
+// ------------------------------------------------------------------------------------------
+// The wide route (vapor_wide.h): sequences up to VAPOR_MAX_WIDE_SEQ_LEN, one pair at a time, explicit dots with 32-bit
+// positions.  The narrow entry points above keep their limit and their refusals.
+namespace {
+
+struct WideBufs {
+    vapor_ctx* c = nullptr;
+    void* p[10] = {};
+    size_t cap[10] = {};
+    enum { KEYS, HEAD, NEXT, CNT, OFF, DOTS, FL, SCR, ACC, BOOK };
+    ~WideBufs() { for (void* q : p) dfree(c, q); }
+    // grow-only: the contents are not kept
+    hipError_t ensure(int b, size_t bytes)
+    {
+        bytes = std::max<size_t>(bytes, 256);
+        if (cap[b] >= bytes) return hipSuccess;
+        dfree(c, p[b]);
+        p[b] = nullptr;
+        cap[b] = 0;
+        hipError_t e = dmalloc(c, &p[b], bytes);
+        if (e == hipSuccess) cap[b] = bytes;
+        return e;
+    }
+    template <typename T> T* at(int b) const { return reinterpret_cast<T*>(p[b]); }
+};
+
+inline unsigned wide_grid(int64_t n) { return (unsigned)((n + 255) / 256); }
+
+// Cleaning and reductions of the n dots in b.DOTS (coordinates i <= maxi, j <= maxj), enqueued on st; the results land in
+// b.ACC, which the caller has initialised.
+hipError_t wide_clean(WideBufs& b, hipStream_t st, int n, int maxi, int maxj, uint32_t flags)
+{
+    const int2* dots = b.at<int2>(WideBufs::DOTS);
+    uint8_t* fl = b.at<uint8_t>(WideBufs::FL);
+    WideAcc* acc = b.at<WideAcc>(WideBufs::ACC);
+    const bool c1 = flags & 1u, c2 = flags & 2u, s3 = c1 && (flags & 4u);
+    const int R = maxi + maxj + 1, shift = maxj;
+    hipError_t e = b.ensure(WideBufs::SCR, sizeof(uint32_t) * 3 * (size_t)R);
+    if (e != hipSuccess) return e;
+    uint32_t* cnt = b.at<uint32_t>(WideBufs::SCR);
+    uint32_t* gid = cnt + R;
+    uint32_t* gsize = gid + R;
+    auto cluster = [&](int axis, uint32_t skip, int slot, int mode) -> hipError_t {
+        hipError_t e2 = hipMemsetAsync(cnt, 0, sizeof(uint32_t) * (size_t)R, st);
+        if (e2 == hipSuccess) e2 = hipMemsetAsync(gsize, 0, sizeof(uint32_t) * (size_t)R, st);
+        if (e2 != hipSuccess) return e2;
+        hipLaunchKernelGGL(wide_hist_kernel, dim3(wide_grid(n)), dim3(256), 0, st, dots, (const uint8_t*)fl, n, axis, shift, skip, cnt);
+        hipLaunchKernelGGL(wide_group_kernel, dim3(1), dim3(WIDE_SCAN_THREADS), 0, st, (const uint32_t*)cnt, R, gid, gsize, acc, slot);
+        hipLaunchKernelGGL(wide_flag_kernel, dim3(wide_grid(n)), dim3(256), 0, st, dots, fl, n, mode, shift, flags,
+                           (const uint32_t*)gid, (const uint32_t*)gsize, (const WideAcc*)acc);
+        return hipGetLastError();
+    };
+    if (n <= 0) return hipSuccess;
+    if (c1 || c2) {
+        if ((e = cluster(0, 0u, 0, 0)) != hipSuccess) return e;
+        if (c1 && (e = cluster(1, 0u, 1, 1)) != hipSuccess) return e;
+        if (c2 && (e = cluster(1, HF_C2D, 2, 2)) != hipSuccess) return e;
+    } else if ((e = hipMemsetAsync(fl, 0, (size_t)n, st)) != hipSuccess) {
+        return e;
+    }
+    hipLaunchKernelGGL(wide_reduce_kernel, dim3(wide_grid(n)), dim3(256), 0, st, dots, fl, n, acc);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (s3) {
+        if ((e = hipMemsetAsync(cnt, 0, sizeof(uint32_t) * (size_t)R, st)) != hipSuccess) return e;
+        hipLaunchKernelGGL(wide_dir_kernel, dim3(1), dim3(WIDE_SCAN_THREADS), 0, st, dots, (const uint8_t*)fl, n, acc, cnt);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+WideAcc wide_acc_init()
+{
+    WideAcc a;
+    memset(&a, 0, sizeof(a));
+    a.min_j = 0x7FFFFFFF; a.max_j = -1; a.kd_lo = 0x7FFFFFFF; a.kd_hi = -0x7FFFFFFF;
+    return a;
+}
+
+void wide_stats(const WideAcc& a, int64_t n, uint32_t flags, int64_t* st)
+{
+    const bool s3 = (flags & 1u) && (flags & 4u);
+    for (int t = 0; t < 16; ++t) st[t] = 0;
+    st[0] = n;
+    st[1] = n ? a.min_j : -1;
+    st[2] = n ? a.max_j : -1;
+    if (!n) return;
+    st[3] = (int64_t)a.c1_kept; st[4] = (int64_t)a.c1_sum_abs; st[5] = (int64_t)a.c2_kept; st[6] = (int64_t)a.c2_count10;
+    st[7] = (int64_t)a.n_diag; st[8] = (int64_t)a.n_lower; st[9] = (int64_t)a.c2_kept_diag;
+    if (s3) { st[10] = a.dir_c2x; st[11] = a.dir_n; st[12] = a.dir_sum2; st[13] = a.dir_lists; }
+}
+
+template <int K>
+void wide_join_launch(WideBufs& b, hipStream_t st, const uint32_t* x4_1, int nk1, const uint32_t* x4_2, int off2, int nk2,
+                      uint32_t hmask, bool emit, unsigned long long cap)
+{
+    const WKey<K>* keys = b.at<const WKey<K>>(WideBufs::KEYS);
+    if (!emit) {
+        hipLaunchKernelGGL(wide_table_kernel<K>, dim3(wide_grid(2 * (int64_t)nk1)), dim3(256), 0, st, x4_1, nk1, b.at<WKey<K>>(WideBufs::KEYS),
+                           b.at<int32_t>(WideBufs::HEAD), b.at<int32_t>(WideBufs::NEXT), hmask);
+        hipLaunchKernelGGL((wide_probe_kernel<K, false>), dim3(wide_grid(nk2)), dim3(256), 0, st, x4_2, off2, nk2, keys,
+                           (const int32_t*)b.at<int32_t>(WideBufs::HEAD), (const int32_t*)b.at<int32_t>(WideBufs::NEXT), hmask,
+                           b.at<uint32_t>(WideBufs::CNT), (const long long*)nullptr, (int2*)nullptr,
+                           b.at<unsigned long long>(WideBufs::BOOK), cap);
+        hipLaunchKernelGGL(wide_scan_kernel, dim3(1), dim3(WIDE_SCAN_THREADS), 0, st, (const uint32_t*)b.at<uint32_t>(WideBufs::CNT), nk2,
+                           b.at<long long>(WideBufs::OFF));
+    } else {
+        hipLaunchKernelGGL((wide_probe_kernel<K, true>), dim3(wide_grid(nk2)), dim3(256), 0, st, x4_2, off2, nk2, keys,
+                           (const int32_t*)b.at<int32_t>(WideBufs::HEAD), (const int32_t*)b.at<int32_t>(WideBufs::NEXT), hmask,
+                           (uint32_t*)nullptr, (const long long*)b.at<long long>(WideBufs::OFF), b.at<int2>(WideBufs::DOTS),
+                           (unsigned long long*)nullptr, cap);
+    }
+}
+
+void wide_join(int k, WideBufs& b, hipStream_t st, const uint32_t* x4_1, int nk1, const uint32_t* x4_2, int off2, int nk2,
+               uint32_t hmask, bool emit, unsigned long long cap)
+{
+    switch (k) {
+    case 10: wide_join_launch<10>(b, st, x4_1, nk1, x4_2, off2, nk2, hmask, emit, cap); break;
+    case 20: wide_join_launch<20>(b, st, x4_1, nk1, x4_2, off2, nk2, hmask, emit, cap); break;
+    case 30: wide_join_launch<30>(b, st, x4_1, nk1, x4_2, off2, nk2, hmask, emit, cap); break;
+    default: wide_join_launch<40>(b, st, x4_1, nk1, x4_2, off2, nk2, hmask, emit, cap); break;
+    }
+}
+
+}  // namespace
+
+#define WIDE_CHK(expr)                                                                        \
+    do {                                                                                      \
+        hipError_t _e = (expr);                                                               \
+        if (_e != hipSuccess)                                                                 \
+            return fail(VAPOR_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));      \
+    } while (0)
+
+extern "C" int vapor_wide_batch(vapor_ctx* ctx, vapor_seqset* set, int64_t n_pairs, const vapor_pair* pairs, int64_t* stats,
+                                int32_t* hits_ji, int64_t hits_capacity, int64_t* hit_off)
+{
+    if (!ctx || !set || n_pairs < 0 || (n_pairs && (!pairs || !stats)) || (hits_ji && !hit_off) || hits_capacity < 0)
+        return fail(VAPOR_E_ARG, "vapor_wide_batch: null argument");
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    WideBufs b;
+    b.c = ctx;
+    WIDE_CHK(b.ensure(WideBufs::ACC, sizeof(WideAcc)));
+    WIDE_CHK(b.ensure(WideBufs::BOOK, sizeof(unsigned long long)));
+    const WideAcc init = wide_acc_init();
+    const unsigned long long cap = (unsigned long long)std::max<int64_t>(ctx->max_pair_cap, 0);
+    int64_t running = 0;
+    if (hit_off) hit_off[0] = 0;
+    for (int64_t t = 0; t < n_pairs; ++t) {
+        const vapor_pair& a = pairs[t];
+        int64_t* s = stats + 16 * t;
+        auto refuse = [&](int code) {
+            for (int q = 0; q < 16; ++q) s[q] = 0;
+            s[1] = s[2] = -1;
+            s[15] = code;
+        };
+        int64_t n = 0;
+        if (a.seq1 < 0 || a.seq1 >= set->n || a.seq2 < 0 || a.seq2 >= set->n || a.off2 < 0 || !k_supported(a.k)) {
+            refuse(VAPOR_E_ARG);
+        } else if (set->h[a.seq1].len > VAPOR_MAX_WIDE_SEQ_LEN || set->h[a.seq2].len > VAPOR_MAX_WIDE_SEQ_LEN) {
+            refuse(VAPOR_E_ARG);
+        } else if (set->h[a.seq1].len - a.k + 1 > 0 && set->h[a.seq1].n_invalid > 0) {
+            refuse(VAPOR_E_KEYERROR);
+        } else {
+            const SeqDesc& s1 = set->h[a.seq1];
+            const SeqDesc& s2 = set->h[a.seq2];
+            const int nk1 = s1.len - a.k + 1, nk2 = std::max(0, s2.len - a.off2) - a.k + 1;
+            WIDE_CHK(hipMemcpyAsync(b.p[WideBufs::ACC], &init, sizeof(WideAcc), hipMemcpyHostToDevice, st));
+            if (nk1 > 0 && nk2 > 0) {
+                const int64_t ne = 2 * (int64_t)nk1;
+                uint32_t H = 1;
+                while ((int64_t)H < 2 * ne) H <<= 1;
+                WIDE_CHK(b.ensure(WideBufs::KEYS, (size_t)ne * sizeof(uint32_t) * ((4 * a.k + 31) / 32)));
+                WIDE_CHK(b.ensure(WideBufs::HEAD, sizeof(int32_t) * (size_t)H));
+                WIDE_CHK(b.ensure(WideBufs::NEXT, sizeof(int32_t) * (size_t)ne));
+                WIDE_CHK(b.ensure(WideBufs::CNT, sizeof(uint32_t) * (size_t)nk2));
+                WIDE_CHK(b.ensure(WideBufs::OFF, sizeof(long long) * ((size_t)nk2 + 1)));
+                WIDE_CHK(hipMemsetAsync(b.p[WideBufs::HEAD], 0xFF, sizeof(int32_t) * (size_t)H, st));
+                WIDE_CHK(hipMemsetAsync(b.p[WideBufs::BOOK], 0, sizeof(unsigned long long), st));
+                const uint32_t* x4_1 = set->d_x4 + (size_t)s1.chunk0 * 4;
+                const uint32_t* x4_2 = set->d_x4 + (size_t)s2.chunk0 * 4;
+                wide_join(a.k, b, st, x4_1, nk1, x4_2, a.off2, nk2, H - 1, false, cap);
+                WIDE_CHK(hipGetLastError());
+                long long total = 0;
+                WIDE_CHK(hipMemcpyAsync(&total, b.at<long long>(WideBufs::OFF) + nk2, sizeof(long long), hipMemcpyDeviceToHost, st));
+                WIDE_CHK(hipStreamSynchronize(st));
+                if (total > ctx->max_pair_cap) {
+                    // more dots than a pair may hold ("max_pair_cap"): the pair keeps VAPOR_E_OVERFLOW with the dots counted
+                    // before the count pass stopped (more than max_pair_cap, not necessarily all of them)
+                    refuse(VAPOR_E_OVERFLOW);
+                    s[0] = total;
+                    s[14] = total;
+                    if (hit_off) hit_off[t + 1] = running;
+                    continue;
+                }
+                n = total;
+                WIDE_CHK(b.ensure(WideBufs::DOTS, sizeof(int2) * (size_t)n));
+                WIDE_CHK(b.ensure(WideBufs::FL, (size_t)n));
+                if (n) {
+                    wide_join(a.k, b, st, x4_1, nk1, x4_2, a.off2, nk2, H - 1, true, cap);
+                    WIDE_CHK(hipGetLastError());
+                    WIDE_CHK(wide_clean(b, st, (int)n, nk1 - 1, nk2 - 1, a.flags));
+                }
+            }
+            WideAcc res;
+            WIDE_CHK(hipMemcpyAsync(&res, b.p[WideBufs::ACC], sizeof(WideAcc), hipMemcpyDeviceToHost, st));
+            if (hits_ji && n && running + n <= hits_capacity)
+                WIDE_CHK(hipMemcpyAsync(hits_ji + 2 * running, b.p[WideBufs::DOTS], sizeof(int2) * (size_t)n, hipMemcpyDeviceToHost, st));
+            WIDE_CHK(hipStreamSynchronize(st));
+            wide_stats(res, n, a.flags, s);
+        }
+        running += n;
+        if (hit_off) hit_off[t + 1] = running;
+    }
+    if (hits_ji && running > hits_capacity)
+        return fail(VAPOR_E_OVERFLOW, "vapor_wide_batch: hits_capacity too small (hit_off[n_pairs] holds the count needed)");
+    return VAPOR_OK;
+}
+
+extern "C" int vapor_clean_hits_wide(vapor_ctx* ctx, int64_t n_lists, const int32_t* hits_ji, const int64_t* off,
+                                     const uint32_t* flags, int64_t* stats, uint8_t* hit_flags)
+{
+    if (!ctx || n_lists < 0 || (n_lists && (!off || !stats))) return fail(VAPOR_E_ARG, "vapor_clean_hits_wide: null argument");
+    if (n_lists == 0) return VAPOR_OK;
+    const int64_t tot = off[n_lists];
+    if (tot && !hits_ji) return fail(VAPOR_E_ARG, "vapor_clean_hits_wide: null hit list");
+    for (int64_t t = 0; t < n_lists; ++t) {
+        if (off[t + 1] < off[t] || off[t + 1] - off[t] > ctx->max_pair_cap)
+            return fail(VAPOR_E_ARG, "vapor_clean_hits_wide: bad list offsets");
+        for (int64_t h = off[t]; h < off[t + 1]; ++h) {
+            const int j = hits_ji[2 * h], i = hits_ji[2 * h + 1];
+            if (j < 0 || i < 0 || j > VAPOR_MAX_WIDE_SEQ_LEN || i > VAPOR_MAX_WIDE_SEQ_LEN)
+                return fail(VAPOR_E_ARG, "vapor_clean_hits_wide: coordinate out of range");
+        }
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    WideBufs b;
+    b.c = ctx;
+    WIDE_CHK(b.ensure(WideBufs::ACC, sizeof(WideAcc)));
+    const WideAcc init = wide_acc_init();
+    for (int64_t t = 0; t < n_lists; ++t) {
+        const int64_t n = off[t + 1] - off[t];
+        const uint32_t f = flags ? flags[t] : 3u;
+        int mi = 0, mj = 0;
+        for (int64_t h = off[t]; h < off[t + 1]; ++h) { mj = std::max(mj, hits_ji[2 * h]); mi = std::max(mi, hits_ji[2 * h + 1]); }
+        WIDE_CHK(hipMemcpyAsync(b.p[WideBufs::ACC], &init, sizeof(WideAcc), hipMemcpyHostToDevice, st));
+        if (n) {
+            WIDE_CHK(b.ensure(WideBufs::DOTS, sizeof(int2) * (size_t)n));
+            WIDE_CHK(b.ensure(WideBufs::FL, (size_t)n));
+            WIDE_CHK(hipMemcpyAsync(b.p[WideBufs::DOTS], hits_ji + 2 * off[t], sizeof(int2) * (size_t)n, hipMemcpyHostToDevice, st));
+            WIDE_CHK(wide_clean(b, st, (int)n, mi, mj, f));
+        }
+        WideAcc res;
+        WIDE_CHK(hipMemcpyAsync(&res, b.p[WideBufs::ACC], sizeof(WideAcc), hipMemcpyDeviceToHost, st));
+        if (hit_flags && n) WIDE_CHK(hipMemcpyAsync(hit_flags + off[t], b.p[WideBufs::FL], (size_t)n, hipMemcpyDeviceToHost, st));
+        WIDE_CHK(hipStreamSynchronize(st));
+        wide_stats(res, n, f, stats + 16 * t);
+    }
+    return VAPOR_OK;
 }
 
 // ------------------------------------------------------------------------------------------

@@ -423,6 +423,68 @@ class Engine:
                                           L.ptr(st, ctypes.c_int64), L.ptr(hf, ctypes.c_uint8)))
         return st[:n], [hf[off[t]:off[t + 1]] for t in range(n)]
 
+    # ---- the wide route: sequences longer than MAX_SEQ_LEN (up to MAX_WIDE_SEQ_LEN) ----
+    @staticmethod
+    def _wide_entry(name: str):
+        lib = L.load()
+        # (the CPU twin of the C ABI exports the names with a stub that refuses every call: it has no wide route either)
+        flags = lib.vapor_build_flags() if hasattr(lib, "vapor_build_flags") else b""
+        if not hasattr(lib, name) or "cpu-twin" in (flags or b"").decode().split(","):
+            raise NotImplementedError("%s: the loaded library has no wide route" % name)
+        return getattr(lib, name)
+
+    def wide_available(self) -> bool:
+        """Whether the loaded library has the wide route (the CPU twin of the C ABI has not)."""
+        try:
+            self._wide_entry("vapor_wide_batch")
+            self._wide_entry("vapor_clean_hits_wide")
+        except NotImplementedError:
+            return False
+        return True
+
+    def score_wide(self, seqset: SeqSet, pairs: np.ndarray, want_hits: bool = False):
+        """Statistics (n,16) of every pair on the wide route (vapor_wide_batch); with want_hits also, per pair, the (n,2) [j,i]
+        hit array sorted the way dotdata() lists it."""
+        fn = self._wide_entry("vapor_wide_batch")
+        pairs = np.ascontiguousarray(pairs, dtype=L.PAIR_DTYPE)
+        n = len(pairs)
+        st = np.zeros((max(n, 1), 16), dtype=np.int64)
+        off = np.zeros(n + 1, dtype=np.int64)
+        pp = pairs.ctypes.data if n else None
+        if not want_hits:
+            L.check(fn(self._ctx, seqset._h, n, pp, L.ptr(st, ctypes.c_int64), None, 0, L.ptr(off, ctypes.c_int64)))
+            return st[:n]
+        cap = 1 << 16
+        while True:
+            hits = np.zeros((cap, 2), dtype=np.int32)
+            rc = fn(self._ctx, seqset._h, n, pp, L.ptr(st, ctypes.c_int64), L.ptr(hits, ctypes.c_int32), cap,
+                    L.ptr(off, ctypes.c_int64))
+            if rc == L.E_OVERFLOW and int(off[n]) > cap:
+                cap = int(off[n])
+                continue
+            L.check(rc)
+            break
+        out = []
+        for t in range(n):
+            h = hits[off[t]:off[t + 1]]
+            out.append(h[np.lexsort((h[:, 1], h[:, 0]))])
+        return st[:n], out
+
+    def clean_hits_wide(self, lists: Sequence[np.ndarray], flags: Optional[Sequence[int]] = None):
+        """clean_hits for lists with coordinates up to MAX_WIDE_SEQ_LEN (vapor_clean_hits_wide)."""
+        fn = self._wide_entry("vapor_clean_hits_wide")
+        n = len(lists)
+        arrs = [np.ascontiguousarray(a, dtype=np.int32).reshape(-1, 2) for a in lists]
+        off = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum([len(a) for a in arrs], out=off[1:])
+        allh = np.concatenate(arrs + [np.zeros((1, 2), np.int32)])
+        fl = np.asarray(flags if flags is not None else [3] * n, dtype=np.uint32)
+        st = np.zeros((max(n, 1), 16), dtype=np.int64)
+        hf = np.zeros(max(int(off[-1]), 1), dtype=np.uint8)
+        L.check(fn(self._ctx, n, L.ptr(allh, ctypes.c_int32), L.ptr(off, ctypes.c_int64),
+                   L.ptr(fl if n else np.zeros(1, np.uint32), ctypes.c_uint32), L.ptr(st, ctypes.c_int64), L.ptr(hf, ctypes.c_uint8)))
+        return st[:n], [hf[off[t]:off[t + 1]] for t in range(n)]
+
     def close(self) -> None:
         if self._ctx:
             live = list(self._live)

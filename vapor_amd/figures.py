@@ -11,6 +11,8 @@ from typing import List, Optional
 
 import numpy as np
 
+from . import _lib as L
+
 TITLES = ('ref vs. ref', 'alt vs. alt', 'read vs. ref', 'read vs. alt')
 POSITIONS = (221, 222, 223, 224)
 
@@ -68,7 +70,25 @@ def figure_specs(reqs, engine=None) -> List[Optional[dict]]:
         rows += [(b, b, 0, k, 0), (b + 1, b + 1, 0, k, 0), (b + 2, b, miss, k, 0), (b + 2, b + 1, miss, k, 0)]
     ss = eng.seqset(seqs)
     try:
-        st, hits = eng.dotplots(ss, eng.make_pairs(rows))
+        pr = eng.make_pairs(rows)
+        # the dot plots of sequences longer than the plan's limit come from the wide route
+        lens = np.asarray([len(x) for x in seqs], dtype=np.int64)
+        longp = np.flatnonzero(np.maximum(lens[pr["seq1"]], lens[pr["seq2"]]) > L.MAX_SEQ_LEN) if pipeline.has_wide(eng) else []
+        if len(longp):
+            shortp = np.setdiff1d(np.arange(len(pr)), longp)
+            st = np.zeros((len(pr), L.STATS_STRIDE), dtype=np.int64)
+            hits = [None] * len(pr)
+            if len(shortp):
+                st_s, h_s = eng.dotplots(ss, pr[shortp])
+                st[shortp] = st_s
+                for q, h in zip(shortp, h_s):
+                    hits[q] = h
+            st_w, h_w = eng.score_wide(ss, pr[longp], want_hits=True)
+            st[longp] = st_w
+            for q, h in zip(longp, h_w):
+                hits[q] = h
+        else:
+            st, hits = eng.dotplots(ss, pr)
     finally:
         ss.close()
     for n, t in enumerate(todo):

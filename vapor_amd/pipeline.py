@@ -149,7 +149,16 @@ def refine_windows(engine, seqs: Sequence[str], region_QC_Cff: float = 0.4) -> L
         pairs["k"] = k
         ss = engine.seqset(useqs)
         plan = engine.plan(ss, pairs)
-        st = plan.run()[which]
+        st_all = plan.run()
+        # self plots of sequences longer than the plan's limit (the plan refuses them): the wide route, dots included
+        wide_hits: Dict[int, np.ndarray] = {}
+        longq = [q for q, s2 in enumerate(useqs) if len(s2) > L.MAX_SEQ_LEN] if has_wide(engine) else []
+        if longq:
+            st_w, h_w = engine.score_wide(ss, pairs[longq], want_hits=True)
+            st_all = st_all.copy()
+            st_all[longq] = st_w
+            wide_hits = dict(zip(longq, h_w))
+        st = st_all[which]
         code = st[:, L.ST_STATUS]
         nh, nd, nl = st[:, L.ST_N_HITS], st[:, L.ST_N_DIAG], st[:, L.ST_N_LOWER]
         with np.errstate(divide="ignore", invalid="ignore"):
@@ -157,7 +166,11 @@ def refine_windows(engine, seqs: Sequence[str], region_QC_Cff: float = 0.4) -> L
             diag = nd.astype(np.float64) / nh.astype(np.float64)
         band = (code == 0) & (nh > 0) & (frac > 0.1) & (frac < 0.5)
         pts = {}
-        need = np.flatnonzero(band)
+        need = np.asarray([w for w in np.flatnonzero(band) if int(which[w]) not in wide_hits], dtype=np.int64)
+        for w in np.flatnonzero(band):
+            if int(which[w]) in wide_hits:
+                h = wide_hits[int(which[w])]
+                pts[int(w)] = h[h[:, 0] > h[:, 1]]
         if len(need):
             hits, _f, off = plan.fetch_hits(which[need].tolist(), want_flags=False)
             for q, w in enumerate(need):
@@ -227,7 +240,95 @@ _FLAGS = {"s1": L.PF_C1, "s2": L.PF_C2, "s3": L.PF_C1 | L.PF_DIR}
 _KIND = {"del": 0, "s1": 1, "s2": 2, "s3": 3}
 
 
+def has_wide(engine) -> bool:
+    """Whether `engine` has the wide route (sequences longer than MAX_SEQ_LEN, up to MAX_WIDE_SEQ_LEN): a score_wide method, and
+    - for an engine that can say so (Engine.wide_available) - a library that has the route."""
+    if not callable(getattr(engine, "score_wide", None)):
+        return False
+    avail = getattr(engine, "wide_available", None)
+    return bool(avail()) if callable(avail) else True
+
+
 def score_requests(engine, reqs: Sequence[Score]) -> List[object]:
+    """Evaluates every Score request (_score_requests_narrow); the requests that route refuses for a window, allele or read
+    longer than MAX_SEQ_LEN are scored again on the wide route (score_requests_wide) when the engine has one, in place."""
+    out = _score_requests_narrow(engine, reqs)
+    if has_wide(engine):
+        redo = [t for t, v in enumerate(out) if isinstance(v, ValueError) and not k_unsupported(reqs[t].k)]
+        if redo:
+            for t, v in zip(redo, score_requests_wide(engine, [reqs[t] for t in redo])):
+                out[t] = v
+    return out
+
+
+def score_requests_wide(engine, reqs: Sequence[Score]) -> List[object]:
+    """score_requests on the wide route: the pairs' statistics from engine.score_wide, the per-read scores and the deletion
+    rule (SF:1718-1726) on the host in float64 (vapor_amd.finish), as the device's finish kernel computes them."""
+    from . import finish
+    seqs: List[str] = []
+    upper: List[bool] = []
+    rows = []                         # (seq1, seq2, off2, k, flags)
+    per_req = []                      # per request: [(kind, ref pair, alt pair)], one entry per scorer, per read
+    for r in reqs:
+        base = len(seqs)
+        seqs += [str(r.ref_seq), str(r.alt_seq)]
+        upper += [False, False]
+        iu = (base, base + 1)
+        if r.kind in ("del", "s1") and not (_is_upper(r.ref_seq) and _is_upper(r.alt_seq)):
+            seqs += [str(r.ref_seq), str(r.alt_seq)]
+            upper += [True, True]
+            iu = (base + 2, base + 3)
+        reads = []
+        for x in r.reads:
+            q = len(seqs)
+            seqs.append(str(x[0]))
+            upper.append(False)
+            miss = int(x[1])
+            sc = []
+            plan_of = {"s1": [(1, iu, L.PF_C1)], "s2": [(2, (base, base + 1), L.PF_C2)],
+                       "s3": [(3, (base, base + 1), L.PF_C1 | L.PF_DIR)],
+                       "del": [(1, iu, L.PF_C1), (2, (base, base + 1), L.PF_C2)]}[r.kind]
+            for kind, (a_ref, a_alt), fl in plan_of:
+                sc.append((kind, len(rows), len(rows) + 1))
+                rows += [(q, a_ref, miss, int(r.k), fl), (q, a_alt, miss, int(r.k), fl)]
+            reads.append(sc)
+        per_req.append(reads)
+    ss = engine.seqset(seqs, upper)
+    try:
+        st = engine.score_wide(ss, engine.make_pairs(rows))
+    finally:
+        ss.close()
+    out: List[object] = []
+    for r, reads in zip(reqs, per_req):
+        idx = [p for sc in reads for (_k, a, b) in sc for p in (a, b)]
+        codes = st[idx, L.ST_STATUS] if idx else np.zeros(0, dtype=np.int64)
+        if (codes == L.E_ARG).any():
+            out.append(ValueError("sequence longer than %d bases or unsupported window size" % L.MAX_WIDE_SEQ_LEN))
+            continue
+        if (codes == L.E_KEYERROR).any():
+            out.append(KeyError("invert_base"))              # what SF:1421 raises on a base outside ATCGN/atcgn
+            continue
+        if (codes != 0).any():
+            out.append(RuntimeError("libvapor_hip pair status %d" % int(codes[codes != 0][0])))
+            continue
+        lr, la = len(r.ref_seq), len(r.alt_seq)
+        vals: List[object] = []
+        for sc in reads:
+            ss_ = []
+            for kind, a, b in sc:
+                av, bv, valid = finish.batch_scores(np.asarray([kind]), st[[a]], st[[b]], np.asarray([lr]), np.asarray([la]))
+                ss_.append(float(finish.read_scores(av, bv)[0]) if bool(valid[0]) else None)
+            if len(ss_) == 2:                                 # a deletion read: the smaller of the two scores wins
+                s1, s2 = ss_
+                v = (s2 if s2 < s1 else s1) if (s1 is not None and s2 is not None) else (s1 if s1 is not None else s2)
+            else:
+                v = ss_[0]
+            vals.append(v)
+        out.append(vals)
+    return out
+
+
+def _score_requests_narrow(engine, reqs: Sequence[Score]) -> List[object]:
     """Evaluates every Score request on the device, per-read reduction included (finish_kernel): per request a list
     with one score (float) or None per read, or the exception the reference would raise (KeyError for a read with a
     base outside invert_base's alphabet, SF:1421).
@@ -403,8 +504,10 @@ def scorer_outputs(engine, kind: str, ref_seq: str, alt_seq: str, x, k):
     from . import finish
     up = kind == "s1"
     ss = engine.seqset([x[0], ref_seq, alt_seq], [False, up, up])
+    wide = has_wide(engine) and max(len(x[0]), len(ref_seq), len(alt_seq)) > L.MAX_SEQ_LEN
     try:
-        st = engine.score(ss, engine.make_pairs([(0, 1, int(x[1]), int(k), _FLAGS[kind]), (0, 2, int(x[1]), int(k), _FLAGS[kind])]))
+        pr = engine.make_pairs([(0, 1, int(x[1]), int(k), _FLAGS[kind]), (0, 2, int(x[1]), int(k), _FLAGS[kind])])
+        st = engine.score_wide(ss, pr) if wide else engine.score(ss, pr)
     finally:
         ss.close()
     _raise_for_status(st[0])

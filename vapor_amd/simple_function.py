@@ -39,8 +39,10 @@ def dotdata(kmerlen, seq1, seq2):
     """SF:545-549: [(pos_in_seq2, pos_in_seq1), ...] in the reference's order."""
     eng = pipeline.get_engine()
     ss = eng.seqset([seq1, seq2])
+    wide = pipeline.has_wide(eng) and max(len(seq1), len(seq2)) > L.MAX_SEQ_LEN
     try:
-        st, hits = eng.dotplots(ss, eng.make_pairs([(0, 1, 0, int(kmerlen), 0)]))
+        pr = eng.make_pairs([(0, 1, 0, int(kmerlen), 0)])
+        st, hits = eng.score_wide(ss, pr, want_hits=True) if wide else eng.dotplots(ss, pr)
     finally:
         ss.close()
     pipeline._raise_for_status(st[0])
@@ -69,7 +71,11 @@ def clean_dotdata_diagnal_and_anti_diagnal(ref_dotdata):
     if ref_dotdata == []:
         return [[], []]
     arr = np.asarray(ref_dotdata, dtype=np.int32).reshape(-1, 2)
-    _st, fl = pipeline.get_engine().clean_hits([arr], flags=[L.PF_C1])
+    eng = pipeline.get_engine()
+    if pipeline.has_wide(eng) and int(arr.max()) > L.MAX_SEQ_LEN:
+        _st, fl = eng.clean_hits_wide([arr], flags=[L.PF_C1])
+    else:
+        _st, fl = eng.clean_hits([arr], flags=[L.PF_C1])
     return [ref_dotdata[t] for t in range(len(ref_dotdata)) if fl[0][t] & L.HF_C1_KEPT]
 
 
