@@ -343,6 +343,28 @@ int vapor_bam_last_stats(vapor_ctx* ctx, double* out, int32_t n);
 /* the descriptor and the inflate-thread count of an open file (vapor_bam_chop_device reads with them) */
 int vapor_bam_fileno(vapor_bam* bam);
 int vapor_bam_threads(vapor_bam* bam);
+
+/* Reference windows of a bgzipped FASTA on the device (the BGZF twin of `samtools faidx`, for a chunk of loci at once).  `fd` is
+ * an open descriptor of the .fa.gz.  Window i is the raw FASTA text (newlines included) between the virtual offsets vbeg[i] and
+ * vend[i] (compressed block offset << 16 | offset in the block's data), which the caller finds with the .fai and .gzi.  Every
+ * distinct block is inflated once, however many windows hold it, and checked by its CRC-32.  The text of window i, without its
+ * '\n' and '\r', is text[text_off[i] .. text_off[i + 1]) (text_off has n + 1 entries; text_cap bytes of room, the raw sizes'
+ * sum always suffices); traits[i] = VAPOR_FASTA_TR_* bits of that text.  status[i] = 0, or a positive VAPOR_FASTA_* code where
+ * the window is left to the host reader (its text is then empty): a damaged or non-BGZF block, offsets outside the blocks of
+ * the file, a byte of 0x80 or more, no room (more than the call's block or text limits).  One host thread per context. */
+#define VAPOR_FASTA_BLOCK 1
+#define VAPOR_FASTA_RANGE 2
+#define VAPOR_FASTA_NON_ASCII 3
+#define VAPOR_FASTA_ROOM 4
+#define VAPOR_FASTA_TR_LOWER 1            /* a byte in a-z */
+#define VAPOR_FASTA_TR_NOT_ACGTN 2        /* a byte other than A C G T N */
+#define VAPOR_FASTA_TR_NOT_ACGTN_ANY_CASE 4   /* a byte other than A C G T N a c g t n */
+#define VAPOR_FASTA_TR_HIGH 8             /* a byte of 0x80 or more */
+int vapor_fasta_windows_device(vapor_ctx* ctx, int fd, int32_t n, const uint64_t* vbeg, const uint64_t* vend, uint8_t* text,
+                               int64_t text_cap, int64_t* text_off, uint8_t* traits, int32_t* status);
+/* what the context's last vapor_fasta_windows_device did: out[0..5] = windows, distinct blocks inflated, compressed bytes read
+ * and sent, inflated bytes, both kernels between two events on their stream (ms), the whole call (ms) */
+int vapor_fasta_last_stats(vapor_ctx* ctx, double* out, int32_t n);
 /*
  * vapor_seqset_create_derived for a set some of whose sequences are on the device already: src_kind[i] = 1 says seq[i] is the
  * DEVICE address of BAM-packed bases (4 bits a base, "=ACMGRSVTWYHKDBN", the first base of a byte in its high half) inside the

@@ -35,6 +35,8 @@ SEQ_UPPER = 1
 E_HIP, E_OVERFLOW, E_KEYERROR, E_ARG, E_NOMEM = -1, -2, -3, -4, -5
 MAX_SEQ_LEN = 65535
 MAX_WIDE_SEQ_LEN = 1048575     # the wide route: vapor_wide_batch / vapor_clean_hits_wide
+FASTA_BLOCK, FASTA_RANGE, FASTA_NON_ASCII, FASTA_ROOM = 1, 2, 3, 4                    # vapor_fasta_windows_device: status of a window
+FASTA_TR_LOWER, FASTA_TR_NOT_ACGTN, FASTA_TR_NOT_ACGTN_ANY_CASE, FASTA_TR_HIGH = 1, 2, 4, 8    # ... and its traits
 ABI_VERSION = 3
 ABI_DEV_OFFSET = 1000000
 
@@ -48,7 +50,7 @@ EXPORTS = [
     "vapor_bam_open", "vapor_bam_close", "vapor_bam_set_threads", "vapor_bam_last_error", "vapor_bam_chop",
     "vapor_inflate_raw", "vapor_chop_records", "vapor_chop_records_many", "vapor_row_tails", "vapor_crc32",
     "vapor_bam_chop_device", "vapor_bam_batch_destroy", "vapor_bam_fileno", "vapor_bam_threads", "vapor_seqset_create_mixed", "vapor_bam_last_stats",
-    "vapor_wide_batch", "vapor_clean_hits_wide",
+    "vapor_wide_batch", "vapor_clean_hits_wide", "vapor_fasta_windows_device", "vapor_fasta_last_stats",
 ]
 # entry points a library may lack (the CPU twin of the C ABI has no wide route): bound when present, and the engine's wide
 # methods raise NotImplementedError when they are not
@@ -197,6 +199,8 @@ def bind(L: ctypes.CDLL) -> ctypes.CDLL:
     L.vapor_clean_hits.argtypes = [vp, ctypes.c_int64, i32p, i64p, u32p, i64p, u8p]
     L.vapor_plan_set_reads.argtypes = [vp, ctypes.c_int64, vp, ctypes.c_int64, f64p]
     L.vapor_plan_run_loci.argtypes = [vp, vp, f64p, f64p]
+    L.vapor_fasta_windows_device.argtypes = [vp, ctypes.c_int, ctypes.c_int32, vp, vp, vp, ctypes.c_int64, vp, vp, vp]
+    L.vapor_fasta_last_stats.argtypes = [vp, vp, ctypes.c_int32]
     if hasattr(L, "vapor_wide_batch"):
         L.vapor_wide_batch.argtypes = [vp, vp, ctypes.c_int64, vp, i64p, i32p, ctypes.c_int64, i64p]
     if hasattr(L, "vapor_clean_hits_wide"):

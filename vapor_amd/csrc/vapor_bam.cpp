@@ -673,3 +673,16 @@ extern "C" __attribute__((weak)) int vapor_clean_hits_wide(vapor_ctx*, int64_t, 
 {
     return bfail(VAPOR_E_ARG, "vapor_clean_hits_wide: this build has no wide route");
 }
+
+// The reference windows of a bgzipped FASTA on the device (vapor_fasta_windows_device, vapor_fasta_last_stats) are device code in
+// vapor_hip.hip as well; the CPU twin answers them with VAPOR_E_ARG, and the caller reads the windows on the host.
+extern "C" __attribute__((weak)) int vapor_fasta_windows_device(vapor_ctx*, int, int32_t, const uint64_t*, const uint64_t*, uint8_t*, int64_t,
+                                                                int64_t*, uint8_t*, int32_t*)
+{
+    return bfail(VAPOR_E_ARG, "vapor_fasta_windows_device: this build has no device FASTA reader");
+}
+
+extern "C" __attribute__((weak)) int vapor_fasta_last_stats(vapor_ctx*, double*, int32_t)
+{
+    return bfail(VAPOR_E_ARG, "vapor_fasta_last_stats: this build has no device FASTA reader");
+}

@@ -8,6 +8,7 @@
 #include "vapor_kernels.h"
 #include "vapor_wide.h"
 #include "vapor_bamdev.h"
+#include "vapor_fasta.h"
 #include "vapor_hip.h"
 
 #include <unistd.h>
@@ -119,6 +120,8 @@ struct vapor_ctx {
     int bam_cu_share = 0;
     hipEvent_t bam_ev[2] = {nullptr, nullptr}; // around the inflate launch of the last vapor_bam_chop_device (vapor_bam_last_stats)
     double bam_stats[6] = {0, 0, 0, 0, 0, 0};  // regions, blocks, compressed bytes, inflated bytes, inflate ms, whole call ms
+    hipEvent_t fasta_ev[2] = {nullptr, nullptr};   // around the kernels of the last vapor_fasta_windows_device (vapor_fasta_last_stats)
+    double fasta_stats[6] = {0, 0, 0, 0, 0, 0};    // windows, distinct blocks, compressed bytes, inflated bytes, kernels ms, whole call ms
     BlockPool pool;
 };
 
@@ -363,6 +366,8 @@ extern "C" int vapor_destroy(vapor_ctx* c)
     if (c->d_crc_pow) (void)hipFree(c->d_crc_pow);
     if (c->bam_stream) (void)hipStreamDestroy(c->bam_stream);
     for (hipEvent_t e : c->bam_ev)
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->fasta_ev)
         if (e) (void)hipEventDestroy(e);
     delete c;
     return VAPOR_OK;
@@ -939,6 +944,32 @@ void scan_span(HostSpan& sp, const uint8_t* stage)
 }
 }   // namespace
 
+// the CRC combination constants bgzf_inflate_kernel multiplies its lanes' slice CRCs by, on the device once per context
+static hipError_t crc_pow_on_device(vapor_ctx* ctx)
+{
+    if (ctx->d_crc_pow) return hipSuccess;
+    // x^(8 * 1024 * (63 - l)) mod P, l = 0 .. 63 (bit 31 = x^0): what lane l's slice CRC is multiplied by
+    uint32_t pw[64];
+    auto mul = [](uint32_t a, uint32_t b) {
+        uint32_t m = 1u << 31, p = 0;
+        for (int i = 0; i < 32; ++i) { if (a & m) p ^= b; m >>= 1; b = (b & 1u) ? (b >> 1) ^ 0xEDB88320u : b >> 1; }
+        return p;
+    };
+    for (int l = 0; l < 64; ++l) {
+        uint64_t e = (uint64_t)8 * 1024 * (uint64_t)(63 - l);
+        uint32_t r = 0x80000000u, b = 0x40000000u;
+        while (e) { if (e & 1) r = mul(r, b); b = mul(b, b); e >>= 1; }
+        pw[l] = r;
+    }
+    uint32_t* d = nullptr;
+    hipError_t e = hipMalloc((void**)&d, sizeof pw);
+    if (e != hipSuccess) return e;
+    e = hipMemcpy(d, pw, sizeof pw, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(d); return e; }
+    ctx->d_crc_pow = d;
+    return hipSuccess;
+}
+
 extern "C" int vapor_bam_chop_device(vapor_ctx* ctx, vapor_bam* bam, int32_t n_regions, const int32_t* tid, const int64_t* start,
                                      const int64_t* end, const int64_t* flank, const int32_t* chunk_first, const uint64_t* chunks,
                                      int32_t max_keep, int32_t* kept_first, uint64_t* sq_addr, int64_t* q0, int64_t* miss,
@@ -1106,23 +1137,7 @@ extern "C" int vapor_bam_chop_device(vapor_ctx* ctx, vapor_bam* bam, int32_t n_r
         if (n_blks) memcpy(h_meta + o_blk, blks.data(), sizeof(BgzfBlk) * n_blks);
         if (!dspans.empty()) memcpy(h_meta + o_span, dspans.data(), sizeof(BamSpan) * dspans.size());
         memcpy(h_meta + o_reg, regs.data(), sizeof(BamRegion) * regs.size());
-        if (!ctx->d_crc_pow) {
-            // x^(8 * 1024 * (63 - l)) mod P, l = 0 .. 63 (bit 31 = x^0): what lane l's slice CRC is multiplied by
-            uint32_t pw[64];
-            auto mul = [](uint32_t a, uint32_t b) {
-                uint32_t m = 1u << 31, p = 0;
-                for (int i = 0; i < 32; ++i) { if (a & m) p ^= b; m >>= 1; b = (b & 1u) ? (b >> 1) ^ 0xEDB88320u : b >> 1; }
-                return p;
-            };
-            for (int l = 0; l < 64; ++l) {
-                uint64_t e = (uint64_t)8 * 1024 * (uint64_t)(63 - l);
-                uint32_t r = 0x80000000u, b = 0x40000000u;
-                while (e) { if (e & 1) r = mul(r, b); b = mul(b, b); e >>= 1; }
-                pw[l] = r;
-            }
-            BD_CHK(hipMalloc((void**)&ctx->d_crc_pow, sizeof pw));
-            BD_CHK(hipMemcpy(ctx->d_crc_pow, pw, sizeof pw, hipMemcpyHostToDevice));
-        }
+        BD_CHK(crc_pow_on_device(ctx));
         {
             const char* sh = getenv("VAPOR_BAM_CU_SHARE");            // (experiments: overrides the parameter)
             const int share = ctx->user_stream ? 0 : (sh ? atoi(sh) : ctx->bam_cu_share);
@@ -1233,6 +1248,295 @@ extern "C" int vapor_bam_last_stats(vapor_ctx* ctx, double* out, int32_t n)
 {
     if (!ctx || !out || n < 0) return fail(VAPOR_E_ARG, "vapor_bam_last_stats: null argument");
     for (int32_t i = 0; i < n && i < 6; ++i) out[i] = ctx->bam_stats[i];
+    return VAPOR_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// Reference windows from a bgzipped FASTA on the device (vapor_fasta.h).  The windows' virtual-offset ranges are sorted and the
+// ranges that share a block or touch are read as one stretch of the file, so that every distinct block is read, sent and
+// inflated once however many windows hold it.  Sizes and offsets are 64-bit throughout; a stretch whose data would pass the
+// arena's limit leaves its windows to the host (VAPOR_FASTA_ROOM).  Everything runs on the context's own stream and is
+// synchronised before the call's blocks go back to the pool (BlockPool: no block is handed back while a kernel may read it).
+// ------------------------------------------------------------------------------------------
+namespace {
+struct FaStretch {                 // compressed bytes [c0, c_end) of the file, read at once; holds the blocks of its windows
+    int64_t c0 = 0, c_last = 0;    // first block; the last needed block starts at c_last (need_last) or ends there
+    bool need_last = false;
+    size_t want = 0, got = 0, stage_off = 0;
+    std::vector<int64_t> coff;     // every block scanned, in file order, and behind them the offset after the last one
+    std::vector<uint64_t> u;       // ... their data's offset inside the stretch (64-bit), the sentinel's = the stretch's size
+    std::vector<uint32_t> isize;
+    std::vector<uint32_t> gidx;    // ... the number of non-empty blocks before them in the call's block table
+    bool cut = false;              // the scan stopped at a damaged or missing block: windows behind it are not found
+    bool room = true;
+    uint64_t arena_off = 0;
+};
+}  // namespace
+
+extern "C" int vapor_fasta_windows_device(vapor_ctx* ctx, int fd, int32_t n, const uint64_t* vbeg, const uint64_t* vend, uint8_t* text,
+                                          int64_t text_cap, int64_t* text_off, uint8_t* traits, int32_t* status)
+{
+    using namespace vapor_bamdev;
+    using namespace vapor_fasta;
+    if (!ctx || fd < 0 || n < 0 || text_cap < 0 || !text_off || (n && (!vbeg || !vend || !traits || !status)) || (text_cap && !text))
+        return fail(VAPOR_E_ARG, "vapor_fasta_windows_device: bad argument");
+    HIPCHK(hipSetDevice(ctx->device));
+    auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    const double t0 = now();
+    constexpr uint64_t ARENA_CAP = (uint64_t)1 << 30, STAGE_CAP = (uint64_t)1 << 29;
+    try {
+        // ---- windows in file order, merged into stretches --------------------------------------------------------------------
+        std::vector<int32_t> order;
+        order.reserve((size_t)n);
+        for (int32_t i = 0; i < n; ++i) {
+            status[i] = WIN_OK;
+            traits[i] = 0;
+            if (vend[i] < vbeg[i]) status[i] = WIN_RANGE;
+            else if (vend[i] > vbeg[i]) order.push_back(i);
+        }
+        std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return vbeg[a] != vbeg[b] ? vbeg[a] < vbeg[b] : a < b; });
+        std::vector<FaStretch> sts;
+        std::vector<int32_t> st_of((size_t)n, -1);
+        for (int32_t i : order) {
+            const int64_t c0 = (int64_t)(vbeg[i] >> 16), cl = (int64_t)(vend[i] >> 16);
+            const bool nl = (vend[i] & 0xFFFFu) != 0;
+            if (!sts.empty() && c0 <= sts.back().c_last) {          // (shares a block with the stretch, or starts where it ends)
+                FaStretch& s = sts.back();
+                if (cl > s.c_last || (cl == s.c_last && nl)) { s.c_last = cl; s.need_last = nl; }
+            } else {
+                FaStretch s;
+                s.c0 = c0; s.c_last = cl; s.need_last = nl;
+                sts.push_back(std::move(s));
+            }
+            st_of[(size_t)i] = (int32_t)sts.size() - 1;
+        }
+        // ---- read and scan the stretches --------------------------------------------------------------------------------------
+        uint64_t stage_bytes = 0;
+        for (FaStretch& s : sts) {
+            // (the last block in full: its BSIZE from its header, or the 64 KB a block can be at most when the header says nothing)
+            uint64_t last_size = 0;
+            if (s.need_last) {
+                uint8_t h[64];
+                const ssize_t r = pread(fd, h, sizeof h, (off_t)s.c_last);
+                int bsize = -1;
+                if (r >= 18 && h[0] == 0x1f && h[1] == 0x8b && h[2] == 8 && (h[3] & 4)) {
+                    const int xlen = std::min<int>(h[10] | (h[11] << 8), (int)r - 12);
+                    for (int q = 0; q + 6 <= xlen;) {
+                        const uint8_t* e = h + 12 + q;
+                        const int slen = e[2] | (e[3] << 8);
+                        if (e[0] == 66 && e[1] == 67 && slen == 2) bsize = (e[4] | (e[5] << 8)) + 1;
+                        q += 4 + slen;
+                    }
+                }
+                last_size = bsize > 0 ? (uint64_t)bsize : 65536u;
+            }
+            const uint64_t want = (uint64_t)(s.c_last - s.c0) + last_size;
+            if (stage_bytes + want > STAGE_CAP) { s.room = false; continue; }
+            s.want = (size_t)want;
+            s.stage_off = (size_t)stage_bytes;
+            stage_bytes += (want + 63) & ~(uint64_t)63;
+        }
+        struct Held {
+            vapor_ctx* ctx;
+            uint8_t *h_comp = nullptr, *d_comp = nullptr, *d_arena = nullptr, *h_meta = nullptr, *d_meta = nullptr, *h_text = nullptr, *d_text = nullptr;
+            explicit Held(vapor_ctx* c) : ctx(c) {}
+            ~Held()
+            {
+                (void)hipStreamSynchronize(ctx->stream);        // (nothing goes back to the pool while a copy or kernel may use it)
+                if (h_comp) hfree(ctx, h_comp);
+                if (h_meta) hfree(ctx, h_meta);
+                if (h_text) hfree(ctx, h_text);
+                if (d_comp) dfree(ctx, d_comp);
+                if (d_arena) dfree(ctx, d_arena);
+                if (d_meta) dfree(ctx, d_meta);
+                if (d_text) dfree(ctx, d_text);
+            }
+        } held(ctx);
+        HIPCHK(hmalloc(ctx, (void**)&held.h_comp, (size_t)std::max<uint64_t>(stage_bytes, 64)));
+        uint8_t* const h_comp = held.h_comp;
+        uint64_t read_bytes = 0;
+        for (FaStretch& s : sts) {
+            if (!s.room) continue;
+            size_t got = 0;
+            while (got < s.want) {
+                const ssize_t r = pread(fd, h_comp + s.stage_off + got, s.want - got, (off_t)(s.c0 + (int64_t)got));
+                if (r <= 0) break;
+                got += (size_t)r;
+            }
+            s.got = got;
+            read_bytes += got;
+            const uint8_t* base = h_comp + s.stage_off;
+            size_t p = 0;
+            uint64_t u = 0;
+            for (;;) {
+                const int64_t coff = s.c0 + (int64_t)p;
+                if (coff > s.c_last || (coff == s.c_last && !s.need_last)) break;
+                if (p + 18 > got) { s.cut = true; break; }
+                const uint8_t* h = base + p;
+                if (h[0] != 0x1f || h[1] != 0x8b || h[2] != 8 || !(h[3] & 4)) { s.cut = true; break; }
+                const int xlen = h[10] | (h[11] << 8);
+                if (p + 12 + (size_t)xlen > got) { s.cut = true; break; }
+                int bsize = -1;
+                for (int q = 0; q + 4 <= xlen;) {
+                    const uint8_t* e = h + 12 + q;
+                    const int slen = e[2] | (e[3] << 8);
+                    if (e[0] == 66 && e[1] == 67 && slen == 2 && q + 6 <= xlen) bsize = (e[4] | (e[5] << 8)) + 1;
+                    q += 4 + slen;
+                }
+                if (bsize < 0 || bsize < xlen + 20 || p + (size_t)bsize > got) { s.cut = true; break; }
+                const uint8_t* t = h + bsize - 8;
+                const uint32_t crc = (uint32_t)t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
+                const uint32_t isz = (uint32_t)t[4] | ((uint32_t)t[5] << 8) | ((uint32_t)t[6] << 16) | ((uint32_t)t[7] << 24);
+                if (isz > 65536u || (isz == 0 && crc != 0)) { s.cut = true; break; }
+                s.coff.push_back(coff);
+                s.u.push_back(u);
+                s.isize.push_back(isz);
+                s.gidx.push_back(0);
+                u += isz;
+                p += (size_t)bsize;
+            }
+            s.coff.push_back(s.c0 + (int64_t)p);
+            s.u.push_back(u);
+            s.isize.push_back(0);
+            s.gidx.push_back(0);
+        }
+        // ---- layout: the arena (64-bit offsets, a limit), the block table ------------------------------------------------------
+        std::vector<BgzfBlk> blks;
+        uint64_t arena = 0;
+        for (FaStretch& s : sts) {
+            if (!s.room) continue;
+            const uint64_t size = s.u.back();
+            if (arena + size + 64 > ARENA_CAP) { s.room = false; continue; }
+            s.arena_off = arena;
+            for (size_t k = 0; k + 1 < s.coff.size(); ++k) {
+                s.gidx[k] = (uint32_t)blks.size();
+                if (!s.isize[k]) continue;
+                const size_t p = (size_t)(s.coff[k] - s.c0);
+                const uint8_t* h = h_comp + s.stage_off + p;
+                const int xlen = h[10] | (h[11] << 8);
+                int bsize = 0;
+                for (int q = 0; q + 4 <= xlen;) {
+                    const uint8_t* e = h + 12 + q;
+                    const int slen = e[2] | (e[3] << 8);
+                    if (e[0] == 66 && e[1] == 67 && slen == 2 && q + 6 <= xlen) bsize = (e[4] | (e[5] << 8)) + 1;
+                    q += 4 + slen;
+                }
+                BgzfBlk b;
+                b.c_off = (uint32_t)(s.stage_off + p + 12 + (size_t)xlen);
+                b.c_len = (uint32_t)(bsize - xlen - 20);
+                b.u_off = (uint32_t)(arena + s.u[k]);
+                b.u_len = s.isize[k];
+                const uint8_t* t = h + bsize - 8;
+                b.crc = (uint32_t)t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
+                b.pad = 0;
+                blks.push_back(b);
+            }
+            s.gidx.back() = (uint32_t)blks.size();
+            arena += (size + 63) & ~(uint64_t)63;
+        }
+        // ---- the windows: their bytes in the arena, their slots in the text buffer --------------------------------------------
+        std::vector<FastaWin> wins((size_t)std::max(n, 1));
+        uint64_t slots = 0;
+        auto find = [](const FaStretch& s, int64_t coff) -> int64_t {
+            auto it = std::lower_bound(s.coff.begin(), s.coff.end(), coff);
+            return it != s.coff.end() && *it == coff ? (int64_t)(it - s.coff.begin()) : -1;
+        };
+        for (int32_t i = 0; i < n; ++i) {
+            FastaWin& W = wins[(size_t)i];
+            W = FastaWin{0, 0, 0, 0, 0};
+            const int32_t si = st_of[(size_t)i];
+            if (status[i] || si < 0) continue;
+            const FaStretch& s = sts[(size_t)si];
+            if (!s.room) { status[i] = WIN_ROOM; continue; }
+            const int64_t kb = find(s, (int64_t)(vbeg[i] >> 16)), ke = find(s, (int64_t)(vend[i] >> 16));
+            const uint32_t ub = (uint32_t)(vbeg[i] & 0xFFFFu), ue = (uint32_t)(vend[i] & 0xFFFFu);
+            const bool last_is_sentinel = ke == (int64_t)s.coff.size() - 1;
+            if (kb < 0 || ke < 0 || kb == (int64_t)s.coff.size() - 1 || ub > s.isize[(size_t)kb] || ue > s.isize[(size_t)ke] || (last_is_sentinel && ue)) {
+                status[i] = s.cut ? WIN_BLOCK : WIN_RANGE;
+                continue;
+            }
+            W.a_beg = s.arena_off + s.u[(size_t)kb] + ub;
+            W.a_end = s.arena_off + s.u[(size_t)ke] + ue;
+            if (W.a_end < W.a_beg) { status[i] = WIN_RANGE; W.a_end = W.a_beg; continue; }
+            const uint64_t len = W.a_end - W.a_beg;
+            if (slots + len > (uint64_t)text_cap) { status[i] = WIN_ROOM; W.a_end = W.a_beg; continue; }
+            W.t_off = slots;
+            slots += len;
+            W.blk_first = s.gidx[(size_t)kb];
+            W.blk_n = s.gidx[(size_t)ke] + (ue ? 1u : 0u) - W.blk_first;
+        }
+        // ---- the device: copies, two kernels, the answers back -----------------------------------------------------------------
+        const size_t n_blks = blks.size(), nw = (size_t)std::max(n, 1);
+        const size_t o_blk = 0, o_win = o_blk + ((sizeof(BgzfBlk) * std::max<size_t>(n_blks, 1) + 63) & ~(size_t)63);
+        const size_t o_st = o_win + ((sizeof(FastaWin) * nw + 63) & ~(size_t)63);
+        const size_t in_bytes = o_st + ((4 * nw + 63) & ~(size_t)63);
+        const size_t o_len = in_bytes, o_tr = o_len + ((8 * nw + 63) & ~(size_t)63);
+        const size_t o_bst = o_tr + ((nw + 63) & ~(size_t)63);
+        const size_t meta_bytes = o_bst + 4 * std::max<size_t>(n_blks, 1);
+        HIPCHK(hmalloc(ctx, (void**)&held.h_meta, meta_bytes));
+        HIPCHK(dmalloc(ctx, (void**)&held.d_meta, meta_bytes));
+        HIPCHK(dmalloc(ctx, (void**)&held.d_comp, (size_t)std::max<uint64_t>(stage_bytes, 64)));
+        HIPCHK(dmalloc(ctx, (void**)&held.d_arena, (size_t)arena + 64));
+        HIPCHK(dmalloc(ctx, (void**)&held.d_text, (size_t)std::max<uint64_t>(slots, 64)));
+        HIPCHK(hmalloc(ctx, (void**)&held.h_text, (size_t)std::max<uint64_t>(slots, 64)));
+        HIPCHK(crc_pow_on_device(ctx));
+        uint8_t* h_meta = held.h_meta;
+        uint8_t* d_meta = held.d_meta;
+        if (n_blks) memcpy(h_meta + o_blk, blks.data(), sizeof(BgzfBlk) * n_blks);
+        memcpy(h_meta + o_win, wins.data(), sizeof(FastaWin) * nw);
+        if (n) memcpy(h_meta + o_st, status, 4 * (size_t)n);
+        hipStream_t st = ctx->stream;
+        if (!ctx->fasta_ev[0]) { HIPCHK(hipEventCreate(&ctx->fasta_ev[0])); HIPCHK(hipEventCreate(&ctx->fasta_ev[1])); }
+        if (stage_bytes) HIPCHK(hipMemcpyAsync(held.d_comp, h_comp, (size_t)stage_bytes, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_meta, h_meta, in_bytes, hipMemcpyHostToDevice, st));
+        HIPCHK(hipEventRecord(ctx->fasta_ev[0], st));
+        if (n_blks) {
+            hipLaunchKernelGGL(bgzf_inflate_kernel, dim3((unsigned)((n_blks + INFLATE_WAVES - 1) / INFLATE_WAVES)), dim3(64 * INFLATE_WAVES), 0, st, held.d_comp,
+                               reinterpret_cast<const BgzfBlk*>(d_meta + o_blk), (int)n_blks, held.d_arena, ctx->d_crc_pow, reinterpret_cast<int32_t*>(d_meta + o_bst));
+            HIPCHK(hipGetLastError());
+        }
+        if (n) {
+            hipLaunchKernelGGL(fasta_window_kernel, dim3((unsigned)((nw + WIN_WAVES - 1) / WIN_WAVES)), dim3(64 * WIN_WAVES), 0, st, held.d_arena,
+                               reinterpret_cast<const FastaWin*>(d_meta + o_win), (int)n, reinterpret_cast<const int32_t*>(d_meta + o_bst), held.d_text,
+                               reinterpret_cast<int64_t*>(d_meta + o_len), d_meta + o_tr, reinterpret_cast<int32_t*>(d_meta + o_st));
+            HIPCHK(hipGetLastError());
+        }
+        HIPCHK(hipEventRecord(ctx->fasta_ev[1], st));
+        HIPCHK(hipMemcpyAsync(h_meta + o_st, d_meta + o_st, meta_bytes - o_st, hipMemcpyDeviceToHost, st));
+        if (slots) HIPCHK(hipMemcpyAsync(held.h_text, held.d_text, (size_t)slots, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        // ---- the texts, one after the other ------------------------------------------------------------------------------------
+        const int32_t* d_status = reinterpret_cast<const int32_t*>(h_meta + o_st);
+        const int64_t* tlen = reinterpret_cast<const int64_t*>(h_meta + o_len);
+        int64_t pos = 0;
+        text_off[0] = 0;
+        for (int32_t i = 0; i < n; ++i) {
+            status[i] = d_status[i];
+            traits[i] = h_meta[o_tr + (size_t)i];
+            if (!status[i] && tlen[i]) {
+                memcpy(text + pos, held.h_text + wins[(size_t)i].t_off, (size_t)tlen[i]);
+                pos += tlen[i];
+            }
+            text_off[i + 1] = pos;
+        }
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, ctx->fasta_ev[0], ctx->fasta_ev[1]) != hipSuccess) ms = 0.f;
+        ctx->fasta_stats[0] = n; ctx->fasta_stats[1] = (double)n_blks; ctx->fasta_stats[2] = (double)read_bytes;
+        ctx->fasta_stats[3] = (double)arena; ctx->fasta_stats[4] = ms; ctx->fasta_stats[5] = now() - t0;
+        return VAPOR_OK;
+    } catch (const std::bad_alloc&) {
+        return fail(VAPOR_E_NOMEM, "vapor_fasta_windows_device: out of memory");
+    } catch (const std::exception& e) {
+        return fail(VAPOR_E_ARG, std::string("vapor_fasta_windows_device: ") + e.what());
+    }
+}
+
+// what the context's last vapor_fasta_windows_device did: windows, distinct blocks inflated, compressed bytes read and sent,
+// inflated bytes, the two kernels between two events on the stream (ms), the whole call on the host's clock (ms)
+extern "C" int vapor_fasta_last_stats(vapor_ctx* ctx, double* out, int32_t n)
+{
+    if (!ctx || !out || n < 0) return fail(VAPOR_E_ARG, "vapor_fasta_last_stats: null argument");
+    for (int32_t i = 0; i < n && i < 6; ++i) out[i] = ctx->fasta_stats[i];
     return VAPOR_OK;
 }
 

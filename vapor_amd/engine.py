@@ -373,6 +373,37 @@ class Engine:
         return {"regions": int(out[0]), "blocks": int(out[1]), "compressed_bytes": int(out[2]), "inflated_bytes": int(out[3]),
                 "inflate_ms": float(out[4]), "call_ms": float(out[5])}
 
+    def fasta_windows_device(self, fd: int, vbeg, vend, text_cap: int):
+        """vapor_fasta_windows_device: reference windows of a bgzipped FASTA (open descriptor `fd`), window i the raw text between
+        the virtual offsets vbeg[i] and vend[i], inflated and cut on the device.  `text_cap`: the sum of the windows' raw sizes
+        (or more).  Returns (texts: str per window, None where status != 0; traits: uint8 VAPOR_FASTA_TR_* bits; status: int32,
+        0 or the VAPOR_FASTA_* reason the window is left to the host reader)."""
+        vbeg = np.ascontiguousarray(vbeg, dtype=np.uint64)
+        vend = np.ascontiguousarray(vend, dtype=np.uint64)
+        n = len(vbeg)
+        if len(vend) != n:
+            raise ValueError("vbeg and vend differ in length")
+        text = np.empty(max(int(text_cap), 1), dtype=np.uint8)
+        off = np.zeros(n + 1, dtype=np.int64)
+        traits = np.zeros(max(n, 1), dtype=np.uint8)
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        vp = ctypes.c_void_p
+        L.check(L.load().vapor_fasta_windows_device(self._ctx, int(fd), n, vbeg.ctypes.data_as(vp), vend.ctypes.data_as(vp), text.ctypes.data_as(vp),
+                                                    int(text_cap), off.ctypes.data_as(vp), traits.ctypes.data_as(vp), status.ctypes.data_as(vp)))
+        raw = text[:int(off[n])].tobytes()
+        o = off.tolist()
+        st = status[:n]
+        bad = st.tolist()
+        texts = [None if bad[i] else raw[o[i]:o[i + 1]].decode("ascii") for i in range(n)]
+        return texts, traits[:n], st
+
+    def fasta_last_stats(self) -> dict:
+        """What this engine's last fasta_windows_device did (vapor_fasta_last_stats)."""
+        out = np.zeros(6, dtype=np.float64)
+        L.check(L.load().vapor_fasta_last_stats(self._ctx, out.ctypes.data_as(ctypes.c_void_p), 6))
+        return {"windows": int(out[0]), "blocks": int(out[1]), "compressed_bytes": int(out[2]), "inflated_bytes": int(out[3]),
+                "kernel_ms": float(out[4]), "call_ms": float(out[5])}
+
     def seqset_raw(self, addr: np.ndarray, lens: np.ndarray, derived=None, keepalive=None, src_kind=None, src_first=None) -> SeqSet:
         """A set from (address, length) pairs - slices of strings the caller keeps alive - and derived sequences as arrays."""
         return SeqSet.from_addresses(self, addr, lens, derived, keepalive, src_kind, src_first)

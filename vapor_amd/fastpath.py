@@ -46,6 +46,53 @@ def _window_traits(w: str):
     return _is_upper(w), bool(rest.translate(None, b"acgtn"))
 
 
+def _window_range(sp, k_, s_, e_, f_):
+    """(chrom, start, end) of the reference window the loop in _run reads for a locus: the same s0 / e0 / flank / INS-length rules."""
+    if k_ == 3:
+        m = len(sp[4])
+        return sp[1], s_ - f_, (s_ + f_ + m if m < 5000 else s_ + f_)
+    return sp[1], s_ - f_, e_ + f_
+
+
+def _device_fasta(be, ref, engine):
+    """The backend's reader of `ref` when it is a bgzipped FASTA whose windows the engine cuts on the device, else None."""
+    if not (hasattr(engine, "fasta_windows_device") and hasattr(be, "_fasta")):
+        return None
+    try:
+        fa = be._fasta(ref)
+    except Exception:                    # noqa: BLE001 - the host reads meet the same error where the drivers would
+        return None
+    return fa if isinstance(fa, seqio.BgzfFasta) else None
+
+
+def _device_windows(engine, fa, specs, idx, kind, s0, e0, flank) -> dict:
+    """locus -> its reference window as text, for every window the device answers with status 0 (one vapor_fasta_windows_device
+    call); the clipping and empty answers of FaiFasta.fetch are the host's."""
+    out = {}
+    ts, first, last = [], [], []
+    for t in idx.tolist():
+        chrom, a, b = _window_range(specs[t], int(kind[t]), int(s0[t]), int(e0[t]), int(flank[t]))
+        r = fa.raw_range(chrom, a, b)
+        if r is None:
+            out[t] = ""
+            continue
+        ts.append(t)
+        first.append(r[0])
+        last.append(r[1])
+    if not ts:
+        return out
+    first_a, last_a = np.asarray(first, dtype=np.int64), np.asarray(last, dtype=np.int64)
+    vb, ve = fa.virtual(first_a), fa.virtual(last_a)
+    ok = (vb >= 0) & (ve >= 0)                # (an offset past a block's 64 KB: the host reads that window)
+    sel = np.flatnonzero(ok)
+    texts, _traits, status = engine.fasta_windows_device(fa._fd, vb[sel].astype(np.uint64), ve[sel].astype(np.uint64),
+                                                         int((last_a[sel] - first_a[sel]).sum()))
+    for q, j in enumerate(sel.tolist()):
+        if status[q] == 0:
+            out[ts[j]] = texts[q]
+    return out
+
+
 def capable(backend, bam_in, engine=None) -> bool:
     """The fast route needs a backend that selects reads for many regions at once and hands windows over as text, a
     single alignment file (bam_in_decide's per-chromosome patterns, SF:69-89, go the drivers' way), and an engine that takes
@@ -108,16 +155,24 @@ def _run(engine, specs, bam_in, ref, num_reads_cff, held) -> List[object]:
         # (The context is still used by one thread at a time: this one does not touch the engine until the helper is back.)
         import threading
         box = {}
+        # A bgzipped reference: the windows are inflated and cut on the device as well, in one call right after the reads' (on
+        # the helper thread: still one thread per context), and this thread has nothing to read.
+        fa_dev = _device_fasta(be, ref, engine)
 
         def extract():
             try:
                 box["got"] = be.chop_many_device(engine, bam_in, chroms, r_start[idx], r_end[idx], flank[idx])
             except BaseException as e:       # noqa: BLE001 - handed to the calling thread below
                 box["err"] = e
+            if fa_dev is not None:
+                try:
+                    box["win"] = _device_windows(engine, fa_dev, specs, idx, kind, s0, e0, flank)
+                except BaseException as e:   # noqa: BLE001 - handed to the calling thread below
+                    box["win_err"] = e
         th = threading.Thread(target=extract)
         th.start()
         try:
-            for t in idx.tolist():
+            for t in (idx.tolist() if fa_dev is None else ()):
                 sp = specs[t]
                 f, s_ = int(flank[t]), int(s0[t])
                 if int(kind[t]) == 3:
@@ -129,6 +184,10 @@ def _run(engine, specs, bam_in, ref, num_reads_cff, held) -> List[object]:
             pass
         finally:
             th.join()
+        if "win_err" in box:
+            raise box["win_err"]
+        # (a window the device left to the host - status != 0 - is not here: the loop below reads it with the host reader)
+        refw_of.update(box.get("win", {}))
         _mark("extract+windows")
         if "got" in box:
             kf, addr, q0, miss, status, keepalive = box["got"]

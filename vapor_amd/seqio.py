@@ -89,6 +89,228 @@ class FaiFasta:
         return [">" + region] + [seq[i:i + 60] for i in range(0, len(seq), 60)]
 
 
+class BgzfFasta:
+    """FaiFasta for a bgzip-compressed FASTA (`samtools faidx ref.fa.gz`): the .fai geometry applied to the uncompressed stream,
+    found through the .gzi block table (htslib's: a little-endian uint64 count, then (compressed, uncompressed) offset pairs
+    of the blocks after the first; without a .gzi the same table is built in memory by walking the block headers).  Blocks are
+    inflated by the library's host decoder and checked by their CRC-32 and size; a damaged block raises.  A small cache of
+    inflated blocks; positioned reads, so that several threads may fetch at once."""
+
+    CACHE_BLOCKS = 64
+
+    def __init__(self, path: str):
+        import numpy as np
+        self.path = path
+        self.index = {}
+        with open(path + ".fai") as f:
+            for ln in f:
+                t = ln.rstrip("\n").split("\t")
+                if len(t) >= 5:
+                    self.index[t[0]] = (int(t[1]), int(t[2]), int(t[3]), int(t[4]))
+        self._fh = open(path, "rb")
+        self._fd = self._fh.fileno()
+        if not is_bgzf(path):
+            raise ValueError(_not_bgzf_msg(path))
+        gzi = path + ".gzi"
+        if os.path.exists(gzi):
+            raw = open(gzi, "rb").read()
+            cnt = int.from_bytes(raw[:8], "little") if len(raw) >= 8 else -1
+            if cnt < 0 or len(raw) != 8 + 16 * cnt:
+                raise ValueError("%s is not a BGZF index (.gzi)" % gzi)
+            pairs = np.frombuffer(raw, dtype="<u8", count=2 * cnt, offset=8).reshape(-1, 2)
+            coff, uoff = pairs[:, 0].astype(np.int64), pairs[:, 1].astype(np.int64)
+        else:
+            coff, uoff = self._walk()
+        self.coff = np.concatenate(([0], coff)).astype(np.int64)        # (the first block's (0, 0) is implicit)
+        self.uoff = np.concatenate(([0], uoff)).astype(np.int64)
+        self._cache = {}
+        self._lock = threading.Lock()
+
+    def _walk(self):
+        """The .gzi table from the block headers (BSIZE and ISIZE; nothing is inflated)."""
+        import numpy as np
+        size = os.fstat(self._fd).st_size
+        c, u = 0, 0
+        cs, us = [], []
+        while c < size:
+            bsize = _bgzf_bsize(os.pread(self._fd, 512, c))
+            tail = os.pread(self._fd, 4, c + bsize - 4) if bsize else b""
+            if bsize is None or len(tail) < 4:
+                raise ValueError("%s: no whole BGZF block at offset %d" % (self.path, c))
+            c += bsize
+            u += int.from_bytes(tail, "little")
+            if c < size:
+                cs.append(c)
+                us.append(u)
+        return np.asarray(cs, dtype=np.int64), np.asarray(us, dtype=np.int64)
+
+    def _header(self, coff: int, hdr: bytes = None):
+        """(BSIZE, CRC32, ISIZE) of the block at `coff`; raises for anything that is not a whole BGZF block."""
+        if hdr is None:
+            hdr = os.pread(self._fd, 65536, coff)
+        bsize = _bgzf_bsize(hdr)
+        if bsize is None or len(hdr) < bsize:
+            raise ValueError("%s: no whole BGZF block at offset %d" % (self.path, coff))
+        crc = int.from_bytes(hdr[bsize - 8:bsize - 4], "little")
+        isize = int.from_bytes(hdr[bsize - 4:bsize], "little")
+        if isize > 65536:
+            raise ValueError("%s: BGZF block at offset %d claims %d bytes (at most 65536)" % (self.path, coff, isize))
+        return bsize, crc, isize
+
+    def block(self, k: int) -> bytes:
+        """The data of block k of the table, inflated and checked."""
+        coff = int(self.coff[k])
+        got = self._cache.get(coff)
+        if got is not None:
+            return got
+        import ctypes
+        from . import _lib
+        raw = os.pread(self._fd, 65536, coff)
+        bsize, crc, isize = self._header(coff, raw)
+        xlen = raw[10] | (raw[11] << 8)
+        payload = raw[12 + xlen:bsize - 8]
+        lib = _lib.load()
+        out = ctypes.create_string_buffer(max(isize, 1))
+        if lib.vapor_inflate_raw(payload, len(payload), out, isize) != 0:
+            raise ValueError("%s: BGZF block at offset %d does not inflate to its %d bytes" % (self.path, coff, isize))
+        data = out.raw[:isize]
+        if (lib.vapor_crc32(data, isize, 0) if isize else 0) != crc:
+            raise ValueError("%s: BGZF block at offset %d fails its CRC32 check" % (self.path, coff))
+        with self._lock:
+            if len(self._cache) >= self.CACHE_BLOCKS:
+                self._cache.clear()
+            self._cache[coff] = data
+        return data
+
+    def raw_range(self, chrom: str, start: int, end: int):
+        """[first, last) of the window's raw text (newlines included) in the uncompressed stream, or None: FaiFasta.fetch's
+        clipping (1-based inclusive, clipped to the contig; unknown contig or empty range: None)."""
+        if chrom not in self.index:
+            return None
+        length, offset, linebases, linewidth = self.index[chrom]
+        start = max(int(start), 1)
+        end = min(int(end), length)
+        if end < start:
+            return None
+        a, b = start - 1, end
+        first = offset + (a // linebases) * linewidth + a % linebases
+        last = offset + ((b - 1) // linebases) * linewidth + (b - 1) % linebases + 1
+        return first, last
+
+    def block_of(self, u):
+        """Index of the block that holds uncompressed offset u (an array of them too)."""
+        import numpy as np
+        return np.searchsorted(self.uoff, u, side="right") - 1
+
+    def virtual(self, u):
+        """Virtual offsets (compressed block offset << 16 | offset in its data) of uncompressed offsets u (numpy arrays); a
+        position past a block's 64 KB cannot be said that way and comes back as -1."""
+        import numpy as np
+        u = np.asarray(u, dtype=np.int64)
+        k = self.block_of(u)
+        w = u - self.uoff[k]
+        return np.where(w < 65536, (self.coff[k] << 16) | w, -1)
+
+    def read_raw(self, first: int, last: int) -> bytes:
+        k0, k1 = int(self.block_of(first)), int(self.block_of(last - 1))
+        parts = []
+        for k in range(k0, k1 + 1):
+            d = self.block(k)
+            u0 = int(self.uoff[k])
+            parts.append(d[max(first - u0, 0):last - u0])
+        raw = b"".join(parts)
+        if len(raw) != last - first:
+            raise ValueError("%s: the BGZF blocks hold %d of the %d bytes at offset %d" % (self.path, len(raw), last - first, first))
+        return raw
+
+    def fetch(self, chrom: str, start: int, end: int) -> str:
+        """1-based inclusive, clipped to the contig like samtools."""
+        r = self.raw_range(chrom, start, end)
+        if r is None:
+            return ""
+        return self.read_raw(*r).replace(b"\n", b"").replace(b"\r", b"").decode("ascii")
+
+    lines = FaiFasta.lines
+
+
+def _bgzf_bsize(hdr: bytes):
+    """BSIZE of the BGZF block whose header starts `hdr`, or None when it is not one (gzip with the BC extra field)."""
+    if len(hdr) < 18 or hdr[:4] != b"\x1f\x8b\x08\x04":
+        return None
+    xlen = hdr[10] | (hdr[11] << 8)
+    p = 12
+    while p + 4 <= 12 + xlen and p + 4 <= len(hdr):
+        slen = hdr[p + 2] | (hdr[p + 3] << 8)
+        if hdr[p] == 66 and hdr[p + 1] == 67 and slen == 2 and p + 6 <= len(hdr):
+            bsize = (hdr[p + 4] | (hdr[p + 5] << 8)) + 1
+            return bsize if bsize >= xlen + 20 else None
+        p += 4 + slen
+    return None
+
+
+def is_bgzf(path: str) -> bool:
+    with open(path, "rb") as f:
+        return _bgzf_bsize(f.read(512)) is not None
+
+
+def _not_bgzf_msg(path: str) -> str:
+    return ("%s is gzip-compressed but not BGZF: a FASTA must be compressed with `bgzip` (and indexed with `samtools faidx`) "
+            "to be read by region" % path)
+
+
+def open_fasta(path: str):
+    """The reader for a FASTA with its .fai: BgzfFasta for a bgzip-compressed file (its first block a gzip member with the BC
+    extra field), FaiFasta for plain text.  Any other gzip file raises."""
+    try:
+        with open(path, "rb") as f:
+            head = f.read(512)
+    except OSError:
+        return FaiFasta(path)             # (which raises as it always has)
+    if head[:2] == b"\x1f\x8b":
+        if _bgzf_bsize(head) is None:
+            raise ValueError(_not_bgzf_msg(path))
+        return BgzfFasta(path)
+    return FaiFasta(path)
+
+
+def write_bgzf_fasta(path: str, contigs, line_width: int = 60, block_size: int = 65280, crlf: bool = False) -> str:
+    """A bgzipped FASTA of `contigs` (name -> sequence, or (name, sequence) pairs) with the .fai `samtools faidx` writes for it
+    (uncompressed offsets) and the .gzi of its blocks; blocks of `block_size` uncompressed bytes (bgzip's 65 280 by default)
+    and the BGZF end-of-file block.  Returns `path`."""
+    import struct
+    from . import bamio
+    items = list(contigs.items()) if hasattr(contigs, "items") else list(contigs)
+    nl = "\r\n" if crlf else "\n"
+    text, fai = [], []
+    off = 0
+    for name, seq in items:
+        hdr = ">" + name + nl
+        off += len(hdr)
+        text.append(hdr)
+        fai.append("%s\t%d\t%d\t%d\t%d\n" % (name, len(seq), off, line_width, line_width + len(nl)))
+        body = "".join(seq[i:i + line_width] + nl for i in range(0, len(seq), line_width))
+        text.append(body)
+        off += len(body)
+    data = "".join(text).encode("ascii")
+    gzi = []
+    c = 0
+    with open(path, "wb") as f:
+        for u in range(0, len(data), block_size):
+            if u:
+                gzi.append((c, u))
+            blk = bamio._bgzf_block(data[u:u + block_size])
+            f.write(blk)
+            c += len(blk)
+        if data:
+            gzi.append((c, len(data)))             # (as htslib indexes it: an entry for every block after the first, the EOF block's too)
+        f.write(bamio._BGZF_EOF)
+    with open(path + ".fai", "w") as f:
+        f.write("".join(fai))
+    with open(path + ".gzi", "wb") as f:
+        f.write(struct.pack("<Q", len(gzi)) + b"".join(struct.pack("<QQ", a, b) for a, b in gzi))
+    return path
+
+
 class SamtoolsHybrid(SamtoolsCLI):
     """samtools for the BAM, the .fai index read in-process for the reference windows: one process per
     locus instead of two or more."""
@@ -102,7 +324,7 @@ class SamtoolsHybrid(SamtoolsCLI):
         if fa is None:
             if not os.path.exists(ref + ".fai"):
                 return super().faidx_lines(ref, region)
-            fa = self._fa[ref] = FaiFasta(ref)
+            fa = self._fa[ref] = open_fasta(ref)
         return fa.lines(region)
 
 
@@ -309,13 +531,13 @@ class InProcessBam(SamtoolsHybrid):
                     out.append([tail[:want], miss_bp, qname])
         return out
 
-    def _fasta(self, ref: str) -> FaiFasta:
+    def _fasta(self, ref: str):
         fa = self._fa.get(ref)
         if fa is None:
             with self._open_lock:
                 fa = self._fa.get(ref)
                 if fa is None:
-                    fa = self._fa[ref] = FaiFasta(ref)
+                    fa = self._fa[ref] = open_fasta(ref)
         return fa
 
     def faidx_lines(self, ref: str, region: str) -> Iterable[str]:

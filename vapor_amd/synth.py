@@ -560,13 +560,29 @@ def complex_vcf_text(world: SynthWorld, header: bool = False) -> str:
     return "\n".join(out) + "\n"
 
 
-def write_world_files(world: SynthWorld, directory: str, block_size: int = 8192, qual_seed=None) -> Tuple[str, str]:
+def write_world_files(world: SynthWorld, directory: str, block_size: int = 8192, qual_seed=None,
+                      bgzip_reference: bool = False) -> Tuple[str, str]:
     """FASTA + .fai and coordinate-sorted BAM + .bai of a synthetic world, written by this package alone
-    (vapor_amd.bamio); returns (fasta path, bam path).  Reads keep their order inside one start position."""
+    (vapor_amd.bamio); returns (fasta path, bam path).  Reads keep their order inside one start position.  With
+    `bgzip_reference` the reference is written bgzipped instead (ref.fa.gz + .fai + .gzi, seqio.write_bgzf_fasta)."""
     import os
     from . import bamio
-    fa = os.path.join(directory, "ref.fa")
     names = list(world.contigs)
+    if bgzip_reference:
+        from . import seqio
+        fa = seqio.write_bgzf_fasta(os.path.join(directory, "ref.fa.gz"),
+                                    [(n, world.contigs[n] if isinstance(world.contigs[n], str) else world.contigs[n][0:len(world.contigs[n])])
+                                     for n in names])
+    else:
+        fa = os.path.join(directory, "ref.fa")
+        _write_plain_fasta(world, fa, names)
+    recs = [(r.qname, names.index(c), r.pos - 1, r.cigar, r.seq) for c, rs in world.reads.items() for r in rs]
+    bam = os.path.join(directory, "reads.bam")
+    bamio.write_bam(bam, [(n, len(world.contigs[n])) for n in names], recs, block_size=block_size, qual_seed=qual_seed)
+    return fa, bam
+
+
+def _write_plain_fasta(world, fa, names):
     with open(fa, "w") as f, open(fa + ".fai", "w") as fi:
         off = 0
         for n in names:
@@ -579,10 +595,6 @@ def write_world_files(world: SynthWorld, directory: str, block_size: int = 8192,
             for i in range(0, len(seq), 60):
                 f.write(seq[i:i + 60] + "\n")
             off += len(seq) + (len(seq) + 59) // 60
-    recs = [(r.qname, names.index(c), r.pos - 1, r.cigar, r.seq) for c, rs in world.reads.items() for r in rs]
-    bam = os.path.join(directory, "reads.bam")
-    bamio.write_bam(bam, [(n, len(world.contigs[n])) for n in names], recs, block_size=block_size, qual_seed=qual_seed)
-    return fa, bam
 
 
 # ---------------------------------------------------------------------------
