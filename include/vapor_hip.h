@@ -39,6 +39,7 @@ extern "C" {
 
 #define VAPOR_MAX_SEQ_LEN 65535 /* positions are packed 16+16 bit on the device */
 #define VAPOR_MAX_WIDE_SEQ_LEN 1048575 /* the wide route (vapor_wide_batch, vapor_clean_hits_wide): 2^20 - 1 */
+#define VAPOR_MAX_ANY_K 64 /* the any-k route (vapor_anyk_batch): k from 1 to this */
 
 typedef struct vapor_ctx vapor_ctx;
 typedef struct vapor_seqset vapor_seqset;
@@ -51,7 +52,7 @@ typedef struct vapor_plan vapor_plan;
  * One dot plot: dotdata(k, seq1, seq2[off2:]) (SF:545-549 -> kmerhits SF:951-983), i.e. the
  * reference's call convention dotdata(window_size, read, allele[miss_bp:]) (SF:185-186,
  * 242-243, 278-279).  seq1/seq2 index a vapor_seqset.  k must be 10, 20, 30 or 40, the only
- * values window_size_refine can return (SF:2031-2041).
+ * values window_size_refine can return (SF:2031-2041); vapor_anyk_batch takes 1 .. VAPOR_MAX_ANY_K.
  */
 typedef struct vapor_pair {
     int32_t seq1;  /* read (the sequence whose k-mers are also searched reverse-complemented) */
@@ -65,6 +66,8 @@ typedef struct vapor_pair {
 #define VAPOR_PF_C2 2u   /* the two-step cleaning of within_10Perc_m1b (SF:281-288) -> ST_C2_* */
 #define VAPOR_PF_DIR 4u  /* with PF_C1: dis_to_diagnal_most_abundant_defined (SF:582-591) and
                             eu_dis_dir_calcu (SF:718-722) over the C1-kept dots -> ST_DIR_* */
+#define VAPOR_PF_FORWARD 8u /* vapor_anyk_batch only: kmerhits(seq1, seq2, k, 1, inversions=False) - no reverse-complement keys,
+                               no KeyError, symbols outside the folded alphabet compared byte for byte */
 
 /* int64 statistics record per pair (VAPOR_STATS_STRIDE words) */
 #define VAPOR_STATS_STRIDE 16
@@ -286,6 +289,22 @@ int vapor_wide_batch(vapor_ctx* ctx, vapor_seqset* set, int64_t n_pairs, const v
                      int32_t* hits_ji, int64_t hits_capacity, int64_t* hit_off);
 int vapor_clean_hits_wide(vapor_ctx* ctx, int64_t n_lists, const int32_t* hits_ji, const int64_t* off,
                           const uint32_t* flags, int64_t* stats, uint8_t* hit_flags);
+
+/* ---- the any-k route: kmerhits at every k from 1 to VAPOR_MAX_ANY_K ------------------------- */
+/*
+ * kmerhits(seq1, seq2[off2:], k, 1, inversions) (SF:951-983) for any 1 <= k <= VAPOR_MAX_ANY_K, inversions unless the pair has
+ * VAPOR_PF_FORWARD.  k <= 40: exact k-mer matches.  k > 40: the reference's edit-distance branch (SF:969-973) - allele k-mer j
+ * matches every distinct read key (forward and, with inversions, reverse-complemented) within Levenshtein distance k / 10.
+ * vapor_wide_batch's contract otherwise (sequences up to VAPOR_MAX_WIDE_SEQ_LEN, one pair at a time, the statistics record,
+ * VAPOR_E_OVERFLOW past "max_pair_cap", hits_ji / hits_capacity / hit_off), except that the dots of a pair come in the
+ * reference's list order: j ascending; for one j, k <= 40: the lookup list (i ascending, a k-mer equal to its own reverse
+ * complement twice), k > 40: the keys in order of first insertion, each key's list in order.  A pair is refused with
+ * VAPOR_E_ARG for k outside 1 .. VAPOR_MAX_ANY_K, and for VAPOR_PF_FORWARD over a derived sequence that holds a symbol outside
+ * the folded alphabet (its bytes are not kept).  With inversions a seq1 of at least k symbols that holds a symbol outside
+ * invert_base's alphabet is VAPOR_E_KEYERROR.
+ */
+int vapor_anyk_batch(vapor_ctx* ctx, vapor_seqset* set, int64_t n_pairs, const vapor_pair* pairs, int64_t* stats,
+                     int32_t* hits_ji, int64_t hits_capacity, int64_t* hit_off);
 
 /*
  * Host helper of the read extraction (cigar2alignstart_by_pos, SF:309-337; no device involved): walks the CIGAR of

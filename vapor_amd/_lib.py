@@ -30,11 +30,13 @@ ST_N_HITS, ST_FIRST_J, ST_LAST_J, ST_C1_KEPT, ST_C1_SUM_ABS = 0, 1, 2, 3, 4
 ST_C2_KEPT, ST_C2_COUNT10, ST_N_DIAG, ST_N_LOWER, ST_C2_KEPT_DIAG, ST_STATUS = 5, 6, 7, 8, 9, 15
 ST_DIR_C2X, ST_DIR_N, ST_DIR_SUM2, ST_DIR_LISTS = 10, 11, 12, 13
 PF_C1, PF_C2, PF_DIR = 1, 2, 4
+PF_FORWARD = 8                 # vapor_anyk_batch: kmerhits(..., inversions=False)
 HF_C1_KEPT, HF_C2_DIAG, HF_C2_ANTI = 1, 2, 4
 SEQ_UPPER = 1
 E_HIP, E_OVERFLOW, E_KEYERROR, E_ARG, E_NOMEM = -1, -2, -3, -4, -5
 MAX_SEQ_LEN = 65535
 MAX_WIDE_SEQ_LEN = 1048575     # the wide route: vapor_wide_batch / vapor_clean_hits_wide
+MAX_ANY_K = 64                 # the any-k route: vapor_anyk_batch takes k from 1 to this
 FASTA_BLOCK, FASTA_RANGE, FASTA_NON_ASCII, FASTA_ROOM = 1, 2, 3, 4                    # vapor_fasta_windows_device: status of a window
 FASTA_TR_LOWER, FASTA_TR_NOT_ACGTN, FASTA_TR_NOT_ACGTN_ANY_CASE, FASTA_TR_HIGH = 1, 2, 4, 8    # ... and its traits
 ABI_VERSION = 3
@@ -50,11 +52,11 @@ EXPORTS = [
     "vapor_bam_open", "vapor_bam_close", "vapor_bam_set_threads", "vapor_bam_last_error", "vapor_bam_chop",
     "vapor_inflate_raw", "vapor_chop_records", "vapor_chop_records_many", "vapor_row_tails", "vapor_crc32",
     "vapor_bam_chop_device", "vapor_bam_batch_destroy", "vapor_bam_fileno", "vapor_bam_threads", "vapor_seqset_create_mixed", "vapor_bam_last_stats",
-    "vapor_wide_batch", "vapor_clean_hits_wide", "vapor_fasta_windows_device", "vapor_fasta_last_stats",
+    "vapor_wide_batch", "vapor_clean_hits_wide", "vapor_fasta_windows_device", "vapor_fasta_last_stats", "vapor_anyk_batch",
 ]
-# entry points a library may lack (the CPU twin of the C ABI has no wide route): bound when present, and the engine's wide
-# methods raise NotImplementedError when they are not
-OPTIONAL_EXPORTS = ("vapor_wide_batch", "vapor_clean_hits_wide")
+# entry points a library may lack (the CPU twin of the C ABI has no wide or any-k route): bound when present, and the engine's
+# wide and any-k methods raise NotImplementedError when they are not
+OPTIONAL_EXPORTS = ("vapor_wide_batch", "vapor_clean_hits_wide", "vapor_anyk_batch")
 
 _lib = None
 
@@ -205,6 +207,8 @@ def bind(L: ctypes.CDLL) -> ctypes.CDLL:
         L.vapor_wide_batch.argtypes = [vp, vp, ctypes.c_int64, vp, i64p, i32p, ctypes.c_int64, i64p]
     if hasattr(L, "vapor_clean_hits_wide"):
         L.vapor_clean_hits_wide.argtypes = [vp, ctypes.c_int64, i32p, i64p, u32p, i64p, u8p]
+    if hasattr(L, "vapor_anyk_batch"):
+        L.vapor_anyk_batch.argtypes = [vp, vp, ctypes.c_int64, vp, i64p, i32p, ctypes.c_int64, i64p]
     for name in EXPORTS:
         if name in OPTIONAL_EXPORTS and not hasattr(L, name):
             continue

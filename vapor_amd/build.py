@@ -11,7 +11,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SO = os.path.join(HERE, "libvapor_hip.so")
 SOURCES = [os.path.join(HERE, "csrc", "vapor_hip.hip"), os.path.join(HERE, "csrc", "vapor_bam.cpp")]
-DEPS = SOURCES + [os.path.join(HERE, "csrc", "vapor_kernels.h"), os.path.join(HERE, "csrc", "vapor_wide.h"), os.path.join(HERE, "csrc", "vapor_inflate.h"),
+DEPS = SOURCES + [os.path.join(HERE, "csrc", "vapor_kernels.h"), os.path.join(HERE, "csrc", "vapor_wide.h"), os.path.join(HERE, "csrc", "vapor_anyk.h"),
+                  os.path.join(HERE, "csrc", "vapor_inflate.h"),
                   os.path.join(HERE, "csrc", "vapor_bamdev.h"), os.path.join(HERE, "csrc", "vapor_fasta.h"),
                   os.path.join(ROOT, "include", "vapor_hip.h")]
 
@@ -31,7 +32,8 @@ def hipcc() -> str:
     raise RuntimeError("hipcc not found")
 
 
-KERNEL_FILES = [os.path.join(HERE, "csrc", "vapor_kernels.h"), os.path.join(HERE, "csrc", "vapor_wide.h"), os.path.join(HERE, "csrc", "vapor_bamdev.h"), os.path.join(HERE, "csrc", "vapor_fasta.h"),
+KERNEL_FILES = [os.path.join(HERE, "csrc", "vapor_kernels.h"), os.path.join(HERE, "csrc", "vapor_wide.h"), os.path.join(HERE, "csrc", "vapor_anyk.h"),
+                os.path.join(HERE, "csrc", "vapor_bamdev.h"), os.path.join(HERE, "csrc", "vapor_fasta.h"),
                 os.path.join(HERE, "csrc", "vapor_hip.hip"), os.path.abspath(__file__)]
 _ID_RE = re.compile(rb"VAPOR_SOURCE_ID=([0-9a-f]{16}:[0-9a-f]{16})")
 

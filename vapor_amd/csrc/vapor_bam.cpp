@@ -674,6 +674,13 @@ extern "C" __attribute__((weak)) int vapor_clean_hits_wide(vapor_ctx*, int64_t, 
     return bfail(VAPOR_E_ARG, "vapor_clean_hits_wide: this build has no wide route");
 }
 
+// The any-k route (vapor_anyk_batch) is device code in vapor_hip.hip too; the CPU twin refuses it the same way.
+extern "C" __attribute__((weak)) int vapor_anyk_batch(vapor_ctx*, vapor_seqset*, int64_t, const vapor_pair*, int64_t*, int32_t*,
+                                                      int64_t, int64_t*)
+{
+    return bfail(VAPOR_E_ARG, "vapor_anyk_batch: this build has no any-k route");
+}
+
 // The reference windows of a bgzipped FASTA on the device (vapor_fasta_windows_device, vapor_fasta_last_stats) are device code in
 // vapor_hip.hip as well; the CPU twin answers them with VAPOR_E_ARG, and the caller reads the windows on the host.
 extern "C" __attribute__((weak)) int vapor_fasta_windows_device(vapor_ctx*, int, int32_t, const uint64_t*, const uint64_t*, uint8_t*, int64_t,

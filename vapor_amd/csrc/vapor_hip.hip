@@ -7,6 +7,7 @@
 // bit planes, a vapor_plan holds pair/task descriptors, the hit workspace and the statistics.
 #include "vapor_kernels.h"
 #include "vapor_wide.h"
+#include "vapor_anyk.h"
 #include "vapor_bamdev.h"
 #include "vapor_fasta.h"
 #include "vapor_hip.h"
@@ -199,6 +200,10 @@ struct vapor_seqset {
     std::vector<std::vector<HSeg>> derived;     // per derived sequence (index - n_lit)
     std::vector<ShareGroup> groups;
     std::vector<int32_t> group_of, slot_of;     // per caller-visible sequence: its group (-1: none) and slot in it
+    // the bytes of the sequences given as bytes that hold a symbol outside invert_base's alphabet (the 4-bit plane keeps one
+    // code for all of them; vapor_anyk_batch's forward pairs compare them byte for byte): sequence i at d_raw + raw_off[i], -1: none
+    uint8_t* d_raw = nullptr;
+    std::vector<int64_t> raw_off;
 };
 
 struct Launch {
@@ -430,6 +435,7 @@ extern "C" int vapor_seqset_destroy(vapor_seqset* s)
     dfree(s->ctx, s->d_p2);
     dfree(s->ctx, s->d_e1);
     dfree(s->ctx, s->d_x4);
+    dfree(s->ctx, s->d_raw);
     delete s;
     return VAPOR_OK;
 }
@@ -769,6 +775,21 @@ static int seqset_create_impl(vapor_ctx* ctx, int32_t n_seqs, SRC src, const int
                                            "(outside ATGCN/atgcn, SF:471-478); upload that allele as bytes");
                     break;
                 }
+        if (rc == VAPOR_OK) {
+            // keep the bytes of the sequences with symbols outside the alphabet (rare) before the staging buffer is reused
+            s->raw_off.assign(s->h.size(), -1);
+            size_t raw_bytes = 0;
+            for (int32_t i = 0; i < n_seqs; ++i)
+                if (s->h[i].n_invalid > 0) { s->raw_off[i] = (int64_t)raw_bytes; raw_bytes += ((size_t)s->h[i].len + 15) & ~(size_t)15; }
+            if (raw_bytes) {
+                SS_CHK(dmalloc(ctx, (void**)&s->d_raw, raw_bytes));
+                for (int32_t i = 0; i < n_seqs; ++i)
+                    if (s->raw_off[i] >= 0 && s->h[i].len)
+                        SS_CHK(hipMemcpyAsync(s->d_raw + s->raw_off[i], d_asc + (size_t)s->h[i].asc0 * 32, (size_t)s->h[i].len,
+                                              hipMemcpyDeviceToDevice, ctx->stream));
+                SS_CHK(hipStreamSynchronize(ctx->stream));
+            }
+        }
         if (seq_info && rc == VAPOR_OK)
             for (int32_t i = 0; i < s->n; ++i) {
                 seq_info[2 * i] = s->h[i].n_exc;
@@ -2756,6 +2777,179 @@ extern "C" int vapor_clean_hits_wide(vapor_ctx* ctx, int64_t n_lists, const int3
         WIDE_CHK(hipStreamSynchronize(st));
         wide_stats(res, n, f, stats + 16 * t);
     }
+    return VAPOR_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// The any-k route (vapor_anyk.h): kmerhits at every k from 1 to VAPOR_MAX_ANY_K, dots in the reference's order, the statistics
+// from the wide route's cleaning.
+namespace {
+
+// the pair's symbol bytes, sorted entries and per-j counts: enqueued on st, the number of dots at b.OFF[nk2]
+struct AnykBufs : WideBufs {
+    enum { SYM, IDX, CNT, FIRST, OFF, ISF, RUN, RANK, KEYS };
+};
+
+inline size_t anyk_pad(int n) { return ((size_t)n + 16 + 15) & ~(size_t)15; }
+
+// the edit-distance pass over allele k-mers 0 .. nk2 - 1, in launches of at most ANYK_EDIT_PAIRS distances (n entries bound the
+// number of keys)
+template <bool EMIT>
+void anyk_edit_launch(AnykBufs& x, hipStream_t st, const AnykSrc& src, int n, int nk2, uint32_t* cnt, const long long* off, int2* dots)
+{
+    const long long per = std::max<long long>(ANYK_EDIT_WAVES, ANYK_EDIT_PAIRS / std::max(n, 1) / ANYK_EDIT_WAVES * ANYK_EDIT_WAVES);
+    for (long long j0 = 0; j0 < nk2; j0 += per) {
+        const int j1 = (int)std::min<long long>(nk2, j0 + per);
+        hipLaunchKernelGGL((anyk_edit_kernel<EMIT>), dim3((unsigned)((j1 - j0 + ANYK_EDIT_WAVES - 1) / ANYK_EDIT_WAVES)), dim3(64 * ANYK_EDIT_WAVES), 0,
+                           st, src, x.at<const uint32_t>(AnykBufs::IDX), (const int4*)x.at<int4>(AnykBufs::KEYS),
+                           (const long long*)(x.at<long long>(AnykBufs::RANK) + n), (int)j0, j1, cnt, off, dots);
+    }
+}
+
+hipError_t anyk_count(AnykBufs& x, hipStream_t st, const AnykSrc& src, int nk1, int nk2)
+{
+    const int n = src.inv ? 2 * nk1 : nk1;
+    int np = ANYK_TILE;
+    while (np < n) np <<= 1;
+    hipError_t e;
+    if ((e = x.ensure(AnykBufs::IDX, sizeof(uint32_t) * (size_t)np)) != hipSuccess) return e;
+    uint32_t* idx = x.at<uint32_t>(AnykBufs::IDX);
+    hipLaunchKernelGGL(anyk_iota_kernel, dim3(wide_grid(np)), dim3(256), 0, st, idx, n, np);
+    hipLaunchKernelGGL(anyk_sort_local_kernel, dim3(np / ANYK_TILE), dim3(256), 0, st, src, idx, 1, 0);
+    for (int kk = 2 * ANYK_TILE; kk <= np; kk <<= 1) {
+        for (int jj = kk >> 1; jj >= ANYK_TILE; jj >>= 1)
+            hipLaunchKernelGGL(anyk_sort_global_kernel, dim3(wide_grid(np / 2)), dim3(256), 0, st, src, idx, np, kk, jj);
+        hipLaunchKernelGGL(anyk_sort_local_kernel, dim3(np / ANYK_TILE), dim3(256), 0, st, src, idx, 0, kk);
+    }
+    if ((e = x.ensure(AnykBufs::CNT, sizeof(uint32_t) * (size_t)nk2)) != hipSuccess) return e;
+    if ((e = x.ensure(AnykBufs::OFF, sizeof(long long) * ((size_t)nk2 + 1))) != hipSuccess) return e;
+    uint32_t* cnt = x.at<uint32_t>(AnykBufs::CNT);
+    if (src.k <= ANYK_EXACT_MAX_K) {
+        if ((e = x.ensure(AnykBufs::FIRST, sizeof(uint32_t) * (size_t)nk2)) != hipSuccess) return e;
+        hipLaunchKernelGGL(anyk_probe_kernel, dim3(wide_grid(nk2)), dim3(256), 0, st, src, (const uint32_t*)idx, n, nk2, cnt,
+                           x.at<uint32_t>(AnykBufs::FIRST));
+    } else {
+        if ((e = x.ensure(AnykBufs::ISF, sizeof(uint32_t) * (size_t)n)) != hipSuccess) return e;
+        if ((e = x.ensure(AnykBufs::RUN, sizeof(int2) * (size_t)n)) != hipSuccess) return e;
+        if ((e = x.ensure(AnykBufs::RANK, sizeof(long long) * ((size_t)n + 1))) != hipSuccess) return e;
+        if ((e = x.ensure(AnykBufs::KEYS, sizeof(int4) * (size_t)n)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(x.p[AnykBufs::ISF], 0, sizeof(uint32_t) * (size_t)n, st)) != hipSuccess) return e;
+        hipLaunchKernelGGL(anyk_group_kernel, dim3(wide_grid(n)), dim3(256), 0, st, src, (const uint32_t*)idx, n,
+                           x.at<uint32_t>(AnykBufs::ISF), x.at<int2>(AnykBufs::RUN));
+        hipLaunchKernelGGL(wide_scan_kernel, dim3(1), dim3(WIDE_SCAN_THREADS), 0, st, (const uint32_t*)x.at<uint32_t>(AnykBufs::ISF), n,
+                           x.at<long long>(AnykBufs::RANK));
+        hipLaunchKernelGGL(anyk_rank_kernel, dim3(wide_grid(n)), dim3(256), 0, st, n, (const uint32_t*)x.at<uint32_t>(AnykBufs::ISF),
+                           (const long long*)x.at<long long>(AnykBufs::RANK), (const int2*)x.at<int2>(AnykBufs::RUN), x.at<int4>(AnykBufs::KEYS));
+        anyk_edit_launch<false>(x, st, src, n, nk2, cnt, nullptr, nullptr);
+    }
+    hipLaunchKernelGGL(wide_scan_kernel, dim3(1), dim3(WIDE_SCAN_THREADS), 0, st, (const uint32_t*)cnt, nk2, x.at<long long>(AnykBufs::OFF));
+    return hipGetLastError();
+}
+
+void anyk_emit(AnykBufs& x, hipStream_t st, const AnykSrc& src, int nk1, int nk2, int2* dots)
+{
+    const int n = src.inv ? 2 * nk1 : nk1;
+    const uint32_t* idx = x.at<const uint32_t>(AnykBufs::IDX);
+    const long long* off = x.at<const long long>(AnykBufs::OFF);
+    if (src.k <= ANYK_EXACT_MAX_K)
+        hipLaunchKernelGGL(anyk_emit_kernel, dim3(wide_grid(nk2)), dim3(256), 0, st, src, idx, nk2, (const uint32_t*)x.at<uint32_t>(AnykBufs::CNT),
+                           (const uint32_t*)x.at<uint32_t>(AnykBufs::FIRST), off, dots);
+    else
+        anyk_edit_launch<true>(x, st, src, n, nk2, nullptr, off, dots);
+}
+
+}  // namespace
+
+extern "C" int vapor_anyk_batch(vapor_ctx* ctx, vapor_seqset* set, int64_t n_pairs, const vapor_pair* pairs, int64_t* stats,
+                                int32_t* hits_ji, int64_t hits_capacity, int64_t* hit_off)
+{
+    if (!ctx || !set || n_pairs < 0 || (n_pairs && (!pairs || !stats)) || (hits_ji && !hit_off) || hits_capacity < 0)
+        return fail(VAPOR_E_ARG, "vapor_anyk_batch: null argument");
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    WideBufs b;
+    b.c = ctx;
+    AnykBufs x;
+    x.c = ctx;
+    WIDE_CHK(b.ensure(WideBufs::ACC, sizeof(WideAcc)));
+    const WideAcc init = wide_acc_init();
+    int64_t running = 0;
+    if (hit_off) hit_off[0] = 0;
+    for (int64_t t = 0; t < n_pairs; ++t) {
+        const vapor_pair& a = pairs[t];
+        int64_t* s = stats + 16 * t;
+        auto refuse = [&](int code) {
+            for (int q = 0; q < 16; ++q) s[q] = 0;
+            s[1] = s[2] = -1;
+            s[15] = code;
+        };
+        const bool inv = !(a.flags & VAPOR_PF_FORWARD);
+        auto no_bytes = [&](int32_t q) {          // a symbol outside the alphabet whose byte was not kept
+            return set->h[q].n_invalid > 0 && (q >= (int32_t)set->raw_off.size() || set->raw_off[q] < 0);
+        };
+        int64_t n = 0;
+        if (a.seq1 < 0 || a.seq1 >= set->n || a.seq2 < 0 || a.seq2 >= set->n || a.off2 < 0 || a.k < 1 || a.k > VAPOR_MAX_ANY_K) {
+            refuse(VAPOR_E_ARG);
+        } else if (set->h[a.seq1].len > VAPOR_MAX_WIDE_SEQ_LEN || set->h[a.seq2].len > VAPOR_MAX_WIDE_SEQ_LEN) {
+            refuse(VAPOR_E_ARG);
+        } else if (inv && set->h[a.seq1].len - a.k + 1 > 0 && set->h[a.seq1].n_invalid > 0) {
+            refuse(VAPOR_E_KEYERROR);
+        } else if (!inv && (no_bytes(a.seq1) || no_bytes(a.seq2))) {
+            refuse(VAPOR_E_ARG);
+        } else {
+            const SeqDesc& s1 = set->h[a.seq1];
+            const SeqDesc& s2 = set->h[a.seq2];
+            const int n2 = std::max(0, s2.len - a.off2);
+            const int nk1 = s1.len - a.k + 1, nk2 = n2 - a.k + 1;
+            WIDE_CHK(hipMemcpyAsync(b.p[WideBufs::ACC], &init, sizeof(WideAcc), hipMemcpyHostToDevice, st));
+            if (nk1 > 0 && nk2 > 0) {
+                const size_t o_r1 = anyk_pad(s1.len), o_s2 = o_r1 + (inv ? anyk_pad(s1.len) : 0);
+                WIDE_CHK(x.ensure(AnykBufs::SYM, o_s2 + anyk_pad(n2)));
+                uint8_t* sym = x.at<uint8_t>(AnykBufs::SYM);
+                const uint32_t* x4_1 = set->d_x4 + (size_t)s1.chunk0 * 4;
+                const uint32_t* x4_2 = set->d_x4 + (size_t)s2.chunk0 * 4;
+                const uint8_t* raw1 = !inv && s1.n_invalid > 0 ? set->d_raw + set->raw_off[a.seq1] : nullptr;
+                const uint8_t* raw2 = s2.n_invalid > 0 && a.seq2 < (int32_t)set->raw_off.size() && set->raw_off[a.seq2] >= 0
+                                          ? set->d_raw + set->raw_off[a.seq2] : nullptr;
+                hipLaunchKernelGGL(anyk_sym_kernel, dim3(wide_grid(s1.len)), dim3(256), 0, st, x4_1, raw1, (int)(s1.flags & 1u), 0, s1.len,
+                                   sym, inv ? sym + o_r1 : (uint8_t*)nullptr);
+                // (with inversions a symbol of seq2 outside the alphabet matches nothing: it stays 0xFF)
+                hipLaunchKernelGGL(anyk_sym_kernel, dim3(wide_grid(n2)), dim3(256), 0, st, x4_2, inv ? (const uint8_t*)nullptr : raw2,
+                                   (int)(s2.flags & 1u), a.off2, n2, sym + o_s2, (uint8_t*)nullptr);
+                const AnykSrc src{sym, sym + o_r1, sym + o_s2, s1.len, a.k, inv ? 1 : 0};
+                WIDE_CHK(anyk_count(x, st, src, nk1, nk2));
+                long long total = 0;
+                WIDE_CHK(hipMemcpyAsync(&total, x.at<long long>(AnykBufs::OFF) + nk2, sizeof(long long), hipMemcpyDeviceToHost, st));
+                WIDE_CHK(hipStreamSynchronize(st));
+                if (total > ctx->max_pair_cap) {
+                    // more dots than a pair may hold ("max_pair_cap"): the pair keeps VAPOR_E_OVERFLOW with its count
+                    refuse(VAPOR_E_OVERFLOW);
+                    s[0] = total;
+                    s[14] = total;
+                    if (hit_off) hit_off[t + 1] = running;
+                    continue;
+                }
+                n = total;
+                WIDE_CHK(b.ensure(WideBufs::DOTS, sizeof(int2) * (size_t)n));
+                WIDE_CHK(b.ensure(WideBufs::FL, (size_t)n));
+                if (n) {
+                    anyk_emit(x, st, src, nk1, nk2, b.at<int2>(WideBufs::DOTS));
+                    WIDE_CHK(hipGetLastError());
+                    WIDE_CHK(wide_clean(b, st, (int)n, nk1 - 1, nk2 - 1, a.flags));
+                }
+            }
+            WideAcc res;
+            WIDE_CHK(hipMemcpyAsync(&res, b.p[WideBufs::ACC], sizeof(WideAcc), hipMemcpyDeviceToHost, st));
+            if (hits_ji && n && running + n <= hits_capacity)
+                WIDE_CHK(hipMemcpyAsync(hits_ji + 2 * running, b.p[WideBufs::DOTS], sizeof(int2) * (size_t)n, hipMemcpyDeviceToHost, st));
+            WIDE_CHK(hipStreamSynchronize(st));
+            wide_stats(res, n, a.flags, s);
+        }
+        running += n;
+        if (hit_off) hit_off[t + 1] = running;
+    }
+    if (hits_ji && running > hits_capacity)
+        return fail(VAPOR_E_OVERFLOW, "vapor_anyk_batch: hits_capacity too small (hit_off[n_pairs] holds the count needed)");
     return VAPOR_OK;
 }
 

@@ -501,6 +501,39 @@ class Engine:
             out.append(h[np.lexsort((h[:, 1], h[:, 0]))])
         return st[:n], out
 
+    # ---- the any-k route: kmerhits at every k from 1 to MAX_ANY_K ----
+    def anyk_available(self) -> bool:
+        """Whether the loaded library has the any-k route (the CPU twin of the C ABI has not)."""
+        try:
+            self._wide_entry("vapor_anyk_batch")
+        except NotImplementedError:
+            return False
+        return True
+
+    def score_anyk(self, seqset: SeqSet, pairs: np.ndarray, want_hits: bool = False):
+        """Statistics (n,16) of every pair on the any-k route (vapor_anyk_batch: k from 1 to MAX_ANY_K, PF_FORWARD for
+        kmerhits(..., inversions=False)); with want_hits also, per pair, the (n,2) [j,i] hit array in the reference's order."""
+        fn = self._wide_entry("vapor_anyk_batch")
+        pairs = np.ascontiguousarray(pairs, dtype=L.PAIR_DTYPE)
+        n = len(pairs)
+        st = np.zeros((max(n, 1), 16), dtype=np.int64)
+        off = np.zeros(n + 1, dtype=np.int64)
+        pp = pairs.ctypes.data if n else None
+        if not want_hits:
+            L.check(fn(self._ctx, seqset._h, n, pp, L.ptr(st, ctypes.c_int64), None, 0, L.ptr(off, ctypes.c_int64)))
+            return st[:n]
+        cap = 1 << 16
+        while True:
+            hits = np.zeros((cap, 2), dtype=np.int32)
+            rc = fn(self._ctx, seqset._h, n, pp, L.ptr(st, ctypes.c_int64), L.ptr(hits, ctypes.c_int32), cap,
+                    L.ptr(off, ctypes.c_int64))
+            if rc == L.E_OVERFLOW and int(off[n]) > cap:
+                cap = int(off[n])
+                continue
+            L.check(rc)
+            break
+        return st[:n], [hits[off[t]:off[t + 1]].copy() for t in range(n)]
+
     def clean_hits_wide(self, lists: Sequence[np.ndarray], flags: Optional[Sequence[int]] = None):
         """clean_hits for lists with coordinates up to MAX_WIDE_SEQ_LEN (vapor_clean_hits_wide)."""
         fn = self._wide_entry("vapor_clean_hits_wide")

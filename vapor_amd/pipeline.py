@@ -249,21 +249,46 @@ def has_wide(engine) -> bool:
     return bool(avail()) if callable(avail) else True
 
 
+def has_anyk(engine) -> bool:
+    """Whether `engine` has the any-k route (window sizes 1 .. MAX_ANY_K, the reference's kmerhits at every k): a score_anyk
+    method, and - for an engine that can say so (Engine.anyk_available) - a library that has the route."""
+    if not callable(getattr(engine, "score_anyk", None)):
+        return False
+    avail = getattr(engine, "anyk_available", None)
+    return bool(avail()) if callable(avail) else True
+
+
+def check_any_k(k) -> int:
+    """The window size as an int, or the ValueError that names the any-k route's limit."""
+    k = int(k)
+    if not 1 <= k <= L.MAX_ANY_K:
+        raise ValueError("window size %d outside 1 .. %d (VAPOR_MAX_ANY_K)" % (k, L.MAX_ANY_K))
+    return k
+
+
 def score_requests(engine, reqs: Sequence[Score]) -> List[object]:
     """Evaluates every Score request (_score_requests_narrow); the requests that route refuses for a window, allele or read
-    longer than MAX_SEQ_LEN are scored again on the wide route (score_requests_wide) when the engine has one, in place."""
+    longer than MAX_SEQ_LEN are scored again on the wide route (score_requests_wide) when the engine has one, in place, and
+    those with a window size other than 10/20/30/40 on the any-k route when the engine has that."""
     out = _score_requests_narrow(engine, reqs)
     if has_wide(engine):
         redo = [t for t, v in enumerate(out) if isinstance(v, ValueError) and not k_unsupported(reqs[t].k)]
         if redo:
             for t, v in zip(redo, score_requests_wide(engine, [reqs[t] for t in redo])):
                 out[t] = v
+    if has_anyk(engine):
+        redo = [t for t, v in enumerate(out) if isinstance(v, ValueError) and k_unsupported(reqs[t].k)
+                and 1 <= int(reqs[t].k) <= L.MAX_ANY_K]
+        if redo:
+            for t, v in zip(redo, score_requests_wide(engine, [reqs[t] for t in redo], anyk=True)):
+                out[t] = v
     return out
 
 
-def score_requests_wide(engine, reqs: Sequence[Score]) -> List[object]:
+def score_requests_wide(engine, reqs: Sequence[Score], anyk: bool = False) -> List[object]:
     """score_requests on the wide route: the pairs' statistics from engine.score_wide, the per-read scores and the deletion
-    rule (SF:1718-1726) on the host in float64 (vapor_amd.finish), as the device's finish kernel computes them."""
+    rule (SF:1718-1726) on the host in float64 (vapor_amd.finish), as the device's finish kernel computes them.  anyk: the
+    statistics from engine.score_anyk instead (any window size from 1 to MAX_ANY_K)."""
     from . import finish
     seqs: List[str] = []
     upper: List[bool] = []
@@ -295,7 +320,7 @@ def score_requests_wide(engine, reqs: Sequence[Score]) -> List[object]:
         per_req.append(reads)
     ss = engine.seqset(seqs, upper)
     try:
-        st = engine.score_wide(ss, engine.make_pairs(rows))
+        st = (engine.score_anyk if anyk else engine.score_wide)(ss, engine.make_pairs(rows))
     finally:
         ss.close()
     out: List[object] = []
@@ -502,12 +527,15 @@ def scorer_outputs(engine, kind: str, ref_seq: str, alt_seq: str, x, k):
     (kind 's1', 's2', 's3'; SF:182-203, 277-294, 241-257) for one read: the two dot plots' statistics from the
     device, the scorer's own gates and ratios on the host in float64 (vapor_amd.finish)."""
     from . import finish
+    anyk = k_unsupported(k) and has_anyk(engine)
+    if anyk:
+        k = check_any_k(k)
     up = kind == "s1"
     ss = engine.seqset([x[0], ref_seq, alt_seq], [False, up, up])
     wide = has_wide(engine) and max(len(x[0]), len(ref_seq), len(alt_seq)) > L.MAX_SEQ_LEN
     try:
         pr = engine.make_pairs([(0, 1, int(x[1]), int(k), _FLAGS[kind]), (0, 2, int(x[1]), int(k), _FLAGS[kind])])
-        st = engine.score_wide(ss, pr) if wide else engine.score(ss, pr)
+        st = engine.score_anyk(ss, pr) if anyk else engine.score_wide(ss, pr) if wide else engine.score(ss, pr)
     finally:
         ss.close()
     _raise_for_status(st[0])

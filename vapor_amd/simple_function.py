@@ -38,11 +38,63 @@ def set_figure_function(fn) -> None:
 def dotdata(kmerlen, seq1, seq2):
     """SF:545-549: [(pos_in_seq2, pos_in_seq1), ...] in the reference's order."""
     eng = pipeline.get_engine()
+    if pipeline.k_unsupported(kmerlen) and pipeline.has_anyk(eng):
+        return kmerhits(seq1, seq2, kmerlen, 1, True)
     ss = eng.seqset([seq1, seq2])
     wide = pipeline.has_wide(eng) and max(len(seq1), len(seq2)) > L.MAX_SEQ_LEN
     try:
         pr = eng.make_pairs([(0, 1, 0, int(kmerlen), 0)])
         st, hits = eng.score_wide(ss, pr, want_hits=True) if wide else eng.dotplots(ss, pr)
+    finally:
+        ss.close()
+    pipeline._raise_for_status(st[0])
+    return [(int(j), int(i)) for j, i in hits[0]]
+
+
+_KEY_FOLD = str.maketrans("RrYySsWwKkMmBbDdHhVv", "NnNnNnNnNnNnNnNnNnNn")
+
+
+def key_modify(key):
+    """SF:908-949: the IUPAC ambiguity codes folded to N (n in lower case)."""
+    return key.translate(_KEY_FOLD)
+
+
+def subkeys(key, nth_base, inversions):
+    """SF:1403-1422 (host strings; every nth_base, 0 keeping the first two bases of each codon)."""
+    key = key_modify(key)
+    keylen = len(key)
+    if nth_base == 1:
+        out = [key]
+    elif nth_base != 0:
+        out = ["".join(key[j] for j in range(keylen) if j % nth_base == k) for k in range(nth_base)]
+    else:
+        out = ["".join(key[i] for i in range(keylen) if i % 3 != 2)]
+    if inversions:
+        out += ["".join(invert_base[c] for c in reversed(s)) for s in out]
+    return out
+
+
+def kmerhits(seq1, seq2, kmerlen, nth_base=1, inversions=False):
+    """SF:951-983 on the any-k route: [(pos_in_seq2, pos_in_seq1), ...] in the reference's order, for k from 1 to
+    MAX_ANY_K (k > 40: the edit-distance branch, keys within k // 10 edits).  nth_base must be 1.  Unlike the reference,
+    nothing is printed for k > 40."""
+    if nth_base != 1:
+        raise ValueError("kmerhits: nth_base must be 1 on the device (got %r)" % (nth_base,))
+    k = pipeline.check_any_k(kmerlen)
+    if max(len(seq1), len(seq2)) > L.MAX_WIDE_SEQ_LEN:
+        raise ValueError("kmerhits: sequence longer than %d bases (VAPOR_MAX_WIDE_SEQ_LEN)" % L.MAX_WIDE_SEQ_LEN)
+    if not inversions:
+        for s in (seq1, seq2):
+            if isinstance(s, str) and not s.isascii():
+                try:
+                    s.encode("latin-1")
+                except UnicodeEncodeError:
+                    raise ValueError("kmerhits: characters outside Latin-1 cannot be compared byte for byte") from None
+    eng = pipeline.get_engine()
+    ss = eng.seqset([seq1, seq2])
+    try:
+        pr = eng.make_pairs([(0, 1, 0, k, 0 if inversions else L.PF_FORWARD)])
+        st, hits = eng.score_anyk(ss, pr, want_hits=True)
     finally:
         ss.close()
     pipeline._raise_for_status(st[0])
