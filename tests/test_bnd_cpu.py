@@ -1,0 +1,239 @@
+"""`vapor vcf --bnd` on the host: the breakend ALT parser, which records are taken, mates and keys, the alleles
+of the scored views against slices of the world's FASTA, and the command line with device work answered by
+tests/fake_engine.py (oracle-backed, test only) - scores against tests/golden/bnd.json.gz (tools/gen_bnd_golden.py: the
+reference's own scorers on the same windows), and every non-breakend row and annotation unchanged by the option."""
+import numpy as np
+import pytest
+
+from conftest import load_golden
+from fake_engine import FakeEngine
+from vapor_amd import cli, drivers, pipeline, seqio, synth
+from vapor_amd import simple_function as SF
+
+BND = load_golden("bnd.json.gz")
+F = 500
+
+
+@pytest.fixture()
+def fake(oracle):
+    pipeline.set_engine(FakeEngine(oracle))
+    yield
+    pipeline.set_engine(None)
+    seqio.set_backend(None)
+
+
+@pytest.mark.parametrize("alt, exp", [
+    ("N[c2:100[", ("3to5", "c2", 100, "")),
+    ("N]c2:100]", ("3to3", "c2", 100, "")),
+    ("]c2:100]N", ("5to3", "c2", 100, "")),
+    ("[c2:100[N", ("5to5", "c2", 100, "")),
+    ("GACG[chr5:1200[", ("3to5", "chr5", 1200, "ACG")),
+    ("GTT]chr5:1200]", ("3to3", "chr5", 1200, "TT")),
+    ("]chr5:1200]CAG", ("5to3", "chr5", 1200, "CA")),
+    ("[chr5:1200[CAG", ("5to5", "chr5", 1200, "CA")),
+    ("acg[c2:7[", ("3to5", "c2", 7, "cg")),
+    ("]c2:7]tn", ("5to3", "c2", 7, "t")),
+    ("T[HLA-A*01:01:01:01:33[", ("3to5", "HLA-A*01:01:01:01", 33, "")),
+    (".A", "single breakend"), ("A.", "single breakend"), (".ACGT", "single breakend"),
+    ("N[c2:1[,N[c3:5[", "several ALTs"), ("<BND>", "malformed ALT"), ("N", "malformed ALT"),
+    ("N[c2:100]", "malformed ALT"), ("[c2:100[", "malformed ALT"), ("N[c2:0[", "malformed ALT"), ("N[c2[", "malformed ALT"),
+    ("N[c2:x[", "malformed ALT"), ("]c2:100", "malformed ALT"), ("N[c2:10[A", "malformed ALT"), ("N.[c2:10[", "malformed ALT"),
+])
+def test_alt_parser(alt, exp):
+    assert cli.bnd_alt(alt) == exp
+
+
+def test_views_mirror_5to3_and_skip_5to5():
+    assert cli.bnd_view("c1", 1000, "A[c5:1200[") == ["c1", 1000, "c5", 1200, "3to5", ""]
+    assert cli.bnd_view("c1", 1000, "AGG]c5:1200]") == ["c1", 1000, "c5", 1200, "3to3", "GG"]
+    # ]B:q]t at A:p is t[A:p[ at B:q: the same junction, its insertion t[:-1]
+    assert cli.bnd_view("c1", 1000, "]c5:1200]GGA") == ["c5", 1200, "c1", 1000, "3to5", "GG"]
+    assert cli.bnd_key(cli.bnd_view("c1", 1000, "]c5:1200]A")) == cli.bnd_key(cli.bnd_view("c5", 1200, "T[c1:1000[")) \
+        == "c5:1200:c1:1000:3to5:BND"
+    assert "5to5" in cli.bnd_view("c1", 1000, "[c5:1200[A")
+    assert cli.bnd_key(["chr1", 1000, "chr5", 1200, "3to5", "ACG"]) == "chr1:1000:chr5:1200:3to5:BND"
+
+
+def _two_contig_world():
+    w = synth.SynthWorld()
+    rng = np.random.default_rng(3)
+    for c in ("c1", "c2", "c3"):
+        w.contigs[c] = synth.random_dna(rng, 4000)
+        w.reads[c] = []
+    return w
+
+
+def test_records_taken_paired_and_skipped(tmp_path, capsys):
+    rows = [
+        ("c1", 1000, "b1", "N[c2:1200[", "SVTYPE=BND;MATEID=b2"),          # 0 taken
+        ("c1", 500, "x1", "<DEL>", "SVTYPE=DEL;END=900"),                  # 1 a deletion
+        ("c2", 1200, "b2", "]c1:1000]N", "SVTYPE=BND;MATEID=b1"),          # 2 its mate: scored at 0
+        ("c1", 2000, "b3", "N]c3:700]", "SVTYPE=bnd;MATE_ID=b4"),          # 3 taken (3to3)
+        ("c3", 700, "b4", "N]c1:2000]", "SVTYPE=BND;MATE_ID=b3"),          # 4 its mate: another view, same locus
+        ("c2", 300, "b5", "]c3:900]N", "SVTYPE=BND"),                     # 5 no mate: its mirror on its own
+        ("c3", 900, "b6", "N[c2:300[", "SVTYPE=BND"),                     # 6 the same key, no MATEID: scored once
+        ("c1", 3000, "b7", "[c2:50[N", "SVTYPE=BND;MATEID=b8"),           # 7 5to5: skipped
+        ("c1", 3100, "b9", ".N", "SVTYPE=BND"),                           # 8 single breakend
+        ("c1", 3200, "b10", "N[c2:5[,N[c3:5[", "SVTYPE=BND"),             # 9 several ALTs
+        ("c1", 3300, "b11", "N[c2:5", "SVTYPE=BND"),                      # 10 malformed
+        ("c1", 3400, "b12", "N[chrZ:5[", "SVTYPE=BND"),                   # 11 contig not in the .fai
+        ("c1", 3500, "b13", "N[c2:5[", "SVTYPE=BND;Other=ab/ab_b/b^_c1:1:2:3"),   # 12 the reference's CANNOT_CLASSIFY branch
+        ("c1", 3600, "b14", "N[c2:5[", "MERGE_TYPE=BND"),                 # 13 MERGE_TYPE= is SVTYPE=
+    ]
+    vcf = tmp_path / "in.vcf"
+    vcf.write_text("".join("%s\t%d\t%s\tN\t%s\t.\tPASS\t%s\tGT\t0/1\n" % r for r in rows))
+    seqio.set_backend(seqio.MemorySamtools(_two_contig_world()))
+    try:
+        off, off_keys = cli.vcf_list_readin(str(vcf))
+        capsys.readouterr()
+        on, on_keys = cli.vcf_list_readin(str(vcf), "ref.fa")
+        err = capsys.readouterr().err.splitlines()
+    finally:
+        seqio.set_backend(None)
+    assert "BND" not in off and set(off) == {"DEL", "Other"}
+    assert list(on)[-1] == "BND" and {k: v for k, v in on.items() if k != "BND"} == off
+    assert on["BND"] == [["c1", 1000, "c2", 1200, "3to5", ""], ["c1", 2000, "c3", 700, "3to3", ""],
+                         ["c3", 900, "c2", 300, "3to5", ""], ["c1", 3600, "c2", 5, "3to5", ""]]
+    k1, k2, k3, k4 = [cli.bnd_key(v) for v in on["BND"]]
+    assert on_keys == {**off_keys, 0: k1, 2: k1, 3: k2, 4: k2, 5: k3, 6: k3, 13: k4}
+    assert k1 == "c1:1000:c2:1200:3to5:BND" and k3 == "c3:900:c2:300:3to5:BND"
+    assert len(err) == 5
+    for line, why in zip(err, ("5to5", "single breakend", "several ALTs", "malformed ALT", "contig chrZ not in the .fai")):
+        assert "skipped" in line and why in line, (line, why)
+
+
+def test_jobs_keys_figure_names_and_cost():
+    vl = {"BND": [["c1", 1000, "c5", 1200, "3to5", "AC"], ["c1", 20, "c5", 30, "3to3", ""]]}
+    jobs = cli.vcf_jobs(vl, 3, "x.bam", "ref.fa", "/o/", "s")
+    assert [j.key for j in jobs] == ["c1:1000:c5:1200:3to5:BND", "c1:20:c5:30:3to3:BND"]
+    assert all(j.spec is None for j in jobs)              # (no array-route spec: the drivers' route)
+    assert cli.job_cost("BND", 0) == cli.job_cost("DEL", 20000) == jobs[0].cost
+    gen = jobs[0].make()
+    assert gen.gi_code is drivers.vapor_bnd.__code__
+    assert gen.gi_frame.f_locals["out_figure_name"] == "/o/s.BND.c1__1000__c5__1200__3to5__BND.png"
+
+
+def test_parser_takes_the_option():
+    assert cli.build_parser().parse_args(["--sv-input", "a", "--reference", "r", "--pacbio-input", "b", "--output-path", "o",
+                                          "--output-file", "f", "--bnd"]).bnd is True
+
+
+def _requests(view, world):
+    """The ref window and alt allele vapor_bnd hands to the scorer (k answered 10, the scores None)."""
+    seqio.set_backend(seqio.MemorySamtools(world))
+    try:
+        gen = drivers.vapor_bnd(3, 1, "x.bam", "ref.fa", view, "f.png")
+        req = next(gen)
+        while not isinstance(req, drivers.Score):
+            req = gen.send([10] if isinstance(req, drivers.Window) else None)
+        return req
+    finally:
+        seqio.set_backend(None)
+
+
+@pytest.mark.parametrize("case", [c for c in BND["cases"] if "alt_seq" in c], ids=lambda c: c["key"])
+def test_alleles_are_slices_of_the_fasta(case):
+    """§7: ref window R(A, p-F, p+F); alt R(A, p-F, p) + ins + R(B, q-1, q-1+F) ('3to5') or + rc(R(B, q-F, q)) ('3to3'), as a
+    derived sequence (segments, not a Python string of its own)."""
+    w = synth.world_from_json(BND["world"])
+    a, p, b, q, ct, ins = case["view"]
+    A, B = w.contigs[a], w.contigs[b]
+    req = _requests(case["view"], w)
+    assert req.kind == "s2" and req.ref_seq == A[p - F - 1:p + F] == case["ref_seq"]
+    right = B[q - 2:q - 1 + F] if ct == "3to5" else synth.revcomp(B[q - F - 1:q])
+    assert req.alt_seq == A[p - F - 1:p] + ins + right == case["alt_seq"]
+    assert req.alt_seq.segs is not None and req.alt_seq.segs[0][0] is req.ref_seq
+    assert [x[3] for x in req.alt_seq.segs] == [False] + ([False] if ins else []) + [ct == "3to3"]
+    assert [r[0] for r in req.reads] == [r[0] for r in case["reads"]]
+
+
+def test_3to5_is_the_long_deletion_branch():
+    """t[A:e+1[ at A:s asks for exactly what the DEL [A, s, e] asks for on the long-deletion branch (SF:1727-1745)."""
+    w = synth.make_world(seed=31, n_loci=2, svtypes=("DEL",), spans=(12000, 15500), read_len=1500, n_reads=6)
+    for l in w.loci:
+        seqio.set_backend(seqio.MemorySamtools(w))
+        try:
+            d, b = drivers.vapor_simple_del(3, 1, "x.bam", "ref.fa", [l.chrom, l.start, l.end], "f.png"), \
+                drivers.vapor_bnd(3, 1, "x.bam", "ref.fa", [l.chrom, l.start, l.chrom, l.end + 1, "3to5", ""], "f.png")
+            rd, rb = next(d), next(b)
+            while True:
+                assert type(rd) is type(rb)
+                if isinstance(rd, drivers.Window):
+                    assert rd.seq == rb.seq and getattr(rd.seq, "segs", None) == getattr(rb.seq, "segs", None)
+                    rd, rb = d.send([10]), b.send([10])
+                elif isinstance(rd, drivers.Score):
+                    assert (rd.kind, rd.ref_seq, rd.alt_seq, rd.k) == (rb.kind, rb.ref_seq, rb.alt_seq, rb.k)
+                    assert rd.reads == rb.reads and rd.alt_seq.segs == rb.alt_seq.segs
+                    rd, rb = d.send([0.5] * len(rd.reads)), b.send([0.5] * len(rb.reads))
+                else:
+                    assert rd.name == "f.png" and rd.scores == rb.scores
+                    break
+        finally:
+            seqio.set_backend(None)
+
+
+def test_golden_scores_on_the_cpu_oracle(fake):
+    """Every scored view of the translocation world through vapor_bnd gives the reference's per-read scores."""
+    w = synth.world_from_json(BND["world"])
+    seqio.set_backend(seqio.MemorySamtools(w))
+    for c in BND["cases"]:
+        got = pipeline.run_sync(drivers.vapor_bnd(3, 1, "x.bam", "ref.fa", list(c["view"]), "f.png"))
+        assert [float(v) for v in got] == [float(v) for v in c["scores"]], c["key"]
+    assert len([c for c in BND["cases"] if c["scores"]]) >= 5
+
+
+def _golden_vcf_case():
+    from test_host_cpu import VCF
+    return [c for c in VCF if not c["header"] and all("ok" in p["scores"] for p in c["per_record"])][0]
+
+
+def _run_vcf(tmp_path, name, text, bnd, monkeypatch):
+    """cli.main vcf; returns (the 6-column table as written, the annotated VCF)."""
+    d = tmp_path / name
+    d.mkdir()
+    vcf = d / "in.vcf"
+    vcf.write_text(text)
+    seen = {}
+    orig = SF.vcf_vapor_modify
+
+    def keep_table(vcf_input, rec_new, *a):
+        seen["table"] = open(vcf_input + ".vapor").read()
+        return orig(vcf_input, rec_new, *a)
+    monkeypatch.setattr(SF, "vcf_vapor_modify", keep_table)
+    args = ["vcf", "--sv-input", str(vcf), "--reference", "ref.fa", "--pacbio-input", "x.bam", "--output-path", str(d / "figs"),
+            "--output-file", "unused", "--no-figures"] + (["--bnd"] if bnd else [])
+    assert cli.main(args) == 0
+    return seen["table"], (d / "in.vcf.vapor").read_text()
+
+
+def test_mixed_vcf_unchanged_without_the_option_and_other_rows_unchanged_with_it(fake, tmp_path, monkeypatch):
+    """A reference-pinned VCF (tests/golden/locus_vcf.json.gz) with the breakend records of the translocation world put in
+    between its records: without --bnd the annotated VCF is the reference's byte for byte; with it every other row and
+    annotation is the same, the breakend rows come last and both mates of a scored pair carry the annotation."""
+    from test_host_cpu import _vcf_world
+    case = _golden_vcf_case()
+    world = _vcf_world(case)
+    bw = synth.world_from_json(BND["world"])
+    world.contigs.update(bw.contigs)
+    world.reads.update(bw.reads)
+    seqio.set_backend(seqio.MemorySamtools(world))
+    plain = case["vcf"].splitlines()
+    brec = BND["vcf"].splitlines()
+    mixed = []
+    for t in range(max(len(plain), len(brec))):
+        mixed += plain[t:t + 1] + brec[t:t + 1]
+    text = "\n".join(mixed) + "\n"
+    t0, v0 = _run_vcf(tmp_path, "plain", case["vcf"], False, monkeypatch)
+    t1, v1 = _run_vcf(tmp_path, "mixed_off", text, False, monkeypatch)
+    assert v0 == v1 == case["final"]
+    assert t1 == t0
+    t2, v2 = _run_vcf(tmp_path, "mixed_on", text, True, monkeypatch)
+    rows = t2.splitlines()
+    assert t2.startswith(t0) and all(":BND\t" in r for r in rows[len(t0.splitlines()):])
+    assert [r.split("\t")[0] for r in rows[len(t0.splitlines()):]] == [c["key"] for c in BND["cases"]]
+    assert "\n".join(rows[len(t0.splitlines()):]) + "\n" == BND["vapor_text"].split("\n", 1)[1]
+    is_bnd = lambda line: "SVTYPE=BND" in line        # noqa: E731
+    assert [x for x in v2.splitlines() if not is_bnd(x)] == v0.splitlines()
+    got_b = [x for x in v2.splitlines() if is_bnd(x)]
+    assert got_b == [x for x in BND["final"].splitlines() if is_bnd(x)]
+    assert len(got_b) == 2 * len(BND["cases"]) and all(";VaPor_GS=" in x for x in got_b)

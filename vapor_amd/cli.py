@@ -7,7 +7,7 @@ to the GPU together.  With more than one rank (torchrun), loci are sharded acros
 the node and the per-locus rows are all-gathered (vapor_amd.dist).
 
 Extra flags (not in the reference): --no-figures (skip the recurrence-plot PNGs),
---chunk (loci per device batch).
+--chunk (loci per device batch), --bnd (vcf: score breakend records as well).
 """
 from __future__ import annotations
 
@@ -91,11 +91,13 @@ def dup_inv_interprete(pin):
     return 'error'
 
 
-def vcf_list_readin(file_in):
+def vcf_list_readin(file_in, bnd_ref=None):
     """vapor_vali/vapor:127-202: records bucketed by type in first-seen order, plus
-    {file line index: key} for the INFO rewrite."""
+    {file line index: key} for the INFO rewrite.  `bnd_ref` (the reference FASTA, `vapor vcf --bnd`): breakend records are
+    read as well, into a 'BND' bucket that comes last (bnd_view); without it they take the reference's last branch."""
     out = {}
     rec_hash = {}
+    bnd = _BndReader(bnd_ref) if bnd_ref is not None else None
     rec = -1
     # `x not in out[T]` of the reference scans the bucket's list (every record against every earlier one of its type: minutes
     # on a call set of 10^5); the same test from a set of the entries as tuples beside each list
@@ -160,6 +162,9 @@ def vcf_list_readin(file_in):
             elif t in ['CNV', 'CSV', 'CPX']:
                 continue
             else:
+                if bnd is not None and t in ('BND', 'bnd') and 'Other=' not in pin[7] and 'OTHER=' not in pin[7]:
+                    bnd.take(rec, pin, rec_hash)
+                    continue
                 if 'Other=' in pin[7]:
                     info = [i for i in pin[7].split(';') if i[:6] == 'Other=']
                 elif 'OTHER=' in pin[7]:
@@ -171,7 +176,107 @@ def vcf_list_readin(file_in):
                 out.setdefault('Other', [])
                 if new('Other', item):
                     rec_hash[rec] = ':'.join([str(i) for i in item + ['CANNOT_CLASSIFY']])
+    if bnd is not None and bnd.loci:
+        out['BND'] = bnd.loci
     return [out, rec_hash]
+
+
+# ------------------------------------------------------------------------------------------
+# breakends (`vapor vcf --bnd`; not in the reference: DESIGN.md §7)
+# ------------------------------------------------------------------------------------------
+
+def bnd_alt(alt: str):
+    """The ALT of a breakend record in one of the four VCF 4.x forms: (CT, B, q, inserted bases), or the reason it is not one.
+    `t[B:q[` 3to5 and `t]B:q]` 3to3 insert t[1:], `]B:q]t` 5to3 and `[B:q[t` 5to5 insert t[:-1] (t: the mate's REF base and
+    the bases inserted between the two pieces)."""
+    if ',' in alt:
+        return 'several ALTs'
+    if '[' not in alt and ']' not in alt:
+        return 'single breakend' if len(alt) >= 2 and (alt[0] == '.' or alt[-1] == '.') else 'malformed ALT'
+    c0, c1 = alt[0], alt[-1]
+    if c0 in '[]':
+        j = alt.find(c0, 1)
+        if j < 0:
+            return 'malformed ALT'
+        inner, t = alt[1:j], alt[j + 1:]
+        ct, ins = ('5to3' if c0 == ']' else '5to5'), t[:-1]
+    elif c1 in '[]':
+        i = alt.find(c1)
+        if i == len(alt) - 1:
+            return 'malformed ALT'
+        t, inner = alt[:i], alt[i + 1:-1]
+        ct, ins = ('3to5' if c1 == '[' else '3to3'), t[1:]
+    else:
+        return 'malformed ALT'
+    b, _, q = inner.rpartition(':')
+    if not (t and t.isascii() and t.isalpha() and b and '[' not in b and ']' not in b and q.isascii() and q.isdigit()
+            and int(q) >= 1):
+        return 'malformed ALT'
+    return ct, b, int(q), ins
+
+
+def bnd_view(chrom: str, pos: int, alt: str):
+    """The scored view of a breakend record at chrom:pos - [A, p, B, q, CT, inserted bases] with CT '3to5' or '3to3', the
+    left-hand piece's reads clipped on the right at A:p - or the reason it is skipped.  A `5to3` record is scored as its mirror
+    `t[A:p[` at B:q (the same junction); a `5to5` record has no such view."""
+    got = bnd_alt(alt)
+    if isinstance(got, str):
+        return got
+    ct, b, q, ins = got
+    if ct == '5to5':
+        return '5to5 junction: its reads are clipped on the left, which the read model (SF:339-354) does not take'
+    if ct == '5to3':
+        return [b, q, chrom, int(pos), '3to5', ins]
+    return [chrom, int(pos), b, q, ct, ins]
+
+
+def bnd_key(view) -> str:
+    """A:p:B:q:CT:BND of a scored view (a `5to3` record and its `3to5` mate share it)."""
+    return ':'.join([str(i) for i in view[:5]] + ['BND'])
+
+
+def _mate_id(info: str):
+    for x in info.split(';'):
+        if x[:7] == 'MATEID=' or x[:8] == 'MATE_ID=':
+            return x.split('=', 1)[1]
+    return None
+
+
+class _BndReader:
+    """vcf_list_readin's breakend records: one locus per key, in first-seen order (as the reference de-duplicates sv_pos);
+    mates (MATEID / MATE_ID) are scored once, at the record that comes first, and every record taken carries its locus's key
+    in rec_hash, so that both mates get the annotation.  A skipped record gets one line on stderr and no row."""
+
+    def __init__(self, ref):
+        from . import seqio
+        self.chromos = seqio.chromos_readin(ref)
+        self.loci, self.keys = [], set()
+        self.by_id, self.by_mate = {}, {}
+
+    def take(self, rec, pin, rec_hash):
+        alt = pin[4] if len(pin) > 4 else ''
+        view = bnd_view(pin[0], int(pin[1]), alt)
+        if not isinstance(view, str):
+            miss = [c for c in (view[0], view[2]) if c not in self.chromos]
+            if miss:
+                view = 'contig %s not in the .fai' % miss[0]
+        if isinstance(view, str):
+            print('vapor vcf --bnd: record %s:%s %s skipped: %s' % (pin[0], pin[1], alt, view), file=sys.stderr)
+            return
+        rid, mate = pin[2] if len(pin) > 2 else '.', _mate_id(pin[7])
+        key = self.by_id.get(mate) if mate else None
+        if key is None and rid != '.':
+            key = self.by_mate.get(rid)
+        if key is None:
+            key = bnd_key(view)
+            if key not in self.keys:
+                self.keys.add(key)
+                self.loci.append(view)
+        rec_hash[rec] = key
+        if rid != '.':
+            self.by_id.setdefault(rid, key)
+        if mate:
+            self.by_mate.setdefault(mate, key)
 
 
 # ------------------------------------------------------------------------------------------
@@ -213,7 +318,9 @@ def job_cost(svtype: str, span: int, extra: int = 0) -> float:
     span = max(int(span), 0)
     f = min(500, span) if span > 0 else 500
     short = span < drivers.default_max_sv_test
-    if svtype == 'DEL':
+    if svtype == 'BND':                     # a breakend: the windows of a long deletion's junction (drivers.vapor_bnd)
+        lr, la = 2 * 500, 4 * 500
+    elif svtype == 'DEL':
         lr, la = 2 * f, ((span + 2 * f) + 2 * f if short else 4 * f)
     elif svtype == 'INV':
         lr, la = (span + 2 * f, 2 * (span + 2 * f)) if short else (2 * f, 4 * f)
@@ -267,20 +374,26 @@ def bed_jobs(bed_info, num_reads_cff, bam_in, ref, out_path, sample_name) -> Lis
 
 
 def vcf_jobs(vcf_list, num_reads_cff, bam_in, ref, out_path, sample_name) -> List[Job]:
-    """The loop of vapor_vali/vapor:387-465 (TANDUP is bucketed but never scored there either)."""
+    """The loop of vapor_vali/vapor:387-465 (TANDUP is bucketed but never scored there either), and the breakends of
+    `vapor vcf --bnd` (vcf_list_readin's last bucket: drivers.vapor_bnd)."""
     jobs = []
     plt_li = 0
     ctx = (num_reads_cff, bam_in, ref)
     for x in list(vcf_list.keys()):
-        if x not in ('DEL', 'INV', 'INS', 'DISDUP', 'DEL_INV', 'DUP_INV', 'Other'):
+        if x not in ('DEL', 'INV', 'INS', 'DISDUP', 'DEL_INV', 'DUP_INV', 'Other', 'BND'):
             print(x)
             continue
         for y in vcf_list[x]:
-            if 'NA' in y:
+            if x != 'BND' and 'NA' in y:          # (a breakend's fields are contig names and bases)
                 continue
             print(y)
             plt_li += 1
-            if x in ('DEL', 'INV'):
+            if x == 'BND':
+                key = bnd_key(y)
+                fig = out_path + sample_name + '.BND.' + key.replace(':', '__') + '.png'
+                jobs.append(Job(key, (lambda p=plt_li, info=y, g=fig: drivers.vapor_bnd(num_reads_cff, p, bam_in, ref, info, g)),
+                                cost=job_cost('BND', 0)))
+            elif x in ('DEL', 'INV'):
                 if y[2] - y[1] < 50:        # both branches label the row DEL (vapor_vali/vapor:394, 407)
                     jobs.append(Job(':'.join([str(i) for i in y] + ['DEL']), fixed=[]))
                     continue
@@ -552,6 +665,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('--PB-supp', required=False, help='minimum number of evaluable PacBio reads')
     p.add_argument('--no-figures', action='store_true', help='do not render recurrence-plot PNGs')
     p.add_argument('--chunk', type=int, default=2048, help='loci per device batch')
+    p.add_argument('--bnd', action='store_true',
+                   help='vcf: also score breakend (SVTYPE=BND) records: t[B:q[, t]B:q] and ]B:q]t junctions')
     return p
 
 
@@ -591,7 +706,7 @@ def main(argv: Optional[List[str]] = None) -> int:
                 for j, tail in zip(jobs, tails):
                     print([j.key, tail[0], tail[1], tail[4]])
     elif mode == 'vcf':
-        vcf_list, rec_hash = vcf_list_readin(args.sv_input)
+        vcf_list, rec_hash = vcf_list_readin(args.sv_input, ref if args.bnd else None)
         rec_new = SF.vcf_rec_hash_modify(rec_hash)
         jobs = vcf_jobs(vcf_list, num_reads_cff, bam_in, ref, out_path, sample_name)
         scores = score_jobs(jobs, args.chunk, figure_fn)

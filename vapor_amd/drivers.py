@@ -174,6 +174,33 @@ def vapor_simple_del(num_reads_cff, plt_li, bam_in, ref, sv_info, out_figure_nam
     return scores
 
 
+def vapor_bnd(num_reads_cff, plt_li, bam_in, ref, bnd_info, out_figure_name):
+    """A breakend junction (`vapor vcf --bnd`; not in the reference): the long-deletion branch of
+    vapor_simple_del_Vapor (SF:1727-1745) for [A, p, q - 1], its right piece taken on contig B - forward from q - 1 ('3to5',
+    as the branch starts at END) or the reverse complement of B up to q ('3to3') - with the breakend's inserted bases between
+    the pieces.  bnd_info = [A, p, B, q, CT, inserted bases] (cli.bnd_view)."""
+    a, p, b, q, ct, ins = bnd_info
+    flank = default_flank_length
+    scores: List[float] = []
+    reads = seqio.simple_del_chop_pacbio_read_simple_short(bam_in, [a, p], flank)
+    if len(reads) > num_reads_cff:
+        ref_seq = seqio.ref_seq_readin(ref, a, p - flank, p + flank)
+        k = yield from _window(ref_seq)
+        if not k == "Error":
+            left = seqio.ref_seq_readin(ref, a, p - flank, p)
+            if ct == "3to5":
+                right = (seqio.ref_seq_readin(ref, b, q - 1, q - 1 + flank), None, None)
+            else:
+                right = (seqio.ref_seq_readin(ref, b, q - flank, q), None, None, True)
+            alt_seq = _cat(_within(ref_seq, p - flank, left, p - flank), (ins, None, None), right)
+            k = yield from _window(alt_seq)
+            if not k == "Error":
+                res = yield Score("s2", ref_seq, alt_seq, reads, k)
+                best = _collect(res, reads, scores)
+                yield Figure(scores, best, k, ref_seq, alt_seq, out_figure_name)
+    return scores
+
+
 def vapor_simple_inv(num_reads_cff, plt_li, bam_in, ref, sv_info, out_figure_name):
     """vapor_simple_inv_Vapor, SF:1895-1933."""
     flank = seqio.flank_length_calculate(sv_info)

@@ -13,7 +13,8 @@ for all loci of a chunk at once when they take the drivers' straight route:
 `vapor_amd.drivers` (generators, one locus each) remains the statement of the reference's control flow and the route of every
 locus that leaves the straight one: a span of 10 kb or more, a window that is refused or repetitive ('Error', a growing window
 size), an inversion or duplication without enough spanning reads (their junction-window fallbacks, SF:1918-1932, 1769-1783), a
-read with N or a character outside the alphabet, windows cut short by a contig end, several BAM files.  Such a locus is
+read with N or a character outside the alphabet, windows cut short by a contig end, several BAM files; a breakend of
+`vapor vcf --bnd` carries no spec and never comes here.  Such a locus is
 answered FALLBACK here and scored by its generator - with the same result by construction; tests/test_fastpath.py compares
 the two routes locus for locus.
 """

@@ -35,6 +35,7 @@ def readme_bed():
 
 def readme_vcf():
     _show("vapor vcf [Parameters]", "	--sv-input:		input file in vcf format (result: <input>.vapor)")
+    print("	--bnd:			also score breakend records (SVTYPE=BND, ALT t[B:q[ / t]B:q] / ]B:q]t; [B:q[t is skipped)")
 
 
 def readme_melt():

@@ -541,6 +541,114 @@ def make_complex_world(seed: int, specs: Sequence[dict], n_reads: int = 8, alt_f
     return w
 
 
+BND_FORMS = ("3to5", "3to3", "5to3", "5to5")
+
+
+def bnd_alt(form: str, ref_base: str, ins: str, chrom: str, pos: int) -> str:
+    """The VCF 4.x ALT of a breakend whose partner is chrom:pos: t[p[ 3to5, t]p] 3to3, ]p]t 5to3, [p[t 5to5."""
+    p = "%s:%d" % (chrom, pos)
+    return {"3to5": ref_base + ins + "[" + p + "[", "3to3": ref_base + ins + "]" + p + "]",
+            "5to3": "]" + p + "]" + ins + ref_base, "5to5": "[" + p + "[" + ins + ref_base}[form]
+
+
+def _clipped_reads(rng, w, chrom, side, at, flank_seq, n, read_len, lead, errors, tag, ref_fraction=0.0):
+    """n reads on `chrom` that carry a junction: side 'R' = aligned up to `at` (1-based) and soft-clipped after it (xM yS, the
+    clip = the start of `flank_seq`); side 'L' = soft-clipped before `at` and aligned from it on (yS xM, the clip = the end of
+    `flank_seq`).  A read drawn as a reference read (`ref_fraction`) is the contig itself across `at`, unclipped."""
+    c = w.contigs[chrom]
+    recs = w.reads.setdefault(chrom, [])
+    for ri in range(n):
+        from_ref = rng.random() < ref_fraction
+        if side == "R":
+            a0 = max(at - 500 - 1 - int(rng.integers(1, lead + 1)), 0)     # from before the window's start (SF:345)
+            if from_ref:
+                b0 = min(a0 + read_len, len(c))
+                read, cig = mutate(rng, c[a0:b0], *errors)
+                recs.append(SamRecord("%s_R%dr" % (tag, ri), chrom, a0 + 1, cig, read, b0 - a0))
+                continue
+            ra, ca = mutate(rng, c[a0:at], *errors)
+            rt, _ = mutate(rng, flank_seq[:max(read_len - (at - a0), 0)], *errors, cigar=False)
+            recs.append(SamRecord("%s_R%da" % (tag, ri), chrom, a0 + 1, ca + ("%dS" % len(rt) if rt else ""), ra + rt, at - a0))
+        else:
+            h = min(len(flank_seq), int(rng.integers(300, 500 + lead)))
+            b0 = min(at - 1 + read_len - h, len(c))
+            rh, _ = mutate(rng, flank_seq[len(flank_seq) - h:], *errors, cigar=False)
+            ra, ca = mutate(rng, c[at - 1:b0], *errors)
+            recs.append(SamRecord("%s_L%da" % (tag, ri), chrom, at, ("%dS" % len(rh) if rh else "") + ca, rh + ra, b0 - at + 1))
+
+
+def make_bnd_world(seed: int, forms: Sequence[str] = BND_FORMS, n_reads: int = 8, read_len: int = 2400, lead: int = 250,
+                   ref_fraction: float = 0.0, ins: Sequence[str] = ("",), errors: Tuple[float, float, float] = (0.01, 0.08, 0.04),
+                   chrom_prefix: str = "t") -> SynthWorld:
+    """Translocation worlds: per junction two contigs of their own, A (<prefix><i>a) and B (<prefix><i>b), joined by a breakend
+    of the given form - the record at A:p, its mate at B:q (VCF 4.x, bnd_alt), inserted bases ins[i % len(ins)] between the
+    pieces, as the record at A:p writes them:
+
+        3to5  t[B:q[   A up to p, then B from q on          5to3  ]B:q]t   B up to q, then A from p on
+        3to3  t]B:q]   A up to p, then rc(B up to q)        5to5  [B:q[t   rc(B from q on), then A from p on
+
+    A read on the piece that ends at the junction is aligned up to it and soft-clipped after it (xM yS); a read on the piece that
+    starts there is soft-clipped before it (yS xM); SEQ holds the clipped bases.  Every side gets n_reads reads, a share
+    `ref_fraction` of those on the right-clipped side drawn from the contig instead.  Loci: svtype 'BND', start = p,
+    end = q, extra = {form, mate_chrom}.  (A generator of its own: make_world's draws stay as they are.)"""
+    rng = np.random.default_rng(seed)
+    w = SynthWorld()
+    for li, form in enumerate(forms):
+        if form not in BND_FORMS:
+            raise ValueError(form)
+        ca, cb = "%s%da" % (chrom_prefix, li + 1), "%s%db" % (chrom_prefix, li + 1)
+        p = 1500 + int(rng.integers(0, 200))
+        q = 1500 + int(rng.integers(0, 200))
+        A = w.contigs[ca] = random_dna(rng, p + read_len + 400)
+        B = w.contigs[cb] = random_dna(rng, q + read_len + 400)
+        I = ins[li % len(ins)]
+        tag = "j%d" % (li + 1)
+        n_ref = ref_fraction
+        if form == "3to5":          # A[:p] + I + B[q-1:]
+            _clipped_reads(rng, w, ca, "R", p, I + B[q - 1:], n_reads, read_len, lead, errors, tag + "a", n_ref)
+            _clipped_reads(rng, w, cb, "L", q, A[:p] + I, n_reads, read_len, lead, errors, tag + "b")
+        elif form == "3to3":        # A[:p] + I + rc(B[:q]); from B: B[:q] + rc(I) + rc(A[:p])
+            _clipped_reads(rng, w, ca, "R", p, I + revcomp(B[:q]), n_reads, read_len, lead, errors, tag + "a", n_ref)
+            _clipped_reads(rng, w, cb, "R", q, revcomp(I) + revcomp(A[:p]), n_reads, read_len, lead, errors, tag + "b", n_ref)
+        elif form == "5to3":        # B[:q] + I + A[p-1:]
+            _clipped_reads(rng, w, cb, "R", q, I + A[p - 1:], n_reads, read_len, lead, errors, tag + "b", n_ref)
+            _clipped_reads(rng, w, ca, "L", p, B[:q] + I, n_reads, read_len, lead, errors, tag + "a")
+        else:                       # rc(B[q-1:]) + I + A[p-1:]; from B: rc(A[p-1:]) + rc(I) + B[q-1:]
+            _clipped_reads(rng, w, ca, "L", p, revcomp(B[q - 1:]) + I, n_reads, read_len, lead, errors, tag + "a")
+            _clipped_reads(rng, w, cb, "L", q, revcomp(A[p - 1:]) + revcomp(I), n_reads, read_len, lead, errors, tag + "b")
+        for c in (ca, cb):
+            w.reads.setdefault(c, []).sort(key=lambda r: r.pos)
+        w.loci.append(Locus(ca, "BND", p, q, "bnd%d" % (li + 1), I, {"form": form, "mate_chrom": cb}))
+    return w
+
+
+def bnd_records(world: SynthWorld, mates: bool = True) -> List[List[str]]:
+    """VCF records (lists of the ten columns) of make_bnd_world's junctions: the record at A:p, then its mate at B:q, paired by
+    ID / MATEID."""
+    mate_form = {"3to5": "5to3", "3to3": "3to3", "5to3": "3to5", "5to5": "5to5"}
+    out = []
+    for l in world.loci:
+        if l.svtype != "BND":
+            continue
+        form, cb, p, q, I = l.extra["form"], l.extra["mate_chrom"], l.start, l.end, l.ins_seq or ""
+        ra, rb = world.contigs[l.chrom][p - 1], world.contigs[cb][q - 1]
+        i1, i2 = l.svid + "_1", l.svid + "_2"
+        out.append([l.chrom, str(p), i1, ra, bnd_alt(form, ra, I, cb, q), ".", "PASS",
+                    "SVTYPE=BND" + (";MATEID=" + i2 if mates else ""), "GT", "0/1"])
+        if mates:
+            mi = I if form in ("3to5", "5to3") else revcomp(I)
+            out.append([cb, str(q), i2, rb, bnd_alt(mate_form[form], rb, mi, l.chrom, p), ".", "PASS", "SVTYPE=BND;MATEID=" + i1,
+                        "GT", "0/1"])
+    return out
+
+
+def bnd_vcf_text(world: SynthWorld, mates: bool = True, header: bool = False) -> str:
+    out = ["##fileformat=VCFv4.2", "##source=vapor_amd.synth",
+           "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\tSAMPLE"] if header else []
+    out += ["\t".join(r) for r in bnd_records(world, mates)]
+    return "\n".join(out) + "\n"
+
+
 def complex_vcf_text(world: SynthWorld, header: bool = False) -> str:
     """VCF records for make_complex_world's loci with the INFO keys vapor_vali/vapor:87-125, 176-202 read:
     insert_point=chrom:pos (DISDUP, DUP_INV), del=/inv= (DEL_INV), Other=ref_alt_chrom:bp:bp:bp."""
