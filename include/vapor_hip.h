@@ -246,6 +246,31 @@ int vapor_plan_then(vapor_plan* plan, void* hip_stream);
 int vapor_plan_after(vapor_plan* plan, void* hip_stream);
 int vapor_plan_sync(vapor_plan* plan, double* loci_out);
 
+/* ---- breakpoint refinement: a grid of candidate breakpoints per locus (`--refine`) --------- */
+/*
+ * Not in the reference: a call whose breakpoints are tens of bases off is scored at a grid of candidate
+ * breakpoints around it - one window, one set of reads, every candidate allele a derived sequence of the window - and the best
+ * candidate is chosen on the device.  The plan's "loci" (vapor_plan_set_reads) are then the CANDIDATES; vapor_plan_set_grid says
+ * which consecutive loci belong to one refined locus: group g = loci first_locus[g] .. first_locus[g + 1], 1 to
+ * VAPOR_MAX_CANDIDATES of them, the first the call itself, all with the same number of reads (the group's reads, in one order);
+ * first_locus[0] = 0 and first_locus[n_groups] = n_loci.  The rule (vapor_amd/refine.py, pick): a candidate is eligible when it
+ * scored at least one read and at least as many as the group's first; among those the largest GS, then the largest QS, then the
+ * lowest index; the first when none is eligible.  A NaN never beats a number.
+ * vapor_plan_run_grid: vapor_plan_run_loci followed on the same stream, with no host step in between, by that choice
+ * (grid_pick_kernel, one wavefront a group).  winner_idx[g] = the winner's index in its group; group_out[16 g ..] = the winner's
+ * VAPOR_LOCUS_STRIDE doubles, then those of the group's first candidate; winner_scores[score_off[g] .. score_off[g + 1]) = the
+ * winner's per-read scores (NaN: a skipped read); score_off (n_groups + 1 entries) is filled by the call.  Any of the four may
+ * be NULL.  Only these cross the link, not the candidates' records and scores.
+ */
+#define VAPOR_MAX_CANDIDATES 128 /* per group: one wavefront holds a group with two candidates per lane */
+int vapor_plan_set_grid(vapor_plan* plan, int64_t n_groups, const int32_t* first_locus);
+int vapor_plan_run_grid(vapor_plan* plan, int32_t* winner_idx, double* group_out, double* winner_scores, int64_t* score_off);
+/* The same choice on the caller's own tables (host arrays in and out, one call): records = VAPOR_LOCUS_STRIDE doubles per
+ * candidate, candidate c's per-read scores = read_scores[read_first[c] .. read_first[c + 1]) (read_first[0] = 0), the groups and
+ * the four outputs as above. */
+int vapor_grid_pick(vapor_ctx* ctx, int64_t n_groups, const int32_t* first_locus, const double* records, const int32_t* read_first,
+                    const double* read_scores, int32_t* winner_idx, double* group_out, double* winner_scores, int64_t* score_off);
+
 /* ---- one-shot conveniences over the above -------------------------------------------------- */
 /* dotdata for a batch (create + run + fetch all + destroy). */
 int vapor_dotplot_batch(vapor_ctx* ctx, vapor_seqset* set, int64_t n_pairs, const vapor_pair* pairs,

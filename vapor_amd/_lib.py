@@ -53,10 +53,13 @@ EXPORTS = [
     "vapor_inflate_raw", "vapor_chop_records", "vapor_chop_records_many", "vapor_row_tails", "vapor_crc32",
     "vapor_bam_chop_device", "vapor_bam_batch_destroy", "vapor_bam_fileno", "vapor_bam_threads", "vapor_seqset_create_mixed", "vapor_bam_last_stats",
     "vapor_wide_batch", "vapor_clean_hits_wide", "vapor_fasta_windows_device", "vapor_fasta_last_stats", "vapor_anyk_batch",
+    "vapor_plan_set_grid", "vapor_plan_run_grid", "vapor_grid_pick",
 ]
-# entry points a library may lack (the CPU twin of the C ABI has no wide or any-k route): bound when present, and the engine's
-# wide and any-k methods raise NotImplementedError when they are not
-OPTIONAL_EXPORTS = ("vapor_wide_batch", "vapor_clean_hits_wide", "vapor_anyk_batch")
+# entry points a library may lack (the CPU twin of the C ABI has no wide or any-k route and no refinement kernel): bound when
+# present, and the engine's wide, any-k and grid methods raise NotImplementedError when they are not
+OPTIONAL_EXPORTS = ("vapor_wide_batch", "vapor_clean_hits_wide", "vapor_anyk_batch", "vapor_plan_set_grid", "vapor_plan_run_grid",
+                    "vapor_grid_pick")
+MAX_CANDIDATES = 128           # breakpoint refinement: candidates per locus (VAPOR_MAX_CANDIDATES)
 
 _lib = None
 
@@ -209,6 +212,12 @@ def bind(L: ctypes.CDLL) -> ctypes.CDLL:
         L.vapor_clean_hits_wide.argtypes = [vp, ctypes.c_int64, i32p, i64p, u32p, i64p, u8p]
     if hasattr(L, "vapor_anyk_batch"):
         L.vapor_anyk_batch.argtypes = [vp, vp, ctypes.c_int64, vp, i64p, i32p, ctypes.c_int64, i64p]
+    if hasattr(L, "vapor_plan_set_grid"):
+        L.vapor_plan_set_grid.argtypes = [vp, ctypes.c_int64, i32p]
+    if hasattr(L, "vapor_grid_pick"):
+        L.vapor_grid_pick.argtypes = [vp, ctypes.c_int64, i32p, f64p, i32p, f64p, i32p, f64p, f64p, i64p]
+    if hasattr(L, "vapor_plan_run_grid"):
+        L.vapor_plan_run_grid.argtypes = [vp, i32p, f64p, f64p, i64p]
     for name in EXPORTS:
         if name in OPTIONAL_EXPORTS and not hasattr(L, name):
             continue

@@ -14,6 +14,7 @@ SOURCES = [os.path.join(HERE, "csrc", "vapor_hip.hip"), os.path.join(HERE, "csrc
 DEPS = SOURCES + [os.path.join(HERE, "csrc", "vapor_kernels.h"), os.path.join(HERE, "csrc", "vapor_wide.h"), os.path.join(HERE, "csrc", "vapor_anyk.h"),
                   os.path.join(HERE, "csrc", "vapor_inflate.h"),
                   os.path.join(HERE, "csrc", "vapor_bamdev.h"), os.path.join(HERE, "csrc", "vapor_fasta.h"),
+                  os.path.join(HERE, "csrc", "vapor_refine.h"),
                   os.path.join(ROOT, "include", "vapor_hip.h")]
 
 
@@ -34,7 +35,7 @@ def hipcc() -> str:
 
 KERNEL_FILES = [os.path.join(HERE, "csrc", "vapor_kernels.h"), os.path.join(HERE, "csrc", "vapor_wide.h"), os.path.join(HERE, "csrc", "vapor_anyk.h"),
                 os.path.join(HERE, "csrc", "vapor_bamdev.h"), os.path.join(HERE, "csrc", "vapor_fasta.h"),
-                os.path.join(HERE, "csrc", "vapor_hip.hip"), os.path.abspath(__file__)]
+                os.path.join(HERE, "csrc", "vapor_refine.h"), os.path.join(HERE, "csrc", "vapor_hip.hip"), os.path.abspath(__file__)]
 _ID_RE = re.compile(rb"VAPOR_SOURCE_ID=([0-9a-f]{16}:[0-9a-f]{16})")
 
 

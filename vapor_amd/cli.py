@@ -7,7 +7,8 @@ to the GPU together.  With more than one rank (torchrun), loci are sharded acros
 the node and the per-locus rows are all-gathered (vapor_amd.dist).
 
 Extra flags (not in the reference): --no-figures (skip the recurrence-plot PNGs),
---chunk (loci per device batch), --bnd (vcf: score breakend records as well).
+--chunk (loci per device batch), --bnd (vcf: score breakend records as well), --refine M[:T] (bed, vcf: score a
+grid of candidate breakpoints within M bp of every short DEL / INV / TANDUP call and report the best).
 """
 from __future__ import annotations
 
@@ -286,13 +287,14 @@ class _BndReader:
 class Job:
     """One output row: how to score it (a driver generator factory, or fixed scores) and how to
     write it.  `cost`: what the locus is expected to take (microseconds, `job_cost`), for the shares of the ranks."""
-    __slots__ = ("key", "make", "fixed", "row_prefix", "label", "cost", "spec", "ctx")
+    __slots__ = ("key", "make", "fixed", "row_prefix", "label", "cost", "spec", "ctx", "refine")
 
     def __init__(self, key, make=None, fixed=None, row_prefix=None, label=None, cost=None, spec=None, ctx=None):
         self.key, self.make, self.fixed, self.row_prefix, self.label = key, make, fixed, row_prefix, label
         # the four simple types also say WHAT they are - (type, chrom, start, end, ins_seq) and (num_reads_cff, bam, ref) - so
         # that a chunk of them can take the array route (vapor_amd.fastpath); `make` stays the driver's own route
         self.spec, self.ctx = spec, ctx
+        self.refine = None             # after scoring under --refine: refine.Refined.info of a locus that was refined
         self.cost = cost if cost is not None else (COST_FIXED_US if make is None else COST_HOST_US)
 
 
@@ -311,10 +313,11 @@ COST_XMEANS_US = 500.0         # a tandem duplication's alt window always meets 
 _READS_KEPT = 20               # minimize_pacbio_read_list keeps at most 20 reads (SF:1091-1102)
 
 
-def job_cost(svtype: str, span: int, extra: int = 0) -> float:
+def job_cost(svtype: str, span: int, extra: int = 0, candidates: int = 1) -> float:
     """Expected cost of one locus in microseconds from its type and span alone (windows as the drivers cut them, SURVEY.md
     3.2): `span` = end - start (INS: the inserted length; complex types: the whole region), `extra` = the duplicated block of
-    DISDUP / DUP_INV.  An estimate for balancing shares - nothing depends on its accuracy but the ranks' idle time."""
+    DISDUP / DUP_INV, `candidates` = the alleles scored on the window (`--refine`: every read meets the window once and every
+    candidate allele once).  An estimate for balancing shares - nothing depends on its accuracy but the ranks' idle time."""
     span = max(int(span), 0)
     f = min(500, span) if span > 0 else 500
     short = span < drivers.default_max_sv_test
@@ -332,12 +335,20 @@ def job_cost(svtype: str, span: int, extra: int = 0) -> float:
         lr, la = (span + extra + 2 * f, (span + 2 * f) + (span + extra + 2 * f)) if short else (2 * f, 4 * f)
     bases = _READS_KEPT * lr + la
     cells = _READS_KEPT * lr * la
+    if candidates > 1:                      # (la = window + one allele: the other candidates' alleles are about that allele's size)
+        cells += _READS_KEPT * lr * (candidates - 1) * (la / 2.0)
     xmeans = COST_XMEANS_US if (svtype == 'TANDUP' and short) else 0.0
     return COST_HOST_US + COST_PER_KBASE_US * bases / 1e3 + COST_PER_GCELL_US * cells / 1e9 + xmeans
 
 
-def bed_jobs(bed_info, num_reads_cff, bam_in, ref, out_path, sample_name) -> List[Job]:
-    """The loop of vapor_vali/vapor:334-367."""
+def _refine_n(refine, s, e, ci=(None, None)) -> int:
+    from . import refine as rf
+    return len(rf.candidates(refine[0], refine[1], s, e, ci[0], ci[1]))
+
+
+def bed_jobs(bed_info, num_reads_cff, bam_in, ref, out_path, sample_name, refine=None) -> List[Job]:
+    """The loop of vapor_vali/vapor:334-367.  `refine` = (M, T) of `--refine`: DEL, INV and TANDUP loci take
+    drivers.vapor_refine (which leaves a locus it cannot refine to the type's own driver)."""
     jobs = []
     plt_li = 0
     ctx = (num_reads_cff, bam_in, ref)
@@ -368,14 +379,46 @@ def bed_jobs(bed_info, num_reads_cff, bam_in, ref, out_path, sample_name) -> Lis
             continue
         plt_li += 1
         fig = out_path + sample_name + '.' + name + '.' + key.replace(':', '__') + '.png'
+        if refine is not None:
+            jobs.append(Job(key, (lambda p=plt_li, n=name, info=x[:-3], g=fig:
+                                  drivers.vapor_refine(n, num_reads_cff, p, bam_in, ref, info, g, refine[0], refine[1])),
+                            row_prefix=x[3], label=x, cost=job_cost(name, x[2] - x[1], candidates=_refine_n(refine, x[1], x[2]))))
+            continue
         jobs.append(Job(key, (lambda p=plt_li, f=fn, info=x[:-3], g=fig: f(num_reads_cff, p, bam_in, ref, info, g)),
                         row_prefix=x[3], label=x, cost=job_cost(name, x[2] - x[1]), spec=(name, x[0], x[1], x[2], None), ctx=ctx))
     return jobs
 
 
-def vcf_jobs(vcf_list, num_reads_cff, bam_in, ref, out_path, sample_name) -> List[Job]:
+def vcf_ci_readin(file_in) -> dict:
+    """{'chrom:start:end:TYPE': ((CIPOS lo, hi) or None, (CIEND lo, hi) or None)} of the DEL and INV records of a VCF, the first
+    record of a key deciding (as vcf_list_readin keeps the first): the bounds `--refine` keeps a record's candidates within."""
+    out = {}
+    with open(file_in) as fin:
+        for line in fin:
+            pin = line.strip().split()
+            if not pin or pin[0][0] == '#' or len(pin) < 8:
+                continue
+            pin[7] = pin[7].replace('MERGE_TYPE=', 'SVTYPE=')
+            t = SF.svtype_extract(pin)
+            name = 'DEL' if t in ['del', 'DEL', 'deletion'] else 'INV' if t in ['inv', 'INV', 'inversion'] else None
+            if name is None:
+                continue
+            ci = {}
+            for x in pin[7].split(';'):
+                if x[:6] in ('CIPOS=', 'CIEND='):
+                    try:
+                        lo, hi = [int(v) for v in x[6:].split(',')]
+                    except ValueError:
+                        continue
+                    ci[x[:5]] = (min(lo, 0), max(hi, 0))
+            out.setdefault(':'.join([str(i) for i in SF.chr_start_end_extract(pin)] + [name]), (ci.get('CIPOS'), ci.get('CIEND')))
+    return out
+
+
+def vcf_jobs(vcf_list, num_reads_cff, bam_in, ref, out_path, sample_name, refine=None, ci_of=None) -> List[Job]:
     """The loop of vapor_vali/vapor:387-465 (TANDUP is bucketed but never scored there either), and the breakends of
-    `vapor vcf --bnd` (vcf_list_readin's last bucket: drivers.vapor_bnd)."""
+    `vapor vcf --bnd` (vcf_list_readin's last bucket: drivers.vapor_bnd).  `refine` = (M, T) of `--refine` and `ci_of`
+    (vcf_ci_readin): DEL and INV records take drivers.vapor_refine, within their CIPOS / CIEND."""
     jobs = []
     plt_li = 0
     ctx = (num_reads_cff, bam_in, ref)
@@ -400,6 +443,12 @@ def vcf_jobs(vcf_list, num_reads_cff, bam_in, ref, out_path, sample_name) -> Lis
                 key = ':'.join([str(i) for i in y] + [x])
                 fn = drivers.vapor_simple_del if x == 'DEL' else drivers.vapor_simple_inv
                 fig = out_path + sample_name + '.' + x + '.' + key.replace(':', '__') + '.png'
+                if refine is not None and len(y) == 3:
+                    ci = (ci_of or {}).get(key, (None, None))
+                    jobs.append(Job(key, (lambda p=plt_li, n=x, info=y, g=fig, c=ci:
+                                          drivers.vapor_refine(n, num_reads_cff, p, bam_in, ref, info, g, refine[0], refine[1], c[0], c[1])),
+                                    cost=job_cost(x, y[2] - y[1], candidates=_refine_n(refine, y[1], y[2], ci))))
+                    continue
                 jobs.append(Job(key, (lambda p=plt_li, f=fn, info=y, g=fig: f(num_reads_cff, p, bam_in, ref, info, g)),
                                 cost=job_cost(x, y[2] - y[1]), spec=(x, y[0], y[1], y[2], None), ctx=ctx))
             elif x == 'INS':
@@ -525,9 +574,10 @@ def output_rows(heads: list, scores_list: list) -> tuple:
     return lines, tails
 
 
-def score_jobs(jobs: List[Job], chunk: int, figure_fn=None) -> List[object]:
+def score_jobs(jobs: List[Job], chunk: int, figure_fn=None, refine=None) -> List[object]:
     """Score every job (sharded over ranks, batched on each GPU); returns per job the list of read
-    scores, in job order, identical on every rank."""
+    scores, in job order, identical on every rank.  With `refine` (`--refine`) every job's `refine` attribute is set as
+    well, on every rank: refine.Refined.info of a locus that was refined, None otherwise."""
     import gc
     import time
     t0 = time.perf_counter()
@@ -539,7 +589,7 @@ def score_jobs(jobs: List[Job], chunk: int, figure_fn=None) -> List[object]:
     gc_was = gc.get_threshold()
     gc.set_threshold(max(gc_was[0], 200000), max(gc_was[1], 50), max(gc_was[2], 1000))
     try:
-        return _score_jobs(jobs, chunk, figure_fn, t0)
+        return _score_jobs(jobs, chunk, figure_fn, t0) if refine is None else _score_jobs(jobs, chunk, figure_fn, t0, refine)
     finally:
         gc.set_threshold(*gc_was)
 
@@ -558,7 +608,7 @@ def _chunk_threads_ok() -> bool:
 last_timing: dict = {}          # of the most recent score_jobs: seconds scoring this rank's share, seconds in the gather
 
 
-def _score_jobs(jobs, chunk, figure_fn, t0):
+def _score_jobs(jobs, chunk, figure_fn, t0, refine=None):
     import time
     # shares by estimated cost (greedy longest-processing-time), the same list on every rank
     costs = [float(j.cost) for j in jobs]
@@ -642,6 +692,12 @@ def _score_jobs(jobs, chunk, figure_fn, t0):
             if jobs[t].make is None:
                 local[t] = jobs[t].fixed
     t1 = time.perf_counter()
+    if refine is not None:
+        # (the four extra columns travel as a second table of "scores": five floats for a refined locus, none otherwise)
+        extra = {t: (list(getattr(r, "info", None) or ()) if not isinstance(r, BaseException) and r is not None else [])
+                 for t, r in local.items()}
+        for j, info in zip(jobs, vdist.gather_results(extra, len(jobs), costs)):
+            j.refine = info if info else None
     allres = vdist.gather_results(local, len(jobs), costs)
     last_timing.update(score_s=t1 - t0, gather_s=time.perf_counter() - t1, loci=len(mine), cost=sum(costs[t] for t in mine))
     if os.environ.get("VAPOR_TIMING") and vdist.rank() == 0:
@@ -667,6 +723,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('--chunk', type=int, default=2048, help='loci per device batch')
     p.add_argument('--bnd', action='store_true',
                    help='vcf: also score breakend (SVTYPE=BND) records: t[B:q[, t]B:q] and ]B:q]t junctions')
+    p.add_argument('--refine', metavar='M[:T]', default=None,
+                   help='bed, vcf: score candidate breakpoints within M bp of every short DEL / INV / TANDUP call, in steps of T bp '
+                        '(default: the smallest step that keeps a locus within 128 candidates), and report the best; appends '
+                        'VaPoR_RPOS, VaPoR_REND, VaPoR_QS0 and VaPoR_GS0 (vcf: to INFO, within CIPOS / CIEND)')
     return p
 
 
@@ -681,8 +741,18 @@ def main(argv: Optional[List[str]] = None) -> int:
         from . import prep
         {'bed': prep.readme_bed, 'vcf': prep.readme_vcf, 'ins': prep.readme_melt}.get(mode, prep.print_read_me)()
         return 0
-    args = build_parser().parse_args(argv[1:])
+    parser = build_parser()
+    args = parser.parse_args(argv[1:])
     num_reads_cff = int(args.PB_supp) if args.PB_supp else 3
+    refine = None
+    if args.refine is not None:
+        from . import refine as rf
+        if mode not in ('bed', 'vcf'):
+            parser.error('--refine applies to `vapor bed` and `vapor vcf`')
+        try:
+            refine = rf.parse(args.refine)
+        except ValueError as e:
+            parser.error(str(e))
     figure_fn = None
     if not args.no_figures:
         from . import figures
@@ -695,26 +765,35 @@ def main(argv: Optional[List[str]] = None) -> int:
     bam_in, ref = args.pacbio_input, args.reference
     if mode == 'bed':
         bed_info = bed_info_readin(args.sv_input, out_path)
-        jobs = bed_jobs(bed_info, num_reads_cff, bam_in, ref, out_path, sample_name)
-        scores = score_jobs(jobs, args.chunk, figure_fn)
+        jobs = bed_jobs(bed_info, num_reads_cff, bam_in, ref, out_path, sample_name, refine)
+        scores = score_jobs(jobs, args.chunk, figure_fn, refine)
         if vdist.rank() == 0:
-            SF.write_output_initiate(args.output_file)
+            SF.write_output_initiate(args.output_file, rf.COLUMNS if refine is not None else ())
             with open(args.output_file, 'a') as fo:
                 # (result_organize_ins + write_output_main of vapor_vali/vapor:356-357 in one go: finish.row_tails)
                 lines, tails = output_rows([j.key.split(':') + [j.row_prefix] for j in jobs], scores)
+                if refine is not None:
+                    lines = [l + '\t' + '\t'.join(rf.columns(j.refine)) for l, j in zip(lines, jobs)]
                 fo.write(''.join([l + '\n' for l in lines]))
                 for j, tail in zip(jobs, tails):
                     print([j.key, tail[0], tail[1], tail[4]])
     elif mode == 'vcf':
         vcf_list, rec_hash = vcf_list_readin(args.sv_input, ref if args.bnd else None)
         rec_new = SF.vcf_rec_hash_modify(rec_hash)
-        jobs = vcf_jobs(vcf_list, num_reads_cff, bam_in, ref, out_path, sample_name)
-        scores = score_jobs(jobs, args.chunk, figure_fn)
+        jobs = vcf_jobs(vcf_list, num_reads_cff, bam_in, ref, out_path, sample_name, refine,
+                        vcf_ci_readin(args.sv_input) if refine is not None else None)
+        scores = score_jobs(jobs, args.chunk, figure_fn, refine)
         if vdist.rank() == 0:
-            SF.write_output_initiate(args.sv_input + '.vapor')
+            SF.write_output_initiate(args.sv_input + '.vapor', rf.COLUMNS if refine is not None else ())
             with open(args.sv_input + '.vapor', 'a') as fo:
-                fo.write(''.join([l + '\n' for l in output_rows([[j.key] for j in jobs], scores)[0]]))
-            SF.vcf_vapor_modify(args.sv_input, rec_new)
+                lines = output_rows([[j.key] for j in jobs], scores)[0]
+                if refine is not None:
+                    lines = [l + '\t' + '\t'.join(rf.columns(j.refine)) for l, j in zip(lines, jobs)]
+                fo.write(''.join([l + '\n' for l in lines]))
+            if refine is not None:
+                SF.vcf_vapor_modify(args.sv_input, rec_new, refined=True)
+            else:
+                SF.vcf_vapor_modify(args.sv_input, rec_new)
     elif mode == 'svelter':
         jobs = svelter_jobs(svelter_readin(args.sv_input), num_reads_cff, bam_in, ref, out_path, sample_name)
         scores = score_jobs(jobs, args.chunk, figure_fn)

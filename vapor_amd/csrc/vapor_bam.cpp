@@ -693,3 +693,21 @@ extern "C" __attribute__((weak)) int vapor_fasta_last_stats(vapor_ctx*, double*,
 {
     return bfail(VAPOR_E_ARG, "vapor_fasta_last_stats: this build has no device FASTA reader");
 }
+
+// Breakpoint refinement's device step (vapor_plan_set_grid, vapor_plan_run_grid: grid_pick_kernel) is device code in vapor_hip.hip;
+// the CPU twin refuses it, and the caller scores the candidates one by one (vapor_amd/refine.py).
+extern "C" __attribute__((weak)) int vapor_plan_set_grid(vapor_plan*, int64_t, const int32_t*)
+{
+    return bfail(VAPOR_E_ARG, "vapor_plan_set_grid: this build has no refinement kernel");
+}
+
+extern "C" __attribute__((weak)) int vapor_plan_run_grid(vapor_plan*, int32_t*, double*, double*, int64_t*)
+{
+    return bfail(VAPOR_E_ARG, "vapor_plan_run_grid: this build has no refinement kernel");
+}
+
+extern "C" __attribute__((weak)) int vapor_grid_pick(vapor_ctx*, int64_t, const int32_t*, const double*, const int32_t*, const double*,
+                                                     int32_t*, double*, double*, int64_t*)
+{
+    return bfail(VAPOR_E_ARG, "vapor_grid_pick: this build has no refinement kernel");
+}

@@ -10,6 +10,7 @@
 #include "vapor_anyk.h"
 #include "vapor_bamdev.h"
 #include "vapor_fasta.h"
+#include "vapor_refine.h"
 #include "vapor_hip.h"
 
 #include <unistd.h>
@@ -281,6 +282,16 @@ struct vapor_plan {
     std::vector<DServe> serve;                 // per pair: where its records come from when a shared join serves it
     DServe* d_serve = nullptr;
     int32_t* d_clean_order = nullptr;          // the pairs in the order their clean workgroups are dealt out (longest first)
+    // breakpoint refinement (vapor_plan_set_grid): groups of consecutive loci, each one locus's candidates (grid_pick_kernel)
+    std::vector<int32_t> h_locus_first;        // host copy of d_locus_first
+    int64_t n_groups = 0, n_grid_scores = 0;
+    std::vector<int32_t> grid_score_off;       // per group: its first slot among the winners' scores
+    int32_t* d_grid = nullptr;                 // one block: first_locus[n_groups + 1], score_off[n_groups + 1], winner_idx[n_groups]
+    double* d_group_out = nullptr;             // 16 doubles a group: the winner's record, candidate 0's record
+    double* d_winner_scores = nullptr;
+    int32_t* grid_idx_out = nullptr;           // host buffers of the vapor_plan_run_grid in progress
+    double* grid_rec_out = nullptr;
+    double* grid_scores_out = nullptr;
 };
 
 // ------------------------------------------------------------------------------------------
@@ -1613,6 +1624,10 @@ static void plan_free_device(vapor_plan* p)
     dfree(p->ctx, p->d_maps); p->d_maps = nullptr;
     dfree(p->ctx, p->d_serve); p->d_serve = nullptr;
     dfree(p->ctx, p->d_clean_order); p->d_clean_order = nullptr;
+    dfree(p->ctx, p->d_grid); p->d_grid = nullptr;
+    dfree(p->ctx, p->d_group_out); p->d_group_out = nullptr;
+    dfree(p->ctx, p->d_winner_scores); p->d_winner_scores = nullptr;
+    p->n_groups = 0;
 }
 
 extern "C" int vapor_plan_destroy(vapor_plan* p)
@@ -3008,6 +3023,57 @@ extern "C" int vapor_plan_set_reads(vapor_plan* p, int64_t n_reads, const vapor_
     }
     p->n_reads = n_reads;
     p->n_loci = n_loci;
+    p->h_locus_first = first;
+    // (a grid described for an earlier read table does not describe this one)
+    dfree(p->ctx, p->d_grid); dfree(p->ctx, p->d_group_out); dfree(p->ctx, p->d_winner_scores);
+    p->d_grid = nullptr; p->d_group_out = nullptr; p->d_winner_scores = nullptr; p->n_groups = 0;
+    return VAPOR_OK;
+}
+
+// Breakpoint refinement: the loci are the candidates of n_groups refined loci, group g the loci first_locus[g] ..
+// first_locus[g + 1].  Every candidate of a group scores the group's reads, so all of them have one read count (lf: the loci's
+// read ranges); off[g] .. off[g + 1]: the group's slots among the winners' scores.  Everything grid_pick_kernel indexes with
+// is checked here.
+static int grid_check(int64_t n_groups, const int32_t* first_locus, int64_t n_loci, const int32_t* lf, std::vector<int32_t>* off)
+{
+    if (first_locus[0] != 0 || first_locus[n_groups] != n_loci) return fail(VAPOR_E_ARG, "grid: the groups must cover the loci");
+    off->assign((size_t)n_groups + 1, 0);
+    for (int64_t g = 0; g < n_groups; ++g) {
+        const int32_t a = first_locus[g], b = first_locus[g + 1];
+        if (a < 0 || b <= a || b - a > VAPOR_MAX_CANDIDATES || b > n_loci)
+            return fail(VAPOR_E_ARG, "grid: a group holds 1 .. VAPOR_MAX_CANDIDATES consecutive loci");
+        const int32_t nr = lf[(size_t)a + 1] - lf[a];
+        if (nr < 0) return fail(VAPOR_E_ARG, "grid: read ranges must not decrease");
+        for (int32_t c = a; c < b; ++c)
+            if (lf[(size_t)c + 1] - lf[c] != nr) return fail(VAPOR_E_ARG, "grid: the candidates of a group score the same reads");
+        if ((int64_t)(*off)[g] + nr > INT32_MAX) return fail(VAPOR_E_ARG, "grid: too many reads");
+        (*off)[g + 1] = (*off)[g] + nr;
+    }
+    return VAPOR_OK;
+}
+
+extern "C" int vapor_plan_set_grid(vapor_plan* p, int64_t n_groups, const int32_t* first_locus)
+{
+    if (!p || n_groups < 0 || !first_locus) return fail(VAPOR_E_ARG, "vapor_plan_set_grid: null argument");
+    if (!p->d_reads) return fail(VAPOR_E_ARG, "vapor_plan_set_grid: call vapor_plan_set_reads first");
+    HIPCHK(hipSetDevice(p->ctx->device));
+    std::vector<int32_t> off;
+    const int rc = grid_check(n_groups, first_locus, p->n_loci, p->h_locus_first.data(), &off);
+    if (rc != VAPOR_OK) return rc;
+    dfree(p->ctx, p->d_grid); dfree(p->ctx, p->d_group_out); dfree(p->ctx, p->d_winner_scores);
+    p->d_grid = nullptr; p->d_group_out = nullptr; p->d_winner_scores = nullptr; p->n_groups = 0;
+    if (n_groups == 0) return VAPOR_OK;
+    const size_t ng = (size_t)n_groups;
+    std::vector<int32_t> block(3 * ng + 2, 0);
+    memcpy(block.data(), first_locus, sizeof(int32_t) * (ng + 1));
+    memcpy(block.data() + ng + 1, off.data(), sizeof(int32_t) * (ng + 1));
+    HIPCHK(dmalloc(p->ctx, (void**)&p->d_grid, sizeof(int32_t) * block.size()));
+    HIPCHK(dmalloc(p->ctx, (void**)&p->d_group_out, sizeof(double) * 16 * ng));
+    HIPCHK(dmalloc(p->ctx, (void**)&p->d_winner_scores, sizeof(double) * (size_t)std::max<int32_t>(off[ng], 1)));
+    HIPCHK(hipMemcpy(p->d_grid, block.data(), sizeof(int32_t) * block.size(), hipMemcpyHostToDevice));
+    p->grid_score_off = off;
+    p->n_grid_scores = off[ng];
+    p->n_groups = n_groups;
     return VAPOR_OK;
 }
 
@@ -3050,6 +3116,18 @@ extern "C" int vapor_plan_run_loci(vapor_plan* p, void* d_loci_out, double* loci
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipEventRecord(e1, st));
+    if (p->n_groups > 0 && p->n_loci > 0) {
+        // the choice among each group's candidates, behind the finish kernel on its stream (no host step in between)
+        const size_t ng = (size_t)p->n_groups;
+        int32_t* d_idx = p->d_grid + 2 * ng + 2;
+        hipLaunchKernelGGL(grid_pick_kernel, dim3((unsigned)ng), dim3(64), 0, st, d_out, p->d_grid, p->d_locus_first, p->d_read_scores,
+                           p->d_grid + ng + 1, d_idx, p->d_group_out, p->d_winner_scores);
+        HIPCHK(hipGetLastError());
+        if (p->grid_idx_out) HIPCHK(hipMemcpyAsync(p->grid_idx_out, d_idx, sizeof(int32_t) * ng, hipMemcpyDeviceToHost, st));
+        if (p->grid_rec_out) HIPCHK(hipMemcpyAsync(p->grid_rec_out, p->d_group_out, sizeof(double) * 16 * ng, hipMemcpyDeviceToHost, st));
+        if (p->grid_scores_out && p->n_grid_scores)
+            HIPCHK(hipMemcpyAsync(p->grid_scores_out, p->d_winner_scores, sizeof(double) * (size_t)p->n_grid_scores, hipMemcpyDeviceToHost, st));
+    }
     // only the overflow count has to come back (after the finish kernel, so that nothing sits between the kernels)
     HIPCHK(hipMemcpyAsync(p->h_overflow, p->d_overflow, 2 * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
     if (loci_out && p->n_loci)
@@ -3079,6 +3157,73 @@ extern "C" int vapor_plan_run_loci(vapor_plan* p, void* d_loci_out, double* loci
     return VAPOR_OK;
 }
 
+// vapor_plan_run_loci with the choice among each group's candidates behind it (grid_pick_kernel): per group the winner's index
+// among its candidates, 16 doubles (the winner's record, candidate 0's), and the winner's per-read scores (group g's at
+// score_off[g] .. score_off[g + 1]; a skipped read is NaN).  Only these cross the link.
+extern "C" int vapor_plan_run_grid(vapor_plan* p, int32_t* winner_idx, double* group_out, double* winner_scores, int64_t* score_off)
+{
+    if (!p) return fail(VAPOR_E_ARG, "vapor_plan_run_grid: null plan");
+    if (p->n_groups <= 0 || !p->d_grid) return fail(VAPOR_E_ARG, "vapor_plan_run_grid: call vapor_plan_set_grid first");
+    if (score_off)
+        for (int64_t g = 0; g <= p->n_groups; ++g) score_off[g] = p->grid_score_off[(size_t)g];
+    p->grid_idx_out = winner_idx; p->grid_rec_out = group_out; p->grid_scores_out = winner_scores;
+    const int rc = vapor_plan_run_loci(p, nullptr, nullptr, nullptr);
+    p->grid_idx_out = nullptr; p->grid_rec_out = nullptr; p->grid_scores_out = nullptr;
+    return rc;
+}
+
+// grid_pick_kernel on the caller's tables (records and scores computed elsewhere; the tests' hand-made ones): one call, host
+// arrays in and out.
+extern "C" int vapor_grid_pick(vapor_ctx* ctx, int64_t n_groups, const int32_t* first_locus, const double* records,
+                               const int32_t* read_first, const double* read_scores, int32_t* winner_idx, double* group_out,
+                               double* winner_scores, int64_t* score_off)
+{
+    if (!ctx || n_groups < 0 || !first_locus || !records || !read_first) return fail(VAPOR_E_ARG, "vapor_grid_pick: null argument");
+    HIPCHK(hipSetDevice(ctx->device));
+    const int64_t n_loci = first_locus[n_groups];
+    if (n_loci < 0 || n_loci > INT32_MAX || read_first[0] != 0) return fail(VAPOR_E_ARG, "vapor_grid_pick: bad ranges");
+    for (int64_t c = 0; c < n_loci; ++c)
+        if (read_first[c + 1] < read_first[c]) return fail(VAPOR_E_ARG, "vapor_grid_pick: read ranges must not decrease");
+    std::vector<int32_t> off;
+    const int rc = grid_check(n_groups, first_locus, n_loci, read_first, &off);
+    if (rc != VAPOR_OK) return rc;
+    if (score_off)
+        for (int64_t g = 0; g <= n_groups; ++g) score_off[g] = off[(size_t)g];
+    if (n_groups == 0) return VAPOR_OK;
+    const size_t ng = (size_t)n_groups, nl = (size_t)n_loci, nr = (size_t)read_first[n_loci], nw = (size_t)off[ng];
+    if (nr && !read_scores) return fail(VAPOR_E_ARG, "vapor_grid_pick: null argument");
+    std::vector<int32_t> block(3 * ng + 2 + nl + 1, 0);
+    memcpy(block.data(), first_locus, sizeof(int32_t) * (ng + 1));
+    memcpy(block.data() + ng + 1, off.data(), sizeof(int32_t) * (ng + 1));
+    memcpy(block.data() + 3 * ng + 2, read_first, sizeof(int32_t) * (nl + 1));
+    int32_t* d_block = nullptr;
+    double *d_rec = nullptr, *d_sc = nullptr, *d_out = nullptr, *d_win = nullptr;
+    hipStream_t st = ctx->stream;
+    int res = VAPOR_OK;
+    auto step = [&](hipError_t e, const char* what) {
+        if (res == VAPOR_OK && e != hipSuccess) res = fail(VAPOR_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
+        return res == VAPOR_OK;
+    };
+    if (step(dmalloc(ctx, (void**)&d_block, sizeof(int32_t) * block.size()), "dmalloc") &&
+        step(dmalloc(ctx, (void**)&d_rec, sizeof(double) * 8 * nl), "dmalloc") &&
+        step(dmalloc(ctx, (void**)&d_sc, sizeof(double) * std::max<size_t>(nr, 1)), "dmalloc") &&
+        step(dmalloc(ctx, (void**)&d_out, sizeof(double) * 16 * ng), "dmalloc") &&
+        step(dmalloc(ctx, (void**)&d_win, sizeof(double) * std::max<size_t>(nw, 1)), "dmalloc") &&
+        step(hipMemcpyAsync(d_block, block.data(), sizeof(int32_t) * block.size(), hipMemcpyHostToDevice, st), "hipMemcpyAsync") &&
+        step(hipMemcpyAsync(d_rec, records, sizeof(double) * 8 * nl, hipMemcpyHostToDevice, st), "hipMemcpyAsync") &&
+        (nr == 0 || step(hipMemcpyAsync(d_sc, read_scores, sizeof(double) * nr, hipMemcpyHostToDevice, st), "hipMemcpyAsync"))) {
+        int32_t* d_idx = d_block + 2 * ng + 2;
+        hipLaunchKernelGGL(grid_pick_kernel, dim3((unsigned)ng), dim3(64), 0, st, d_rec, d_block, d_block + 3 * ng + 2, d_sc,
+                           d_block + ng + 1, d_idx, d_out, d_win);
+        step(hipGetLastError(), "grid_pick_kernel");
+        if (winner_idx) step(hipMemcpyAsync(winner_idx, d_idx, sizeof(int32_t) * ng, hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
+        if (group_out) step(hipMemcpyAsync(group_out, d_out, sizeof(double) * 16 * ng, hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
+        if (winner_scores && nw) step(hipMemcpyAsync(winner_scores, d_win, sizeof(double) * nw, hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
+    }
+    (void)hipStreamSynchronize(st);
+    dfree(ctx, d_block); dfree(ctx, d_rec); dfree(ctx, d_sc); dfree(ctx, d_out); dfree(ctx, d_win);
+    return res;
+}
 
 // ------------------------------------------------------------------------------------------
 // Host helper of the read extraction: cigar2alignstart_by_pos, SF:309-337.  Walks the CIGAR until the

@@ -43,6 +43,16 @@ class Score:
         self.kind, self.ref_seq, self.alt_seq, self.reads, self.k = kind, ref_seq, alt_seq, reads, k
 
 
+class ScoreGrid:
+    """Breakpoint refinement (vapor_refine): one window, one set of reads, `alts` = the candidate alleles (each a _cat of
+    slices of `ref_seq`; the first is the call itself), all scored as Score(kind, ref_seq, alt, reads, k) would be.  Result: a
+    refine.GridResult - the winner among the candidates (refine.pick), its per-read scores, its record and candidate 0's."""
+    __slots__ = ("kind", "ref_seq", "alts", "reads", "k")
+
+    def __init__(self, kind, ref_seq, alts, reads, k):
+        self.kind, self.ref_seq, self.alts, self.reads, self.k = kind, ref_seq, list(alts), reads, k
+
+
 class Figure:
     """make_event_figure_1 (SF:1072-1089) request; executors may render it or drop it."""
     __slots__ = ("scores", "best_read", "k", "ref_seq", "alt_seq", "name")
@@ -265,6 +275,70 @@ def vapor_simple_tandup(num_reads_cff, plt_li, bam_in, ref, sv_info, out_figure_
                 res = yield Score("s2", ref_seq, alt_seq, reads, k)
                 best = _collect(res, reads, scores)
                 yield Figure(scores, best, k, ref_seq, alt_seq, out_figure_name)
+    return scores
+
+
+_REFINE_BASE = {"DEL": vapor_simple_del, "INV": vapor_simple_inv, "TANDUP": vapor_simple_tandup}
+_REFINE_KIND = {"DEL": "del", "INV": "s1", "TANDUP": "s3"}
+
+
+def refine_allele(svtype, window, flank, margin, ds, de):
+    """The alt allele of candidate (ds, de) on the widened window W = ref[s - M - F : e + M + F]: with L = W[:F + M + ds],
+    R = W[-(F + M - de):] and mid what lies between, DEL L + R, INV L + rc(mid) + R, TANDUP L + mid + mid + R.  At M = 0 these
+    are the alleles of vapor_simple_del / _inv / _tandup (SF:1712, 1907, 1755)."""
+    lo, hi = flank + margin + ds, -(flank + margin - de)
+    if svtype == "DEL":
+        return _cat((window, None, lo), (window, hi, None))
+    if svtype == "INV":
+        return _cat((window, None, lo), (window, lo, hi, True), (window, hi, None))
+    return _cat((window, None, lo), (window, lo, hi), (window, lo, hi), (window, hi, None))
+
+
+def vapor_refine(svtype, num_reads_cff, plt_li, bam_in, ref, sv_info, out_figure_name, margin, step, cipos=None, ciend=None):
+    """`--refine M[:T]` (not in the reference) for a DEL, INV or TANDUP record: the short branch of the type's
+    driver for the widened record [c, s - M, e + M] with the flank of the called record - its window, its reads, its gates in
+    its order - and, instead of one allele, the grid of candidate breakpoints (refine.candidates) as one ScoreGrid request.
+    Returns the winner's scores as a refine.Refined (info = the winner's a and b, candidate 0's QS, GS and positive scores).  A locus the
+    short branch would not score that way - a long record, a window check that fails, too few reads - is not refined: the
+    type's own driver runs on the called record, exactly as without the option, and its plain list comes back."""
+    from . import refine
+    base = _REFINE_BASE[svtype]
+    c, s, e = sv_info[0], sv_info[1], sv_info[2]
+    flank = seqio.flank_length_calculate(sv_info)
+    wide = [c, s - margin, e + margin]
+    grid = None
+    if e - s < default_max_sv_test and wide[2] - wide[1] < default_max_sv_test and wide[1] - flank >= 1:
+        cands = refine.candidates(margin, step, s, e, cipos, ciend)
+
+        def alts(window):
+            return [refine_allele(svtype, window, flank, margin, ds, de) for ds, de in cands]
+        if svtype == "DEL":
+            reads = seqio.simple_del_chop_pacbio_read_simple_short(bam_in, wide, flank)
+            if len(reads) > num_reads_cff:
+                ref_seq = seqio.ref_seq_readin(ref, c, wide[1] - flank, wide[2] + flank)
+                k = yield from _window(ref_seq)
+                if not k == "Error":
+                    grid = (ref_seq, alts(ref_seq), reads, k)
+        else:
+            ref_seq = seqio.ref_seq_readin(ref, c, wide[1] - flank, wide[2] + flank)
+            k = yield from _window(ref_seq)
+            if not k == "Error":
+                cand_alts = alts(ref_seq)
+                k = yield from _window(cand_alts[0])           # (one k per locus: the candidates' scores are comparable)
+                if not k == "Error":
+                    end = wide[2] if svtype == "INV" else wide[1] + 2 * (wide[2] - wide[1])
+                    reads = seqio.simple_chop_pacbio_read_simple_short(bam_in, wide[:2] + [end], flank)
+                    if len(reads) > num_reads_cff:
+                        grid = (ref_seq, cand_alts, reads, k)
+    if grid is None:
+        return (yield from base(num_reads_cff, plt_li, bam_in, ref, sv_info, out_figure_name))
+    ref_seq, cand_alts, reads, k = grid
+    got = yield ScoreGrid(_REFINE_KIND[svtype], ref_seq, cand_alts, reads, k)
+    scores = refine.Refined()
+    best = _collect(got.scores, reads, scores)
+    ds, de = cands[got.winner]
+    scores.info = (float(s + ds), float(e + de), float(got.rec0[0]), float(got.rec0[1]), float(got.rec0[5]))
+    yield Figure(scores, best, k, ref_seq, cand_alts[got.winner], out_figure_name)
     return scores
 
 

@@ -269,6 +269,32 @@ class Plan:
                                              L.ptr(self.read_scores, ctypes.c_double) if want_scores else None))
         return self.loci[:self.n_loci]
 
+    def set_grid(self, first_locus: np.ndarray) -> None:
+        """Breakpoint refinement (vapor_plan_set_grid): the plan's loci are candidates, group g the loci first_locus[g] ..
+        first_locus[g + 1].  NotImplementedError when the loaded library has no refinement kernel (the CPU twin)."""
+        fn = Engine._wide_entry("vapor_plan_set_grid", "refinement kernel")
+        self.first_locus = np.ascontiguousarray(first_locus, dtype=np.int32)
+        self.n_groups = len(self.first_locus) - 1
+        L.check(fn(self._h, self.n_groups, L.ptr(self.first_locus, ctypes.c_int32)))
+
+    def run_grid(self):
+        """vapor_plan_run_grid: join -> clean -> finish -> the choice among each group's candidates, on the device.  Returns
+        (winner index per group, (n_groups, 16) float64: the winner's record and candidate 0's, the winners' per-read scores,
+        score_off (n_groups + 1,): group g's scores are winner_scores[score_off[g]:score_off[g + 1]])."""
+        fn = Engine._wide_entry("vapor_plan_run_grid", "refinement kernel")
+        ng = self.n_groups
+        lf = np.zeros(self.n_loci + 1, dtype=np.int64)
+        np.cumsum(np.bincount(self.reads["locus"], minlength=self.n_loci), out=lf[1:])
+        n_sc = int((lf[self.first_locus[:-1] + 1] - lf[self.first_locus[:-1]]).sum()) if ng else 0
+        idx = np.zeros(max(ng, 1), dtype=np.int32)
+        rec = np.zeros((max(ng, 1), 2 * L.LOCUS_STRIDE), dtype=np.float64)
+        sc = np.zeros(max(n_sc, 1), dtype=np.float64)
+        off = np.zeros(ng + 1, dtype=np.int64)
+        L.check(fn(self._h, L.ptr(idx, ctypes.c_int32), L.ptr(rec, ctypes.c_double), L.ptr(sc, ctypes.c_double), L.ptr(off, ctypes.c_int64)))
+        if int(off[ng]) != n_sc:
+            raise RuntimeError("vapor_plan_run_grid: %d winner scores, %d expected" % (int(off[ng]), n_sc))
+        return idx[:ng], rec[:ng], sc[:n_sc], off
+
     def run_loci_async(self, device_out: int = 0) -> None:
         """Enqueue join -> clean -> finish without waiting (after one run_loci(), which sizes the slots)."""
         L.check(L.load().vapor_plan_run_loci_async(self._h, ctypes.c_void_p(device_out) if device_out else None))
@@ -456,12 +482,12 @@ class Engine:
 
     # ---- the wide route: sequences longer than MAX_SEQ_LEN (up to MAX_WIDE_SEQ_LEN) ----
     @staticmethod
-    def _wide_entry(name: str):
+    def _wide_entry(name: str, what: str = "wide route"):
         lib = L.load()
         # (the CPU twin of the C ABI exports the names with a stub that refuses every call: it has no wide route either)
         flags = lib.vapor_build_flags() if hasattr(lib, "vapor_build_flags") else b""
         if not hasattr(lib, name) or "cpu-twin" in (flags or b"").decode().split(","):
-            raise NotImplementedError("%s: the loaded library has no wide route" % name)
+            raise NotImplementedError("%s: the loaded library has no %s" % (name, what))
         return getattr(lib, name)
 
     def wide_available(self) -> bool:
@@ -500,6 +526,37 @@ class Engine:
             h = hits[off[t]:off[t + 1]]
             out.append(h[np.lexsort((h[:, 1], h[:, 0]))])
         return st[:n], out
+
+    def grid_available(self) -> bool:
+        """Whether the loaded library has breakpoint refinement's device step (the CPU twin of the C ABI has not)."""
+        try:
+            self._wide_entry("vapor_plan_set_grid", "refinement kernel")
+            self._wide_entry("vapor_plan_run_grid", "refinement kernel")
+        except NotImplementedError:
+            return False
+        return True
+
+    def grid_pick(self, records: np.ndarray, first_locus, read_first, read_scores):
+        """vapor_grid_pick: grid_pick_kernel on the caller's tables - (n, 8) candidate records, groups first_locus[g] ..
+        first_locus[g + 1], candidate c's per-read scores read_scores[read_first[c]:read_first[c + 1]].  Returns what
+        Plan.run_grid returns."""
+        fn = self._wide_entry("vapor_grid_pick", "refinement kernel")
+        rec = np.ascontiguousarray(records, dtype=np.float64).reshape(-1, L.LOCUS_STRIDE)
+        fl = np.ascontiguousarray(first_locus, dtype=np.int32)
+        rf = np.ascontiguousarray(read_first, dtype=np.int32)
+        sc = np.ascontiguousarray(read_scores, dtype=np.float64)
+        ng = len(fl) - 1
+        if len(rf) != len(rec) + 1 or int(fl[-1]) != len(rec) or (len(rf) and int(rf[-1]) != len(sc)):
+            raise ValueError("grid_pick: the tables do not describe each other")
+        n_sc = int((rf[fl[:-1] + 1] - rf[fl[:-1]]).sum()) if ng else 0
+        idx = np.zeros(max(ng, 1), dtype=np.int32)
+        out = np.zeros((max(ng, 1), 2 * L.LOCUS_STRIDE), dtype=np.float64)
+        win = np.zeros(max(n_sc, 1), dtype=np.float64)
+        off = np.zeros(ng + 1, dtype=np.int64)
+        L.check(fn(self._ctx, ng, L.ptr(fl, ctypes.c_int32), L.ptr(rec if len(rec) else np.zeros((1, 8)), ctypes.c_double), L.ptr(rf, ctypes.c_int32),
+                   L.ptr(sc if len(sc) else np.zeros(1), ctypes.c_double), L.ptr(idx, ctypes.c_int32), L.ptr(out, ctypes.c_double),
+                   L.ptr(win, ctypes.c_double), L.ptr(off, ctypes.c_int64)))
+        return idx[:ng], out[:ng], win[:n_sc], off
 
     # ---- the any-k route: kmerhits at every k from 1 to MAX_ANY_K ----
     def anyk_available(self) -> bool:

@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _lib as L
 from . import repeat_qc
-from .drivers import Figure, Score, Window
+from .drivers import Figure, Score, ScoreGrid, Window
 
 import threading
 
@@ -353,37 +353,35 @@ def score_requests_wide(engine, reqs: Sequence[Score], anyk: bool = False) -> Li
     return out
 
 
-def _score_requests_narrow(engine, reqs: Sequence[Score]) -> List[object]:
-    """Evaluates every Score request on the device, per-read reduction included (finish_kernel): per request a list
-    with one score (float) or None per read, or the exception the reference would raise (KeyError for a read with a
-    base outside invert_base's alphabet, SF:1421).
+class _SetBuilder:
+    """The sequences of one device batch: `seqs` travel as bytes (windows, insertion payloads, reads), `derived` are described
+    instead (drivers.Allele.segs; the str.upper() twins of abs_dis_m1b) as (segments, upper)."""
 
-    One sequence set and one plan for all requests: request t is "locus" t of the plan, its reads are the plan's
-    reads in order.  The arrays are put together with numpy per request, not per read."""
-    seqs: List[str] = []              # sequences that travel as bytes: windows, insertion payloads, reads
-    derived: List[tuple] = []         # sequences described instead (drivers.Allele.segs; the str.upper() twins of abs_dis_m1b): (segments, upper)
-    lit_of: Dict[int, int] = {}       # id(string) -> its index among the literals (a window is uploaded once per batch)
-    nocomp_of: Dict[int, bool] = {}
+    def __init__(self):
+        self.seqs: List[str] = []
+        self.derived: List[tuple] = []
+        self.lit_of: Dict[int, int] = {}       # id(string) -> its index among the literals (a window is uploaded once per batch)
+        self.nocomp_of: Dict[int, bool] = {}
+        self.derived_of: Dict[tuple, int] = {}  # (id(string), upper) -> its derived index: requests that share a window share its twins too
 
-    def lit(sq: str) -> int:
-        q = lit_of.get(id(sq))
+    def lit(self, sq: str) -> int:
+        q = self.lit_of.get(id(sq))
         if q is None:
-            q = lit_of[id(sq)] = len(seqs)
-            seqs.append(sq)
+            q = self.lit_of[id(sq)] = len(self.seqs)
+            self.seqs.append(sq)
         return q
 
-    derived_of: Dict[tuple, int] = {}  # (id(string), upper) -> its derived index: requests that share a window share its twins too
-
-    def describe(sq, up: bool) -> int:
-        got = derived_of.get((id(sq), up))
+    def describe(self, sq, up: bool) -> int:
+        got = self.derived_of.get((id(sq), up))
         if got is not None:
             return got
-        got = derived_of[(id(sq), up)] = _describe(sq, up)
+        got = self.derived_of[(id(sq), up)] = self._describe(sq, up)
         return got
 
-    def _describe(sq, up: bool) -> int:
+    def _describe(self, sq, up: bool) -> int:
         """Index of `sq` (upper-cased when `up`) in the set: a literal, or - (d + 1) for derived sequence d (their place behind
         the literals is known when all literals are)."""
+        derived, lit = self.derived, self.lit
         segs = getattr(sq, "segs", None)
         if segs is not None and len(segs) > L.MAX_SEGMENTS:
             segs = None               # (more blocks than a descriptor holds, include/vapor_hip.h: this allele travels as bytes)
@@ -391,9 +389,9 @@ def _score_requests_narrow(engine, reqs: Sequence[Score]) -> List[object]:
             # (a reversed slice needs a parent complementary() keeps whole, SF:471-478: the library checks the same)
             for par, _o, _n, rc in segs:
                 if rc:
-                    bad = nocomp_of.get(id(par))
+                    bad = self.nocomp_of.get(id(par))
                     if bad is None:
-                        bad = nocomp_of[id(par)] = _NOCOMP.search(par) is not None
+                        bad = self.nocomp_of[id(par)] = _NOCOMP.search(par) is not None
                     if bad:
                         segs = None
                         break
@@ -404,6 +402,17 @@ def _score_requests_narrow(engine, reqs: Sequence[Score]) -> List[object]:
             derived.append(([(lit(sq), 0, len(sq), False)], True))
             return -len(derived)
         return lit(sq)
+
+
+def _score_requests_narrow(engine, reqs: Sequence[Score]) -> List[object]:
+    """Evaluates every Score request on the device, per-read reduction included (finish_kernel): per request a list
+    with one score (float) or None per read, or the exception the reference would raise (KeyError for a read with a
+    base outside invert_base's alphabet, SF:1421).
+
+    One sequence set and one plan for all requests: request t is "locus" t of the plan, its reads are the plan's
+    reads in order.  The arrays are put together with numpy per request, not per read."""
+    sb = _SetBuilder()
+    seqs, derived, describe = sb.seqs, sb.derived, sb.describe
 
     # per request: scalars only; the per-read and per-pair columns are expanded from them in one go below
     rq_n, rq_k, rq_kind, rq_lref, rq_lalt, rq_blk_a, rq_blk_b = [], [], [], [], [], [], []
@@ -522,6 +531,170 @@ def _score_requests_narrow(engine, reqs: Sequence[Score]) -> List[object]:
     return out
 
 
+# ------------------------------------------------------------------------------------------
+# breakpoint refinement: grids of candidate alleles (drivers.ScoreGrid)
+# ------------------------------------------------------------------------------------------
+GRID_PAIRS_PER_PLAN = 150000      # a plan of grids is sized by pairs, not by loci (121 candidates x 20 reads: some 5 000 pairs a locus;
+                                  # a chunk of 2 048 unrefined loci makes a plan of about as many pairs)
+
+
+def has_grid(engine) -> bool:
+    """Whether `engine` has breakpoint refinement's device step (vapor_plan_set_grid / vapor_plan_run_grid): an engine that
+    can say so (Engine.grid_available) over a library that has it.  The tests' stand-in and the CPU twin have not."""
+    avail = getattr(engine, "grid_available", None)
+    return bool(avail()) if callable(avail) else False
+
+
+def score_grids(engine, reqs: Sequence[object], route: Optional[str] = None, want_all: bool = False) -> List[object]:
+    """Evaluates every ScoreGrid request: per request a refine.GridResult, or the exception its scoring ended with.
+    route 'batched': one sequence set and one plan for many grids, the choice on the device (_score_grids_batched);
+    'brute': refine.score_grid_brute per request; None: VAPOR_REFINE_ROUTE, else batched where the engine has the device step.
+    A request the narrow route refuses (a window size other than 10/20/30/40, a sequence longer than MAX_SEQ_LEN) goes the
+    brute-force way on either route, where the wide and any-k routes take it."""
+    import os
+    from . import refine
+    route = route or os.environ.get("VAPOR_REFINE_ROUTE") or ("batched" if has_grid(engine) else "brute")
+    if route not in ("batched", "brute"):
+        raise ValueError("refinement route %r (batched | brute)" % route)
+    if route == "batched" and not has_grid(engine):
+        raise NotImplementedError("the loaded library has no refinement kernel (vapor_plan_run_grid)")
+    out: List[object] = [None] * len(reqs)
+    fast = []
+    for t, r in enumerate(reqs):
+        narrow = (not k_unsupported(r.k) and len(r.reads) > 0 and 0 < len(r.alts) <= L.MAX_CANDIDATES
+                  and max([len(r.ref_seq)] + [len(a) for a in r.alts] + [len(x[0]) for x in r.reads]) <= L.MAX_SEQ_LEN)
+        if route == "batched" and narrow:
+            fast.append(t)
+        else:
+            out[t] = refine.score_grid_brute(engine, r)
+    # plans by pairs: a grid request holds (candidates + 1) x reads x blocks pairs
+    batch, n_pairs = [], 0
+    for t in fast + [None]:
+        cost = 0 if t is None else 2 * (len(reqs[t].alts) + 1) * len(reqs[t].reads)
+        if batch and (t is None or n_pairs + cost > GRID_PAIRS_PER_PLAN):
+            for q, v in zip(batch, _score_grids_batched(engine, [reqs[q] for q in batch], want_all)):
+                out[q] = v
+            batch, n_pairs = [], 0
+        if t is not None:
+            batch.append(t)
+            n_pairs += cost
+    return out
+
+
+def _score_grids_batched(engine, reqs: Sequence[object], want_all: bool = False) -> List[object]:
+    """The batched route: one sequence set and one plan for all requests.  Per request the window and every read are uploaded
+    once and every candidate allele is a derived sequence of the window; the pairs are (read, window) once per read and
+    block of pairs (the upper-cased and the plain block of a soft-masked deletion, as _score_requests_narrow cuts them) plus
+    (read, candidate) per candidate; the read table has a row per (candidate, read) whose ref_a / ref_b point at the shared
+    (read, window) pair; the plan's loci are the candidates and its groups the requests (Plan.set_grid).  finish_kernel
+    scores every candidate, grid_pick_kernel behind it chooses; the winners' records and scores come back."""
+    from . import refine
+    sb = _SetBuilder()
+    i32 = np.int32
+    pr_seq1, pr_seq2, pr_off2, pr_k, pr_flags = [], [], [], [], []
+    tb = {f: [] for f in ("ref_a", "alt_a", "ref_b", "alt_b", "kind", "locus", "len_ref", "len_alt")}
+    first_locus = [0]
+    read_q0 = []
+    n_pairs = 0
+    for r in reqs:
+        n, nc = len(r.reads), len(r.alts)
+        soft = r.kind in ("del", "s1") and not (_is_upper(r.ref_seq) and all(_is_upper(a) for a in r.alts))
+        ri = sb.describe(r.ref_seq, False)
+        ai = [sb.describe(a, False) for a in r.alts]
+        if soft:
+            uri, uai = sb.describe(r.ref_seq, True), [sb.describe(a, True) for a in r.alts]
+        else:
+            uri, uai = ri, ai
+        if r.kind == "del" and soft:
+            blocks = [(uri, uai, L.PF_C1), (ri, ai, L.PF_C2)]
+        else:
+            plain = r.kind in ("del", "s2", "s3")
+            blocks = [(ri if plain else uri, ai if plain else uai, L.PF_C1 | L.PF_C2 if r.kind == "del" else _FLAGS[r.kind])]
+        nb = len(blocks)
+        q0 = len(sb.seqs)
+        read_q0.append(q0)
+        sb.seqs.extend(x[0] for x in r.reads)                 # (reads are never shared between requests: no look-up)
+        rd = np.arange(q0, q0 + n, dtype=np.int64)
+        miss = np.asarray([int(x[1]) for x in r.reads], dtype=np.int64)
+        base = n_pairs
+        # pairs: block b's (read, window) at base + b n + i, its (read, candidate c) at base + nb n + (c nb + b) n + i
+        rows = (nc + 1) * nb
+        w_idx = np.asarray([blk[0] for blk in blocks], dtype=np.int64)
+        a_idx = np.asarray([blk[1] for blk in blocks], dtype=np.int64).T.reshape(-1)        # (candidate, block) order
+        pr_seq1.append(np.tile(rd, rows)); pr_off2.append(np.tile(miss, rows))
+        pr_seq2.append(np.repeat(np.concatenate((w_idx, a_idx)), n))
+        pr_flags.append(np.tile(np.repeat(np.asarray([blk[2] for blk in blocks], dtype=np.int64), n), nc + 1))
+        pr_k.append(np.full(rows * n, int(r.k), dtype=np.int64))
+        n_pairs += rows * n
+        it = np.arange(n, dtype=np.int64)
+        cand = np.repeat(np.arange(nc, dtype=np.int64), n)
+        alt_a = base + nb * n + cand * (nb * n) + np.tile(it, nc)
+        tb["ref_a"].append(np.tile(base + it, nc)); tb["alt_a"].append(alt_a)
+        tb["ref_b"].append(np.tile(base + (nb - 1) * n + it, nc)); tb["alt_b"].append(alt_a + (nb - 1) * n)
+        tb["kind"].append(np.full(nc * n, _KIND[r.kind], dtype=np.int64))
+        tb["locus"].append(first_locus[-1] + cand)
+        tb["len_ref"].append(np.full(nc * n, len(r.ref_seq), dtype=np.int64))
+        tb["len_alt"].append(np.repeat(np.asarray([len(x) for x in r.alts], dtype=np.int64), n))
+        first_locus.append(first_locus[-1] + nc)
+    n_lit = len(sb.seqs)
+    pairs = np.zeros(n_pairs, dtype=L.PAIR_DTYPE)
+    pairs["seq1"] = np.concatenate(pr_seq1).astype(i32)
+    s2 = np.concatenate(pr_seq2)
+    pairs["seq2"] = np.where(s2 < 0, n_lit - 1 - s2, s2).astype(i32)      # derived sequence d: behind the literals
+    pairs["off2"] = np.concatenate(pr_off2).astype(i32)
+    pairs["k"] = np.concatenate(pr_k).astype(i32)
+    pairs["flags"] = np.concatenate(pr_flags).astype(np.uint32)
+    n_rows = sum(len(x) for x in tb["kind"])
+    table = np.zeros(n_rows, dtype=L.READ_DTYPE)
+    for f, cols in tb.items():
+        table[f] = np.concatenate(cols).astype(i32)
+    # (the descriptors as arrays, put together in one go: a grid of 121 candidates is some 250 derived sequences)
+    flat = [g for sg, _u in sb.derived for g in sg]
+    seg_first = np.zeros(len(sb.derived) + 1, dtype=i32)
+    np.cumsum([len(sg) for sg, _u in sb.derived], out=seg_first[1:])
+    segs = np.zeros(max(len(flat), 1), dtype=L.SEG_DTYPE)
+    if flat:
+        cols = np.asarray(flat, dtype=np.int64)
+        segs["parent"][:len(flat)], segs["off"][:len(flat)], segs["len"][:len(flat)] = cols[:, 0], cols[:, 1], cols[:, 2]
+        segs["flags"][:len(flat)] = np.where(cols[:, 3] != 0, L.SEG_REVCOMP, 0)
+    dflags = np.asarray([L.SEQ_UPPER if u else 0 for _sg, u in sb.derived], dtype=np.uint8)
+    ss = engine.seqset(sb.seqs, None, (seg_first, segs, dflags)) if sb.derived else engine.seqset(sb.seqs)
+    try:
+        plan = engine.plan(ss, pairs)
+        try:
+            plan.set_reads(table, first_locus[-1])
+            plan.set_grid(np.asarray(first_locus, dtype=i32))
+            widx, rec, wsc, off = plan.run_grid()
+            widx, rec, wsc = widx.copy(), rec.copy(), wsc.copy()
+            if want_all:
+                all_recs = plan.run_loci(want_host=True, want_scores=True).copy()
+                all_sc = plan.read_scores[:n_rows].copy()
+        finally:
+            plan.close()
+        bad_inv = np.asarray(ss.n_invalid) > 0
+        lens = np.asarray(ss.lens)
+    finally:
+        ss.close()
+
+    def as_list(a):
+        return [None if x != x else x for x in a.tolist()]
+    out: List[object] = []
+    row0 = 0
+    for g, r in enumerate(reqs):
+        n, nc = len(r.reads), len(r.alts)
+        q = np.arange(read_q0[g], read_q0[g] + n)
+        if bool((bad_inv[q] & (lens[q] - int(r.k) + 1 > 0)).any()):
+            out.append(KeyError("invert_base"))              # what SF:1421 raises on a base outside ATCGN/atcgn
+        else:
+            res = refine.GridResult(widx[g], rec[g, :L.LOCUS_STRIDE], rec[g, L.LOCUS_STRIDE:], as_list(wsc[off[g]:off[g + 1]]))
+            if want_all:
+                res.all_recs = all_recs[first_locus[g]:first_locus[g + 1]]
+                res.all_scores = [as_list(all_sc[row0 + c * n:row0 + (c + 1) * n]) for c in range(nc)]
+            out.append(res)
+        row0 += nc * n
+    return out
+
+
 def scorer_outputs(engine, kind: str, ref_seq: str, alt_seq: str, x, k):
     """[a, b] of calcu_vapor_single_read_score_{abs_dis_m1b, within_10Perc_m1b, directed_dis_m1b_redefine_diagnal}
     (kind 's1', 's2', 's3'; SF:182-203, 277-294, 241-257) for one read: the two dot plots' statistics from the
@@ -571,6 +744,10 @@ def _answer(engine, reqs: Sequence[object], figure_fn) -> List[object]:
             res[t] = v
     if si:
         for t, v in zip(si, score_requests(engine, [reqs[t] for t in si])):
+            res[t] = v
+    gi = [t for t, r in enumerate(reqs) if isinstance(r, ScoreGrid)]
+    if gi:
+        for t, v in zip(gi, score_grids(engine, [reqs[t] for t in gi])):
             res[t] = v
     if figure_fn is not None:
         figs = [r for r in reqs if isinstance(r, Figure)]

@@ -222,11 +222,11 @@ def path_modify(path):
     return path if path[-1] == '/' else path + '/'
 
 
-def write_output_initiate(out_name):
-    """SF:2079-2082."""
+def write_output_initiate(out_name, more_columns=()):
+    """SF:2079-2082.  `more_columns`: names appended to the header (`--refine`'s four)."""
     with open(out_name, 'w') as fo:
         print('\t'.join(['#CHR', 'POS', 'END', 'SVTYPE', 'SVID', 'VaPoR_QS', 'VaPoR_GS', 'VaPoR_GT', 'VaPoR_GQ',
-                         'VaPoR_Rec']), file=fo)
+                         'VaPoR_Rec'] + list(more_columns)), file=fo)
 
 
 def format_output_row(out_list) -> str:
@@ -301,7 +301,7 @@ def vcf_rec_hash_modify(vcf_rec_hash):
     return out
 
 
-def vcf_vapor_modify(vcf_input, vcf_rec_hash_new, header_offset_compat=False):
+def vcf_vapor_modify(vcf_input, vcf_rec_hash_new, header_offset_compat=False, refined=False):
     """SF:1972-2028 (the second definition, which shadows SF:1942): rewrite <vcf>.vapor as the
     input VCF with ;VaPor_GS=..;VaPor_GT=..;VaPor_GQ=..;VaPor_REC=.. appended to INFO of every
     scored record.
@@ -311,7 +311,9 @@ def vcf_vapor_modify(vcf_input, vcf_rec_hash_new, header_offset_compat=False):
     H header lines it annotates record r+H instead of r, or dies with KeyError.  Both agree, and
     this function matches the reference byte for byte, on header-less input.  Here record indices
     are file line numbers throughout, so headers are fine; header_offset_compat=True reproduces
-    the reference's shifted lookup."""
+    the reference's shifted lookup.  refined (`--refine`): the rows of <vcf>.vapor carry four more fields - the refined
+    breakpoints and candidate 0's QS and GS - which follow as ;VaPor_RPOS=..;VaPor_REND=..;VaPor_QS0=..;VaPor_GS0=.. ('.' for
+    a record that was not refined), with ##INFO lines of their own."""
     vapor_input = vcf_input + '.vapor'
     info = {}
     meta, header = [], []
@@ -338,6 +340,8 @@ def vcf_vapor_modify(vcf_input, vcf_rec_hash_new, header_offset_compat=False):
                     gq = round(float(pin[4]), 2) if not pin[4] == 'NA' else pin[4]
                     info[y][7] += (';VaPor_GS=' + str(gs) + ';VaPor_GT=' + str(pin[3]) + ';VaPor_GQ=' + str(gq)
                                    + ';VaPor_REC=' + str(pin[5]))
+                    if refined:
+                        info[y][7] += ';VaPor_RPOS=%s;VaPor_REND=%s;VaPor_QS0=%s;VaPor_GS0=%s' % tuple(pin[6:10])
                     keep.append(y)
     with open(vapor_input, 'w') as fo:
         prev = ''
@@ -349,6 +353,11 @@ def vcf_vapor_modify(vcf_input, vcf_rec_hash_new, header_offset_compat=False):
                 print('##INFO=<ID=VaPoR_GT,Number=1,Type=String,Description="Genotype with the highest likelihood as estimated by VaPoR">', file=fo)
                 print('##INFO=<ID=VaPoR_GQ,Number=1,Type=Float,Description="Genotype quality score - likelihood of the second most likely genotype on a -log10 normalized scale"', file=fo)
                 print('##INFO=<ID=VaPoR_REC,Number=.,Type=Float,Description="Similarity scores assigned to each of the reads traversings the predicted SV">', file=fo)
+                if refined:
+                    print('##INFO=<ID=VaPoR_RPOS,Number=1,Type=Integer,Description="Start of the best-scoring candidate breakpoint pair (--refine)">', file=fo)
+                    print('##INFO=<ID=VaPoR_REND,Number=1,Type=Integer,Description="End of the best-scoring candidate breakpoint pair (--refine)">', file=fo)
+                    print('##INFO=<ID=VaPoR_QS0,Number=1,Type=Float,Description="VaPoR_QS of the called breakpoints on the widened window (--refine)">', file=fo)
+                    print('##INFO=<ID=VaPoR_GS0,Number=1,Type=Float,Description="VaPoR_GS of the called breakpoints on the widened window (--refine)">', file=fo)
             print(joined, file=fo)
             prev = cur
         print('\t'.join(header), file=fo)
