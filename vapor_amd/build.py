@@ -10,13 +10,14 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SO = os.path.join(HERE, "libvapor_hip.so")
-SOURCES = [os.path.join(HERE, "csrc", "vapor_hip.hip"), os.path.join(HERE, "csrc", "vapor_bam.cpp")]
-DEPS = SOURCES + [os.path.join(HERE, "csrc", "vapor_kernels.h"), os.path.join(HERE, "csrc", "vapor_wide.h"), os.path.join(HERE, "csrc", "vapor_anyk.h"),
-                  os.path.join(HERE, "csrc", "vapor_inflate.h"),
-                  os.path.join(HERE, "csrc", "vapor_bamdev.h"), os.path.join(HERE, "csrc", "vapor_fasta.h"),
-                  os.path.join(HERE, "csrc", "vapor_refine.h"),
-                  os.path.join(ROOT, "include", "vapor_hip.h")]
-
+CSRC = os.path.join(HERE, "csrc")
+SOURCES = [os.path.join(CSRC, "vapor_hip.hip"), os.path.join(CSRC, "vapor_bam.cpp")]
+# The csrc headers, once, in the order both lists below keep.  The ones that hold device code are part of kernel_source_id();
+# vapor_inflate.h is host-only.  A new route's header goes here.
+_HEADERS = [("vapor_kernels.h", True), ("vapor_wide.h", True), ("vapor_anyk.h", True), ("vapor_inflate.h", False),
+            ("vapor_bamdev.h", True), ("vapor_fasta.h", True), ("vapor_refine.h", True)]
+DEPS = SOURCES + [os.path.join(CSRC, h) for h, _dev in _HEADERS] + [os.path.join(ROOT, "include", "vapor_hip.h")]
+KERNEL_FILES = [os.path.join(CSRC, h) for h, dev in _HEADERS if dev] + [SOURCES[0], os.path.abspath(__file__)]
 
 # The kernels issue their wave-level atomics from one lane already (`if (lane == 0) atomicAdd(...)`); LLVM's atomic
 # optimizer wraps each of them in another mbcnt / compare / exec-mask sequence.  Off: clean_kernel 0.0837 -> 0.0826 ms.
@@ -33,9 +34,6 @@ def hipcc() -> str:
     raise RuntimeError("hipcc not found")
 
 
-KERNEL_FILES = [os.path.join(HERE, "csrc", "vapor_kernels.h"), os.path.join(HERE, "csrc", "vapor_wide.h"), os.path.join(HERE, "csrc", "vapor_anyk.h"),
-                os.path.join(HERE, "csrc", "vapor_bamdev.h"), os.path.join(HERE, "csrc", "vapor_fasta.h"),
-                os.path.join(HERE, "csrc", "vapor_refine.h"), os.path.join(HERE, "csrc", "vapor_hip.hip"), os.path.abspath(__file__)]
 _ID_RE = re.compile(rb"VAPOR_SOURCE_ID=([0-9a-f]{16}:[0-9a-f]{16})")
 
 

@@ -22,6 +22,7 @@
 #include <new>
 #include <numeric>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <set>
 #include <string>
@@ -63,7 +64,7 @@ static int fail(int code, const std::string& msg)
 // creates and destroys a sequence set and a plan per batch, and a dozen hipMalloc / hipHostMalloc / hipFree calls per
 // batch cost more than the batch's kernels.  Freed blocks go to a per-context free list (by capacity) and are handed
 // out again to requests of similar size; vapor_destroy releases them.  A set or plan that outlives its context
-// frees its blocks directly.
+// frees its blocks directly.  Who gives a block back, and when it may: see CallScope / Block below the pool's functions.
 struct BlockPool {
     std::multimap<size_t, void*> free_dev, free_host;
     std::map<const void*, size_t> cap_of;               // capacity of every block this pool has handed out or holds
@@ -171,6 +172,71 @@ static void pool_free(vapor_ctx* c, void* p, bool host)
 }
 static void dfree(vapor_ctx* c, void* p) { pool_free(c, p, false); }
 static void hfree(vapor_ctx* c, void* p) { pool_free(c, p, true); }
+
+// Who gives a block back.  An object that outlives the call that made it (vapor_seqset, vapor_plan, vapor_bam_batch) owns its
+// members and releases them in its destroy function; a create function that fails half-way hands the half-built object to
+// that function by scope (Building<>).  A block whose life ends with the call that took it is a Block of that call's
+// CallScope.  The rule, for every route: no block returns to the pool while work this call enqueued may still read or write
+// it, and no host buffer that an enqueued copy reads or fills dies first.  A call that succeeds ends in a
+// hipStreamSynchronize of its own and says so (settled()): unwinding adds nothing there.  A call that leaves early - a HIPCHK
+// that fails, a refusal, an exception - has its stream synchronised by the first owner that unwinds.  So a function declares
+// the host buffers that its copies use before its owners (which unwind first).  HIPCHK is the only check macro: with every
+// owner on the stack, returning at once is always right.
+struct CallScope {
+    vapor_ctx* ctx;
+    hipStream_t st;                            // the stream this call enqueues on
+    bool pending = true;                       // work may be in flight (assumed until the call says otherwise)
+    CallScope(vapor_ctx* c, hipStream_t s) : ctx(c), st(s) {}
+    void settled() { pending = false; }        // the caller has just synchronised `st` and enqueues nothing more
+    void settle()
+    {
+        if (pending) (void)hipStreamSynchronize(st);
+        pending = false;
+    }
+};
+
+// A device (or pinned host) block from the context's pool, given back when the handle goes out of scope.
+template <typename T = uint8_t, bool HOST = false>
+struct Block {
+    CallScope* sc = nullptr;
+    T* p = nullptr;
+    size_t cap = 0;
+    Block() = default;                         // (an array's element: its owner sets `sc`)
+    explicit Block(CallScope& s) : sc(&s) {}
+    Block(const Block&) = delete;
+    Block& operator=(const Block&) = delete;
+    ~Block()
+    {
+        if (!p) return;
+        sc->settle();
+        pool_free(sc->ctx, p, HOST);
+    }
+    // Grow-only, the contents are not kept.  A block that grows goes back to the pool at once, without a synchronisation: the
+    // caller grows a block only when nothing it has enqueued since its last synchronisation touches it.
+    hipError_t ensure(size_t bytes)
+    {
+        if (cap >= bytes) return hipSuccess;
+        pool_free(sc->ctx, p, HOST);
+        p = nullptr;
+        cap = 0;
+        const hipError_t e = pool_alloc(sc->ctx, (void**)&p, bytes, HOST);
+        if (e == hipSuccess) cap = bytes;
+        return e;
+    }
+    operator T*() const { return p; }
+};
+template <typename T = uint8_t> using HostBlock = Block<T, true>;
+
+// The deleter of a half-built set, plan or batch: std::unique_ptr<T, Building<T, destroy>> until the create function releases it.
+template <typename T, int (*DESTROY)(T*)>
+struct Building {
+    CallScope* sc;
+    void operator()(T* o) const
+    {
+        sc->settle();
+        DESTROY(o);
+    }
+};
 
 // A derived sequence as the caller described it (destination offsets added), and the groups the plan shares joins in.
 struct HSeg { int32_t parent, off, len, dst; bool rc; };
@@ -542,7 +608,8 @@ static int seqset_create_impl(vapor_ctx* ctx, int32_t n_seqs, SRC src, const int
     const bool dbg_t = getenv("VAPOR_DEBUG_UPLOAD") != nullptr;
     auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     double tq[8] = {now(), 0, 0, 0, 0, 0, 0, 0};
-    vapor_seqset* s = new (std::nothrow) vapor_seqset();
+    CallScope sc(ctx, ctx->stream);
+    std::unique_ptr<vapor_seqset, Building<vapor_seqset, vapor_seqset_destroy>> s(new (std::nothrow) vapor_seqset(), {&sc});
     if (!s) return fail(VAPOR_E_NOMEM, "out of memory");
     s->ctx = ctx;
     s->device = ctx->device;
@@ -551,7 +618,7 @@ static int seqset_create_impl(vapor_ctx* ctx, int32_t n_seqs, SRC src, const int
     s->h.resize((size_t)std::max(n_seqs + n_derived, 1));
     size_t asc = 0, pl = 0;
     for (int32_t i = 0; i < n_seqs; ++i) {
-        if (len[i] < 0) { delete s; return fail(VAPOR_E_ARG, "negative sequence length"); }
+        if (len[i] < 0) return fail(VAPOR_E_ARG, "negative sequence length");
         SeqDesc& d = s->h[i];
         memset(&d, 0, sizeof d);
         size_t ch = ((size_t)len[i] + 31) / 32;
@@ -561,7 +628,7 @@ static int seqset_create_impl(vapor_ctx* ctx, int32_t n_seqs, SRC src, const int
         d.flags = flags ? flags[i] : 0;
         asc += ch;
         pl += ch + VP_PAD_CHUNKS;
-        if (pl > 0xFFFFFFF0ull) { delete s; return fail(VAPOR_E_ARG, "sequence set too large"); }
+        if (pl > 0xFFFFFFF0ull) return fail(VAPOR_E_ARG, "sequence set too large");
     }
     // derived sequences (the caller's, then the hidden shared ones): planes behind the literals', assembled by derive_kernel
     std::vector<std::vector<HSeg>> hidden;
@@ -571,24 +638,20 @@ static int seqset_create_impl(vapor_ctx* ctx, int32_t n_seqs, SRC src, const int
         s->derived.resize((size_t)n_derived);
         for (int32_t d = 0; d < n_derived; ++d) {
             const int32_t g0 = seg_first[d], g1 = seg_first[d + 1];
-            if (g1 < g0 || g1 - g0 > VAPOR_MAX_SEGMENTS) { delete s; return fail(VAPOR_E_ARG, "vapor_seqset_create_derived: bad segment count"); }
+            if (g1 < g0 || g1 - g0 > VAPOR_MAX_SEGMENTS) return fail(VAPOR_E_ARG, "vapor_seqset_create_derived: bad segment count");
             int64_t tot = 0;
             for (int32_t g = g0; g < g1; ++g) {
                 const vapor_segment& x = segs[g];
-                if (x.parent < 0 || x.parent >= n_seqs || x.off < 0 || x.len < 0 || (int64_t)x.off + x.len > len[x.parent]) {
-                    delete s;
+                if (x.parent < 0 || x.parent >= n_seqs || x.off < 0 || x.len < 0 || (int64_t)x.off + x.len > len[x.parent])
                     return fail(VAPOR_E_ARG, "vapor_seqset_create_derived: segment outside its parent");
-                }
                 if (x.len == 0) continue;
                 // (a derived sequence is slices of its parents' BYTES: one that is not upper-cased itself cannot be cut from a
                 // parent that was upper-cased at upload - its planes hold the upper-cased text)
-                if (flags && (flags[x.parent] & VAPOR_SEQ_UPPER) && !(derived_flags && (derived_flags[d] & VAPOR_SEQ_UPPER))) {
-                    delete s;
+                if (flags && (flags[x.parent] & VAPOR_SEQ_UPPER) && !(derived_flags && (derived_flags[d] & VAPOR_SEQ_UPPER)))
                     return fail(VAPOR_E_ARG, "vapor_seqset_create_derived: a derived sequence without VAPOR_SEQ_UPPER over a parent uploaded with it");
-                }
                 s->derived[(size_t)d].push_back(HSeg{x.parent, x.off, x.len, (int32_t)tot, (x.flags & VAPOR_SEG_REVCOMP) != 0});
                 tot += x.len;
-                if (tot > 0x7FFFFFF0LL) { delete s; return fail(VAPOR_E_ARG, "vapor_seqset_create_derived: sequence too long"); }
+                if (tot > 0x7FFFFFF0LL) return fail(VAPOR_E_ARG, "vapor_seqset_create_derived: sequence too long");
             }
             dfl[(size_t)d] = derived_flags ? derived_flags[d] : 0;
             SeqDesc& dd = s->h[(size_t)(n_seqs + d)];
@@ -596,7 +659,7 @@ static int seqset_create_impl(vapor_ctx* ctx, int32_t n_seqs, SRC src, const int
             dd.len = (int32_t)tot;
             dd.flags = dfl[(size_t)d];
         }
-        if (ctx->shared_join) build_share_groups(s, dfl, &hidden);
+        if (ctx->shared_join) build_share_groups(s.get(), dfl, &hidden);
         s->h.resize((size_t)(n_seqs + n_derived) + hidden.size());
         for (size_t t = 0; t < hidden.size(); ++t) {
             SeqDesc& dd = s->h[(size_t)(n_seqs + n_derived) + t];
@@ -614,19 +677,13 @@ static int seqset_create_impl(vapor_ctx* ctx, int32_t n_seqs, SRC src, const int
             dd.chunk0 = (uint32_t)pl;
             der_chunks += ch;
             pl += ch + VP_PAD_CHUNKS;
-            if (pl > 0xFFFFFFF0ull) { delete s; return fail(VAPOR_E_ARG, "sequence set too large"); }
+            if (pl > 0xFFFFFFF0ull) return fail(VAPOR_E_ARG, "sequence set too large");
         }
     }
     pl += VP_PAD_CHUNKS + 1;
     s->plane_chunks = pl;
     const size_t n_asc = asc;
-    int rc = VAPOR_OK;
     tq[1] = now();
-#define SS_CHK(expr)                                                                               \
-    do {                                                                                           \
-        hipError_t _e = (expr);                                                                    \
-        if (_e != hipSuccess) { rc = fail(VAPOR_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); goto done; } \
-    } while (0)
     {
         // staging (ASCII at 32-byte chunks, then the chunk -> sequence map, then what derive_kernel reads: segment lists, their
         // offsets, the chunk -> sequence map of the derived sequences), kept in the context and grown on demand
@@ -643,13 +700,13 @@ static int seqset_create_impl(vapor_ctx* ctx, int32_t n_seqs, SRC src, const int
         const size_t der_bytes = der_chunks ? sizeof(DSeg) * std::max<size_t>(n_seg, 1) + sizeof(int32_t) * (n_dseq + 1) + sizeof(uint32_t) * der_chunks : 0;
         const size_t need = std::max<size_t>(der_off + der_bytes, 64);
         if (need > ctx->stage_cap) {
-            SS_CHK(hipStreamSynchronize(ctx->stream));
+            HIPCHK(hipStreamSynchronize(ctx->stream));
             if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
             if (ctx->d_stage) (void)hipFree(ctx->d_stage);
             ctx->h_stage = nullptr; ctx->d_stage = nullptr; ctx->stage_cap = 0;
             const size_t cap = need + need / 4;
-            SS_CHK(hipHostMalloc((void**)&ctx->h_stage, cap));
-            SS_CHK(hipMalloc((void**)&ctx->d_stage, cap));
+            HIPCHK(hipHostMalloc((void**)&ctx->h_stage, cap));
+            HIPCHK(hipMalloc((void**)&ctx->d_stage, cap));
             ctx->stage_cap = cap;
         }
         uint8_t* h_asc = ctx->h_stage;
@@ -677,14 +734,14 @@ static int seqset_create_impl(vapor_ctx* ctx, int32_t n_seqs, SRC src, const int
             for (int32_t i = 0; i < n_seqs; ++i)
                 if (!src_kind[i] && s->h[i].len > 0) host_end = std::max(host_end, (size_t)s->h[i].asc0 + ((size_t)s->h[i].len + 31) / 32);
         }
-        SS_CHK(dmalloc(ctx, (void**)&s->d_seqs, sizeof(SeqDesc) * s->h.size()));
-        SS_CHK(dmalloc(ctx, (void**)&s->d_p2, pl * 2 * sizeof(uint32_t)));
-        SS_CHK(dmalloc(ctx, (void**)&s->d_e1, pl * sizeof(uint32_t)));
-        SS_CHK(dmalloc(ctx, (void**)&s->d_x4, pl * 4 * sizeof(uint32_t)));
-        SS_CHK(hipMemsetAsync(s->d_p2, 0, pl * 2 * sizeof(uint32_t), ctx->stream));
-        SS_CHK(hipMemsetAsync(s->d_e1, 0, pl * sizeof(uint32_t), ctx->stream));
-        SS_CHK(hipMemsetAsync(s->d_x4, 0, pl * 4 * sizeof(uint32_t), ctx->stream));
-        SS_CHK(hipMemcpyAsync(s->d_seqs, s->h.data(), sizeof(SeqDesc) * s->h.size(), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(dmalloc(ctx, (void**)&s->d_seqs, sizeof(SeqDesc) * s->h.size()));
+        HIPCHK(dmalloc(ctx, (void**)&s->d_p2, pl * 2 * sizeof(uint32_t)));
+        HIPCHK(dmalloc(ctx, (void**)&s->d_e1, pl * sizeof(uint32_t)));
+        HIPCHK(dmalloc(ctx, (void**)&s->d_x4, pl * 4 * sizeof(uint32_t)));
+        HIPCHK(hipMemsetAsync(s->d_p2, 0, pl * 2 * sizeof(uint32_t), ctx->stream));
+        HIPCHK(hipMemsetAsync(s->d_e1, 0, pl * sizeof(uint32_t), ctx->stream));
+        HIPCHK(hipMemsetAsync(s->d_x4, 0, pl * 4 * sizeof(uint32_t), ctx->stream));
+        HIPCHK(hipMemcpyAsync(s->d_seqs, s->h.data(), sizeof(SeqDesc) * s->h.size(), hipMemcpyHostToDevice, ctx->stream));
         tq[2] = now();
         const int n_thr = (!mixed && n_asc * 32 >= ((size_t)4 << 20) && n_seqs >= 8) ? ctx->stage_threads : 1;
         if (mixed) {
@@ -695,19 +752,19 @@ static int seqset_create_impl(vapor_ctx* ctx, int32_t n_seqs, SRC src, const int
                 h_src[i] = src_kind[i] ? (unsigned long long)reinterpret_cast<uintptr_t>(src(i)) : 0ull;
                 h_first[i] = src_kind[i] ? (int32_t)src_first[i] : 0;
             }
-            if (host_end) SS_CHK(hipMemcpyAsync(d_asc, h_asc, host_end * 32, hipMemcpyHostToDevice, ctx->stream));
-            if (n_asc) SS_CHK(hipMemcpyAsync(d_map, h_map, n_asc * 4, hipMemcpyHostToDevice, ctx->stream));
-            SS_CHK(hipMemcpyAsync(ctx->d_stage + mix_off, ctx->h_stage + mix_off, mix_bytes, hipMemcpyHostToDevice, ctx->stream));
+            if (host_end) HIPCHK(hipMemcpyAsync(d_asc, h_asc, host_end * 32, hipMemcpyHostToDevice, ctx->stream));
+            if (n_asc) HIPCHK(hipMemcpyAsync(d_map, h_map, n_asc * 4, hipMemcpyHostToDevice, ctx->stream));
+            HIPCHK(hipMemcpyAsync(ctx->d_stage + mix_off, ctx->h_stage + mix_off, mix_bytes, hipMemcpyHostToDevice, ctx->stream));
             if (n_asc) {
                 hipLaunchKernelGGL(vapor_bamdev::bam_expand_kernel, dim3((unsigned)((n_asc + 255) / 256)), dim3(256), 0, ctx->stream, d_asc, d_map,
                                    (uint32_t)n_asc, reinterpret_cast<const uint32_t*>(s->d_seqs),
                                    reinterpret_cast<const unsigned long long*>(ctx->d_stage + mix_off),
                                    reinterpret_cast<const int32_t*>(ctx->d_stage + mix_off + (size_t)n_seqs * 8));
-                SS_CHK(hipGetLastError());
+                HIPCHK(hipGetLastError());
             }
         } else if (n_thr == 1) {
             stage_range(0, n_seqs);
-            if (n_asc) SS_CHK(hipMemcpyAsync(d_asc, h_asc, n_asc * 36, hipMemcpyHostToDevice, ctx->stream));
+            if (n_asc) HIPCHK(hipMemcpyAsync(d_asc, h_asc, n_asc * 36, hipMemcpyHostToDevice, ctx->stream));
         } else {
             // slices of equal shares of the bytes, staged by the threads in order; this thread sends a slice to the device
             // as soon as it is staged, so that the link works while the cores still copy
@@ -739,15 +796,15 @@ static int seqset_create_impl(vapor_ctx* ctx, int32_t n_seqs, SRC src, const int
                     err = hipMemcpyAsync(d_asc + c0 * 32, h_asc + c0 * 32, (c1 - c0) * 32, hipMemcpyHostToDevice, ctx->stream);
             }
             for (auto& x : th) x.join();
-            SS_CHK(err);
-            SS_CHK(hipMemcpyAsync(d_map, h_map, n_asc * 4, hipMemcpyHostToDevice, ctx->stream));
+            HIPCHK(err);
+            HIPCHK(hipMemcpyAsync(d_map, h_map, n_asc * 4, hipMemcpyHostToDevice, ctx->stream));
         }
         tq[3] = now();
         if (n_asc) {
             unsigned grid = (unsigned)((n_asc + 255) / 256);
             hipLaunchKernelGGL(pack_kernel, dim3(grid), dim3(256), 0, ctx->stream, d_asc, s->d_seqs, n_seqs, d_map,
                                (uint32_t)n_asc, s->d_p2, s->d_e1, s->d_x4);
-            SS_CHK(hipGetLastError());
+            HIPCHK(hipGetLastError());
         }
         if (der_chunks) {
             uint8_t* blk = ctx->h_stage + der_off;
@@ -764,54 +821,47 @@ static int seqset_create_impl(vapor_ctx* ctx, int32_t n_seqs, SRC src, const int
             }
             hf[n_dseq] = (int32_t)w;
             uint8_t* d_blk = ctx->d_stage + der_off;
-            SS_CHK(hipMemcpyAsync(d_blk, blk, der_bytes, hipMemcpyHostToDevice, ctx->stream));
+            HIPCHK(hipMemcpyAsync(d_blk, blk, der_bytes, hipMemcpyHostToDevice, ctx->stream));
             const DSeg* dsg = reinterpret_cast<const DSeg*>(d_blk);
             const int32_t* dsf = reinterpret_cast<const int32_t*>(d_blk + sizeof(DSeg) * std::max<size_t>(n_seg, 1));
             const uint32_t* dsc = reinterpret_cast<const uint32_t*>(dsf + n_dseq + 1);
             hipLaunchKernelGGL(derive_kernel, dim3((unsigned)((der_chunks + 255) / 256)), dim3(256), 0, ctx->stream, s->d_seqs, dsc,
                                (uint32_t)der_chunks, dsf, dsg, n_seqs, s->d_p2, s->d_e1, s->d_x4);
-            SS_CHK(hipGetLastError());
+            HIPCHK(hipGetLastError());
         }
         tq[4] = now();
-        SS_CHK(hipMemcpyAsync(s->h.data(), s->d_seqs, sizeof(SeqDesc) * s->h.size(), hipMemcpyDeviceToHost, ctx->stream));
-        SS_CHK(hipStreamSynchronize(ctx->stream));
+        HIPCHK(hipMemcpyAsync(s->h.data(), s->d_seqs, sizeof(SeqDesc) * s->h.size(), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
         tq[5] = now();
         if (dbg_t) fprintf(stderr, "seqset: layout+groups %.3f  alloc+memset %.3f  stage+h2d %.3f  launches %.3f  sync %.3f ms\n", tq[1] - tq[0], tq[2] - tq[1], tq[3] - tq[2], tq[4] - tq[3], tq[5] - tq[4]);
         // complementary() drops what is not ATGCN / atgcn (SF:471-478): a reversed slice of a window that holds such a
         // character is not what the reference would have built
-        for (size_t d = 0; d < s->derived.size() && rc == VAPOR_OK; ++d)
-            for (const HSeg& x : s->derived[d])
-                if (x.rc && s->h[(size_t)x.parent].n_nocomp > 0) {
-                    rc = fail(VAPOR_E_ARG, "vapor_seqset_create_derived: a reverse-complemented segment's parent holds characters complementary() drops "
-                                           "(outside ATGCN/atgcn, SF:471-478); upload that allele as bytes");
-                    break;
-                }
-        if (rc == VAPOR_OK) {
-            // keep the bytes of the sequences with symbols outside the alphabet (rare) before the staging buffer is reused
-            s->raw_off.assign(s->h.size(), -1);
-            size_t raw_bytes = 0;
+        for (const auto& v : s->derived)
+            for (const HSeg& x : v)
+                if (x.rc && s->h[(size_t)x.parent].n_nocomp > 0)
+                    return fail(VAPOR_E_ARG, "vapor_seqset_create_derived: a reverse-complemented segment's parent holds characters complementary() drops "
+                                             "(outside ATGCN/atgcn, SF:471-478); upload that allele as bytes");
+        // keep the bytes of the sequences with symbols outside the alphabet (rare) before the staging buffer is reused
+        s->raw_off.assign(s->h.size(), -1);
+        size_t raw_bytes = 0;
+        for (int32_t i = 0; i < n_seqs; ++i)
+            if (s->h[i].n_invalid > 0) { s->raw_off[i] = (int64_t)raw_bytes; raw_bytes += ((size_t)s->h[i].len + 15) & ~(size_t)15; }
+        if (raw_bytes) {
+            HIPCHK(dmalloc(ctx, (void**)&s->d_raw, raw_bytes));
             for (int32_t i = 0; i < n_seqs; ++i)
-                if (s->h[i].n_invalid > 0) { s->raw_off[i] = (int64_t)raw_bytes; raw_bytes += ((size_t)s->h[i].len + 15) & ~(size_t)15; }
-            if (raw_bytes) {
-                SS_CHK(dmalloc(ctx, (void**)&s->d_raw, raw_bytes));
-                for (int32_t i = 0; i < n_seqs; ++i)
-                    if (s->raw_off[i] >= 0 && s->h[i].len)
-                        SS_CHK(hipMemcpyAsync(s->d_raw + s->raw_off[i], d_asc + (size_t)s->h[i].asc0 * 32, (size_t)s->h[i].len,
-                                              hipMemcpyDeviceToDevice, ctx->stream));
-                SS_CHK(hipStreamSynchronize(ctx->stream));
-            }
+                if (s->raw_off[i] >= 0 && s->h[i].len)
+                    HIPCHK(hipMemcpyAsync(s->d_raw + s->raw_off[i], d_asc + (size_t)s->h[i].asc0 * 32, (size_t)s->h[i].len,
+                                          hipMemcpyDeviceToDevice, ctx->stream));
+            HIPCHK(hipStreamSynchronize(ctx->stream));
         }
-        if (seq_info && rc == VAPOR_OK)
+        if (seq_info)
             for (int32_t i = 0; i < s->n; ++i) {
                 seq_info[2 * i] = s->h[i].n_exc;
                 seq_info[2 * i + 1] = s->h[i].n_invalid;
             }
     }
-done:
-    if (rc != VAPOR_OK) { vapor_seqset_destroy(s); return rc; }
-    *out = s;
+    *out = s.release();
     return VAPOR_OK;
-#undef SS_CHK
 }
 
 extern "C" int vapor_seqset_create(vapor_ctx* ctx, int32_t n_seqs, const uint8_t* blob, const int64_t* off,
@@ -1050,40 +1100,13 @@ extern "C" int vapor_bam_chop_device(vapor_ctx* ctx, vapor_bam* bam, int32_t n_r
         if (stage_bytes > ((size_t)3 << 29)) return fail(VAPOR_E_ARG, "vapor_bam_chop_device: more than 1.5 GB of blocks in one call (use smaller batches)");
         // (what the call holds while it runs goes back to the context's pool on every way out, an exception's included; the batch
         // survives a successful return only)
-        struct Held {
-            vapor_ctx* ctx;
-            vapor_bam_batch* B = nullptr;
-            uint8_t *h_comp = nullptr, *d_comp = nullptr, *h_meta = nullptr, *d_meta = nullptr;
-            explicit Held(vapor_ctx* c) : ctx(c) {}
-            void release_temporaries()
-            {
-                if (h_comp) hfree(ctx, h_comp);
-                if (d_comp) dfree(ctx, d_comp);
-                if (h_meta) hfree(ctx, h_meta);
-                if (d_meta) dfree(ctx, d_meta);
-                h_comp = d_comp = h_meta = d_meta = nullptr;
-            }
-            ~Held()
-            {
-                release_temporaries();
-                if (B) vapor_bam_batch_destroy(B);
-            }
-        } held(ctx);
-        held.B = new vapor_bam_batch();
-        vapor_bam_batch*& B = held.B;
+        CallScope sc(ctx, ctx->stream);
+        std::unique_ptr<vapor_bam_batch, Building<vapor_bam_batch, vapor_bam_batch_destroy>> B(new vapor_bam_batch(), {&sc});
         B->ctx = ctx;
         B->device = ctx->device;
-        uint8_t*& h_comp = held.h_comp;
-        uint8_t*& d_comp = held.d_comp;
-        uint8_t*& h_meta = held.h_meta;
-        uint8_t*& d_meta = held.d_meta;
-        auto cleanup = [&](int code) { return code; };      // (the destructor above does the work)
-#define BD_CHK(expr)                                                                                                  \
-    do {                                                                                                              \
-        hipError_t _e = (expr);                                                                                       \
-        if (_e != hipSuccess) return cleanup(fail(VAPOR_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)));   \
-    } while (0)
-        BD_CHK(hmalloc(ctx, (void**)&h_comp, std::max<size_t>(stage_bytes, 64)));
+        HostBlock<> h_comp(sc), h_meta(sc);
+        Block<> d_comp(sc), d_meta(sc);
+        HIPCHK(h_comp.ensure(std::max<size_t>(stage_bytes, 64)));
         // ---- read and scan, a few threads -------------------------------------------------------------------------------------
         {
             const int n_thr = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(vapor_bam_threads(bam), 1) * 2, spans.size() / 8 + 1));
@@ -1134,7 +1157,7 @@ extern "C" int vapor_bam_chop_device(vapor_ctx* ctx, vapor_bam* bam, int32_t n_r
             if (status[g]) continue;
             for (int32_t si = span_first[(size_t)g]; si < span_first[(size_t)g + 1]; ++si) {
                 const HostSpan& sp = spans[(size_t)si];
-                if (arena + sp.u_total + 64 > ((size_t)1 << 31)) return cleanup(fail(VAPOR_E_ARG, "vapor_bam_chop_device: more than 2 GB of block data in one call (use smaller batches)"));
+                if (arena + sp.u_total + 64 > ((size_t)1 << 31)) return fail(VAPOR_E_ARG, "vapor_bam_chop_device: more than 2 GB of block data in one call (use smaller batches)");
                 BamSpan d;
                 d.u_begin = (uint32_t)arena + sp.u_begin;
                 d.u_end = (uint32_t)arena + sp.u_end;
@@ -1160,16 +1183,16 @@ extern "C" int vapor_bam_chop_device(vapor_ctx* ctx, vapor_bam* bam, int32_t n_r
         const size_t o_bst = in_bytes, o_nk = o_bst + ((4 * std::max<size_t>(n_blks, 1) + 63) & ~(size_t)63);
         const size_t o_rst = o_nk + ((4 * regs.size() + 63) & ~(size_t)63), o_kept = o_rst + ((4 * regs.size() + 63) & ~(size_t)63);
         const size_t meta_bytes = o_kept + sizeof(BamKept) * KEPT_CAP * regs.size();
-        BD_CHK(hmalloc(ctx, (void**)&h_meta, meta_bytes));
-        BD_CHK(dmalloc(ctx, (void**)&d_meta, meta_bytes));
-        BD_CHK(dmalloc(ctx, (void**)&d_comp, std::max<size_t>(stage_bytes, 64)));
-        BD_CHK(dmalloc(ctx, (void**)&B->d_arena, arena + 64));
+        HIPCHK(h_meta.ensure(meta_bytes));
+        HIPCHK(d_meta.ensure(meta_bytes));
+        HIPCHK(d_comp.ensure(std::max<size_t>(stage_bytes, 64)));
+        HIPCHK(dmalloc(ctx, (void**)&B->d_arena, arena + 64));
         B->arena_bytes = arena + 64;
         ctx->arenas[B->d_arena] = B->arena_bytes;
         if (n_blks) memcpy(h_meta + o_blk, blks.data(), sizeof(BgzfBlk) * n_blks);
         if (!dspans.empty()) memcpy(h_meta + o_span, dspans.data(), sizeof(BamSpan) * dspans.size());
         memcpy(h_meta + o_reg, regs.data(), sizeof(BamRegion) * regs.size());
-        BD_CHK(crc_pow_on_device(ctx));
+        HIPCHK(crc_pow_on_device(ctx));
         {
             const char* sh = getenv("VAPOR_BAM_CU_SHARE");            // (experiments: overrides the parameter)
             const int share = ctx->user_stream ? 0 : (sh ? atoi(sh) : ctx->bam_cu_share);
@@ -1186,28 +1209,29 @@ extern "C" int vapor_bam_chop_device(vapor_ctx* ctx, vapor_bam* bam, int32_t n_r
             }
         }
         hipStream_t st = ctx->bam_stream ? ctx->bam_stream : ctx->stream;
+        sc.st = st;
         tq[2] = now();
-        if (stage_bytes) BD_CHK(hipMemcpyAsync(d_comp, h_comp, stage_bytes, hipMemcpyHostToDevice, st));
-        if (dbg_t) { BD_CHK(hipStreamSynchronize(st)); tq[3] = now(); }
-        BD_CHK(hipMemcpyAsync(d_meta, h_meta, in_bytes, hipMemcpyHostToDevice, st));
-        if (!ctx->bam_ev[0]) { BD_CHK(hipEventCreate(&ctx->bam_ev[0])); BD_CHK(hipEventCreate(&ctx->bam_ev[1])); }
-        BD_CHK(hipEventRecord(ctx->bam_ev[0], st));
+        if (stage_bytes) HIPCHK(hipMemcpyAsync(d_comp, h_comp, stage_bytes, hipMemcpyHostToDevice, st));
+        if (dbg_t) { HIPCHK(hipStreamSynchronize(st)); tq[3] = now(); }
+        HIPCHK(hipMemcpyAsync(d_meta, h_meta, in_bytes, hipMemcpyHostToDevice, st));
+        if (!ctx->bam_ev[0]) { HIPCHK(hipEventCreate(&ctx->bam_ev[0])); HIPCHK(hipEventCreate(&ctx->bam_ev[1])); }
+        HIPCHK(hipEventRecord(ctx->bam_ev[0], st));
         if (n_blks) {
             hipLaunchKernelGGL(bgzf_inflate_kernel, dim3((unsigned)((n_blks + INFLATE_WAVES - 1) / INFLATE_WAVES)), dim3(64 * INFLATE_WAVES), 0, st, d_comp, reinterpret_cast<const BgzfBlk*>(d_meta + o_blk),
                                (int)n_blks, B->d_arena, ctx->d_crc_pow, reinterpret_cast<int32_t*>(d_meta + o_bst));
-            BD_CHK(hipGetLastError());
+            HIPCHK(hipGetLastError());
         }
-        BD_CHK(hipEventRecord(ctx->bam_ev[1], st));
-        if (dbg_t) { BD_CHK(hipStreamSynchronize(st)); tq[4] = now(); }
+        HIPCHK(hipEventRecord(ctx->bam_ev[1], st));
+        if (dbg_t) { HIPCHK(hipStreamSynchronize(st)); tq[4] = now(); }
         if (n_regions) {
             hipLaunchKernelGGL(bam_chop_kernel, dim3((unsigned)n_regions), dim3(64), 0, st, B->d_arena, reinterpret_cast<const BamRegion*>(d_meta + o_reg),
                                reinterpret_cast<const BamSpan*>(d_meta + o_span), reinterpret_cast<const int32_t*>(d_meta + o_bst), (int)n_regions,
                                reinterpret_cast<BamKept*>(d_meta + o_kept), reinterpret_cast<int32_t*>(d_meta + o_nk), reinterpret_cast<int32_t*>(d_meta + o_rst));
-            BD_CHK(hipGetLastError());
+            HIPCHK(hipGetLastError());
         }
         // (counts and statuses first; the kept reads of a region are read where its count says)
-        BD_CHK(hipMemcpyAsync(h_meta + o_bst, d_meta + o_bst, meta_bytes - o_bst, hipMemcpyDeviceToHost, st));
-        BD_CHK(hipStreamSynchronize(st));
+        HIPCHK(hipMemcpyAsync(h_meta + o_bst, d_meta + o_bst, meta_bytes - o_bst, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
         tq[5] = now();
         {
             float ms = 0.f;
@@ -1221,7 +1245,7 @@ extern "C" int vapor_bam_chop_device(vapor_ctx* ctx, vapor_bam* bam, int32_t n_r
 #ifdef VBD_TIMING
         if (dbg_t && n_blks) {
             std::vector<uint8_t> back(stage_bytes);
-            BD_CHK(hipMemcpy(back.data(), d_comp, stage_bytes, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(back.data(), d_comp, stage_bytes, hipMemcpyDeviceToHost));
             double sum[13] = {0};
             size_t cnt = 0;
             for (const BgzfBlk& k : blks) {
@@ -1262,11 +1286,9 @@ extern "C" int vapor_bam_chop_device(vapor_ctx* ctx, vapor_bam* bam, int32_t n_r
             }
         }
         kept_first[n_regions] = w;
-        held.release_temporaries();
-        *out = B;
-        held.B = nullptr;
+        sc.settled();
+        *out = B.release();
         return VAPOR_OK;
-#undef BD_CHK
     } catch (const std::bad_alloc&) {
         return fail(VAPOR_E_NOMEM, "vapor_bam_chop_device: out of memory");
     } catch (const std::exception& e) {             // (no exception crosses the C boundary: a thread that could not start, ...)
@@ -1368,24 +1390,10 @@ extern "C" int vapor_fasta_windows_device(vapor_ctx* ctx, int fd, int32_t n, con
             s.stage_off = (size_t)stage_bytes;
             stage_bytes += (want + 63) & ~(uint64_t)63;
         }
-        struct Held {
-            vapor_ctx* ctx;
-            uint8_t *h_comp = nullptr, *d_comp = nullptr, *d_arena = nullptr, *h_meta = nullptr, *d_meta = nullptr, *h_text = nullptr, *d_text = nullptr;
-            explicit Held(vapor_ctx* c) : ctx(c) {}
-            ~Held()
-            {
-                (void)hipStreamSynchronize(ctx->stream);        // (nothing goes back to the pool while a copy or kernel may use it)
-                if (h_comp) hfree(ctx, h_comp);
-                if (h_meta) hfree(ctx, h_meta);
-                if (h_text) hfree(ctx, h_text);
-                if (d_comp) dfree(ctx, d_comp);
-                if (d_arena) dfree(ctx, d_arena);
-                if (d_meta) dfree(ctx, d_meta);
-                if (d_text) dfree(ctx, d_text);
-            }
-        } held(ctx);
-        HIPCHK(hmalloc(ctx, (void**)&held.h_comp, (size_t)std::max<uint64_t>(stage_bytes, 64)));
-        uint8_t* const h_comp = held.h_comp;
+        CallScope sc(ctx, ctx->stream);
+        HostBlock<> h_comp(sc), h_meta(sc), h_text(sc);
+        Block<> d_comp(sc), d_arena(sc), d_meta(sc), d_text(sc);
+        HIPCHK(h_comp.ensure((size_t)std::max<uint64_t>(stage_bytes, 64)));
         uint64_t read_bytes = 0;
         for (FaStretch& s : sts) {
             if (!s.room) continue;
@@ -1505,38 +1513,37 @@ extern "C" int vapor_fasta_windows_device(vapor_ctx* ctx, int fd, int32_t n, con
         const size_t o_len = in_bytes, o_tr = o_len + ((8 * nw + 63) & ~(size_t)63);
         const size_t o_bst = o_tr + ((nw + 63) & ~(size_t)63);
         const size_t meta_bytes = o_bst + 4 * std::max<size_t>(n_blks, 1);
-        HIPCHK(hmalloc(ctx, (void**)&held.h_meta, meta_bytes));
-        HIPCHK(dmalloc(ctx, (void**)&held.d_meta, meta_bytes));
-        HIPCHK(dmalloc(ctx, (void**)&held.d_comp, (size_t)std::max<uint64_t>(stage_bytes, 64)));
-        HIPCHK(dmalloc(ctx, (void**)&held.d_arena, (size_t)arena + 64));
-        HIPCHK(dmalloc(ctx, (void**)&held.d_text, (size_t)std::max<uint64_t>(slots, 64)));
-        HIPCHK(hmalloc(ctx, (void**)&held.h_text, (size_t)std::max<uint64_t>(slots, 64)));
+        HIPCHK(h_meta.ensure(meta_bytes));
+        HIPCHK(d_meta.ensure(meta_bytes));
+        HIPCHK(d_comp.ensure((size_t)std::max<uint64_t>(stage_bytes, 64)));
+        HIPCHK(d_arena.ensure((size_t)arena + 64));
+        HIPCHK(d_text.ensure((size_t)std::max<uint64_t>(slots, 64)));
+        HIPCHK(h_text.ensure((size_t)std::max<uint64_t>(slots, 64)));
         HIPCHK(crc_pow_on_device(ctx));
-        uint8_t* h_meta = held.h_meta;
-        uint8_t* d_meta = held.d_meta;
         if (n_blks) memcpy(h_meta + o_blk, blks.data(), sizeof(BgzfBlk) * n_blks);
         memcpy(h_meta + o_win, wins.data(), sizeof(FastaWin) * nw);
         if (n) memcpy(h_meta + o_st, status, 4 * (size_t)n);
         hipStream_t st = ctx->stream;
         if (!ctx->fasta_ev[0]) { HIPCHK(hipEventCreate(&ctx->fasta_ev[0])); HIPCHK(hipEventCreate(&ctx->fasta_ev[1])); }
-        if (stage_bytes) HIPCHK(hipMemcpyAsync(held.d_comp, h_comp, (size_t)stage_bytes, hipMemcpyHostToDevice, st));
+        if (stage_bytes) HIPCHK(hipMemcpyAsync(d_comp, h_comp, (size_t)stage_bytes, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(d_meta, h_meta, in_bytes, hipMemcpyHostToDevice, st));
         HIPCHK(hipEventRecord(ctx->fasta_ev[0], st));
         if (n_blks) {
-            hipLaunchKernelGGL(bgzf_inflate_kernel, dim3((unsigned)((n_blks + INFLATE_WAVES - 1) / INFLATE_WAVES)), dim3(64 * INFLATE_WAVES), 0, st, held.d_comp,
-                               reinterpret_cast<const BgzfBlk*>(d_meta + o_blk), (int)n_blks, held.d_arena, ctx->d_crc_pow, reinterpret_cast<int32_t*>(d_meta + o_bst));
+            hipLaunchKernelGGL(bgzf_inflate_kernel, dim3((unsigned)((n_blks + INFLATE_WAVES - 1) / INFLATE_WAVES)), dim3(64 * INFLATE_WAVES), 0, st, d_comp,
+                               reinterpret_cast<const BgzfBlk*>(d_meta + o_blk), (int)n_blks, d_arena, ctx->d_crc_pow, reinterpret_cast<int32_t*>(d_meta + o_bst));
             HIPCHK(hipGetLastError());
         }
         if (n) {
-            hipLaunchKernelGGL(fasta_window_kernel, dim3((unsigned)((nw + WIN_WAVES - 1) / WIN_WAVES)), dim3(64 * WIN_WAVES), 0, st, held.d_arena,
-                               reinterpret_cast<const FastaWin*>(d_meta + o_win), (int)n, reinterpret_cast<const int32_t*>(d_meta + o_bst), held.d_text,
+            hipLaunchKernelGGL(fasta_window_kernel, dim3((unsigned)((nw + WIN_WAVES - 1) / WIN_WAVES)), dim3(64 * WIN_WAVES), 0, st, d_arena,
+                               reinterpret_cast<const FastaWin*>(d_meta + o_win), (int)n, reinterpret_cast<const int32_t*>(d_meta + o_bst), d_text,
                                reinterpret_cast<int64_t*>(d_meta + o_len), d_meta + o_tr, reinterpret_cast<int32_t*>(d_meta + o_st));
             HIPCHK(hipGetLastError());
         }
         HIPCHK(hipEventRecord(ctx->fasta_ev[1], st));
         HIPCHK(hipMemcpyAsync(h_meta + o_st, d_meta + o_st, meta_bytes - o_st, hipMemcpyDeviceToHost, st));
-        if (slots) HIPCHK(hipMemcpyAsync(held.h_text, held.d_text, (size_t)slots, hipMemcpyDeviceToHost, st));
+        if (slots) HIPCHK(hipMemcpyAsync(h_text, d_text, (size_t)slots, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
+        sc.settled();
         // ---- the texts, one after the other ------------------------------------------------------------------------------------
         const int32_t* d_status = reinterpret_cast<const int32_t*>(h_meta + o_st);
         const int64_t* tlen = reinterpret_cast<const int64_t*>(h_meta + o_len);
@@ -1546,7 +1553,7 @@ extern "C" int vapor_fasta_windows_device(vapor_ctx* ctx, int fd, int32_t n, con
             status[i] = d_status[i];
             traits[i] = h_meta[o_tr + (size_t)i];
             if (!status[i] && tlen[i]) {
-                memcpy(text + pos, held.h_text + wins[(size_t)i].t_off, (size_t)tlen[i]);
+                memcpy(text + pos, h_text + wins[(size_t)i].t_off, (size_t)tlen[i]);
                 pos += tlen[i];
             }
             text_off[i + 1] = pos;
@@ -1605,6 +1612,24 @@ extern "C" int vapor_seqset_create_mixed(vapor_ctx* ctx, int32_t n_seqs, const u
 }
 
 // ------------------------------------------------------------------------------------------
+static void plan_free_grid(vapor_plan* p)
+{
+    dfree(p->ctx, p->d_grid); p->d_grid = nullptr;
+    dfree(p->ctx, p->d_group_out); p->d_group_out = nullptr;
+    dfree(p->ctx, p->d_winner_scores); p->d_winner_scores = nullptr;
+    p->n_groups = 0;
+}
+
+static void plan_free_reads(vapor_plan* p)
+{
+    dfree(p->ctx, p->d_reads); p->d_reads = nullptr;
+    p->d_locus_first = nullptr;           // (inside d_reads' block)
+    if (p->own_gt) dfree(p->ctx, p->d_gt);
+    p->d_gt = nullptr; p->own_gt = false;
+    dfree(p->ctx, p->d_read_scores); p->d_read_scores = nullptr;
+    dfree(p->ctx, p->d_loci); p->d_loci = nullptr;
+}
+
 static void plan_free_device(vapor_plan* p)
 {
     dfree(p->ctx, p->d_pairs); p->d_pairs = nullptr;
@@ -1614,20 +1639,12 @@ static void plan_free_device(vapor_plan* p)
     dfree(p->ctx, p->d_hflags); p->d_hflags = nullptr;
     dfree(p->ctx, p->d_nhits); p->d_nhits = nullptr;
     dfree(p->ctx, p->d_stats); p->d_stats = nullptr;
-    dfree(p->ctx, p->d_reads); p->d_reads = nullptr;
-    p->d_locus_first = nullptr;           // (inside d_reads' block)
-    if (p->own_gt) dfree(p->ctx, p->d_gt);
-    p->d_gt = nullptr;
-    dfree(p->ctx, p->d_read_scores); p->d_read_scores = nullptr;
-    dfree(p->ctx, p->d_loci); p->d_loci = nullptr;
+    plan_free_reads(p);
     dfree(p->ctx, p->d_shares); p->d_shares = nullptr;
     dfree(p->ctx, p->d_maps); p->d_maps = nullptr;
     dfree(p->ctx, p->d_serve); p->d_serve = nullptr;
     dfree(p->ctx, p->d_clean_order); p->d_clean_order = nullptr;
-    dfree(p->ctx, p->d_grid); p->d_grid = nullptr;
-    dfree(p->ctx, p->d_group_out); p->d_group_out = nullptr;
-    dfree(p->ctx, p->d_winner_scores); p->d_winner_scores = nullptr;
-    p->n_groups = 0;
+    plan_free_grid(p);
 }
 
 extern "C" int vapor_plan_destroy(vapor_plan* p)
@@ -1723,7 +1740,8 @@ extern "C" int vapor_plan_create(vapor_ctx* ctx, vapor_seqset* set, int64_t n_pa
         return fail(VAPOR_E_ARG, "vapor_plan_create: null argument");
     if (n_pairs > 0x7FFFFFF0LL) return fail(VAPOR_E_ARG, "too many pairs");
     HIPCHK(hipSetDevice(ctx->device));
-    vapor_plan* p = new (std::nothrow) vapor_plan();
+    CallScope sc(ctx, ctx->stream);
+    std::unique_ptr<vapor_plan, Building<vapor_plan, vapor_plan_destroy>> p(new (std::nothrow) vapor_plan(), {&sc});
     if (!p) return fail(VAPOR_E_NOMEM, "out of memory");
     p->ctx = ctx;
     p->device = ctx->device;
@@ -1996,47 +2014,43 @@ extern "C" int vapor_plan_create(vapor_ctx* ctx, vapor_seqset* set, int64_t n_pa
         }
         q = e;
     }
-    int rc = VAPOR_OK;
-    auto chk = [&](hipError_t e, const char* what) {
-        if (e != hipSuccess && rc == VAPOR_OK) rc = fail(VAPOR_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
-    };
-    chk(dmalloc(ctx, (void**)&p->d_pairs, sizeof(DPair) * p->hp.size()), "hipMalloc pairs");
-    chk(dmalloc(ctx, (void**)&p->d_tasks, sizeof(DTask) * std::max<size_t>(p->tasks.size(), 1)), "hipMalloc tasks");
-    chk(dmalloc(ctx, (void**)&p->d_task_pairs, sizeof(int32_t) * std::max<size_t>(order.size(), 1)), "hipMalloc task_pairs");
-    chk(dmalloc(ctx, (void**)&p->d_nhits, sizeof(unsigned long long) * p->hp.size()), "hipMalloc nhits");
-    if (rc == VAPOR_OK) chk(hipMemsetAsync(p->d_nhits, 0, sizeof(unsigned long long) * p->hp.size(), ctx->stream), "memset nhits");
-    chk(dmalloc(ctx, (void**)&p->d_stats, sizeof(long long) * 16 * p->hp.size()), "hipMalloc stats");
-    chk(hmalloc(ctx, (void**)&p->h_stats, sizeof(long long) * 16 * p->hp.size()), "hipHostMalloc stats");
-    chk(dmalloc(ctx, (void**)&p->d_overflow, 4 * sizeof(unsigned int)), "hipMalloc overflow");
-    if (rc == VAPOR_OK) chk(hipMemsetAsync(p->d_overflow, 0, 4 * sizeof(unsigned int), ctx->stream), "memset overflow");
-    chk(dmalloc(ctx, (void**)&p->d_big_list, sizeof(int32_t) * p->hp.size()), "hipMalloc big list");
-    chk(hmalloc(ctx, (void**)&p->h_overflow, 2 * sizeof(unsigned int)), "hipHostMalloc overflow");
+    HIPCHK(dmalloc(ctx, (void**)&p->d_pairs, sizeof(DPair) * p->hp.size()));
+    HIPCHK(dmalloc(ctx, (void**)&p->d_tasks, sizeof(DTask) * std::max<size_t>(p->tasks.size(), 1)));
+    HIPCHK(dmalloc(ctx, (void**)&p->d_task_pairs, sizeof(int32_t) * std::max<size_t>(order.size(), 1)));
+    HIPCHK(dmalloc(ctx, (void**)&p->d_nhits, sizeof(unsigned long long) * p->hp.size()));
+    HIPCHK(hipMemsetAsync(p->d_nhits, 0, sizeof(unsigned long long) * p->hp.size(), ctx->stream));
+    HIPCHK(dmalloc(ctx, (void**)&p->d_stats, sizeof(long long) * 16 * p->hp.size()));
+    HIPCHK(hmalloc(ctx, (void**)&p->h_stats, sizeof(long long) * 16 * p->hp.size()));
+    HIPCHK(dmalloc(ctx, (void**)&p->d_overflow, 4 * sizeof(unsigned int)));
+    HIPCHK(hipMemsetAsync(p->d_overflow, 0, 4 * sizeof(unsigned int), ctx->stream));
+    HIPCHK(dmalloc(ctx, (void**)&p->d_big_list, sizeof(int32_t) * p->hp.size()));
+    HIPCHK(hmalloc(ctx, (void**)&p->h_overflow, 2 * sizeof(unsigned int)));
     if (p->n_dpairs) {
-        chk(dmalloc(ctx, (void**)&p->d_shares, sizeof(DShare) * p->shares.size()), "hipMalloc shares");
-        chk(dmalloc(ctx, (void**)&p->d_maps, sizeof(int32_t) * std::max<size_t>(p->tables.size(), 1)), "hipMalloc maps");
-        chk(dmalloc(ctx, (void**)&p->d_serve, sizeof(DServe) * p->serve.size()), "hipMalloc serve");
-        if (rc == VAPOR_OK) chk(hipMemcpyAsync(p->d_shares, p->shares.data(), sizeof(DShare) * p->shares.size(), hipMemcpyHostToDevice, ctx->stream), "copy shares");
-        if (rc == VAPOR_OK && !p->tables.empty())
-            chk(hipMemcpyAsync(p->d_maps, p->tables.data(), sizeof(int32_t) * p->tables.size(), hipMemcpyHostToDevice, ctx->stream), "copy maps");
+        HIPCHK(dmalloc(ctx, (void**)&p->d_shares, sizeof(DShare) * p->shares.size()));
+        HIPCHK(dmalloc(ctx, (void**)&p->d_maps, sizeof(int32_t) * std::max<size_t>(p->tables.size(), 1)));
+        HIPCHK(dmalloc(ctx, (void**)&p->d_serve, sizeof(DServe) * p->serve.size()));
+        HIPCHK(hipMemcpyAsync(p->d_shares, p->shares.data(), sizeof(DShare) * p->shares.size(), hipMemcpyHostToDevice, ctx->stream));
+        if (!p->tables.empty())
+            HIPCHK(hipMemcpyAsync(p->d_maps, p->tables.data(), sizeof(int32_t) * p->tables.size(), hipMemcpyHostToDevice, ctx->stream));
     }
     // (a plan of many rounds of clean workgroups has no tail worth ordering for - cfg3's 62 rounds gain nothing - and sorting
     // 80 000 pairs costs a pipeline chunk's plan 3-4 ms: the order is made for plans of up to eight rounds)
     if (ctx->clean_order && n_pairs > 1 && n_pairs <= (int64_t)8 * (2048 / CLEAN_THREADS) * ctx->n_cus) {
-        chk(dmalloc(ctx, (void**)&p->d_clean_order, sizeof(int32_t) * (size_t)n_pairs), "hipMalloc clean order");
-        if (rc == VAPOR_OK && plan_clean_order(p, nullptr) != VAPOR_OK) rc = VAPOR_E_HIP;
+        HIPCHK(dmalloc(ctx, (void**)&p->d_clean_order, sizeof(int32_t) * (size_t)n_pairs));
+        if (const int rc = plan_clean_order(p.get(), nullptr)) return rc;
     }
-    for (auto& e : p->ev) chk(hipEventCreate(&e), "hipEventCreate");
-    for (auto& e : p->ev_f) chk(hipEventCreate(&e), "hipEventCreate");
-    chk(hipEventCreate(&p->ev_t0), "hipEventCreate");
-    if (rc == VAPOR_OK && !p->tasks.empty())
-        chk(hipMemcpyAsync(p->d_tasks, p->tasks.data(), sizeof(DTask) * p->tasks.size(), hipMemcpyHostToDevice, ctx->stream), "copy tasks");
-    if (rc == VAPOR_OK && !order.empty())
-        chk(hipMemcpyAsync(p->d_task_pairs, order.data(), sizeof(int32_t) * order.size(), hipMemcpyHostToDevice, ctx->stream), "copy task_pairs");
-    if (rc == VAPOR_OK) rc = plan_alloc_hits(p);
-    if (rc == VAPOR_OK) chk(hipStreamSynchronize(ctx->stream), "sync");
-    if (rc != VAPOR_OK) { vapor_plan_destroy(p); return rc; }
+    for (auto& e : p->ev) HIPCHK(hipEventCreate(&e));
+    for (auto& e : p->ev_f) HIPCHK(hipEventCreate(&e));
+    HIPCHK(hipEventCreate(&p->ev_t0));
+    // (the copies read the plan's own vectors: a plan that fails here is destroyed after its stream is synchronised)
+    if (!p->tasks.empty())
+        HIPCHK(hipMemcpyAsync(p->d_tasks, p->tasks.data(), sizeof(DTask) * p->tasks.size(), hipMemcpyHostToDevice, ctx->stream));
+    if (!order.empty())
+        HIPCHK(hipMemcpyAsync(p->d_task_pairs, p->task_pairs.data(), sizeof(int32_t) * order.size(), hipMemcpyHostToDevice, ctx->stream));
+    if (const int rc = plan_alloc_hits(p.get())) return rc;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
     p->last_stats.assign((size_t)n_pairs * 16, 0);
-    *out = p;
+    *out = p.release();
     return VAPOR_OK;
 }
 
@@ -2372,35 +2386,27 @@ extern "C" int vapor_plan_fetch_hits(vapor_plan* p, int64_t n_sel, const int64_t
     std::vector<long long> nrec((size_t)n_sel, 0);
     for (int64_t q = 0; q < n_sel; ++q)
         if (off[q + 1] > off[q]) nrec[q] = (long long)(uint32_t)cnt[sel[q]];
-    long long *d_sel = nullptr, *d_off = nullptr, *d_nrec = nullptr;
-    int32_t* d_ji = nullptr;
-    uint8_t* d_fl = nullptr;
-    int rc = VAPOR_OK;
-    auto chk = [&](hipError_t e, const char* what) {
-        if (e != hipSuccess && rc == VAPOR_OK) rc = fail(VAPOR_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
-    };
     hipStream_t st = p->ctx->stream;
-    vapor_ctx* ctx = p->ctx;
-    chk(dmalloc(ctx, (void**)&d_sel, sizeof(long long) * sel.size()), "hipMalloc");
-    chk(dmalloc(ctx, (void**)&d_off, sizeof(long long) * off.size()), "hipMalloc");
-    chk(dmalloc(ctx, (void**)&d_nrec, sizeof(long long) * nrec.size()), "hipMalloc");
-    chk(dmalloc(ctx, (void**)&d_ji, sizeof(int32_t) * 2 * (size_t)off[n_sel]), "hipMalloc");
-    if (hit_flags) chk(dmalloc(ctx, (void**)&d_fl, (size_t)off[n_sel]), "hipMalloc");
-    if (rc == VAPOR_OK) {
-        chk(hipMemcpyAsync(d_sel, sel.data(), sizeof(long long) * sel.size(), hipMemcpyHostToDevice, st), "copy");
-        chk(hipMemcpyAsync(d_off, off.data(), sizeof(long long) * off.size(), hipMemcpyHostToDevice, st), "copy");
-        chk(hipMemcpyAsync(d_nrec, nrec.data(), sizeof(long long) * nrec.size(), hipMemcpyHostToDevice, st), "copy");
-    }
-    if (rc == VAPOR_OK) {
-        hipLaunchKernelGGL(gather_kernel, dim3((unsigned)n_sel), dim3(256), 0, st, p->d_pairs, d_sel, d_off, d_nrec, p->d_hits,
-                           p->d_hflags, d_ji, d_fl);
-        chk(hipGetLastError(), "gather launch");
-        chk(hipMemcpyAsync(hits_ji, d_ji, sizeof(int32_t) * 2 * (size_t)off[n_sel], hipMemcpyDeviceToHost, st), "copy");
-        if (hit_flags) chk(hipMemcpyAsync(hit_flags, d_fl, (size_t)off[n_sel], hipMemcpyDeviceToHost, st), "copy");
-        chk(hipStreamSynchronize(st), "sync");
-    }
-    dfree(ctx, d_sel); dfree(ctx, d_off); dfree(ctx, d_nrec); dfree(ctx, d_ji); dfree(ctx, d_fl);
-    return rc;
+    CallScope sc(p->ctx, st);
+    Block<long long> d_sel(sc), d_off(sc), d_nrec(sc);
+    Block<int32_t> d_ji(sc);
+    Block<uint8_t> d_fl(sc);
+    HIPCHK(d_sel.ensure(sizeof(long long) * sel.size()));
+    HIPCHK(d_off.ensure(sizeof(long long) * off.size()));
+    HIPCHK(d_nrec.ensure(sizeof(long long) * nrec.size()));
+    HIPCHK(d_ji.ensure(sizeof(int32_t) * 2 * (size_t)off[n_sel]));
+    if (hit_flags) HIPCHK(d_fl.ensure((size_t)off[n_sel]));
+    HIPCHK(hipMemcpyAsync(d_sel, sel.data(), sizeof(long long) * sel.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_off, off.data(), sizeof(long long) * off.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_nrec, nrec.data(), sizeof(long long) * nrec.size(), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(gather_kernel, dim3((unsigned)n_sel), dim3(256), 0, st, p->d_pairs, d_sel.p, d_off.p, d_nrec.p, p->d_hits,
+                       p->d_hflags, d_ji.p, d_fl.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(hits_ji, d_ji, sizeof(int32_t) * 2 * (size_t)off[n_sel], hipMemcpyDeviceToHost, st));
+    if (hit_flags) HIPCHK(hipMemcpyAsync(hit_flags, d_fl, (size_t)off[n_sel], hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    sc.settled();
+    return VAPOR_OK;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2456,14 +2462,32 @@ extern "C" int vapor_selfplot_qc(vapor_ctx* ctx, vapor_seqset* set, int32_t n, c
 // Cleaning and reductions on caller-supplied hit lists: what clean_dotdata_diagnal_and_anti_diagnal
 // (SF:432-448), clean_dotdata_diagnal_m1b / clean_dotdata_anti_diagnal_m1b (SF:404-430) and the
 // eu_dis_* reductions do when handed an explicit dot list instead of a fresh dotdata() result.
+// The lists of vapor_clean_hits and vapor_clean_hits_wide: coordinates in 0 .. coord_max.  Only the wide entry point has ever
+// checked the offsets themselves (list_cap >= 0: they do not decrease, no list longer than that); the narrow one (list_cap < 0)
+// takes them as given.  Each entry point keeps its own set of refusals here; aligning them is a change of behaviour.
+static int clean_lists_check(const std::string& who, vapor_ctx* ctx, int64_t n_lists, const int32_t* hits_ji, const int64_t* off,
+                             const int64_t* stats, int coord_max, int64_t list_cap)
+{
+    if (!ctx || n_lists < 0 || (n_lists && (!off || !stats))) return fail(VAPOR_E_ARG, who + ": null argument");
+    if (n_lists == 0) return VAPOR_OK;
+    if (off[n_lists] && !hits_ji) return fail(VAPOR_E_ARG, who + ": null hit list");
+    for (int64_t t = 0; t < n_lists; ++t) {
+        if (list_cap >= 0 && (off[t + 1] < off[t] || off[t + 1] - off[t] > list_cap)) return fail(VAPOR_E_ARG, who + ": bad list offsets");
+        for (int64_t h = off[t]; h < off[t + 1]; ++h) {
+            const int j = hits_ji[2 * h], i = hits_ji[2 * h + 1];
+            if (j < 0 || i < 0 || j > coord_max || i > coord_max) return fail(VAPOR_E_ARG, who + ": coordinate out of range");
+        }
+    }
+    return VAPOR_OK;
+}
+
 extern "C" int vapor_clean_hits(vapor_ctx* ctx, int64_t n_lists, const int32_t* hits_ji, const int64_t* off,
                                 const uint32_t* flags, int64_t* stats, uint8_t* hit_flags)
 {
-    if (!ctx || n_lists < 0 || (n_lists && (!off || !stats))) return fail(VAPOR_E_ARG, "vapor_clean_hits: null argument");
+    if (const int rc = clean_lists_check("vapor_clean_hits", ctx, n_lists, hits_ji, off, stats, VAPOR_MAX_SEQ_LEN, -1)) return rc;
     if (n_lists == 0) return VAPOR_OK;
     HIPCHK(hipSetDevice(ctx->device));
     const int64_t tot = off[n_lists];
-    if (tot && !hits_ji) return fail(VAPOR_E_ARG, "vapor_clean_hits: null hit list");
     std::vector<DPair> dp((size_t)n_lists);
     std::vector<unsigned long long> nh((size_t)n_lists);
     // device layout: one record per dot, every list's slot padded to a multiple of four records (the kernels
@@ -2476,8 +2500,6 @@ extern "C" int vapor_clean_hits(vapor_ctx* ctx, int64_t n_lists, const int32_t* 
         int mi = 0, mj = 0;
         for (int64_t h = off[t]; h < off[t + 1]; ++h) {
             int j = hits_ji[2 * h], i = hits_ji[2 * h + 1];
-            if (j < 0 || i < 0 || j > VAPOR_MAX_SEQ_LEN || i > VAPOR_MAX_SEQ_LEN)
-                return fail(VAPOR_E_ARG, "vapor_clean_hits: coordinate out of range");
             mi = std::max(mi, i); mj = std::max(mj, j);
             packed[poff[t] + (h - off[t])] = (unsigned long long)(((uint32_t)j << 16) | (uint32_t)i) | (1ull << 32);
         }
@@ -2491,46 +2513,42 @@ extern "C" int vapor_clean_hits(vapor_ctx* ctx, int64_t n_lists, const int32_t* 
         // the largest values, i + j = 131070 and i - j + len2 = 131071, still fall into word 4095
         rw = std::min(std::max(rw, (mi + mj + 4 + 31) / 32), CLEAN_RANGE_WORDS_MAX);
     }
-    DPair* d_dp = nullptr; unsigned long long* d_nh = nullptr; unsigned int* d_ov = nullptr; int32_t* d_big = nullptr;
-    unsigned long long* d_hits = nullptr; uint8_t* d_fl = nullptr; long long* d_st = nullptr;
-    int rc = VAPOR_OK;
-    auto chk = [&](hipError_t e, const char* what) {
-        if (e != hipSuccess && rc == VAPOR_OK) rc = fail(VAPOR_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
-    };
+    std::vector<uint8_t> fl(hit_flags && tot ? packed.size() : 0);
     hipStream_t st = ctx->stream;
-    chk(dmalloc(ctx, (void**)&d_ov, 4 * sizeof(unsigned int)), "hipMalloc");
-    chk(dmalloc(ctx, (void**)&d_big, sizeof(int32_t) * dp.size()), "hipMalloc");
-    chk(dmalloc(ctx, (void**)&d_dp, sizeof(DPair) * dp.size()), "hipMalloc");
-    chk(dmalloc(ctx, (void**)&d_nh, sizeof(unsigned long long) * nh.size()), "hipMalloc");
-    chk(dmalloc(ctx, (void**)&d_hits, sizeof(unsigned long long) * packed.size()), "hipMalloc");
-    chk(dmalloc(ctx, (void**)&d_fl, packed.size()), "hipMalloc");
-    chk(dmalloc(ctx, (void**)&d_st, sizeof(long long) * 16 * (size_t)n_lists), "hipMalloc");
-    if (rc == VAPOR_OK) {
-        chk(hipMemsetAsync(d_ov, 0, 4 * sizeof(unsigned int), st), "memset");
-        chk(hipMemcpyAsync(d_dp, dp.data(), sizeof(DPair) * dp.size(), hipMemcpyHostToDevice, st), "copy");
-        chk(hipMemcpyAsync(d_nh, nh.data(), sizeof(unsigned long long) * nh.size(), hipMemcpyHostToDevice, st), "copy");
-        chk(hipMemcpyAsync(d_hits, packed.data(), sizeof(unsigned long long) * packed.size(), hipMemcpyHostToDevice, st), "copy");
-    }
-    if (rc == VAPOR_OK) {
-        const CleanGeom cg = clean_geom(rw, 4096);
-        const int hcap = cg.hcap;
-        launch_clean(rw, (unsigned)n_lists, clean_lds_bytes(rw, hcap, cg.dual), st, (const DPair*)d_dp, (const int32_t*)nullptr,
-                     d_nh, d_hits, d_fl, d_st, rw,
-                     clean_groups_lds(rw, hcap), hcap, d_ov, d_big, 1, cg.dual ? 1 : 0,
-                     (const DServe*)nullptr, (const int32_t*)nullptr, 1);
-        chk(hipGetLastError(), "clean launch");
-        hipLaunchKernelGGL(clean_big_kernel, dim3((unsigned)std::min<int64_t>(n_lists, CLEAN_BIG_GRID)), dim3(CLEAN_THREADS),
-                           clean_fixed_bytes(rw, true), st, d_dp, d_nh, d_hits, d_fl, d_st, rw, clean_groups_cap(rw), d_ov, d_big);
-        chk(hipGetLastError(), "clean launch");
-        chk(hipMemcpyAsync(stats, d_st, sizeof(long long) * 16 * (size_t)n_lists, hipMemcpyDeviceToHost, st), "copy");
-        std::vector<uint8_t> fl(hit_flags && tot ? packed.size() : 0);
-        if (!fl.empty()) chk(hipMemcpyAsync(fl.data(), d_fl, fl.size(), hipMemcpyDeviceToHost, st), "copy");
-        chk(hipStreamSynchronize(st), "sync");
-        if (!fl.empty() && rc == VAPOR_OK)
-            for (int64_t t = 0; t < n_lists; ++t) memcpy(hit_flags + off[t], fl.data() + poff[t], (size_t)(off[t + 1] - off[t]));
-    }
-    dfree(ctx, d_ov); dfree(ctx, d_big); dfree(ctx, d_dp); dfree(ctx, d_nh); dfree(ctx, d_hits); dfree(ctx, d_fl); dfree(ctx, d_st);
-    return rc;
+    CallScope sc(ctx, st);
+    Block<DPair> d_dp(sc);
+    Block<unsigned long long> d_nh(sc), d_hits(sc);
+    Block<unsigned int> d_ov(sc);
+    Block<int32_t> d_big(sc);
+    Block<uint8_t> d_fl(sc);
+    Block<long long> d_st(sc);
+    HIPCHK(d_ov.ensure(4 * sizeof(unsigned int)));
+    HIPCHK(d_big.ensure(sizeof(int32_t) * dp.size()));
+    HIPCHK(d_dp.ensure(sizeof(DPair) * dp.size()));
+    HIPCHK(d_nh.ensure(sizeof(unsigned long long) * nh.size()));
+    HIPCHK(d_hits.ensure(sizeof(unsigned long long) * packed.size()));
+    HIPCHK(d_fl.ensure(packed.size()));
+    HIPCHK(d_st.ensure(sizeof(long long) * 16 * (size_t)n_lists));
+    HIPCHK(hipMemsetAsync(d_ov, 0, 4 * sizeof(unsigned int), st));
+    HIPCHK(hipMemcpyAsync(d_dp, dp.data(), sizeof(DPair) * dp.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_nh, nh.data(), sizeof(unsigned long long) * nh.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_hits, packed.data(), sizeof(unsigned long long) * packed.size(), hipMemcpyHostToDevice, st));
+    const CleanGeom cg = clean_geom(rw, 4096);
+    const int hcap = cg.hcap;
+    launch_clean(rw, (unsigned)n_lists, clean_lds_bytes(rw, hcap, cg.dual), st, (const DPair*)d_dp, (const int32_t*)nullptr,
+                 d_nh.p, d_hits.p, d_fl.p, d_st.p, rw,
+                 clean_groups_lds(rw, hcap), hcap, d_ov.p, d_big.p, 1, cg.dual ? 1 : 0,
+                 (const DServe*)nullptr, (const int32_t*)nullptr, 1);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(clean_big_kernel, dim3((unsigned)std::min<int64_t>(n_lists, CLEAN_BIG_GRID)), dim3(CLEAN_THREADS),
+                       clean_fixed_bytes(rw, true), st, d_dp.p, d_nh.p, d_hits.p, d_fl.p, d_st.p, rw, clean_groups_cap(rw), d_ov.p, d_big.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(stats, d_st, sizeof(long long) * 16 * (size_t)n_lists, hipMemcpyDeviceToHost, st));
+    if (!fl.empty()) HIPCHK(hipMemcpyAsync(fl.data(), d_fl, fl.size(), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    sc.settled();
+    for (int64_t t = 0; !fl.empty() && t < n_lists; ++t) memcpy(hit_flags + off[t], fl.data() + poff[t], (size_t)(off[t + 1] - off[t]));
+    return VAPOR_OK;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2538,25 +2556,12 @@ extern "C" int vapor_clean_hits(vapor_ctx* ctx, int64_t n_lists, const int32_t* 
 // positions.  The narrow entry points above keep their limit and their refusals.
 namespace {
 
-struct WideBufs {
-    vapor_ctx* c = nullptr;
-    void* p[10] = {};
-    size_t cap[10] = {};
+struct WideBufs {                  // a route's blocks by slot, each grown to the largest pair so far (Block::ensure)
+    Block<> p[10];
     enum { KEYS, HEAD, NEXT, CNT, OFF, DOTS, FL, SCR, ACC, BOOK };
-    ~WideBufs() { for (void* q : p) dfree(c, q); }
-    // grow-only: the contents are not kept
-    hipError_t ensure(int b, size_t bytes)
-    {
-        bytes = std::max<size_t>(bytes, 256);
-        if (cap[b] >= bytes) return hipSuccess;
-        dfree(c, p[b]);
-        p[b] = nullptr;
-        cap[b] = 0;
-        hipError_t e = dmalloc(c, &p[b], bytes);
-        if (e == hipSuccess) cap[b] = bytes;
-        return e;
-    }
-    template <typename T> T* at(int b) const { return reinterpret_cast<T*>(p[b]); }
+    explicit WideBufs(CallScope& sc) { for (auto& q : p) q.sc = &sc; }
+    hipError_t ensure(int b, size_t bytes) { return p[b].ensure(std::max<size_t>(bytes, 256)); }
+    template <typename T> T* at(int b) const { return reinterpret_cast<T*>(p[b].p); }
 };
 
 inline unsigned wide_grid(int64_t n) { return (unsigned)((n + 255) / 256); }
@@ -2659,26 +2664,29 @@ void wide_join(int k, WideBufs& b, hipStream_t st, const uint32_t* x4_1, int nk1
 
 }  // namespace
 
-#define WIDE_CHK(expr)                                                                        \
-    do {                                                                                      \
-        hipError_t _e = (expr);                                                               \
-        if (_e != hipSuccess)                                                                 \
-            return fail(VAPOR_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));      \
-    } while (0)
-
-extern "C" int vapor_wide_batch(vapor_ctx* ctx, vapor_seqset* set, int64_t n_pairs, const vapor_pair* pairs, int64_t* stats,
-                                int32_t* hits_ji, int64_t hits_capacity, int64_t* hit_off)
+// The per-pair loop of the explicit-dot routes (vapor_wide_batch, vapor_anyk_batch).  A Route supplies three things:
+//   admit(a)                         the status the pair gets before any device work, 0 to go on (the order of a route's
+//                                    refusals is part of its contract);
+//   count(a, s1, s2, nk1, nk2, &at)  enqueues the count pass and says where on the device the number of dots will stand;
+//   emit(a, nk1, nk2)                enqueues the dots into b.DOTS.
+// The loop owns everything else: the accumulator, the read-back of the total, the pair that outgrows max_pair_cap, DOTS / FL,
+// the cleaning, the copies out and hit_off.  Two synchronisations per scored pair, one for a pair without k-mers.
+template <typename Route>
+static int dot_pairs(const std::string& who, vapor_ctx* ctx, vapor_seqset* set, int64_t n_pairs, const vapor_pair* pairs, int64_t* stats,
+              int32_t* hits_ji, int64_t hits_capacity, int64_t* hit_off)
 {
     if (!ctx || !set || n_pairs < 0 || (n_pairs && (!pairs || !stats)) || (hits_ji && !hit_off) || hits_capacity < 0)
-        return fail(VAPOR_E_ARG, "vapor_wide_batch: null argument");
+        return fail(VAPOR_E_ARG, who + ": null argument");
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    WideBufs b;
-    b.c = ctx;
-    WIDE_CHK(b.ensure(WideBufs::ACC, sizeof(WideAcc)));
-    WIDE_CHK(b.ensure(WideBufs::BOOK, sizeof(unsigned long long)));
+    CallScope sc(ctx, st);
     const WideAcc init = wide_acc_init();
-    const unsigned long long cap = (unsigned long long)std::max<int64_t>(ctx->max_pair_cap, 0);
+    WideAcc res;
+    long long total = 0;
+    WideBufs b(sc);
+    Route route(sc, b, set);
+    HIPCHK(b.ensure(WideBufs::ACC, sizeof(WideAcc)));
+    HIPCHK(route.prepare());
     int64_t running = 0;
     if (hit_off) hit_off[0] = 0;
     for (int64_t t = 0; t < n_pairs; ++t) {
@@ -2690,38 +2698,21 @@ extern "C" int vapor_wide_batch(vapor_ctx* ctx, vapor_seqset* set, int64_t n_pai
             s[15] = code;
         };
         int64_t n = 0;
-        if (a.seq1 < 0 || a.seq1 >= set->n || a.seq2 < 0 || a.seq2 >= set->n || a.off2 < 0 || !k_supported(a.k)) {
-            refuse(VAPOR_E_ARG);
-        } else if (set->h[a.seq1].len > VAPOR_MAX_WIDE_SEQ_LEN || set->h[a.seq2].len > VAPOR_MAX_WIDE_SEQ_LEN) {
-            refuse(VAPOR_E_ARG);
-        } else if (set->h[a.seq1].len - a.k + 1 > 0 && set->h[a.seq1].n_invalid > 0) {
-            refuse(VAPOR_E_KEYERROR);
+        if (const int code = route.admit(a)) {
+            refuse(code);
         } else {
             const SeqDesc& s1 = set->h[a.seq1];
             const SeqDesc& s2 = set->h[a.seq2];
             const int nk1 = s1.len - a.k + 1, nk2 = std::max(0, s2.len - a.off2) - a.k + 1;
-            WIDE_CHK(hipMemcpyAsync(b.p[WideBufs::ACC], &init, sizeof(WideAcc), hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(b.p[WideBufs::ACC], &init, sizeof(WideAcc), hipMemcpyHostToDevice, st));
             if (nk1 > 0 && nk2 > 0) {
-                const int64_t ne = 2 * (int64_t)nk1;
-                uint32_t H = 1;
-                while ((int64_t)H < 2 * ne) H <<= 1;
-                WIDE_CHK(b.ensure(WideBufs::KEYS, (size_t)ne * sizeof(uint32_t) * ((4 * a.k + 31) / 32)));
-                WIDE_CHK(b.ensure(WideBufs::HEAD, sizeof(int32_t) * (size_t)H));
-                WIDE_CHK(b.ensure(WideBufs::NEXT, sizeof(int32_t) * (size_t)ne));
-                WIDE_CHK(b.ensure(WideBufs::CNT, sizeof(uint32_t) * (size_t)nk2));
-                WIDE_CHK(b.ensure(WideBufs::OFF, sizeof(long long) * ((size_t)nk2 + 1)));
-                WIDE_CHK(hipMemsetAsync(b.p[WideBufs::HEAD], 0xFF, sizeof(int32_t) * (size_t)H, st));
-                WIDE_CHK(hipMemsetAsync(b.p[WideBufs::BOOK], 0, sizeof(unsigned long long), st));
-                const uint32_t* x4_1 = set->d_x4 + (size_t)s1.chunk0 * 4;
-                const uint32_t* x4_2 = set->d_x4 + (size_t)s2.chunk0 * 4;
-                wide_join(a.k, b, st, x4_1, nk1, x4_2, a.off2, nk2, H - 1, false, cap);
-                WIDE_CHK(hipGetLastError());
-                long long total = 0;
-                WIDE_CHK(hipMemcpyAsync(&total, b.at<long long>(WideBufs::OFF) + nk2, sizeof(long long), hipMemcpyDeviceToHost, st));
-                WIDE_CHK(hipStreamSynchronize(st));
+                const long long* d_total = nullptr;
+                HIPCHK(route.count(a, s1, s2, nk1, nk2, &d_total));
+                HIPCHK(hipMemcpyAsync(&total, d_total, sizeof(long long), hipMemcpyDeviceToHost, st));
+                HIPCHK(hipStreamSynchronize(st));
                 if (total > ctx->max_pair_cap) {
                     // more dots than a pair may hold ("max_pair_cap"): the pair keeps VAPOR_E_OVERFLOW with the dots counted
-                    // before the count pass stopped (more than max_pair_cap, not necessarily all of them)
+                    // (the wide route's count pass stops early: more than max_pair_cap, not necessarily all of them)
                     refuse(VAPOR_E_OVERFLOW);
                     s[0] = total;
                     s[14] = total;
@@ -2729,69 +2720,110 @@ extern "C" int vapor_wide_batch(vapor_ctx* ctx, vapor_seqset* set, int64_t n_pai
                     continue;
                 }
                 n = total;
-                WIDE_CHK(b.ensure(WideBufs::DOTS, sizeof(int2) * (size_t)n));
-                WIDE_CHK(b.ensure(WideBufs::FL, (size_t)n));
+                HIPCHK(b.ensure(WideBufs::DOTS, sizeof(int2) * (size_t)n));
+                HIPCHK(b.ensure(WideBufs::FL, (size_t)n));
                 if (n) {
-                    wide_join(a.k, b, st, x4_1, nk1, x4_2, a.off2, nk2, H - 1, true, cap);
-                    WIDE_CHK(hipGetLastError());
-                    WIDE_CHK(wide_clean(b, st, (int)n, nk1 - 1, nk2 - 1, a.flags));
+                    HIPCHK(route.emit(a, nk1, nk2));
+                    HIPCHK(wide_clean(b, st, (int)n, nk1 - 1, nk2 - 1, a.flags));
                 }
             }
-            WideAcc res;
-            WIDE_CHK(hipMemcpyAsync(&res, b.p[WideBufs::ACC], sizeof(WideAcc), hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(&res, b.p[WideBufs::ACC], sizeof(WideAcc), hipMemcpyDeviceToHost, st));
             if (hits_ji && n && running + n <= hits_capacity)
-                WIDE_CHK(hipMemcpyAsync(hits_ji + 2 * running, b.p[WideBufs::DOTS], sizeof(int2) * (size_t)n, hipMemcpyDeviceToHost, st));
-            WIDE_CHK(hipStreamSynchronize(st));
+                HIPCHK(hipMemcpyAsync(hits_ji + 2 * running, b.p[WideBufs::DOTS], sizeof(int2) * (size_t)n, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
             wide_stats(res, n, a.flags, s);
         }
         running += n;
         if (hit_off) hit_off[t + 1] = running;
     }
+    sc.settled();              // (every pair ended in a synchronisation, a refused one enqueued nothing)
     if (hits_ji && running > hits_capacity)
-        return fail(VAPOR_E_OVERFLOW, "vapor_wide_batch: hits_capacity too small (hit_off[n_pairs] holds the count needed)");
+        return fail(VAPOR_E_OVERFLOW, who + ": hits_capacity too small (hit_off[n_pairs] holds the count needed)");
     return VAPOR_OK;
+}
+
+namespace {
+struct WideRoute {
+    WideBufs& b;
+    hipStream_t st;
+    const vapor_seqset* set;
+    const unsigned long long cap;
+    const uint32_t *x4_1 = nullptr, *x4_2 = nullptr;       // of the pair being counted, for its emit pass
+    uint32_t H = 1;
+    WideRoute(CallScope& sc, WideBufs& bufs, const vapor_seqset* s)
+        : b(bufs), st(sc.st), set(s), cap((unsigned long long)std::max<int64_t>(sc.ctx->max_pair_cap, 0)) {}
+    hipError_t prepare() { return b.ensure(WideBufs::BOOK, sizeof(unsigned long long)); }
+    int admit(const vapor_pair& a) const
+    {
+        if (a.seq1 < 0 || a.seq1 >= set->n || a.seq2 < 0 || a.seq2 >= set->n || a.off2 < 0 || !k_supported(a.k)) return VAPOR_E_ARG;
+        if (set->h[a.seq1].len > VAPOR_MAX_WIDE_SEQ_LEN || set->h[a.seq2].len > VAPOR_MAX_WIDE_SEQ_LEN) return VAPOR_E_ARG;
+        if (set->h[a.seq1].len - a.k + 1 > 0 && set->h[a.seq1].n_invalid > 0) return VAPOR_E_KEYERROR;
+        return 0;
+    }
+    hipError_t count(const vapor_pair& a, const SeqDesc& s1, const SeqDesc& s2, int nk1, int nk2, const long long** d_total)
+    {
+        const int64_t ne = 2 * (int64_t)nk1;
+        for (H = 1; (int64_t)H < 2 * ne;) H <<= 1;
+        hipError_t e;
+        if ((e = b.ensure(WideBufs::KEYS, (size_t)ne * sizeof(uint32_t) * ((4 * a.k + 31) / 32))) != hipSuccess) return e;
+        if ((e = b.ensure(WideBufs::HEAD, sizeof(int32_t) * (size_t)H)) != hipSuccess) return e;
+        if ((e = b.ensure(WideBufs::NEXT, sizeof(int32_t) * (size_t)ne)) != hipSuccess) return e;
+        if ((e = b.ensure(WideBufs::CNT, sizeof(uint32_t) * (size_t)nk2)) != hipSuccess) return e;
+        if ((e = b.ensure(WideBufs::OFF, sizeof(long long) * ((size_t)nk2 + 1))) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(b.p[WideBufs::HEAD], 0xFF, sizeof(int32_t) * (size_t)H, st)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(b.p[WideBufs::BOOK], 0, sizeof(unsigned long long), st)) != hipSuccess) return e;
+        x4_1 = set->d_x4 + (size_t)s1.chunk0 * 4;
+        x4_2 = set->d_x4 + (size_t)s2.chunk0 * 4;
+        wide_join(a.k, b, st, x4_1, nk1, x4_2, a.off2, nk2, H - 1, false, cap);
+        *d_total = b.at<long long>(WideBufs::OFF) + nk2;
+        return hipGetLastError();
+    }
+    hipError_t emit(const vapor_pair& a, int nk1, int nk2)
+    {
+        wide_join(a.k, b, st, x4_1, nk1, x4_2, a.off2, nk2, H - 1, true, cap);
+        return hipGetLastError();
+    }
+};
+}  // namespace
+
+extern "C" int vapor_wide_batch(vapor_ctx* ctx, vapor_seqset* set, int64_t n_pairs, const vapor_pair* pairs, int64_t* stats,
+                                int32_t* hits_ji, int64_t hits_capacity, int64_t* hit_off)
+{
+    return dot_pairs<WideRoute>("vapor_wide_batch", ctx, set, n_pairs, pairs, stats, hits_ji, hits_capacity, hit_off);
 }
 
 extern "C" int vapor_clean_hits_wide(vapor_ctx* ctx, int64_t n_lists, const int32_t* hits_ji, const int64_t* off,
                                      const uint32_t* flags, int64_t* stats, uint8_t* hit_flags)
 {
-    if (!ctx || n_lists < 0 || (n_lists && (!off || !stats))) return fail(VAPOR_E_ARG, "vapor_clean_hits_wide: null argument");
+    if (const int rc = clean_lists_check("vapor_clean_hits_wide", ctx, n_lists, hits_ji, off, stats, VAPOR_MAX_WIDE_SEQ_LEN,
+                                         ctx ? ctx->max_pair_cap : 0))
+        return rc;
     if (n_lists == 0) return VAPOR_OK;
-    const int64_t tot = off[n_lists];
-    if (tot && !hits_ji) return fail(VAPOR_E_ARG, "vapor_clean_hits_wide: null hit list");
-    for (int64_t t = 0; t < n_lists; ++t) {
-        if (off[t + 1] < off[t] || off[t + 1] - off[t] > ctx->max_pair_cap)
-            return fail(VAPOR_E_ARG, "vapor_clean_hits_wide: bad list offsets");
-        for (int64_t h = off[t]; h < off[t + 1]; ++h) {
-            const int j = hits_ji[2 * h], i = hits_ji[2 * h + 1];
-            if (j < 0 || i < 0 || j > VAPOR_MAX_WIDE_SEQ_LEN || i > VAPOR_MAX_WIDE_SEQ_LEN)
-                return fail(VAPOR_E_ARG, "vapor_clean_hits_wide: coordinate out of range");
-        }
-    }
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    WideBufs b;
-    b.c = ctx;
-    WIDE_CHK(b.ensure(WideBufs::ACC, sizeof(WideAcc)));
+    CallScope sc(ctx, st);
     const WideAcc init = wide_acc_init();
+    WideAcc res;
+    WideBufs b(sc);
+    HIPCHK(b.ensure(WideBufs::ACC, sizeof(WideAcc)));
     for (int64_t t = 0; t < n_lists; ++t) {
         const int64_t n = off[t + 1] - off[t];
         const uint32_t f = flags ? flags[t] : 3u;
         int mi = 0, mj = 0;
         for (int64_t h = off[t]; h < off[t + 1]; ++h) { mj = std::max(mj, hits_ji[2 * h]); mi = std::max(mi, hits_ji[2 * h + 1]); }
-        WIDE_CHK(hipMemcpyAsync(b.p[WideBufs::ACC], &init, sizeof(WideAcc), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(b.p[WideBufs::ACC], &init, sizeof(WideAcc), hipMemcpyHostToDevice, st));
         if (n) {
-            WIDE_CHK(b.ensure(WideBufs::DOTS, sizeof(int2) * (size_t)n));
-            WIDE_CHK(b.ensure(WideBufs::FL, (size_t)n));
-            WIDE_CHK(hipMemcpyAsync(b.p[WideBufs::DOTS], hits_ji + 2 * off[t], sizeof(int2) * (size_t)n, hipMemcpyHostToDevice, st));
-            WIDE_CHK(wide_clean(b, st, (int)n, mi, mj, f));
+            HIPCHK(b.ensure(WideBufs::DOTS, sizeof(int2) * (size_t)n));
+            HIPCHK(b.ensure(WideBufs::FL, (size_t)n));
+            HIPCHK(hipMemcpyAsync(b.p[WideBufs::DOTS], hits_ji + 2 * off[t], sizeof(int2) * (size_t)n, hipMemcpyHostToDevice, st));
+            HIPCHK(wide_clean(b, st, (int)n, mi, mj, f));
         }
-        WideAcc res;
-        WIDE_CHK(hipMemcpyAsync(&res, b.p[WideBufs::ACC], sizeof(WideAcc), hipMemcpyDeviceToHost, st));
-        if (hit_flags && n) WIDE_CHK(hipMemcpyAsync(hit_flags + off[t], b.p[WideBufs::FL], (size_t)n, hipMemcpyDeviceToHost, st));
-        WIDE_CHK(hipStreamSynchronize(st));
+        HIPCHK(hipMemcpyAsync(&res, b.p[WideBufs::ACC], sizeof(WideAcc), hipMemcpyDeviceToHost, st));
+        if (hit_flags && n) HIPCHK(hipMemcpyAsync(hit_flags + off[t], b.p[WideBufs::FL], (size_t)n, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
         wide_stats(res, n, f, stats + 16 * t);
     }
+    sc.settled();
     return VAPOR_OK;
 }
 
@@ -2802,6 +2834,7 @@ namespace {
 
 // the pair's symbol bytes, sorted entries and per-j counts: enqueued on st, the number of dots at b.OFF[nk2]
 struct AnykBufs : WideBufs {
+    using WideBufs::WideBufs;
     enum { SYM, IDX, CNT, FIRST, OFF, ISF, RUN, RANK, KEYS };
 };
 
@@ -2875,97 +2908,63 @@ void anyk_emit(AnykBufs& x, hipStream_t st, const AnykSrc& src, int nk1, int nk2
 
 }  // namespace
 
+namespace {
+struct AnykRoute {
+    WideBufs& b;
+    AnykBufs x;
+    hipStream_t st;
+    const vapor_seqset* set;
+    AnykSrc src{};                                 // of the pair being counted, for its emit pass
+    AnykRoute(CallScope& sc, WideBufs& bufs, const vapor_seqset* s) : b(bufs), x(sc), st(sc.st), set(s) {}
+    hipError_t prepare() { return hipSuccess; }
+    bool no_bytes(int32_t q) const                 // a symbol outside the alphabet whose byte was not kept
+    {
+        return set->h[q].n_invalid > 0 && (q >= (int32_t)set->raw_off.size() || set->raw_off[q] < 0);
+    }
+    int admit(const vapor_pair& a) const
+    {
+        const bool inv = !(a.flags & VAPOR_PF_FORWARD);
+        if (a.seq1 < 0 || a.seq1 >= set->n || a.seq2 < 0 || a.seq2 >= set->n || a.off2 < 0 || a.k < 1 || a.k > VAPOR_MAX_ANY_K) return VAPOR_E_ARG;
+        if (set->h[a.seq1].len > VAPOR_MAX_WIDE_SEQ_LEN || set->h[a.seq2].len > VAPOR_MAX_WIDE_SEQ_LEN) return VAPOR_E_ARG;
+        if (inv && set->h[a.seq1].len - a.k + 1 > 0 && set->h[a.seq1].n_invalid > 0) return VAPOR_E_KEYERROR;
+        if (!inv && (no_bytes(a.seq1) || no_bytes(a.seq2))) return VAPOR_E_ARG;
+        return 0;
+    }
+    hipError_t count(const vapor_pair& a, const SeqDesc& s1, const SeqDesc& s2, int nk1, int nk2, const long long** d_total)
+    {
+        const bool inv = !(a.flags & VAPOR_PF_FORWARD);
+        const int n2 = std::max(0, s2.len - a.off2);
+        const size_t o_r1 = anyk_pad(s1.len), o_s2 = o_r1 + (inv ? anyk_pad(s1.len) : 0);
+        hipError_t e = x.ensure(AnykBufs::SYM, o_s2 + anyk_pad(n2));
+        if (e != hipSuccess) return e;
+        uint8_t* sym = x.at<uint8_t>(AnykBufs::SYM);
+        const uint32_t* x4_1 = set->d_x4 + (size_t)s1.chunk0 * 4;
+        const uint32_t* x4_2 = set->d_x4 + (size_t)s2.chunk0 * 4;
+        const uint8_t* raw1 = !inv && s1.n_invalid > 0 ? set->d_raw + set->raw_off[a.seq1] : nullptr;
+        const uint8_t* raw2 = s2.n_invalid > 0 && a.seq2 < (int32_t)set->raw_off.size() && set->raw_off[a.seq2] >= 0
+                                  ? set->d_raw + set->raw_off[a.seq2] : nullptr;
+        hipLaunchKernelGGL(anyk_sym_kernel, dim3(wide_grid(s1.len)), dim3(256), 0, st, x4_1, raw1, (int)(s1.flags & 1u), 0, s1.len,
+                           sym, inv ? sym + o_r1 : (uint8_t*)nullptr);
+        // (with inversions a symbol of seq2 outside the alphabet matches nothing: it stays 0xFF)
+        hipLaunchKernelGGL(anyk_sym_kernel, dim3(wide_grid(n2)), dim3(256), 0, st, x4_2, inv ? (const uint8_t*)nullptr : raw2,
+                           (int)(s2.flags & 1u), a.off2, n2, sym + o_s2, (uint8_t*)nullptr);
+        src = AnykSrc{sym, sym + o_r1, sym + o_s2, s1.len, a.k, inv ? 1 : 0};
+        if ((e = anyk_count(x, st, src, nk1, nk2)) != hipSuccess) return e;
+        *d_total = x.at<long long>(AnykBufs::OFF) + nk2;
+        return hipSuccess;
+    }
+    hipError_t emit(const vapor_pair&, int nk1, int nk2)
+    {
+        anyk_emit(x, st, src, nk1, nk2, b.at<int2>(WideBufs::DOTS));
+        return hipGetLastError();
+    }
+};
+}  // namespace
+
 extern "C" int vapor_anyk_batch(vapor_ctx* ctx, vapor_seqset* set, int64_t n_pairs, const vapor_pair* pairs, int64_t* stats,
                                 int32_t* hits_ji, int64_t hits_capacity, int64_t* hit_off)
 {
-    if (!ctx || !set || n_pairs < 0 || (n_pairs && (!pairs || !stats)) || (hits_ji && !hit_off) || hits_capacity < 0)
-        return fail(VAPOR_E_ARG, "vapor_anyk_batch: null argument");
-    HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    WideBufs b;
-    b.c = ctx;
-    AnykBufs x;
-    x.c = ctx;
-    WIDE_CHK(b.ensure(WideBufs::ACC, sizeof(WideAcc)));
-    const WideAcc init = wide_acc_init();
-    int64_t running = 0;
-    if (hit_off) hit_off[0] = 0;
-    for (int64_t t = 0; t < n_pairs; ++t) {
-        const vapor_pair& a = pairs[t];
-        int64_t* s = stats + 16 * t;
-        auto refuse = [&](int code) {
-            for (int q = 0; q < 16; ++q) s[q] = 0;
-            s[1] = s[2] = -1;
-            s[15] = code;
-        };
-        const bool inv = !(a.flags & VAPOR_PF_FORWARD);
-        auto no_bytes = [&](int32_t q) {          // a symbol outside the alphabet whose byte was not kept
-            return set->h[q].n_invalid > 0 && (q >= (int32_t)set->raw_off.size() || set->raw_off[q] < 0);
-        };
-        int64_t n = 0;
-        if (a.seq1 < 0 || a.seq1 >= set->n || a.seq2 < 0 || a.seq2 >= set->n || a.off2 < 0 || a.k < 1 || a.k > VAPOR_MAX_ANY_K) {
-            refuse(VAPOR_E_ARG);
-        } else if (set->h[a.seq1].len > VAPOR_MAX_WIDE_SEQ_LEN || set->h[a.seq2].len > VAPOR_MAX_WIDE_SEQ_LEN) {
-            refuse(VAPOR_E_ARG);
-        } else if (inv && set->h[a.seq1].len - a.k + 1 > 0 && set->h[a.seq1].n_invalid > 0) {
-            refuse(VAPOR_E_KEYERROR);
-        } else if (!inv && (no_bytes(a.seq1) || no_bytes(a.seq2))) {
-            refuse(VAPOR_E_ARG);
-        } else {
-            const SeqDesc& s1 = set->h[a.seq1];
-            const SeqDesc& s2 = set->h[a.seq2];
-            const int n2 = std::max(0, s2.len - a.off2);
-            const int nk1 = s1.len - a.k + 1, nk2 = n2 - a.k + 1;
-            WIDE_CHK(hipMemcpyAsync(b.p[WideBufs::ACC], &init, sizeof(WideAcc), hipMemcpyHostToDevice, st));
-            if (nk1 > 0 && nk2 > 0) {
-                const size_t o_r1 = anyk_pad(s1.len), o_s2 = o_r1 + (inv ? anyk_pad(s1.len) : 0);
-                WIDE_CHK(x.ensure(AnykBufs::SYM, o_s2 + anyk_pad(n2)));
-                uint8_t* sym = x.at<uint8_t>(AnykBufs::SYM);
-                const uint32_t* x4_1 = set->d_x4 + (size_t)s1.chunk0 * 4;
-                const uint32_t* x4_2 = set->d_x4 + (size_t)s2.chunk0 * 4;
-                const uint8_t* raw1 = !inv && s1.n_invalid > 0 ? set->d_raw + set->raw_off[a.seq1] : nullptr;
-                const uint8_t* raw2 = s2.n_invalid > 0 && a.seq2 < (int32_t)set->raw_off.size() && set->raw_off[a.seq2] >= 0
-                                          ? set->d_raw + set->raw_off[a.seq2] : nullptr;
-                hipLaunchKernelGGL(anyk_sym_kernel, dim3(wide_grid(s1.len)), dim3(256), 0, st, x4_1, raw1, (int)(s1.flags & 1u), 0, s1.len,
-                                   sym, inv ? sym + o_r1 : (uint8_t*)nullptr);
-                // (with inversions a symbol of seq2 outside the alphabet matches nothing: it stays 0xFF)
-                hipLaunchKernelGGL(anyk_sym_kernel, dim3(wide_grid(n2)), dim3(256), 0, st, x4_2, inv ? (const uint8_t*)nullptr : raw2,
-                                   (int)(s2.flags & 1u), a.off2, n2, sym + o_s2, (uint8_t*)nullptr);
-                const AnykSrc src{sym, sym + o_r1, sym + o_s2, s1.len, a.k, inv ? 1 : 0};
-                WIDE_CHK(anyk_count(x, st, src, nk1, nk2));
-                long long total = 0;
-                WIDE_CHK(hipMemcpyAsync(&total, x.at<long long>(AnykBufs::OFF) + nk2, sizeof(long long), hipMemcpyDeviceToHost, st));
-                WIDE_CHK(hipStreamSynchronize(st));
-                if (total > ctx->max_pair_cap) {
-                    // more dots than a pair may hold ("max_pair_cap"): the pair keeps VAPOR_E_OVERFLOW with its count
-                    refuse(VAPOR_E_OVERFLOW);
-                    s[0] = total;
-                    s[14] = total;
-                    if (hit_off) hit_off[t + 1] = running;
-                    continue;
-                }
-                n = total;
-                WIDE_CHK(b.ensure(WideBufs::DOTS, sizeof(int2) * (size_t)n));
-                WIDE_CHK(b.ensure(WideBufs::FL, (size_t)n));
-                if (n) {
-                    anyk_emit(x, st, src, nk1, nk2, b.at<int2>(WideBufs::DOTS));
-                    WIDE_CHK(hipGetLastError());
-                    WIDE_CHK(wide_clean(b, st, (int)n, nk1 - 1, nk2 - 1, a.flags));
-                }
-            }
-            WideAcc res;
-            WIDE_CHK(hipMemcpyAsync(&res, b.p[WideBufs::ACC], sizeof(WideAcc), hipMemcpyDeviceToHost, st));
-            if (hits_ji && n && running + n <= hits_capacity)
-                WIDE_CHK(hipMemcpyAsync(hits_ji + 2 * running, b.p[WideBufs::DOTS], sizeof(int2) * (size_t)n, hipMemcpyDeviceToHost, st));
-            WIDE_CHK(hipStreamSynchronize(st));
-            wide_stats(res, n, a.flags, s);
-        }
-        running += n;
-        if (hit_off) hit_off[t + 1] = running;
-    }
-    if (hits_ji && running > hits_capacity)
-        return fail(VAPOR_E_OVERFLOW, "vapor_anyk_batch: hits_capacity too small (hit_off[n_pairs] holds the count needed)");
-    return VAPOR_OK;
+    return dot_pairs<AnykRoute>("vapor_anyk_batch", ctx, set, n_pairs, pairs, stats, hits_ji, hits_capacity, hit_off);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2990,9 +2989,7 @@ extern "C" int vapor_plan_set_reads(vapor_plan* p, int64_t n_reads, const vapor_
         first[(size_t)x.locus + 1]++;
     }
     for (int64_t l = 0; l < n_loci; ++l) first[l + 1] += first[l];
-    dfree(p->ctx, p->d_reads); dfree(p->ctx, p->d_read_scores); dfree(p->ctx, p->d_loci);
-    if (p->own_gt) dfree(p->ctx, p->d_gt);
-    p->d_reads = nullptr; p->d_locus_first = nullptr; p->d_gt = nullptr; p->own_gt = false; p->d_read_scores = nullptr; p->d_loci = nullptr;
+    plan_free_reads(p);
     // the read table and the locus offsets travel as one block (one blocking copy out of caller memory instead of two)
     const size_t reads_bytes = (sizeof(DRead) * (size_t)std::max<int64_t>(n_reads, 1) + 15) & ~(size_t)15;
     const size_t first_bytes = sizeof(int32_t) * first.size();
@@ -3025,8 +3022,7 @@ extern "C" int vapor_plan_set_reads(vapor_plan* p, int64_t n_reads, const vapor_
     p->n_loci = n_loci;
     p->h_locus_first = first;
     // (a grid described for an earlier read table does not describe this one)
-    dfree(p->ctx, p->d_grid); dfree(p->ctx, p->d_group_out); dfree(p->ctx, p->d_winner_scores);
-    p->d_grid = nullptr; p->d_group_out = nullptr; p->d_winner_scores = nullptr; p->n_groups = 0;
+    plan_free_grid(p);
     return VAPOR_OK;
 }
 
@@ -3060,8 +3056,7 @@ extern "C" int vapor_plan_set_grid(vapor_plan* p, int64_t n_groups, const int32_
     std::vector<int32_t> off;
     const int rc = grid_check(n_groups, first_locus, p->n_loci, p->h_locus_first.data(), &off);
     if (rc != VAPOR_OK) return rc;
-    dfree(p->ctx, p->d_grid); dfree(p->ctx, p->d_group_out); dfree(p->ctx, p->d_winner_scores);
-    p->d_grid = nullptr; p->d_group_out = nullptr; p->d_winner_scores = nullptr; p->n_groups = 0;
+    plan_free_grid(p);
     if (n_groups == 0) return VAPOR_OK;
     const size_t ng = (size_t)n_groups;
     std::vector<int32_t> block(3 * ng + 2, 0);
@@ -3196,33 +3191,28 @@ extern "C" int vapor_grid_pick(vapor_ctx* ctx, int64_t n_groups, const int32_t* 
     memcpy(block.data(), first_locus, sizeof(int32_t) * (ng + 1));
     memcpy(block.data() + ng + 1, off.data(), sizeof(int32_t) * (ng + 1));
     memcpy(block.data() + 3 * ng + 2, read_first, sizeof(int32_t) * (nl + 1));
-    int32_t* d_block = nullptr;
-    double *d_rec = nullptr, *d_sc = nullptr, *d_out = nullptr, *d_win = nullptr;
     hipStream_t st = ctx->stream;
-    int res = VAPOR_OK;
-    auto step = [&](hipError_t e, const char* what) {
-        if (res == VAPOR_OK && e != hipSuccess) res = fail(VAPOR_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
-        return res == VAPOR_OK;
-    };
-    if (step(dmalloc(ctx, (void**)&d_block, sizeof(int32_t) * block.size()), "dmalloc") &&
-        step(dmalloc(ctx, (void**)&d_rec, sizeof(double) * 8 * nl), "dmalloc") &&
-        step(dmalloc(ctx, (void**)&d_sc, sizeof(double) * std::max<size_t>(nr, 1)), "dmalloc") &&
-        step(dmalloc(ctx, (void**)&d_out, sizeof(double) * 16 * ng), "dmalloc") &&
-        step(dmalloc(ctx, (void**)&d_win, sizeof(double) * std::max<size_t>(nw, 1)), "dmalloc") &&
-        step(hipMemcpyAsync(d_block, block.data(), sizeof(int32_t) * block.size(), hipMemcpyHostToDevice, st), "hipMemcpyAsync") &&
-        step(hipMemcpyAsync(d_rec, records, sizeof(double) * 8 * nl, hipMemcpyHostToDevice, st), "hipMemcpyAsync") &&
-        (nr == 0 || step(hipMemcpyAsync(d_sc, read_scores, sizeof(double) * nr, hipMemcpyHostToDevice, st), "hipMemcpyAsync"))) {
-        int32_t* d_idx = d_block + 2 * ng + 2;
-        hipLaunchKernelGGL(grid_pick_kernel, dim3((unsigned)ng), dim3(64), 0, st, d_rec, d_block, d_block + 3 * ng + 2, d_sc,
-                           d_block + ng + 1, d_idx, d_out, d_win);
-        step(hipGetLastError(), "grid_pick_kernel");
-        if (winner_idx) step(hipMemcpyAsync(winner_idx, d_idx, sizeof(int32_t) * ng, hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
-        if (group_out) step(hipMemcpyAsync(group_out, d_out, sizeof(double) * 16 * ng, hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
-        if (winner_scores && nw) step(hipMemcpyAsync(winner_scores, d_win, sizeof(double) * nw, hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
-    }
-    (void)hipStreamSynchronize(st);
-    dfree(ctx, d_block); dfree(ctx, d_rec); dfree(ctx, d_sc); dfree(ctx, d_out); dfree(ctx, d_win);
-    return res;
+    CallScope sc(ctx, st);
+    Block<int32_t> d_block(sc);
+    Block<double> d_rec(sc), d_sc(sc), d_out(sc), d_win(sc);
+    HIPCHK(d_block.ensure(sizeof(int32_t) * block.size()));
+    HIPCHK(d_rec.ensure(sizeof(double) * 8 * nl));
+    HIPCHK(d_sc.ensure(sizeof(double) * std::max<size_t>(nr, 1)));
+    HIPCHK(d_out.ensure(sizeof(double) * 16 * ng));
+    HIPCHK(d_win.ensure(sizeof(double) * std::max<size_t>(nw, 1)));
+    HIPCHK(hipMemcpyAsync(d_block, block.data(), sizeof(int32_t) * block.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_rec, records, sizeof(double) * 8 * nl, hipMemcpyHostToDevice, st));
+    if (nr) HIPCHK(hipMemcpyAsync(d_sc, read_scores, sizeof(double) * nr, hipMemcpyHostToDevice, st));
+    int32_t* d_idx = d_block + 2 * ng + 2;
+    hipLaunchKernelGGL(grid_pick_kernel, dim3((unsigned)ng), dim3(64), 0, st, d_rec.p, d_block.p, d_block + 3 * ng + 2, d_sc.p,
+                       d_block + ng + 1, d_idx, d_out.p, d_win.p);
+    HIPCHK(hipGetLastError());
+    if (winner_idx) HIPCHK(hipMemcpyAsync(winner_idx, d_idx, sizeof(int32_t) * ng, hipMemcpyDeviceToHost, st));
+    if (group_out) HIPCHK(hipMemcpyAsync(group_out, d_out, sizeof(double) * 16 * ng, hipMemcpyDeviceToHost, st));
+    if (winner_scores && nw) HIPCHK(hipMemcpyAsync(winner_scores, d_win, sizeof(double) * nw, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    sc.settled();
+    return VAPOR_OK;
 }
 
 // ------------------------------------------------------------------------------------------

@@ -29,6 +29,13 @@ def _ascii_data_offset() -> int:
 _ASCII_OFF = _ascii_data_offset()
 
 
+def _derived_lens(seg_first, segs) -> np.ndarray:
+    """The lengths of derived sequences: the sum of each one's segment lengths."""
+    dl = np.zeros(len(seg_first) - 1, dtype=np.int32)
+    np.add.at(dl, np.repeat(np.arange(len(dl)), np.diff(seg_first)), segs["len"][:int(seg_first[-1])])
+    return dl
+
+
 def _as_bytes(s) -> bytes:
     return s if isinstance(s, (bytes, bytearray)) else s.encode("latin-1", "replace")
 
@@ -107,9 +114,7 @@ class SeqSet:
                                                     np.ascontiguousarray(segs, dtype=L.SEG_DTYPE).ctypes.data_as(ctypes.c_void_p),
                                                     L.ptr(np.ascontiguousarray(dflags, dtype=np.uint8), ctypes.c_uint8),
                                                     L.ptr(info, ctypes.c_int32), ctypes.byref(h)))
-            dl = np.zeros(nd, dtype=np.int32)
-            np.add.at(dl, np.repeat(np.arange(nd), np.diff(seg_first)), segs["len"][:int(seg_first[-1])])
-            self.lens = np.concatenate([self.lens[:self.n], dl])
+            self.lens = np.concatenate([self.lens[:self.n], _derived_lens(seg_first, segs)])
             self.n += nd
         else:
             info = np.zeros(2 * n1, dtype=np.int32)
@@ -156,23 +161,17 @@ class SeqSet:
                                                   nd, L.ptr(seg_first, ctypes.c_int32) if nd else None,
                                                   segs.ctypes.data_as(ctypes.c_void_p) if nd else None,
                                                   L.ptr(dfl, ctypes.c_uint8) if nd else None, L.ptr(info, ctypes.c_int32), ctypes.byref(h)))
-            if nd:
-                dl = np.zeros(nd, dtype=np.int32)
-                np.add.at(dl, np.repeat(np.arange(nd), np.diff(seg_first)), segs["len"][:int(seg_first[-1])])
-                self.lens = np.concatenate([self.lens, dl])
-                self.n += nd
         elif nd:
             seg_first = np.ascontiguousarray(seg_first, dtype=np.int32)
             segs = np.ascontiguousarray(segs, dtype=L.SEG_DTYPE)
             L.check(lib.vapor_seqset_create_derived(engine._ctx, self.n, ptrs, lens_p, None, nd, L.ptr(seg_first, ctypes.c_int32),
                                                     segs.ctypes.data_as(ctypes.c_void_p), L.ptr(np.ascontiguousarray(dflags, dtype=np.uint8), ctypes.c_uint8),
                                                     L.ptr(info, ctypes.c_int32), ctypes.byref(h)))
-            dl = np.zeros(nd, dtype=np.int32)
-            np.add.at(dl, np.repeat(np.arange(nd), np.diff(seg_first)), segs["len"][:int(seg_first[-1])])
-            self.lens = np.concatenate([self.lens, dl])
-            self.n += nd
         else:
             L.check(lib.vapor_seqset_create_ptrs(engine._ctx, self.n, ptrs, lens_p, None, L.ptr(info, ctypes.c_int32), ctypes.byref(h)))
+        if nd:
+            self.lens = np.concatenate([self.lens, _derived_lens(seg_first, segs)])
+            self.n += nd
         del keepalive
         self._h = h
         engine._live.add(self)
@@ -465,8 +464,7 @@ class Engine:
             out.append(h[np.lexsort((h[:, 1], h[:, 0]))])
         return st, out
 
-    def clean_hits(self, lists: Sequence[np.ndarray], flags: Optional[Sequence[int]] = None):
-        """Cleaning + reductions on explicit dot lists -> (stats (n,16), [flag bytes per list])."""
+    def _clean_lists(self, fn, lists, flags):
         n = len(lists)
         arrs = [np.ascontiguousarray(a, dtype=np.int32).reshape(-1, 2) for a in lists]
         off = np.zeros(n + 1, dtype=np.int64)
@@ -475,34 +473,40 @@ class Engine:
         fl = np.asarray(flags if flags is not None else [3] * n, dtype=np.uint32)
         st = np.zeros((max(n, 1), 16), dtype=np.int64)
         hf = np.zeros(max(int(off[-1]), 1), dtype=np.uint8)
-        L.check(L.load().vapor_clean_hits(self._ctx, n, L.ptr(allh, ctypes.c_int32), L.ptr(off, ctypes.c_int64),
-                                          L.ptr(fl if n else np.zeros(1, np.uint32), ctypes.c_uint32),
-                                          L.ptr(st, ctypes.c_int64), L.ptr(hf, ctypes.c_uint8)))
+        L.check(fn(self._ctx, n, L.ptr(allh, ctypes.c_int32), L.ptr(off, ctypes.c_int64),
+                   L.ptr(fl if n else np.zeros(1, np.uint32), ctypes.c_uint32), L.ptr(st, ctypes.c_int64), L.ptr(hf, ctypes.c_uint8)))
         return st[:n], [hf[off[t]:off[t + 1]] for t in range(n)]
 
-    # ---- the wide route: sequences longer than MAX_SEQ_LEN (up to MAX_WIDE_SEQ_LEN) ----
+    def clean_hits(self, lists: Sequence[np.ndarray], flags: Optional[Sequence[int]] = None):
+        """Cleaning + reductions on explicit dot lists -> (stats (n,16), [flag bytes per list])."""
+        return self._clean_lists(L.load().vapor_clean_hits, lists, flags)
+
+    # ---- the optional entry points: the wide route (sequences up to MAX_WIDE_SEQ_LEN), the any-k route, refinement ----
     @staticmethod
     def _wide_entry(name: str, what: str = "wide route"):
+        """An optional entry point of the loaded library - any of them, not the wide route's alone (the name is older than the
+        others) - or NotImplementedError."""
         lib = L.load()
-        # (the CPU twin of the C ABI exports the names with a stub that refuses every call: it has no wide route either)
+        # (the CPU twin of the C ABI exports the names with a stub that refuses every call: it has none of these routes either)
         flags = lib.vapor_build_flags() if hasattr(lib, "vapor_build_flags") else b""
         if not hasattr(lib, name) or "cpu-twin" in (flags or b"").decode().split(","):
             raise NotImplementedError("%s: the loaded library has no %s" % (name, what))
         return getattr(lib, name)
 
-    def wide_available(self) -> bool:
-        """Whether the loaded library has the wide route (the CPU twin of the C ABI has not)."""
+    def _available(self, *names: str) -> bool:
         try:
-            self._wide_entry("vapor_wide_batch")
-            self._wide_entry("vapor_clean_hits_wide")
+            for name in names:
+                self._wide_entry(name)
         except NotImplementedError:
             return False
         return True
 
-    def score_wide(self, seqset: SeqSet, pairs: np.ndarray, want_hits: bool = False):
-        """Statistics (n,16) of every pair on the wide route (vapor_wide_batch); with want_hits also, per pair, the (n,2) [j,i]
-        hit array sorted the way dotdata() lists it."""
-        fn = self._wide_entry("vapor_wide_batch")
+    def wide_available(self) -> bool:
+        """Whether the loaded library has the wide route (the CPU twin of the C ABI has not)."""
+        return self._available("vapor_wide_batch", "vapor_clean_hits_wide")
+
+    def _score_dots(self, name: str, seqset: SeqSet, pairs: np.ndarray, want_hits: bool, sort: bool):
+        fn = self._wide_entry(name)
         pairs = np.ascontiguousarray(pairs, dtype=L.PAIR_DTYPE)
         n = len(pairs)
         st = np.zeros((max(n, 1), 16), dtype=np.int64)
@@ -521,20 +525,17 @@ class Engine:
                 continue
             L.check(rc)
             break
-        out = []
-        for t in range(n):
-            h = hits[off[t]:off[t + 1]]
-            out.append(h[np.lexsort((h[:, 1], h[:, 0]))])
-        return st[:n], out
+        out = [hits[off[t]:off[t + 1]] for t in range(n)]
+        return st[:n], [h[np.lexsort((h[:, 1], h[:, 0]))] if sort else h.copy() for h in out]
+
+    def score_wide(self, seqset: SeqSet, pairs: np.ndarray, want_hits: bool = False):
+        """Statistics (n,16) of every pair on the wide route (vapor_wide_batch); with want_hits also, per pair, the (n,2) [j,i]
+        hit array sorted the way dotdata() lists it."""
+        return self._score_dots("vapor_wide_batch", seqset, pairs, want_hits, sort=True)
 
     def grid_available(self) -> bool:
         """Whether the loaded library has breakpoint refinement's device step (the CPU twin of the C ABI has not)."""
-        try:
-            self._wide_entry("vapor_plan_set_grid", "refinement kernel")
-            self._wide_entry("vapor_plan_run_grid", "refinement kernel")
-        except NotImplementedError:
-            return False
-        return True
+        return self._available("vapor_plan_set_grid", "vapor_plan_run_grid")
 
     def grid_pick(self, records: np.ndarray, first_locus, read_first, read_scores):
         """vapor_grid_pick: grid_pick_kernel on the caller's tables - (n, 8) candidate records, groups first_locus[g] ..
@@ -561,50 +562,16 @@ class Engine:
     # ---- the any-k route: kmerhits at every k from 1 to MAX_ANY_K ----
     def anyk_available(self) -> bool:
         """Whether the loaded library has the any-k route (the CPU twin of the C ABI has not)."""
-        try:
-            self._wide_entry("vapor_anyk_batch")
-        except NotImplementedError:
-            return False
-        return True
+        return self._available("vapor_anyk_batch")
 
     def score_anyk(self, seqset: SeqSet, pairs: np.ndarray, want_hits: bool = False):
         """Statistics (n,16) of every pair on the any-k route (vapor_anyk_batch: k from 1 to MAX_ANY_K, PF_FORWARD for
         kmerhits(..., inversions=False)); with want_hits also, per pair, the (n,2) [j,i] hit array in the reference's order."""
-        fn = self._wide_entry("vapor_anyk_batch")
-        pairs = np.ascontiguousarray(pairs, dtype=L.PAIR_DTYPE)
-        n = len(pairs)
-        st = np.zeros((max(n, 1), 16), dtype=np.int64)
-        off = np.zeros(n + 1, dtype=np.int64)
-        pp = pairs.ctypes.data if n else None
-        if not want_hits:
-            L.check(fn(self._ctx, seqset._h, n, pp, L.ptr(st, ctypes.c_int64), None, 0, L.ptr(off, ctypes.c_int64)))
-            return st[:n]
-        cap = 1 << 16
-        while True:
-            hits = np.zeros((cap, 2), dtype=np.int32)
-            rc = fn(self._ctx, seqset._h, n, pp, L.ptr(st, ctypes.c_int64), L.ptr(hits, ctypes.c_int32), cap,
-                    L.ptr(off, ctypes.c_int64))
-            if rc == L.E_OVERFLOW and int(off[n]) > cap:
-                cap = int(off[n])
-                continue
-            L.check(rc)
-            break
-        return st[:n], [hits[off[t]:off[t + 1]].copy() for t in range(n)]
+        return self._score_dots("vapor_anyk_batch", seqset, pairs, want_hits, sort=False)
 
     def clean_hits_wide(self, lists: Sequence[np.ndarray], flags: Optional[Sequence[int]] = None):
         """clean_hits for lists with coordinates up to MAX_WIDE_SEQ_LEN (vapor_clean_hits_wide)."""
-        fn = self._wide_entry("vapor_clean_hits_wide")
-        n = len(lists)
-        arrs = [np.ascontiguousarray(a, dtype=np.int32).reshape(-1, 2) for a in lists]
-        off = np.zeros(n + 1, dtype=np.int64)
-        np.cumsum([len(a) for a in arrs], out=off[1:])
-        allh = np.concatenate(arrs + [np.zeros((1, 2), np.int32)])
-        fl = np.asarray(flags if flags is not None else [3] * n, dtype=np.uint32)
-        st = np.zeros((max(n, 1), 16), dtype=np.int64)
-        hf = np.zeros(max(int(off[-1]), 1), dtype=np.uint8)
-        L.check(fn(self._ctx, n, L.ptr(allh, ctypes.c_int32), L.ptr(off, ctypes.c_int64),
-                   L.ptr(fl if n else np.zeros(1, np.uint32), ctypes.c_uint32), L.ptr(st, ctypes.c_int64), L.ptr(hf, ctypes.c_uint8)))
-        return st[:n], [hf[off[t]:off[t + 1]] for t in range(n)]
+        return self._clean_lists(self._wide_entry("vapor_clean_hits_wide"), lists, flags)
 
     def close(self) -> None:
         if self._ctx:

@@ -240,22 +240,22 @@ _FLAGS = {"s1": L.PF_C1, "s2": L.PF_C2, "s3": L.PF_C1 | L.PF_DIR}
 _KIND = {"del": 0, "s1": 1, "s2": 2, "s3": 3}
 
 
-def has_wide(engine) -> bool:
-    """Whether `engine` has the wide route (sequences longer than MAX_SEQ_LEN, up to MAX_WIDE_SEQ_LEN): a score_wide method, and
-    - for an engine that can say so (Engine.wide_available) - a library that has the route."""
-    if not callable(getattr(engine, "score_wide", None)):
+def _has_route(engine, route: str) -> bool:
+    """A score_<route> method, and - for an engine that can say so (Engine.<route>_available) - a library that has the route."""
+    if not callable(getattr(engine, "score_" + route, None)):
         return False
-    avail = getattr(engine, "wide_available", None)
+    avail = getattr(engine, route + "_available", None)
     return bool(avail()) if callable(avail) else True
+
+
+def has_wide(engine) -> bool:
+    """Whether `engine` has the wide route (sequences longer than MAX_SEQ_LEN, up to MAX_WIDE_SEQ_LEN)."""
+    return _has_route(engine, "wide")
 
 
 def has_anyk(engine) -> bool:
-    """Whether `engine` has the any-k route (window sizes 1 .. MAX_ANY_K, the reference's kmerhits at every k): a score_anyk
-    method, and - for an engine that can say so (Engine.anyk_available) - a library that has the route."""
-    if not callable(getattr(engine, "score_anyk", None)):
-        return False
-    avail = getattr(engine, "anyk_available", None)
-    return bool(avail()) if callable(avail) else True
+    """Whether `engine` has the any-k route (window sizes 1 .. MAX_ANY_K, the reference's kmerhits at every k)."""
+    return _has_route(engine, "anyk")
 
 
 def check_any_k(k) -> int:
