@@ -359,6 +359,17 @@ int vapor_bam_chop(vapor_bam* bam, int32_t tid, int64_t start, int64_t end, int6
                    const uint64_t* chunks, uint8_t* seq_out, int64_t seq_cap, char* names_out, int64_t names_cap,
                    int64_t* meta, int32_t max_reads, int32_t* n_reads, int64_t* need);
 /*
+ * The same with the haplotype tags of a haplotagged BAM (`--phased`; not in the reference, which reads nothing behind SEQ,
+ * SF:339-354): six numbers per read in `meta` - read r is seq_out[meta[6r] .. + meta[6r+1]), meta[6r+2] = miss_bp, its name at
+ * names_out + meta[6r+3], meta[6r+4] = hap, meta[6r+5] = ps.  hap = the value of the record's first HP aux field of integer
+ * type (c C s S i I) if that is 1 or 2, else 0; ps = the value of its first PS aux field of integer type (I values up to
+ * 2^32 - 1 exactly), INT64_MIN without one.  The aux walk ends at the first malformed field; what it found before stands.
+ * minimize_pacbio_read_list (SF:1091-1102) is applied per group by the caller (vapor_amd/phase.py select).
+ */
+int vapor_bam_chop_tagged(vapor_bam* bam, int32_t tid, int64_t start, int64_t end, int64_t flank, int32_t n_chunks,
+                          const uint64_t* chunks, uint8_t* seq_out, int64_t seq_cap, char* names_out, int64_t names_cap,
+                          int64_t* meta, int32_t max_reads, int32_t* n_reads, int64_t* need);
+/*
  * The read extraction of MANY regions on the DEVICE (vapor_amd/csrc/vapor_bamdev.h): what vapor_bam_chop does for one region on
  * host threads - and the reference as a `samtools view` process per locus piped into chop_pacbio_read_by_pos (SF:339-354) and
  * minimize_pacbio_read_list (SF:1091-1102) - for n_regions regions of the open file `bam` in one call.  Region g =
@@ -381,8 +392,27 @@ int vapor_bam_chop_device(vapor_ctx* ctx, vapor_bam* bam, int32_t n_regions, con
                           int32_t max_keep, int32_t* kept_first, uint64_t* sq_addr, int64_t* q0, int64_t* miss, int32_t* status,
                           vapor_bam_batch** batch);
 int vapor_bam_batch_destroy(vapor_bam_batch* batch);
-/* what the context's last vapor_bam_chop_device did, for measurement (bench.py): out[0..5] = regions, BGZF blocks, compressed bytes
- * sent over the link, inflated bytes, the inflate kernel's duration between two events on its stream (ms), the whole call (ms) */
+/*
+ * vapor_bam_chop_device for a haplotagged file (`--phased`; not in the reference, whose chop_pacbio_read_by_pos, SF:339-354,
+ * reads nothing behind SEQ, and whose minimize_pacbio_read_list, SF:1091-1102, is applied here per group).  The chop kernel also
+ * walks the aux fields of every record it keeps, once, for hap and ps (vapor_bam_chop_tagged has the rule; a CG:B,I array is
+ * found in the same walk); a second kernel, one wavefront a region, then makes the region's answer on the device: P = the ps
+ * most frequent among the kept records with hap != 0 (ties to the smallest value, "none" below every number); group A = all
+ * kept records, H1 / H2 = those with hap == 1 / 2 and ps == P; a group's list = at most max_keep of it, record order when the
+ * group has no more, else the smallest miss_bp first, record order inside one value.  What comes back is the union of the three
+ * lists in record order: entries kept_first[g] .. kept_first[g + 1] of sq_addr, q0 and miss (as above) and `member` - bits 0-2:
+ * the read is in the list of A / H1 / H2; bits 8-15, 16-23, 24-31: its position in that list.  The four arrays have room for
+ * 3 * max_keep entries per region.  phase_set[g] = P (INT64_MIN: none), tagged[g] = 1 when a kept record has hap != 0.  status[g]
+ * as above; a record whose aux area is malformed leaves its region to the host route.  A library without a device (the CPU
+ * twin of the tests) does not have this entry: the caller's host readers select the groups.
+ */
+int vapor_bam_chop_device_tagged(vapor_ctx* ctx, vapor_bam* bam, int32_t n_regions, const int32_t* tid, const int64_t* start,
+                                 const int64_t* end, const int64_t* flank, const int32_t* chunk_first, const uint64_t* chunks,
+                                 int32_t max_keep, int32_t* kept_first, uint64_t* sq_addr, int64_t* q0, int64_t* miss,
+                                 uint32_t* member, int64_t* phase_set, int32_t* tagged, int32_t* status, vapor_bam_batch** batch);
+/* what the context's last vapor_bam_chop_device (or _tagged) did, for measurement (bench.py): out[0..6] = regions, BGZF blocks,
+ * compressed bytes sent over the link, inflated bytes, the inflate kernel's duration between two events on its stream (ms), the
+ * whole call (ms), bytes of kept reads and statuses copied back from the device */
 int vapor_bam_last_stats(vapor_ctx* ctx, double* out, int32_t n);
 /* the descriptor and the inflate-thread count of an open file (vapor_bam_chop_device reads with them) */
 int vapor_bam_fileno(vapor_bam* bam);

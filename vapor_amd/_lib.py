@@ -54,11 +54,12 @@ EXPORTS = [
     "vapor_bam_chop_device", "vapor_bam_batch_destroy", "vapor_bam_fileno", "vapor_bam_threads", "vapor_seqset_create_mixed", "vapor_bam_last_stats",
     "vapor_wide_batch", "vapor_clean_hits_wide", "vapor_fasta_windows_device", "vapor_fasta_last_stats", "vapor_anyk_batch",
     "vapor_plan_set_grid", "vapor_plan_run_grid", "vapor_grid_pick",
+    "vapor_bam_chop_tagged", "vapor_bam_chop_device_tagged",
 ]
 # entry points a library may lack (the CPU twin of the C ABI has no wide or any-k route and no refinement kernel): bound when
 # present, and the engine's wide, any-k and grid methods raise NotImplementedError when they are not
 OPTIONAL_EXPORTS = ("vapor_wide_batch", "vapor_clean_hits_wide", "vapor_anyk_batch", "vapor_plan_set_grid", "vapor_plan_run_grid",
-                    "vapor_grid_pick")
+                    "vapor_grid_pick", "vapor_bam_chop_device_tagged")
 MAX_CANDIDATES = 128           # breakpoint refinement: candidates per locus (VAPOR_MAX_CANDIDATES)
 
 _lib = None
@@ -184,6 +185,7 @@ def bind(L: ctypes.CDLL) -> ctypes.CDLL:
     L.vapor_bam_last_error.restype = ctypes.c_char_p
     L.vapor_bam_chop.argtypes = [vp, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, vp,
                                  vp, ctypes.c_int64, vp, ctypes.c_int64, vp, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), vp]
+    L.vapor_bam_chop_tagged.argtypes = L.vapor_bam_chop.argtypes
     L.vapor_bam_chop_device.argtypes = [vp, vp, ctypes.c_int32, vp, vp, vp, vp, vp, vp, ctypes.c_int32, vp, vp, vp, vp, vp, ctypes.POINTER(vp)]
     L.vapor_bam_batch_destroy.argtypes = [vp]
     L.vapor_bam_last_stats.argtypes = [vp, vp, ctypes.c_int32]
@@ -216,6 +218,9 @@ def bind(L: ctypes.CDLL) -> ctypes.CDLL:
         L.vapor_plan_set_grid.argtypes = [vp, ctypes.c_int64, i32p]
     if hasattr(L, "vapor_grid_pick"):
         L.vapor_grid_pick.argtypes = [vp, ctypes.c_int64, i32p, f64p, i32p, f64p, i32p, f64p, f64p, i64p]
+    if hasattr(L, "vapor_bam_chop_device_tagged"):
+        L.vapor_bam_chop_device_tagged.argtypes = [vp, vp, ctypes.c_int32, vp, vp, vp, vp, vp, vp, ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                   ctypes.POINTER(vp)]
     if hasattr(L, "vapor_plan_run_grid"):
         L.vapor_plan_run_grid.argtypes = [vp, i32p, f64p, f64p, i64p]
     for name in EXPORTS:

@@ -261,12 +261,14 @@ class BamFile:
             real = cls._aux_cigar(rec, p + nb + l_seq)      # placeholder <l_seq>S<ref len>N: the operations are in CG
             if real is not None:
                 cig = real
-        return ref_id, pos, name, flag, cig, l_seq, sq
+        from . import phase
+        return ref_id, pos, name, flag, cig, l_seq, sq, phase.tags_from_aux(rec, p + nb + l_seq)
 
-    def chop_native(self, chrom: str, start: int, end: int, flank_length: int):
+    def chop_native(self, chrom: str, start: int, end: int, flank_length: int, tagged: bool = False):
         """chop_pacbio_read_by_pos (SF:339-354) for one region through the library's native reader (vapor_bam_chop:
         threaded inflate, binary CIGAR walk, only kept bases decoded); the .bai lookup stays here.  Returns the same
-        [[read tail, miss_bp, qname], ...] as the Python statement of it (seqio.InProcessBam.chop_python)."""
+        [[read tail, miss_bp, qname], ...] as the Python statement of it (seqio.InProcessBam.chop_python); with `tagged`
+        (vapor_bam_chop_tagged) every entry also carries the record's hap and ps."""
         import ctypes
         from . import _lib
         lib = _lib.load()
@@ -278,14 +280,15 @@ class BamFile:
             return []
         tl = self._take_handle(lib)
         try:
-            return self._chop_with(lib, tl, tid, ch, start, end, flank_length)
+            return self._chop_with(lib, tl, tid, ch, start, end, flank_length, tagged=tagged)
         finally:
             with self._lock:
                 self._free.append(tl)
 
-    def chop_native_raw(self, chrom: str, start: int, end: int, flank_length: int):
+    def chop_native_raw(self, chrom: str, start: int, end: int, flank_length: int, tagged: bool = False):
         """chop_native's answer as numbers: (text, offsets, lengths, miss_bp) - read r is text[offsets[r] : offsets[r] + lengths[r]]
-        - for callers that hand the reads on by address (vapor_amd.fastpath) instead of making a string per read."""
+        - for callers that hand the reads on by address (vapor_amd.fastpath) instead of making a string per read; with `tagged`
+        also hap and ps per read (ps: phase.PS_NONE for none)."""
         from . import _lib
         lib = _lib.load()
         tid = self.tid.get(chrom)
@@ -296,7 +299,7 @@ class BamFile:
             return None
         tl = self._take_handle(lib)
         try:
-            return self._chop_with(lib, tl, tid, ch, start, end, flank_length, raw=True)
+            return self._chop_with(lib, tl, tid, ch, start, end, flank_length, raw=True, tagged=tagged)
         finally:
             with self._lock:
                 self._free.append(tl)
@@ -321,16 +324,17 @@ class BamFile:
             self._handles.append(h)
         return tl
 
-    def _chop_with(self, lib, tl, tid, ch, start, end, flank_length, raw=False):
+    def _chop_with(self, lib, tl, tid, ch, start, end, flank_length, raw=False, tagged=False):
         import ctypes
         from . import _lib
         chunks = np.asarray(ch, dtype=np.uint64).reshape(-1)
         n = ctypes.c_int32(0)
+        fn, w = (lib.vapor_bam_chop_tagged, 6) if tagged else (lib.vapor_bam_chop, 4)      # (numbers per read in `meta`)
         while True:
             bf = tl["buf"]
-            rc = lib.vapor_bam_chop(tl["native"], tid, int(start), int(end), int(flank_length), len(ch), chunks.ctypes.data,
-                                    bf["seq"].ctypes.data, bf["seq"].size, ctypes.cast(bf["names"], ctypes.c_void_p), len(bf["names"]),
-                                    bf["meta"].ctypes.data, bf["meta"].size // 4, ctypes.byref(n), bf["need"].ctypes.data)
+            rc = fn(tl["native"], tid, int(start), int(end), int(flank_length), len(ch), chunks.ctypes.data,
+                    bf["seq"].ctypes.data, bf["seq"].size, ctypes.cast(bf["names"], ctypes.c_void_p), len(bf["names"]),
+                    bf["meta"].ctypes.data, bf["meta"].size // w, ctypes.byref(n), bf["need"].ctypes.data)
             if rc == 0:
                 break
             if rc != _lib.E_OVERFLOW:
@@ -345,17 +349,20 @@ class BamFile:
         if n.value == 0:
             return None if raw else []
         if raw:
-            meta = bf["meta"][:4 * n.value].reshape(-1, 4).copy()
+            meta = bf["meta"][:w * n.value].reshape(-1, w).copy()
             whole = bf["seq"][:int((meta[:, 0] + meta[:, 1]).max())].tobytes().decode("ascii")
-            return whole, meta[:, 0], meta[:, 1], meta[:, 2]
+            return (whole, meta[:, 0], meta[:, 1], meta[:, 2]) + ((meta[:, 4], meta[:, 5]) if tagged else ())
         # (one conversion of the numbers, one of the bases: this runs under the interpreter lock on every pool thread)
-        m = bf["meta"][:4 * n.value].tolist()
-        whole = bf["seq"][:max(m[4 * r] + m[4 * r + 1] for r in range(n.value))].tobytes().decode("ascii")
+        m = bf["meta"][:w * n.value].tolist()
+        whole = bf["seq"][:max(m[w * r] + m[w * r + 1] for r in range(n.value))].tobytes().decode("ascii")
         names = bf["names"].raw
         out = []
         for r in range(n.value):
-            o, ln, miss, no = m[4 * r:4 * r + 4]
+            o, ln, miss, no = m[w * r:w * r + 4]
             out.append([whole[o:o + ln], miss, names[no:names.index(b"\0", no)].decode()])
+            if tagged:
+                from .phase import PS_NONE
+                out[-1] += [m[w * r + 4], None if m[w * r + 5] == PS_NONE else m[w * r + 5]]
         return out
 
     def close(self) -> None:
@@ -373,8 +380,9 @@ class BamFile:
             pass
 
     def fetch_raw(self, chrom: str, start: int, end: int):
-        """(QNAME, 1-based POS, CIGAR operations as a uint32 tuple, packed SEQ bytes, l_seq, FLAG) of the alignments
-        that overlap the 1-based inclusive region, in file order; nothing is decoded to text."""
+        """(QNAME, 1-based POS, CIGAR operations as a uint32 tuple, packed SEQ bytes, l_seq, FLAG, (hap, ps)) of the alignments
+        that overlap the 1-based inclusive region, in file order; nothing is decoded to text.  (hap, ps): the record's
+        haplotype and phase set (phase.tags_from_aux)."""
         tid = self.tid.get(chrom)
         if tid is None:
             return []
@@ -387,7 +395,7 @@ class BamFile:
                 if len(hdr) < 4:
                     break
                 rec = cur.read(struct.unpack("<i", hdr)[0])
-                ref_id, pos, name, flag, cig, l_seq, sq = self._parse(rec)
+                ref_id, pos, name, flag, cig, l_seq, sq, tags = self._parse(rec)
                 if ref_id != tid or pos >= stop:
                     if ref_id > tid or (ref_id == tid and pos >= stop):
                         break
@@ -395,13 +403,13 @@ class BamFile:
                 rlen = int(((cig >> 4) * _REF_OP[cig & 15]).sum()) if len(cig) else 0     # M, D, N, =, X consume reference
                 if pos + max(rlen, 1) <= beg:
                     continue
-                out.append((name, pos + 1, cig, sq, l_seq, flag))
+                out.append((name, pos + 1, cig, sq, l_seq, flag, tags))
         return out
 
     def fetch_records(self, chrom: str, start: int, end: int) -> List[Tuple[str, int, str, str, int]]:
         """(QNAME, 1-based POS, CIGAR, SEQ, FLAG) as text fields - what `samtools view bam chrom:start-end` lists."""
         return [(name, pos, "".join("%d%s" % (c >> 4, _CIG[c & 15]) for c in cig.tolist()) or "*", _decode_seq(sq, l_seq) or "*", flag)
-                for name, pos, cig, sq, l_seq, flag in self.fetch_raw(chrom, start, end)]
+                for name, pos, cig, sq, l_seq, flag, _tags in self.fetch_raw(chrom, start, end)]
 
     def fetch_lines(self, chrom: str, start: int, end: int) -> List[str]:
         """The same as SAM-ordered text lines (QNAME FLAG RNAME POS MAPQ CIGAR * 0 0 SEQ *)."""
@@ -425,8 +433,9 @@ _BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000
 
 def write_bam(path: str, refs: List[Tuple[str, int]], records: List[Tuple[str, int, int, str, str]],
               block_size: int = 16384, qual_seed=None) -> None:
-    """records: (qname, tid, pos0, cigar string, seq), will be sorted by (tid, pos).  Writes path and
-    path + '.bai'.  Qualities are 0xFF ("absent") - or, with qual_seed, seeded values in runs of a few bases between 2 and 60,
+    """records: (qname, tid, pos0, cigar string, seq[, aux]), will be sorted by (tid, pos).  Writes path and
+    path + '.bai'.  aux: the record's optional fields as raw bytes, or a tag dict (phase.encode_aux); they follow the CG array
+    of a long-CIGAR record.  Qualities are 0xFF ("absent") - or, with qual_seed, seeded values in runs of a few bases between 2 and 60,
     which is what makes the blocks of a sequencer's file literal-heavy for its DEFLATE decoder."""
     import re
     import numpy as np
@@ -441,7 +450,12 @@ def write_bam(path: str, refs: List[Tuple[str, int]], records: List[Tuple[str, i
     blobs = []
     meta = []
     qrng = np.random.default_rng(qual_seed) if qual_seed is not None else None
-    for qname, tid, pos, cigar, seq in recs:
+    for rec in recs:
+        qname, tid, pos, cigar, seq = rec[:5]
+        more = rec[5] if len(rec) > 5 and rec[5] else b""
+        if isinstance(more, dict):
+            from .phase import encode_aux
+            more = encode_aux(more)
         ops = [(int(n), _CIG.index(o)) for n, o in re.findall(r"(\d+)([MIDNSHP=X])", cigar)]
         rlen = sum(n for n, o in ops if o in (0, 2, 3, 7, 8))
         end = pos + max(rlen, 1)
@@ -461,7 +475,7 @@ def write_bam(path: str, refs: List[Tuple[str, int]], records: List[Tuple[str, i
         else:
             runs = qrng.integers(1, 6, size=len(seq) // 2 + 1)
             qual = np.repeat(qrng.integers(2, 61, size=len(runs)).astype(np.uint8), runs)[:len(seq)].tobytes()
-        body += qname.encode() + b"\x00" + b"".join(struct.pack("<I", c) for c in packed) + bytes(sq) + qual + aux
+        body += qname.encode() + b"\x00" + b"".join(struct.pack("<I", c) for c in packed) + bytes(sq) + qual + aux + bytes(more)
         blobs.append(struct.pack("<i", len(body)) + body)
         meta.append((tid, pos, end))
     # lay the stream out in BGZF blocks, remembering the virtual offset of every record

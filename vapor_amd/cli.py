@@ -8,7 +8,10 @@ the node and the per-locus rows are all-gathered (vapor_amd.dist).
 
 Extra flags (not in the reference): --no-figures (skip the recurrence-plot PNGs),
 --chunk (loci per device batch), --bnd (vcf: score breakend records as well), --refine M[:T] (bed, vcf: score a
-grid of candidate breakpoints within M bp of every short DEL / INV / TANDUP call and report the best).
+grid of candidate breakpoints within M bp of every short DEL / INV / TANDUP call and report the best),
+--phased (bed, vcf: read the HP and PS tags of a haplotagged BAM and score the reads of each haplotype of a DEL / INV / TANDUP /
+INS call beside the pooled list; appends VaPoR_PS, VaPoR_PGT, VaPoR_PGQ and QS / GS / Rec per haplotype; not
+together with --refine).
 """
 from __future__ import annotations
 
@@ -287,7 +290,7 @@ class _BndReader:
 class Job:
     """One output row: how to score it (a driver generator factory, or fixed scores) and how to
     write it.  `cost`: what the locus is expected to take (microseconds, `job_cost`), for the shares of the ranks."""
-    __slots__ = ("key", "make", "fixed", "row_prefix", "label", "cost", "spec", "ctx", "refine")
+    __slots__ = ("key", "make", "fixed", "row_prefix", "label", "cost", "spec", "ctx", "refine", "phase")
 
     def __init__(self, key, make=None, fixed=None, row_prefix=None, label=None, cost=None, spec=None, ctx=None):
         self.key, self.make, self.fixed, self.row_prefix, self.label = key, make, fixed, row_prefix, label
@@ -295,6 +298,7 @@ class Job:
         # that a chunk of them can take the array route (vapor_amd.fastpath); `make` stays the driver's own route
         self.spec, self.ctx = spec, ctx
         self.refine = None             # after scoring under --refine: refine.Refined.info of a locus that was refined
+        self.phase = None              # after scoring under --phased: phase.Phased.phase of a locus that was phased
         self.cost = cost if cost is not None else (COST_FIXED_US if make is None else COST_HOST_US)
 
 
@@ -346,12 +350,14 @@ def _refine_n(refine, s, e, ci=(None, None)) -> int:
     return len(rf.candidates(refine[0], refine[1], s, e, ci[0], ci[1]))
 
 
-def bed_jobs(bed_info, num_reads_cff, bam_in, ref, out_path, sample_name, refine=None) -> List[Job]:
+def bed_jobs(bed_info, num_reads_cff, bam_in, ref, out_path, sample_name, refine=None, phased=False) -> List[Job]:
     """The loop of vapor_vali/vapor:334-367.  `refine` = (M, T) of `--refine`: DEL, INV and TANDUP loci take
-    drivers.vapor_refine (which leaves a locus it cannot refine to the type's own driver)."""
+    drivers.vapor_refine (which leaves a locus it cannot refine to the type's own driver).  `phased` (`--phased`): the four
+    simple drivers run with phased=True (the array route takes the option from score_jobs)."""
     jobs = []
     plt_li = 0
     ctx = (num_reads_cff, bam_in, ref)
+    ph = {'phased': True} if phased else {}
     for x in bed_info:
         tag = x[-1]
         if tag in ['a/', '/a', '/', 'DEL']:
@@ -367,7 +373,7 @@ def bed_jobs(bed_info, num_reads_cff, bam_in, ref, out_path, sample_name, refine
             ins_seq = ''.join(['X' for _ in range(x[4])]) if type(x[4]) == type(4) else x[4]
             fig = out_path + sample_name + '.INS.' + key.replace(':', '__') + '.png'
             jobs.append(Job(key, (lambda p=plt_li, a=ins_pos, s=ins_seq, f=fig:
-                                  drivers.vapor_simple_ins(num_reads_cff, p, bam_in, ref, a, s, f, '+')),
+                                  drivers.vapor_simple_ins(num_reads_cff, p, bam_in, ref, a, s, f, '+', **ph)),
                             row_prefix=x[3], label=x, cost=job_cost('INS', len(ins_seq)),
                             spec=('INS', x[0], x[1], None, ins_seq), ctx=ctx))
             continue
@@ -384,7 +390,7 @@ def bed_jobs(bed_info, num_reads_cff, bam_in, ref, out_path, sample_name, refine
                                   drivers.vapor_refine(n, num_reads_cff, p, bam_in, ref, info, g, refine[0], refine[1])),
                             row_prefix=x[3], label=x, cost=job_cost(name, x[2] - x[1], candidates=_refine_n(refine, x[1], x[2]))))
             continue
-        jobs.append(Job(key, (lambda p=plt_li, f=fn, info=x[:-3], g=fig: f(num_reads_cff, p, bam_in, ref, info, g)),
+        jobs.append(Job(key, (lambda p=plt_li, f=fn, info=x[:-3], g=fig: f(num_reads_cff, p, bam_in, ref, info, g, **ph)),
                         row_prefix=x[3], label=x, cost=job_cost(name, x[2] - x[1]), spec=(name, x[0], x[1], x[2], None), ctx=ctx))
     return jobs
 
@@ -415,13 +421,15 @@ def vcf_ci_readin(file_in) -> dict:
     return out
 
 
-def vcf_jobs(vcf_list, num_reads_cff, bam_in, ref, out_path, sample_name, refine=None, ci_of=None) -> List[Job]:
+def vcf_jobs(vcf_list, num_reads_cff, bam_in, ref, out_path, sample_name, refine=None, ci_of=None, phased=False) -> List[Job]:
     """The loop of vapor_vali/vapor:387-465 (TANDUP is bucketed but never scored there either), and the breakends of
     `vapor vcf --bnd` (vcf_list_readin's last bucket: drivers.vapor_bnd).  `refine` = (M, T) of `--refine` and `ci_of`
-    (vcf_ci_readin): DEL and INV records take drivers.vapor_refine, within their CIPOS / CIEND."""
+    (vcf_ci_readin): DEL and INV records take drivers.vapor_refine, within their CIPOS / CIEND.  `phased`: as in bed_jobs, for
+    the DEL, INV and INS records."""
     jobs = []
     plt_li = 0
     ctx = (num_reads_cff, bam_in, ref)
+    ph = {'phased': True} if phased else {}
     for x in list(vcf_list.keys()):
         if x not in ('DEL', 'INV', 'INS', 'DISDUP', 'DEL_INV', 'DUP_INV', 'Other', 'BND'):
             print(x)
@@ -449,7 +457,7 @@ def vcf_jobs(vcf_list, num_reads_cff, bam_in, ref, out_path, sample_name, refine
                                           drivers.vapor_refine(n, num_reads_cff, p, bam_in, ref, info, g, refine[0], refine[1], c[0], c[1])),
                                     cost=job_cost(x, y[2] - y[1], candidates=_refine_n(refine, y[1], y[2], ci))))
                     continue
-                jobs.append(Job(key, (lambda p=plt_li, f=fn, info=y, g=fig: f(num_reads_cff, p, bam_in, ref, info, g)),
+                jobs.append(Job(key, (lambda p=plt_li, f=fn, info=y, g=fig: f(num_reads_cff, p, bam_in, ref, info, g, **ph)),
                                 cost=job_cost(x, y[2] - y[1]), spec=(x, y[0], y[1], y[2], None), ctx=ctx))
             elif x == 'INS':
                 key = ':'.join([str(i) for i in y[:3] + ['INS']])
@@ -457,7 +465,7 @@ def vcf_jobs(vcf_list, num_reads_cff, bam_in, ref, out_path, sample_name, refine
                 ins_seq = y[-1] if len(y) == 4 else ''.join(['X' for _ in range(y[2])])
                 fig = out_path + sample_name + '.INS.' + key.replace(':', '__') + '.png'
                 jobs.append(Job(key, (lambda p=plt_li, a=ins_pos, s=ins_seq, g=fig:
-                                      drivers.vapor_simple_ins(num_reads_cff, p, bam_in, ref, a, s, g, '+')),
+                                      drivers.vapor_simple_ins(num_reads_cff, p, bam_in, ref, a, s, g, '+', **ph)),
                                 cost=job_cost('INS', len(ins_seq)), spec=('INS', y[0], y[1], None, ins_seq), ctx=ctx))
             elif x == 'DISDUP':
                 key = ':'.join([str(i) for i in y + ['DISDUP']])
@@ -574,10 +582,11 @@ def output_rows(heads: list, scores_list: list) -> tuple:
     return lines, tails
 
 
-def score_jobs(jobs: List[Job], chunk: int, figure_fn=None, refine=None) -> List[object]:
+def score_jobs(jobs: List[Job], chunk: int, figure_fn=None, refine=None, phased=False) -> List[object]:
     """Score every job (sharded over ranks, batched on each GPU); returns per job the list of read
     scores, in job order, identical on every rank.  With `refine` (`--refine`) every job's `refine` attribute is set as
-    well, on every rank: refine.Refined.info of a locus that was refined, None otherwise."""
+    well, on every rank: refine.Refined.info of a locus that was refined, None otherwise; with `phased` (`--phased`) every
+    job's `phase` attribute likewise: phase.Phased.phase of a locus that was phased."""
     import gc
     import time
     t0 = time.perf_counter()
@@ -589,6 +598,8 @@ def score_jobs(jobs: List[Job], chunk: int, figure_fn=None, refine=None) -> List
     gc_was = gc.get_threshold()
     gc.set_threshold(max(gc_was[0], 200000), max(gc_was[1], 50), max(gc_was[2], 1000))
     try:
+        if phased:
+            return _score_jobs(jobs, chunk, figure_fn, t0, phased=True)
         return _score_jobs(jobs, chunk, figure_fn, t0) if refine is None else _score_jobs(jobs, chunk, figure_fn, t0, refine)
     finally:
         gc.set_threshold(*gc_was)
@@ -608,7 +619,7 @@ def _chunk_threads_ok() -> bool:
 last_timing: dict = {}          # of the most recent score_jobs: seconds scoring this rank's share, seconds in the gather
 
 
-def _score_jobs(jobs, chunk, figure_fn, t0, refine=None):
+def _score_jobs(jobs, chunk, figure_fn, t0, refine=None, phased=False):
     import time
     # shares by estimated cost (greedy longest-processing-time), the same list on every rank
     costs = [float(j.cost) for j in jobs]
@@ -632,7 +643,7 @@ def _score_jobs(jobs, chunk, figure_fn, t0, refine=None):
             for ctx, ts in by_ctx.items():
                 eng = engine or pipeline.get_engine()
                 if len(ts) >= 8 and fastpath.capable(seqio.get_backend(), ctx[1], eng):
-                    got = fastpath.run(eng, [jobs[t].spec for t in ts], ctx[1], ctx[2], ctx[0])
+                    got = fastpath.run(eng, [jobs[t].spec for t in ts], ctx[1], ctx[2], ctx[0], **({"phased": True} if phased else {}))
                     for t, r in zip(ts, got):
                         if r is not fastpath.FALLBACK:
                             done[t] = r
@@ -698,6 +709,13 @@ def _score_jobs(jobs, chunk, figure_fn, t0, refine=None):
                  for t, r in local.items()}
         for j, info in zip(jobs, vdist.gather_results(extra, len(jobs), costs)):
             j.refine = info if info else None
+    if phased:
+        # (the nine extra columns travel the same way: phase.pack's floats for a phased locus, none otherwise)
+        from . import phase as ph
+        extra = {t: (ph.pack(getattr(r, "phase", None)) if not isinstance(r, BaseException) and r is not None else [])
+                 for t, r in local.items()}
+        for j, v in zip(jobs, vdist.gather_results(extra, len(jobs), costs)):
+            j.phase = ph.unpack(v)
     allres = vdist.gather_results(local, len(jobs), costs)
     last_timing.update(score_s=t1 - t0, gather_s=time.perf_counter() - t1, loci=len(mine), cost=sum(costs[t] for t in mine))
     if os.environ.get("VAPOR_TIMING") and vdist.rank() == 0:
@@ -727,6 +745,10 @@ def build_parser() -> argparse.ArgumentParser:
                    help='bed, vcf: score candidate breakpoints within M bp of every short DEL / INV / TANDUP call, in steps of T bp '
                         '(default: the smallest step that keeps a locus within 128 candidates), and report the best; appends '
                         'VaPoR_RPOS, VaPoR_REND, VaPoR_QS0 and VaPoR_GS0 (vcf: to INFO, within CIPOS / CIEND)')
+    p.add_argument('--phased', action='store_true',
+                   help='bed, vcf: read the HP and PS tags of a haplotagged BAM; every DEL / INV / TANDUP / INS call is scored per '
+                        'haplotype as well (the reads with HP 1, with HP 2, of the majority phase set): appends VaPoR_PS, VaPoR_PGT, '
+                        'VaPoR_PGQ and VaPoR_H1_QS / _GS / _Rec, VaPoR_H2_QS / _GS / _Rec (vcf: to INFO); not together with --refine')
     return p
 
 
@@ -753,6 +775,13 @@ def main(argv: Optional[List[str]] = None) -> int:
             refine = rf.parse(args.refine)
         except ValueError as e:
             parser.error(str(e))
+    if args.phased:
+        if mode not in ('bed', 'vcf'):
+            parser.error('--phased applies to `vapor bed` and `vapor vcf`')
+        if refine is not None:
+            parser.error('--phased and --refine cannot be combined (refinement per haplotype is not implemented)')
+        from . import phase as ph
+    more = rf.COLUMNS if refine is not None else ph.COLUMNS if args.phased else ()
     figure_fn = None
     if not args.no_figures:
         from . import figures
@@ -765,15 +794,17 @@ def main(argv: Optional[List[str]] = None) -> int:
     bam_in, ref = args.pacbio_input, args.reference
     if mode == 'bed':
         bed_info = bed_info_readin(args.sv_input, out_path)
-        jobs = bed_jobs(bed_info, num_reads_cff, bam_in, ref, out_path, sample_name, refine)
-        scores = score_jobs(jobs, args.chunk, figure_fn, refine)
+        jobs = bed_jobs(bed_info, num_reads_cff, bam_in, ref, out_path, sample_name, refine, args.phased)
+        scores = score_jobs(jobs, args.chunk, figure_fn, refine, args.phased)
         if vdist.rank() == 0:
-            SF.write_output_initiate(args.output_file, rf.COLUMNS if refine is not None else ())
+            SF.write_output_initiate(args.output_file, more)
             with open(args.output_file, 'a') as fo:
                 # (result_organize_ins + write_output_main of vapor_vali/vapor:356-357 in one go: finish.row_tails)
                 lines, tails = output_rows([j.key.split(':') + [j.row_prefix] for j in jobs], scores)
                 if refine is not None:
                     lines = [l + '\t' + '\t'.join(rf.columns(j.refine)) for l, j in zip(lines, jobs)]
+                if args.phased:
+                    lines = [l + '\t' + '\t'.join(c) for l, c in zip(lines, ph.columns_many([j.phase for j in jobs]))]
                 fo.write(''.join([l + '\n' for l in lines]))
                 for j, tail in zip(jobs, tails):
                     print([j.key, tail[0], tail[1], tail[4]])
@@ -781,17 +812,21 @@ def main(argv: Optional[List[str]] = None) -> int:
         vcf_list, rec_hash = vcf_list_readin(args.sv_input, ref if args.bnd else None)
         rec_new = SF.vcf_rec_hash_modify(rec_hash)
         jobs = vcf_jobs(vcf_list, num_reads_cff, bam_in, ref, out_path, sample_name, refine,
-                        vcf_ci_readin(args.sv_input) if refine is not None else None)
-        scores = score_jobs(jobs, args.chunk, figure_fn, refine)
+                        vcf_ci_readin(args.sv_input) if refine is not None else None, args.phased)
+        scores = score_jobs(jobs, args.chunk, figure_fn, refine, args.phased)
         if vdist.rank() == 0:
-            SF.write_output_initiate(args.sv_input + '.vapor', rf.COLUMNS if refine is not None else ())
+            SF.write_output_initiate(args.sv_input + '.vapor', more)
             with open(args.sv_input + '.vapor', 'a') as fo:
                 lines = output_rows([[j.key] for j in jobs], scores)[0]
                 if refine is not None:
                     lines = [l + '\t' + '\t'.join(rf.columns(j.refine)) for l, j in zip(lines, jobs)]
+                if args.phased:
+                    lines = [l + '\t' + '\t'.join(c) for l, c in zip(lines, ph.columns_many([j.phase for j in jobs]))]
                 fo.write(''.join([l + '\n' for l in lines]))
             if refine is not None:
                 SF.vcf_vapor_modify(args.sv_input, rec_new, refined=True)
+            elif args.phased:
+                SF.vcf_vapor_modify(args.sv_input, rec_new, phased=True)
             else:
                 SF.vcf_vapor_modify(args.sv_input, rec_new)
     elif mode == 'svelter':

@@ -262,11 +262,72 @@ static const uint8_t* find_cg(const uint8_t* p, const uint8_t* end, int32_t* cou
     return nullptr;
 }
 
+// The haplotype and phase set of a record's aux fields (`--phased`; vapor_amd/phase.py tags_from_aux is the same
+// walk in Python): *hap = the value of the first HP field of integer type (c C s S i I) if it is 1 or 2, else 0; *ps = the value
+// of the first PS field of integer type, VAPOR_PS_NONE without one.  find_cg's walk; it ends where both are found, at the end
+// of the record, or at the first malformed field - what was found before that point stands.
+static const int64_t VAPOR_PS_NONE = INT64_MIN;
+static void find_tags(const uint8_t* p, const uint8_t* end, int64_t* hap, int64_t* ps)
+{
+    bool have_hp = false, have_ps = false;
+    int64_t hp = 0;
+    *ps = VAPOR_PS_NONE;
+    while (p + 3 <= end && !(have_hp && have_ps)) {
+        const uint8_t t0 = p[0], t1 = p[1], ty = p[2];
+        p += 3;
+        int sz = 0;
+        bool is_int = true;
+        switch (ty) {
+        case 'A': is_int = false; sz = 1; break;
+        case 'c': case 'C': sz = 1; break;
+        case 's': case 'S': sz = 2; break;
+        case 'f': is_int = false; sz = 4; break;
+        case 'i': case 'I': sz = 4; break;
+        case 'Z': case 'H': {
+            const void* nul = memchr(p, 0, (size_t)(end - p));
+            if (!nul) goto done;
+            p = (const uint8_t*)nul + 1;
+            continue;
+        }
+        case 'B': {
+            if (p + 5 > end) goto done;
+            const uint8_t sub = p[0];
+            const int32_t cnt = rd32(p + 1);
+            p += 5;
+            const int es = (sub == 'c' || sub == 'C') ? 1 : (sub == 's' || sub == 'S') ? 2 : 4;
+            if (cnt < 0 || (int64_t)cnt * es > (int64_t)(end - p)) goto done;
+            p += (size_t)cnt * (size_t)es;
+            continue;
+        }
+        default: goto done;
+        }
+        if (sz > end - p) goto done;
+        if (is_int) {
+            const bool is_hp = t0 == 'H' && t1 == 'P' && !have_hp, is_ps = t0 == 'P' && t1 == 'S' && !have_ps;
+            if (is_hp || is_ps) {
+                int64_t v;
+                switch (ty) {
+                case 'c': v = (int8_t)p[0]; break;
+                case 'C': v = p[0]; break;
+                case 's': v = (int16_t)(p[0] | (p[1] << 8)); break;
+                case 'S': v = p[0] | (p[1] << 8); break;
+                case 'i': v = rd32(p); break;
+                default:  v = (uint32_t)rd32(p); break;
+                }
+                if (is_hp) { hp = v; have_hp = true; } else { *ps = v; have_ps = true; }
+            }
+        }
+        p += sz;
+    }
+done:
+    *hap = (hp == 1 || hp == 2) ? hp : 0;
+}
+
 // Every size field of the file is checked before it is used (a damaged ISIZE reached the inflaters as a
 // buffer size); a file that breaks a rule is VAPOR_E_ARG with a message, never a read or write outside `comp` / `data`.
 static int bam_chop_impl(vapor_bam* b, int32_t tid, int64_t start, int64_t end, int64_t flank, int32_t n_chunks,
                          const uint64_t* chunks, uint8_t* seq_out, int64_t seq_cap, char* names_out, int64_t names_cap,
-                         int64_t* meta, int32_t max_reads, int32_t* n_reads, int64_t* need)
+                         int64_t* meta, int32_t max_reads, int32_t* n_reads, int64_t* need, int meta_w = 4)
 {
     if (!b || !n_reads || (n_chunks && !chunks)) return bfail(VAPOR_E_ARG, "vapor_bam_chop: null argument");
     if (seq_cap < 0 || names_cap < 0 || max_reads < 0 || (max_reads && (!meta || !seq_out || !names_out)))
@@ -397,7 +458,9 @@ static int bam_chop_impl(vapor_bam* b, int32_t tid, int64_t start, int64_t end, 
             }
             memcpy(names_out + names_used, name, (size_t)nl);
             names_out[names_used + nl] = 0;
-            meta[4 * nr] = seq_used; meta[4 * nr + 1] = want_len; meta[4 * nr + 2] = miss; meta[4 * nr + 3] = names_used;
+            int64_t* m = meta + (size_t)meta_w * (size_t)nr;
+            m[0] = seq_used; m[1] = want_len; m[2] = miss; m[3] = names_used;
+            if (meta_w == 6) find_tags(sq + (l_seq + 1) / 2 + l_seq, rec_end, m + 4, m + 5);
             seq_used += want_len; names_used += nl + 1; ++nr;
         }
     }
@@ -418,6 +481,20 @@ extern "C" int vapor_bam_chop(vapor_bam* b, int32_t tid, int64_t start, int64_t 
         return bfail(VAPOR_E_NOMEM, "vapor_bam_chop: out of memory");
     } catch (const std::exception& e) {
         return bfail(VAPOR_E_ARG, std::string("vapor_bam_chop: ") + e.what());
+    }
+}
+
+// vapor_bam_chop with six numbers per read in `meta`: the four above, then the record's hap and ps (find_tags).
+extern "C" int vapor_bam_chop_tagged(vapor_bam* b, int32_t tid, int64_t start, int64_t end, int64_t flank, int32_t n_chunks,
+                                     const uint64_t* chunks, uint8_t* seq_out, int64_t seq_cap, char* names_out, int64_t names_cap,
+                                     int64_t* meta, int32_t max_reads, int32_t* n_reads, int64_t* need)
+{
+    try {
+        return bam_chop_impl(b, tid, start, end, flank, n_chunks, chunks, seq_out, seq_cap, names_out, names_cap, meta, max_reads, n_reads, need, 6);
+    } catch (const std::bad_alloc&) {
+        return bfail(VAPOR_E_NOMEM, "vapor_bam_chop_tagged: out of memory");
+    } catch (const std::exception& e) {
+        return bfail(VAPOR_E_ARG, std::string("vapor_bam_chop_tagged: ") + e.what());
     }
 }
 
@@ -710,4 +787,13 @@ extern "C" __attribute__((weak)) int vapor_grid_pick(vapor_ctx*, int64_t, const 
                                                      int32_t*, double*, double*, int64_t*)
 {
     return bfail(VAPOR_E_ARG, "vapor_grid_pick: this build has no refinement kernel");
+}
+
+// The phased read extraction on the device (vapor_bam_chop_device_tagged: the tag walk of the chop kernel, bam_select_kernel) is
+// device code in vapor_hip.hip; the CPU twin refuses it, and the caller's host readers select the groups (vapor_bam_chop_tagged).
+extern "C" __attribute__((weak)) int vapor_bam_chop_device_tagged(vapor_ctx*, vapor_bam*, int32_t, const int32_t*, const int64_t*, const int64_t*,
+                                                                  const int64_t*, const int32_t*, const uint64_t*, int32_t, int32_t*, uint64_t*,
+                                                                  int64_t*, int64_t*, uint32_t*, int64_t*, int32_t*, int32_t*, vapor_bam_batch**)
+{
+    return bfail(VAPOR_E_ARG, "vapor_bam_chop_device_tagged: this build has no device reader");
 }

@@ -898,10 +898,92 @@ __device__ __forceinline__ uint32_t find_cg_dev(const uint8_t* arena, uint32_t p
     return 0;
 }
 
-// One wavefront per region (vapor_bam.cpp bam_chop_impl is the statement this follows, line for line in its decisions).
-__global__ __launch_bounds__(64) void bam_chop_kernel(const uint8_t* __restrict__ arena, const BamRegion* __restrict__ regs,
-                                                     const BamSpan* __restrict__ spans, const int32_t* __restrict__ blk_status, int n_regs,
-                                                     BamKept* __restrict__ kept, int32_t* __restrict__ n_kept, int32_t* __restrict__ reg_status)
+// ---- haplotype tags (`--phased`) ----------------------------------------------------------------------------
+struct BamTag {           // beside a region's BamKept entry, in an array of its own: the record's phase set and haplotype
+    long long ps;         // value of the first PS field of integer type, PS_NONE without one
+    int32_t hap, pad;     // value of the first HP field of integer type if it is 1 or 2, else 0
+};
+constexpr long long PS_NONE = (long long)0x8000000000000000ull;
+struct BamPick {          // a read of a region's union of the three group lists (A, H1, H2), in record order
+    uint32_t sq_off;
+    int32_t q0, miss;
+    uint32_t member;      // bits 0-2: in the list of A / H1 / H2; bits 8-15, 16-23, 24-31: its position in that list
+};
+struct BamPhase {         // a region's answer: its phase set P, whether any kept record is tagged, the size of the union
+    long long ps;
+    int32_t tagged, n_union;
+};
+
+// One walk over a record's aux fields [p, end) for the first HP and PS fields of integer type and - WANT_CG - the CG:B,I array
+// (vapor_bam.cpp find_tags and find_cg are the statement).  Wave-uniform like find_cg_dev: every lane reads the same bytes, but
+// for a Z / H string, whose NUL is found 64 bytes a step, a byte a lane, with a ballot (methylation strings run to kilobytes).  B
+// arrays are skipped by arithmetic.  The walk ends where all it looks for is found or at the end of the record; false for a
+// malformed area (an unknown type, a field, string or array that runs past the record).
+template <bool WANT_CG>
+__device__ __forceinline__ bool walk_aux_dev(const uint8_t* arena, uint32_t p, uint32_t end, uint32_t lane, uint32_t* cg, int32_t* cg_count,
+                                             int32_t* hap, long long* ps)
+{
+    bool have_hp = false, have_ps = false, have_cg = !WANT_CG;
+    long long hp = 0;
+    *ps = PS_NONE;
+    *cg = 0;
+    bool ok = true;
+    // (every step moves p forward by three bytes at least: the loop ends)
+    while (p + 3 <= end && !(have_hp && have_ps && have_cg)) {
+        const uint8_t t0 = arena[p], t1 = arena[p + 1], ty = arena[p + 2];
+        p += 3;
+        if (ty == 'Z' || ty == 'H') {
+            bool found = false;
+            while (p < end) {
+                const uint32_t q = p + lane;
+                const unsigned long long m = __ballot(q < end && arena[q] == 0);
+                if (m) { p += (uint32_t)__ffsll((long long)m); found = true; break; }
+                p += 64u;
+            }
+            if (!found) { ok = false; break; }
+            continue;
+        }
+        if (ty == 'B') {
+            if (p + 5 > end) { ok = false; break; }
+            const uint8_t sub = arena[p];
+            const int32_t cnt = (int32_t)rd32u(arena + p + 1);
+            p += 5;
+            const int es = (sub == 'c' || sub == 'C') ? 1 : (sub == 's' || sub == 'S') ? 2 : 4;
+            if (cnt < 0 || (long long)cnt * es > (long long)(end - p)) { ok = false; break; }
+            if (WANT_CG && !have_cg && t0 == 'C' && t1 == 'G' && sub == 'I') { *cg_count = cnt; *cg = p; have_cg = true; }
+            p += (uint32_t)cnt * (uint32_t)es;
+            continue;
+        }
+        const bool one = ty == 'c' || ty == 'C', two = ty == 's' || ty == 'S', four = ty == 'i' || ty == 'I';
+        const uint32_t sz = (one || ty == 'A') ? 1u : two ? 2u : (four || ty == 'f') ? 4u : 0u;
+        if (sz == 0u || sz > end - p) { ok = false; break; }
+        if (one || two || four) {
+            const bool is_hp = t0 == 'H' && t1 == 'P' && !have_hp, is_ps = t0 == 'P' && t1 == 'S' && !have_ps;
+            if (is_hp || is_ps) {
+                uint32_t raw = arena[p];
+                if (sz >= 2u) raw |= (uint32_t)arena[p + 1] << 8;
+                if (sz == 4u) raw |= ((uint32_t)arena[p + 2] << 16) | ((uint32_t)arena[p + 3] << 24);
+                long long v = (long long)raw;
+                if (ty == 'c') v = (long long)(int8_t)raw;
+                else if (ty == 's') v = (long long)(int16_t)raw;
+                else if (ty == 'i') v = (long long)(int32_t)raw;
+                if (is_hp) { hp = v; have_hp = true; } else { *ps = v; have_ps = true; }
+            }
+        }
+        p += sz;
+    }
+    *hap = (hp == 1 || hp == 2) ? (int32_t)hp : 0;
+    return ok;
+}
+
+// One wavefront per region (vapor_bam.cpp bam_chop_impl is the statement this follows, line for line in its decisions).  TAGGED:
+// every kept record's HP and PS go to tags[] beside its BamKept entry; a record whose aux area is malformed sends the region to
+// the host route (REG_MALFORMED).  The unphased instantiation holds none of it.
+template <bool TAGGED>
+__device__ __forceinline__ void bam_chop_body(const uint8_t* __restrict__ arena, const BamRegion* __restrict__ regs,
+                                              const BamSpan* __restrict__ spans, const int32_t* __restrict__ blk_status, int n_regs,
+                                              BamKept* __restrict__ kept, int32_t* __restrict__ n_kept, int32_t* __restrict__ reg_status,
+                                              BamTag* __restrict__ tags)
 {
     const int g = (int)blockIdx.x;
     if (g >= n_regs) return;
@@ -942,12 +1024,23 @@ __global__ __launch_bounds__(64) void bam_chop_kernel(const uint8_t* __restrict_
             const uint32_t rec_end = r + (uint32_t)bs;
             uint32_t ops = cig;
             int32_t n_ops = n_cig;
+            int32_t hap = 0;
+            long long ps = PS_NONE;
+            bool have_tags = false;
             if (n_cig == 2) {
                 const uint32_t o0 = rd32u(arena + cig), o1 = rd32u(arena + cig + 4);
                 if ((o0 & 15u) == 4u && (int32_t)(o0 >> 4) == l_seq && (o1 & 15u) == 3u) {
                     int32_t cnt = 0;
-                    const uint32_t cg = find_cg_dev(arena, sq + (uint32_t)((l_seq + 1) / 2) + (uint32_t)l_seq, rec_end, &cnt);
-                    if (cg) { ops = cg; n_ops = cnt; }
+                    if constexpr (TAGGED) {
+                        // (the CG array and the tags in one walk)
+                        uint32_t cg = 0;
+                        if (!walk_aux_dev<true>(arena, sq + (uint32_t)((l_seq + 1) / 2) + (uint32_t)l_seq, rec_end, lane, &cg, &cnt, &hap, &ps)) { st = REG_MALFORMED; break; }
+                        have_tags = true;
+                        if (cg) { ops = cg; n_ops = cnt; }
+                    } else {
+                        const uint32_t cg = find_cg_dev(arena, sq + (uint32_t)((l_seq + 1) / 2) + (uint32_t)l_seq, rec_end, &cnt);
+                        if (cg) { ops = cg; n_ops = cnt; }
+                    }
                 }
             }
             // 64 operations a step: the reference length of the region rule (M D N = X) and the walk of cigar2alignstart_by_pos
@@ -994,11 +1087,127 @@ __global__ __launch_bounds__(64) void bam_chop_kernel(const uint8_t* __restrict_
             if (want_len < 0 || !(tail > want_len)) continue;
             if (l_seq <= 0) { st = REG_NO_SEQ; break; }
             if (nk >= KEPT_CAP) { st = REG_KEPT_FULL; break; }
+            if constexpr (TAGGED) {
+                if (!have_tags) {
+                    uint32_t cg = 0;
+                    int32_t cnt = 0;
+                    if (!walk_aux_dev<false>(arena, sq + (uint32_t)((l_seq + 1) / 2) + (uint32_t)l_seq, rec_end, lane, &cg, &cnt, &hap, &ps)) { st = REG_MALFORMED; break; }
+                }
+                if (lane == 0) tags[(size_t)g * KEPT_CAP + (size_t)nk] = BamTag{ps, hap, 0};
+            }
             if (lane == 0) kept[(size_t)g * KEPT_CAP + (size_t)nk] = BamKept{sq, (int32_t)q0, (int32_t)miss, l_seq};
             ++nk;
         }
     }
     if (lane == 0) { n_kept[g] = nk; reg_status[g] = st; }
+}
+
+__global__ __launch_bounds__(64) void bam_chop_kernel(const uint8_t* __restrict__ arena, const BamRegion* __restrict__ regs,
+                                                     const BamSpan* __restrict__ spans, const int32_t* __restrict__ blk_status, int n_regs,
+                                                     BamKept* __restrict__ kept, int32_t* __restrict__ n_kept, int32_t* __restrict__ reg_status)
+{
+    bam_chop_body<false>(arena, regs, spans, blk_status, n_regs, kept, n_kept, reg_status, nullptr);
+}
+
+__global__ __launch_bounds__(64) void bam_chop_tagged_kernel(const uint8_t* __restrict__ arena, const BamRegion* __restrict__ regs,
+                                                            const BamSpan* __restrict__ spans, const int32_t* __restrict__ blk_status, int n_regs,
+                                                            BamKept* __restrict__ kept, int32_t* __restrict__ n_kept, int32_t* __restrict__ reg_status,
+                                                            BamTag* __restrict__ tags)
+{
+    bam_chop_body<true>(arena, regs, spans, blk_status, n_regs, kept, n_kept, reg_status, tags);
+}
+
+// The groups of a phased region (vapor_amd/phase.py select is the statement): one wavefront a region, right after the chop
+// kernel on its stream.  From the region's up to KEPT_CAP kept entries and their tags: P = the ps value most frequent among the
+// entries with hap != 0 (ties to the smallest value, "none" below every number); the lists of A (all entries), H1 and H2 (hap ==
+// h and ps == P) under minimize_pacbio_read_list (SF:1091-1102: at most max_keep, record order when the group has no more, else
+// a stable rank by (miss_bp, index)); the union of the three lists in record order, every member with its 3-bit membership and
+// its position in each of its lists.  Counting is all-against-all over LDS (n <= 256: every lane reads the same entry, a
+// broadcast); only the union - at most 3 * max_keep entries - and the region's BamPhase are for the host.
+__global__ __launch_bounds__(64) void bam_select_kernel(const BamKept* __restrict__ kept, const BamTag* __restrict__ tags,
+                                                       const int32_t* __restrict__ n_kept, const int32_t* __restrict__ reg_status, int n_regs,
+                                                       int max_keep, BamPick* __restrict__ picks, BamPhase* __restrict__ phase)
+{
+    __shared__ long long s_key[KEPT_CAP];
+    __shared__ int32_t s_miss[KEPT_CAP];
+    __shared__ uint32_t s_grp[KEPT_CAP];       // the entry's hap, then its group bits
+    __shared__ uint32_t s_mem[KEPT_CAP];       // its member word (0: in no list)
+    const int g = (int)blockIdx.x;
+    if (g >= n_regs) return;
+    const int lane = (int)threadIdx.x;
+    int n = reg_status[g] == REG_OK ? n_kept[g] : 0;
+    n = n < 0 ? 0 : (n > KEPT_CAP ? KEPT_CAP : n);
+    const BamKept* K = kept + (size_t)g * KEPT_CAP;
+    const BamTag* T = tags + (size_t)g * KEPT_CAP;
+    for (int e = lane; e < n; e += 64) {
+        s_key[e] = T[e].ps;
+        s_grp[e] = (uint32_t)T[e].hap;
+        s_miss[e] = K[e].miss;
+    }
+    __syncthreads();
+    // P: per tagged entry the number of tagged entries with its ps; the best (count, then the smallest ps) of the wavefront
+    int best_c = 0;
+    long long best_k = 0x7FFFFFFFFFFFFFFFll;
+    for (int e = lane; e < n; e += 64) {
+        if (s_grp[e] == 0u) continue;
+        const long long key = s_key[e];
+        int c = 0;
+        for (int m = 0; m < n; ++m) c += (s_grp[m] != 0u && s_key[m] == key) ? 1 : 0;
+        if (c > best_c || (c == best_c && key < best_k)) { best_c = c; best_k = key; }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const int oc = __shfl_xor(best_c, d);
+        const long long ok = __shfl_xor(best_k, d);
+        if (oc > best_c || (oc == best_c && ok < best_k)) { best_c = oc; best_k = ok; }
+    }
+    const bool tagged = best_c > 0;
+    const long long P = tagged ? best_k : PS_NONE;
+    __syncthreads();
+    int cnt0 = 0, cnt1 = 0, cnt2 = 0;
+    for (int e = lane; e < n; e += 64) {
+        const uint32_t h = s_grp[e];
+        const bool mine = tagged && s_key[e] == P;
+        const uint32_t bits = 1u | ((mine && h == 1u) ? 2u : 0u) | ((mine && h == 2u) ? 4u : 0u);
+        s_grp[e] = bits;
+        cnt0 += 1; cnt1 += (int)((bits >> 1) & 1u); cnt2 += (int)((bits >> 2) & 1u);
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) { cnt0 += __shfl_xor(cnt0, d); cnt1 += __shfl_xor(cnt1, d); cnt2 += __shfl_xor(cnt2, d); }
+    __syncthreads();
+    const bool by_miss0 = cnt0 > max_keep, by_miss1 = cnt1 > max_keep, by_miss2 = cnt2 > max_keep;
+    for (int e = lane; e < n; e += 64) {
+        const uint32_t bits = s_grp[e];
+        const int me = s_miss[e];
+        int r0 = 0, r1 = 0, r2 = 0;
+        for (int m = 0; m < n; ++m) {
+            const uint32_t b = s_grp[m];
+            const bool before = m < e, less = s_miss[m] < me || (s_miss[m] == me && before);
+            r0 += (by_miss0 ? less : before) ? 1 : 0;
+            r1 += (((b >> 1) & 1u) && (by_miss1 ? less : before)) ? 1 : 0;
+            r2 += (((b >> 2) & 1u) && (by_miss2 ? less : before)) ? 1 : 0;
+        }
+        uint32_t w = 0;
+        if (r0 < max_keep) w |= 1u | ((uint32_t)r0 << 8);
+        if ((bits & 2u) && r1 < max_keep) w |= 2u | ((uint32_t)r1 << 16);
+        if ((bits & 4u) && r2 < max_keep) w |= 4u | ((uint32_t)r2 << 24);
+        s_mem[e] = w;
+    }
+    __syncthreads();
+    int n_union = 0;
+    BamPick* out = picks + (size_t)g * 3u * (size_t)max_keep;
+    for (int e = lane; e < n; e += 64) {
+        const uint32_t w = s_mem[e];
+        if (!(w & 7u)) continue;
+        int u = 0;
+        for (int m = 0; m < e; ++m) u += (s_mem[m] & 7u) ? 1 : 0;
+        // (every list holds at most max_keep entries: u < 3 * max_keep)
+        if (u < 3 * max_keep) out[u] = BamPick{K[e].sq_off, K[e].q0, K[e].miss, w};
+        ++n_union;
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) n_union += __shfl_xor(n_union, d);
+    if (lane == 0) phase[g] = BamPhase{P, tagged ? 1 : 0, n_union};
 }
 
 // The bases of device-held reads (4 bits each, BAM's "=ACMGRSVTWYHKDBN") into the ASCII staging layout of pack_kernel: one

@@ -122,7 +122,7 @@ struct vapor_ctx {
     int bam_stream_share = 0;                  // the share bam_stream was made for
     int bam_cu_share = 0;
     hipEvent_t bam_ev[2] = {nullptr, nullptr}; // around the inflate launch of the last vapor_bam_chop_device (vapor_bam_last_stats)
-    double bam_stats[6] = {0, 0, 0, 0, 0, 0};  // regions, blocks, compressed bytes, inflated bytes, inflate ms, whole call ms
+    double bam_stats[7] = {0, 0, 0, 0, 0, 0, 0};  // regions, blocks, compressed bytes, inflated bytes, inflate ms, whole call ms, bytes copied back
     hipEvent_t fasta_ev[2] = {nullptr, nullptr};   // around the kernels of the last vapor_fasta_windows_device (vapor_fasta_last_stats)
     double fasta_stats[6] = {0, 0, 0, 0, 0, 0};    // windows, distinct blocks, compressed bytes, inflated bytes, kernels ms, whole call ms
     BlockPool pool;
@@ -1052,14 +1052,18 @@ static hipError_t crc_pow_on_device(vapor_ctx* ctx)
     return hipSuccess;
 }
 
-extern "C" int vapor_bam_chop_device(vapor_ctx* ctx, vapor_bam* bam, int32_t n_regions, const int32_t* tid, const int64_t* start,
-                                     const int64_t* end, const int64_t* flank, const int32_t* chunk_first, const uint64_t* chunks,
-                                     int32_t max_keep, int32_t* kept_first, uint64_t* sq_addr, int64_t* q0, int64_t* miss,
-                                     int32_t* status, vapor_bam_batch** out)
+// vapor_bam_chop_device, and with `member` (vapor_bam_chop_device_tagged) the phased form of it: the tagged chop kernel, the
+// select kernel behind it on the same stream, and only the regions' compact unions and phase sets copied back.
+static int bam_chop_device_impl(vapor_ctx* ctx, vapor_bam* bam, int32_t n_regions, const int32_t* tid, const int64_t* start,
+                                const int64_t* end, const int64_t* flank, const int32_t* chunk_first, const uint64_t* chunks,
+                                int32_t max_keep, int32_t* kept_first, uint64_t* sq_addr, int64_t* q0, int64_t* miss,
+                                int32_t* status, vapor_bam_batch** out, uint32_t* member, int64_t* phase_set, int32_t* tagged)
 {
     using namespace vapor_bamdev;
+    const bool phased = member != nullptr;
     if (!ctx || !bam || !out || n_regions < 0 || max_keep < 1 || max_keep > KEPT_CAP ||
-        (n_regions && (!tid || !start || !end || !flank || !chunk_first || !kept_first || !sq_addr || !q0 || !miss || !status)))
+        (n_regions && (!tid || !start || !end || !flank || !chunk_first || !kept_first || !sq_addr || !q0 || !miss || !status)) ||
+        (phased && n_regions && (!phase_set || !tagged)))
         return fail(VAPOR_E_ARG, "vapor_bam_chop_device: bad argument");
     const int fd = vapor_bam_fileno(bam);
     if (fd < 0) return fail(VAPOR_E_ARG, "vapor_bam_chop_device: the file is not open");
@@ -1181,9 +1185,16 @@ extern "C" int vapor_bam_chop_device(vapor_ctx* ctx, vapor_bam* bam, int32_t n_r
         const size_t o_reg = o_span + ((sizeof(BamSpan) * std::max<size_t>(dspans.size(), 1) + 63) & ~(size_t)63);
         const size_t in_bytes = o_reg + ((sizeof(BamRegion) * regs.size() + 63) & ~(size_t)63);
         const size_t o_bst = in_bytes, o_nk = o_bst + ((4 * std::max<size_t>(n_blks, 1) + 63) & ~(size_t)63);
-        const size_t o_rst = o_nk + ((4 * regs.size() + 63) & ~(size_t)63), o_kept = o_rst + ((4 * regs.size() + 63) & ~(size_t)63);
-        const size_t meta_bytes = o_kept + sizeof(BamKept) * KEPT_CAP * regs.size();
-        HIPCHK(h_meta.ensure(meta_bytes));
+        const size_t o_rst = o_nk + ((4 * regs.size() + 63) & ~(size_t)63);
+        // (phased: the regions' BamPhase and their unions - 3 * max_keep picks each - come back; the kept entries and their tags
+        // stay on the device)
+        const size_t o_phase = o_rst + ((4 * regs.size() + 63) & ~(size_t)63);
+        const size_t o_picks = o_phase + (phased ? (sizeof(BamPhase) * regs.size() + 63) & ~(size_t)63 : 0);
+        const size_t o_kept = o_picks + (phased ? (sizeof(BamPick) * 3 * (size_t)max_keep * regs.size() + 63) & ~(size_t)63 : 0);
+        const size_t o_tags = o_kept + sizeof(BamKept) * KEPT_CAP * regs.size();
+        const size_t back_end = phased ? o_kept : o_tags;            // what the host reads back ends here
+        const size_t meta_bytes = o_tags + (phased ? sizeof(BamTag) * KEPT_CAP * regs.size() : 0);
+        HIPCHK(h_meta.ensure(std::max(back_end, in_bytes)));
         HIPCHK(d_meta.ensure(meta_bytes));
         HIPCHK(d_comp.ensure(std::max<size_t>(stage_bytes, 64)));
         HIPCHK(dmalloc(ctx, (void**)&B->d_arena, arena + 64));
@@ -1223,14 +1234,26 @@ extern "C" int vapor_bam_chop_device(vapor_ctx* ctx, vapor_bam* bam, int32_t n_r
         }
         HIPCHK(hipEventRecord(ctx->bam_ev[1], st));
         if (dbg_t) { HIPCHK(hipStreamSynchronize(st)); tq[4] = now(); }
-        if (n_regions) {
+        if (n_regions && phased) {
+            hipLaunchKernelGGL(bam_chop_tagged_kernel, dim3((unsigned)n_regions), dim3(64), 0, st, B->d_arena, reinterpret_cast<const BamRegion*>(d_meta + o_reg),
+                               reinterpret_cast<const BamSpan*>(d_meta + o_span), reinterpret_cast<const int32_t*>(d_meta + o_bst), (int)n_regions,
+                               reinterpret_cast<BamKept*>(d_meta + o_kept), reinterpret_cast<int32_t*>(d_meta + o_nk), reinterpret_cast<int32_t*>(d_meta + o_rst),
+                               reinterpret_cast<BamTag*>(d_meta + o_tags));
+            HIPCHK(hipGetLastError());
+            hipLaunchKernelGGL(bam_select_kernel, dim3((unsigned)n_regions), dim3(64), 0, st, reinterpret_cast<const BamKept*>(d_meta + o_kept),
+                               reinterpret_cast<const BamTag*>(d_meta + o_tags), reinterpret_cast<const int32_t*>(d_meta + o_nk),
+                               reinterpret_cast<const int32_t*>(d_meta + o_rst), (int)n_regions, (int)max_keep,
+                               reinterpret_cast<BamPick*>(d_meta + o_picks), reinterpret_cast<BamPhase*>(d_meta + o_phase));
+            HIPCHK(hipGetLastError());
+        } else if (n_regions) {
             hipLaunchKernelGGL(bam_chop_kernel, dim3((unsigned)n_regions), dim3(64), 0, st, B->d_arena, reinterpret_cast<const BamRegion*>(d_meta + o_reg),
                                reinterpret_cast<const BamSpan*>(d_meta + o_span), reinterpret_cast<const int32_t*>(d_meta + o_bst), (int)n_regions,
                                reinterpret_cast<BamKept*>(d_meta + o_kept), reinterpret_cast<int32_t*>(d_meta + o_nk), reinterpret_cast<int32_t*>(d_meta + o_rst));
             HIPCHK(hipGetLastError());
         }
         // (counts and statuses first; the kept reads of a region are read where its count says)
-        HIPCHK(hipMemcpyAsync(h_meta + o_bst, d_meta + o_bst, meta_bytes - o_bst, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(h_meta + o_bst, d_meta + o_bst, back_end - o_bst, hipMemcpyDeviceToHost, st));
+        ctx->bam_stats[6] = (double)(back_end - o_bst);
         HIPCHK(hipStreamSynchronize(st));
         tq[5] = now();
         {
@@ -1263,10 +1286,30 @@ extern "C" int vapor_bam_chop_device(vapor_ctx* ctx, vapor_bam* bam, int32_t n_r
         // ---- minimize_pacbio_read_list (SF:1091-1102): at most max_keep, the smallest miss_bp first, file order inside one value
         const int32_t* nk = reinterpret_cast<const int32_t*>(h_meta + o_nk);
         const int32_t* rst = reinterpret_cast<const int32_t*>(h_meta + o_rst);
-        const BamKept* kept = reinterpret_cast<const BamKept*>(h_meta + o_kept);
+        const BamKept* kept = reinterpret_cast<const BamKept*>(h_meta + o_kept);       // (not read when phased)
         int32_t w = 0;
         std::vector<int32_t> order;
-        for (int32_t g = 0; g < n_regions; ++g) {
+        for (int32_t g = 0; phased && g < n_regions; ++g) {
+            // (the selection was made on the device: the union as it lies, at most 3 * max_keep entries)
+            const BamPhase& ph = reinterpret_cast<const BamPhase*>(h_meta + o_phase)[g];
+            kept_first[g] = w;
+            phase_set[g] = INT64_MIN;
+            tagged[g] = 0;
+            if (status[g]) continue;
+            if (rst[g] != REG_OK) { status[g] = rst[g]; continue; }
+            if (ph.n_union < 0 || ph.n_union > 3 * max_keep) { status[g] = REG_MALFORMED; continue; }
+            phase_set[g] = (int64_t)ph.ps;
+            tagged[g] = ph.tagged;
+            const BamPick* pk = reinterpret_cast<const BamPick*>(h_meta + o_picks) + (size_t)g * 3u * (size_t)max_keep;
+            for (int32_t i = 0; i < ph.n_union; ++i) {
+                sq_addr[w] = (uint64_t)reinterpret_cast<uintptr_t>(B->d_arena + pk[i].sq_off);
+                q0[w] = pk[i].q0;
+                miss[w] = pk[i].miss;
+                member[w] = pk[i].member;
+                ++w;
+            }
+        }
+        for (int32_t g = 0; !phased && g < n_regions; ++g) {
             kept_first[g] = w;
             if (status[g]) continue;
             if (rst[g] != REG_OK) { status[g] = rst[g]; continue; }
@@ -1296,12 +1339,31 @@ extern "C" int vapor_bam_chop_device(vapor_ctx* ctx, vapor_bam* bam, int32_t n_r
     }
 }
 
+extern "C" int vapor_bam_chop_device(vapor_ctx* ctx, vapor_bam* bam, int32_t n_regions, const int32_t* tid, const int64_t* start,
+                                     const int64_t* end, const int64_t* flank, const int32_t* chunk_first, const uint64_t* chunks,
+                                     int32_t max_keep, int32_t* kept_first, uint64_t* sq_addr, int64_t* q0, int64_t* miss,
+                                     int32_t* status, vapor_bam_batch** out)
+{
+    return bam_chop_device_impl(ctx, bam, n_regions, tid, start, end, flank, chunk_first, chunks, max_keep, kept_first, sq_addr, q0, miss,
+                                status, out, nullptr, nullptr, nullptr);
+}
+
+extern "C" int vapor_bam_chop_device_tagged(vapor_ctx* ctx, vapor_bam* bam, int32_t n_regions, const int32_t* tid, const int64_t* start,
+                                            const int64_t* end, const int64_t* flank, const int32_t* chunk_first, const uint64_t* chunks,
+                                            int32_t max_keep, int32_t* kept_first, uint64_t* sq_addr, int64_t* q0, int64_t* miss,
+                                            uint32_t* member, int64_t* phase_set, int32_t* tagged, int32_t* status, vapor_bam_batch** out)
+{
+    if (!member) return fail(VAPOR_E_ARG, "vapor_bam_chop_device_tagged: bad argument");
+    return bam_chop_device_impl(ctx, bam, n_regions, tid, start, end, flank, chunk_first, chunks, max_keep, kept_first, sq_addr, q0, miss,
+                                status, out, member, phase_set, tagged);
+}
+
 // what the context's last vapor_bam_chop_device did: regions, blocks, compressed bytes sent, inflated bytes, the inflate kernel's
 // duration between two events on its stream (ms), the whole call on the host's clock (ms)
 extern "C" int vapor_bam_last_stats(vapor_ctx* ctx, double* out, int32_t n)
 {
     if (!ctx || !out || n < 0) return fail(VAPOR_E_ARG, "vapor_bam_last_stats: null argument");
-    for (int32_t i = 0; i < n && i < 6; ++i) out[i] = ctx->bam_stats[i];
+    for (int32_t i = 0; i < n && i < 7; ++i) out[i] = ctx->bam_stats[i];
     return VAPOR_OK;
 }
 

@@ -84,6 +84,39 @@ def _collect(results, reads, scores: List[float], keep=None):
     return best
 
 
+def _scores(phased):
+    """A driver's score list: a plain list, or with `--phased` a phase.Phased (a list that can carry the groups' scores)."""
+    if not phased:
+        return []
+    from .phase import Phased
+    return Phased()
+
+
+def _score_phased(kind, ref_seq, alt_seq, reads, k, scores, num_reads_cff, keep_fn=None):
+    """The Score request and the per-read loop of a simple driver for a phased locus (`--phased`; not in the
+    reference).  `reads` is a phase.PhasedReads: group A's list - today's list - with the lists of H1 and H2 beside it.  The
+    distinct reads of the three lists go into ONE Score request (every read is scored once); group A's part of the answer
+    goes through _collect exactly as the unphased driver's answer does, and the parts of H1 and H2 ride on `scores.phase`
+    for the writer.  keep_fn: the INS driver's per-read N rule (SF:1878), applied to every read of the union.  A group whose
+    list has no more than num_reads_cff reads - the gate group A has passed - is not reported (None)."""
+    union = reads.union
+    kept = [keep_fn(x) for x in union] if keep_fn is not None else [True] * len(union)
+    used = [x for x, f in zip(union, kept) if f]
+    res = (yield Score(kind, ref_seq, alt_seq, used, k)) if used else []
+    it = iter(res)
+    got = [next(it) if f else None for f in kept]            # per read of the union: its score, None where it was skipped
+    pos_a = reads.pos[0]
+    best = _collect([got[u] for u in pos_a if kept[u]], reads, scores, keep=[kept[u] for u in pos_a])
+    halves = []
+    for g in (1, 2):
+        if len(reads.groups[g]) > num_reads_cff:
+            halves.append([got[u] for u in reads.pos[g] if got[u] is not None])
+        else:
+            halves.append(None)
+    scores.phase = (reads.tagged, reads.ps, halves[0], halves[1])
+    return best
+
+
 def _window(seq):
     res = yield Window(seq)
     return res[0]
@@ -153,22 +186,27 @@ def _rcpart(part):
 
 
 # ------------------------------------------------------------------------------------------
-def vapor_simple_del(num_reads_cff, plt_li, bam_in, ref, sv_info, out_figure_name):
-    """vapor_simple_del_Vapor, SF:1701-1745."""
+def vapor_simple_del(num_reads_cff, plt_li, bam_in, ref, sv_info, out_figure_name, phased=False):
+    """vapor_simple_del_Vapor, SF:1701-1745.  phased (`--phased`, here and in the three drivers below): the reads come as a
+    phase.PhasedReads and the Score request goes through _score_phased; nothing else differs."""
     flank = seqio.flank_length_calculate(sv_info)
-    scores: List[float] = []
+    scores: List[float] = _scores(phased)
+    ph = (True,) if phased else ()
     if sv_info[2] - sv_info[1] < default_max_sv_test:
-        reads = seqio.simple_del_chop_pacbio_read_simple_short(bam_in, sv_info, flank)
+        reads = seqio.simple_del_chop_pacbio_read_simple_short(bam_in, sv_info, flank, *ph)
         if len(reads) > num_reads_cff:
             ref_seq = seqio.ref_seq_readin(ref, sv_info[0], sv_info[1] - flank, sv_info[2] + flank)
             k = yield from _window(ref_seq)
             if not k == "Error":
                 alt_seq = _cat((ref_seq, None, flank), (ref_seq, -flank, None))      # ref_seq[:flank] + ref_seq[-flank:], SF:1712
-                res = yield Score("del", ref_seq, alt_seq, reads, k)     # min of the two scorers' scores, SF:1718-1726
-                best = _collect(res, reads, scores)
+                if phased:
+                    best = yield from _score_phased("del", ref_seq, alt_seq, reads, k, scores, num_reads_cff)
+                else:
+                    res = yield Score("del", ref_seq, alt_seq, reads, k)     # min of the two scorers' scores, SF:1718-1726
+                    best = _collect(res, reads, scores)
                 yield Figure(scores, best, k, ref_seq, alt_seq, out_figure_name)
     else:
-        reads = seqio.simple_del_chop_pacbio_read_simple_short(bam_in, sv_info, flank)
+        reads = seqio.simple_del_chop_pacbio_read_simple_short(bam_in, sv_info, flank, *ph)
         if len(reads) > num_reads_cff:
             ref_seq = seqio.ref_seq_readin(ref, sv_info[0], sv_info[1] - flank, sv_info[1] + flank)
             k = yield from _window(ref_seq)
@@ -178,8 +216,11 @@ def vapor_simple_del(num_reads_cff, plt_li, bam_in, ref, sv_info, out_figure_nam
                                (seqio.ref_seq_readin(ref, sv_info[0], sv_info[2], sv_info[2] + flank), None, None))
                 k = yield from _window(alt_seq)
                 if not k == "Error":
-                    res = yield Score("s2", ref_seq, alt_seq, reads, k)
-                    best = _collect(res, reads, scores)
+                    if phased:
+                        best = yield from _score_phased("s2", ref_seq, alt_seq, reads, k, scores, num_reads_cff)
+                    else:
+                        res = yield Score("s2", ref_seq, alt_seq, reads, k)
+                        best = _collect(res, reads, scores)
                     yield Figure(scores, best, k, ref_seq, alt_seq, out_figure_name)
     return scores
 
@@ -211,10 +252,11 @@ def vapor_bnd(num_reads_cff, plt_li, bam_in, ref, bnd_info, out_figure_name):
     return scores
 
 
-def vapor_simple_inv(num_reads_cff, plt_li, bam_in, ref, sv_info, out_figure_name):
+def vapor_simple_inv(num_reads_cff, plt_li, bam_in, ref, sv_info, out_figure_name, phased=False):
     """vapor_simple_inv_Vapor, SF:1895-1933."""
     flank = seqio.flank_length_calculate(sv_info)
-    scores: List[float] = []
+    scores: List[float] = _scores(phased)
+    ph = (True,) if phased else ()
     if sv_info[2] - sv_info[1] < default_max_sv_test:
         ref_seq = seqio.ref_seq_readin(ref, sv_info[0], sv_info[1] - flank, sv_info[2] + flank)
         k = yield from _window(ref_seq)
@@ -223,10 +265,13 @@ def vapor_simple_inv(num_reads_cff, plt_li, bam_in, ref, sv_info, out_figure_nam
             alt_seq = _cat((ref_seq, None, flank), (ref_seq, flank, -flank, True), (ref_seq, -flank, None))
             k = yield from _window(alt_seq)
             if not k == "Error":
-                reads = seqio.simple_chop_pacbio_read_simple_short(bam_in, sv_info, flank)
+                reads = seqio.simple_chop_pacbio_read_simple_short(bam_in, sv_info, flank, *ph)
                 if len(reads) > num_reads_cff:
-                    res = yield Score("s1", ref_seq, alt_seq, reads, k)
-                    best = _collect(res, reads, scores)
+                    if phased:
+                        best = yield from _score_phased("s1", ref_seq, alt_seq, reads, k, scores, num_reads_cff)
+                    else:
+                        res = yield Score("s1", ref_seq, alt_seq, reads, k)
+                        best = _collect(res, reads, scores)
                     yield Figure(scores, best, k, ref_seq, alt_seq, out_figure_name)
                     return scores
     ref_seq = seqio.ref_seq_readin(ref, sv_info[0], sv_info[1] - flank, sv_info[1] + flank)
@@ -235,18 +280,22 @@ def vapor_simple_inv(num_reads_cff, plt_li, bam_in, ref, sv_info, out_figure_nam
         alt_seq = _cat((ref_seq, None, flank), (seqio.ref_seq_readin(ref, sv_info[0], sv_info[2] - flank, sv_info[2], "TRUE"), None, None))
         k = yield from _window(alt_seq)
         if not k == "Error":
-            reads = seqio.simple_del_chop_pacbio_read_simple_short(bam_in, sv_info, flank)
+            reads = seqio.simple_del_chop_pacbio_read_simple_short(bam_in, sv_info, flank, *ph)
             if len(reads) > num_reads_cff:
-                res = yield Score("s2", ref_seq, alt_seq, reads, k)
-                best = _collect(res, reads, scores)
+                if phased:
+                    best = yield from _score_phased("s2", ref_seq, alt_seq, reads, k, scores, num_reads_cff)
+                else:
+                    res = yield Score("s2", ref_seq, alt_seq, reads, k)
+                    best = _collect(res, reads, scores)
                 yield Figure(scores, best, k, ref_seq, alt_seq, out_figure_name)
     return scores
 
 
-def vapor_simple_tandup(num_reads_cff, plt_li, bam_in, ref, sv_info, out_figure_name):
+def vapor_simple_tandup(num_reads_cff, plt_li, bam_in, ref, sv_info, out_figure_name, phased=False):
     """vapor_simple_tandup_Vapor, SF:1747-1784."""
     flank = seqio.flank_length_calculate(sv_info)
-    scores: List[float] = []
+    scores: List[float] = _scores(phased)
+    ph = (True,) if phased else ()
     if sv_info[2] - sv_info[1] < default_max_sv_test:
         ref_seq = seqio.ref_seq_readin(ref, sv_info[0], sv_info[1] - flank, sv_info[2] + flank)
         k = yield from _window(ref_seq)
@@ -256,10 +305,13 @@ def vapor_simple_tandup(num_reads_cff, plt_li, bam_in, ref, sv_info, out_figure_
             k = yield from _window(alt_seq)
             if not k == "Error":
                 reads = seqio.simple_chop_pacbio_read_simple_short(
-                    bam_in, sv_info[:2] + [sv_info[1] + 2 * (sv_info[2] - sv_info[1])], flank)
+                    bam_in, sv_info[:2] + [sv_info[1] + 2 * (sv_info[2] - sv_info[1])], flank, *ph)
                 if len(reads) > num_reads_cff:
-                    res = yield Score("s3", ref_seq, alt_seq, reads, k)
-                    best = _collect(res, reads, scores)
+                    if phased:
+                        best = yield from _score_phased("s3", ref_seq, alt_seq, reads, k, scores, num_reads_cff)
+                    else:
+                        res = yield Score("s3", ref_seq, alt_seq, reads, k)
+                        best = _collect(res, reads, scores)
                     yield Figure(scores, best, k, ref_seq, alt_seq, out_figure_name)
                     return scores
     ref_seq = seqio.ref_seq_readin(ref, sv_info[0], sv_info[2] - flank, sv_info[2] + flank)
@@ -270,10 +322,13 @@ def vapor_simple_tandup(num_reads_cff, plt_li, bam_in, ref, sv_info, out_figure_
                        (seqio.ref_seq_readin(ref, sv_info[0], sv_info[1], sv_info[1] + flank), None, None))
         k = yield from _window(alt_seq)
         if not k == "Error":
-            reads = seqio.simple_del_chop_pacbio_read_simple_short(bam_in, [sv_info[0], sv_info[2]], flank)
+            reads = seqio.simple_del_chop_pacbio_read_simple_short(bam_in, [sv_info[0], sv_info[2]], flank, *ph)
             if len(reads) > num_reads_cff:
-                res = yield Score("s2", ref_seq, alt_seq, reads, k)
-                best = _collect(res, reads, scores)
+                if phased:
+                    best = yield from _score_phased("s2", ref_seq, alt_seq, reads, k, scores, num_reads_cff)
+                else:
+                    res = yield Score("s2", ref_seq, alt_seq, reads, k)
+                    best = _collect(res, reads, scores)
                 yield Figure(scores, best, k, ref_seq, alt_seq, out_figure_name)
     return scores
 
@@ -342,7 +397,7 @@ def vapor_refine(svtype, num_reads_cff, plt_li, bam_in, ref, sv_info, out_figure
     return scores
 
 
-def vapor_simple_ins(num_reads_cff, plt_li, bam_in, ref, ins_pos, ins_seq, out_figure_name, POLARITY):
+def vapor_simple_ins(num_reads_cff, plt_li, bam_in, ref, ins_pos, ins_seq, out_figure_name, POLARITY, phased=False):
     """vapor_simple_ins_Vapor, SF:1856-1893.  ins_pos is 'chrom_pos'."""
     if POLARITY == "+":
         ins_seq_2 = ins_seq
@@ -354,8 +409,8 @@ def vapor_simple_ins(num_reads_cff, plt_li, bam_in, ref, ins_pos, ins_seq, out_f
     chrom = "_".join(ins_pos.split("_")[:-1])
     pos_s = ins_pos.split("_")[-1]
     pos = int(pos_s)
-    scores: List[float] = []
-    reads = seqio.simple_chop_pacbio_read_simple_short(bam_in, [chrom, pos_s] + [pos + len(ins_seq)], flank)
+    scores: List[float] = _scores(phased)
+    reads = seqio.simple_chop_pacbio_read_simple_short(bam_in, [chrom, pos_s] + [pos + len(ins_seq)], flank, *((True,) if phased else ()))
     if len(reads) > num_reads_cff:
         if len(ins_seq) < 5000:
             ref_seq = seqio.ref_seq_readin(ref, chrom, pos - flank, pos + flank + len(ins_seq))
@@ -372,10 +427,13 @@ def vapor_simple_ins(num_reads_cff, plt_li, bam_in, ref, ins_pos, ins_seq, out_f
             def few_n(x):                                   # SF:1878
                 return float(x[0].count("N") + x[0].count("n")) / float(len(x[0])) < 0.1
 
-            kept = [few_n(x) for x in reads]
-            used = [x for x, f in zip(reads, kept) if f]
-            res = (yield Score("s1", ref_seq, alt_seq, used, k)) if used else []
-            best = _collect(res, reads, scores, keep=kept)
+            if phased:
+                best = yield from _score_phased("s1", ref_seq, alt_seq, reads, k, scores, num_reads_cff, few_n)
+            else:
+                kept = [few_n(x) for x in reads]
+                used = [x for x, f in zip(reads, kept) if f]
+                res = (yield Score("s1", ref_seq, alt_seq, used, k)) if used else []
+                best = _collect(res, reads, scores, keep=kept)
             if ins_seq_2.count("X") == len(ins_seq_2):
                 yield Figure(scores, best, k, ref_seq, ref_seq[2:flank], out_figure_name)
             else:

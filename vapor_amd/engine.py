@@ -363,10 +363,15 @@ class Engine:
     def seqset(self, seqs: Sequence, upper: Optional[Sequence[bool]] = None, derived=None) -> SeqSet:
         return SeqSet(self, seqs, upper, derived)
 
-    def bam_chop_device(self, native_bam, tids, starts, ends, flanks, chunk_first, chunks, max_keep: int = 20):
+    def bam_chop_device(self, native_bam, tids, starts, ends, flanks, chunk_first, chunks, max_keep: int = 20, tagged: bool = False):
         """vapor_bam_chop_device: the read selection of many regions of an open BAM file on the device.  Returns (kept_first,
         device addresses of the kept reads' packed bases, q0, miss_bp, status per region, BamBatch); the batch owns the data the
-        addresses point into - close it after the sequence sets made from them."""
+        addresses point into - close it after the sequence sets made from them.  tagged (`--phased`,
+        vapor_bam_chop_device_tagged): the reads of a region are the union of its three group lists, and three more arrays
+        follow the batch - member (uint32 per read), phase_set (int64 per region, phase.PS_NONE for none), tagged (per region);
+        NotImplementedError where the library has no such entry (the CPU twin)."""
+        if tagged:
+            tagged_fn = Engine._wide_entry("vapor_bam_chop_device_tagged", "tagged device reader")
         n = len(tids)
         tids = np.ascontiguousarray(tids, dtype=np.int32)
         starts = np.ascontiguousarray(starts, dtype=np.int64)
@@ -377,13 +382,24 @@ class Engine:
         if len(chunk_first) != n + 1 or len(chunks) != 2 * int(chunk_first[-1]):
             raise ValueError("chunk_first / chunks do not describe %d regions" % n)
         kept_first = np.zeros(n + 1, dtype=np.int32)
-        cap = max(n * max_keep, 1)
+        cap = max(n * max_keep * (3 if tagged else 1), 1)
         addr = np.zeros(cap, dtype=np.uint64)
         q0 = np.zeros(cap, dtype=np.int64)
         miss = np.zeros(cap, dtype=np.int64)
         status = np.zeros(max(n, 1), dtype=np.int32)
         h = ctypes.c_void_p()
         vp = ctypes.c_void_p
+        if tagged:
+            member = np.zeros(cap, dtype=np.uint32)
+            pset = np.zeros(max(n, 1), dtype=np.int64)
+            tg = np.zeros(max(n, 1), dtype=np.int32)
+            L.check(tagged_fn(
+                self._ctx, native_bam, n, tids.ctypes.data_as(vp), starts.ctypes.data_as(vp), ends.ctypes.data_as(vp),
+                flanks.ctypes.data_as(vp), chunk_first.ctypes.data_as(vp), chunks.ctypes.data_as(vp) if len(chunks) else None,
+                int(max_keep), kept_first.ctypes.data_as(vp), addr.ctypes.data_as(vp), q0.ctypes.data_as(vp), miss.ctypes.data_as(vp),
+                member.ctypes.data_as(vp), pset.ctypes.data_as(vp), tg.ctypes.data_as(vp), status.ctypes.data_as(vp), ctypes.byref(h)))
+            w = int(kept_first[n])
+            return kept_first, addr[:w], q0[:w], miss[:w], status[:n], BamBatch(h), member[:w], pset[:n], tg[:n]
         L.check(L.load().vapor_bam_chop_device(self._ctx, native_bam, n, tids.ctypes.data_as(vp), starts.ctypes.data_as(vp), ends.ctypes.data_as(vp),
                                                flanks.ctypes.data_as(vp), chunk_first.ctypes.data_as(vp), chunks.ctypes.data_as(vp) if len(chunks) else None,
                                                int(max_keep), kept_first.ctypes.data_as(vp), addr.ctypes.data_as(vp), q0.ctypes.data_as(vp),
@@ -393,10 +409,10 @@ class Engine:
 
     def bam_last_stats(self) -> dict:
         """What this engine's last bam_chop_device did (vapor_bam_last_stats)."""
-        out = np.zeros(6, dtype=np.float64)
-        L.check(L.load().vapor_bam_last_stats(self._ctx, out.ctypes.data_as(ctypes.c_void_p), 6))
+        out = np.zeros(7, dtype=np.float64)
+        L.check(L.load().vapor_bam_last_stats(self._ctx, out.ctypes.data_as(ctypes.c_void_p), 7))
         return {"regions": int(out[0]), "blocks": int(out[1]), "compressed_bytes": int(out[2]), "inflated_bytes": int(out[3]),
-                "inflate_ms": float(out[4]), "call_ms": float(out[5])}
+                "inflate_ms": float(out[4]), "call_ms": float(out[5]), "d2h_bytes": int(out[6])}
 
     def fasta_windows_device(self, fd: int, vbeg, vend, text_cap: int):
         """vapor_fasta_windows_device: reference windows of a bgzipped FASTA (open descriptor `fd`), window i the raw text between

@@ -102,18 +102,20 @@ def capable(backend, bam_in, engine=None) -> bool:
             and (engine is None or hasattr(engine, "seqset_raw")))
 
 
-def run(engine, specs: Sequence[tuple], bam_in: str, ref: str, num_reads_cff: int) -> List[object]:
+def run(engine, specs: Sequence[tuple], bam_in: str, ref: str, num_reads_cff: int, phased: bool = False) -> List[object]:
     """specs: (type, chrom, start, end, ins_seq) per locus (`end` unused for INS, `start` its position).  Returns per locus the
-    list of read scores the driver would return, or FALLBACK."""
+    list of read scores the driver would return, or FALLBACK.  phased (`--phased`): the reads of a region are
+    the union of its three group lists (the backend's chop_many with groups=True: on the device where it can), every read is
+    scored once, and a scored locus comes back as a phase.Phased - group A's scores with the haplotypes' beside them."""
     held: list = []                       # device batches of the read selection: closed on this thread on every way out
     try:
-        return _run(engine, specs, bam_in, ref, num_reads_cff, held)
+        return _run(engine, specs, bam_in, ref, num_reads_cff, held, phased)
     finally:
         for bt in held:
             bt.close()
 
 
-def _run(engine, specs, bam_in, ref, num_reads_cff, held) -> List[object]:
+def _run(engine, specs, bam_in, ref, num_reads_cff, held, phased=False) -> List[object]:
     import os as _os
     import time as _time
     _dbg = _os.environ.get("VAPOR_DEBUG_FASTPATH")
@@ -150,6 +152,8 @@ def _run(engine, specs, bam_in, ref, num_reads_cff, held) -> List[object]:
     on_device = False
     kf = None
     refw_of = {}                         # locus -> its reference window as text, read ahead while the device extracts the reads
+    grp = {"groups": True} if phased else {}
+    member = pset = tagged = None
     if hasattr(be, "chop_many_device") and hasattr(engine, "bam_chop_device"):
         # The extraction is a native call that waits for the device (it releases the interpreter lock): on a helper thread, while
         # this one reads the loci's reference windows - the text work of the loop below that does not need to know the reads.
@@ -162,7 +166,7 @@ def _run(engine, specs, bam_in, ref, num_reads_cff, held) -> List[object]:
 
         def extract():
             try:
-                box["got"] = be.chop_many_device(engine, bam_in, chroms, r_start[idx], r_end[idx], flank[idx])
+                box["got"] = be.chop_many_device(engine, bam_in, chroms, r_start[idx], r_end[idx], flank[idx], **grp)
             except BaseException as e:       # noqa: BLE001 - handed to the calling thread below
                 box["err"] = e
             if fa_dev is not None:
@@ -191,23 +195,31 @@ def _run(engine, specs, bam_in, ref, num_reads_cff, held) -> List[object]:
         refw_of.update(box.get("win", {}))
         _mark("extract+windows")
         if "got" in box:
-            kf, addr, q0, miss, status, keepalive = box["got"]
+            kf, addr, q0, miss, status, keepalive = box["got"][:6]
+            member, pset, tagged = box["got"][6:] if phased else (None, None, None)
             held.extend(keepalive)
             on_device = True
         elif not isinstance(box.get("err"), NotImplementedError):
             raise box["err"]
     if kf is None:
         try:
-            kf, addr, q0, miss, status, keepalive = be.chop_many(bam_in, chroms, r_start[idx], r_end[idx], flank[idx])
+            got = be.chop_many(bam_in, chroms, r_start[idx], r_end[idx], flank[idx], **grp)
         except NotImplementedError:
             return out
+        kf, addr, q0, miss, status, keepalive = got[:6]
+        member, pset, tagged = got[6:] if phased else (None, None, None)
     n_reads = np.diff(kf).astype(np.int64)
+    n_list = n_reads                       # the length of the driver's read list: under --phased group A's, not the union's
+    if phased:
+        n_list = np.zeros(len(idx), dtype=np.int64)
+        if len(member):
+            np.add.at(n_list, np.repeat(np.arange(len(idx)), n_reads), (member & 1).astype(np.int64))
     # (a read that starts before its record: Python's negative slice - the drivers' way)
     neg = np.zeros(len(idx), dtype=bool)
     if len(q0):
         np.logical_or.at(neg, np.repeat(np.arange(len(idx)), n_reads), q0 < 0)
     good = (status == 0) & ~neg
-    enough = n_reads > num_reads_cff
+    enough = n_list > num_reads_cff
     # deletions and insertions without enough reads are done: [] (SF:1707, 1866); inversions and duplications go on to their
     # junction-window fallbacks in that case (SF:1918, 1769): the drivers' route
     for j in np.flatnonzero(good & ~enough & ((kind[idx] == 0) | (kind[idx] == 3))).tolist():
@@ -404,8 +416,15 @@ def _run(engine, specs, bam_in, ref, num_reads_cff, held) -> List[object]:
         keep_sc = [(q, k) for q, k in scored if not refuse[q]]
         _mark("refine+select")
         if keep_sc:
-            sc_lists = _score(engine, ss, loc, keep_sc, rd_first, kfl, rd_miss, n_lit_w, place)
+            sc_lists = _score(engine, ss, loc, keep_sc, rd_first, kfl, rd_miss, n_lit_w, place, raw=phased)
             for (q, _k), v in zip(keep_sc, sc_lists):
+                if phased:
+                    # (one score per read of the union, NaN for a skipped read: split by membership on the host)
+                    from . import phase
+                    j = loc[q][0]
+                    a_, h1, h2 = phase.split_scores(member[kfl[j]:kfl[j + 1]].tolist(), v, num_reads_cff)
+                    v = phase.Phased(a_)
+                    v.phase = (bool(tagged[j]), None if int(pset[j]) == phase.PS_NONE else int(pset[j]), h1, h2)
                 out[loc[q][1]] = v
         _mark("score")
         if _dbg:
@@ -416,8 +435,9 @@ def _run(engine, specs, bam_in, ref, num_reads_cff, held) -> List[object]:
     return out
 
 
-def _score(engine, ss, loc, scored, rd_first, kfl, rd_miss, n_lit_w, place):
-    """One plan for every scored locus: the pair and read tables of pipeline.score_requests, from arrays."""
+def _score(engine, ss, loc, scored, rd_first, kfl, rd_miss, n_lit_w, place, raw=False):
+    """One plan for every scored locus: the pair and read tables of pipeline.score_requests, from arrays.  raw: a locus's
+    scores as they come back, one per read, NaN for a skipped read (else the skipped reads are left out)."""
     import time as _time
     _ts = _time.perf_counter()
     i32 = np.int32
@@ -501,7 +521,7 @@ def _score(engine, ss, loc, scored, rd_first, kfl, rd_miss, n_lit_w, place):
     for x in range(len(scored)):
         a = int(rq_first[x])
         # (a read whose scorer output holds a 0 is skipped, e.g. SF:1913: NaN here)
-        out.append([v for v in sc[a:a + rq_n[x]] if v == v])
+        out.append(sc[a:a + rq_n[x]] if raw else [v for v in sc[a:a + rq_n[x]] if v == v])
     if _dbg:
         import sys as _sys
         print("  _score of %d loci, %d pairs: tables %.1f  plan %.1f  set_reads %.1f  run_loci %.1f  lists %.1f ms" % (

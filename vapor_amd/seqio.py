@@ -360,18 +360,20 @@ class InProcessBam(SamtoolsHybrid):
         """(QNAME, POS, CIGAR, SEQ) per alignment overlapping chrom:start-end."""
         return [r[:4] for r in self._open(bam).fetch_records(chrom, int(start), int(end))]
 
-    def chop(self, bam: str, chrom: str, start: int, end: int, flank_length: int):
+    def chop(self, bam: str, chrom: str, start: int, end: int, flank_length: int, tagged: bool = False):
         """chop_pacbio_read_by_pos (SF:339-354) straight from the BAM file: the library's native reader
-        (vapor_bam_chop), or with VAPOR_BAM_NATIVE=0 the Python statement of the same steps below."""
+        (vapor_bam_chop), or with VAPOR_BAM_NATIVE=0 the Python statement of the same steps below.  `tagged` (`--phased`):
+        every entry is [read, miss_bp, qname, hap, ps] (vapor_bam_chop_tagged; vapor_amd.phase has the tag rule)."""
         if not _env_is(b"VAPOR_BAM_NATIVE", b"0"):
-            return self._open(bam).chop_native(chrom, int(start), int(end), int(flank_length))
-        return self.chop_python(bam, chrom, start, end, flank_length)
+            return self._open(bam).chop_native(chrom, int(start), int(end), int(flank_length), tagged=tagged)
+        return self.chop_python(bam, chrom, start, end, flank_length, tagged=tagged)
 
-    def chop_many(self, bam: str, chroms, starts, ends, flanks, max_keep: int = 20):
+    def chop_many(self, bam: str, chroms, starts, ends, flanks, max_keep: int = 20, groups: bool = False):
         """MemorySamtools.chop_many's contract from a BAM file: every region through the library's native reader (vapor_bam_chop:
         threaded inflate, binary CIGAR walk, only the kept bases decoded) on a few threads, the kept reads of a region as slices
         of ONE text per region - (kept_first, addr, q0 = 0, miss, status, keepalive).  minimize_pacbio_read_list (SF:1091-1102)
-        on the numbers: the first max_keep in a stable order by miss_bp."""
+        on the numbers: the first max_keep in a stable order by miss_bp.  groups (`--phased`): through vapor_bam_chop_tagged,
+        with the selection of phase.select_numbers - see MemorySamtools.chop_many."""
         import numpy as np
         from .engine import _ASCII_OFF
         if _env_is(b"VAPOR_BAM_NATIVE", b"0") or not (0 < _ASCII_OFF < 256):
@@ -382,7 +384,7 @@ class InProcessBam(SamtoolsHybrid):
 
         def one(g):
             try:
-                return b.chop_native_raw(chroms[g], st[g], en[g], fl[g])
+                return b.chop_native_raw(chroms[g], st[g], en[g], fl[g], tagged=groups)
             except IndexError:
                 return IndexError                       # (a record without CIGAR: the drivers' route raises it where the reference does)
         from . import pipeline
@@ -397,6 +399,9 @@ class InProcessBam(SamtoolsHybrid):
         status = np.zeros(n, dtype=np.int32)
         pa, pm, keep = [], [], []
         w = 0
+        if groups:
+            from . import phase
+            member, pset, tagged = [], np.full(n, phase.PS_NONE, dtype=np.int64), np.zeros(n, dtype=np.int32)
         for g, r in enumerate(got):
             kept_first[g] = w
             if r is IndexError:
@@ -404,9 +409,14 @@ class InProcessBam(SamtoolsHybrid):
                 continue
             if r is None:
                 continue
-            whole, off, ln, miss = r
-            order = np.arange(len(off))
-            if len(order) > max_keep:
+            whole, off, ln, miss = r[:4]
+            if groups:
+                tagged[g], pset[g], order, words = phase.select_numbers(miss, r[4], r[5], max_keep)
+                order = np.asarray(order, dtype=np.int64)
+                member += words
+            else:
+                order = np.arange(len(off))
+            if not groups and len(order) > max_keep:
                 order = np.argsort(miss, kind="stable")[:max_keep]
             keep.append(whole)
             pa.append((off[order] + (id(whole) + _ASCII_OFF)).astype(np.uint64))
@@ -415,14 +425,17 @@ class InProcessBam(SamtoolsHybrid):
         kept_first[n] = w
         addr = np.concatenate(pa) if pa else np.zeros(0, dtype=np.uint64)
         miss_a = np.concatenate(pm).astype(np.int64) if pm else np.zeros(0, dtype=np.int64)
+        if groups:
+            return kept_first, addr, np.zeros(w, dtype=np.int64), miss_a, status, keep, np.asarray(member, dtype=np.uint32), pset, tagged
         return kept_first, addr, np.zeros(w, dtype=np.int64), miss_a, status, keep
 
-    def chop_many_device(self, engine, bam: str, chroms, starts, ends, flanks, max_keep: int = 20):
+    def chop_many_device(self, engine, bam: str, chroms, starts, ends, flanks, max_keep: int = 20, groups: bool = False):
         """chop_many with the work on the device (vapor_bam_chop_device: the regions' BGZF blocks go over the link compressed,
         one wavefront inflates a block, one walks a region's records): (kept_first, DEVICE addresses of the kept reads' packed
         bases, q0 = first base of each read's part, miss, status, keepalive).  A region the device leaves to the host route
         (status != 0: a damaged block, a record without CIGAR, ...) is answered by the caller's per-locus route, which words
-        the reference's errors."""
+        the reference's errors.  groups (`--phased`): vapor_bam_chop_device_tagged - the reads of a region are the union of its
+        three group lists, selected on the device; member, phase set and tagged follow as in MemorySamtools.chop_many."""
         import numpy as np
         if _env_is(b"VAPOR_BAM_NATIVE", b"0") or _env_is(b"VAPOR_BAM_DEVICE", b"0") or not hasattr(engine, "bam_chop_device"):
             raise NotImplementedError("no device reader")
@@ -430,6 +443,8 @@ class InProcessBam(SamtoolsHybrid):
         lib = _lib.load()
         if not hasattr(lib, "vapor_bam_chop_device"):
             raise NotImplementedError("no device reader")
+        phased = bool(groups)                 # (`groups` below is the list of region batches)
+        more = {"tagged": True} if phased else {}
         b = self._open(bam)
         n = len(chroms)
         tids = np.zeros(n, dtype=np.int32)
@@ -471,7 +486,7 @@ class InProcessBam(SamtoolsHybrid):
                 c0, c1 = int(chunk_first[a]), int(chunk_first[e])
                 try:
                     got = engine.bam_chop_device(tl["native"], tids[a:e], starts[a:e], ends[a:e], flanks[a:e], chunk_first[a:e + 1] - c0,
-                                                 flat_a[c0:c1].reshape(-1), max_keep)
+                                                 flat_a[c0:c1].reshape(-1), max_keep, **more)
                 except _lib.VaporHipError as err:
                     if "in one call" in str(err) and e - a >= 2:
                         groups[:0] = [(a, (a + e) // 2), ((a + e) // 2, e)]
@@ -479,12 +494,13 @@ class InProcessBam(SamtoolsHybrid):
                     if "in one call" in str(err):
                         # one region whose blocks alone are more than a call takes: the host route's (it streams them)
                         parts.append((np.zeros(2, dtype=np.int32), np.zeros(0, dtype=np.uint64), np.zeros(0, dtype=np.int64),
-                                      np.zeros(0, dtype=np.int64), np.ones(1, dtype=np.int32)))
+                                      np.zeros(0, dtype=np.int64), np.ones(1, dtype=np.int32), np.zeros(0, dtype=np.uint32),
+                                      np.zeros(1, dtype=np.int64), np.zeros(1, dtype=np.int32)))
                         continue
                     for bt in batches:
                         bt.close()
                     raise
-                parts.append(got[:5])
+                parts.append(got[:5] + got[6:])
                 batches.append(got[5])
         finally:
             with b._lock:
@@ -498,6 +514,8 @@ class InProcessBam(SamtoolsHybrid):
             w += int(p[0][-1])
             g += m
         cat = lambda k, dt: np.concatenate([p[k] for p in parts]) if parts else np.zeros(0, dtype=dt)    # noqa: E731
+        if phased:
+            return kf, cat(1, np.uint64), cat(2, np.int64), cat(3, np.int64), cat(4, np.int32), batches, cat(5, np.uint32), cat(6, np.int64), cat(7, np.int32)
         return kf, cat(1, np.uint64), cat(2, np.int64), cat(3, np.int64), cat(4, np.int32), batches
 
     def isfile(self, path: str) -> bool:
@@ -505,7 +523,7 @@ class InProcessBam(SamtoolsHybrid):
         # the interpreter lock around one, for the loci after the first)
         return path in self._bam or os.path.isfile(path)
 
-    def chop_python(self, bam: str, chrom: str, start: int, end: int, flank_length: int):
+    def chop_python(self, bam: str, chrom: str, start: int, end: int, flank_length: int, tagged: bool = False):
         """The same from the records as Python parses them: the CIGAR is walked in its binary form (the library's
         host helper) and only the reads that are kept have their bases decoded."""
         import ctypes
@@ -515,7 +533,7 @@ class InProcessBam(SamtoolsHybrid):
         res = np.zeros(2, dtype=np.int64)
         res_p = res.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
         out = []
-        for qname, pos, cig, sq, l_seq, _flag in self._open(bam).fetch_raw(chrom, int(start), int(end)):
+        for qname, pos, cig, sq, l_seq, _flag, tags in self._open(bam).fetch_raw(chrom, int(start), int(end)):
             if not pos < start + 1:
                 continue
             ops = np.ascontiguousarray(cig, dtype=np.uint32)
@@ -528,7 +546,7 @@ class InProcessBam(SamtoolsHybrid):
                 tail = seq[q0:]
                 want = end - start - miss_bp
                 if len(tail) > want:
-                    out.append([tail[:want], miss_bp, qname])
+                    out.append([tail[:want], miss_bp, qname] + (list(tags) if tagged else []))
         return out
 
     def _fasta(self, ref: str):
@@ -613,9 +631,15 @@ class MemorySamtools:
                 cache[key] = got
         return got
 
-    def chop(self, bam: str, chrom: str, start: int, end: int, flank_length):
+    def chop(self, bam: str, chrom: str, start: int, end: int, flank_length, tagged: bool = False):
+        """`tagged` (`--phased`): every entry is [read, miss_bp, qname, hap, ps], the tags read from the record's SAM text
+        fields (phase.tags_from_sam)."""
+        if tagged:
+            from .phase import tags_from_sam
         if _memory_chop_by_records():
-            return _chop_records(self.records(bam, chrom, start, end), start, end, flank_length)
+            recs = self.world.overlapping(chrom, int(start), int(end))
+            return _chop_records([(r.qname, r.pos, r.cigar, r.seq) for r in recs], start, end, flank_length,
+                                 [tags_from_sam(r.tag_fields()) for r in recs] if tagged else None)
         recs, arrs, ptr, _keep, _n = self._arrays(chrom)
         if not recs:
             return []
@@ -639,10 +663,17 @@ class MemorySamtools:
             q0, miss = qm[2 * t], qm[2 * t + 1]
             r = recs[t]
             out.append([r.seq[q0:q0 + (end - start - miss)] if q0 >= 0 else r.seq[q0:][:end - start - miss], miss, r.qname])
+            if tagged:
+                out[-1] += list(tags_from_sam(r.tag_fields()))
         return out
 
-    def chop_many(self, bam: str, chroms, starts, ends, flanks, max_keep: int = 20):
-        """chop_pacbio_read_by_pos (SF:339-354) + minimize_pacbio_read_list (SF:1091-1102) for many regions in ONE native call
+    def chop_many(self, bam: str, chroms, starts, ends, flanks, max_keep: int = 20, groups: bool = False):
+        """groups (`--phased`, not in the reference): the reads of a region are the union of the lists of its three groups (A: all
+        kept records, H1 / H2: those of one haplotype in the region's phase set; phase.select) in record order, at most
+        3 * max_keep, and three arrays follow the keepalive - member (uint32 per read: bits 0-2 the read is in the list of A / H1 /
+        H2, bits 8-15, 16-23, 24-31 its position there), phase set (int64 per region, phase.PS_NONE for none) and tagged (per
+        region: a kept record has hap != 0).  Without it:
+        chop_pacbio_read_by_pos (SF:339-354) + minimize_pacbio_read_list (SF:1091-1102) for many regions in ONE native call
         (vapor_chop_records_many): per region its kept reads as numbers, not as lists of strings -
         (kept_first [n + 1], addr, q0, miss, status [n], keepalive): read t of region g (kept_first[g] <= t < kept_first[g + 1])
         is the `end - start - miss[t]` bytes at address addr[t] + q0[t] (inside the record's own sequence string, which
@@ -673,6 +704,9 @@ class MemorySamtools:
         ptr = np.asarray([(e[1], e[2], e[3], e[4]) for e in ent], dtype=np.uint64).reshape(n, 4).T.copy()
         sa_ptr = np.fromiter((e[5].ctypes.data if e[5] is not None else 0 for e in ent), dtype=np.uint64, count=n)
         bad = np.fromiter((e[5] is None and e[0] > 0 for e in ent), dtype=bool, count=n)
+        keep_sel = max_keep
+        if groups:                                   # (every kept record comes back, in record order: the selection is below)
+            max_keep = max(int(n_rec.max()) if n else 1, 1)
         cap = max_keep * max(n, 1)
         kept_first = np.zeros(n + 1, dtype=np.int32)
         rec_idx = np.zeros(cap, dtype=np.int32)
@@ -692,6 +726,24 @@ class MemorySamtools:
         tot = int(kept_first[n])
         addr = addr[:tot]
         status[:n][bad] = -1
+        if groups:
+            from . import phase
+            pset, tagged = np.full(n, phase.PS_NONE, dtype=np.int64), np.zeros(n, dtype=np.int32)
+            kf2 = np.zeros(n + 1, dtype=np.int32)
+            take, member = [], []
+            for g in range(n):
+                a, b = int(kept_first[g]), int(kept_first[g + 1])
+                if b > a and status[g] == 0:
+                    recs = ent[g][6]
+                    tg = [phase.tags_from_sam(recs[t].tag_fields()) for t in rec_idx[a:b].tolist()]
+                    hap = np.asarray([h for h, _p in tg], dtype=np.int64)
+                    ps = np.asarray([phase.PS_NONE if p is None else p for _h, p in tg], dtype=np.int64)
+                    tagged[g], pset[g], order, words = phase.select_numbers(miss[a:b], hap, ps, keep_sel)
+                    take += [a + i for i in order]
+                    member += words
+                kf2[g + 1] = len(take)
+            take = np.asarray(take, dtype=np.int64)
+            return kf2, addr[take], q0[take], miss[take], status[:n], ent, np.asarray(member, dtype=np.uint32), pset, tagged
         return kept_first, addr, q0[:tot], miss[:tot], status[:n], ent      # (the entries hold the records the addresses point into)
 
     def isfile(self, path: str) -> bool:
@@ -822,35 +874,41 @@ def cigar2alignstart_by_pos(cigar: str, align_start: int, start: int, end: int):
     return [int(_cigar_out[0]), int(_cigar_out[1])]
 
 
-def chop_pacbio_read_by_pos(bam_in_new, chrom, start, end, flank_length):
-    """SF:339-354."""
+def chop_pacbio_read_by_pos(bam_in_new, chrom, start, end, flank_length, tagged=False):
+    """SF:339-354.  `tagged` (`--phased`, not in the reference): every kept record as [read, miss_bp, qname, hap, ps], its
+    haplotype and phase set read from the HP and PS fields behind SEQ (vapor_amd.phase)."""
     out = []
     be = get_backend()
     if hasattr(be, "chop"):
-        return be.chop(bam_in_new, chrom, start, end, flank_length)
-    if hasattr(be, "records"):
+        return be.chop(bam_in_new, chrom, start, end, flank_length, tagged=True) if tagged else be.chop(bam_in_new, chrom, start, end, flank_length)
+    tags = None
+    if hasattr(be, "records") and not tagged:
         recs = be.records(bam_in_new, chrom, start, end)
     else:
-        recs = []
+        from .phase import tags_from_sam
+        recs, tags = [], ([] if tagged else None)
         for line in be.view_lines(bam_in_new, "%s:%d-%d" % (chrom, start, end)):
             f = line.strip().split()
             if not f or f[0] == "@":
                 continue
             recs.append((f[0], f[3], f[5], f[9]))
-    return _chop_records(recs, start, end, flank_length)
+            if tagged:
+                tags.append(tags_from_sam(f[11:]))
+    return _chop_records(recs, start, end, flank_length, tags)
 
 
-def _chop_records(recs, start, end, flank_length):
-    """The body of chop_pacbio_read_by_pos (SF:345-353) over (qname, pos, cigar, seq) records."""
+def _chop_records(recs, start, end, flank_length, tags=None):
+    """The body of chop_pacbio_read_by_pos (SF:345-353) over (qname, pos, cigar, seq) records; tags: (hap, ps) per record, which
+    the kept ones then carry."""
     out = []
-    for qname, pos, cigar, seq in recs:
+    for t, (qname, pos, cigar, seq) in enumerate(recs):
         if int(pos) < start + 1:
             q0, miss_bp = cigar2alignstart_by_pos(cigar, int(pos), start, end)
             if not miss_bp > flank_length / 2:
                 tail = seq[q0:]
                 want = end - start - miss_bp
                 if len(tail) > want:
-                    out.append([tail[:want], miss_bp, qname])
+                    out.append([tail[:want], miss_bp, qname] + (list(tags[t]) if tags is not None else []))
     return out
 
 
@@ -888,27 +946,34 @@ def bam_in_decide(bam_in, bps):
             if k.split(".")[-1] == ext and all(y in k for y in keys)]
 
 
-def simple_del_chop_pacbio_read_simple_short(bam_in, sv_info, flank_length):
-    """SF:1378-1390: reads around the left breakpoint only."""
+def simple_del_chop_pacbio_read_simple_short(bam_in, sv_info, flank_length, phased=False):
+    """SF:1378-1390: reads around the left breakpoint only.  `phased` (`--phased`): the same list as a phase.PhasedReads, with
+    the lists of the two haplotype groups beside it (phase.select over the kept records of all files, before the cap)."""
     bams = bam_in_decide(bam_in, sv_info)
     if bams == "":
         return [[], [], []]
     x = []
     for b in bams:
         x += chop_pacbio_read_by_pos(b, sv_info[0], int(sv_info[1]) - flank_length,
-                                     int(sv_info[1]) + flank_length, flank_length)
+                                     int(sv_info[1]) + flank_length, flank_length, *((True,) if phased else ()))
+    if phased:
+        from .phase import select
+        return select(x)
     return minimize_pacbio_read_list(x)
 
 
-def simple_chop_pacbio_read_simple_short(bam_in, sv_info, flank_length):
-    """SF:1392-1401: reads spanning first to last breakpoint."""
+def simple_chop_pacbio_read_simple_short(bam_in, sv_info, flank_length, phased=False):
+    """SF:1392-1401: reads spanning first to last breakpoint.  `phased`: as in simple_del_chop_pacbio_read_simple_short."""
     bams = bam_in_decide(bam_in, sv_info)
     if bams == "":
         return [[], [], []]
     x = []
     for b in bams:
         x += chop_pacbio_read_by_pos(b, sv_info[0], int(sv_info[1]) - flank_length,
-                                     int(sv_info[-1]) + flank_length, flank_length)
+                                     int(sv_info[-1]) + flank_length, flank_length, *((True,) if phased else ()))
+    if phased:
+        from .phase import select
+        return select(x)
     return minimize_pacbio_read_list(x)
 
 

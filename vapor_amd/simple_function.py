@@ -301,7 +301,20 @@ def vcf_rec_hash_modify(vcf_rec_hash):
     return out
 
 
-def vcf_vapor_modify(vcf_input, vcf_rec_hash_new, header_offset_compat=False, refined=False):
+_PHASED_INFO = (
+    ('VaPoR_PS', 'Integer', 'Phase set (PS tag) of the haplotagged reads the haplotype columns were taken from (--phased)'),
+    ('VaPoR_PGT', 'String', 'Phased genotype a1|a2: whether most reads of haplotype 1 / haplotype 2 support the prediction (--phased)'),
+    ('VaPoR_PGQ', 'Float', 'Quality of the phased genotype: the smaller log10 likelihood ratio of the two called alleles (--phased)'),
+    ('VaPoR_H1_QS', 'Float', 'VaPoR_QS of the reads of haplotype 1 (--phased)'),
+    ('VaPoR_H1_GS', 'Float', 'VaPoR_GS of the reads of haplotype 1 (--phased)'),
+    ('VaPoR_H1_Rec', 'Float', 'Similarity scores of the reads of haplotype 1 (--phased)'),
+    ('VaPoR_H2_QS', 'Float', 'VaPoR_QS of the reads of haplotype 2 (--phased)'),
+    ('VaPoR_H2_GS', 'Float', 'VaPoR_GS of the reads of haplotype 2 (--phased)'),
+    ('VaPoR_H2_Rec', 'Float', 'Similarity scores of the reads of haplotype 2 (--phased)'),
+)
+
+
+def vcf_vapor_modify(vcf_input, vcf_rec_hash_new, header_offset_compat=False, refined=False, phased=False):
     """SF:1972-2028 (the second definition, which shadows SF:1942): rewrite <vcf>.vapor as the
     input VCF with ;VaPor_GS=..;VaPor_GT=..;VaPor_GQ=..;VaPor_REC=.. appended to INFO of every
     scored record.
@@ -313,7 +326,8 @@ def vcf_vapor_modify(vcf_input, vcf_rec_hash_new, header_offset_compat=False, re
     are file line numbers throughout, so headers are fine; header_offset_compat=True reproduces
     the reference's shifted lookup.  refined (`--refine`): the rows of <vcf>.vapor carry four more fields - the refined
     breakpoints and candidate 0's QS and GS - which follow as ;VaPor_RPOS=..;VaPor_REND=..;VaPor_QS0=..;VaPor_GS0=.. ('.' for
-    a record that was not refined), with ##INFO lines of their own."""
+    a record that was not refined), with ##INFO lines of their own.  phased (`--phased`): the rows carry nine more fields
+    (phase.COLUMNS), which follow under their column names; a key whose value is '.' is left out."""
     vapor_input = vcf_input + '.vapor'
     info = {}
     meta, header = [], []
@@ -342,6 +356,8 @@ def vcf_vapor_modify(vcf_input, vcf_rec_hash_new, header_offset_compat=False, re
                                    + ';VaPor_REC=' + str(pin[5]))
                     if refined:
                         info[y][7] += ';VaPor_RPOS=%s;VaPor_REND=%s;VaPor_QS0=%s;VaPor_GS0=%s' % tuple(pin[6:10])
+                    if phased:
+                        info[y][7] += ''.join(';%s=%s' % (name[0], v) for name, v in zip(_PHASED_INFO, pin[6:15]) if v != '.')
                     keep.append(y)
     with open(vapor_input, 'w') as fo:
         prev = ''
@@ -358,6 +374,9 @@ def vcf_vapor_modify(vcf_input, vcf_rec_hash_new, header_offset_compat=False, re
                     print('##INFO=<ID=VaPoR_REND,Number=1,Type=Integer,Description="End of the best-scoring candidate breakpoint pair (--refine)">', file=fo)
                     print('##INFO=<ID=VaPoR_QS0,Number=1,Type=Float,Description="VaPoR_QS of the called breakpoints on the widened window (--refine)">', file=fo)
                     print('##INFO=<ID=VaPoR_GS0,Number=1,Type=Float,Description="VaPoR_GS of the called breakpoints on the widened window (--refine)">', file=fo)
+                if phased:
+                    for name, typ, text in _PHASED_INFO:
+                        print('##INFO=<ID=%s,Number=%s,Type=%s,Description="%s">' % (name, '.' if name.endswith('_Rec') else '1', typ, text), file=fo)
             print(joined, file=fo)
             prev = cur
         print('\t'.join(header), file=fo)

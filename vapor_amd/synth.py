@@ -93,10 +93,18 @@ class SamRecord:
     cigar: str
     seq: str
     ref_span: int     # reference bases the alignment is taken to cover (for region overlap)
+    tags: Optional[dict] = None      # optional fields, e.g. {"HP": 1, "PS": 7} (vapor_amd.phase: encode_aux, sam_fields)
+
+    def tag_fields(self) -> List[str]:
+        """The optional fields as SAM text (`HP:i:1`, ...)."""
+        if not self.tags:
+            return []
+        from .phase import sam_fields
+        return sam_fields(self.tags)
 
     def line(self) -> str:
         return "\t".join([self.qname, "0", self.rname, str(self.pos), "60", self.cigar,
-                          "*", "0", "0", self.seq, "*"])
+                          "*", "0", "0", self.seq, "*"] + self.tag_fields())
 
 
 @dataclasses.dataclass
@@ -668,6 +676,21 @@ def complex_vcf_text(world: SynthWorld, header: bool = False) -> str:
     return "\n".join(out) + "\n"
 
 
+def phase_world(world: SynthWorld, seed: int, untagged: float = 0.2, phase_set: int = 1) -> SynthWorld:
+    """Haplotag an existing world in place (make_world's own draws are not touched): the loci in world.loci order, inside a
+    locus one rng.random() per read of world.reads[chrom], in list order, from default_rng(seed).  A draw below `untagged`
+    leaves the read untagged; otherwise a read whose name ends in 'a' (drawn from the alt haplotype) gets HP = 1, any other
+    HP = 2, and PS = phase_set.  (A contig that several loci share is walked once per locus; the last walk decides.)"""
+    rng = np.random.default_rng(seed)
+    for l in world.loci:
+        for r in world.reads.get(l.chrom, ()):
+            if rng.random() < untagged:
+                r.tags = None
+            else:
+                r.tags = {"HP": 1 if r.qname.endswith("a") else 2, "PS": int(phase_set)}
+    return world
+
+
 def write_world_files(world: SynthWorld, directory: str, block_size: int = 8192, qual_seed=None,
                       bgzip_reference: bool = False) -> Tuple[str, str]:
     """FASTA + .fai and coordinate-sorted BAM + .bai of a synthetic world, written by this package alone
@@ -684,7 +707,7 @@ def write_world_files(world: SynthWorld, directory: str, block_size: int = 8192,
     else:
         fa = os.path.join(directory, "ref.fa")
         _write_plain_fasta(world, fa, names)
-    recs = [(r.qname, names.index(c), r.pos - 1, r.cigar, r.seq) for c, rs in world.reads.items() for r in rs]
+    recs = [(r.qname, names.index(c), r.pos - 1, r.cigar, r.seq, r.tags) for c, rs in world.reads.items() for r in rs]
     bam = os.path.join(directory, "reads.bam")
     bamio.write_bam(bam, [(n, len(world.contigs[n])) for n in names], recs, block_size=block_size, qual_seed=qual_seed)
     return fa, bam
