@@ -369,6 +369,12 @@ int vapor_bam_chop(vapor_bam* bam, int32_t tid, int64_t start, int64_t end, int6
 int vapor_bam_chop_tagged(vapor_bam* bam, int32_t tid, int64_t start, int64_t end, int64_t flank, int32_t n_chunks,
                           const uint64_t* chunks, uint8_t* seq_out, int64_t seq_cap, char* names_out, int64_t names_cap,
                           int64_t* meta, int32_t max_reads, int32_t* n_reads, int64_t* need);
+/* vapor_bam_chop for the right-anchored reads of the window (vapor_bam_chop_device_right has the rule): the same outputs, every
+ * read written as the reverse complement of its part that ends on the window end ("=ACMGRSVTWYHKDBN" complemented by reversing
+ * the bits of a symbol's code), miss_bp counted from there. */
+int vapor_bam_chop_right(vapor_bam* bam, int32_t tid, int64_t start, int64_t end, int64_t flank, int32_t n_chunks,
+                         const uint64_t* chunks, uint8_t* seq_out, int64_t seq_cap, char* names_out, int64_t names_cap,
+                         int64_t* meta, int32_t max_reads, int32_t* n_reads, int64_t* need);
 /*
  * The read extraction of MANY regions on the DEVICE (vapor_amd/csrc/vapor_bamdev.h): what vapor_bam_chop does for one region on
  * host threads - and the reference as a `samtools view` process per locus piped into chop_pacbio_read_by_pos (SF:339-354) and
@@ -410,6 +416,18 @@ int vapor_bam_chop_device_tagged(vapor_ctx* ctx, vapor_bam* bam, int32_t n_regio
                                  const int64_t* end, const int64_t* flank, const int32_t* chunk_first, const uint64_t* chunks,
                                  int32_t max_keep, int32_t* kept_first, uint64_t* sq_addr, int64_t* q0, int64_t* miss,
                                  uint32_t* member, int64_t* phase_set, int32_t* tagged, int32_t* status, vapor_bam_batch** batch);
+/*
+ * vapor_bam_chop_device for the RIGHT-anchored reads of every region (`--both-ends`; not in the reference): the
+ * alignments whose last reference base (POS + the M, = and D operations - 1) is at or behind the window end, walked from the far
+ * end of the CIGAR (CG:B,I arrays included) - chop_pacbio_read_by_pos (SF:339-354) of the records as the reverse-complemented
+ * contig holds them.  Same arguments, statuses and selection (SF:1091-1102) as vapor_bam_chop_device, but q1[t] is the base of
+ * read t that its reverse complement STARTS with and miss[t] counts from the window end: with src_kind 2,
+ * vapor_seqset_create_mixed takes the read as the reverse complement of the end - start - miss[t] bases that end at q1[t].
+ */
+int vapor_bam_chop_device_right(vapor_ctx* ctx, vapor_bam* bam, int32_t n_regions, const int32_t* tid, const int64_t* start,
+                                const int64_t* end, const int64_t* flank, const int32_t* chunk_first, const uint64_t* chunks,
+                                int32_t max_keep, int32_t* kept_first, uint64_t* sq_addr, int64_t* q1, int64_t* miss,
+                                int32_t* status, vapor_bam_batch** batch);
 /* what the context's last vapor_bam_chop_device (or _tagged) did, for measurement (bench.py): out[0..6] = regions, BGZF blocks,
  * compressed bytes sent over the link, inflated bytes, the inflate kernel's duration between two events on its stream (ms), the
  * whole call (ms), bytes of kept reads and statuses copied back from the device */
@@ -444,6 +462,9 @@ int vapor_fasta_last_stats(vapor_ctx* ctx, double* out, int32_t n);
  * DEVICE address of BAM-packed bases (4 bits a base, "=ACMGRSVTWYHKDBN", the first base of a byte in its high half) inside the
  * data of a live vapor_bam_batch of this context, and the sequence is the len[i] bases from base src_first[i] on; src_kind[i] = 0
  * (or src_kind == NULL): bytes on the host, as vapor_seqset_create_derived takes them.  Only the host bytes cross the link.
+ * src_kind[i] = 2: a device source like 1, taken reverse complemented - the sequence is the complement (a symbol's 4-bit code
+ * with its bits reversed: = and N stay) of base src_first[i], then of src_first[i] - 1, ... for len[i] bases
+ * (len[i] <= src_first[i] + 1).
  * VAPOR_E_ARG for a device source that does not lie inside a live batch.
  */
 int vapor_seqset_create_mixed(vapor_ctx* ctx, int32_t n_seqs, const uint8_t* const* seq, const int32_t* len, const uint8_t* flags,
@@ -473,6 +494,17 @@ int vapor_chop_records_many(int32_t n_regions, const int32_t* n_rec, const int64
                             const char* const* const* cigar, const int64_t* const* seq_len, const int64_t* start,
                             const int64_t* end, const int64_t* flank, int32_t max_keep, int32_t* kept_first, int32_t* rec_idx,
                             int64_t* q0, int64_t* miss, int32_t* status, const uint64_t* const* seq_addr, uint64_t* addr_out);
+/*
+ * The right-anchored forms of the two calls above (vapor_bam_chop_device_right has the rule): q1_miss[2r] / q1[] = the number of
+ * bases to drop from the END of the read, miss_bp counted from the window end; the kept read is the reverse complement of the
+ * end - start - miss_bp bases before the dropped ones.  The whole CIGAR text of a qualifying record is read.
+ */
+int vapor_chop_records_right(int32_t n, const int64_t* pos, const int64_t* ref_span, const char* const* cigar,
+                             const int64_t* seq_len, int64_t start, int64_t end, int64_t flank, int64_t* q1_miss, uint8_t* keep);
+int vapor_chop_records_right_many(int32_t n_regions, const int32_t* n_rec, const int64_t* const* pos, const int64_t* const* ref_span,
+                                  const char* const* const* cigar, const int64_t* const* seq_len, const int64_t* start,
+                                  const int64_t* end, const int64_t* flank, int32_t max_keep, int32_t* kept_first, int32_t* rec_idx,
+                                  int64_t* q1, int64_t* miss, int32_t* status, const uint64_t* const* seq_addr, uint64_t* addr_out);
 /*
  * The row tails of a whole output table in one call (host, no device): per locus t with read scores
  * scores[off[t] .. off[t+1]) what result_organize_ins (SF:1219-1231) and gt_estimate_log_likelihood (SF:2054-2069, reading

@@ -55,11 +55,13 @@ EXPORTS = [
     "vapor_wide_batch", "vapor_clean_hits_wide", "vapor_fasta_windows_device", "vapor_fasta_last_stats", "vapor_anyk_batch",
     "vapor_plan_set_grid", "vapor_plan_run_grid", "vapor_grid_pick",
     "vapor_bam_chop_tagged", "vapor_bam_chop_device_tagged",
+    "vapor_chop_records_right", "vapor_chop_records_right_many", "vapor_bam_chop_right", "vapor_bam_chop_device_right",
 ]
 # entry points a library may lack (the CPU twin of the C ABI has no wide or any-k route and no refinement kernel): bound when
 # present, and the engine's wide, any-k and grid methods raise NotImplementedError when they are not
 OPTIONAL_EXPORTS = ("vapor_wide_batch", "vapor_clean_hits_wide", "vapor_anyk_batch", "vapor_plan_set_grid", "vapor_plan_run_grid",
-                    "vapor_grid_pick", "vapor_bam_chop_device_tagged")
+                    "vapor_grid_pick", "vapor_bam_chop_device_tagged",
+                    "vapor_chop_records_right", "vapor_chop_records_right_many", "vapor_bam_chop_right", "vapor_bam_chop_device_right")
 MAX_CANDIDATES = 128           # breakpoint refinement: candidates per locus (VAPOR_MAX_CANDIDATES)
 
 _lib = None
@@ -221,6 +223,14 @@ def bind(L: ctypes.CDLL) -> ctypes.CDLL:
     if hasattr(L, "vapor_bam_chop_device_tagged"):
         L.vapor_bam_chop_device_tagged.argtypes = [vp, vp, ctypes.c_int32, vp, vp, vp, vp, vp, vp, ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp, vp,
                                                    ctypes.POINTER(vp)]
+    if hasattr(L, "vapor_chop_records_right"):
+        L.vapor_chop_records_right.argtypes = L.vapor_chop_records.argtypes
+    if hasattr(L, "vapor_chop_records_right_many"):
+        L.vapor_chop_records_right_many.argtypes = L.vapor_chop_records_many.argtypes
+    if hasattr(L, "vapor_bam_chop_right"):
+        L.vapor_bam_chop_right.argtypes = L.vapor_bam_chop.argtypes
+    if hasattr(L, "vapor_bam_chop_device_right"):
+        L.vapor_bam_chop_device_right.argtypes = L.vapor_bam_chop_device.argtypes
     if hasattr(L, "vapor_plan_run_grid"):
         L.vapor_plan_run_grid.argtypes = [vp, i32p, f64p, f64p, i64p]
     for name in EXPORTS:
@@ -245,6 +255,9 @@ def load_holding_gil():
         vp = ctypes.c_void_p
         h.vapor_chop_records.argtypes = [ctypes.c_int32, vp, vp, vp, vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, vp, vp]
         h.vapor_chop_records.restype = ctypes.c_int
+        if hasattr(h, "vapor_chop_records_right"):
+            h.vapor_chop_records_right.argtypes = h.vapor_chop_records.argtypes
+            h.vapor_chop_records_right.restype = ctypes.c_int
         _held = h
     return _held
 

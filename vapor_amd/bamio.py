@@ -264,11 +264,12 @@ class BamFile:
         from . import phase
         return ref_id, pos, name, flag, cig, l_seq, sq, phase.tags_from_aux(rec, p + nb + l_seq)
 
-    def chop_native(self, chrom: str, start: int, end: int, flank_length: int, tagged: bool = False):
+    def chop_native(self, chrom: str, start: int, end: int, flank_length: int, tagged: bool = False, right: bool = False):
         """chop_pacbio_read_by_pos (SF:339-354) for one region through the library's native reader (vapor_bam_chop:
         threaded inflate, binary CIGAR walk, only kept bases decoded); the .bai lookup stays here.  Returns the same
         [[read tail, miss_bp, qname], ...] as the Python statement of it (seqio.InProcessBam.chop_python); with `tagged`
-        (vapor_bam_chop_tagged) every entry also carries the record's hap and ps."""
+        (vapor_bam_chop_tagged) every entry also carries the record's hap and ps; with `right` (vapor_bam_chop_right, `--both-ends`)
+        the right-anchored reads of the window, reverse complemented (seqio._chop_records)."""
         import ctypes
         from . import _lib
         lib = _lib.load()
@@ -280,12 +281,12 @@ class BamFile:
             return []
         tl = self._take_handle(lib)
         try:
-            return self._chop_with(lib, tl, tid, ch, start, end, flank_length, tagged=tagged)
+            return self._chop_with(lib, tl, tid, ch, start, end, flank_length, tagged=tagged, right=right)
         finally:
             with self._lock:
                 self._free.append(tl)
 
-    def chop_native_raw(self, chrom: str, start: int, end: int, flank_length: int, tagged: bool = False):
+    def chop_native_raw(self, chrom: str, start: int, end: int, flank_length: int, tagged: bool = False, right: bool = False):
         """chop_native's answer as numbers: (text, offsets, lengths, miss_bp) - read r is text[offsets[r] : offsets[r] + lengths[r]]
         - for callers that hand the reads on by address (vapor_amd.fastpath) instead of making a string per read; with `tagged`
         also hap and ps per read (ps: phase.PS_NONE for none)."""
@@ -299,7 +300,7 @@ class BamFile:
             return None
         tl = self._take_handle(lib)
         try:
-            return self._chop_with(lib, tl, tid, ch, start, end, flank_length, raw=True, tagged=tagged)
+            return self._chop_with(lib, tl, tid, ch, start, end, flank_length, raw=True, tagged=tagged, right=right)
         finally:
             with self._lock:
                 self._free.append(tl)
@@ -324,12 +325,16 @@ class BamFile:
             self._handles.append(h)
         return tl
 
-    def _chop_with(self, lib, tl, tid, ch, start, end, flank_length, raw=False, tagged=False):
+    def _chop_with(self, lib, tl, tid, ch, start, end, flank_length, raw=False, tagged=False, right=False):
         import ctypes
         from . import _lib
         chunks = np.asarray(ch, dtype=np.uint64).reshape(-1)
         n = ctypes.c_int32(0)
         fn, w = (lib.vapor_bam_chop_tagged, 6) if tagged else (lib.vapor_bam_chop, 4)      # (numbers per read in `meta`)
+        if right:
+            if tagged or not hasattr(lib, "vapor_bam_chop_right"):
+                raise NotImplementedError("no right-anchored native reader")
+            fn = lib.vapor_bam_chop_right
         while True:
             bf = tl["buf"]
             rc = fn(tl["native"], tid, int(start), int(end), int(flank_length), len(ch), chunks.ctypes.data,

@@ -1,0 +1,70 @@
+"""`--both-ends` (not in the reference): the seven extra columns of a row, from the per-view score lists that
+drivers.vapor_both_ends leaves on a locus's score list (drivers.BothEnds.views)."""
+from __future__ import annotations
+
+from typing import List, Optional
+
+COLUMNS = ("VaPoR_BE_N", "VaPoR_BE_QS", "VaPoR_BE_GS", "VaPoR_BE_GT", "VaPoR_BE_GQ", "VaPoR_BE_Rec", "VaPoR_BE_SQS")
+
+INFO = (
+    ("VaPoR_BE_N", "Integer", "1", "Number of views of the junction that were scored, the primary one included (--both-ends)"),
+    ("VaPoR_BE_QS", "Float", "1", "VaPoR_QS of the reads of all scored views (--both-ends)"),
+    ("VaPoR_BE_GS", "Float", "1", "VaPoR_GS of the reads of all scored views (--both-ends)"),
+    ("VaPoR_BE_GT", "String", "1", "Genotype with the highest likelihood from the reads of all scored views (--both-ends)"),
+    ("VaPoR_BE_GQ", "Float", "1", "Genotype quality from the reads of all scored views (--both-ends)"),
+    ("VaPoR_BE_Rec", "Float", ".", "Similarity scores of the reads of all scored views, in view order (--both-ends)"),
+    ("VaPoR_BE_SQS", "String", ".", "VaPoR_QS of every view of the junction in table order, '.' for a view that was not scored (--both-ends)"),
+)
+
+
+def pack(views) -> List[float]:
+    """A locus's views as one list of floats (they travel between ranks as a second table of "scores"): the number of views,
+    per view its number of scores or -1 for a view that was not scored, then all scores; nothing for a locus without views."""
+    if views is None:
+        return []
+    out = [float(len(views))] + [float(-1 if v is None else len(v)) for v in views]
+    for v in views:
+        out += [float(x) for x in (v or ())]
+    return out
+
+
+def unpack(flat) -> Optional[list]:
+    if flat is None or len(flat) == 0:
+        return None
+    n = int(flat[0])
+    lens = [int(x) for x in flat[1:1 + n]]
+    at = 1 + n
+    views = []
+    for m in lens:
+        if m < 0:
+            views.append(None)
+        else:
+            views.append([float(x) for x in flat[at:at + m]])
+            at += m
+    return views
+
+
+def columns_many(views_list) -> List[List[str]]:
+    """The seven fields of every row: '.' seven times for a locus without junction branch; else the number of scored views, the
+    row routines (finish.row_tails: result_organize_ins, SF:1219-1231, and gt_estimate_log_likelihood, SF:2054-2069) over the
+    concatenation of the scored views' lists in table order, and the views' own QS, comma-separated, '.' for a view that was
+    not scored."""
+    from .finish import row_tails
+    lists, where = [], []
+    for views in views_list:
+        if views is None:
+            where.append(None)
+            continue
+        where.append((len(lists), len(views)))
+        lists.append([x for v in views if v is not None for x in v])
+        lists += [list(v) if v is not None else [] for v in views]
+    tails = row_tails(lists)
+    out = []
+    for views, w in zip(views_list, where):
+        if w is None:
+            out.append(["."] * 7)
+            continue
+        t = tails[w[0]]
+        sqs = [("." if v is None else str(tails[w[0] + 1 + i][0])) for i, v in enumerate(views)]
+        out.append([str(sum(1 for v in views if v is not None))] + [str(x) for x in t] + [",".join(sqs)])
+    return out

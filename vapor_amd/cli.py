@@ -11,7 +11,8 @@ Extra flags (not in the reference): --no-figures (skip the recurrence-plot PNGs,
 grid of candidate breakpoints within M bp of every short DEL / INV / TANDUP call and report the best),
 --phased (bed, vcf: read the HP and PS tags of a haplotagged BAM and score the reads of each haplotype of a DEL / INV / TANDUP /
 INS call beside the pooled list; appends VaPoR_PS, VaPoR_PGT, VaPoR_PGQ and QS / GS / Rec per haplotype; not
-together with --refine).
+together with --refine), --both-ends (bed, vcf: every junction branch - long DEL / INV, TANDUP, breakends - is scored from both of
+its sides, with right-anchored reads; appends the VaPoR_BE_* columns; not together with --refine or --phased).
 """
 from __future__ import annotations
 
@@ -95,13 +96,13 @@ def dup_inv_interprete(pin):
     return 'error'
 
 
-def vcf_list_readin(file_in, bnd_ref=None):
+def vcf_list_readin(file_in, bnd_ref=None, both_ends=False):
     """vapor_vali/vapor:127-202: records bucketed by type in first-seen order, plus
     {file line index: key} for the INFO rewrite.  `bnd_ref` (the reference FASTA, `vapor vcf --bnd`): breakend records are
     read as well, into a 'BND' bucket that comes last (bnd_view); without it they take the reference's last branch."""
     out = {}
     rec_hash = {}
-    bnd = _BndReader(bnd_ref) if bnd_ref is not None else None
+    bnd = _BndReader(bnd_ref, both_ends) if bnd_ref is not None else None
     rec = -1
     # `x not in out[T]` of the reference scans the bucket's list (every record against every earlier one of its type: minutes
     # on a call set of 10^5); the same test from a set of the entries as tuples beside each list
@@ -219,14 +220,17 @@ def bnd_alt(alt: str):
     return ct, b, int(q), ins
 
 
-def bnd_view(chrom: str, pos: int, alt: str):
+def bnd_view(chrom: str, pos: int, alt: str, both_ends: bool = False):
     """The scored view of a breakend record at chrom:pos - [A, p, B, q, CT, inserted bases] with CT '3to5' or '3to3', the
     left-hand piece's reads clipped on the right at A:p - or the reason it is skipped.  A `5to3` record is scored as its mirror
-    `t[A:p[` at B:q (the same junction); a `5to5` record has no such view."""
+    `t[A:p[` at B:q (the same junction); a `5to5` record has no such view - with both_ends (`--both-ends`: right-anchored
+    reads) it is taken with CT '5to5'."""
     got = bnd_alt(alt)
     if isinstance(got, str):
         return got
     ct, b, q, ins = got
+    if ct == '5to5' and both_ends:
+        return [chrom, int(pos), b, q, ct, ins]
     if ct == '5to5':
         return '5to5 junction: its reads are clipped on the left, which the read model (SF:339-354) does not take'
     if ct == '5to3':
@@ -251,15 +255,16 @@ class _BndReader:
     mates (MATEID / MATE_ID) are scored once, at the record that comes first, and every record taken carries its locus's key
     in rec_hash, so that both mates get the annotation.  A skipped record gets one line on stderr and no row."""
 
-    def __init__(self, ref):
+    def __init__(self, ref, both_ends=False):
         from . import seqio
+        self.both_ends = both_ends
         self.chromos = seqio.chromos_readin(ref)
         self.loci, self.keys = [], set()
         self.by_id, self.by_mate = {}, {}
 
     def take(self, rec, pin, rec_hash):
         alt = pin[4] if len(pin) > 4 else ''
-        view = bnd_view(pin[0], int(pin[1]), alt)
+        view = bnd_view(pin[0], int(pin[1]), alt, True) if self.both_ends else bnd_view(pin[0], int(pin[1]), alt)
         if not isinstance(view, str):
             miss = [c for c in (view[0], view[2]) if c not in self.chromos]
             if miss:
@@ -290,7 +295,7 @@ class _BndReader:
 class Job:
     """One output row: how to score it (a driver generator factory, or fixed scores) and how to
     write it.  `cost`: what the locus is expected to take (microseconds, `job_cost`), for the shares of the ranks."""
-    __slots__ = ("key", "make", "fixed", "row_prefix", "label", "cost", "spec", "ctx", "refine", "phase")
+    __slots__ = ("key", "make", "fixed", "row_prefix", "label", "cost", "spec", "ctx", "refine", "phase", "views", "be")
 
     def __init__(self, key, make=None, fixed=None, row_prefix=None, label=None, cost=None, spec=None, ctx=None):
         self.key, self.make, self.fixed, self.row_prefix, self.label = key, make, fixed, row_prefix, label
@@ -299,6 +304,9 @@ class Job:
         self.spec, self.ctx = spec, ctx
         self.refine = None             # after scoring under --refine: refine.Refined.info of a locus that was refined
         self.phase = None              # after scoring under --phased: phase.Phased.phase of a locus that was phased
+        self.views = None              # after scoring under --both-ends: drivers.BothEnds.views of a locus with a junction branch
+        self.be = None                 # under --both-ends: vapor_both_ends' arguments (svtype, num_reads_cff, plt_li, bam, ref, info, figure
+                                       # name), so that a chunk can hand it the reads its windows' device extraction kept
         self.cost = cost if cost is not None else (COST_FIXED_US if make is None else COST_HOST_US)
 
 
@@ -317,11 +325,12 @@ COST_XMEANS_US = 500.0         # a tandem duplication's alt window always meets 
 _READS_KEPT = 20               # minimize_pacbio_read_list keeps at most 20 reads (SF:1091-1102)
 
 
-def job_cost(svtype: str, span: int, extra: int = 0, candidates: int = 1) -> float:
+def job_cost(svtype: str, span: int, extra: int = 0, candidates: int = 1, views: int = 1) -> float:
     """Expected cost of one locus in microseconds from its type and span alone (windows as the drivers cut them, SURVEY.md
     3.2): `span` = end - start (INS: the inserted length; complex types: the whole region), `extra` = the duplicated block of
     DISDUP / DUP_INV, `candidates` = the alleles scored on the window (`--refine`: every read meets the window once and every
-    candidate allele once).  An estimate for balancing shares - nothing depends on its accuracy but the ranks' idle time."""
+    candidate allele once), `views` = the views of the locus's junction (`--both-ends`: 2, 4 for an INV).  An estimate for
+    balancing shares - nothing depends on its accuracy but the ranks' idle time."""
     span = max(int(span), 0)
     f = min(500, span) if span > 0 else 500
     short = span < drivers.default_max_sv_test
@@ -342,6 +351,9 @@ def job_cost(svtype: str, span: int, extra: int = 0, candidates: int = 1) -> flo
     if candidates > 1:                      # (la = window + one allele: the other candidates' alleles are about that allele's size)
         cells += _READS_KEPT * lr * (candidates - 1) * (la / 2.0)
     xmeans = COST_XMEANS_US if (svtype == 'TANDUP' and short) else 0.0
+    if views > 1:                           # (`--both-ends`: every extra view is a junction window pair with reads of its own)
+        bases += (views - 1) * (_READS_KEPT * 2 * f + 4 * f)
+        cells += (views - 1) * _READS_KEPT * 2 * f * 4 * f
     return COST_HOST_US + COST_PER_KBASE_US * bases / 1e3 + COST_PER_GCELL_US * cells / 1e9 + xmeans
 
 
@@ -350,7 +362,16 @@ def _refine_n(refine, s, e, ci=(None, None)) -> int:
     return len(rf.candidates(refine[0], refine[1], s, e, ci[0], ci[1]))
 
 
-def bed_jobs(bed_info, num_reads_cff, bam_in, ref, out_path, sample_name, refine=None, phased=False) -> List[Job]:
+def _views_n(name, span) -> int:
+    """The views `--both-ends` may score for a locus (job_cost): the junction branch of a long call, 1 for a short one."""
+    if name == 'BND':
+        return 2
+    if span < drivers.default_max_sv_test:
+        return 1
+    return 4 if name == 'INV' else 2
+
+
+def bed_jobs(bed_info, num_reads_cff, bam_in, ref, out_path, sample_name, refine=None, phased=False, both_ends=False) -> List[Job]:
     """The loop of vapor_vali/vapor:334-367.  `refine` = (M, T) of `--refine`: DEL, INV and TANDUP loci take
     drivers.vapor_refine (which leaves a locus it cannot refine to the type's own driver).  `phased` (`--phased`): the four
     simple drivers run with phased=True (the array route takes the option from score_jobs)."""
@@ -390,6 +411,16 @@ def bed_jobs(bed_info, num_reads_cff, bam_in, ref, out_path, sample_name, refine
                                   drivers.vapor_refine(n, num_reads_cff, p, bam_in, ref, info, g, refine[0], refine[1])),
                             row_prefix=x[3], label=x, cost=job_cost(name, x[2] - x[1], candidates=_refine_n(refine, x[1], x[2]))))
             continue
+        if both_ends:
+            # (a call that may reach its junction branch takes the drivers' route: the array route has no extra views; a short
+            # DEL never reaches it and stays where it was)
+            long_or_falls = name != 'DEL' or not x[2] - x[1] < drivers.default_max_sv_test
+            jobs.append(Job(key, (lambda p=plt_li, n=name, info=x[:-3], g=fig:
+                                  drivers.vapor_both_ends(n, num_reads_cff, p, bam_in, ref, info, g)),
+                            row_prefix=x[3], label=x, cost=job_cost(name, x[2] - x[1], views=_views_n(name, x[2] - x[1])),
+                            **({} if long_or_falls else {'spec': (name, x[0], x[1], x[2], None), 'ctx': ctx})))
+            jobs[-1].be = (name, num_reads_cff, plt_li, bam_in, ref, x[:-3], fig)
+            continue
         jobs.append(Job(key, (lambda p=plt_li, f=fn, info=x[:-3], g=fig: f(num_reads_cff, p, bam_in, ref, info, g, **ph)),
                         row_prefix=x[3], label=x, cost=job_cost(name, x[2] - x[1]), spec=(name, x[0], x[1], x[2], None), ctx=ctx))
     return jobs
@@ -421,7 +452,8 @@ def vcf_ci_readin(file_in) -> dict:
     return out
 
 
-def vcf_jobs(vcf_list, num_reads_cff, bam_in, ref, out_path, sample_name, refine=None, ci_of=None, phased=False) -> List[Job]:
+def vcf_jobs(vcf_list, num_reads_cff, bam_in, ref, out_path, sample_name, refine=None, ci_of=None, phased=False,
+             both_ends=False) -> List[Job]:
     """The loop of vapor_vali/vapor:387-465 (TANDUP is bucketed but never scored there either), and the breakends of
     `vapor vcf --bnd` (vcf_list_readin's last bucket: drivers.vapor_bnd).  `refine` = (M, T) of `--refine` and `ci_of`
     (vcf_ci_readin): DEL and INV records take drivers.vapor_refine, within their CIPOS / CIEND.  `phased`: as in bed_jobs, for
@@ -442,6 +474,11 @@ def vcf_jobs(vcf_list, num_reads_cff, bam_in, ref, out_path, sample_name, refine
             if x == 'BND':
                 key = bnd_key(y)
                 fig = out_path + sample_name + '.BND.' + key.replace(':', '__') + '.png'
+                if both_ends:
+                    jobs.append(Job(key, (lambda p=plt_li, info=y, g=fig: drivers.vapor_both_ends('BND', num_reads_cff, p, bam_in, ref, info, g)),
+                                    cost=job_cost('BND', 0, views=2)))
+                    jobs[-1].be = ('BND', num_reads_cff, plt_li, bam_in, ref, y, fig)
+                    continue
                 jobs.append(Job(key, (lambda p=plt_li, info=y, g=fig: drivers.vapor_bnd(num_reads_cff, p, bam_in, ref, info, g)),
                                 cost=job_cost('BND', 0)))
             elif x in ('DEL', 'INV'):
@@ -456,6 +493,13 @@ def vcf_jobs(vcf_list, num_reads_cff, bam_in, ref, out_path, sample_name, refine
                     jobs.append(Job(key, (lambda p=plt_li, n=x, info=y, g=fig, c=ci:
                                           drivers.vapor_refine(n, num_reads_cff, p, bam_in, ref, info, g, refine[0], refine[1], c[0], c[1])),
                                     cost=job_cost(x, y[2] - y[1], candidates=_refine_n(refine, y[1], y[2], ci))))
+                    continue
+                if both_ends and len(y) == 3:
+                    long_or_falls = x != 'DEL' or not y[2] - y[1] < drivers.default_max_sv_test
+                    jobs.append(Job(key, (lambda p=plt_li, n=x, info=y, g=fig: drivers.vapor_both_ends(n, num_reads_cff, p, bam_in, ref, info, g)),
+                                    cost=job_cost(x, y[2] - y[1], views=_views_n(x, y[2] - y[1])),
+                                    **({} if long_or_falls else {'spec': (x, y[0], y[1], y[2], None), 'ctx': ctx})))
+                    jobs[-1].be = (x, num_reads_cff, plt_li, bam_in, ref, y, fig)
                     continue
                 jobs.append(Job(key, (lambda p=plt_li, f=fn, info=y, g=fig: f(num_reads_cff, p, bam_in, ref, info, g, **ph)),
                                 cost=job_cost(x, y[2] - y[1]), spec=(x, y[0], y[1], y[2], None), ctx=ctx))
@@ -582,11 +626,12 @@ def output_rows(heads: list, scores_list: list) -> tuple:
     return lines, tails
 
 
-def score_jobs(jobs: List[Job], chunk: int, figure_fn=None, refine=None, phased=False) -> List[object]:
+def score_jobs(jobs: List[Job], chunk: int, figure_fn=None, refine=None, phased=False, both_ends=False) -> List[object]:
     """Score every job (sharded over ranks, batched on each GPU); returns per job the list of read
     scores, in job order, identical on every rank.  With `refine` (`--refine`) every job's `refine` attribute is set as
     well, on every rank: refine.Refined.info of a locus that was refined, None otherwise; with `phased` (`--phased`) every
-    job's `phase` attribute likewise: phase.Phased.phase of a locus that was phased."""
+    job's `phase` attribute likewise: phase.Phased.phase of a locus that was phased; with `both_ends` (`--both-ends`) every
+    job's `views` attribute: drivers.BothEnds.views of a locus that took its junction branch."""
     import gc
     import time
     t0 = time.perf_counter()
@@ -598,6 +643,8 @@ def score_jobs(jobs: List[Job], chunk: int, figure_fn=None, refine=None, phased=
     gc_was = gc.get_threshold()
     gc.set_threshold(max(gc_was[0], 200000), max(gc_was[1], 50), max(gc_was[2], 1000))
     try:
+        if both_ends:
+            return _score_jobs(jobs, chunk, figure_fn, t0, both_ends=True)
         if phased:
             return _score_jobs(jobs, chunk, figure_fn, t0, phased=True)
         return _score_jobs(jobs, chunk, figure_fn, t0) if refine is None else _score_jobs(jobs, chunk, figure_fn, t0, refine)
@@ -616,10 +663,42 @@ def _chunk_threads_ok() -> bool:
     return os.environ.get("VAPOR_MEMORY_CHOP", "") != "records"
 
 
+def _both_ends_gens(jobs, rest, gens, engine):
+    """`--both-ends` from BAM files: the read windows of a chunk's loci - every view's, the primary ones included
+    (drivers.both_ends_windows) - go through the device extraction in one call per anchor kind (seqio.prefetch_views:
+    bam_chop_kernel, bam_chop_right_kernel), per BAM file, and the loci's generators are made over the file name that carries
+    the kept reads by device address.  A window the device leaves to the host route is read by the host reader when its view
+    asks.  Returns (the generators, the device batches to close when the chunk is scored); the generators as they were when
+    the backend or the engine has no device reader, or figures need the reads as text."""
+    from . import _lib, seqio
+    be = seqio.get_backend()
+    if (not hasattr(be, "chop_many_device") or not hasattr(engine, "bam_chop_device") or os.environ.get("VAPOR_BAM_DEVICE", "1") == "0"
+            or os.environ.get("VAPOR_BAM_NATIVE", "1") == "0"):
+        return gens, []
+    by_bam = {}
+    for k, t in enumerate(rest):
+        a = jobs[t].be
+        if a is not None and be.isfile(a[3]):
+            by_bam.setdefault(a[3], []).append(k)
+    held = []
+    gens = list(gens)
+    for bam, ks in by_bam.items():
+        windows = [w for k in ks for w in drivers.both_ends_windows(jobs[rest[k]].be[0], jobs[rest[k]].be[5])]
+        try:
+            pre = seqio.prefetch_views(engine, bam, windows)
+        except (NotImplementedError, _lib.VaporHipError):       # (a library without the right-anchored device reader)
+            continue
+        held += pre.batches
+        for k in ks:
+            svtype, n_cff, plt_li, _bam, ref, info, fig = jobs[rest[k]].be
+            gens[k] = drivers.vapor_both_ends(svtype, n_cff, plt_li, pre, ref, info, fig)
+    return gens, held
+
+
 last_timing: dict = {}          # of the most recent score_jobs: seconds scoring this rank's share, seconds in the gather
 
 
-def _score_jobs(jobs, chunk, figure_fn, t0, refine=None, phased=False):
+def _score_jobs(jobs, chunk, figure_fn, t0, refine=None, phased=False, both_ends=False):
     import time
     # shares by estimated cost (greedy longest-processing-time, SURVEY.md 8e), the same list on every rank
     costs = [float(j.cost) for j in jobs]
@@ -648,7 +727,15 @@ def _score_jobs(jobs, chunk, figure_fn, t0, refine=None, phased=False):
                         if r is not fastpath.FALLBACK:
                             done[t] = r
         rest = [t for t in todo if t not in done]
-        res = pipeline.run_batch([jobs[t].make() for t in rest], engine=engine, figure_fn=figure_fn) if rest else []
+        gens, held = [jobs[t].make() for t in rest], []
+        if both_ends and figure_fn is None and rest:
+            gens, held = _both_ends_gens(jobs, rest, gens, engine or pipeline.get_engine())
+        try:
+            res = pipeline.run_batch(gens, engine=engine, figure_fn=figure_fn) if rest else []
+        finally:
+            del gens
+            for bt in held:                          # (the reads' blocks on the device: the sets made from them are closed)
+                bt.close()
         for t, r in zip(rest, res):
             done[t] = r
         return part, todo, [done[t] for t in todo]
@@ -716,6 +803,13 @@ def _score_jobs(jobs, chunk, figure_fn, t0, refine=None, phased=False):
                  for t, r in local.items()}
         for j, v in zip(jobs, vdist.gather_results(extra, len(jobs), costs)):
             j.phase = ph.unpack(v)
+    if both_ends:
+        # (the views' score lists travel the same way: bothends.pack's floats for a locus with a junction branch)
+        from . import bothends as be
+        extra = {t: (be.pack(getattr(r, "views", None)) if not isinstance(r, BaseException) and r is not None else [])
+                 for t, r in local.items()}
+        for j, v in zip(jobs, vdist.gather_results(extra, len(jobs), costs)):
+            j.views = be.unpack(v)
     allres = vdist.gather_results(local, len(jobs), costs)
     last_timing.update(score_s=t1 - t0, gather_s=time.perf_counter() - t1, loci=len(mine), cost=sum(costs[t] for t in mine))
     if os.environ.get("VAPOR_TIMING") and vdist.rank() == 0:
@@ -749,6 +843,11 @@ def build_parser() -> argparse.ArgumentParser:
                    help='bed, vcf: read the HP and PS tags of a haplotagged BAM; every DEL / INV / TANDUP / INS call is scored per '
                         'haplotype as well (the reads with HP 1, with HP 2, of the majority phase set): appends VaPoR_PS, VaPoR_PGT, '
                         'VaPoR_PGQ and VaPoR_H1_QS / _GS / _Rec, VaPoR_H2_QS / _GS / _Rec (vcf: to INFO); not together with --refine')
+    p.add_argument('--both-ends', action='store_true',
+                   help='bed, vcf: score every junction - a DEL or INV of 10 kb or more, the junction branch of a TANDUP, every '
+                        'breakend of --bnd - from both of its sides: the reads that end behind the window (right-anchored) are scored '
+                        'as well, [B:q[t breakends are taken; appends VaPoR_BE_N, VaPoR_BE_QS / _GS / _GT / _GQ / _Rec and VaPoR_BE_SQS '
+                        '(vcf: to INFO); not together with --refine or --phased')
     return p
 
 
@@ -781,7 +880,15 @@ def main(argv: Optional[List[str]] = None) -> int:
         if refine is not None:
             parser.error('--phased and --refine cannot be combined (refinement per haplotype is not implemented)')
         from . import phase as ph
-    more = rf.COLUMNS if refine is not None else ph.COLUMNS if args.phased else ()
+    if args.both_ends:
+        if mode not in ('bed', 'vcf'):
+            parser.error('--both-ends applies to `vapor bed` and `vapor vcf`')
+        if refine is not None:
+            parser.error('--both-ends and --refine cannot be combined (refined candidates are scored from one side)')
+        if args.phased:
+            parser.error('--both-ends and --phased cannot be combined (right-anchored reads are not read with their tags)')
+        from . import bothends as be
+    more = rf.COLUMNS if refine is not None else ph.COLUMNS if args.phased else be.COLUMNS if args.both_ends else ()
     figure_fn = None
     if not args.no_figures:
         from . import figures
@@ -794,8 +901,9 @@ def main(argv: Optional[List[str]] = None) -> int:
     bam_in, ref = args.pacbio_input, args.reference
     if mode == 'bed':
         bed_info = bed_info_readin(args.sv_input, out_path)
-        jobs = bed_jobs(bed_info, num_reads_cff, bam_in, ref, out_path, sample_name, refine, args.phased)
-        scores = score_jobs(jobs, args.chunk, figure_fn, refine, args.phased)
+        opt = {'both_ends': True} if args.both_ends else {}
+        jobs = bed_jobs(bed_info, num_reads_cff, bam_in, ref, out_path, sample_name, refine, args.phased, **opt)
+        scores = score_jobs(jobs, args.chunk, figure_fn, refine, args.phased, **opt)
         if vdist.rank() == 0:
             SF.write_output_initiate(args.output_file, more)
             with open(args.output_file, 'a') as fo:
@@ -805,15 +913,18 @@ def main(argv: Optional[List[str]] = None) -> int:
                     lines = [l + '\t' + '\t'.join(rf.columns(j.refine)) for l, j in zip(lines, jobs)]
                 if args.phased:
                     lines = [l + '\t' + '\t'.join(c) for l, c in zip(lines, ph.columns_many([j.phase for j in jobs]))]
+                if args.both_ends:
+                    lines = [l + '\t' + '\t'.join(c) for l, c in zip(lines, be.columns_many([j.views for j in jobs]))]
                 fo.write(''.join([l + '\n' for l in lines]))
                 for j, tail in zip(jobs, tails):
                     print([j.key, tail[0], tail[1], tail[4]])
     elif mode == 'vcf':
-        vcf_list, rec_hash = vcf_list_readin(args.sv_input, ref if args.bnd else None)
+        opt = {'both_ends': True} if args.both_ends else {}
+        vcf_list, rec_hash = vcf_list_readin(args.sv_input, ref if args.bnd else None, **opt)
         rec_new = SF.vcf_rec_hash_modify(rec_hash)
         jobs = vcf_jobs(vcf_list, num_reads_cff, bam_in, ref, out_path, sample_name, refine,
-                        vcf_ci_readin(args.sv_input) if refine is not None else None, args.phased)
-        scores = score_jobs(jobs, args.chunk, figure_fn, refine, args.phased)
+                        vcf_ci_readin(args.sv_input) if refine is not None else None, args.phased, **opt)
+        scores = score_jobs(jobs, args.chunk, figure_fn, refine, args.phased, **opt)
         if vdist.rank() == 0:
             SF.write_output_initiate(args.sv_input + '.vapor', more)
             with open(args.sv_input + '.vapor', 'a') as fo:
@@ -822,11 +933,15 @@ def main(argv: Optional[List[str]] = None) -> int:
                     lines = [l + '\t' + '\t'.join(rf.columns(j.refine)) for l, j in zip(lines, jobs)]
                 if args.phased:
                     lines = [l + '\t' + '\t'.join(c) for l, c in zip(lines, ph.columns_many([j.phase for j in jobs]))]
+                if args.both_ends:
+                    lines = [l + '\t' + '\t'.join(c) for l, c in zip(lines, be.columns_many([j.views for j in jobs]))]
                 fo.write(''.join([l + '\n' for l in lines]))
             if refine is not None:
                 SF.vcf_vapor_modify(args.sv_input, rec_new, refined=True)
             elif args.phased:
                 SF.vcf_vapor_modify(args.sv_input, rec_new, phased=True)
+            elif args.both_ends:
+                SF.vcf_vapor_modify(args.sv_input, rec_new, both_ends=True)
             else:
                 SF.vcf_vapor_modify(args.sv_input, rec_new)
     elif mode == 'svelter':

@@ -327,7 +327,7 @@ done:
 // buffer size); a file that breaks a rule is VAPOR_E_ARG with a message, never a read or write outside `comp` / `data`.
 static int bam_chop_impl(vapor_bam* b, int32_t tid, int64_t start, int64_t end, int64_t flank, int32_t n_chunks,
                          const uint64_t* chunks, uint8_t* seq_out, int64_t seq_cap, char* names_out, int64_t names_cap,
-                         int64_t* meta, int32_t max_reads, int32_t* n_reads, int64_t* need, int meta_w = 4)
+                         int64_t* meta, int32_t max_reads, int32_t* n_reads, int64_t* need, int meta_w = 4, bool right = false)
 {
     if (!b || !n_reads || (n_chunks && !chunks)) return bfail(VAPOR_E_ARG, "vapor_bam_chop: null argument");
     if (seq_cap < 0 || names_cap < 0 || max_reads < 0 || (max_reads && (!meta || !seq_out || !names_out)))
@@ -414,6 +414,32 @@ static int bam_chop_impl(vapor_bam* b, int32_t tid, int64_t start, int64_t end, 
                 if (code == 0 || code == 2 || code == 3 || code == 7 || code == 8) rlen += o >> 4;
             }
             if ((int64_t)pos + std::max<int64_t>(rlen, 1) <= beg) continue;
+            int64_t q0, miss;
+            if (right) {
+                // the right-anchored chop (vapor_chop_records_right is the statement): alignments whose last reference base is
+                // at or behind the window end, walked from the far end of the CIGAR; q0 = bases dropped from the read's end
+                int64_t span = 0;
+                for (int32_t t = 0; t < n_ops; ++t) {
+                    const uint32_t o = (uint32_t)rd32(ops + 4 * t), code = o & 15u;
+                    if (code == 0u || code == 7u || code == 2u) span += o >> 4;
+                }
+                const int64_t last_ref = (int64_t)pos + span;                     // 1-based
+                if (!(last_ref >= end)) continue;
+                if (n_ops <= 0) return bfail(VAPOR_E_ARG, "vapor_bam_chop: record without CIGAR (the reference raises IndexError, SF:331)");
+                int64_t q = 0, c = last_ref;
+                uint32_t last = 0;
+                for (int32_t t = n_ops; t-- > 0;) {
+                    const uint32_t o = (uint32_t)rd32(ops + 4 * t);
+                    const int64_t n = o >> 4;
+                    last = o & 15u;
+                    if (last == 4u || last == 1u) q += n;
+                    else if (last == 0u || last == 7u) { q += n; c -= n; }
+                    else if (last == 2u) c -= n;
+                    if (c < end + 1) break;
+                }
+                const int64_t over = end - c;
+                if (last == 0u || last == 7u) { q0 = q - over; miss = 0; } else { q0 = q; miss = over; }
+            } else {
             // chop_pacbio_read_by_pos: only alignments that start at or before the window start
             if (!((int64_t)pos + 1 < start + 1)) continue;
             if (n_ops <= 0) return bfail(VAPOR_E_ARG, "vapor_bam_chop: record without CIGAR (the reference raises IndexError, SF:331)");
@@ -429,8 +455,8 @@ static int bam_chop_impl(vapor_bam* b, int32_t tid, int64_t start, int64_t end, 
                 if (rr > start - 1) break;
             }
             const int64_t over = rr - start;
-            int64_t q0, miss;
             if (last == 0u || last == 7u) { q0 = q - over; miss = 0; } else { q0 = q; miss = over; }
+            }
             if (2 * miss > flank) continue;                                   // miss_bp > flank_length / 2
             const int64_t seq_len = l_seq > 0 ? l_seq : 1;                    // an absent sequence reads "*"
             const int64_t tail = q0 < seq_len ? seq_len - std::max<int64_t>(q0, 0) : 0;
@@ -444,7 +470,16 @@ static int bam_chop_impl(vapor_bam* b, int32_t tid, int64_t start, int64_t end, 
                 continue;
             }
             uint8_t* dst = seq_out + seq_used;
-            if (l_seq > 0) {
+            if (right && l_seq > 0) {
+                // the want_len bases that end before the dropped ones, last base first, complemented ("=ACMGRSVTWYHKDBN" with the
+                // nibble's bits reversed)
+                static const char* NT16_RC = "=TGKCYSBAWRDMHVN";
+                int64_t i = (int64_t)l_seq - q0 - 1;
+                for (int64_t t = 0; t < want_len; ++t, --i) {
+                    const uint8_t byte = sq[i >> 1];
+                    dst[t] = (uint8_t)NT16_RC[(i & 1) ? (byte & 15) : (byte >> 4)];
+                }
+            } else if (l_seq > 0) {
                 int64_t t = 0, i = q0;
                 if ((i & 1) && t < want_len) { dst[t++] = (uint8_t)NT16[sq[i >> 1] & 15]; ++i; }
                 for (; t + 2 <= want_len; t += 2, i += 2) {              // two bases a byte
@@ -481,6 +516,21 @@ extern "C" int vapor_bam_chop(vapor_bam* b, int32_t tid, int64_t start, int64_t 
         return bfail(VAPOR_E_NOMEM, "vapor_bam_chop: out of memory");
     } catch (const std::exception& e) {
         return bfail(VAPOR_E_ARG, std::string("vapor_bam_chop: ") + e.what());
+    }
+}
+
+// vapor_bam_chop for the right-anchored reads of the window (`--both-ends`): the same outputs, every read the
+// reverse complement of its part that ends on the window end, miss_bp counted from there.
+extern "C" int vapor_bam_chop_right(vapor_bam* b, int32_t tid, int64_t start, int64_t end, int64_t flank, int32_t n_chunks,
+                                    const uint64_t* chunks, uint8_t* seq_out, int64_t seq_cap, char* names_out, int64_t names_cap,
+                                    int64_t* meta, int32_t max_reads, int32_t* n_reads, int64_t* need)
+{
+    try {
+        return bam_chop_impl(b, tid, start, end, flank, n_chunks, chunks, seq_out, seq_cap, names_out, names_cap, meta, max_reads, n_reads, need, 4, true);
+    } catch (const std::bad_alloc&) {
+        return bfail(VAPOR_E_NOMEM, "vapor_bam_chop_right: out of memory");
+    } catch (const std::exception& e) {
+        return bfail(VAPOR_E_ARG, std::string("vapor_bam_chop_right: ") + e.what());
     }
 }
 
@@ -548,6 +598,66 @@ extern "C" int vapor_chop_records(int32_t n, const int64_t* pos, const int64_t* 
     return VAPOR_OK;
 }
 
+// The right-anchored chop (`--both-ends`; not in the reference): vapor_chop_records of the records as the
+// reverse-complemented contig holds them, in closed form.  An alignment qualifies when its last reference base (pos + the M, =
+// and D operations - 1) is >= end; the walk goes from the far end of the CIGAR, the cursor moving left from that base, to the
+// first operation after which it is <= end.  q1_miss[2r] = read bases to drop from the END of the read, q1_miss[2r + 1] = miss_bp
+// counted from the window end; the kept read is the reverse complement of the end - start - miss_bp bases before the dropped
+// ones.  A window shorter than its miss_bp keeps nothing here (callers leave such a window to the Python statement).
+extern "C" int vapor_chop_records_right(int32_t n, const int64_t* pos, const int64_t* ref_span, const char* const* cigar,
+                                        const int64_t* seq_len, int64_t start, int64_t end, int64_t flank,
+                                        int64_t* q1_miss, uint8_t* keep)
+{
+    if (n < 0 || (n && (!pos || !ref_span || !cigar || !seq_len || !q1_miss || !keep)))
+        return bfail(VAPOR_E_ARG, "vapor_chop_records_right: null argument");
+    try {
+        std::vector<std::pair<int64_t, char>> ops;
+        for (int32_t r = 0; r < n; ++r) {
+            keep[r] = 0;
+            if (!(pos[r] <= end && pos[r] + ref_span[r] - 1 >= start)) continue;      // not in the region
+            ops.clear();
+            int64_t num = 0, span = 0;
+            bool have_n = false;
+            for (const char* c = cigar[r] ? cigar[r] : ""; *c; ++c) {
+                const char ch = *c;
+                if (ch >= '0' && ch <= '9') { num = num * 10 + (ch - '0'); have_n = true; continue; }
+                const bool op = ch == 'M' || ch == 'I' || ch == 'D' || ch == 'N' || ch == 'S' || ch == 'H' || ch == 'P' || ch == '=' || ch == 'X';
+                if (op && have_n) {
+                    ops.emplace_back(num, ch);
+                    if (ch == 'M' || ch == '=' || ch == 'D') span += num;
+                }
+                num = 0; have_n = false;
+            }
+            const int64_t last_ref = pos[r] + span - 1;
+            if (!(last_ref >= end)) continue;
+            if (ops.empty()) return bfail(VAPOR_E_ARG, "vapor_chop_records_right: record without CIGAR (the reference raises IndexError, SF:331)");
+            int64_t q = 0, c = last_ref;
+            char last = 0;
+            for (size_t t = ops.size(); t-- > 0;) {
+                const int64_t m = ops[t].first;
+                last = ops[t].second;
+                if (last == 'S' || last == 'I') q += m;
+                else if (last == 'M' || last == '=') { q += m; c -= m; }
+                else if (last == 'D') c -= m;
+                if (c < end + 1) break;
+            }
+            const int64_t over = end - c;
+            int64_t q1, miss;
+            if (last == 'M' || last == '=') { q1 = q - over; miss = 0; } else { q1 = q; miss = over; }
+            if (2 * miss > flank) continue;
+            const int64_t want = end - start - miss;
+            const int64_t head = std::max<int64_t>(seq_len[r] - q1, 0);
+            if (want < 0 || q1 < 0 || !(head > want)) continue;
+            keep[r] = 1;
+            q1_miss[2 * r] = q1;
+            q1_miss[2 * r + 1] = miss;
+        }
+    } catch (const std::bad_alloc&) {
+        return bfail(VAPOR_E_NOMEM, "vapor_chop_records_right: out of memory");
+    }
+    return VAPOR_OK;
+}
+
 // chop_pacbio_read_by_pos (SF:339-354) and minimize_pacbio_read_list (SF:1091-1102: at most `max_keep` reads, smallest miss_bp
 // first, input order inside one miss_bp value) for MANY regions in one call: region g looks at n_rec[g] records given as the
 // arrays of vapor_chop_records (one pointer per region), keeps what that call keeps and, when there are more than max_keep,
@@ -555,12 +665,14 @@ extern "C" int vapor_chop_records(int32_t n, const int64_t* pos, const int64_t* 
 // (capacity max_keep per region); addr_out (may be NULL) receives seq_addr[g][record] for every kept read - where the caller
 // keeps the records' sequences.  status[g] = 0, or VAPOR_E_ARG where a record without CIGAR reaches the walk (the reference
 // raises IndexError there, SF:331: the caller lets that region take the reference-named route).
-extern "C" int vapor_chop_records_many(int32_t n_regions, const int32_t* n_rec, const int64_t* const* pos,
-                                       const int64_t* const* ref_span, const char* const* const* cigar,
-                                       const int64_t* const* seq_len, const int64_t* start, const int64_t* end,
-                                       const int64_t* flank, int32_t max_keep, int32_t* kept_first, int32_t* rec_idx,
-                                       int64_t* q0, int64_t* miss, int32_t* status, const uint64_t* const* seq_addr,
-                                       uint64_t* addr_out)
+typedef int (*chop_records_fn)(int32_t, const int64_t*, const int64_t*, const char* const*, const int64_t*, int64_t, int64_t, int64_t,
+                               int64_t*, uint8_t*);
+static int chop_records_many_impl(chop_records_fn chop_one, int32_t n_regions, const int32_t* n_rec, const int64_t* const* pos,
+                                  const int64_t* const* ref_span, const char* const* const* cigar,
+                                  const int64_t* const* seq_len, const int64_t* start, const int64_t* end,
+                                  const int64_t* flank, int32_t max_keep, int32_t* kept_first, int32_t* rec_idx,
+                                  int64_t* q0, int64_t* miss, int32_t* status, const uint64_t* const* seq_addr,
+                                  uint64_t* addr_out)
 {
     if (n_regions < 0 || max_keep < 1 || (n_regions && (!n_rec || !pos || !ref_span || !cigar || !seq_len || !start || !end || !flank ||
                                                            !kept_first || !rec_idx || !q0 || !miss || !status)))
@@ -578,7 +690,7 @@ extern "C" int vapor_chop_records_many(int32_t n_regions, const int32_t* n_rec, 
             if (n <= 0) continue;
             qm.resize((size_t)2 * n);
             keep.resize((size_t)n);
-            if (vapor_chop_records(n, pos[g], ref_span[g], cigar[g], seq_len[g], start[g], end[g], flank[g], qm.data(), keep.data()) != VAPOR_OK) {
+            if (chop_one(n, pos[g], ref_span[g], cigar[g], seq_len[g], start[g], end[g], flank[g], qm.data(), keep.data()) != VAPOR_OK) {
                 status[g] = VAPOR_E_ARG;
                 continue;
             }
@@ -618,6 +730,29 @@ extern "C" int vapor_chop_records_many(int32_t n_regions, const int32_t* n_rec, 
     }
     kept_first[n_regions] = w;
     return VAPOR_OK;
+}
+
+extern "C" int vapor_chop_records_many(int32_t n_regions, const int32_t* n_rec, const int64_t* const* pos,
+                                       const int64_t* const* ref_span, const char* const* const* cigar,
+                                       const int64_t* const* seq_len, const int64_t* start, const int64_t* end,
+                                       const int64_t* flank, int32_t max_keep, int32_t* kept_first, int32_t* rec_idx,
+                                       int64_t* q0, int64_t* miss, int32_t* status, const uint64_t* const* seq_addr,
+                                       uint64_t* addr_out)
+{
+    return chop_records_many_impl(vapor_chop_records, n_regions, n_rec, pos, ref_span, cigar, seq_len, start, end, flank, max_keep, kept_first,
+                                  rec_idx, q0, miss, status, seq_addr, addr_out);
+}
+
+// vapor_chop_records_many over the right-anchored chop (vapor_chop_records_right): q1[] = bases to drop from the read's end.
+extern "C" int vapor_chop_records_right_many(int32_t n_regions, const int32_t* n_rec, const int64_t* const* pos,
+                                             const int64_t* const* ref_span, const char* const* const* cigar,
+                                             const int64_t* const* seq_len, const int64_t* start, const int64_t* end,
+                                             const int64_t* flank, int32_t max_keep, int32_t* kept_first, int32_t* rec_idx,
+                                             int64_t* q1, int64_t* miss, int32_t* status, const uint64_t* const* seq_addr,
+                                             uint64_t* addr_out)
+{
+    return chop_records_many_impl(vapor_chop_records_right, n_regions, n_rec, pos, ref_span, cigar, seq_len, start, end, flank, max_keep,
+                                  kept_first, rec_idx, q1, miss, status, seq_addr, addr_out);
 }
 
 // The row tails of a whole table in one call (no device): what result_organize_ins (SF:1219-1231) and
@@ -796,4 +931,12 @@ extern "C" __attribute__((weak)) int vapor_bam_chop_device_tagged(vapor_ctx*, va
                                                                   int64_t*, int64_t*, uint32_t*, int64_t*, int32_t*, int32_t*, vapor_bam_batch**)
 {
     return bfail(VAPOR_E_ARG, "vapor_bam_chop_device_tagged: this build has no device reader");
+}
+
+// ... and so is the right-anchored one (vapor_bam_chop_device_right: bam_chop_right_kernel).
+extern "C" __attribute__((weak)) int vapor_bam_chop_device_right(vapor_ctx*, vapor_bam*, int32_t, const int32_t*, const int64_t*, const int64_t*,
+                                                                 const int64_t*, const int32_t*, const uint64_t*, int32_t, int32_t*, uint64_t*,
+                                                                 int64_t*, int64_t*, int32_t*, vapor_bam_batch**)
+{
+    return bfail(VAPOR_E_ARG, "vapor_bam_chop_device_right: this build has no device reader");
 }

@@ -978,8 +978,12 @@ __device__ __forceinline__ bool walk_aux_dev(const uint8_t* arena, uint32_t p, u
 
 // One wavefront per region (vapor_bam.cpp bam_chop_impl is the statement this follows, line for line in its decisions).  TAGGED:
 // every kept record's HP and PS go to tags[] beside its BamKept entry; a record whose aux area is malformed sends the region to
-// the host route (REG_MALFORMED).  The unphased instantiation holds none of it.
-template <bool TAGGED>
+// the host route (REG_MALFORMED).  The unphased instantiation holds none of it.  RIGHT (`--both-ends`; the
+// right-anchored branch of bam_chop_impl is its statement): the alignments whose last reference base is at or behind the window
+// end, their CIGAR walked from its far end - a first pass over the operations for the reference length, a second over the tiles in
+// reverse, lane l on operation n_ops - 1 - (t0 + l), so that the inclusive scans are suffix sums.  The entry's q0 is then the read
+// base the reverse-complemented read starts with (l_seq - 1 - the bases dropped from the read's end), miss counts from the end.
+template <bool TAGGED, bool RIGHT = false>
 __device__ __forceinline__ void bam_chop_body(const uint8_t* __restrict__ arena, const BamRegion* __restrict__ regs,
                                               const BamSpan* __restrict__ spans, const int32_t* __restrict__ blk_status, int n_regs,
                                               BamKept* __restrict__ kept, int32_t* __restrict__ n_kept, int32_t* __restrict__ reg_status,
@@ -1018,7 +1022,7 @@ __device__ __forceinline__ void bam_chop_body(const uint8_t* __restrict__ arena,
             }
             // chop_pacbio_read_by_pos: only alignments that start at or before the window start (decided before the CIGAR is
             // read: the region rule below only skips)
-            if (!((long long)pos < start)) continue;
+            if (!RIGHT && !((long long)pos < start)) continue;
             const uint32_t cig = r + 32u + (uint32_t)l_name;
             const uint32_t sq = cig + 4u * (uint32_t)n_cig;
             const uint32_t rec_end = r + (uint32_t)bs;
@@ -1049,6 +1053,47 @@ __device__ __forceinline__ void bam_chop_body(const uint8_t* __restrict__ arena,
             long long r1 = 0, rr = (long long)pos + 1, q = 0;
             bool r1_over = false, walked = false;
             uint32_t last = 0;
+            if constexpr (RIGHT) {
+                long long span = 0;
+                for (int32_t t0 = 0; t0 < n_ops; t0 += 64) {
+                    const int32_t t = t0 + (int32_t)lane;
+                    const bool valid = t < n_ops;
+                    const uint32_t o = valid ? rd32u(arena + ops + 4u * (uint32_t)t) : 15u;
+                    const uint32_t code = o & 15u;
+                    const long long n = (long long)(o >> 4);
+                    const long long a = (code == 0u || code == 2u || code == 3u || code == 7u || code == 8u) ? n : 0;
+                    const long long b = (code == 0u || code == 7u || code == 2u) ? n : 0;
+                    const long long A = wave_scan64(a, lane), B = wave_scan64(b, lane);
+                    if (!r1_over) {
+                        if (__any(valid && (long long)pos + r1 + A > beg)) r1_over = true;
+                        r1 += __shfl(A, 63);
+                    }
+                    span += __shfl(B, 63);
+                }
+                if (!r1_over && (long long)pos + (r1 > 1 ? r1 : 1) <= beg) continue;
+                const long long last_ref = (long long)pos + span;                 // 1-based
+                if (!(last_ref >= end)) continue;
+                if (n_ops <= 0) { st = REG_NO_CIGAR; break; }
+                long long back = 0;                                               // reference bases walked from the far end
+                for (int32_t t0 = 0; t0 < n_ops && !walked; t0 += 64) {
+                    const int32_t t = n_ops - 1 - (t0 + (int32_t)lane);
+                    const bool valid = t >= 0;
+                    const uint32_t o = valid ? rd32u(arena + ops + 4u * (uint32_t)t) : 15u;
+                    const uint32_t code = o & 15u;
+                    const long long n = (long long)(o >> 4);
+                    const long long b = (code == 0u || code == 7u || code == 2u) ? n : 0;
+                    const long long c = (code == 4u || code == 1u || code == 0u || code == 7u) ? n : 0;
+                    const long long B = wave_scan64(b, lane), C = wave_scan64(c, lane);
+                    const unsigned long long m = __ballot(valid && last_ref - (back + B) < end + 1);
+                    int f;
+                    if (m) { f = __ffsll((long long)m) - 1; walked = true; }
+                    else f = (n_ops - t0 > 64 ? 64 : n_ops - t0) - 1;            // (the tile's last operation)
+                    last = __shfl(code, f);
+                    q += __shfl(C, f);
+                    back += __shfl(B, f);
+                }
+                rr = last_ref - back;                                             // the cursor: over = end - cursor
+            } else
             for (int32_t t0 = 0; t0 < n_ops && !(r1_over && walked); t0 += 64) {
                 const int32_t t = t0 + (int32_t)lane;
                 const bool valid = t < n_ops;
@@ -1076,7 +1121,7 @@ __device__ __forceinline__ void bam_chop_body(const uint8_t* __restrict__ arena,
             // the region rule of `samtools view`
             if (!r1_over && (long long)pos + (r1 > 1 ? r1 : 1) <= beg) continue;
             if (n_ops <= 0) { st = REG_NO_CIGAR; break; }
-            const long long over = rr - start;
+            const long long over = RIGHT ? end - rr : rr - start;
             long long q0, miss;
             if (last == 0u || last == 7u) { q0 = q - over; miss = 0; } else { q0 = q; miss = over; }
             if (2 * miss > R.flank) continue;                                   // miss_bp > flank_length / 2
@@ -1095,7 +1140,7 @@ __device__ __forceinline__ void bam_chop_body(const uint8_t* __restrict__ arena,
                 }
                 if (lane == 0) tags[(size_t)g * KEPT_CAP + (size_t)nk] = BamTag{ps, hap, 0};
             }
-            if (lane == 0) kept[(size_t)g * KEPT_CAP + (size_t)nk] = BamKept{sq, (int32_t)q0, (int32_t)miss, l_seq};
+            if (lane == 0) kept[(size_t)g * KEPT_CAP + (size_t)nk] = BamKept{sq, (int32_t)(RIGHT ? (long long)l_seq - 1 - q0 : q0), (int32_t)miss, l_seq};
             ++nk;
         }
     }
@@ -1107,6 +1152,13 @@ __global__ __launch_bounds__(64) void bam_chop_kernel(const uint8_t* __restrict_
                                                      BamKept* __restrict__ kept, int32_t* __restrict__ n_kept, int32_t* __restrict__ reg_status)
 {
     bam_chop_body<false>(arena, regs, spans, blk_status, n_regs, kept, n_kept, reg_status, nullptr);
+}
+
+__global__ __launch_bounds__(64) void bam_chop_right_kernel(const uint8_t* __restrict__ arena, const BamRegion* __restrict__ regs,
+                                                           const BamSpan* __restrict__ spans, const int32_t* __restrict__ blk_status, int n_regs,
+                                                           BamKept* __restrict__ kept, int32_t* __restrict__ n_kept, int32_t* __restrict__ reg_status)
+{
+    bam_chop_body<false, true>(arena, regs, spans, blk_status, n_regs, kept, n_kept, reg_status, nullptr);
 }
 
 __global__ __launch_bounds__(64) void bam_chop_tagged_kernel(const uint8_t* __restrict__ arena, const BamRegion* __restrict__ regs,
@@ -1213,7 +1265,8 @@ __global__ __launch_bounds__(64) void bam_select_kernel(const BamKept* __restric
 // The bases of device-held reads (4 bits each, BAM's "=ACMGRSVTWYHKDBN") into the ASCII staging layout of pack_kernel: one
 // thread per 32-byte chunk.  src[s] = 0 for a sequence that came from the host; else the address of its packed bases, first[s]
 // its first base.  chunk_seq as pack_kernel reads it; seq_words = the sequence descriptors pack_kernel reads (vapor::SeqDesc,
-// eight words each: word 1 the length, word 4 the first ASCII chunk).
+// eight words each: word 1 the length, word 4 the first ASCII chunk).  A source with bit 63 of its address set (src_kind 2) is
+// taken reverse complemented: base t of the sequence is the complement of base first[s] - t - the nibble with its bits reversed.
 __global__ __launch_bounds__(256) void bam_expand_kernel(uint8_t* __restrict__ ascii, const uint32_t* __restrict__ chunk_seq, uint32_t n_chunks,
                                                         const uint32_t* __restrict__ seq_words,
                                                         const unsigned long long* __restrict__ src, const int32_t* __restrict__ first)
@@ -1221,18 +1274,21 @@ __global__ __launch_bounds__(256) void bam_expand_kernel(uint8_t* __restrict__ a
     const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= n_chunks) return;
     const uint32_t s = chunk_seq[c];
-    const unsigned long long a = src[s];
-    if (!a) return;
+    const unsigned long long a0 = src[s];
+    if (!a0) return;
+    const bool rc = (a0 >> 63) != 0ull;
+    const unsigned long long a = a0 & 0x7FFFFFFFFFFFFFFFull;
     const uint8_t* sq = reinterpret_cast<const uint8_t*>(a);
     const int base = (int)(c - seq_words[8u * s + 4u]) * 32;
     int valid = (int)seq_words[8u * s + 1u] - base;
     if (valid > 32) valid = 32;
-    const long long i0 = (long long)first[s] + base;
+    const long long i0 = rc ? (long long)first[s] - base : (long long)first[s] + base;
     uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     for (int t = 0; t < valid; ++t) {
-        const long long i = i0 + t;
+        const long long i = rc ? i0 - t : i0 + t;
         const uint32_t byte = sq[i >> 1];
-        const uint32_t nib = (i & 1) ? (byte & 15u) : (byte >> 4);
+        uint32_t nib = (i & 1) ? (byte & 15u) : (byte >> 4);
+        if (rc) nib = __brev(nib) >> 28;
         const uint32_t ch = (uint32_t)(uint8_t)"=ACMGRSVTWYHKDBN"[nib];
         w[t >> 2] |= ch << ((t & 3) * 8);
     }

@@ -749,7 +749,8 @@ static int seqset_create_impl(vapor_ctx* ctx, int32_t n_seqs, SRC src, const int
             unsigned long long* h_src = reinterpret_cast<unsigned long long*>(ctx->h_stage + mix_off);
             int32_t* h_first = reinterpret_cast<int32_t*>(ctx->h_stage + mix_off + (size_t)n_seqs * 8);
             for (int32_t i = 0; i < n_seqs; ++i) {
-                h_src[i] = src_kind[i] ? (unsigned long long)reinterpret_cast<uintptr_t>(src(i)) : 0ull;
+                // (src_kind 2: the source reverse complemented from base src_first downwards - bit 63 tells bam_expand_kernel)
+                h_src[i] = src_kind[i] ? (unsigned long long)reinterpret_cast<uintptr_t>(src(i)) | (src_kind[i] == 2 ? 1ull << 63 : 0ull) : 0ull;
                 h_first[i] = src_kind[i] ? (int32_t)src_first[i] : 0;
             }
             if (host_end) HIPCHK(hipMemcpyAsync(d_asc, h_asc, host_end * 32, hipMemcpyHostToDevice, ctx->stream));
@@ -1057,7 +1058,8 @@ static hipError_t crc_pow_on_device(vapor_ctx* ctx)
 static int bam_chop_device_impl(vapor_ctx* ctx, vapor_bam* bam, int32_t n_regions, const int32_t* tid, const int64_t* start,
                                 const int64_t* end, const int64_t* flank, const int32_t* chunk_first, const uint64_t* chunks,
                                 int32_t max_keep, int32_t* kept_first, uint64_t* sq_addr, int64_t* q0, int64_t* miss,
-                                int32_t* status, vapor_bam_batch** out, uint32_t* member, int64_t* phase_set, int32_t* tagged)
+                                int32_t* status, vapor_bam_batch** out, uint32_t* member, int64_t* phase_set, int32_t* tagged,
+                                bool right = false)
 {
     using namespace vapor_bamdev;
     const bool phased = member != nullptr;
@@ -1245,6 +1247,11 @@ static int bam_chop_device_impl(vapor_ctx* ctx, vapor_bam* bam, int32_t n_region
                                reinterpret_cast<const int32_t*>(d_meta + o_rst), (int)n_regions, (int)max_keep,
                                reinterpret_cast<BamPick*>(d_meta + o_picks), reinterpret_cast<BamPhase*>(d_meta + o_phase));
             HIPCHK(hipGetLastError());
+        } else if (n_regions && right) {
+            hipLaunchKernelGGL(bam_chop_right_kernel, dim3((unsigned)n_regions), dim3(64), 0, st, B->d_arena, reinterpret_cast<const BamRegion*>(d_meta + o_reg),
+                               reinterpret_cast<const BamSpan*>(d_meta + o_span), reinterpret_cast<const int32_t*>(d_meta + o_bst), (int)n_regions,
+                               reinterpret_cast<BamKept*>(d_meta + o_kept), reinterpret_cast<int32_t*>(d_meta + o_nk), reinterpret_cast<int32_t*>(d_meta + o_rst));
+            HIPCHK(hipGetLastError());
         } else if (n_regions) {
             hipLaunchKernelGGL(bam_chop_kernel, dim3((unsigned)n_regions), dim3(64), 0, st, B->d_arena, reinterpret_cast<const BamRegion*>(d_meta + o_reg),
                                reinterpret_cast<const BamSpan*>(d_meta + o_span), reinterpret_cast<const int32_t*>(d_meta + o_bst), (int)n_regions,
@@ -1346,6 +1353,18 @@ extern "C" int vapor_bam_chop_device(vapor_ctx* ctx, vapor_bam* bam, int32_t n_r
 {
     return bam_chop_device_impl(ctx, bam, n_regions, tid, start, end, flank, chunk_first, chunks, max_keep, kept_first, sq_addr, q0, miss,
                                 status, out, nullptr, nullptr, nullptr);
+}
+
+// vapor_bam_chop_device for the right-anchored reads of every region (`--both-ends`, DESIGN.md 4.14: bam_chop_right_kernel).
+// q1[t] = the base of read t its reverse complement starts with: with src_kind 2, vapor_seqset_create_mixed takes the read as
+// the reverse complement of the end - start - miss[t] bases that end there.
+extern "C" int vapor_bam_chop_device_right(vapor_ctx* ctx, vapor_bam* bam, int32_t n_regions, const int32_t* tid, const int64_t* start,
+                                           const int64_t* end, const int64_t* flank, const int32_t* chunk_first, const uint64_t* chunks,
+                                           int32_t max_keep, int32_t* kept_first, uint64_t* sq_addr, int64_t* q1, int64_t* miss,
+                                           int32_t* status, vapor_bam_batch** out)
+{
+    return bam_chop_device_impl(ctx, bam, n_regions, tid, start, end, flank, chunk_first, chunks, max_keep, kept_first, sq_addr, q1, miss,
+                                status, out, nullptr, nullptr, nullptr, true);
 }
 
 extern "C" int vapor_bam_chop_device_tagged(vapor_ctx* ctx, vapor_bam* bam, int32_t n_regions, const int32_t* tid, const int64_t* start,
@@ -1657,13 +1676,15 @@ extern "C" int vapor_seqset_create_mixed(vapor_ctx* ctx, int32_t n_seqs, const u
         if (len[i] < 0) return fail(VAPOR_E_ARG, "negative sequence length");
         if (len[i] > 0 && !seq[i]) return fail(VAPOR_E_ARG, "vapor_seqset_create_mixed: null sequence");
         if (!src_kind || !src_kind[i]) continue;
-        if (src_kind[i] != 1 || !src_first || src_first[i] < 0 || src_first[i] > 0x7FFFFFF0LL)
+        if ((src_kind[i] != 1 && src_kind[i] != 2) || !src_first || src_first[i] < 0 || src_first[i] > 0x7FFFFFF0LL ||
+            (src_kind[i] == 2 && (int64_t)len[i] > src_first[i] + 1))
             return fail(VAPOR_E_ARG, "vapor_seqset_create_mixed: bad source description");
         any_dev = true;
         if (len[i] == 0) continue;
         // the bytes that will be read must lie inside the arena of a batch that is alive
-        const uint8_t* a = seq[i] + (src_first[i] >> 1);
-        const uint8_t* b = seq[i] + ((src_first[i] + len[i] - 1) >> 1);
+        const int64_t lo = src_kind[i] == 2 ? src_first[i] - len[i] + 1 : src_first[i];        // (kind 2 reads downwards)
+        const uint8_t* a = seq[i] + (lo >> 1);
+        const uint8_t* b = seq[i] + ((lo + len[i] - 1) >> 1);
         auto it = ctx->arenas.upper_bound(a);
         if (it == ctx->arenas.begin()) return fail(VAPOR_E_ARG, "vapor_seqset_create_mixed: a device source outside every live batch");
         --it;

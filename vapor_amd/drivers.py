@@ -333,6 +333,157 @@ def vapor_simple_tandup(num_reads_cff, plt_li, bam_in, ref, sv_info, out_figure_
     return scores
 
 
+# ------------------------------------------------------------------------------------------
+# `--both-ends` (not in the reference): every junction scored from both of its sides
+# ------------------------------------------------------------------------------------------
+
+def _junction_view(num_reads_cff, bam_in, ref, form, info, flank, mirror):
+    """One more view of a junction, scored the way the long branches score theirs: reads of the window anchor +- flank, the gate
+    len(reads) > num_reads_cff, _window(ref), _window(alt), Score('s2').  Returns the per-read scores, or None for a view that
+    was gated out or whose k was "Error".  form / info name the alleles by the existing long branches:
+        'del' [c, s, e]                 anchor c:s, ref R(c, s-F, s+F), alt R(c, s-F, s) + R(c, e, e+F)      (SF:1727-1745)
+        'inv' [c, s, e]                 anchor c:s, ref as above, alt ref[:F] + rc(R(c, e-F, e))              (SF:1917-1933)
+        'bnd' [A, p, B, q, CT, ins]     vapor_bnd's, CT 3to5 or 3to3
+    mirror: an R view - `info` holds coordinates of the reverse-complemented contigs, written as the NEGATIVE of the contig's
+    own (x^ = L + 1 - x with L + 1 taken as 0: L cancels).  R^(c, a, b) = rc(R(c, -b, -a)) then, and the reads are the
+    right-anchored ones of the window -anchor +- F, which come reverse complemented (seqio._chop_records)."""
+    if mirror:
+        def fetch(c, a, b):
+            return _rc(seqio.ref_seq_readin(ref, c, -b, -a))
+    else:
+        def fetch(c, a, b):
+            return seqio.ref_seq_readin(ref, c, a, b)
+    c, x = info[0], info[1]
+    if mirror:
+        reads = seqio.simple_del_chop_pacbio_read_simple_short(bam_in, [c, -x], flank, right=True)
+    else:
+        reads = seqio.simple_del_chop_pacbio_read_simple_short(bam_in, [c, x], flank)
+    if not len(reads) > num_reads_cff:
+        return None
+    ref_seq = fetch(c, x - flank, x + flank)
+    k = yield from _window(ref_seq)
+    if k == "Error":
+        return None
+    if form == "del":
+        alt_seq = _cat(_within(ref_seq, x - flank, fetch(c, x - flank, x), x - flank), (fetch(c, info[2], info[2] + flank), None, None))
+    elif form == "inv":
+        alt_seq = _cat((ref_seq, None, flank), (fetch(c, info[2] - flank, info[2]), None, None, True))
+    else:
+        b, q, ct, ins = info[2], info[3], info[4], info[5]
+        if ct == "3to5":
+            right = (fetch(b, q - 1, q - 1 + flank), None, None)
+        else:
+            right = (fetch(b, q - flank, q), None, None, True)
+        alt_seq = _cat(_within(ref_seq, x - flank, fetch(c, x - flank, x), x - flank), (ins, None, None), right)
+    k = yield from _window(alt_seq)
+    if k == "Error":
+        return None
+    res = yield Score("s2", ref_seq, alt_seq, reads, k)
+    scores: List[float] = []
+    _collect(res, reads, scores)
+    return scores
+
+
+def both_ends_views(svtype, info, flank=default_flank_length):
+    """The extra views of a locus's junction branch, in table order: (name, form, info, mirror) each, for
+    _junction_view.  svtype DEL / INV / TANDUP with info [c, s, e]; BND with info [A, p, B, q, CT, ins] (cli.bnd_view with
+    both_ends: CT may be 5to5, whose FIRST view is the locus's primary one)."""
+    if svtype == "DEL":
+        c, s, e = info[:3]
+        return [("R@e", "del", [c, -e, -s], True)]
+    if svtype == "TANDUP":
+        c, s, e = info[:3]
+        return [("R@s", "del", [c, -s, -e], True)]
+    if svtype == "INV":
+        c, s, e = info[:3]
+        return [("L@e", "bnd", [c, e, c, s, "3to3", ""], False), ("R@e", "inv", [c, -e, -s], True),
+                ("R@s", "bnd", [c, -s, c, -e, "3to3", ""], True)]
+    a, p, b, q, ct, ins = info
+    if ct == "3to5":
+        return [("R@B", "bnd", [b, -q, a, -p, "3to5", seqio.rc_read(ins)], True)]
+    if ct == "3to3":
+        return [("L@B", "bnd", [b, q, a, p, "3to3", seqio.rc_read(ins)], False)]
+    return [("R@A", "bnd", [a, -p, b, -q, "3to3", seqio.rc_read(ins)], True), ("R@B", "bnd", [b, -q, a, -p, "3to3", ins], True)]
+
+
+def both_ends_windows(svtype, info):
+    """Every read window vapor_both_ends may ask for, as (chrom, start, end, flank, right) - the windows of the type's own driver
+    (short branch and junction branch) and of the extra views - for one extraction call per chunk (seqio.prefetch_views)."""
+    out = []
+    if svtype == "BND":
+        flank = default_flank_length
+        if info[4] != "5to5":
+            out.append((info[0], info[1] - flank, info[1] + flank, flank, False))
+    else:
+        c, s, e = info[:3]
+        flank = seqio.flank_length_calculate(info)
+        if svtype == "DEL":
+            out.append((c, s - flank, s + flank, flank, False))
+        elif svtype == "INV":
+            out += [(c, s - flank, e + flank, flank, False), (c, s - flank, s + flank, flank, False)]
+        else:
+            out += [(c, s - flank, s + 2 * (e - s) + flank, flank, False), (c, e - flank, e + flank, flank, False)]
+        if svtype == "DEL" and e - s < default_max_sv_test:
+            return out
+    for _name, _form, v, mirror in both_ends_views(svtype, info, flank):
+        x = -v[1] if mirror else v[1]
+        out.append((v[0], x - flank, x + flank, flank, bool(mirror)))
+    return out
+
+
+class BothEnds(list):
+    """The score list of a locus under `--both-ends` - the primary view's, as without the option - with `views`: per scored or
+    gated view of its junction branch, in table order and the primary first, its per-read scores or None (gated out, or k
+    "Error"); None for a locus without junction branch."""
+    views = None
+
+
+def vapor_both_ends(svtype, num_reads_cff, plt_li, bam_in, ref, info, out_figure_name):
+    """`--both-ends` for a DEL, INV or TANDUP record [c, s, e] or a breakend view [A, p, B, q, CT, ins]: the type's own driver
+    runs as it is - its requests, its figure, its scores: the row's own columns -, and when it took its junction branch
+    (a DEL of 10 kb or more; an INV or TANDUP that did not score its short branch; every breakend) the extra views of that
+    junction follow (both_ends_views), none of them drawn.  A 5to5 breakend has no view in the reference's read model: its
+    primary view is its first right-anchored one."""
+    out = BothEnds()
+    seen = []
+    if svtype == "BND" and info[4] == "5to5":
+        views = both_ends_views("BND", info)
+        got = yield from _junction_view(num_reads_cff, bam_in, ref, views[0][1], views[0][2], default_flank_length, True)
+        out.extend(got or [])
+        out.views = [got]
+        for _name, form, vinfo, mirror in views[1:]:
+            out.views.append((yield from _junction_view(num_reads_cff, bam_in, ref, form, vinfo, default_flank_length, mirror)))
+        return out
+    if svtype == "BND":
+        gen = vapor_bnd(num_reads_cff, plt_li, bam_in, ref, info, out_figure_name)
+        flank = default_flank_length
+    else:
+        gen = {"DEL": vapor_simple_del, "INV": vapor_simple_inv, "TANDUP": vapor_simple_tandup}[svtype](
+            num_reads_cff, plt_li, bam_in, ref, info, out_figure_name)
+        flank = seqio.flank_length_calculate(info)
+    # the type's own driver, its Score requests noted on the way through
+    try:
+        req = next(gen)
+        while True:
+            if isinstance(req, Score):
+                seen.append(req.kind)
+            req = gen.send((yield req))
+    except StopIteration as fin:
+        scores = fin.value
+    out.extend(scores)
+    if svtype == "DEL":
+        junction = not info[2] - info[1] < default_max_sv_test
+    elif svtype == "BND":
+        junction = True
+    else:
+        junction = not [k for k in seen if k != "s2"]        # (the short branch did not score: the driver fell through, SF:1917, 1769)
+    if junction:
+        out.views = [list(scores) if "s2" in seen else None]
+        for _name, form, vinfo, mirror in both_ends_views(svtype, info, flank):
+            out.views.append((yield from _junction_view(num_reads_cff, bam_in, ref, form, vinfo, flank, mirror)))
+    return out
+
+
 _REFINE_BASE = {"DEL": vapor_simple_del, "INV": vapor_simple_inv, "TANDUP": vapor_simple_tandup}
 _REFINE_KIND = {"DEL": "del", "INV": "s1", "TANDUP": "s3"}
 

@@ -40,6 +40,20 @@ def _as_bytes(s) -> bytes:
     return s if isinstance(s, (bytes, bytearray)) else s.encode("latin-1", "replace")
 
 
+class DevRead:
+    """A read whose bases are on the device already (Engine.bam_chop_device): `addr` the device address of the record's
+    BAM-packed bases inside `batch` (kept alive by this object), `kind` 1 = the `length` bases from base `first` on, 2 = the
+    reverse complement of the `length` bases that end at `first` (a right-anchored read).  It stands where a read's text
+    stands in a Score request; a SeqSet takes it by address (vapor_seqset_create_mixed) - no base crosses the link."""
+    __slots__ = ("addr", "first", "length", "kind", "batch")
+
+    def __init__(self, addr, first, length, kind, batch):
+        self.addr, self.first, self.length, self.kind, self.batch = int(addr), int(first), int(length), int(kind), batch
+
+    def __len__(self):
+        return self.length
+
+
 class SeqSet:
     """Sequences packed on the device.  `n_exc[s]` = symbols outside upper-case ACGT,
     `n_invalid[s]` = symbols outside invert_base's alphabet after IUPAC folding."""
@@ -60,6 +74,7 @@ class SeqSet:
         size = ctypes.c_ssize_t()
         fast = (self.n > 64 and 0 < _ASCII_OFF < 256 and isinstance(seqs, (list, tuple)) and set(map(type, seqs)) == {str}
                 and all(map(str.isascii, seqs)))
+        src_kind = src_first = None           # (set when some sequences are DevRead: the set is a mixed one)
         if fast:
             # all ASCII str (the usual case): the characters of every one lie at the same offset behind the object, so the
             # pointers are id() + offset - four passes of map() instead of a ctypes call per sequence (2 200 sequences:
@@ -75,6 +90,13 @@ class SeqSet:
         else:
             ptrs = (ctypes.c_void_p * n1)()
         for t, sq in enumerate(() if fast else seqs):
+            if type(sq) is DevRead:
+                if src_kind is None:
+                    src_kind, src_first = np.zeros(n1, dtype=np.uint8), np.zeros(n1, dtype=np.int64)
+                ptrs[t] = sq.addr
+                self.lens[t] = sq.length
+                src_kind[t], src_first[t] = sq.kind, sq.first
+                continue
             if isinstance(sq, str):
                 p = _utf8(sq, ctypes.byref(size))
                 if p and size.value == len(sq):
@@ -93,8 +115,9 @@ class SeqSet:
         h = ctypes.c_void_p()
         lib = L.load()
         lens = self.lens if self.n else np.zeros(1, np.int32)
-        if derived:
-            nd = len(derived)
+        if derived or src_kind is not None:
+            nd = len(derived) if derived else 0
+            derived = derived or []
             if isinstance(derived, tuple) and len(derived) == 3 and isinstance(derived[0], np.ndarray):
                 seg_first, segs, dflags = derived                      # (already as arrays: pipeline builds them in one go)
                 nd = len(seg_first) - 1
@@ -107,9 +130,17 @@ class SeqSet:
                     for par, off, ln, rc in sg:
                         segs[w] = (par, off, ln, L.SEG_REVCOMP if rc else 0)
                         w += 1
-                dflags = np.asarray([L.SEQ_UPPER if u else 0 for _sg, u in derived], dtype=np.uint8)
-            info = np.zeros(2 * (self.n + nd), dtype=np.int32)
-            L.check(lib.vapor_seqset_create_derived(engine._ctx, self.n, ptrs, L.ptr(lens, ctypes.c_int32), L.ptr(flags, ctypes.c_uint8),
+                dflags = np.asarray([L.SEQ_UPPER if u else 0 for _sg, u in derived] or [0], dtype=np.uint8)
+            info = np.zeros(2 * max(self.n + nd, 1), dtype=np.int32)
+            if src_kind is not None:
+                L.check(lib.vapor_seqset_create_mixed(engine._ctx, self.n, ptrs, L.ptr(lens, ctypes.c_int32), L.ptr(flags, ctypes.c_uint8),
+                                                      L.ptr(src_kind, ctypes.c_uint8), src_first.ctypes.data_as(ctypes.c_void_p), nd,
+                                                      L.ptr(np.ascontiguousarray(seg_first, dtype=np.int32), ctypes.c_int32),
+                                                      np.ascontiguousarray(segs, dtype=L.SEG_DTYPE).ctypes.data_as(ctypes.c_void_p),
+                                                      L.ptr(np.ascontiguousarray(dflags, dtype=np.uint8), ctypes.c_uint8),
+                                                      L.ptr(info, ctypes.c_int32), ctypes.byref(h)))
+            else:
+                L.check(lib.vapor_seqset_create_derived(engine._ctx, self.n, ptrs, L.ptr(lens, ctypes.c_int32), L.ptr(flags, ctypes.c_uint8),
                                                     nd, L.ptr(np.ascontiguousarray(seg_first, dtype=np.int32), ctypes.c_int32),
                                                     np.ascontiguousarray(segs, dtype=L.SEG_DTYPE).ctypes.data_as(ctypes.c_void_p),
                                                     L.ptr(np.ascontiguousarray(dflags, dtype=np.uint8), ctypes.c_uint8),
@@ -133,7 +164,9 @@ class SeqSet:
         alive (`keepalive`) until this returns: a read is a slice of its record's sequence, a window a slice of its contig;
         nothing is copied on the Python side.  `derived` as (seg_first, segs, flags) arrays.  `src_kind` (uint8 per sequence;
         vapor_seqset_create_mixed): 1 where `addr` is the DEVICE address of BAM-packed bases inside a live BamBatch and the
-        sequence the `lens` bases from base `src_first` on (Engine.bam_chop_device's reads); those never cross the link."""
+        sequence the `lens` bases from base `src_first` on (Engine.bam_chop_device's reads); those never cross the link.  2: such
+        a source taken reverse complemented - the complement of base `src_first`, then of the bases before it (its
+        right-anchored reads)."""
         self = cls.__new__(cls)
         self.engine = engine
         self.n_lit = self.n = int(len(addr))
@@ -363,13 +396,19 @@ class Engine:
     def seqset(self, seqs: Sequence, upper: Optional[Sequence[bool]] = None, derived=None) -> SeqSet:
         return SeqSet(self, seqs, upper, derived)
 
-    def bam_chop_device(self, native_bam, tids, starts, ends, flanks, chunk_first, chunks, max_keep: int = 20, tagged: bool = False):
+    def bam_chop_device(self, native_bam, tids, starts, ends, flanks, chunk_first, chunks, max_keep: int = 20, tagged: bool = False,
+                        right: bool = False):
         """vapor_bam_chop_device: the read selection of many regions of an open BAM file on the device.  Returns (kept_first,
         device addresses of the kept reads' packed bases, q0, miss_bp, status per region, BamBatch); the batch owns the data the
         addresses point into - close it after the sequence sets made from them.  tagged (`--phased`,
         vapor_bam_chop_device_tagged): the reads of a region are the union of its three group lists, and three more arrays
         follow the batch - member (uint32 per read), phase_set (int64 per region, phase.PS_NONE for none), tagged (per region);
-        NotImplementedError where the library has no such entry (the CPU twin)."""
+        NotImplementedError where the library has no such entry (the CPU twin).  right (`--both-ends`,
+        vapor_bam_chop_device_right): the right-anchored reads of every region - q0 is then the base a read's reverse complement
+        starts with (SeqSet.from_addresses: src_kind 2) and miss_bp counts from the window end."""
+        if tagged and right:
+            raise ValueError("right-anchored reads are not read with tags")
+        chop_fn = Engine._wide_entry("vapor_bam_chop_device_right", "right-anchored device reader") if right else None
         if tagged:
             tagged_fn = Engine._wide_entry("vapor_bam_chop_device_tagged", "tagged device reader")
         n = len(tids)
@@ -400,7 +439,7 @@ class Engine:
                 member.ctypes.data_as(vp), pset.ctypes.data_as(vp), tg.ctypes.data_as(vp), status.ctypes.data_as(vp), ctypes.byref(h)))
             w = int(kept_first[n])
             return kept_first, addr[:w], q0[:w], miss[:w], status[:n], BamBatch(h), member[:w], pset[:n], tg[:n]
-        L.check(L.load().vapor_bam_chop_device(self._ctx, native_bam, n, tids.ctypes.data_as(vp), starts.ctypes.data_as(vp), ends.ctypes.data_as(vp),
+        L.check((chop_fn or L.load().vapor_bam_chop_device)(self._ctx, native_bam, n, tids.ctypes.data_as(vp), starts.ctypes.data_as(vp), ends.ctypes.data_as(vp),
                                                flanks.ctypes.data_as(vp), chunk_first.ctypes.data_as(vp), chunks.ctypes.data_as(vp) if len(chunks) else None,
                                                int(max_keep), kept_first.ctypes.data_as(vp), addr.ctypes.data_as(vp), q0.ctypes.data_as(vp),
                                                miss.ctypes.data_as(vp), status.ctypes.data_as(vp), ctypes.byref(h)))

@@ -360,10 +360,17 @@ class InProcessBam(SamtoolsHybrid):
         """(QNAME, POS, CIGAR, SEQ) per alignment overlapping chrom:start-end."""
         return [r[:4] for r in self._open(bam).fetch_records(chrom, int(start), int(end))]
 
-    def chop(self, bam: str, chrom: str, start: int, end: int, flank_length: int, tagged: bool = False):
+    def chop(self, bam: str, chrom: str, start: int, end: int, flank_length: int, tagged: bool = False, right: bool = False):
         """chop_pacbio_read_by_pos (SF:339-354) straight from the BAM file: the library's native reader
         (vapor_bam_chop), or with VAPOR_BAM_NATIVE=0 the Python statement of the same steps below.  `tagged` (`--phased`):
-        every entry is [read, miss_bp, qname, hap, ps] (vapor_bam_chop_tagged; vapor_amd.phase has the tag rule)."""
+        every entry is [read, miss_bp, qname, hap, ps] (vapor_bam_chop_tagged; vapor_amd.phase has the tag rule).  `right`
+        (`--both-ends`): the right-anchored reads (vapor_bam_chop_right, or _chop_records over the records as text)."""
+        if right:
+            if not _env_is(b"VAPOR_BAM_NATIVE", b"0"):
+                from . import _lib
+                if hasattr(_lib.load(), "vapor_bam_chop_right"):
+                    return self._open(bam).chop_native(chrom, int(start), int(end), int(flank_length), right=True)
+            return _chop_records(self.records(bam, chrom, start, end), int(start), int(end), flank_length, right=True)
         if not _env_is(b"VAPOR_BAM_NATIVE", b"0"):
             return self._open(bam).chop_native(chrom, int(start), int(end), int(flank_length), tagged=tagged)
         return self.chop_python(bam, chrom, start, end, flank_length, tagged=tagged)
@@ -429,13 +436,16 @@ class InProcessBam(SamtoolsHybrid):
             return kept_first, addr, np.zeros(w, dtype=np.int64), miss_a, status, keep, np.asarray(member, dtype=np.uint32), pset, tagged
         return kept_first, addr, np.zeros(w, dtype=np.int64), miss_a, status, keep
 
-    def chop_many_device(self, engine, bam: str, chroms, starts, ends, flanks, max_keep: int = 20, groups: bool = False):
+    def chop_many_device(self, engine, bam: str, chroms, starts, ends, flanks, max_keep: int = 20, groups: bool = False,
+                         right: bool = False):
         """chop_many with the work on the device (vapor_bam_chop_device: the regions' BGZF blocks go over the link compressed,
         one wavefront inflates a block, one walks a region's records): (kept_first, DEVICE addresses of the kept reads' packed
         bases, q0 = first base of each read's part, miss, status, keepalive).  A region the device leaves to the host route
         (status != 0: a damaged block, a record without CIGAR, ...) is answered by the caller's per-locus route, which words
         the reference's errors.  groups (`--phased`): vapor_bam_chop_device_tagged - the reads of a region are the union of its
-        three group lists, selected on the device; member, phase set and tagged follow as in MemorySamtools.chop_many."""
+        three group lists, selected on the device; member, phase set and tagged follow as in MemorySamtools.chop_many.  right
+        (`--both-ends`): the right-anchored reads of every region (vapor_bam_chop_device_right) - q0 is then the base a read's
+        reverse complement starts with: such a read goes into a sequence set with src_kind 2."""
         import numpy as np
         if _env_is(b"VAPOR_BAM_NATIVE", b"0") or _env_is(b"VAPOR_BAM_DEVICE", b"0") or not hasattr(engine, "bam_chop_device"):
             raise NotImplementedError("no device reader")
@@ -444,7 +454,9 @@ class InProcessBam(SamtoolsHybrid):
         if not hasattr(lib, "vapor_bam_chop_device"):
             raise NotImplementedError("no device reader")
         phased = bool(groups)                 # (`groups` below is the list of region batches)
-        more = {"tagged": True} if phased else {}
+        more = {"tagged": True} if phased else {"right": True} if right else {}
+        if right and (phased or not hasattr(lib, "vapor_bam_chop_device_right")):
+            raise NotImplementedError("no right-anchored device reader")
         b = self._open(bam)
         n = len(chroms)
         tids = np.zeros(n, dtype=np.int32)
@@ -631,9 +643,12 @@ class MemorySamtools:
                 cache[key] = got
         return got
 
-    def chop(self, bam: str, chrom: str, start: int, end: int, flank_length, tagged: bool = False):
+    def chop(self, bam: str, chrom: str, start: int, end: int, flank_length, tagged: bool = False, right: bool = False):
         """`tagged` (`--phased`): every entry is [read, miss_bp, qname, hap, ps], the tags read from the record's SAM text
-        fields (phase.tags_from_sam)."""
+        fields (phase.tags_from_sam).  `right` (`--both-ends`): the right-anchored reads, reverse complemented - the walk in
+        the library's host helper (vapor_chop_records_right), or _chop_records itself with VAPOR_MEMORY_CHOP=records."""
+        if right:
+            return self._chop_right(chrom, int(start), int(end), flank_length)
         if tagged:
             from .phase import tags_from_sam
         if _memory_chop_by_records():
@@ -665,6 +680,28 @@ class MemorySamtools:
             out.append([r.seq[q0:q0 + (end - start - miss)] if q0 >= 0 else r.seq[q0:][:end - start - miss], miss, r.qname])
             if tagged:
                 out[-1] += list(tags_from_sam(r.tag_fields()))
+        return out
+
+    def _chop_right(self, chrom: str, start: int, end: int, flank_length):
+        from . import _lib
+        fn = None if _memory_chop_by_records() else getattr(_lib.load_holding_gil(), "vapor_chop_records_right", None)
+        if fn is None or end - start < flank_length:        # (a window shorter than its flank: Python's slice rules decide)
+            return _chop_records([(r.qname, r.pos, r.cigar, r.seq) for r in self.world.overlapping(chrom, start, end)],
+                                 start, end, flank_length, right=True)
+        recs, arrs, ptr, _keep, _n = self._arrays(chrom)
+        if not recs:
+            return []
+        import numpy as np
+        qm_a, keep_a = np.empty(2 * len(recs), dtype=np.int64), np.empty(len(recs), dtype=np.uint8)
+        if fn(len(recs), ptr[0], ptr[1], ptr[2], ptr[3], start, end, int(flank_length), qm_a.ctypes.data, keep_a.ctypes.data) != 0:
+            raise IndexError("string index out of range")
+        qm = qm_a.tolist()
+        out = []
+        for t in keep_a.nonzero()[0].tolist():
+            q1, miss = qm[2 * t], qm[2 * t + 1]
+            r = recs[t]
+            stop = len(r.seq) - q1                  # (the kept part ends here: q1 bases are dropped from the read's end)
+            out.append([rc_read(r.seq[stop - (end - start - miss):stop]), miss, r.qname])
         return out
 
     def chop_many(self, bam: str, chroms, starts, ends, flanks, max_keep: int = 20, groups: bool = False):
@@ -849,6 +886,79 @@ def _cigar2alignstart_py(cigar: str, align_start: int, start: int, end: int):
     return [q, over]
 
 
+class PrefetchedBam(str):
+    """A BAM file's name that carries reads already selected on the device: `prefetched` maps (chrom, start, end, flank, right)
+    to the window's kept reads as [engine.DevRead, miss_bp, ""] entries (prefetch_views); chop_pacbio_read_by_pos answers
+    from it, and a window that is not there - one the device left to the host route - goes the usual way."""
+    prefetched = None
+    batches = ()
+
+
+def prefetch_views(engine, bam: str, windows, max_keep: int = 20) -> PrefetchedBam:
+    """The reads of many windows - (chrom, start, end, flank, right) each - of one BAM file in two device calls
+    (InProcessBam.chop_many_device: the left-anchored windows, the right-anchored ones), under minimize_pacbio_read_list's cap.
+    Returns the file's name as a PrefetchedBam; it holds the batches the reads lie in."""
+    from .engine import DevRead
+    out = PrefetchedBam(bam)
+    out.prefetched, out.batches = {}, []
+    be = get_backend()
+    for right in (False, True):
+        ws = sorted({w for w in windows if bool(w[4]) == right and w[1] >= 0})
+        if not ws:
+            continue
+        kf, addr, q, miss, status, batches = be.chop_many_device(
+            engine, bam, [w[0] for w in ws], [w[1] for w in ws], [w[2] for w in ws], [w[3] for w in ws], max_keep,
+            **({"right": True} if right else {}))
+        out.batches += batches
+        keep = tuple(batches)
+        for g, w in enumerate(ws):
+            if status[g] == 0:
+                out.prefetched[(w[0], int(w[1]), int(w[2]), int(w[3]), right)] = [
+                    [DevRead(addr[t], q[t], w[2] - w[1] - int(miss[t]), 2 if right else 1, keep), int(miss[t]), ""]
+                    for t in range(int(kf[g]), int(kf[g + 1]))]
+    return out
+
+
+def _cigar2alignend_py(cigar: str, align_start: int, end: int):
+    """The mirror image of the walk above (`--both-ends`; not in the reference): the CIGAR walked from its far
+    end, the reference cursor starting on the alignment's last reference base (align_start + M/=/D total - 1) and moving left,
+    until it has reached `end` or passed it.  Returns [last reference base, q1 = read bases to drop from the read's END,
+    miss_bp counted from the window end] - cigar2alignstart_by_pos of the reversed operations at L + 1 - last base against
+    L + 1 - end, for any L."""
+    ops = [(int(m.group(1)), m.group(2)) for m in _CIGAR_RE.finditer(cigar)]
+    if not ops:
+        raise IndexError("string index out of range")
+    last_ref = align_start + sum(n for n, op in ops if op in "M=D") - 1
+    q = 0
+    c = last_ref
+    last = None
+    for n, op in reversed(ops):
+        if op == "S" or op == "I":
+            q += n
+        elif op == "M" or op == "=":
+            q += n
+            c -= n
+        elif op == "D":
+            c -= n
+        last = op
+        if c < end + 1:
+            break
+    over = end - c
+    if last in ("M", "="):
+        return [last_ref, q - over, 0]
+    return [last_ref, q, over]
+
+
+# BAM's 4-bit alphabet "=ACMGRSVTWYHKDBN": the complement of a symbol is its nibble with the bits reversed (= and N stay); on
+# text the same table in both letter cases, every other character as it is
+_RC_TEXT = {ord(a): b for a, b in zip("ACMGRSVTWYHKDBNacmgrsvtwyhkdbn", "TGKCYSBAWRDMHVNtgkcysbawrdmhvn")}
+
+
+def rc_read(seq: str) -> str:
+    """The reverse complement of a read's SEQ (`--both-ends`): position reversal and the table above - nothing is dropped."""
+    return seq.translate(_RC_TEXT)[::-1]
+
+
 _cigar_out = None
 _cigar_ptr = None
 _cigar_fn = None
@@ -874,11 +984,33 @@ def cigar2alignstart_by_pos(cigar: str, align_start: int, start: int, end: int):
     return [int(_cigar_out[0]), int(_cigar_out[1])]
 
 
-def chop_pacbio_read_by_pos(bam_in_new, chrom, start, end, flank_length, tagged=False):
+def chop_pacbio_read_by_pos(bam_in_new, chrom, start, end, flank_length, tagged=False, right=False):
     """SF:339-354.  `tagged` (`--phased`, not in the reference): every kept record as [read, miss_bp, qname, hap, ps], its
-    haplotype and phase set read from the HP and PS fields behind SEQ (vapor_amd.phase)."""
+    haplotype and phase set read from the HP and PS fields behind SEQ (vapor_amd.phase).  `right` (`--both-ends`, not in the
+    reference): the right-anchored reads of the window - alignments that end at or after `end` - each as the
+    reverse complement of its part that ends on the window end, miss_bp counted from there (_chop_records)."""
     out = []
     be = get_backend()
+    pre = getattr(bam_in_new, "prefetched", None)
+    if pre is not None and not tagged:
+        # (`--both-ends` from files: the reads of this window were selected on the device with the chunk's other windows)
+        got = pre.get((chrom, int(start), int(end), int(flank_length), bool(right)))
+        if got is not None:
+            return [list(x) for x in got]
+    if right:
+        if tagged:
+            raise ValueError("right-anchored reads are not read with tags")
+        if hasattr(be, "chop"):
+            return be.chop(bam_in_new, chrom, start, end, flank_length, right=True)
+        if hasattr(be, "records"):
+            recs = be.records(bam_in_new, chrom, start, end)
+        else:
+            recs = []
+            for line in be.view_lines(bam_in_new, "%s:%d-%d" % (chrom, start, end)):
+                f = line.strip().split()
+                if f and f[0] != "@":
+                    recs.append((f[0], f[3], f[5], f[9]))
+        return _chop_records(recs, start, end, flank_length, right=True)
     if hasattr(be, "chop"):
         return be.chop(bam_in_new, chrom, start, end, flank_length, tagged=True) if tagged else be.chop(bam_in_new, chrom, start, end, flank_length)
     tags = None
@@ -897,10 +1029,38 @@ def chop_pacbio_read_by_pos(bam_in_new, chrom, start, end, flank_length, tagged=
     return _chop_records(recs, start, end, flank_length, tags)
 
 
-def _chop_records(recs, start, end, flank_length, tags=None):
-    """The body of chop_pacbio_read_by_pos (SF:345-353) over (qname, pos, cigar, seq) records; tags: (hap, ps) per record, which
-    the kept ones then carry."""
+def mirror_records(recs, length):
+    """The records of a contig of `length` bases as the reverse-complemented contig holds them (x -> length + 1 - x):
+    (qname, length + 1 - last reference base, CIGAR operations reversed, rc_read(SEQ)) - the definition the right-anchored chop
+    is tested against.  The last reference base follows the cursor rule of SF:309-337 (M, = and D advance the reference)."""
     out = []
+    for qname, pos, cigar, seq in recs:
+        ops = _CIGAR_RE.findall(cigar)
+        last_ref = int(pos) + sum(int(n) for n, op in ops if op in "M=D") - 1
+        out.append((qname, length + 1 - last_ref, "".join(n + op for n, op in reversed(ops)) or cigar, rc_read(seq)))
+    return out
+
+
+def _chop_records(recs, start, end, flank_length, tags=None, right=False):
+    """The body of chop_pacbio_read_by_pos (SF:345-353) over (qname, pos, cigar, seq) records; tags: (hap, ps) per record, which
+    the kept ones then carry.  right: the closed form of _chop_records(mirror_records(recs, L), L + 1 - end, L + 1 - start,
+    flank_length) - an alignment qualifies when its last reference base is >= end, the walk goes from the far end of the CIGAR
+    (_cigar2alignend_py), and of the read without its last q1 bases the last end - start - miss_bp are kept, reverse
+    complemented, when more than that many are there."""
+    out = []
+    if right:
+        for qname, pos, cigar, seq in recs:
+            # (the M / = / D total first: only an alignment that qualifies is walked - one without operation "ends" at pos - 1
+            # and raises where the mirror would)
+            if int(pos) + sum(int(n) for n, op in _CIGAR_RE.findall(cigar) if op in "M=D") - 1 < end:
+                continue
+            last_ref, q1, miss_bp = _cigar2alignend_py(cigar, int(pos), end)
+            if not miss_bp > flank_length / 2:
+                head = seq[:max(len(seq) - q1, 0)]
+                want = end - start - miss_bp
+                if len(head) > want:
+                    out.append([rc_read(head)[:want] if want < 0 else rc_read(head[len(head) - want:]), miss_bp, qname])
+        return out
     for t, (qname, pos, cigar, seq) in enumerate(recs):
         if int(pos) < start + 1:
             q0, miss_bp = cigar2alignstart_by_pos(cigar, int(pos), start, end)
@@ -946,13 +1106,19 @@ def bam_in_decide(bam_in, bps):
             if k.split(".")[-1] == ext and all(y in k for y in keys)]
 
 
-def simple_del_chop_pacbio_read_simple_short(bam_in, sv_info, flank_length, phased=False):
+def simple_del_chop_pacbio_read_simple_short(bam_in, sv_info, flank_length, phased=False, right=False):
     """SF:1378-1390: reads around the left breakpoint only.  `phased` (`--phased`): the same list as a phase.PhasedReads, with
-    the lists of the two haplotype groups beside it (phase.select over the kept records of all files, before the cap)."""
+    the lists of the two haplotype groups beside it (phase.select over the kept records of all files, before the cap).
+    `right` (`--both-ends`): the right-anchored reads of the same window (chop_pacbio_read_by_pos), under the same cap."""
     bams = bam_in_decide(bam_in, sv_info)
     if bams == "":
         return [[], [], []]
     x = []
+    if right:
+        for b in bams:
+            x += chop_pacbio_read_by_pos(b, sv_info[0], int(sv_info[1]) - flank_length, int(sv_info[1]) + flank_length,
+                                         flank_length, right=True)
+        return minimize_pacbio_read_list(x)
     for b in bams:
         x += chop_pacbio_read_by_pos(b, sv_info[0], int(sv_info[1]) - flank_length,
                                      int(sv_info[1]) + flank_length, flank_length, *((True,) if phased else ()))

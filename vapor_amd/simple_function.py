@@ -314,7 +314,7 @@ _PHASED_INFO = (
 )
 
 
-def vcf_vapor_modify(vcf_input, vcf_rec_hash_new, header_offset_compat=False, refined=False, phased=False):
+def vcf_vapor_modify(vcf_input, vcf_rec_hash_new, header_offset_compat=False, refined=False, phased=False, both_ends=False):
     """SF:1972-2028 (the second definition, which shadows SF:1942): rewrite <vcf>.vapor as the
     input VCF with ;VaPor_GS=..;VaPor_GT=..;VaPor_GQ=..;VaPor_REC=.. appended to INFO of every
     scored record.
@@ -327,7 +327,10 @@ def vcf_vapor_modify(vcf_input, vcf_rec_hash_new, header_offset_compat=False, re
     the reference's shifted lookup.  refined (`--refine`): the rows of <vcf>.vapor carry four more fields - the refined
     breakpoints and candidate 0's QS and GS - which follow as ;VaPor_RPOS=..;VaPor_REND=..;VaPor_QS0=..;VaPor_GS0=.. ('.' for
     a record that was not refined), with ##INFO lines of their own.  phased (`--phased`): the rows carry nine more fields
-    (phase.COLUMNS), which follow under their column names; a key whose value is '.' is left out."""
+    (phase.COLUMNS), which follow under their column names; a key whose value is '.' is left out.  both_ends (`--both-ends`):
+    the rows carry seven more fields (bothends.COLUMNS), written the same way."""
+    if both_ends:
+        from .bothends import INFO as _BE_INFO
     vapor_input = vcf_input + '.vapor'
     info = {}
     meta, header = [], []
@@ -358,6 +361,8 @@ def vcf_vapor_modify(vcf_input, vcf_rec_hash_new, header_offset_compat=False, re
                         info[y][7] += ';VaPor_RPOS=%s;VaPor_REND=%s;VaPor_QS0=%s;VaPor_GS0=%s' % tuple(pin[6:10])
                     if phased:
                         info[y][7] += ''.join(';%s=%s' % (name[0], v) for name, v in zip(_PHASED_INFO, pin[6:15]) if v != '.')
+                    if both_ends:
+                        info[y][7] += ''.join(';%s=%s' % (name[0], v) for name, v in zip(_BE_INFO, pin[6:13]) if v != '.')
                     keep.append(y)
     with open(vapor_input, 'w') as fo:
         prev = ''
@@ -377,6 +382,9 @@ def vcf_vapor_modify(vcf_input, vcf_rec_hash_new, header_offset_compat=False, re
                 if phased:
                     for name, typ, text in _PHASED_INFO:
                         print('##INFO=<ID=%s,Number=%s,Type=%s,Description="%s">' % (name, '.' if name.endswith('_Rec') else '1', typ, text), file=fo)
+                if both_ends:
+                    for name, typ, num, text in _BE_INFO:
+                        print('##INFO=<ID=%s,Number=%s,Type=%s,Description="%s">' % (name, num, typ, text), file=fo)
             print(joined, file=fo)
             prev = cur
         print('\t'.join(header), file=fo)

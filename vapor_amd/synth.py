@@ -580,6 +580,11 @@ def _clipped_reads(rng, w, chrom, side, at, flank_seq, n, read_len, lead, errors
         else:
             h = min(len(flank_seq), int(rng.integers(300, 500 + lead)))
             b0 = min(at - 1 + read_len - h, len(c))
+            if from_ref:
+                a0 = max(at - 1 - h, 0)
+                read, cig = mutate(rng, c[a0:b0], *errors)
+                recs.append(SamRecord("%s_L%dr" % (tag, ri), chrom, a0 + 1, cig, read, b0 - a0))
+                continue
             rh, _ = mutate(rng, flank_seq[len(flank_seq) - h:], *errors, cigar=False)
             ra, ca = mutate(rng, c[at - 1:b0], *errors)
             recs.append(SamRecord("%s_L%da" % (tag, ri), chrom, at, ("%dS" % len(rh) if rh else "") + ca, rh + ra, b0 - at + 1))
@@ -628,6 +633,75 @@ def make_bnd_world(seed: int, forms: Sequence[str] = BND_FORMS, n_reads: int = 8
             w.reads.setdefault(c, []).sort(key=lambda r: r.pos)
         w.loci.append(Locus(ca, "BND", p, q, "bnd%d" % (li + 1), I, {"form": form, "mate_chrom": cb}))
     return w
+
+
+def make_junction_world(seed: int, svtypes: Sequence[str] = ("DEL", "INV", "TANDUP"), span: int = 12000, n_reads: int = 12,
+                        read_len: int = 2400, lead: int = 250, ref_fraction: float = 0.25,
+                        errors: Tuple[float, float, float] = (0.01, 0.08, 0.04), chrom_prefix: str = "k") -> SynthWorld:
+    """Long DEL / INV / TANDUP loci (a contig each, BED columns s and e = s + span) whose junctions are read from BOTH sides, the
+    way an aligner reports a long read across a junction: the piece that ends there aligned and soft-clipped after it (xM yS),
+    the piece that starts there soft-clipped before it (yS xM) - make_world's reads all start left of the first breakpoint.
+    Per junction side n_reads reads, a share ref_fraction of them the contig itself.  DEL: A = ref[:s] + ref[e:], one junction;
+    TANDUP: ref[:e] + ref[s:], one junction; INV: ref[:s] + rc(ref[s:e]) + ref[e:], two junctions, each also seen from the
+    inverted strand."""
+    rng = np.random.default_rng(seed)
+    w = SynthWorld()
+    for li in range(len(svtypes)):
+        t = svtypes[li]
+        c = "%s%d" % (chrom_prefix, li + 1)
+        s = 1500 + int(rng.integers(0, 200))
+        e = s + int(span)
+        ref = w.contigs[c] = random_dna(rng, e + read_len + 600)
+        tag = "g%d" % (li + 1)
+        if t == "DEL":
+            sides = [("R", s, ref[e:]), ("L", e + 1, ref[:s])]
+        elif t in ("TANDUP", "DUP"):
+            t = "TANDUP"
+            sides = [("R", e, ref[s:]), ("L", s + 1, ref[:e])]
+        elif t == "INV":
+            blk = revcomp(ref[s:e])
+            sides = [("R", s, blk), ("R", e, revcomp(ref[:s])), ("L", e + 1, blk), ("L", s + 1, revcomp(ref[e:]))]
+        else:
+            raise ValueError(t)
+        for k, (side, at, other) in enumerate(sides):
+            _clipped_reads(rng, w, c, side, at, other, n_reads, read_len, lead, errors, "%s%s" % (tag, "abcd"[k]), ref_fraction)
+        w.reads[c].sort(key=lambda r: r.pos)
+        w.loci.append(Locus(c, t, s, e, "jn%d" % (li + 1)))
+    return w
+
+
+def mirror_world(world: SynthWorld) -> SynthWorld:
+    """M(W): the world as its reverse-complemented contigs hold it (x -> L + 1 - x on a contig of L bases; `--both-ends`,
+    DESIGN.md 4.14).  Contigs: their reverse complement (seqio.rc_read: nothing is dropped).  Records: seqio.mirror_records -
+    POS = L + 1 - the alignment's last reference base, the CIGAR operations reversed, rc(SEQ), tags kept - sorted by the new POS
+    (stable).  Loci: DEL / INV / TANDUP / INS at (L + 1 - end, L + 1 - start); a breakend at (La + 1 - p, Lb + 1 - q) in the form
+    the junction has on the other strand (3to5 <-> 5to3, 3to3 <-> 5to5), its inserted bases reverse complemented.  The contigs
+    must be text (a world of virtual contigs is not mirrored)."""
+    from . import seqio
+    m = SynthWorld()
+    for c, seq in world.contigs.items():
+        if not isinstance(seq, str):
+            raise TypeError("mirror_world: contig %s is not text" % c)
+        m.contigs[c] = seqio.rc_read(seq)
+    for c, recs in world.reads.items():
+        n = len(world.contigs[c])
+        out = []
+        for r, (q, pos, cig, seq) in zip(recs, seqio.mirror_records([(r.qname, r.pos, r.cigar, r.seq) for r in recs], n)):
+            span = sum(int(k) for k, op in seqio._CIGAR_RE.findall(cig) if op in "M=D")
+            out.append(SamRecord(q, c, pos, cig, seq, span, dict(r.tags) if r.tags else None))
+        out.sort(key=lambda r: r.pos)
+        m.reads[c] = out
+    other = {"3to5": "5to3", "5to3": "3to5", "3to3": "5to5", "5to5": "3to3"}
+    for l in world.loci:
+        n = len(world.contigs[l.chrom])
+        if l.svtype == "BND":
+            nb = len(world.contigs[l.extra["mate_chrom"]])
+            m.loci.append(Locus(l.chrom, "BND", n + 1 - l.start, nb + 1 - l.end, l.svid, seqio.rc_read(l.ins_seq or ""),
+                                {"form": other[l.extra["form"]], "mate_chrom": l.extra["mate_chrom"]}))
+        else:
+            m.loci.append(Locus(l.chrom, l.svtype, n + 1 - l.end, n + 1 - l.start, l.svid,
+                                seqio.rc_read(l.ins_seq) if l.ins_seq else l.ins_seq, dict(l.extra) if l.extra else None))
+    return m
 
 
 def bnd_records(world: SynthWorld, mates: bool = True) -> List[List[str]]:
