@@ -39,7 +39,8 @@ def build_twin(force: bool = False) -> str:
     # (vapor_bam.cpp: the BGZF/BAM host helper of the product library, plain C++ without device code, is part of the ABI)
     bam = os.path.join(os.path.dirname(_HERE), "vapor_amd", "csrc", "vapor_bam.cpp")
     srcs = [os.path.join(_HERE, "cpu_twin.cpp"), os.path.join(_HERE, "vapor_oracle.c"),
-            os.path.join(os.path.dirname(_HERE), "include", "vapor_hip.h"), bam]
+            os.path.join(os.path.dirname(_HERE), "include", "vapor_hip.h"), bam,
+            os.path.join(os.path.dirname(bam), "vapor_bgzf.h"), os.path.join(os.path.dirname(bam), "vapor_inflate.h")]
     if force or not os.path.exists(_TWIN) or any(os.path.getmtime(_TWIN) < os.path.getmtime(x) for x in srcs):
         os.makedirs(os.path.dirname(_TWIN), exist_ok=True)
         obj = os.path.join(_HERE, "_build", "vapor_oracle_twin.o")

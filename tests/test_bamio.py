@@ -415,7 +415,10 @@ def _blocks(raw: bytes):
     out, p = [], 0
     while p + 18 <= len(raw):
         xlen = struct.unpack_from("<H", raw, p + 10)[0]
-        bsize = struct.unpack_from("<H", raw, p + 16)[0] + 1
+        q = p + 12
+        while raw[q:q + 4] != b"BC\x02\x00":                   # (the subfields in front of BC)
+            q += 4 + struct.unpack_from("<H", raw, q + 2)[0]
+        bsize = struct.unpack_from("<H", raw, q + 4)[0] + 1
         out.append((p, bsize, xlen))
         p += bsize
     return out
@@ -447,6 +450,21 @@ def _both_raise(path, query=("c", 4000, 5500, 200)):
     return got
 
 
+def _foreign_block(data: bytes) -> bytes:
+    """bamio._bgzf_block with a foreign 6-byte subfield in front of BC in the extra field (XLEN 12)."""
+    comp = zlib.compressobj(6, zlib.DEFLATED, -15)
+    cdata = comp.compress(data) + comp.flush()
+    return (b"\x1f\x8b\x08\x04\x00\x00\x00\x00\x00\xff\x0c\x00XY\x02\x00\xab\xcdBC\x02\x00" + struct.pack("<H", len(cdata) + 31)
+            + cdata + struct.pack("<II", zlib.crc32(data) & 0xFFFFFFFF, len(data)))
+
+
+def foreign_subfield_writer(monkeypatch):
+    """Until monkeypatch.undo(): bamio.write_bam and seqio.write_bgzf_fasta write every block, the end-of-file block too, with
+    _foreign_block."""
+    monkeypatch.setattr(bamio, "_bgzf_block", _foreign_block)
+    monkeypatch.setattr(bamio, "_BGZF_EOF", _foreign_block(b""))
+
+
 def _data_block_index(raw, path):
     """A block well inside the region the query reads (not the header block, not the EOF marker)."""
     bl = _blocks(raw)
@@ -465,7 +483,18 @@ def test_good_file_is_read_and_its_crcs_hold(tmp_path):
         assert isize == len(data) and crc == zlib.crc32(data) & 0xFFFFFFFF
 
 
-@pytest.mark.parametrize("field", ["isize_huge", "isize_small", "bsize_tiny", "crc", "payload_bit"])
+def test_a_foreign_subfield_in_front_of_bc_reads_the_same(tmp_path, monkeypatch):
+    plain = _small_bam(tmp_path, "plain.bam")
+    foreign_subfield_writer(monkeypatch)
+    foreign = _small_bam(tmp_path, "foreign.bam")
+    monkeypatch.undo()
+    assert all(xlen == 12 for _off, _bsize, xlen in _blocks(open(foreign, "rb").read()))
+    q = [("c", 4000, 5500, 200), ("c", 12000, 12800, 300)]
+    nat, py = _chop_both(foreign, q)
+    assert nat == py == _chop_both(plain, q)[0] and len(nat[0]) > 3
+
+
+@pytest.mark.parametrize("field", ["isize_huge", "isize_small", "bsize_tiny", "bc_cut", "crc", "payload_bit"])
 def test_damaged_bgzf_block_is_an_exception_not_a_crash(tmp_path, field):
     path = _small_bam(tmp_path)
     raw = bytearray(open(path, "rb").read())
@@ -477,6 +506,8 @@ def test_damaged_bgzf_block_is_an_exception_not_a_crash(tmp_path, field):
         struct.pack_into("<I", raw, off + bsize - 4, 17)
     elif field == "bsize_tiny":
         struct.pack_into("<H", raw, off + 16, 9)                          # BSIZE below header + trailer
+    elif field == "bc_cut":
+        struct.pack_into("<H", raw, off + 10, 5)                          # XLEN 5: the BC subfield's value lies behind the extra field
     elif field == "crc":
         raw[off + bsize - 8] ^= 0x40
     else:

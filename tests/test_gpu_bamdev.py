@@ -159,7 +159,28 @@ def test_blocks_of_every_deflate_kind(eng, tmp_path, kind, monkeypatch):
     assert status.tolist() == [0] * len(w.loci) and n > 60
 
 
-@pytest.mark.parametrize("field", ["crc", "payload_bit", "isize_small"])
+def test_a_foreign_subfield_in_front_of_bc_in_every_block(eng, tmp_path, monkeypatch):
+    """XLEN 12: the payload starts where the extra field ends, not at byte 18.  60 reads in 20 000-byte blocks: a region's span holds
+    several blocks, so the walk goes from block to block and ends by its stop rule."""
+    rng = np.random.default_rng(9)
+    contig = synth.random_dna(rng, 100000)
+    recs = []
+    for i in range(60):
+        pos = 1500 * i + int(rng.integers(0, 400))
+        read, cg = synth.mutate(rng, contig[pos:pos + 5000])
+        recs.append(("f%d" % i, 0, pos, cg, read))
+    p = str(tmp_path / "foreign.bam")
+    TB.foreign_subfield_writer(monkeypatch)
+    bamio.write_bam(p, [("c", 100000)], recs, block_size=20000)
+    monkeypatch.undo()
+    bl = TB._blocks(open(p, "rb").read())
+    assert len(bl) > 15 and all(xlen == 12 for _off, _bsize, xlen in bl)
+    # (a read covers 5 000 bases and one starts every 1 500: each window has one that starts before it and covers it)
+    status, n = compare(eng, p, [("c", 7000 * i + 2000, 7000 * i + 2900, 300) for i in range(12)])
+    assert status.tolist() == [0] * 12 and n >= 12
+
+
+@pytest.mark.parametrize("field", ["crc", "payload_bit", "isize_small", "bc_cut"])
 def test_a_damaged_block_sends_its_regions_to_the_host_route_and_no_other(eng, tmp_path, field):
     rng = np.random.default_rng(5)
     contig = synth.random_dna(rng, 400000)
@@ -177,8 +198,10 @@ def test_a_damaged_block_sends_its_regions_to_the_host_route_and_no_other(eng, t
         raw[off + bsize - 8] ^= 0x40
     elif field == "payload_bit":
         raw[off + 12 + xlen + (bsize - xlen - 20) // 2] ^= 0x04
-    else:
+    elif field == "isize_small":
         struct.pack_into("<I", raw, off + bsize - 4, 17)
+    else:
+        struct.pack_into("<H", raw, off + 10, 5)               # XLEN 5: the BC subfield's value lies behind the extra field
     bad = str(tmp_path / "bad.bam")
     open(bad, "wb").write(bytes(raw))
     shutil.copy(good + ".bai", bad + ".bai")

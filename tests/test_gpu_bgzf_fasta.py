@@ -113,6 +113,28 @@ def test_device_windows_equal_the_host_reader(eng, tmp_path, line_width, block_s
             assert up
 
 
+def test_a_foreign_subfield_in_front_of_bc_in_every_block(eng, tmp_path, monkeypatch):
+    """XLEN 12 in every block.  Two contigs of 100 kb in blocks of 20 000 bytes: a stretch holds several blocks, and some windows
+    end exactly on a block boundary or start right behind one."""
+    import test_bamio as TB
+    rnd = random.Random(12)
+    TB.foreign_subfield_writer(monkeypatch)
+    gz = seqio.write_bgzf_fasta(str(tmp_path / "ref.fa.gz"), {"chr1": "".join(rnd.choice("ACGT") for _ in range(100000)),
+                                                             "chr2": "".join(rnd.choice("ACGTN") for _ in range(100000))}, 60, 20000)
+    monkeypatch.undo()
+    assert all(xlen == 12 for _off, _bsize, xlen in TB._blocks(open(gz, "rb").read()))
+    bz = seqio.BgzfFasta(gz)
+    wins = _windows(bz, random.Random(13), 9)
+    on_boundary = sum(1 for w in wins if int(bz.raw_range(*w)[1]) in bz.uoff.tolist() or int(bz.raw_range(*w)[0]) in bz.uoff.tolist())
+    assert 18 <= len(wins) <= 24 and on_boundary >= 4
+    keep, texts, traits, status, blocks = _device(eng, bz, wins)
+    assert len(keep) == len(wins) and status.tolist() == [0] * len(keep)
+    for q, i in enumerate(keep):
+        exp = bz.fetch(*wins[i])
+        assert texts[q] == exp and int(traits[q]) == _host_traits(exp), wins[i]
+    assert eng.fasta_last_stats()["blocks"] == len(blocks) > 5
+
+
 def test_a_damaged_block_sends_exactly_its_windows_to_the_host(eng, tmp_path):
     gz = seqio.write_bgzf_fasta(str(tmp_path / "ref.fa.gz"), _contigs(3), 60, 1000)
     bz = seqio.BgzfFasta(gz)

@@ -8,6 +8,7 @@
 // start (cigar2alignstart_by_pos, SF:309-337; the CG:B,I long-CIGAR convention included) and only the bases that are
 // kept are decoded.  The .bai lookup (bins, linear index) stays in Python: it is a few dictionary reads per locus.
 #include "vapor_hip.h"
+#include "vapor_bgzf.h"
 #include "vapor_inflate.h"
 
 #include <fcntl.h>
@@ -80,40 +81,24 @@ extern "C" int vapor_bam_set_threads(vapor_bam* b, int32_t n)
     return VAPOR_OK;
 }
 
-// Parses the BGZF block headers from scan_pos on and appends the whole blocks found to the block lists (a truncated
-// last block is left for the next read); -1 when the bytes are not BGZF.
+// Parses the BGZF blocks from scan_pos on (vapor_bgzf.h) and appends the whole ones to the block lists (a truncated last block
+// is left for the next read); -1 when the bytes at scan_pos, behind them, are not BGZF.
 static int scan_blocks(vapor_bam* b)
 {
     int n = 0;
-    size_t p = b->scan_pos;
-    while (p + 18 <= b->comp.size()) {
-        const uint8_t* h = b->comp.data() + p;
-        if (h[0] != 0x1f || h[1] != 0x8b || h[2] != 8 || !(h[3] & 4)) return -1;
-        const int xlen = h[10] | (h[11] << 8);
-        if (p + 12 + (size_t)xlen > b->comp.size()) break;
-        int bsize = -1;
-        for (int q = 0; q + 4 <= xlen;) {
-            const uint8_t* e = h + 12 + q;
-            const int slen = e[2] | (e[3] << 8);
-            if (e[0] == 66 && e[1] == 67 && slen == 2) bsize = (e[4] | (e[5] << 8)) + 1;
-            q += 4 + slen;
-        }
-        // (a block is its 12-byte header, the extra field, the payload, CRC32 and ISIZE: anything shorter is not one, and its
-        // trailer would be read from before the block)
-        if (bsize < 0 || bsize < xlen + 20) return -1;
-        if (p + (size_t)bsize > b->comp.size()) break;
-        const uint8_t* t = h + bsize - 4;
-        const uint32_t isize = (uint32_t)t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
-        if (isize > 65536u) return -1;                       // BGZF: at most 64 KB of data per block
-        b->blk_coff.push_back(b->comp_base + (int64_t)p);
-        b->blk_cpos.push_back((int64_t)p);
-        b->blk_csize.push_back(bsize);
-        b->blk_usize.push_back((int32_t)isize);
-        p += (size_t)bsize;
-        ++n;
-    }
-    b->scan_pos = p;
-    return n;
+    const size_t p0 = b->scan_pos;
+    const vapor_bgzf::Walked w = vapor_bgzf::walk(b->comp.data() + p0, b->comp.size() - p0, b->comp_base + (int64_t)p0,
+        [](int64_t) { return false; },
+        [&](const vapor_bgzf::Block& k) {
+            b->blk_coff.push_back(b->comp_base + (int64_t)(p0 + k.pos));
+            b->blk_cpos.push_back((int64_t)(p0 + k.pos));
+            b->blk_csize.push_back(k.bsize);
+            b->blk_usize.push_back((int32_t)k.isize);
+            ++n;
+            return true;
+        });
+    b->scan_pos = p0 + w.pos;
+    return w.end == vapor_bgzf::End::BAD ? -1 : n;
 }
 
 // the block's own CRC32 (the four bytes before ISIZE) against the inflated bytes, as htslib checks it: a decoder bug or a
@@ -222,8 +207,10 @@ static bool ensure(vapor_bam* b, int64_t upto)
             if (!take_blocks(b, b->blk_ustart.size() + (size_t)std::max(b->n_threads, 1))) { g_bam_damaged = true; return false; }
             continue;
         }
-        if (!read_more(b, (size_t)1 << 17)) return false;
+        // (bytes that are not BGZF behind the chunk's end are met here, with or without more of the file behind them)
+        const bool more = read_more(b, (size_t)1 << 17);
         if (scan_blocks(b) < 0) { g_bam_damaged = true; return false; }
+        if (!more) return false;
     }
     return true;
 }
@@ -349,7 +336,10 @@ static int bam_chop_impl(vapor_bam* b, int32_t tid, int64_t start, int64_t end, 
         // through the block that holds the chunk's end (none of it when the chunk ends on a block boundary)
         const size_t span = (size_t)((int64_t)(ce >> 16) - b->comp_base) + ((ce & 0xFFFFu) ? ((size_t)1 << 16) + 64 : 0);
         if (span == 0 || !read_more(b, span)) continue;
-        if (scan_blocks(b) < 0) return bfail(VAPOR_E_ARG, "vapor_bam_chop: not a BGZF block in " + b->path);
+        // (the read holds more than the chunk: what is not BGZF behind the chunk's end is refused when a record runs into it, ensure(),
+        // as the device reader, whose scan ends with the chunk, leaves such a region to this one)
+        if (scan_blocks(b) < 0 && ((uint64_t)(b->comp_base + (int64_t)b->scan_pos) << 16) < ce)
+            return bfail(VAPOR_E_ARG, "vapor_bam_chop: not a BGZF block in " + b->path);
         // the blocks the chunk covers (the read holds a few more behind its end block: those wait until a record needs them)
         size_t own = 0;
         while (own < b->blk_coff.size() && ((uint64_t)b->blk_coff[own] << 16) < ce) ++own;

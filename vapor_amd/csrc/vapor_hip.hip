@@ -9,6 +9,7 @@
 #include "vapor_wide.h"
 #include "vapor_anyk.h"
 #include "vapor_bamdev.h"
+#include "vapor_bgzf.h"
 #include "vapor_fasta.h"
 #include "vapor_refine.h"
 #include "vapor_hip.h"
@@ -940,93 +941,6 @@ extern "C" int vapor_bam_batch_destroy(vapor_bam_batch* b)
     return VAPOR_OK;
 }
 
-namespace {
-struct HostSpan {                  // one index chunk of a region on the host side
-    int32_t region;
-    uint64_t cs, ce;
-    int64_t file_off;              // compressed range read from the file
-    size_t want, got;
-    size_t stage_off;              // ... into the pinned staging buffer here
-    std::vector<vapor_bamdev::BgzfBlk> blks;   // c_off relative to the staging buffer, u_off relative to the span's data
-    uint32_t u_begin = 0, u_end = 0, u_total = 0;
-    bool bad = false;              // not BGZF, or a begin offset outside its block: the host route words the error
-};
-
-// the whole blocks of a span, through the block that holds the chunk's end
-void scan_span(HostSpan& sp, const uint8_t* stage)
-{
-    const uint8_t* base = stage + sp.stage_off;
-    const int64_t end_coff = (int64_t)(sp.ce >> 16);
-    const uint32_t end_uoff = (uint32_t)(sp.ce & 0xFFFFu);
-    size_t p = 0;
-    uint32_t u = 0;
-    bool have_end = false;
-    sp.u_end = 0;
-    while (p + 18 <= sp.got) {
-        const int64_t coff = sp.file_off + (int64_t)p;
-        if (coff > end_coff || (coff == end_coff && end_uoff == 0)) break;
-        const uint8_t* h = base + p;
-        if (h[0] != 0x1f || h[1] != 0x8b || h[2] != 8 || !(h[3] & 4)) { sp.bad = true; return; }
-        const int xlen = h[10] | (h[11] << 8);
-        if (p + 12 + (size_t)xlen > sp.got) break;
-        int bsize = -1;
-        for (int q = 0; q + 4 <= xlen;) {
-            const uint8_t* e = h + 12 + q;
-            const int slen = e[2] | (e[3] << 8);
-            if (e[0] == 66 && e[1] == 67 && slen == 2) bsize = (e[4] | (e[5] << 8)) + 1;
-            q += 4 + slen;
-        }
-        if (bsize < 0 || bsize < xlen + 20) { sp.bad = true; return; }
-        if (p + (size_t)bsize > sp.got) break;
-        const uint8_t* t = h + bsize - 8;
-        const uint32_t crc = (uint32_t)t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
-        const uint32_t isize = (uint32_t)t[4] | ((uint32_t)t[5] << 8) | ((uint32_t)t[6] << 16) | ((uint32_t)t[7] << 24);
-        if (isize > 65536u) { sp.bad = true; return; }
-        if (coff == end_coff) { have_end = true; sp.u_end = u + std::min(end_uoff, isize); }
-        if (isize == 0) {
-            if (crc != 0) { sp.bad = true; return; }        // (the CRC-32 of no bytes)
-        } else {
-            vapor_bamdev::BgzfBlk k;
-            k.c_off = (uint32_t)(sp.stage_off + p + 12 + (size_t)xlen);
-            k.c_len = (uint32_t)(bsize - xlen - 20);
-            k.u_off = u;
-            k.u_len = isize;
-            k.crc = crc;
-            k.pad = 0;
-            sp.blks.push_back(k);
-        }
-        u += isize;
-        p += (size_t)bsize;
-    }
-    sp.u_total = u;
-    if (!have_end) sp.u_end = u;                            // the chunk ends on a block boundary (or the file ends inside it)
-    const uint32_t b0 = (uint32_t)(sp.cs & 0xFFFFu);
-    // the first record's offset must lie inside the first block
-    uint32_t first_usize = 0;
-    {
-        // (the first block in the file order, empty ones included, is the one `cs` names)
-        const uint8_t* h = base;
-        if (sp.got >= 18) {
-            const int xlen = h[10] | (h[11] << 8);
-            int bsize = -1;
-            if (12 + (size_t)xlen <= sp.got)
-                for (int q = 0; q + 4 <= xlen;) {
-                    const uint8_t* e = h + 12 + q;
-                    const int slen = e[2] | (e[3] << 8);
-                    if (e[0] == 66 && e[1] == 67 && slen == 2) bsize = (e[4] | (e[5] << 8)) + 1;
-                    q += 4 + slen;
-                }
-            if (bsize >= xlen + 20 && (size_t)bsize <= sp.got) {
-                const uint8_t* t = h + bsize - 4;
-                first_usize = (uint32_t)t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
-            }
-        }
-    }
-    if (b0 > first_usize) { sp.bad = true; return; }
-    sp.u_begin = b0;
-}
-}   // namespace
-
 // the CRC combination constants bgzf_inflate_kernel multiplies its lanes' slice CRCs by, on the device once per context
 static hipError_t crc_pow_on_device(vapor_ctx* ctx)
 {
@@ -1053,6 +967,82 @@ static hipError_t crc_pow_on_device(vapor_ctx* ctx)
     return hipSuccess;
 }
 
+static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+// A running offset into a metadata block: every table starts on a multiple of 64.
+struct Carve {
+    size_t off = 0;
+    size_t take(size_t bytes) { const size_t o = off; off += (bytes + 63) & ~(size_t)63; return o; }
+};
+
+// The inflate stage of the two device readers (vapor_bam_chop_device*, vapor_fasta_windows_device): the file's bytes read into a
+// pinned block, one metadata block whose first table is the BgzfBlk list, both sent on the call's stream, bgzf_inflate_kernel.
+// Its blocks are Blocks of the call's CallScope, so they go back to the pool as every other block of the call does.
+struct InflateStage {
+    CallScope& sc;
+    HostBlock<> h_comp, h_meta;
+    Block<> d_comp, d_meta;
+    size_t stage_bytes = 0;
+    explicit InflateStage(CallScope& s) : sc(s), h_comp(s), h_meta(s), d_comp(s), d_meta(s) {}
+    hipError_t begin(size_t bytes) { stage_bytes = bytes; return h_comp.ensure(std::max<size_t>(bytes, 64)); }     // room for the call's compressed bytes
+    // file bytes [file_off, file_off + want) to h_comp + stage_off; how many there were
+    size_t read(int fd, size_t stage_off, size_t want, int64_t file_off) const
+    {
+        size_t got = 0;
+        while (got < want) {
+            const ssize_t r = pread(fd, h_comp + stage_off + got, want - got, (off_t)(file_off + (int64_t)got));
+            if (r <= 0) break;
+            got += (size_t)r;
+        }
+        return got;
+    }
+    static vapor_bamdev::BgzfBlk blk(size_t stage_off, const vapor_bgzf::Block& b, uint64_t arena)     // (arena + b.u below 2^31: the callers' limits)
+    {
+        return {(uint32_t)(stage_off + b.payload()), b.c_len(), (uint32_t)(arena + b.u), b.isize, b.crc, 0};
+    }
+    int alloc(size_t h_meta_bytes, size_t d_meta_bytes)
+    {
+        HIPCHK(h_meta.ensure(h_meta_bytes));
+        HIPCHK(d_meta.ensure(d_meta_bytes));
+        HIPCHK(d_comp.ensure(std::max<size_t>(stage_bytes, 64)));
+        HIPCHK(crc_pow_on_device(sc.ctx));
+        return VAPOR_OK;
+    }
+    // On sc.st: the compressed bytes and the first in_bytes of the metadata go to the device, ev[0], the blocks (the table at the
+    // metadata's start) inflate to `arena`, their statuses to the metadata's o_bst.  The caller records ev[1] where its timing ends.
+    // (t_comp: the developer's timing - the stream is synchronised behind the first copy and the clock written there)
+    int run(const std::vector<vapor_bamdev::BgzfBlk>& blks, size_t in_bytes, size_t o_bst, uint8_t* arena, hipEvent_t* ev, double* t_comp = nullptr)
+    {
+        using namespace vapor_bamdev;
+        const size_t n_blks = blks.size();
+        if (n_blks) memcpy(h_meta, blks.data(), sizeof(BgzfBlk) * n_blks);
+        if (!ev[0]) { HIPCHK(hipEventCreate(&ev[0])); HIPCHK(hipEventCreate(&ev[1])); }
+        if (stage_bytes) HIPCHK(hipMemcpyAsync(d_comp, h_comp, stage_bytes, hipMemcpyHostToDevice, sc.st));
+        if (t_comp) { HIPCHK(hipStreamSynchronize(sc.st)); *t_comp = now_ms(); }
+        HIPCHK(hipMemcpyAsync(d_meta, h_meta, in_bytes, hipMemcpyHostToDevice, sc.st));
+        HIPCHK(hipEventRecord(ev[0], sc.st));
+        if (n_blks) {
+            hipLaunchKernelGGL(bgzf_inflate_kernel, dim3((unsigned)((n_blks + INFLATE_WAVES - 1) / INFLATE_WAVES)), dim3(64 * INFLATE_WAVES), 0, sc.st, d_comp,
+                               reinterpret_cast<const BgzfBlk*>(d_meta.p), (int)n_blks, arena, sc.ctx->d_crc_pow, reinterpret_cast<int32_t*>(d_meta + o_bst));
+            HIPCHK(hipGetLastError());
+        }
+        return VAPOR_OK;
+    }
+};
+
+// No exception crosses the C boundary (a thread that could not start, a vector that could not grow, ...).
+template <typename F>
+static int guarded(const char* name, F body)
+{
+    try {
+        return body();
+    } catch (const std::bad_alloc&) {
+        return fail(VAPOR_E_NOMEM, std::string(name) + ": out of memory");
+    } catch (const std::exception& e) {
+        return fail(VAPOR_E_ARG, std::string(name) + ": " + e.what());
+    }
+}
+
 // vapor_bam_chop_device, and with `member` (vapor_bam_chop_device_tagged) the phased form of it: the tagged chop kernel, the
 // select kernel behind it on the same stream, and only the regions' compact unions and phase sets copied back.
 static int bam_chop_device_impl(vapor_ctx* ctx, vapor_bam* bam, int32_t n_regions, const int32_t* tid, const int64_t* start,
@@ -1062,6 +1052,7 @@ static int bam_chop_device_impl(vapor_ctx* ctx, vapor_bam* bam, int32_t n_region
                                 bool right = false)
 {
     using namespace vapor_bamdev;
+    using vapor_bgzf::HostSpan;
     const bool phased = member != nullptr;
     if (!ctx || !bam || !out || n_regions < 0 || max_keep < 1 || max_keep > KEPT_CAP ||
         (n_regions && (!tid || !start || !end || !flank || !chunk_first || !kept_first || !sq_addr || !q0 || !miss || !status)) ||
@@ -1072,9 +1063,8 @@ static int bam_chop_device_impl(vapor_ctx* ctx, vapor_bam* bam, int32_t n_region
     HIPCHK(hipSetDevice(ctx->device));
     *out = nullptr;
     const bool dbg_t = getenv("VAPOR_DEBUG_BAMDEV") != nullptr;
-    auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    double tq[8] = {now(), 0, 0, 0, 0, 0, 0, 0};
-    try {
+    double tq[8] = {now_ms(), 0, 0, 0, 0, 0, 0, 0};
+    return guarded("vapor_bam_chop_device", [&]() -> int {
         // ---- what to read ---------------------------------------------------------------------------------------------------
         std::vector<HostSpan> spans;
         std::vector<int32_t> span_first((size_t)n_regions + 1, 0);
@@ -1110,9 +1100,10 @@ static int bam_chop_device_impl(vapor_ctx* ctx, vapor_bam* bam, int32_t n_region
         std::unique_ptr<vapor_bam_batch, Building<vapor_bam_batch, vapor_bam_batch_destroy>> B(new vapor_bam_batch(), {&sc});
         B->ctx = ctx;
         B->device = ctx->device;
-        HostBlock<> h_comp(sc), h_meta(sc);
-        Block<> d_comp(sc), d_meta(sc);
-        HIPCHK(h_comp.ensure(std::max<size_t>(stage_bytes, 64)));
+        InflateStage stage(sc);
+        HIPCHK(stage.begin(stage_bytes));
+        HostBlock<>& h_meta = stage.h_meta;
+        Block<>& d_meta = stage.d_meta;
         // ---- read and scan, a few threads -------------------------------------------------------------------------------------
         {
             const int n_thr = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(vapor_bam_threads(bam), 1) * 2, spans.size() / 8 + 1));
@@ -1122,15 +1113,9 @@ static int bam_chop_device_impl(vapor_ctx* ctx, vapor_bam* bam, int32_t n_region
                     const size_t i = next.fetch_add(1, std::memory_order_relaxed);
                     if (i >= spans.size()) break;
                     HostSpan& sp = spans[i];
-                    size_t got = 0;
-                    while (got < sp.want) {
-                        const ssize_t r = pread(fd, h_comp + sp.stage_off + got, sp.want - got, (off_t)(sp.file_off + (int64_t)got));
-                        if (r <= 0) break;
-                        got += (size_t)r;
-                    }
-                    sp.got = got;
+                    sp.got = stage.read(fd, sp.stage_off, sp.want, sp.file_off);
                     try {
-                        scan_span(sp, h_comp);
+                        vapor_bgzf::scan_span(sp, stage.h_comp);
                     } catch (const std::exception&) {       // (out of memory for the block list: the region goes the host route)
                         sp.blks.clear();
                         sp.bad = true;
@@ -1146,7 +1131,7 @@ static int bam_chop_device_impl(vapor_ctx* ctx, vapor_bam* bam, int32_t n_region
                 for (auto& x : th) x.join();
             }
         }
-        tq[1] = now();
+        tq[1] = now_ms();
         // ---- layout of the arena and the tables -------------------------------------------------------------------------------
         for (const HostSpan& sp : spans)
             if (sp.bad) status[sp.region] = REG_MALFORMED;
@@ -1154,7 +1139,6 @@ static int bam_chop_device_impl(vapor_ctx* ctx, vapor_bam* bam, int32_t n_region
         std::vector<BamSpan> dspans;
         std::vector<BamRegion> regs((size_t)std::max(n_regions, 1));
         size_t arena = 0;
-        uint32_t max_usize = 0;
         for (int32_t g = 0; g < n_regions; ++g) {
             BamRegion& R = regs[(size_t)g];
             R.start = start[g]; R.end = end[g]; R.flank = flank[g]; R.tid = tid[g]; R.pad = 0;
@@ -1171,11 +1155,7 @@ static int bam_chop_device_impl(vapor_ctx* ctx, vapor_bam* bam, int32_t n_region
                 d.blk_first = (uint32_t)blks.size();
                 d.blk_n = (uint32_t)sp.blks.size();
                 d.pad = 0;
-                for (BgzfBlk k : sp.blks) {
-                    k.u_off += (uint32_t)arena;
-                    max_usize = std::max(max_usize, k.u_len);
-                    blks.push_back(k);
-                }
+                for (const vapor_bgzf::Block& k : sp.blks) blks.push_back(InflateStage::blk(sp.stage_off, k, arena));
                 dspans.push_back(d);
                 ++R.span_n;
                 arena += ((size_t)sp.u_total + 63) & ~(size_t)63;
@@ -1183,29 +1163,22 @@ static int bam_chop_device_impl(vapor_ctx* ctx, vapor_bam* bam, int32_t n_region
         }
         const size_t n_blks = blks.size();
         // metadata in one block: blocks, spans, regions in; block status, kept counts, region status, kept reads out
-        const size_t o_blk = 0, o_span = o_blk + ((sizeof(BgzfBlk) * std::max<size_t>(n_blks, 1) + 63) & ~(size_t)63);
-        const size_t o_reg = o_span + ((sizeof(BamSpan) * std::max<size_t>(dspans.size(), 1) + 63) & ~(size_t)63);
-        const size_t in_bytes = o_reg + ((sizeof(BamRegion) * regs.size() + 63) & ~(size_t)63);
-        const size_t o_bst = in_bytes, o_nk = o_bst + ((4 * std::max<size_t>(n_blks, 1) + 63) & ~(size_t)63);
-        const size_t o_rst = o_nk + ((4 * regs.size() + 63) & ~(size_t)63);
+        Carve m;
+        m.take(sizeof(BgzfBlk) * std::max<size_t>(n_blks, 1));
+        const size_t o_span = m.take(sizeof(BamSpan) * std::max<size_t>(dspans.size(), 1)), o_reg = m.take(sizeof(BamRegion) * regs.size());
+        const size_t in_bytes = m.off;
+        const size_t o_bst = m.take(4 * std::max<size_t>(n_blks, 1)), o_nk = m.take(4 * regs.size()), o_rst = m.take(4 * regs.size());
         // (phased: the regions' BamPhase and their unions - 3 * max_keep picks each - come back; the kept entries and their tags
         // stay on the device)
-        const size_t o_phase = o_rst + ((4 * regs.size() + 63) & ~(size_t)63);
-        const size_t o_picks = o_phase + (phased ? (sizeof(BamPhase) * regs.size() + 63) & ~(size_t)63 : 0);
-        const size_t o_kept = o_picks + (phased ? (sizeof(BamPick) * 3 * (size_t)max_keep * regs.size() + 63) & ~(size_t)63 : 0);
-        const size_t o_tags = o_kept + sizeof(BamKept) * KEPT_CAP * regs.size();
+        const size_t o_phase = m.take(phased ? sizeof(BamPhase) * regs.size() : 0), o_picks = m.take(phased ? sizeof(BamPick) * 3 * (size_t)max_keep * regs.size() : 0);
+        const size_t o_kept = m.take(sizeof(BamKept) * KEPT_CAP * regs.size()), o_tags = m.take(phased ? sizeof(BamTag) * KEPT_CAP * regs.size() : 0);
         const size_t back_end = phased ? o_kept : o_tags;            // what the host reads back ends here
-        const size_t meta_bytes = o_tags + (phased ? sizeof(BamTag) * KEPT_CAP * regs.size() : 0);
-        HIPCHK(h_meta.ensure(std::max(back_end, in_bytes)));
-        HIPCHK(d_meta.ensure(meta_bytes));
-        HIPCHK(d_comp.ensure(std::max<size_t>(stage_bytes, 64)));
+        if (const int rc = stage.alloc(std::max(back_end, in_bytes), m.off)) return rc;
         HIPCHK(dmalloc(ctx, (void**)&B->d_arena, arena + 64));
         B->arena_bytes = arena + 64;
         ctx->arenas[B->d_arena] = B->arena_bytes;
-        if (n_blks) memcpy(h_meta + o_blk, blks.data(), sizeof(BgzfBlk) * n_blks);
         if (!dspans.empty()) memcpy(h_meta + o_span, dspans.data(), sizeof(BamSpan) * dspans.size());
         memcpy(h_meta + o_reg, regs.data(), sizeof(BamRegion) * regs.size());
-        HIPCHK(crc_pow_on_device(ctx));
         {
             const char* sh = getenv("VAPOR_BAM_CU_SHARE");            // (experiments: overrides the parameter)
             const int share = ctx->user_stream ? 0 : (sh ? atoi(sh) : ctx->bam_cu_share);
@@ -1223,46 +1196,33 @@ static int bam_chop_device_impl(vapor_ctx* ctx, vapor_bam* bam, int32_t n_region
         }
         hipStream_t st = ctx->bam_stream ? ctx->bam_stream : ctx->stream;
         sc.st = st;
-        tq[2] = now();
-        if (stage_bytes) HIPCHK(hipMemcpyAsync(d_comp, h_comp, stage_bytes, hipMemcpyHostToDevice, st));
-        if (dbg_t) { HIPCHK(hipStreamSynchronize(st)); tq[3] = now(); }
-        HIPCHK(hipMemcpyAsync(d_meta, h_meta, in_bytes, hipMemcpyHostToDevice, st));
-        if (!ctx->bam_ev[0]) { HIPCHK(hipEventCreate(&ctx->bam_ev[0])); HIPCHK(hipEventCreate(&ctx->bam_ev[1])); }
-        HIPCHK(hipEventRecord(ctx->bam_ev[0], st));
-        if (n_blks) {
-            hipLaunchKernelGGL(bgzf_inflate_kernel, dim3((unsigned)((n_blks + INFLATE_WAVES - 1) / INFLATE_WAVES)), dim3(64 * INFLATE_WAVES), 0, st, d_comp, reinterpret_cast<const BgzfBlk*>(d_meta + o_blk),
-                               (int)n_blks, B->d_arena, ctx->d_crc_pow, reinterpret_cast<int32_t*>(d_meta + o_bst));
-            HIPCHK(hipGetLastError());
-        }
+        tq[2] = now_ms();
+        if (const int rc = stage.run(blks, in_bytes, o_bst, B->d_arena, ctx->bam_ev, dbg_t ? &tq[3] : nullptr)) return rc;
         HIPCHK(hipEventRecord(ctx->bam_ev[1], st));
-        if (dbg_t) { HIPCHK(hipStreamSynchronize(st)); tq[4] = now(); }
-        if (n_regions && phased) {
-            hipLaunchKernelGGL(bam_chop_tagged_kernel, dim3((unsigned)n_regions), dim3(64), 0, st, B->d_arena, reinterpret_cast<const BamRegion*>(d_meta + o_reg),
-                               reinterpret_cast<const BamSpan*>(d_meta + o_span), reinterpret_cast<const int32_t*>(d_meta + o_bst), (int)n_regions,
-                               reinterpret_cast<BamKept*>(d_meta + o_kept), reinterpret_cast<int32_t*>(d_meta + o_nk), reinterpret_cast<int32_t*>(d_meta + o_rst),
-                               reinterpret_cast<BamTag*>(d_meta + o_tags));
+        if (dbg_t) { HIPCHK(hipStreamSynchronize(st)); tq[4] = now_ms(); }
+        if (n_regions) {
+            // the chop kernel of the call: plain, right-anchored, or (phased) the tagged one with the select kernel behind it
+            auto chop = [&](auto kernel, auto... tags) {
+                hipLaunchKernelGGL(kernel, dim3((unsigned)n_regions), dim3(64), 0, st, B->d_arena, reinterpret_cast<const BamRegion*>(d_meta + o_reg),
+                                   reinterpret_cast<const BamSpan*>(d_meta + o_span), reinterpret_cast<const int32_t*>(d_meta + o_bst), (int)n_regions,
+                                   reinterpret_cast<BamKept*>(d_meta + o_kept), reinterpret_cast<int32_t*>(d_meta + o_nk), reinterpret_cast<int32_t*>(d_meta + o_rst), tags...);
+            };
+            if (phased) chop(bam_chop_tagged_kernel, reinterpret_cast<BamTag*>(d_meta + o_tags));
+            else chop(right ? bam_chop_right_kernel : bam_chop_kernel);
             HIPCHK(hipGetLastError());
-            hipLaunchKernelGGL(bam_select_kernel, dim3((unsigned)n_regions), dim3(64), 0, st, reinterpret_cast<const BamKept*>(d_meta + o_kept),
-                               reinterpret_cast<const BamTag*>(d_meta + o_tags), reinterpret_cast<const int32_t*>(d_meta + o_nk),
-                               reinterpret_cast<const int32_t*>(d_meta + o_rst), (int)n_regions, (int)max_keep,
-                               reinterpret_cast<BamPick*>(d_meta + o_picks), reinterpret_cast<BamPhase*>(d_meta + o_phase));
-            HIPCHK(hipGetLastError());
-        } else if (n_regions && right) {
-            hipLaunchKernelGGL(bam_chop_right_kernel, dim3((unsigned)n_regions), dim3(64), 0, st, B->d_arena, reinterpret_cast<const BamRegion*>(d_meta + o_reg),
-                               reinterpret_cast<const BamSpan*>(d_meta + o_span), reinterpret_cast<const int32_t*>(d_meta + o_bst), (int)n_regions,
-                               reinterpret_cast<BamKept*>(d_meta + o_kept), reinterpret_cast<int32_t*>(d_meta + o_nk), reinterpret_cast<int32_t*>(d_meta + o_rst));
-            HIPCHK(hipGetLastError());
-        } else if (n_regions) {
-            hipLaunchKernelGGL(bam_chop_kernel, dim3((unsigned)n_regions), dim3(64), 0, st, B->d_arena, reinterpret_cast<const BamRegion*>(d_meta + o_reg),
-                               reinterpret_cast<const BamSpan*>(d_meta + o_span), reinterpret_cast<const int32_t*>(d_meta + o_bst), (int)n_regions,
-                               reinterpret_cast<BamKept*>(d_meta + o_kept), reinterpret_cast<int32_t*>(d_meta + o_nk), reinterpret_cast<int32_t*>(d_meta + o_rst));
-            HIPCHK(hipGetLastError());
+            if (phased) {
+                hipLaunchKernelGGL(bam_select_kernel, dim3((unsigned)n_regions), dim3(64), 0, st, reinterpret_cast<const BamKept*>(d_meta + o_kept),
+                                   reinterpret_cast<const BamTag*>(d_meta + o_tags), reinterpret_cast<const int32_t*>(d_meta + o_nk),
+                                   reinterpret_cast<const int32_t*>(d_meta + o_rst), (int)n_regions, (int)max_keep,
+                                   reinterpret_cast<BamPick*>(d_meta + o_picks), reinterpret_cast<BamPhase*>(d_meta + o_phase));
+                HIPCHK(hipGetLastError());
+            }
         }
         // (counts and statuses first; the kept reads of a region are read where its count says)
         HIPCHK(hipMemcpyAsync(h_meta + o_bst, d_meta + o_bst, back_end - o_bst, hipMemcpyDeviceToHost, st));
         ctx->bam_stats[6] = (double)(back_end - o_bst);
         HIPCHK(hipStreamSynchronize(st));
-        tq[5] = now();
+        tq[5] = now_ms();
         {
             float ms = 0.f;
             if (hipEventElapsedTime(&ms, ctx->bam_ev[0], ctx->bam_ev[1]) != hipSuccess) ms = 0.f;
@@ -1275,7 +1235,7 @@ static int bam_chop_device_impl(vapor_ctx* ctx, vapor_bam* bam, int32_t n_region
 #ifdef VBD_TIMING
         if (dbg_t && n_blks) {
             std::vector<uint8_t> back(stage_bytes);
-            HIPCHK(hipMemcpy(back.data(), d_comp, stage_bytes, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(back.data(), stage.d_comp, stage_bytes, hipMemcpyDeviceToHost));
             double sum[13] = {0};
             size_t cnt = 0;
             for (const BgzfBlk& k : blks) {
@@ -1339,11 +1299,7 @@ static int bam_chop_device_impl(vapor_ctx* ctx, vapor_bam* bam, int32_t n_region
         sc.settled();
         *out = B.release();
         return VAPOR_OK;
-    } catch (const std::bad_alloc&) {
-        return fail(VAPOR_E_NOMEM, "vapor_bam_chop_device: out of memory");
-    } catch (const std::exception& e) {             // (no exception crosses the C boundary: a thread that could not start, ...)
-        return fail(VAPOR_E_ARG, std::string("vapor_bam_chop_device: ") + e.what());
-    }
+    });
 }
 
 extern "C" int vapor_bam_chop_device(vapor_ctx* ctx, vapor_bam* bam, int32_t n_regions, const int32_t* tid, const int64_t* start,
@@ -1393,33 +1349,18 @@ extern "C" int vapor_bam_last_stats(vapor_ctx* ctx, double* out, int32_t n)
 // arena's limit leaves its windows to the host (VAPOR_FASTA_ROOM).  Everything runs on the context's own stream and is
 // synchronised before the call's blocks go back to the pool (BlockPool: no block is handed back while a kernel may read it).
 // ------------------------------------------------------------------------------------------
-namespace {
-struct FaStretch {                 // compressed bytes [c0, c_end) of the file, read at once; holds the blocks of its windows
-    int64_t c0 = 0, c_last = 0;    // first block; the last needed block starts at c_last (need_last) or ends there
-    bool need_last = false;
-    size_t want = 0, got = 0, stage_off = 0;
-    std::vector<int64_t> coff;     // every block scanned, in file order, and behind them the offset after the last one
-    std::vector<uint64_t> u;       // ... their data's offset inside the stretch (64-bit), the sentinel's = the stretch's size
-    std::vector<uint32_t> isize;
-    std::vector<uint32_t> gidx;    // ... the number of non-empty blocks before them in the call's block table
-    bool cut = false;              // the scan stopped at a damaged or missing block: windows behind it are not found
-    bool room = true;
-    uint64_t arena_off = 0;
-};
-}  // namespace
-
 extern "C" int vapor_fasta_windows_device(vapor_ctx* ctx, int fd, int32_t n, const uint64_t* vbeg, const uint64_t* vend, uint8_t* text,
                                           int64_t text_cap, int64_t* text_off, uint8_t* traits, int32_t* status)
 {
     using namespace vapor_bamdev;
     using namespace vapor_fasta;
+    using vapor_bgzf::FaStretch;
     if (!ctx || fd < 0 || n < 0 || text_cap < 0 || !text_off || (n && (!vbeg || !vend || !traits || !status)) || (text_cap && !text))
         return fail(VAPOR_E_ARG, "vapor_fasta_windows_device: bad argument");
     HIPCHK(hipSetDevice(ctx->device));
-    auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t0 = now();
+    const double t0 = now_ms();
     constexpr uint64_t ARENA_CAP = (uint64_t)1 << 30, STAGE_CAP = (uint64_t)1 << 29;
-    try {
+    return guarded("vapor_fasta_windows_device", [&]() -> int {
         // ---- windows in file order, merged into stretches --------------------------------------------------------------------
         std::vector<int32_t> order;
         order.reserve((size_t)n);
@@ -1453,17 +1394,7 @@ extern "C" int vapor_fasta_windows_device(vapor_ctx* ctx, int fd, int32_t n, con
             if (s.need_last) {
                 uint8_t h[64];
                 const ssize_t r = pread(fd, h, sizeof h, (off_t)s.c_last);
-                int bsize = -1;
-                if (r >= 18 && h[0] == 0x1f && h[1] == 0x8b && h[2] == 8 && (h[3] & 4)) {
-                    const int xlen = std::min<int>(h[10] | (h[11] << 8), (int)r - 12);
-                    for (int q = 0; q + 6 <= xlen;) {
-                        const uint8_t* e = h + 12 + q;
-                        const int slen = e[2] | (e[3] << 8);
-                        if (e[0] == 66 && e[1] == 67 && slen == 2) bsize = (e[4] | (e[5] << 8)) + 1;
-                        q += 4 + slen;
-                    }
-                }
-                last_size = bsize > 0 ? (uint64_t)bsize : 65536u;
+                last_size = vapor_bgzf::last_block_size(h, (size_t)std::max<ssize_t>(r, 0));
             }
             const uint64_t want = (uint64_t)(s.c_last - s.c0) + last_size;
             if (stage_bytes + want > STAGE_CAP) { s.room = false; continue; }
@@ -1472,95 +1403,40 @@ extern "C" int vapor_fasta_windows_device(vapor_ctx* ctx, int fd, int32_t n, con
             stage_bytes += (want + 63) & ~(uint64_t)63;
         }
         CallScope sc(ctx, ctx->stream);
-        HostBlock<> h_comp(sc), h_meta(sc), h_text(sc);
-        Block<> d_comp(sc), d_arena(sc), d_meta(sc), d_text(sc);
-        HIPCHK(h_comp.ensure((size_t)std::max<uint64_t>(stage_bytes, 64)));
+        InflateStage stage(sc);
+        HostBlock<>& h_meta = stage.h_meta;
+        HostBlock<> h_text(sc);
+        Block<>& d_meta = stage.d_meta;
+        Block<> d_arena(sc), d_text(sc);
+        HIPCHK(stage.begin((size_t)stage_bytes));
         uint64_t read_bytes = 0;
         for (FaStretch& s : sts) {
             if (!s.room) continue;
-            size_t got = 0;
-            while (got < s.want) {
-                const ssize_t r = pread(fd, h_comp + s.stage_off + got, s.want - got, (off_t)(s.c0 + (int64_t)got));
-                if (r <= 0) break;
-                got += (size_t)r;
-            }
-            s.got = got;
-            read_bytes += got;
-            const uint8_t* base = h_comp + s.stage_off;
-            size_t p = 0;
-            uint64_t u = 0;
-            for (;;) {
-                const int64_t coff = s.c0 + (int64_t)p;
-                if (coff > s.c_last || (coff == s.c_last && !s.need_last)) break;
-                if (p + 18 > got) { s.cut = true; break; }
-                const uint8_t* h = base + p;
-                if (h[0] != 0x1f || h[1] != 0x8b || h[2] != 8 || !(h[3] & 4)) { s.cut = true; break; }
-                const int xlen = h[10] | (h[11] << 8);
-                if (p + 12 + (size_t)xlen > got) { s.cut = true; break; }
-                int bsize = -1;
-                for (int q = 0; q + 4 <= xlen;) {
-                    const uint8_t* e = h + 12 + q;
-                    const int slen = e[2] | (e[3] << 8);
-                    if (e[0] == 66 && e[1] == 67 && slen == 2 && q + 6 <= xlen) bsize = (e[4] | (e[5] << 8)) + 1;
-                    q += 4 + slen;
-                }
-                if (bsize < 0 || bsize < xlen + 20 || p + (size_t)bsize > got) { s.cut = true; break; }
-                const uint8_t* t = h + bsize - 8;
-                const uint32_t crc = (uint32_t)t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
-                const uint32_t isz = (uint32_t)t[4] | ((uint32_t)t[5] << 8) | ((uint32_t)t[6] << 16) | ((uint32_t)t[7] << 24);
-                if (isz > 65536u || (isz == 0 && crc != 0)) { s.cut = true; break; }
-                s.coff.push_back(coff);
-                s.u.push_back(u);
-                s.isize.push_back(isz);
-                s.gidx.push_back(0);
-                u += isz;
-                p += (size_t)bsize;
-            }
-            s.coff.push_back(s.c0 + (int64_t)p);
-            s.u.push_back(u);
-            s.isize.push_back(0);
-            s.gidx.push_back(0);
+            s.got = stage.read(fd, s.stage_off, s.want, s.c0);
+            read_bytes += s.got;
+            vapor_bgzf::scan_stretch(s, stage.h_comp);
         }
         // ---- layout: the arena (64-bit offsets, a limit), the block table ------------------------------------------------------
         std::vector<BgzfBlk> blks;
         uint64_t arena = 0;
         for (FaStretch& s : sts) {
             if (!s.room) continue;
-            const uint64_t size = s.u.back();
+            const uint64_t size = s.blks.back().u;
             if (arena + size + 64 > ARENA_CAP) { s.room = false; continue; }
             s.arena_off = arena;
-            for (size_t k = 0; k + 1 < s.coff.size(); ++k) {
+            for (size_t k = 0; k < s.blks.size(); ++k) {
                 s.gidx[k] = (uint32_t)blks.size();
-                if (!s.isize[k]) continue;
-                const size_t p = (size_t)(s.coff[k] - s.c0);
-                const uint8_t* h = h_comp + s.stage_off + p;
-                const int xlen = h[10] | (h[11] << 8);
-                int bsize = 0;
-                for (int q = 0; q + 4 <= xlen;) {
-                    const uint8_t* e = h + 12 + q;
-                    const int slen = e[2] | (e[3] << 8);
-                    if (e[0] == 66 && e[1] == 67 && slen == 2 && q + 6 <= xlen) bsize = (e[4] | (e[5] << 8)) + 1;
-                    q += 4 + slen;
-                }
-                BgzfBlk b;
-                b.c_off = (uint32_t)(s.stage_off + p + 12 + (size_t)xlen);
-                b.c_len = (uint32_t)(bsize - xlen - 20);
-                b.u_off = (uint32_t)(arena + s.u[k]);
-                b.u_len = s.isize[k];
-                const uint8_t* t = h + bsize - 8;
-                b.crc = (uint32_t)t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
-                b.pad = 0;
-                blks.push_back(b);
+                if (s.blks[k].isize) blks.push_back(InflateStage::blk(s.stage_off, s.blks[k], arena));
             }
-            s.gidx.back() = (uint32_t)blks.size();
             arena += (size + 63) & ~(uint64_t)63;
         }
         // ---- the windows: their bytes in the arena, their slots in the text buffer --------------------------------------------
         std::vector<FastaWin> wins((size_t)std::max(n, 1));
         uint64_t slots = 0;
         auto find = [](const FaStretch& s, int64_t coff) -> int64_t {
-            auto it = std::lower_bound(s.coff.begin(), s.coff.end(), coff);
-            return it != s.coff.end() && *it == coff ? (int64_t)(it - s.coff.begin()) : -1;
+            const size_t pos = (size_t)(coff - s.c0);
+            auto it = std::lower_bound(s.blks.begin(), s.blks.end(), pos, [](const vapor_bgzf::Block& b, size_t p) { return b.pos < p; });
+            return it != s.blks.end() && it->pos == pos ? (int64_t)(it - s.blks.begin()) : -1;
         };
         for (int32_t i = 0; i < n; ++i) {
             FastaWin& W = wins[(size_t)i];
@@ -1571,13 +1447,13 @@ extern "C" int vapor_fasta_windows_device(vapor_ctx* ctx, int fd, int32_t n, con
             if (!s.room) { status[i] = WIN_ROOM; continue; }
             const int64_t kb = find(s, (int64_t)(vbeg[i] >> 16)), ke = find(s, (int64_t)(vend[i] >> 16));
             const uint32_t ub = (uint32_t)(vbeg[i] & 0xFFFFu), ue = (uint32_t)(vend[i] & 0xFFFFu);
-            const bool last_is_sentinel = ke == (int64_t)s.coff.size() - 1;
-            if (kb < 0 || ke < 0 || kb == (int64_t)s.coff.size() - 1 || ub > s.isize[(size_t)kb] || ue > s.isize[(size_t)ke] || (last_is_sentinel && ue)) {
+            const bool last_is_sentinel = ke == (int64_t)s.blks.size() - 1;
+            if (kb < 0 || ke < 0 || kb == (int64_t)s.blks.size() - 1 || ub > s.blks[(size_t)kb].isize || ue > s.blks[(size_t)ke].isize || (last_is_sentinel && ue)) {
                 status[i] = s.cut ? WIN_BLOCK : WIN_RANGE;
                 continue;
             }
-            W.a_beg = s.arena_off + s.u[(size_t)kb] + ub;
-            W.a_end = s.arena_off + s.u[(size_t)ke] + ue;
+            W.a_beg = s.arena_off + s.blks[(size_t)kb].u + ub;
+            W.a_end = s.arena_off + s.blks[(size_t)ke].u + ue;
             if (W.a_end < W.a_beg) { status[i] = WIN_RANGE; W.a_end = W.a_beg; continue; }
             const uint64_t len = W.a_end - W.a_beg;
             if (slots + len > (uint64_t)text_cap) { status[i] = WIN_ROOM; W.a_end = W.a_beg; continue; }
@@ -1588,32 +1464,20 @@ extern "C" int vapor_fasta_windows_device(vapor_ctx* ctx, int fd, int32_t n, con
         }
         // ---- the device: copies, two kernels, the answers back -----------------------------------------------------------------
         const size_t n_blks = blks.size(), nw = (size_t)std::max(n, 1);
-        const size_t o_blk = 0, o_win = o_blk + ((sizeof(BgzfBlk) * std::max<size_t>(n_blks, 1) + 63) & ~(size_t)63);
-        const size_t o_st = o_win + ((sizeof(FastaWin) * nw + 63) & ~(size_t)63);
-        const size_t in_bytes = o_st + ((4 * nw + 63) & ~(size_t)63);
-        const size_t o_len = in_bytes, o_tr = o_len + ((8 * nw + 63) & ~(size_t)63);
-        const size_t o_bst = o_tr + ((nw + 63) & ~(size_t)63);
+        Carve m;
+        m.take(sizeof(BgzfBlk) * std::max<size_t>(n_blks, 1));
+        const size_t o_win = m.take(sizeof(FastaWin) * nw), o_st = m.take(4 * nw);
+        const size_t in_bytes = m.off;
+        const size_t o_len = m.take(8 * nw), o_tr = m.take(nw), o_bst = m.off;
         const size_t meta_bytes = o_bst + 4 * std::max<size_t>(n_blks, 1);
-        HIPCHK(h_meta.ensure(meta_bytes));
-        HIPCHK(d_meta.ensure(meta_bytes));
-        HIPCHK(d_comp.ensure((size_t)std::max<uint64_t>(stage_bytes, 64)));
+        if (const int rc = stage.alloc(meta_bytes, meta_bytes)) return rc;
         HIPCHK(d_arena.ensure((size_t)arena + 64));
         HIPCHK(d_text.ensure((size_t)std::max<uint64_t>(slots, 64)));
         HIPCHK(h_text.ensure((size_t)std::max<uint64_t>(slots, 64)));
-        HIPCHK(crc_pow_on_device(ctx));
-        if (n_blks) memcpy(h_meta + o_blk, blks.data(), sizeof(BgzfBlk) * n_blks);
         memcpy(h_meta + o_win, wins.data(), sizeof(FastaWin) * nw);
         if (n) memcpy(h_meta + o_st, status, 4 * (size_t)n);
         hipStream_t st = ctx->stream;
-        if (!ctx->fasta_ev[0]) { HIPCHK(hipEventCreate(&ctx->fasta_ev[0])); HIPCHK(hipEventCreate(&ctx->fasta_ev[1])); }
-        if (stage_bytes) HIPCHK(hipMemcpyAsync(d_comp, h_comp, (size_t)stage_bytes, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(d_meta, h_meta, in_bytes, hipMemcpyHostToDevice, st));
-        HIPCHK(hipEventRecord(ctx->fasta_ev[0], st));
-        if (n_blks) {
-            hipLaunchKernelGGL(bgzf_inflate_kernel, dim3((unsigned)((n_blks + INFLATE_WAVES - 1) / INFLATE_WAVES)), dim3(64 * INFLATE_WAVES), 0, st, d_comp,
-                               reinterpret_cast<const BgzfBlk*>(d_meta + o_blk), (int)n_blks, d_arena, ctx->d_crc_pow, reinterpret_cast<int32_t*>(d_meta + o_bst));
-            HIPCHK(hipGetLastError());
-        }
+        if (const int rc = stage.run(blks, in_bytes, o_bst, d_arena, ctx->fasta_ev)) return rc;
         if (n) {
             hipLaunchKernelGGL(fasta_window_kernel, dim3((unsigned)((nw + WIN_WAVES - 1) / WIN_WAVES)), dim3(64 * WIN_WAVES), 0, st, d_arena,
                                reinterpret_cast<const FastaWin*>(d_meta + o_win), (int)n, reinterpret_cast<const int32_t*>(d_meta + o_bst), d_text,
@@ -1642,13 +1506,9 @@ extern "C" int vapor_fasta_windows_device(vapor_ctx* ctx, int fd, int32_t n, con
         float ms = 0.f;
         if (hipEventElapsedTime(&ms, ctx->fasta_ev[0], ctx->fasta_ev[1]) != hipSuccess) ms = 0.f;
         ctx->fasta_stats[0] = n; ctx->fasta_stats[1] = (double)n_blks; ctx->fasta_stats[2] = (double)read_bytes;
-        ctx->fasta_stats[3] = (double)arena; ctx->fasta_stats[4] = ms; ctx->fasta_stats[5] = now() - t0;
+        ctx->fasta_stats[3] = (double)arena; ctx->fasta_stats[4] = ms; ctx->fasta_stats[5] = now_ms() - t0;
         return VAPOR_OK;
-    } catch (const std::bad_alloc&) {
-        return fail(VAPOR_E_NOMEM, "vapor_fasta_windows_device: out of memory");
-    } catch (const std::exception& e) {
-        return fail(VAPOR_E_ARG, std::string("vapor_fasta_windows_device: ") + e.what());
-    }
+    });
 }
 
 // what the context's last vapor_fasta_windows_device did: windows, distinct blocks inflated, compressed bytes read and sent,
