@@ -369,6 +369,23 @@ int vapor_bam_chop(vapor_bam* bam, int32_t tid, int64_t start, int64_t end, int6
 int vapor_bam_chop_tagged(vapor_bam* bam, int32_t tid, int64_t start, int64_t end, int64_t flank, int32_t n_chunks,
                           const uint64_t* chunks, uint8_t* seq_out, int64_t seq_cap, char* names_out, int64_t names_cap,
                           int64_t* meta, int32_t max_reads, int32_t* n_reads, int64_t* need);
+/*
+ * vapor_bam_chop_tagged for a file that is NOT haplotagged (`--phase-vcf`; not in the reference, which reads nothing behind SEQ,
+ * SF:339-354): hap and ps of every kept read are made from the phased heterozygous SNVs of the locus, and the record's own HP /
+ * PS fields are not read.  The n_sites sites of the locus - those of its contig within VAPOR_PHASE_REACH of [start, end] - come
+ * in position order, none twice: site_pos (1-based), site_a1 / site_a2 = what haplotype 1 / 2 carries as a BAM 4-bit code
+ * (A C G T = 1 2 4 8), site_ps = the site's phase set.  The record's operations (the CG:B,I array where it has the long-CIGAR
+ * form) are walked with SAM's cursors, not cigar2alignstart_by_pos's: M = X advance reference and query, I S the query, D N the
+ * reference, H P neither.  A site inside an M, = or X operation reads its base of SEQ: a1 is one vote for haplotype 1 in the
+ * site's phase set, a2 one for haplotype 2, anything else none.  Among the phase sets with a vote the one with the most votes
+ * decides (ties to the smallest value): hap = 1 or 2 by its majority; on a tie or without a vote hap = 0 and ps = INT64_MIN.
+ * `meta` as in vapor_bam_chop_tagged; minimize_pacbio_read_list (SF:1091-1102) is the caller's, per group.
+ */
+#define VAPOR_PHASE_REACH 100000
+int vapor_bam_chop_haplotag(vapor_bam* bam, int32_t tid, int64_t start, int64_t end, int64_t flank, int32_t n_chunks,
+                            const uint64_t* chunks, uint8_t* seq_out, int64_t seq_cap, char* names_out, int64_t names_cap,
+                            int64_t* meta, int32_t max_reads, int32_t* n_reads, int64_t* need, int32_t n_sites,
+                            const int64_t* site_pos, const uint8_t* site_a1, const uint8_t* site_a2, const int64_t* site_ps);
 /* vapor_bam_chop for the right-anchored reads of the window (vapor_bam_chop_device_right has the rule): the same outputs, every
  * read written as the reverse complement of its part that ends on the window end ("=ACMGRSVTWYHKDBN" complemented by reversing
  * the bits of a symbol's code), miss_bp counted from there. */
@@ -416,6 +433,24 @@ int vapor_bam_chop_device_tagged(vapor_ctx* ctx, vapor_bam* bam, int32_t n_regio
                                  const int64_t* end, const int64_t* flank, const int32_t* chunk_first, const uint64_t* chunks,
                                  int32_t max_keep, int32_t* kept_first, uint64_t* sq_addr, int64_t* q0, int64_t* miss,
                                  uint32_t* member, int64_t* phase_set, int32_t* tagged, int32_t* status, vapor_bam_batch** batch);
+/*
+ * vapor_bam_chop_device_tagged for a file that is not haplotagged (`--phase-vcf`; chop_pacbio_read_by_pos,
+ * SF:339-354, and minimize_pacbio_read_list, SF:1091-1102, as there): the same answer, with hap and ps of every kept record made
+ * on the device from the phased heterozygous SNVs of its region (vapor_bam_chop_haplotag has the rule) and the records' own HP /
+ * PS fields not read.  The chop kernel stores the place of every kept record's operations; bam_haplotag_kernel, one wavefront a
+ * kept record, walks them 64 a step against the region's sites and writes the tags the select kernel reads.  Region g's sites
+ * are entries site_first[g] .. site_first[g + 1] of `sites`, in position order, 8 bytes each: int32 pos (1-based), uint8 a1,
+ * uint8 a2 (BAM 4-bit codes), uint8 index of the site's phase set in the region's own table, uint8 0.  That table is entries
+ * ps_first[g] .. ps_first[g + 1] of ps_values, at most VAPOR_PHASE_SETS_DEVICE of them: a region with more (or with an index
+ * outside its table, or sites out of order) is left to the host route with a status of its own, as is every region the device
+ * hands back for the reasons above.  A library without a device does not have this entry.
+ */
+#define VAPOR_PHASE_SETS_DEVICE 64
+int vapor_bam_chop_device_haplotag(vapor_ctx* ctx, vapor_bam* bam, int32_t n_regions, const int32_t* tid, const int64_t* start,
+                                   const int64_t* end, const int64_t* flank, const int32_t* chunk_first, const uint64_t* chunks,
+                                   int32_t max_keep, int32_t* kept_first, uint64_t* sq_addr, int64_t* q0, int64_t* miss,
+                                   uint32_t* member, int64_t* phase_set, int32_t* tagged, int32_t* status, vapor_bam_batch** batch,
+                                   const int32_t* site_first, const void* sites, const int32_t* ps_first, const int64_t* ps_values);
 /*
  * vapor_bam_chop_device for the RIGHT-anchored reads of every region (`--both-ends`; not in the reference): the
  * alignments whose last reference base (POS + the M, = and D operations - 1) is at or behind the window end, walked from the far

@@ -56,12 +56,14 @@ EXPORTS = [
     "vapor_plan_set_grid", "vapor_plan_run_grid", "vapor_grid_pick",
     "vapor_bam_chop_tagged", "vapor_bam_chop_device_tagged",
     "vapor_chop_records_right", "vapor_chop_records_right_many", "vapor_bam_chop_right", "vapor_bam_chop_device_right",
+    "vapor_bam_chop_haplotag", "vapor_bam_chop_device_haplotag",
 ]
 # entry points a library may lack (the CPU twin of the C ABI has no wide or any-k route and no refinement kernel): bound when
 # present, and the engine's wide, any-k and grid methods raise NotImplementedError when they are not
 OPTIONAL_EXPORTS = ("vapor_wide_batch", "vapor_clean_hits_wide", "vapor_anyk_batch", "vapor_plan_set_grid", "vapor_plan_run_grid",
                     "vapor_grid_pick", "vapor_bam_chop_device_tagged",
-                    "vapor_chop_records_right", "vapor_chop_records_right_many", "vapor_bam_chop_right", "vapor_bam_chop_device_right")
+                    "vapor_chop_records_right", "vapor_chop_records_right_many", "vapor_bam_chop_right", "vapor_bam_chop_device_right",
+                    "vapor_bam_chop_device_haplotag")
 MAX_CANDIDATES = 128           # breakpoint refinement: candidates per locus (VAPOR_MAX_CANDIDATES)
 
 _lib = None
@@ -188,6 +190,7 @@ def bind(L: ctypes.CDLL) -> ctypes.CDLL:
     L.vapor_bam_chop.argtypes = [vp, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, vp,
                                  vp, ctypes.c_int64, vp, ctypes.c_int64, vp, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), vp]
     L.vapor_bam_chop_tagged.argtypes = L.vapor_bam_chop.argtypes
+    L.vapor_bam_chop_haplotag.argtypes = L.vapor_bam_chop.argtypes + [ctypes.c_int32, vp, vp, vp, vp]
     L.vapor_bam_chop_device.argtypes = [vp, vp, ctypes.c_int32, vp, vp, vp, vp, vp, vp, ctypes.c_int32, vp, vp, vp, vp, vp, ctypes.POINTER(vp)]
     L.vapor_bam_batch_destroy.argtypes = [vp]
     L.vapor_bam_last_stats.argtypes = [vp, vp, ctypes.c_int32]
@@ -223,6 +226,9 @@ def bind(L: ctypes.CDLL) -> ctypes.CDLL:
     if hasattr(L, "vapor_bam_chop_device_tagged"):
         L.vapor_bam_chop_device_tagged.argtypes = [vp, vp, ctypes.c_int32, vp, vp, vp, vp, vp, vp, ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp, vp,
                                                    ctypes.POINTER(vp)]
+    if hasattr(L, "vapor_bam_chop_device_haplotag"):
+        L.vapor_bam_chop_device_haplotag.argtypes = [vp, vp, ctypes.c_int32, vp, vp, vp, vp, vp, vp, ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                     ctypes.POINTER(vp), vp, vp, vp, vp]
     if hasattr(L, "vapor_chop_records_right"):
         L.vapor_chop_records_right.argtypes = L.vapor_chop_records.argtypes
     if hasattr(L, "vapor_chop_records_right_many"):

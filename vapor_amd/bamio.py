@@ -264,12 +264,13 @@ class BamFile:
         from . import phase
         return ref_id, pos, name, flag, cig, l_seq, sq, phase.tags_from_aux(rec, p + nb + l_seq)
 
-    def chop_native(self, chrom: str, start: int, end: int, flank_length: int, tagged: bool = False, right: bool = False):
+    def chop_native(self, chrom: str, start: int, end: int, flank_length: int, tagged: bool = False, right: bool = False, sites=None):
         """chop_pacbio_read_by_pos (SF:339-354) for one region through the library's native reader (vapor_bam_chop:
         threaded inflate, binary CIGAR walk, only kept bases decoded); the .bai lookup stays here.  Returns the same
         [[read tail, miss_bp, qname], ...] as the Python statement of it (seqio.InProcessBam.chop_python); with `tagged`
         (vapor_bam_chop_tagged) every entry also carries the record's hap and ps; with `right` (vapor_bam_chop_right, `--both-ends`)
-        the right-anchored reads of the window, reverse complemented (seqio._chop_records)."""
+        the right-anchored reads of the window, reverse complemented (seqio._chop_records).  sites (`--phase-vcf`, with tagged: a
+        phase.Sites): hap and ps come from the locus's phased sites instead (vapor_bam_chop_haplotag)."""
         import ctypes
         from . import _lib
         lib = _lib.load()
@@ -281,12 +282,24 @@ class BamFile:
             return []
         tl = self._take_handle(lib)
         try:
-            return self._chop_with(lib, tl, tid, ch, start, end, flank_length, tagged=tagged, right=right)
+            return self._chop_with(lib, tl, tid, ch, start, end, flank_length, tagged=tagged, right=right,
+                                   sites=self._locus_sites(sites, chrom, start, end) if tagged else None)
         finally:
             with self._lock:
                 self._free.append(tl)
 
-    def chop_native_raw(self, chrom: str, start: int, end: int, flank_length: int, tagged: bool = False, right: bool = False):
+    @staticmethod
+    def _locus_sites(sites, chrom, start, end):
+        """A locus's slice of a phase.Sites as the four arrays vapor_bam_chop_haplotag takes (empty ones without a site); None
+        when no Sites was given."""
+        if sites is None:
+            return None
+        v = sites.of(chrom, int(start), int(end))
+        if v is None:
+            return (np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.uint8), np.zeros(0, dtype=np.uint8), np.zeros(0, dtype=np.int64))
+        return tuple(np.ascontiguousarray(a) for a in v)
+
+    def chop_native_raw(self, chrom: str, start: int, end: int, flank_length: int, tagged: bool = False, right: bool = False, sites=None):
         """chop_native's answer as numbers: (text, offsets, lengths, miss_bp) - read r is text[offsets[r] : offsets[r] + lengths[r]]
         - for callers that hand the reads on by address (vapor_amd.fastpath) instead of making a string per read; with `tagged`
         also hap and ps per read (ps: phase.PS_NONE for none)."""
@@ -300,7 +313,8 @@ class BamFile:
             return None
         tl = self._take_handle(lib)
         try:
-            return self._chop_with(lib, tl, tid, ch, start, end, flank_length, raw=True, tagged=tagged, right=right)
+            return self._chop_with(lib, tl, tid, ch, start, end, flank_length, raw=True, tagged=tagged, right=right,
+                                   sites=self._locus_sites(sites, chrom, start, end) if tagged else None)
         finally:
             with self._lock:
                 self._free.append(tl)
@@ -325,7 +339,7 @@ class BamFile:
             self._handles.append(h)
         return tl
 
-    def _chop_with(self, lib, tl, tid, ch, start, end, flank_length, raw=False, tagged=False, right=False):
+    def _chop_with(self, lib, tl, tid, ch, start, end, flank_length, raw=False, tagged=False, right=False, sites=None):
         import ctypes
         from . import _lib
         chunks = np.asarray(ch, dtype=np.uint64).reshape(-1)
@@ -335,11 +349,15 @@ class BamFile:
             if tagged or not hasattr(lib, "vapor_bam_chop_right"):
                 raise NotImplementedError("no right-anchored native reader")
             fn = lib.vapor_bam_chop_right
+        more = ()
+        if sites is not None:
+            fn = lib.vapor_bam_chop_haplotag
+            more = (len(sites[0]),) + tuple(a.ctypes.data if len(a) else None for a in sites)
         while True:
             bf = tl["buf"]
             rc = fn(tl["native"], tid, int(start), int(end), int(flank_length), len(ch), chunks.ctypes.data,
                     bf["seq"].ctypes.data, bf["seq"].size, ctypes.cast(bf["names"], ctypes.c_void_p), len(bf["names"]),
-                    bf["meta"].ctypes.data, bf["meta"].size // w, ctypes.byref(n), bf["need"].ctypes.data)
+                    bf["meta"].ctypes.data, bf["meta"].size // w, ctypes.byref(n), bf["need"].ctypes.data, *more)
             if rc == 0:
                 break
             if rc != _lib.E_OVERFLOW:
@@ -384,10 +402,11 @@ class BamFile:
         except Exception:       # noqa: BLE001
             pass
 
-    def fetch_raw(self, chrom: str, start: int, end: int):
+    def fetch_raw(self, chrom: str, start: int, end: int, sites=None):
         """(QNAME, 1-based POS, CIGAR operations as a uint32 tuple, packed SEQ bytes, l_seq, FLAG, (hap, ps)) of the alignments
         that overlap the 1-based inclusive region, in file order; nothing is decoded to text.  (hap, ps): the record's
-        haplotype and phase set (phase.tags_from_aux)."""
+        haplotype and phase set (phase.tags_from_aux) - or, with sites (`--phase-vcf`: the locus's phased sites as
+        phase.haplotag takes them), what phase.haplotag makes of its CIGAR and SEQ, the record's own tags not looked at."""
         tid = self.tid.get(chrom)
         if tid is None:
             return []
@@ -408,6 +427,9 @@ class BamFile:
                 rlen = int(((cig >> 4) * _REF_OP[cig & 15]).sum()) if len(cig) else 0     # M, D, N, =, X consume reference
                 if pos + max(rlen, 1) <= beg:
                     continue
+                if sites is not None:
+                    from . import phase
+                    tags = phase.haplotag(pos + 1, cig, _decode_seq(sq, l_seq), sites)
                 out.append((name, pos + 1, cig, sq, l_seq, flag, tags))
         return out
 

@@ -12,7 +12,9 @@ grid of candidate breakpoints within M bp of every short DEL / INV / TANDUP call
 --phased (bed, vcf: read the HP and PS tags of a haplotagged BAM and score the reads of each haplotype of a DEL / INV / TANDUP /
 INS call beside the pooled list; appends VaPoR_PS, VaPoR_PGT, VaPoR_PGQ and QS / GS / Rec per haplotype; not
 together with --refine), --both-ends (bed, vcf: every junction branch - long DEL / INV, TANDUP, breakends - is scored from both of
-its sides, with right-anchored reads; appends the VaPoR_BE_* columns; not together with --refine or --phased).
+its sides, with right-anchored reads; appends the VaPoR_BE_* columns; not together with --refine or --phased),
+--phase-vcf FILE [--phase-sample NAME] (bed, vcf: --phased for a BAM that is NOT haplotagged - every read's haplotype and phase
+set come from its bases at the phased heterozygous SNVs of FILE; the HP / PS tags of the BAM are not read).
 """
 from __future__ import annotations
 
@@ -843,6 +845,12 @@ def build_parser() -> argparse.ArgumentParser:
                    help='bed, vcf: read the HP and PS tags of a haplotagged BAM; every DEL / INV / TANDUP / INS call is scored per '
                         'haplotype as well (the reads with HP 1, with HP 2, of the majority phase set): appends VaPoR_PS, VaPoR_PGT, '
                         'VaPoR_PGQ and VaPoR_H1_QS / _GS / _Rec, VaPoR_H2_QS / _GS / _Rec (vcf: to INFO); not together with --refine')
+    p.add_argument('--phase-vcf', metavar='FILE', default=None,
+                   help='bed, vcf: --phased for a BAM that is not haplotagged: FILE is a phased small-variant VCF of the sample (plain '
+                        'or gzipped); a read is assigned the haplotype most of its bases at the phased heterozygous SNVs within '
+                        '100 kb of the locus vote for, in the phase set with the most votes; the HP / PS tags of the BAM are not read')
+    p.add_argument('--phase-sample', metavar='NAME', default=None,
+                   help='with --phase-vcf: the sample column of FILE to read (default: the first)')
     p.add_argument('--both-ends', action='store_true',
                    help='bed, vcf: score every junction - a DEL or INV of 10 kb or more, the junction branch of a TANDUP, every '
                         'breakend of --bnd - from both of its sides: the reads that end behind the window (right-anchored) are scored '
@@ -852,6 +860,15 @@ def build_parser() -> argparse.ArgumentParser:
 
 
 def main(argv: Optional[List[str]] = None) -> int:
+    held: list = []                      # (`--phase-vcf`: the backend that carries the run's sites, for as long as the run lasts)
+    try:
+        return _main(argv, held)
+    finally:
+        for backend in held:
+            backend.phase_sites = None
+
+
+def _main(argv, held) -> int:
     argv = list(sys.argv[1:] if argv is None else argv)
     if len(argv) < 1:
         from . import prep
@@ -874,6 +891,10 @@ def main(argv: Optional[List[str]] = None) -> int:
             refine = rf.parse(args.refine)
         except ValueError as e:
             parser.error(str(e))
+    if args.phase_sample is not None and args.phase_vcf is None:
+        parser.error('--phase-sample names a sample of --phase-vcf: give that option too')
+    if args.phase_vcf is not None:
+        args.phased = True               # (the groups, the scoring and the columns are --phased's: only the tags' source differs)
     if args.phased:
         if mode not in ('bed', 'vcf'):
             parser.error('--phased applies to `vapor bed` and `vapor vcf`')
@@ -888,6 +909,16 @@ def main(argv: Optional[List[str]] = None) -> int:
         if args.phased:
             parser.error('--both-ends and --phased cannot be combined (right-anchored reads are not read with their tags)')
         from . import bothends as be
+    if args.phase_vcf is not None:
+        # (every rank reads the VCF itself; the sites ride on the backend the reads are taken through)
+        try:
+            sites = ph.read_sites(args.phase_vcf, args.phase_sample)
+        except (OSError, ValueError) as e:
+            parser.error('--phase-vcf: %s' % e)
+        from . import seqio
+        backend = seqio.get_backend()
+        backend.phase_sites = sites
+        held.append(backend)
     more = rf.COLUMNS if refine is not None else ph.COLUMNS if args.phased else be.COLUMNS if args.both_ends else ()
     figure_fn = None
     if not args.no_figures:

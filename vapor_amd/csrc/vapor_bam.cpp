@@ -310,11 +310,63 @@ done:
     *hap = (hp == 1 || hp == 2) ? hp : 0;
 }
 
+// The haplotag of a record from the phased heterozygous SNVs of its locus (`--phase-vcf`; vapor_amd/phase.py
+// haplotag is the statement): n sites in position order - pos 1-based, a1 / a2 what haplotype 1 / 2 carries as BAM 4-bit codes,
+// ps the site's phase set.  The record's operations are walked with SAM's cursors (M = X advance reference and query, I S the
+// query, D N the reference, H P neither); a site inside an M, = or X operation reads its base from the packed SEQ and votes for
+// haplotype 1 (a1), haplotype 2 (a2) or not at all.  The phase set with the most votes decides, ties to the smallest value.
+struct HapSites {
+    int32_t n;
+    const int64_t* pos;
+    const uint8_t* a1;
+    const uint8_t* a2;
+    const int64_t* ps;
+};
+static void haplotag_record(const uint8_t* ops, int32_t n_ops, int64_t pos1, const uint8_t* sq, int32_t l_seq, const HapSites& hs,
+                            int64_t* hap, int64_t* ps)
+{
+    struct Tally { int64_t ps, n1, n2; };
+    std::vector<Tally> tally;
+    int64_t rr = pos1, q = 0;
+    int32_t si = 0;
+    for (int32_t t = 0; t < n_ops && si < hs.n; ++t) {
+        const uint32_t o = (uint32_t)rd32(ops + 4 * t), code = o & 15u;
+        const int64_t n = o >> 4;
+        if (code == 0u || code == 7u || code == 8u) {
+            while (si < hs.n && hs.pos[si] < rr) ++si;
+            for (; si < hs.n && hs.pos[si] < rr + n; ++si) {
+                const int64_t qi = q + hs.pos[si] - rr;
+                if (qi >= l_seq) continue;
+                const uint8_t byte = sq[qi >> 1];
+                const uint8_t nib = (qi & 1) ? (byte & 15) : (byte >> 4);
+                const int vote = nib == hs.a1[si] ? 1 : nib == hs.a2[si] ? 2 : 0;
+                if (!vote) continue;
+                size_t k = 0;
+                while (k < tally.size() && tally[k].ps != hs.ps[si]) ++k;
+                if (k == tally.size()) tally.push_back({hs.ps[si], 0, 0});
+                ++(vote == 1 ? tally[k].n1 : tally[k].n2);
+            }
+            rr += n; q += n;
+        } else if (code == 1u || code == 4u) {
+            q += n;
+        } else if (code == 2u || code == 3u) {
+            rr += n;
+        }
+    }
+    *hap = 0;
+    *ps = VAPOR_PS_NONE;
+    const Tally* best = nullptr;
+    for (const Tally& t : tally)
+        if (!best || t.n1 + t.n2 > best->n1 + best->n2 || (t.n1 + t.n2 == best->n1 + best->n2 && t.ps < best->ps)) best = &t;
+    if (best && best->n1 != best->n2) { *hap = best->n1 > best->n2 ? 1 : 2; *ps = best->ps; }
+}
+
 // Every size field of the file is checked before it is used (a damaged ISIZE reached the inflaters as a
 // buffer size); a file that breaks a rule is VAPOR_E_ARG with a message, never a read or write outside `comp` / `data`.
 static int bam_chop_impl(vapor_bam* b, int32_t tid, int64_t start, int64_t end, int64_t flank, int32_t n_chunks,
                          const uint64_t* chunks, uint8_t* seq_out, int64_t seq_cap, char* names_out, int64_t names_cap,
-                         int64_t* meta, int32_t max_reads, int32_t* n_reads, int64_t* need, int meta_w = 4, bool right = false)
+                         int64_t* meta, int32_t max_reads, int32_t* n_reads, int64_t* need, int meta_w = 4, bool right = false,
+                         const HapSites* sites = nullptr)
 {
     if (!b || !n_reads || (n_chunks && !chunks)) return bfail(VAPOR_E_ARG, "vapor_bam_chop: null argument");
     if (seq_cap < 0 || names_cap < 0 || max_reads < 0 || (max_reads && (!meta || !seq_out || !names_out)))
@@ -485,7 +537,9 @@ static int bam_chop_impl(vapor_bam* b, int32_t tid, int64_t start, int64_t end, 
             names_out[names_used + nl] = 0;
             int64_t* m = meta + (size_t)meta_w * (size_t)nr;
             m[0] = seq_used; m[1] = want_len; m[2] = miss; m[3] = names_used;
-            if (meta_w == 6) find_tags(sq + (l_seq + 1) / 2 + l_seq, rec_end, m + 4, m + 5);
+            // (hap and ps: from the phased sites where the caller gave them - the record's own tags are not read then)
+            if (meta_w == 6 && sites) haplotag_record(ops, n_ops, (int64_t)pos + 1, sq, l_seq, *sites, m + 4, m + 5);
+            else if (meta_w == 6) find_tags(sq + (l_seq + 1) / 2 + l_seq, rec_end, m + 4, m + 5);
             seq_used += want_len; names_used += nl + 1; ++nr;
         }
     }
@@ -535,6 +589,28 @@ extern "C" int vapor_bam_chop_tagged(vapor_bam* b, int32_t tid, int64_t start, i
         return bfail(VAPOR_E_NOMEM, "vapor_bam_chop_tagged: out of memory");
     } catch (const std::exception& e) {
         return bfail(VAPOR_E_ARG, std::string("vapor_bam_chop_tagged: ") + e.what());
+    }
+}
+
+// vapor_bam_chop_tagged with hap and ps made from the phased heterozygous SNVs of the locus instead of the record's HP / PS
+// fields, which are not read (`--phase-vcf`; haplotag_record): n_sites sites in position order, none twice.
+extern "C" int vapor_bam_chop_haplotag(vapor_bam* b, int32_t tid, int64_t start, int64_t end, int64_t flank, int32_t n_chunks,
+                                       const uint64_t* chunks, uint8_t* seq_out, int64_t seq_cap, char* names_out, int64_t names_cap,
+                                       int64_t* meta, int32_t max_reads, int32_t* n_reads, int64_t* need, int32_t n_sites,
+                                       const int64_t* site_pos, const uint8_t* site_a1, const uint8_t* site_a2, const int64_t* site_ps)
+{
+    if (n_sites < 0 || (n_sites && (!site_pos || !site_a1 || !site_a2 || !site_ps)))
+        return bfail(VAPOR_E_ARG, "vapor_bam_chop_haplotag: bad site arrays");
+    for (int32_t i = 1; i < n_sites; ++i)
+        if (!(site_pos[i - 1] < site_pos[i])) return bfail(VAPOR_E_ARG, "vapor_bam_chop_haplotag: the sites are not in position order");
+    try {
+        const HapSites hs{n_sites, site_pos, site_a1, site_a2, site_ps};
+        return bam_chop_impl(b, tid, start, end, flank, n_chunks, chunks, seq_out, seq_cap, names_out, names_cap, meta, max_reads, n_reads, need, 6,
+                             false, &hs);
+    } catch (const std::bad_alloc&) {
+        return bfail(VAPOR_E_NOMEM, "vapor_bam_chop_haplotag: out of memory");
+    } catch (const std::exception& e) {
+        return bfail(VAPOR_E_ARG, std::string("vapor_bam_chop_haplotag: ") + e.what());
     }
 }
 
@@ -921,6 +997,16 @@ extern "C" __attribute__((weak)) int vapor_bam_chop_device_tagged(vapor_ctx*, va
                                                                   int64_t*, int64_t*, uint32_t*, int64_t*, int32_t*, int32_t*, vapor_bam_batch**)
 {
     return bfail(VAPOR_E_ARG, "vapor_bam_chop_device_tagged: this build has no device reader");
+}
+
+// ... so is the one that haplotags the reads from phased SNVs (vapor_bam_chop_device_haplotag: bam_haplotag_kernel; the host
+// readers take vapor_bam_chop_haplotag) ...
+extern "C" __attribute__((weak)) int vapor_bam_chop_device_haplotag(vapor_ctx*, vapor_bam*, int32_t, const int32_t*, const int64_t*, const int64_t*,
+                                                                    const int64_t*, const int32_t*, const uint64_t*, int32_t, int32_t*, uint64_t*,
+                                                                    int64_t*, int64_t*, uint32_t*, int64_t*, int32_t*, int32_t*, vapor_bam_batch**,
+                                                                    const int32_t*, const void*, const int32_t*, const int64_t*)
+{
+    return bfail(VAPOR_E_ARG, "vapor_bam_chop_device_haplotag: this build has no device reader");
 }
 
 // ... and so is the right-anchored one (vapor_bam_chop_device_right: bam_chop_right_kernel).

@@ -851,6 +851,7 @@ struct BamKept {          // a read the reference keeps: its packed bases at are
 constexpr int KEPT_CAP = 256;      // kept reads a region's slot holds (minimize_pacbio_read_list keeps 20 of them)
 // status of a region: 0, or why the host route must do it
 constexpr int REG_OK = 0, REG_BEYOND = 1, REG_MALFORMED = 2, REG_NO_CIGAR = 3, REG_KEPT_FULL = 4, REG_BLOCK = 5, REG_NEG_Q0 = 6, REG_NO_SEQ = 7;
+constexpr int REG_PHASE_SETS = 8;  // (`--phase-vcf`) more phase sets among the region's sites than a wavefront tallies: set by the host, before anything is sent
 
 __device__ __forceinline__ uint32_t rd32u(const uint8_t* p)
 {
@@ -913,6 +914,25 @@ struct BamPhase {         // a region's answer: its phase set P, whether any kep
     long long ps;
     int32_t tagged, n_union;
 };
+
+// ---- haplotags from phased SNVs (`--phase-vcf`) --------------------------------------------------------------
+struct BamOps {           // beside a region's BamKept entry, in an array of its own: where bam_haplotag_kernel finds the record
+    uint32_t ops_off;     // its operations in the arena (the CIGAR, or the CG:B,I array of a long-CIGAR record)
+    int32_t n_ops;
+    int32_t pos;          // 0-based POS
+    uint32_t sq_off;      // its packed bases
+};
+struct BamSite {          // a phased heterozygous SNV of a region, 8 B
+    int32_t pos;          // 1-based
+    uint8_t a1, a2;       // what haplotype 1 / 2 carries, BAM 4-bit codes
+    uint8_t ps_idx, pad;  // its phase set: index into the region's table, below PHASE_SETS_CAP
+};
+struct BamSiteRange {     // a region's sites (in position order) and its table of phase-set values
+    int32_t site_first, site_n, ps_first, ps_n;
+};
+constexpr int PHASE_SETS_CAP = 64;     // phase sets a wavefront tallies: lane p holds the two counts of phase set p
+constexpr int HAPLOTAG_WAVES = 4;      // kept records a workgroup of bam_haplotag_kernel takes, a wavefront each
+static_assert(sizeof(BamOps) == 16 && sizeof(BamSite) == 8, "the side arrays' entry sizes");
 
 // One walk over a record's aux fields [p, end) for the first HP and PS fields of integer type and - WANT_CG - the CG:B,I array
 // (vapor_bam.cpp find_tags and find_cg are the statement).  Wave-uniform like find_cg_dev: every lane reads the same bytes, but
@@ -983,11 +1003,13 @@ __device__ __forceinline__ bool walk_aux_dev(const uint8_t* arena, uint32_t p, u
 // end, their CIGAR walked from its far end - a first pass over the operations for the reference length, a second over the tiles in
 // reverse, lane l on operation n_ops - 1 - (t0 + l), so that the inclusive scans are suffix sums.  The entry's q0 is then the read
 // base the reverse-complemented read starts with (l_seq - 1 - the bases dropped from the read's end), miss counts from the end.
-template <bool TAGGED, bool RIGHT = false>
+// OPS (`--phase-vcf`): no aux walk for tags; where every kept record's operations, POS and bases lie goes to
+// opsv[] beside its BamKept entry, for bam_haplotag_kernel.
+template <bool TAGGED, bool RIGHT = false, bool OPS = false>
 __device__ __forceinline__ void bam_chop_body(const uint8_t* __restrict__ arena, const BamRegion* __restrict__ regs,
                                               const BamSpan* __restrict__ spans, const int32_t* __restrict__ blk_status, int n_regs,
                                               BamKept* __restrict__ kept, int32_t* __restrict__ n_kept, int32_t* __restrict__ reg_status,
-                                              BamTag* __restrict__ tags)
+                                              BamTag* __restrict__ tags, BamOps* __restrict__ opsv = nullptr)
 {
     const int g = (int)blockIdx.x;
     if (g >= n_regs) return;
@@ -1140,6 +1162,9 @@ __device__ __forceinline__ void bam_chop_body(const uint8_t* __restrict__ arena,
                 }
                 if (lane == 0) tags[(size_t)g * KEPT_CAP + (size_t)nk] = BamTag{ps, hap, 0};
             }
+            if constexpr (OPS) {
+                if (lane == 0) opsv[(size_t)g * KEPT_CAP + (size_t)nk] = BamOps{ops, n_ops, pos, sq};
+            }
             if (lane == 0) kept[(size_t)g * KEPT_CAP + (size_t)nk] = BamKept{sq, (int32_t)(RIGHT ? (long long)l_seq - 1 - q0 : q0), (int32_t)miss, l_seq};
             ++nk;
         }
@@ -1167,6 +1192,107 @@ __global__ __launch_bounds__(64) void bam_chop_tagged_kernel(const uint8_t* __re
                                                             BamTag* __restrict__ tags)
 {
     bam_chop_body<true>(arena, regs, spans, blk_status, n_regs, kept, n_kept, reg_status, tags);
+}
+
+__global__ __launch_bounds__(64) void bam_chop_ops_kernel(const uint8_t* __restrict__ arena, const BamRegion* __restrict__ regs,
+                                                         const BamSpan* __restrict__ spans, const int32_t* __restrict__ blk_status, int n_regs,
+                                                         BamKept* __restrict__ kept, int32_t* __restrict__ n_kept, int32_t* __restrict__ reg_status,
+                                                         BamOps* __restrict__ opsv)
+{
+    bam_chop_body<false, false, true>(arena, regs, spans, blk_status, n_regs, kept, n_kept, reg_status, nullptr, opsv);
+}
+
+// The haplotag of every kept record from the phased heterozygous SNVs of its region (`--phase-vcf`, DESIGN.md 4.15;
+// vapor_amd/phase.py haplotag is the statement, vapor_bam.cpp haplotag_record the host's): between bam_chop_ops_kernel and
+// bam_select_kernel on their stream, one wavefront a kept record (HAPLOTAG_WAVES of them a workgroup, KEPT_CAP / HAPLOTAG_WAVES
+// workgroups a region; a wavefront without a record ends at once).  The record's operations go 64 a step, a lane each, with
+// SAM's cursors as inclusive scans (reference: M D N = X; query: M I S = X).  The region's sites, in position order, are
+// consumed against each tile's reference range 64 a step; the lane whose M / = / X operation covers a site reads its base - the
+// nibble arena[sq_off + (qi >> 1)], the high one for an even qi - and the vote goes to the lane that holds the site's phase set
+// (its index in the region's table is below 64).  The pick - most votes, ties to the smallest ps value - is one wave reduction.
+// What the chop kernel has checked is relied on: the operations and the packed bases lie inside the record (n_cig, l_seq and the
+// CG array against the record's size), so no read here leaves it - a base index at or behind l_seq votes nothing.
+__global__ __launch_bounds__(64 * HAPLOTAG_WAVES) void bam_haplotag_kernel(const uint8_t* __restrict__ arena, const BamKept* __restrict__ kept,
+                                                                          const BamOps* __restrict__ opsv, const int32_t* __restrict__ n_kept,
+                                                                          const int32_t* __restrict__ reg_status, int n_regs,
+                                                                          const BamSiteRange* __restrict__ ranges, const BamSite* __restrict__ sites,
+                                                                          const long long* __restrict__ ps_values, BamTag* __restrict__ tags)
+{
+    constexpr int PER = KEPT_CAP / HAPLOTAG_WAVES;
+    const int g = (int)(blockIdx.x / PER);
+    const int slot = __builtin_amdgcn_readfirstlane((int)(blockIdx.x % PER) * HAPLOTAG_WAVES + (int)(threadIdx.x >> 6));
+    if (g >= n_regs || reg_status[g] != REG_OK || slot >= n_kept[g]) return;
+    const uint32_t lane = threadIdx.x & 63u;
+    const size_t e = (size_t)g * KEPT_CAP + (size_t)slot;
+    const BamOps O = opsv[e];
+    const long long l_seq = kept[e].l_seq;
+    const BamSiteRange SR = ranges[g];
+    const BamSite* S = sites + SR.site_first;
+    const int ns = SR.site_n;
+    int n1 = 0, n2 = 0;                         // lane p: the votes of phase set p for haplotype 1 / 2
+    long long rr = (long long)O.pos + 1, q = 0; // the cursors before the tile: 1-based reference position, query index
+    int si = 0;                                 // sites consumed (wave-uniform)
+    // the sites before the alignment's first base
+    while (si < ns) {
+        const int j = si + (int)lane;
+        const unsigned long long m = __ballot(j < ns && (long long)S[j].pos < rr);
+        const int c = m == ~0ull ? 64 : __ffsll((long long)~m) - 1;
+        si += c;
+        if (c < 64) break;
+    }
+    for (int32_t t0 = 0; t0 < O.n_ops && si < ns; t0 += 64) {
+        const int32_t t = t0 + (int32_t)lane;
+        const uint32_t o = t < O.n_ops ? rd32u(arena + O.ops_off + 4u * (uint32_t)t) : 15u;     // (code 15 advances nothing)
+        const uint32_t code = o & 15u;
+        const long long n = (long long)(o >> 4);
+        const bool both = code == 0u || code == 7u || code == 8u;
+        const long long a = (both || code == 2u || code == 3u) ? n : 0;
+        const long long c = (both || code == 1u || code == 4u) ? n : 0;
+        const long long A = wave_scan64(a, lane), C = wave_scan64(c, lane);
+        const long long lo = rr + A - a, hi = rr + A, qs = q + C - c;     // this lane's operation: reference [lo, hi), query from qs
+        const long long tile_end = rr + __shfl(A, 63);
+        // the sites below the tile's end, in order (a site inside a D or N operation finds no lane)
+        while (si < ns) {
+            const int j = si + (int)lane;
+            int32_t s_pos = 0;
+            uint32_t s_al = 0;
+            if (j < ns) { const BamSite s = S[j]; s_pos = s.pos; s_al = (uint32_t)s.a1 | ((uint32_t)s.a2 << 8) | ((uint32_t)s.ps_idx << 16); }
+            const unsigned long long m = __ballot(j < ns && (long long)s_pos < tile_end);
+            const int cnt = m == ~0ull ? 64 : __ffsll((long long)~m) - 1;
+            for (int k = 0; k < cnt; ++k) {
+                const long long v = (long long)__shfl(s_pos, k);
+                const uint32_t al = __shfl(s_al, k);
+                int vote = 0;
+                if (both && v >= lo && v < hi) {
+                    const long long qi = qs + (v - lo);
+                    if (qi < l_seq) {
+                        const uint32_t byte = arena[O.sq_off + (uint32_t)(qi >> 1)];
+                        const uint32_t nib = (qi & 1) ? (byte & 15u) : (byte >> 4);
+                        vote = nib == (al & 255u) ? 1 : nib == ((al >> 8) & 255u) ? 2 : 0;
+                    }
+                }
+                const int v1 = __any(vote == 1) ? 1 : 0, v2 = __any(vote == 2) ? 1 : 0;
+                if (lane == ((al >> 16) & 63u)) { n1 += v1; n2 += v2; }
+            }
+            si += cnt;
+            if (cnt < 64) break;
+        }
+        rr = tile_end;
+        q += __shfl(C, 63);
+    }
+    // the phase set with the most votes, ties to the smallest value
+    int bt = n1 + n2, b1 = n1, b2 = n2;
+    long long bk = (int)lane < SR.ps_n ? ps_values[SR.ps_first + (int)lane] : 0x7FFFFFFFFFFFFFFFll;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const int ot = __shfl_xor(bt, d), o1 = __shfl_xor(b1, d), o2 = __shfl_xor(b2, d);
+        const long long ok = __shfl_xor(bk, d);
+        if (ot > bt || (ot == bt && ok < bk)) { bt = ot; b1 = o1; b2 = o2; bk = ok; }
+    }
+    if (lane == 0) {
+        const bool called = bt > 0 && b1 != b2;
+        tags[e] = BamTag{called ? bk : PS_NONE, called ? (b1 > b2 ? 1 : 2) : 0, 0};
+    }
 }
 
 // The groups of a phased region (vapor_amd/phase.py select is the statement): one wavefront a region, right after the chop

@@ -1043,21 +1043,39 @@ static int guarded(const char* name, F body)
     }
 }
 
+// the phased sites of a vapor_bam_chop_device_haplotag call, as its caller gave them
+struct HaplotagIn {
+    const int32_t* site_first;
+    const vapor_bamdev::BamSite* sites;
+    const int32_t* ps_first;
+    const int64_t* ps_values;
+};
+
 // vapor_bam_chop_device, and with `member` (vapor_bam_chop_device_tagged) the phased form of it: the tagged chop kernel, the
-// select kernel behind it on the same stream, and only the regions' compact unions and phase sets copied back.
+// select kernel behind it on the same stream, and only the regions' compact unions and phase sets copied back.  With `hin`
+// (vapor_bam_chop_device_haplotag) the tags the select kernel reads come from bam_haplotag_kernel, which runs between the two.
 static int bam_chop_device_impl(vapor_ctx* ctx, vapor_bam* bam, int32_t n_regions, const int32_t* tid, const int64_t* start,
                                 const int64_t* end, const int64_t* flank, const int32_t* chunk_first, const uint64_t* chunks,
                                 int32_t max_keep, int32_t* kept_first, uint64_t* sq_addr, int64_t* q0, int64_t* miss,
                                 int32_t* status, vapor_bam_batch** out, uint32_t* member, int64_t* phase_set, int32_t* tagged,
-                                bool right = false)
+                                bool right = false, const HaplotagIn* hin = nullptr)
 {
     using namespace vapor_bamdev;
     using vapor_bgzf::HostSpan;
-    const bool phased = member != nullptr;
+    const bool phased = member != nullptr, haplo = hin != nullptr;
     if (!ctx || !bam || !out || n_regions < 0 || max_keep < 1 || max_keep > KEPT_CAP ||
         (n_regions && (!tid || !start || !end || !flank || !chunk_first || !kept_first || !sq_addr || !q0 || !miss || !status)) ||
-        (phased && n_regions && (!phase_set || !tagged)))
+        (phased && n_regions && (!phase_set || !tagged)) || (haplo && (!phased || right)) ||
+        (haplo && n_regions && (!hin->site_first || !hin->ps_first || hin->site_first[0] != 0 || hin->ps_first[0] != 0)))
         return fail(VAPOR_E_ARG, "vapor_bam_chop_device: bad argument");
+    if (haplo && n_regions) {
+        // (the two tables are the caller's: their offsets must ascend and their arrays be there before a region is looked at)
+        for (int32_t g = 0; g < n_regions; ++g)
+            if (hin->site_first[g + 1] < hin->site_first[g] || hin->ps_first[g + 1] < hin->ps_first[g])
+                return fail(VAPOR_E_ARG, "vapor_bam_chop_device_haplotag: site_first / ps_first do not ascend");
+        if ((hin->site_first[n_regions] && !hin->sites) || (hin->ps_first[n_regions] && !hin->ps_values))
+            return fail(VAPOR_E_ARG, "vapor_bam_chop_device_haplotag: bad argument");
+    }
     const int fd = vapor_bam_fileno(bam);
     if (fd < 0) return fail(VAPOR_E_ARG, "vapor_bam_chop_device: the file is not open");
     HIPCHK(hipSetDevice(ctx->device));
@@ -1075,6 +1093,14 @@ static int bam_chop_device_impl(vapor_ctx* ctx, vapor_bam* bam, int32_t n_region
             const int32_t c0 = chunk_first[g], c1 = chunk_first[g + 1];
             // (positions are 32-bit in a BAM file; a region that is not is the host route's to refuse)
             bool ok = c1 >= c0 && (c0 == c1 || chunks) && start[g] >= 0 && end[g] >= start[g] && end[g] < ((int64_t)1 << 31) && flank[g] >= 0 && tid[g] >= 0;
+            int why = REG_MALFORMED;
+            if (ok && haplo) {
+                // a wavefront tallies PHASE_SETS_CAP phase sets; the sites in position order, their indices inside the region's table
+                const int32_t n_ps = hin->ps_first[g + 1] - hin->ps_first[g];
+                if (n_ps > PHASE_SETS_CAP) { ok = false; why = REG_PHASE_SETS; }
+                for (int32_t i = hin->site_first[g]; ok && i < hin->site_first[g + 1]; ++i)
+                    ok = hin->sites[i].ps_idx < n_ps && hin->sites[i].pos >= 1 && (i == hin->site_first[g] || hin->sites[i - 1].pos < hin->sites[i].pos);
+            }
             for (int32_t c = c0; ok && c < c1; ++c) {
                 const uint64_t cs = chunks[2 * (size_t)c], ce = chunks[2 * (size_t)c + 1];
                 if (ce < cs || (ce >> 16) - (cs >> 16) > ((uint64_t)1 << 27)) { ok = false; break; }
@@ -1088,7 +1114,7 @@ static int bam_chop_device_impl(vapor_ctx* ctx, vapor_bam* bam, int32_t n_region
                 spans.push_back(std::move(sp));
             }
             if (!ok) {
-                status[g] = REG_MALFORMED;
+                status[g] = why;
                 while (!spans.empty() && spans.back().region == g) { stage_bytes = spans.back().stage_off; spans.pop_back(); }
             }
         }
@@ -1166,12 +1192,17 @@ static int bam_chop_device_impl(vapor_ctx* ctx, vapor_bam* bam, int32_t n_region
         Carve m;
         m.take(sizeof(BgzfBlk) * std::max<size_t>(n_blks, 1));
         const size_t o_span = m.take(sizeof(BamSpan) * std::max<size_t>(dspans.size(), 1)), o_reg = m.take(sizeof(BamRegion) * regs.size());
+        // (haplotagging: every region's range of sites and of phase-set values, the sites, the values - sent with the tables above)
+        const size_t n_sites = haplo && n_regions ? (size_t)hin->site_first[n_regions] : 0, n_psv = haplo && n_regions ? (size_t)hin->ps_first[n_regions] : 0;
+        const size_t o_srange = m.take(haplo ? sizeof(BamSiteRange) * regs.size() : 0), o_sites = m.take(haplo ? sizeof(BamSite) * std::max<size_t>(n_sites, 1) : 0);
+        const size_t o_psv = m.take(haplo ? 8 * std::max<size_t>(n_psv, 1) : 0);
         const size_t in_bytes = m.off;
         const size_t o_bst = m.take(4 * std::max<size_t>(n_blks, 1)), o_nk = m.take(4 * regs.size()), o_rst = m.take(4 * regs.size());
         // (phased: the regions' BamPhase and their unions - 3 * max_keep picks each - come back; the kept entries and their tags
         // stay on the device)
         const size_t o_phase = m.take(phased ? sizeof(BamPhase) * regs.size() : 0), o_picks = m.take(phased ? sizeof(BamPick) * 3 * (size_t)max_keep * regs.size() : 0);
         const size_t o_kept = m.take(sizeof(BamKept) * KEPT_CAP * regs.size()), o_tags = m.take(phased ? sizeof(BamTag) * KEPT_CAP * regs.size() : 0);
+        const size_t o_ops = m.take(haplo ? sizeof(BamOps) * KEPT_CAP * regs.size() : 0);
         const size_t back_end = phased ? o_kept : o_tags;            // what the host reads back ends here
         if (const int rc = stage.alloc(std::max(back_end, in_bytes), m.off)) return rc;
         HIPCHK(dmalloc(ctx, (void**)&B->d_arena, arena + 64));
@@ -1179,6 +1210,17 @@ static int bam_chop_device_impl(vapor_ctx* ctx, vapor_bam* bam, int32_t n_region
         ctx->arenas[B->d_arena] = B->arena_bytes;
         if (!dspans.empty()) memcpy(h_meta + o_span, dspans.data(), sizeof(BamSpan) * dspans.size());
         memcpy(h_meta + o_reg, regs.data(), sizeof(BamRegion) * regs.size());
+        if (haplo) {
+            BamSiteRange* sr = reinterpret_cast<BamSiteRange*>(h_meta + o_srange);
+            for (int32_t g = 0; g < n_regions; ++g) {
+                // (a region that is not sent keeps an empty range: its wavefronts end on its status)
+                const bool on = status[g] == 0;
+                sr[g] = {hin->site_first[g], on ? hin->site_first[g + 1] - hin->site_first[g] : 0, hin->ps_first[g], on ? hin->ps_first[g + 1] - hin->ps_first[g] : 0};
+            }
+            if (n_regions == 0) sr[0] = {0, 0, 0, 0};
+            if (n_sites) memcpy(h_meta + o_sites, hin->sites, sizeof(BamSite) * n_sites);
+            if (n_psv) memcpy(h_meta + o_psv, hin->ps_values, 8 * n_psv);
+        }
         {
             const char* sh = getenv("VAPOR_BAM_CU_SHARE");            // (experiments: overrides the parameter)
             const int share = ctx->user_stream ? 0 : (sh ? atoi(sh) : ctx->bam_cu_share);
@@ -1207,9 +1249,19 @@ static int bam_chop_device_impl(vapor_ctx* ctx, vapor_bam* bam, int32_t n_region
                                    reinterpret_cast<const BamSpan*>(d_meta + o_span), reinterpret_cast<const int32_t*>(d_meta + o_bst), (int)n_regions,
                                    reinterpret_cast<BamKept*>(d_meta + o_kept), reinterpret_cast<int32_t*>(d_meta + o_nk), reinterpret_cast<int32_t*>(d_meta + o_rst), tags...);
             };
-            if (phased) chop(bam_chop_tagged_kernel, reinterpret_cast<BamTag*>(d_meta + o_tags));
+            if (haplo) chop(bam_chop_ops_kernel, reinterpret_cast<BamOps*>(d_meta + o_ops));
+            else if (phased) chop(bam_chop_tagged_kernel, reinterpret_cast<BamTag*>(d_meta + o_tags));
             else chop(right ? bam_chop_right_kernel : bam_chop_kernel);
             HIPCHK(hipGetLastError());
+            if (haplo) {
+                // the tags of the kept records from the region's phased sites: a wavefront a (region, slot)
+                hipLaunchKernelGGL(bam_haplotag_kernel, dim3((unsigned)n_regions * (unsigned)(KEPT_CAP / HAPLOTAG_WAVES)), dim3(64 * HAPLOTAG_WAVES), 0, st,
+                                   B->d_arena, reinterpret_cast<const BamKept*>(d_meta + o_kept), reinterpret_cast<const BamOps*>(d_meta + o_ops),
+                                   reinterpret_cast<const int32_t*>(d_meta + o_nk), reinterpret_cast<const int32_t*>(d_meta + o_rst), (int)n_regions,
+                                   reinterpret_cast<const BamSiteRange*>(d_meta + o_srange), reinterpret_cast<const BamSite*>(d_meta + o_sites),
+                                   reinterpret_cast<const long long*>(d_meta + o_psv), reinterpret_cast<BamTag*>(d_meta + o_tags));
+                HIPCHK(hipGetLastError());
+            }
             if (phased) {
                 hipLaunchKernelGGL(bam_select_kernel, dim3((unsigned)n_regions), dim3(64), 0, st, reinterpret_cast<const BamKept*>(d_meta + o_kept),
                                    reinterpret_cast<const BamTag*>(d_meta + o_tags), reinterpret_cast<const int32_t*>(d_meta + o_nk),
@@ -1331,6 +1383,20 @@ extern "C" int vapor_bam_chop_device_tagged(vapor_ctx* ctx, vapor_bam* bam, int3
     if (!member) return fail(VAPOR_E_ARG, "vapor_bam_chop_device_tagged: bad argument");
     return bam_chop_device_impl(ctx, bam, n_regions, tid, start, end, flank, chunk_first, chunks, max_keep, kept_first, sq_addr, q0, miss,
                                 status, out, member, phase_set, tagged);
+}
+
+// vapor_bam_chop_device_tagged with the tags made on the device from phased SNVs (`--phase-vcf`): bam_chop_ops_kernel,
+// bam_haplotag_kernel, bam_select_kernel on one stream.
+extern "C" int vapor_bam_chop_device_haplotag(vapor_ctx* ctx, vapor_bam* bam, int32_t n_regions, const int32_t* tid, const int64_t* start,
+                                              const int64_t* end, const int64_t* flank, const int32_t* chunk_first, const uint64_t* chunks,
+                                              int32_t max_keep, int32_t* kept_first, uint64_t* sq_addr, int64_t* q0, int64_t* miss,
+                                              uint32_t* member, int64_t* phase_set, int32_t* tagged, int32_t* status, vapor_bam_batch** out,
+                                              const int32_t* site_first, const void* sites, const int32_t* ps_first, const int64_t* ps_values)
+{
+    if (!member) return fail(VAPOR_E_ARG, "vapor_bam_chop_device_haplotag: bad argument");
+    const HaplotagIn hin{site_first, static_cast<const vapor_bamdev::BamSite*>(sites), ps_first, ps_values};
+    return bam_chop_device_impl(ctx, bam, n_regions, tid, start, end, flank, chunk_first, chunks, max_keep, kept_first, sq_addr, q0, miss,
+                                status, out, member, phase_set, tagged, false, &hin);
 }
 
 // what the context's last vapor_bam_chop_device did: regions, blocks, compressed bytes sent, inflated bytes, the inflate kernel's

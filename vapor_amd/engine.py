@@ -397,7 +397,7 @@ class Engine:
         return SeqSet(self, seqs, upper, derived)
 
     def bam_chop_device(self, native_bam, tids, starts, ends, flanks, chunk_first, chunks, max_keep: int = 20, tagged: bool = False,
-                        right: bool = False):
+                        right: bool = False, sites=None):
         """vapor_bam_chop_device: the read selection of many regions of an open BAM file on the device.  Returns (kept_first,
         device addresses of the kept reads' packed bases, q0, miss_bp, status per region, BamBatch); the batch owns the data the
         addresses point into - close it after the sequence sets made from them.  tagged (`--phased`,
@@ -405,12 +405,18 @@ class Engine:
         follow the batch - member (uint32 per read), phase_set (int64 per region, phase.PS_NONE for none), tagged (per region);
         NotImplementedError where the library has no such entry (the CPU twin).  right (`--both-ends`,
         vapor_bam_chop_device_right): the right-anchored reads of every region - q0 is then the base a read's reverse complement
-        starts with (SeqSet.from_addresses: src_kind 2) and miss_bp counts from the window end."""
+        starts with (SeqSet.from_addresses: src_kind 2) and miss_bp counts from the window end.  sites (`--phase-vcf`, with tagged;
+        vapor_bam_chop_device_haplotag): the regions' phased sites as phase.device_site_tables makes them - the tags are then made
+        on the device from them and the records' own HP / PS fields are not read."""
         if tagged and right:
             raise ValueError("right-anchored reads are not read with tags")
+        if sites is not None and not tagged:
+            raise ValueError("sites come with tagged=True")
         chop_fn = Engine._wide_entry("vapor_bam_chop_device_right", "right-anchored device reader") if right else None
         if tagged:
             tagged_fn = Engine._wide_entry("vapor_bam_chop_device_tagged", "tagged device reader")
+            if sites is not None:
+                tagged_fn = Engine._wide_entry("vapor_bam_chop_device_haplotag", "haplotagging device reader")
         n = len(tids)
         tids = np.ascontiguousarray(tids, dtype=np.int32)
         starts = np.ascontiguousarray(starts, dtype=np.int64)
@@ -432,11 +438,23 @@ class Engine:
             member = np.zeros(cap, dtype=np.uint32)
             pset = np.zeros(max(n, 1), dtype=np.int64)
             tg = np.zeros(max(n, 1), dtype=np.int32)
+            more = ()
+            if sites is not None:
+                site_first, ent, ps_first, ps_values = sites
+                site_first = np.ascontiguousarray(site_first, dtype=np.int32)
+                ps_first = np.ascontiguousarray(ps_first, dtype=np.int32)
+                ent = np.ascontiguousarray(ent)
+                ps_values = np.ascontiguousarray(ps_values, dtype=np.int64)
+                if (len(site_first) != n + 1 or len(ps_first) != n + 1 or ent.dtype.itemsize != 8 or len(ent) != int(site_first[-1])
+                        or len(ps_values) != int(ps_first[-1])):
+                    raise ValueError("the site tables do not describe %d regions" % n)
+                more = (site_first.ctypes.data_as(vp), ent.ctypes.data_as(vp) if len(ent) else None, ps_first.ctypes.data_as(vp),
+                        ps_values.ctypes.data_as(vp) if len(ps_values) else None)
             L.check(tagged_fn(
                 self._ctx, native_bam, n, tids.ctypes.data_as(vp), starts.ctypes.data_as(vp), ends.ctypes.data_as(vp),
                 flanks.ctypes.data_as(vp), chunk_first.ctypes.data_as(vp), chunks.ctypes.data_as(vp) if len(chunks) else None,
                 int(max_keep), kept_first.ctypes.data_as(vp), addr.ctypes.data_as(vp), q0.ctypes.data_as(vp), miss.ctypes.data_as(vp),
-                member.ctypes.data_as(vp), pset.ctypes.data_as(vp), tg.ctypes.data_as(vp), status.ctypes.data_as(vp), ctypes.byref(h)))
+                member.ctypes.data_as(vp), pset.ctypes.data_as(vp), tg.ctypes.data_as(vp), status.ctypes.data_as(vp), ctypes.byref(h), *more))
             w = int(kept_first[n])
             return kept_first, addr[:w], q0[:w], miss[:w], status[:n], BamBatch(h), member[:w], pset[:n], tg[:n]
         L.check((chop_fn or L.load().vapor_bam_chop_device)(self._ctx, native_bam, n, tids.ctypes.data_as(vp), starts.ctypes.data_as(vp), ends.ctypes.data_as(vp),

@@ -4,6 +4,10 @@ A haplotagged BAM carries `HP:i:1|2` and a phase set `PS:i:n` on its alignments.
 those tags mean here - the tag rule (`tags_from_aux`, `tags_from_sam`), the groups of a locus (`select`), the phased genotype
 (`allele`, `quality`) and the nine columns (`columns`) - for the three readers (bamio's Python reader, the library's
 vapor_bam_chop_tagged, SAM text), the drivers and the writer.
+
+`--phase-vcf` makes the same (hap, ps) for a BAM that is not haplotagged, from the phased heterozygous SNVs
+of a VCF: `read_sites` and `haplotag` are the statement of that rule, for the same three readers (vapor_bam_chop_haplotag in
+the library) and for the device's bam_haplotag_kernel.
 """
 from __future__ import annotations
 
@@ -15,6 +19,8 @@ import numpy as np
 COLUMNS = ("VaPoR_PS", "VaPoR_PGT", "VaPoR_PGQ", "VaPoR_H1_QS", "VaPoR_H1_GS", "VaPoR_H1_Rec", "VaPoR_H2_QS", "VaPoR_H2_GS",
            "VaPoR_H2_Rec")
 PS_NONE = -(1 << 63)          # "no PS field" where a phase set travels as an int64 (vapor_bam_chop_tagged's meta)
+PHASE_REACH = 100000          # `--phase-vcf`: a locus's sites lie within this many bases of its region (VAPOR_PHASE_REACH in the header)
+PHASE_SETS_DEVICE = 64        # ... and a region with more distinct phase sets among them takes the host route
 
 _AUX_SIZE = {"A": 1, "c": 1, "C": 1, "s": 2, "S": 2, "i": 4, "I": 4, "f": 4}
 _AUX_INT = {"c": "<b", "C": "<B", "s": "<h", "S": "<H", "i": "<i", "I": "<I"}
@@ -124,6 +130,214 @@ def sam_fields(tags: dict) -> List[str]:
         else:
             out.append("%s:%s:%s" % (name, t[0], t[1]))
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# haplotags from a phased VCF (`--phase-vcf`): the sites, the vote of a record, its tag
+# ---------------------------------------------------------------------------------------------
+_NT16 = "=ACMGRSVTWYHKDBN"                       # BAM's 4-bit alphabet: A C G T are 1 2 4 8
+_CIGAR_OPS = "MIDNSHP=X"
+_CIGAR_TEXT = None
+
+
+class Sites:
+    """The phased heterozygous SNVs of one sample: per contig four arrays in position order - pos (int64, 1-based), a1 and a2
+    (uint8: what haplotype 1 / 2 carries, as BAM 4-bit codes), ps (int64)."""
+
+    def __init__(self, by_contig: dict):
+        self.by_contig = by_contig
+
+    def __len__(self) -> int:
+        return sum(len(v[0]) for v in self.by_contig.values())
+
+    def of(self, chrom: str, start: int, end: int):
+        """The sites of a locus whose region is [start, end]: those of its contig with start - PHASE_REACH <= pos <= end +
+        PHASE_REACH, as (pos, a1, a2, ps) arrays; None without any."""
+        v = self.by_contig.get(chrom)
+        if v is None:
+            return None
+        a = int(np.searchsorted(v[0], int(start) - PHASE_REACH, side="left"))
+        b = int(np.searchsorted(v[0], int(end) + PHASE_REACH, side="right"))
+        if b <= a:
+            return None
+        return v[0][a:b], v[1][a:b], v[2][a:b], v[3][a:b]
+
+    def rows(self, chrom: str, start: int, end: int):
+        """The same as (pos, a1 letter, a2 letter, ps) tuples - haplotag's form."""
+        v = self.of(chrom, start, end)
+        if v is None:
+            return []
+        return [(p, _NT16[x], _NT16[y], s) for p, x, y, s in zip(v[0].tolist(), v[1].tolist(), v[2].tolist(), v[3].tolist())]
+
+    @staticmethod
+    def from_rows(rows) -> "Sites":
+        """From (contig, pos, a1 letter, a2 letter, ps) rows in any order; a second row at a contig and position is dropped."""
+        by = {}
+        for c, p, x, y, s in rows:
+            by.setdefault(c, {}).setdefault(int(p), (_NT16.index(x.upper()), _NT16.index(y.upper()), int(s)))
+        out = {}
+        for c, d in by.items():
+            pos = sorted(d)
+            out[c] = (np.asarray(pos, dtype=np.int64), np.asarray([d[p][0] for p in pos], dtype=np.uint8),
+                      np.asarray([d[p][1] for p in pos], dtype=np.uint8), np.asarray([d[p][2] for p in pos], dtype=np.int64))
+        return Sites(out)
+
+
+_sites_cache: dict = {}
+
+
+def read_sites(path: str, sample: Optional[str] = None, contigs=None) -> Sites:
+    """The sites of a phased VCF (plain or gzip / bgzip compressed; read whole with the standard library, once per process, no
+    index).  The sample is the first sample column or the one named.  With alleles = [REF] + ALT.split(','), a record is a site
+    when REF is one letter, the sample's GT is `x|y` with integers x != y, and alleles[x] and alleles[y] are each one letter of
+    ACGT in either case; a1 = alleles[x] is what haplotype 1 carries, a2 = alleles[y] haplotype 2.  ps = the integer value of
+    the PS FORMAT key, 0 where it is absent or '.'.  FILTER is ignored.  Of the sites at one contig and position the first
+    stands.  contigs: the names to keep (the BAM's), None for all.  ValueError for a VCF without a sample column or without
+    the sample that was named."""
+    import gzip
+    import os
+    st = os.stat(path)
+    key = (os.path.abspath(path), sample, st.st_mtime_ns, st.st_size)
+    rows = _sites_cache.get(key)
+    if rows is None:
+        with open(path, "rb") as f:
+            raw = f.read()
+        text = (gzip.decompress(raw) if raw[:2] == b"\x1f\x8b" else raw).decode("utf-8", "replace")
+        rows = []
+        col = None
+        for ln in text.splitlines():
+            if ln.startswith("##") or not ln.strip():
+                continue
+            f = ln.split("\t")
+            if ln.startswith("#"):
+                names = f[9:]
+                if not names:
+                    raise ValueError("%s has no sample column" % path)
+                if sample is None:
+                    col = 9
+                elif sample in names:
+                    col = 9 + names.index(sample)
+                else:
+                    raise ValueError("%s has no sample %r (it has: %s)" % (path, sample, ", ".join(names)))
+                continue
+            if col is None:
+                raise ValueError("%s has no #CHROM header line" % path)
+            if len(f) <= col or len(f[3]) != 1:
+                continue
+            keys = f[8].split(":")
+            vals = f[col].split(":")
+            if "GT" not in keys or keys.index("GT") >= len(vals):
+                continue
+            gt = vals[keys.index("GT")].split("|")
+            if len(gt) != 2 or not (gt[0].isdigit() and gt[1].isdigit()) or int(gt[0]) == int(gt[1]):
+                continue
+            alleles = [f[3]] + f[4].split(",")
+            x, y = int(gt[0]), int(gt[1])
+            if x >= len(alleles) or y >= len(alleles):
+                continue
+            a1, a2 = alleles[x].upper(), alleles[y].upper()
+            if len(a1) != 1 or len(a2) != 1 or a1 not in "ACGT" or a2 not in "ACGT":
+                continue
+            ps = 0
+            if "PS" in keys and keys.index("PS") < len(vals):
+                try:
+                    ps = int(vals[keys.index("PS")])
+                except ValueError:
+                    ps = 0
+            rows.append((f[0], int(f[1]), a1, a2, ps))
+        if col is None:
+            raise ValueError("%s has no #CHROM header line" % path)
+        if len(_sites_cache) > 8:
+            _sites_cache.clear()
+        _sites_cache[key] = rows
+    return Sites.from_rows(r for r in rows if contigs is None or r[0] in contigs)
+
+
+def cigar_ops(cigar):
+    """A CIGAR as (length, operation letter) pairs: from SAM text, from BAM's packed uint32 operations, or from such pairs."""
+    global _CIGAR_TEXT
+    if isinstance(cigar, str):
+        if _CIGAR_TEXT is None:
+            import re
+            _CIGAR_TEXT = re.compile(r"(\d+)([MIDNSHP=X])")
+        return [(int(n), op) for n, op in _CIGAR_TEXT.findall(cigar)]
+    if isinstance(cigar, np.ndarray):
+        return [(c >> 4, _CIGAR_OPS[c & 15] if (c & 15) < 9 else "?") for c in cigar.tolist()]
+    return list(cigar)
+
+
+def haplotag(pos: int, cigar, seq: str, sites):
+    """(hap, ps) of an alignment record from the phased sites of its locus - (pos, a1, a2, ps) tuples in position order, no
+    position twice.  pos: the record's 1-based POS; cigar: its operations (cigar_ops' forms; the CG:B,I array where the record
+    has the long-CIGAR form); seq: its SEQ.  The walk keeps SAM's cursors (not cigar2alignstart_by_pos's): M = X advance the
+    reference and the query cursor, I S the query cursor, D N the reference cursor, H P neither.  A site at reference position
+    v inside an M, = or X operation that covers [rr, rr + n) with query cursor q reads the base SEQ[q + v - rr]: a1 is one vote
+    for haplotype 1 in the site's phase set, a2 one for haplotype 2, anything else (N, =, another letter, a site inside D / N
+    or outside the alignment) none.  Among the phase sets with a vote the one with the most votes n1 + n2 is taken, ties to the
+    numerically smallest; hap = 1 when its n1 > n2, 2 when n2 > n1; on n1 == n2 or without a vote (0, None)."""
+    sites = sites if isinstance(sites, list) else list(sites)
+    ns = len(sites)
+    if ns == 0:
+        return 0, None
+    votes = {}
+    rr, q, si = int(pos), 0, 0
+    for n, op in cigar_ops(cigar):
+        if op in "M=X":
+            while si < ns and sites[si][0] < rr:
+                si += 1
+            while si < ns and sites[si][0] < rr + n:
+                v, a1, a2, ps = sites[si]
+                qi = q + v - rr
+                b = seq[qi].upper() if qi < len(seq) else ""
+                if b == a1.upper() or b == a2.upper():
+                    t = votes.setdefault(int(ps), [0, 0])
+                    t[0 if b == a1.upper() else 1] += 1
+                si += 1
+            rr += n
+            q += n
+        elif op in "IS":
+            q += n
+        elif op in "DN":
+            rr += n
+        if si >= ns:
+            break
+    if not votes:
+        return 0, None
+    ps = min(votes, key=lambda p: (-(votes[p][0] + votes[p][1]), p))
+    n1, n2 = votes[ps]
+    return (1, ps) if n1 > n2 else (2, ps) if n2 > n1 else (0, None)
+
+
+def device_site_tables(sites: Optional[Sites], chroms, starts, ends):
+    """The sites of many regions as vapor_bam_chop_device_haplotag takes them: site_first (int32, n + 1), the regions' slices
+    as 8-byte entries (int32 pos, uint8 a1, a2, the phase set's index in the region's own table, 0), ps_first (int32, n + 1)
+    and the regions' tables of phase-set values (int64, ascending).  A region with more than PHASE_SETS_DEVICE distinct phase
+    sets gets an empty slice and a table of PHASE_SETS_DEVICE + 1 entries: the library leaves such a region to the host route."""
+    n = len(chroms)
+    site_first, ps_first = np.zeros(n + 1, dtype=np.int32), np.zeros(n + 1, dtype=np.int32)
+    ent, tabs = [], []
+    dt = np.dtype([("pos", "<i4"), ("a1", "u1"), ("a2", "u1"), ("idx", "u1"), ("pad", "u1")])
+    ns = nt = 0
+    for g in range(n):
+        v = sites.of(chroms[g], int(starts[g]), int(ends[g])) if sites is not None else None
+        if v is not None and int(v[0][-1]) >= 1 << 31:      # (a BAM position is 32-bit: no record reaches such a site)
+            v = tuple(x[v[0] < (1 << 31)] for x in v)
+            v = v if len(v[0]) else None
+        if v is not None:
+            tab, idx = np.unique(v[3], return_inverse=True)
+            if len(tab) > PHASE_SETS_DEVICE:
+                tabs.append(tab[:PHASE_SETS_DEVICE + 1])
+                nt += PHASE_SETS_DEVICE + 1
+            else:
+                e = np.zeros(len(v[0]), dtype=dt)
+                e["pos"], e["a1"], e["a2"], e["idx"] = v[0], v[1], v[2], idx
+                ent.append(e)
+                tabs.append(tab)
+                ns += len(e)
+                nt += len(tab)
+        site_first[g + 1], ps_first[g + 1] = ns, nt
+    return (site_first, np.concatenate(ent) if ent else np.zeros(0, dtype=dt), ps_first,
+            np.concatenate(tabs).astype(np.int64) if tabs else np.zeros(0, dtype=np.int64))
 
 
 # ---------------------------------------------------------------------------------------------

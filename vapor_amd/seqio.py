@@ -334,6 +334,7 @@ class InProcessBam(SamtoolsHybrid):
 
     threads_ok = True                  # pipeline.run_batch may start loci on several threads (native chop, positioned reads)
     chunk_threads_ok = True            # cli.score_jobs may score several chunks at once, a thread each
+    phase_sites = None                 # `--phase-vcf`: the phase.Sites a tagged chop of this backend makes its (hap, ps) from
 
     def __init__(self) -> None:        # noqa: D401 - does not require the samtools binary
         self.exe = None
@@ -360,38 +361,47 @@ class InProcessBam(SamtoolsHybrid):
         """(QNAME, POS, CIGAR, SEQ) per alignment overlapping chrom:start-end."""
         return [r[:4] for r in self._open(bam).fetch_records(chrom, int(start), int(end))]
 
-    def chop(self, bam: str, chrom: str, start: int, end: int, flank_length: int, tagged: bool = False, right: bool = False):
+    def chop(self, bam: str, chrom: str, start: int, end: int, flank_length: int, tagged: bool = False, right: bool = False, sites=None):
         """chop_pacbio_read_by_pos (SF:339-354) straight from the BAM file: the library's native reader
         (vapor_bam_chop), or with VAPOR_BAM_NATIVE=0 the Python statement of the same steps below.  `tagged` (`--phased`):
-        every entry is [read, miss_bp, qname, hap, ps] (vapor_bam_chop_tagged; vapor_amd.phase has the tag rule).  `right`
+        every entry is [read, miss_bp, qname, hap, ps] (vapor_bam_chop_tagged; vapor_amd.phase has the tag rule) - with sites
+        (`--phase-vcf`: a phase.Sites, the argument or this backend's phase_sites) hap and ps are phase.haplotag's from the
+        locus's phased sites (vapor_bam_chop_haplotag) and the records' tags are not read.  `right`
         (`--both-ends`): the right-anchored reads (vapor_bam_chop_right, or _chop_records over the records as text)."""
+        if tagged and sites is None:
+            sites = self.phase_sites
         if right:
             if not _env_is(b"VAPOR_BAM_NATIVE", b"0"):
                 from . import _lib
                 if hasattr(_lib.load(), "vapor_bam_chop_right"):
                     return self._open(bam).chop_native(chrom, int(start), int(end), int(flank_length), right=True)
             return _chop_records(self.records(bam, chrom, start, end), int(start), int(end), flank_length, right=True)
+        st = {"sites": sites} if tagged and sites is not None else {}
         if not _env_is(b"VAPOR_BAM_NATIVE", b"0"):
-            return self._open(bam).chop_native(chrom, int(start), int(end), int(flank_length), tagged=tagged)
-        return self.chop_python(bam, chrom, start, end, flank_length, tagged=tagged)
+            return self._open(bam).chop_native(chrom, int(start), int(end), int(flank_length), tagged=tagged, **st)
+        return self.chop_python(bam, chrom, start, end, flank_length, tagged=tagged, **st)
 
-    def chop_many(self, bam: str, chroms, starts, ends, flanks, max_keep: int = 20, groups: bool = False):
+    def chop_many(self, bam: str, chroms, starts, ends, flanks, max_keep: int = 20, groups: bool = False, sites=None):
         """MemorySamtools.chop_many's contract from a BAM file: every region through the library's native reader (vapor_bam_chop:
         threaded inflate, binary CIGAR walk, only the kept bases decoded) on a few threads, the kept reads of a region as slices
         of ONE text per region - (kept_first, addr, q0 = 0, miss, status, keepalive).  minimize_pacbio_read_list (SF:1091-1102)
         on the numbers: the first max_keep in a stable order by miss_bp.  groups (`--phased`): through vapor_bam_chop_tagged,
-        with the selection of phase.select_numbers - see MemorySamtools.chop_many."""
+        with the selection of phase.select_numbers - see MemorySamtools.chop_many; with sites (`--phase-vcf`, as in chop)
+        through vapor_bam_chop_haplotag."""
         import numpy as np
         from .engine import _ASCII_OFF
         if _env_is(b"VAPOR_BAM_NATIVE", b"0") or not (0 < _ASCII_OFF < 256):
             raise NotImplementedError("chop_many needs the native reader")
+        if groups and sites is None:
+            sites = self.phase_sites
+        st_kw = {"sites": sites} if groups and sites is not None else {}
         n = len(chroms)
         b = self._open(bam)
         st, en, fl = [int(x) for x in starts], [int(x) for x in ends], [int(x) for x in flanks]
 
         def one(g):
             try:
-                return b.chop_native_raw(chroms[g], st[g], en[g], fl[g], tagged=groups)
+                return b.chop_native_raw(chroms[g], st[g], en[g], fl[g], tagged=groups, **st_kw)
             except IndexError:
                 return IndexError                       # (a record without CIGAR: the drivers' route raises it where the reference does)
         from . import pipeline
@@ -437,7 +447,7 @@ class InProcessBam(SamtoolsHybrid):
         return kept_first, addr, np.zeros(w, dtype=np.int64), miss_a, status, keep
 
     def chop_many_device(self, engine, bam: str, chroms, starts, ends, flanks, max_keep: int = 20, groups: bool = False,
-                         right: bool = False):
+                         right: bool = False, sites=None):
         """chop_many with the work on the device (vapor_bam_chop_device: the regions' BGZF blocks go over the link compressed,
         one wavefront inflates a block, one walks a region's records): (kept_first, DEVICE addresses of the kept reads' packed
         bases, q0 = first base of each read's part, miss, status, keepalive).  A region the device leaves to the host route
@@ -445,7 +455,10 @@ class InProcessBam(SamtoolsHybrid):
         the reference's errors.  groups (`--phased`): vapor_bam_chop_device_tagged - the reads of a region are the union of its
         three group lists, selected on the device; member, phase set and tagged follow as in MemorySamtools.chop_many.  right
         (`--both-ends`): the right-anchored reads of every region (vapor_bam_chop_device_right) - q0 is then the base a read's
-        reverse complement starts with: such a read goes into a sequence set with src_kind 2."""
+        reverse complement starts with: such a read goes into a sequence set with src_kind 2.  sites (`--phase-vcf`, with
+        groups; as in chop): vapor_bam_chop_device_haplotag - the tags behind the selection are made on the device from every
+        region's phased sites (phase.device_site_tables); a region with more phase sets than a wavefront tallies comes back
+        with a status, for the host route."""
         import numpy as np
         if _env_is(b"VAPOR_BAM_NATIVE", b"0") or _env_is(b"VAPOR_BAM_DEVICE", b"0") or not hasattr(engine, "bam_chop_device"):
             raise NotImplementedError("no device reader")
@@ -459,6 +472,14 @@ class InProcessBam(SamtoolsHybrid):
             raise NotImplementedError("no right-anchored device reader")
         b = self._open(bam)
         n = len(chroms)
+        if phased and sites is None:
+            sites = self.phase_sites
+        tables = None
+        if phased and sites is not None:
+            if not hasattr(lib, "vapor_bam_chop_device_haplotag"):
+                raise NotImplementedError("no haplotagging device reader")
+            from . import phase
+            tables = phase.device_site_tables(sites, chroms, starts, ends)
         tids = np.zeros(n, dtype=np.int32)
         chunk_first = np.zeros(n + 1, dtype=np.int32)
         flat = []
@@ -496,6 +517,9 @@ class InProcessBam(SamtoolsHybrid):
             while groups:
                 a, e = groups.pop(0)
                 c0, c1 = int(chunk_first[a]), int(chunk_first[e])
+                if tables is not None:                  # (the batch's slice of the site tables, its offsets from zero)
+                    sf, ent, pf, psv = tables
+                    more["sites"] = (sf[a:e + 1] - sf[a], ent[int(sf[a]):int(sf[e])], pf[a:e + 1] - pf[a], psv[int(pf[a]):int(pf[e])])
                 try:
                     got = engine.bam_chop_device(tl["native"], tids[a:e], starts[a:e], ends[a:e], flanks[a:e], chunk_first[a:e + 1] - c0,
                                                  flat_a[c0:c1].reshape(-1), max_keep, **more)
@@ -535,9 +559,10 @@ class InProcessBam(SamtoolsHybrid):
         # the interpreter lock around one, for the loci after the first)
         return path in self._bam or os.path.isfile(path)
 
-    def chop_python(self, bam: str, chrom: str, start: int, end: int, flank_length: int, tagged: bool = False):
+    def chop_python(self, bam: str, chrom: str, start: int, end: int, flank_length: int, tagged: bool = False, sites=None):
         """The same from the records as Python parses them: the CIGAR is walked in its binary form (the library's
-        host helper) and only the reads that are kept have their bases decoded."""
+        host helper) and only the reads that are kept have their bases decoded.  sites (with tagged: a phase.Sites): the
+        tags are phase.haplotag's from the locus's sites (bamio's fetch_raw)."""
         import ctypes
         import numpy as np
         from . import _lib, bamio
@@ -545,7 +570,8 @@ class InProcessBam(SamtoolsHybrid):
         res = np.zeros(2, dtype=np.int64)
         res_p = res.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
         out = []
-        for qname, pos, cig, sq, l_seq, _flag, tags in self._open(bam).fetch_raw(chrom, int(start), int(end)):
+        rows = {"sites": sites.rows(chrom, int(start), int(end))} if tagged and sites is not None else {}
+        for qname, pos, cig, sq, l_seq, _flag, tags in self._open(bam).fetch_raw(chrom, int(start), int(end), **rows):
             if not pos < start + 1:
                 continue
             ops = np.ascontiguousarray(cig, dtype=np.uint32)
@@ -581,6 +607,7 @@ class MemorySamtools:
     # cli.score_jobs may score several chunks at once, a thread each: the native chop writes to arrays of the call's own
     # (not with VAPOR_MEMORY_CHOP=records: that path's CIGAR walk answers into one module-level array, see cli._chunk_threads_ok)
     chunk_threads_ok = True
+    phase_sites = None                 # `--phase-vcf`: the phase.Sites a tagged chop of this backend makes its (hap, ps) from
 
     """Answers faidx/view from a `SynthWorld`; file names are ignored."""
 
@@ -643,16 +670,24 @@ class MemorySamtools:
                 cache[key] = got
         return got
 
-    def chop(self, bam: str, chrom: str, start: int, end: int, flank_length, tagged: bool = False, right: bool = False):
+    def chop(self, bam: str, chrom: str, start: int, end: int, flank_length, tagged: bool = False, right: bool = False, sites=None):
         """`tagged` (`--phased`): every entry is [read, miss_bp, qname, hap, ps], the tags read from the record's SAM text
-        fields (phase.tags_from_sam).  `right` (`--both-ends`): the right-anchored reads, reverse complemented - the walk in
+        fields (phase.tags_from_sam) - or, with sites (`--phase-vcf`: a phase.Sites, the argument or this backend's
+        phase_sites), made by phase.haplotag from the locus's phased sites, the record's tags not looked at.  `right`
+        (`--both-ends`): the right-anchored reads, reverse complemented - the walk in
         the library's host helper (vapor_chop_records_right), or _chop_records itself with VAPOR_MEMORY_CHOP=records."""
         if right:
             return self._chop_right(chrom, int(start), int(end), flank_length)
         if tagged:
-            from .phase import tags_from_sam
+            from .phase import haplotag, tags_from_sam
+            if sites is None:
+                sites = self.phase_sites
+            rows = sites.rows(chrom, int(start), int(end)) if sites is not None else None
         if _memory_chop_by_records():
             recs = self.world.overlapping(chrom, int(start), int(end))
+            if tagged and sites is not None:
+                return _chop_records([(r.qname, r.pos, r.cigar, r.seq) for r in recs], start, end, flank_length,
+                                     [haplotag(r.pos, r.cigar, r.seq, rows) for r in recs])
             return _chop_records([(r.qname, r.pos, r.cigar, r.seq) for r in recs], start, end, flank_length,
                                  [tags_from_sam(r.tag_fields()) for r in recs] if tagged else None)
         recs, arrs, ptr, _keep, _n = self._arrays(chrom)
@@ -679,7 +714,7 @@ class MemorySamtools:
             r = recs[t]
             out.append([r.seq[q0:q0 + (end - start - miss)] if q0 >= 0 else r.seq[q0:][:end - start - miss], miss, r.qname])
             if tagged:
-                out[-1] += list(tags_from_sam(r.tag_fields()))
+                out[-1] += list(haplotag(r.pos, r.cigar, r.seq, rows) if sites is not None else tags_from_sam(r.tag_fields()))
         return out
 
     def _chop_right(self, chrom: str, start: int, end: int, flank_length):
@@ -704,12 +739,12 @@ class MemorySamtools:
             out.append([rc_read(r.seq[stop - (end - start - miss):stop]), miss, r.qname])
         return out
 
-    def chop_many(self, bam: str, chroms, starts, ends, flanks, max_keep: int = 20, groups: bool = False):
+    def chop_many(self, bam: str, chroms, starts, ends, flanks, max_keep: int = 20, groups: bool = False, sites=None):
         """groups (`--phased`, not in the reference): the reads of a region are the union of the lists of its three groups (A: all
         kept records, H1 / H2: those of one haplotype in the region's phase set; phase.select) in record order, at most
         3 * max_keep, and three arrays follow the keepalive - member (uint32 per read: bits 0-2 the read is in the list of A / H1 /
         H2, bits 8-15, 16-23, 24-31 its position there), phase set (int64 per region, phase.PS_NONE for none) and tagged (per
-        region: a kept record has hap != 0).  Without it:
+        region: a kept record has hap != 0); with sites (`--phase-vcf`, as in chop) hap and ps are phase.haplotag's.  Without it:
         chop_pacbio_read_by_pos (SF:339-354) + minimize_pacbio_read_list (SF:1091-1102) for many regions in ONE native call
         (vapor_chop_records_many): per region its kept reads as numbers, not as lists of strings -
         (kept_first [n + 1], addr, q0, miss, status [n], keepalive): read t of region g (kept_first[g] <= t < kept_first[g + 1])
@@ -765,6 +800,8 @@ class MemorySamtools:
         status[:n][bad] = -1
         if groups:
             from . import phase
+            if sites is None:
+                sites = self.phase_sites
             pset, tagged = np.full(n, phase.PS_NONE, dtype=np.int64), np.zeros(n, dtype=np.int32)
             kf2 = np.zeros(n + 1, dtype=np.int32)
             take, member = [], []
@@ -772,7 +809,11 @@ class MemorySamtools:
                 a, b = int(kept_first[g]), int(kept_first[g + 1])
                 if b > a and status[g] == 0:
                     recs = ent[g][6]
-                    tg = [phase.tags_from_sam(recs[t].tag_fields()) for t in rec_idx[a:b].tolist()]
+                    if sites is not None:
+                        rows = sites.rows(chroms[g], int(st[g]), int(en[g]))
+                        tg = [phase.haplotag(recs[t].pos, recs[t].cigar, recs[t].seq, rows) for t in rec_idx[a:b].tolist()]
+                    else:
+                        tg = [phase.tags_from_sam(recs[t].tag_fields()) for t in rec_idx[a:b].tolist()]
                     hap = np.asarray([h for h, _p in tg], dtype=np.int64)
                     ps = np.asarray([phase.PS_NONE if p is None else p for _h, p in tg], dtype=np.int64)
                     tagged[g], pset[g], order, words = phase.select_numbers(miss[a:b], hap, ps, keep_sel)
@@ -984,9 +1025,10 @@ def cigar2alignstart_by_pos(cigar: str, align_start: int, start: int, end: int):
     return [int(_cigar_out[0]), int(_cigar_out[1])]
 
 
-def chop_pacbio_read_by_pos(bam_in_new, chrom, start, end, flank_length, tagged=False, right=False):
+def chop_pacbio_read_by_pos(bam_in_new, chrom, start, end, flank_length, tagged=False, right=False, sites=None):
     """SF:339-354.  `tagged` (`--phased`, not in the reference): every kept record as [read, miss_bp, qname, hap, ps], its
-    haplotype and phase set read from the HP and PS fields behind SEQ (vapor_amd.phase).  `right` (`--both-ends`, not in the
+    haplotype and phase set read from the HP and PS fields behind SEQ (vapor_amd.phase) - or, with sites (`--phase-vcf`: a
+    phase.Sites, the argument or the backend's phase_sites), made from the locus's phased sites (phase.haplotag).  `right` (`--both-ends`, not in the
     reference): the right-anchored reads of the window - alignments that end at or after `end` - each as the
     reverse complement of its part that ends on the window end, miss_bp counted from there (_chop_records)."""
     out = []
@@ -1011,7 +1053,11 @@ def chop_pacbio_read_by_pos(bam_in_new, chrom, start, end, flank_length, tagged=
                 if f and f[0] != "@":
                     recs.append((f[0], f[3], f[5], f[9]))
         return _chop_records(recs, start, end, flank_length, right=True)
+    if tagged and sites is None:
+        sites = getattr(be, "phase_sites", None)
     if hasattr(be, "chop"):
+        if tagged and sites is not None:
+            return be.chop(bam_in_new, chrom, start, end, flank_length, tagged=True, sites=sites)
         return be.chop(bam_in_new, chrom, start, end, flank_length, tagged=True) if tagged else be.chop(bam_in_new, chrom, start, end, flank_length)
     tags = None
     if hasattr(be, "records") and not tagged:
@@ -1026,6 +1072,10 @@ def chop_pacbio_read_by_pos(bam_in_new, chrom, start, end, flank_length, tagged=
             recs.append((f[0], f[3], f[5], f[9]))
             if tagged:
                 tags.append(tags_from_sam(f[11:]))
+        if tagged and sites is not None:
+            from .phase import haplotag
+            rows = sites.rows(chrom, int(start), int(end))
+            tags = [haplotag(int(pos), cigar, seq, rows) for _q, pos, cigar, seq in recs]
     return _chop_records(recs, start, end, flank_length, tags)
 
 

@@ -765,6 +765,72 @@ def phase_world(world: SynthWorld, seed: int, untagged: float = 0.2, phase_set: 
     return world
 
 
+def snv_world(world: SynthWorld, seed: int, spacing: int = 40) -> dict:
+    """Plant phased heterozygous SNVs into an existing world in place (make_world's own draws are not touched; do it before a
+    backend has seen the world - the reads' SEQ strings are replaced).  From default_rng(seed), the loci in world.loci order: the
+    sites of a locus lie left of its SV start - the reads' CIGARs are relative to their own haplotype, and only there do both
+    haplotypes share the reference's coordinates - at 1-based positions that step by `spacing` with a jitter of a quarter of it
+    either way; per site a random other base as ALT and a random `1|0` or `0|1`.  Then, per read of the locus's contig and
+    per site its CIGAR covers with M, the read's base is overwritten with its haplotype's allele (a name ending in 'a' is
+    haplotype 1, any other haplotype 2) where it still equals the reference base - so the read's own substitution errors at
+    sites survive.  Returns {contig: [(pos, REF, ALT, GT), ...]} in position order (snv_vcf_text writes it)."""
+    import re
+    rng = np.random.default_rng(seed)
+    ops_re = re.compile(r"(\d+)([MIDNSHP=X])")
+    out: dict = {}
+    jit = max(spacing // 4, 1)
+    for l in world.loci:
+        ref = world.contigs[l.chrom]
+        sites = []
+        p = 1 + int(rng.integers(1, spacing + 1))
+        while p <= l.start:
+            r = ref[p - 1]
+            alt = [c for c in "ACGT" if c != r][int(rng.integers(0, 3))]
+            sites.append((p, r, alt, "1|0" if rng.random() < 0.5 else "0|1"))
+            p += spacing + int(rng.integers(-jit, jit + 1))
+        out[l.chrom] = sites
+        for rec in world.reads.get(l.chrom, ()):
+            h = 0 if rec.qname.endswith("a") else 1
+            seq = None
+            rr, q, si = rec.pos, 0, 0
+            for m in ops_re.finditer(rec.cigar):              # (lazily: the sites end left of the SV, a few operations in)
+                n, op = int(m.group(1)), m.group(2)
+                if op == "M":
+                    while si < len(sites) and sites[si][0] < rr:
+                        si += 1
+                    while si < len(sites) and sites[si][0] < rr + n:
+                        pos, r, alt, gt = sites[si]
+                        qi = q + pos - rr
+                        allele = alt if gt.split("|")[h] == "1" else r
+                        if qi < len(rec.seq) and rec.seq[qi] == r and allele != r:
+                            if seq is None:
+                                seq = bytearray(rec.seq.encode("ascii"))
+                            seq[qi] = ord(allele)
+                        si += 1
+                    rr += n
+                    q += n
+                elif op == "I":
+                    q += n
+                elif op == "D":
+                    rr += n
+                if si >= len(sites):
+                    break
+            if seq is not None:
+                rec.seq = seq.decode("ascii")
+    return out
+
+
+def snv_vcf_text(sites: dict, sample: str = "S1", phase_set: int = 1) -> str:
+    """snv_world's sites as a phased VCF of one sample: GT:PS per record, every site in phase set `phase_set`."""
+    out = ["##fileformat=VCFv4.2", "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">",
+           "##FORMAT=<ID=PS,Number=1,Type=Integer,Description=\"Phase set\">", "##source=vapor_amd.synth",
+           "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t" + sample]
+    for chrom, rows in sites.items():
+        for pos, r, alt, gt in rows:
+            out.append("\t".join([chrom, str(pos), ".", r, alt, ".", "PASS", ".", "GT:PS", "%s:%d" % (gt, phase_set)]))
+    return "\n".join(out) + "\n"
+
+
 def write_world_files(world: SynthWorld, directory: str, block_size: int = 8192, qual_seed=None,
                       bgzip_reference: bool = False) -> Tuple[str, str]:
     """FASTA + .fai and coordinate-sorted BAM + .bai of a synthetic world, written by this package alone
