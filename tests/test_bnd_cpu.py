@@ -196,9 +196,9 @@ def _run_vcf(tmp_path, name, text, bnd, monkeypatch):
     seen = {}
     orig = SF.vcf_vapor_modify
 
-    def keep_table(vcf_input, rec_new, *a):
+    def keep_table(vcf_input, rec_new, *a, **k):
         seen["table"] = open(vcf_input + ".vapor").read()
-        return orig(vcf_input, rec_new, *a)
+        return orig(vcf_input, rec_new, *a, **k)
     monkeypatch.setattr(SF, "vcf_vapor_modify", keep_table)
     args = ["vcf", "--sv-input", str(vcf), "--reference", "ref.fa", "--pacbio-input", "x.bam", "--output-path", str(d / "figs"),
             "--output-file", "unused", "--no-figures"] + (["--bnd"] if bnd else [])

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 from fake_engine import FakeEngine
-from vapor_amd import bothends, cli, drivers, finish, pipeline, seqio, synth
+from vapor_amd import bothends, cli, drivers, finish, modes, pipeline, seqio, synth
 from vapor_amd import simple_function as SF
 
 F = 500
@@ -159,13 +159,13 @@ def _score_vcf(world, text, tmp_path, name, both_ends=False):
     vcf.write_text(text)
     if both_ends:
         vl, _ = cli.vcf_list_readin(str(vcf), "ref.fa", True)
-        jobs = cli.vcf_jobs(vl, 3, "x.bam", "ref.fa", str(tmp_path) + "/", "s", both_ends=True)
-        scores = cli.score_jobs(jobs, 2048, None, both_ends=True)
+        jobs = cli.vcf_jobs(vl, 3, "x.bam", "ref.fa", str(tmp_path) + "/", "s", modes.BOTH_ENDS)
+        scores = cli.score_jobs(jobs, 2048, None, modes.BOTH_ENDS)
     else:
         vl, _ = cli.vcf_list_readin(str(vcf), "ref.fa")
         jobs = cli.vcf_jobs(vl, 3, "x.bam", "ref.fa", str(tmp_path) + "/", "s")
         scores = cli.score_jobs(jobs, 2048, None)
-    return {j.key: ([float(x) for x in s], j.views) for j, s in zip(jobs, scores)}
+    return {j.key: ([float(x) for x in s], j.extra) for j, s in zip(jobs, scores)}
 
 
 def _kept(world, svtype, info, flank=F):

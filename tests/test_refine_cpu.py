@@ -12,7 +12,7 @@ import pytest
 from conftest import ROOT, load_golden
 from fake_engine import FakeEngine
 
-from vapor_amd import cli, drivers, pipeline, refine, seqio, synth
+from vapor_amd import cli, drivers, modes, pipeline, refine, seqio, synth
 from vapor_amd import _lib as L
 
 
@@ -211,11 +211,11 @@ def test_without_the_option_the_jobs_are_todays(fake, tmp_path):
     bed.write_text(case["bed"])
     info = cli.bed_info_readin(str(bed), str(tmp_path / "figs"))
     plain = cli.bed_jobs(info, 3, "x.bam", "ref.fa", "o/", "in")
-    ref = cli.bed_jobs(info, 3, "x.bam", "ref.fa", "o/", "in", (50, 10))
+    ref = cli.bed_jobs(info, 3, "x.bam", "ref.fa", "o/", "in", modes.refine(50, 10))
     assert [j.key for j in plain] == [j.key for j in ref]
     for a, b in zip(plain, ref):
         name = a.key.split(":")[-1]
-        assert a.spec is not None and a.refine is None
+        assert a.spec is not None and a.extra is None
         if name in _SHORT_KIND:
             assert b.spec is None and b.cost > a.cost           # fastpath leaves it alone; its cost counts the candidates
         else:

@@ -4,8 +4,6 @@ from __future__ import annotations
 
 from typing import List, Optional
 
-COLUMNS = ("VaPoR_BE_N", "VaPoR_BE_QS", "VaPoR_BE_GS", "VaPoR_BE_GT", "VaPoR_BE_GQ", "VaPoR_BE_Rec", "VaPoR_BE_SQS")
-
 INFO = (
     ("VaPoR_BE_N", "Integer", "1", "Number of views of the junction that were scored, the primary one included (--both-ends)"),
     ("VaPoR_BE_QS", "Float", "1", "VaPoR_QS of the reads of all scored views (--both-ends)"),
@@ -15,6 +13,7 @@ INFO = (
     ("VaPoR_BE_Rec", "Float", ".", "Similarity scores of the reads of all scored views, in view order (--both-ends)"),
     ("VaPoR_BE_SQS", "String", ".", "VaPoR_QS of every view of the junction in table order, '.' for a view that was not scored (--both-ends)"),
 )
+COLUMNS = tuple(i[0] for i in INFO)
 
 
 def pack(views) -> List[float]:

@@ -15,6 +15,11 @@ together with --refine), --both-ends (bed, vcf: every junction branch - long DEL
 its sides, with right-anchored reads; appends the VaPoR_BE_* columns; not together with --refine or --phased),
 --phase-vcf FILE [--phase-sample NAME] (bed, vcf: --phased for a BAM that is NOT haplotagged - every read's haplotype and phase
 set come from its bases at the phased heterozygous SNVs of FILE; the HP / PS tags of the BAM are not read).
+
+--refine, --phased (with --phase-vcf) and --both-ends each append columns to every row and exclude one another: a run has one
+mode (vapor_amd.modes) or none, built once in _main and handed as one argument to bed_jobs / vcf_jobs (which
+driver a locus takes), score_jobs (the payload gathered into Job.extra), the table writer and SF.vcf_vapor_modify.  An option
+that adds columns is a module with INFO, COLUMNS, pack, unpack and columns_many, a Mode made of it, and its branch in _simple_job.
 """
 from __future__ import annotations
 
@@ -24,7 +29,7 @@ import sys
 from typing import List, Optional
 
 from . import dist as vdist
-from . import drivers, pipeline
+from . import drivers, modes, pipeline
 from . import simple_function as SF
 from .finish import result_organize_ins, row_tail
 
@@ -295,20 +300,20 @@ class _BndReader:
 # ------------------------------------------------------------------------------------------
 
 class Job:
-    """One output row: how to score it (a driver generator factory, or fixed scores) and how to
+    """One output row: how to score it (a driver call, a generator factory, or fixed scores) and how to
     write it.  `cost`: what the locus is expected to take (microseconds, `job_cost`), for the shares of the ranks."""
-    __slots__ = ("key", "make", "fixed", "row_prefix", "label", "cost", "spec", "ctx", "refine", "phase", "views", "be")
+    __slots__ = ("key", "make", "fixed", "row_prefix", "label", "cost", "spec", "ctx", "call", "extra")
 
-    def __init__(self, key, make=None, fixed=None, row_prefix=None, label=None, cost=None, spec=None, ctx=None):
-        self.key, self.make, self.fixed, self.row_prefix, self.label = key, make, fixed, row_prefix, label
+    def __init__(self, key, make=None, fixed=None, row_prefix=None, label=None, cost=None, spec=None, ctx=None, call=None):
+        # `call` = (driver, its arguments ..): `make` is that call, and a mode's chunk hook can make it again over other reads
+        if call is not None:
+            make = lambda: call[0](*call[1:])               # noqa: E731
+        self.key, self.make, self.fixed, self.row_prefix, self.label, self.call = key, make, fixed, row_prefix, label, call
         # the four simple types also say WHAT they are - (type, chrom, start, end, ins_seq) and (num_reads_cff, bam, ref) - so
         # that a chunk of them can take the array route (vapor_amd.fastpath); `make` stays the driver's own route
         self.spec, self.ctx = spec, ctx
-        self.refine = None             # after scoring under --refine: refine.Refined.info of a locus that was refined
-        self.phase = None              # after scoring under --phased: phase.Phased.phase of a locus that was phased
-        self.views = None              # after scoring under --both-ends: drivers.BothEnds.views of a locus with a junction branch
-        self.be = None                 # under --both-ends: vapor_both_ends' arguments (svtype, num_reads_cff, plt_li, bam, ref, info, figure
-                                       # name), so that a chunk can hand it the reads its windows' device extraction kept
+        self.extra = None              # after scoring under a mode (vapor_amd.modes): the locus's payload - refine.Refined.info,
+                                       # phase.Phased.phase or drivers.BothEnds.views -, None for a locus without one
         self.cost = cost if cost is not None else (COST_FIXED_US if make is None else COST_HOST_US)
 
 
@@ -359,11 +364,6 @@ def job_cost(svtype: str, span: int, extra: int = 0, candidates: int = 1, views:
     return COST_HOST_US + COST_PER_KBASE_US * bases / 1e3 + COST_PER_GCELL_US * cells / 1e9 + xmeans
 
 
-def _refine_n(refine, s, e, ci=(None, None)) -> int:
-    from . import refine as rf
-    return len(rf.candidates(refine[0], refine[1], s, e, ci[0], ci[1]))
-
-
 def _views_n(name, span) -> int:
     """The views `--both-ends` may score for a locus (job_cost): the junction branch of a long call, 1 for a short one."""
     if name == 'BND':
@@ -373,58 +373,69 @@ def _views_n(name, span) -> int:
     return 4 if name == 'INV' else 2
 
 
-def bed_jobs(bed_info, num_reads_cff, bam_in, ref, out_path, sample_name, refine=None, phased=False, both_ends=False) -> List[Job]:
-    """The loop of vapor_vali/vapor:334-367.  `refine` = (M, T) of `--refine`: DEL, INV and TANDUP loci take
-    drivers.vapor_refine (which leaves a locus it cannot refine to the type's own driver).  `phased` (`--phased`): the four
-    simple drivers run with phased=True (the array route takes the option from score_jobs)."""
+_SIMPLE = {'DEL': drivers.vapor_simple_del, 'INV': drivers.vapor_simple_inv, 'TANDUP': drivers.vapor_simple_tandup}
+
+
+def _simple_job(name, info, key, fig, row_prefix, label, plt_li, ctx, mode, with_mode=True) -> Job:
+    """The job of a DEL / INV / TANDUP record `info` = [chrom, start, end].  Plain and `--phased`: the type's own driver, with
+    its array-route description.  `--refine`: drivers.vapor_refine (which leaves a locus it cannot refine to the type's own
+    driver), within the record's CIPOS / CIEND where the mode has them.  `--both-ends`: drivers.vapor_both_ends.  `with_mode`
+    False: a record that these two drivers do not take goes the plain way."""
+    n_cff, bam_in, ref = ctx
+    span = info[2] - info[1]
+    spec = (name, info[0], info[1], info[2], None)       # (None below: the locus is not for the array route)
+    kind = mode.name if mode is not None and with_mode else None
+    if kind == 'refine':
+        from . import refine as rf
+        (m, t), ci = mode.margin_step, mode.ci_of.get(key, (None, None))
+        call = (drivers.vapor_refine, name, n_cff, plt_li, bam_in, ref, info, fig, m, t, ci[0], ci[1])
+        cost, spec = job_cost(name, span, candidates=len(rf.candidates(m, t, info[1], info[2], ci[0], ci[1]))), None
+    elif kind == 'both-ends':
+        # (a call that may reach its junction branch takes the drivers' route: the array route has no extra views; a short
+        # DEL never reaches it and stays where it was)
+        if name != 'DEL' or not span < drivers.default_max_sv_test:
+            spec = None
+        call = (drivers.vapor_both_ends, name, n_cff, plt_li, bam_in, ref, info, fig)
+        cost = job_cost(name, span, views=_views_n(name, span))
+    else:
+        call = (_SIMPLE[name], n_cff, plt_li, bam_in, ref, info, fig, mode is not None and mode.phased)
+        cost = job_cost(name, span)
+    return Job(key, None, None, row_prefix, label, cost, spec, ctx, call)
+
+
+def bed_jobs(bed_info, num_reads_cff, bam_in, ref, out_path, sample_name, mode=None) -> List[Job]:
+    """The loop of vapor_vali/vapor:334-367.  `mode` (vapor_amd.modes): the run's extra-columns option, None without one -
+    _simple_job for the DEL, INV and TANDUP loci, and under `--phased` the INS driver reads the tags as well (the array
+    route takes the option from score_jobs)."""
     jobs = []
     plt_li = 0
     ctx = (num_reads_cff, bam_in, ref)
-    ph = {'phased': True} if phased else {}
+    phased = mode is not None and mode.phased
     for x in bed_info:
         tag = x[-1]
         if tag in ['a/', '/a', '/', 'DEL']:
-            key = ':'.join([str(i) for i in x[:-3]] + ['DEL'])
-            fn, name = drivers.vapor_simple_del, 'DEL'
+            name = 'DEL'
         elif tag in ['a/a^', 'a^/a', 'a^/a^', 'INV']:
-            key = ':'.join([str(i) for i in x[:-3]] + ['INV'])
-            fn, name = drivers.vapor_simple_inv, 'INV'
+            name = 'INV'
         elif tag in ['INS']:
             key = ':'.join([str(i) for i in x[:-3] + ['INS']])
             plt_li += 1
             ins_pos = '_'.join([str(i) for i in x[:2]])
             ins_seq = ''.join(['X' for _ in range(x[4])]) if type(x[4]) == type(4) else x[4]
             fig = out_path + sample_name + '.INS.' + key.replace(':', '__') + '.png'
-            jobs.append(Job(key, (lambda p=plt_li, a=ins_pos, s=ins_seq, f=fig:
-                                  drivers.vapor_simple_ins(num_reads_cff, p, bam_in, ref, a, s, f, '+', **ph)),
+            jobs.append(Job(key, call=(drivers.vapor_simple_ins, num_reads_cff, plt_li, bam_in, ref, ins_pos, ins_seq, fig, '+', phased),
                             row_prefix=x[3], label=x, cost=job_cost('INS', len(ins_seq)),
                             spec=('INS', x[0], x[1], None, ins_seq), ctx=ctx))
             continue
         elif tag in ['a/aa', 'aa/a', 'aa/aa', 'DUP', 'TANDUP']:
-            key = ':'.join([str(i) for i in x[:-3]] + ['TANDUP'])
-            fn, name = drivers.vapor_simple_tandup, 'TANDUP'
+            name = 'TANDUP'
         else:
             print(x)
             continue
+        key = ':'.join([str(i) for i in x[:-3]] + [name])
         plt_li += 1
         fig = out_path + sample_name + '.' + name + '.' + key.replace(':', '__') + '.png'
-        if refine is not None:
-            jobs.append(Job(key, (lambda p=plt_li, n=name, info=x[:-3], g=fig:
-                                  drivers.vapor_refine(n, num_reads_cff, p, bam_in, ref, info, g, refine[0], refine[1])),
-                            row_prefix=x[3], label=x, cost=job_cost(name, x[2] - x[1], candidates=_refine_n(refine, x[1], x[2]))))
-            continue
-        if both_ends:
-            # (a call that may reach its junction branch takes the drivers' route: the array route has no extra views; a short
-            # DEL never reaches it and stays where it was)
-            long_or_falls = name != 'DEL' or not x[2] - x[1] < drivers.default_max_sv_test
-            jobs.append(Job(key, (lambda p=plt_li, n=name, info=x[:-3], g=fig:
-                                  drivers.vapor_both_ends(n, num_reads_cff, p, bam_in, ref, info, g)),
-                            row_prefix=x[3], label=x, cost=job_cost(name, x[2] - x[1], views=_views_n(name, x[2] - x[1])),
-                            **({} if long_or_falls else {'spec': (name, x[0], x[1], x[2], None), 'ctx': ctx})))
-            jobs[-1].be = (name, num_reads_cff, plt_li, bam_in, ref, x[:-3], fig)
-            continue
-        jobs.append(Job(key, (lambda p=plt_li, f=fn, info=x[:-3], g=fig: f(num_reads_cff, p, bam_in, ref, info, g, **ph)),
-                        row_prefix=x[3], label=x, cost=job_cost(name, x[2] - x[1]), spec=(name, x[0], x[1], x[2], None), ctx=ctx))
+        jobs.append(_simple_job(name, x[:-3], key, fig, x[3], x, plt_li, ctx, mode))
     return jobs
 
 
@@ -454,16 +465,14 @@ def vcf_ci_readin(file_in) -> dict:
     return out
 
 
-def vcf_jobs(vcf_list, num_reads_cff, bam_in, ref, out_path, sample_name, refine=None, ci_of=None, phased=False,
-             both_ends=False) -> List[Job]:
+def vcf_jobs(vcf_list, num_reads_cff, bam_in, ref, out_path, sample_name, mode=None) -> List[Job]:
     """The loop of vapor_vali/vapor:387-465 (TANDUP is bucketed but never scored there either), and the breakends of
-    `vapor vcf --bnd` (vcf_list_readin's last bucket: drivers.vapor_bnd).  `refine` = (M, T) of `--refine` and `ci_of`
-    (vcf_ci_readin): DEL and INV records take drivers.vapor_refine, within their CIPOS / CIEND.  `phased`: as in bed_jobs, for
-    the DEL, INV and INS records."""
+    `vapor vcf --bnd` (vcf_list_readin's last bucket: drivers.vapor_bnd).  `mode`: as in bed_jobs, for the DEL, INV and INS
+    records (`--refine` within a record's CIPOS / CIEND, the mode's `ci_of`) and, under `--both-ends`, the breakends."""
     jobs = []
     plt_li = 0
     ctx = (num_reads_cff, bam_in, ref)
-    ph = {'phased': True} if phased else {}
+    phased = mode is not None and mode.phased
     for x in list(vcf_list.keys()):
         if x not in ('DEL', 'INV', 'INS', 'DISDUP', 'DEL_INV', 'DUP_INV', 'Other', 'BND'):
             print(x)
@@ -476,67 +485,42 @@ def vcf_jobs(vcf_list, num_reads_cff, bam_in, ref, out_path, sample_name, refine
             if x == 'BND':
                 key = bnd_key(y)
                 fig = out_path + sample_name + '.BND.' + key.replace(':', '__') + '.png'
-                if both_ends:
-                    jobs.append(Job(key, (lambda p=plt_li, info=y, g=fig: drivers.vapor_both_ends('BND', num_reads_cff, p, bam_in, ref, info, g)),
+                if mode is modes.BOTH_ENDS:
+                    jobs.append(Job(key, call=(drivers.vapor_both_ends, 'BND', num_reads_cff, plt_li, bam_in, ref, y, fig),
                                     cost=job_cost('BND', 0, views=2)))
-                    jobs[-1].be = ('BND', num_reads_cff, plt_li, bam_in, ref, y, fig)
                     continue
-                jobs.append(Job(key, (lambda p=plt_li, info=y, g=fig: drivers.vapor_bnd(num_reads_cff, p, bam_in, ref, info, g)),
-                                cost=job_cost('BND', 0)))
+                jobs.append(Job(key, call=(drivers.vapor_bnd, num_reads_cff, plt_li, bam_in, ref, y, fig), cost=job_cost('BND', 0)))
             elif x in ('DEL', 'INV'):
                 if y[2] - y[1] < 50:        # both branches label the row DEL (vapor_vali/vapor:394, 407)
                     jobs.append(Job(':'.join([str(i) for i in y] + ['DEL']), fixed=[]))
                     continue
                 key = ':'.join([str(i) for i in y] + [x])
-                fn = drivers.vapor_simple_del if x == 'DEL' else drivers.vapor_simple_inv
                 fig = out_path + sample_name + '.' + x + '.' + key.replace(':', '__') + '.png'
-                if refine is not None and len(y) == 3:
-                    ci = (ci_of or {}).get(key, (None, None))
-                    jobs.append(Job(key, (lambda p=plt_li, n=x, info=y, g=fig, c=ci:
-                                          drivers.vapor_refine(n, num_reads_cff, p, bam_in, ref, info, g, refine[0], refine[1], c[0], c[1])),
-                                    cost=job_cost(x, y[2] - y[1], candidates=_refine_n(refine, y[1], y[2], ci))))
-                    continue
-                if both_ends and len(y) == 3:
-                    long_or_falls = x != 'DEL' or not y[2] - y[1] < drivers.default_max_sv_test
-                    jobs.append(Job(key, (lambda p=plt_li, n=x, info=y, g=fig: drivers.vapor_both_ends(n, num_reads_cff, p, bam_in, ref, info, g)),
-                                    cost=job_cost(x, y[2] - y[1], views=_views_n(x, y[2] - y[1])),
-                                    **({} if long_or_falls else {'spec': (x, y[0], y[1], y[2], None), 'ctx': ctx})))
-                    jobs[-1].be = (x, num_reads_cff, plt_li, bam_in, ref, y, fig)
-                    continue
-                jobs.append(Job(key, (lambda p=plt_li, f=fn, info=y, g=fig: f(num_reads_cff, p, bam_in, ref, info, g, **ph)),
-                                cost=job_cost(x, y[2] - y[1]), spec=(x, y[0], y[1], y[2], None), ctx=ctx))
+                jobs.append(_simple_job(x, y, key, fig, None, None, plt_li, ctx, mode, len(y) == 3))
             elif x == 'INS':
                 key = ':'.join([str(i) for i in y[:3] + ['INS']])
                 ins_pos = '_'.join([str(i) for i in y[:2]])
                 ins_seq = y[-1] if len(y) == 4 else ''.join(['X' for _ in range(y[2])])
                 fig = out_path + sample_name + '.INS.' + key.replace(':', '__') + '.png'
-                jobs.append(Job(key, (lambda p=plt_li, a=ins_pos, s=ins_seq, g=fig:
-                                      drivers.vapor_simple_ins(num_reads_cff, p, bam_in, ref, a, s, g, '+', **ph)),
+                jobs.append(Job(key, call=(drivers.vapor_simple_ins, num_reads_cff, plt_li, bam_in, ref, ins_pos, ins_seq, fig, '+', phased),
                                 cost=job_cost('INS', len(ins_seq)), spec=('INS', y[0], y[1], None, ins_seq), ctx=ctx))
             elif x == 'DISDUP':
                 key = ':'.join([str(i) for i in y + ['DISDUP']])
                 fig = out_path + sample_name + '.DISDUP.' + key.replace(':', '__') + '.png'
-                jobs.append(Job(key, (lambda p=plt_li, info=y, g=fig:
-                                      drivers.vapor_simple_disdup(num_reads_cff, p, bam_in, ref, info, g)),
-                                cost=_dup_cost('DISDUP', y)))
+                jobs.append(Job(key, call=(drivers.vapor_simple_disdup, num_reads_cff, plt_li, bam_in, ref, y, fig), cost=_dup_cost('DISDUP', y)))
             elif x == 'DEL_INV':
                 key = ':'.join(['_'.join([str(i) for i in j]) for j in y] + ['DEL_INV'])
                 fig = out_path + sample_name + '.DEL_INV.' + key.replace(':', '__') + '.png'
-                jobs.append(Job(key, (lambda p=plt_li, info=y, g=fig:
-                                      drivers.vapor_del_inv(num_reads_cff, p, bam_in, ref, info, g)),
+                jobs.append(Job(key, call=(drivers.vapor_del_inv, num_reads_cff, plt_li, bam_in, ref, y, fig),
                                 cost=job_cost('DEL_INV', _num(y[-1][2]) - _num(y[0][1]))))
             elif x == 'DUP_INV':
                 key = ':'.join([str(i) for i in y + ['DUP_INV']])
                 fig = out_path + sample_name + '.DUP_INV.' + key.replace(':', '__') + '.png'
-                jobs.append(Job(key, (lambda p=plt_li, info=y, g=fig:
-                                      drivers.vapor_dup_inv(num_reads_cff, p, bam_in, ref, info, g)),
-                                cost=_dup_cost('DUP_INV', y)))
+                jobs.append(Job(key, call=(drivers.vapor_dup_inv, num_reads_cff, plt_li, bam_in, ref, y, fig), cost=_dup_cost('DUP_INV', y)))
             elif x == 'Other':
                 key = ':'.join([str(i) for i in y + ['CANNOT_CLASSIFY']])
                 fig = out_path + sample_name + '.CANNOT_CLASSIFY.' + key.replace(':', '__') + '.png'
-                jobs.append(Job(key, (lambda p=plt_li, info=y, g=fig:
-                                      drivers.vapor_cannot_classify(num_reads_cff, p, bam_in, ref, info, g)),
-                                cost=_other_cost(y)))
+                jobs.append(Job(key, call=(drivers.vapor_cannot_classify, num_reads_cff, plt_li, bam_in, ref, y, fig), cost=_other_cost(y)))
     return jobs
 
 
@@ -597,9 +581,7 @@ def svelter_jobs(sv_hash, num_reads_cff, bam_in, ref, out_path, sample_name) -> 
                 fig = out_path + sample_name + key.replace(':', '__') + '.png'
                 info = [k1, k2] + k3
                 print(info)
-                jobs.append(Job(key, (lambda p=plt_li, i=info, g=fig:
-                                      drivers.vapor_cannot_classify(num_reads_cff, p, bam_in, ref, i, g)),
-                                cost=_other_cost(info)))
+                jobs.append(Job(key, call=(drivers.vapor_cannot_classify, num_reads_cff, plt_li, bam_in, ref, info, fig), cost=_other_cost(info)))
     return jobs
 
 
@@ -628,12 +610,11 @@ def output_rows(heads: list, scores_list: list) -> tuple:
     return lines, tails
 
 
-def score_jobs(jobs: List[Job], chunk: int, figure_fn=None, refine=None, phased=False, both_ends=False) -> List[object]:
+def score_jobs(jobs: List[Job], chunk: int, figure_fn=None, mode=None) -> List[object]:
     """Score every job (sharded over ranks, batched on each GPU); returns per job the list of read
-    scores, in job order, identical on every rank.  With `refine` (`--refine`) every job's `refine` attribute is set as
-    well, on every rank: refine.Refined.info of a locus that was refined, None otherwise; with `phased` (`--phased`) every
-    job's `phase` attribute likewise: phase.Phased.phase of a locus that was phased; with `both_ends` (`--both-ends`) every
-    job's `views` attribute: drivers.BothEnds.views of a locus that took its junction branch."""
+    scores, in job order, identical on every rank.  With a `mode` (vapor_amd.modes) every job's `extra` attribute is set as
+    well, on every rank: the payload of a locus that has one (refine.Refined.info of a locus that was refined, phase.Phased.phase
+    of one that was phased, drivers.BothEnds.views of one that took its junction branch), None otherwise."""
     import gc
     import time
     t0 = time.perf_counter()
@@ -645,11 +626,7 @@ def score_jobs(jobs: List[Job], chunk: int, figure_fn=None, refine=None, phased=
     gc_was = gc.get_threshold()
     gc.set_threshold(max(gc_was[0], 200000), max(gc_was[1], 50), max(gc_was[2], 1000))
     try:
-        if both_ends:
-            return _score_jobs(jobs, chunk, figure_fn, t0, both_ends=True)
-        if phased:
-            return _score_jobs(jobs, chunk, figure_fn, t0, phased=True)
-        return _score_jobs(jobs, chunk, figure_fn, t0) if refine is None else _score_jobs(jobs, chunk, figure_fn, t0, refine)
+        return _score_jobs(jobs, chunk, figure_fn, t0) if mode is None else _score_jobs(jobs, chunk, figure_fn, t0, mode)
     finally:
         gc.set_threshold(*gc_was)
 
@@ -679,28 +656,31 @@ def _both_ends_gens(jobs, rest, gens, engine):
         return gens, []
     by_bam = {}
     for k, t in enumerate(rest):
-        a = jobs[t].be
-        if a is not None and be.isfile(a[3]):
-            by_bam.setdefault(a[3], []).append(k)
+        a = jobs[t].call              # (vapor_both_ends, svtype, num_reads_cff, plt_li, bam, ref, info, figure name)
+        if a is not None and a[0] is drivers.vapor_both_ends and be.isfile(a[4]):
+            by_bam.setdefault(a[4], []).append(k)
     held = []
     gens = list(gens)
     for bam, ks in by_bam.items():
-        windows = [w for k in ks for w in drivers.both_ends_windows(jobs[rest[k]].be[0], jobs[rest[k]].be[5])]
+        windows = [w for k in ks for w in drivers.both_ends_windows(jobs[rest[k]].call[1], jobs[rest[k]].call[6])]
         try:
             pre = seqio.prefetch_views(engine, bam, windows)
         except (NotImplementedError, _lib.VaporHipError):       # (a library without the right-anchored device reader)
             continue
         held += pre.batches
         for k in ks:
-            svtype, n_cff, plt_li, _bam, ref, info, fig = jobs[rest[k]].be
-            gens[k] = drivers.vapor_both_ends(svtype, n_cff, plt_li, pre, ref, info, fig)
+            a = jobs[rest[k]].call
+            gens[k] = a[0](*a[1:4], pre, *a[5:])
     return gens, held
+
+
+modes.BOTH_ENDS.chunk_gens = _both_ends_gens          # (the only mode with a hook of its own in a chunk)
 
 
 last_timing: dict = {}          # of the most recent score_jobs: seconds scoring this rank's share, seconds in the gather
 
 
-def _score_jobs(jobs, chunk, figure_fn, t0, refine=None, phased=False, both_ends=False):
+def _score_jobs(jobs, chunk, figure_fn, t0, mode=None):
     import time
     # shares by estimated cost (greedy longest-processing-time), the same list on every rank
     costs = [float(j.cost) for j in jobs]
@@ -724,14 +704,14 @@ def _score_jobs(jobs, chunk, figure_fn, t0, refine=None, phased=False, both_ends
             for ctx, ts in by_ctx.items():
                 eng = engine or pipeline.get_engine()
                 if len(ts) >= 8 and fastpath.capable(seqio.get_backend(), ctx[1], eng):
-                    got = fastpath.run(eng, [jobs[t].spec for t in ts], ctx[1], ctx[2], ctx[0], **({"phased": True} if phased else {}))
+                    got = fastpath.run(eng, [jobs[t].spec for t in ts], ctx[1], ctx[2], ctx[0], **({"phased": True} if mode is not None and mode.phased else {}))
                     for t, r in zip(ts, got):
                         if r is not fastpath.FALLBACK:
                             done[t] = r
         rest = [t for t in todo if t not in done]
         gens, held = [jobs[t].make() for t in rest], []
-        if both_ends and figure_fn is None and rest:
-            gens, held = _both_ends_gens(jobs, rest, gens, engine or pipeline.get_engine())
+        if mode is not None and mode.chunk_gens is not None and figure_fn is None and rest:
+            gens, held = mode.chunk_gens(jobs, rest, gens, engine or pipeline.get_engine())
         try:
             res = pipeline.run_batch(gens, engine=engine, figure_fn=figure_fn) if rest else []
         finally:
@@ -792,26 +772,12 @@ def _score_jobs(jobs, chunk, figure_fn, t0, refine=None, phased=False, both_ends
             if jobs[t].make is None:
                 local[t] = jobs[t].fixed
     t1 = time.perf_counter()
-    if refine is not None:
-        # (the four extra columns travel as a second table of "scores": five floats for a refined locus, none otherwise)
-        extra = {t: (list(getattr(r, "info", None) or ()) if not isinstance(r, BaseException) and r is not None else [])
-                 for t, r in local.items()}
-        for j, info in zip(jobs, vdist.gather_results(extra, len(jobs), costs)):
-            j.refine = info if info else None
-    if phased:
-        # (the nine extra columns travel the same way: phase.pack's floats for a phased locus, none otherwise)
-        from . import phase as ph
-        extra = {t: (ph.pack(getattr(r, "phase", None)) if not isinstance(r, BaseException) and r is not None else [])
+    if mode is not None:
+        # (the extra columns travel as a second table of "scores": mode.pack's floats for a locus with a payload, none otherwise)
+        extra = {t: (mode.pack(getattr(r, mode.attr, None)) if not isinstance(r, BaseException) and r is not None else [])
                  for t, r in local.items()}
         for j, v in zip(jobs, vdist.gather_results(extra, len(jobs), costs)):
-            j.phase = ph.unpack(v)
-    if both_ends:
-        # (the views' score lists travel the same way: bothends.pack's floats for a locus with a junction branch)
-        from . import bothends as be
-        extra = {t: (be.pack(getattr(r, "views", None)) if not isinstance(r, BaseException) and r is not None else [])
-                 for t, r in local.items()}
-        for j, v in zip(jobs, vdist.gather_results(extra, len(jobs), costs)):
-            j.views = be.unpack(v)
+            j.extra = mode.unpack(v)
     allres = vdist.gather_results(local, len(jobs), costs)
     last_timing.update(score_s=t1 - t0, gather_s=time.perf_counter() - t1, loci=len(mine), cost=sum(costs[t] for t in mine))
     if os.environ.get("VAPOR_TIMING") and vdist.rank() == 0:
@@ -868,16 +834,28 @@ def main(argv: Optional[List[str]] = None) -> int:
             backend.phase_sites = None
 
 
+def _write_table(path, heads, jobs, scores, mode) -> list:
+    """A table: the header, a row per job (result_organize_ins + write_output_main of vapor_vali/vapor:356-357 in one go:
+    finish.row_tails) with the mode's columns behind it.  Returns the rows' tails (output_rows)."""
+    SF.write_output_initiate(path, mode.COLUMNS if mode is not None else ())
+    lines, tails = output_rows(heads, scores)
+    if mode is not None:
+        lines = [l + '\t' + '\t'.join(c) for l, c in zip(lines, mode.columns_many([j.extra for j in jobs]))]
+    with open(path, 'a') as fo:
+        fo.write(''.join([l + '\n' for l in lines]))
+    return tails
+
+
 def _main(argv, held) -> int:
     argv = list(sys.argv[1:] if argv is None else argv)
     if len(argv) < 1:
         from . import prep
         prep.print_read_me()
         return 0
-    mode = argv[0]
+    cmd = argv[0]
     if len(argv) == 1:
         from . import prep
-        {'bed': prep.readme_bed, 'vcf': prep.readme_vcf, 'ins': prep.readme_melt}.get(mode, prep.print_read_me)()
+        {'bed': prep.readme_bed, 'vcf': prep.readme_vcf, 'ins': prep.readme_melt}.get(cmd, prep.print_read_me)()
         return 0
     parser = build_parser()
     args = parser.parse_args(argv[1:])
@@ -885,7 +863,7 @@ def _main(argv, held) -> int:
     refine = None
     if args.refine is not None:
         from . import refine as rf
-        if mode not in ('bed', 'vcf'):
+        if cmd not in ('bed', 'vcf'):
             parser.error('--refine applies to `vapor bed` and `vapor vcf`')
         try:
             refine = rf.parse(args.refine)
@@ -896,21 +874,20 @@ def _main(argv, held) -> int:
     if args.phase_vcf is not None:
         args.phased = True               # (the groups, the scoring and the columns are --phased's: only the tags' source differs)
     if args.phased:
-        if mode not in ('bed', 'vcf'):
+        if cmd not in ('bed', 'vcf'):
             parser.error('--phased applies to `vapor bed` and `vapor vcf`')
         if refine is not None:
             parser.error('--phased and --refine cannot be combined (refinement per haplotype is not implemented)')
-        from . import phase as ph
     if args.both_ends:
-        if mode not in ('bed', 'vcf'):
+        if cmd not in ('bed', 'vcf'):
             parser.error('--both-ends applies to `vapor bed` and `vapor vcf`')
         if refine is not None:
             parser.error('--both-ends and --refine cannot be combined (refined candidates are scored from one side)')
         if args.phased:
             parser.error('--both-ends and --phased cannot be combined (right-anchored reads are not read with their tags)')
-        from . import bothends as be
     if args.phase_vcf is not None:
         # (every rank reads the VCF itself; the sites ride on the backend the reads are taken through)
+        from . import phase as ph
         try:
             sites = ph.read_sites(args.phase_vcf, args.phase_sample)
         except (OSError, ValueError) as e:
@@ -919,7 +896,13 @@ def _main(argv, held) -> int:
         backend = seqio.get_backend()
         backend.phase_sites = sites
         held.append(backend)
-    more = rf.COLUMNS if refine is not None else ph.COLUMNS if args.phased else be.COLUMNS if args.both_ends else ()
+    mode = None                          # (at most one of the three: every pair was refused above)
+    if refine is not None:
+        mode = modes.refine(*refine, ci_of=vcf_ci_readin(args.sv_input) if cmd == 'vcf' else None)
+    elif args.phased:
+        mode = modes.PHASED
+    elif args.both_ends:
+        mode = modes.BOTH_ENDS
     figure_fn = None
     if not args.no_figures:
         from . import figures
@@ -930,62 +913,33 @@ def _main(argv, held) -> int:
     SF.path_mkdir(out_path)
     sample_name = '.'.join(args.sv_input.split('/')[-1].split('.')[:-1])
     bam_in, ref = args.pacbio_input, args.reference
-    if mode == 'bed':
+    if cmd == 'bed':
         bed_info = bed_info_readin(args.sv_input, out_path)
-        opt = {'both_ends': True} if args.both_ends else {}
-        jobs = bed_jobs(bed_info, num_reads_cff, bam_in, ref, out_path, sample_name, refine, args.phased, **opt)
-        scores = score_jobs(jobs, args.chunk, figure_fn, refine, args.phased, **opt)
+        jobs = bed_jobs(bed_info, num_reads_cff, bam_in, ref, out_path, sample_name, mode)
+        scores = score_jobs(jobs, args.chunk, figure_fn, mode)
         if vdist.rank() == 0:
-            SF.write_output_initiate(args.output_file, more)
-            with open(args.output_file, 'a') as fo:
-                # (result_organize_ins + write_output_main of vapor_vali/vapor:356-357 in one go: finish.row_tails)
-                lines, tails = output_rows([j.key.split(':') + [j.row_prefix] for j in jobs], scores)
-                if refine is not None:
-                    lines = [l + '\t' + '\t'.join(rf.columns(j.refine)) for l, j in zip(lines, jobs)]
-                if args.phased:
-                    lines = [l + '\t' + '\t'.join(c) for l, c in zip(lines, ph.columns_many([j.phase for j in jobs]))]
-                if args.both_ends:
-                    lines = [l + '\t' + '\t'.join(c) for l, c in zip(lines, be.columns_many([j.views for j in jobs]))]
-                fo.write(''.join([l + '\n' for l in lines]))
-                for j, tail in zip(jobs, tails):
-                    print([j.key, tail[0], tail[1], tail[4]])
-    elif mode == 'vcf':
-        opt = {'both_ends': True} if args.both_ends else {}
-        vcf_list, rec_hash = vcf_list_readin(args.sv_input, ref if args.bnd else None, **opt)
+            tails = _write_table(args.output_file, [j.key.split(':') + [j.row_prefix] for j in jobs], jobs, scores, mode)
+            for j, tail in zip(jobs, tails):
+                print([j.key, tail[0], tail[1], tail[4]])
+    elif cmd == 'vcf':
+        vcf_list, rec_hash = vcf_list_readin(args.sv_input, ref if args.bnd else None, args.both_ends)
         rec_new = SF.vcf_rec_hash_modify(rec_hash)
-        jobs = vcf_jobs(vcf_list, num_reads_cff, bam_in, ref, out_path, sample_name, refine,
-                        vcf_ci_readin(args.sv_input) if refine is not None else None, args.phased, **opt)
-        scores = score_jobs(jobs, args.chunk, figure_fn, refine, args.phased, **opt)
+        jobs = vcf_jobs(vcf_list, num_reads_cff, bam_in, ref, out_path, sample_name, mode)
+        scores = score_jobs(jobs, args.chunk, figure_fn, mode)
         if vdist.rank() == 0:
-            SF.write_output_initiate(args.sv_input + '.vapor', more)
-            with open(args.sv_input + '.vapor', 'a') as fo:
-                lines = output_rows([[j.key] for j in jobs], scores)[0]
-                if refine is not None:
-                    lines = [l + '\t' + '\t'.join(rf.columns(j.refine)) for l, j in zip(lines, jobs)]
-                if args.phased:
-                    lines = [l + '\t' + '\t'.join(c) for l, c in zip(lines, ph.columns_many([j.phase for j in jobs]))]
-                if args.both_ends:
-                    lines = [l + '\t' + '\t'.join(c) for l, c in zip(lines, be.columns_many([j.views for j in jobs]))]
-                fo.write(''.join([l + '\n' for l in lines]))
-            if refine is not None:
-                SF.vcf_vapor_modify(args.sv_input, rec_new, refined=True)
-            elif args.phased:
-                SF.vcf_vapor_modify(args.sv_input, rec_new, phased=True)
-            elif args.both_ends:
-                SF.vcf_vapor_modify(args.sv_input, rec_new, both_ends=True)
-            else:
-                SF.vcf_vapor_modify(args.sv_input, rec_new)
-    elif mode == 'svelter':
+            _write_table(args.sv_input + '.vapor', [[j.key] for j in jobs], jobs, scores, mode)
+            SF.vcf_vapor_modify(args.sv_input, rec_new, mode=mode)
+    elif cmd == 'svelter':
         jobs = svelter_jobs(svelter_readin(args.sv_input), num_reads_cff, bam_in, ref, out_path, sample_name)
         scores = score_jobs(jobs, args.chunk, figure_fn)
         if vdist.rank() == 0:
             with open(args.output_file, 'a') as fo:      # appended, never initialised (vapor_vali/vapor:492)
                 fo.write(''.join([l + '\n' for l in output_rows([[j.key] for j in jobs], scores)[0]]))
-    elif mode == 'ins':
+    elif cmd == 'ins':
         from . import melt
         melt.run(args.sv_input, out_path, sample_name.split('.')[0], bam_in, ref, num_reads_cff, args.chunk, figure_fn)
     else:
-        raise SystemExit("vapor: unknown mode %r (bed | vcf | svelter | ins)" % mode)
+        raise SystemExit("vapor: unknown mode %r (bed | vcf | svelter | ins)" % cmd)
     vdist.finalize()
     return 0
 

@@ -1,0 +1,35 @@
+"""The run modes of `vapor bed | vcf` that append columns to every row: `--refine`, `--phased` (and `--phase-vcf`, the same mode
+with another source of tags) and `--both-ends`.  At most one holds for a run (the parser refuses every pair); None is the plain
+run.  A Mode is everything cli.py and the VCF writer need to know about one; what the option computes stays in
+its own module - refine.py, phase.py, bothends.py - which gives the mode its columns and the way they travel between ranks."""
+from __future__ import annotations
+
+from . import bothends, phase
+from . import refine as _refine
+
+
+class Mode:
+    """`name`; `COLUMNS`, the table header's names, and `INFO`, their ##INFO lines as (ID, Type, Number, Description); `keys`,
+    the INFO keys of a record in column order, and `skip_dot`, whether a key whose value is '.' is left out; `attr`, the
+    attribute of a driver's result that carries the locus's payload; `pack` / `unpack`, the payload as a list of floats for the
+    gather across ranks and back (nothing and None for a locus without one); `columns_many`, the fields of every row from the
+    payloads.  `phased`: the drivers and the array route run with phased=True.  `chunk_gens`: None, or a hook
+    (jobs, rest, gens, engine) -> (gens, held) that may replace a chunk's generators before they run (cli._both_ends_gens).
+    `--refine`'s own: `margin_step` = (M, T), and `ci_of` (cli.vcf_ci_readin: the bounds of a VCF record's candidates)."""
+    chunk_gens = None
+
+    def __init__(self, name, src, attr, keys=None, skip_dot=True, phased=False, margin_step=None, ci_of=None):
+        self.name, self.attr, self.skip_dot, self.phased = name, attr, skip_dot, phased
+        self.COLUMNS, self.INFO, self.keys = src.COLUMNS, src.INFO, keys or src.COLUMNS
+        self.pack, self.unpack, self.columns_many = src.pack, src.unpack, src.columns_many
+        self.margin_step, self.ci_of = margin_step, ci_of or {}
+
+
+def refine(margin, step, ci_of=None) -> Mode:
+    """(the record's keys keep the spelling of the reference's own VaPor_GS .. VaPor_REC, and a '.' is written)"""
+    return Mode("refine", _refine, "info", ("VaPor_RPOS", "VaPor_REND", "VaPor_QS0", "VaPor_GS0"), False, margin_step=(margin, step),
+                ci_of=ci_of)
+
+
+PHASED = Mode("phased", phase, "phase", phased=True)
+BOTH_ENDS = Mode("both-ends", bothends, "views")

@@ -16,8 +16,18 @@ from typing import List, Optional
 
 import numpy as np
 
-COLUMNS = ("VaPoR_PS", "VaPoR_PGT", "VaPoR_PGQ", "VaPoR_H1_QS", "VaPoR_H1_GS", "VaPoR_H1_Rec", "VaPoR_H2_QS", "VaPoR_H2_GS",
-           "VaPoR_H2_Rec")
+INFO = (
+    ("VaPoR_PS", "Integer", "1", "Phase set (PS tag) of the haplotagged reads the haplotype columns were taken from (--phased)"),
+    ("VaPoR_PGT", "String", "1", "Phased genotype a1|a2: whether most reads of haplotype 1 / haplotype 2 support the prediction (--phased)"),
+    ("VaPoR_PGQ", "Float", "1", "Quality of the phased genotype: the smaller log10 likelihood ratio of the two called alleles (--phased)"),
+    ("VaPoR_H1_QS", "Float", "1", "VaPoR_QS of the reads of haplotype 1 (--phased)"),
+    ("VaPoR_H1_GS", "Float", "1", "VaPoR_GS of the reads of haplotype 1 (--phased)"),
+    ("VaPoR_H1_Rec", "Float", ".", "Similarity scores of the reads of haplotype 1 (--phased)"),
+    ("VaPoR_H2_QS", "Float", "1", "VaPoR_QS of the reads of haplotype 2 (--phased)"),
+    ("VaPoR_H2_GS", "Float", "1", "VaPoR_GS of the reads of haplotype 2 (--phased)"),
+    ("VaPoR_H2_Rec", "Float", ".", "Similarity scores of the reads of haplotype 2 (--phased)"),
+)
+COLUMNS = tuple(i[0] for i in INFO)
 PS_NONE = -(1 << 63)          # "no PS field" where a phase set travels as an int64 (vapor_bam_chop_tagged's meta)
 PHASE_REACH = 100000          # `--phase-vcf`: a locus's sites lie within this many bases of its region (VAPOR_PHASE_REACH in the header)
 PHASE_SETS_DEVICE = 64        # ... and a region with more distinct phase sets among them takes the host route

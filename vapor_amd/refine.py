@@ -149,7 +149,22 @@ class Refined(list):
     info = None
 
 
-COLUMNS = ("VaPoR_RPOS", "VaPoR_REND", "VaPoR_QS0", "VaPoR_GS0")
+INFO = (
+    ("VaPoR_RPOS", "Integer", "1", "Start of the best-scoring candidate breakpoint pair (--refine)"),
+    ("VaPoR_REND", "Integer", "1", "End of the best-scoring candidate breakpoint pair (--refine)"),
+    ("VaPoR_QS0", "Float", "1", "VaPoR_QS of the called breakpoints on the widened window (--refine)"),
+    ("VaPoR_GS0", "Float", "1", "VaPoR_GS of the called breakpoints on the widened window (--refine)"),
+)
+COLUMNS = tuple(i[0] for i in INFO)
+
+
+def pack(info) -> List[float]:
+    """`info` as it travels between ranks (a second table of "scores"): its five floats, none for a locus that was not refined."""
+    return list(info or ())
+
+
+def unpack(flat):
+    return flat if flat is not None and len(flat) else None
 
 
 def columns(info) -> List[str]:
@@ -162,3 +177,7 @@ def columns(info) -> List[str]:
     if gs0 != gs0:
         return [str(int(a)), str(int(b)), "NA", "NA"]
     return [str(int(a)), str(int(b)), "0" if npos0 == 0 else str(qs0), str(gs0)]
+
+
+def columns_many(infos) -> List[List[str]]:
+    return [columns(info) for info in infos]

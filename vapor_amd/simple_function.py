@@ -223,7 +223,7 @@ def path_modify(path):
 
 
 def write_output_initiate(out_name, more_columns=()):
-    """SF:2079-2082.  `more_columns`: names appended to the header (`--refine`'s four)."""
+    """SF:2079-2082.  `more_columns`: names appended to the header (the COLUMNS of the run's mode, vapor_amd.modes)."""
     with open(out_name, 'w') as fo:
         print('\t'.join(['#CHR', 'POS', 'END', 'SVTYPE', 'SVID', 'VaPoR_QS', 'VaPoR_GS', 'VaPoR_GT', 'VaPoR_GQ',
                          'VaPoR_Rec'] + list(more_columns)), file=fo)
@@ -301,20 +301,7 @@ def vcf_rec_hash_modify(vcf_rec_hash):
     return out
 
 
-_PHASED_INFO = (
-    ('VaPoR_PS', 'Integer', 'Phase set (PS tag) of the haplotagged reads the haplotype columns were taken from (--phased)'),
-    ('VaPoR_PGT', 'String', 'Phased genotype a1|a2: whether most reads of haplotype 1 / haplotype 2 support the prediction (--phased)'),
-    ('VaPoR_PGQ', 'Float', 'Quality of the phased genotype: the smaller log10 likelihood ratio of the two called alleles (--phased)'),
-    ('VaPoR_H1_QS', 'Float', 'VaPoR_QS of the reads of haplotype 1 (--phased)'),
-    ('VaPoR_H1_GS', 'Float', 'VaPoR_GS of the reads of haplotype 1 (--phased)'),
-    ('VaPoR_H1_Rec', 'Float', 'Similarity scores of the reads of haplotype 1 (--phased)'),
-    ('VaPoR_H2_QS', 'Float', 'VaPoR_QS of the reads of haplotype 2 (--phased)'),
-    ('VaPoR_H2_GS', 'Float', 'VaPoR_GS of the reads of haplotype 2 (--phased)'),
-    ('VaPoR_H2_Rec', 'Float', 'Similarity scores of the reads of haplotype 2 (--phased)'),
-)
-
-
-def vcf_vapor_modify(vcf_input, vcf_rec_hash_new, header_offset_compat=False, refined=False, phased=False, both_ends=False):
+def vcf_vapor_modify(vcf_input, vcf_rec_hash_new, header_offset_compat=False, mode=None):
     """SF:1972-2028 (the second definition, which shadows SF:1942): rewrite <vcf>.vapor as the
     input VCF with ;VaPor_GS=..;VaPor_GT=..;VaPor_GQ=..;VaPor_REC=.. appended to INFO of every
     scored record.
@@ -324,13 +311,9 @@ def vcf_vapor_modify(vcf_input, vcf_rec_hash_new, header_offset_compat=False, re
     H header lines it annotates record r+H instead of r, or dies with KeyError.  Both agree, and
     this function matches the reference byte for byte, on header-less input.  Here record indices
     are file line numbers throughout, so headers are fine; header_offset_compat=True reproduces
-    the reference's shifted lookup.  refined (`--refine`): the rows of <vcf>.vapor carry four more fields - the refined
-    breakpoints and candidate 0's QS and GS - which follow as ;VaPor_RPOS=..;VaPor_REND=..;VaPor_QS0=..;VaPor_GS0=.. ('.' for
-    a record that was not refined), with ##INFO lines of their own.  phased (`--phased`): the rows carry nine more fields
-    (phase.COLUMNS), which follow under their column names; a key whose value is '.' is left out.  both_ends (`--both-ends`):
-    the rows carry seven more fields (bothends.COLUMNS), written the same way."""
-    if both_ends:
-        from .bothends import INFO as _BE_INFO
+    the reference's shifted lookup.  `mode` (vapor_amd.modes: `--refine`, `--phased`, `--both-ends`): the rows of <vcf>.vapor carry
+    the mode's COLUMNS as further fields, which follow in INFO under the mode's `keys` (a key whose value is '.' left out where
+    the mode says so), with the mode's ##INFO lines."""
     vapor_input = vcf_input + '.vapor'
     info = {}
     meta, header = [], []
@@ -357,12 +340,8 @@ def vcf_vapor_modify(vcf_input, vcf_rec_hash_new, header_offset_compat=False, re
                     gq = round(float(pin[4]), 2) if not pin[4] == 'NA' else pin[4]
                     info[y][7] += (';VaPor_GS=' + str(gs) + ';VaPor_GT=' + str(pin[3]) + ';VaPor_GQ=' + str(gq)
                                    + ';VaPor_REC=' + str(pin[5]))
-                    if refined:
-                        info[y][7] += ';VaPor_RPOS=%s;VaPor_REND=%s;VaPor_QS0=%s;VaPor_GS0=%s' % tuple(pin[6:10])
-                    if phased:
-                        info[y][7] += ''.join(';%s=%s' % (name[0], v) for name, v in zip(_PHASED_INFO, pin[6:15]) if v != '.')
-                    if both_ends:
-                        info[y][7] += ''.join(';%s=%s' % (name[0], v) for name, v in zip(_BE_INFO, pin[6:13]) if v != '.')
+                    if mode is not None:
+                        info[y][7] += ''.join(';%s=%s' % (k, v) for k, v in zip(mode.keys, pin[6:]) if not (mode.skip_dot and v == '.'))
                     keep.append(y)
     with open(vapor_input, 'w') as fo:
         prev = ''
@@ -374,17 +353,8 @@ def vcf_vapor_modify(vcf_input, vcf_rec_hash_new, header_offset_compat=False, re
                 print('##INFO=<ID=VaPoR_GT,Number=1,Type=String,Description="Genotype with the highest likelihood as estimated by VaPoR">', file=fo)
                 print('##INFO=<ID=VaPoR_GQ,Number=1,Type=Float,Description="Genotype quality score - likelihood of the second most likely genotype on a -log10 normalized scale"', file=fo)
                 print('##INFO=<ID=VaPoR_REC,Number=.,Type=Float,Description="Similarity scores assigned to each of the reads traversings the predicted SV">', file=fo)
-                if refined:
-                    print('##INFO=<ID=VaPoR_RPOS,Number=1,Type=Integer,Description="Start of the best-scoring candidate breakpoint pair (--refine)">', file=fo)
-                    print('##INFO=<ID=VaPoR_REND,Number=1,Type=Integer,Description="End of the best-scoring candidate breakpoint pair (--refine)">', file=fo)
-                    print('##INFO=<ID=VaPoR_QS0,Number=1,Type=Float,Description="VaPoR_QS of the called breakpoints on the widened window (--refine)">', file=fo)
-                    print('##INFO=<ID=VaPoR_GS0,Number=1,Type=Float,Description="VaPoR_GS of the called breakpoints on the widened window (--refine)">', file=fo)
-                if phased:
-                    for name, typ, text in _PHASED_INFO:
-                        print('##INFO=<ID=%s,Number=%s,Type=%s,Description="%s">' % (name, '.' if name.endswith('_Rec') else '1', typ, text), file=fo)
-                if both_ends:
-                    for name, typ, num, text in _BE_INFO:
-                        print('##INFO=<ID=%s,Number=%s,Type=%s,Description="%s">' % (name, num, typ, text), file=fo)
+                for name, typ, num, text in (mode.INFO if mode is not None else ()):
+                    print('##INFO=<ID=%s,Number=%s,Type=%s,Description="%s">' % (name, num, typ, text), file=fo)
             print(joined, file=fo)
             prev = cur
         print('\t'.join(header), file=fo)
