@@ -12,6 +12,7 @@
 #include "vapor_bgzf.h"
 #include "vapor_fasta.h"
 #include "vapor_refine.h"
+#include "vapor_planner.h"
 #include "vapor_hip.h"
 
 #include <unistd.h>
@@ -34,16 +35,6 @@
 #include <vector>
 
 using namespace vapor;
-
-// Cost of building an allele's table relative to probing one read base against it, in eighths.  Round 2 measured 0.4 per allele
-// base (a table of 20 000 positions ~10 us, a 10 000-base read ~12 us) when a task held sixteen reads; with shared joins a cfg2
-// task holds eight and the same measurement (tools/task_balance.py on a -DVAPOR_BLOCK_TIMING build: tasks with one table 71 us,
-// with two 82-85 us: a table 11 us = 1.5 reads of 7.5 us) gives 0.75: priced at 3 the tasks that straddle two windows were the
-// launch's longest by 15 %.  At 6: cfg2 join 0.0849 -> 0.0797 ms (5 .. 10 the same; profiles/r05_join_rounds.txt).
-#ifndef VAPOR_BUILD_COST_X8
-#define VAPOR_BUILD_COST_X8 6
-#endif
-
 
 static thread_local std::string g_err;
 
@@ -106,7 +97,7 @@ struct vapor_ctx {
     int64_t max_pair_cap = (int64_t)1 << 28;
     bool shared_join = true;                   // reads scored against a window and alleles derived from it: one join for all
     int remap_in_clean = 1;                    // ... and the clean workgroup of a target cuts its records out of the shared plot (0: remap_kernel)
-    int clean_order = 1;                       // 1: the clean workgroups are dealt out longest pair first (plan_clean_order); 0: in pair order
+    int clean_order = 1;                       // 1: the clean workgroups are dealt out longest pair first (clean_order); 0: in pair order
     int clean_fit = 1;                         // 1: after a blocking run the clean kernel's LDS copy is sized for the records the pairs really hold
     int stage_threads = 3;                     // host threads that copy a large upload into the pinned staging buffer (measured:
                                                // two to four are as fast as it gets, more are slower - tools/upload_sweep.py)
@@ -239,23 +230,6 @@ struct Building {
     }
 };
 
-// A derived sequence as the caller described it (destination offsets added), and the groups the plan shares joins in.
-struct HSeg { int32_t parent, off, len, dst; bool rc; };
-struct SharePiece {                // a stretch of a member that holds k-mers its parent window does not (for the largest window size)
-    int32_t slot;                  // member slot (1 ..)
-    int32_t a_from, a_to;          // symbols [a_from, a_to) of the member
-    int32_t tile_off;              // where they lie in the shared sequence
-};
-struct ShareGroup {                // a window uploaded as bytes (or its upper-cased twin) and the sequences derived from it
-    int32_t parent = -1;           // the literal sequence
-    bool upper = false;
-    int32_t identity = -1;         // user index of the sequence that IS the window (slot 0), -1: not in the set
-    int32_t t_seq = -1;            // hidden shared sequence: the window followed by the pieces
-    std::vector<int32_t> members;  // user indices of the derived sequences (slot 1 + position), at most 3
-    std::vector<SharePiece> pieces;
-};
-constexpr int SHARE_KMAX = 40;     // the largest window size (pieces carry SHARE_KMAX - 1 symbols of context)
-
 struct vapor_seqset {
     vapor_ctx* ctx = nullptr;
     int device = 0;                // kept here: the set may be destroyed after its context
@@ -274,23 +248,12 @@ struct vapor_seqset {
     std::vector<int64_t> raw_off;
 };
 
-struct Launch {
-    int bps, k, task_begin, n_tasks;
-    int exc;       // 2-bit planes: 1 = alleles with symbols outside upper-case ACGT, 2 = reads with such symbols (join_kernel<.., EXC>)
-};
-
-struct vapor_plan {
+struct vapor_plan : PlanLayout {   // the layout the planner made (vapor_planner.h) and what the device holds of it
     vapor_ctx* ctx = nullptr;
     int device = 0;                // kept here: the plan may be destroyed after its context
     vapor_seqset* set = nullptr;
     int64_t n_pairs = 0;
-    std::vector<DPair> hp;
-    std::vector<int32_t> status;
-    std::vector<DTask> tasks;
-    std::vector<int32_t> task_pairs;
-    std::vector<Launch> launches;
     std::vector<int64_t> last_stats;
-    int range_words_cap = 1;
     int hcap_want = 4096;
     bool hcap_measured = false;                // hcap_want is the largest record count a blocking run saw (else: an estimate)
     int64_t total_cap = 0;
@@ -340,13 +303,9 @@ struct vapor_plan {
     double t_finish = 0;
     // shared joins (remap_kernel): pairs n_pairs .. n_pairs + n_dpairs - 1 of hp are the (read, shared sequence) pairs the
     // join runs instead of the pairs they serve
-    int64_t n_dpairs = 0, n_served = 0;
-    std::vector<DShare> shares;
-    std::vector<DMap> maps;                    // (host only: the interval maps the tables are cut from)
-    std::vector<int32_t> tables;               // per (group, k): boundaries and op words (remap_kernel)
+    int64_t n_dpairs = 0;                      // shares.size()
     DShare* d_shares = nullptr;
-    int32_t* d_maps = nullptr;
-    std::vector<DServe> serve;                 // per pair: where its records come from when a shared join serves it
+    int32_t* d_maps = nullptr;                 // `tables`
     DServe* d_serve = nullptr;
     int32_t* d_clean_order = nullptr;          // the pairs in the order their clean workgroups are dealt out (longest first)
     // breakpoint refinement (vapor_plan_set_grid): groups of consecutive loci, each one locus's candidates (grid_pick_kernel)
@@ -519,86 +478,6 @@ extern "C" int vapor_seqset_destroy(vapor_seqset* s)
 }
 
 // Shared by the two entry points: sequence i starts at src(i).
-// The groups a plan shares joins in: every derived sequence goes to the group of the literal that gives it most of its symbols
-// (same upper-casing), a derived sequence that is that literal from end to end (an upper-cased twin) is the group's identity,
-// and the hidden sequence of a group is the window followed by the stretches of its members that hold k-mers the window does
-// not: around every junction of two segments and over every segment that is not a long enough forward or reversed slice of
-// the window itself, with SHARE_KMAX - 1 symbols of context on either side (cut for the largest window size, so that one
-// hidden sequence serves every k; the plan cuts the interval maps for its k).  Returns the hidden sequences' segment lists.
-static void build_share_groups(vapor_seqset* s, const std::vector<uint8_t>& dflags, std::vector<std::vector<HSeg>>* hidden)
-{
-    const int32_t n_lit = s->n_lit, n_der = (int32_t)s->derived.size();
-    s->group_of.assign((size_t)s->n, -1);
-    s->slot_of.assign((size_t)s->n, -1);
-    std::map<std::pair<int32_t, bool>, int32_t> gid;
-    for (int32_t d = 0; d < n_der; ++d) {
-        const auto& sg = s->derived[(size_t)d];
-        const bool up = dflags[(size_t)d] & VAPOR_SEQ_UPPER;
-        // the literal with the largest share of this sequence's symbols (forward or reversed)
-        std::map<int32_t, int64_t> share;
-        for (const HSeg& g : sg) share[g.parent] += g.len;
-        int32_t par = -1; int64_t best = 0;
-        for (auto& kv : share) if (kv.second > best) { best = kv.second; par = kv.first; }
-        if (par < 0) continue;
-        if ((s->h[(size_t)par].flags & VAPOR_SEQ_UPPER) && !up) continue;     // (the literal was upper-cased at upload: not this one's text)
-        auto it = gid.find({par, up});
-        if (it == gid.end()) {
-            it = gid.emplace(std::make_pair(par, up), (int32_t)s->groups.size()).first;
-            ShareGroup g; g.parent = par; g.upper = up;
-            if (!up) { g.identity = par; }
-            s->groups.push_back(g);
-        }
-        ShareGroup& g = s->groups[(size_t)it->second];
-        const bool whole = sg.size() == 1 && sg[0].parent == par && sg[0].off == 0 && sg[0].len == s->h[(size_t)par].len && !sg[0].rc;
-        if (whole && g.identity < 0) { g.identity = n_lit + d; continue; }
-        if (whole && g.identity >= 0) continue;                     // (another copy of the window - plain, or a second upper-cased twin: it
-                                                                    // would only take one of the group's three member slots; its pairs are joined on their own)
-        if (g.members.size() < 3) g.members.push_back(n_lit + d);
-    }
-    for (size_t q = 0; q < s->groups.size(); ++q) {
-        ShareGroup& g = s->groups[q];
-        if (g.members.empty()) continue;
-        const int32_t n_r = s->h[(size_t)g.parent].len;
-        std::vector<HSeg> t;                                         // the hidden sequence's segments
-        t.push_back(HSeg{g.parent, 0, n_r, 0, false});
-        int64_t t_len = n_r;
-        for (size_t m = 0; m < g.members.size(); ++m) {
-            const auto& sg = s->derived[(size_t)(g.members[m] - n_lit)];
-            const int32_t n_a = s->h[(size_t)g.members[m]].len;
-            // k-mer starts of the member that are k-mers of the window at the largest window size
-            std::vector<std::pair<int32_t, int32_t>> mapped;
-            for (const HSeg& x : sg)
-                if (x.parent == g.parent && x.len >= SHARE_KMAX) mapped.push_back({x.dst, x.dst + x.len - SHARE_KMAX});
-            int32_t u = 0;
-            auto add_piece = [&](int32_t from, int32_t to_start) {       // novel k-mer starts [from, to_start]
-                const int32_t a0 = from, a1 = std::min(n_a, to_start + SHARE_KMAX);
-                if (a1 <= a0) return;
-                g.pieces.push_back(SharePiece{(int32_t)m + 1, a0, a1, (int32_t)t_len});
-                // its symbols as slices of the member's own segments
-                for (const HSeg& x : sg) {
-                    const int32_t lo = std::max(a0, x.dst), hi = std::min(a1, x.dst + x.len);
-                    if (hi <= lo) continue;
-                    HSeg y;
-                    y.parent = x.parent; y.len = hi - lo; y.rc = x.rc; y.dst = (int32_t)t_len + (lo - a0);
-                    y.off = x.rc ? x.off + (x.dst + x.len - hi) : x.off + (lo - x.dst);
-                    t.push_back(y);
-                }
-                t_len += a1 - a0;
-            };
-            for (auto& r : mapped) {                                     // (segments come in order of dst)
-                if (r.first > u) add_piece(u, r.first - 1);
-                u = std::max(u, r.second + 1);
-            }
-            if (u <= n_a - 1) add_piece(u, n_a - 1);
-        }
-        if (t_len > VAPOR_MAX_SEQ_LEN || t_len > (int64_t)2 * n_r + 4096) { g.members.clear(); g.pieces.clear(); continue; }   // not worth sharing
-        g.t_seq = s->n + (int32_t)hidden->size();
-        hidden->push_back(std::move(t));
-        if (g.identity >= 0) { s->group_of[(size_t)g.identity] = (int32_t)q; s->slot_of[(size_t)g.identity] = 0; }
-        for (size_t m = 0; m < g.members.size(); ++m) { s->group_of[(size_t)g.members[m]] = (int32_t)q; s->slot_of[(size_t)g.members[m]] = (int32_t)m + 1; }
-    }
-}
-
 template <typename SRC>
 static int seqset_create_impl(vapor_ctx* ctx, int32_t n_seqs, SRC src, const int32_t* len, const uint8_t* flags,
                               int32_t* seq_info, vapor_seqset** out, int32_t n_derived = 0, const int32_t* seg_first = nullptr,
@@ -660,7 +539,7 @@ static int seqset_create_impl(vapor_ctx* ctx, int32_t n_seqs, SRC src, const int
             dd.len = (int32_t)tot;
             dd.flags = dfl[(size_t)d];
         }
-        if (ctx->shared_join) build_share_groups(s.get(), dfl, &hidden);
+        if (ctx->shared_join) hidden = share_layout(s->h, s->n, n_seqs, s->derived, dfl, &s->groups, &s->group_of, &s->slot_of);
         s->h.resize((size_t)(n_seqs + n_derived) + hidden.size());
         for (size_t t = 0; t < hidden.size(); ++t) {
             SeqDesc& dd = s->h[(size_t)(n_seqs + n_derived) + t];
@@ -1688,8 +1567,6 @@ extern "C" int vapor_plan_destroy(vapor_plan* p)
 
 static_assert((2 * VAPOR_MAX_SEQ_LEN + 2 + 31) / 32 <= CLEAN_RANGE_WORDS_MAX, "cluster_axis sizes its per-thread word list for this");
 
-static bool k_supported(int k) { return k == 10 || k == 20 || k == 30 || k == 40; }
-
 // lays out the hit workspace from hp[].cap and (re)allocates it
 static int plan_alloc_hits(vapor_plan* p)
 {
@@ -1714,34 +1591,6 @@ static int plan_alloc_hits(vapor_plan* p)
     return VAPOR_OK;
 }
 
-// The clean kernel is one workgroup per pair, dealt out in grid order, a few per CU at a time: a plan of a couple of rounds of
-// them (4 000 pairs at seven or eight per CU: two rounds and a bit) ends when the LAST round's slowest workgroup does, so the
-// pairs that take longest go first and the tail is made of the shortest (longest-processing-time order; measured on cfg2: clean
-// 0.091 -> 0.079 ms, profiles/r05_clean_order.txt).  What a pair takes: its records - about the shorter sequence's length -
-// times the passes its flags ask for: C1 two clusterings, C2 one or two more, the directed statistics five passes over the kept
-// records, plus the cutting of a served pair.  Pairs of equal cost keep their order (a read's two pairs lie side by side and
-// read the same shared plot); sorting by the record counts a blocking run measured instead (`records`) was tried and is no
-// better - it scatters those neighbours (0.0738 -> 0.0749 ms) - so the library does not use it.
-static int plan_clean_order(vapor_plan* p, const unsigned long long* records)
-{
-    const int64_t n_pairs = p->n_pairs;
-    std::vector<std::pair<int64_t, int32_t>> cost((size_t)n_pairs);
-    for (int64_t i = 0; i < n_pairs; ++i) {
-        const DPair& d = p->hp[(size_t)i];
-        const bool c1 = d.flags & VAPOR_PF_C1, c2 = d.flags & VAPOR_PF_C2, dir = (d.flags & VAPOR_PF_DIR) && c1;
-        int64_t w = 4 + (c1 ? 8 : 0) + (c2 ? (c1 ? 5 : 8) : 0) + (dir ? 7 : 0);
-        if (!p->serve.empty() && p->serve[(size_t)i].dpair >= 0) w += p->serve[(size_t)i].slot == 0 ? 2 : 4;
-        const int64_t size = records ? (int64_t)(uint32_t)records[(size_t)i] * 4 + 256
-                                     : std::min<int64_t>(d.len1, std::max(0, d.len2 - d.off2));
-        cost[(size_t)i] = {-(p->status[(size_t)i] == 0 ? w * size : 0), (int32_t)i};
-    }
-    std::stable_sort(cost.begin(), cost.end());
-    std::vector<int32_t> ord((size_t)n_pairs);
-    for (int64_t i = 0; i < n_pairs; ++i) ord[(size_t)i] = cost[(size_t)i].second;
-    HIPCHK(hipMemcpy(p->d_clean_order, ord.data(), sizeof(int32_t) * (size_t)n_pairs, hipMemcpyHostToDevice));
-    return VAPOR_OK;
-}
-
 extern "C" int vapor_plan_create(vapor_ctx* ctx, vapor_seqset* set, int64_t n_pairs, const vapor_pair* pairs,
                                  vapor_plan** out)
 {
@@ -1756,276 +1605,15 @@ extern "C" int vapor_plan_create(vapor_ctx* ctx, vapor_seqset* set, int64_t n_pa
     p->device = ctx->device;
     p->set = set;
     p->n_pairs = n_pairs;
-    p->hp.resize((size_t)std::max<int64_t>(n_pairs, 1));
-    memset(p->hp.data(), 0, sizeof(DPair) * p->hp.size());
-    p->status.assign((size_t)n_pairs, 0);
-    std::vector<int32_t> order;
-    order.reserve((size_t)n_pairs);
-    std::vector<uint8_t> mode((size_t)n_pairs, 2);
-    int rw = 1;
-    int64_t hwant = 1024;
-    for (int64_t i = 0; i < n_pairs; ++i) {
-        const vapor_pair& a = pairs[i];
-        DPair& d = p->hp[i];
-        d.seq1 = a.seq1; d.seq2 = a.seq2; d.off2 = a.off2; d.k = a.k; d.flags = a.flags; d.cap = 0;
-        if (a.seq1 < 0 || a.seq1 >= set->n || a.seq2 < 0 || a.seq2 >= set->n || a.off2 < 0 || !k_supported(a.k)) {
-            p->status[i] = VAPOR_E_ARG;
-            d.seq1 = d.seq2 = 0;
-            continue;
-        }
-        const SeqDesc& s1 = set->h[a.seq1];
-        const SeqDesc& s2 = set->h[a.seq2];
-        d.len1 = s1.len; d.len2 = s2.len;
-        if (s1.len > VAPOR_MAX_SEQ_LEN || s2.len > VAPOR_MAX_SEQ_LEN) { p->status[i] = VAPOR_E_ARG; continue; }
-        if (s1.len - a.k + 1 > 0 && s1.n_invalid > 0) { p->status[i] = VAPOR_E_KEYERROR; continue; }
-        int64_t n1 = s1.len, n2 = std::max(0, s2.len - a.off2);
-        int64_t cap = std::min(n1, n2) + ((n1 * n2) >> 17) + 1024;
-        d.cap = (uint32_t)std::min<int64_t>(cap, ctx->max_pair_cap);
-        // 2: 2-bit planes; 3: 2-bit planes, the allele has symbols outside upper-case ACGT (a launch of its own: the table
-        // leaves their k-mers out and runs end before them); 5: 2-bit planes, the read has such symbols (a launch of its own:
-        // their positions are masked out of the lookup, runs end before them); 4: both sides have them - the 4-bit planes
-        mode[i] = (s1.n_exc > 0 && s2.n_exc > 0) ? 4 : (s2.n_exc > 0 ? 3 : (s1.n_exc > 0 ? 5 : 2));
-        rw = std::max(rw, (s1.len + s2.len + 2 + 31) / 32);
-        // records expected: the shared diagonal in runs of a few dots plus the chance dots
-        hwant = std::max<int64_t>(hwant, std::min(n1, n2) / 10 + ((n1 * n2) >> 19) + 192);
-        if (s1.len - a.k + 1 > 0 && s2.len - a.k + 1 > 0) order.push_back((int32_t)i);
-    }
-    p->range_words_cap = rw;
-    p->hcap_want = (int)std::min<int64_t>(hwant, CLEAN_HCAP_MAX);
-    // Shared joins: a read that is scored against a window AND against alleles derived from it (the usual case: the
-    // reference's dotdata(read, ref) and dotdata(read, alt), SF:185-186) is joined once against the group's hidden sequence -
-    // the window followed by the alleles' own stretches - and remap_kernel cuts that dot plot into the targets'.
-    if (ctx->shared_join && !set->groups.empty() && n_pairs > 0) {
-        struct Cand { int32_t seq1, group, k, slot, pair; };
-        std::vector<Cand> cand;
-        for (int32_t x : order) {
-            const DPair& d = p->hp[(size_t)x];
-            const int32_t g = set->group_of[(size_t)d.seq2];
-            if (g >= 0 && set->groups[(size_t)g].t_seq >= 0) cand.push_back(Cand{d.seq1, g, d.k, set->slot_of[(size_t)d.seq2], x});
-        }
-        std::sort(cand.begin(), cand.end(), [](const Cand& a, const Cand& b) {
-            if (a.seq1 != b.seq1) return a.seq1 < b.seq1;
-            if (a.group != b.group) return a.group < b.group;
-            if (a.k != b.k) return a.k < b.k;
-            if (a.slot != b.slot) return a.slot < b.slot;
-            return a.pair < b.pair;
-        });
-        std::map<std::pair<int32_t, int32_t>, std::pair<int32_t, int32_t>> maps_of;      // (group, k) -> (first map, maps); n < 0: cannot
-        auto build_maps = [&](int32_t gi, int k) -> std::pair<int32_t, int32_t> {
-            auto it = maps_of.find({gi, k});
-            if (it != maps_of.end()) return it->second;
-            const ShareGroup& g = set->groups[(size_t)gi];
-            const int32_t first = (int32_t)p->maps.size();
-            const int32_t n_r = set->h[(size_t)g.parent].len;
-            bool ok = true;
-            if (n_r >= k) p->maps.push_back(DMap{0, n_r - k, 0, 0, 0});
-            for (size_t m = 0; m < g.members.size() && ok; ++m) {
-                const auto& sg = set->derived[(size_t)(g.members[m] - set->n_lit)];
-                const int32_t n_a = set->h[(size_t)g.members[m]].len;
-                int32_t u = 0;                                   // next k-mer start of the member not yet accounted for
-                auto novel = [&](int32_t from, int32_t to) {     // k-mer starts [from, to] lie in one of the member's own stretches
-                    for (const SharePiece& pc : g.pieces)
-                        if (pc.slot == (int32_t)m + 1 && pc.a_from <= from && to + k <= pc.a_to) {
-                            p->maps.push_back(DMap{pc.tile_off + (from - pc.a_from), pc.tile_off + (to - pc.a_from), from, 0, (uint16_t)(m + 1)});
-                            return;
-                        }
-                    ok = false;
-                };
-                for (const HSeg& x : sg) {
-                    if (x.parent != g.parent || x.len < k) continue;
-                    if (x.dst > u) novel(u, x.dst - 1);
-                    if (!ok) break;
-                    p->maps.push_back(DMap{x.off, x.off + x.len - k, x.rc ? x.dst + x.len - k : x.dst, (uint16_t)(x.rc ? 1 : 0), (uint16_t)(m + 1)});
-                    u = x.dst + x.len - k + 1;
-                }
-                if (ok && u <= n_a - k) novel(u, n_a - k);
-            }
-            std::pair<int32_t, int32_t> res{-1, -1};
-            if (ok && (int32_t)p->maps.size() > first) {
-                // the maps cut at each other's ends: boundaries over the k-mer starts of the shared sequence and, per elementary
-                // interval, the op words of the maps that cover it (remap_kernel)
-                std::vector<int32_t> bd{0};
-                for (size_t m = (size_t)first; m < p->maps.size(); ++m) { bd.push_back(p->maps[m].lo); bd.push_back(p->maps[m].hi + 1); }
-                std::sort(bd.begin(), bd.end());
-                bd.erase(std::unique(bd.begin(), bd.end()), bd.end());
-                const int n_iv = (int)bd.size() - 1;
-                if (n_iv >= 1 && n_iv <= REMAP_MAX_IV) {
-                    std::vector<int32_t> ops((size_t)n_iv * REMAP_OPS, 0);
-                    for (int t = 0; t < n_iv && ok; ++t)
-                        for (size_t m = (size_t)first; m < p->maps.size(); ++m) {
-                            const DMap& mp = p->maps[m];
-                            if (!(mp.lo <= bd[(size_t)t] && bd[(size_t)t + 1] - 1 <= mp.hi)) continue;
-                            const int32_t delta = mp.flip ? mp.base + mp.lo : mp.base - mp.lo;
-                            int32_t* o = &ops[(size_t)t * REMAP_OPS + (size_t)mp.slot * 2];
-                            const int c = (o[0] & 1) ? 1 : 0;
-                            if (c == 1 && (o[1] & 1)) { ok = false; break; }            // a third copy of one stretch in one allele
-                            o[c] = (int32_t)(((uint32_t)delta << 2) | (mp.flip ? 2u : 0u) | 1u);
-                        }
-                    if (ok) {
-                        res = {(int32_t)p->tables.size(), n_iv};
-                        p->tables.insert(p->tables.end(), bd.begin(), bd.end());
-                        p->tables.insert(p->tables.end(), ops.begin(), ops.end());
-                    }
-                }
-            }
-            p->maps.resize((size_t)first);
-            maps_of[{gi, k}] = res;
-            return res;
-        };
-        auto tiles = [&](int32_t len_a, int k, int m) {
-            const int ta = m != 4 ? tile_pos<JoinCfg, 2>() : tile_pos<JoinCfg, 4>();
-            return std::max(1, (len_a - k + 1 + ta - 1) / ta);
-        };
-        std::vector<uint8_t> served((size_t)n_pairs, 0);
-        { DServe none; memset(&none, 0, sizeof(none)); none.dpair = -1; p->serve.assign((size_t)n_pairs, none); }
-        for (size_t a = 0; a < cand.size();) {
-            size_t b = a;
-            while (b < cand.size() && cand[b].seq1 == cand[a].seq1 && cand[b].group == cand[a].group && cand[b].k == cand[a].k) ++b;
-            int32_t tgt[4] = {-1, -1, -1, -1};
-            int n_t = 0;
-            for (size_t c = a; c < b; ++c)
-                if (cand[c].slot >= 0 && cand[c].slot < 4 && tgt[cand[c].slot] < 0) { tgt[cand[c].slot] = cand[c].pair; ++n_t; }
-            const Cand c0 = cand[a];
-            a = b;
-            if (n_t < 2) continue;
-            const ShareGroup& g = set->groups[(size_t)c0.group];
-            const SeqDesc& s1 = set->h[(size_t)c0.seq1];
-            const SeqDesc& st = set->h[(size_t)g.t_seq];
-            if (st.len - c0.k + 1 <= 0) continue;
-            const int md = (s1.n_exc > 0 && st.n_exc > 0) ? 4 : (st.n_exc > 0 ? 3 : (s1.n_exc > 0 ? 5 : 2));
-            int sep = 0;
-            for (int t = 0; t < 4; ++t)
-                if (tgt[t] >= 0) sep += tiles(p->hp[(size_t)tgt[t]].len2, c0.k, mode[(size_t)tgt[t]]);
-            if (tiles(st.len, c0.k, md) >= sep) continue;           // (a shared sequence of more tiles than its targets together: no gain)
-            const auto mp = build_maps(c0.group, c0.k);
-            if (mp.second <= 0) continue;
-            DPair d;
-            memset(&d, 0, sizeof d);
-            d.seq1 = c0.seq1; d.seq2 = g.t_seq; d.off2 = 0; d.k = c0.k; d.flags = 0;
-            d.len1 = s1.len; d.len2 = st.len;
-            const int64_t n1 = s1.len, n2 = st.len;
-            d.cap = (uint32_t)std::min<int64_t>(std::min(n1, n2) + ((n1 * n2) >> 17) + 1024, ctx->max_pair_cap);
-            DShare sh;
-            memset(&sh, 0, sizeof sh);
-            sh.dpair = (int32_t)p->hp.size();
-            sh.iv_first = mp.first; sh.n_iv = mp.second;
-            bool counted = false;
-            for (int t = 0; t < 4; ++t) {
-                sh.target[t] = tgt[t];
-                if (tgt[t] >= 0) {
-                    served[(size_t)tgt[t]] = 1; ++p->n_served;
-                    DServe& sv = p->serve[(size_t)tgt[t]];
-                    sv.dpair = sh.dpair; sv.iv_first = sh.iv_first; sv.n_iv = sh.n_iv; sv.slot = t;      // (slot and cap of the join: below)
-                    sv.pad = counted ? 0 : 1;          // (the target whose clean workgroup counts an overflow of the SHARED plot: once per plot)
-                    counted = true;
-                }
-            }
-            p->hp.push_back(d);
-            mode.push_back((uint8_t)md);
-            p->shares.push_back(sh);
-        }
-        p->n_dpairs = (int64_t)p->shares.size();
-        if (p->n_dpairs) {
-            std::vector<int32_t> kept;
-            kept.reserve(order.size());
-            for (int32_t x : order) if (!served[(size_t)x]) kept.push_back(x);
-            for (int64_t t = 0; t < p->n_dpairs; ++t) kept.push_back((int32_t)(n_pairs + t));
-            order.swap(kept);
-        }
-    }
-    // Sort by (mode, k, allele): one launch per (mode, k); inside a launch the sorted pair list is
-    // cut into contiguous, cost-balanced ranges (tasks).  A workgroup rebuilds its allele hash table
-    // only where the allele changes inside its range.
-    // (the three fields packed into one word per pair, the index behind it: the comparisons touch nothing else)
-    {
-        std::vector<std::pair<uint64_t, int32_t>> keyed(order.size());
-        for (size_t t = 0; t < order.size(); ++t) {
-            const int32_t x = order[t];
-            keyed[t] = {((uint64_t)mode[(size_t)x] << 48) | ((uint64_t)(uint32_t)p->hp[(size_t)x].k << 32) | (uint32_t)p->hp[(size_t)x].seq2, x};
-        }
-        std::sort(keyed.begin(), keyed.end());
-        for (size_t t = 0; t < order.size(); ++t) order[t] = keyed[t].second;
-    }
-    p->task_pairs = order;
-    auto tiles_of = [&](int32_t seq2, int k, int m) {
-        const int ta = m != 4 ? tile_pos<JoinCfg, 2>() : tile_pos<JoinCfg, 4>();
-        return std::max(1, (set->h[seq2].len - k + 1 + ta - 1) / ta);
-    };
-    for (size_t q = 0; q < order.size();) {
-        size_t e = q;
-        const int m = mode[order[q]], k = p->hp[order[q]].k;
-        while (e < order.size() && mode[order[e]] == m && p->hp[order[e]].k == k) ++e;
-        // Cost of a range of consecutive pairs = its probe passes + one table build for its first allele + one for
-        // every further allele it reaches into.  The ranges are the contiguous partition into at most `want`
-        // pieces whose most expensive piece is cheapest (binary search on that bound, greedy packing under it).
-        const size_t n = e - q;
-        std::vector<int64_t> probe(n), build(n);
-        int64_t total = 0, biggest = 0;
-        for (size_t t = q; t < e; ++t) {
-            const DPair& d = p->hp[order[t]];
-            probe[t - q] = (int64_t)set->h[d.seq1].len * tiles_of(d.seq2, k, m) + 256;
-            build[t - q] = (VAPOR_BUILD_COST_X8 * (int64_t)set->h[d.seq2].len) / 8;
-            total += probe[t - q] + build[t - q];
-            biggest = std::max(biggest, probe[t - q] + build[t - q]);
-        }
-        // `join_tasks` ranges (one per CU) - or, when the limit of reads per task asks for more than that, WHOLE ROUNDS of them: a
-        // launch of 625 tasks on 256 CUs takes three rounds' time for 2.44 rounds' work (BASELINE configs[2]: 40 000 reads in
-        // tasks of at most 64), 768 equal tasks take three rounds of 52 reads each - join 2.42 -> 2.10 ms with one plan in flight
-        // (profiles/r05_join_rounds.txt; with two plans in flight the other plan's clean kernel filled that tail already)
-        int64_t want = std::max<int64_t>(1, std::min<int64_t>((int64_t)n, ctx->join_tasks));
-        {
-            const int64_t need = ((int64_t)n + ctx->reads_per_task - 1) / ctx->reads_per_task;
-            if (need > want) want = std::min<int64_t>((int64_t)n, (need + want - 1) / want * want);
-        }
-        // (what a pair adds to a range it does not start: its probe, and a table build when it brings a new allele)
-        std::vector<int64_t> inside(n);
-        for (size_t t = 0; t < n; ++t)
-            inside[t] = probe[t] + ((t > 0 && p->hp[order[q + t]].seq2 != p->hp[order[q + t - 1]].seq2) ? build[t] : 0);
-        // number of ranges a bound needs (cuts[] = first pair of every range when asked for)
-        auto pack = [&](int64_t bound, std::vector<size_t>* cuts) {
-            int64_t ranges = 0, acc = 0;
-            size_t t0 = 0;
-            for (size_t t = 0; t < n; ++t) {
-                const int64_t add = t == t0 ? probe[t] + build[t] : inside[t];
-                const bool full = (int)(t - t0) >= ctx->reads_per_task;
-                if (t > t0 && (acc + add > bound || full)) {
-                    ++ranges;
-                    if (cuts) cuts->push_back(t0);
-                    t0 = t;
-                    acc = probe[t] + build[t];
-                } else {
-                    acc += add;
-                }
-            }
-            ++ranges;
-            if (cuts) cuts->push_back(t0);
-            return ranges;
-        };
-        // the smallest bound that needs at most `want` ranges: no partition can do with less than the costs inside
-        // ranges shared out evenly, a doubling search finds a bound that is enough, bisection the smallest between
-        int64_t in_sum = 0;
-        for (size_t t = 0; t < n; ++t) in_sum += inside[t];
-        int64_t lo = std::max(biggest, in_sum / want), hi = lo;
-        while (hi < total && pack(hi, nullptr) > want) { lo = hi + 1; hi = std::min(total, hi * 2); }
-        while (lo < hi) {
-            const int64_t mid = lo + (hi - lo) / 2;
-            if (pack(mid, nullptr) <= want) hi = mid; else lo = mid + 1;
-        }
-        std::vector<size_t> cuts;
-        pack(lo, &cuts);
-        p->launches.push_back(Launch{m == 4 ? 4 : 2, k, (int)p->tasks.size(), 0, m == 3 ? 1 : m == 5 ? 2 : 0});
-        for (size_t c = 0; c < cuts.size(); ++c) {
-            const size_t t0 = q + cuts[c], t1 = q + (c + 1 < cuts.size() ? cuts[c + 1] : n);
-            DTask tk;
-            tk.seq2 = p->hp[order[t0]].seq2; tk.k = k; tk.n_reads = (int32_t)(t1 - t0); tk.first = (int32_t)t0;
-            p->tasks.push_back(tk);
-            p->launches.back().n_tasks++;
-        }
-        q = e;
-    }
+    static_cast<PlanLayout&>(*p) = plan_layout(PlanParams{ctx->reads_per_task, ctx->join_tasks, ctx->max_pair_cap, ctx->shared_join,
+                                                          tile_pos<JoinCfg, 2>(), tile_pos<JoinCfg, 4>()},
+                                               SetView{set->h, set->n, set->n_lit, set->derived, set->groups, set->group_of, set->slot_of},
+                                               n_pairs, pairs);
+    p->hcap_want = (int)std::min<int64_t>(p->hwant, CLEAN_HCAP_MAX);
+    p->n_dpairs = (int64_t)p->shares.size();
     HIPCHK(dmalloc(ctx, (void**)&p->d_pairs, sizeof(DPair) * p->hp.size()));
     HIPCHK(dmalloc(ctx, (void**)&p->d_tasks, sizeof(DTask) * std::max<size_t>(p->tasks.size(), 1)));
-    HIPCHK(dmalloc(ctx, (void**)&p->d_task_pairs, sizeof(int32_t) * std::max<size_t>(order.size(), 1)));
+    HIPCHK(dmalloc(ctx, (void**)&p->d_task_pairs, sizeof(int32_t) * std::max<size_t>(p->task_pairs.size(), 1)));
     HIPCHK(dmalloc(ctx, (void**)&p->d_nhits, sizeof(unsigned long long) * p->hp.size()));
     HIPCHK(hipMemsetAsync(p->d_nhits, 0, sizeof(unsigned long long) * p->hp.size(), ctx->stream));
     HIPCHK(dmalloc(ctx, (void**)&p->d_stats, sizeof(long long) * 16 * p->hp.size()));
@@ -2046,7 +1634,8 @@ extern "C" int vapor_plan_create(vapor_ctx* ctx, vapor_seqset* set, int64_t n_pa
     // 80 000 pairs costs a pipeline chunk's plan 3-4 ms: the order is made for plans of up to eight rounds)
     if (ctx->clean_order && n_pairs > 1 && n_pairs <= (int64_t)8 * (2048 / CLEAN_THREADS) * ctx->n_cus) {
         HIPCHK(dmalloc(ctx, (void**)&p->d_clean_order, sizeof(int32_t) * (size_t)n_pairs));
-        if (const int rc = plan_clean_order(p.get(), nullptr)) return rc;
+        const std::vector<int32_t> ord = clean_order(*p, n_pairs);
+        HIPCHK(hipMemcpy(p->d_clean_order, ord.data(), sizeof(int32_t) * (size_t)n_pairs, hipMemcpyHostToDevice));
     }
     for (auto& e : p->ev) HIPCHK(hipEventCreate(&e));
     for (auto& e : p->ev_f) HIPCHK(hipEventCreate(&e));
@@ -2054,8 +1643,8 @@ extern "C" int vapor_plan_create(vapor_ctx* ctx, vapor_seqset* set, int64_t n_pa
     // (the copies read the plan's own vectors: a plan that fails here is destroyed after its stream is synchronised)
     if (!p->tasks.empty())
         HIPCHK(hipMemcpyAsync(p->d_tasks, p->tasks.data(), sizeof(DTask) * p->tasks.size(), hipMemcpyHostToDevice, ctx->stream));
-    if (!order.empty())
-        HIPCHK(hipMemcpyAsync(p->d_task_pairs, p->task_pairs.data(), sizeof(int32_t) * order.size(), hipMemcpyHostToDevice, ctx->stream));
+    if (!p->task_pairs.empty())
+        HIPCHK(hipMemcpyAsync(p->d_task_pairs, p->task_pairs.data(), sizeof(int32_t) * p->task_pairs.size(), hipMemcpyHostToDevice, ctx->stream));
     if (const int rc = plan_alloc_hits(p.get())) return rc;
     HIPCHK(hipStreamSynchronize(ctx->stream));
     p->last_stats.assign((size_t)n_pairs * 16, 0);

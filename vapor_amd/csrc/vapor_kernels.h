@@ -19,6 +19,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "vapor_records.h"   // SeqDesc, DPair, DTask, the shared joins' DMap / DShare / DServe and their table format
+
 // Developer switches (phase / workgroup timing builds, tools/ab.py variants, non-default tuning constants) exist only in
 // a build made with -DVAPOR_DEV_BUILD, which reports itself through vapor_build_flags() and a different
 // vapor_abi_version(): the product loader (vapor_amd/_lib.py) refuses such a library.  A stray -D of one of them without
@@ -30,38 +32,12 @@
 
 namespace vapor {
 
-// ------------------------------------------------------------------------------------------
-// device-side records
-// ------------------------------------------------------------------------------------------
-struct SeqDesc {       // 32 B
-    uint32_t chunk0;   // first 32-base chunk of this sequence in the planes
-    int32_t len;
-    int32_t n_exc;     // symbols outside upper-case ACGT
-    int32_t n_invalid; // symbols outside invert_base's alphabet (after IUPAC folding)
-    uint32_t asc0;     // first 32-byte chunk in the ASCII staging blob (pack only)
-    uint32_t flags;
-    int32_t n_nocomp;  // symbols complementary() would DROP (SF:471-478: anything outside ATGCN / atgcn); bytes only
-    uint32_t pad;
-};
-
-struct DPair {         // 40 B
-    int32_t seq1, seq2, off2, k;
-    uint32_t flags, cap;
-    int64_t hit_off;
-    int32_t len1, len2;  // sequence lengths (the clean kernels need nothing else of the sequences)
-};
-
-struct DTask {         // 16 B: pairs task_pairs[first .. first + n_reads) of one launch, sorted by allele
-    int32_t seq2, k, n_reads, first;
-};
-
 // plane geometry: every sequence starts on a 32-base chunk; a chunk is 2 words of the 2-bit
 // plane, 1 word of the exception plane, 4 words of the 4-bit plane.
 #define VP_P2_WORDS_PER_CHUNK 2
 #define VP_X4_WORDS_PER_CHUNK 4
 #define VP_PAD_CHUNKS 3  // zeroed chunks after each sequence: window reads may run this far
 
-constexpr int MAX_READS_PER_TASK = 64;
 #ifndef VAPOR_CLEAN_THREADS
 #define VAPOR_CLEAN_THREADS 256
 #endif
@@ -839,38 +815,8 @@ __device__ __forceinline__ void build_walk16(const uint32_t* tile, const uint32_
     }
 }
 
-// ---- shared joins: what remap_kernel reads (described with the kernel below) ----
-struct DMap {          // 16 B (host side: the interval maps of a (window, k) group before they are cut into the table below)
-    int32_t lo, hi;    // k-mer starts of the shared sequence, inclusive
-    int32_t base;      // position in the target at e == lo
-    uint16_t flip;     // 1: reverse-complemented slice (j decreases with e, strands swap)
-    uint16_t slot;     // which target of the share
-};
-// What the kernel reads is the same maps cut at each other's ends: boundaries B[0] = 0 < B[1] < ... < B[n_iv] over the k-mer
-// starts of the shared sequence, and per elementary interval [B[t], B[t+1]) what a dot inside it becomes - for every target
-// slot up to two ops (a tandem duplication's repeated stretch lies twice in its allele), each one word:
-//     bit 0 valid, bit 1 flip, bits 2.. delta (signed):   j = e + delta,  or  j = delta - e with the strands swapped.
-// A record looks its interval up once (binary search) and is then copied, shifted, under the ops of that interval; only a run
-// that crosses a boundary is cut, interval by interval.
-constexpr int REMAP_MAX_IV = 48;       // elementary intervals per share (the host shares no group with more)
+// ---- shared joins: the records and the table format remap_kernel reads are in vapor_records.h ----
 constexpr int REMAP_PER = 4;           // records per thread and round
-constexpr int REMAP_OPS = 8;           // op words per interval: 4 target slots x 2 copies
-struct DShare {        // 32 B
-    int32_t dpair;     // the (read, T) pair the join ran
-    int32_t iv_first;  // first word of this group's table in the maps buffer: B[0 .. n_iv], then n_iv x REMAP_OPS op words
-    int32_t n_iv;
-    int32_t target[4]; // pair index per slot, -1: this read has no pair against that allele
-    int32_t pad;
-};
-
-struct DServe {        // 32 B per pair: what the clean workgroup of a pair served by a shared join needs to cut its records out
-    int64_t hit_off;   // of the shared dot plot: the (read, T) pair's record slot ...
-    uint32_t cap;
-    int32_t dpair;     // ... its index (-1: this pair ran a join of its own),
-    int32_t iv_first, n_iv;   // the group's table
-    int32_t slot;      // and this pair's slot in it
-    int32_t pad;
-};
 
 // EXC (2-bit planes; the host groups the pairs): 1 - the launch holds the pairs whose ALLELE has symbols outside upper-case
 // ACGT: the table leaves out the k-mers that cover one, runs end before them.  2 - the pairs whose READ has such symbols (and
