@@ -358,6 +358,20 @@ def test_block_decoder_against_zlib():
     assert n_cases == 6 * 10 * 4 * 4
 
 
+def test_block_decoder_on_legal_deflate_that_zlib_never_writes():
+    """The same decoder on the families of tests/deflate_forms.py (codes of 15 bits with the widest extra fields, the widest
+    header, code lengths in any order, 284 + 31 for length 258, a lone one-bit distance code, empty stored blocks, 65 536-byte
+    blocks ...; every stream confirmed by zlib's inflate): zlib's bytes, nothing written behind them, size +- 1 refused."""
+    import deflate_forms
+    items = deflate_forms.all_forms(1)
+    assert len(items) >= 3000
+    for k, (family, stream, data) in enumerate(items):
+        assert _native_inflate(stream, len(data)) == data, (k, family, len(stream), len(data))
+        if data:
+            assert _native_inflate(stream, len(data) - 1) is None, (k, family)
+        assert _native_inflate(stream, len(data) + 1) is None, (k, family)
+
+
 def test_block_crc_against_zlib():
     """vapor_crc32 - the CRC-32 every inflated block is checked with - against zlib.crc32 on both of its paths (carry-less
     multiply folding for the 16-byte multiples of 64 bytes and more where the host has it; tables for the rest and,

@@ -4,10 +4,16 @@
 // 65 536 bytes, the CRC-32 by slices against zlib's, and damaged streams (every outcome but a wrong "ok" is fine; the address
 // and undefined-behaviour sanitizers watch the buffers).  Built and run by tests/test_bamdev_emu.py:
 //   g++ -O1 -g -fsanitize=address,undefined -DVBD_EMU -Ivapor_amd/csrc tools/bamdev_emu.cpp -lz -o /tmp/bamdev_emu
+//   bamdev_emu [rounds]         the zlib-made streams
+//   bamdev_emu --forms FILE     streams from a file of records (u32 number, u32 c_len, u32 u_len, the stream, the expected bytes:
+//                               tests/deflate_forms.py writes legal DEFLATE that zlib's encoder never does) through this decoder and
+//                               through the host's (vapor_inflate::inflate_raw), and the wrong-CRC / wrong-size variants of each
 #include "vapor_bamdev.h"
+#include "vapor_inflate.h"
 
 #include <zlib.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -65,9 +71,55 @@ static int run(const std::vector<uint8_t>& comp, size_t u_len, uint32_t crc, std
     return rc;
 }
 
+static int run_forms(const char* path)
+{
+    FILE* f = fopen(path, "rb");
+    if (!f) { fprintf(stderr, "cannot open %s\n", path); return 2; }
+    std::mt19937_64 rng(777);
+    static vapor_inflate::Decoder work;
+    long n = 0, n_equal = 0, n_refused = 0, n_wrong = 0, n_tables = 0, n_host = 0, n_variants = 0;
+    uint32_t h[3];
+    while (fread(h, 4, 3, f) == 3) {
+        if (h[2] > (uint32_t)U_MAX || h[1] > (1u << 20)) { fprintf(stderr, "record %u: sizes %u / %u\n", h[0], h[1], h[2]); return 2; }
+        std::vector<uint8_t> comp(h[1]), data(h[2]), got;
+        if ((h[1] && fread(comp.data(), 1, h[1], f) != h[1]) || (h[2] && fread(data.data(), 1, h[2], f) != h[2])) { fprintf(stderr, "record %u is cut short\n", h[0]); return 2; }
+        ++n;
+        const size_t u = data.size();
+        const uint32_t crc = (uint32_t)crc32(0L, data.data(), (uInt)u);
+        const int align = (int)(rng() % 16);
+        const int rc = run(comp, u, crc, got, align);
+        if (rc == BLK_OK && got == data) ++n_equal;
+        else {
+            if (rc == BLK_TABLES) ++n_tables;
+            if (rc == BLK_OK) ++n_wrong; else ++n_refused;
+            if (n_refused + n_wrong <= 400) fprintf(stderr, "FAIL record %u (%u -> %u bytes, alignment %d): rc %d, bytes %s\n", h[0], h[1], h[2], align, rc, got == data ? "equal" : "differ");
+        }
+        // the host's decoder on the same stream (exact buffers: the sanitizer sees a read or write outside them)
+        std::vector<uint8_t> hout(u ? u : 1);                 // (never a null pointer, also for an empty block)
+        if (!vapor_inflate::inflate_raw(comp.data(), comp.size(), hout.data(), u, work) || !std::equal(data.begin(), data.end(), hout.begin())) {
+            ++n_host;
+            fprintf(stderr, "FAIL record %u: the host decoder refuses it or gives other bytes\n", h[0]);
+        }
+        if (u > 0 && vapor_inflate::inflate_raw(comp.data(), comp.size(), hout.data(), u - 1, work)) { ++n_host; fprintf(stderr, "FAIL record %u: the host decoder accepts size - 1\n", h[0]); }
+        hout.resize(u + 1);
+        if (vapor_inflate::inflate_raw(comp.data(), comp.size(), hout.data(), u + 1, work)) { ++n_host; fprintf(stderr, "FAIL record %u: the host decoder accepts size + 1\n", h[0]); }
+        // the same stream with a wrong CRC and a wrong size
+        int bad = 0;
+        if (run(comp, u, crc ^ 1u, got, align) != BLK_CRC) ++bad;
+        if (u > 0 && run(comp, u - 1, crc, got, align) == BLK_OK) ++bad;
+        if (u < (size_t)U_MAX && run(comp, u + 1, crc, got, align) == BLK_OK) ++bad;
+        if (bad && rc == BLK_OK) { ++n_variants; fprintf(stderr, "FAIL record %u: %d of its wrong-CRC / wrong-size variants were not refused as they must be\n", h[0], bad); }
+    }
+    fclose(f);
+    printf("bamdev_emu forms: %ld streams, %ld equal, %ld refused (%ld refused for table size), %ld wrong bytes, %ld host decoder failures, %ld variant failures\n",
+           n, n_equal, n_refused, n_tables, n_wrong, n_host, n_variants);
+    return n_refused || n_wrong || n_host || n_variants ? 1 : 0;
+}
+
 int main(int argc, char** argv)
 {
-    const int rounds = argc > 1 ? atoi(argv[1]) : 40;
+    const bool forms = argc > 2 && !strcmp(argv[1], "--forms");
+    const int rounds = argc > 1 && !forms ? atoi(argv[1]) : 40;
     for (int l = 0; l < 64; ++l) {
         // x^(8 * 1024 * (63 - l)) mod P by square and multiply (bit 31 = x^0, bit 30 = x^1)
         uint64_t e = (uint64_t)8 * 1024 * (uint64_t)(63 - l);
@@ -75,6 +127,7 @@ int main(int argc, char** argv)
         while (e) { if (e & 1) r = crc_mulmod(r, b); b = crc_mulmod(b, b); e >>= 1; }
         g_pow[l] = r;
     }
+    if (forms) return run_forms(argv[2]);
     std::mt19937_64 rng(12345);
     long n_ok = 0, n_damaged = 0, n_damaged_caught = 0, n_tables = 0;
     const int sizes[] = {0, 1, 2, 3, 4, 5, 63, 64, 65, 1023, 1024, 1025, 4096, 16384, 40000, 65279, 65280, 65535, 65536};

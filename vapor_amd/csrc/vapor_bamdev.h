@@ -459,15 +459,19 @@ VBD_DEV void decode_batch(InflateLds& L, uint8_t* out, uint32_t u_len, uint32_t 
             if (err) break;
             phase = 1;
         }
-        // ---- the fast loop: sixteen stream bytes behind ip (two refills that clamp nothing), eight bytes of room in the output
-        // (four double literals stored without a test).  No bit count can go negative here: every symbol starts with 48 bits.
+        // ---- the fast loop: sixteen stream bytes behind ip (two refills that clamp nothing - a third could take the zeros behind
+        // in_have for stream bits), eight bytes of room in the output (four double literals stored without a test).  The bit budget:
+        // a refill leaves 64 stream bits in buf (n counts the whole bytes among them); a general symbol takes 48 at most
+        // (15 + 5 + 15 + 13) and the first-level lookup that closes the iteration reads LLB more, so a general symbol is decoded
+        // only where bits dropped since the last refill + 48 + LLB <= 64.  No bit count can go negative here.
         nq = (int)VBD_CTL(nq);
         if ((int)VBD_CTL(b.n) >= 0 && (int)VBD_CTL(b.ip) + 16 <= b.in_have && VBD_CTL(op) + 8 <= u_len) {
             refill_fast<SC>(b);
             uint32_t e = VBD_UNI(L.ll[(uint32_t)b.buf & LL_MASK]);
             bool leave = false;
             for (;;) {
-                // (e is the first-level entry at the current position: a refill leaves the bits that are there in place)
+                // (e is the first-level entry at the current position, read from LLB stream bits - the bit budget above sees to
+                // that; the refill below leaves the bits that are there in place, so e still holds behind it)
                 // (said to be uniform once more - it costs nothing where the compiler knows, and keeps the loop on the scalar
                 // unit where a branch on something a table builder read made it doubt)
                 b.buf = (uint64_t)VBD_UNI((uint32_t)b.buf) | ((uint64_t)VBD_UNI((uint32_t)(b.buf >> 32)) << 32);
@@ -504,8 +508,11 @@ VBD_DEV void decode_batch(InflateLds& L, uint8_t* out, uint32_t u_len, uint32_t 
 #undef VBD_EMIT
                     if (VBD_IS_LIT1(VBD_CTL(e))) continue;
                     if ((int)VBD_CTL(b.ip) + 8 > b.in_have || VBD_CTL(op) + 8 > u_len) break;
-                    // (the symbol that follows needs 48 bits at most; one literal step out of a refill of 57 and more leaves them)
-                    if ((int)VBD_CTL(b.n) < 48) refill_fast<SC>(b);
+                    // (the symbol that follows takes 48 bits at most and the closing lookup LLB more: n >= 48 + LLB says that at most
+                    // 63 - 48 - LLB bits were dropped since the refill.  With n < 48 alone the closing lookup could read zeros
+                    // above the stream bits that were left - behind literals of 8 and more bits and a symbol of 40 and more -
+                    // and a valid block ended as BLK_BAD_STREAM.)
+                    if ((int)VBD_CTL(b.n) < 48 + LLB) refill_fast<SC>(b);
                 }
                 VBD_COUNT(4);
 #if defined(VBD_TIMING) && !defined(VBD_EMU)
