@@ -296,6 +296,8 @@ static int run_pair(const vapor_seqset* s, const vapor_pair& a, PairRes& r)
     if (rc != 0) return fail(VAPOR_E_NOMEM, "oracle failure");
     r.hits.resize((size_t)n * 2); r.k1.resize((size_t)n); r.k2.resize((size_t)n);
     mask_flags(a.flags, r.st);
+    if (!(a.flags & VAPOR_PF_C1)) std::fill(r.k1.begin(), r.k1.end(), 0);      // (a cleaner the pair did not ask for sets no flag byte)
+    if (!(a.flags & VAPOR_PF_C2)) std::fill(r.k2.begin(), r.k2.end(), 0);
     if ((a.flags & VAPOR_PF_DIR) && (a.flags & VAPOR_PF_C1) && r.st[3] > 0) dir_stats(r, r.st);
     return 0;
 }

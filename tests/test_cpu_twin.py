@@ -64,6 +64,16 @@ def test_derived_sequences_on_the_twin(eng, oracle):
     assert D.check_random_structures(eng, oracle, n_windows=3) == 0
 
 
+def test_dot_designs_on_the_twin(eng, oracle):
+    """The plan-route bodies of tests/test_gpu_dot_designs.py on the twin (its list bodies run in tests/test_dot_designs_cpu.py; the
+    twin has no wide route and joins pair by pair): the sequence-built designs, the doubled 33 kb pair and the group of a window
+    with a derived inversion and duplication give the record and the flag bytes of tests/dot_designs.py's reference."""
+    import test_gpu_dot_designs as G
+    G.check_sequences(eng)
+    G.check_doubled_33kb(eng)
+    G.check_served_group(eng, 0, want_shared=False)
+
+
 def test_pipeline_and_cli_on_the_twin(eng, tmp_path):
     """`vapor bed` through pipeline.run_batch with the real Engine on the twin: the reference's table."""
     from conftest import load_golden

@@ -5,6 +5,7 @@ import hashlib
 import numpy as np
 import pytest
 
+import dot_designs
 from conftest import load_golden
 
 pytestmark = pytest.mark.gpu
@@ -90,6 +91,7 @@ def _check_stats_vs_oracle(eng, oracle, seqs, upper, rows, tag=""):
             assert got[10] == int(round(2 * float(c))), (tag, t, "c", got[10], c)
             assert got[11] == len(far), (tag, t, "dir_n")
             assert got[12] == int(round(2 * sum(d[0] - d[1] for d in far))), (tag, t, "dir_sum")
+            assert got[13] == dot_designs.r4_lists(kept)[1], (tag, t, "dir_lists", got[13])
     return st
 
 

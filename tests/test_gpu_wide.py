@@ -3,6 +3,8 @@ against the C oracle (int32 positions, no length limit) and, for pairs both rout
 import numpy as np
 import pytest
 
+import dot_designs
+
 pytestmark = pytest.mark.gpu
 
 ACGT = np.frombuffer(b"ACGT", dtype=np.uint8)
@@ -74,18 +76,24 @@ def test_stats_against_oracle(eng, oracle):
     ss = eng.seqset(seqs)
     st = eng.score_wide(ss, eng.make_pairs(rows))
     ss.close()
-    exp_of = {}
+    exp_of, r4_of, n_dir = {}, {}, 0
     for t, (s1, s2, off2, k, fl) in enumerate(rows):
         key = (s1, s2, off2, k)
         if key not in exp_of:
-            exp_of[key] = oracle.pair_stats(k, seqs[s1], seqs[s2][off2:])
-        exp = exp_of[key].copy()
+            exp_of[key] = oracle.pair_stats(k, seqs[s1], seqs[s2][off2:], want_hits=True)
+        exp = exp_of[key][0].copy()
         if not fl & 1:
             exp[3] = exp[4] = 0
         if not fl & 2:
             exp[5] = exp[6] = exp[9] = 0
         _check_stats(st[t], exp, (t, rows[t]))
-    assert int(st[:, 0].min()) > 0
+        if fl == 5:                                 # the directed statistics, once per pair and window size
+            if key not in r4_of:
+                _st, h, k1, _k2 = exp_of[key]
+                r4_of[key] = dot_designs.r4_words(h[k1 > 0].tolist()) if exp[3] > 0 else [0, 0, 0, 0]
+            assert st[t, 10:14].tolist() == r4_of[key], (t, rows[t], st[t, 10:14].tolist(), r4_of[key])
+            n_dir += 1
+    assert int(st[:, 0].min()) > 0 and n_dir == len(rows) // 4
 
 
 def test_large_pairs_cap_and_refusal(eng, oracle):

@@ -1711,8 +1711,9 @@ __device__ __forceinline__ void directed_stats(HP recs, FP hflags, int n, uint32
     if (tid == 0) { sh->n_lists = 0; sh->c2x = 0; sh->dir_n = 0; sh->dir_sum2 = 0; sh->win_w = -1; }
     if (tid < 11) sh->cnt1[tid] = 0;
     __syncthreads();
+    if (sh->kd_hi < sh->kd_lo) return;             // no kept dots (uniform): kd_lo / kd_hi hold their initial +/- 2^31 - 1, whose
+                                                   // difference does not fit an int - compare them, do not subtract
     const int lo1 = sh->kd_lo, range1 = sh->kd_hi - sh->kd_lo;
-    if (range1 < 0) return;                        // no kept dots (uniform)
     const R4Div d1(lo1, range1);
     // level 1: sizes of the eleven lists
     for (int h = tid; h < n; h += CLEAN_THREADS) {

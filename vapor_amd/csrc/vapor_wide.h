@@ -273,11 +273,11 @@ __global__ __launch_bounds__(WIDE_SCAN_THREADS) void wide_dir_kernel(const int2*
     __shared__ unsigned long long dir_sum;
     __shared__ uint32_t part[WIDE_SCAN_THREADS];
     const int tid = threadIdx.x;
-    const int lo1 = acc->kd_lo, range1 = acc->kd_hi - acc->kd_lo;
-    if (range1 < 0) {                                  // no kept dots
+    if (acc->kd_hi < acc->kd_lo) {                     // no kept dots (the initial +/- 2^31 - 1: their difference does not fit an int)
         if (tid == 0) { acc->dir_c2x = 0; acc->dir_n = 0; acc->dir_sum2 = 0; acc->dir_lists = 0; }
         return;
     }
+    const int lo1 = acc->kd_lo, range1 = acc->kd_hi - acc->kd_lo;
     if (tid < 11) cnt1[tid] = 0;
     if (tid == 0) { n_lists = 0; c2x = 0; dir_n = 0; dir_sum = 0; sel_w = -1; }
     __syncthreads();
