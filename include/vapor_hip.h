@@ -354,6 +354,14 @@ typedef struct vapor_bam vapor_bam;
 int vapor_bam_open(const char* path, vapor_bam** bam);
 int vapor_bam_close(vapor_bam* bam);
 int vapor_bam_set_threads(vapor_bam* bam, int32_t n_threads);
+/* Read filter of an open handle (`--min-mapq Q`, `--exclude-flags F`), Q = min_mapq and F = exclude_flags:
+ * A record is *filtered* iff `MAPQ < Q` or `(FLAG & F) != 0` - this is `samtools view -q Q -F F`; MAPQ 255 passes every Q.
+ * A filtered record is treated as if it were not in the file.  It is skipped after the checks every record gets (record size,
+ * inner layout, contig and position order) and before the first decision about keeping it, so it sets no status, raises no
+ * error and counts towards no limit; a malformed record is still malformed.  The setting is a property of the handle:
+ * vapor_bam_chop, _tagged, _haplotag, _right and the four vapor_bam_chop_device* calls made with it apply it.  A new handle
+ * has (0, 0), which filters nothing.  VAPOR_E_ARG outside 0 <= min_mapq <= 255, exclude_flags <= 65535. */
+int vapor_bam_set_filter(vapor_bam* bam, int32_t min_mapq, uint32_t exclude_flags);
 const char* vapor_bam_last_error(void);
 int vapor_bam_chop(vapor_bam* bam, int32_t tid, int64_t start, int64_t end, int64_t flank, int32_t n_chunks,
                    const uint64_t* chunks, uint8_t* seq_out, int64_t seq_cap, char* names_out, int64_t names_cap,

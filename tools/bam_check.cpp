@@ -2,7 +2,9 @@
 // record of a file through vapor_bam_chop - one index chunk from the given virtual offset to the end of the file, a window
 // per call - and prints the status of each call.  A damaged file must end in a status, never in a report of the sanitizer.
 //   g++ -O1 -g -fsanitize=address,undefined -Iinclude -Ivapor_amd/csrc -o /tmp/bam_check tools/bam_check.cpp -lz -lpthread
-//   ASAN_OPTIONS=detect_leaks=0 /tmp/bam_check file.bam <first virtual offset> <tid> <start> <end> <flank> [threads]
+//   ASAN_OPTIONS=detect_leaks=0 /tmp/bam_check file.bam <first virtual offset> <tid> <start> <end> <flank> [threads [min_mapq exclude_flags]]
+// With min_mapq and exclude_flags (decimal or 0x hex) the handle carries that read filter (vapor_bam_set_filter), and
+// the right-anchored and the tagged reader walk the file behind the plain one; without them nothing changes.
 // tests/test_bamio.py builds it and runs it over the damaged files of its other tests and a few hundred randomly damaged ones.
 #include "vapor_bam.cpp"
 #include <cstdio>
@@ -10,10 +12,15 @@
 
 int main(int argc, char** argv)
 {
-    if (argc < 7) { fprintf(stderr, "usage: bam_check file.bam first_voffset tid start end flank [threads]\n"); return 2; }
+    if (argc < 7) { fprintf(stderr, "usage: bam_check file.bam first_voffset tid start end flank [threads [min_mapq exclude_flags]]\n"); return 2; }
     vapor_bam* b = nullptr;
     if (vapor_bam_open(argv[1], &b) != 0) { printf("open: %s\n", vapor_bam_last_error()); return 0; }
     if (argc > 7) vapor_bam_set_threads(b, atoi(argv[7]));
+    const bool filtered = argc > 9;
+    if (filtered) {
+        const int frc = vapor_bam_set_filter(b, (int32_t)strtol(argv[8], nullptr, 0), (uint32_t)strtoul(argv[9], nullptr, 0));
+        printf("filter: rc %d %s\n", frc, frc ? vapor_bam_last_error() : "");
+    }
     struct stat st;
     if (stat(argv[1], &st) != 0) return 2;
     const uint64_t chunk[2] = {strtoull(argv[2], nullptr, 10), (uint64_t)st.st_size << 16};
@@ -36,6 +43,27 @@ int main(int argc, char** argv)
         long long bases = 0;
         for (int32_t r = 0; r < n && rc == 0; ++r) bases += meta[4 * r + 1];
         printf("sized buffers: rc %d reads %d bases %lld %s\n", rc, n, bases, rc ? vapor_bam_last_error() : "");
+    }
+    if (filtered) {
+        // the other flavours of the reader under the same filter, their buffers sized by a first call each
+        for (int flavour = 0; flavour < 2; ++flavour) {
+            const int w = flavour ? 6 : 4;
+            auto call = [&](int32_t max_reads) {
+                return flavour ? vapor_bam_chop_tagged(b, tid, start, end, flank, 1, chunk, seq.data(), (int64_t)seq.size(), names.data(),
+                                                       (int64_t)names.size(), meta.data(), max_reads, &n, need)
+                               : vapor_bam_chop_right(b, tid, start, end, flank, 1, chunk, seq.data(), (int64_t)seq.size(), names.data(),
+                                                      (int64_t)names.size(), meta.data(), max_reads, &n, need);
+            };
+            meta.resize((size_t)w * std::max<size_t>(meta.size() / 4, 1));
+            rc = call((int32_t)(meta.size() / (size_t)w));
+            if (rc == VAPOR_E_OVERFLOW) {
+                seq.resize((size_t)need[0] + 16); names.resize((size_t)need[1] + 16); meta.resize((size_t)w * ((size_t)need[2] + 1));
+                rc = call((int32_t)need[2] + 1);
+            }
+            long long bases = 0;
+            for (int32_t r = 0; r < n && rc == 0; ++r) bases += meta[(size_t)w * r + 1];
+            printf("%s: rc %d reads %d bases %lld %s\n", flavour ? "tagged" : "right", rc, n, bases, rc ? vapor_bam_last_error() : "");
+        }
     }
     vapor_bam_close(b);
     return 0;

@@ -57,13 +57,17 @@ EXPORTS = [
     "vapor_bam_chop_tagged", "vapor_bam_chop_device_tagged",
     "vapor_chop_records_right", "vapor_chop_records_right_many", "vapor_bam_chop_right", "vapor_bam_chop_device_right",
     "vapor_bam_chop_haplotag", "vapor_bam_chop_device_haplotag",
+    "vapor_bam_set_filter",
 ]
 # entry points a library may lack (the CPU twin of the C ABI has no wide or any-k route and no refinement kernel): bound when
 # present, and the engine's wide, any-k and grid methods raise NotImplementedError when they are not
 OPTIONAL_EXPORTS = ("vapor_wide_batch", "vapor_clean_hits_wide", "vapor_anyk_batch", "vapor_plan_set_grid", "vapor_plan_run_grid",
                     "vapor_grid_pick", "vapor_bam_chop_device_tagged",
                     "vapor_chop_records_right", "vapor_chop_records_right_many", "vapor_bam_chop_right", "vapor_bam_chop_device_right",
-                    "vapor_bam_chop_device_haplotag")
+                    "vapor_bam_chop_device_haplotag",
+                    # (the read filter of a handle, `--min-mapq` / `--exclude-flags`: without it a run with a filter takes the
+                    # Python statement of the readers, seqio.InProcessBam)
+                    "vapor_bam_set_filter")
 MAX_CANDIDATES = 128           # breakpoint refinement: candidates per locus (VAPOR_MAX_CANDIDATES)
 
 _lib = None
@@ -237,6 +241,8 @@ def bind(L: ctypes.CDLL) -> ctypes.CDLL:
         L.vapor_bam_chop_right.argtypes = L.vapor_bam_chop.argtypes
     if hasattr(L, "vapor_bam_chop_device_right"):
         L.vapor_bam_chop_device_right.argtypes = L.vapor_bam_chop_device.argtypes
+    if hasattr(L, "vapor_bam_set_filter"):
+        L.vapor_bam_set_filter.argtypes = [vp, ctypes.c_int32, ctypes.c_uint32]
     if hasattr(L, "vapor_plan_run_grid"):
         L.vapor_plan_run_grid.argtypes = [vp, i32p, f64p, f64p, i64p]
     for name in EXPORTS:

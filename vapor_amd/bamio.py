@@ -221,6 +221,10 @@ class BamFile:
         self._free = []
         self._handles = []
         self._lock = threading.Lock()
+        # the read filter (min_mapq, exclude_flags): a record is filtered iff MAPQ < min_mapq or FLAG & exclude_flags,
+        # and a filtered record is as if it were not in the file.  fetch_raw applies it for the Python statement, every native
+        # handle carries it (set_filter)
+        self.read_filter = (0, 0)
         import os
         bai = path + ".bai" if os.path.exists(path + ".bai") else path[:-4] + ".bai"
         self.index = BaiIndex(bai)
@@ -249,7 +253,7 @@ class BamFile:
 
     @classmethod
     def _parse(cls, rec: bytes):
-        ref_id, pos, l_name, _mapq, _bin, n_cig, flag, l_seq = struct.unpack_from("<iiBBHHHi", rec, 0)
+        ref_id, pos, l_name, mapq, _bin, n_cig, flag, l_seq = struct.unpack_from("<iiBBHHHi", rec, 0)
         p = 32
         name = rec[p:p + l_name - 1].decode()
         p += l_name
@@ -262,7 +266,32 @@ class BamFile:
             if real is not None:
                 cig = real
         from . import phase
-        return ref_id, pos, name, flag, cig, l_seq, sq, phase.tags_from_aux(rec, p + nb + l_seq)
+        return ref_id, pos, name, flag, cig, l_seq, sq, phase.tags_from_aux(rec, p + nb + l_seq), mapq
+
+    def set_filter(self, min_mapq: int, exclude_flags: int) -> None:
+        """The read filter of this file: fetch_raw and everything on it from now on, the native handles that
+        exist and every one made later (vapor_bam_set_filter).  A library without that entry keeps its handles unfiltered:
+        native_filter_ok() says so, and the callers take the Python statement then."""
+        flt = check_filter(min_mapq, exclude_flags)
+        with self._lock:
+            # (under the lock: no other thread takes a handle between the new value and the handles that carry it)
+            if flt == self.read_filter:
+                return
+            if self._handles:
+                from . import _lib
+                lib = _lib.load()
+                if hasattr(lib, "vapor_bam_set_filter"):
+                    for h in self._handles:
+                        if lib.vapor_bam_set_filter(h, flt[0], flt[1]) != 0:
+                            raise ValueError(lib.vapor_bam_last_error().decode())
+            self.read_filter = flt
+
+    def native_filter_ok(self) -> bool:
+        """Whether the native readers of this file apply its filter: none is set, or the library has vapor_bam_set_filter."""
+        if self.read_filter == (0, 0):
+            return True
+        from . import _lib
+        return hasattr(_lib.load(), "vapor_bam_set_filter")
 
     def chop_native(self, chrom: str, start: int, end: int, flank_length: int, tagged: bool = False, right: bool = False, sites=None):
         """chop_pacbio_read_by_pos (SF:339-354) for one region through the library's native reader (vapor_bam_chop:
@@ -324,6 +353,9 @@ class BamFile:
         (Handles are not tied to threads: a pool of threads that lives for one batch would leave its handles - a file
         descriptor and the inflate buffers each - behind for every batch of a long run.)"""
         import ctypes
+        if self.read_filter != (0, 0) and not hasattr(lib, "vapor_bam_set_filter"):
+            # (no handle of such a library applies the filter: the callers take the Python statement, seqio.InProcessBam)
+            raise NotImplementedError("the loaded library has no read filter (vapor_bam_set_filter)")
         with self._lock:
             if self._free:
                 return self._free.pop()
@@ -333,6 +365,11 @@ class BamFile:
         if threading.current_thread() is not threading.main_thread():
             import os
             lib.vapor_bam_set_threads(h, int(os.environ.get("VAPOR_BAM_INFLATE_THREADS", "2")))   # several readers at once: fewer inflate threads each
+        if self.read_filter != (0, 0):
+            # (every handle of the file gets the filter when it is made)
+            if lib.vapor_bam_set_filter(h, self.read_filter[0], self.read_filter[1]) != 0:
+                lib.vapor_bam_close(h)
+                raise ValueError(lib.vapor_bam_last_error().decode())
         tl = {"native": h, "buf": {"seq": np.empty(1 << 20, dtype=np.uint8), "names": ctypes.create_string_buffer(1 << 16),
                                    "meta": np.empty(4 * 256, dtype=np.int64), "need": np.zeros(3, dtype=np.int64)}}
         with self._lock:
@@ -411,6 +448,7 @@ class BamFile:
         if tid is None:
             return []
         beg, stop = max(start - 1, 0), end               # 0-based half-open
+        min_mapq, exclude = self.read_filter
         out = []
         for cs, ce in self.index.chunks(tid, beg, stop):
             cur = self.bgzf.read_from(cs)
@@ -419,10 +457,12 @@ class BamFile:
                 if len(hdr) < 4:
                     break
                 rec = cur.read(struct.unpack("<i", hdr)[0])
-                ref_id, pos, name, flag, cig, l_seq, sq, tags = self._parse(rec)
+                ref_id, pos, name, flag, cig, l_seq, sq, tags, mapq = self._parse(rec)
                 if ref_id != tid or pos >= stop:
                     if ref_id > tid or (ref_id == tid and pos >= stop):
                         break
+                    continue
+                if not record_passes(mapq, flag, min_mapq, exclude):     # the read filter: as if the record were not in the file
                     continue
                 rlen = int(((cig >> 4) * _REF_OP[cig & 15]).sum()) if len(cig) else 0     # M, D, N, =, X consume reference
                 if pos + max(rlen, 1) <= beg:
@@ -458,11 +498,29 @@ def _bgzf_block(data: bytes) -> bytes:
 _BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
 
 
+def check_filter(min_mapq, exclude_flags):
+    """(min_mapq, exclude_flags) as integers, ValueError outside 0..255 and 0..65535."""
+    q, f = int(min_mapq), int(exclude_flags)
+    if not 0 <= q <= 255:
+        raise ValueError("min_mapq must be between 0 and 255, not %d" % q)
+    if not 0 <= f <= 65535:
+        raise ValueError("exclude_flags must be between 0 and 65535, not %d" % f)
+    return q, f
+
+
+def record_passes(mapq: int, flag: int, min_mapq: int, exclude_flags: int) -> bool:
+    """The rule of DESIGN.md 4.17 (`samtools view -q min_mapq -F exclude_flags`): a record is filtered iff MAPQ < min_mapq or
+    (FLAG & exclude_flags) != 0.  The one statement of the rule in the Python readers (fetch_raw, seqio.MemorySamtools,
+    seqio._sam_fields)."""
+    return not (mapq < min_mapq or (flag & exclude_flags))
+
+
 def write_bam(path: str, refs: List[Tuple[str, int]], records: List[Tuple[str, int, int, str, str]],
               block_size: int = 16384, qual_seed=None) -> None:
-    """records: (qname, tid, pos0, cigar string, seq[, aux]), will be sorted by (tid, pos).  Writes path and
+    """records: (qname, tid, pos0, cigar string, seq[, aux[, mapq[, flag]]]), will be sorted by (tid, pos).  Writes path and
     path + '.bai'.  aux: the record's optional fields as raw bytes, or a tag dict (phase.encode_aux); they follow the CG array
-    of a long-CIGAR record.  Qualities are 0xFF ("absent") - or, with qual_seed, seeded values in runs of a few bases between 2 and 60,
+    of a long-CIGAR record.  mapq and flag: the record's MAPQ (0..255, default 60) and FLAG (0..65535, default 0); a record with
+    cigar "*" is written without operations and one with seq "" with l_seq 0, as an unmapped mate and a secondary record are.  Qualities are 0xFF ("absent") - or, with qual_seed, seeded values in runs of a few bases between 2 and 60,
     which is what makes the blocks of a sequencer's file literal-heavy for its DEFLATE decoder."""
     import re
     import numpy as np
@@ -480,6 +538,10 @@ def write_bam(path: str, refs: List[Tuple[str, int]], records: List[Tuple[str, i
     for rec in recs:
         qname, tid, pos, cigar, seq = rec[:5]
         more = rec[5] if len(rec) > 5 and rec[5] else b""
+        mapq = 60 if len(rec) <= 6 or rec[6] is None else int(rec[6])
+        flag = 0 if len(rec) <= 7 or rec[7] is None else int(rec[7])
+        if not (0 <= mapq <= 255 and 0 <= flag <= 65535):
+            raise ValueError("write_bam: MAPQ %d / FLAG %d out of range" % (mapq, flag))
         if isinstance(more, dict):
             from .phase import encode_aux
             more = encode_aux(more)
@@ -496,7 +558,7 @@ def write_bam(path: str, refs: List[Tuple[str, int]], records: List[Tuple[str, i
             # SAM spec 4.2.2: the operations go to CG:B,I, the CIGAR field holds <l_seq>S<reference length>N
             aux = b"CGBI" + struct.pack("<i", len(packed)) + struct.pack("<%dI" % len(packed), *packed)
             packed = [(len(seq) << 4) | 4, (rlen << 4) | 3]
-        body = struct.pack("<iiBBHHHiiii", tid, pos, len(qname) + 1, 60, reg2bin(pos, end), len(packed), 0, len(seq), -1, -1, 0)
+        body = struct.pack("<iiBBHHHiiii", tid, pos, len(qname) + 1, mapq, reg2bin(pos, end), len(packed), flag, len(seq), -1, -1, 0)
         if qrng is None:
             qual = b"\xff" * len(seq)
         else:

@@ -14,7 +14,10 @@ INS call beside the pooled list; appends VaPoR_PS, VaPoR_PGT, VaPoR_PGQ and QS /
 together with --refine), --both-ends (bed, vcf: every junction branch - long DEL / INV, TANDUP, breakends - is scored from both of
 its sides, with right-anchored reads; appends the VaPoR_BE_* columns; not together with --refine or --phased),
 --phase-vcf FILE [--phase-sample NAME] (bed, vcf: --phased for a BAM that is NOT haplotagged - every read's haplotype and phase
-set come from its bases at the phased heterozygous SNVs of FILE; the HP / PS tags of the BAM are not read).
+set come from its bases at the phased heterozygous SNVs of FILE; the HP / PS tags of the BAM are not read),
+--min-mapq Q and --exclude-flags F (every sub-command, with every other option): a record is filtered iff
+MAPQ < Q or (FLAG & F) != 0 - `samtools view -q Q -F F` - and a filtered record is treated as if it were not in the file, on
+every read route; the default, 0 and 0, filters nothing.
 
 --refine, --phased (with --phase-vcf) and --both-ends each append columns to every row and exclude one another: a run has one
 mode (vapor_amd.modes) or none, built once in _main and handed as one argument to bed_jobs / vcf_jobs (which
@@ -822,16 +825,37 @@ def build_parser() -> argparse.ArgumentParser:
                         'breakend of --bnd - from both of its sides: the reads that end behind the window (right-anchored) are scored '
                         'as well, [B:q[t breakends are taken; appends VaPoR_BE_N, VaPoR_BE_QS / _GS / _GT / _GQ / _Rec and VaPoR_BE_SQS '
                         '(vcf: to INFO); not together with --refine or --phased')
+    p.add_argument('--min-mapq', metavar='Q', type=_int_in('--min-mapq', 0, 255), default=0,
+                   help='every sub-command: skip records with MAPQ below Q (0..255, default 0), as `samtools view -q Q` does; a '
+                        'filtered record is treated as if it were not in the file')
+    p.add_argument('--exclude-flags', metavar='F', type=_int_in('--exclude-flags', 0, 65535), default=0,
+                   help='every sub-command: skip records with any bit of F set in FLAG (0..65535, decimal or 0x hex, default 0), as '
+                        '`samtools view -F F` does; for minimap2 / pbmm2 files --min-mapq 20 --exclude-flags 0x704 (unmapped, '
+                        'secondary, QC-fail, duplicate) is a sensible start, and 0x800 (supplementary) is the user\'s choice')
     return p
 
 
+def _int_in(name, lo, hi):
+    """argparse type: an integer in lo..hi as int(x, 0) reads it (decimal or 0x hex); anything else is a parser error."""
+    def parse(text):
+        try:
+            v = int(text, 0)
+        except (TypeError, ValueError):
+            raise argparse.ArgumentTypeError('%s takes an integer (decimal or 0x hex), not %r' % (name, text)) from None
+        if not lo <= v <= hi:
+            raise argparse.ArgumentTypeError('%s must be between %d and %d, not %r' % (name, lo, hi, text))
+        return v
+    return parse
+
+
 def main(argv: Optional[List[str]] = None) -> int:
-    held: list = []                      # (`--phase-vcf`: the backend that carries the run's sites, for as long as the run lasts)
+    held: list = []                      # (`--phase-vcf`, the read filter: the backend that carries the run's sites and its (Q, F), for as long as the run lasts)
     try:
         return _main(argv, held)
     finally:
         for backend in held:
             backend.phase_sites = None
+            backend.read_filter = (0, 0)
 
 
 def _write_table(path, heads, jobs, scores, mode) -> list:
@@ -896,6 +920,13 @@ def _main(argv, held) -> int:
         backend = seqio.get_backend()
         backend.phase_sites = sites
         held.append(backend)
+    if args.min_mapq or args.exclude_flags:
+        # (set once, on the backend every read route takes its records through)
+        from . import seqio
+        backend = seqio.get_backend()
+        backend.read_filter = (args.min_mapq, args.exclude_flags)
+        if backend not in held:
+            held.append(backend)
     mode = None                          # (at most one of the three: every pair was refused above)
     if refine is not None:
         mode = modes.refine(*refine, ci_of=vcf_ci_readin(args.sv_input) if cmd == 'vcf' else None)

@@ -30,6 +30,7 @@ struct vapor_bam {
     int fd = -1;
     std::string path;
     int n_threads = 4;
+    uint32_t min_mapq = 0, exclude_flags = 0;   // the read filter (vapor_bam_set_filter): (0, 0) filters nothing
     // the blocks of the chunk being walked: `comp` holds the file bytes from `comp_base` on, `data` their inflated bytes
     std::vector<uint8_t> comp, data;
     int64_t comp_base = 0;
@@ -79,6 +80,23 @@ extern "C" int vapor_bam_set_threads(vapor_bam* b, int32_t n)
     if (!b || n < 1 || n > 64) return bfail(VAPOR_E_ARG, "vapor_bam_set_threads: out of range");
     b->n_threads = n;
     return VAPOR_OK;
+}
+
+// The read filter of the handle: a record is filtered iff MAPQ < min_mapq or (FLAG & exclude_flags) != 0, and a
+// filtered record is as if it were not in the file - every reader of this handle skips it behind the record checks.
+extern "C" int vapor_bam_set_filter(vapor_bam* b, int32_t min_mapq, uint32_t exclude_flags)
+{
+    if (!b || min_mapq < 0 || min_mapq > 255 || exclude_flags > 65535u) return bfail(VAPOR_E_ARG, "vapor_bam_set_filter: out of range");
+    b->min_mapq = (uint32_t)min_mapq;
+    b->exclude_flags = exclude_flags;
+    return VAPOR_OK;
+}
+
+// the filter as the device reader carries it in a region's spare word (vapor_hip.hip; not part of the C ABI):
+// exclude_flags | min_mapq << 16
+extern "C" __attribute__((visibility("hidden"))) uint32_t vapor_bam_filter_word(vapor_bam* b)
+{
+    return b ? (b->exclude_flags | (b->min_mapq << 16)) : 0u;
 }
 
 // Parses the BGZF blocks from scan_pos on (vapor_bgzf.h) and appends the whole ones to the block lists (a truncated last block
@@ -434,6 +452,8 @@ static int bam_chop_impl(vapor_bam* b, int32_t tid, int64_t start, int64_t end, 
                 if (ref_id > tid || (ref_id == tid && pos >= stop)) break;
                 continue;
             }
+            // the read filter: a filtered record is as if it were not in the file
+            if ((uint32_t)r[9] < b->min_mapq || (((uint32_t)r[14] | ((uint32_t)r[15] << 8)) & b->exclude_flags)) continue;
             const uint8_t* name = r + 32;
             const uint8_t* cig = name + l_name;
             const uint8_t* sq = cig + 4 * n_cig;

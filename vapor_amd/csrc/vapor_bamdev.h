@@ -849,7 +849,8 @@ struct BamSpan {          // one index chunk of a region: its records start in a
 };
 struct BamRegion {        // `samtools view bam tid:start-end` + chop_pacbio_read_by_pos(start, end, flank)
     int64_t start, end, flank;
-    int32_t tid, span_first, span_n, pad;
+    int32_t tid, span_first, span_n;
+    int32_t pad;          // the read filter: exclude_flags | min_mapq << 16; 0 filters nothing
 };
 struct BamKept {          // a read the reference keeps: its packed bases at arena + sq_off, from base q0 on, miss_bp
     uint32_t sq_off;
@@ -1024,6 +1025,7 @@ __device__ __forceinline__ void bam_chop_body(const uint8_t* __restrict__ arena,
     const BamRegion R = regs[g];
     const long long start = R.start, end = R.end;
     const long long beg = start - 1 > 0 ? start - 1 : 0, stop = end;
+    const uint32_t flt_excl = (uint32_t)R.pad & 0xFFFFu, flt_mapq = ((uint32_t)R.pad >> 16) & 0xFFu;
     int nk = 0, st = REG_OK;
     for (int s = 0; s < R.span_n && st == REG_OK; ++s) {
         const BamSpan SP = spans[R.span_first + s];
@@ -1049,6 +1051,9 @@ __device__ __forceinline__ void bam_chop_body(const uint8_t* __restrict__ arena,
                 if (ref_id > R.tid || (ref_id == R.tid && (long long)pos >= stop)) break;
                 continue;
             }
+            // the read filter (vapor_bam_set_filter): MAPQ < min_mapq or FLAG & exclude_flags - as if the record
+            // were not in the file.  Both fields were loaded with the record's header: no new load.
+            if (((w3 >> 8) & 0xFFu) < flt_mapq || ((w4 >> 16) & flt_excl)) continue;
             // chop_pacbio_read_by_pos: only alignments that start at or before the window start (decided before the CIGAR is
             // read: the region rule below only skips)
             if (!RIGHT && !((long long)pos < start)) continue;

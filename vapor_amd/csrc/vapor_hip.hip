@@ -796,6 +796,7 @@ extern "C" int vapor_seqset_planes(vapor_seqset* s, int32_t seq, uint32_t* p2, u
 // ------------------------------------------------------------------------------------------
 extern "C" int vapor_bam_fileno(vapor_bam* b);
 extern "C" int vapor_bam_threads(vapor_bam* b);
+extern "C" uint32_t vapor_bam_filter_word(vapor_bam* b);      // the handle's read filter as BamRegion::pad carries it (vapor_bam.cpp)
 
 struct vapor_bam_batch {
     vapor_ctx* ctx = nullptr;
@@ -957,6 +958,7 @@ static int bam_chop_device_impl(vapor_ctx* ctx, vapor_bam* bam, int32_t n_region
     }
     const int fd = vapor_bam_fileno(bam);
     if (fd < 0) return fail(VAPOR_E_ARG, "vapor_bam_chop_device: the file is not open");
+    const uint32_t filter_word = vapor_bam_filter_word(bam);      // (the handle's read filter, DESIGN.md 4.17: every region of the call carries it)
     HIPCHK(hipSetDevice(ctx->device));
     *out = nullptr;
     const bool dbg_t = getenv("VAPOR_DEBUG_BAMDEV") != nullptr;
@@ -1046,7 +1048,7 @@ static int bam_chop_device_impl(vapor_ctx* ctx, vapor_bam* bam, int32_t n_region
         size_t arena = 0;
         for (int32_t g = 0; g < n_regions; ++g) {
             BamRegion& R = regs[(size_t)g];
-            R.start = start[g]; R.end = end[g]; R.flank = flank[g]; R.tid = tid[g]; R.pad = 0;
+            R.start = start[g]; R.end = end[g]; R.flank = flank[g]; R.tid = tid[g]; R.pad = (int32_t)filter_word;
             R.span_first = (int32_t)dspans.size();
             R.span_n = 0;
             if (status[g]) continue;

@@ -27,6 +27,11 @@ _backend = None
 class SamtoolsCLI:
     """Runs the samtools binary; raises if it is missing instead of yielding nothing."""
 
+    # `--min-mapq`, `--exclude-flags` (DESIGN.md 4.17): (min_mapq, exclude_flags) - a record is filtered iff MAPQ < min_mapq or
+    # FLAG & exclude_flags, and a filtered record is as if it were not in the file.  view_lines lists what `samtools view` lists;
+    # the lines are filtered on columns 2 and 5 where they are read (_sam_fields)
+    read_filter = (0, 0)
+
     def __init__(self, exe: str = "samtools") -> None:
         self.exe = shutil.which(exe)
         if self.exe is None:
@@ -335,6 +340,7 @@ class InProcessBam(SamtoolsHybrid):
     threads_ok = True                  # pipeline.run_batch may start loci on several threads (native chop, positioned reads)
     chunk_threads_ok = True            # cli.score_jobs may score several chunks at once, a thread each
     phase_sites = None                 # `--phase-vcf`: the phase.Sites a tagged chop of this backend makes its (hap, ps) from
+    # (read_filter, inherited: `--min-mapq`, `--exclude-flags` - every open file carries it, bamio.BamFile.set_filter)
 
     def __init__(self) -> None:        # noqa: D401 - does not require the samtools binary
         self.exe = None
@@ -350,6 +356,8 @@ class InProcessBam(SamtoolsHybrid):
                 b = self._bam.get(bam)
                 if b is None:
                     b = self._bam[bam] = bamio.BamFile(bam)
+        if b.read_filter != self.read_filter:          # (the run's read filter, DESIGN.md 4.17: the file and its native handles carry it)
+            b.set_filter(*self.read_filter)
         return b
 
     def view_lines(self, bam: str, region: str) -> Iterable[str]:
@@ -370,15 +378,18 @@ class InProcessBam(SamtoolsHybrid):
         (`--both-ends`): the right-anchored reads (vapor_bam_chop_right, or _chop_records over the records as text)."""
         if tagged and sites is None:
             sites = self.phase_sites
+        b = self._open(bam)
+        # (a library without vapor_bam_set_filter does not filter: a run with a filter goes through the Python statement then)
+        native = not _env_is(b"VAPOR_BAM_NATIVE", b"0") and b.native_filter_ok()
         if right:
-            if not _env_is(b"VAPOR_BAM_NATIVE", b"0"):
+            if native:
                 from . import _lib
                 if hasattr(_lib.load(), "vapor_bam_chop_right"):
-                    return self._open(bam).chop_native(chrom, int(start), int(end), int(flank_length), right=True)
+                    return b.chop_native(chrom, int(start), int(end), int(flank_length), right=True)
             return _chop_records(self.records(bam, chrom, start, end), int(start), int(end), flank_length, right=True)
         st = {"sites": sites} if tagged and sites is not None else {}
-        if not _env_is(b"VAPOR_BAM_NATIVE", b"0"):
-            return self._open(bam).chop_native(chrom, int(start), int(end), int(flank_length), tagged=tagged, **st)
+        if native:
+            return b.chop_native(chrom, int(start), int(end), int(flank_length), tagged=tagged, **st)
         return self.chop_python(bam, chrom, start, end, flank_length, tagged=tagged, **st)
 
     def chop_many(self, bam: str, chroms, starts, ends, flanks, max_keep: int = 20, groups: bool = False, sites=None):
@@ -397,6 +408,8 @@ class InProcessBam(SamtoolsHybrid):
         st_kw = {"sites": sites} if groups and sites is not None else {}
         n = len(chroms)
         b = self._open(bam)
+        if not b.native_filter_ok():
+            raise NotImplementedError("the loaded library has no read filter")
         st, en, fl = [int(x) for x in starts], [int(x) for x in ends], [int(x) for x in flanks]
 
         def one(g):
@@ -471,6 +484,8 @@ class InProcessBam(SamtoolsHybrid):
         if right and (phased or not hasattr(lib, "vapor_bam_chop_device_right")):
             raise NotImplementedError("no right-anchored device reader")
         b = self._open(bam)
+        if not b.native_filter_ok():
+            raise NotImplementedError("the loaded library has no read filter")
         n = len(chroms)
         if phased and sites is None:
             sites = self.phase_sites
@@ -608,11 +623,40 @@ class MemorySamtools:
     # (not with VAPOR_MEMORY_CHOP=records: that path's CIGAR walk answers into one module-level array, see cli._chunk_threads_ok)
     chunk_threads_ok = True
     phase_sites = None                 # `--phase-vcf`: the phase.Sites a tagged chop of this backend makes its (hap, ps) from
+    # `--min-mapq`, `--exclude-flags`: every list of records below holds the records that pass (_recs)
+    read_filter = (0, 0)
 
     """Answers faidx/view from a `SynthWorld`; file names are ignored."""
 
     def __init__(self, world) -> None:
         self.world = world
+
+    def _recs(self, chrom: str):
+        """The contig's records that pass the read filter: the world's own list without a filter, else a list made once per
+        (record list, filter)."""
+        recs = self.world.reads.get(chrom, ())
+        q, f = self.read_filter
+        if not (q or f) or not recs:
+            return recs
+        cache = self.__dict__.setdefault("_filter_cache", {})
+        got = cache.get(id(recs))
+        if got is None or got[0] is not recs or got[1] != (q, f, len(recs)):
+            from .bamio import record_passes
+            got = (recs, (q, f, len(recs)), [r for r in recs if record_passes(r.mapq, r.flag, q, f)])
+            if getattr(self.world, "cache_ok", True):
+                if len(cache) > 200000:
+                    cache.clear()
+                cache[id(recs)] = got
+        return got[2]
+
+    def _overlapping(self, chrom: str, start: int, end: int):
+        """world.overlapping over the records that pass."""
+        q, f = self.read_filter
+        recs = self.world.overlapping(chrom, start, end)
+        if not (q or f):
+            return recs
+        from .bamio import record_passes
+        return [r for r in recs if record_passes(r.mapq, r.flag, q, f)]
 
     @staticmethod
     def _region(region: str):
@@ -634,10 +678,10 @@ class MemorySamtools:
 
     def view_lines(self, bam: str, region: str) -> Iterable[str]:
         chrom, a, b = self._region(region)
-        return [r.line() for r in self.world.overlapping(chrom, a, b)]
+        return [r.line() for r in self._overlapping(chrom, a, b)]
 
     def records(self, bam: str, chrom: str, start: int, end: int):
-        return [(r.qname, r.pos, r.cigar, r.seq) for r in self.world.overlapping(chrom, int(start), int(end))]
+        return [(r.qname, r.pos, r.cigar, r.seq) for r in self._overlapping(chrom, int(start), int(end))]
 
     def fetch_seq(self, ref: str, chrom: str, start: int, end: int) -> str:
         return self.world.fetch(chrom, start, end) if chrom in self.world.contigs else ""
@@ -649,7 +693,7 @@ class MemorySamtools:
     # it is tested against; VAPOR_MEMORY_CHOP=records selects it.
     def _arrays(self, chrom: str):
         cache = self.__dict__.setdefault("_chop_cache", {})
-        recs = self.world.reads.get(chrom, ())
+        recs = self._recs(chrom)
         key = id(recs)                       # (contigs that share one record list - tiled worlds - share its arrays)
         keep_it = getattr(self.world, "cache_ok", True)      # (a world that makes its record lists on demand: nothing is kept)
         got = cache.get(key) if keep_it else None
@@ -684,7 +728,7 @@ class MemorySamtools:
                 sites = self.phase_sites
             rows = sites.rows(chrom, int(start), int(end)) if sites is not None else None
         if _memory_chop_by_records():
-            recs = self.world.overlapping(chrom, int(start), int(end))
+            recs = self._overlapping(chrom, int(start), int(end))
             if tagged and sites is not None:
                 return _chop_records([(r.qname, r.pos, r.cigar, r.seq) for r in recs], start, end, flank_length,
                                      [haplotag(r.pos, r.cigar, r.seq, rows) for r in recs])
@@ -721,7 +765,7 @@ class MemorySamtools:
         from . import _lib
         fn = None if _memory_chop_by_records() else getattr(_lib.load_holding_gil(), "vapor_chop_records_right", None)
         if fn is None or end - start < flank_length:        # (a window shorter than its flank: Python's slice rules decide)
-            return _chop_records([(r.qname, r.pos, r.cigar, r.seq) for r in self.world.overlapping(chrom, start, end)],
+            return _chop_records([(r.qname, r.pos, r.cigar, r.seq) for r in self._overlapping(chrom, start, end)],
                                  start, end, flank_length, right=True)
         recs, arrs, ptr, _keep, _n = self._arrays(chrom)
         if not recs:
@@ -770,7 +814,7 @@ class MemorySamtools:
         ent = [per.get(c) or entry(c) for c in chroms]
         if keep_it:
             for g, e in enumerate(ent):                        # (a contig whose record list was replaced since)
-                if e[6] is not self.world.reads.get(chroms[g], ()) or e[0] != len(e[6]):
+                if e[6] is not self._recs(chroms[g]) or e[0] != len(e[6]):
                     ent[g] = entry(chroms[g])
         n_rec = np.fromiter((e[0] for e in ent), dtype=np.int32, count=n)
         ptr = np.asarray([(e[1], e[2], e[3], e[4]) for e in ent], dtype=np.uint64).reshape(n, 4).T.copy()
@@ -1025,6 +1069,20 @@ def cigar2alignstart_by_pos(cigar: str, align_start: int, start: int, end: int):
     return [int(_cigar_out[0]), int(_cigar_out[1])]
 
 
+def _sam_fields(be, bam, chrom, start, end):
+    """The fields of every alignment line of the backend's `view bam chrom:start-end` that passes the backend's read filter
+    (FLAG is column 2, MAPQ column 5) - the one place SAM text is filtered."""
+    from .bamio import record_passes
+    min_mapq, exclude = getattr(be, "read_filter", (0, 0))
+    for line in be.view_lines(bam, "%s:%d-%d" % (chrom, start, end)):
+        f = line.strip().split()
+        if not f or f[0] == "@":
+            continue
+        if (min_mapq or exclude) and not record_passes(int(f[4]), int(f[1]), min_mapq, exclude):
+            continue
+        yield f
+
+
 def chop_pacbio_read_by_pos(bam_in_new, chrom, start, end, flank_length, tagged=False, right=False, sites=None):
     """SF:339-354.  `tagged` (`--phased`, not in the reference): every kept record as [read, miss_bp, qname, hap, ps], its
     haplotype and phase set read from the HP and PS fields behind SEQ (vapor_amd.phase) - or, with sites (`--phase-vcf`: a
@@ -1047,11 +1105,7 @@ def chop_pacbio_read_by_pos(bam_in_new, chrom, start, end, flank_length, tagged=
         if hasattr(be, "records"):
             recs = be.records(bam_in_new, chrom, start, end)
         else:
-            recs = []
-            for line in be.view_lines(bam_in_new, "%s:%d-%d" % (chrom, start, end)):
-                f = line.strip().split()
-                if f and f[0] != "@":
-                    recs.append((f[0], f[3], f[5], f[9]))
+            recs = [(f[0], f[3], f[5], f[9]) for f in _sam_fields(be, bam_in_new, chrom, start, end)]
         return _chop_records(recs, start, end, flank_length, right=True)
     if tagged and sites is None:
         sites = getattr(be, "phase_sites", None)
@@ -1065,10 +1119,7 @@ def chop_pacbio_read_by_pos(bam_in_new, chrom, start, end, flank_length, tagged=
     else:
         from .phase import tags_from_sam
         recs, tags = [], ([] if tagged else None)
-        for line in be.view_lines(bam_in_new, "%s:%d-%d" % (chrom, start, end)):
-            f = line.strip().split()
-            if not f or f[0] == "@":
-                continue
+        for f in _sam_fields(be, bam_in_new, chrom, start, end):
             recs.append((f[0], f[3], f[5], f[9]))
             if tagged:
                 tags.append(tags_from_sam(f[11:]))

@@ -94,6 +94,8 @@ class SamRecord:
     seq: str
     ref_span: int     # reference bases the alignment is taken to cover (for region overlap)
     tags: Optional[dict] = None      # optional fields, e.g. {"HP": 1, "PS": 7} (vapor_amd.phase: encode_aux, sam_fields)
+    flag: int = 0                    # FLAG and MAPQ, what the read filter looks at
+    mapq: int = 60
 
     def tag_fields(self) -> List[str]:
         """The optional fields as SAM text (`HP:i:1`, ...)."""
@@ -103,8 +105,8 @@ class SamRecord:
         return sam_fields(self.tags)
 
     def line(self) -> str:
-        return "\t".join([self.qname, "0", self.rname, str(self.pos), "60", self.cigar,
-                          "*", "0", "0", self.seq, "*"] + self.tag_fields())
+        return "\t".join([self.qname, str(self.flag), self.rname, str(self.pos), str(self.mapq), self.cigar,
+                          "*", "0", "0", self.seq or "*", "*"] + self.tag_fields())
 
 
 @dataclasses.dataclass
@@ -765,6 +767,89 @@ def phase_world(world: SynthWorld, seed: int, untagged: float = 0.2, phase_set: 
     return world
 
 
+DECOY_MARKS = ("mapq0", "mapq_low", "unmapped", "secondary", "qcfail", "duplicate", "supplementary")
+
+
+def add_decoys(world: SynthWorld, seed: int, per_contig: int = 7, min_mapq: int = 20, marks: Sequence[str] = DECOY_MARKS,
+               errors: Tuple[float, float, float] = (0.01, 0.08, 0.04), stoppers: int = 0) -> SynthWorld:
+    """A copy of `world` with decoy records planted between its own (the read filter's worlds; `world` itself, its
+    records and make_world's draws are not touched - the copy shares contigs, loci and record objects).  Per contig that has
+    reads, `per_contig` decoys from default_rng(seed): decoy i takes record R = recs[i * len(recs) // per_contig] as its template -
+    it starts where R's bases start on the contig (POS minus a leading soft clip) and is as long as R's SEQ, so it lies before the
+    same windows with as many bases behind them - and its bases come from the OTHER allele: the contig itself (a reference read)
+    where R's name ends in 'a', the alternative haplotype (apply_sv of the contig's one DEL / TANDUP / INV / INS locus) where it
+    ends in 'r'; a template whose other allele cannot be made (a reference read on a contig of breakends) is passed over.  The
+    decoy follows R in the list, named d<i>_<R's name> with the last letter that of its own allele, and carries mark marks[i % len(marks)]:
+
+        mapq0          MAPQ 0                              qcfail         FLAG 0x200
+        mapq_low       MAPQ min_mapq - 1                   duplicate      FLAG 0x400
+        unmapped       FLAG 0x4, CIGAR '*' (no operation)  supplementary  FLAG 0x800
+        secondary      FLAG 0x100, SEQ '' (l_seq 0)
+
+    Every other field is MAPQ 60, FLAG 0.  Five of the marks sit on records today's rule keeps: they vote.  The unmapped mate and
+    the secondary record without SEQ lie where today's rule passes them over (a mate without CIGAR stops a region only when its
+    POS is the window start itself).  `--min-mapq min_mapq --exclude-flags 0xF04` filters every decoy and nothing else; 0x904 does
+    when `marks` leaves out qcfail and duplicate.  `stoppers`: on the first that many contigs of one DEL / INV / TANDUP locus the
+    unmapped decoy is placed ON the start of the locus's read window (SV start minus min(500, span), SF:794-802) instead: there
+    it reaches the CIGAR walk, and without the filter the whole run ends in the reference's IndexError (SF:331).  A tagged template (phase_world) hands the decoy HP of its own allele and R's PS."""
+    import re
+    rng = np.random.default_rng(seed)
+    out = SynthWorld()
+    out.contigs, out.loci = world.contigs, world.loci
+    for attr in ("cache_ok",):
+        if hasattr(world, attr):
+            setattr(out, attr, getattr(world, attr))
+    simple = {}
+    for l in world.loci:
+        if l.svtype in ("DEL", "TANDUP", "DUP", "INV", "INS"):
+            simple.setdefault(l.chrom, []).append(l)
+    for c, recs in world.reads.items():
+        ref = world.contigs[c]
+        alt = None
+        if len(simple.get(c, ())) == 1:
+            l = simple[c][0]
+            alt = apply_sv(ref, l.svtype, l.start, l.end, l.ins_seq)
+        new = list(recs)
+        planted = 0
+        stop_at = None
+        if stoppers > 0 and len(simple.get(c, ())) == 1 and simple[c][0].svtype in ("DEL", "TANDUP", "DUP", "INV") and recs:
+            l = simple[c][0]
+            stop_at = l.start - min(500, l.end - l.start)
+            stoppers -= 1
+        for i in range(per_contig if recs else 0):
+            at = i * len(recs) // per_contig
+            R = recs[at]
+            hap = ref if R.qname.endswith("a") else alt
+            if hap is None:
+                continue
+            m = re.match(r"(\d+)S", R.cigar)
+            a = max(R.pos - 1 - (int(m.group(1)) if m else 0), 0)
+            b = min(a + max(len(R.seq), 1), len(hap))
+            read, cigar = mutate(rng, hap[a:b], *errors)
+            mark = marks[i % len(marks)]
+            d = SamRecord("d%d_" % i + R.qname[:-1] + ("r" if hap is ref else "a"), c, a + 1, cigar, read, b - a)
+            if R.tags:
+                d.tags = {"HP": 2 if hap is ref else 1, "PS": R.tags.get("PS", 1)}
+            if mark == "mapq0":
+                d.mapq = 0
+            elif mark == "mapq_low":
+                d.mapq = max(int(min_mapq) - 1, 0)
+            elif mark == "unmapped":
+                d.flag, d.cigar, d.ref_span = 0x4, "*", 1
+                if stop_at is not None and stop_at >= 1:
+                    d.pos = stop_at
+            elif mark == "secondary":
+                d.flag, d.seq = 0x100, ""
+            elif mark in ("qcfail", "duplicate", "supplementary"):
+                d.flag = {"qcfail": 0x200, "duplicate": 0x400, "supplementary": 0x800}[mark]
+            else:
+                raise ValueError("add_decoys: unknown mark %r" % (mark,))
+            new.insert(at + 1 + planted, d)
+            planted += 1
+        out.reads[c] = new
+    return out
+
+
 def snv_world(world: SynthWorld, seed: int, spacing: int = 40) -> dict:
     """Plant phased heterozygous SNVs into an existing world in place (make_world's own draws are not touched; do it before a
     backend has seen the world - the reads' SEQ strings are replaced).  From default_rng(seed), the loci in world.loci order: the
@@ -847,7 +932,7 @@ def write_world_files(world: SynthWorld, directory: str, block_size: int = 8192,
     else:
         fa = os.path.join(directory, "ref.fa")
         _write_plain_fasta(world, fa, names)
-    recs = [(r.qname, names.index(c), r.pos - 1, r.cigar, r.seq, r.tags) for c, rs in world.reads.items() for r in rs]
+    recs = [(r.qname, names.index(c), r.pos - 1, r.cigar, r.seq, r.tags, r.mapq, r.flag) for c, rs in world.reads.items() for r in rs]
     bam = os.path.join(directory, "reads.bam")
     bamio.write_bam(bam, [(n, len(world.contigs[n])) for n in names], recs, block_size=block_size, qual_seed=qual_seed)
     return fa, bam
