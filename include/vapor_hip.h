@@ -362,6 +362,16 @@ int vapor_bam_set_threads(vapor_bam* bam, int32_t n_threads);
  * vapor_bam_chop, _tagged, _haplotag, _right and the four vapor_bam_chop_device* calls made with it apply it.  A new handle
  * has (0, 0), which filters nothing.  VAPOR_E_ARG outside 0 <= min_mapq <= 255, exclude_flags <= 65535. */
 int vapor_bam_set_filter(vapor_bam* bam, int32_t min_mapq, uint32_t exclude_flags);
+/* De-duplication of molecules by QNAME (`--dedup-qname`), a property of the open handle like the read filter.
+ * Two records are the same molecule iff their name keys are equal: b_0 .. b_{n-1} the QNAME bytes without the NUL,
+ * h = n + sum_i (b_i + 1) * M^(i+1) mod 2^64 with M = 0x9E3779B97F4A7C15, key = the splitmix64 finaliser of h (csrc/vapor_names.h).
+ * Rule W: among the records a reader keeps for one region (after the read filter), those with one key leave exactly one - the
+ * one with the smallest ((FLAG & 0x900) != 0, record order): the first that is neither secondary nor supplementary, else the
+ * first.  A dropped record is treated as if it were not in the file: it counts towards no list, limit, group or phase set.
+ * vapor_bam_chop, _tagged, _haplotag, _right apply the rule before they write their outputs (with buffers too small, `need` holds
+ * the sizes before it); the four vapor_bam_chop_device* calls run bam_dedup_kernel behind their chop kernel.  A region with more
+ * than 256 kept records before the rule still comes back for the host route.  on: 0 or 1, else VAPOR_E_ARG; a new handle has 0. */
+int vapor_bam_set_dedup(vapor_bam* bam, int32_t on);
 const char* vapor_bam_last_error(void);
 int vapor_bam_chop(vapor_bam* bam, int32_t tid, int64_t start, int64_t end, int64_t flank, int32_t n_chunks,
                    const uint64_t* chunks, uint8_t* seq_out, int64_t seq_cap, char* names_out, int64_t names_cap,
@@ -423,6 +433,10 @@ int vapor_bam_chop_device(vapor_ctx* ctx, vapor_bam* bam, int32_t n_regions, con
                           int32_t max_keep, int32_t* kept_first, uint64_t* sq_addr, int64_t* q0, int64_t* miss, int32_t* status,
                           vapor_bam_batch** batch);
 int vapor_bam_batch_destroy(vapor_bam_batch* batch);
+/* The name keys (vapor_bam_set_dedup) of the n entries that the vapor_bam_chop_device or vapor_bam_chop_device_right call which
+ * made `batch` returned, in their order: n must be that call's kept_first[n_regions].  VAPOR_E_ARG for a batch made with a handle
+ * that does not de-duplicate, for a batch of a _tagged / _haplotag call, and for another n. */
+int vapor_bam_batch_name_keys(vapor_bam_batch* batch, int64_t n, uint64_t* keys);
 /*
  * vapor_bam_chop_device for a haplotagged file (`--phased`; not in the reference, whose chop_pacbio_read_by_pos, SF:339-354,
  * reads nothing behind SEQ, and whose minimize_pacbio_read_list, SF:1091-1102, is applied here per group).  The chop kernel also

@@ -58,6 +58,7 @@ EXPORTS = [
     "vapor_chop_records_right", "vapor_chop_records_right_many", "vapor_bam_chop_right", "vapor_bam_chop_device_right",
     "vapor_bam_chop_haplotag", "vapor_bam_chop_device_haplotag",
     "vapor_bam_set_filter",
+    "vapor_bam_set_dedup", "vapor_bam_batch_name_keys",
 ]
 # entry points a library may lack (the CPU twin of the C ABI has no wide or any-k route and no refinement kernel): bound when
 # present, and the engine's wide, any-k and grid methods raise NotImplementedError when they are not
@@ -67,7 +68,9 @@ OPTIONAL_EXPORTS = ("vapor_wide_batch", "vapor_clean_hits_wide", "vapor_anyk_bat
                     "vapor_bam_chop_device_haplotag",
                     # (the read filter of a handle, `--min-mapq` / `--exclude-flags`: without it a run with a filter takes the
                     # Python statement of the readers, seqio.InProcessBam)
-                    "vapor_bam_set_filter")
+                    "vapor_bam_set_filter",
+                    # (`--dedup-qname`, DESIGN.md 4.18: without them a de-duplicating run takes the Python statement as well)
+                    "vapor_bam_set_dedup", "vapor_bam_batch_name_keys")
 MAX_CANDIDATES = 128           # breakpoint refinement: candidates per locus (VAPOR_MAX_CANDIDATES)
 
 _lib = None
@@ -243,6 +246,10 @@ def bind(L: ctypes.CDLL) -> ctypes.CDLL:
         L.vapor_bam_chop_device_right.argtypes = L.vapor_bam_chop_device.argtypes
     if hasattr(L, "vapor_bam_set_filter"):
         L.vapor_bam_set_filter.argtypes = [vp, ctypes.c_int32, ctypes.c_uint32]
+    if hasattr(L, "vapor_bam_set_dedup"):
+        L.vapor_bam_set_dedup.argtypes = [vp, ctypes.c_int32]
+    if hasattr(L, "vapor_bam_batch_name_keys"):
+        L.vapor_bam_batch_name_keys.argtypes = [vp, ctypes.c_int64, vp]
     if hasattr(L, "vapor_plan_run_grid"):
         L.vapor_plan_run_grid.argtypes = [vp, i32p, f64p, f64p, i64p]
     for name in EXPORTS:

@@ -225,6 +225,9 @@ class BamFile:
         # and a filtered record is as if it were not in the file.  fetch_raw applies it for the Python statement, every native
         # handle carries it (set_filter)
         self.read_filter = (0, 0)
+        # `--dedup-qname`: one kept record per QNAME and region.  The native handles carry it (set_dedup); the
+        # Python statement of the rule is seqio.dedup_kept, on the kept records
+        self.dedup_qname = False
         import os
         bai = path + ".bai" if os.path.exists(path + ".bai") else path[:-4] + ".bai"
         self.index = BaiIndex(bai)
@@ -293,6 +296,30 @@ class BamFile:
         from . import _lib
         return hasattr(_lib.load(), "vapor_bam_set_filter")
 
+    def set_dedup(self, on: bool) -> None:
+        """De-duplication by QNAME for this file (DESIGN.md 4.18 rule W): the native handles that exist and every one made later
+        (vapor_bam_set_dedup).  A library without that entry keeps its handles as they are: native_dedup_ok() says so, and the
+        callers take the Python statement then."""
+        on = bool(on)
+        with self._lock:
+            if on == self.dedup_qname:
+                return
+            if self._handles:
+                from . import _lib
+                lib = _lib.load()
+                if hasattr(lib, "vapor_bam_set_dedup"):
+                    for h in self._handles:
+                        if lib.vapor_bam_set_dedup(h, 1 if on else 0) != 0:
+                            raise ValueError(lib.vapor_bam_last_error().decode())
+            self.dedup_qname = on
+
+    def native_dedup_ok(self) -> bool:
+        """Whether the native readers of this file de-duplicate as it asks: it does not, or the library has vapor_bam_set_dedup."""
+        if not self.dedup_qname:
+            return True
+        from . import _lib
+        return hasattr(_lib.load(), "vapor_bam_set_dedup")
+
     def chop_native(self, chrom: str, start: int, end: int, flank_length: int, tagged: bool = False, right: bool = False, sites=None):
         """chop_pacbio_read_by_pos (SF:339-354) for one region through the library's native reader (vapor_bam_chop:
         threaded inflate, binary CIGAR walk, only kept bases decoded); the .bai lookup stays here.  Returns the same
@@ -356,6 +383,8 @@ class BamFile:
         if self.read_filter != (0, 0) and not hasattr(lib, "vapor_bam_set_filter"):
             # (no handle of such a library applies the filter: the callers take the Python statement, seqio.InProcessBam)
             raise NotImplementedError("the loaded library has no read filter (vapor_bam_set_filter)")
+        if self.dedup_qname and not hasattr(lib, "vapor_bam_set_dedup"):
+            raise NotImplementedError("the loaded library does not de-duplicate by QNAME (vapor_bam_set_dedup)")
         with self._lock:
             if self._free:
                 return self._free.pop()
@@ -368,6 +397,10 @@ class BamFile:
         if self.read_filter != (0, 0):
             # (every handle of the file gets the filter when it is made)
             if lib.vapor_bam_set_filter(h, self.read_filter[0], self.read_filter[1]) != 0:
+                lib.vapor_bam_close(h)
+                raise ValueError(lib.vapor_bam_last_error().decode())
+        if self.dedup_qname:
+            if lib.vapor_bam_set_dedup(h, 1) != 0:
                 lib.vapor_bam_close(h)
                 raise ValueError(lib.vapor_bam_last_error().decode())
         tl = {"native": h, "buf": {"seq": np.empty(1 << 20, dtype=np.uint8), "names": ctypes.create_string_buffer(1 << 16),

@@ -17,7 +17,10 @@ its sides, with right-anchored reads; appends the VaPoR_BE_* columns, DESIGN.md 
 set come from its bases at the phased heterozygous SNVs of FILE; the HP / PS tags of the BAM are not read),
 --min-mapq Q and --exclude-flags F (every sub-command, with every other option): a record is filtered iff
 MAPQ < Q or (FLAG & F) != 0 - `samtools view -q Q -F F` - and a filtered record is treated as if it were not in the file, on
-every read route; the default, 0 and 0, filters nothing.
+every read route; the default, 0 and 0, filters nothing.  --dedup-qname (every sub-command, with every other option; DESIGN.md
+§4.18): records with one QNAME are one molecule - among the kept records of one (file, region, anchor kind) one survives, the
+first that is neither secondary (0x100) nor supplementary (0x800), else the first, and the others are treated as if they were
+not in the file; with --both-ends the pooled VaPoR_BE_* columns count a molecule once across the views.  It adds no column.
 
 --refine, --phased (with --phase-vcf) and --both-ends each append columns to every row and exclude one another: a run has one
 mode (vapor_amd.modes) or none, built once in _main and handed as one argument to bed_jobs / vcf_jobs (which
@@ -832,6 +835,10 @@ def build_parser() -> argparse.ArgumentParser:
                    help='every sub-command: skip records with any bit of F set in FLAG (0..65535, decimal or 0x hex, default 0), as '
                         '`samtools view -F F` does; for minimap2 / pbmm2 files --min-mapq 20 --exclude-flags 0x704 (unmapped, '
                         'secondary, QC-fail, duplicate) is a sensible start, and 0x800 (supplementary) is the user\'s choice')
+    p.add_argument('--dedup-qname', action='store_true',
+                   help='every sub-command: records with one QNAME are one molecule - of the kept records of a region one per QNAME '
+                        'survives (the first that is neither secondary nor supplementary, else the first); with --both-ends a '
+                        'molecule that is kept in several views counts once in the pooled VaPoR_BE_* columns')
     return p
 
 
@@ -856,6 +863,7 @@ def main(argv: Optional[List[str]] = None) -> int:
         for backend in held:
             backend.phase_sites = None
             backend.read_filter = (0, 0)
+            backend.dedup_qname = False
 
 
 def _write_table(path, heads, jobs, scores, mode) -> list:
@@ -925,6 +933,13 @@ def _main(argv, held) -> int:
         from . import seqio
         backend = seqio.get_backend()
         backend.read_filter = (args.min_mapq, args.exclude_flags)
+        if backend not in held:
+            held.append(backend)
+    if args.dedup_qname:
+        # (likewise - rule W where the records are kept, rule V where the views are pooled)
+        from . import seqio
+        backend = seqio.get_backend()
+        backend.dedup_qname = True
         if backend not in held:
             held.append(backend)
     mode = None                          # (at most one of the three: every pair was refused above)

@@ -10,6 +10,7 @@
 #include "vapor_hip.h"
 #include "vapor_bgzf.h"
 #include "vapor_inflate.h"
+#include "vapor_names.h"
 
 #include <fcntl.h>
 #include <unistd.h>
@@ -31,6 +32,7 @@ struct vapor_bam {
     std::string path;
     int n_threads = 4;
     uint32_t min_mapq = 0, exclude_flags = 0;   // the read filter (vapor_bam_set_filter): (0, 0) filters nothing
+    bool dedup = false;                         // one kept record per QNAME and region (vapor_bam_set_dedup; DESIGN.md 4.18 rule W)
     // the blocks of the chunk being walked: `comp` holds the file bytes from `comp_base` on, `data` their inflated bytes
     std::vector<uint8_t> comp, data;
     int64_t comp_base = 0;
@@ -91,6 +93,18 @@ extern "C" int vapor_bam_set_filter(vapor_bam* b, int32_t min_mapq, uint32_t exc
     b->exclude_flags = exclude_flags;
     return VAPOR_OK;
 }
+
+// De-duplication by QNAME (`--dedup-qname`, DESIGN.md 4.18 rule W): among the records a reader of this handle keeps for one
+// region, those with one name key (vapor_names.h) leave one survivor - the first that is neither secondary nor supplementary,
+// else the first - and the others are as if they were not in the file.
+extern "C" int vapor_bam_set_dedup(vapor_bam* b, int32_t on)
+{
+    if (!b || (on != 0 && on != 1)) return bfail(VAPOR_E_ARG, "vapor_bam_set_dedup: 0 or 1");
+    b->dedup = on == 1;
+    return VAPOR_OK;
+}
+// (for the device reader, vapor_hip.hip; not part of the C ABI)
+extern "C" __attribute__((visibility("hidden"))) int vapor_bam_dedup_on(vapor_bam* b) { return b && b->dedup ? 1 : 0; }
 
 // the filter as the device reader carries it in a region's spare word (vapor_hip.hip; not part of the C ABI):
 // exclude_flags | min_mapq << 16
@@ -394,6 +408,8 @@ static int bam_chop_impl(vapor_bam* b, int32_t tid, int64_t start, int64_t end, 
     int64_t seq_used = 0, names_used = 0;
     int32_t nr = 0;
     bool overflow = false;
+    std::vector<uint64_t> dd_key;         // `--dedup-qname`: key and (FLAG & 0x900) != 0 of every kept record, in record order
+    std::vector<uint8_t> dd_sec;
     for (int32_t c = 0; c < n_chunks; ++c) {
         const uint64_t cs = chunks[2 * c], ce = chunks[2 * c + 1];
         // the chunk's own compressed range in one read, its blocks inflated together
@@ -526,6 +542,10 @@ static int bam_chop_impl(vapor_bam* b, int32_t tid, int64_t start, int64_t end, 
             if (q0 < 0) return bfail(VAPOR_E_ARG, "vapor_bam_chop: negative read offset");
             if (want_len < 0 || !(tail > want_len)) continue;
             const int64_t nl = l_name > 0 ? l_name - 1 : 0;
+            if (b->dedup) {
+                dd_key.push_back(vapor_names::name_key(name, (int)nl));
+                dd_sec.push_back((uint8_t)(((((uint32_t)r[14] | ((uint32_t)r[15] << 8)) & vapor_names::SEC_FLAGS) != 0u) ? 1 : 0));
+            }
             if (nr >= max_reads || seq_used + want_len > seq_cap || names_used + nl + 1 > names_cap) {
                 overflow = true;
                 seq_used += want_len; names_used += nl + 1; ++nr;
@@ -562,6 +582,24 @@ static int bam_chop_impl(vapor_bam* b, int32_t tid, int64_t start, int64_t end, 
             else if (meta_w == 6) find_tags(sq + (l_seq + 1) / 2 + l_seq, rec_end, m + 4, m + 5);
             seq_used += want_len; names_used += nl + 1; ++nr;
         }
+    }
+    if (b->dedup && !overflow && nr > 1) {
+        // rule W on the records kept: the survivors move to the front of the three outputs, in record order.
+        // (With buffers too small the sizes below are those of all kept records - enough for the call that follows.)
+        int64_t s_used = 0, n_used = 0;
+        int32_t w = 0;
+        for (int32_t i = 0; i < nr; ++i) {
+            if (vapor_names::drops(dd_key.data(), dd_sec.data(), nr, i)) continue;
+            const int64_t* mi = meta + (size_t)meta_w * (size_t)i;
+            const int64_t len = mi[1], nlen = (int64_t)strlen(names_out + mi[3]) + 1;
+            memmove(seq_out + s_used, seq_out + mi[0], (size_t)len);
+            memmove(names_out + n_used, names_out + mi[3], (size_t)nlen);
+            int64_t* mw = meta + (size_t)meta_w * (size_t)w;
+            if (w != i) memmove(mw, mi, sizeof(int64_t) * (size_t)meta_w);
+            mw[0] = s_used; mw[3] = n_used;
+            s_used += len; n_used += nlen; ++w;
+        }
+        seq_used = s_used; names_used = n_used; nr = w;
     }
     *n_reads = nr;
     if (need) { need[0] = seq_used; need[1] = names_used; need[2] = nr; }
@@ -1027,6 +1065,12 @@ extern "C" __attribute__((weak)) int vapor_bam_chop_device_haplotag(vapor_ctx*, 
                                                                     const int32_t*, const void*, const int32_t*, const int64_t*)
 {
     return bfail(VAPOR_E_ARG, "vapor_bam_chop_device_haplotag: this build has no device reader");
+}
+
+// ... and the name keys of a device batch (vapor_bam_batch_name_keys, `--dedup-qname`): no device reader, no batch.
+extern "C" __attribute__((weak)) int vapor_bam_batch_name_keys(vapor_bam_batch*, int64_t, uint64_t*)
+{
+    return bfail(VAPOR_E_ARG, "vapor_bam_batch_name_keys: this build has no device reader");
 }
 
 // ... and so is the right-anchored one (vapor_bam_chop_device_right: bam_chop_right_kernel).

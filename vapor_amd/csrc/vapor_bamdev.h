@@ -23,6 +23,7 @@
 // "lane" doing the wavefront's loops in order) and checks it against zlib on this machine; the kernels proper are HIP.
 #pragma once
 #include <stdint.h>
+#include "vapor_names.h"
 
 #ifndef VBD_EMU
 #include <hip/hip_runtime.h>
@@ -1212,6 +1213,117 @@ __global__ __launch_bounds__(64) void bam_chop_ops_kernel(const uint8_t* __restr
                                                          BamOps* __restrict__ opsv)
 {
     bam_chop_body<false, false, true>(arena, regs, spans, blk_status, n_regs, kept, n_kept, reg_status, nullptr, opsv);
+}
+
+// One record of a molecule per region (`--dedup-qname`, DESIGN.md 4.18 rule W; vapor_names.h holds the arithmetic, vapor_bam.cpp
+// bam_chop_impl the host's statement): one wavefront a region, right behind the chop kernel on its stream and before
+// bam_haplotag_kernel / bam_select_kernel, launched only for a handle with the option.  BamKept has no record offset, so the
+// region's spans are walked once more as bam_chop_body walks them - six header words on lanes 0 to 5, pos_u += 4 + block_size,
+// the same end of a span - and merged with the kept entries, which are in record order: the record whose packed bases start at
+// kept[next].sq_off IS entry next.  Its name is hashed by the wavefront (lane l bytes 4l .. 4l + 3, never one behind the name;
+// the powers of M from NAME_POW; a butterfly of shuffles), key and (FLAG & 0x900) != 0 go to LDS, the key to name_key[] as well.
+// The layout was validated by the walk before this one; the bounds are tested again all the same, and a walk that ends before
+// every kept entry was met sends the region to the host route (REG_MALFORMED).  Entry i is dropped iff an entry j has its key and
+// (sec_j, j) < (sec_i, i) - all against all over LDS, a broadcast read.  A region without two equal keys - nearly every one - ends
+// there.  Else kept[], tags[] (tagged call), opsv[] (ops flavour) and name_key[] are compacted in place in record order, a tile
+// of 64 at a time: ballot of the survivors, prefix popcount, entries to registers, fence, store - the destination index is never
+// above the source index and the tiles ascend, so nothing unread is overwritten - and lane 0 rewrites n_kept.
+__device__ static const vapor_names::PowTable NAME_POW = vapor_names::PowTable();
+
+__global__ __launch_bounds__(64) void bam_dedup_kernel(const uint8_t* __restrict__ arena, const BamRegion* __restrict__ regs,
+                                                      const BamSpan* __restrict__ spans, int n_regs, BamKept* kept, int32_t* n_kept,
+                                                      int32_t* reg_status, BamTag* tags, BamOps* opsv, uint64_t* name_key)
+{
+    __shared__ uint64_t s_key[KEPT_CAP];
+    __shared__ uint8_t s_sec[KEPT_CAP];
+    const int g = (int)blockIdx.x;
+    if (g >= n_regs) return;
+    const uint32_t lane = threadIdx.x;
+    if (reg_status[g] != REG_OK) return;
+    int n = n_kept[g];
+    n = n < 0 ? 0 : (n > KEPT_CAP ? KEPT_CAP : n);
+    // (a single kept record is walked for as well: its key is part of the call's answer)
+    if (n < 1) return;
+    BamKept* K = kept + (size_t)g * KEPT_CAP;
+    uint64_t* NK = name_key + (size_t)g * KEPT_CAP;
+    const BamRegion R = regs[g];
+    const long long stop = R.end;
+    // ---- the walk
+    int next = 0;
+    bool bad = false;
+    uint32_t want = K[0].sq_off;
+    for (int s = 0; s < R.span_n && next < n && !bad; ++s) {
+        const BamSpan SP = spans[R.span_first + s];
+        uint32_t pos_u = SP.u_begin;
+        while (pos_u < SP.u_end && next < n) {
+            if ((unsigned long long)pos_u + 36ull > SP.u_limit) { bad = true; break; }
+            uint32_t w = 0;
+            if (lane < 6) w = rd32u(arena + pos_u + 4u * lane);
+            const int32_t bs = (int32_t)__shfl(w, 0), ref_id = (int32_t)__shfl(w, 1), pos = (int32_t)__shfl(w, 2);
+            const uint32_t w3 = __shfl(w, 3), w4 = __shfl(w, 4);
+            if (bs < 32 || bs > (1 << 29) || (unsigned long long)pos_u + 4ull + (unsigned long long)bs > SP.u_limit) { bad = true; break; }
+            const uint32_t r = pos_u + 4u;
+            pos_u += 4u + (uint32_t)bs;
+            const int l_name = (int)(w3 & 0xFFu), n_cig = (int)(w4 & 0xFFFFu);
+            if (32ll + l_name + 4ll * n_cig > (long long)bs) { bad = true; break; }
+            if (ref_id != R.tid || (long long)pos >= stop) {
+                if (ref_id > R.tid || (ref_id == R.tid && (long long)pos >= stop)) break;
+                continue;
+            }
+            if (r + 32u + (uint32_t)l_name + 4u * (uint32_t)n_cig != want) continue;
+            const int nl = l_name > 0 ? l_name - 1 : 0;
+            uint64_t sum = vapor_names::lane_terms(arena + r + 32u, nl, (int)lane, NAME_POW.p);
+#pragma unroll
+            for (int d = 32; d >= 1; d >>= 1) sum += (uint64_t)__shfl_xor((unsigned long long)sum, d);
+            const uint64_t key = vapor_names::key_of_sum(nl, sum);
+            if (lane == 0) {
+                s_key[next] = key;
+                s_sec[next] = (uint8_t)((((w4 >> 16) & vapor_names::SEC_FLAGS) != 0u) ? 1 : 0);
+                NK[next] = key;
+            }
+            ++next;
+            if (next < n) want = K[next].sq_off;
+        }
+    }
+    if (bad || next != n) {
+        if (lane == 0) reg_status[g] = REG_MALFORMED;
+        return;
+    }
+    __syncthreads();
+    if (n < 2) return;
+    // ---- mark
+    bool any = false;
+    for (int t0 = 0; t0 < n; t0 += 64) {
+        const int i = t0 + (int)lane;
+        if (__any(i < n && vapor_names::drops(s_key, s_sec, n, i))) any = true;
+    }
+    if (!any) return;
+    // ---- compact
+    BamTag* T = tags ? tags + (size_t)g * KEPT_CAP : nullptr;
+    BamOps* O = opsv ? opsv + (size_t)g * KEPT_CAP : nullptr;
+    int wr = 0;
+    for (int t0 = 0; t0 < n; t0 += 64) {
+        const int i = t0 + (int)lane;
+        const bool keep = i < n && !vapor_names::drops(s_key, s_sec, n, i);
+        const unsigned long long m = __ballot(keep);
+        const int dst = wr + __popcll(m & ((1ull << lane) - 1ull));
+        // (a lane without a survivor loads entry 0 and stores nothing)
+        const int src = keep ? i : 0;
+        const BamKept k = K[src];
+        const uint64_t ky = s_key[src];
+        const BamTag tg = T ? T[src] : BamTag{0, 0, 0};
+        const BamOps op = O ? O[src] : BamOps{0, 0, 0, 0};
+        VBD_SYNC();
+        if (keep && dst != i) {
+            K[dst] = k;
+            NK[dst] = ky;
+            if (T) T[dst] = tg;
+            if (O) O[dst] = op;
+        }
+        VBD_SYNC();
+        wr += __popcll(m);
+    }
+    if (lane == 0) n_kept[g] = wr;
 }
 
 // The haplotag of every kept record from the phased heterozygous SNVs of its region (`--phase-vcf`, DESIGN.md 4.15;

@@ -797,12 +797,16 @@ extern "C" int vapor_seqset_planes(vapor_seqset* s, int32_t seq, uint32_t* p2, u
 extern "C" int vapor_bam_fileno(vapor_bam* b);
 extern "C" int vapor_bam_threads(vapor_bam* b);
 extern "C" uint32_t vapor_bam_filter_word(vapor_bam* b);      // the handle's read filter as BamRegion::pad carries it (vapor_bam.cpp)
+extern "C" int vapor_bam_dedup_on(vapor_bam* b);              // whether the handle de-duplicates by QNAME (vapor_bam_set_dedup, vapor_bam.cpp)
 
 struct vapor_bam_batch {
     vapor_ctx* ctx = nullptr;
     int device = 0;
     uint8_t* d_arena = nullptr;
     size_t arena_bytes = 0;
+    // `--dedup-qname`: the name keys of the entries a plain or right-anchored call returned, in their order
+    bool has_keys = false;
+    std::vector<uint64_t> name_keys;
 };
 
 extern "C" int vapor_bam_batch_destroy(vapor_bam_batch* b)
@@ -959,6 +963,7 @@ static int bam_chop_device_impl(vapor_ctx* ctx, vapor_bam* bam, int32_t n_region
     const int fd = vapor_bam_fileno(bam);
     if (fd < 0) return fail(VAPOR_E_ARG, "vapor_bam_chop_device: the file is not open");
     const uint32_t filter_word = vapor_bam_filter_word(bam);      // (the handle's read filter, DESIGN.md 4.17: every region of the call carries it)
+    const bool dedup = vapor_bam_dedup_on(bam) != 0;              // (`--dedup-qname`, DESIGN.md 4.18: bam_dedup_kernel behind the chop kernel)
     HIPCHK(hipSetDevice(ctx->device));
     *out = nullptr;
     const bool dbg_t = getenv("VAPOR_DEBUG_BAMDEV") != nullptr;
@@ -1082,7 +1087,10 @@ static int bam_chop_device_impl(vapor_ctx* ctx, vapor_bam* bam, int32_t n_region
         // (phased: the regions' BamPhase and their unions - 3 * max_keep picks each - come back; the kept entries and their tags
         // stay on the device)
         const size_t o_phase = m.take(phased ? sizeof(BamPhase) * regs.size() : 0), o_picks = m.take(phased ? sizeof(BamPick) * 3 * (size_t)max_keep * regs.size() : 0);
-        const size_t o_kept = m.take(sizeof(BamKept) * KEPT_CAP * regs.size()), o_tags = m.take(phased ? sizeof(BamTag) * KEPT_CAP * regs.size() : 0);
+        // (de-duplicating: the kept entries' name keys lie behind them and come back with them; without the option the slot is empty
+        // and every offset is what it was)
+        const size_t o_kept = m.take(sizeof(BamKept) * KEPT_CAP * regs.size()), o_keys = m.take(dedup ? 8 * (size_t)KEPT_CAP * regs.size() : 0);
+        const size_t o_tags = m.take(phased ? sizeof(BamTag) * KEPT_CAP * regs.size() : 0);
         const size_t o_ops = m.take(haplo ? sizeof(BamOps) * KEPT_CAP * regs.size() : 0);
         const size_t back_end = phased ? o_kept : o_tags;            // what the host reads back ends here
         if (const int rc = stage.alloc(std::max(back_end, in_bytes), m.off)) return rc;
@@ -1134,6 +1142,15 @@ static int bam_chop_device_impl(vapor_ctx* ctx, vapor_bam* bam, int32_t n_region
             else if (phased) chop(bam_chop_tagged_kernel, reinterpret_cast<BamTag*>(d_meta + o_tags));
             else chop(right ? bam_chop_right_kernel : bam_chop_kernel);
             HIPCHK(hipGetLastError());
+            if (dedup) {
+                // one record of a molecule per region (rule W), before anything looks at the kept entries
+                hipLaunchKernelGGL(bam_dedup_kernel, dim3((unsigned)n_regions), dim3(64), 0, st, B->d_arena, reinterpret_cast<const BamRegion*>(d_meta + o_reg),
+                                   reinterpret_cast<const BamSpan*>(d_meta + o_span), (int)n_regions, reinterpret_cast<BamKept*>(d_meta + o_kept),
+                                   reinterpret_cast<int32_t*>(d_meta + o_nk), reinterpret_cast<int32_t*>(d_meta + o_rst),
+                                   phased && !haplo ? reinterpret_cast<BamTag*>(d_meta + o_tags) : (BamTag*)nullptr,
+                                   haplo ? reinterpret_cast<BamOps*>(d_meta + o_ops) : (BamOps*)nullptr, reinterpret_cast<uint64_t*>(d_meta + o_keys));
+                HIPCHK(hipGetLastError());
+            }
             if (haplo) {
                 // the tags of the kept records from the region's phased sites: a wavefront a (region, slot)
                 hipLaunchKernelGGL(bam_haplotag_kernel, dim3((unsigned)n_regions * (unsigned)(KEPT_CAP / HAPLOTAG_WAVES)), dim3(64 * HAPLOTAG_WAVES), 0, st,
@@ -1187,6 +1204,8 @@ static int bam_chop_device_impl(vapor_ctx* ctx, vapor_bam* bam, int32_t n_region
         const int32_t* nk = reinterpret_cast<const int32_t*>(h_meta + o_nk);
         const int32_t* rst = reinterpret_cast<const int32_t*>(h_meta + o_rst);
         const BamKept* kept = reinterpret_cast<const BamKept*>(h_meta + o_kept);       // (not read when phased)
+        const uint64_t* keys = reinterpret_cast<const uint64_t*>(h_meta + o_keys);     // (de-duplicating and not phased)
+        B->has_keys = dedup && !phased;
         int32_t w = 0;
         std::vector<int32_t> order;
         for (int32_t g = 0; phased && g < n_regions; ++g) {
@@ -1225,6 +1244,7 @@ static int bam_chop_device_impl(vapor_ctx* ctx, vapor_bam* bam, int32_t n_region
                 sq_addr[w] = (uint64_t)reinterpret_cast<uintptr_t>(B->d_arena + k[i].sq_off);
                 q0[w] = k[i].q0;
                 miss[w] = k[i].miss;
+                if (dedup) B->name_keys.push_back(keys[(size_t)g * KEPT_CAP + (size_t)i]);
                 ++w;
             }
         }
@@ -1242,6 +1262,17 @@ extern "C" int vapor_bam_chop_device(vapor_ctx* ctx, vapor_bam* bam, int32_t n_r
 {
     return bam_chop_device_impl(ctx, bam, n_regions, tid, start, end, flank, chunk_first, chunks, max_keep, kept_first, sq_addr, q0, miss,
                                 status, out, nullptr, nullptr, nullptr);
+}
+
+// The name keys (`--dedup-qname`; vapor_names.h name_key) of the n entries the call that made the batch returned, in
+// their order: n = kept_first[n_regions].  VAPOR_E_ARG for a batch of a handle without the option, of a tagged / haplotag call
+// (their unions are made on the device, and no caller needs their keys) and for another n.
+extern "C" int vapor_bam_batch_name_keys(vapor_bam_batch* b, int64_t n, uint64_t* keys)
+{
+    if (!b || !b->has_keys || n != (int64_t)b->name_keys.size() || (n && !keys))
+        return fail(VAPOR_E_ARG, "vapor_bam_batch_name_keys: no keys in this batch, or another count");
+    if (n) memcpy(keys, b->name_keys.data(), sizeof(uint64_t) * (size_t)n);
+    return VAPOR_OK;
 }
 
 // vapor_bam_chop_device for the right-anchored reads of every region (`--both-ends`, DESIGN.md 4.14: bam_chop_right_kernel).

@@ -380,8 +380,29 @@ def _junction_view(num_reads_cff, bam_in, ref, form, info, flank, mirror):
         return None
     res = yield Score("s2", ref_seq, alt_seq, reads, k)
     scores: List[float] = []
+    if _dedup_on():
+        # (`--dedup-qname` rule V: the key of every read that contributes a score, built where _collect drops the others)
+        res = list(res)
+        scores = KeyedScores()
+        scores.keys = [_read_key(x) for x, s in zip(reads, res) if s is not None]
     _collect(res, reads, scores)
     return scores
+
+
+class KeyedScores(list):
+    """A view's per-read scores with `keys`: per score the name key of its read (`--dedup-qname`, DESIGN.md 4.18 rule V)."""
+    keys = None
+
+
+def _dedup_on() -> bool:
+    return bool(getattr(seqio.get_backend(), "dedup_qname", False))
+
+
+def _read_key(x) -> int:
+    """The name key of a read entry [read, miss_bp, slot]: seqio.name_key of a QNAME, the slot itself where the device route put
+    the key there (seqio.prefetch_views)."""
+    s = x[2]
+    return int(s) if not isinstance(s, str) else seqio.name_key(s)
 
 
 def both_ends_views(svtype, info, flank=default_flank_length):
@@ -434,8 +455,11 @@ def both_ends_windows(svtype, info):
 class BothEnds(list):
     """The score list of a locus under `--both-ends` - the primary view's, as without the option - with `views`: per scored or
     gated view of its junction branch, in table order and the primary first, its per-read scores or None (gated out, or k
-    "Error"); None for a locus without junction branch."""
+    "Error"); None for a locus without junction branch.  `view_keys` (`--dedup-qname`, DESIGN.md 4.18 rule V; else None): per
+    view the name keys of the reads behind its scores, None for a view without scores - the same list `views.keys` holds, which is
+    how it travels with the views (bothends.pack)."""
     views = None
+    view_keys = None
 
 
 def vapor_both_ends(svtype, num_reads_cff, plt_li, bam_in, ref, info, out_figure_name):
@@ -453,6 +477,7 @@ def vapor_both_ends(svtype, num_reads_cff, plt_li, bam_in, ref, info, out_figure
         out.views = [got]
         for _name, form, vinfo, mirror in views[1:]:
             out.views.append((yield from _junction_view(num_reads_cff, bam_in, ref, form, vinfo, default_flank_length, mirror)))
+        _keyed_views(out)
         return out
     if svtype == "BND":
         gen = vapor_bnd(num_reads_cff, plt_li, bam_in, ref, info, out_figure_name)
@@ -461,13 +486,20 @@ def vapor_both_ends(svtype, num_reads_cff, plt_li, bam_in, ref, info, out_figure
         gen = {"DEL": vapor_simple_del, "INV": vapor_simple_inv, "TANDUP": vapor_simple_tandup}[svtype](
             num_reads_cff, plt_li, bam_in, ref, info, out_figure_name)
         flank = seqio.flank_length_calculate(info)
-    # the type's own driver, its Score requests noted on the way through
+    # the type's own driver, its Score requests noted on the way through - and with `--dedup-qname` the keys of the reads behind
+    # the scores of its junction branch, from the request and the answer that pass here (the driver itself stays as it is)
+    dedup = _dedup_on()
+    prim_keys: List[int] = []
     try:
         req = next(gen)
         while True:
             if isinstance(req, Score):
                 seen.append(req.kind)
-            req = gen.send((yield req))
+            ans = yield req
+            if dedup and isinstance(req, Score) and req.kind == "s2":
+                ans = list(ans)
+                prim_keys += [_read_key(x) for x, s in zip(req.reads, ans) if s is not None]
+            req = gen.send(ans)
     except StopIteration as fin:
         scores = fin.value
     out.extend(scores)
@@ -479,9 +511,25 @@ def vapor_both_ends(svtype, num_reads_cff, plt_li, bam_in, ref, info, out_figure
         junction = not [k for k in seen if k != "s2"]        # (the short branch did not score: the driver fell through, SF:1917, 1769)
     if junction:
         out.views = [list(scores) if "s2" in seen else None]
+        if dedup and out.views[0] is not None:
+            if len(prim_keys) != len(scores):
+                raise AssertionError("--dedup-qname: %d keys for %d scores of the primary view" % (len(prim_keys), len(scores)))
+            out.views[0] = KeyedScores(scores)
+            out.views[0].keys = prim_keys
         for _name, form, vinfo, mirror in both_ends_views(svtype, info, flank):
             out.views.append((yield from _junction_view(num_reads_cff, bam_in, ref, form, vinfo, flank, mirror)))
+        _keyed_views(out)
     return out
+
+
+def _keyed_views(out) -> None:
+    """With `--dedup-qname`: out.views becomes a bothends.Views that carries the views' keys, out.view_keys names the same list."""
+    if not _dedup_on():
+        return
+    from .bothends import Views
+    v = Views(out.views)
+    v.keys = [None if x is None else list(x.keys) for x in out.views]
+    out.views, out.view_keys = v, v.keys
 
 
 _REFINE_BASE = {"DEL": vapor_simple_del, "INV": vapor_simple_inv, "TANDUP": vapor_simple_tandup}

@@ -235,8 +235,18 @@ class SeqSet:
 class BamBatch:
     """The inflated blocks of one vapor_bam_chop_device call on the device (the reads' packed bases lie in them)."""
 
+    name_keys = None                # `--dedup-qname`: the name keys (seqio.name_key) of the call's entries, in their order (uint64)
+
     def __init__(self, handle):
         self._h = handle
+
+    def read_name_keys(self, n: int) -> np.ndarray:
+        """vapor_bam_batch_name_keys: the keys of the n entries the call that made this batch returned.  VaporHipError for a
+        batch made without the option or by a tagged call; NotImplementedError where the library has no such entry."""
+        fn = Engine._wide_entry("vapor_bam_batch_name_keys", "name keys of a device batch")
+        keys = np.zeros(max(int(n), 1), dtype=np.uint64)
+        L.check(fn(self._h, int(n), keys.ctypes.data_as(ctypes.c_void_p)))
+        return keys[:int(n)]
 
     def close(self) -> None:
         if self._h:
@@ -397,7 +407,7 @@ class Engine:
         return SeqSet(self, seqs, upper, derived)
 
     def bam_chop_device(self, native_bam, tids, starts, ends, flanks, chunk_first, chunks, max_keep: int = 20, tagged: bool = False,
-                        right: bool = False, sites=None):
+                        right: bool = False, sites=None, name_keys: bool = False):
         """vapor_bam_chop_device: the read selection of many regions of an open BAM file on the device.  Returns (kept_first,
         device addresses of the kept reads' packed bases, q0, miss_bp, status per region, BamBatch); the batch owns the data the
         addresses point into - close it after the sequence sets made from them.  tagged (`--phased`,
@@ -407,7 +417,9 @@ class Engine:
         vapor_bam_chop_device_right): the right-anchored reads of every region - q0 is then the base a read's reverse complement
         starts with (SeqSet.from_addresses: src_kind 2) and miss_bp counts from the window end.  sites (`--phase-vcf`, with tagged;
         vapor_bam_chop_device_haplotag): the regions' phased sites as phase.device_site_tables makes them - the tags are then made
-        on the device from them and the records' own HP / PS fields are not read."""
+        on the device from them and the records' own HP / PS fields are not read.  name_keys (`--dedup-qname`, a handle with
+        vapor_bam_set_dedup; not with tagged): the entries' name keys are put on the batch (batch.name_keys); the tuple keeps
+        its shape."""
         if tagged and right:
             raise ValueError("right-anchored reads are not read with tags")
         if sites is not None and not tagged:
@@ -462,7 +474,10 @@ class Engine:
                                                int(max_keep), kept_first.ctypes.data_as(vp), addr.ctypes.data_as(vp), q0.ctypes.data_as(vp),
                                                miss.ctypes.data_as(vp), status.ctypes.data_as(vp), ctypes.byref(h)))
         w = int(kept_first[n])
-        return kept_first, addr[:w], q0[:w], miss[:w], status[:n], BamBatch(h)
+        batch = BamBatch(h)
+        if name_keys:
+            batch.name_keys = batch.read_name_keys(w)
+        return kept_first, addr[:w], q0[:w], miss[:w], status[:n], batch
 
     def bam_last_stats(self) -> dict:
         """What this engine's last bam_chop_device did (vapor_bam_last_stats)."""

@@ -31,6 +31,9 @@ class SamtoolsCLI:
     # FLAG & exclude_flags, and a filtered record is as if it were not in the file.  view_lines lists what `samtools view` lists;
     # the lines are filtered on columns 2 and 5 where they are read (_sam_fields)
     read_filter = (0, 0)
+    # `--dedup-qname`: among the kept records of one (file, region, anchor kind) one per QNAME survives
+    # (dedup_kept); the SAM text readers take FLAG from column 2
+    dedup_qname = False
 
     def __init__(self, exe: str = "samtools") -> None:
         self.exe = shutil.which(exe)
@@ -358,6 +361,8 @@ class InProcessBam(SamtoolsHybrid):
                     b = self._bam[bam] = bamio.BamFile(bam)
         if b.read_filter != self.read_filter:          # (the run's read filter, DESIGN.md 4.17: the file and its native handles carry it)
             b.set_filter(*self.read_filter)
+        if b.dedup_qname != bool(self.dedup_qname):    # (`--dedup-qname`, DESIGN.md 4.18: likewise)
+            b.set_dedup(self.dedup_qname)
         return b
 
     def view_lines(self, bam: str, region: str) -> Iterable[str]:
@@ -365,9 +370,9 @@ class InProcessBam(SamtoolsHybrid):
         a, _, e = span.partition("-")
         return self._open(bam).fetch_lines(chrom, int(a), int(e))
 
-    def records(self, bam: str, chrom: str, start: int, end: int):
-        """(QNAME, POS, CIGAR, SEQ) per alignment overlapping chrom:start-end."""
-        return [r[:4] for r in self._open(bam).fetch_records(chrom, int(start), int(end))]
+    def records(self, bam: str, chrom: str, start: int, end: int, flags: bool = False):
+        """(QNAME, POS, CIGAR, SEQ) per alignment overlapping chrom:start-end; with flags also FLAG."""
+        return [r if flags else r[:4] for r in self._open(bam).fetch_records(chrom, int(start), int(end))]
 
     def chop(self, bam: str, chrom: str, start: int, end: int, flank_length: int, tagged: bool = False, right: bool = False, sites=None):
         """chop_pacbio_read_by_pos (SF:339-354) straight from the BAM file: the library's native reader
@@ -380,13 +385,15 @@ class InProcessBam(SamtoolsHybrid):
             sites = self.phase_sites
         b = self._open(bam)
         # (a library without vapor_bam_set_filter does not filter: a run with a filter goes through the Python statement then)
-        native = not _env_is(b"VAPOR_BAM_NATIVE", b"0") and b.native_filter_ok()
+        # (nor does one without vapor_bam_set_dedup de-duplicate)
+        native = not _env_is(b"VAPOR_BAM_NATIVE", b"0") and b.native_filter_ok() and b.native_dedup_ok()
         if right:
             if native:
                 from . import _lib
                 if hasattr(_lib.load(), "vapor_bam_chop_right"):
                     return b.chop_native(chrom, int(start), int(end), int(flank_length), right=True)
-            return _chop_records(self.records(bam, chrom, start, end), int(start), int(end), flank_length, right=True)
+            dd = bool(self.dedup_qname)
+            return _chop_records(self.records(bam, chrom, start, end, flags=dd), int(start), int(end), flank_length, right=True, dedup=dd)
         st = {"sites": sites} if tagged and sites is not None else {}
         if native:
             return b.chop_native(chrom, int(start), int(end), int(flank_length), tagged=tagged, **st)
@@ -410,6 +417,8 @@ class InProcessBam(SamtoolsHybrid):
         b = self._open(bam)
         if not b.native_filter_ok():
             raise NotImplementedError("the loaded library has no read filter")
+        if not b.native_dedup_ok():
+            raise NotImplementedError("the loaded library does not de-duplicate by QNAME")
         st, en, fl = [int(x) for x in starts], [int(x) for x in ends], [int(x) for x in flanks]
 
         def one(g):
@@ -486,6 +495,13 @@ class InProcessBam(SamtoolsHybrid):
         b = self._open(bam)
         if not b.native_filter_ok():
             raise NotImplementedError("the loaded library has no read filter")
+        if not b.native_dedup_ok():
+            raise NotImplementedError("the loaded library does not de-duplicate by QNAME")
+        if b.dedup_qname and not phased:
+            # (the entries' name keys come back on every batch, BamBatch.name_keys: rule V of `--both-ends` compares them)
+            if not hasattr(lib, "vapor_bam_batch_name_keys"):
+                raise NotImplementedError("the loaded library has no name keys")
+            more["name_keys"] = True
         n = len(chroms)
         if phased and sites is None:
             sites = self.phase_sites
@@ -585,8 +601,9 @@ class InProcessBam(SamtoolsHybrid):
         res = np.zeros(2, dtype=np.int64)
         res_p = res.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
         out = []
+        flags = []
         rows = {"sites": sites.rows(chrom, int(start), int(end))} if tagged and sites is not None else {}
-        for qname, pos, cig, sq, l_seq, _flag, tags in self._open(bam).fetch_raw(chrom, int(start), int(end), **rows):
+        for qname, pos, cig, sq, l_seq, flag, tags in self._open(bam).fetch_raw(chrom, int(start), int(end), **rows):
             if not pos < start + 1:
                 continue
             ops = np.ascontiguousarray(cig, dtype=np.uint32)
@@ -600,7 +617,8 @@ class InProcessBam(SamtoolsHybrid):
                 want = end - start - miss_bp
                 if len(tail) > want:
                     out.append([tail[:want], miss_bp, qname] + (list(tags) if tagged else []))
-        return out
+                    flags.append(flag)
+        return dedup_kept(out, flags) if self.dedup_qname else out
 
     def _fasta(self, ref: str):
         fa = self._fa.get(ref)
@@ -625,6 +643,8 @@ class MemorySamtools:
     phase_sites = None                 # `--phase-vcf`: the phase.Sites a tagged chop of this backend makes its (hap, ps) from
     # `--min-mapq`, `--exclude-flags`: every list of records below holds the records that pass (_recs)
     read_filter = (0, 0)
+    # `--dedup-qname`: every chop below applies rule W to the records it keeps (dedup_kept)
+    dedup_qname = False
 
     """Answers faidx/view from a `SynthWorld`; file names are ignored."""
 
@@ -680,7 +700,9 @@ class MemorySamtools:
         chrom, a, b = self._region(region)
         return [r.line() for r in self._overlapping(chrom, a, b)]
 
-    def records(self, bam: str, chrom: str, start: int, end: int):
+    def records(self, bam: str, chrom: str, start: int, end: int, flags: bool = False):
+        if flags:
+            return [(r.qname, r.pos, r.cigar, r.seq, r.flag) for r in self._overlapping(chrom, int(start), int(end))]
         return [(r.qname, r.pos, r.cigar, r.seq) for r in self._overlapping(chrom, int(start), int(end))]
 
     def fetch_seq(self, ref: str, chrom: str, start: int, end: int) -> str:
@@ -727,13 +749,14 @@ class MemorySamtools:
             if sites is None:
                 sites = self.phase_sites
             rows = sites.rows(chrom, int(start), int(end)) if sites is not None else None
+        dd = bool(self.dedup_qname)
         if _memory_chop_by_records():
             recs = self._overlapping(chrom, int(start), int(end))
             if tagged and sites is not None:
-                return _chop_records([(r.qname, r.pos, r.cigar, r.seq) for r in recs], start, end, flank_length,
-                                     [haplotag(r.pos, r.cigar, r.seq, rows) for r in recs])
-            return _chop_records([(r.qname, r.pos, r.cigar, r.seq) for r in recs], start, end, flank_length,
-                                 [tags_from_sam(r.tag_fields()) for r in recs] if tagged else None)
+                return _chop_records([(r.qname, r.pos, r.cigar, r.seq, r.flag) for r in recs], start, end, flank_length,
+                                     [haplotag(r.pos, r.cigar, r.seq, rows) for r in recs], dedup=dd)
+            return _chop_records([(r.qname, r.pos, r.cigar, r.seq, r.flag) for r in recs], start, end, flank_length,
+                                 [tags_from_sam(r.tag_fields()) for r in recs] if tagged else None, dedup=dd)
         recs, arrs, ptr, _keep, _n = self._arrays(chrom)
         if not recs:
             return []
@@ -759,14 +782,14 @@ class MemorySamtools:
             out.append([r.seq[q0:q0 + (end - start - miss)] if q0 >= 0 else r.seq[q0:][:end - start - miss], miss, r.qname])
             if tagged:
                 out[-1] += list(haplotag(r.pos, r.cigar, r.seq, rows) if sites is not None else tags_from_sam(r.tag_fields()))
-        return out
+        return dedup_kept(out, [recs[t].flag for t in kept.tolist()]) if dd else out
 
     def _chop_right(self, chrom: str, start: int, end: int, flank_length):
         from . import _lib
         fn = None if _memory_chop_by_records() else getattr(_lib.load_holding_gil(), "vapor_chop_records_right", None)
         if fn is None or end - start < flank_length:        # (a window shorter than its flank: Python's slice rules decide)
-            return _chop_records([(r.qname, r.pos, r.cigar, r.seq) for r in self._overlapping(chrom, start, end)],
-                                 start, end, flank_length, right=True)
+            return _chop_records([(r.qname, r.pos, r.cigar, r.seq, r.flag) for r in self._overlapping(chrom, start, end)],
+                                 start, end, flank_length, right=True, dedup=bool(self.dedup_qname))
         recs, arrs, ptr, _keep, _n = self._arrays(chrom)
         if not recs:
             return []
@@ -776,12 +799,13 @@ class MemorySamtools:
             raise IndexError("string index out of range")
         qm = qm_a.tolist()
         out = []
-        for t in keep_a.nonzero()[0].tolist():
+        kept = keep_a.nonzero()[0].tolist()
+        for t in kept:
             q1, miss = qm[2 * t], qm[2 * t + 1]
             r = recs[t]
             stop = len(r.seq) - q1                  # (the kept part ends here: q1 bases are dropped from the read's end)
             out.append([rc_read(r.seq[stop - (end - start - miss):stop]), miss, r.qname])
-        return out
+        return dedup_kept(out, [recs[t].flag for t in kept]) if self.dedup_qname else out
 
     def chop_many(self, bam: str, chroms, starts, ends, flanks, max_keep: int = 20, groups: bool = False, sites=None):
         """groups (`--phased`, not in the reference): the reads of a region are the union of the lists of its three groups (A: all
@@ -821,7 +845,8 @@ class MemorySamtools:
         sa_ptr = np.fromiter((e[5].ctypes.data if e[5] is not None else 0 for e in ent), dtype=np.uint64, count=n)
         bad = np.fromiter((e[5] is None and e[0] > 0 for e in ent), dtype=bool, count=n)
         keep_sel = max_keep
-        if groups:                                   # (every kept record comes back, in record order: the selection is below)
+        dd = bool(self.dedup_qname)
+        if groups or dd:                             # (every kept record comes back, in record order: the selection is below)
             max_keep = max(int(n_rec.max()) if n else 1, 1)
         cap = max_keep * max(n, 1)
         kept_first = np.zeros(n + 1, dtype=np.int32)
@@ -842,6 +867,30 @@ class MemorySamtools:
         tot = int(kept_first[n])
         addr = addr[:tot]
         status[:n][bad] = -1
+        live = None
+        if dd:
+            # rule W on every region's kept records, before any list is made of them
+            live = np.ones(tot, dtype=bool)
+            for g in range(n):
+                a, b = int(kept_first[g]), int(kept_first[g + 1])
+                if b - a > 1 and status[g] == 0:
+                    recs = ent[g][6]
+                    ts = rec_idx[a:b].tolist()
+                    live[a:b] = dedup_mask([recs[t].qname for t in ts], [recs[t].flag for t in ts])
+        if dd and not groups:
+            # minimize_pacbio_read_list on the survivors: the first keep_sel in a stable order by miss_bp
+            kf2 = np.zeros(n + 1, dtype=np.int32)
+            take = []
+            for g in range(n):
+                a, b = int(kept_first[g]), int(kept_first[g + 1])
+                if status[g] == 0:
+                    sel = a + np.flatnonzero(live[a:b])
+                    if len(sel) > keep_sel:
+                        sel = sel[np.argsort(miss[sel], kind="stable")[:keep_sel]]
+                    take += sel.tolist()
+                kf2[g + 1] = len(take)
+            take = np.asarray(take, dtype=np.int64)
+            return kf2, addr[take], q0[take], miss[take], status[:n], ent
         if groups:
             from . import phase
             if sites is None:
@@ -853,15 +902,16 @@ class MemorySamtools:
                 a, b = int(kept_first[g]), int(kept_first[g + 1])
                 if b > a and status[g] == 0:
                     recs = ent[g][6]
+                    at = np.arange(a, b) if live is None else a + np.flatnonzero(live[a:b])    # (the survivors of rule W)
                     if sites is not None:
                         rows = sites.rows(chroms[g], int(st[g]), int(en[g]))
-                        tg = [phase.haplotag(recs[t].pos, recs[t].cigar, recs[t].seq, rows) for t in rec_idx[a:b].tolist()]
+                        tg = [phase.haplotag(recs[t].pos, recs[t].cigar, recs[t].seq, rows) for t in rec_idx[at].tolist()]
                     else:
-                        tg = [phase.tags_from_sam(recs[t].tag_fields()) for t in rec_idx[a:b].tolist()]
+                        tg = [phase.tags_from_sam(recs[t].tag_fields()) for t in rec_idx[at].tolist()]
                     hap = np.asarray([h for h, _p in tg], dtype=np.int64)
                     ps = np.asarray([phase.PS_NONE if p is None else p for _h, p in tg], dtype=np.int64)
-                    tagged[g], pset[g], order, words = phase.select_numbers(miss[a:b], hap, ps, keep_sel)
-                    take += [a + i for i in order]
+                    tagged[g], pset[g], order, words = phase.select_numbers(miss[at], hap, ps, keep_sel)
+                    take += [int(at[i]) for i in order]
                     member += words
                 kf2[g + 1] = len(take)
             take = np.asarray(take, dtype=np.int64)
@@ -996,10 +1046,18 @@ def prefetch_views(engine, bam: str, windows, max_keep: int = 20) -> PrefetchedB
             **({"right": True} if right else {}))
         out.batches += batches
         keep = tuple(batches)
+        # (`--dedup-qname`: the device route carries no names - the third slot holds the read's name key, an int, for rule V)
+        keys = None
+        if getattr(be, "dedup_qname", False):
+            import numpy as np
+            keys = np.concatenate([bt.name_keys for bt in batches]) if batches else np.zeros(0, dtype=np.uint64)
+            if len(keys) != int(kf[-1]):
+                raise RuntimeError("prefetch_views: %d name keys for %d reads" % (len(keys), int(kf[-1])))
         for g, w in enumerate(ws):
             if status[g] == 0:
                 out.prefetched[(w[0], int(w[1]), int(w[2]), int(w[3]), right)] = [
-                    [DevRead(addr[t], q[t], w[2] - w[1] - int(miss[t]), 2 if right else 1, keep), int(miss[t]), ""]
+                    [DevRead(addr[t], q[t], w[2] - w[1] - int(miss[t]), 2 if right else 1, keep), int(miss[t]),
+                     "" if keys is None else int(keys[t])]
                     for t in range(int(kf[g]), int(kf[g + 1]))]
     return out
 
@@ -1091,6 +1149,7 @@ def chop_pacbio_read_by_pos(bam_in_new, chrom, start, end, flank_length, tagged=
     reverse complement of its part that ends on the window end, miss_bp counted from there (_chop_records)."""
     out = []
     be = get_backend()
+    dedup = bool(getattr(be, "dedup_qname", False))      # (`--dedup-qname`, DESIGN.md 4.18: rule W on the kept records)
     pre = getattr(bam_in_new, "prefetched", None)
     if pre is not None and not tagged:
         # (`--both-ends` from files: the reads of this window were selected on the device with the chunk's other windows)
@@ -1102,11 +1161,11 @@ def chop_pacbio_read_by_pos(bam_in_new, chrom, start, end, flank_length, tagged=
             raise ValueError("right-anchored reads are not read with tags")
         if hasattr(be, "chop"):
             return be.chop(bam_in_new, chrom, start, end, flank_length, right=True)
-        if hasattr(be, "records"):
+        if hasattr(be, "records") and not dedup:
             recs = be.records(bam_in_new, chrom, start, end)
         else:
-            recs = [(f[0], f[3], f[5], f[9]) for f in _sam_fields(be, bam_in_new, chrom, start, end)]
-        return _chop_records(recs, start, end, flank_length, right=True)
+            recs = [(f[0], f[3], f[5], f[9], int(f[1])) for f in _sam_fields(be, bam_in_new, chrom, start, end)]
+        return _chop_records(recs, start, end, flank_length, right=True, dedup=dedup)
     if tagged and sites is None:
         sites = getattr(be, "phase_sites", None)
     if hasattr(be, "chop"):
@@ -1114,20 +1173,20 @@ def chop_pacbio_read_by_pos(bam_in_new, chrom, start, end, flank_length, tagged=
             return be.chop(bam_in_new, chrom, start, end, flank_length, tagged=True, sites=sites)
         return be.chop(bam_in_new, chrom, start, end, flank_length, tagged=True) if tagged else be.chop(bam_in_new, chrom, start, end, flank_length)
     tags = None
-    if hasattr(be, "records") and not tagged:
+    if hasattr(be, "records") and not tagged and not dedup:
         recs = be.records(bam_in_new, chrom, start, end)
     else:
         from .phase import tags_from_sam
         recs, tags = [], ([] if tagged else None)
         for f in _sam_fields(be, bam_in_new, chrom, start, end):
-            recs.append((f[0], f[3], f[5], f[9]))
+            recs.append((f[0], f[3], f[5], f[9], int(f[1])))
             if tagged:
                 tags.append(tags_from_sam(f[11:]))
         if tagged and sites is not None:
             from .phase import haplotag
             rows = sites.rows(chrom, int(start), int(end))
-            tags = [haplotag(int(pos), cigar, seq, rows) for _q, pos, cigar, seq in recs]
-    return _chop_records(recs, start, end, flank_length, tags)
+            tags = [haplotag(int(r[1]), r[2], r[3], rows) for r in recs]
+    return _chop_records(recs, start, end, flank_length, tags, dedup=dedup)
 
 
 def mirror_records(recs, length):
@@ -1142,15 +1201,59 @@ def mirror_records(recs, length):
     return out
 
 
-def _chop_records(recs, start, end, flank_length, tags=None, right=False):
+def name_key(qname) -> int:
+    """The identity of a molecule (`--dedup-qname`): two records are the same molecule iff name_key(QNAME) is
+    equal.  b_0 .. b_{n-1} the QNAME bytes: h = n + sum_i (b_i + 1) * M^(i+1) mod 2^64 with M = 0x9E3779B97F4A7C15, key = the
+    splitmix64 finaliser of h.  The Python statement of csrc/vapor_names.h name_key, which the native host reader and
+    bam_dedup_kernel compute."""
+    b = qname.encode("utf-8", "surrogateescape") if isinstance(qname, str) else bytes(qname)
+    mask = 0xFFFFFFFFFFFFFFFF
+    h, x = len(b), 0x9E3779B97F4A7C15
+    for c in b:
+        h = (h + (c + 1) * x) & mask
+        x = (x * 0x9E3779B97F4A7C15) & mask
+    h ^= h >> 30
+    h = (h * 0xBF58476D1CE4E5B9) & mask
+    h ^= h >> 27
+    h = (h * 0x94D049BB133111EB) & mask
+    return h ^ (h >> 31)
+
+
+def dedup_mask(qnames, flags):
+    """Rule W over the kept records of one (file, region, anchor kind), in record order: per name key exactly
+    one survives, the one with the smallest ((FLAG & 0x900) != 0, record order) - the first that is neither secondary nor
+    supplementary, else the first.  Returns one bool per record."""
+    best = {}
+    for i, (q, f) in enumerate(zip(qnames, flags)):
+        k = name_key(q)
+        rank = ((int(f) & 0x900) != 0, i)
+        if k not in best or rank < best[k]:
+            best[k] = rank
+    live = {i for _s, i in best.values()}
+    return [i in live for i in range(len(qnames))]
+
+
+def dedup_kept(kept, flags):
+    """Rule W on a list of kept entries ([read, miss_bp, qname, ...], in record order) and their records' FLAGs: the one place the
+    Python readers de-duplicate (chop_python, _chop_records, MemorySamtools).  A dropped record is as if it were not in the
+    file."""
+    if len(kept) < 2:
+        return kept
+    return [e for e, ok in zip(kept, dedup_mask([e[2] for e in kept], flags)) if ok]
+
+
+def _chop_records(recs, start, end, flank_length, tags=None, right=False, dedup=False):
     """The body of chop_pacbio_read_by_pos (SF:345-353) over (qname, pos, cigar, seq) records; tags: (hap, ps) per record, which
-    the kept ones then carry.  right: the closed form of _chop_records(mirror_records(recs, L), L + 1 - end, L + 1 - start,
+    the kept ones then carry.  dedup (`--dedup-qname`): the records are (qname, pos, cigar, seq, FLAG) and rule W (dedup_kept) is
+    applied to the list that is returned.  right: the closed form of _chop_records(mirror_records(recs, L), L + 1 - end, L + 1 - start,
     flank_length) - an alignment qualifies when its last reference base is >= end, the walk goes from the far end of the CIGAR
     (_cigar2alignend_py), and of the read without its last q1 bases the last end - start - miss_bp are kept, reverse
     complemented, when more than that many are there."""
     out = []
+    flags = []
     if right:
-        for qname, pos, cigar, seq in recs:
+        for rec in recs:
+            qname, pos, cigar, seq = rec[:4]
             # (the M / = / D total first: only an alignment that qualifies is walked - one without operation "ends" at pos - 1
             # and raises where the mirror would)
             if int(pos) + sum(int(n) for n, op in _CIGAR_RE.findall(cigar) if op in "M=D") - 1 < end:
@@ -1161,8 +1264,11 @@ def _chop_records(recs, start, end, flank_length, tags=None, right=False):
                 want = end - start - miss_bp
                 if len(head) > want:
                     out.append([rc_read(head)[:want] if want < 0 else rc_read(head[len(head) - want:]), miss_bp, qname])
-        return out
-    for t, (qname, pos, cigar, seq) in enumerate(recs):
+                    if dedup:
+                        flags.append(rec[4])
+        return dedup_kept(out, flags) if dedup else out
+    for t, rec in enumerate(recs):
+        qname, pos, cigar, seq = rec[:4]
         if int(pos) < start + 1:
             q0, miss_bp = cigar2alignstart_by_pos(cigar, int(pos), start, end)
             if not miss_bp > flank_length / 2:
@@ -1170,7 +1276,9 @@ def _chop_records(recs, start, end, flank_length, tags=None, right=False):
                 want = end - start - miss_bp
                 if len(tail) > want:
                     out.append([tail[:want], miss_bp, qname] + (list(tags[t]) if tags is not None else []))
-    return out
+                    if dedup:
+                        flags.append(rec[4])
+    return dedup_kept(out, flags) if dedup else out
 
 
 def minimize_pacbio_read_list(x, ideal_list_length=20):

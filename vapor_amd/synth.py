@@ -850,6 +850,63 @@ def add_decoys(world: SynthWorld, seed: int, per_contig: int = 7, min_mapq: int 
     return out
 
 
+def add_split_alignments(world: SynthWorld, variant: str = "full", window_dups: int = 2) -> SynthWorld:
+    """A copy of `world` in which a molecule that crosses a junction is written the way an aligner reports it: several records
+    with one QNAME (the worlds of `--dedup-qname`; `world` itself and its records are not touched - the copy
+    shares contigs, loci and the records it does not add).  For the loci whose two pieces lie on forward strands - DEL and
+    TANDUP of make_junction_world, 3to5 breakends without inserted bases of make_bnd_world - every alt-allele read that is
+    aligned up to the junction and soft-clipped after it (xM yS, the primary record, FLAG 0) gets a supplementary record (FLAG
+    0x800, MAPQ and tags of the primary) with the same QNAME at the far breakpoint, S then M: the clipped bases aligned from
+    there on as one M operation.  variant:
+
+        'full'  the supplementary carries the whole SEQ, xS yM (minimap2 -Y): the right-anchored view of the far breakpoint keeps
+                it, so the molecule is in two views of `--both-ends`
+        'hard'  it is hard-clipped, xH yM, SEQ the y bases alone: too short for any window of 2 * 500 bases, no view keeps it
+
+    window_dups: on every TANDUP contig the first that many primary records also get a twin inside the same window - FLAG 0x100
+    (secondary), the same QNAME, SEQ and CIGAR, five bases further right - which today's rule keeps beside the primary.
+    `planted` on the copy counts what was added: {'split': n, 'window': m}."""
+    import re
+    if variant not in ("full", "hard"):
+        raise ValueError("add_split_alignments: variant %r" % (variant,))
+    out = SynthWorld()
+    out.contigs, out.loci = world.contigs, world.loci
+    if hasattr(world, "cache_ok"):
+        out.cache_ok = world.cache_ok
+    out.reads = {c: list(rs) for c, rs in world.reads.items()}
+    out.planted = {"split": 0, "window": 0}
+    for l in world.loci:
+        if l.svtype == "DEL":
+            near, far_c, far_at = l.start, l.chrom, l.end + 1
+        elif l.svtype == "TANDUP":
+            near, far_c, far_at = l.end, l.chrom, l.start + 1
+        elif l.svtype == "BND" and (l.extra or {}).get("form") == "3to5" and not l.ins_seq:
+            near, far_c, far_at = l.start, l.extra["mate_chrom"], l.end
+        else:
+            continue
+        dups = window_dups if l.svtype == "TANDUP" else 0
+        for r in world.reads.get(l.chrom, ()):
+            m = re.fullmatch(r"(.*[MIDN=X])(\d+)S", r.cigar)
+            if m is None or r.flag != 0 or r.pos - 1 + r.ref_span != near:
+                continue
+            y = int(m.group(2))
+            x = len(r.seq) - y
+            if x < 1 or y < 1:
+                continue
+            sup = SamRecord(r.qname, far_c, far_at, ("%dS%dM" if variant == "full" else "%dH%dM") % (x, y),
+                            r.seq if variant == "full" else r.seq[x:], y, dict(r.tags) if r.tags else None, 0x800, r.mapq)
+            out.reads.setdefault(far_c, []).append(sup)
+            out.planted["split"] += 1
+            if dups > 0:
+                out.reads[l.chrom].append(SamRecord(r.qname, r.rname, r.pos + 5, r.cigar, r.seq, r.ref_span,
+                                                    dict(r.tags) if r.tags else None, 0x100, r.mapq))
+                out.planted["window"] += 1
+                dups -= 1
+    for rs in out.reads.values():
+        rs.sort(key=lambda r: r.pos)            # (stable: a planted record follows the records of its position)
+    return out
+
+
 def snv_world(world: SynthWorld, seed: int, spacing: int = 40) -> dict:
     """Plant phased heterozygous SNVs into an existing world in place (make_world's own draws are not touched; do it before a
     backend has seen the world - the reads' SEQ strings are replaced).  From default_rng(seed), the loci in world.loci order: the
