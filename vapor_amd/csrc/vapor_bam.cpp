@@ -11,6 +11,7 @@
 #include "vapor_bgzf.h"
 #include "vapor_inflate.h"
 #include "vapor_names.h"
+#include "vapor_readplan.h"
 
 #include <fcntl.h>
 #include <unistd.h>
@@ -821,10 +822,7 @@ static int chop_records_many_impl(chop_records_fn chop_one, int32_t n_regions, c
             order.clear();
             for (int32_t r = 0; r < n; ++r)
                 if (keep[(size_t)r]) order.push_back(r);
-            if ((int32_t)order.size() > max_keep) {
-                std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return qm[(size_t)2 * a + 1] < qm[(size_t)2 * b + 1]; });
-                order.resize((size_t)max_keep);
-            }
+            vapor_readplan::keep_smallest_miss(order, max_keep, [&](int32_t r) { return qm[(size_t)2 * r + 1]; });
             int32_t c = 0;
             for (int32_t r : order) {
                 const size_t o = (size_t)g * max_keep + (size_t)c++;

@@ -12,17 +12,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "vapor_readrec.h"      // FastaWin and the WIN_* codes
 
 namespace vapor_fasta {
 
-struct FastaWin {               // 32 B
-    uint64_t a_beg, a_end;      // the window's raw bytes (newlines included) in the arena
-    uint64_t t_off;             // its slot in the text buffer (a_end - a_beg bytes: the text is never longer)
-    uint32_t blk_first, blk_n;  // its blocks in the block table
-};
-
-// status of a window (include/vapor_hip.h: VAPOR_FASTA_*)
-constexpr int WIN_OK = 0, WIN_BLOCK = 1, WIN_RANGE = 2, WIN_NON_ASCII = 3, WIN_ROOM = 4;
 // traits of a window's text
 constexpr uint32_t TR_LOWER = 1, TR_NOT_ACGTN = 2, TR_NOT_ACGTN_ANY_CASE = 4, TR_HIGH = 8;
 

@@ -13,6 +13,7 @@
 #include "vapor_fasta.h"
 #include "vapor_refine.h"
 #include "vapor_planner.h"
+#include "vapor_readplan.h"
 #include "vapor_hip.h"
 
 #include <unistd.h>
@@ -853,14 +854,8 @@ static hipError_t crc_pow_on_device(vapor_ctx* ctx)
 
 static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-// A running offset into a metadata block: every table starts on a multiple of 64.
-struct Carve {
-    size_t off = 0;
-    size_t take(size_t bytes) { const size_t o = off; off += (bytes + 63) & ~(size_t)63; return o; }
-};
-
 // The inflate stage of the two device readers (vapor_bam_chop_device*, vapor_fasta_windows_device): the file's bytes read into a
-// pinned block, one metadata block whose first table is the BgzfBlk list, both sent on the call's stream, bgzf_inflate_kernel.
+// pinned block, one metadata block (vapor_readplan.h carves it) that holds the BgzfBlk list, both sent on the call's stream, bgzf_inflate_kernel.
 // Its blocks are Blocks of the call's CallScope, so they go back to the pool as every other block of the call does.
 struct InflateStage {
     CallScope& sc;
@@ -880,10 +875,6 @@ struct InflateStage {
         }
         return got;
     }
-    static vapor_bamdev::BgzfBlk blk(size_t stage_off, const vapor_bgzf::Block& b, uint64_t arena)     // (arena + b.u below 2^31: the callers' limits)
-    {
-        return {(uint32_t)(stage_off + b.payload()), b.c_len(), (uint32_t)(arena + b.u), b.isize, b.crc, 0};
-    }
     int alloc(size_t h_meta_bytes, size_t d_meta_bytes)
     {
         HIPCHK(h_meta.ensure(h_meta_bytes));
@@ -892,14 +883,13 @@ struct InflateStage {
         HIPCHK(crc_pow_on_device(sc.ctx));
         return VAPOR_OK;
     }
-    // On sc.st: the compressed bytes and the first in_bytes of the metadata go to the device, ev[0], the blocks (the table at the
-    // metadata's start) inflate to `arena`, their statuses to the metadata's o_bst.  The caller records ev[1] where its timing ends.
+    // On sc.st: the compressed bytes and the first in_bytes of the metadata (the tables the call's plan filled in, the n_blks blocks
+    // of d_blks among them) go to the device, ev[0], the blocks inflate to `arena`, their statuses to d_blk_status.  The caller
+    // records ev[1] where its timing ends.
     // (t_comp: the developer's timing - the stream is synchronised behind the first copy and the clock written there)
-    int run(const std::vector<vapor_bamdev::BgzfBlk>& blks, size_t in_bytes, size_t o_bst, uint8_t* arena, hipEvent_t* ev, double* t_comp = nullptr)
+    int run(size_t n_blks, size_t in_bytes, const vapor_bamdev::BgzfBlk* d_blks, int32_t* d_blk_status, uint8_t* arena, hipEvent_t* ev, double* t_comp = nullptr)
     {
         using namespace vapor_bamdev;
-        const size_t n_blks = blks.size();
-        if (n_blks) memcpy(h_meta, blks.data(), sizeof(BgzfBlk) * n_blks);
         if (!ev[0]) { HIPCHK(hipEventCreate(&ev[0])); HIPCHK(hipEventCreate(&ev[1])); }
         if (stage_bytes) HIPCHK(hipMemcpyAsync(d_comp, h_comp, stage_bytes, hipMemcpyHostToDevice, sc.st));
         if (t_comp) { HIPCHK(hipStreamSynchronize(sc.st)); *t_comp = now_ms(); }
@@ -907,7 +897,7 @@ struct InflateStage {
         HIPCHK(hipEventRecord(ev[0], sc.st));
         if (n_blks) {
             hipLaunchKernelGGL(bgzf_inflate_kernel, dim3((unsigned)((n_blks + INFLATE_WAVES - 1) / INFLATE_WAVES)), dim3(64 * INFLATE_WAVES), 0, sc.st, d_comp,
-                               reinterpret_cast<const BgzfBlk*>(d_meta.p), (int)n_blks, arena, sc.ctx->d_crc_pow, reinterpret_cast<int32_t*>(d_meta + o_bst));
+                               d_blks, (int)n_blks, arena, sc.ctx->d_crc_pow, d_blk_status);
             HIPCHK(hipGetLastError());
         }
         return VAPOR_OK;
@@ -927,85 +917,72 @@ static int guarded(const char* name, F body)
     }
 }
 
-// the phased sites of a vapor_bam_chop_device_haplotag call, as its caller gave them
-struct HaplotagIn {
-    const int32_t* site_first;
-    const vapor_bamdev::BamSite* sites;
-    const int32_t* ps_first;
-    const int64_t* ps_values;
-};
+// The stream the chop kernels run on: the context's own, or - a share of the CUs set aside for them - a CU-masked one, made again
+// when the share changes.
+static hipStream_t bam_stream_of(vapor_ctx* ctx)
+{
+    const char* sh = getenv("VAPOR_BAM_CU_SHARE");            // (experiments: overrides the parameter)
+    const int share = ctx->user_stream ? 0 : (sh ? atoi(sh) : ctx->bam_cu_share);
+    if (share != ctx->bam_stream_share) {
+        if (ctx->bam_stream) { (void)hipStreamSynchronize(ctx->bam_stream); (void)hipStreamDestroy(ctx->bam_stream); ctx->bam_stream = nullptr; }
+        ctx->bam_stream_share = share;
+        if (share >= 1 && share <= 7) {
+            // (CU i of the mask's enumeration is on in s of every 8: every XCD keeps CUs of both kinds)
+            std::vector<uint32_t> mask((size_t)(ctx->n_cus + 31) / 32, 0u);
+            for (int i = 0; i < ctx->n_cus; ++i)
+                if (i % 8 < share) mask[(size_t)i / 32] |= 1u << (i % 32);
+            if (hipExtStreamCreateWithCUMask(&ctx->bam_stream, (uint32_t)mask.size(), mask.data()) != hipSuccess) ctx->bam_stream = nullptr;
+        }
+    }
+    return ctx->bam_stream ? ctx->bam_stream : ctx->stream;
+}
 
-// vapor_bam_chop_device, and with `member` (vapor_bam_chop_device_tagged) the phased form of it: the tagged chop kernel, the
-// select kernel behind it on the same stream, and only the regions' compact unions and phase sets copied back.  With `hin`
-// (vapor_bam_chop_device_haplotag) the tags the select kernel reads come from bam_haplotag_kernel, which runs between the two.
-static int bam_chop_device_impl(vapor_ctx* ctx, vapor_bam* bam, int32_t n_regions, const int32_t* tid, const int64_t* start,
-                                const int64_t* end, const int64_t* flank, const int32_t* chunk_first, const uint64_t* chunks,
-                                int32_t max_keep, int32_t* kept_first, uint64_t* sq_addr, int64_t* q0, int64_t* miss,
-                                int32_t* status, vapor_bam_batch** out, uint32_t* member, int64_t* phase_set, int32_t* tagged,
-                                bool right = false, const HaplotagIn* hin = nullptr)
+#ifdef VBD_TIMING
+// (developer builds) the shader clocks bgzf_inflate_kernel left where the blocks' compressed bytes were
+static int dump_inflate_timing(const uint8_t* d_comp, size_t stage_bytes, const std::vector<vapor_bamdev::BgzfBlk>& blks)
+{
+    std::vector<uint8_t> back(stage_bytes);
+    HIPCHK(hipMemcpy(back.data(), d_comp, stage_bytes, hipMemcpyDeviceToHost));
+    double sum[13] = {0};
+    size_t cnt = 0;
+    for (const vapor_bamdev::BgzfBlk& k : blks) {
+        if (k.c_len < 128) continue;
+        const long long* d = reinterpret_cast<const long long*>(back.data() + ((k.c_off + 7u) & ~7u));
+        for (int t = 0; t < 13; ++t) sum[t] += (double)d[t];
+        ++cnt;
+    }
+    fprintf(stderr, "  per block (shader clocks, mean of %zu): top-up %.0f  decode %.0f (tables %.0f)  matches %.0f  crc %.0f  all %.0f\n"
+                    "  counts: fast literal steps %.0f, fast general symbols %.0f, careful symbols %.0f, matches %.0f (fills %.0f), batches %.0f; clocks in the fast loop's general symbols %.0f\n", cnt,
+            sum[0] / cnt, sum[1] / cnt, sum[2] / cnt, sum[3] / cnt, sum[4] / cnt, sum[5] / cnt, sum[6] / cnt, sum[10] / cnt, sum[7] / cnt, sum[8] / cnt,
+            sum[11] / cnt, sum[9] / cnt, sum[12] / cnt);
+    return VAPOR_OK;
+}
+#endif
+
+// The four vapor_bam_chop_device* entries (vapor_readplan.h ChopMode).  TAGGED: the tagged chop kernel, the select kernel behind it
+// on the same stream, and only the regions' compact unions and phase sets copied back.  HAPLOTAG: the tags the select kernel reads
+// come from bam_haplotag_kernel, which runs between the two.
+static int bam_chop_device_impl(vapor_ctx* ctx, vapor_bam* bam, vapor_readplan::ChopCall call, const vapor_readplan::ChopOut& o, vapor_bam_batch** out)
 {
     using namespace vapor_bamdev;
-    using vapor_bgzf::HostSpan;
-    const bool phased = member != nullptr, haplo = hin != nullptr;
-    if (!ctx || !bam || !out || n_regions < 0 || max_keep < 1 || max_keep > KEPT_CAP ||
-        (n_regions && (!tid || !start || !end || !flank || !chunk_first || !kept_first || !sq_addr || !q0 || !miss || !status)) ||
-        (phased && n_regions && (!phase_set || !tagged)) || (haplo && (!phased || right)) ||
-        (haplo && n_regions && (!hin->site_first || !hin->ps_first || hin->site_first[0] != 0 || hin->ps_first[0] != 0)))
-        return fail(VAPOR_E_ARG, "vapor_bam_chop_device: bad argument");
-    if (haplo && n_regions) {
-        // (the two tables are the caller's: their offsets must ascend and their arrays be there before a region is looked at)
-        for (int32_t g = 0; g < n_regions; ++g)
-            if (hin->site_first[g + 1] < hin->site_first[g] || hin->ps_first[g + 1] < hin->ps_first[g])
-                return fail(VAPOR_E_ARG, "vapor_bam_chop_device_haplotag: site_first / ps_first do not ascend");
-        if ((hin->site_first[n_regions] && !hin->sites) || (hin->ps_first[n_regions] && !hin->ps_values))
-            return fail(VAPOR_E_ARG, "vapor_bam_chop_device_haplotag: bad argument");
-    }
+    using namespace vapor_readplan;
+    if (!ctx || !bam || !out) return fail(VAPOR_E_ARG, "vapor_bam_chop_device: bad argument");
+    if (const Refusal r = check_args(call, o)) return fail(r.code, r.msg);
     const int fd = vapor_bam_fileno(bam);
     if (fd < 0) return fail(VAPOR_E_ARG, "vapor_bam_chop_device: the file is not open");
-    const uint32_t filter_word = vapor_bam_filter_word(bam);      // (the handle's read filter, DESIGN.md 4.17: every region of the call carries it)
-    const bool dedup = vapor_bam_dedup_on(bam) != 0;              // (`--dedup-qname`, DESIGN.md 4.18: bam_dedup_kernel behind the chop kernel)
+    call.filter_word = vapor_bam_filter_word(bam);
+    call.dedup = vapor_bam_dedup_on(bam) != 0;
+    const int32_t n_regions = call.n_regions;
+    const bool phased = call.phased(), haplo = call.haplo();
     HIPCHK(hipSetDevice(ctx->device));
     *out = nullptr;
     const bool dbg_t = getenv("VAPOR_DEBUG_BAMDEV") != nullptr;
     double tq[8] = {now_ms(), 0, 0, 0, 0, 0, 0, 0};
     return guarded("vapor_bam_chop_device", [&]() -> int {
         // ---- what to read ---------------------------------------------------------------------------------------------------
-        std::vector<HostSpan> spans;
-        std::vector<int32_t> span_first((size_t)n_regions + 1, 0);
-        size_t stage_bytes = 0;
-        for (int32_t g = 0; g < n_regions; ++g) {
-            span_first[(size_t)g] = (int32_t)spans.size();
-            status[g] = 0;
-            const int32_t c0 = chunk_first[g], c1 = chunk_first[g + 1];
-            // (positions are 32-bit in a BAM file; a region that is not is the host route's to refuse)
-            bool ok = c1 >= c0 && (c0 == c1 || chunks) && start[g] >= 0 && end[g] >= start[g] && end[g] < ((int64_t)1 << 31) && flank[g] >= 0 && tid[g] >= 0;
-            int why = REG_MALFORMED;
-            if (ok && haplo) {
-                // a wavefront tallies PHASE_SETS_CAP phase sets; the sites in position order, their indices inside the region's table
-                const int32_t n_ps = hin->ps_first[g + 1] - hin->ps_first[g];
-                if (n_ps > PHASE_SETS_CAP) { ok = false; why = REG_PHASE_SETS; }
-                for (int32_t i = hin->site_first[g]; ok && i < hin->site_first[g + 1]; ++i)
-                    ok = hin->sites[i].ps_idx < n_ps && hin->sites[i].pos >= 1 && (i == hin->site_first[g] || hin->sites[i - 1].pos < hin->sites[i].pos);
-            }
-            for (int32_t c = c0; ok && c < c1; ++c) {
-                const uint64_t cs = chunks[2 * (size_t)c], ce = chunks[2 * (size_t)c + 1];
-                if (ce < cs || (ce >> 16) - (cs >> 16) > ((uint64_t)1 << 27)) { ok = false; break; }
-                HostSpan sp;
-                sp.region = g; sp.cs = cs; sp.ce = ce;
-                sp.file_off = (int64_t)(cs >> 16);
-                sp.want = (size_t)((int64_t)(ce >> 16) - sp.file_off) + ((ce & 0xFFFFu) ? ((size_t)1 << 16) + 64 : 0);
-                sp.got = 0;
-                sp.stage_off = stage_bytes;
-                stage_bytes += (sp.want + 63) & ~(size_t)63;
-                spans.push_back(std::move(sp));
-            }
-            if (!ok) {
-                status[g] = why;
-                while (!spans.empty() && spans.back().region == g) { stage_bytes = spans.back().stage_off; spans.pop_back(); }
-            }
-        }
-        span_first[(size_t)n_regions] = (int32_t)spans.size();
-        if (stage_bytes > ((size_t)3 << 29)) return fail(VAPOR_E_ARG, "vapor_bam_chop_device: more than 1.5 GB of blocks in one call (use smaller batches)");
+        SpanPlan plan;
+        if (const Refusal r = plan_spans(call, o.status, plan)) return fail(r.code, r.msg);
+        std::vector<HostSpan>& spans = plan.spans;
         // (what the call holds while it runs goes back to the context's pool on every way out, an exception's included; the batch
         // survives a successful return only)
         CallScope sc(ctx, ctx->stream);
@@ -1013,9 +990,7 @@ static int bam_chop_device_impl(vapor_ctx* ctx, vapor_bam* bam, int32_t n_region
         B->ctx = ctx;
         B->device = ctx->device;
         InflateStage stage(sc);
-        HIPCHK(stage.begin(stage_bytes));
-        HostBlock<>& h_meta = stage.h_meta;
-        Block<>& d_meta = stage.d_meta;
+        HIPCHK(stage.begin(plan.stage_bytes));
         // ---- read and scan, a few threads -------------------------------------------------------------------------------------
         {
             const int n_thr = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(vapor_bam_threads(bam), 1) * 2, spans.size() / 8 + 1));
@@ -1045,214 +1020,85 @@ static int bam_chop_device_impl(vapor_ctx* ctx, vapor_bam* bam, int32_t n_region
         }
         tq[1] = now_ms();
         // ---- layout of the arena and the tables -------------------------------------------------------------------------------
-        for (const HostSpan& sp : spans)
-            if (sp.bad) status[sp.region] = REG_MALFORMED;
-        std::vector<BgzfBlk> blks;
-        std::vector<BamSpan> dspans;
-        std::vector<BamRegion> regs((size_t)std::max(n_regions, 1));
-        size_t arena = 0;
-        for (int32_t g = 0; g < n_regions; ++g) {
-            BamRegion& R = regs[(size_t)g];
-            R.start = start[g]; R.end = end[g]; R.flank = flank[g]; R.tid = tid[g]; R.pad = (int32_t)filter_word;
-            R.span_first = (int32_t)dspans.size();
-            R.span_n = 0;
-            if (status[g]) continue;
-            for (int32_t si = span_first[(size_t)g]; si < span_first[(size_t)g + 1]; ++si) {
-                const HostSpan& sp = spans[(size_t)si];
-                if (arena + sp.u_total + 64 > ((size_t)1 << 31)) return fail(VAPOR_E_ARG, "vapor_bam_chop_device: more than 2 GB of block data in one call (use smaller batches)");
-                BamSpan d;
-                d.u_begin = (uint32_t)arena + sp.u_begin;
-                d.u_end = (uint32_t)arena + sp.u_end;
-                d.u_limit = (uint32_t)arena + sp.u_total;
-                d.blk_first = (uint32_t)blks.size();
-                d.blk_n = (uint32_t)sp.blks.size();
-                d.pad = 0;
-                for (const vapor_bgzf::Block& k : sp.blks) blks.push_back(InflateStage::blk(sp.stage_off, k, arena));
-                dspans.push_back(d);
-                ++R.span_n;
-                arena += ((size_t)sp.u_total + 63) & ~(size_t)63;
-            }
-        }
-        const size_t n_blks = blks.size();
-        // metadata in one block: blocks, spans, regions in; block status, kept counts, region status, kept reads out
-        Carve m;
-        m.take(sizeof(BgzfBlk) * std::max<size_t>(n_blks, 1));
-        const size_t o_span = m.take(sizeof(BamSpan) * std::max<size_t>(dspans.size(), 1)), o_reg = m.take(sizeof(BamRegion) * regs.size());
-        // (haplotagging: every region's range of sites and of phase-set values, the sites, the values - sent with the tables above)
-        const size_t n_sites = haplo && n_regions ? (size_t)hin->site_first[n_regions] : 0, n_psv = haplo && n_regions ? (size_t)hin->ps_first[n_regions] : 0;
-        const size_t o_srange = m.take(haplo ? sizeof(BamSiteRange) * regs.size() : 0), o_sites = m.take(haplo ? sizeof(BamSite) * std::max<size_t>(n_sites, 1) : 0);
-        const size_t o_psv = m.take(haplo ? 8 * std::max<size_t>(n_psv, 1) : 0);
-        const size_t in_bytes = m.off;
-        const size_t o_bst = m.take(4 * std::max<size_t>(n_blks, 1)), o_nk = m.take(4 * regs.size()), o_rst = m.take(4 * regs.size());
-        // (phased: the regions' BamPhase and their unions - 3 * max_keep picks each - come back; the kept entries and their tags
-        // stay on the device)
-        const size_t o_phase = m.take(phased ? sizeof(BamPhase) * regs.size() : 0), o_picks = m.take(phased ? sizeof(BamPick) * 3 * (size_t)max_keep * regs.size() : 0);
-        // (de-duplicating: the kept entries' name keys lie behind them and come back with them; without the option the slot is empty
-        // and every offset is what it was)
-        const size_t o_kept = m.take(sizeof(BamKept) * KEPT_CAP * regs.size()), o_keys = m.take(dedup ? 8 * (size_t)KEPT_CAP * regs.size() : 0);
-        const size_t o_tags = m.take(phased ? sizeof(BamTag) * KEPT_CAP * regs.size() : 0);
-        const size_t o_ops = m.take(haplo ? sizeof(BamOps) * KEPT_CAP * regs.size() : 0);
-        const size_t back_end = phased ? o_kept : o_tags;            // what the host reads back ends here
-        if (const int rc = stage.alloc(std::max(back_end, in_bytes), m.off)) return rc;
-        HIPCHK(dmalloc(ctx, (void**)&B->d_arena, arena + 64));
-        B->arena_bytes = arena + 64;
+        ChopLayout L;
+        if (const Refusal r = layout(call, plan, o.status, L)) return fail(r.code, r.msg);
+        const ChopMeta& M = L.meta;
+        const size_t n_blks = L.blks.size();
+        if (const int rc = stage.alloc(M.host_bytes(), M.bytes)) return rc;
+        HIPCHK(dmalloc(ctx, (void**)&B->d_arena, L.arena + 64));
+        B->arena_bytes = L.arena + 64;
         ctx->arenas[B->d_arena] = B->arena_bytes;
-        if (!dspans.empty()) memcpy(h_meta + o_span, dspans.data(), sizeof(BamSpan) * dspans.size());
-        memcpy(h_meta + o_reg, regs.data(), sizeof(BamRegion) * regs.size());
-        if (haplo) {
-            BamSiteRange* sr = reinterpret_cast<BamSiteRange*>(h_meta + o_srange);
-            for (int32_t g = 0; g < n_regions; ++g) {
-                // (a region that is not sent keeps an empty range: its wavefronts end on its status)
-                const bool on = status[g] == 0;
-                sr[g] = {hin->site_first[g], on ? hin->site_first[g + 1] - hin->site_first[g] : 0, hin->ps_first[g], on ? hin->ps_first[g + 1] - hin->ps_first[g] : 0};
-            }
-            if (n_regions == 0) sr[0] = {0, 0, 0, 0};
-            if (n_sites) memcpy(h_meta + o_sites, hin->sites, sizeof(BamSite) * n_sites);
-            if (n_psv) memcpy(h_meta + o_psv, hin->ps_values, 8 * n_psv);
-        }
-        {
-            const char* sh = getenv("VAPOR_BAM_CU_SHARE");            // (experiments: overrides the parameter)
-            const int share = ctx->user_stream ? 0 : (sh ? atoi(sh) : ctx->bam_cu_share);
-            if (share != ctx->bam_stream_share) {
-                if (ctx->bam_stream) { (void)hipStreamSynchronize(ctx->bam_stream); (void)hipStreamDestroy(ctx->bam_stream); ctx->bam_stream = nullptr; }
-                ctx->bam_stream_share = share;
-                if (share >= 1 && share <= 7) {
-                    // (CU i of the mask's enumeration is on in s of every 8: every XCD keeps CUs of both kinds)
-                    std::vector<uint32_t> mask((size_t)(ctx->n_cus + 31) / 32, 0u);
-                    for (int i = 0; i < ctx->n_cus; ++i)
-                        if (i % 8 < share) mask[(size_t)i / 32] |= 1u << (i % 32);
-                    if (hipExtStreamCreateWithCUMask(&ctx->bam_stream, (uint32_t)mask.size(), mask.data()) != hipSuccess) ctx->bam_stream = nullptr;
-                }
-            }
-        }
-        hipStream_t st = ctx->bam_stream ? ctx->bam_stream : ctx->stream;
-        sc.st = st;
+        uint8_t *const h_meta = stage.h_meta, *const d_meta = stage.d_meta;
+        M.fill(h_meta, call, L, o.status);
+        const hipStream_t st = sc.st = bam_stream_of(ctx);
         tq[2] = now_ms();
-        if (const int rc = stage.run(blks, in_bytes, o_bst, B->d_arena, ctx->bam_ev, dbg_t ? &tq[3] : nullptr)) return rc;
+        if (const int rc = stage.run(n_blks, M.in_bytes, M.blks.in(d_meta), M.blk_status.in(d_meta), B->d_arena, ctx->bam_ev, dbg_t ? &tq[3] : nullptr)) return rc;
         HIPCHK(hipEventRecord(ctx->bam_ev[1], st));
         if (dbg_t) { HIPCHK(hipStreamSynchronize(st)); tq[4] = now_ms(); }
         if (n_regions) {
             // the chop kernel of the call: plain, right-anchored, or (phased) the tagged one with the select kernel behind it
             auto chop = [&](auto kernel, auto... tags) {
-                hipLaunchKernelGGL(kernel, dim3((unsigned)n_regions), dim3(64), 0, st, B->d_arena, reinterpret_cast<const BamRegion*>(d_meta + o_reg),
-                                   reinterpret_cast<const BamSpan*>(d_meta + o_span), reinterpret_cast<const int32_t*>(d_meta + o_bst), (int)n_regions,
-                                   reinterpret_cast<BamKept*>(d_meta + o_kept), reinterpret_cast<int32_t*>(d_meta + o_nk), reinterpret_cast<int32_t*>(d_meta + o_rst), tags...);
+                hipLaunchKernelGGL(kernel, dim3((unsigned)n_regions), dim3(64), 0, st, B->d_arena, M.regs.in(d_meta), M.spans.in(d_meta), M.blk_status.in(d_meta),
+                                   (int)n_regions, M.kept.in(d_meta), M.n_kept.in(d_meta), M.reg_status.in(d_meta), tags...);
             };
-            if (haplo) chop(bam_chop_ops_kernel, reinterpret_cast<BamOps*>(d_meta + o_ops));
-            else if (phased) chop(bam_chop_tagged_kernel, reinterpret_cast<BamTag*>(d_meta + o_tags));
-            else chop(right ? bam_chop_right_kernel : bam_chop_kernel);
+            if (haplo) chop(bam_chop_ops_kernel, M.ops.in(d_meta));
+            else if (phased) chop(bam_chop_tagged_kernel, M.tags.in(d_meta));
+            else chop(call.mode == ChopMode::RIGHT ? bam_chop_right_kernel : bam_chop_kernel);
             HIPCHK(hipGetLastError());
-            if (dedup) {
+            if (call.dedup) {
                 // one record of a molecule per region (rule W), before anything looks at the kept entries
-                hipLaunchKernelGGL(bam_dedup_kernel, dim3((unsigned)n_regions), dim3(64), 0, st, B->d_arena, reinterpret_cast<const BamRegion*>(d_meta + o_reg),
-                                   reinterpret_cast<const BamSpan*>(d_meta + o_span), (int)n_regions, reinterpret_cast<BamKept*>(d_meta + o_kept),
-                                   reinterpret_cast<int32_t*>(d_meta + o_nk), reinterpret_cast<int32_t*>(d_meta + o_rst),
-                                   phased && !haplo ? reinterpret_cast<BamTag*>(d_meta + o_tags) : (BamTag*)nullptr,
-                                   haplo ? reinterpret_cast<BamOps*>(d_meta + o_ops) : (BamOps*)nullptr, reinterpret_cast<uint64_t*>(d_meta + o_keys));
+                hipLaunchKernelGGL(bam_dedup_kernel, dim3((unsigned)n_regions), dim3(64), 0, st, B->d_arena, M.regs.in(d_meta), M.spans.in(d_meta), (int)n_regions,
+                                   M.kept.in(d_meta), M.n_kept.in(d_meta), M.reg_status.in(d_meta), phased && !haplo ? M.tags.in(d_meta) : (BamTag*)nullptr,
+                                   haplo ? M.ops.in(d_meta) : (BamOps*)nullptr, M.keys.in(d_meta));
                 HIPCHK(hipGetLastError());
             }
             if (haplo) {
                 // the tags of the kept records from the region's phased sites: a wavefront a (region, slot)
                 hipLaunchKernelGGL(bam_haplotag_kernel, dim3((unsigned)n_regions * (unsigned)(KEPT_CAP / HAPLOTAG_WAVES)), dim3(64 * HAPLOTAG_WAVES), 0, st,
-                                   B->d_arena, reinterpret_cast<const BamKept*>(d_meta + o_kept), reinterpret_cast<const BamOps*>(d_meta + o_ops),
-                                   reinterpret_cast<const int32_t*>(d_meta + o_nk), reinterpret_cast<const int32_t*>(d_meta + o_rst), (int)n_regions,
-                                   reinterpret_cast<const BamSiteRange*>(d_meta + o_srange), reinterpret_cast<const BamSite*>(d_meta + o_sites),
-                                   reinterpret_cast<const long long*>(d_meta + o_psv), reinterpret_cast<BamTag*>(d_meta + o_tags));
+                                   B->d_arena, M.kept.in(d_meta), M.ops.in(d_meta), M.n_kept.in(d_meta), M.reg_status.in(d_meta), (int)n_regions,
+                                   M.site_ranges.in(d_meta), M.sites.in(d_meta), M.ps_values.in(d_meta), M.tags.in(d_meta));
                 HIPCHK(hipGetLastError());
             }
             if (phased) {
-                hipLaunchKernelGGL(bam_select_kernel, dim3((unsigned)n_regions), dim3(64), 0, st, reinterpret_cast<const BamKept*>(d_meta + o_kept),
-                                   reinterpret_cast<const BamTag*>(d_meta + o_tags), reinterpret_cast<const int32_t*>(d_meta + o_nk),
-                                   reinterpret_cast<const int32_t*>(d_meta + o_rst), (int)n_regions, (int)max_keep,
-                                   reinterpret_cast<BamPick*>(d_meta + o_picks), reinterpret_cast<BamPhase*>(d_meta + o_phase));
+                hipLaunchKernelGGL(bam_select_kernel, dim3((unsigned)n_regions), dim3(64), 0, st, M.kept.in(d_meta), M.tags.in(d_meta), M.n_kept.in(d_meta),
+                                   M.reg_status.in(d_meta), (int)n_regions, (int)call.max_keep, M.picks.in(d_meta), M.phases.in(d_meta));
                 HIPCHK(hipGetLastError());
             }
         }
         // (counts and statuses first; the kept reads of a region are read where its count says)
-        HIPCHK(hipMemcpyAsync(h_meta + o_bst, d_meta + o_bst, back_end - o_bst, hipMemcpyDeviceToHost, st));
-        ctx->bam_stats[6] = (double)(back_end - o_bst);
+        HIPCHK(hipMemcpyAsync(M.back(h_meta), M.back(d_meta), M.back_bytes(), hipMemcpyDeviceToHost, st));
+        ctx->bam_stats[6] = (double)M.back_bytes();
         HIPCHK(hipStreamSynchronize(st));
         tq[5] = now_ms();
         {
             float ms = 0.f;
             if (hipEventElapsedTime(&ms, ctx->bam_ev[0], ctx->bam_ev[1]) != hipSuccess) ms = 0.f;
-            ctx->bam_stats[0] = n_regions; ctx->bam_stats[1] = (double)n_blks; ctx->bam_stats[2] = (double)stage_bytes;
-            ctx->bam_stats[3] = (double)arena; ctx->bam_stats[4] = ms; ctx->bam_stats[5] = tq[5] - tq[0];
+            ctx->bam_stats[0] = n_regions; ctx->bam_stats[1] = (double)n_blks; ctx->bam_stats[2] = (double)plan.stage_bytes;
+            ctx->bam_stats[3] = (double)L.arena; ctx->bam_stats[4] = ms; ctx->bam_stats[5] = tq[5] - tq[0];
         }
         if (dbg_t)
             fprintf(stderr, "bam_chop_device: %d regions, %zu blocks, %.1f MB compressed -> %.1f MB; read+scan %.2f  layout+alloc %.2f  h2d %.2f  inflate %.2f  chop+d2h %.2f ms\n",
-                    n_regions, n_blks, stage_bytes / 1e6, arena / 1e6, tq[1] - tq[0], tq[2] - tq[1], tq[3] - tq[2], tq[4] - tq[3], tq[5] - tq[4]);
+                    n_regions, n_blks, plan.stage_bytes / 1e6, L.arena / 1e6, tq[1] - tq[0], tq[2] - tq[1], tq[3] - tq[2], tq[4] - tq[3], tq[5] - tq[4]);
 #ifdef VBD_TIMING
-        if (dbg_t && n_blks) {
-            std::vector<uint8_t> back(stage_bytes);
-            HIPCHK(hipMemcpy(back.data(), stage.d_comp, stage_bytes, hipMemcpyDeviceToHost));
-            double sum[13] = {0};
-            size_t cnt = 0;
-            for (const BgzfBlk& k : blks) {
-                if (k.c_len < 128) continue;
-                const long long* d = reinterpret_cast<const long long*>(back.data() + ((k.c_off + 7u) & ~7u));
-                for (int t = 0; t < 13; ++t) sum[t] += (double)d[t];
-                ++cnt;
-            }
-            fprintf(stderr, "  per block (shader clocks, mean of %zu): top-up %.0f  decode %.0f (tables %.0f)  matches %.0f  crc %.0f  all %.0f\n"
-                            "  counts: fast literal steps %.0f, fast general symbols %.0f, careful symbols %.0f, matches %.0f (fills %.0f), batches %.0f; clocks in the fast loop's general symbols %.0f\n", cnt,
-                    sum[0] / cnt, sum[1] / cnt, sum[2] / cnt, sum[3] / cnt, sum[4] / cnt, sum[5] / cnt, sum[6] / cnt, sum[10] / cnt, sum[7] / cnt, sum[8] / cnt,
-                    sum[11] / cnt, sum[9] / cnt, sum[12] / cnt);
-        }
+        if (dbg_t && n_blks)
+            if (const int rc = dump_inflate_timing(stage.d_comp, plan.stage_bytes, L.blks)) return rc;
 #endif
-        // ---- minimize_pacbio_read_list (SF:1091-1102): at most max_keep, the smallest miss_bp first, file order inside one value
-        const int32_t* nk = reinterpret_cast<const int32_t*>(h_meta + o_nk);
-        const int32_t* rst = reinterpret_cast<const int32_t*>(h_meta + o_rst);
-        const BamKept* kept = reinterpret_cast<const BamKept*>(h_meta + o_kept);       // (not read when phased)
-        const uint64_t* keys = reinterpret_cast<const uint64_t*>(h_meta + o_keys);     // (de-duplicating and not phased)
-        B->has_keys = dedup && !phased;
-        int32_t w = 0;
-        std::vector<int32_t> order;
-        for (int32_t g = 0; phased && g < n_regions; ++g) {
-            // (the selection was made on the device: the union as it lies, at most 3 * max_keep entries)
-            const BamPhase& ph = reinterpret_cast<const BamPhase*>(h_meta + o_phase)[g];
-            kept_first[g] = w;
-            phase_set[g] = INT64_MIN;
-            tagged[g] = 0;
-            if (status[g]) continue;
-            if (rst[g] != REG_OK) { status[g] = rst[g]; continue; }
-            if (ph.n_union < 0 || ph.n_union > 3 * max_keep) { status[g] = REG_MALFORMED; continue; }
-            phase_set[g] = (int64_t)ph.ps;
-            tagged[g] = ph.tagged;
-            const BamPick* pk = reinterpret_cast<const BamPick*>(h_meta + o_picks) + (size_t)g * 3u * (size_t)max_keep;
-            for (int32_t i = 0; i < ph.n_union; ++i) {
-                sq_addr[w] = (uint64_t)reinterpret_cast<uintptr_t>(B->d_arena + pk[i].sq_off);
-                q0[w] = pk[i].q0;
-                miss[w] = pk[i].miss;
-                member[w] = pk[i].member;
-                ++w;
-            }
-        }
-        for (int32_t g = 0; !phased && g < n_regions; ++g) {
-            kept_first[g] = w;
-            if (status[g]) continue;
-            if (rst[g] != REG_OK) { status[g] = rst[g]; continue; }
-            const int32_t n = nk[g];
-            const BamKept* k = kept + (size_t)g * KEPT_CAP;
-            order.resize((size_t)n);
-            for (int32_t i = 0; i < n; ++i) order[(size_t)i] = i;
-            if (n > max_keep) {
-                std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return k[a].miss < k[b].miss; });
-                order.resize((size_t)max_keep);
-            }
-            for (int32_t i : order) {
-                sq_addr[w] = (uint64_t)reinterpret_cast<uintptr_t>(B->d_arena + k[i].sq_off);
-                q0[w] = k[i].q0;
-                miss[w] = k[i].miss;
-                if (dedup) B->name_keys.push_back(keys[(size_t)g * KEPT_CAP + (size_t)i]);
-                ++w;
-            }
-        }
-        kept_first[n_regions] = w;
+        B->has_keys = call.dedup && !phased;
+        collect(call, M, h_meta, (uint64_t)reinterpret_cast<uintptr_t>(B->d_arena), o, B->name_keys);
         sc.settled();
         *out = B.release();
         return VAPOR_OK;
     });
+}
+
+// the caller's region arrays and answer arrays of the four entries, as bam_chop_device_impl takes them
+static vapor_readplan::ChopCall chop_call(vapor_readplan::ChopMode mode, int32_t n_regions, const int32_t* tid, const int64_t* start, const int64_t* end,
+                                          const int64_t* flank, const int32_t* chunk_first, const uint64_t* chunks, int32_t max_keep)
+{
+    vapor_readplan::ChopCall c;
+    c.n_regions = n_regions; c.tid = tid; c.start = start; c.end = end; c.flank = flank; c.chunk_first = chunk_first; c.chunks = chunks;
+    c.max_keep = max_keep; c.mode = mode;
+    return c;
 }
 
 extern "C" int vapor_bam_chop_device(vapor_ctx* ctx, vapor_bam* bam, int32_t n_regions, const int32_t* tid, const int64_t* start,
@@ -1260,8 +1106,9 @@ extern "C" int vapor_bam_chop_device(vapor_ctx* ctx, vapor_bam* bam, int32_t n_r
                                      int32_t max_keep, int32_t* kept_first, uint64_t* sq_addr, int64_t* q0, int64_t* miss,
                                      int32_t* status, vapor_bam_batch** out)
 {
-    return bam_chop_device_impl(ctx, bam, n_regions, tid, start, end, flank, chunk_first, chunks, max_keep, kept_first, sq_addr, q0, miss,
-                                status, out, nullptr, nullptr, nullptr);
+    using namespace vapor_readplan;
+    return bam_chop_device_impl(ctx, bam, chop_call(ChopMode::PLAIN, n_regions, tid, start, end, flank, chunk_first, chunks, max_keep),
+                                ChopOut{kept_first, sq_addr, q0, miss, status}, out);
 }
 
 // The name keys (`--dedup-qname`; vapor_names.h name_key) of the n entries the call that made the batch returned, in
@@ -1283,8 +1130,9 @@ extern "C" int vapor_bam_chop_device_right(vapor_ctx* ctx, vapor_bam* bam, int32
                                            int32_t max_keep, int32_t* kept_first, uint64_t* sq_addr, int64_t* q1, int64_t* miss,
                                            int32_t* status, vapor_bam_batch** out)
 {
-    return bam_chop_device_impl(ctx, bam, n_regions, tid, start, end, flank, chunk_first, chunks, max_keep, kept_first, sq_addr, q1, miss,
-                                status, out, nullptr, nullptr, nullptr, true);
+    using namespace vapor_readplan;
+    return bam_chop_device_impl(ctx, bam, chop_call(ChopMode::RIGHT, n_regions, tid, start, end, flank, chunk_first, chunks, max_keep),
+                                ChopOut{kept_first, sq_addr, q1, miss, status}, out);
 }
 
 extern "C" int vapor_bam_chop_device_tagged(vapor_ctx* ctx, vapor_bam* bam, int32_t n_regions, const int32_t* tid, const int64_t* start,
@@ -1292,9 +1140,10 @@ extern "C" int vapor_bam_chop_device_tagged(vapor_ctx* ctx, vapor_bam* bam, int3
                                             int32_t max_keep, int32_t* kept_first, uint64_t* sq_addr, int64_t* q0, int64_t* miss,
                                             uint32_t* member, int64_t* phase_set, int32_t* tagged, int32_t* status, vapor_bam_batch** out)
 {
+    using namespace vapor_readplan;
     if (!member) return fail(VAPOR_E_ARG, "vapor_bam_chop_device_tagged: bad argument");
-    return bam_chop_device_impl(ctx, bam, n_regions, tid, start, end, flank, chunk_first, chunks, max_keep, kept_first, sq_addr, q0, miss,
-                                status, out, member, phase_set, tagged);
+    return bam_chop_device_impl(ctx, bam, chop_call(ChopMode::TAGGED, n_regions, tid, start, end, flank, chunk_first, chunks, max_keep),
+                                ChopOut{kept_first, sq_addr, q0, miss, status, member, phase_set, tagged}, out);
 }
 
 // vapor_bam_chop_device_tagged with the tags made on the device from phased SNVs (`--phase-vcf`): bam_chop_ops_kernel,
@@ -1305,10 +1154,11 @@ extern "C" int vapor_bam_chop_device_haplotag(vapor_ctx* ctx, vapor_bam* bam, in
                                               uint32_t* member, int64_t* phase_set, int32_t* tagged, int32_t* status, vapor_bam_batch** out,
                                               const int32_t* site_first, const void* sites, const int32_t* ps_first, const int64_t* ps_values)
 {
+    using namespace vapor_readplan;
     if (!member) return fail(VAPOR_E_ARG, "vapor_bam_chop_device_haplotag: bad argument");
-    const HaplotagIn hin{site_first, static_cast<const vapor_bamdev::BamSite*>(sites), ps_first, ps_values};
-    return bam_chop_device_impl(ctx, bam, n_regions, tid, start, end, flank, chunk_first, chunks, max_keep, kept_first, sq_addr, q0, miss,
-                                status, out, member, phase_set, tagged, false, &hin);
+    ChopCall c = chop_call(ChopMode::HAPLOTAG, n_regions, tid, start, end, flank, chunk_first, chunks, max_keep);
+    c.site_first = site_first; c.sites = static_cast<const vapor_bamdev::BamSite*>(sites); c.ps_first = ps_first; c.ps_values = ps_values;
+    return bam_chop_device_impl(ctx, bam, c, ChopOut{kept_first, sq_addr, q0, miss, status, member, phase_set, tagged}, out);
 }
 
 // what the context's last vapor_bam_chop_device did: regions, blocks, compressed bytes sent, inflated bytes, the inflate kernel's
@@ -1332,159 +1182,60 @@ extern "C" int vapor_fasta_windows_device(vapor_ctx* ctx, int fd, int32_t n, con
 {
     using namespace vapor_bamdev;
     using namespace vapor_fasta;
-    using vapor_bgzf::FaStretch;
+    using namespace vapor_readplan;
     if (!ctx || fd < 0 || n < 0 || text_cap < 0 || !text_off || (n && (!vbeg || !vend || !traits || !status)) || (text_cap && !text))
         return fail(VAPOR_E_ARG, "vapor_fasta_windows_device: bad argument");
     HIPCHK(hipSetDevice(ctx->device));
     const double t0 = now_ms();
-    constexpr uint64_t ARENA_CAP = (uint64_t)1 << 30, STAGE_CAP = (uint64_t)1 << 29;
     return guarded("vapor_fasta_windows_device", [&]() -> int {
-        // ---- windows in file order, merged into stretches --------------------------------------------------------------------
-        std::vector<int32_t> order;
-        order.reserve((size_t)n);
-        for (int32_t i = 0; i < n; ++i) {
-            status[i] = WIN_OK;
-            traits[i] = 0;
-            if (vend[i] < vbeg[i]) status[i] = WIN_RANGE;
-            else if (vend[i] > vbeg[i]) order.push_back(i);
-        }
-        std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return vbeg[a] != vbeg[b] ? vbeg[a] < vbeg[b] : a < b; });
-        std::vector<FaStretch> sts;
-        std::vector<int32_t> st_of((size_t)n, -1);
-        for (int32_t i : order) {
-            const int64_t c0 = (int64_t)(vbeg[i] >> 16), cl = (int64_t)(vend[i] >> 16);
-            const bool nl = (vend[i] & 0xFFFFu) != 0;
-            if (!sts.empty() && c0 <= sts.back().c_last) {          // (shares a block with the stretch, or starts where it ends)
-                FaStretch& s = sts.back();
-                if (cl > s.c_last || (cl == s.c_last && nl)) { s.c_last = cl; s.need_last = nl; }
-            } else {
-                FaStretch s;
-                s.c0 = c0; s.c_last = cl; s.need_last = nl;
-                sts.push_back(std::move(s));
-            }
-            st_of[(size_t)i] = (int32_t)sts.size() - 1;
-        }
-        // ---- read and scan the stretches --------------------------------------------------------------------------------------
-        uint64_t stage_bytes = 0;
-        for (FaStretch& s : sts) {
-            // (the last block in full: its BSIZE from its header, or the 64 KB a block can be at most when the header says nothing)
-            uint64_t last_size = 0;
-            if (s.need_last) {
-                uint8_t h[64];
-                const ssize_t r = pread(fd, h, sizeof h, (off_t)s.c_last);
-                last_size = vapor_bgzf::last_block_size(h, (size_t)std::max<ssize_t>(r, 0));
-            }
-            const uint64_t want = (uint64_t)(s.c_last - s.c0) + last_size;
-            if (stage_bytes + want > STAGE_CAP) { s.room = false; continue; }
-            s.want = (size_t)want;
-            s.stage_off = (size_t)stage_bytes;
-            stage_bytes += (want + 63) & ~(uint64_t)63;
-        }
+        // ---- what to read: the windows in file order, merged into stretches ---------------------------------------------------
+        const FastaCall call{n, vbeg, vend, text_cap};
+        StretchPlan plan;
+        plan_stretches(call, status, traits, plan);
+        stage_stretches(plan, [&](int64_t file_off, uint8_t* h) { return (size_t)std::max<ssize_t>(pread(fd, h, 64, (off_t)file_off), 0); });
         CallScope sc(ctx, ctx->stream);
         InflateStage stage(sc);
-        HostBlock<>& h_meta = stage.h_meta;
         HostBlock<> h_text(sc);
-        Block<>& d_meta = stage.d_meta;
         Block<> d_arena(sc), d_text(sc);
-        HIPCHK(stage.begin((size_t)stage_bytes));
+        HIPCHK(stage.begin((size_t)plan.stage_bytes));
+        // ---- read and scan the stretches --------------------------------------------------------------------------------------
         uint64_t read_bytes = 0;
-        for (FaStretch& s : sts) {
+        for (FaStretch& s : plan.sts) {
             if (!s.room) continue;
             s.got = stage.read(fd, s.stage_off, s.want, s.c0);
             read_bytes += s.got;
             vapor_bgzf::scan_stretch(s, stage.h_comp);
         }
-        // ---- layout: the arena (64-bit offsets, a limit), the block table ------------------------------------------------------
-        std::vector<BgzfBlk> blks;
-        uint64_t arena = 0;
-        for (FaStretch& s : sts) {
-            if (!s.room) continue;
-            const uint64_t size = s.blks.back().u;
-            if (arena + size + 64 > ARENA_CAP) { s.room = false; continue; }
-            s.arena_off = arena;
-            for (size_t k = 0; k < s.blks.size(); ++k) {
-                s.gidx[k] = (uint32_t)blks.size();
-                if (s.blks[k].isize) blks.push_back(InflateStage::blk(s.stage_off, s.blks[k], arena));
-            }
-            arena += (size + 63) & ~(uint64_t)63;
-        }
-        // ---- the windows: their bytes in the arena, their slots in the text buffer --------------------------------------------
-        std::vector<FastaWin> wins((size_t)std::max(n, 1));
-        uint64_t slots = 0;
-        auto find = [](const FaStretch& s, int64_t coff) -> int64_t {
-            const size_t pos = (size_t)(coff - s.c0);
-            auto it = std::lower_bound(s.blks.begin(), s.blks.end(), pos, [](const vapor_bgzf::Block& b, size_t p) { return b.pos < p; });
-            return it != s.blks.end() && it->pos == pos ? (int64_t)(it - s.blks.begin()) : -1;
-        };
-        for (int32_t i = 0; i < n; ++i) {
-            FastaWin& W = wins[(size_t)i];
-            W = FastaWin{0, 0, 0, 0, 0};
-            const int32_t si = st_of[(size_t)i];
-            if (status[i] || si < 0) continue;
-            const FaStretch& s = sts[(size_t)si];
-            if (!s.room) { status[i] = WIN_ROOM; continue; }
-            const int64_t kb = find(s, (int64_t)(vbeg[i] >> 16)), ke = find(s, (int64_t)(vend[i] >> 16));
-            const uint32_t ub = (uint32_t)(vbeg[i] & 0xFFFFu), ue = (uint32_t)(vend[i] & 0xFFFFu);
-            const bool last_is_sentinel = ke == (int64_t)s.blks.size() - 1;
-            if (kb < 0 || ke < 0 || kb == (int64_t)s.blks.size() - 1 || ub > s.blks[(size_t)kb].isize || ue > s.blks[(size_t)ke].isize || (last_is_sentinel && ue)) {
-                status[i] = s.cut ? WIN_BLOCK : WIN_RANGE;
-                continue;
-            }
-            W.a_beg = s.arena_off + s.blks[(size_t)kb].u + ub;
-            W.a_end = s.arena_off + s.blks[(size_t)ke].u + ue;
-            if (W.a_end < W.a_beg) { status[i] = WIN_RANGE; W.a_end = W.a_beg; continue; }
-            const uint64_t len = W.a_end - W.a_beg;
-            if (slots + len > (uint64_t)text_cap) { status[i] = WIN_ROOM; W.a_end = W.a_beg; continue; }
-            W.t_off = slots;
-            slots += len;
-            W.blk_first = s.gidx[(size_t)kb];
-            W.blk_n = s.gidx[(size_t)ke] + (ue ? 1u : 0u) - W.blk_first;
-        }
+        // ---- layout: the arena, the block table, the windows, the metadata block ----------------------------------------------
+        FastaLayout L;
+        layout_arena(plan, L);
+        place_windows(call, plan, status, L);
+        const FastaMeta M(n, L.blks.size());
+        if (const int rc = stage.alloc(M.bytes, M.bytes)) return rc;
+        HIPCHK(d_arena.ensure((size_t)L.arena + 64));
+        HIPCHK(d_text.ensure((size_t)std::max<uint64_t>(L.slots, 64)));
+        HIPCHK(h_text.ensure((size_t)std::max<uint64_t>(L.slots, 64)));
+        uint8_t *const h_meta = stage.h_meta, *const d_meta = stage.d_meta;
+        M.fill(h_meta, L, status, n);
         // ---- the device: copies, two kernels, the answers back -----------------------------------------------------------------
-        const size_t n_blks = blks.size(), nw = (size_t)std::max(n, 1);
-        Carve m;
-        m.take(sizeof(BgzfBlk) * std::max<size_t>(n_blks, 1));
-        const size_t o_win = m.take(sizeof(FastaWin) * nw), o_st = m.take(4 * nw);
-        const size_t in_bytes = m.off;
-        const size_t o_len = m.take(8 * nw), o_tr = m.take(nw), o_bst = m.off;
-        const size_t meta_bytes = o_bst + 4 * std::max<size_t>(n_blks, 1);
-        if (const int rc = stage.alloc(meta_bytes, meta_bytes)) return rc;
-        HIPCHK(d_arena.ensure((size_t)arena + 64));
-        HIPCHK(d_text.ensure((size_t)std::max<uint64_t>(slots, 64)));
-        HIPCHK(h_text.ensure((size_t)std::max<uint64_t>(slots, 64)));
-        memcpy(h_meta + o_win, wins.data(), sizeof(FastaWin) * nw);
-        if (n) memcpy(h_meta + o_st, status, 4 * (size_t)n);
         hipStream_t st = ctx->stream;
-        if (const int rc = stage.run(blks, in_bytes, o_bst, d_arena, ctx->fasta_ev)) return rc;
+        if (const int rc = stage.run(L.blks.size(), M.in_bytes, M.blks.in(d_meta), M.blk_status.in(d_meta), d_arena, ctx->fasta_ev)) return rc;
         if (n) {
-            hipLaunchKernelGGL(fasta_window_kernel, dim3((unsigned)((nw + WIN_WAVES - 1) / WIN_WAVES)), dim3(64 * WIN_WAVES), 0, st, d_arena,
-                               reinterpret_cast<const FastaWin*>(d_meta + o_win), (int)n, reinterpret_cast<const int32_t*>(d_meta + o_bst), d_text,
-                               reinterpret_cast<int64_t*>(d_meta + o_len), d_meta + o_tr, reinterpret_cast<int32_t*>(d_meta + o_st));
+            hipLaunchKernelGGL(fasta_window_kernel, dim3((unsigned)(((size_t)n + WIN_WAVES - 1) / WIN_WAVES)), dim3(64 * WIN_WAVES), 0, st, d_arena,
+                               M.wins.in(d_meta), (int)n, M.blk_status.in(d_meta), d_text, M.text_len.in(d_meta), M.traits.in(d_meta), M.status.in(d_meta));
             HIPCHK(hipGetLastError());
         }
         HIPCHK(hipEventRecord(ctx->fasta_ev[1], st));
-        HIPCHK(hipMemcpyAsync(h_meta + o_st, d_meta + o_st, meta_bytes - o_st, hipMemcpyDeviceToHost, st));
-        if (slots) HIPCHK(hipMemcpyAsync(h_text, d_text, (size_t)slots, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(M.back(h_meta), M.back(d_meta), M.back_bytes(), hipMemcpyDeviceToHost, st));
+        if (L.slots) HIPCHK(hipMemcpyAsync(h_text, d_text, (size_t)L.slots, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         sc.settled();
         // ---- the texts, one after the other ------------------------------------------------------------------------------------
-        const int32_t* d_status = reinterpret_cast<const int32_t*>(h_meta + o_st);
-        const int64_t* tlen = reinterpret_cast<const int64_t*>(h_meta + o_len);
-        int64_t pos = 0;
-        text_off[0] = 0;
-        for (int32_t i = 0; i < n; ++i) {
-            status[i] = d_status[i];
-            traits[i] = h_meta[o_tr + (size_t)i];
-            if (!status[i] && tlen[i]) {
-                memcpy(text + pos, h_text + wins[(size_t)i].t_off, (size_t)tlen[i]);
-                pos += tlen[i];
-            }
-            text_off[i + 1] = pos;
-        }
+        gather_texts(n, M, h_meta, h_text, L.wins, text, text_off, traits, status);
         float ms = 0.f;
         if (hipEventElapsedTime(&ms, ctx->fasta_ev[0], ctx->fasta_ev[1]) != hipSuccess) ms = 0.f;
-        ctx->fasta_stats[0] = n; ctx->fasta_stats[1] = (double)n_blks; ctx->fasta_stats[2] = (double)read_bytes;
-        ctx->fasta_stats[3] = (double)arena; ctx->fasta_stats[4] = ms; ctx->fasta_stats[5] = now_ms() - t0;
+        ctx->fasta_stats[0] = n; ctx->fasta_stats[1] = (double)L.blks.size(); ctx->fasta_stats[2] = (double)read_bytes;
+        ctx->fasta_stats[3] = (double)L.arena; ctx->fasta_stats[4] = ms; ctx->fasta_stats[5] = now_ms() - t0;
         return VAPOR_OK;
     });
 }
