@@ -485,6 +485,22 @@ int vapor_bam_chop_device_right(vapor_ctx* ctx, vapor_bam* bam, int32_t n_region
                                 const int64_t* end, const int64_t* flank, const int32_t* chunk_first, const uint64_t* chunks,
                                 int32_t max_keep, int32_t* kept_first, uint64_t* sq_addr, int64_t* q1, int64_t* miss,
                                 int32_t* status, vapor_bam_batch** batch);
+/*
+ * Read depth (`--depth`; not in the reference).  A depth region is a contig and four bounds b0 <= b1 <= b2 <= b3,
+ * 0-based: three consecutive half-open intervals [b0, b1) [b1, b2) [b2, b3), any of them empty.  A record counts iff it passes
+ * the handle's read filter (vapor_bam_set_filter) with 0x704 - unmapped, secondary, QC-fail, duplicate - always among the
+ * excluded flags; vapor_bam_set_dedup has no effect.  Of a counting record every M, = and X operation covers the reference bases
+ * it spans; D and N move the reference cursor and cover nothing; I S H P do neither; a CG:B,I array replaces its two-operation
+ * stand-in; a record without operations covers nothing.  cov[i] = the sum over those operations of their overlap with interval i.
+ * vapor_bam_depth: one region on the host, `chunks` its .bai chunks (sorted and merged: a record is met once) as in
+ * vapor_bam_chop; errors as there.  VAPOR_E_ARG for bounds that do not ascend from 0, b3 >= 2^31 or tid < 0.
+ * vapor_bam_depth_device: n_regions regions in one call as vapor_bam_chop_device takes them (bounds: four a region, cov: three
+ * a region) - their blocks inflated on the device, bam_depth_kernel, one wavefront a region.  status[g] = 0, or a positive code
+ * of vapor_bam_chop_device's where the region is the host route's (its cov are 0 then).  Nothing stays on the device.
+ */
+int vapor_bam_depth(vapor_bam* bam, int32_t tid, const int64_t* bounds, int32_t n_chunks, const uint64_t* chunks, uint64_t* cov);
+int vapor_bam_depth_device(vapor_ctx* ctx, vapor_bam* bam, int32_t n_regions, const int32_t* tid, const int64_t* bounds,
+                           const int32_t* chunk_first, const uint64_t* chunks, uint64_t* cov, int32_t* status);
 /* what the context's last vapor_bam_chop_device (or _tagged) did, for measurement (bench.py): out[0..6] = regions, BGZF blocks,
  * compressed bytes sent over the link, inflated bytes, the inflate kernel's duration between two events on its stream (ms), the
  * whole call (ms), bytes of kept reads and statuses copied back from the device */

@@ -5,6 +5,8 @@
 //   ASAN_OPTIONS=detect_leaks=0 /tmp/bam_check file.bam <first virtual offset> <tid> <start> <end> <flank> [threads [min_mapq exclude_flags]]
 // With min_mapq and exclude_flags (decimal or 0x hex) the handle carries that read filter (vapor_bam_set_filter), and
 // the right-anchored and the tagged reader walk the file behind the plain one; without them nothing changes.
+// A last argument `depth` adds a depth pass (vapor_bam_depth) over every record of the file behind the others:
+// the intervals [0, start) [start, end) [end, 2^31 - 1) of the contig, under the handle's filter.
 // tests/test_bamio.py builds it and runs it over the damaged files of its other tests and a few hundred randomly damaged ones.
 #include "vapor_bam.cpp"
 #include <cstdio>
@@ -12,7 +14,9 @@
 
 int main(int argc, char** argv)
 {
-    if (argc < 7) { fprintf(stderr, "usage: bam_check file.bam first_voffset tid start end flank [threads [min_mapq exclude_flags]]\n"); return 2; }
+    const bool depth = argc > 7 && !strcmp(argv[argc - 1], "depth");
+    if (depth) --argc;
+    if (argc < 7) { fprintf(stderr, "usage: bam_check file.bam first_voffset tid start end flank [threads [min_mapq exclude_flags]] [depth]\n"); return 2; }
     vapor_bam* b = nullptr;
     if (vapor_bam_open(argv[1], &b) != 0) { printf("open: %s\n", vapor_bam_last_error()); return 0; }
     if (argc > 7) vapor_bam_set_threads(b, atoi(argv[7]));
@@ -64,6 +68,14 @@ int main(int argc, char** argv)
             for (int32_t r = 0; r < n && rc == 0; ++r) bases += meta[(size_t)w * r + 1];
             printf("%s: rc %d reads %d bases %lld %s\n", flavour ? "tagged" : "right", rc, n, bases, rc ? vapor_bam_last_error() : "");
         }
+    }
+    if (depth) {
+        const int64_t s = std::max<int64_t>(start, 0), e = std::max(end, s);
+        const int64_t bounds[4] = {0, s, e, std::max<int64_t>(e, ((int64_t)1 << 31) - 1)};
+        uint64_t cov[3] = {0, 0, 0};
+        rc = vapor_bam_depth(b, tid, bounds, 1, chunk, cov);
+        printf("depth: rc %d cov %llu %llu %llu %s\n", rc, (unsigned long long)cov[0], (unsigned long long)cov[1], (unsigned long long)cov[2],
+               rc ? vapor_bam_last_error() : "");
     }
     vapor_bam_close(b);
     return 0;

@@ -472,16 +472,38 @@ class BamFile:
         except Exception:       # noqa: BLE001
             pass
 
-    def fetch_raw(self, chrom: str, start: int, end: int, sites=None):
+    def depth_native(self, tid: int, bounds, chunks=None):
+        """[cov0, cov1, cov2] of one depth region (`--depth`, DESIGN.md 4.19) through the library's host reader (vapor_bam_depth);
+        the .bai lookup stays here.  ValueError with the reader's message for a file that breaks a rule."""
+        from . import _lib
+        lib = _lib.load()
+        b = np.ascontiguousarray(bounds, dtype=np.int64)
+        ch = self.index.chunks(tid, int(b[0]), int(b[3])) if chunks is None else chunks
+        cov = np.zeros(3, dtype=np.uint64)
+        if not len(ch):
+            return [0, 0, 0]
+        flat = np.asarray(ch, dtype=np.uint64).reshape(-1)
+        tl = self._take_handle(lib)
+        try:
+            if lib.vapor_bam_depth(tl["native"], int(tid), b.ctypes.data, len(flat) // 2, flat.ctypes.data, cov.ctypes.data) != 0:
+                raise ValueError(lib.vapor_bam_last_error().decode())
+        finally:
+            with self._lock:
+                self._free.append(tl)
+        return [int(x) for x in cov]
+
+    def fetch_raw(self, chrom: str, start: int, end: int, sites=None, exclude_more: int = 0):
         """(QNAME, 1-based POS, CIGAR operations as a uint32 tuple, packed SEQ bytes, l_seq, FLAG, (hap, ps)) of the alignments
         that overlap the 1-based inclusive region, in file order; nothing is decoded to text.  (hap, ps): the record's
         haplotype and phase set (phase.tags_from_aux) - or, with sites (`--phase-vcf`: the locus's phased sites as
-        phase.haplotag takes them), what phase.haplotag makes of its CIGAR and SEQ, the record's own tags not looked at."""
+        phase.haplotag takes them), what phase.haplotag makes of its CIGAR and SEQ, the record's own tags not looked at.
+        exclude_more (`--depth`): flags excluded beside the read filter's."""
         tid = self.tid.get(chrom)
         if tid is None:
             return []
         beg, stop = max(start - 1, 0), end               # 0-based half-open
         min_mapq, exclude = self.read_filter
+        exclude |= exclude_more
         out = []
         for cs, ce in self.index.chunks(tid, beg, stop):
             cur = self.bgzf.read_from(cs)

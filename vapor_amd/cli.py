@@ -21,8 +21,11 @@ every read route; the default, 0 and 0, filters nothing.  --dedup-qname (every s
 §4.18): records with one QNAME are one molecule - among the kept records of one (file, region, anchor kind) one survives, the
 first that is neither secondary (0x100) nor supplementary (0x800), else the first, and the others are treated as if they were
 not in the file; with --both-ends the pooled VaPoR_BE_* columns count a molecule once across the views.  It adds no column.
+--depth (bed, vcf): read depth inside every DEL and TANDUP call against the depth of its 1 kb flanks, a second
+line of evidence beside the dot plots; appends VaPoR_DP_IN, VaPoR_DP_FL, VaPoR_DFC and VaPoR_DSUP; the row's own columns are
+the plain run's; not together with --refine, --phased, --phase-vcf or --both-ends.
 
---refine, --phased (with --phase-vcf) and --both-ends each append columns to every row and exclude one another: a run has one
+--refine, --phased (with --phase-vcf), --both-ends and --depth each append columns to every row and exclude one another: a run has one
 mode (vapor_amd.modes) or none, built once in _main and handed as one argument to bed_jobs / vcf_jobs (which
 driver a locus takes), score_jobs (the payload gathered into Job.extra), the table writer and SF.vcf_vapor_modify.  An option
 that adds columns is a module with INFO, COLUMNS, pack, unpack and columns_many, a Mode made of it, and its branch in _simple_job.
@@ -680,7 +683,42 @@ def _both_ends_gens(jobs, rest, gens, engine):
     return gens, held
 
 
-modes.BOTH_ENDS.chunk_gens = _both_ends_gens          # (the only mode with a hook of its own in a chunk)
+modes.BOTH_ENDS.chunk_gens = _both_ends_gens          # (the only mode that replaces a chunk's generators)
+
+
+def _depth_payloads(jobs, todo, engine):
+    """`--depth`: depth is not a property of a driver's result but of the chunk - the depth regions of all
+    its DEL and TANDUP loci (depth.regions of Job.spec, clipped to the backend's contig length), array route and drivers' route
+    alike, go to the read backend in one depth_many call per BAM file (a per-chromosome pattern: per file, summed).  Returns
+    {t: depth.Payload}; a locus of another type has none."""
+    from . import depth, seqio
+    be = seqio.get_backend()
+    by_bam = {}
+    for t in todo:
+        j = jobs[t]
+        if j.spec is not None and j.ctx is not None and j.spec[0] in depth.TYPES:
+            by_bam.setdefault((j.ctx[1], j.ctx[2]), []).append(t)
+    out = {}
+    for (bam, ref), ts in by_bam.items():
+        files = seqio.bam_in_decide(bam, None)
+        where, chroms, bounds = [], [], []
+        for t in ts:
+            name, chrom, s, e = jobs[t].spec[:4]
+            regs = depth.regions(name, [chrom, s, e], be.contig_length(files[0], ref, chrom) if files else 0)
+            where.append((len(bounds), regs))
+            chroms += [chrom] * len(regs)
+            bounds += regs
+        covs = [[0, 0, 0] for _ in bounds]
+        for f in files:
+            for k, c in enumerate(be.depth_many(engine, f, chroms, bounds)):
+                covs[k] = [x + int(y) for x, y in zip(covs[k], c)]
+        for t, (at, regs) in zip(ts, where):
+            p = depth.payload(jobs[t].spec[0], regs, covs[at:at + len(regs)])
+            out[t] = depth.Payload(p, jobs[t].spec[0]) if p is not None else None
+    return out
+
+
+modes.DEPTH.chunk_payloads = _depth_payloads
 
 
 last_timing: dict = {}          # of the most recent score_jobs: seconds scoring this rank's share, seconds in the gather
@@ -692,6 +730,7 @@ def _score_jobs(jobs, chunk, figure_fn, t0, mode=None):
     costs = [float(j.cost) for j in jobs]
     mine = vdist.my_share(len(jobs), costs)
     local: dict = {}
+    payloads: dict = {}            # of a mode with chunk_payloads: {job: payload}, written by one_chunk (a chunk's jobs are its own)
 
     def one_chunk(a, engine=None):
         part = mine[a:a + chunk]
@@ -726,6 +765,9 @@ def _score_jobs(jobs, chunk, figure_fn, t0, mode=None):
                 bt.close()
         for t, r in zip(rest, res):
             done[t] = r
+        if mode is not None and mode.chunk_payloads is not None and todo:
+            # (a payload of the chunk, not of a driver's result: one call for all its loci, whichever route scored them)
+            payloads.update(mode.chunk_payloads(jobs, todo, engine))
         return part, todo, [done[t] for t in todo]
 
     in_flight = max(1, int(os.environ.get("VAPOR_CHUNKS_IN_FLIGHT", "3")))
@@ -780,8 +822,11 @@ def _score_jobs(jobs, chunk, figure_fn, t0, mode=None):
     t1 = time.perf_counter()
     if mode is not None:
         # (the extra columns travel as a second table of "scores": mode.pack's floats for a locus with a payload, none otherwise)
-        extra = {t: (mode.pack(getattr(r, mode.attr, None)) if not isinstance(r, BaseException) and r is not None else [])
-                 for t, r in local.items()}
+        if mode.chunk_payloads is not None:
+            extra = {t: mode.pack(payloads.get(t)) for t in local}
+        else:
+            extra = {t: (mode.pack(getattr(r, mode.attr, None)) if not isinstance(r, BaseException) and r is not None else [])
+                     for t, r in local.items()}
         for j, v in zip(jobs, vdist.gather_results(extra, len(jobs), costs)):
             j.extra = mode.unpack(v)
     allres = vdist.gather_results(local, len(jobs), costs)
@@ -828,6 +873,11 @@ def build_parser() -> argparse.ArgumentParser:
                         'breakend of --bnd - from both of its sides: the reads that end behind the window (right-anchored) are scored '
                         'as well, [B:q[t breakends are taken; appends VaPoR_BE_N, VaPoR_BE_QS / _GS / _GT / _GQ / _Rec and VaPoR_BE_SQS '
                         '(vcf: to INFO); not together with --refine or --phased')
+    p.add_argument('--depth', action='store_true',
+                   help='bed, vcf: compare read depth inside every DEL and TANDUP call with the depth of its 1 kb flanks (an event '
+                        'above 20 kb: 10 kb at each of its ends); unmapped, secondary, QC-fail and duplicate records never count; '
+                        'appends VaPoR_DP_IN, VaPoR_DP_FL, VaPoR_DFC and VaPoR_DSUP - 1 where the fold change is below 0.7 for a DEL, '
+                        'above 1.3 for a TANDUP (vcf: to INFO); not together with --refine, --phased, --phase-vcf or --both-ends')
     p.add_argument('--min-mapq', metavar='Q', type=_int_in('--min-mapq', 0, 255), default=0,
                    help='every sub-command: skip records with MAPQ below Q (0..255, default 0), as `samtools view -q Q` does; a '
                         'filtered record is treated as if it were not in the file')
@@ -917,6 +967,17 @@ def _main(argv, held) -> int:
             parser.error('--both-ends and --refine cannot be combined (refined candidates are scored from one side)')
         if args.phased:
             parser.error('--both-ends and --phased cannot be combined (right-anchored reads are not read with their tags)')
+    if args.depth:
+        if cmd not in ('bed', 'vcf'):
+            parser.error('--depth applies to `vapor bed` and `vapor vcf`')
+        if refine is not None:
+            parser.error('--depth and --refine cannot be combined (depth is measured over the called breakpoints)')
+        if args.phase_vcf is not None:
+            parser.error('--depth and --phase-vcf cannot be combined (depth is not measured per haplotype)')
+        if args.phased:
+            parser.error('--depth and --phased cannot be combined (depth is not measured per haplotype)')
+        if args.both_ends:
+            parser.error('--depth and --both-ends cannot be combined (a run has one mode)')
     if args.phase_vcf is not None:
         # (every rank reads the VCF itself; the sites ride on the backend the reads are taken through)
         from . import phase as ph
@@ -942,13 +1003,15 @@ def _main(argv, held) -> int:
         backend.dedup_qname = True
         if backend not in held:
             held.append(backend)
-    mode = None                          # (at most one of the three: every pair was refused above)
+    mode = None                          # (at most one of the four: every pair was refused above)
     if refine is not None:
         mode = modes.refine(*refine, ci_of=vcf_ci_readin(args.sv_input) if cmd == 'vcf' else None)
     elif args.phased:
         mode = modes.PHASED
     elif args.both_ends:
         mode = modes.BOTH_ENDS
+    elif args.depth:
+        mode = modes.DEPTH
     figure_fn = None
     if not args.no_figures:
         from . import figures

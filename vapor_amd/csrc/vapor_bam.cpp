@@ -673,6 +673,111 @@ extern "C" int vapor_bam_chop_haplotag(vapor_bam* b, int32_t tid, int64_t start,
     }
 }
 
+// Read depth of three consecutive intervals [b0, b1) [b1, b2) [b2, b3) of contig `tid`, 0-based half-open (`--depth`, DESIGN.md
+// 4.19; vapor_amd/depth.py cover is the rule, bam_depth_kernel the device's form): bam_chop_impl's walk over the chunks' records
+// with its checks, the handle's read filter with DEPTH_EXCLUDE among its flags, and per passing record the overlap of every M, =
+// and X operation with each interval - D and N move the reference cursor and cover nothing, a record without operations covers
+// nothing.  A record at or behind b3 ends a chunk.
+static int bam_depth_impl(vapor_bam* b, int32_t tid, const int64_t* bounds, int32_t n_chunks, const uint64_t* chunks, uint64_t* cov)
+{
+    if (!b || !bounds || !cov || n_chunks < 0 || (n_chunks && !chunks)) return bfail(VAPOR_E_ARG, "vapor_bam_depth: null argument");
+    const int64_t b0 = bounds[0], b1 = bounds[1], b2 = bounds[2], b3 = bounds[3];
+    if (b0 < 0 || b1 < b0 || b2 < b1 || b3 < b2 || b3 >= ((int64_t)1 << 31) || tid < 0)
+        return bfail(VAPOR_E_ARG, "vapor_bam_depth: the bounds do not ascend from 0 to a BAM position, or the contig is none");
+    const uint32_t excl = b->exclude_flags | vapor_bamdev::DEPTH_EXCLUDE;
+    cov[0] = cov[1] = cov[2] = 0;
+    auto overlap = [](int64_t s, int64_t e, int64_t lo, int64_t hi) -> uint64_t {
+        const int64_t a = std::max(s, lo), z = std::min(e, hi);
+        return z > a ? (uint64_t)(z - a) : 0u;
+    };
+    for (int32_t c = 0; c < n_chunks; ++c) {
+        const uint64_t cs = chunks[2 * c], ce = chunks[2 * c + 1];
+        b->comp.clear(); b->data.clear(); b->scan_pos = 0;
+        b->blk_coff.clear(); b->blk_cpos.clear(); b->blk_csize.clear(); b->blk_ustart.clear(); b->blk_usize.clear();
+        b->comp_base = (int64_t)(cs >> 16);
+        if (ce < cs || (ce >> 16) - (cs >> 16) > ((uint64_t)1 << 31))
+            return bfail(VAPOR_E_ARG, "vapor_bam_depth: implausible index chunk for " + b->path);
+        const size_t span = (size_t)((int64_t)(ce >> 16) - b->comp_base) + ((ce & 0xFFFFu) ? ((size_t)1 << 16) + 64 : 0);
+        if (span == 0 || !read_more(b, span)) continue;
+        if (scan_blocks(b) < 0 && ((uint64_t)(b->comp_base + (int64_t)b->scan_pos) << 16) < ce)
+            return bfail(VAPOR_E_ARG, "vapor_bam_depth: not a BGZF block in " + b->path);
+        size_t own = 0;
+        while (own < b->blk_coff.size() && ((uint64_t)b->blk_coff[own] << 16) < ce) ++own;
+        if (!take_blocks(b, own)) return bfail(VAPOR_E_ARG, "vapor_bam_depth: inflate failed in " + b->path);
+        int64_t pos_u = (int64_t)(cs & 0xFFFF);
+        size_t blk = 0;
+        for (;;) {
+            // (the virtual offset of pos_u, as bam_chop_impl decides it)
+            uint64_t voff;
+            if (pos_u >= (int64_t)b->data.size()) {
+                const size_t taken = b->blk_ustart.size();
+                if (taken == 0) break;
+                voff = (uint64_t)(b->blk_coff[taken - 1] + b->blk_csize[taken - 1]) << 16;
+            } else {
+                while (blk + 1 < b->blk_ustart.size() && pos_u >= b->blk_ustart[blk + 1]) ++blk;
+                voff = ((uint64_t)b->blk_coff[blk] << 16) | (uint64_t)(pos_u - b->blk_ustart[blk]);
+            }
+            if (voff >= ce) break;
+            if (!ensure(b, pos_u + 4)) {
+                if (!g_bam_damaged) break;
+                return bfail(VAPOR_E_ARG, "vapor_bam_depth: damaged BGZF block in " + b->path);
+            }
+            const int32_t bs = rd32(b->data.data() + pos_u);
+            if (bs < 32 || bs > (1 << 29)) return bfail(VAPOR_E_ARG, "vapor_bam_depth: implausible record size in " + b->path);
+            if (!ensure(b, pos_u + 4 + bs)) return bfail(VAPOR_E_ARG, "vapor_bam_depth: truncated record (or damaged block) in " + b->path);
+            const uint8_t* r = b->data.data() + pos_u + 4;
+            pos_u += 4 + bs;
+            const int32_t ref_id = rd32(r), pos = rd32(r + 4);
+            const int l_name = r[8];
+            const int n_cig = r[12] | (r[13] << 8);
+            const int32_t l_seq = rd32(r + 16);
+            if (l_seq < 0 || 32 + (int64_t)l_name + 4 * (int64_t)n_cig + ((int64_t)l_seq + 1) / 2 + (int64_t)l_seq > (int64_t)bs)
+                return bfail(VAPOR_E_ARG, "vapor_bam_depth: record fields exceed the record in " + b->path);
+            if (ref_id != tid || (int64_t)pos >= b3) {
+                if (ref_id > tid || (ref_id == tid && (int64_t)pos >= b3)) break;
+                continue;
+            }
+            if ((uint32_t)r[9] < b->min_mapq || (((uint32_t)r[14] | ((uint32_t)r[15] << 8)) & excl)) continue;
+            const uint8_t* cig = r + 32 + l_name;
+            const uint8_t* ops = cig;
+            int32_t n_ops = n_cig;
+            if (n_cig == 2) {
+                const uint32_t o0 = (uint32_t)rd32(cig), o1 = (uint32_t)rd32(cig + 4);
+                if ((o0 & 15u) == 4u && (int32_t)(o0 >> 4) == l_seq && (o1 & 15u) == 3u) {
+                    int32_t cnt = 0;
+                    const uint8_t* cg = find_cg(cig + 8 + (l_seq + 1) / 2 + l_seq, r + bs, &cnt);
+                    if (cg) { ops = cg; n_ops = cnt; }
+                }
+            }
+            int64_t cur = pos;
+            for (int32_t t = 0; t < n_ops && cur < b3; ++t) {
+                const uint32_t o = (uint32_t)rd32(ops + 4 * (size_t)t), code = o & 15u;
+                const int64_t n = o >> 4;
+                if (code == 0u || code == 7u || code == 8u) {
+                    cov[0] += overlap(cur, cur + n, b0, b1);
+                    cov[1] += overlap(cur, cur + n, b1, b2);
+                    cov[2] += overlap(cur, cur + n, b2, b3);
+                    cur += n;
+                } else if (code == 2u || code == 3u) {
+                    cur += n;
+                }
+            }
+        }
+    }
+    return VAPOR_OK;
+}
+
+extern "C" int vapor_bam_depth(vapor_bam* b, int32_t tid, const int64_t* bounds, int32_t n_chunks, const uint64_t* chunks, uint64_t* cov)
+{
+    try {
+        return bam_depth_impl(b, tid, bounds, n_chunks, chunks, cov);
+    } catch (const std::bad_alloc&) {
+        return bfail(VAPOR_E_NOMEM, "vapor_bam_depth: out of memory");
+    } catch (const std::exception& e) {
+        return bfail(VAPOR_E_ARG, std::string("vapor_bam_depth: ") + e.what());
+    }
+}
+
 // chop_pacbio_read_by_pos (SF:339-354) over alignment records that are in memory already (a caller that holds its reads as
 // objects - the synthetic worlds of the tests and benches, a reader of another format): the region rule of `samtools view`,
 // the reference's `POS < start + 1`, the CIGAR walk to the window start (cigar2alignstart_by_pos, SF:309-337, over the CIGAR
@@ -1077,4 +1182,11 @@ extern "C" __attribute__((weak)) int vapor_bam_chop_device_right(vapor_ctx*, vap
                                                                  int64_t*, int64_t*, int32_t*, vapor_bam_batch**)
 {
     return bfail(VAPOR_E_ARG, "vapor_bam_chop_device_right: this build has no device reader");
+}
+
+// ... and the read depth on the device (vapor_bam_depth_device: bam_depth_kernel; the host reader is vapor_bam_depth).
+extern "C" __attribute__((weak)) int vapor_bam_depth_device(vapor_ctx*, vapor_bam*, int32_t, const int32_t*, const int64_t*, const int32_t*,
+                                                            const uint64_t*, uint64_t*, int32_t*)
+{
+    return bfail(VAPOR_E_ARG, "vapor_bam_depth_device: this build has no device reader");
 }

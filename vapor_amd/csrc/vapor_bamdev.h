@@ -1154,6 +1154,102 @@ __global__ __launch_bounds__(64) void bam_chop_ops_kernel(const uint8_t* __restr
     bam_chop_body<false, false, true>(arena, regs, spans, blk_status, n_regs, kept, n_kept, reg_status, nullptr, opsv);
 }
 
+// Read depth of three consecutive intervals per region (`--depth`; vapor_bam.cpp bam_depth_impl is the host's
+// statement, vapor_amd/depth.py cover the rule): one wavefront a region, bam_chop_body's record walk - the six header words on
+// lanes 0 to 5, the same checks of size, layout, contig and order with the same statuses, the same filter test on the same
+// words - with another question behind it.  Per passing record the operations go 64 a step: one wave_scan64 of the reference
+// advance (M D N = X) gives every lane where its operation starts, the total is carried from tile to tile, and an M, = or X
+// operation adds its overlap with each interval to the lane's three 64-bit sums.  A tile that ends at or behind b3 is the
+// record's last (what follows starts behind every interval); a record at or behind b3 ends the region.  The sums are reduced
+// across the wavefront once, at the end.  No kept-read table, no LDS; a record without operations covers nothing.
+__device__ __forceinline__ unsigned long long depth_overlap(long long s, long long e, long long lo, long long hi)
+{
+    const long long a = s > lo ? s : lo, b = e < hi ? e : hi;
+    return b > a ? (unsigned long long)(b - a) : 0ull;
+}
+
+__global__ __launch_bounds__(64) void bam_depth_kernel(const uint8_t* __restrict__ arena, const DepthRegion* __restrict__ regs,
+                                                      const BamSpan* __restrict__ spans, const int32_t* __restrict__ blk_status, int n_regs,
+                                                      unsigned long long* __restrict__ cov, int32_t* __restrict__ reg_status)
+{
+    const int g = (int)blockIdx.x;
+    if (g >= n_regs) return;
+    const uint32_t lane = threadIdx.x;
+    const DepthRegion R = regs[g];
+    const long long b0 = R.b[0], b1 = R.b[1], b2 = R.b[2], b3 = R.b[3];
+    const uint32_t flt_excl = R.filter & 0xFFFFu, flt_mapq = (R.filter >> 16) & 0xFFu;
+    unsigned long long c0 = 0, c1 = 0, c2 = 0;
+    int st = REG_OK;
+    for (int s = 0; s < R.span_n && st == REG_OK; ++s) {
+        const BamSpan SP = spans[R.span_first + s];
+        int bad = 0;
+        for (uint32_t i = lane; i < SP.blk_n; i += 64) bad |= blk_status[SP.blk_first + i] != 0;
+        if (__any(bad)) { st = REG_BLOCK; break; }
+        uint32_t pos_u = SP.u_begin;
+        // (a record is 36 bytes at least: pos_u grows every turn and the loop ends at u_end)
+        while (pos_u < SP.u_end) {
+            if ((unsigned long long)pos_u + 36ull > SP.u_limit) { st = REG_BEYOND; break; }
+            uint32_t w = 0;
+            if (lane < 6) w = rd32u(arena + pos_u + 4u * lane);
+            const int32_t bs = (int32_t)__shfl(w, 0), ref_id = (int32_t)__shfl(w, 1), pos = (int32_t)__shfl(w, 2);
+            const uint32_t w3 = __shfl(w, 3), w4 = __shfl(w, 4);
+            const int32_t l_seq = (int32_t)__shfl(w, 5);
+            if (bs < 32 || bs > (1 << 29)) { st = REG_MALFORMED; break; }
+            if ((unsigned long long)pos_u + 4ull + (unsigned long long)bs > SP.u_limit) { st = REG_BEYOND; break; }
+            const uint32_t r = pos_u + 4u;
+            pos_u += 4u + (uint32_t)bs;
+            const int l_name = (int)(w3 & 0xFFu), n_cig = (int)(w4 & 0xFFFFu);
+            if (l_seq < 0 || 32ll + l_name + 4ll * n_cig + ((long long)l_seq + 1) / 2 + (long long)l_seq > (long long)bs) { st = REG_MALFORMED; break; }
+            if (ref_id != R.tid || (long long)pos >= b3) {
+                if (ref_id > R.tid || (ref_id == R.tid && (long long)pos >= b3)) break;
+                continue;
+            }
+            // the read filter, DEPTH_EXCLUDE among its flags: both fields came with the record's header
+            if (((w3 >> 8) & 0xFFu) < flt_mapq || ((w4 >> 16) & flt_excl)) continue;
+            const uint32_t cig = r + 32u + (uint32_t)l_name;
+            uint32_t ops = cig;
+            int32_t n_ops = n_cig;
+            if (n_cig == 2) {
+                const uint32_t o0 = rd32u(arena + cig), o1 = rd32u(arena + cig + 4);
+                if ((o0 & 15u) == 4u && (int32_t)(o0 >> 4) == l_seq && (o1 & 15u) == 3u) {
+                    int32_t cnt = 0;
+                    const uint32_t cg = find_cg_dev(arena, cig + 8u + (uint32_t)((l_seq + 1) / 2) + (uint32_t)l_seq, r + (uint32_t)bs, &cnt);
+                    if (cg) { ops = cg; n_ops = cnt; }
+                }
+            }
+            long long cur = (long long)pos;                 // the reference cursor where the tile starts, 0-based
+            for (int32_t t0 = 0; t0 < n_ops && cur < b3; t0 += 64) {
+                const int32_t t = t0 + (int32_t)lane;
+                const uint32_t o = t < n_ops ? rd32u(arena + ops + 4u * (uint32_t)t) : 15u;
+                const uint32_t code = o & 15u;
+                const long long n = (long long)(o >> 4);
+                const bool covers = code == 0u || code == 7u || code == 8u;
+                const long long adv = (covers || code == 2u || code == 3u) ? n : 0;
+                const long long A = wave_scan64(adv, lane);
+                if (covers) {
+                    const long long e = cur + A, sb = e - n;
+                    c0 += depth_overlap(sb, e, b0, b1);
+                    c1 += depth_overlap(sb, e, b1, b2);
+                    c2 += depth_overlap(sb, e, b2, b3);
+                }
+                cur += __shfl(A, 63);
+            }
+        }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        c0 += __shfl_down(c0, (unsigned)d);
+        c1 += __shfl_down(c1, (unsigned)d);
+        c2 += __shfl_down(c2, (unsigned)d);
+    }
+    if (lane == 0) {
+        cov[3 * (size_t)g] = c0;
+        cov[3 * (size_t)g + 1] = c1;
+        cov[3 * (size_t)g + 2] = c2;
+        reg_status[g] = st;
+    }
+}
+
 // One record of a molecule per region (`--dedup-qname`, DESIGN.md 4.18 rule W; vapor_names.h holds the arithmetic, vapor_bam.cpp
 // bam_chop_impl the host's statement): one wavefront a region, right behind the chop kernel on its stream and before
 // bam_haplotag_kernel / bam_select_kernel, launched only for a handle with the option.  BamKept has no record offset, so the

@@ -1161,6 +1161,80 @@ extern "C" int vapor_bam_chop_device_haplotag(vapor_ctx* ctx, vapor_bam* bam, in
     return bam_chop_device_impl(ctx, bam, c, ChopOut{kept_first, sq_addr, q0, miss, status, member, phase_set, tagged}, out);
 }
 
+// Read depth of many regions of an open BAM file (`--depth`; vapor_readplan.h DepthCall): what
+// bam_chop_device_impl does up to the inflate launch - the regions' chunks staged, scanned, laid out in the arena, inflated with
+// CRC - then bam_depth_kernel, one wavefront a region, and one copy back.  The arena is a block of the call: nothing stays on the
+// device, and there is no batch.  The statistics of the chop call (vapor_bam_last_stats) are left alone.
+extern "C" int vapor_bam_depth_device(vapor_ctx* ctx, vapor_bam* bam, int32_t n_regions, const int32_t* tid, const int64_t* bounds,
+                                      const int32_t* chunk_first, const uint64_t* chunks, uint64_t* cov, int32_t* status)
+{
+    using namespace vapor_bamdev;
+    using namespace vapor_readplan;
+    if (!ctx || !bam) return fail(VAPOR_E_ARG, "vapor_bam_depth_device: bad argument");
+    DepthCall call;
+    call.n_regions = n_regions; call.tid = tid; call.bounds = bounds; call.chunk_first = chunk_first; call.chunks = chunks;
+    if (const Refusal r = check_args(call, cov, status)) return fail(r.code, r.msg);
+    const int fd = vapor_bam_fileno(bam);
+    if (fd < 0) return fail(VAPOR_E_ARG, "vapor_bam_depth_device: the file is not open");
+    call.filter_word = depth_filter_word(vapor_bam_filter_word(bam));
+    HIPCHK(hipSetDevice(ctx->device));
+    return guarded("vapor_bam_depth_device", [&]() -> int {
+        SpanPlan plan;
+        if (const Refusal r = plan_spans(call, status, plan)) return fail(r.code, r.msg);
+        std::vector<HostSpan>& spans = plan.spans;
+        CallScope sc(ctx, ctx->stream);
+        InflateStage stage(sc);
+        Block<> d_arena(sc);
+        HIPCHK(stage.begin(plan.stage_bytes));
+        {
+            const int n_thr = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(vapor_bam_threads(bam), 1) * 2, spans.size() / 8 + 1));
+            std::atomic<size_t> next{0};
+            auto work = [&] {
+                for (;;) {
+                    const size_t i = next.fetch_add(1, std::memory_order_relaxed);
+                    if (i >= spans.size()) break;
+                    HostSpan& sp = spans[i];
+                    sp.got = stage.read(fd, sp.stage_off, sp.want, sp.file_off);
+                    try {
+                        vapor_bgzf::scan_span(sp, stage.h_comp);
+                    } catch (const std::exception&) {       // (out of memory for the block list: the region goes the host route)
+                        sp.blks.clear();
+                        sp.bad = true;
+                    }
+                }
+            };
+            if (n_thr <= 1) {
+                work();
+            } else {
+                std::vector<std::thread> th;
+                for (int t = 1; t < n_thr; ++t) th.emplace_back(work);
+                work();
+                for (auto& x : th) x.join();
+            }
+        }
+        DepthLayout L;
+        if (const Refusal r = layout(call, plan, status, L)) return fail(r.code, r.msg);
+        const DepthMeta& M = L.meta;
+        const size_t n_blks = L.blks.size();
+        if (const int rc = stage.alloc(M.bytes, M.bytes)) return rc;
+        HIPCHK(d_arena.ensure(L.arena + 64));
+        uint8_t *const h_meta = stage.h_meta, *const d_meta = stage.d_meta;
+        L.fill(h_meta);
+        const hipStream_t st = sc.st = bam_stream_of(ctx);
+        if (const int rc = stage.run(n_blks, M.in_bytes, M.blks.in(d_meta), M.blk_status.in(d_meta), d_arena, ctx->bam_ev)) return rc;
+        if (n_regions) {
+            hipLaunchKernelGGL(bam_depth_kernel, dim3((unsigned)n_regions), dim3(64), 0, st, d_arena, M.regs.in(d_meta), M.spans.in(d_meta), M.blk_status.in(d_meta),
+                               (int)n_regions, reinterpret_cast<unsigned long long*>(M.cov.in(d_meta)), M.reg_status.in(d_meta));
+            HIPCHK(hipGetLastError());
+        }
+        HIPCHK(hipMemcpyAsync(M.back(h_meta), M.back(d_meta), M.back_bytes(), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        sc.settled();
+        collect(call, M, h_meta, cov, status);
+        return VAPOR_OK;
+    });
+}
+
 // what the context's last vapor_bam_chop_device did: regions, blocks, compressed bytes sent, inflated bytes, the inflate kernel's
 // duration between two events on its stream (ms), the whole call on the host's clock (ms)
 extern "C" int vapor_bam_last_stats(vapor_ctx* ctx, double* out, int32_t n)

@@ -1,5 +1,5 @@
 // vapor_readplan.h - the plan of a device reader call (the planning is host arithmetic without HIP), for
-// vapor_bam_chop_device* and vapor_fasta_windows_device in vapor_hip.hip.  Plain C++17 over vapor_readrec.h and vapor_bgzf.h: which
+// vapor_bam_chop_device*, vapor_bam_depth_device and vapor_fasta_windows_device in vapor_hip.hip.  Plain C++17 over vapor_readrec.h and vapor_bgzf.h: which
 // regions are refused and why, which file ranges are read and where they go in the staging block, where every span, stretch and
 // block lands in the arena, where the tables lie in the call's metadata block, what the host reads back and how that becomes the
 // caller's arrays.  The .hip keeps the reads, the allocations, the copies and the launches.  tools/readplan_check.cpp holds all of
@@ -125,29 +125,25 @@ struct SpanPlan {
 };
 
 // The region rules (a call that passed check_args): status[g] = 0 and the region's spans, or why the host route must do it - a
-// refused region leaves no span behind and takes no staging bytes.
-inline Refusal plan_spans(const ChopCall& c, int32_t* status, SpanPlan& p)
+// refused region leaves no span behind and takes no staging bytes.  plan_spans_of is the walk over the regions' chunks that the
+// chop call and the depth call share; plan_spans states a call's own rules for a region.
+// (region_ok(g, &why): whether region g's own fields let the device take it - `why` is the status of one they do not;
+// `too_big`: the entry's size error, whose "in one call" the Python side reads to halve a group)
+template <typename RegionOk>
+inline Refusal plan_spans_of(int32_t n_regions, const int32_t* chunk_first, const uint64_t* chunks, int32_t* status, SpanPlan& p, const char* too_big,
+                             RegionOk region_ok)
 {
-    const int32_t n_regions = c.n_regions;
     p.spans.clear();
     p.span_first.assign((size_t)n_regions + 1, 0);
     p.stage_bytes = 0;
     for (int32_t g = 0; g < n_regions; ++g) {
         p.span_first[(size_t)g] = (int32_t)p.spans.size();
         status[g] = 0;
-        const int32_t c0 = c.chunk_first[g], c1 = c.chunk_first[g + 1];
-        // (positions are 32-bit in a BAM file; a region that is not is the host route's to refuse)
-        bool ok = c1 >= c0 && (c0 == c1 || c.chunks) && c.start[g] >= 0 && c.end[g] >= c.start[g] && c.end[g] < ((int64_t)1 << 31) && c.flank[g] >= 0 && c.tid[g] >= 0;
+        const int32_t c0 = chunk_first[g], c1 = chunk_first[g + 1];
         int why = REG_MALFORMED;
-        if (ok && c.haplo()) {
-            // a wavefront tallies PHASE_SETS_CAP phase sets; the sites in position order, their indices inside the region's table
-            const int32_t n_ps = c.ps_first[g + 1] - c.ps_first[g];
-            if (n_ps > PHASE_SETS_CAP) { ok = false; why = REG_PHASE_SETS; }
-            for (int32_t i = c.site_first[g]; ok && i < c.site_first[g + 1]; ++i)
-                ok = c.sites[i].ps_idx < n_ps && c.sites[i].pos >= 1 && (i == c.site_first[g] || c.sites[i - 1].pos < c.sites[i].pos);
-        }
+        bool ok = c1 >= c0 && (c0 == c1 || chunks) && region_ok(g, &why);
         for (int32_t k = c0; ok && k < c1; ++k) {
-            const uint64_t cs = c.chunks[2 * (size_t)k], ce = c.chunks[2 * (size_t)k + 1];
+            const uint64_t cs = chunks[2 * (size_t)k], ce = chunks[2 * (size_t)k + 1];
             if (ce < cs || (ce >> 16) - (cs >> 16) > ((uint64_t)1 << 27)) { ok = false; break; }
             HostSpan sp;
             sp.region = g; sp.cs = cs; sp.ce = ce;
@@ -164,8 +160,25 @@ inline Refusal plan_spans(const ChopCall& c, int32_t* status, SpanPlan& p)
         }
     }
     p.span_first[(size_t)n_regions] = (int32_t)p.spans.size();
-    if (p.stage_bytes > ((size_t)3 << 29)) return {VAPOR_E_ARG, "vapor_bam_chop_device: more than 1.5 GB of blocks in one call (use smaller batches)"};
+    if (p.stage_bytes > ((size_t)3 << 29)) return {VAPOR_E_ARG, too_big};
     return {};
+}
+
+inline Refusal plan_spans(const ChopCall& c, int32_t* status, SpanPlan& p)
+{
+    return plan_spans_of(c.n_regions, c.chunk_first, c.chunks, status, p, "vapor_bam_chop_device: more than 1.5 GB of blocks in one call (use smaller batches)",
+                         [&](int32_t g, int* why) {
+        // (positions are 32-bit in a BAM file; a region that is not is the host route's to refuse)
+        bool ok = c.start[g] >= 0 && c.end[g] >= c.start[g] && c.end[g] < ((int64_t)1 << 31) && c.flank[g] >= 0 && c.tid[g] >= 0;
+        if (ok && c.haplo()) {
+            // a wavefront tallies PHASE_SETS_CAP phase sets; the sites in position order, their indices inside the region's table
+            const int32_t n_ps = c.ps_first[g + 1] - c.ps_first[g];
+            if (n_ps > PHASE_SETS_CAP) { ok = false; *why = REG_PHASE_SETS; }
+            for (int32_t i = c.site_first[g]; ok && i < c.site_first[g + 1]; ++i)
+                ok = c.sites[i].ps_idx < n_ps && c.sites[i].pos >= 1 && (i == c.site_first[g] || c.sites[i - 1].pos < c.sites[i].pos);
+        }
+        return ok;
+    });
 }
 
 struct ChopLayout;
@@ -238,39 +251,51 @@ struct ChopLayout {
 };
 
 // After the scan: a region with a span that did not scan gets REG_MALFORMED; the spans of the others one after the other in the
-// arena, their blocks behind each other in the block table.
-inline Refusal layout(const ChopCall& c, const SpanPlan& p, int32_t* status, ChopLayout& L)
+// arena, their blocks behind each other in the block table.  layout_of is that walk for the chop call and the depth call alike.
+// (regs: the call's region records, any struct with span_first and span_n; set(R, g) writes the rest of region g's)
+template <typename Region, typename SetRegion>
+inline Refusal layout_of(int32_t n_regions, const SpanPlan& p, int32_t* status, std::vector<BgzfBlk>& blks, std::vector<BamSpan>& spans,
+                         std::vector<Region>& regs, size_t* arena_out, const char* too_big, SetRegion set)
 {
-    const int32_t n_regions = c.n_regions;
     for (const HostSpan& sp : p.spans)
         if (sp.bad) status[sp.region] = REG_MALFORMED;
-    L.blks.clear();
-    L.spans.clear();
-    L.regs.assign((size_t)std::max(n_regions, 1), BamRegion());
+    blks.clear();
+    spans.clear();
+    regs.assign((size_t)std::max(n_regions, 1), Region());
     size_t arena = 0;
     for (int32_t g = 0; g < n_regions; ++g) {
-        BamRegion& R = L.regs[(size_t)g];
-        R.start = c.start[g]; R.end = c.end[g]; R.flank = c.flank[g]; R.tid = c.tid[g]; R.pad = (int32_t)c.filter_word;
-        R.span_first = (int32_t)L.spans.size();
+        Region& R = regs[(size_t)g];
+        set(R, g);
+        R.span_first = (int32_t)spans.size();
         R.span_n = 0;
         if (status[g]) continue;
         for (int32_t si = p.span_first[(size_t)g]; si < p.span_first[(size_t)g + 1]; ++si) {
             const HostSpan& sp = p.spans[(size_t)si];
-            if (arena + sp.u_total + 64 > ((size_t)1 << 31)) return {VAPOR_E_ARG, "vapor_bam_chop_device: more than 2 GB of block data in one call (use smaller batches)"};
+            if (arena + sp.u_total + 64 > ((size_t)1 << 31)) return {VAPOR_E_ARG, too_big};
             BamSpan d;
             d.u_begin = (uint32_t)arena + (uint32_t)sp.u_begin;
             d.u_end = (uint32_t)arena + (uint32_t)sp.u_end;
             d.u_limit = (uint32_t)arena + (uint32_t)sp.u_total;
-            d.blk_first = (uint32_t)L.blks.size();
+            d.blk_first = (uint32_t)blks.size();
             d.blk_n = (uint32_t)sp.blks.size();
             d.pad = 0;
-            for (const vapor_bgzf::Block& k : sp.blks) L.blks.push_back(bgzf_blk(sp.stage_off, k, arena));
-            L.spans.push_back(d);
+            for (const vapor_bgzf::Block& k : sp.blks) blks.push_back(bgzf_blk(sp.stage_off, k, arena));
+            spans.push_back(d);
             ++R.span_n;
             arena += pad64((size_t)sp.u_total);
         }
     }
-    L.arena = arena;
+    *arena_out = arena;
+    return {};
+}
+
+inline Refusal layout(const ChopCall& c, const SpanPlan& p, int32_t* status, ChopLayout& L)
+{
+    if (const Refusal r = layout_of(c.n_regions, p, status, L.blks, L.spans, L.regs, &L.arena,
+                                    "vapor_bam_chop_device: more than 2 GB of block data in one call (use smaller batches)", [&](BamRegion& R, int32_t g) {
+            R.start = c.start[g]; R.end = c.end[g]; R.flank = c.flank[g]; R.tid = c.tid[g]; R.pad = (int32_t)c.filter_word;
+        }))
+        return r;
     L.meta = ChopMeta(c, L.blks.size(), L.spans.size());
     return {};
 }
@@ -342,6 +367,109 @@ inline void collect(const ChopCall& c, const ChopMeta& M, const uint8_t* h_meta,
         }
     }
     o.kept_first[n_regions] = w;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// vapor_bam_depth_device (`--depth`)
+// ------------------------------------------------------------------------------------------------------------------------------
+struct DepthCall {
+    int32_t n_regions = 0;
+    const int32_t* tid = nullptr;
+    const int64_t* bounds = nullptr;       // four a region: b0 <= b1 <= b2 <= b3, 0-based
+    const int32_t* chunk_first = nullptr;
+    const uint64_t* chunks = nullptr;
+    uint32_t filter_word = 0;              // the handle's read filter with DEPTH_EXCLUDE among its flags (depth_filter_word)
+};
+
+// the handle's filter word as a depth region carries it: unmapped, secondary, QC-fail and duplicate records never count
+inline uint32_t depth_filter_word(uint32_t handle_word) { return handle_word | DEPTH_EXCLUDE; }
+
+inline Refusal check_args(const DepthCall& c, const uint64_t* cov, const int32_t* status)
+{
+    if (c.n_regions < 0 || (c.n_regions && (!c.tid || !c.bounds || !c.chunk_first || !cov || !status)))
+        return {VAPOR_E_ARG, "vapor_bam_depth_device: bad argument"};
+    return {};
+}
+
+// The region rules: the bounds ascend from 0, b3 is a BAM position, the contig is one - else REG_MALFORMED and the host route's
+// to refuse.  The spans and the staging block as plan_spans makes them.
+inline Refusal plan_spans(const DepthCall& c, int32_t* status, SpanPlan& p)
+{
+    return plan_spans_of(c.n_regions, c.chunk_first, c.chunks, status, p, "vapor_bam_depth_device: more than 1.5 GB of blocks in one call (use smaller batches)",
+                         [&](int32_t g, int*) {
+        const int64_t* b = c.bounds + 4 * (size_t)g;
+        return b[0] >= 0 && b[1] >= b[0] && b[2] >= b[1] && b[3] >= b[2] && b[3] < ((int64_t)1 << 31) && c.tid[g] >= 0;
+    });
+}
+
+// Where each table of a depth call lies in its metadata block: blocks, spans and regions go in; block status, the three sums a
+// region and the region status come back.
+struct DepthMeta {
+    Table<BgzfBlk> blks;
+    Table<BamSpan> spans;
+    Table<DepthRegion> regs;
+    Table<int32_t> blk_status;
+    Table<uint64_t> cov;                   // three a region
+    Table<int32_t> reg_status;
+    size_t in_bytes = 0, bytes = 0;
+
+    DepthMeta() = default;
+    DepthMeta(int32_t n_regions, size_t n_blks, size_t n_spans)
+    {
+        const size_t nr = (size_t)std::max(n_regions, 1);
+        Carve m;
+        m.take(blks, std::max<size_t>(n_blks, 1));
+        m.take(spans, std::max<size_t>(n_spans, 1));
+        m.take(regs, nr);
+        in_bytes = m.off;
+        m.take(blk_status, std::max<size_t>(n_blks, 1));
+        m.take(cov, 3 * nr);
+        m.take(reg_status, nr);
+        bytes = m.off;
+    }
+    size_t back_bytes() const { return bytes - blk_status.off; }       // the host's block is the device's: [blk_status.off, bytes) comes back
+    template <typename B> B* back(B* block) const { return block + blk_status.off; }
+};
+
+struct DepthLayout {
+    std::vector<BgzfBlk> blks;
+    std::vector<BamSpan> spans;
+    std::vector<DepthRegion> regs;
+    size_t arena = 0;
+    DepthMeta meta;
+    void fill(uint8_t* h_meta) const
+    {
+        if (!blks.empty()) memcpy(meta.blks.in(h_meta), blks.data(), sizeof(BgzfBlk) * blks.size());
+        if (!spans.empty()) memcpy(meta.spans.in(h_meta), spans.data(), sizeof(BamSpan) * spans.size());
+        memcpy(meta.regs.in(h_meta), regs.data(), sizeof(DepthRegion) * regs.size());
+    }
+};
+
+inline Refusal layout(const DepthCall& c, const SpanPlan& p, int32_t* status, DepthLayout& L)
+{
+    if (const Refusal r = layout_of(c.n_regions, p, status, L.blks, L.spans, L.regs, &L.arena,
+                                    "vapor_bam_depth_device: more than 2 GB of block data in one call (use smaller batches)", [&](DepthRegion& R, int32_t g) {
+            for (int k = 0; k < 4; ++k) R.b[k] = c.bounds[4 * (size_t)g + (size_t)k];
+            R.tid = c.tid[g]; R.filter = c.filter_word;
+        }))
+        return r;
+    L.meta = DepthMeta(c.n_regions, L.blks.size(), L.spans.size());
+    return {};
+}
+
+// The read-back block into the caller's arrays: a region the host refused keeps its status and zeros, one the device refused
+// takes the device's status (its sums are then the host route's to make), the others their three sums.
+inline void collect(const DepthCall& c, const DepthMeta& M, const uint8_t* h_meta, uint64_t* cov, int32_t* status)
+{
+    const uint64_t* dc = M.cov.in(h_meta);
+    const int32_t* rst = M.reg_status.in(h_meta);
+    for (int32_t g = 0; g < c.n_regions; ++g) {
+        uint64_t* o = cov + 3 * (size_t)g;
+        o[0] = o[1] = o[2] = 0;
+        if (status[g]) continue;
+        if (rst[g] != REG_OK) { status[g] = rst[g]; continue; }
+        for (int k = 0; k < 3; ++k) o[k] = dc[3 * (size_t)g + (size_t)k];
+    }
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------

@@ -26,11 +26,17 @@ struct BamRegion {        // `samtools view bam tid:start-end` + chop_pacbio_rea
     int32_t tid, span_first, span_n;
     int32_t pad;          // the read filter: exclude_flags | min_mapq << 16; 0 filters nothing
 };
+struct DepthRegion {      // `--depth`: three consecutive intervals [b0, b1) [b1, b2) [b2, b3) of a contig, 0-based half-open
+    int64_t b[4];
+    int32_t tid, span_first, span_n;
+    uint32_t filter;      // the read filter as BamRegion::pad carries it, 0x704 already among the excluded flags
+};
 struct BamKept {          // a read the reference keeps: its packed bases at arena + sq_off, from base q0 on, miss_bp
     uint32_t sq_off;
     int32_t q0, miss, l_seq;
 };
-constexpr int KEPT_CAP = 256;      // kept reads a region's slot holds (minimize_pacbio_read_list keeps 20 of them)
+constexpr uint32_t DEPTH_EXCLUDE = 0x704u;   // what never counts towards depth: unmapped, secondary, QC-fail, duplicate (`samtools depth`)
+constexpr int KEPT_CAP = 256;     // kept reads a region's slot holds (minimize_pacbio_read_list keeps 20 of them)
 // status of a region: 0, or why the host route must do it
 constexpr int REG_OK = 0, REG_BEYOND = 1, REG_MALFORMED = 2, REG_NO_CIGAR = 3, REG_KEPT_FULL = 4, REG_BLOCK = 5, REG_NEG_Q0 = 6, REG_NO_SEQ = 7;
 constexpr int REG_PHASE_SETS = 8;  // (`--phase-vcf`) more phase sets among the region's sites than a wavefront tallies: set by the host, before anything is sent
@@ -68,7 +74,7 @@ struct BamSiteRange {     // a region's sites (in position order) and its table 
 };
 constexpr int PHASE_SETS_CAP = 64;     // phase sets a wavefront tallies: lane p holds the two counts of phase set p
 
-static_assert(sizeof(BgzfBlk) == 24 && sizeof(BamSpan) == 24 && sizeof(BamRegion) == 40 && sizeof(BamKept) == 16 && sizeof(BamTag) == 16 &&
+static_assert(sizeof(BgzfBlk) == 24 && sizeof(BamSpan) == 24 && sizeof(BamRegion) == 40 && sizeof(DepthRegion) == 48 && sizeof(BamKept) == 16 && sizeof(BamTag) == 16 &&
               sizeof(BamPick) == 16 && sizeof(BamPhase) == 16 && sizeof(BamOps) == 16 && sizeof(BamSite) == 8 && sizeof(BamSiteRange) == 16,
               "the kernels index arrays of these, and the metadata block of a call is carved by their sizes");
 

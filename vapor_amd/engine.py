@@ -479,6 +479,26 @@ class Engine:
             batch.name_keys = batch.read_name_keys(w)
         return kept_first, addr[:w], q0[:w], miss[:w], status[:n], batch
 
+    def bam_depth_device(self, native_bam, tids, bounds, chunk_first, chunks):
+        """vapor_bam_depth_device (`--depth`): the read depth of many depth regions of an open BAM file on the
+        device.  bounds: (n, 4) int64, chunk_first / chunks as in bam_chop_device.  Returns (cov, status): cov (n, 3) uint64,
+        status per region - 0, or the code of a region that is the host route's (its sums are 0 then).  Nothing stays on the
+        device.  NotImplementedError where the library has no such entry."""
+        fn = Engine._wide_entry("vapor_bam_depth_device", "device depth reader")
+        n = len(tids)
+        tids = np.ascontiguousarray(tids, dtype=np.int32)
+        bounds = np.ascontiguousarray(bounds, dtype=np.int64).reshape(-1)
+        chunk_first = np.ascontiguousarray(chunk_first, dtype=np.int32)
+        chunks = np.ascontiguousarray(chunks, dtype=np.uint64).reshape(-1)
+        if len(bounds) != 4 * n or len(chunk_first) != n + 1 or len(chunks) != 2 * int(chunk_first[-1]):
+            raise ValueError("bounds / chunk_first / chunks do not describe %d regions" % n)
+        cov = np.zeros(3 * max(n, 1), dtype=np.uint64)
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        vp = ctypes.c_void_p
+        L.check(fn(self._ctx, native_bam, n, tids.ctypes.data_as(vp), bounds.ctypes.data_as(vp), chunk_first.ctypes.data_as(vp),
+                   chunks.ctypes.data_as(vp) if len(chunks) else None, cov.ctypes.data_as(vp), status.ctypes.data_as(vp)))
+        return cov[:3 * n].reshape(n, 3), status[:n]
+
     def bam_last_stats(self) -> dict:
         """What this engine's last bam_chop_device did (vapor_bam_last_stats)."""
         out = np.zeros(7, dtype=np.float64)

@@ -56,6 +56,27 @@ class SamtoolsCLI:
         with open(ref + ".fai") as f:
             return f.read().splitlines()
 
+    # `--depth`: the length every bound of a depth region is clipped to, and the regions' sums
+    def contig_length(self, bam: str, ref: str, chrom: str) -> int:
+        """From the reference's .fai; 0 for a contig it does not list."""
+        cache = self.__dict__.setdefault("_fai_len", {})
+        if ref not in cache:
+            cache[ref] = {f[0]: int(f[1]) for f in (ln.split("\t") for ln in self.fai_lines(ref)) if len(f) > 1}
+        return cache[ref].get(chrom, 0)
+
+    def depth_many(self, engine, bam: str, chroms, bounds):
+        """[cov0, cov1, cov2] per depth region (chroms[g], bounds[g] = (b0, b1, b2, b3)): depth.cover over POS and CIGAR of the
+        alignment lines of `view`, filtered where they are read (_sam_fields) with depth.EXCLUDE among the excluded flags."""
+        from . import depth
+        out = []
+        for chrom, b in zip(chroms, bounds):
+            if not b[3] > b[0]:
+                out.append([0, 0, 0])
+                continue
+            recs = [(int(f[3]), depth.parse_cigar(f[5])) for f in _sam_fields(self, bam, chrom, int(b[0]) + 1, int(b[3]), depth.EXCLUDE)]
+            out.append(depth.cover(recs, b))
+        return out
+
 
 class FaiFasta:
     """In-process `samtools faidx ref chrom:start-end` through the .fai index (no process per locus)."""
@@ -585,6 +606,98 @@ class InProcessBam(SamtoolsHybrid):
             return kf, cat(1, np.uint64), cat(2, np.int64), cat(3, np.int64), cat(4, np.int32), batches, cat(5, np.uint32), cat(6, np.int64), cat(7, np.int32)
         return kf, cat(1, np.uint64), cat(2, np.int64), cat(3, np.int64), cat(4, np.int32), batches
 
+    def contig_length(self, bam: str, ref: str, chrom: str) -> int:
+        """(`--depth`) l_ref of the BAM header; 0 for a contig the file does not have."""
+        b = self._open(bam)
+        t = b.tid.get(chrom)
+        return int(b.refs[t][1]) if t is not None else 0
+
+    def depth_many(self, engine, bam: str, chroms, bounds):
+        """[cov0, cov1, cov2] per depth region (`--depth`; chroms[g], bounds[g] = (b0, b1, b2, b3)) of a BAM
+        file.  The regions go to the device in groups by compressed size, like chop_many_device's, a group the library refuses
+        for its size ("in one call") in halves (vapor_bam_depth_device: bam_depth_kernel, one wavefront a region); a region the
+        device hands back with a status, and every region with VAPOR_BAM_DEVICE=0 or without a device reader, goes to the native
+        host reader (vapor_bam_depth).  A library without the entries, one without the read filter the file carries, or
+        VAPOR_BAM_NATIVE=0: the Python statement, depth.cover over fetch_raw with depth.EXCLUDE added to the excluded flags.
+        `engine`: an Engine, or None for the one of pipeline.get_engine() when the device is asked."""
+        import numpy as np
+        from . import _lib, depth
+        n = len(chroms)
+        b = self._open(bam)
+        bounds = np.ascontiguousarray(bounds, dtype=np.int64).reshape(n, 4)
+        out = [[0, 0, 0] for _ in range(n)]
+        todo = [g for g in range(n) if chroms[g] in b.tid and bounds[g][3] > bounds[g][0]]
+        lib = _lib.load()
+        if _env_is(b"VAPOR_BAM_NATIVE", b"0") or not hasattr(lib, "vapor_bam_depth") or not b.native_filter_ok():
+            for g in todo:
+                recs = [(r[1], r[2]) for r in b.fetch_raw(chroms[g], int(bounds[g][0]) + 1, int(bounds[g][3]), exclude_more=depth.EXCLUDE)]
+                out[g] = depth.cover(recs, bounds[g])
+            return out
+        tid_of, index_chunks = b.tid, b.index.chunks
+        chunks_of = {g: index_chunks(tid_of[chroms[g]], int(bounds[g][0]), int(bounds[g][3])) for g in todo}
+        host = todo
+        flags = lib.vapor_build_flags() or b""
+        if (todo and not _env_is(b"VAPOR_BAM_DEVICE", b"0") and hasattr(lib, "vapor_bam_depth_device")
+                and b"cpu-twin" not in flags.split(b",")):
+            if engine is None:
+                from . import pipeline
+                engine = pipeline.get_engine()
+        else:
+            engine = None
+        if engine is not None and hasattr(engine, "bam_depth_device"):
+            host = []
+            m = len(todo)
+            tids = np.asarray([tid_of[chroms[g]] for g in todo], dtype=np.int32)
+            chunk_first = np.zeros(m + 1, dtype=np.int32)
+            flat = []
+            for k, g in enumerate(todo):
+                for c in chunks_of[g]:
+                    flat.append(c[0])
+                    flat.append(c[1])
+                chunk_first[k + 1] = len(flat) >> 1
+            flat_a = np.asarray(flat, dtype=np.uint64).reshape(-1, 2)
+            comp = np.zeros(m, dtype=np.int64)
+            if len(flat_a):
+                per_chunk = ((flat_a[:, 1] >> np.uint64(16)) - (flat_a[:, 0] >> np.uint64(16))).astype(np.int64) + 65600
+                np.add.at(comp, np.repeat(np.arange(m), np.diff(chunk_first)), per_chunk)
+            cap = int(os.environ.get("VAPOR_BAM_DEVICE_BATCH_MB", "192")) << 20
+            groups = []
+            a = 0
+            while a < m:
+                e, tot = a, 0
+                while e < m and (e == a or tot + int(comp[e]) <= cap):
+                    tot += int(comp[e])
+                    e += 1
+                groups.append((a, e))
+                a = e
+            bt = bounds[todo]
+            tl = b._take_handle(lib)
+            try:
+                while groups:
+                    a, e = groups.pop(0)
+                    c0, c1 = int(chunk_first[a]), int(chunk_first[e])
+                    try:
+                        cov, status = engine.bam_depth_device(tl["native"], tids[a:e], bt[a:e], chunk_first[a:e + 1] - c0, flat_a[c0:c1].reshape(-1))
+                    except _lib.VaporHipError as err:
+                        if "in one call" in str(err) and e - a >= 2:
+                            groups[:0] = [(a, (a + e) // 2), ((a + e) // 2, e)]
+                            continue
+                        if "in one call" in str(err):
+                            host.append(todo[a])          # (one region whose blocks alone are more than a call takes)
+                            continue
+                        raise
+                    for k in range(a, e):
+                        if status[k - a]:
+                            host.append(todo[k])
+                        else:
+                            out[todo[k]] = [int(x) for x in cov[k - a]]
+            finally:
+                with b._lock:
+                    b._free.append(tl)
+        for g in host:
+            out[g] = b.depth_native(tid_of[chroms[g]], bounds[g], chunks_of[g])
+        return out
+
     def isfile(self, path: str) -> bool:
         # (bam_in_decide, SF:69-89, asks once per locus: a file this reader holds open is a file - no stat, and no release of
         # the interpreter lock around one, for the loci after the first)
@@ -921,6 +1034,33 @@ class MemorySamtools:
     def isfile(self, path: str) -> bool:
         return True
 
+    def contig_length(self, bam: str, ref: str, chrom: str) -> int:
+        """(`--depth`) the world's contig; 0 for one it does not have."""
+        return len(self.world.contigs[chrom]) if chrom in self.world.contigs else 0
+
+    def depth_many(self, engine, bam: str, chroms, bounds):
+        """[cov0, cov1, cov2] per depth region (`--depth`) from the world's records that pass the read filter
+        with depth.EXCLUDE among its flags: depth.cover over (POS, operations), every CIGAR text parsed once per record list."""
+        from . import depth
+        from .bamio import record_passes
+        q, f = self.read_filter
+        f |= depth.EXCLUDE
+        cache = self.__dict__.setdefault("_depth_cache", {})
+        out = []
+        for chrom, b in zip(chroms, bounds):
+            recs = self.world.reads.get(chrom, ())
+            got = cache.get(id(recs))
+            if got is None or got[0] is not recs or got[1] != len(recs):
+                got = (recs, len(recs), [depth.parse_cigar(r.cigar) for r in recs])
+                if getattr(self.world, "cache_ok", True):
+                    if len(cache) > 200000:
+                        cache.clear()
+                    cache[id(recs)] = got
+            b0, b3 = int(b[0]), int(b[3])
+            out.append(depth.cover([(r.pos, ops) for r, ops in zip(recs, got[2])
+                                    if b0 < b3 and r.pos - 1 < b3 and record_passes(r.mapq, r.flag, q, f)], b))
+        return out
+
     def fai_lines(self, ref: str) -> Iterable[str]:
         rows = self.world.fai_rows() if hasattr(self.world, "fai_rows") else [(k, len(v)) for k, v in self.world.contigs.items()]
         return ["%s\t%d\t0\t60\t61" % (k, n) for k, n in rows]
@@ -1127,11 +1267,13 @@ def cigar2alignstart_by_pos(cigar: str, align_start: int, start: int, end: int):
     return [int(_cigar_out[0]), int(_cigar_out[1])]
 
 
-def _sam_fields(be, bam, chrom, start, end):
+def _sam_fields(be, bam, chrom, start, end, exclude_more=0):
     """The fields of every alignment line of the backend's `view bam chrom:start-end` that passes the backend's read filter
-    (FLAG is column 2, MAPQ column 5) - the one place SAM text is filtered."""
+    (FLAG is column 2, MAPQ column 5) - the one place SAM text is filtered.  exclude_more (`--depth`): flags
+    excluded beside the filter's."""
     from .bamio import record_passes
     min_mapq, exclude = getattr(be, "read_filter", (0, 0))
+    exclude |= exclude_more
     for line in be.view_lines(bam, "%s:%d-%d" % (chrom, start, end)):
         f = line.strip().split()
         if not f or f[0] == "@":

@@ -672,6 +672,100 @@ def make_junction_world(seed: int, svtypes: Sequence[str] = ("DEL", "INV", "TAND
     return w
 
 
+DEPTH_SPECS = (("DEL", 600, "hom"), ("DEL", 1500, "het"), ("TANDUP", 900, "het"), ("TANDUP", 1200, "hom"), ("INV", 700, "het"),
+               ("DEL", 24000, "het"), ("TANDUP", 22000, "het"))
+
+
+def _noisy(rng, seg: str, errors) -> Tuple[str, str]:
+    """`seg` read with substitutions, insertions and deletions at the rates `errors` = (sub, ins, del): (read, CIGAR with M, X, I
+    and D).  The first and the last base are matches, so that the piece starts and ends on an aligned base."""
+    sub, ins, dele = errors
+    n = len(seg)
+    b = np.frombuffer(seg.encode("ascii"), dtype=np.uint8)
+    u = rng.random(n)
+    kind = np.where(u < dele, ord("D"), np.where(u < dele + sub, ord("X"), ord("M"))).astype(np.uint8)
+    is_ins = rng.random(n) < ins
+    kind[0] = kind[-1] = ord("M")
+    is_ins[-1] = False
+    code = np.full(256, 0, dtype=np.uint8)
+    code[_ACGT] = np.arange(4, dtype=np.uint8)
+    base = np.where(kind == ord("X"), _ACGT[(code[b] + rng.integers(1, 4, size=n).astype(np.uint8)) & 3], b)
+    ins_b = _ACGT[rng.integers(0, 4, size=n)]
+    keep = kind != ord("D")
+    cnt = keep.astype(np.int64) + is_ins.astype(np.int64)
+    off = np.concatenate(([0], np.cumsum(cnt)))
+    out = np.empty(off[-1], dtype=np.uint8)
+    out[off[:-1][keep]] = base[keep]
+    out[(off[:-1] + keep.astype(np.int64))[is_ins]] = ins_b[is_ins]
+    ooff = np.concatenate(([0], np.cumsum(1 + is_ins.astype(np.int64))))
+    ops = np.empty(ooff[-1], dtype=np.uint8)
+    ops[ooff[:-1]] = kind
+    ops[(ooff[:-1] + 1)[is_ins]] = ord("I")
+    return out.tobytes().decode("ascii"), _rle_cigar(ops)
+
+
+def make_depth_world(seed: int, specs: Sequence[Tuple[str, int, str]] = DEPTH_SPECS, layers: int = 4, read_len: int = 1000,
+                     margin: int = 3000, errors: Optional[Tuple[float, float, float]] = None, short_del: int = 2000,
+                     chrom_prefix: str = "d") -> SynthWorld:
+    """A world whose read DEPTH means something (`--depth`; the other worlds only hold reads that start just
+    left of a window).  Per spec (svtype, span L, 'hom' | 'het') a contig of margin + L + margin bases with the event on bases
+    [margin + 1, margin + L] (the BED columns), and two haplotypes, each TILED with reads: `layers` layers a haplotype, layer k
+    cut every read_len bases from offset k * read_len // layers, so that every base of a haplotype is in exactly `layers`
+    reads and a diploid contig has depth 2 * layers.  A 'het' locus has one reference and one alt haplotype, a 'hom' one two
+    alt haplotypes; an INV locus is read from two reference haplotypes.  The alt haplotype's reads are aligned as a mapper
+    reports them: a read across a deletion of at most short_del bases carries it as a D; across a longer deletion, or across
+    the junction of a tandem duplication (the end of the first copy, where the second starts), its longest piece is the primary
+    record with the rest soft-clipped and every other piece a supplementary record (0x800) soft-clipped likewise; the second
+    copy of a duplicated block aligns where the first does, which doubles the block's coverage.  Without errors every piece is
+    one M and the depth of every base is known in closed form: outside the event 2 * layers; inside a DEL layers ('het') or 0
+    ('hom'); inside a TANDUP 3 * layers ('het') or 4 * layers ('hom').  errors = (sub, ins, del): read errors as X, I and D."""
+    rng = np.random.default_rng(seed)
+    w = SynthWorld()
+    for li, (t, span, zyg) in enumerate(specs):
+        c = "%s%d" % (chrom_prefix, li + 1)
+        s0, e0 = margin, margin + int(span)             # the event, 0-based half-open
+        n = e0 + margin
+        ref = w.contigs[c] = random_dna(rng, n)
+        if t == "DEL":
+            alt = [(0, s0), (e0, n)]
+        elif t in ("TANDUP", "DUP"):
+            t = "TANDUP"
+            alt = [(0, e0), (s0, n)]
+        elif t == "INV":
+            alt = [(0, n)]
+        else:
+            raise ValueError(t)
+        haps = [alt, alt] if zyg == "hom" else [[(0, n)], alt]
+        recs = w.reads.setdefault(c, [])
+        for h, segs in enumerate(haps):
+            # the haplotype's segments in its own coordinates: (hap start, hap end, ref start)
+            at, table = 0, []
+            for lo, hi in segs:
+                table.append((at, at + hi - lo, lo))
+                at += hi - lo
+            m = at
+            for k in range(layers):
+                cuts = sorted({0, m} | set(range((k * read_len) // layers, m, read_len)))
+                for ri, (a, z) in enumerate(zip(cuts[:-1], cuts[1:])):
+                    pieces = [(max(a, p0) - p0 + r0, min(z, p1) - p0 + r0) for p0, p1, r0 in table if min(z, p1) > max(a, p0)]
+                    made = [(_noisy(rng, ref[lo:hi], errors) if errors else (ref[lo:hi], "%dM" % (hi - lo))) for lo, hi in pieces]
+                    qname = "%s_h%d_l%d_r%d" % (c, h, k, ri)
+                    seq = "".join(x[0] for x in made)
+                    if len(pieces) == 2 and 0 < pieces[1][0] - pieces[0][1] <= short_del:
+                        gap = pieces[1][0] - pieces[0][1]
+                        recs.append(SamRecord(qname, c, pieces[0][0] + 1, made[0][1] + "%dD" % gap + made[1][1], seq, pieces[1][1] - pieces[0][0]))
+                        continue
+                    main = max(range(len(pieces)), key=lambda i: (pieces[i][1] - pieces[i][0], -i))
+                    for i, (lo, hi) in enumerate(pieces):
+                        left = sum(len(x[0]) for x in made[:i])
+                        right = sum(len(x[0]) for x in made[i + 1:])
+                        cg = ("%dS" % left if left else "") + made[i][1] + ("%dS" % right if right else "")
+                        recs.append(SamRecord(qname, c, lo + 1, cg, seq, hi - lo, flag=0 if i == main else 0x800))
+        recs.sort(key=lambda r: r.pos)
+        w.loci.append(Locus(c, t, s0 + 1, e0, "dp%d" % (li + 1)))
+    return w
+
+
 def mirror_world(world: SynthWorld) -> SynthWorld:
     """M(W): the world as its reverse-complemented contigs hold it (x -> L + 1 - x on a contig of L bases; `--both-ends`,
     DESIGN.md 4.14).  Contigs: their reverse complement (seqio.rc_read: nothing is dropped).  Records: seqio.mirror_records -
