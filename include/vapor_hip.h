@@ -501,6 +501,26 @@ int vapor_bam_chop_device_right(vapor_ctx* ctx, vapor_bam* bam, int32_t n_region
 int vapor_bam_depth(vapor_bam* bam, int32_t tid, const int64_t* bounds, int32_t n_chunks, const uint64_t* chunks, uint64_t* cov);
 int vapor_bam_depth_device(vapor_ctx* ctx, vapor_bam* bam, int32_t n_regions, const int32_t* tid, const int64_t* bounds,
                            const int32_t* chunk_first, const uint64_t* chunks, uint64_t* cov, int32_t* status);
+/*
+ * Split-read and CIGAR evidence (`--signatures`; not in the reference).  A signature region is a contig and nine
+ * fields: w0, w3 (the walk window [w0, w3), 0-based), x0, x1 (the two targets), tol (0..255), min_clip, nmin, nmax, mask.  A
+ * record counts as for vapor_bam_depth (the handle's filter with 0x704 among the excluded flags; vapor_bam_set_dedup has no
+ * effect; a CG:B,I array replaces its stand-in; a record without operations has no event).  Its events: LCLIP at POS when the S/H
+ * operations among its first two sum to min_clip or more, RCLIP at its reference end likewise from its last two (a record of at
+ * most two operations, all S/H, has neither); GAP(a, n) per D or N and INSOP(a, n) per I of length n at reference cursor a.
+ * mask bit 0: LCLIP at x0, 1: RCLIP at x0, 2: LCLIP at x1, 3: RCLIP at x1 (|coordinate - x| <= tol), 4: GAP (nmin <= n <= nmax,
+ * |a - x0| <= tol, |a + n - x1| <= tol), 5: INSOP (nmin <= n <= nmax, x0 - tol <= a <= x1 + tol).  out, ten a region: the six
+ * counts, then offset and count of the mode of each target's histogram of offsets (largest count, then smallest |offset|, then
+ * the negative one; 0 and 0 without an event).
+ * vapor_bam_signature: one region on the host, `chunks` its .bai chunks as in vapor_bam_depth; errors as there.  VAPOR_E_ARG for
+ * w0 < 0, w0 > w3, w3 >= 2^31, tol outside 0..255, nmin > nmax or tid < 0.
+ * vapor_bam_signature_device: n_regions regions in one call as vapor_bam_depth_device takes them (regions: nine a region, out:
+ * ten a region) - bam_signature_kernel, one wavefront a region.  status[g] = 0, or a positive code of vapor_bam_chop_device's
+ * where the region is the host route's (its words are 0 then).  Nothing stays on the device.
+ */
+int vapor_bam_signature(vapor_bam* bam, int32_t tid, const int64_t* fields, int32_t n_chunks, const uint64_t* chunks, int64_t* out);
+int vapor_bam_signature_device(vapor_ctx* ctx, vapor_bam* bam, int32_t n_regions, const int32_t* tid, const int64_t* regions,
+                               const int32_t* chunk_first, const uint64_t* chunks, int64_t* out, int32_t* status);
 /* what the context's last vapor_bam_chop_device (or _tagged) did, for measurement (bench.py): out[0..6] = regions, BGZF blocks,
  * compressed bytes sent over the link, inflated bytes, the inflate kernel's duration between two events on its stream (ms), the
  * whole call (ms), bytes of kept reads and statuses copied back from the device */

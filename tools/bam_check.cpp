@@ -7,6 +7,9 @@
 // the right-anchored and the tagged reader walk the file behind the plain one; without them nothing changes.
 // A last argument `depth` adds a depth pass (vapor_bam_depth) over every record of the file behind the others:
 // the intervals [0, start) [start, end) [end, 2^31 - 1) of the contig, under the handle's filter.
+// A last argument `sig` adds, in place of the depth pass, a signature pass (vapor_bam_signature) over every record: a
+// region per contig from 0 to the one behind `tid`, its window [0, 2^31 - 1), the targets start and end, tolerance 50, minimum
+// clip 30, every length and every event kind, under the handle's filter.
 // tests/test_bamio.py builds it and runs it over the damaged files of its other tests and a few hundred randomly damaged ones.
 #include "vapor_bam.cpp"
 #include <cstdio>
@@ -15,8 +18,9 @@
 int main(int argc, char** argv)
 {
     const bool depth = argc > 7 && !strcmp(argv[argc - 1], "depth");
-    if (depth) --argc;
-    if (argc < 7) { fprintf(stderr, "usage: bam_check file.bam first_voffset tid start end flank [threads [min_mapq exclude_flags]] [depth]\n"); return 2; }
+    const bool sig = argc > 7 && !strcmp(argv[argc - 1], "sig");
+    if (depth || sig) --argc;
+    if (argc < 7) { fprintf(stderr, "usage: bam_check file.bam first_voffset tid start end flank [threads [min_mapq exclude_flags]] [depth | sig]\n"); return 2; }
     vapor_bam* b = nullptr;
     if (vapor_bam_open(argv[1], &b) != 0) { printf("open: %s\n", vapor_bam_last_error()); return 0; }
     if (argc > 7) vapor_bam_set_threads(b, atoi(argv[7]));
@@ -76,6 +80,16 @@ int main(int argc, char** argv)
         rc = vapor_bam_depth(b, tid, bounds, 1, chunk, cov);
         printf("depth: rc %d cov %llu %llu %llu %s\n", rc, (unsigned long long)cov[0], (unsigned long long)cov[1], (unsigned long long)cov[2],
                rc ? vapor_bam_last_error() : "");
+    }
+    if (sig) {
+        for (int32_t t = 0; t <= std::max(tid, 0) + 1; ++t) {
+            const int64_t fields[9] = {0, ((int64_t)1 << 31) - 1, start, std::max(end, start), 50, 30, 0, (int64_t)1 << 28, 63};
+            int64_t out[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+            rc = vapor_bam_signature(b, t, fields, 1, chunk, out);
+            printf("sig: contig %d rc %d counts %lld %lld %lld %lld %lld %lld modes %lld %lld %lld %lld %s\n", t, rc, (long long)out[0], (long long)out[1],
+                   (long long)out[2], (long long)out[3], (long long)out[4], (long long)out[5], (long long)out[6], (long long)out[7], (long long)out[8],
+                   (long long)out[9], rc ? vapor_bam_last_error() : "");
+        }
     }
     vapor_bam_close(b);
     return 0;

@@ -1,5 +1,5 @@
 // readplan_check.cpp - the plan of a device reader call (vapor_amd/csrc/vapor_readplan.h: check_args, plan_spans, layout, ChopMeta,
-// collect for vapor_bam_chop_device*; the same five over DepthCall, DepthMeta, DepthLayout for vapor_bam_depth_device; plan_stretches, stage_stretches, layout_arena, place_windows, FastaMeta, gather_texts for
+// collect for vapor_bam_chop_device*; the same five over DepthCall, DepthMeta, DepthLayout for vapor_bam_depth_device and over SigCall, SigMeta, SigLayout for vapor_bam_signature_device; plan_stretches, stage_stretches, layout_arena, place_windows, FastaMeta, gather_texts for
 // vapor_fasta_windows_device) on a CPU, against direct statements of its rules.  It needs neither zlib nor files: the spans and
 // stretches are block tables the program fills in itself, the calls come from fixed seeds, and every buffer is a heap allocation
 // of exactly the bytes the header says it needs.  Nothing here is compared with recorded plans.
@@ -1091,6 +1091,197 @@ static void check_depth()
            n_calls, n_regions_seen, n_refused);
 }
 
+// ================================================================================================================================
+// vapor_bam_signature_device: SigCall's plan over the same plan_spans_of / layout_of
+// ================================================================================================================================
+struct SRegion {
+    int32_t tid = 0;
+    int64_t f[SIG_FIELDS] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    std::vector<std::pair<uint64_t, uint64_t>> chunks;
+    bool bad = false;
+};
+
+static SRegion sig_region(int bad)       // bad: 0 good; 1 w0 < 0; 2 w0 > w3; 3 w3 = 2^31; 4 tol < 0; 5 tol > 255; 6 nmin > nmax; 7 tid < 0; 8 ce < cs
+{
+    SRegion r;
+    r.tid = rnd(0, 30);
+    r.f[0] = one_in(6) ? 0 : rnd(0, 1 << 30);
+    r.f[1] = r.f[0] + (one_in(5) ? 0 : rnd(0, 20000));
+    if (one_in(10)) r.f[1] = ((int64_t)1 << 31) - 1;
+    r.f[2] = r.f[0] + rnd(-300, 300);
+    r.f[3] = r.f[2] + rnd(0, 12000);
+    r.f[4] = one_in(4) ? (one_in(2) ? 0 : 255) : rnd(0, 255);
+    r.f[5] = one_in(5) ? rnd(-5, 0) : rnd(1, 100);
+    r.f[6] = one_in(6) ? -(int64_t)rnd(0, 1 << 30) : rnd(0, 5000);
+    r.f[7] = r.f[6] + (one_in(6) ? ((int64_t)1 << 40) : rnd(0, 9000));
+    r.f[8] = one_in(8) ? 0xFFFF : rnd(0, 63);
+    for (int k = rnd(0, 3); k > 0; --k) {
+        const uint64_t c0 = (uint64_t)rnd(0, 1 << 28), len = one_in(4) ? 0 : (uint64_t)rnd(0, 300000);
+        const uint64_t u0 = (uint64_t)rnd(0, 65535), u1 = len == 0 ? (uint64_t)rnd((int)u0, 65535) : (uint64_t)rnd(0, 65535);
+        r.chunks.push_back({c0 << 16 | u0, (c0 + len) << 16 | u1});
+    }
+    r.bad = bad != 0;
+    if (bad == 1) { r.f[0] = -1 - rnd(0, 5); }
+    if (bad == 2) { r.f[0] = r.f[1] + 1 + rnd(0, 9); }
+    if (bad == 3) r.f[1] = (int64_t)1 << 31;
+    if (bad == 4) r.f[4] = -1 - rnd(0, 3);
+    if (bad == 5) r.f[4] = 256 + rnd(0, 1000);
+    if (bad == 6) r.f[6] = r.f[7] + 1 + rnd(0, 9);
+    if (bad == 7) r.tid = -1 - rnd(0, 3);
+    if (bad == 8) {
+        if (r.chunks.empty()) r.chunks.push_back({(uint64_t)5 << 16, (uint64_t)9 << 16});
+        auto& c = r.chunks[(size_t)rnd(0, (int)r.chunks.size() - 1)];
+        c.second = c.first - 1 - (c.first > 1 ? (uint64_t)rnd(0, 1) : 0);
+    }
+    return r;
+}
+
+static void check_signature()
+{
+    long n_calls = 0, n_refused = 0, n_regions_seen = 0;
+    for (int it = 0; it < 1500; ++it) {
+        g_case = it;
+        const int n = one_in(15) ? 0 : rnd(1, 12);
+        std::vector<SRegion> regs;
+        for (int g = 0; g < n; ++g) regs.push_back(sig_region(one_in(4) ? rnd(1, 8) : 0));
+        std::vector<int32_t> tid((size_t)n), chunk_first((size_t)n + 1, 0);
+        std::vector<int64_t> fields((size_t)SIG_FIELDS * (size_t)n);
+        std::vector<uint64_t> chunks;
+        for (int g = 0; g < n; ++g) {
+            tid[(size_t)g] = regs[(size_t)g].tid;
+            for (int k = 0; k < SIG_FIELDS; ++k) fields[(size_t)SIG_FIELDS * (size_t)g + (size_t)k] = regs[(size_t)g].f[k];
+            for (auto& c : regs[(size_t)g].chunks) { chunks.push_back(c.first); chunks.push_back(c.second); }
+            chunk_first[(size_t)g + 1] = (int32_t)(chunks.size() / 2);
+        }
+        SigCall c;
+        c.n_regions = n; c.tid = tid.data(); c.regions = fields.data(); c.chunk_first = chunk_first.data();
+        c.chunks = chunks.empty() ? nullptr : chunks.data();
+        c.filter_word = depth_filter_word((uint32_t)rnd(0, 65535) | ((uint32_t)rnd(0, 255) << 16));
+        std::vector<int64_t> out((size_t)SIG_ANSWER_WORDS * (size_t)std::max(n, 1), 77);
+        std::vector<int32_t> status((size_t)std::max(n, 1), -9);
+        CHECK(!check_args(c, out.data(), status.data()), "a good call is refused");
+        if (n) {
+            CHECK(check_args(c, nullptr, status.data()).code == VAPOR_E_ARG && check_args(c, out.data(), nullptr).code == VAPOR_E_ARG, "null outputs pass");
+            SigCall d = c; d.regions = nullptr;
+            CHECK(check_args(d, out.data(), status.data()).code == VAPOR_E_ARG, "null regions pass");
+        }
+        SpanPlan p;
+        CHECK(!plan_spans(c, status.data(), p), "a call below the size limit is refused");
+        size_t si = 0, stage = 0;
+        for (int g = 0; g < n; ++g) {
+            const SRegion& r = regs[(size_t)g];
+            CHECK(status[(size_t)g] == (r.bad ? REG_MALFORMED : 0), "region %d: status %d, bad %d", g, status[(size_t)g], (int)r.bad);
+            CHECK(p.span_first[(size_t)g] == (int32_t)si, "region %d: span_first", g);
+            if (r.bad) { ++n_refused; continue; }
+            for (auto& ch : r.chunks) {
+                CHECK(si < p.spans.size(), "region %d: a span is missing", g);
+                const HostSpan& sp = p.spans[si++];
+                const size_t want = (size_t)((ch.second >> 16) - (ch.first >> 16)) + ((ch.second & 0xFFFFu) ? 65536 + 64 : 0);
+                CHECK(sp.region == g && sp.cs == ch.first && sp.ce == ch.second && sp.file_off == (int64_t)(ch.first >> 16) && sp.want == want && sp.stage_off == stage,
+                      "region %d: span fields", g);
+                stage += up64(want);
+            }
+        }
+        CHECK(si == p.spans.size() && p.span_first[(size_t)n] == (int32_t)si && p.stage_bytes == stage, "spans %zu of %zu, stage %zu of %zu", si, p.spans.size(), stage, p.stage_bytes);
+        for (HostSpan& sp : p.spans) fake_scan(sp);
+        std::vector<int32_t> before = status;
+        SigLayout L;
+        CHECK(!layout(c, p, status.data(), L), "a layout below the size limit is refused");
+        size_t arena = 0, n_blk = 0, n_sp = 0;
+        CHECK((int)L.regs.size() == std::max(n, 1), "regions in the layout");
+        for (int g = 0; g < n; ++g) {
+            bool scan_bad = false;
+            for (int32_t s = p.span_first[(size_t)g]; s < p.span_first[(size_t)g + 1]; ++s) scan_bad |= p.spans[(size_t)s].bad;
+            CHECK(status[(size_t)g] == (scan_bad ? REG_MALFORMED : before[(size_t)g]), "region %d: status after the scan", g);
+            const SigRegion& R = L.regs[(size_t)g];
+            const int64_t* f = regs[(size_t)g].f;
+            CHECK(R.span_first == (int32_t)n_sp, "region %d: span_first in the layout", g);
+            if (status[(size_t)g]) {
+                // a region the plan or the scan refused carries a record that asks nothing
+                CHECK(R.span_n == 0 && R.mask == 0 && R.tol == 0 && R.w0 == 0 && R.w3 == 0, "region %d: a refused region's record", g);
+                continue;
+            }
+            // the record: the fields as given where they are in range, clamped where a clamp admits the same operations
+            CHECK(R.tid == tid[(size_t)g] && R.filter == c.filter_word && R.w0 == f[0] && R.w3 == f[1] && R.x0 == f[2] && R.x1 == f[3] && R.tol == f[4], "region %d: its record", g);
+            CHECK(R.min_clip == (f[5] < 1 ? 1 : f[5]) && R.mask == ((uint32_t)f[8] & 63u), "region %d: min_clip %d of %lld, mask %u", g, R.min_clip, (long long)f[5], R.mask);
+            auto clamped = [](int64_t v) { return v < -1 ? (int64_t)-1 : (v > ((int64_t)1 << 28) ? ((int64_t)1 << 28) : v); };
+            CHECK(R.nmin == clamped(f[6]) && R.nmax == clamped(f[7]) && R.nmin <= R.nmax, "region %d: length bounds", g);
+            for (int64_t len : {(int64_t)0, (int64_t)1, f[6] - 1, f[6], f[7], f[7] + 1, ((int64_t)1 << 28) - 1})
+                if (len >= 0 && len < ((int64_t)1 << 28))
+                    CHECK((len >= f[6] && len <= f[7]) == (len >= R.nmin && len <= R.nmax), "region %d: the clamped bounds admit other operations at %lld", g, (long long)len);
+            CHECK(R.span_n == p.span_first[(size_t)g + 1] - p.span_first[(size_t)g], "region %d: span_n", g);
+            for (int32_t s = p.span_first[(size_t)g]; s < p.span_first[(size_t)g + 1]; ++s) {
+                const HostSpan& sp = p.spans[(size_t)s];
+                const BamSpan& d = L.spans[n_sp++];
+                CHECK(d.u_begin == arena + sp.u_begin && d.u_end == arena + sp.u_end && d.u_limit == arena + sp.u_total && d.blk_first == n_blk && d.blk_n == sp.blks.size(),
+                      "region %d: a span in the arena", g);
+                for (const Block& k : sp.blks) {
+                    const BgzfBlk& B = L.blks[n_blk++];
+                    CHECK(B.c_off == sp.stage_off + k.payload() && B.c_len == k.c_len() && B.u_off == arena + k.u && B.u_len == k.isize && B.crc == k.crc, "a block of region %d", g);
+                }
+                arena += up64(sp.u_total);
+            }
+        }
+        CHECK(L.arena == arena && L.blks.size() == n_blk && L.spans.size() == n_sp, "arena %zu of %zu", arena, L.arena);
+        const SigMeta& M = L.meta;
+        const size_t nr = (size_t)std::max(n, 1), nb = std::max<size_t>(n_blk, 1), ns = std::max<size_t>(n_sp, 1);
+        const size_t offs[6] = {M.blks.off, M.spans.off, M.regs.off, M.blk_status.off, M.ans.off, M.reg_status.off};
+        const size_t sizes[6] = {24 * nb, 24 * ns, 72 * nr, 4 * nb, 40 * nr, 4 * nr};
+        size_t at = 0;
+        for (int t = 0; t < 6; ++t) { CHECK(offs[t] == at && at % 64 == 0, "table %d at %zu, not %zu", t, offs[t], at); at += up64(sizes[t]); }
+        CHECK(M.bytes == at && M.in_bytes == M.blk_status.off && M.back_bytes() == M.bytes - M.blk_status.off, "the block's sizes");
+        std::vector<uint8_t> h(M.bytes, 0xEE);
+        L.fill(h.data());
+        CHECK(!memcmp(M.regs.in(h.data()), L.regs.data(), 72 * nr) && (!n_blk || !memcmp(M.blks.in(h.data()), L.blks.data(), 24 * n_blk)) &&
+              (!n_sp || !memcmp(M.spans.in(h.data()), L.spans.data(), 24 * n_sp)), "fill");
+        uint32_t* da = M.ans.in(h.data());
+        int32_t* rs = M.reg_status.in(h.data());
+        for (size_t g = 0; g < nr; ++g) {
+            for (int k = 0; k < SIG_ANSWER_WORDS; ++k) da[(size_t)SIG_ANSWER_WORDS * g + (size_t)k] = (uint32_t)rng();
+            da[(size_t)SIG_ANSWER_WORDS * g + 6] = (uint32_t)(int32_t)rnd(-255, 255);
+            da[(size_t)SIG_ANSWER_WORDS * g + 8] = (uint32_t)(int32_t)rnd(-255, 255);
+            rs[g] = one_in(5) ? rnd(1, 5) : 0;
+        }
+        std::vector<int32_t> st2 = status;
+        collect(c, M, h.data(), out.data(), st2.data());
+        for (int g = 0; g < n; ++g) {
+            const bool host_refused = status[(size_t)g] != 0, dev_refused = rs[(size_t)g] != 0;
+            CHECK(st2[(size_t)g] == (host_refused ? status[(size_t)g] : rs[(size_t)g]), "region %d: collected status", g);
+            for (int k = 0; k < SIG_ANSWER_WORDS; ++k) {
+                const uint32_t wd = da[(size_t)SIG_ANSWER_WORDS * (size_t)g + (size_t)k];
+                const int64_t want = host_refused || dev_refused ? 0 : ((k == 6 || k == 8) ? (int64_t)(int32_t)wd : (int64_t)wd);
+                CHECK(out[(size_t)SIG_ANSWER_WORDS * (size_t)g + (size_t)k] == want, "region %d: word %d", g, k);
+            }
+        }
+        ++n_calls;
+        n_regions_seen += n;
+    }
+    // the two "in one call" refusals the Python side halves a group on
+    {
+        std::vector<int32_t> tid(40, 0), chunk_first(41), status(40);
+        std::vector<int64_t> fields;
+        std::vector<uint64_t> chunks;
+        for (int g = 0; g < 40; ++g) {
+            for (int64_t v : {0, 100, 40, 60, 50, 30, 30, 200, 63}) fields.push_back(v);
+            chunks.push_back((uint64_t)g << 44); chunks.push_back(((uint64_t)g << 44) + (((uint64_t)1 << 26) << 16));
+            chunk_first[(size_t)g + 1] = g + 1;
+        }
+        SigCall c;
+        c.n_regions = 40; c.tid = tid.data(); c.regions = fields.data(); c.chunk_first = chunk_first.data(); c.chunks = chunks.data();
+        SpanPlan p;
+        const Refusal r = plan_spans(c, status.data(), p);
+        CHECK(r.code == VAPOR_E_ARG && strstr(r.msg, "vapor_bam_signature_device") && strstr(r.msg, "in one call"), "2.5 GB of blocks pass");
+        c.n_regions = 20;
+        CHECK(!plan_spans(c, status.data(), p), "1.25 GB of blocks are refused");
+        for (HostSpan& sp : p.spans) { sp.blks.push_back(Block{0, 6, 100, 0, 65536, 0}); sp.u_total = (uint64_t)120 << 20; sp.u_begin = 0; sp.u_end = 100; sp.got = sp.want; }
+        SigLayout L;
+        const Refusal r2 = layout(c, p, status.data(), L);
+        CHECK(r2.code == VAPOR_E_ARG && strstr(r2.msg, "vapor_bam_signature_device") && strstr(r2.msg, "in one call"), "2.4 GB of block data pass");
+    }
+    printf("signature plan: %ld calls with %ld regions (%ld refused): statuses, spans, arena, tables, clamped fields and collected words equal the rule; both size refusals say \"in one call\"\n",
+           n_calls, n_regions_seen, n_refused);
+}
+
 int main()
 {
     check_statuses();
@@ -1099,7 +1290,8 @@ int main()
     check_collect();
     check_fasta();
     check_fasta_caps();
-    check_depth();          // (last: the calls above draw from the one seeded stream, and their counts are quoted)
+    check_depth();          // (behind the others: the calls above draw from the one seeded stream, and their counts are quoted)
+    check_signature();
     printf("readplan_check: all equal\n");
     return 0;
 }

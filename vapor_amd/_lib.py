@@ -60,6 +60,7 @@ EXPORTS = [
     "vapor_bam_set_filter",
     "vapor_bam_set_dedup", "vapor_bam_batch_name_keys",
     "vapor_bam_depth", "vapor_bam_depth_device",
+    "vapor_bam_signature", "vapor_bam_signature_device",
 ]
 # entry points a library may lack (the CPU twin of the C ABI has no wide or any-k route and no refinement kernel): bound when
 # present, and the engine's wide, any-k and grid methods raise NotImplementedError when they are not
@@ -73,7 +74,9 @@ OPTIONAL_EXPORTS = ("vapor_wide_batch", "vapor_clean_hits_wide", "vapor_anyk_bat
                     # (`--dedup-qname`, DESIGN.md 4.18: without them a de-duplicating run takes the Python statement as well)
                     "vapor_bam_set_dedup", "vapor_bam_batch_name_keys",
                     # (`--depth`, DESIGN.md 4.19: without them a run takes the Python statement, depth.cover over bamio's records)
-                    "vapor_bam_depth", "vapor_bam_depth_device")
+                    "vapor_bam_depth", "vapor_bam_depth_device",
+                    # (`--signatures`, DESIGN.md 4.20: without them a run takes signature.answer over bamio's records)
+                    "vapor_bam_signature", "vapor_bam_signature_device")
 MAX_CANDIDATES = 128           # breakpoint refinement: candidates per locus (VAPOR_MAX_CANDIDATES)
 
 _lib = None
@@ -257,6 +260,10 @@ def bind(L: ctypes.CDLL) -> ctypes.CDLL:
         L.vapor_bam_depth.argtypes = [vp, ctypes.c_int32, vp, ctypes.c_int32, vp, vp]
     if hasattr(L, "vapor_bam_depth_device"):
         L.vapor_bam_depth_device.argtypes = [vp, vp, ctypes.c_int32, vp, vp, vp, vp, vp, vp]
+    if hasattr(L, "vapor_bam_signature"):
+        L.vapor_bam_signature.argtypes = [vp, ctypes.c_int32, vp, ctypes.c_int32, vp, vp]
+    if hasattr(L, "vapor_bam_signature_device"):
+        L.vapor_bam_signature_device.argtypes = [vp, vp, ctypes.c_int32, vp, vp, vp, vp, vp, vp]
     if hasattr(L, "vapor_plan_run_grid"):
         L.vapor_plan_run_grid.argtypes = [vp, i32p, f64p, f64p, i64p]
     for name in EXPORTS:

@@ -492,6 +492,26 @@ class BamFile:
                 self._free.append(tl)
         return [int(x) for x in cov]
 
+    def signature_native(self, tid: int, region, chunks=None):
+        """The ten words of one signature region (`--signatures`; region: signature.FIELDS) through the library's
+        host reader (vapor_bam_signature); the .bai lookup stays here.  ValueError with the reader's message for a file that
+        breaks a rule or a region the reader refuses."""
+        from . import _lib
+        lib = _lib.load()
+        r = np.ascontiguousarray(region, dtype=np.int64)
+        ch = self.index.chunks(tid, int(r[0]), int(r[1])) if chunks is None and tid >= 0 and 0 <= r[0] <= r[1] else (chunks or [])
+        out = np.zeros(10, dtype=np.int64)
+        flat = np.asarray(ch, dtype=np.uint64).reshape(-1)
+        tl = self._take_handle(lib)
+        try:
+            if lib.vapor_bam_signature(tl["native"], int(tid), r.ctypes.data, len(flat) // 2, flat.ctypes.data if len(flat) else None,
+                                       out.ctypes.data) != 0:
+                raise ValueError(lib.vapor_bam_last_error().decode())
+        finally:
+            with self._lock:
+                self._free.append(tl)
+        return [int(x) for x in out]
+
     def fetch_raw(self, chrom: str, start: int, end: int, sites=None, exclude_more: int = 0):
         """(QNAME, 1-based POS, CIGAR operations as a uint32 tuple, packed SEQ bytes, l_seq, FLAG, (hap, ps)) of the alignments
         that overlap the 1-based inclusive region, in file order; nothing is decoded to text.  (hap, ps): the record's

@@ -24,8 +24,12 @@ not in the file; with --both-ends the pooled VaPoR_BE_* columns count a molecule
 --depth (bed, vcf): read depth inside every DEL and TANDUP call against the depth of its 1 kb flanks, a second
 line of evidence beside the dot plots; appends VaPoR_DP_IN, VaPoR_DP_FL, VaPoR_DFC and VaPoR_DSUP; the row's own columns are
 the plain run's; not together with --refine, --phased, --phase-vcf or --both-ends.
+--signatures (bed, vcf): split-read and CIGAR evidence per DEL, TANDUP, INV and INS call - the alignments clipped
+at its breakpoints, those that carry it as a D, N or I, and the modal breakpoints they give; appends VaPoR_SIG_L, VaPoR_SIG_R,
+VaPoR_SIG_CG, VaPoR_SIG_N, VaPoR_SIG_POS and VaPoR_SIG_END; the row's own columns are the plain run's; not together with another
+of these modes.
 
---refine, --phased (with --phase-vcf), --both-ends and --depth each append columns to every row and exclude one another: a run has one
+--refine, --phased (with --phase-vcf), --both-ends, --depth and --signatures each append columns to every row and exclude one another: a run has one
 mode (vapor_amd.modes) or none, built once in _main and handed as one argument to bed_jobs / vcf_jobs (which
 driver a locus takes), score_jobs (the payload gathered into Job.extra), the table writer and SF.vcf_vapor_modify.  An option
 that adds columns is a module with INFO, COLUMNS, pack, unpack and columns_many, a Mode made of it, and its branch in _simple_job.
@@ -721,6 +725,42 @@ def _depth_payloads(jobs, todo, engine):
 modes.DEPTH.chunk_payloads = _depth_payloads
 
 
+def _signature_payloads(jobs, todo, engine):
+    """`--signatures`: like depth, the evidence is the chunk's - the signature regions of all its DEL, TANDUP,
+    INV and INS loci (signature.regions of Job.spec, clipped to the backend's contig length) go to the read backend in one
+    signature_many call per BAM file (a per-chromosome pattern: per file, merged by signature.merge_words).  Returns
+    {t: signature.Payload}; a locus of another type has none."""
+    from . import seqio, signature
+    be = seqio.get_backend()
+    by_bam = {}
+    for t in todo:
+        j = jobs[t]
+        if j.spec is not None and j.ctx is not None and j.spec[0] in signature.TYPES:
+            by_bam.setdefault((j.ctx[1], j.ctx[2]), []).append(t)
+    out = {}
+    for (bam, ref), ts in by_bam.items():
+        files = seqio.bam_in_decide(bam, None)
+        where, chroms, regs_all, loci = [], [], [], []
+        for t in ts:
+            name, chrom, s, e, ins_seq = jobs[t].spec[:5]
+            locus = [chrom, s, len(ins_seq)] if name == 'INS' else [chrom, s, e]
+            regs = signature.regions(name, locus, be.contig_length(files[0], ref, chrom) if files else 0)
+            where.append((len(regs_all), regs))
+            loci.append(locus)
+            chroms += [chrom] * len(regs)
+            regs_all += regs
+        got = [[0] * 10 for _ in regs_all]
+        for f in files:
+            for k, a in enumerate(be.signature_many(engine, f, chroms, regs_all)):
+                got[k] = signature.merge_words(got[k], a)
+        for t, locus, (at, regs) in zip(ts, loci, where):
+            out[t] = signature.payload(jobs[t].spec[0], locus, regs, got[at:at + len(regs)])
+    return out
+
+
+modes.SIGNATURES.chunk_payloads = _signature_payloads
+
+
 last_timing: dict = {}          # of the most recent score_jobs: seconds scoring this rank's share, seconds in the gather
 
 
@@ -878,6 +918,13 @@ def build_parser() -> argparse.ArgumentParser:
                         'above 20 kb: 10 kb at each of its ends); unmapped, secondary, QC-fail and duplicate records never count; '
                         'appends VaPoR_DP_IN, VaPoR_DP_FL, VaPoR_DFC and VaPoR_DSUP - 1 where the fold change is below 0.7 for a DEL, '
                         'above 1.3 for a TANDUP (vcf: to INFO); not together with --refine, --phased, --phase-vcf or --both-ends')
+    p.add_argument('--signatures', action='store_true',
+                   help='bed, vcf: split-read and CIGAR evidence per DEL, TANDUP, INV and INS call: alignments soft- or hard-clipped by '
+                        '30 bases or more within 50 bases of a breakpoint, alignments that carry the event as a D or N (DEL) or an I '
+                        '(INS, TANDUP) of a fitting length, and the modal breakpoints they give; unmapped, secondary, QC-fail and '
+                        'duplicate records never count, supplementary records do; appends VaPoR_SIG_L, VaPoR_SIG_R, VaPoR_SIG_CG, '
+                        'VaPoR_SIG_N, VaPoR_SIG_POS and VaPoR_SIG_END (vcf: to INFO); not together with --refine, --phased, '
+                        '--phase-vcf, --both-ends or --depth')
     p.add_argument('--min-mapq', metavar='Q', type=_int_in('--min-mapq', 0, 255), default=0,
                    help='every sub-command: skip records with MAPQ below Q (0..255, default 0), as `samtools view -q Q` does; a '
                         'filtered record is treated as if it were not in the file')
@@ -978,6 +1025,19 @@ def _main(argv, held) -> int:
             parser.error('--depth and --phased cannot be combined (depth is not measured per haplotype)')
         if args.both_ends:
             parser.error('--depth and --both-ends cannot be combined (a run has one mode)')
+    if args.signatures:
+        if cmd not in ('bed', 'vcf'):
+            parser.error('--signatures applies to `vapor bed` and `vapor vcf`')
+        if refine is not None:
+            parser.error('--signatures and --refine cannot be combined (a run has one mode)')
+        if args.phase_vcf is not None:
+            parser.error('--signatures and --phase-vcf cannot be combined (signatures are not counted per haplotype)')
+        if args.phased:
+            parser.error('--signatures and --phased cannot be combined (signatures are not counted per haplotype)')
+        if args.both_ends:
+            parser.error('--signatures and --both-ends cannot be combined (a run has one mode)')
+        if args.depth:
+            parser.error('--signatures and --depth cannot be combined (a run has one mode)')
     if args.phase_vcf is not None:
         # (every rank reads the VCF itself; the sites ride on the backend the reads are taken through)
         from . import phase as ph
@@ -1003,7 +1063,7 @@ def _main(argv, held) -> int:
         backend.dedup_qname = True
         if backend not in held:
             held.append(backend)
-    mode = None                          # (at most one of the four: every pair was refused above)
+    mode = None                          # (at most one of the five: every pair was refused above)
     if refine is not None:
         mode = modes.refine(*refine, ci_of=vcf_ci_readin(args.sv_input) if cmd == 'vcf' else None)
     elif args.phased:
@@ -1012,6 +1072,8 @@ def _main(argv, held) -> int:
         mode = modes.BOTH_ENDS
     elif args.depth:
         mode = modes.DEPTH
+    elif args.signatures:
+        mode = modes.SIGNATURES
     figure_fn = None
     if not args.no_figures:
         from . import figures

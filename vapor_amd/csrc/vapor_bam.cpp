@@ -673,37 +673,27 @@ extern "C" int vapor_bam_chop_haplotag(vapor_bam* b, int32_t tid, int64_t start,
     }
 }
 
-// Read depth of three consecutive intervals [b0, b1) [b1, b2) [b2, b3) of contig `tid`, 0-based half-open (`--depth`, DESIGN.md
-// 4.19; vapor_amd/depth.py cover is the rule, bam_depth_kernel the device's form): bam_chop_impl's walk over the chunks' records
-// with its checks, the handle's read filter with DEPTH_EXCLUDE among its flags, and per passing record the overlap of every M, =
-// and X operation with each interval - D and N move the reference cursor and cover nothing, a record without operations covers
-// nothing.  A record at or behind b3 ends a chunk.
-static int bam_depth_impl(vapor_bam* b, int32_t tid, const int64_t* bounds, int32_t n_chunks, const uint64_t* chunks, uint64_t* cov)
+// The walk of the depth and the signature reader (`--depth`, `--signatures`): bam_chop_impl's walk over the chunks' records with
+// its checks, the handle's read filter with DEPTH_EXCLUDE among its flags, a CG:B,I array in place of its stand-in.  A record at
+// or behind `stop` ends a chunk.  rec(pos, ops, n_ops): a passing record of contig `tid`, its operations as the file holds them.
+template <typename PerRecord>
+static int bam_walk_records(vapor_bam* b, const char* who, int32_t tid, int64_t stop, int32_t n_chunks, const uint64_t* chunks, PerRecord rec)
 {
-    if (!b || !bounds || !cov || n_chunks < 0 || (n_chunks && !chunks)) return bfail(VAPOR_E_ARG, "vapor_bam_depth: null argument");
-    const int64_t b0 = bounds[0], b1 = bounds[1], b2 = bounds[2], b3 = bounds[3];
-    if (b0 < 0 || b1 < b0 || b2 < b1 || b3 < b2 || b3 >= ((int64_t)1 << 31) || tid < 0)
-        return bfail(VAPOR_E_ARG, "vapor_bam_depth: the bounds do not ascend from 0 to a BAM position, or the contig is none");
     const uint32_t excl = b->exclude_flags | vapor_bamdev::DEPTH_EXCLUDE;
-    cov[0] = cov[1] = cov[2] = 0;
-    auto overlap = [](int64_t s, int64_t e, int64_t lo, int64_t hi) -> uint64_t {
-        const int64_t a = std::max(s, lo), z = std::min(e, hi);
-        return z > a ? (uint64_t)(z - a) : 0u;
-    };
     for (int32_t c = 0; c < n_chunks; ++c) {
         const uint64_t cs = chunks[2 * c], ce = chunks[2 * c + 1];
         b->comp.clear(); b->data.clear(); b->scan_pos = 0;
         b->blk_coff.clear(); b->blk_cpos.clear(); b->blk_csize.clear(); b->blk_ustart.clear(); b->blk_usize.clear();
         b->comp_base = (int64_t)(cs >> 16);
         if (ce < cs || (ce >> 16) - (cs >> 16) > ((uint64_t)1 << 31))
-            return bfail(VAPOR_E_ARG, "vapor_bam_depth: implausible index chunk for " + b->path);
+            return bfail(VAPOR_E_ARG, std::string(who) + ": implausible index chunk for " + b->path);
         const size_t span = (size_t)((int64_t)(ce >> 16) - b->comp_base) + ((ce & 0xFFFFu) ? ((size_t)1 << 16) + 64 : 0);
         if (span == 0 || !read_more(b, span)) continue;
         if (scan_blocks(b) < 0 && ((uint64_t)(b->comp_base + (int64_t)b->scan_pos) << 16) < ce)
-            return bfail(VAPOR_E_ARG, "vapor_bam_depth: not a BGZF block in " + b->path);
+            return bfail(VAPOR_E_ARG, std::string(who) + ": not a BGZF block in " + b->path);
         size_t own = 0;
         while (own < b->blk_coff.size() && ((uint64_t)b->blk_coff[own] << 16) < ce) ++own;
-        if (!take_blocks(b, own)) return bfail(VAPOR_E_ARG, "vapor_bam_depth: inflate failed in " + b->path);
+        if (!take_blocks(b, own)) return bfail(VAPOR_E_ARG, std::string(who) + ": inflate failed in " + b->path);
         int64_t pos_u = (int64_t)(cs & 0xFFFF);
         size_t blk = 0;
         for (;;) {
@@ -720,11 +710,11 @@ static int bam_depth_impl(vapor_bam* b, int32_t tid, const int64_t* bounds, int3
             if (voff >= ce) break;
             if (!ensure(b, pos_u + 4)) {
                 if (!g_bam_damaged) break;
-                return bfail(VAPOR_E_ARG, "vapor_bam_depth: damaged BGZF block in " + b->path);
+                return bfail(VAPOR_E_ARG, std::string(who) + ": damaged BGZF block in " + b->path);
             }
             const int32_t bs = rd32(b->data.data() + pos_u);
-            if (bs < 32 || bs > (1 << 29)) return bfail(VAPOR_E_ARG, "vapor_bam_depth: implausible record size in " + b->path);
-            if (!ensure(b, pos_u + 4 + bs)) return bfail(VAPOR_E_ARG, "vapor_bam_depth: truncated record (or damaged block) in " + b->path);
+            if (bs < 32 || bs > (1 << 29)) return bfail(VAPOR_E_ARG, std::string(who) + ": implausible record size in " + b->path);
+            if (!ensure(b, pos_u + 4 + bs)) return bfail(VAPOR_E_ARG, std::string(who) + ": truncated record (or damaged block) in " + b->path);
             const uint8_t* r = b->data.data() + pos_u + 4;
             pos_u += 4 + bs;
             const int32_t ref_id = rd32(r), pos = rd32(r + 4);
@@ -732,9 +722,9 @@ static int bam_depth_impl(vapor_bam* b, int32_t tid, const int64_t* bounds, int3
             const int n_cig = r[12] | (r[13] << 8);
             const int32_t l_seq = rd32(r + 16);
             if (l_seq < 0 || 32 + (int64_t)l_name + 4 * (int64_t)n_cig + ((int64_t)l_seq + 1) / 2 + (int64_t)l_seq > (int64_t)bs)
-                return bfail(VAPOR_E_ARG, "vapor_bam_depth: record fields exceed the record in " + b->path);
-            if (ref_id != tid || (int64_t)pos >= b3) {
-                if (ref_id > tid || (ref_id == tid && (int64_t)pos >= b3)) break;
+                return bfail(VAPOR_E_ARG, std::string(who) + ": record fields exceed the record in " + b->path);
+            if (ref_id != tid || (int64_t)pos >= stop) {
+                if (ref_id > tid || (ref_id == tid && (int64_t)pos >= stop)) break;
                 continue;
             }
             if ((uint32_t)r[9] < b->min_mapq || (((uint32_t)r[14] | ((uint32_t)r[15] << 8)) & excl)) continue;
@@ -749,22 +739,42 @@ static int bam_depth_impl(vapor_bam* b, int32_t tid, const int64_t* bounds, int3
                     if (cg) { ops = cg; n_ops = cnt; }
                 }
             }
-            int64_t cur = pos;
-            for (int32_t t = 0; t < n_ops && cur < b3; ++t) {
-                const uint32_t o = (uint32_t)rd32(ops + 4 * (size_t)t), code = o & 15u;
-                const int64_t n = o >> 4;
-                if (code == 0u || code == 7u || code == 8u) {
-                    cov[0] += overlap(cur, cur + n, b0, b1);
-                    cov[1] += overlap(cur, cur + n, b1, b2);
-                    cov[2] += overlap(cur, cur + n, b2, b3);
-                    cur += n;
-                } else if (code == 2u || code == 3u) {
-                    cur += n;
-                }
-            }
+            rec((int64_t)pos, ops, n_ops);
         }
     }
     return VAPOR_OK;
+}
+
+// Read depth of three consecutive intervals [b0, b1) [b1, b2) [b2, b3) of contig `tid`, 0-based half-open (`--depth`, DESIGN.md
+// 4.19; vapor_amd/depth.py cover is the rule, bam_depth_kernel the device's form): bam_walk_records, and per passing record the overlap of every M, =
+// and X operation with each interval - D and N move the reference cursor and cover nothing, a record without operations covers
+// nothing.  A record at or behind b3 ends a chunk.
+static int bam_depth_impl(vapor_bam* b, int32_t tid, const int64_t* bounds, int32_t n_chunks, const uint64_t* chunks, uint64_t* cov)
+{
+    if (!b || !bounds || !cov || n_chunks < 0 || (n_chunks && !chunks)) return bfail(VAPOR_E_ARG, "vapor_bam_depth: null argument");
+    const int64_t b0 = bounds[0], b1 = bounds[1], b2 = bounds[2], b3 = bounds[3];
+    if (b0 < 0 || b1 < b0 || b2 < b1 || b3 < b2 || b3 >= ((int64_t)1 << 31) || tid < 0)
+        return bfail(VAPOR_E_ARG, "vapor_bam_depth: the bounds do not ascend from 0 to a BAM position, or the contig is none");
+    cov[0] = cov[1] = cov[2] = 0;
+    auto overlap = [](int64_t s, int64_t e, int64_t lo, int64_t hi) -> uint64_t {
+        const int64_t a = std::max(s, lo), z = std::min(e, hi);
+        return z > a ? (uint64_t)(z - a) : 0u;
+    };
+    return bam_walk_records(b, "vapor_bam_depth", tid, b3, n_chunks, chunks, [&](int64_t pos, const uint8_t* ops, int32_t n_ops) {
+        int64_t cur = pos;
+        for (int32_t t = 0; t < n_ops && cur < b3; ++t) {
+            const uint32_t o = (uint32_t)rd32(ops + 4 * (size_t)t), code = o & 15u;
+            const int64_t n = o >> 4;
+            if (code == 0u || code == 7u || code == 8u) {
+                cov[0] += overlap(cur, cur + n, b0, b1);
+                cov[1] += overlap(cur, cur + n, b1, b2);
+                cov[2] += overlap(cur, cur + n, b2, b3);
+                cur += n;
+            } else if (code == 2u || code == 3u) {
+                cur += n;
+            }
+        }
+    });
 }
 
 extern "C" int vapor_bam_depth(vapor_bam* b, int32_t tid, const int64_t* bounds, int32_t n_chunks, const uint64_t* chunks, uint64_t* cov)
@@ -775,6 +785,87 @@ extern "C" int vapor_bam_depth(vapor_bam* b, int32_t tid, const int64_t* bounds,
         return bfail(VAPOR_E_NOMEM, "vapor_bam_depth: out of memory");
     } catch (const std::exception& e) {
         return bfail(VAPOR_E_ARG, std::string("vapor_bam_depth: ") + e.what());
+    }
+}
+
+// Split-read and CIGAR evidence of one signature region (`--signatures`; vapor_amd/signature.py answer is the
+// rule, bam_signature_kernel the device's form): bam_walk_records to w3, and per passing record its events - the leading clip
+// from the first two operations, the trailing from the last two, a GAP per D or N and an INSOP per I at the cursor where the
+// operation starts - counted at the region's targets, with the two histograms of offsets and their modes.  An empty window has
+// no records.
+// fields: w0, w3, x0, x1, tol, min_clip, nmin, nmax, mask (vapor_readplan.h SIG_FIELDS); out: six counts, off0, cnt0, off1, cnt1.
+static int bam_signature_impl(vapor_bam* b, int32_t tid, const int64_t* fields, int32_t n_chunks, const uint64_t* chunks, int64_t* out)
+{
+    using namespace vapor_bamdev;
+    if (!b || !fields || !out || n_chunks < 0 || (n_chunks && !chunks)) return bfail(VAPOR_E_ARG, "vapor_bam_signature: null argument");
+    if (!vapor_readplan::sig_region_ok(tid, fields))
+        return bfail(VAPOR_E_ARG, "vapor_bam_signature: the window does not ascend from 0 to a BAM position, the tolerance is not 0..255, "
+                                  "the length bounds descend, or the contig is none");
+    SigRegion R;
+    vapor_readplan::sig_region_set(R, tid, fields, 0);
+    const int64_t x[2] = {R.x0, R.x1}, tol = R.tol, width = 2 * tol + 1;
+    std::vector<uint32_t> hist((size_t)(2 * width), 0u);
+    int64_t cnt[6] = {0, 0, 0, 0, 0, 0};
+    auto is_clip = [](uint32_t o) { return (o & 15u) == 4u || (o & 15u) == 5u; };
+    const int rc = bam_walk_records(b, "vapor_bam_signature", tid, R.w3, R.w3 > R.w0 ? n_chunks : 0, chunks, [&](int64_t pos, const uint8_t* ops, int32_t n_ops) {
+        if (n_ops <= 0) return;
+        auto op = [&](int32_t t) { return (uint32_t)rd32(ops + 4 * (size_t)t); };
+        const uint32_t o0 = op(0), o1 = n_ops >= 2 ? op(1) : 15u, ol = op(n_ops - 1), op2 = n_ops >= 2 ? op(n_ops - 2) : 15u;
+        if (is_clip(o0) && (n_ops == 1 || (n_ops == 2 && is_clip(o1)))) return;     // all clips: neither event
+        const int64_t lead = is_clip(o0) ? (int64_t)(o0 >> 4) + (is_clip(o1) ? (int64_t)(o1 >> 4) : 0) : 0;
+        const int64_t trail = is_clip(ol) ? (int64_t)(ol >> 4) + (is_clip(op2) ? (int64_t)(op2 >> 4) : 0) : 0;
+        int64_t cur = pos;
+        for (int32_t t = 0; t < n_ops; ++t) {
+            const uint32_t o = op(t), code = o & 15u;
+            const int64_t n = o >> 4;
+            if ((code == 2u || code == 3u) && (R.mask & SIG_GAP) && n >= R.nmin && n <= R.nmax) {
+                const int64_t d0 = cur - x[0], d1 = cur + n - x[1];
+                if (d0 >= -tol && d0 <= tol && d1 >= -tol && d1 <= tol) {
+                    ++cnt[4];
+                    ++hist[(size_t)(d0 + tol)];
+                    ++hist[(size_t)(width + d1 + tol)];
+                }
+            }
+            if (code == 1u && (R.mask & SIG_INSOP) && n >= R.nmin && n <= R.nmax && cur >= x[0] - tol && cur <= x[1] + tol) {
+                ++cnt[5];
+                if (cur - x[0] >= -tol && cur - x[0] <= tol) ++hist[(size_t)(cur - x[0] + tol)];
+            }
+            if (code == 0u || code == 2u || code == 3u || code == 7u || code == 8u) cur += n;
+        }
+        for (int k = 0; k < 4; ++k) {
+            if (!((R.mask >> k) & 1u)) continue;
+            const int64_t have = (k & 1) ? trail : lead, d = ((k & 1) ? cur : pos) - x[k >> 1];
+            if (have >= R.min_clip && d >= -tol && d <= tol) {
+                ++cnt[k];
+                ++hist[(size_t)((k >> 1) * width + d + tol)];
+            }
+        }
+    });
+    for (int k = 0; k < 10; ++k) out[k] = 0;
+    if (rc != VAPOR_OK) return rc;
+    for (int k = 0; k < 6; ++k) out[k] = cnt[k];
+    for (int h = 0; h < 2; ++h) {
+        // the mode: the largest count, then the smallest |offset|, then the negative offset
+        int64_t best_off = 0, best = 0;
+        for (int64_t off = -tol; off <= tol; ++off) {
+            const int64_t c = hist[(size_t)(h * width + off + tol)];
+            const int64_t a = off < 0 ? -off : off, ba = best_off < 0 ? -best_off : best_off;
+            if (c > best || (c == best && c > 0 && (a < ba || (a == ba && off < best_off)))) { best = c; best_off = off; }
+        }
+        out[6 + 2 * h] = best ? best_off : 0;
+        out[7 + 2 * h] = best;
+    }
+    return VAPOR_OK;
+}
+
+extern "C" int vapor_bam_signature(vapor_bam* b, int32_t tid, const int64_t* fields, int32_t n_chunks, const uint64_t* chunks, int64_t* out)
+{
+    try {
+        return bam_signature_impl(b, tid, fields, n_chunks, chunks, out);
+    } catch (const std::bad_alloc&) {
+        return bfail(VAPOR_E_NOMEM, "vapor_bam_signature: out of memory");
+    } catch (const std::exception& e) {
+        return bfail(VAPOR_E_ARG, std::string("vapor_bam_signature: ") + e.what());
     }
 }
 
@@ -1189,4 +1280,11 @@ extern "C" __attribute__((weak)) int vapor_bam_depth_device(vapor_ctx*, vapor_ba
                                                             const uint64_t*, uint64_t*, int32_t*)
 {
     return bfail(VAPOR_E_ARG, "vapor_bam_depth_device: this build has no device reader");
+}
+
+// ... and the signatures on the device (vapor_bam_signature_device: bam_signature_kernel; the host reader is vapor_bam_signature).
+extern "C" __attribute__((weak)) int vapor_bam_signature_device(vapor_ctx*, vapor_bam*, int32_t, const int32_t*, const int64_t*, const int32_t*,
+                                                                const uint64_t*, int64_t*, int32_t*)
+{
+    return bfail(VAPOR_E_ARG, "vapor_bam_signature_device: this build has no device reader");
 }

@@ -1250,6 +1250,171 @@ __global__ __launch_bounds__(64) void bam_depth_kernel(const uint8_t* __restrict
     }
 }
 
+// Split-read and CIGAR evidence per region (`--signatures`; vapor_bam.cpp bam_signature_impl is the host's
+// statement, vapor_amd/signature.py answer the rule): one wavefront a region, bam_depth_kernel's record walk with its checks,
+// statuses and filter test, and behind it the events of a record.  The operations go 64 a step to the record's end (RCLIP needs
+// the reference end): one wave_scan64 of the reference advance gives every lane the cursor where its operation starts, and a D
+// or N (GAP) or an I (INSOP) is tested on the lane that holds it.  The leading clip is operations 0 and 1 of the first tile; the
+// trailing clip the last two operations, of which n - 2 may be lane 63 of the tile before (carried in `prev63`).  Lanes 0 to 3
+// own the four clip bits (bit k: the leading clip for even k, the trailing for odd; target x0 below 2, x1 above), so a record's
+// clip events cost one comparison on four lanes.  Counts are per-lane registers, reduced once; the two histograms are
+// 2 * (2 * tol + 1) words of LDS, updated with LDS atomics by the lane that owns the event; the mode of each is one wave
+// maximum over a key that orders (count, smaller |offset|, negative offset) exactly.
+__device__ __forceinline__ bool sig_is_clip(uint32_t o) { return (o & 15u) == 4u || (o & 15u) == 5u; }
+
+__global__ __launch_bounds__(64) void bam_signature_kernel(const uint8_t* __restrict__ arena, const SigRegion* __restrict__ regs,
+                                                          const BamSpan* __restrict__ spans, const int32_t* __restrict__ blk_status, int n_regs,
+                                                          uint32_t* __restrict__ ans, int32_t* __restrict__ reg_status)
+{
+    __shared__ uint32_t hist[SIG_HIST_WORDS];
+    const int g = (int)blockIdx.x;
+    if (g >= n_regs) return;
+    const uint32_t lane = threadIdx.x;
+    const SigRegion R = regs[g];
+    const long long w3 = R.w3, x0 = R.x0, x1 = R.x1;
+    // (the host made tol 0..255; the clamp keeps every histogram index inside the array whatever the table holds)
+    const long long tol = R.tol < 0 ? 0 : (R.tol > SIG_TOL_MAX ? SIG_TOL_MAX : R.tol);
+    const uint32_t width = 2u * (uint32_t)tol + 1u;
+    const long long nmin = R.nmin, nmax = R.nmax, min_clip = R.min_clip;
+    const uint32_t mask = R.mask;
+    const uint32_t flt_excl = R.filter & 0xFFFFu, flt_mapq = (R.filter >> 16) & 0xFFu;
+    for (uint32_t i = lane; i < 2u * width; i += 64) hist[i] = 0u;
+    __syncthreads();
+    // this lane's clip bit, for lanes 0 to 3: which end of the record, which target, which histogram
+    const bool my_clip = lane < 4u && ((mask >> lane) & 1u);
+    const long long my_x = (lane & 2u) ? x1 : x0;
+    const uint32_t my_hist = (lane & 2u) ? width : 0u;
+    uint32_t c_clip = 0, c_gap = 0, c_ins = 0;
+    int st = REG_OK;
+    const int span_n = w3 > R.w0 ? R.span_n : 0;            // (an empty window has no records, whatever chunks came with it)
+    for (int s = 0; s < span_n && st == REG_OK; ++s) {
+        const BamSpan SP = spans[R.span_first + s];
+        int bad = 0;
+        for (uint32_t i = lane; i < SP.blk_n; i += 64) bad |= blk_status[SP.blk_first + i] != 0;
+        if (__any(bad)) { st = REG_BLOCK; break; }
+        uint32_t pos_u = SP.u_begin;
+        // (a record is 36 bytes at least: pos_u grows every turn and the loop ends at u_end)
+        while (pos_u < SP.u_end) {
+            if ((unsigned long long)pos_u + 36ull > SP.u_limit) { st = REG_BEYOND; break; }
+            uint32_t w = 0;
+            if (lane < 6) w = rd32u(arena + pos_u + 4u * lane);
+            const int32_t bs = (int32_t)__shfl(w, 0), ref_id = (int32_t)__shfl(w, 1), pos = (int32_t)__shfl(w, 2);
+            const uint32_t wd3 = __shfl(w, 3), wd4 = __shfl(w, 4);
+            const int32_t l_seq = (int32_t)__shfl(w, 5);
+            if (bs < 32 || bs > (1 << 29)) { st = REG_MALFORMED; break; }
+            if ((unsigned long long)pos_u + 4ull + (unsigned long long)bs > SP.u_limit) { st = REG_BEYOND; break; }
+            const uint32_t r = pos_u + 4u;
+            pos_u += 4u + (uint32_t)bs;
+            const int l_name = (int)(wd3 & 0xFFu), n_cig = (int)(wd4 & 0xFFFFu);
+            if (l_seq < 0 || 32ll + l_name + 4ll * n_cig + ((long long)l_seq + 1) / 2 + (long long)l_seq > (long long)bs) { st = REG_MALFORMED; break; }
+            if (ref_id != R.tid || (long long)pos >= w3) {
+                if (ref_id > R.tid || (ref_id == R.tid && (long long)pos >= w3)) break;
+                continue;
+            }
+            // the read filter, DEPTH_EXCLUDE among its flags: both fields came with the record's header
+            if (((wd3 >> 8) & 0xFFu) < flt_mapq || ((wd4 >> 16) & flt_excl)) continue;
+            const uint32_t cig = r + 32u + (uint32_t)l_name;
+            uint32_t ops = cig;
+            int32_t n_ops = n_cig;
+            if (n_cig == 2) {
+                const uint32_t o0 = rd32u(arena + cig), o1 = rd32u(arena + cig + 4);
+                if ((o0 & 15u) == 4u && (int32_t)(o0 >> 4) == l_seq && (o1 & 15u) == 3u) {
+                    int32_t cnt = 0;
+                    const uint32_t cg = find_cg_dev(arena, cig + 8u + (uint32_t)((l_seq + 1) / 2) + (uint32_t)l_seq, r + (uint32_t)bs, &cnt);
+                    if (cg) { ops = cg; n_ops = cnt; }
+                }
+            }
+            if (n_ops <= 0) continue;                       // no CIGAR: nothing, and no error
+            long long cur = (long long)pos;                 // the reference cursor where the tile starts, 0-based
+            long long lead = 0, trail = 0;                  // the clipped bases at the record's two ends
+            uint32_t prev63 = 15u;                          // operation t0 - 1, for a trailing clip that starts on the tile before
+            for (int32_t t0 = 0; t0 < n_ops; t0 += 64) {
+                const int32_t t = t0 + (int32_t)lane;
+                const uint32_t o = t < n_ops ? rd32u(arena + ops + 4u * (uint32_t)t) : 15u;
+                const uint32_t code = o & 15u;
+                const long long n = (long long)(o >> 4);
+                const long long adv = (code == 0u || code == 2u || code == 3u || code == 7u || code == 8u) ? n : 0;
+                const long long A = wave_scan64(adv, lane);
+                const long long a = cur + A - adv;          // where this lane's operation starts
+                if ((code == 2u || code == 3u) && (mask & SIG_GAP) && n >= nmin && n <= nmax) {
+                    const long long d0 = a - x0, d1 = a + n - x1;
+                    if (d0 >= -tol && d0 <= tol && d1 >= -tol && d1 <= tol) {
+                        ++c_gap;
+                        atomicAdd(&hist[(uint32_t)(d0 + tol)], 1u);
+                        atomicAdd(&hist[width + (uint32_t)(d1 + tol)], 1u);
+                    }
+                }
+                if (code == 1u && (mask & SIG_INSOP) && n >= nmin && n <= nmax && a >= x0 - tol && a <= x1 + tol) {
+                    ++c_ins;
+                    const long long d0 = a - x0;
+                    if (d0 >= -tol && d0 <= tol) atomicAdd(&hist[(uint32_t)(d0 + tol)], 1u);
+                }
+                if (t0 == 0) {
+                    const uint32_t o0 = __shfl(o, 0), o1 = __shfl(o, 1);
+                    if (sig_is_clip(o0)) lead = (long long)(o0 >> 4) + ((n_ops >= 2 && sig_is_clip(o1)) ? (long long)(o1 >> 4) : 0);
+                    // (a record of at most two operations that are all clips has neither event)
+                    if (sig_is_clip(o0) && (n_ops == 1 || (n_ops == 2 && sig_is_clip(o1)))) lead = -1;
+                }
+                if (t0 + 64 >= n_ops) {
+                    const int32_t l = n_ops - 1 - t0;       // the lane of the last operation, 0..63
+                    const uint32_t ol = __shfl(o, l), op = l > 0 ? __shfl(o, l - 1) : prev63;
+                    if (sig_is_clip(ol)) trail = (long long)(ol >> 4) + ((n_ops >= 2 && sig_is_clip(op)) ? (long long)(op >> 4) : 0);
+                }
+                prev63 = __shfl(o, 63);
+                cur += __shfl(A, 63);
+            }
+            if (lead < 0) continue;
+            if (my_clip) {
+                const long long have = (lane & 1u) ? trail : lead;
+                const long long d = ((lane & 1u) ? cur : (long long)pos) - my_x;
+                if (have >= min_clip && d >= -tol && d <= tol) {
+                    ++c_clip;
+                    atomicAdd(&hist[my_hist + (uint32_t)(d + tol)], 1u);
+                }
+            }
+        }
+    }
+    __syncthreads();
+    // the six counts: lanes 0 to 3 hold the clip bits', the GAP and INSOP counts are sums over the wavefront
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        c_gap += __shfl_down(c_gap, (unsigned)d);
+        c_ins += __shfl_down(c_ins, (unsigned)d);
+    }
+    const uint32_t k0 = __shfl(c_clip, 0), k1 = __shfl(c_clip, 1), k2 = __shfl(c_clip, 2), k3 = __shfl(c_clip, 3);
+    // the modes: key = count << 10 | 1023 - rank, rank = 2 |offset| + (offset > 0) - the largest key is the largest count, then
+    // the smallest |offset|, then the negative one
+    unsigned long long best[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        unsigned long long key = 0;
+        for (uint32_t i = lane; i < width; i += 64) {
+            const long long off = (long long)i - tol;
+            const uint32_t rank = (uint32_t)(off < 0 ? -2 * off : 2 * off + 1);
+            const unsigned long long k = ((unsigned long long)hist[(uint32_t)h * width + i] << 10) | (unsigned long long)(1023u - rank);
+            key = k > key ? k : key;
+        }
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            const unsigned long long o = __shfl_xor(key, d);
+            key = o > key ? o : key;
+        }
+        best[h] = key;
+    }
+    if (lane == 0) {
+        uint32_t* o = ans + (size_t)SIG_ANSWER_WORDS * (size_t)g;
+        o[0] = k0; o[1] = k1; o[2] = k2; o[3] = k3; o[4] = c_gap; o[5] = c_ins;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const uint32_t cnt = (uint32_t)(best[h] >> 10), rank = 1023u - (uint32_t)(best[h] & 1023u);
+            const int32_t off = cnt ? ((rank & 1u) ? (int32_t)(rank >> 1) : -(int32_t)(rank >> 1)) : 0;
+            o[6 + 2 * h] = (uint32_t)off;
+            o[7 + 2 * h] = cnt;
+        }
+        reg_status[g] = st;
+    }
+}
+
 // One record of a molecule per region (`--dedup-qname`, DESIGN.md 4.18 rule W; vapor_names.h holds the arithmetic, vapor_bam.cpp
 // bam_chop_impl the host's statement): one wavefront a region, right behind the chop kernel on its stream and before
 // bam_haplotag_kernel / bam_select_kernel, launched only for a handle with the option.  BamKept has no record offset, so the

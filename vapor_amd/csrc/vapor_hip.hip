@@ -959,6 +959,36 @@ static int dump_inflate_timing(const uint8_t* d_comp, size_t stage_bytes, const 
 }
 #endif
 
+// The read and the scan of a device reader call's spans, a few threads: every span's file range into the staging block, its BGZF
+// blocks listed (vapor_bgzf::scan_span).  A span whose block list cannot be held is marked bad: its region goes the host route.
+static void read_and_scan(InflateStage& stage, int fd, vapor_bam* bam, std::vector<vapor_readplan::HostSpan>& spans)
+{
+    const int n_thr = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(vapor_bam_threads(bam), 1) * 2, spans.size() / 8 + 1));
+    std::atomic<size_t> next{0};
+    auto work = [&] {
+        for (;;) {
+            const size_t i = next.fetch_add(1, std::memory_order_relaxed);
+            if (i >= spans.size()) break;
+            vapor_readplan::HostSpan& sp = spans[i];
+            sp.got = stage.read(fd, sp.stage_off, sp.want, sp.file_off);
+            try {
+                vapor_bgzf::scan_span(sp, stage.h_comp);
+            } catch (const std::exception&) {       // (out of memory for the block list: the region goes the host route)
+                sp.blks.clear();
+                sp.bad = true;
+            }
+        }
+    };
+    if (n_thr <= 1) {
+        work();
+    } else {
+        std::vector<std::thread> th;
+        for (int t = 1; t < n_thr; ++t) th.emplace_back(work);
+        work();
+        for (auto& x : th) x.join();
+    }
+}
+
 // The four vapor_bam_chop_device* entries (vapor_readplan.h ChopMode).  TAGGED: the tagged chop kernel, the select kernel behind it
 // on the same stream, and only the regions' compact unions and phase sets copied back.  HAPLOTAG: the tags the select kernel reads
 // come from bam_haplotag_kernel, which runs between the two.
@@ -992,32 +1022,7 @@ static int bam_chop_device_impl(vapor_ctx* ctx, vapor_bam* bam, vapor_readplan::
         InflateStage stage(sc);
         HIPCHK(stage.begin(plan.stage_bytes));
         // ---- read and scan, a few threads -------------------------------------------------------------------------------------
-        {
-            const int n_thr = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(vapor_bam_threads(bam), 1) * 2, spans.size() / 8 + 1));
-            std::atomic<size_t> next{0};
-            auto work = [&] {
-                for (;;) {
-                    const size_t i = next.fetch_add(1, std::memory_order_relaxed);
-                    if (i >= spans.size()) break;
-                    HostSpan& sp = spans[i];
-                    sp.got = stage.read(fd, sp.stage_off, sp.want, sp.file_off);
-                    try {
-                        vapor_bgzf::scan_span(sp, stage.h_comp);
-                    } catch (const std::exception&) {       // (out of memory for the block list: the region goes the host route)
-                        sp.blks.clear();
-                        sp.bad = true;
-                    }
-                }
-            };
-            if (n_thr <= 1) {
-                work();
-            } else {
-                std::vector<std::thread> th;
-                for (int t = 1; t < n_thr; ++t) th.emplace_back(work);
-                work();
-                for (auto& x : th) x.join();
-            }
-        }
+        read_and_scan(stage, fd, bam, spans);
         tq[1] = now_ms();
         // ---- layout of the arena and the tables -------------------------------------------------------------------------------
         ChopLayout L;
@@ -1186,32 +1191,7 @@ extern "C" int vapor_bam_depth_device(vapor_ctx* ctx, vapor_bam* bam, int32_t n_
         InflateStage stage(sc);
         Block<> d_arena(sc);
         HIPCHK(stage.begin(plan.stage_bytes));
-        {
-            const int n_thr = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(vapor_bam_threads(bam), 1) * 2, spans.size() / 8 + 1));
-            std::atomic<size_t> next{0};
-            auto work = [&] {
-                for (;;) {
-                    const size_t i = next.fetch_add(1, std::memory_order_relaxed);
-                    if (i >= spans.size()) break;
-                    HostSpan& sp = spans[i];
-                    sp.got = stage.read(fd, sp.stage_off, sp.want, sp.file_off);
-                    try {
-                        vapor_bgzf::scan_span(sp, stage.h_comp);
-                    } catch (const std::exception&) {       // (out of memory for the block list: the region goes the host route)
-                        sp.blks.clear();
-                        sp.bad = true;
-                    }
-                }
-            };
-            if (n_thr <= 1) {
-                work();
-            } else {
-                std::vector<std::thread> th;
-                for (int t = 1; t < n_thr; ++t) th.emplace_back(work);
-                work();
-                for (auto& x : th) x.join();
-            }
-        }
+        read_and_scan(stage, fd, bam, spans);
         DepthLayout L;
         if (const Refusal r = layout(call, plan, status, L)) return fail(r.code, r.msg);
         const DepthMeta& M = L.meta;
@@ -1231,6 +1211,53 @@ extern "C" int vapor_bam_depth_device(vapor_ctx* ctx, vapor_bam* bam, int32_t n_
         HIPCHK(hipStreamSynchronize(st));
         sc.settled();
         collect(call, M, h_meta, cov, status);
+        return VAPOR_OK;
+    });
+}
+
+// Split-read and CIGAR evidence of many regions of an open BAM file (`--signatures`; vapor_readplan.h SigCall):
+// vapor_bam_depth_device's steps with another plan and another kernel - the regions' chunks staged, scanned, laid out, inflated
+// with CRC, then bam_signature_kernel, one wavefront a region, and one copy back.  Nothing stays on the device.
+extern "C" int vapor_bam_signature_device(vapor_ctx* ctx, vapor_bam* bam, int32_t n_regions, const int32_t* tid, const int64_t* regions,
+                                          const int32_t* chunk_first, const uint64_t* chunks, int64_t* out, int32_t* status)
+{
+    using namespace vapor_bamdev;
+    using namespace vapor_readplan;
+    if (!ctx || !bam) return fail(VAPOR_E_ARG, "vapor_bam_signature_device: bad argument");
+    SigCall call;
+    call.n_regions = n_regions; call.tid = tid; call.regions = regions; call.chunk_first = chunk_first; call.chunks = chunks;
+    if (const Refusal r = check_args(call, out, status)) return fail(r.code, r.msg);
+    const int fd = vapor_bam_fileno(bam);
+    if (fd < 0) return fail(VAPOR_E_ARG, "vapor_bam_signature_device: the file is not open");
+    call.filter_word = depth_filter_word(vapor_bam_filter_word(bam));
+    HIPCHK(hipSetDevice(ctx->device));
+    return guarded("vapor_bam_signature_device", [&]() -> int {
+        SpanPlan plan;
+        if (const Refusal r = plan_spans(call, status, plan)) return fail(r.code, r.msg);
+        CallScope sc(ctx, ctx->stream);
+        InflateStage stage(sc);
+        Block<> d_arena(sc);
+        HIPCHK(stage.begin(plan.stage_bytes));
+        read_and_scan(stage, fd, bam, plan.spans);
+        SigLayout L;
+        if (const Refusal r = layout(call, plan, status, L)) return fail(r.code, r.msg);
+        const SigMeta& M = L.meta;
+        const size_t n_blks = L.blks.size();
+        if (const int rc = stage.alloc(M.bytes, M.bytes)) return rc;
+        HIPCHK(d_arena.ensure(L.arena + 64));
+        uint8_t *const h_meta = stage.h_meta, *const d_meta = stage.d_meta;
+        L.fill(h_meta);
+        const hipStream_t st = sc.st = bam_stream_of(ctx);
+        if (const int rc = stage.run(n_blks, M.in_bytes, M.blks.in(d_meta), M.blk_status.in(d_meta), d_arena, ctx->bam_ev)) return rc;
+        if (n_regions) {
+            hipLaunchKernelGGL(bam_signature_kernel, dim3((unsigned)n_regions), dim3(64), 0, st, d_arena, M.regs.in(d_meta), M.spans.in(d_meta), M.blk_status.in(d_meta),
+                               (int)n_regions, M.ans.in(d_meta), M.reg_status.in(d_meta));
+            HIPCHK(hipGetLastError());
+        }
+        HIPCHK(hipMemcpyAsync(M.back(h_meta), M.back(d_meta), M.back_bytes(), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        sc.settled();
+        collect(call, M, h_meta, out, status);
         return VAPOR_OK;
     });
 }

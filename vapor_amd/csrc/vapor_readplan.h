@@ -473,6 +473,132 @@ inline void collect(const DepthCall& c, const DepthMeta& M, const uint8_t* h_met
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
+// vapor_bam_signature_device (`--signatures`)
+// ------------------------------------------------------------------------------------------------------------------------------
+constexpr int SIG_FIELDS = 9;              // a region as the caller gives it: w0, w3, x0, x1, tol, min_clip, nmin, nmax, mask
+struct SigCall {
+    int32_t n_regions = 0;
+    const int32_t* tid = nullptr;
+    const int64_t* regions = nullptr;      // SIG_FIELDS a region
+    const int32_t* chunk_first = nullptr;
+    const uint64_t* chunks = nullptr;
+    uint32_t filter_word = 0;              // the handle's read filter with DEPTH_EXCLUDE among its flags (depth_filter_word)
+};
+
+inline Refusal check_args(const SigCall& c, const int64_t* out, const int32_t* status)
+{
+    if (c.n_regions < 0 || (c.n_regions && (!c.tid || !c.regions || !c.chunk_first || !out || !status)))
+        return {VAPOR_E_ARG, "vapor_bam_signature_device: bad argument"};
+    return {};
+}
+
+// Whether a region's own fields are a question the readers answer: the window ascends from 0 and ends at a BAM position, the
+// tolerance fits the histograms, the length bounds ascend, the contig is one.  One statement for the device's plan and the host
+// reader (vapor_bam.cpp bam_signature_impl).
+inline bool sig_region_ok(int32_t tid, const int64_t* f)
+{
+    return f[0] >= 0 && f[1] >= f[0] && f[1] < ((int64_t)1 << 31) && f[4] >= 0 && f[4] <= SIG_TOL_MAX && f[6] <= f[7] && tid >= 0;
+}
+
+// The caller's fields as the kernel and the host reader take them: the length bounds clamped to [-1, 2^28] (no operation is
+// longer than 2^28 - 1, none shorter than 0: the clamped bounds admit the same operations), the minimum clip to [1, 2^30] (a
+// clip event has one clipped base at least; two operations sum to less than 2^29), the targets to +-2^40 (far from every
+// coordinate either way), the mask to its six bits.
+inline void sig_region_set(SigRegion& R, int32_t tid, const int64_t* f, uint32_t filter_word)
+{
+    const int64_t far = (int64_t)1 << 40;
+    R.w0 = f[0]; R.w3 = f[1];
+    R.x0 = std::min(std::max(f[2], -far), far); R.x1 = std::min(std::max(f[3], -far), far);
+    R.tol = (int32_t)f[4];
+    R.min_clip = (int32_t)std::min<int64_t>(std::max<int64_t>(f[5], 1), (int64_t)1 << 30);
+    R.nmin = (int32_t)std::min<int64_t>(std::max<int64_t>(f[6], -1), (int64_t)1 << 28);
+    R.nmax = (int32_t)std::min<int64_t>(std::max<int64_t>(f[7], -1), (int64_t)1 << 28);
+    R.mask = (uint32_t)f[8] & 63u;
+    R.tid = tid; R.filter = filter_word; R.pad = 0;
+}
+
+// The region rules: sig_region_ok - else REG_MALFORMED and the host route's to refuse.  The spans and the staging block as
+// plan_spans makes them.
+inline Refusal plan_spans(const SigCall& c, int32_t* status, SpanPlan& p)
+{
+    return plan_spans_of(c.n_regions, c.chunk_first, c.chunks, status, p, "vapor_bam_signature_device: more than 1.5 GB of blocks in one call (use smaller batches)",
+                         [&](int32_t g, int*) { return sig_region_ok(c.tid[g], c.regions + SIG_FIELDS * (size_t)g); });
+}
+
+// Where each table of a signature call lies in its metadata block: blocks, spans and regions go in; block status, the
+// SIG_ANSWER_WORDS words a region and the region status come back.
+struct SigMeta {
+    Table<BgzfBlk> blks;
+    Table<BamSpan> spans;
+    Table<SigRegion> regs;
+    Table<int32_t> blk_status;
+    Table<uint32_t> ans;                   // SIG_ANSWER_WORDS a region: six counts, then (offset, count) of each mode - the offsets are int32
+    Table<int32_t> reg_status;
+    size_t in_bytes = 0, bytes = 0;
+
+    SigMeta() = default;
+    SigMeta(int32_t n_regions, size_t n_blks, size_t n_spans)
+    {
+        const size_t nr = (size_t)std::max(n_regions, 1);
+        Carve m;
+        m.take(blks, std::max<size_t>(n_blks, 1));
+        m.take(spans, std::max<size_t>(n_spans, 1));
+        m.take(regs, nr);
+        in_bytes = m.off;
+        m.take(blk_status, std::max<size_t>(n_blks, 1));
+        m.take(ans, (size_t)SIG_ANSWER_WORDS * nr);
+        m.take(reg_status, nr);
+        bytes = m.off;
+    }
+    size_t back_bytes() const { return bytes - blk_status.off; }       // the host's block is the device's: [blk_status.off, bytes) comes back
+    template <typename B> B* back(B* block) const { return block + blk_status.off; }
+};
+
+struct SigLayout {
+    std::vector<BgzfBlk> blks;
+    std::vector<BamSpan> spans;
+    std::vector<SigRegion> regs;
+    size_t arena = 0;
+    SigMeta meta;
+    void fill(uint8_t* h_meta) const
+    {
+        if (!blks.empty()) memcpy(meta.blks.in(h_meta), blks.data(), sizeof(BgzfBlk) * blks.size());
+        if (!spans.empty()) memcpy(meta.spans.in(h_meta), spans.data(), sizeof(BamSpan) * spans.size());
+        memcpy(meta.regs.in(h_meta), regs.data(), sizeof(SigRegion) * regs.size());
+    }
+};
+
+inline Refusal layout(const SigCall& c, const SpanPlan& p, int32_t* status, SigLayout& L)
+{
+    if (const Refusal r = layout_of(c.n_regions, p, status, L.blks, L.spans, L.regs, &L.arena,
+                                    "vapor_bam_signature_device: more than 2 GB of block data in one call (use smaller batches)", [&](SigRegion& R, int32_t g) {
+            const int64_t* f = c.regions + SIG_FIELDS * (size_t)g;
+            // (a region the plan refused keeps a record that asks nothing: no kernel reads it, its span_n is 0)
+            if (status[g]) { R = SigRegion(); return; }
+            sig_region_set(R, c.tid[g], f, c.filter_word);
+        }))
+        return r;
+    L.meta = SigMeta(c.n_regions, L.blks.size(), L.spans.size());
+    return {};
+}
+
+// The read-back block into the caller's arrays: a region the host refused keeps its status and zeros, one the device refused
+// takes the device's status (its answer is then the host route's to make), the others their ten words - the offsets signed.
+inline void collect(const SigCall& c, const SigMeta& M, const uint8_t* h_meta, int64_t* out, int32_t* status)
+{
+    const uint32_t* da = M.ans.in(h_meta);
+    const int32_t* rst = M.reg_status.in(h_meta);
+    for (int32_t g = 0; g < c.n_regions; ++g) {
+        int64_t* o = out + (size_t)SIG_ANSWER_WORDS * (size_t)g;
+        for (int k = 0; k < SIG_ANSWER_WORDS; ++k) o[k] = 0;
+        if (status[g]) continue;
+        if (rst[g] != REG_OK) { status[g] = rst[g]; continue; }
+        const uint32_t* a = da + (size_t)SIG_ANSWER_WORDS * (size_t)g;
+        for (int k = 0; k < SIG_ANSWER_WORDS; ++k) o[k] = (k == 6 || k == 8) ? (int64_t)(int32_t)a[k] : (int64_t)a[k];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
 // vapor_fasta_windows_device
 // ------------------------------------------------------------------------------------------------------------------------------
 constexpr uint64_t ARENA_CAP = (uint64_t)1 << 30;       // inflated bytes of a call; a stretch that would pass it leaves its windows to the host

@@ -31,11 +31,24 @@ struct DepthRegion {      // `--depth`: three consecutive inter
     int32_t tid, span_first, span_n;
     uint32_t filter;      // the read filter as BamRegion::pad carries it, 0x704 already among the excluded flags
 };
+struct SigRegion {        // `--signatures`: the walk window [w0, w3) of a contig, two targets and what counts at them
+    int64_t w0, w3, x0, x1;
+    int32_t nmin, nmax;   // length bounds of GAP and INSOP, clamped to [-1, 2^28] (no operation is longer than 2^28 - 1)
+    int32_t tid, span_first, span_n;
+    uint32_t filter;      // the read filter as BamRegion::pad carries it, 0x704 already among the excluded flags
+    int32_t tol, min_clip;    // 0..255; 1..2^30
+    uint32_t mask;        // SIG_* bits
+    int32_t pad;
+};
 struct BamKept {          // a read the reference keeps: its packed bases at arena + sq_off, from base q0 on, miss_bp
     uint32_t sq_off;
     int32_t q0, miss, l_seq;
 };
 constexpr uint32_t DEPTH_EXCLUDE = 0x704u;   // what never counts towards depth: unmapped, secondary, QC-fail, duplicate (`samtools depth`)
+// `--signatures`: the event kinds of a region's mask and of its six counts, the widest tolerance (the histograms of a region are
+// 2 * (2 * SIG_TOL_MAX + 1) words of LDS), and the words of a region's answer: six counts, then offset and count of each mode
+constexpr uint32_t SIG_LCLIP0 = 1u, SIG_RCLIP0 = 2u, SIG_LCLIP1 = 4u, SIG_RCLIP1 = 8u, SIG_GAP = 16u, SIG_INSOP = 32u;
+constexpr int SIG_TOL_MAX = 255, SIG_HIST_WORDS = 2 * (2 * SIG_TOL_MAX + 1), SIG_ANSWER_WORDS = 10;
 constexpr int KEPT_CAP = 256;     // kept reads a region's slot holds (minimize_pacbio_read_list keeps 20 of them)
 // status of a region: 0, or why the host route must do it
 constexpr int REG_OK = 0, REG_BEYOND = 1, REG_MALFORMED = 2, REG_NO_CIGAR = 3, REG_KEPT_FULL = 4, REG_BLOCK = 5, REG_NEG_Q0 = 6, REG_NO_SEQ = 7;
@@ -74,7 +87,7 @@ struct BamSiteRange {     // a region's sites (in position order) and its table 
 };
 constexpr int PHASE_SETS_CAP = 64;     // phase sets a wavefront tallies: lane p holds the two counts of phase set p
 
-static_assert(sizeof(BgzfBlk) == 24 && sizeof(BamSpan) == 24 && sizeof(BamRegion) == 40 && sizeof(DepthRegion) == 48 && sizeof(BamKept) == 16 && sizeof(BamTag) == 16 &&
+static_assert(sizeof(BgzfBlk) == 24 && sizeof(BamSpan) == 24 && sizeof(BamRegion) == 40 && sizeof(DepthRegion) == 48 && sizeof(SigRegion) == 72 && sizeof(BamKept) == 16 && sizeof(BamTag) == 16 &&
               sizeof(BamPick) == 16 && sizeof(BamPhase) == 16 && sizeof(BamOps) == 16 && sizeof(BamSite) == 8 && sizeof(BamSiteRange) == 16,
               "the kernels index arrays of these, and the metadata block of a call is carved by their sizes");
 

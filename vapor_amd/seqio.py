@@ -77,6 +77,20 @@ class SamtoolsCLI:
             out.append(depth.cover(recs, b))
         return out
 
+    def signature_many(self, engine, bam: str, chroms, regions):
+        """The ten words per signature region (`--signatures`; chroms[g], regions[g] = signature.FIELDS):
+        signature.answer over POS and CIGAR of the alignment lines of `view`, filtered where they are read (_sam_fields) with
+        signature.EXCLUDE among the excluded flags."""
+        from . import signature
+        out = []
+        for chrom, rg in zip(chroms, regions):
+            if not rg[1] > rg[0]:
+                out.append([0] * 10)
+                continue
+            recs = [(int(f[3]), signature.parse_cigar(f[5])) for f in _sam_fields(self, bam, chrom, int(rg[0]) + 1, int(rg[1]), signature.EXCLUDE)]
+            out.append(signature.words(signature.answer(recs, rg)))
+        return out
+
 
 class FaiFasta:
     """In-process `samtools faidx ref chrom:start-end` through the .fai index (no process per locus)."""
@@ -620,31 +634,57 @@ class InProcessBam(SamtoolsHybrid):
         host reader (vapor_bam_depth).  A library without the entries, one without the read filter the file carries, or
         VAPOR_BAM_NATIVE=0: the Python statement, depth.cover over fetch_raw with depth.EXCLUDE added to the excluded flags.
         `engine`: an Engine, or None for the one of pipeline.get_engine() when the device is asked."""
+        from . import depth
+
+        def python(b, chrom, bd):
+            recs = [(r[1], r[2]) for r in b.fetch_raw(chrom, int(bd[0]) + 1, int(bd[3]), exclude_more=depth.EXCLUDE)]
+            return depth.cover(recs, bd)
+        return self._regions_many(engine, bam, chroms, bounds, 4, 0, 3, [0, 0, 0], ("vapor_bam_depth", "vapor_bam_depth_device"),
+                                  "bam_depth_device", "depth_native", python)
+
+    def signature_many(self, engine, bam: str, chroms, regions):
+        """The ten words per signature region (`--signatures`; chroms[g], regions[g] = signature.FIELDS) of a BAM
+        file: the six counts, then offset and count of each target's mode.  The routes are depth_many's: the device in groups
+        (vapor_bam_signature_device: bam_signature_kernel, one wavefront a region), a region it hands back and every region with
+        VAPOR_BAM_DEVICE=0 to the native host reader (vapor_bam_signature), and the Python statement - signature.answer over
+        fetch_raw with signature.EXCLUDE added to the excluded flags - for a library without the entries or VAPOR_BAM_NATIVE=0."""
+        from . import signature
+
+        def python(b, chrom, rg):
+            recs = [(r[1], r[2]) for r in b.fetch_raw(chrom, int(rg[0]) + 1, int(rg[1]), exclude_more=signature.EXCLUDE)]
+            return signature.words(signature.answer(recs, rg))
+        return self._regions_many(engine, bam, chroms, regions, len(signature.FIELDS), 0, 1, [0] * 10,
+                                  ("vapor_bam_signature", "vapor_bam_signature_device"), "bam_signature_device", "signature_native", python)
+
+    def _regions_many(self, engine, bam, chroms, rows, width, lo, hi, zero, entries, device, native, python):
+        """The routes of depth_many and signature_many.  rows[g]: the `width` integers of region g, its walk window
+        [rows[g][lo], rows[g][hi]); zero: the answer of a region without records (an unknown contig, an empty window);
+        entries: the library's host and device entry; device: the Engine's method, native: the BamFile's, python(b, chrom, row)
+        the Python statement."""
         import numpy as np
-        from . import _lib, depth
+        from . import _lib
         n = len(chroms)
         b = self._open(bam)
-        bounds = np.ascontiguousarray(bounds, dtype=np.int64).reshape(n, 4)
-        out = [[0, 0, 0] for _ in range(n)]
-        todo = [g for g in range(n) if chroms[g] in b.tid and bounds[g][3] > bounds[g][0]]
+        bounds = np.ascontiguousarray(rows, dtype=np.int64).reshape(n, width)
+        out = [list(zero) for _ in range(n)]
+        todo = [g for g in range(n) if chroms[g] in b.tid and bounds[g][hi] > bounds[g][lo]]
         lib = _lib.load()
-        if _env_is(b"VAPOR_BAM_NATIVE", b"0") or not hasattr(lib, "vapor_bam_depth") or not b.native_filter_ok():
+        if _env_is(b"VAPOR_BAM_NATIVE", b"0") or not hasattr(lib, entries[0]) or not b.native_filter_ok():
             for g in todo:
-                recs = [(r[1], r[2]) for r in b.fetch_raw(chroms[g], int(bounds[g][0]) + 1, int(bounds[g][3]), exclude_more=depth.EXCLUDE)]
-                out[g] = depth.cover(recs, bounds[g])
+                out[g] = python(b, chroms[g], bounds[g])
             return out
         tid_of, index_chunks = b.tid, b.index.chunks
-        chunks_of = {g: index_chunks(tid_of[chroms[g]], int(bounds[g][0]), int(bounds[g][3])) for g in todo}
+        chunks_of = {g: index_chunks(tid_of[chroms[g]], int(bounds[g][lo]), int(bounds[g][hi])) for g in todo}
         host = todo
         flags = lib.vapor_build_flags() or b""
-        if (todo and not _env_is(b"VAPOR_BAM_DEVICE", b"0") and hasattr(lib, "vapor_bam_depth_device")
+        if (todo and not _env_is(b"VAPOR_BAM_DEVICE", b"0") and hasattr(lib, entries[1])
                 and b"cpu-twin" not in flags.split(b",")):
             if engine is None:
                 from . import pipeline
                 engine = pipeline.get_engine()
         else:
             engine = None
-        if engine is not None and hasattr(engine, "bam_depth_device"):
+        if engine is not None and hasattr(engine, device):
             host = []
             m = len(todo)
             tids = np.asarray([tid_of[chroms[g]] for g in todo], dtype=np.int32)
@@ -677,7 +717,7 @@ class InProcessBam(SamtoolsHybrid):
                     a, e = groups.pop(0)
                     c0, c1 = int(chunk_first[a]), int(chunk_first[e])
                     try:
-                        cov, status = engine.bam_depth_device(tl["native"], tids[a:e], bt[a:e], chunk_first[a:e + 1] - c0, flat_a[c0:c1].reshape(-1))
+                        cov, status = getattr(engine, device)(tl["native"], tids[a:e], bt[a:e], chunk_first[a:e + 1] - c0, flat_a[c0:c1].reshape(-1))
                     except _lib.VaporHipError as err:
                         if "in one call" in str(err) and e - a >= 2:
                             groups[:0] = [(a, (a + e) // 2), ((a + e) // 2, e)]
@@ -695,7 +735,7 @@ class InProcessBam(SamtoolsHybrid):
                 with b._lock:
                     b._free.append(tl)
         for g in host:
-            out[g] = b.depth_native(tid_of[chroms[g]], bounds[g], chunks_of[g])
+            out[g] = getattr(b, native)(tid_of[chroms[g]], bounds[g], chunks_of[g])
         return out
 
     def isfile(self, path: str) -> bool:
@@ -1059,6 +1099,30 @@ class MemorySamtools:
             b0, b3 = int(b[0]), int(b[3])
             out.append(depth.cover([(r.pos, ops) for r, ops in zip(recs, got[2])
                                     if b0 < b3 and r.pos - 1 < b3 and record_passes(r.mapq, r.flag, q, f)], b))
+        return out
+
+    def signature_many(self, engine, bam: str, chroms, regions):
+        """The ten words per signature region (`--signatures`) from the world's records that pass the read filter
+        with signature.EXCLUDE among its flags: signature.answer over (POS, operations) of the records that start before w3 and
+        do not end before w0, every CIGAR text parsed once per record list."""
+        from . import signature
+        from .bamio import record_passes
+        q, f = self.read_filter
+        f |= signature.EXCLUDE
+        cache = self.__dict__.setdefault("_depth_cache", {})
+        out = []
+        for chrom, rg in zip(chroms, regions):
+            recs = self.world.reads.get(chrom, ())
+            got = cache.get(id(recs))
+            if got is None or got[0] is not recs or got[1] != len(recs):
+                got = (recs, len(recs), [signature.parse_cigar(r.cigar) for r in recs])
+                if getattr(self.world, "cache_ok", True):
+                    if len(cache) > 200000:
+                        cache.clear()
+                    cache[id(recs)] = got
+            w0, w3 = int(rg[0]), int(rg[1])
+            out.append(signature.words(signature.answer([(r.pos, ops) for r, ops in zip(recs, got[2])
+                                                         if w0 < w3 and r.pos - 1 < w3 and record_passes(r.mapq, r.flag, q, f)], rg)))
         return out
 
     def fai_lines(self, ref: str) -> Iterable[str]:

@@ -766,6 +766,149 @@ def make_depth_world(seed: int, specs: Sequence[Tuple[str, int, str]] = DEPTH_SP
     return w
 
 
+SIGNATURE_SPECS = (("DEL", 600, "hom"), ("DEL", 1500, "het"), ("DEL", 6000, "het"), ("DEL", 12000, "hom"), ("TANDUP", 300, "het"),
+                   ("TANDUP", 4000, "hom"), ("TANDUP", 15000, "het"), ("INV", 700, "het"), ("INV", 11000, "hom"), ("INS", 250, "het"),
+                   ("INS", 3000, "hom"))
+
+
+def make_signature_world(seed: int, specs: Sequence[Tuple[str, int, str]] = SIGNATURE_SPECS, layers: int = 4, read_len: int = 1000,
+                         margin: int = 3000, short: int = 2000, guard: int = 100, jitter: Sequence[int] = (0,),
+                         chrom_prefix: str = "s") -> SynthWorld:
+    """A world whose split reads and CIGARs mean something (`--signatures`).  Per spec (svtype, span L, 'hom' |
+    'het') a contig with the event on bases [margin + 1, margin + L] (an INS of L bases behind base `margin`, on a contig of
+    2 * margin bases), and two haplotypes tiled with error-free reads as make_depth_world tiles them: `layers` layers a
+    haplotype, 'het' one reference and one alt haplotype, 'hom' two alt haplotypes.  A cut that falls less than `guard` bases
+    from a junction of the alt haplotype - for an event of at most `short` bases: anywhere from `guard` before the event to
+    `guard` behind it - is left out, so that exactly one read of every layer crosses each junction, with `guard` bases at least
+    on either side.  That read is aligned as a mapper reports it:
+      DEL, L <= short: one record with an L D at cursor margin; longer: the piece left of the junction with the rest soft-clipped
+        and the piece right of it likewise, the longer the primary and the other a supplementary record (0x800);
+      TANDUP, L <= short: one record with an L I at cursor margin (left-aligned); longer: the piece that ends at margin + L and
+        the piece that starts at margin, clipped primary and supplementary;
+      INS, L <= short: one record with an L I at cursor margin; longer: the flanking pieces with the inserted bases soft-clipped
+        (a read inside the insertion is not aligned and not in the file);
+      INV: at each junction a forward piece and a reverse-strand piece (0x10), each with the rest soft-clipped.
+    jitter: the alt reads of layer k report their breakpoints jitter[k % len(jitter)] bases to the right (a negative number: to
+    the left), as alignments in a repeat do - so that the histograms have more than one bin.  With A = 1 ('het') or 2 ('hom')
+    alt haplotypes every locus has A * layers reads at each junction, and its six columns are known in closed form:
+      D / I carriers: L = R = 0, CG = A * layers;  split DEL, TANDUP, INS: L = R = A * layers, CG = 0;  INV: L = R = 2 * A * layers."""
+    rng = np.random.default_rng(seed)
+    w = SynthWorld()
+    for li, (t, span, zyg) in enumerate(specs):
+        c = "%s%d" % (chrom_prefix, li + 1)
+        t = "TANDUP" if t == "DUP" else t
+        span = int(span)
+        s0 = margin
+        e0 = margin + (span if t != "INS" else 0)       # the event, 0-based half-open
+        n = e0 + margin
+        ref = w.contigs[c] = random_dna(rng, n)
+        ins_seq = random_dna(rng, span) if t == "INS" else None
+        # the alt haplotype's segments: (ref start, ref end, strand) or (None, inserted bases, '+')
+        if t == "DEL":
+            alt = [(0, s0, "+"), (e0, n, "+")]
+        elif t == "TANDUP":
+            alt = [(0, e0, "+"), (s0, n, "+")]
+        elif t == "INV":
+            alt = [(0, s0, "+"), (s0, e0, "-"), (e0, n, "+")]
+        elif t == "INS":
+            alt = [(0, s0, "+"), (None, ins_seq, "+"), (s0, n, "+")]
+        else:
+            raise ValueError(t)
+        plain = [(0, n, "+")]
+        haps = [alt, alt] if zyg == "hom" else [plain, alt]
+        small = span <= short and t != "INV"
+        recs = w.reads.setdefault(c, [])
+        for h, segs in enumerate(haps):
+            # the haplotype's segments in its own coordinates: (hap start, hap end, segment)
+            at, table = 0, []
+            for sg in segs:
+                ln = len(sg[1]) if sg[0] is None else sg[1] - sg[0]
+                table.append((at, at + ln, sg))
+                at += ln
+            m = at
+            joints = [p1 for _p0, p1, _sg in table[:-1]]
+            if segs is plain:
+                zones = []
+            elif small:
+                zones = [(joints[0] - guard - (span if t == "TANDUP" else 0), joints[-1] + guard + (span if t == "TANDUP" else 0))]
+            else:
+                zones = [(j - guard, j + guard) for j in joints]
+            for k in range(layers):
+                d = int(jitter[k % len(jitter)]) if segs is not plain else 0
+                cuts = sorted({0, m} | {x for x in range((k * read_len) // layers, m, read_len) if not any(lo < x < hi for lo, hi in zones)})
+                for ri, (a, z) in enumerate(zip(cuts[:-1], cuts[1:])):
+                    qname = "%s_h%d_l%d_r%d" % (c, h, k, ri)
+                    pieces = []                       # (segment, offset of the piece in it, length)
+                    for p0, p1, sg in table:
+                        lo, hi = max(a, p0), min(z, p1)
+                        if hi > lo:
+                            pieces.append((sg, lo - p0, hi - lo))
+                    seqs = []
+                    for sg, off, ln in pieces:
+                        if sg[0] is None:
+                            seqs.append(sg[1][off:off + ln])
+                        elif sg[2] == "+":
+                            seqs.append(ref[sg[0] + off:sg[0] + off + ln])
+                        else:
+                            seqs.append(revcomp(ref[sg[0]:sg[1]])[off:off + ln])
+                    seq = "".join(seqs)
+                    if len(pieces) == 1:
+                        sg, off, ln = pieces[0]
+                        if sg[0] is None:
+                            continue                  # (inside a long insertion: not aligned)
+                        if sg[2] == "+":
+                            recs.append(SamRecord(qname, c, sg[0] + off + 1, "%dM" % ln, seq, ln))
+                        else:
+                            lo = sg[1] - off - ln
+                            recs.append(SamRecord(qname, c, lo + 1, "%dM" % ln, revcomp(seq), ln, flag=0x10))
+                        continue
+                    if small:
+                        # one record: the bases left of the event, the event as one operation, the bases right of it
+                        lo = pieces[0][0][0] + pieces[0][1]
+                        if t == "DEL":
+                            left, right = pieces[0][2], pieces[1][2]
+                            cg = "%dM%dD%dM" % (left + d, span, right - d)
+                            rspan = left + span + right
+                        elif t == "INS":
+                            left, right = pieces[0][2], pieces[2][2]
+                            cg = "%dM%dI%dM" % (left + d, span, right - d)
+                            rspan = left + right
+                        else:                         # TANDUP: the first copy is the inserted one (left-aligned)
+                            left = s0 - lo
+                            right = len(seq) - left - span
+                            cg = "%dM%dI%dM" % (left + d, span, right - d)
+                            rspan = left + right
+                        recs.append(SamRecord(qname, c, lo + 1, cg, seq, rspan))
+                        continue
+                    # split: a record per aligned piece, the rest of the read soft-clipped; the longest is the primary.  The
+                    # jitter moves a breakpoint to the right: the piece left of it d bases longer, the one right of it d shorter
+                    aligned = [i for i, pc in enumerate(pieces) if pc[0][0] is not None]
+                    main = max(aligned, key=lambda i: (pieces[i][2], -i))
+                    for i in aligned:
+                        sg, off, ln = pieces[i]
+                        before = sum(pc[2] for pc in pieces[:i])
+                        after = sum(pc[2] for pc in pieces[i + 1:])
+                        gl = -d if before else 0      # the piece's left end in the read moves right by d: it loses d bases there
+                        gr = d if after else 0        # ... its right end moves right by d: it gains d bases there
+                        before, ln, after = before - gl, ln + gl + gr, after - gr
+                        flag = 0 if i == main else 0x800
+                        if sg[2] == "+":
+                            lo = sg[0] + off - gl
+                            cg = ("%dS" % before if before else "") + "%dM" % ln + ("%dS" % after if after else "")
+                            recs.append(SamRecord(qname, c, lo + 1, cg, seq, ln, flag=flag))
+                        else:
+                            # the reverse strand: the read's left end is the record's right end
+                            hi = sg[1] - off + gl
+                            cg = ("%dS" % after if after else "") + "%dM" % ln + ("%dS" % before if before else "")
+                            recs.append(SamRecord(qname, c, hi - ln + 1, cg, revcomp(seq), ln, flag=flag | 0x10))
+        recs.sort(key=lambda r: r.pos)
+        if t == "INS":
+            w.loci.append(Locus(c, t, s0, s0 + 1, "sg%d" % (li + 1), ins_seq))
+        else:
+            w.loci.append(Locus(c, t, s0 + 1, e0, "sg%d" % (li + 1)))
+    return w
+
+
 def mirror_world(world: SynthWorld) -> SynthWorld:
     """M(W): the world as its reverse-complemented contigs hold it (x -> L + 1 - x on a contig of L bases; `--both-ends`,
     DESIGN.md 4.14).  Contigs: their reverse complement (seqio.rc_read: nothing is dropped).  Records: seqio.mirror_records -
