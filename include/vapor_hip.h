@@ -521,6 +521,29 @@ int vapor_bam_depth_device(vapor_ctx* ctx, vapor_bam* bam, int32_t n_regions, co
 int vapor_bam_signature(vapor_bam* bam, int32_t tid, const int64_t* fields, int32_t n_chunks, const uint64_t* chunks, int64_t* out);
 int vapor_bam_signature_device(vapor_ctx* ctx, vapor_bam* bam, int32_t n_regions, const int32_t* tid, const int64_t* regions,
                                const int32_t* chunk_first, const uint64_t* chunks, int64_t* out, int32_t* status);
+/*
+ * Split reads joined through their SA tags (`--links`; not in the reference).  A link region is a contig and
+ * eleven fields: w0, w3 (the walk window [w0, w3), 0-based), x (the local target), y (the partner target), tol (0..255),
+ * min_clip, ev (0: LCLIP, 1: RCLIP), pend (0: the entry's a, 1: its b), rel (0: the entry's strand is the record's, 1: it is the
+ * other), name_off, name_len (the partner contig's name, bytes [name_off, name_off + name_len) of `names`, one blob for all the
+ * regions of a call).  A record counts and has clip events as for vapor_bam_signature.  A clip record has event ev with
+ * |coordinate - x| <= tol.  Its entries are the well-formed pieces of the value of its first aux field named SA, when that is of
+ * type Z - rname,pos,strand,CIGAR,mapQ,NM; per piece, a = pos - 1, b = a + the lengths of M D N = X - with mapQ at or above the
+ * handle's minimum MAPQ; an entry matches when its rname is the partner's name byte for byte, the strand relation holds and
+ * |c - y| <= tol for c = a or b by pend.  out, five a region: n_clip, n_split (clip records with an entry), n_link (clip records
+ * with a matching entry), then offset and count of the mode of the histogram of c - y of every linked record's first matching
+ * entry (the tie rule of vapor_bam_signature).
+ * vapor_bam_links: one region on the host, `chunks` its .bai chunks as in vapor_bam_depth; errors as there.  VAPOR_E_ARG for
+ * w0 < 0, w0 > w3, w3 >= 2^31, tol outside 0..255, ev, pend or rel outside 0..1, an empty name or one outside `names`, tid < 0.
+ * vapor_bam_links_device: n_regions regions in one call as vapor_bam_depth_device takes them (regions: eleven a region, out:
+ * five a region) - bam_link_kernel, one wavefront a region; `names` is uploaded once.  status[g] = 0, or a positive code of
+ * vapor_bam_chop_device's where the region is the host route's - a record whose aux area is malformed among them (its words are
+ * 0 then).  Nothing stays on the device.
+ */
+int vapor_bam_links(vapor_bam* bam, int32_t tid, const int64_t* fields, const uint8_t* names, int64_t names_len, int32_t n_chunks,
+                    const uint64_t* chunks, int64_t* out);
+int vapor_bam_links_device(vapor_ctx* ctx, vapor_bam* bam, int32_t n_regions, const int32_t* tid, const int64_t* regions, const uint8_t* names,
+                           int64_t names_len, const int32_t* chunk_first, const uint64_t* chunks, int64_t* out, int32_t* status);
 /* what the context's last vapor_bam_chop_device (or _tagged) did, for measurement (bench.py): out[0..6] = regions, BGZF blocks,
  * compressed bytes sent over the link, inflated bytes, the inflate kernel's duration between two events on its stream (ms), the
  * whole call (ms), bytes of kept reads and statuses copied back from the device */

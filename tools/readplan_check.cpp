@@ -1282,6 +1282,156 @@ static void check_signature()
            n_calls, n_regions_seen, n_refused);
 }
 
+// ================================================================================================================================
+// vapor_bam_links_device: LinkCall's plan over the same plan_spans_of / layout_of, with the name blob
+// ================================================================================================================================
+static void check_links()
+{
+    long n_calls = 0, n_refused = 0, n_regions_seen = 0;
+    for (int it = 0; it < 1000; ++it) {
+        g_case = it;
+        const int n = one_in(15) ? 0 : rnd(1, 12);
+        const int64_t names_len = one_in(10) ? 0 : rnd(1, 400);
+        std::vector<uint8_t> names((size_t)names_len);
+        for (auto& ch : names) ch = (uint8_t)rnd(33, 126);
+        std::vector<int32_t> tid((size_t)n), chunk_first((size_t)n + 1, 0);
+        std::vector<int64_t> fields((size_t)LINK_FIELDS * (size_t)n);
+        std::vector<uint64_t> chunks;
+        std::vector<char> bad((size_t)n, 0);
+        for (int g = 0; g < n; ++g) {
+            int64_t* f = fields.data() + (size_t)LINK_FIELDS * (size_t)g;
+            tid[(size_t)g] = rnd(0, 30);
+            f[0] = one_in(6) ? 0 : rnd(0, 1 << 30);
+            f[1] = f[0] + (one_in(5) ? 0 : rnd(0, 200));
+            if (one_in(10)) f[1] = ((int64_t)1 << 31) - 1;
+            f[2] = one_in(8) ? ((int64_t)1 << 50) : f[0] + rnd(-300, 300);
+            f[3] = one_in(8) ? -((int64_t)1 << 50) : rnd(0, 1 << 30);
+            f[4] = one_in(4) ? (one_in(2) ? 0 : 255) : rnd(0, 255);
+            f[5] = one_in(5) ? rnd(-5, 0) : rnd(1, 100);
+            f[6] = rnd(0, 1); f[7] = rnd(0, 1); f[8] = rnd(0, 1);
+            f[10] = names_len ? rnd(1, (int)names_len) : 1;
+            f[9] = names_len ? rnd(0, (int)(names_len - f[10])) : 0;
+            for (int k = rnd(0, 3); k > 0; --k) {
+                const uint64_t c0 = (uint64_t)rnd(0, 1 << 28), len = one_in(4) ? 0 : (uint64_t)rnd(0, 300000);
+                const uint64_t u0 = (uint64_t)rnd(0, 65535), u1 = len == 0 ? (uint64_t)rnd((int)u0, 65535) : (uint64_t)rnd(0, 65535);
+                chunks.push_back(c0 << 16 | u0); chunks.push_back((c0 + len) << 16 | u1);
+            }
+            chunk_first[(size_t)g + 1] = (int32_t)(chunks.size() / 2);
+            // 1 w0 < 0; 2 w0 > w3; 3 w3 = 2^31; 4 tol < 0; 5 tol > 255; 6 ev; 7 pend; 8 rel; 9 an empty name; 10 a name past the blob;
+            // 11 a negative offset; 12 tid < 0
+            const int how = one_in(3) ? rnd(1, 12) : 0;
+            if (how == 1) f[0] = -1 - rnd(0, 5);
+            if (how == 2) f[0] = f[1] + 1 + rnd(0, 9);
+            if (how == 3) f[1] = (int64_t)1 << 31;
+            if (how == 4) f[4] = -1 - rnd(0, 3);
+            if (how == 5) f[4] = 256 + rnd(0, 1000);
+            if (how >= 6 && how <= 8) f[how] = one_in(2) ? 2 + rnd(0, 5) : -1 - rnd(0, 5);
+            if (how == 9) f[10] = 0;
+            if (how == 10) f[10] = names_len - f[9] + 1 + rnd(0, 5);
+            if (how == 11) f[9] = -1 - rnd(0, 5);
+            if (how == 12) tid[(size_t)g] = -1 - rnd(0, 3);
+            bad[(size_t)g] = how != 0 || names_len == 0;
+            // the one statement, against the rule spelled out
+            CHECK(link_region_ok(tid[(size_t)g], f, names_len) == !bad[(size_t)g], "region %d: link_region_ok, how %d", g, how);
+        }
+        LinkCall c;
+        c.n_regions = n; c.tid = tid.data(); c.regions = fields.data(); c.names = names_len ? names.data() : nullptr; c.names_len = names_len;
+        c.chunk_first = chunk_first.data(); c.chunks = chunks.empty() ? nullptr : chunks.data();
+        c.filter_word = depth_filter_word((uint32_t)rnd(0, 65535) | ((uint32_t)rnd(0, 255) << 16));
+        std::vector<int64_t> out((size_t)LINK_ANSWER_WORDS * (size_t)std::max(n, 1), 77);
+        std::vector<int32_t> status((size_t)std::max(n, 1), -9);
+        CHECK(!check_args(c, out.data(), status.data()), "a good call is refused");
+        if (n) {
+            CHECK(check_args(c, nullptr, status.data()).code == VAPOR_E_ARG && check_args(c, out.data(), nullptr).code == VAPOR_E_ARG, "null outputs pass");
+            LinkCall d = c; d.names_len = -1;
+            CHECK(check_args(d, out.data(), status.data()).code == VAPOR_E_ARG, "a negative blob passes");
+            if (names_len) { d = c; d.names = nullptr; CHECK(check_args(d, out.data(), status.data()).code == VAPOR_E_ARG, "a null blob passes"); }
+        }
+        SpanPlan p;
+        CHECK(!plan_spans(c, status.data(), p), "a call below the size limit is refused");
+        for (int g = 0; g < n; ++g) {
+            CHECK(status[(size_t)g] == (bad[(size_t)g] ? REG_MALFORMED : 0), "region %d: status %d, bad %d", g, status[(size_t)g], (int)bad[(size_t)g]);
+            n_refused += bad[(size_t)g];
+        }
+        for (HostSpan& sp : p.spans) fake_scan(sp);
+        LinkLayout L;
+        CHECK(!layout(c, p, status.data(), L), "a layout below the size limit is refused");
+        CHECK((int)L.regs.size() == std::max(n, 1), "regions in the layout");
+        size_t n_sp = 0;
+        for (int g = 0; g < n; ++g) {
+            const LinkRegion& R = L.regs[(size_t)g];
+            const int64_t* f = fields.data() + (size_t)LINK_FIELDS * (size_t)g;
+            CHECK(R.span_first == (int32_t)n_sp, "region %d: span_first in the layout", g);
+            if (status[(size_t)g]) {
+                CHECK(R.span_n == 0 && R.name_len == 0 && R.tol == 0 && R.w0 == 0 && R.w3 == 0 && R.bits == 0, "region %d: a refused region's record", g);
+                continue;
+            }
+            const int64_t far = (int64_t)1 << 40;
+            CHECK(R.tid == tid[(size_t)g] && R.filter == c.filter_word && R.w0 == f[0] && R.w3 == f[1] && R.tol == f[4], "region %d: its record", g);
+            CHECK(R.x == (f[2] > far ? far : f[2]) && R.y == (f[3] < -far ? -far : f[3]) && R.min_clip == (f[5] < 1 ? 1 : f[5]), "region %d: clamped fields", g);
+            CHECK(R.bits == ((uint32_t)f[6] | (uint32_t)f[7] << 1 | (uint32_t)f[8] << 2) && R.name_off == (uint32_t)f[9] && R.name_len == (uint32_t)f[10], "region %d: bits and name", g);
+            CHECK((uint64_t)R.name_off + R.name_len <= (uint64_t)names_len, "region %d: its name leaves the blob", g);
+            CHECK(R.span_n == p.span_first[(size_t)g + 1] - p.span_first[(size_t)g], "region %d: span_n", g);
+            n_sp += (size_t)R.span_n;
+        }
+        const LinkMeta& M = L.meta;
+        const size_t nr = (size_t)std::max(n, 1), nb = std::max<size_t>(L.blks.size(), 1), ns = std::max<size_t>(L.spans.size(), 1);
+        const size_t offs[7] = {M.blks.off, M.spans.off, M.regs.off, M.names.off, M.blk_status.off, M.ans.off, M.reg_status.off};
+        const size_t sizes[7] = {24 * nb, 24 * ns, 72 * nr, std::max<size_t>((size_t)names_len, 1), 4 * nb, 20 * nr, 4 * nr};
+        size_t at = 0;
+        for (int t = 0; t < 7; ++t) { CHECK(offs[t] == at && at % 64 == 0, "table %d at %zu, not %zu", t, offs[t], at); at += up64(sizes[t]); }
+        CHECK(M.bytes == at && M.in_bytes == M.blk_status.off && M.back_bytes() == M.bytes - M.blk_status.off, "the block's sizes");
+        std::vector<uint8_t> h(M.bytes, 0xEE);
+        L.fill(h.data());
+        CHECK(!memcmp(M.regs.in(h.data()), L.regs.data(), 72 * nr) && (!names_len || !memcmp(M.names.in(h.data()), names.data(), (size_t)names_len)), "fill");
+        uint32_t* da = M.ans.in(h.data());
+        int32_t* rs = M.reg_status.in(h.data());
+        for (size_t g = 0; g < nr; ++g) {
+            for (int k = 0; k < LINK_ANSWER_WORDS; ++k) da[(size_t)LINK_ANSWER_WORDS * g + (size_t)k] = (uint32_t)rng();
+            da[(size_t)LINK_ANSWER_WORDS * g + 3] = (uint32_t)(int32_t)rnd(-255, 255);
+            rs[g] = one_in(5) ? rnd(1, 5) : 0;
+        }
+        std::vector<int32_t> st2 = status;
+        collect(c, M, h.data(), out.data(), st2.data());
+        for (int g = 0; g < n; ++g) {
+            const bool host_refused = status[(size_t)g] != 0, dev_refused = rs[(size_t)g] != 0;
+            CHECK(st2[(size_t)g] == (host_refused ? status[(size_t)g] : rs[(size_t)g]), "region %d: collected status", g);
+            for (int k = 0; k < LINK_ANSWER_WORDS; ++k) {
+                const uint32_t wd = da[(size_t)LINK_ANSWER_WORDS * (size_t)g + (size_t)k];
+                const int64_t want = host_refused || dev_refused ? 0 : (k == 3 ? (int64_t)(int32_t)wd : (int64_t)wd);
+                CHECK(out[(size_t)LINK_ANSWER_WORDS * (size_t)g + (size_t)k] == want, "region %d: word %d", g, k);
+            }
+        }
+        ++n_calls;
+        n_regions_seen += n;
+    }
+    // the two "in one call" refusals the Python side halves a group on
+    {
+        std::vector<int32_t> tid(40, 0), chunk_first(41), status(40);
+        std::vector<int64_t> fields;
+        std::vector<uint64_t> chunks;
+        const uint8_t names[2] = {'c', '1'};
+        for (int g = 0; g < 40; ++g) {
+            for (int64_t v : {0, 100, 40, 60, 50, 30, 1, 0, 0, 0, 2}) fields.push_back(v);
+            chunks.push_back((uint64_t)g << 44); chunks.push_back(((uint64_t)g << 44) + (((uint64_t)1 << 26) << 16));
+            chunk_first[(size_t)g + 1] = g + 1;
+        }
+        LinkCall c;
+        c.n_regions = 40; c.tid = tid.data(); c.regions = fields.data(); c.names = names; c.names_len = 2; c.chunk_first = chunk_first.data(); c.chunks = chunks.data();
+        SpanPlan p;
+        const Refusal r = plan_spans(c, status.data(), p);
+        CHECK(r.code == VAPOR_E_ARG && strstr(r.msg, "vapor_bam_links_device") && strstr(r.msg, "in one call"), "2.5 GB of blocks pass");
+        c.n_regions = 20;
+        CHECK(!plan_spans(c, status.data(), p), "1.25 GB of blocks are refused");
+        for (HostSpan& sp : p.spans) { sp.blks.push_back(Block{0, 6, 100, 0, 65536, 0}); sp.u_total = (uint64_t)120 << 20; sp.u_begin = 0; sp.u_end = 100; sp.got = sp.want; }
+        LinkLayout L;
+        const Refusal r2 = layout(c, p, status.data(), L);
+        CHECK(r2.code == VAPOR_E_ARG && strstr(r2.msg, "vapor_bam_links_device") && strstr(r2.msg, "in one call"), "2.4 GB of block data pass");
+    }
+    printf("links plan: %ld calls with %ld regions (%ld refused): statuses, tables, the name blob, clamped fields and collected words equal the rule; both size refusals say \"in one call\"\n",
+           n_calls, n_regions_seen, n_refused);
+}
+
 int main()
 {
     check_statuses();
@@ -1292,6 +1442,7 @@ int main()
     check_fasta_caps();
     check_depth();          // (behind the others: the calls above draw from the one seeded stream, and their counts are quoted)
     check_signature();
+    check_links();
     printf("readplan_check: all equal\n");
     return 0;
 }

@@ -512,6 +512,91 @@ class BamFile:
                 self._free.append(tl)
         return [int(x) for x in out]
 
+    def links_native(self, tid: int, region, chunks=None, names: bytes = b""):
+        """The five words of one link region (`--links`; region: links.FIELDS, then offset and length of the
+        partner contig's name in `names`) through the library's host reader (vapor_bam_links); the .bai lookup stays here.
+        ValueError with the reader's message for a file that breaks a rule or a region the reader refuses."""
+        from . import _lib
+        lib = _lib.load()
+        r = np.ascontiguousarray(region, dtype=np.int64)
+        ch = self.index.chunks(tid, int(r[0]), int(r[1])) if chunks is None and tid >= 0 and 0 <= r[0] <= r[1] else (chunks or [])
+        out = np.zeros(5, dtype=np.int64)
+        flat = np.asarray(ch, dtype=np.uint64).reshape(-1)
+        names = bytes(names)
+        tl = self._take_handle(lib)
+        try:
+            if lib.vapor_bam_links(tl["native"], int(tid), r.ctypes.data, names, len(names), len(flat) // 2,
+                                   flat.ctypes.data if len(flat) else None, out.ctypes.data) != 0:
+                raise ValueError(lib.vapor_bam_last_error().decode())
+        finally:
+            with self._lock:
+                self._free.append(tl)
+        return [int(x) for x in out]
+
+    @staticmethod
+    def sa_of_aux(rec: bytes, p: int):
+        """The SA value of a record whose aux fields start at byte p (`--links`): the bytes before the NUL of
+        the first aux field named SA when its type is Z; None when there is none, when its type is another, or when the area is
+        malformed before one is found (phase.tags_from_aux's walk: what stood before the damage stands)."""
+        n = len(rec)
+        size = {"A": 1, "c": 1, "C": 1, "s": 2, "S": 2, "i": 4, "I": 4, "f": 4}
+        while p + 3 <= n:
+            tag, typ = rec[p:p + 2], chr(rec[p + 2])
+            p += 3
+            if tag == b"SA" and typ != "Z":
+                return None
+            if typ in size:
+                if size[typ] > n - p:
+                    return None
+                p += size[typ]
+            elif typ in "ZH":
+                e = rec.find(b"\x00", p)
+                if e < 0:
+                    return None
+                if tag == b"SA":
+                    return bytes(rec[p:e])
+                p = e + 1
+            elif typ == "B":
+                if p + 5 > n:
+                    return None
+                sub, cnt = chr(rec[p]), struct.unpack_from("<i", rec, p + 1)[0]
+                p += 5
+                es = 1 if sub in "cC" else 2 if sub in "sS" else 4
+                if cnt < 0 or cnt * es > n - p:
+                    return None
+                p += cnt * es
+            else:
+                return None
+        return None
+
+    def fetch_links(self, chrom: str, start: int, end: int, exclude_more: int = 0):
+        """(1-based POS, CIGAR operations, FLAG, SA value or None) of the alignments fetch_raw lists for the region - what
+        links.answer takes (`--links`): fetch_raw's tuple stays what it is, a record's SA value is handed out here."""
+        tid = self.tid.get(chrom)
+        if tid is None:
+            return []
+        beg, stop = max(start - 1, 0), end
+        min_mapq, exclude = self.read_filter
+        exclude |= exclude_more
+        out = []
+        for cs, ce in self.index.chunks(tid, beg, stop):
+            cur = self.bgzf.read_from(cs)
+            while cur.tell() < ce:
+                hdr = cur.read(4)
+                if len(hdr) < 4:
+                    break
+                rec = cur.read(struct.unpack("<i", hdr)[0])
+                ref_id, pos, l_name, mapq, _bin, n_cig, flag, l_seq = struct.unpack_from("<iiBBHHHi", rec, 0)
+                if ref_id != tid or pos >= stop:
+                    if ref_id > tid or (ref_id == tid and pos >= stop):
+                        break
+                    continue
+                if not record_passes(mapq, flag, min_mapq, exclude):
+                    continue
+                cig = self._parse(rec)[4]
+                out.append((pos + 1, cig, flag, self.sa_of_aux(rec, 32 + l_name + 4 * n_cig + (l_seq + 1) // 2 + l_seq)))
+        return out
+
     def fetch_raw(self, chrom: str, start: int, end: int, sites=None, exclude_more: int = 0):
         """(QNAME, 1-based POS, CIGAR operations as a uint32 tuple, packed SEQ bytes, l_seq, FLAG, (hap, ps)) of the alignments
         that overlap the 1-based inclusive region, in file order; nothing is decoded to text.  (hap, ps): the record's

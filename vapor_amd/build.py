@@ -19,7 +19,7 @@ SOURCES = [os.path.join(CSRC, "vapor_hip.hip"), os.path.join(CSRC, "vapor_bam.cp
 _HEADERS = [("vapor_kernels.h", True), ("vapor_wide.h", True), ("vapor_anyk.h", True), ("vapor_inflate.h", False),
             ("vapor_bamdev.h", True), ("vapor_fasta.h", True), ("vapor_refine.h", True), ("vapor_bgzf.h", False),
             ("vapor_records.h", True), ("vapor_planner.h", False), ("vapor_names.h", True),
-            ("vapor_readrec.h", True), ("vapor_readplan.h", False)]
+            ("vapor_readrec.h", True), ("vapor_readplan.h", False), ("vapor_sa.h", False)]
 DEPS = SOURCES + [os.path.join(CSRC, h) for h, _dev in _HEADERS] + [os.path.join(ROOT, "include", "vapor_hip.h")]
 KERNEL_FILES = [os.path.join(CSRC, h) for h, dev in _HEADERS if dev] + [SOURCES[0], os.path.abspath(__file__)]
 

@@ -28,8 +28,13 @@ the plain run's; not together with --refine, --phased, --phase-vcf or --both-end
 at its breakpoints, those that carry it as a D, N or I, and the modal breakpoints they give; appends VaPoR_SIG_L, VaPoR_SIG_R,
 VaPoR_SIG_CG, VaPoR_SIG_N, VaPoR_SIG_POS and VaPoR_SIG_END; the row's own columns are the plain run's; not together with another
 of these modes.
+--links (bed, vcf): split reads joined through their SA tags, per DEL, TANDUP and INV call and per breakend of
+--bnd - the alignments clipped at a breakpoint whose SA tag names a piece at the call's other breakpoint, on the strand the event
+gives it; those that are split but go elsewhere; and the modal coordinates the linked pieces name; appends VaPoR_LNK_L,
+VaPoR_LNK_R, VaPoR_LNK_N, VaPoR_LNK_OL, VaPoR_LNK_OR, VaPoR_LNK_POS and VaPoR_LNK_END; the row's own columns are the plain
+run's; not together with another of these modes.
 
---refine, --phased (with --phase-vcf), --both-ends, --depth and --signatures each append columns to every row and exclude one another: a run has one
+--refine, --phased (with --phase-vcf), --both-ends, --depth, --signatures and --links each append columns to every row and exclude one another: a run has one
 mode (vapor_amd.modes) or none, built once in _main and handed as one argument to bed_jobs / vcf_jobs (which
 driver a locus takes), score_jobs (the payload gathered into Job.extra), the table writer and SF.vcf_vapor_modify.  An option
 that adds columns is a module with INFO, COLUMNS, pack, unpack and columns_many, a Mode made of it, and its branch in _simple_job.
@@ -315,9 +320,9 @@ class _BndReader:
 class Job:
     """One output row: how to score it (a driver call, a generator factory, or fixed scores) and how to
     write it.  `cost`: what the locus is expected to take (microseconds, `job_cost`), for the shares of the ranks."""
-    __slots__ = ("key", "make", "fixed", "row_prefix", "label", "cost", "spec", "ctx", "call", "extra")
+    __slots__ = ("key", "make", "fixed", "row_prefix", "label", "cost", "spec", "ctx", "call", "extra", "bnd")
 
-    def __init__(self, key, make=None, fixed=None, row_prefix=None, label=None, cost=None, spec=None, ctx=None, call=None):
+    def __init__(self, key, make=None, fixed=None, row_prefix=None, label=None, cost=None, spec=None, ctx=None, call=None, bnd=None):
         # `call` = (driver, its arguments ..): `make` is that call, and a mode's chunk hook can make it again over other reads
         if call is not None:
             make = lambda: call[0](*call[1:])               # noqa: E731
@@ -325,6 +330,9 @@ class Job:
         # the four simple types also say WHAT they are - (type, chrom, start, end, ins_seq) and (num_reads_cff, bam, ref) - so
         # that a chunk of them can take the array route (vapor_amd.fastpath); `make` stays the driver's own route
         self.spec, self.ctx = spec, ctx
+        # a breakend says what it is apart from them - (its scored view, (num_reads_cff, bam, ref)) - for a mode's chunk hook
+        # (`--links`); spec and ctx stay None: a breakend is not for the array route
+        self.bnd = bnd
         self.extra = None              # after scoring under a mode (vapor_amd.modes): the locus's payload - refine.Refined.info,
                                        # phase.Phased.phase or drivers.BothEnds.views -, None for a locus without one
         self.cost = cost if cost is not None else (COST_FIXED_US if make is None else COST_HOST_US)
@@ -502,7 +510,8 @@ def vcf_jobs(vcf_list, num_reads_cff, bam_in, ref, out_path, sample_name, mode=N
                     jobs.append(Job(key, call=(drivers.vapor_both_ends, 'BND', num_reads_cff, plt_li, bam_in, ref, y, fig),
                                     cost=job_cost('BND', 0, views=2)))
                     continue
-                jobs.append(Job(key, call=(drivers.vapor_bnd, num_reads_cff, plt_li, bam_in, ref, y, fig), cost=job_cost('BND', 0)))
+                jobs.append(Job(key, call=(drivers.vapor_bnd, num_reads_cff, plt_li, bam_in, ref, y, fig), cost=job_cost('BND', 0),
+                                bnd=(y, ctx)))
             elif x in ('DEL', 'INV'):
                 if y[2] - y[1] < 50:        # both branches label the row DEL (vapor_vali/vapor:394, 407)
                     jobs.append(Job(':'.join([str(i) for i in y] + ['DEL']), fixed=[]))
@@ -761,6 +770,47 @@ def _signature_payloads(jobs, todo, engine):
 modes.SIGNATURES.chunk_payloads = _signature_payloads
 
 
+def _links_payloads(jobs, todo, engine):
+    """`--links`: like the signatures, the evidence is the chunk's - the link regions of all its DEL, TANDUP and
+    INV loci (links.regions of Job.spec) and of its breakends (of Job.bnd's view), every window clipped to the backend's contig
+    length, go to the read backend in one links_many call per BAM file (a per-chromosome pattern: per file, merged by
+    links.merge_words; a region on a contig that a file lacks is zero there).  Returns {t: links.Payload}; a locus of another
+    type has none."""
+    from . import links, seqio
+    be = seqio.get_backend()
+    by_bam = {}
+    for t in todo:
+        j = jobs[t]
+        if j.bnd is not None:
+            by_bam.setdefault((j.bnd[1][1], j.bnd[1][2]), []).append((t, 'BND', list(j.bnd[0])))
+        elif j.spec is not None and j.ctx is not None and j.spec[0] in links.TYPES:
+            by_bam.setdefault((j.ctx[1], j.ctx[2]), []).append((t, j.spec[0], [j.spec[1], j.spec[2], j.spec[3]]))
+    out = {}
+    for (bam, ref), loci in by_bam.items():
+        files = seqio.bam_in_decide(bam, None)
+
+        def length_of(chrom):
+            return be.contig_length(files[0], ref, chrom) if files else 0
+        where, chroms, regs_all, partners = [], [], [], []
+        for _t, name, locus in loci:
+            left, right = links.regions(name, locus, length_of)
+            where.append((len(regs_all), len(left), len(right)))
+            for c, fields, pc in left + right:
+                chroms.append(c)
+                regs_all.append(fields)
+                partners.append(pc)
+        got = [[0] * 5 for _ in regs_all]
+        for f in files:
+            for k, a in enumerate(be.links_many(engine, f, chroms, regs_all, partners)):
+                got[k] = links.merge_words(got[k], a)
+        for (t, name, locus), (at, nl, nr) in zip(loci, where):
+            out[t] = links.payload(name, locus, got[at:at + nl], got[at + nl:at + nl + nr])
+    return out
+
+
+modes.LINKS.chunk_payloads = _links_payloads
+
+
 last_timing: dict = {}          # of the most recent score_jobs: seconds scoring this rank's share, seconds in the gather
 
 
@@ -925,6 +975,14 @@ def build_parser() -> argparse.ArgumentParser:
                         'duplicate records never count, supplementary records do; appends VaPoR_SIG_L, VaPoR_SIG_R, VaPoR_SIG_CG, '
                         'VaPoR_SIG_N, VaPoR_SIG_POS and VaPoR_SIG_END (vcf: to INFO); not together with --refine, --phased, '
                         '--phase-vcf, --both-ends or --depth')
+    p.add_argument('--links', action='store_true',
+                   help='bed, vcf: split reads joined through their SA tags, per DEL, TANDUP and INV call and per breakend of --bnd: '
+                        'alignments soft- or hard-clipped by 30 bases or more within 50 bases of a breakpoint whose SA tag names a piece '
+                        'within 50 bases of the other breakpoint, on the strand the event gives it; clipped alignments whose SA '
+                        'entries all lie elsewhere; and the modal coordinates the linked pieces name; unmapped, secondary, QC-fail and '
+                        'duplicate records never count, supplementary records do, --min-mapq holds for the entries as well; appends '
+                        'VaPoR_LNK_L, VaPoR_LNK_R, VaPoR_LNK_N, VaPoR_LNK_OL, VaPoR_LNK_OR, VaPoR_LNK_POS and VaPoR_LNK_END (vcf: to '
+                        'INFO); not together with --refine, --phased, --phase-vcf, --both-ends, --depth or --signatures')
     p.add_argument('--min-mapq', metavar='Q', type=_int_in('--min-mapq', 0, 255), default=0,
                    help='every sub-command: skip records with MAPQ below Q (0..255, default 0), as `samtools view -q Q` does; a '
                         'filtered record is treated as if it were not in the file')
@@ -1038,6 +1096,21 @@ def _main(argv, held) -> int:
             parser.error('--signatures and --both-ends cannot be combined (a run has one mode)')
         if args.depth:
             parser.error('--signatures and --depth cannot be combined (a run has one mode)')
+    if args.links:
+        if cmd not in ('bed', 'vcf'):
+            parser.error('--links applies to `vapor bed` and `vapor vcf`')
+        if refine is not None:
+            parser.error('--links and --refine cannot be combined (a run has one mode)')
+        if args.phase_vcf is not None:
+            parser.error('--links and --phase-vcf cannot be combined (links are not counted per haplotype)')
+        if args.phased:
+            parser.error('--links and --phased cannot be combined (links are not counted per haplotype)')
+        if args.both_ends:
+            parser.error('--links and --both-ends cannot be combined (a run has one mode)')
+        if args.depth:
+            parser.error('--links and --depth cannot be combined (a run has one mode)')
+        if args.signatures:
+            parser.error('--links and --signatures cannot be combined (a run has one mode)')
     if args.phase_vcf is not None:
         # (every rank reads the VCF itself; the sites ride on the backend the reads are taken through)
         from . import phase as ph
@@ -1063,7 +1136,7 @@ def _main(argv, held) -> int:
         backend.dedup_qname = True
         if backend not in held:
             held.append(backend)
-    mode = None                          # (at most one of the five: every pair was refused above)
+    mode = None                          # (at most one mode: every pair of the options that make one was refused above)
     if refine is not None:
         mode = modes.refine(*refine, ci_of=vcf_ci_readin(args.sv_input) if cmd == 'vcf' else None)
     elif args.phased:
@@ -1074,6 +1147,8 @@ def _main(argv, held) -> int:
         mode = modes.DEPTH
     elif args.signatures:
         mode = modes.SIGNATURES
+    elif args.links:
+        mode = modes.LINKS
     figure_fn = None
     if not args.no_figures:
         from . import figures

@@ -12,6 +12,7 @@
 #include "vapor_inflate.h"
 #include "vapor_names.h"
 #include "vapor_readplan.h"
+#include "vapor_sa.h"
 
 #include <fcntl.h>
 #include <unistd.h>
@@ -26,6 +27,7 @@
 #include <new>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 struct vapor_bam {
@@ -739,7 +741,11 @@ static int bam_walk_records(vapor_bam* b, const char* who, int32_t tid, int64_t 
                     if (cg) { ops = cg; n_ops = cnt; }
                 }
             }
-            rec((int64_t)pos, ops, n_ops);
+            // (a reader that needs more of the record - its FLAG, its aux fields - takes the record itself as well)
+            if constexpr (std::is_invocable_v<PerRecord, int64_t, const uint8_t*, int32_t, const uint8_t*, int32_t>)
+                rec((int64_t)pos, ops, n_ops, r, (int32_t)bs);
+            else
+                rec((int64_t)pos, ops, n_ops);
         }
     }
     return VAPOR_OK;
@@ -866,6 +872,104 @@ extern "C" int vapor_bam_signature(vapor_bam* b, int32_t tid, const int64_t* fie
         return bfail(VAPOR_E_NOMEM, "vapor_bam_signature: out of memory");
     } catch (const std::exception& e) {
         return bfail(VAPOR_E_ARG, std::string("vapor_bam_signature: ") + e.what());
+    }
+}
+
+// Split reads joined through their SA tags, one link region (`--links`; vapor_amd/links.py answer is the rule,
+// bam_link_kernel the device's form): bam_walk_records to w3, and per passing record the clip event the region asks for - read as
+// bam_signature_impl reads it - within tol of x; of such a clip record the entries of its SA value (vapor_sa.h), an entry below
+// the handle's minimum MAPQ ignored; the first entry in text order that names the partner, holds the strand relation and lies
+// within tol of y gives the record's offset.  A malformed aux area: what stood before the damage stands - the record has no
+// entries.  An empty window has no records.
+// fields: w0, w3, x, y, tol, min_clip, ev, pend, rel, name_off, name_len (vapor_readplan.h LINK_FIELDS); out: n_clip, n_split,
+// n_link, the mode's offset and count.
+static int bam_links_impl(vapor_bam* b, int32_t tid, const int64_t* fields, const uint8_t* names, int64_t names_len, int32_t n_chunks,
+                          const uint64_t* chunks, int64_t* out)
+{
+    using namespace vapor_bamdev;
+    if (!b || !fields || !out || names_len < 0 || (names_len && !names) || n_chunks < 0 || (n_chunks && !chunks))
+        return bfail(VAPOR_E_ARG, "vapor_bam_links: null argument");
+    if (!vapor_readplan::link_region_ok(tid, fields, names_len))
+        return bfail(VAPOR_E_ARG, "vapor_bam_links: the window does not ascend from 0 to a BAM position, the tolerance is not 0..255, "
+                                  "ev, pend or rel is not 0 or 1, the partner's name is empty or outside the names, or the contig is none");
+    LinkRegion R;
+    vapor_readplan::link_region_set(R, tid, fields, 0);
+    const int64_t tol = R.tol, width = 2 * tol + 1;
+    const bool want_r = R.bits & LINK_EV, use_b = R.bits & LINK_PEND, differ = R.bits & LINK_REL;
+    const uint8_t* pname = names + R.name_off;
+    std::vector<uint32_t> hist((size_t)width, 0u);
+    int64_t n_clip = 0, n_split = 0, n_link = 0;
+    auto is_clip = [](uint32_t o) { return (o & 15u) == 4u || (o & 15u) == 5u; };
+    const int rc = bam_walk_records(b, "vapor_bam_links", tid, R.w3, R.w3 > R.w0 ? n_chunks : 0, chunks,
+                                    [&](int64_t pos, const uint8_t* ops, int32_t n_ops, const uint8_t* r, int32_t bs) {
+        if (n_ops <= 0) return;
+        auto op = [&](int32_t t) { return (uint32_t)rd32(ops + 4 * (size_t)t); };
+        const uint32_t o0 = op(0), o1 = n_ops >= 2 ? op(1) : 15u, ol = op(n_ops - 1), op2 = n_ops >= 2 ? op(n_ops - 2) : 15u;
+        if (is_clip(o0) && (n_ops == 1 || (n_ops == 2 && is_clip(o1)))) return;     // all clips: neither event
+        int64_t have, at;
+        if (!want_r) {
+            have = is_clip(o0) ? (int64_t)(o0 >> 4) + (is_clip(o1) ? (int64_t)(o1 >> 4) : 0) : 0;
+            at = pos;
+        } else {
+            have = is_clip(ol) ? (int64_t)(ol >> 4) + (is_clip(op2) ? (int64_t)(op2 >> 4) : 0) : 0;
+            at = pos;
+            for (int32_t t = 0; t < n_ops; ++t) {
+                const uint32_t o = op(t), code = o & 15u;
+                if (code == 0u || code == 2u || code == 3u || code == 7u || code == 8u) at += (int64_t)(o >> 4);
+            }
+        }
+        const int64_t d = at - R.x;
+        if (have < R.min_clip || d < -tol || d > tol) return;
+        ++n_clip;
+        const int l_name = r[8], n_cig = r[12] | (r[13] << 8);
+        const int32_t l_seq = rd32(r + 16);
+        const bool minus = (r[14] & 0x10u) != 0;
+        const uint8_t* value = nullptr;
+        size_t len = 0;
+        if (vapor_sa::find_sa(r + 32 + l_name + 4 * (size_t)n_cig + ((size_t)l_seq + 1) / 2 + (size_t)l_seq, r + bs, &value, &len) != vapor_sa::FIND_VALUE) return;
+        bool any = false, linked = false;
+        int64_t off = 0;
+        vapor_sa::for_each_piece(value, len, [&](bool ok, const vapor_sa::Entry& e) {
+            if (!ok || e.mapq < b->min_mapq) return false;
+            any = true;
+            const int64_t dy = (use_b ? e.b : e.a) - R.y;
+            if (e.name_len == R.name_len && !memcmp(e.name, pname, e.name_len) && ((e.minus != minus) == differ) && dy >= -tol && dy <= tol) {
+                linked = true;
+                off = dy;
+                return true;
+            }
+            return false;
+        });
+        if (any) ++n_split;
+        if (linked) {
+            ++n_link;
+            ++hist[(size_t)(off + tol)];
+        }
+    });
+    for (int k = 0; k < LINK_ANSWER_WORDS; ++k) out[k] = 0;
+    if (rc != VAPOR_OK) return rc;
+    out[0] = n_clip; out[1] = n_split; out[2] = n_link;
+    // the mode: the largest count, then the smallest |offset|, then the negative offset
+    int64_t best_off = 0, best = 0;
+    for (int64_t off = -tol; off <= tol; ++off) {
+        const int64_t c = hist[(size_t)(off + tol)];
+        const int64_t a = off < 0 ? -off : off, ba = best_off < 0 ? -best_off : best_off;
+        if (c > best || (c == best && c > 0 && (a < ba || (a == ba && off < best_off)))) { best = c; best_off = off; }
+    }
+    out[3] = best ? best_off : 0;
+    out[4] = best;
+    return VAPOR_OK;
+}
+
+extern "C" int vapor_bam_links(vapor_bam* b, int32_t tid, const int64_t* fields, const uint8_t* names, int64_t names_len, int32_t n_chunks,
+                               const uint64_t* chunks, int64_t* out)
+{
+    try {
+        return bam_links_impl(b, tid, fields, names, names_len, n_chunks, chunks, out);
+    } catch (const std::bad_alloc&) {
+        return bfail(VAPOR_E_NOMEM, "vapor_bam_links: out of memory");
+    } catch (const std::exception& e) {
+        return bfail(VAPOR_E_ARG, std::string("vapor_bam_links: ") + e.what());
     }
 }
 
@@ -1287,4 +1391,11 @@ extern "C" __attribute__((weak)) int vapor_bam_signature_device(vapor_ctx*, vapo
                                                                 const uint64_t*, int64_t*, int32_t*)
 {
     return bfail(VAPOR_E_ARG, "vapor_bam_signature_device: this build has no device reader");
+}
+
+// ... and the links on the device (vapor_bam_links_device: bam_link_kernel; the host reader is vapor_bam_links).
+extern "C" __attribute__((weak)) int vapor_bam_links_device(vapor_ctx*, vapor_bam*, int32_t, const int32_t*, const int64_t*, const uint8_t*, int64_t,
+                                                            const int32_t*, const uint64_t*, int64_t*, int32_t*)
+{
+    return bfail(VAPOR_E_ARG, "vapor_bam_links_device: this build has no device reader");
 }

@@ -1415,6 +1415,311 @@ __global__ __launch_bounds__(64) void bam_signature_kernel(const uint8_t* __rest
     }
 }
 
+// ---- `--links` ----------------------------------------------------------------------------------------------
+// The first aux field named SA among [p, end) (vapor_sa.h find_sa is the statement): 1 with the bytes before its NUL when its type
+// is Z, 0 when there is none or its type is another, 2 for an area that is damaged before one is found.  walk_aux_dev's walk -
+// wave-uniform, the NUL of a Z / H string found 64 bytes a step with a ballot, B arrays skipped by arithmetic - as a sibling:
+// walk_aux_dev's instantiations are what they were.
+__device__ __forceinline__ int find_sa_dev(const uint8_t* arena, uint32_t p, uint32_t end, uint32_t lane, uint32_t* value, uint32_t* len)
+{
+    *value = 0;
+    *len = 0;
+    // (every step moves p forward by three bytes at least: the loop ends)
+    while (p + 3 <= end) {
+        const uint8_t t0 = arena[p], t1 = arena[p + 1], ty = arena[p + 2];
+        p += 3;
+        const bool sa = t0 == 'S' && t1 == 'A';
+        if (sa && ty != 'Z') return 0;
+        if (ty == 'Z' || ty == 'H') {
+            const uint32_t s = p;
+            bool found = false;
+            while (p < end) {
+                const uint32_t q = p + lane;
+                const unsigned long long m = __ballot(q < end && arena[q] == 0);
+                if (m) { p += (uint32_t)__ffsll((long long)m); found = true; break; }
+                p += 64u;
+            }
+            if (!found) return 2;
+            if (sa) { *value = s; *len = p - 1u - s; return 1; }
+            continue;
+        }
+        if (ty == 'B') {
+            if (p + 5 > end) return 2;
+            const uint8_t sub = arena[p];
+            const int32_t cnt = (int32_t)rd32u(arena + p + 1);
+            p += 5;
+            const int es = (sub == 'c' || sub == 'C') ? 1 : (sub == 's' || sub == 'S') ? 2 : 4;
+            if (cnt < 0 || (long long)cnt * es > (long long)(end - p)) return 2;
+            p += (uint32_t)cnt * (uint32_t)es;
+            continue;
+        }
+        const uint32_t sz = (ty == 'A' || ty == 'c' || ty == 'C') ? 1u : (ty == 's' || ty == 'S') ? 2u : (ty == 'i' || ty == 'I' || ty == 'f') ? 4u : 0u;
+        if (sz == 0u || sz > end - p) return 2;
+        p += sz;
+    }
+    return 0;
+}
+
+__device__ __forceinline__ bool link_is_digit(uint8_t c) { return c >= '0' && c <= '9'; }
+// 1 for an operation letter that moves the reference cursor (M D N = X), 0 for another letter (I S H P), -1 for another byte
+__device__ __forceinline__ int link_op_kind(uint8_t c)
+{
+    return (c == 'M' || c == 'D' || c == 'N' || c == '=' || c == 'X') ? 1 : (c == 'I' || c == 'S' || c == 'H' || c == 'P') ? 0 : -1;
+}
+__device__ __forceinline__ long long wave_sum64(long long v)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+    return v;
+}
+// a decimal field [s, e) of 1 .. max_digits (at most 10) digits, wave-uniform: a bounded field, ten bytes at the most
+__device__ __forceinline__ bool link_number(const uint8_t* arena, uint32_t s, uint32_t e, uint32_t max_digits, long long* v)
+{
+    if (e <= s || e - s > max_digits) return false;
+    long long x = 0;
+    for (uint32_t q = s; q < e; ++q) {
+        const uint8_t c = arena[q];
+        if (!link_is_digit(c)) return false;
+        x = 10 * x + (long long)(c - '0');
+    }
+    *v = x;
+    return true;
+}
+
+// The entries of an SA value [v, vend) across the wavefront (vapor_sa.h for_each_piece / parse_piece is the statement).  Bit 0 of
+// the result: the value has an entry (a well-formed piece at or above min_mapq); bit 1: one matches, *off = c - y of the first
+// that does, in text order.  Piece by piece; the tiles of a piece are 64 bytes from the piece's start, a byte a lane.
+//   The cut: one pass of tiles from the piece's start with a ballot for ';' and one for ','.  What is carried from tile to tile is
+//   the number of commas seen and the places of the first five (five scalars, no array); the commas of the tile that holds the
+//   ';' count only below it.  A sixth comma is an extra field, fewer than five a missing one.
+//   pos, strand and mapq are bounded fields (10, 1 and 3 bytes) between known commas, read wave-uniformly; NM is unbounded: its
+//   tiles are tested with a ballot for a byte that is no digit.
+//   The CIGAR: a lane per byte; a lane that holds an operation letter reads its digits backwards from memory, up to ten bytes
+//   or to the field's start - so a digit run that crosses a tile edge, or a letter on lane 0, needs no carry - and refuses
+//   no digit, ten or more, or a length above 2^28 - 1; a byte that is neither a digit nor a letter, and a last byte that is no
+//   letter, refuse the piece.  Every digit run then ends in a letter and has 1..9 digits: the field matches the grammar.  The
+//   reference length is a wave sum a tile, carried in a 64-bit scalar.
+//   The name is compared with the partner's 64 bytes a step, after the lengths.
+__device__ __forceinline__ uint32_t link_scan_sa(const uint8_t* arena, uint32_t v, uint32_t vend, uint32_t lane, const uint8_t* __restrict__ pname,
+                                                 uint32_t pname_len, bool rec_minus, bool differ, bool use_b, long long y, long long tol,
+                                                 uint32_t min_mapq, long long* off)
+{
+    uint32_t res = 0;
+    uint32_t s = v;
+    // (every turn moves s behind a ';' or to the value's end: the loop ends)
+    while (s < vend) {
+        uint32_t e = vend, nc = 0, c0 = 0, c1 = 0, c2 = 0, c3 = 0, c4 = 0;
+        for (uint32_t t0 = s; t0 < vend; t0 += 64u) {
+            const uint32_t q = t0 + lane;
+            const uint8_t ch = q < vend ? arena[q] : (uint8_t)0;
+            const unsigned long long ms = __ballot(ch == ';');
+            unsigned long long mc = __ballot(ch == ',');
+            uint32_t stop = 64u;
+            if (ms) {
+                stop = (uint32_t)__ffsll((long long)ms) - 1u;
+                mc &= (1ull << stop) - 1ull;
+            }
+            while (mc && nc < 5u) {
+                const uint32_t at = t0 + (uint32_t)__ffsll((long long)mc) - 1u;
+                mc &= mc - 1ull;
+                if (nc == 0u) c0 = at; else if (nc == 1u) c1 = at; else if (nc == 2u) c2 = at; else if (nc == 3u) c3 = at; else c4 = at;
+                ++nc;
+            }
+            nc += (uint32_t)__popcll(mc);
+            if (ms) { e = t0 + stop; break; }
+        }
+        const uint32_t piece = s;
+        s = e + 1u;
+        if (e == piece) continue;                               // an empty piece is dropped
+        if (nc != 5u || c0 == piece) continue;                  // a missing or an extra field, an empty name
+        long long pos = 0, mapq = 0;
+        if (!link_number(arena, c0 + 1u, c1, 10u, &pos) || pos < 1 || pos > 0x7FFFFFFFll) continue;
+        if (c2 - c1 != 2u) continue;
+        const uint8_t strand = arena[c1 + 1u];
+        if (strand != '+' && strand != '-') continue;
+        if (!link_number(arena, c3 + 1u, c4, 3u, &mapq) || mapq > 255) continue;
+        if (c4 + 1u >= e) continue;                             // an empty NM
+        bool ok = true;
+        for (uint32_t t0 = c4 + 1u; t0 < e; t0 += 64u) {
+            const uint32_t q = t0 + lane;
+            if (__any(q < e && !link_is_digit(arena[q]))) { ok = false; break; }
+        }
+        if (!ok) continue;
+        const uint32_t cs = c2 + 1u, ce = c3;
+        if (cs >= ce || link_op_kind(arena[ce - 1u]) < 0) continue;    // an empty CIGAR, one without its last letter
+        long long span = 0;
+        for (uint32_t t0 = cs; t0 < ce; t0 += 64u) {
+            const uint32_t q = t0 + lane;
+            const bool in = q < ce;
+            const uint8_t ch = in ? arena[q] : (uint8_t)'0';
+            const int kind = link_op_kind(ch);
+            bool bad = !link_is_digit(ch) && kind < 0;
+            long long n = 0;
+            if (in && kind >= 0) {
+                long long mul = 1;
+                uint32_t d = 0;
+                // (q - k >= cs: the lane reads inside the field, whatever tile the digits lie in)
+                for (uint32_t k = 1; k <= 10u && q >= cs + k; ++k) {
+                    const uint8_t c = arena[q - k];
+                    if (!link_is_digit(c)) break;
+                    d = k;
+                    if (k <= 9u) { n += (long long)(c - '0') * mul; mul *= 10; }
+                }
+                bad = d < 1u || d > 9u || n > 0xFFFFFFFll;
+            }
+            if (__any(bad)) { ok = false; break; }
+            span += wave_sum64(kind == 1 ? n : 0);
+        }
+        if (!ok) continue;
+        if ((uint32_t)mapq < min_mapq) continue;                // a well-formed piece below the cut is ignored too
+        res |= 1u;
+        const long long a = pos - 1, c = use_b ? a + span : a;
+        const long long d = c - y;
+        if (d < -tol || d > tol || ((strand == '-') != rec_minus) != differ) continue;
+        const uint32_t nlen = c0 - piece;
+        if (nlen != pname_len) continue;
+        bool same = true;
+        for (uint32_t t0 = 0; t0 < nlen; t0 += 64u) {
+            const uint32_t i = t0 + lane;
+            if (__any(i < nlen && arena[piece + i] != pname[i])) { same = false; break; }
+        }
+        if (!same) continue;
+        *off = d;
+        return res | 2u;
+    }
+    return res;
+}
+
+// Split reads joined through their SA tags, per region (`--links`; vapor_bam.cpp bam_links_impl is the host's
+// statement, vapor_amd/links.py answer the rule): one wavefront a region; the header checks, statuses, filter test, CG
+// replacement and clip test are bam_signature_kernel's.  A region asks for one clip event.  LCLIP needs the first two operations
+// only; RCLIP the last two and the reference end, a wave sum per 64 operations.  Only a clip record - the event within tol of x -
+// pays for the aux walk to SA (find_sa_dev) and the scan of its value (link_scan_sa).  Everything about a record is
+// wave-uniform here: the three counts are scalars, the histogram - 2 * tol + 1 words of LDS - takes one LDS atomic from lane 0
+// per linked record, and the mode is bam_signature_kernel's wave maximum over the same key.
+__global__ __launch_bounds__(64) void bam_link_kernel(const uint8_t* __restrict__ arena, const LinkRegion* __restrict__ regs,
+                                                     const BamSpan* __restrict__ spans, const int32_t* __restrict__ blk_status,
+                                                     const uint8_t* __restrict__ names, uint32_t names_len, int n_regs,
+                                                     uint32_t* __restrict__ ans, int32_t* __restrict__ reg_status)
+{
+    __shared__ uint32_t hist[LINK_HIST_WORDS];
+    const int g = (int)blockIdx.x;
+    if (g >= n_regs) return;
+    const uint32_t lane = threadIdx.x;
+    const LinkRegion R = regs[g];
+    const long long w3 = R.w3, x = R.x, y = R.y;
+    // (the host made tol 0..255; the clamp keeps every histogram index inside the array whatever the table holds)
+    const long long tol = R.tol < 0 ? 0 : (R.tol > SIG_TOL_MAX ? SIG_TOL_MAX : R.tol);
+    const uint32_t width = 2u * (uint32_t)tol + 1u;
+    const long long min_clip = R.min_clip;
+    const bool want_r = R.bits & LINK_EV, use_b = R.bits & LINK_PEND, differ = R.bits & LINK_REL;
+    const uint32_t flt_excl = R.filter & 0xFFFFu, flt_mapq = (R.filter >> 16) & 0xFFu;
+    for (uint32_t i = lane; i < width; i += 64) hist[i] = 0u;
+    __syncthreads();
+    uint32_t n_clip = 0, n_split = 0, n_link = 0;
+    int st = REG_OK;
+    // (the host checked the name against the blob; a table that says otherwise is the host route's to refuse)
+    if (R.name_len == 0u || R.name_off > names_len || R.name_len > names_len - R.name_off) st = REG_MALFORMED;
+    const uint8_t* pname = names + R.name_off;
+    const int span_n = w3 > R.w0 ? R.span_n : 0;            // (an empty window has no records, whatever chunks came with it)
+    for (int s = 0; s < span_n && st == REG_OK; ++s) {
+        const BamSpan SP = spans[R.span_first + s];
+        int bad = 0;
+        for (uint32_t i = lane; i < SP.blk_n; i += 64) bad |= blk_status[SP.blk_first + i] != 0;
+        if (__any(bad)) { st = REG_BLOCK; break; }
+        uint32_t pos_u = SP.u_begin;
+        // (a record is 36 bytes at least: pos_u grows every turn and the loop ends at u_end)
+        while (pos_u < SP.u_end) {
+            if ((unsigned long long)pos_u + 36ull > SP.u_limit) { st = REG_BEYOND; break; }
+            uint32_t w = 0;
+            if (lane < 6) w = rd32u(arena + pos_u + 4u * lane);
+            const int32_t bs = (int32_t)__shfl(w, 0), ref_id = (int32_t)__shfl(w, 1), pos = (int32_t)__shfl(w, 2);
+            const uint32_t wd3 = __shfl(w, 3), wd4 = __shfl(w, 4);
+            const int32_t l_seq = (int32_t)__shfl(w, 5);
+            if (bs < 32 || bs > (1 << 29)) { st = REG_MALFORMED; break; }
+            if ((unsigned long long)pos_u + 4ull + (unsigned long long)bs > SP.u_limit) { st = REG_BEYOND; break; }
+            const uint32_t r = pos_u + 4u;
+            pos_u += 4u + (uint32_t)bs;
+            const int l_name = (int)(wd3 & 0xFFu), n_cig = (int)(wd4 & 0xFFFFu);
+            if (l_seq < 0 || 32ll + l_name + 4ll * n_cig + ((long long)l_seq + 1) / 2 + (long long)l_seq > (long long)bs) { st = REG_MALFORMED; break; }
+            if (ref_id != R.tid || (long long)pos >= w3) {
+                if (ref_id > R.tid || (ref_id == R.tid && (long long)pos >= w3)) break;
+                continue;
+            }
+            // the read filter, DEPTH_EXCLUDE among its flags: both fields came with the record's header
+            if (((wd3 >> 8) & 0xFFu) < flt_mapq || ((wd4 >> 16) & flt_excl)) continue;
+            const uint32_t cig = r + 32u + (uint32_t)l_name;
+            const uint32_t aux = cig + 4u * (uint32_t)n_cig + (uint32_t)((l_seq + 1) / 2) + (uint32_t)l_seq, rec_end = r + (uint32_t)bs;
+            uint32_t ops = cig;
+            int32_t n_ops = n_cig;
+            if (n_cig == 2) {
+                const uint32_t o0 = rd32u(arena + cig), o1 = rd32u(arena + cig + 4);
+                if ((o0 & 15u) == 4u && (int32_t)(o0 >> 4) == l_seq && (o1 & 15u) == 3u) {
+                    int32_t cnt = 0;
+                    const uint32_t cg = find_cg_dev(arena, aux, rec_end, &cnt);
+                    if (cg) { ops = cg; n_ops = cnt; }
+                }
+            }
+            if (n_ops <= 0) continue;                       // no CIGAR: nothing, and no error
+            const uint32_t o0 = rd32u(arena + ops), o1 = n_ops >= 2 ? rd32u(arena + ops + 4u) : 15u;
+            // (a record of at most two operations that are all clips has neither event)
+            if (sig_is_clip(o0) && (n_ops == 1 || (n_ops == 2 && sig_is_clip(o1)))) continue;
+            long long have = 0, at = (long long)pos;
+            if (!want_r) {
+                // LCLIP: the operations behind the first two are not walked
+                if (sig_is_clip(o0)) have = (long long)(o0 >> 4) + (sig_is_clip(o1) ? (long long)(o1 >> 4) : 0);
+            } else {
+                const uint32_t ol = rd32u(arena + ops + 4u * (uint32_t)(n_ops - 1)), op = n_ops >= 2 ? rd32u(arena + ops + 4u * (uint32_t)(n_ops - 2)) : 15u;
+                if (sig_is_clip(ol)) have = (long long)(ol >> 4) + (sig_is_clip(op) ? (long long)(op >> 4) : 0);
+                if (have < min_clip) continue;              // (no event: its reference end is not needed)
+                for (int32_t t0 = 0; t0 < n_ops; t0 += 64) {
+                    const int32_t t = t0 + (int32_t)lane;
+                    const uint32_t o = t < n_ops ? rd32u(arena + ops + 4u * (uint32_t)t) : 15u;
+                    const uint32_t code = o & 15u;
+                    at += wave_sum64((code == 0u || code == 2u || code == 3u || code == 7u || code == 8u) ? (long long)(o >> 4) : 0);
+                }
+            }
+            const long long d = at - x;
+            if (have < min_clip || d < -tol || d > tol) continue;
+            ++n_clip;
+            uint32_t value = 0, len = 0;
+            const int found = find_sa_dev(arena, aux, rec_end, lane, &value, &len);
+            if (found == 2) { st = REG_MALFORMED; break; }
+            if (found != 1) continue;
+            long long off = 0;
+            const uint32_t got = link_scan_sa(arena, value, value + len, lane, pname, R.name_len, ((wd4 >> 16) & 0x10u) != 0u, differ, use_b, y, tol,
+                                              flt_mapq, &off);
+            if (got & 1u) ++n_split;
+            if (got & 2u) {
+                ++n_link;
+                if (lane == 0) atomicAdd(&hist[(uint32_t)(off + tol)], 1u);
+            }
+        }
+    }
+    __syncthreads();
+    // the mode: key = count << 10 | 1023 - rank, rank = 2 |offset| + (offset > 0) - bam_signature_kernel's
+    unsigned long long key = 0;
+    for (uint32_t i = lane; i < width; i += 64) {
+        const long long off = (long long)i - tol;
+        const uint32_t rank = (uint32_t)(off < 0 ? -2 * off : 2 * off + 1);
+        const unsigned long long k = ((unsigned long long)hist[i] << 10) | (unsigned long long)(1023u - rank);
+        key = k > key ? k : key;
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const unsigned long long o = __shfl_xor(key, d);
+        key = o > key ? o : key;
+    }
+    if (lane == 0) {
+        uint32_t* o = ans + (size_t)LINK_ANSWER_WORDS * (size_t)g;
+        const uint32_t cnt = (uint32_t)(key >> 10), rank = 1023u - (uint32_t)(key & 1023u);
+        o[0] = n_clip; o[1] = n_split; o[2] = n_link;
+        o[3] = (uint32_t)(cnt ? ((rank & 1u) ? (int32_t)(rank >> 1) : -(int32_t)(rank >> 1)) : 0);
+        o[4] = cnt;
+        reg_status[g] = st;
+    }
+}
+
 // One record of a molecule per region (`--dedup-qname`, DESIGN.md 4.18 rule W; vapor_names.h holds the arithmetic, vapor_bam.cpp
 // bam_chop_impl the host's statement): one wavefront a region, right behind the chop kernel on its stream and before
 // bam_haplotag_kernel / bam_select_kernel, launched only for a handle with the option.  BamKept has no record offset, so the

@@ -599,6 +599,139 @@ inline void collect(const SigCall& c, const SigMeta& M, const uint8_t* h_meta, i
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
+// vapor_bam_links_device (`--links`)
+// ------------------------------------------------------------------------------------------------------------------------------
+constexpr int LINK_FIELDS = 11;            // a region as the caller gives it: w0, w3, x, y, tol, min_clip, ev, pend, rel, name_off, name_len
+struct LinkCall {
+    int32_t n_regions = 0;
+    const int32_t* tid = nullptr;
+    const int64_t* regions = nullptr;      // LINK_FIELDS a region
+    const uint8_t* names = nullptr;        // the partner contigs' names, one blob: region g's is names[name_off, name_off + name_len)
+    int64_t names_len = 0;
+    const int32_t* chunk_first = nullptr;
+    const uint64_t* chunks = nullptr;
+    uint32_t filter_word = 0;              // the handle's read filter with DEPTH_EXCLUDE among its flags (depth_filter_word)
+};
+
+inline Refusal check_args(const LinkCall& c, const int64_t* out, const int32_t* status)
+{
+    if (c.n_regions < 0 || c.names_len < 0 || c.names_len >= ((int64_t)1 << 30) || (c.names_len && !c.names) ||
+        (c.n_regions && (!c.tid || !c.regions || !c.chunk_first || !out || !status)))
+        return {VAPOR_E_ARG, "vapor_bam_links_device: bad argument"};
+    return {};
+}
+
+// Whether a region's own fields are a question the readers answer: the window ascends from 0 and ends at a BAM position, the
+// tolerance fits the histogram, ev, pend and rel are 0 or 1, the partner's name is not empty and lies inside the blob, the contig
+// is one.  One statement for the device's plan and the host reader (vapor_bam.cpp bam_links_impl).
+inline bool link_region_ok(int32_t tid, const int64_t* f, int64_t names_len)
+{
+    return f[0] >= 0 && f[1] >= f[0] && f[1] < ((int64_t)1 << 31) && f[4] >= 0 && f[4] <= SIG_TOL_MAX && f[6] >= 0 && f[6] <= 1 &&
+           f[7] >= 0 && f[7] <= 1 && f[8] >= 0 && f[8] <= 1 && f[10] >= 1 && f[9] >= 0 && f[9] <= names_len && f[10] <= names_len - f[9] && tid >= 0;
+}
+
+// The caller's fields as the kernel and the host reader take them: the minimum clip clamped to [1, 2^30] and the two targets to
+// +-2^40, as sig_region_set clamps them.
+inline void link_region_set(LinkRegion& R, int32_t tid, const int64_t* f, uint32_t filter_word)
+{
+    const int64_t far = (int64_t)1 << 40;
+    R.w0 = f[0]; R.w3 = f[1];
+    R.x = std::min(std::max(f[2], -far), far); R.y = std::min(std::max(f[3], -far), far);
+    R.tol = (int32_t)f[4];
+    R.min_clip = (int32_t)std::min<int64_t>(std::max<int64_t>(f[5], 1), (int64_t)1 << 30);
+    R.bits = (f[6] ? LINK_EV : 0u) | (f[7] ? LINK_PEND : 0u) | (f[8] ? LINK_REL : 0u);
+    R.name_off = (uint32_t)f[9]; R.name_len = (uint32_t)f[10];
+    R.tid = tid; R.filter = filter_word; R.pad = 0;
+}
+
+// The region rules: link_region_ok - else REG_MALFORMED and the host route's to refuse.  The spans and the staging block as
+// plan_spans makes them.
+inline Refusal plan_spans(const LinkCall& c, int32_t* status, SpanPlan& p)
+{
+    return plan_spans_of(c.n_regions, c.chunk_first, c.chunks, status, p, "vapor_bam_links_device: more than 1.5 GB of blocks in one call (use smaller batches)",
+                         [&](int32_t g, int*) { return link_region_ok(c.tid[g], c.regions + LINK_FIELDS * (size_t)g, c.names_len); });
+}
+
+// Where each table of a links call lies in its metadata block: blocks, spans, regions and the name blob go in - the blob once,
+// whatever number of regions name a contig; block status, the LINK_ANSWER_WORDS words a region and the region status come back.
+struct LinkMeta {
+    Table<BgzfBlk> blks;
+    Table<BamSpan> spans;
+    Table<LinkRegion> regs;
+    Table<uint8_t> names;
+    Table<int32_t> blk_status;
+    Table<uint32_t> ans;                   // LINK_ANSWER_WORDS a region: n_clip, n_split, n_link, the mode's offset (int32) and count
+    Table<int32_t> reg_status;
+    size_t in_bytes = 0, bytes = 0;
+
+    LinkMeta() = default;
+    LinkMeta(int32_t n_regions, size_t n_blks, size_t n_spans, size_t names_len)
+    {
+        const size_t nr = (size_t)std::max(n_regions, 1);
+        Carve m;
+        m.take(blks, std::max<size_t>(n_blks, 1));
+        m.take(spans, std::max<size_t>(n_spans, 1));
+        m.take(regs, nr);
+        m.take(names, std::max<size_t>(names_len, 1));
+        in_bytes = m.off;
+        m.take(blk_status, std::max<size_t>(n_blks, 1));
+        m.take(ans, (size_t)LINK_ANSWER_WORDS * nr);
+        m.take(reg_status, nr);
+        bytes = m.off;
+    }
+    size_t back_bytes() const { return bytes - blk_status.off; }       // the host's block is the device's: [blk_status.off, bytes) comes back
+    template <typename B> B* back(B* block) const { return block + blk_status.off; }
+};
+
+struct LinkLayout {
+    std::vector<BgzfBlk> blks;
+    std::vector<BamSpan> spans;
+    std::vector<LinkRegion> regs;
+    const uint8_t* names = nullptr;
+    size_t names_len = 0;
+    size_t arena = 0;
+    LinkMeta meta;
+    void fill(uint8_t* h_meta) const
+    {
+        if (!blks.empty()) memcpy(meta.blks.in(h_meta), blks.data(), sizeof(BgzfBlk) * blks.size());
+        if (!spans.empty()) memcpy(meta.spans.in(h_meta), spans.data(), sizeof(BamSpan) * spans.size());
+        memcpy(meta.regs.in(h_meta), regs.data(), sizeof(LinkRegion) * regs.size());
+        if (names_len) memcpy(meta.names.in(h_meta), names, names_len);
+    }
+};
+
+inline Refusal layout(const LinkCall& c, const SpanPlan& p, int32_t* status, LinkLayout& L)
+{
+    if (const Refusal r = layout_of(c.n_regions, p, status, L.blks, L.spans, L.regs, &L.arena,
+                                    "vapor_bam_links_device: more than 2 GB of block data in one call (use smaller batches)", [&](LinkRegion& R, int32_t g) {
+            const int64_t* f = c.regions + LINK_FIELDS * (size_t)g;
+            // (a region the plan refused keeps a record that asks nothing: no kernel reads it, its span_n is 0)
+            if (status[g]) { R = LinkRegion(); return; }
+            link_region_set(R, c.tid[g], f, c.filter_word);
+        }))
+        return r;
+    L.names = c.names;
+    L.names_len = (size_t)c.names_len;
+    L.meta = LinkMeta(c.n_regions, L.blks.size(), L.spans.size(), L.names_len);
+    return {};
+}
+
+// The read-back block into the caller's arrays, as collect(SigCall) does it: five words, the fourth signed.
+inline void collect(const LinkCall& c, const LinkMeta& M, const uint8_t* h_meta, int64_t* out, int32_t* status)
+{
+    const uint32_t* da = M.ans.in(h_meta);
+    const int32_t* rst = M.reg_status.in(h_meta);
+    for (int32_t g = 0; g < c.n_regions; ++g) {
+        int64_t* o = out + (size_t)LINK_ANSWER_WORDS * (size_t)g;
+        for (int k = 0; k < LINK_ANSWER_WORDS; ++k) o[k] = 0;
+        if (status[g]) continue;
+        if (rst[g] != REG_OK) { status[g] = rst[g]; continue; }
+        const uint32_t* a = da + (size_t)LINK_ANSWER_WORDS * (size_t)g;
+        for (int k = 0; k < LINK_ANSWER_WORDS; ++k) o[k] = k == 3 ? (int64_t)(int32_t)a[k] : (int64_t)a[k];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
 // vapor_fasta_windows_device
 // ------------------------------------------------------------------------------------------------------------------------------
 constexpr uint64_t ARENA_CAP = (uint64_t)1 << 30;       // inflated bytes of a call; a stretch that would pass it leaves its windows to the host

@@ -91,6 +91,22 @@ class SamtoolsCLI:
             out.append(signature.words(signature.answer(recs, rg)))
         return out
 
+    def links_many(self, engine, bam: str, chroms, regions, partners):
+        """The five words per link region (`--links`; chroms[g], regions[g] = links.FIELDS, partners[g] the
+        partner contig's name): links.answer over POS, CIGAR, FLAG and the SA field of the alignment lines of `view`, filtered
+        where they are read (_sam_fields) with links.EXCLUDE among the excluded flags; the entries' mapQ meets the filter's
+        minimum MAPQ."""
+        from . import links, signature
+        out = []
+        for chrom, rg, pc in zip(chroms, regions, partners):
+            if not rg[1] > rg[0]:
+                out.append([0] * 5)
+                continue
+            recs = [(int(f[3]), signature.parse_cigar(f[5]), int(f[1]), links.sa_of_sam(f[11:]))
+                    for f in _sam_fields(self, bam, chrom, int(rg[0]) + 1, int(rg[1]), links.EXCLUDE)]
+            out.append(links.words(links.answer(recs, rg, pc, getattr(self, "read_filter", (0, 0))[0])))
+        return out
+
 
 class FaiFasta:
     """In-process `samtools faidx ref chrom:start-end` through the .fai index (no process per locus)."""
@@ -656,11 +672,37 @@ class InProcessBam(SamtoolsHybrid):
         return self._regions_many(engine, bam, chroms, regions, len(signature.FIELDS), 0, 1, [0] * 10,
                                   ("vapor_bam_signature", "vapor_bam_signature_device"), "bam_signature_device", "signature_native", python)
 
-    def _regions_many(self, engine, bam, chroms, rows, width, lo, hi, zero, entries, device, native, python):
-        """The routes of depth_many and signature_many.  rows[g]: the `width` integers of region g, its walk window
+    def links_many(self, engine, bam: str, chroms, regions, partners):
+        """The five words per link region (`--links`; chroms[g], regions[g] = links.FIELDS, partners[g] the
+        partner contig's name) of a BAM file: n_clip, n_split, n_link, then offset and count of the mode.  The routes are
+        depth_many's: the device in groups (vapor_bam_links_device: bam_link_kernel, one wavefront a region), a region it hands
+        back - one with a record whose aux area is malformed among them - and every region with VAPOR_BAM_DEVICE=0 to the native
+        host reader (vapor_bam_links), and the Python statement - links.answer over fetch_links with links.EXCLUDE added to the
+        excluded flags - for a library without the entries or VAPOR_BAM_NATIVE=0.  The native readers do not know contig names:
+        the partners' go as one byte blob, every name once, and each region's row ends in its name's offset and length."""
+        from . import links
+        where, blob, rows = {}, bytearray(), []
+        for rg, pc in zip(regions, partners):
+            name = pc.encode("latin-1") if isinstance(pc, str) else bytes(pc)
+            if name not in where:
+                where[name] = len(blob)
+                blob += name
+            rows.append([int(v) for v in rg] + [where[name], len(name)])
+        names = bytes(blob)
+
+        def python(b, chrom, row):
+            recs = b.fetch_links(chrom, int(row[0]) + 1, int(row[1]), exclude_more=links.EXCLUDE)
+            return links.words(links.answer(recs, row[:9], names[int(row[9]):int(row[9]) + int(row[10])], b.read_filter[0]))
+        return self._regions_many(engine, bam, chroms, rows, len(links.FIELDS) + 2, 0, 1, [0] * 5, ("vapor_bam_links", "vapor_bam_links_device"),
+                                  "bam_links_device", "links_native", python, names=names)
+
+    def _regions_many(self, engine, bam, chroms, rows, width, lo, hi, zero, entries, device, native, python, names=None):
+        """The routes of depth_many, signature_many and links_many.  rows[g]: the `width` integers of region g, its walk window
         [rows[g][lo], rows[g][hi]); zero: the answer of a region without records (an unknown contig, an empty window);
         entries: the library's host and device entry; device: the Engine's method, native: the BamFile's, python(b, chrom, row)
-        the Python statement."""
+        the Python statement.  names (links_many): a byte blob the rows point into, handed to the device and the native entry
+        as their `names`."""
+        more = {} if names is None else {"names": names}
         import numpy as np
         from . import _lib
         n = len(chroms)
@@ -717,7 +759,7 @@ class InProcessBam(SamtoolsHybrid):
                     a, e = groups.pop(0)
                     c0, c1 = int(chunk_first[a]), int(chunk_first[e])
                     try:
-                        cov, status = getattr(engine, device)(tl["native"], tids[a:e], bt[a:e], chunk_first[a:e + 1] - c0, flat_a[c0:c1].reshape(-1))
+                        cov, status = getattr(engine, device)(tl["native"], tids[a:e], bt[a:e], chunk_first[a:e + 1] - c0, flat_a[c0:c1].reshape(-1), **more)
                     except _lib.VaporHipError as err:
                         if "in one call" in str(err) and e - a >= 2:
                             groups[:0] = [(a, (a + e) // 2), ((a + e) // 2, e)]
@@ -735,7 +777,7 @@ class InProcessBam(SamtoolsHybrid):
                 with b._lock:
                     b._free.append(tl)
         for g in host:
-            out[g] = getattr(b, native)(tid_of[chroms[g]], bounds[g], chunks_of[g])
+            out[g] = getattr(b, native)(tid_of[chroms[g]], bounds[g], chunks_of[g], **more)
         return out
 
     def isfile(self, path: str) -> bool:
@@ -1123,6 +1165,34 @@ class MemorySamtools:
             w0, w3 = int(rg[0]), int(rg[1])
             out.append(signature.words(signature.answer([(r.pos, ops) for r, ops in zip(recs, got[2])
                                                          if w0 < w3 and r.pos - 1 < w3 and record_passes(r.mapq, r.flag, q, f)], rg)))
+        return out
+
+    def links_many(self, engine, bam: str, chroms, regions, partners):
+        """The five words per link region (`--links`) from the world's records that pass the read filter with
+        links.EXCLUDE among its flags: links.answer over (POS, operations, FLAG, SA) of the records that start before w3, the SA
+        value the record's `SA` tag when that is a string."""
+        from . import links, signature
+        from .bamio import record_passes
+        q, f = self.read_filter
+        f |= links.EXCLUDE
+        cache = self.__dict__.setdefault("_depth_cache", {})
+        out = []
+        for chrom, rg, pc in zip(chroms, regions, partners):
+            recs = self.world.reads.get(chrom, ())
+            got = cache.get(id(recs))
+            if got is None or got[0] is not recs or got[1] != len(recs):
+                got = (recs, len(recs), [signature.parse_cigar(r.cigar) for r in recs])
+                if getattr(self.world, "cache_ok", True):
+                    if len(cache) > 200000:
+                        cache.clear()
+                    cache[id(recs)] = got
+            w0, w3 = int(rg[0]), int(rg[1])
+            rows = []
+            for r, ops in zip(recs, got[2]):
+                if w0 < w3 and r.pos - 1 < w3 and record_passes(r.mapq, r.flag, q, f):
+                    sa = (r.tags or {}).get("SA")
+                    rows.append((r.pos, ops, r.flag, sa.encode("latin-1") if isinstance(sa, str) else None))
+            out.append(links.words(links.answer(rows, rg, pc, q)))
         return out
 
     def fai_lines(self, ref: str) -> Iterable[str]:

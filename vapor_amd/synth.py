@@ -909,6 +909,138 @@ def make_signature_world(seed: int, specs: Sequence[Tuple[str, int, str]] = SIGN
     return w
 
 
+LINKS_SPECS = ("DEL", "TANDUP", "INV", "3to5", "3to3")
+LINKS_DECOYS = ("no_sa", "other_contig", "off_by_one", "wrong_strand", "low_mapq")
+LINKS_DECOY_MAPQ = 3           # the mapQ of the `low_mapq` decoy's entry: a link for --min-mapq 3 and below, nothing above
+
+
+def make_links_world(seed: int, specs: Sequence[str] = LINKS_SPECS, reads: int = 4, half: int = 500, span: int = 12000,
+                     margin: int = 3000, jitter: Sequence[int] = (0,), ref_reads: int = 2, tol: int = 50,
+                     decoys: Sequence[str] = LINKS_DECOYS, chrom_prefix: str = "k") -> SynthWorld:
+    """A world whose SA tags mean something (`--links`).  Per spec a locus: DEL, TANDUP and INV of `span` bases on
+    a contig of their own, the event on bases [margin + 1, margin + span]; '3to5' and '3to3' breakends between two contigs of
+    their own, A:p and B:q with p = q = margin.  Every junction of the alt allele is crossed by `reads` molecules of 2 * half
+    bases, each written as an aligner writes it - a primary and a supplementary record (0x800), each aligned on its side of the
+    junction with the rest soft-clipped and an SA tag that names the other, `rname,pos,strand,CIGAR,60,0;` - molecule k read
+    from the forward strand for even k and from the reverse strand for odd k (both records' strand flips, the relation of the two
+    does not).  The molecules are those of DESIGN.md 4.21, with the junction's two coordinates x1 < x2 (or A:p and B:q):
+      DEL      x1 = J0, x2 = J1:  a piece that ends at J0 (RCLIP) and one that starts at J1 (LCLIP), same strand
+      TANDUP   a piece that starts at J0 (LCLIP) and one that ends at J1 (RCLIP), same strand
+      INV      the left junction: a piece that ends at J0 and one that ends at J1 (both RCLIP), opposite strands;
+               the right junction: a piece that starts at J0 and one that starts at J1 (both LCLIP), opposite strands
+      3to5     a piece that ends at A:p (RCLIP) and one that starts at B:q - 1 (LCLIP), same strand
+      3to3     a piece that ends at A:p and one that ends at B:q (both RCLIP), opposite strands
+    jitter: molecule k reports the first coordinate d = jitter[k % len(jitter)] bases to the right; the second moves with it -
+    by d when the two events differ (one piece grows by what the other loses on the same strand), by -d when they are the same
+    event.  `ref_reads` unclipped reads cross every breakpoint.  Decoys, one record each per locus, clipped at a breakpoint
+    exactly (`decoys` names those planted):
+      no_sa         at the left breakpoint, no SA tag                                        (a clip, not a split)
+      other_contig  at the left breakpoint, the right entry on a contig named <partner>x      (split, not linked: OL)
+      off_by_one    at the left breakpoint, the entry tol + 1 bases off                       (OL)
+      wrong_strand  at the right breakpoint, the right place on the other strand              (OR)
+      low_mapq      at the right breakpoint, the right entry with mapQ LINKS_DECOY_MAPQ        (a link at offset 0 unless cut)
+    For an INV the decoys are planted for the first region of each side.  With these all seven columns are known in closed form:
+    L = R = reads (INV: 2 * reads) + what low_mapq adds to R, OL = 2, OR = 1, the offsets the modes of the jitter."""
+    from . import links as _links
+    rng = np.random.default_rng(seed)
+    w = SynthWorld()
+    h = int(half)
+
+    def piece(c, x, ev, m):
+        """(pos0, CIGAR without its clip side filled in) of a piece of m aligned bases with event ev at x"""
+        return (x - m, x) if ev == _links.RCLIP else (x, x + m)
+
+    def record(qname, c, x, ev, m, clip_seq, flag, sa, mapq=60):
+        lo, hi = piece(c, x, ev, m)
+        own = w.contigs[c][lo:hi]
+        s = len(clip_seq)
+        if ev == _links.RCLIP:
+            cg, seq = "%dM%dS" % (m, s), own + clip_seq
+        else:
+            cg, seq = "%dS%dM" % (s, m), clip_seq + own
+        w.reads.setdefault(c, []).append(SamRecord(qname, c, lo + 1, cg, seq, m, {"SA": sa} if sa is not None else None, flag, mapq))
+
+    def entry(c, x, ev, m, s, minus, mapq=60):
+        lo, _hi = piece(c, x, ev, m)
+        cg = "%dM%dS" % (m, s) if ev == _links.RCLIP else "%dS%dM" % (s, m)
+        return "%s,%d,%s,%s,%d,0;" % (c, lo + 1, "-" if minus else "+", cg, mapq)
+
+    def molecule(qname, c1, x1, ev1, c2, x2, ev2, other, d, flip):
+        """the two records of a molecule whose pieces have (ev1 at x1 + d) and (ev2 at x2 + d or x2 - d)"""
+        d2 = d if ev1 != ev2 else -d
+        m1 = h + d if ev1 == _links.RCLIP else h - d
+        m2 = 2 * h - m1
+        f1, f2 = (0x10 if flip else 0), (0x10 if flip != other else 0)
+        lo1, hi1 = piece(c1, x1 + d, ev1, m1)
+        lo2, hi2 = piece(c2, x2 + d2, ev2, m2)
+        s1, s2 = w.contigs[c1][lo1:hi1], w.contigs[c2][lo2:hi2]
+        record(qname, c1, x1 + d, ev1, m1, revcomp(s2) if other else s2, f1, entry(c2, x2 + d2, ev2, m2, m1, bool(f2)))
+        record(qname, c2, x2 + d2, ev2, m2, revcomp(s1) if other else s1, f2 | 0x800, entry(c1, x1 + d, ev1, m1, m2, bool(f1)))
+
+    for li, t in enumerate(specs):
+        tag = "%s%d" % (chrom_prefix, li + 1)
+        if t in ("DEL", "TANDUP", "INV"):
+            c = tag
+            n = 2 * margin + span
+            w.contigs[c] = random_dna(rng, n)
+            j0, j1 = margin, margin + span
+            locus = [c, j0 + 1, j1]
+            w.loci.append(Locus(c, t, j0 + 1, j1, "lk%d" % (li + 1)))
+            if t == "DEL":
+                juncs = [(c, j0, _links.RCLIP, c, j1, _links.LCLIP, False)]
+            elif t == "TANDUP":
+                juncs = [(c, j0, _links.LCLIP, c, j1, _links.RCLIP, False)]
+            else:
+                juncs = [(c, j0, _links.RCLIP, c, j1, _links.RCLIP, True), (c, j0, _links.LCLIP, c, j1, _links.LCLIP, True)]
+            points = [(c, j0), (c, j1)]
+        elif t in ("3to5", "3to3"):
+            ca, cb = tag + "a", tag + "b"
+            p = q = margin
+            w.contigs[ca] = random_dna(rng, 2 * margin)
+            w.contigs[cb] = random_dna(rng, 2 * margin)
+            locus = [ca, p, cb, q, t, ""]
+            w.loci.append(Locus(ca, "BND", p, q, "lk%d" % (li + 1), "", {"form": t, "mate_chrom": cb}))
+            if t == "3to5":
+                juncs = [(ca, p, _links.RCLIP, cb, q - 1, _links.LCLIP, False)]
+            else:
+                juncs = [(ca, p, _links.RCLIP, cb, q, _links.RCLIP, True)]
+            points = [(ca, p), (cb, q)]
+        else:
+            raise ValueError(t)
+        for ji, (c1, x1, ev1, c2, x2, ev2, other) in enumerate(juncs):
+            for k in range(reads):
+                molecule("%s_j%d_m%d" % (tag, ji, k), c1, x1, ev1, c2, x2, ev2, other, int(jitter[k % len(jitter)]), bool(k & 1))
+        for c, x in points:
+            for k in range(ref_reads):
+                lo = x - h + 37 * (k + 1)
+                w.reads.setdefault(c, []).append(SamRecord("%s_ref%d_%d" % (tag, x, k), c, lo + 1, "%dM" % (2 * h), w.contigs[c][lo:lo + 2 * h], 2 * h))
+        # the decoys: the question of the side's first region, answered wrongly in one way each
+        left, right = _links.regions("BND" if t in ("3to5", "3to3") else t, locus, lambda name: len(w.contigs[name]))
+        for name in decoys:
+            c, f, pc = (left if name in ("no_sa", "other_contig", "off_by_one") else right)[0]
+            x, y, ev, pend, rel = f[2], f[3], f[6], f[7], f[8]
+            clip = random_dna(rng, h)
+            minus = bool(rel)                      # the record is on the forward strand: the entry's strand by the relation
+            if name == "no_sa":
+                sa = None
+            else:
+                yy = y + tol + 1 if name == "off_by_one" else y
+                sa = entry(pc + "x" if name == "other_contig" else pc, yy, _links.RCLIP if pend == _links.END_B else _links.LCLIP, h, h,
+                           (not minus) if name == "wrong_strand" else minus, LINKS_DECOY_MAPQ if name == "low_mapq" else 60)
+            record("%s_decoy_%s" % (tag, name), c, x, ev, h, clip, 0, sa)
+    for c in w.reads:
+        w.reads[c].sort(key=lambda r: r.pos)
+    return w
+
+
+def links_vcf_text(world: SynthWorld) -> str:
+    """make_links_world's loci as `vapor vcf --bnd` reads them: the DEL, TANDUP and INV records of vcf_text, then the breakend
+    records of bnd_vcf_text with their mates."""
+    simple = SynthWorld()
+    simple.loci = [l for l in world.loci if l.svtype != "BND"]
+    return vcf_text(simple) + bnd_vcf_text(world, True)
+
+
 def mirror_world(world: SynthWorld) -> SynthWorld:
     """M(W): the world as its reverse-complemented contigs hold it (x -> L + 1 - x on a contig of L bases; `--both-ends`,
     DESIGN.md 4.14).  Contigs: their reverse complement (seqio.rc_read: nothing is dropped).  Records: seqio.mirror_records -
