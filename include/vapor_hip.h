@@ -544,6 +544,25 @@ int vapor_bam_links(vapor_bam* bam, int32_t tid, const int64_t* fields, const ui
                     const uint64_t* chunks, int64_t* out);
 int vapor_bam_links_device(vapor_ctx* ctx, vapor_bam* bam, int32_t n_regions, const int32_t* tid, const int64_t* regions, const uint8_t* names,
                            int64_t names_len, const int32_t* chunk_first, const uint64_t* chunks, int64_t* out, int32_t* status);
+/*
+ * Alt and ref alignments per call (`--support`; not in the reference).  A support region is a contig and eleven
+ * fields: the nine of a signature region with their meaning - w0, w3, x0, x1, tol, min_clip, nmin, nmax, mask - then flank (F,
+ * 1..65535) and gmin (g, 1 or more); mask bit 6: reference support is asked at x0, bit 7: at x1.  A record counts and has events
+ * as for vapor_bam_signature; every fact is per record.  With pos its 0-based start and q its reference end: cg - it has a GAP
+ * or INSOP that vapor_bam_signature counts; clip_k (k = 0, 1) - it has a clip event that vapor_bam_signature counts at target k
+ * (bits 2k, 2k + 1); blocked_k - a D or N of n >= g bases at cursor a with a < x_k + F and a + n > x_k - F, or an I of n >= g
+ * bases at cursor a with x_k - F <= a <= x_k + F; span_k - pos <= x_k - F, q >= x_k + F and not blocked_k; cov_k - pos <= x_k < q.
+ * out, seven a region: alt_cg (records with cg), alt_l (clip_0, not cg), alt_r (clip_1, not cg), ref_0 (bit 6, span_0, not cg, not
+ * clip_0), ref_1 (bit 7, span_1, not cg, not clip_1), cov_0, cov_1 (whatever the mask).
+ * vapor_bam_support: one region on the host, `chunks` its .bai chunks as in vapor_bam_depth; errors as there.  VAPOR_E_ARG for
+ * what vapor_bam_signature refuses, flank outside 1..65535 or gmin < 1.
+ * vapor_bam_support_device: n_regions regions in one call as vapor_bam_depth_device takes them (regions: eleven a region, out:
+ * seven a region) - bam_support_kernel, one wavefront a region.  status[g] = 0, or a positive code of vapor_bam_chop_device's
+ * where the region is the host route's (its words are 0 then).  Nothing stays on the device.
+ */
+int vapor_bam_support(vapor_bam* bam, int32_t tid, const int64_t* fields, int32_t n_chunks, const uint64_t* chunks, int64_t* out);
+int vapor_bam_support_device(vapor_ctx* ctx, vapor_bam* bam, int32_t n_regions, const int32_t* tid, const int64_t* regions,
+                             const int32_t* chunk_first, const uint64_t* chunks, int64_t* out, int32_t* status);
 /* what the context's last vapor_bam_chop_device (or _tagged) did, for measurement (bench.py): out[0..6] = regions, BGZF blocks,
  * compressed bytes sent over the link, inflated bytes, the inflate kernel's duration between two events on its stream (ms), the
  * whole call (ms), bytes of kept reads and statuses copied back from the device */

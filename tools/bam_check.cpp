@@ -14,6 +14,9 @@
 // contig from 0 to the one behind `tid` the eight regions ev x pend x rel, the window [0, 2^31 - 1), the local target start, the
 // partner target end, tolerance 50, minimum clip 30, the partner's name the bytes "c1" of a three-name blob, under the handle's
 // filter.
+// A last argument `sup` adds, in place of the depth pass, a support pass (vapor_bam_support) over every record: a
+// region per contig from 0 to the one behind `tid`, the signature pass's nine fields with the mask 255, the flank 51 and the
+// blocking length 30, under the handle's filter.
 // tests/test_bamio.py builds it and runs it over the damaged files of its other tests and a few hundred randomly damaged ones.
 #include "vapor_bam.cpp"
 #include <cstdio>
@@ -24,8 +27,9 @@ int main(int argc, char** argv)
     const bool depth = argc > 7 && !strcmp(argv[argc - 1], "depth");
     const bool sig = argc > 7 && !strcmp(argv[argc - 1], "sig");
     const bool lnk = argc > 7 && !strcmp(argv[argc - 1], "links");
-    if (depth || sig || lnk) --argc;
-    if (argc < 7) { fprintf(stderr, "usage: bam_check file.bam first_voffset tid start end flank [threads [min_mapq exclude_flags]] [depth | sig | links]\n"); return 2; }
+    const bool sup = argc > 7 && !strcmp(argv[argc - 1], "sup");
+    if (depth || sig || lnk || sup) --argc;
+    if (argc < 7) { fprintf(stderr, "usage: bam_check file.bam first_voffset tid start end flank [threads [min_mapq exclude_flags]] [depth | sig | links | sup]\n"); return 2; }
     vapor_bam* b = nullptr;
     if (vapor_bam_open(argv[1], &b) != 0) { printf("open: %s\n", vapor_bam_last_error()); return 0; }
     if (argc > 7) vapor_bam_set_threads(b, atoi(argv[7]));
@@ -106,6 +110,15 @@ int main(int argc, char** argv)
                 printf("links: contig %d ev %d pend %d rel %d rc %d words %lld %lld %lld %lld %lld %s\n", t, q & 1, (q >> 1) & 1, (q >> 2) & 1, rc, (long long)out[0],
                        (long long)out[1], (long long)out[2], (long long)out[3], (long long)out[4], rc ? vapor_bam_last_error() : "");
             }
+    }
+    if (sup) {
+        for (int32_t t = 0; t <= std::max(tid, 0) + 1; ++t) {
+            const int64_t fields[11] = {0, ((int64_t)1 << 31) - 1, start, std::max(end, start), 50, 30, 0, (int64_t)1 << 28, 255, 51, 30};
+            int64_t out[7] = {0, 0, 0, 0, 0, 0, 0};
+            rc = vapor_bam_support(b, t, fields, 1, chunk, out);
+            printf("sup: contig %d rc %d words %lld %lld %lld %lld %lld %lld %lld %s\n", t, rc, (long long)out[0], (long long)out[1], (long long)out[2],
+                   (long long)out[3], (long long)out[4], (long long)out[5], (long long)out[6], rc ? vapor_bam_last_error() : "");
+        }
     }
     vapor_bam_close(b);
     return 0;

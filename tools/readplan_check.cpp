@@ -1,5 +1,5 @@
 // readplan_check.cpp - the plan of a device reader call (vapor_amd/csrc/vapor_readplan.h: check_args, plan_spans, layout, ChopMeta,
-// collect for vapor_bam_chop_device*; the same five over DepthCall, DepthMeta, DepthLayout for vapor_bam_depth_device and over SigCall, SigMeta, SigLayout for vapor_bam_signature_device; plan_stretches, stage_stretches, layout_arena, place_windows, FastaMeta, gather_texts for
+// collect for vapor_bam_chop_device*; the same five over DepthCall, DepthMeta, DepthLayout for vapor_bam_depth_device and over SigCall, SigMeta, SigLayout for vapor_bam_signature_device, LinkCall's for vapor_bam_links_device and SupCall's for vapor_bam_support_device; plan_stretches, stage_stretches, layout_arena, place_windows, FastaMeta, gather_texts for
 // vapor_fasta_windows_device) on a CPU, against direct statements of its rules.  It needs neither zlib nor files: the spans and
 // stretches are block tables the program fills in itself, the calls come from fixed seeds, and every buffer is a heap allocation
 // of exactly the bytes the header says it needs.  Nothing here is compared with recorded plans.
@@ -1432,6 +1432,165 @@ static void check_links()
            n_calls, n_regions_seen, n_refused);
 }
 
+// ================================================================================================================================
+// vapor_bam_support_device: SupCall's plan over the same plan_spans_of / layout_of
+// ================================================================================================================================
+static void check_support()
+{
+    long n_calls = 0, n_refused = 0, n_regions_seen = 0;
+    for (int it = 0; it < 1000; ++it) {
+        g_case = it;
+        const int n = one_in(15) ? 0 : rnd(1, 12);
+        std::vector<SRegion> regs;
+        std::vector<int32_t> tid((size_t)n), chunk_first((size_t)n + 1, 0);
+        std::vector<int64_t> fields((size_t)SUP_FIELDS * (size_t)n);
+        std::vector<uint64_t> chunks;
+        std::vector<char> bad((size_t)n, 0);
+        for (int g = 0; g < n; ++g) {
+            // the nine signature fields with their eight ways to be bad, then 9 flank < 1; 10 flank > 65535; 11 gmin < 1
+            const int how = one_in(3) ? rnd(1, 11) : 0;
+            regs.push_back(sig_region(how <= 8 ? how : 0));
+            SRegion& r = regs.back();
+            int64_t* f = fields.data() + (size_t)SUP_FIELDS * (size_t)g;
+            for (int k = 0; k < SIG_FIELDS; ++k) f[k] = r.f[k];
+            if (one_in(8)) f[8] = rnd(0, 255);
+            f[9] = one_in(4) ? (one_in(2) ? 1 : 65535) : rnd(1, 65535);
+            f[10] = one_in(6) ? ((int64_t)1 << rnd(28, 40)) : rnd(1, 5000);
+            if (how == 9) f[9] = -(int64_t)rnd(0, 9);
+            if (how == 10) f[9] = 65536 + rnd(0, 1 << 20);
+            if (how == 11) f[10] = -(int64_t)rnd(0, 9);
+            bad[(size_t)g] = how != 0;
+            tid[(size_t)g] = r.tid;
+            for (auto& c : r.chunks) { chunks.push_back(c.first); chunks.push_back(c.second); }
+            chunk_first[(size_t)g + 1] = (int32_t)(chunks.size() / 2);
+            // the one statement, against the rule spelled out (how 8 is a chunk that descends: the fields are good)
+            const bool fields_bad = how != 0 && how != 8;
+            CHECK(sup_region_ok(tid[(size_t)g], f) == !fields_bad, "region %d: sup_region_ok, how %d", g, how);
+            CHECK(!sup_region_ok(tid[(size_t)g], f) || sig_region_ok(tid[(size_t)g], f), "region %d: a support region is a signature region", g);
+        }
+        SupCall c;
+        c.n_regions = n; c.tid = tid.data(); c.regions = fields.data(); c.chunk_first = chunk_first.data();
+        c.chunks = chunks.empty() ? nullptr : chunks.data();
+        c.filter_word = depth_filter_word((uint32_t)rnd(0, 65535) | ((uint32_t)rnd(0, 255) << 16));
+        std::vector<int64_t> out((size_t)SUP_ANSWER_WORDS * (size_t)std::max(n, 1), 77);
+        std::vector<int32_t> status((size_t)std::max(n, 1), -9);
+        CHECK(!check_args(c, out.data(), status.data()), "a good call is refused");
+        if (n) {
+            CHECK(check_args(c, nullptr, status.data()).code == VAPOR_E_ARG && check_args(c, out.data(), nullptr).code == VAPOR_E_ARG, "null outputs pass");
+            SupCall d = c; d.regions = nullptr;
+            CHECK(check_args(d, out.data(), status.data()).code == VAPOR_E_ARG, "null regions pass");
+            d = c; d.n_regions = -1;
+            CHECK(check_args(d, out.data(), status.data()).code == VAPOR_E_ARG, "a negative count passes");
+        }
+        SpanPlan p;
+        CHECK(!plan_spans(c, status.data(), p), "a call below the size limit is refused");
+        size_t si = 0, stage = 0;
+        for (int g = 0; g < n; ++g) {
+            CHECK(status[(size_t)g] == (bad[(size_t)g] ? REG_MALFORMED : 0), "region %d: status %d, bad %d", g, status[(size_t)g], (int)bad[(size_t)g]);
+            CHECK(p.span_first[(size_t)g] == (int32_t)si, "region %d: span_first", g);
+            if (bad[(size_t)g]) { ++n_refused; continue; }
+            for (auto& ch : regs[(size_t)g].chunks) {
+                CHECK(si < p.spans.size(), "region %d: a span is missing", g);
+                const HostSpan& sp = p.spans[si++];
+                const size_t want = (size_t)((ch.second >> 16) - (ch.first >> 16)) + ((ch.second & 0xFFFFu) ? 65536 + 64 : 0);
+                CHECK(sp.region == g && sp.cs == ch.first && sp.ce == ch.second && sp.want == want && sp.stage_off == stage, "region %d: span fields", g);
+                stage += up64(want);
+            }
+        }
+        CHECK(si == p.spans.size() && p.span_first[(size_t)n] == (int32_t)si && p.stage_bytes == stage, "spans %zu of %zu, stage %zu of %zu", si, p.spans.size(), stage, p.stage_bytes);
+        for (HostSpan& sp : p.spans) fake_scan(sp);
+        std::vector<int32_t> before = status;
+        SupLayout L;
+        CHECK(!layout(c, p, status.data(), L), "a layout below the size limit is refused");
+        CHECK((int)L.regs.size() == std::max(n, 1), "regions in the layout");
+        size_t n_sp = 0, arena = 0, n_blk = 0;
+        for (int g = 0; g < n; ++g) {
+            bool scan_bad = false;
+            for (int32_t s = p.span_first[(size_t)g]; s < p.span_first[(size_t)g + 1]; ++s) scan_bad |= p.spans[(size_t)s].bad;
+            CHECK(status[(size_t)g] == (scan_bad ? REG_MALFORMED : before[(size_t)g]), "region %d: status after the scan", g);
+            const SupRegion& R = L.regs[(size_t)g];
+            const int64_t* f = fields.data() + (size_t)SUP_FIELDS * (size_t)g;
+            CHECK(R.span_first == (int32_t)n_sp, "region %d: span_first in the layout", g);
+            if (status[(size_t)g]) {
+                CHECK(R.span_n == 0 && R.mask == 0 && R.tol == 0 && R.w0 == 0 && R.w3 == 0 && R.flank == 0 && R.gmin == 0, "region %d: a refused region's record", g);
+                continue;
+            }
+            // the record: the fields as given where they are in range, clamped where a clamp admits the same records
+            CHECK(R.tid == tid[(size_t)g] && R.filter == c.filter_word && R.w0 == f[0] && R.w3 == f[1] && R.x0 == f[2] && R.x1 == f[3] && R.tol == f[4], "region %d: its record", g);
+            CHECK(R.min_clip == (f[5] < 1 ? 1 : f[5]) && R.mask == ((uint32_t)f[8] & 255u) && R.flank == f[9], "region %d: min_clip, mask %u, flank %d", g, R.mask, R.flank);
+            auto clamped = [](int64_t v) { return v < -1 ? (int64_t)-1 : (v > ((int64_t)1 << 28) ? ((int64_t)1 << 28) : v); };
+            CHECK(R.nmin == clamped(f[6]) && R.nmax == clamped(f[7]) && R.nmin <= R.nmax, "region %d: length bounds", g);
+            CHECK(R.gmin == (f[10] > ((int64_t)1 << 28) ? ((int64_t)1 << 28) : f[10]) && R.gmin >= 1, "region %d: gmin %d of %lld", g, R.gmin, (long long)f[10]);
+            for (int64_t len : {(int64_t)0, (int64_t)1, f[10] - 1, f[10], f[10] + 1, ((int64_t)1 << 28) - 1})
+                if (len >= 0 && len < ((int64_t)1 << 28))
+                    CHECK((len >= f[10]) == (len >= R.gmin), "region %d: the clamped blocking length admits other operations at %lld", g, (long long)len);
+            CHECK(R.span_n == p.span_first[(size_t)g + 1] - p.span_first[(size_t)g], "region %d: span_n", g);
+            for (int32_t s = p.span_first[(size_t)g]; s < p.span_first[(size_t)g + 1]; ++s) {
+                const HostSpan& sp = p.spans[(size_t)s];
+                const BamSpan& d = L.spans[n_sp++];
+                CHECK(d.u_begin == arena + sp.u_begin && d.u_end == arena + sp.u_end && d.u_limit == arena + sp.u_total && d.blk_first == n_blk && d.blk_n == sp.blks.size(),
+                      "region %d: a span in the arena", g);
+                n_blk += sp.blks.size();
+                arena += up64(sp.u_total);
+            }
+        }
+        CHECK(L.arena == arena && L.blks.size() == n_blk && L.spans.size() == n_sp, "arena %zu of %zu", arena, L.arena);
+        const SupMeta& M = L.meta;
+        const size_t nr = (size_t)std::max(n, 1), nb = std::max<size_t>(n_blk, 1), ns = std::max<size_t>(n_sp, 1);
+        const size_t offs[6] = {M.blks.off, M.spans.off, M.regs.off, M.blk_status.off, M.ans.off, M.reg_status.off};
+        const size_t sizes[6] = {24 * nb, 24 * ns, 80 * nr, 4 * nb, 28 * nr, 4 * nr};
+        size_t at = 0;
+        for (int t = 0; t < 6; ++t) { CHECK(offs[t] == at && at % 64 == 0, "table %d at %zu, not %zu", t, offs[t], at); at += up64(sizes[t]); }
+        CHECK(M.bytes == at && M.in_bytes == M.blk_status.off && M.back_bytes() == M.bytes - M.blk_status.off, "the block's sizes");
+        std::vector<uint8_t> h(M.bytes, 0xEE);
+        L.fill(h.data());
+        CHECK(!memcmp(M.regs.in(h.data()), L.regs.data(), 80 * nr) && (!n_blk || !memcmp(M.blks.in(h.data()), L.blks.data(), 24 * n_blk)) &&
+              (!n_sp || !memcmp(M.spans.in(h.data()), L.spans.data(), 24 * n_sp)), "fill");
+        uint32_t* da = M.ans.in(h.data());
+        int32_t* rs = M.reg_status.in(h.data());
+        for (size_t g = 0; g < nr; ++g) {
+            for (int k = 0; k < SUP_ANSWER_WORDS; ++k) da[(size_t)SUP_ANSWER_WORDS * g + (size_t)k] = (uint32_t)rng();
+            rs[g] = one_in(5) ? rnd(1, 5) : 0;
+        }
+        std::vector<int32_t> st2 = status;
+        collect(c, M, h.data(), out.data(), st2.data());
+        for (int g = 0; g < n; ++g) {
+            const bool host_refused = status[(size_t)g] != 0, dev_refused = rs[(size_t)g] != 0;
+            CHECK(st2[(size_t)g] == (host_refused ? status[(size_t)g] : rs[(size_t)g]), "region %d: collected status", g);
+            for (int k = 0; k < SUP_ANSWER_WORDS; ++k) {
+                const int64_t want = host_refused || dev_refused ? 0 : (int64_t)da[(size_t)SUP_ANSWER_WORDS * (size_t)g + (size_t)k];
+                CHECK(out[(size_t)SUP_ANSWER_WORDS * (size_t)g + (size_t)k] == want, "region %d: word %d", g, k);
+            }
+        }
+        ++n_calls;
+        n_regions_seen += n;
+    }
+    // the two "in one call" refusals the Python side halves a group on
+    {
+        std::vector<int32_t> tid(40, 0), chunk_first(41), status(40);
+        std::vector<int64_t> fields;
+        std::vector<uint64_t> chunks;
+        for (int g = 0; g < 40; ++g) {
+            for (int64_t v : {0, 100, 40, 60, 50, 30, 30, 200, 255, 51, 30}) fields.push_back(v);
+            chunks.push_back((uint64_t)g << 44); chunks.push_back(((uint64_t)g << 44) + (((uint64_t)1 << 26) << 16));
+            chunk_first[(size_t)g + 1] = g + 1;
+        }
+        SupCall c;
+        c.n_regions = 40; c.tid = tid.data(); c.regions = fields.data(); c.chunk_first = chunk_first.data(); c.chunks = chunks.data();
+        SpanPlan p;
+        const Refusal r = plan_spans(c, status.data(), p);
+        CHECK(r.code == VAPOR_E_ARG && strstr(r.msg, "vapor_bam_support_device") && strstr(r.msg, "in one call"), "2.5 GB of blocks pass");
+        c.n_regions = 20;
+        CHECK(!plan_spans(c, status.data(), p), "1.25 GB of blocks are refused");
+        for (HostSpan& sp : p.spans) { sp.blks.push_back(Block{0, 6, 100, 0, 65536, 0}); sp.u_total = (uint64_t)120 << 20; sp.u_begin = 0; sp.u_end = 100; sp.got = sp.want; }
+        SupLayout L;
+        const Refusal r2 = layout(c, p, status.data(), L);
+        CHECK(r2.code == VAPOR_E_ARG && strstr(r2.msg, "vapor_bam_support_device") && strstr(r2.msg, "in one call"), "2.4 GB of block data pass");
+    }
+    printf("support plan: %ld calls with %ld regions (%ld refused): statuses, spans, arena, tables, clamped fields and collected words equal the rule; both size refusals say \"in one call\"\n",
+           n_calls, n_regions_seen, n_refused);
+}
+
 int main()
 {
     check_statuses();
@@ -1443,6 +1602,7 @@ int main()
     check_depth();          // (behind the others: the calls above draw from the one seeded stream, and their counts are quoted)
     check_signature();
     check_links();
+    check_support();
     printf("readplan_check: all equal\n");
     return 0;
 }

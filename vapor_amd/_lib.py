@@ -62,6 +62,7 @@ EXPORTS = [
     "vapor_bam_depth", "vapor_bam_depth_device",
     "vapor_bam_signature", "vapor_bam_signature_device",
     "vapor_bam_links", "vapor_bam_links_device",
+    "vapor_bam_support", "vapor_bam_support_device",
 ]
 # entry points a library may lack (the CPU twin of the C ABI has no wide or any-k route and no refinement kernel): bound when
 # present, and the engine's wide, any-k and grid methods raise NotImplementedError when they are not
@@ -79,7 +80,9 @@ OPTIONAL_EXPORTS = ("vapor_wide_batch", "vapor_clean_hits_wide", "vapor_anyk_bat
                     # (`--signatures`, DESIGN.md 4.20: without them a run takes signature.answer over bamio's records)
                     "vapor_bam_signature", "vapor_bam_signature_device",
                     # (`--links`, DESIGN.md 4.21: without them a run takes links.answer over bamio's records)
-                    "vapor_bam_links", "vapor_bam_links_device")
+                    "vapor_bam_links", "vapor_bam_links_device",
+                    # (`--support`, DESIGN.md 4.22: without them a run takes support.answer over bamio's records)
+                    "vapor_bam_support", "vapor_bam_support_device")
 MAX_CANDIDATES = 128           # breakpoint refinement: candidates per locus (VAPOR_MAX_CANDIDATES)
 
 _lib = None
@@ -267,6 +270,10 @@ def bind(L: ctypes.CDLL) -> ctypes.CDLL:
         L.vapor_bam_signature.argtypes = [vp, ctypes.c_int32, vp, ctypes.c_int32, vp, vp]
     if hasattr(L, "vapor_bam_signature_device"):
         L.vapor_bam_signature_device.argtypes = [vp, vp, ctypes.c_int32, vp, vp, vp, vp, vp, vp]
+    if hasattr(L, "vapor_bam_support"):
+        L.vapor_bam_support.argtypes = [vp, ctypes.c_int32, vp, ctypes.c_int32, vp, vp]
+    if hasattr(L, "vapor_bam_support_device"):
+        L.vapor_bam_support_device.argtypes = [vp, vp, ctypes.c_int32, vp, vp, vp, vp, vp, vp]
     if hasattr(L, "vapor_bam_links"):
         L.vapor_bam_links.argtypes = [vp, ctypes.c_int32, vp, vp, ctypes.c_int64, ctypes.c_int32, vp, vp]
     if hasattr(L, "vapor_bam_links_device"):

@@ -512,6 +512,26 @@ class BamFile:
                 self._free.append(tl)
         return [int(x) for x in out]
 
+    def support_native(self, tid: int, region, chunks=None):
+        """The seven words of one support region (`--support`; region: support.FIELDS) through the library's host
+        reader (vapor_bam_support); the .bai lookup stays here.  ValueError with the reader's message for a file that breaks a
+        rule or a region the reader refuses."""
+        from . import _lib
+        lib = _lib.load()
+        r = np.ascontiguousarray(region, dtype=np.int64)
+        ch = self.index.chunks(tid, int(r[0]), int(r[1])) if chunks is None and tid >= 0 and 0 <= r[0] <= r[1] else (chunks or [])
+        out = np.zeros(7, dtype=np.int64)
+        flat = np.asarray(ch, dtype=np.uint64).reshape(-1)
+        tl = self._take_handle(lib)
+        try:
+            if lib.vapor_bam_support(tl["native"], int(tid), r.ctypes.data, len(flat) // 2, flat.ctypes.data if len(flat) else None,
+                                     out.ctypes.data) != 0:
+                raise ValueError(lib.vapor_bam_last_error().decode())
+        finally:
+            with self._lock:
+                self._free.append(tl)
+        return [int(x) for x in out]
+
     def links_native(self, tid: int, region, chunks=None, names: bytes = b""):
         """The five words of one link region (`--links`; region: links.FIELDS, then offset and length of the
         partner contig's name in `names`) through the library's host reader (vapor_bam_links); the .bai lookup stays here.

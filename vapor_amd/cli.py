@@ -33,8 +33,12 @@ of these modes.
 gives it; those that are split but go elsewhere; and the modal coordinates the linked pieces name; appends VaPoR_LNK_L,
 VaPoR_LNK_R, VaPoR_LNK_N, VaPoR_LNK_OL, VaPoR_LNK_OR, VaPoR_LNK_POS and VaPoR_LNK_END; the row's own columns are the plain
 run's; not together with another of these modes.
+--support (bed, vcf): alt and ref alignments per DEL, TANDUP, INV and INS call - the records that carry the event
+and the records that run straight through a breakpoint as the reference does - with the allele fraction and the genotype the two
+numbers give; appends VaPoR_SUP_ALT, VaPoR_SUP_REF, VaPoR_SUP_REFL, VaPoR_SUP_REFR, VaPoR_SUP_COVL, VaPoR_SUP_COVR, VaPoR_SUP_VAF,
+VaPoR_SUP_GT and VaPoR_SUP_GQ; the row's own columns are the plain run's; not together with another of these modes.
 
---refine, --phased (with --phase-vcf), --both-ends, --depth, --signatures and --links each append columns to every row and exclude one another: a run has one
+--refine, --phased (with --phase-vcf), --both-ends, --depth, --signatures, --links and --support each append columns to every row and exclude one another: a run has one
 mode (vapor_amd.modes) or none, built once in _main and handed as one argument to bed_jobs / vcf_jobs (which
 driver a locus takes), score_jobs (the payload gathered into Job.extra), the table writer and SF.vcf_vapor_modify.  An option
 that adds columns is a module with INFO, COLUMNS, pack, unpack and columns_many, a Mode made of it, and its branch in _simple_job.
@@ -811,6 +815,42 @@ def _links_payloads(jobs, todo, engine):
 modes.LINKS.chunk_payloads = _links_payloads
 
 
+def _support_payloads(jobs, todo, engine):
+    """`--support`: like the signatures, the evidence is the chunk's - the support regions of all its DEL,
+    TANDUP, INV and INS loci (support.regions of Job.spec, clipped to the backend's contig length) go to the read backend in one
+    support_many call per BAM file (a per-chromosome pattern: per file, the words summed).  Returns {t: support.Payload}; a
+    locus of another type has none."""
+    from . import seqio, support
+    be = seqio.get_backend()
+    by_bam = {}
+    for t in todo:
+        j = jobs[t]
+        if j.spec is not None and j.ctx is not None and j.spec[0] in support.TYPES:
+            by_bam.setdefault((j.ctx[1], j.ctx[2]), []).append(t)
+    out = {}
+    for (bam, ref), ts in by_bam.items():
+        files = seqio.bam_in_decide(bam, None)
+        where, chroms, regs_all, loci = [], [], [], []
+        for t in ts:
+            name, chrom, s, e, ins_seq = jobs[t].spec[:5]
+            locus = [chrom, s, len(ins_seq)] if name == 'INS' else [chrom, s, e]
+            regs = support.regions(name, locus, be.contig_length(files[0], ref, chrom) if files else 0)
+            where.append((len(regs_all), regs))
+            loci.append(locus)
+            chroms += [chrom] * len(regs)
+            regs_all += regs
+        got = [[0] * 7 for _ in regs_all]
+        for f in files:
+            for k, a in enumerate(be.support_many(engine, f, chroms, regs_all)):
+                got[k] = support.merge_words(got[k], a)
+        for t, locus, (at, regs) in zip(ts, loci, where):
+            out[t] = support.payload(jobs[t].spec[0], locus, regs, got[at:at + len(regs)])
+    return out
+
+
+modes.SUPPORT.chunk_payloads = _support_payloads
+
+
 last_timing: dict = {}          # of the most recent score_jobs: seconds scoring this rank's share, seconds in the gather
 
 
@@ -983,6 +1023,14 @@ def build_parser() -> argparse.ArgumentParser:
                         'duplicate records never count, supplementary records do, --min-mapq holds for the entries as well; appends '
                         'VaPoR_LNK_L, VaPoR_LNK_R, VaPoR_LNK_N, VaPoR_LNK_OL, VaPoR_LNK_OR, VaPoR_LNK_POS and VaPoR_LNK_END (vcf: to '
                         'INFO); not together with --refine, --phased, --phase-vcf, --both-ends, --depth or --signatures')
+    p.add_argument('--support', action='store_true',
+                   help='bed, vcf: alt and ref alignments per DEL, TANDUP, INV and INS call: the records that carry the event as '
+                        '--signatures counts them (once a record), the records that reach 51 bases to either side of a breakpoint '
+                        'with no D, N or I of 30 bases or more near it, and the records that cover each breakpoint; unmapped, '
+                        'secondary, QC-fail and duplicate records never count, supplementary records do; appends VaPoR_SUP_ALT, '
+                        'VaPoR_SUP_REF, VaPoR_SUP_REFL, VaPoR_SUP_REFR, VaPoR_SUP_COVL, VaPoR_SUP_COVR, VaPoR_SUP_VAF, VaPoR_SUP_GT and '
+                        'VaPoR_SUP_GQ (vcf: to INFO; no VAF, GT or GQ for a TANDUP); not together with --refine, --phased, '
+                        '--phase-vcf, --both-ends, --depth, --signatures or --links')
     p.add_argument('--min-mapq', metavar='Q', type=_int_in('--min-mapq', 0, 255), default=0,
                    help='every sub-command: skip records with MAPQ below Q (0..255, default 0), as `samtools view -q Q` does; a '
                         'filtered record is treated as if it were not in the file')
@@ -1111,6 +1159,14 @@ def _main(argv, held) -> int:
             parser.error('--links and --depth cannot be combined (a run has one mode)')
         if args.signatures:
             parser.error('--links and --signatures cannot be combined (a run has one mode)')
+    if args.support:
+        if cmd not in ('bed', 'vcf'):
+            parser.error('--support applies to `vapor bed` and `vapor vcf`')
+        for on, what in ((refine is not None, '--refine'), (args.phase_vcf is not None, '--phase-vcf'), (args.phased, '--phased'),
+                         (args.both_ends, '--both-ends'), (args.depth, '--depth'), (args.signatures, '--signatures'),
+                         (args.links, '--links')):
+            if on:
+                parser.error('--support and %s cannot be combined (a run has one mode)' % what)
     if args.phase_vcf is not None:
         # (every rank reads the VCF itself; the sites ride on the backend the reads are taken through)
         from . import phase as ph
@@ -1149,6 +1205,8 @@ def _main(argv, held) -> int:
         mode = modes.SIGNATURES
     elif args.links:
         mode = modes.LINKS
+    elif args.support:
+        mode = modes.SUPPORT
     figure_fn = None
     if not args.no_figures:
         from . import figures

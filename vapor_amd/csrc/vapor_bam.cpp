@@ -875,6 +875,77 @@ extern "C" int vapor_bam_signature(vapor_bam* b, int32_t tid, const int64_t* fie
     }
 }
 
+// Alt and ref alignments of one support region (`--support`; vapor_amd/support.py answer is the rule,
+// bam_support_kernel the device's form): bam_walk_records to w3, and per passing record - not per event - whether it carries a
+// GAP or INSOP that 4.20 counts, whether a clip of it counts at either target, whether it reaches `flank` bases to either side
+// of a target with no D, N or I of gmin bases in between, and whether it covers the target's base.  An empty window has no
+// records.
+// fields: the nine of bam_signature_impl, then flank and gmin (vapor_readplan.h SUP_FIELDS); out: alt_cg, alt_l, alt_r, ref_0,
+// ref_1, cov_0, cov_1.
+static int bam_support_impl(vapor_bam* b, int32_t tid, const int64_t* fields, int32_t n_chunks, const uint64_t* chunks, int64_t* out)
+{
+    using namespace vapor_bamdev;
+    if (!b || !fields || !out || n_chunks < 0 || (n_chunks && !chunks)) return bfail(VAPOR_E_ARG, "vapor_bam_support: null argument");
+    if (!vapor_readplan::sup_region_ok(tid, fields))
+        return bfail(VAPOR_E_ARG, "vapor_bam_support: the window does not ascend from 0 to a BAM position, the tolerance is not 0..255, "
+                                  "the length bounds descend, the flank is not 1..65535, the blocking length is below 1, or the contig is none");
+    SupRegion R;
+    vapor_readplan::sup_region_set(R, tid, fields, 0);
+    const int64_t x[2] = {R.x0, R.x1}, tol = R.tol, F = R.flank, gmin = R.gmin;
+    int64_t cnt[SUP_ANSWER_WORDS] = {0, 0, 0, 0, 0, 0, 0};
+    auto is_clip = [](uint32_t o) { return (o & 15u) == 4u || (o & 15u) == 5u; };
+    const int rc = bam_walk_records(b, "vapor_bam_support", tid, R.w3, R.w3 > R.w0 ? n_chunks : 0, chunks, [&](int64_t pos, const uint8_t* ops, int32_t n_ops) {
+        if (n_ops <= 0) return;
+        auto op = [&](int32_t t) { return (uint32_t)rd32(ops + 4 * (size_t)t); };
+        const uint32_t o0 = op(0), o1 = n_ops >= 2 ? op(1) : 15u, ol = op(n_ops - 1), op2 = n_ops >= 2 ? op(n_ops - 2) : 15u;
+        if (is_clip(o0) && (n_ops == 1 || (n_ops == 2 && is_clip(o1)))) return;     // all clips: no event, no base covered
+        const int64_t lead = is_clip(o0) ? (int64_t)(o0 >> 4) + (is_clip(o1) ? (int64_t)(o1 >> 4) : 0) : 0;
+        const int64_t trail = is_clip(ol) ? (int64_t)(ol >> 4) + (is_clip(op2) ? (int64_t)(op2 >> 4) : 0) : 0;
+        bool cg = false, blocked[2] = {false, false};
+        int64_t cur = pos;
+        for (int32_t t = 0; t < n_ops; ++t) {
+            const uint32_t o = op(t), code = o & 15u;
+            const int64_t n = o >> 4;
+            const bool gap = code == 2u || code == 3u, ins = code == 1u;
+            if (gap && (R.mask & SIG_GAP) && n >= R.nmin && n <= R.nmax) {
+                const int64_t d0 = cur - x[0], d1 = cur + n - x[1];
+                if (d0 >= -tol && d0 <= tol && d1 >= -tol && d1 <= tol) cg = true;
+            }
+            if (ins && (R.mask & SIG_INSOP) && n >= R.nmin && n <= R.nmax && cur >= x[0] - tol && cur <= x[1] + tol) cg = true;
+            if (n >= gmin)
+                for (int k = 0; k < 2; ++k)
+                    if ((gap && cur < x[k] + F && cur + n > x[k] - F) || (ins && cur >= x[k] - F && cur <= x[k] + F)) blocked[k] = true;
+            if (code == 0u || code == 2u || code == 3u || code == 7u || code == 8u) cur += n;
+        }
+        const int64_t q = cur;
+        cnt[0] += cg;
+        for (int k = 0; k < 2; ++k) {
+            const int64_t dp = pos - x[k], dq = q - x[k];
+            const bool clip = (((R.mask >> (2 * k)) & 1u) && lead >= R.min_clip && dp >= -tol && dp <= tol) ||
+                              (((R.mask >> (2 * k + 1)) & 1u) && trail >= R.min_clip && dq >= -tol && dq <= tol);
+            const bool span = pos <= x[k] - F && q >= x[k] + F && !blocked[k];
+            cnt[1 + k] += clip && !cg;
+            cnt[3 + k] += (R.mask & (k ? SUP_REF1 : SUP_REF0)) && span && !cg && !clip;
+            cnt[5 + k] += pos <= x[k] && x[k] < q;
+        }
+    });
+    for (int k = 0; k < SUP_ANSWER_WORDS; ++k) out[k] = 0;
+    if (rc != VAPOR_OK) return rc;
+    for (int k = 0; k < SUP_ANSWER_WORDS; ++k) out[k] = cnt[k];
+    return VAPOR_OK;
+}
+
+extern "C" int vapor_bam_support(vapor_bam* b, int32_t tid, const int64_t* fields, int32_t n_chunks, const uint64_t* chunks, int64_t* out)
+{
+    try {
+        return bam_support_impl(b, tid, fields, n_chunks, chunks, out);
+    } catch (const std::bad_alloc&) {
+        return bfail(VAPOR_E_NOMEM, "vapor_bam_support: out of memory");
+    } catch (const std::exception& e) {
+        return bfail(VAPOR_E_ARG, std::string("vapor_bam_support: ") + e.what());
+    }
+}
+
 // Split reads joined through their SA tags, one link region (`--links`; vapor_amd/links.py answer is the rule,
 // bam_link_kernel the device's form): bam_walk_records to w3, and per passing record the clip event the region asks for - read as
 // bam_signature_impl reads it - within tol of x; of such a clip record the entries of its SA value (vapor_sa.h), an entry below
@@ -1398,4 +1469,11 @@ extern "C" __attribute__((weak)) int vapor_bam_links_device(vapor_ctx*, vapor_ba
                                                             const int32_t*, const uint64_t*, int64_t*, int32_t*)
 {
     return bfail(VAPOR_E_ARG, "vapor_bam_links_device: this build has no device reader");
+}
+
+// ... and the support on the device (vapor_bam_support_device: bam_support_kernel; the host reader is vapor_bam_support).
+extern "C" __attribute__((weak)) int vapor_bam_support_device(vapor_ctx*, vapor_bam*, int32_t, const int32_t*, const int64_t*, const int32_t*,
+                                                              const uint64_t*, int64_t*, int32_t*)
+{
+    return bfail(VAPOR_E_ARG, "vapor_bam_support_device: this build has no device reader");
 }

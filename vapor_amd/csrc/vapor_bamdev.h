@@ -1720,6 +1720,130 @@ __global__ __launch_bounds__(64) void bam_link_kernel(const uint8_t* __restrict_
     }
 }
 
+// Alt and ref alignments per region (`--support`; vapor_bam.cpp bam_support_impl is the host's statement,
+// vapor_amd/support.py answer the rule): one wavefront a region, bam_signature_kernel's record walk with its checks, statuses,
+// filter test, tiles of 64 operations and `prev63` carry.  The question is per record, not per event: each lane tests its own
+// operation for "a GAP or INSOP that 4.20 counts", "blocks target 0" and "blocks target 1", __any makes the three answers
+// wave-uniform and they are OR-ed over the record's tiles.  Behind the last tile the reference end, the two clips and the three
+// flags are uniform, so the record's class and its coverage are a few uniform comparisons, and the seven counts are uniform
+// registers: no LDS, no atomics, no reduction.  Lane 0 stores them.
+__global__ __launch_bounds__(64) void bam_support_kernel(const uint8_t* __restrict__ arena, const SupRegion* __restrict__ regs,
+                                                        const BamSpan* __restrict__ spans, const int32_t* __restrict__ blk_status, int n_regs,
+                                                        uint32_t* __restrict__ ans, int32_t* __restrict__ reg_status)
+{
+    const int g = (int)blockIdx.x;
+    if (g >= n_regs) return;
+    const uint32_t lane = threadIdx.x;
+    const SupRegion R = regs[g];
+    const long long w3 = R.w3, x0 = R.x0, x1 = R.x1;
+    const long long tol = R.tol, nmin = R.nmin, nmax = R.nmax, min_clip = R.min_clip;
+    const long long F = R.flank, gmin = R.gmin;
+    const uint32_t mask = R.mask;
+    const uint32_t flt_excl = R.filter & 0xFFFFu, flt_mapq = (R.filter >> 16) & 0xFFu;
+    uint32_t n_cg = 0, n_l = 0, n_r = 0, n_ref0 = 0, n_ref1 = 0, n_cov0 = 0, n_cov1 = 0;
+    int st = REG_OK;
+    const int span_n = w3 > R.w0 ? R.span_n : 0;            // (an empty window has no records, whatever chunks came with it)
+    for (int s = 0; s < span_n && st == REG_OK; ++s) {
+        const BamSpan SP = spans[R.span_first + s];
+        int bad = 0;
+        for (uint32_t i = lane; i < SP.blk_n; i += 64) bad |= blk_status[SP.blk_first + i] != 0;
+        if (__any(bad)) { st = REG_BLOCK; break; }
+        uint32_t pos_u = SP.u_begin;
+        // (a record is 36 bytes at least: pos_u grows every turn and the loop ends at u_end)
+        while (pos_u < SP.u_end) {
+            if ((unsigned long long)pos_u + 36ull > SP.u_limit) { st = REG_BEYOND; break; }
+            uint32_t w = 0;
+            if (lane < 6) w = rd32u(arena + pos_u + 4u * lane);
+            const int32_t bs = (int32_t)__shfl(w, 0), ref_id = (int32_t)__shfl(w, 1), pos = (int32_t)__shfl(w, 2);
+            const uint32_t wd3 = __shfl(w, 3), wd4 = __shfl(w, 4);
+            const int32_t l_seq = (int32_t)__shfl(w, 5);
+            if (bs < 32 || bs > (1 << 29)) { st = REG_MALFORMED; break; }
+            if ((unsigned long long)pos_u + 4ull + (unsigned long long)bs > SP.u_limit) { st = REG_BEYOND; break; }
+            const uint32_t r = pos_u + 4u;
+            pos_u += 4u + (uint32_t)bs;
+            const int l_name = (int)(wd3 & 0xFFu), n_cig = (int)(wd4 & 0xFFFFu);
+            if (l_seq < 0 || 32ll + l_name + 4ll * n_cig + ((long long)l_seq + 1) / 2 + (long long)l_seq > (long long)bs) { st = REG_MALFORMED; break; }
+            if (ref_id != R.tid || (long long)pos >= w3) {
+                if (ref_id > R.tid || (ref_id == R.tid && (long long)pos >= w3)) break;
+                continue;
+            }
+            // the read filter, DEPTH_EXCLUDE among its flags: both fields came with the record's header
+            if (((wd3 >> 8) & 0xFFu) < flt_mapq || ((wd4 >> 16) & flt_excl)) continue;
+            const uint32_t cig = r + 32u + (uint32_t)l_name;
+            uint32_t ops = cig;
+            int32_t n_ops = n_cig;
+            if (n_cig == 2) {
+                const uint32_t o0 = rd32u(arena + cig), o1 = rd32u(arena + cig + 4);
+                if ((o0 & 15u) == 4u && (int32_t)(o0 >> 4) == l_seq && (o1 & 15u) == 3u) {
+                    int32_t cnt = 0;
+                    const uint32_t cg = find_cg_dev(arena, cig + 8u + (uint32_t)((l_seq + 1) / 2) + (uint32_t)l_seq, r + (uint32_t)bs, &cnt);
+                    if (cg) { ops = cg; n_ops = cnt; }
+                }
+            }
+            if (n_ops <= 0) continue;                       // no CIGAR: nothing, and no error
+            long long cur = (long long)pos;                 // the reference cursor where the tile starts, 0-based
+            long long lead = 0, trail = 0;                  // the clipped bases at the record's two ends
+            uint32_t prev63 = 15u;                          // operation t0 - 1, for a trailing clip that starts on the tile before
+            bool cg = false, blk0 = false, blk1 = false;    // the record's three flags, wave-uniform, OR-ed over its tiles
+            for (int32_t t0 = 0; t0 < n_ops; t0 += 64) {
+                const int32_t t = t0 + (int32_t)lane;
+                const uint32_t o = t < n_ops ? rd32u(arena + ops + 4u * (uint32_t)t) : 15u;
+                const uint32_t code = o & 15u;
+                const long long n = (long long)(o >> 4);
+                const long long adv = (code == 0u || code == 2u || code == 3u || code == 7u || code == 8u) ? n : 0;
+                const long long A = wave_scan64(adv, lane);
+                const long long a = cur + A - adv;          // where this lane's operation starts
+                const bool gap = code == 2u || code == 3u, ins = code == 1u;
+                bool my_cg = false;
+                if (gap && (mask & SIG_GAP) && n >= nmin && n <= nmax) {
+                    const long long d0 = a - x0, d1 = a + n - x1;
+                    my_cg = d0 >= -tol && d0 <= tol && d1 >= -tol && d1 <= tol;
+                }
+                if (ins && (mask & SIG_INSOP) && n >= nmin && n <= nmax && a >= x0 - tol && a <= x1 + tol) my_cg = true;
+                const bool big = n >= gmin;
+                const bool my_b0 = big && ((gap && a < x0 + F && a + n > x0 - F) || (ins && a >= x0 - F && a <= x0 + F));
+                const bool my_b1 = big && ((gap && a < x1 + F && a + n > x1 - F) || (ins && a >= x1 - F && a <= x1 + F));
+                cg = cg || __any(my_cg);
+                blk0 = blk0 || __any(my_b0);
+                blk1 = blk1 || __any(my_b1);
+                if (t0 == 0) {
+                    const uint32_t o0 = __shfl(o, 0), o1 = __shfl(o, 1);
+                    if (sig_is_clip(o0)) lead = (long long)(o0 >> 4) + ((n_ops >= 2 && sig_is_clip(o1)) ? (long long)(o1 >> 4) : 0);
+                    // (a record of at most two operations that are all clips has neither event)
+                    if (sig_is_clip(o0) && (n_ops == 1 || (n_ops == 2 && sig_is_clip(o1)))) lead = -1;
+                }
+                if (t0 + 64 >= n_ops) {
+                    const int32_t l = n_ops - 1 - t0;       // the lane of the last operation, 0..63
+                    const uint32_t ol = __shfl(o, l), op = l > 0 ? __shfl(o, l - 1) : prev63;
+                    if (sig_is_clip(ol)) trail = (long long)(ol >> 4) + ((n_ops >= 2 && sig_is_clip(op)) ? (long long)(op >> 4) : 0);
+                }
+                prev63 = __shfl(o, 63);
+                cur += __shfl(A, 63);
+            }
+            if (lead < 0) continue;                         // (it covers no base either: nothing of the rule holds for it)
+            // the record: [pos, q) on the reference, every value below is the same on all lanes
+            const long long p = (long long)pos, q = cur;
+            const bool lc = lead >= min_clip, tc = trail >= min_clip;
+            const long long dp0 = p - x0, dq0 = q - x0, dp1 = p - x1, dq1 = q - x1;
+            const bool clip0 = ((mask & SIG_LCLIP0) && lc && dp0 >= -tol && dp0 <= tol) || ((mask & SIG_RCLIP0) && tc && dq0 >= -tol && dq0 <= tol);
+            const bool clip1 = ((mask & SIG_LCLIP1) && lc && dp1 >= -tol && dp1 <= tol) || ((mask & SIG_RCLIP1) && tc && dq1 >= -tol && dq1 <= tol);
+            const bool span0 = p <= x0 - F && q >= x0 + F && !blk0, span1 = p <= x1 - F && q >= x1 + F && !blk1;
+            n_cg += cg ? 1u : 0u;
+            n_l += (clip0 && !cg) ? 1u : 0u;
+            n_r += (clip1 && !cg) ? 1u : 0u;
+            n_ref0 += ((mask & SUP_REF0) && span0 && !cg && !clip0) ? 1u : 0u;
+            n_ref1 += ((mask & SUP_REF1) && span1 && !cg && !clip1) ? 1u : 0u;
+            n_cov0 += (p <= x0 && x0 < q) ? 1u : 0u;
+            n_cov1 += (p <= x1 && x1 < q) ? 1u : 0u;
+        }
+    }
+    if (lane == 0) {
+        uint32_t* o = ans + (size_t)SUP_ANSWER_WORDS * (size_t)g;
+        o[0] = n_cg; o[1] = n_l; o[2] = n_r; o[3] = n_ref0; o[4] = n_ref1; o[5] = n_cov0; o[6] = n_cov1;
+        reg_status[g] = st;
+    }
+}
+
 // One record of a molecule per region (`--dedup-qname`, DESIGN.md 4.18 rule W; vapor_names.h holds the arithmetic, vapor_bam.cpp
 // bam_chop_impl the host's statement): one wavefront a region, right behind the chop kernel on its stream and before
 // bam_haplotag_kernel / bam_select_kernel, launched only for a handle with the option.  BamKept has no record offset, so the

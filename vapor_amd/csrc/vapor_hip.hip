@@ -1310,6 +1310,53 @@ extern "C" int vapor_bam_links_device(vapor_ctx* ctx, vapor_bam* bam, int32_t n_
     });
 }
 
+// Alt and ref alignments of many regions of an open BAM file (`--support`; vapor_readplan.h SupCall):
+// vapor_bam_signature_device's steps with another plan and another kernel - bam_support_kernel, one wavefront a region, and one
+// copy back.  Nothing stays on the device.
+extern "C" int vapor_bam_support_device(vapor_ctx* ctx, vapor_bam* bam, int32_t n_regions, const int32_t* tid, const int64_t* regions,
+                                        const int32_t* chunk_first, const uint64_t* chunks, int64_t* out, int32_t* status)
+{
+    using namespace vapor_bamdev;
+    using namespace vapor_readplan;
+    if (!ctx || !bam) return fail(VAPOR_E_ARG, "vapor_bam_support_device: bad argument");
+    SupCall call;
+    call.n_regions = n_regions; call.tid = tid; call.regions = regions; call.chunk_first = chunk_first; call.chunks = chunks;
+    if (const Refusal r = check_args(call, out, status)) return fail(r.code, r.msg);
+    const int fd = vapor_bam_fileno(bam);
+    if (fd < 0) return fail(VAPOR_E_ARG, "vapor_bam_support_device: the file is not open");
+    call.filter_word = depth_filter_word(vapor_bam_filter_word(bam));
+    HIPCHK(hipSetDevice(ctx->device));
+    return guarded("vapor_bam_support_device", [&]() -> int {
+        SpanPlan plan;
+        if (const Refusal r = plan_spans(call, status, plan)) return fail(r.code, r.msg);
+        CallScope sc(ctx, ctx->stream);
+        InflateStage stage(sc);
+        Block<> d_arena(sc);
+        HIPCHK(stage.begin(plan.stage_bytes));
+        read_and_scan(stage, fd, bam, plan.spans);
+        SupLayout L;
+        if (const Refusal r = layout(call, plan, status, L)) return fail(r.code, r.msg);
+        const SupMeta& M = L.meta;
+        const size_t n_blks = L.blks.size();
+        if (const int rc = stage.alloc(M.bytes, M.bytes)) return rc;
+        HIPCHK(d_arena.ensure(L.arena + 64));
+        uint8_t *const h_meta = stage.h_meta, *const d_meta = stage.d_meta;
+        L.fill(h_meta);
+        const hipStream_t st = sc.st = bam_stream_of(ctx);
+        if (const int rc = stage.run(n_blks, M.in_bytes, M.blks.in(d_meta), M.blk_status.in(d_meta), d_arena, ctx->bam_ev)) return rc;
+        if (n_regions) {
+            hipLaunchKernelGGL(bam_support_kernel, dim3((unsigned)n_regions), dim3(64), 0, st, d_arena, M.regs.in(d_meta), M.spans.in(d_meta), M.blk_status.in(d_meta),
+                               (int)n_regions, M.ans.in(d_meta), M.reg_status.in(d_meta));
+            HIPCHK(hipGetLastError());
+        }
+        HIPCHK(hipMemcpyAsync(M.back(h_meta), M.back(d_meta), M.back_bytes(), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        sc.settled();
+        collect(call, M, h_meta, out, status);
+        return VAPOR_OK;
+    });
+}
+
 // what the context's last vapor_bam_chop_device did: regions, blocks, compressed bytes sent, inflated bytes, the inflate kernel's
 // duration between two events on its stream (ms), the whole call on the host's clock (ms)
 extern "C" int vapor_bam_last_stats(vapor_ctx* ctx, double* out, int32_t n)

@@ -732,6 +732,130 @@ inline void collect(const LinkCall& c, const LinkMeta& M, const uint8_t* h_meta,
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
+// vapor_bam_support_device (`--support`)
+// ------------------------------------------------------------------------------------------------------------------------------
+constexpr int SUP_FIELDS = 11;             // a region as the caller gives it: the nine SIG_FIELDS, then flank and gmin
+struct SupCall {
+    int32_t n_regions = 0;
+    const int32_t* tid = nullptr;
+    const int64_t* regions = nullptr;      // SUP_FIELDS a region
+    const int32_t* chunk_first = nullptr;
+    const uint64_t* chunks = nullptr;
+    uint32_t filter_word = 0;              // the handle's read filter with DEPTH_EXCLUDE among its flags (depth_filter_word)
+};
+
+inline Refusal check_args(const SupCall& c, const int64_t* out, const int32_t* status)
+{
+    if (c.n_regions < 0 || (c.n_regions && (!c.tid || !c.regions || !c.chunk_first || !out || !status)))
+        return {VAPOR_E_ARG, "vapor_bam_support_device: bad argument"};
+    return {};
+}
+
+// Whether a region's own fields are a question the readers answer: sig_region_ok of its first nine, a flank of 1..65535 and a
+// blocking length of 1 at least.  One statement for the device's plan and the host reader (vapor_bam.cpp bam_support_impl).
+inline bool sup_region_ok(int32_t tid, const int64_t* f)
+{
+    return sig_region_ok(tid, f) && f[9] >= 1 && f[9] <= SUP_FLANK_MAX && f[10] >= 1;
+}
+
+// The caller's fields as the kernel and the host reader take them: sig_region_set's clamps for the first nine (the mask keeps
+// its eight bits), and the blocking length clamped to 2^28 (no operation is that long: the clamped bound admits the same - none).
+inline void sup_region_set(SupRegion& R, int32_t tid, const int64_t* f, uint32_t filter_word)
+{
+    const int64_t far = (int64_t)1 << 40;
+    R.w0 = f[0]; R.w3 = f[1];
+    R.x0 = std::min(std::max(f[2], -far), far); R.x1 = std::min(std::max(f[3], -far), far);
+    R.tol = (int32_t)f[4];
+    R.min_clip = (int32_t)std::min<int64_t>(std::max<int64_t>(f[5], 1), (int64_t)1 << 30);
+    R.nmin = (int32_t)std::min<int64_t>(std::max<int64_t>(f[6], -1), (int64_t)1 << 28);
+    R.nmax = (int32_t)std::min<int64_t>(std::max<int64_t>(f[7], -1), (int64_t)1 << 28);
+    R.mask = (uint32_t)f[8] & 255u;
+    R.flank = (int32_t)f[9];
+    R.gmin = (int32_t)std::min<int64_t>(f[10], (int64_t)1 << 28);
+    R.tid = tid; R.filter = filter_word; R.pad = 0;
+}
+
+// The region rules: sup_region_ok - else REG_MALFORMED and the host route's to refuse.  The spans and the staging block as
+// plan_spans makes them.
+inline Refusal plan_spans(const SupCall& c, int32_t* status, SpanPlan& p)
+{
+    return plan_spans_of(c.n_regions, c.chunk_first, c.chunks, status, p, "vapor_bam_support_device: more than 1.5 GB of blocks in one call (use smaller batches)",
+                         [&](int32_t g, int*) { return sup_region_ok(c.tid[g], c.regions + SUP_FIELDS * (size_t)g); });
+}
+
+// Where each table of a support call lies in its metadata block: blocks, spans and regions go in; block status, the
+// SUP_ANSWER_WORDS words a region and the region status come back.
+struct SupMeta {
+    Table<BgzfBlk> blks;
+    Table<BamSpan> spans;
+    Table<SupRegion> regs;
+    Table<int32_t> blk_status;
+    Table<uint32_t> ans;                   // SUP_ANSWER_WORDS a region: alt_cg, alt_l, alt_r, ref_0, ref_1, cov_0, cov_1
+    Table<int32_t> reg_status;
+    size_t in_bytes = 0, bytes = 0;
+
+    SupMeta() = default;
+    SupMeta(int32_t n_regions, size_t n_blks, size_t n_spans)
+    {
+        const size_t nr = (size_t)std::max(n_regions, 1);
+        Carve m;
+        m.take(blks, std::max<size_t>(n_blks, 1));
+        m.take(spans, std::max<size_t>(n_spans, 1));
+        m.take(regs, nr);
+        in_bytes = m.off;
+        m.take(blk_status, std::max<size_t>(n_blks, 1));
+        m.take(ans, (size_t)SUP_ANSWER_WORDS * nr);
+        m.take(reg_status, nr);
+        bytes = m.off;
+    }
+    size_t back_bytes() const { return bytes - blk_status.off; }       // the host's block is the device's: [blk_status.off, bytes) comes back
+    template <typename B> B* back(B* block) const { return block + blk_status.off; }
+};
+
+struct SupLayout {
+    std::vector<BgzfBlk> blks;
+    std::vector<BamSpan> spans;
+    std::vector<SupRegion> regs;
+    size_t arena = 0;
+    SupMeta meta;
+    void fill(uint8_t* h_meta) const
+    {
+        if (!blks.empty()) memcpy(meta.blks.in(h_meta), blks.data(), sizeof(BgzfBlk) * blks.size());
+        if (!spans.empty()) memcpy(meta.spans.in(h_meta), spans.data(), sizeof(BamSpan) * spans.size());
+        memcpy(meta.regs.in(h_meta), regs.data(), sizeof(SupRegion) * regs.size());
+    }
+};
+
+inline Refusal layout(const SupCall& c, const SpanPlan& p, int32_t* status, SupLayout& L)
+{
+    if (const Refusal r = layout_of(c.n_regions, p, status, L.blks, L.spans, L.regs, &L.arena,
+                                    "vapor_bam_support_device: more than 2 GB of block data in one call (use smaller batches)", [&](SupRegion& R, int32_t g) {
+            const int64_t* f = c.regions + SUP_FIELDS * (size_t)g;
+            // (a region the plan refused keeps a record that asks nothing: no kernel reads it, its span_n is 0)
+            if (status[g]) { R = SupRegion(); return; }
+            sup_region_set(R, c.tid[g], f, c.filter_word);
+        }))
+        return r;
+    L.meta = SupMeta(c.n_regions, L.blks.size(), L.spans.size());
+    return {};
+}
+
+// The read-back block into the caller's arrays, as collect(SigCall) does it: seven counts.
+inline void collect(const SupCall& c, const SupMeta& M, const uint8_t* h_meta, int64_t* out, int32_t* status)
+{
+    const uint32_t* da = M.ans.in(h_meta);
+    const int32_t* rst = M.reg_status.in(h_meta);
+    for (int32_t g = 0; g < c.n_regions; ++g) {
+        int64_t* o = out + (size_t)SUP_ANSWER_WORDS * (size_t)g;
+        for (int k = 0; k < SUP_ANSWER_WORDS; ++k) o[k] = 0;
+        if (status[g]) continue;
+        if (rst[g] != REG_OK) { status[g] = rst[g]; continue; }
+        const uint32_t* a = da + (size_t)SUP_ANSWER_WORDS * (size_t)g;
+        for (int k = 0; k < SUP_ANSWER_WORDS; ++k) o[k] = (int64_t)a[k];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
 // vapor_fasta_windows_device
 // ------------------------------------------------------------------------------------------------------------------------------
 constexpr uint64_t ARENA_CAP = (uint64_t)1 << 30;       // inflated bytes of a call; a stretch that would pass it leaves its windows to the host

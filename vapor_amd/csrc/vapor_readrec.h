@@ -49,6 +49,16 @@ struct LinkRegion {       // `--links`: the walk window [w0, w3
     uint32_t name_off, name_len;   // the partner contig's name in the call's name blob
     int32_t pad;
 };
+struct SupRegion {        // `--support`: a signature region, the flank a reference alignment must reach on either side of a target, the shortest D, N or I that blocks it
+    int64_t w0, w3, x0, x1;
+    int32_t nmin, nmax;   // as SigRegion's
+    int32_t tid, span_first, span_n;
+    uint32_t filter;      // the read filter as BamRegion::pad carries it, 0x704 already among the excluded flags
+    int32_t tol, min_clip;    // 0..255; 1..2^30
+    uint32_t mask;        // SIG_* bits, SUP_REF0, SUP_REF1
+    int32_t flank, gmin;  // 1..65535; 1..2^28
+    int32_t pad;
+};
 struct BamKept {          // a read the reference keeps: its packed bases at arena + sq_off, from base q0 on, miss_bp
     uint32_t sq_off;
     int32_t q0, miss, l_seq;
@@ -62,6 +72,10 @@ constexpr int SIG_TOL_MAX = 255, SIG_HIST_WORDS = 2 * (2 * SIG_TOL_MAX + 1), SIG
 // then offset and count of the mode
 constexpr uint32_t LINK_EV = 1u, LINK_PEND = 2u, LINK_REL = 4u;
 constexpr int LINK_HIST_WORDS = 2 * SIG_TOL_MAX + 1, LINK_ANSWER_WORDS = 5;
+// `--support`: reference support is asked at x0 / at x1 (bits 6 and 7 of a region's mask, behind the six SIG_* bits), the widest
+// flank, and the words of a region's answer: alt_cg, alt_l, alt_r, ref_0, ref_1, cov_0, cov_1
+constexpr uint32_t SUP_REF0 = 64u, SUP_REF1 = 128u;
+constexpr int SUP_FLANK_MAX = 65535, SUP_ANSWER_WORDS = 7;
 constexpr int KEPT_CAP = 256;     // kept reads a region's slot holds (minimize_pacbio_read_list keeps 20 of them)
 // status of a region: 0, or why the host route must do it
 constexpr int REG_OK = 0, REG_BEYOND = 1, REG_MALFORMED = 2, REG_NO_CIGAR = 3, REG_KEPT_FULL = 4, REG_BLOCK = 5, REG_NEG_Q0 = 6, REG_NO_SEQ = 7;
@@ -100,7 +114,7 @@ struct BamSiteRange {     // a region's sites (in position order) and its table 
 };
 constexpr int PHASE_SETS_CAP = 64;     // phase sets a wavefront tallies: lane p holds the two counts of phase set p
 
-static_assert(sizeof(BgzfBlk) == 24 && sizeof(BamSpan) == 24 && sizeof(BamRegion) == 40 && sizeof(DepthRegion) == 48 && sizeof(SigRegion) == 72 && sizeof(LinkRegion) == 72 && sizeof(BamKept) == 16 && sizeof(BamTag) == 16 &&
+static_assert(sizeof(BgzfBlk) == 24 && sizeof(BamSpan) == 24 && sizeof(BamRegion) == 40 && sizeof(DepthRegion) == 48 && sizeof(SigRegion) == 72 && sizeof(LinkRegion) == 72 && sizeof(SupRegion) == 80 && sizeof(BamKept) == 16 && sizeof(BamTag) == 16 &&
               sizeof(BamPick) == 16 && sizeof(BamPhase) == 16 && sizeof(BamOps) == 16 && sizeof(BamSite) == 8 && sizeof(BamSiteRange) == 16,
               "the kernels index arrays of these, and the metadata block of a call is carved by their sizes");
 

@@ -544,6 +544,27 @@ class Engine:
                    status.ctypes.data_as(vp)))
         return out[:5 * n].reshape(n, 5), status[:n]
 
+    def bam_support_device(self, native_bam, tids, regions, chunk_first, chunks):
+        """vapor_bam_support_device (`--support`): alt and ref alignments of many support regions of an open BAM
+        file on the device.  regions: (n, 11) int64 - signature.FIELDS, then flank and gmin (support.FIELDS); chunk_first /
+        chunks as in bam_chop_device.  Returns (out, status): out (n, 7) int64 - alt_cg, alt_l, alt_r, ref_0, ref_1, cov_0,
+        cov_1 - and status per region: 0, or the code of a region that is the host route's (its words are 0 then).  Nothing
+        stays on the device.  NotImplementedError where the library has no such entry."""
+        fn = Engine._wide_entry("vapor_bam_support_device", "device support reader")
+        n = len(tids)
+        tids = np.ascontiguousarray(tids, dtype=np.int32)
+        regions = np.ascontiguousarray(regions, dtype=np.int64).reshape(-1)
+        chunk_first = np.ascontiguousarray(chunk_first, dtype=np.int32)
+        chunks = np.ascontiguousarray(chunks, dtype=np.uint64).reshape(-1)
+        if len(regions) != 11 * n or len(chunk_first) != n + 1 or len(chunks) != 2 * int(chunk_first[-1]):
+            raise ValueError("regions / chunk_first / chunks do not describe %d regions" % n)
+        out = np.zeros(7 * max(n, 1), dtype=np.int64)
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        vp = ctypes.c_void_p
+        L.check(fn(self._ctx, native_bam, n, tids.ctypes.data_as(vp), regions.ctypes.data_as(vp), chunk_first.ctypes.data_as(vp),
+                   chunks.ctypes.data_as(vp) if len(chunks) else None, out.ctypes.data_as(vp), status.ctypes.data_as(vp)))
+        return out[:7 * n].reshape(n, 7), status[:n]
+
     def bam_last_stats(self) -> dict:
         """What this engine's last bam_chop_device did (vapor_bam_last_stats)."""
         out = np.zeros(7, dtype=np.float64)

@@ -91,6 +91,20 @@ class SamtoolsCLI:
             out.append(signature.words(signature.answer(recs, rg)))
         return out
 
+    def support_many(self, engine, bam: str, chroms, regions):
+        """The seven words per support region (`--support`; chroms[g], regions[g] = support.FIELDS):
+        support.answer over POS and CIGAR of the alignment lines of `view`, filtered where they are read (_sam_fields) with
+        support.EXCLUDE among the excluded flags."""
+        from . import support
+        out = []
+        for chrom, rg in zip(chroms, regions):
+            if not rg[1] > rg[0]:
+                out.append([0] * 7)
+                continue
+            recs = [(int(f[3]), support.parse_cigar(f[5])) for f in _sam_fields(self, bam, chrom, int(rg[0]) + 1, int(rg[1]), support.EXCLUDE)]
+            out.append(support.answer(recs, rg))
+        return out
+
     def links_many(self, engine, bam: str, chroms, regions, partners):
         """The five words per link region (`--links`; chroms[g], regions[g] = links.FIELDS, partners[g] the
         partner contig's name): links.answer over POS, CIGAR, FLAG and the SA field of the alignment lines of `view`, filtered
@@ -696,8 +710,22 @@ class InProcessBam(SamtoolsHybrid):
         return self._regions_many(engine, bam, chroms, rows, len(links.FIELDS) + 2, 0, 1, [0] * 5, ("vapor_bam_links", "vapor_bam_links_device"),
                                   "bam_links_device", "links_native", python, names=names)
 
+    def support_many(self, engine, bam: str, chroms, regions):
+        """The seven words per support region (`--support`; chroms[g], regions[g] = support.FIELDS) of a BAM
+        file: alt_cg, alt_l, alt_r, ref_0, ref_1, cov_0, cov_1.  The routes are depth_many's: the device in groups
+        (vapor_bam_support_device: bam_support_kernel, one wavefront a region), a region it hands back and every region with
+        VAPOR_BAM_DEVICE=0 to the native host reader (vapor_bam_support), and the Python statement - support.answer over
+        fetch_raw with support.EXCLUDE added to the excluded flags - for a library without the entries or VAPOR_BAM_NATIVE=0."""
+        from . import support
+
+        def python(b, chrom, rg):
+            recs = [(r[1], r[2]) for r in b.fetch_raw(chrom, int(rg[0]) + 1, int(rg[1]), exclude_more=support.EXCLUDE)]
+            return support.answer(recs, rg)
+        return self._regions_many(engine, bam, chroms, regions, len(support.FIELDS), 0, 1, [0] * 7,
+                                  ("vapor_bam_support", "vapor_bam_support_device"), "bam_support_device", "support_native", python)
+
     def _regions_many(self, engine, bam, chroms, rows, width, lo, hi, zero, entries, device, native, python, names=None):
-        """The routes of depth_many, signature_many and links_many.  rows[g]: the `width` integers of region g, its walk window
+        """The routes of depth_many, signature_many, links_many and support_many.  rows[g]: the `width` integers of region g, its walk window
         [rows[g][lo], rows[g][hi]); zero: the answer of a region without records (an unknown contig, an empty window);
         entries: the library's host and device entry; device: the Engine's method, native: the BamFile's, python(b, chrom, row)
         the Python statement.  names (links_many): a byte blob the rows point into, handed to the device and the native entry
@@ -1193,6 +1221,30 @@ class MemorySamtools:
                     sa = (r.tags or {}).get("SA")
                     rows.append((r.pos, ops, r.flag, sa.encode("latin-1") if isinstance(sa, str) else None))
             out.append(links.words(links.answer(rows, rg, pc, q)))
+        return out
+
+    def support_many(self, engine, bam: str, chroms, regions):
+        """The seven words per support region (`--support`) from the world's records that pass the read filter
+        with support.EXCLUDE among its flags: support.answer over (POS, operations) of the records that start before w3, every
+        CIGAR text parsed once per record list."""
+        from . import support
+        from .bamio import record_passes
+        q, f = self.read_filter
+        f |= support.EXCLUDE
+        cache = self.__dict__.setdefault("_depth_cache", {})
+        out = []
+        for chrom, rg in zip(chroms, regions):
+            recs = self.world.reads.get(chrom, ())
+            got = cache.get(id(recs))
+            if got is None or got[0] is not recs or got[1] != len(recs):
+                got = (recs, len(recs), [support.parse_cigar(r.cigar) for r in recs])
+                if getattr(self.world, "cache_ok", True):
+                    if len(cache) > 200000:
+                        cache.clear()
+                    cache[id(recs)] = got
+            w0, w3 = int(rg[0]), int(rg[1])
+            out.append(support.answer([(r.pos, ops) for r, ops in zip(recs, got[2])
+                                       if w0 < w3 and r.pos - 1 < w3 and record_passes(r.mapq, r.flag, q, f)], rg))
         return out
 
     def fai_lines(self, ref: str) -> Iterable[str]:

@@ -771,6 +771,10 @@ SIGNATURE_SPECS = (("DEL", 600, "hom"), ("DEL", 1500, "het"), ("DEL", 6000, "het
                    ("INS", 3000, "hom"))
 
 
+SUPPORT_SPECS = tuple((t, span, z) for t, span in (("DEL", 600), ("DEL", 12000), ("TANDUP", 300), ("TANDUP", 15000), ("INV", 700),
+                                                   ("INV", 11000), ("INS", 250), ("INS", 3000)) for z in ("het", "hom", "ref"))
+
+
 def make_signature_world(seed: int, specs: Sequence[Tuple[str, int, str]] = SIGNATURE_SPECS, layers: int = 4, read_len: int = 1000,
                          margin: int = 3000, short: int = 2000, guard: int = 100, jitter: Sequence[int] = (0,),
                          chrom_prefix: str = "s") -> SynthWorld:
@@ -792,6 +796,29 @@ def make_signature_world(seed: int, specs: Sequence[Tuple[str, int, str]] = SIGN
     the left), as alignments in a repeat do - so that the histograms have more than one bin.  With A = 1 ('het') or 2 ('hom')
     alt haplotypes every locus has A * layers reads at each junction, and its six columns are known in closed form:
       D / I carriers: L = R = 0, CG = A * layers;  split DEL, TANDUP, INS: L = R = A * layers, CG = 0;  INV: L = R = 2 * A * layers."""
+    return _tiled_world(seed, specs, layers, read_len, margin, short, guard, jitter, chrom_prefix, False)
+
+
+def make_support_world(seed: int, specs: Sequence[Tuple[str, int, str]] = SUPPORT_SPECS, layers: int = 4, read_len: int = 1000,
+                       margin: int = 3000, short: int = 2000, guard: int = 100, jitter: Sequence[int] = (0,),
+                       chrom_prefix: str = "u") -> SynthWorld:
+    """A world whose reference alignments mean something as well (`--support`): make_signature_world's tiling
+    with two changes.  The guard holds for every haplotype at the event's two reference breakpoints too: a cut nearer than
+    `guard` (51 at least: support.F) to base `margin` or `margin + L` of the reference, wherever a haplotype carries that base
+    with its neighbours, is left out - so every layer of such a haplotype has exactly one record that runs through the
+    breakpoint, with `guard` bases on either side.  And there is a third zygosity, 'ref': two reference haplotypes.  With A = 0
+    ('ref'), 1 ('het') or 2 ('hom') alt haplotypes the nine columns are known in closed form:
+      ALT = A * layers - for an INV twice that: either junction has a forward and a reverse-strand record of every alt read;
+      REFL = REFR = (2 - A) * layers for DEL, INS and INV, and for a TANDUP of at most `short` bases (its one record carries
+        the I); 2 * layers for a longer TANDUP - the duplicated allele runs through both outer breakpoints contiguously;
+      COVL = COVR = REF + the alt records that cover the breakpoint's base;  GT = 0/0, 0/1, 1/1 for A = 0, 1, 2.
+    (With a jitter other than 0 the alt records' ends move over the breakpoints' bases, and the COV columns with them.)"""
+    return _tiled_world(seed, specs, layers, read_len, margin, short, guard, jitter, chrom_prefix, True)
+
+
+def _tiled_world(seed, specs, layers, read_len, margin, short, guard, jitter, chrom_prefix, ref_guard) -> SynthWorld:
+    """make_signature_world (ref_guard False) and make_support_world (True: the guard at the reference breakpoints of every
+    haplotype, and the zygosity 'ref')."""
     rng = np.random.default_rng(seed)
     w = SynthWorld()
     for li, (t, span, zyg) in enumerate(specs):
@@ -815,7 +842,7 @@ def make_signature_world(seed: int, specs: Sequence[Tuple[str, int, str]] = SIGN
         else:
             raise ValueError(t)
         plain = [(0, n, "+")]
-        haps = [alt, alt] if zyg == "hom" else [plain, alt]
+        haps = [alt, alt] if zyg == "hom" else [plain, plain] if ref_guard and zyg == "ref" else [plain, alt]
         small = span <= short and t != "INV"
         recs = w.reads.setdefault(c, [])
         for h, segs in enumerate(haps):
@@ -833,6 +860,10 @@ def make_signature_world(seed: int, specs: Sequence[Tuple[str, int, str]] = SIGN
                 zones = [(joints[0] - guard - (span if t == "TANDUP" else 0), joints[-1] + guard + (span if t == "TANDUP" else 0))]
             else:
                 zones = [(j - guard, j + guard) for j in joints]
+            if ref_guard:
+                # (where the haplotype carries a reference breakpoint inside or at an end of a forward segment)
+                zones = zones + [(p0 + bp - sg[0] - guard, p0 + bp - sg[0] + guard) for p0, _p1, sg in table
+                                 if sg[0] is not None and sg[2] == "+" for bp in (s0, e0) if sg[0] <= bp <= sg[1]]
             for k in range(layers):
                 d = int(jitter[k % len(jitter)]) if segs is not plain else 0
                 cuts = sorted({0, m} | {x for x in range((k * read_len) // layers, m, read_len) if not any(lo < x < hi for lo, hi in zones)})
