@@ -1041,7 +1041,7 @@ static void check_depth()
         // the metadata block: the tables in order, on multiples of 64, without overlap; what goes in first, what comes back last
         const DepthMeta& M = L.meta;
         const size_t nr = (size_t)std::max(n, 1), nb = std::max<size_t>(n_blk, 1), ns = std::max<size_t>(n_sp, 1);
-        const size_t offs[6] = {M.blks.off, M.spans.off, M.regs.off, M.blk_status.off, M.cov.off, M.reg_status.off};
+        const size_t offs[6] = {M.blks.off, M.spans.off, M.regs.off, M.blk_status.off, M.ans.off, M.reg_status.off};
         const size_t sizes[6] = {24 * nb, 24 * ns, 48 * nr, 4 * nb, 24 * nr, 4 * nr};
         size_t at = 0;
         for (int t = 0; t < 6; ++t) { CHECK(offs[t] == at && at % 64 == 0, "table %d at %zu, not %zu", t, offs[t], at); at += up64(sizes[t]); }
@@ -1051,7 +1051,7 @@ static void check_depth()
         L.fill(h.data());
         CHECK(!memcmp(M.regs.in(h.data()), L.regs.data(), 48 * nr) && (!n_blk || !memcmp(M.blks.in(h.data()), L.blks.data(), 24 * n_blk)) &&
               (!n_sp || !memcmp(M.spans.in(h.data()), L.spans.data(), 24 * n_sp)), "fill");
-        uint64_t* dc = M.cov.in(h.data());
+        uint64_t* dc = M.ans.in(h.data());
         int32_t* rs = M.reg_status.in(h.data());
         for (size_t g = 0; g < nr; ++g) { for (int k = 0; k < 3; ++k) dc[3 * g + (size_t)k] = rng(); rs[g] = one_in(5) ? rnd(1, 5) : 0; }
         std::vector<int32_t> st2 = status;
@@ -1591,8 +1591,71 @@ static void check_support()
            n_calls, n_regions_seen, n_refused);
 }
 
+// ================================================================================================================================
+// The metadata blocks of the four evidence calls, pinned: one small call of each kind - three regions of which the second is
+// refused (tid -1), chunks 2 + 1 + 2 so that four spans are left, a made-up scan of 2 + 1 + 1 + 1 = 5 blocks - and the literal
+// in_bytes, bytes, back_bytes() and every table's offset.  The numbers were taken by running the four separate plans
+// (DepthMeta, SigMeta, LinkMeta, SupMeta as structs of their own) before they became one template: what the device and the
+// host agree on byte for byte must not move.  Nothing here draws from the seeded stream.
+// ================================================================================================================================
+template <typename Call, typename Layout>
+static void pin_layout(const char* what, Call& c, std::initializer_list<size_t> want, bool none = false)      // none: a links call without a blob - no region has a name, all are refused
+{
+    const int32_t tid[3] = {0, -1, 0}, chunk_first[4] = {0, 2, 3, 5};
+    uint64_t chunks[10];
+    for (uint64_t k = 0; k < 5; ++k) { chunks[2 * k] = (k << 20) << 16; chunks[2 * k + 1] = ((k << 20) + 3000) << 16 | 100; }
+    c.n_regions = 3; c.tid = tid; c.chunk_first = chunk_first; c.chunks = chunks;
+    int32_t status[3];
+    SpanPlan p;
+    CHECK(!plan_spans(c, status, p), "%s: the pinned call is refused", what);
+    CHECK(status[1] == REG_MALFORMED && p.spans.size() == (none ? 0u : 4u), "%s: %zu spans", what, p.spans.size());
+    for (size_t s = 0; s < p.spans.size(); ++s) {
+        HostSpan& sp = p.spans[s];
+        for (int k = 0; k < (s == 0 ? 2 : 1); ++k) sp.blks.push_back(Block{(size_t)k * 500, 6, 426, 7u, 1000u, (uint64_t)k * 1000});
+        sp.got = sp.want; sp.u_total = 1000 * sp.blks.size(); sp.u_begin = 10; sp.u_end = 900;
+    }
+    Layout L;
+    CHECK(!layout(c, p, status, L), "%s: the pinned layout is refused", what);
+    CHECK(L.blks.size() == (none ? 0u : 5u) && L.spans.size() == p.spans.size() && L.regs.size() == 3, "%s: blocks, spans, regions", what);
+    const auto& M = L.meta;
+    std::vector<size_t> got = {M.in_bytes, M.bytes, M.back_bytes(), M.blks.off, M.spans.off, M.regs.off};
+    if constexpr (std::is_same<Call, LinkCall>::value) got.push_back(M.names.off);
+    got.insert(got.end(), {M.blk_status.off, M.ans.off, M.reg_status.off});
+    std::string s;
+    for (size_t v : got) s += " " + std::to_string(v);
+    CHECK(got == std::vector<size_t>(want), "%s: in_bytes, bytes, back_bytes, offsets:%s", what, s.c_str());
+}
+
+static void check_pins()
+{
+    const int64_t bounds[12] = {0, 10, 20, 30, 0, 10, 20, 30, 0, 10, 20, 30};
+    int64_t sig[3 * SIG_FIELDS], link[3 * LINK_FIELDS], sup[3 * SUP_FIELDS];
+    for (int g = 0; g < 3; ++g) {
+        const int64_t f[SUP_FIELDS] = {0, 100, 40, 60, 5, 30, 1, 50, 63, 500, 50}, l[LINK_FIELDS] = {0, 100, 40, 60, 5, 30, 1, 0, 0, 0, 1};
+        std::copy(f, f + SIG_FIELDS, sig + g * SIG_FIELDS);
+        std::copy(f, f + SUP_FIELDS, sup + g * SUP_FIELDS);
+        std::copy(l, l + LINK_FIELDS, link + g * LINK_FIELDS);
+    }
+    DepthCall d; d.bounds = bounds;
+    pin_layout<DepthCall, DepthLayout>("depth", d, {448, 704, 256, 0, 128, 256, 448, 512, 640});
+    SigCall s; s.regions = sig;
+    pin_layout<SigCall, SigLayout>("signature", s, {512, 768, 256, 0, 128, 256, 512, 576, 704});
+    const std::vector<uint8_t> names(70, 'c');
+    LinkCall k; k.regions = link; k.names = names.data();
+    k.names_len = 0;
+    pin_layout<LinkCall, LinkLayout>("links, no blob", k, {448, 640, 192, 0, 64, 128, 384, 448, 512, 576}, true);
+    k.names_len = 1;
+    pin_layout<LinkCall, LinkLayout>("links, 1 byte", k, {576, 768, 192, 0, 128, 256, 512, 576, 640, 704});
+    k.names_len = 70;
+    pin_layout<LinkCall, LinkLayout>("links, 70 bytes", k, {640, 832, 192, 0, 128, 256, 512, 640, 704, 768});
+    SupCall u; u.regions = sup;
+    pin_layout<SupCall, SupLayout>("support", u, {512, 768, 256, 0, 128, 256, 512, 576, 704});
+    printf("evidence pins: the metadata blocks of six small calls lie where the four separate plans put them\n");
+}
+
 int main()
 {
+    check_pins();
     check_statuses();
     check_layout();
     check_limits();

@@ -675,9 +675,23 @@ extern "C" int vapor_bam_chop_haplotag(vapor_bam* b, int32_t tid, int64_t start,
     }
 }
 
-// The walk of the depth and the signature reader (`--depth`, `--signatures`): bam_chop_impl's walk over the chunks' records with
-// its checks, the handle's read filter with DEPTH_EXCLUDE among its flags, a CG:B,I array in place of its stand-in.  A record at
-// or behind `stop` ends a chunk.  rec(pos, ops, n_ops): a passing record of contig `tid`, its operations as the file holds them.
+// an entry of the evidence readers: its body, with what it throws worded under its name
+template <typename Body>
+static int bam_guarded(const char* who, Body body)
+{
+    try {
+        return body();
+    } catch (const std::bad_alloc&) {
+        return bfail(VAPOR_E_NOMEM, std::string(who) + ": out of memory");
+    } catch (const std::exception& e) {
+        return bfail(VAPOR_E_ARG, std::string(who) + ": " + e.what());
+    }
+}
+
+// The walk of the four evidence readers (`--depth`, `--signatures`, `--links`, `--support`; walk_records in vapor_bamdev.h is the
+// device's form): bam_chop_impl's walk over the chunks' records with its checks, the handle's read filter with DEPTH_EXCLUDE
+// among its flags, a CG:B,I array in place of its stand-in.  A record at or behind `stop` ends a chunk.  rec(pos, ops, n_ops): a
+// passing record of contig `tid`, its operations as the file holds them.
 template <typename PerRecord>
 static int bam_walk_records(vapor_bam* b, const char* who, int32_t tid, int64_t stop, int32_t n_chunks, const uint64_t* chunks, PerRecord rec)
 {
@@ -785,13 +799,7 @@ static int bam_depth_impl(vapor_bam* b, int32_t tid, const int64_t* bounds, int3
 
 extern "C" int vapor_bam_depth(vapor_bam* b, int32_t tid, const int64_t* bounds, int32_t n_chunks, const uint64_t* chunks, uint64_t* cov)
 {
-    try {
-        return bam_depth_impl(b, tid, bounds, n_chunks, chunks, cov);
-    } catch (const std::bad_alloc&) {
-        return bfail(VAPOR_E_NOMEM, "vapor_bam_depth: out of memory");
-    } catch (const std::exception& e) {
-        return bfail(VAPOR_E_ARG, std::string("vapor_bam_depth: ") + e.what());
-    }
+    return bam_guarded("vapor_bam_depth", [&] { return bam_depth_impl(b, tid, bounds, n_chunks, chunks, cov); });
 }
 
 // Split-read and CIGAR evidence of one signature region (`--signatures`; vapor_amd/signature.py answer is the
@@ -866,13 +874,7 @@ static int bam_signature_impl(vapor_bam* b, int32_t tid, const int64_t* fields, 
 
 extern "C" int vapor_bam_signature(vapor_bam* b, int32_t tid, const int64_t* fields, int32_t n_chunks, const uint64_t* chunks, int64_t* out)
 {
-    try {
-        return bam_signature_impl(b, tid, fields, n_chunks, chunks, out);
-    } catch (const std::bad_alloc&) {
-        return bfail(VAPOR_E_NOMEM, "vapor_bam_signature: out of memory");
-    } catch (const std::exception& e) {
-        return bfail(VAPOR_E_ARG, std::string("vapor_bam_signature: ") + e.what());
-    }
+    return bam_guarded("vapor_bam_signature", [&] { return bam_signature_impl(b, tid, fields, n_chunks, chunks, out); });
 }
 
 // Alt and ref alignments of one support region (`--support`; vapor_amd/support.py answer is the rule,
@@ -937,13 +939,7 @@ static int bam_support_impl(vapor_bam* b, int32_t tid, const int64_t* fields, in
 
 extern "C" int vapor_bam_support(vapor_bam* b, int32_t tid, const int64_t* fields, int32_t n_chunks, const uint64_t* chunks, int64_t* out)
 {
-    try {
-        return bam_support_impl(b, tid, fields, n_chunks, chunks, out);
-    } catch (const std::bad_alloc&) {
-        return bfail(VAPOR_E_NOMEM, "vapor_bam_support: out of memory");
-    } catch (const std::exception& e) {
-        return bfail(VAPOR_E_ARG, std::string("vapor_bam_support: ") + e.what());
-    }
+    return bam_guarded("vapor_bam_support", [&] { return bam_support_impl(b, tid, fields, n_chunks, chunks, out); });
 }
 
 // Split reads joined through their SA tags, one link region (`--links`; vapor_amd/links.py answer is the rule,
@@ -1035,13 +1031,7 @@ static int bam_links_impl(vapor_bam* b, int32_t tid, const int64_t* fields, cons
 extern "C" int vapor_bam_links(vapor_bam* b, int32_t tid, const int64_t* fields, const uint8_t* names, int64_t names_len, int32_t n_chunks,
                                const uint64_t* chunks, int64_t* out)
 {
-    try {
-        return bam_links_impl(b, tid, fields, names, names_len, n_chunks, chunks, out);
-    } catch (const std::bad_alloc&) {
-        return bfail(VAPOR_E_NOMEM, "vapor_bam_links: out of memory");
-    } catch (const std::exception& e) {
-        return bfail(VAPOR_E_ARG, std::string("vapor_bam_links: ") + e.what());
-    }
+    return bam_guarded("vapor_bam_links", [&] { return bam_links_impl(b, tid, fields, names, names_len, n_chunks, chunks, out); });
 }
 
 // chop_pacbio_read_by_pos (SF:339-354) over alignment records that are in memory already (a caller that holds its reads as

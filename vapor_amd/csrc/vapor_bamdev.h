@@ -967,6 +967,7 @@ __device__ __forceinline__ void bam_chop_body(const uint8_t* __restrict__ arena,
     const long long beg = start - 1 > 0 ? start - 1 : 0, stop = end;
     const uint32_t flt_excl = (uint32_t)R.pad & 0xFFFFu, flt_mapq = ((uint32_t)R.pad >> 16) & 0xFFu;
     int nk = 0, st = REG_OK;
+    // (its own walk: the tagged CG step reads the tags too; the evidence kernels share walk_records, below)
     for (int s = 0; s < R.span_n && st == REG_OK; ++s) {
         const BamSpan SP = spans[R.span_first + s];
         int bad = 0;
@@ -1154,10 +1155,122 @@ __global__ __launch_bounds__(64) void bam_chop_ops_kernel(const uint8_t* __restr
     bam_chop_body<false, false, true>(arena, regs, spans, blk_status, n_regs, kept, n_kept, reg_status, nullptr, opsv);
 }
 
+// ---- the evidence readers (`--depth`, `--signatures`, `--links`, `--support`) ---------------------------
+// A record that passed the walk, as walk_records hands it to its caller: wave-uniform, by value.
+struct RecView {
+    int32_t pos, l_seq;
+    uint32_t flag_word;             // the header's FLAG << 16 | n_cigar_op
+    uint32_t ops;                   // the operations in the arena, n_ops of them: the CG:B,I array of a `kS mN` record
+    int32_t n_ops;
+    uint32_t aux, end;              // the aux area [aux, end); end is the record's
+};
+
+// The record walk of the four evidence kernels, one wavefront a region (vapor_bam.cpp bam_walk_records is the host's statement;
+// bam_chop_body's walk is where it comes from): the region's spans in order, a span with a damaged block REG_BLOCK; per record the
+// six header words on lanes 0 to 5, the checks of size, staged bytes and layout with their statuses, the contig and order test
+// that skips a record or ends the region at `stop`, the read filter (MAPQ below filter bits 16-23 or FLAG &
+// filter bits 0-15 - as if the record were not in the file; both fields came with the header), the `kS mN` -> CG:B,I
+// replacement.  on_record(RecView) is asked once per passing record and returns REG_OK to go on or the status that ends the
+// region; the walk returns the region's status.
+template <typename OnRecord>
+__device__ __forceinline__ int walk_records(const uint8_t* __restrict__ arena, const BamSpan* __restrict__ spans, const int32_t* __restrict__ blk_status,
+                                            uint32_t lane, int32_t tid, long long stop, int32_t span_first, int span_n, uint32_t filter,
+                                            OnRecord on_record)
+{
+    const uint32_t flt_excl = filter & 0xFFFFu, flt_mapq = (filter >> 16) & 0xFFu;
+    int st = REG_OK;
+    for (int s = 0; s < span_n && st == REG_OK; ++s) {
+        const BamSpan SP = spans[span_first + s];
+        int bad = 0;
+        for (uint32_t i = lane; i < SP.blk_n; i += 64) bad |= blk_status[SP.blk_first + i] != 0;
+        if (__any(bad)) { st = REG_BLOCK; break; }
+        uint32_t pos_u = SP.u_begin;
+        // (a record is 36 bytes at least: pos_u grows every turn and the loop ends at u_end)
+        while (pos_u < SP.u_end) {
+            if ((unsigned long long)pos_u + 36ull > SP.u_limit) { st = REG_BEYOND; break; }
+            uint32_t w = 0;
+            if (lane < 6) w = rd32u(arena + pos_u + 4u * lane);
+            const int32_t bs = (int32_t)__shfl(w, 0), ref_id = (int32_t)__shfl(w, 1), pos = (int32_t)__shfl(w, 2);
+            const uint32_t wd3 = __shfl(w, 3), wd4 = __shfl(w, 4);
+            const int32_t l_seq = (int32_t)__shfl(w, 5);
+            if (bs < 32 || bs > (1 << 29)) { st = REG_MALFORMED; break; }
+            if ((unsigned long long)pos_u + 4ull + (unsigned long long)bs > SP.u_limit) { st = REG_BEYOND; break; }
+            const uint32_t r = pos_u + 4u;
+            pos_u += 4u + (uint32_t)bs;
+            const int l_name = (int)(wd3 & 0xFFu), n_cig = (int)(wd4 & 0xFFFFu);
+            if (l_seq < 0 || 32ll + l_name + 4ll * n_cig + ((long long)l_seq + 1) / 2 + (long long)l_seq > (long long)bs) { st = REG_MALFORMED; break; }
+            if (ref_id != tid || (long long)pos >= stop) {
+                if (ref_id > tid || (ref_id == tid && (long long)pos >= stop)) break;
+                continue;
+            }
+            if (((wd3 >> 8) & 0xFFu) < flt_mapq || ((wd4 >> 16) & flt_excl)) continue;
+            const uint32_t cig = r + 32u + (uint32_t)l_name;
+            RecView rec{pos, l_seq, wd4, cig, n_cig, cig + 4u * (uint32_t)n_cig + (uint32_t)((l_seq + 1) / 2) + (uint32_t)l_seq, r + (uint32_t)bs};
+            if (n_cig == 2) {
+                const uint32_t o0 = rd32u(arena + cig), o1 = rd32u(arena + cig + 4);
+                if ((o0 & 15u) == 4u && (int32_t)(o0 >> 4) == l_seq && (o1 & 15u) == 3u) {
+                    int32_t cnt = 0;
+                    const uint32_t cg = find_cg_dev(arena, rec.aux, rec.end, &cnt);
+                    if (cg) { rec.ops = cg; rec.n_ops = cnt; }
+                }
+            }
+            st = on_record(rec);
+            if (st != REG_OK) break;
+        }
+    }
+    return st;
+}
+
+__device__ __forceinline__ bool sig_is_clip(uint32_t o) { return (o & 15u) == 4u || (o & 15u) == 5u; }
+
+// The clipped bases at a record's two ends, for a kernel that walks the operations 64 a step: tile(o, t0, n_ops) once per tile
+// with the lane's operation.  The leading clip is operations 0 and 1 of the first tile; the trailing clip the last two
+// operations, of which n_ops - 2 may be lane 63 of the tile before (carried in prev63).  A record of at most two operations
+// that are all clips has neither event: lead = -1.
+struct ClipEnds {
+    long long lead = 0, trail = 0;
+    uint32_t prev63 = 15u;          // operation t0 - 1
+    __device__ __forceinline__ void tile(uint32_t o, int32_t t0, int32_t n_ops)
+    {
+        if (t0 == 0) {
+            const uint32_t o0 = __shfl(o, 0), o1 = __shfl(o, 1);
+            if (sig_is_clip(o0)) lead = (long long)(o0 >> 4) + ((n_ops >= 2 && sig_is_clip(o1)) ? (long long)(o1 >> 4) : 0);
+            if (sig_is_clip(o0) && (n_ops == 1 || (n_ops == 2 && sig_is_clip(o1)))) lead = -1;
+        }
+        if (t0 + 64 >= n_ops) {
+            const int32_t l = n_ops - 1 - t0;       // the lane of the last operation, 0..63
+            const uint32_t ol = __shfl(o, l), op = l > 0 ? __shfl(o, l - 1) : prev63;
+            if (sig_is_clip(ol)) trail = (long long)(ol >> 4) + ((n_ops >= 2 && sig_is_clip(op)) ? (long long)(op >> 4) : 0);
+        }
+        prev63 = __shfl(o, 63);
+    }
+};
+
+// The mode of a histogram of offsets -tol .. tol (hist[i] counts offset i - tol; width = 2 tol + 1): one wave maximum over
+// key = count << 10 | 1023 - rank, rank = 2 |offset| + (offset > 0) - the largest key is the largest count, then the smallest
+// |offset|, then the negative one.  The same on every lane; offset 0 for an empty histogram.
+struct HistMode { int32_t off; uint32_t cnt; };
+__device__ __forceinline__ HistMode hist_mode(const uint32_t* hist, uint32_t width, long long tol, uint32_t lane)
+{
+    unsigned long long key = 0;
+    for (uint32_t i = lane; i < width; i += 64) {
+        const long long off = (long long)i - tol;
+        const uint32_t rank = (uint32_t)(off < 0 ? -2 * off : 2 * off + 1);
+        const unsigned long long k = ((unsigned long long)hist[i] << 10) | (unsigned long long)(1023u - rank);
+        key = k > key ? k : key;
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const unsigned long long o = __shfl_xor(key, d);
+        key = o > key ? o : key;
+    }
+    const uint32_t cnt = (uint32_t)(key >> 10), rank = 1023u - (uint32_t)(key & 1023u);
+    return {cnt ? ((rank & 1u) ? (int32_t)(rank >> 1) : -(int32_t)(rank >> 1)) : 0, cnt};
+}
+
 // Read depth of three consecutive intervals per region (`--depth`; vapor_bam.cpp bam_depth_impl is the host's
-// statement, vapor_amd/depth.py cover the rule): one wavefront a region, bam_chop_body's record walk - the six header words on
-// lanes 0 to 5, the same checks of size, layout, contig and order with the same statuses, the same filter test on the same
-// words - with another question behind it.  Per passing record the operations go 64 a step: one wave_scan64 of the reference
+// statement, vapor_amd/depth.py cover the rule): one wavefront a region, walk_records to b3 with the depth question behind
+// it.  Per passing record the operations go 64 a step: one wave_scan64 of the reference
 // advance (M D N = X) gives every lane where its operation starts, the total is carried from tile to tile, and an M, = or X
 // operation adds its overlap with each interval to the lane's three 64-bit sums.  A tile that ends at or behind b3 is the
 // record's last (what follows starts behind every interval); a record at or behind b3 ends the region.  The sums are reduced
@@ -1177,65 +1290,27 @@ __global__ __launch_bounds__(64) void bam_depth_kernel(const uint8_t* __restrict
     const uint32_t lane = threadIdx.x;
     const DepthRegion R = regs[g];
     const long long b0 = R.b[0], b1 = R.b[1], b2 = R.b[2], b3 = R.b[3];
-    const uint32_t flt_excl = R.filter & 0xFFFFu, flt_mapq = (R.filter >> 16) & 0xFFu;
     unsigned long long c0 = 0, c1 = 0, c2 = 0;
-    int st = REG_OK;
-    for (int s = 0; s < R.span_n && st == REG_OK; ++s) {
-        const BamSpan SP = spans[R.span_first + s];
-        int bad = 0;
-        for (uint32_t i = lane; i < SP.blk_n; i += 64) bad |= blk_status[SP.blk_first + i] != 0;
-        if (__any(bad)) { st = REG_BLOCK; break; }
-        uint32_t pos_u = SP.u_begin;
-        // (a record is 36 bytes at least: pos_u grows every turn and the loop ends at u_end)
-        while (pos_u < SP.u_end) {
-            if ((unsigned long long)pos_u + 36ull > SP.u_limit) { st = REG_BEYOND; break; }
-            uint32_t w = 0;
-            if (lane < 6) w = rd32u(arena + pos_u + 4u * lane);
-            const int32_t bs = (int32_t)__shfl(w, 0), ref_id = (int32_t)__shfl(w, 1), pos = (int32_t)__shfl(w, 2);
-            const uint32_t w3 = __shfl(w, 3), w4 = __shfl(w, 4);
-            const int32_t l_seq = (int32_t)__shfl(w, 5);
-            if (bs < 32 || bs > (1 << 29)) { st = REG_MALFORMED; break; }
-            if ((unsigned long long)pos_u + 4ull + (unsigned long long)bs > SP.u_limit) { st = REG_BEYOND; break; }
-            const uint32_t r = pos_u + 4u;
-            pos_u += 4u + (uint32_t)bs;
-            const int l_name = (int)(w3 & 0xFFu), n_cig = (int)(w4 & 0xFFFFu);
-            if (l_seq < 0 || 32ll + l_name + 4ll * n_cig + ((long long)l_seq + 1) / 2 + (long long)l_seq > (long long)bs) { st = REG_MALFORMED; break; }
-            if (ref_id != R.tid || (long long)pos >= b3) {
-                if (ref_id > R.tid || (ref_id == R.tid && (long long)pos >= b3)) break;
-                continue;
+    const int st = walk_records(arena, spans, blk_status, lane, R.tid, b3, R.span_first, R.span_n, R.filter, [&](const RecView rec) {
+        long long cur = (long long)rec.pos;             // the reference cursor where the tile starts, 0-based
+        for (int32_t t0 = 0; t0 < rec.n_ops && cur < b3; t0 += 64) {
+            const int32_t t = t0 + (int32_t)lane;
+            const uint32_t o = t < rec.n_ops ? rd32u(arena + rec.ops + 4u * (uint32_t)t) : 15u;
+            const uint32_t code = o & 15u;
+            const long long n = (long long)(o >> 4);
+            const bool covers = code == 0u || code == 7u || code == 8u;
+            const long long adv = (covers || code == 2u || code == 3u) ? n : 0;
+            const long long A = wave_scan64(adv, lane);
+            if (covers) {
+                const long long e = cur + A, sb = e - n;
+                c0 += depth_overlap(sb, e, b0, b1);
+                c1 += depth_overlap(sb, e, b1, b2);
+                c2 += depth_overlap(sb, e, b2, b3);
             }
-            // the read filter, DEPTH_EXCLUDE among its flags: both fields came with the record's header
-            if (((w3 >> 8) & 0xFFu) < flt_mapq || ((w4 >> 16) & flt_excl)) continue;
-            const uint32_t cig = r + 32u + (uint32_t)l_name;
-            uint32_t ops = cig;
-            int32_t n_ops = n_cig;
-            if (n_cig == 2) {
-                const uint32_t o0 = rd32u(arena + cig), o1 = rd32u(arena + cig + 4);
-                if ((o0 & 15u) == 4u && (int32_t)(o0 >> 4) == l_seq && (o1 & 15u) == 3u) {
-                    int32_t cnt = 0;
-                    const uint32_t cg = find_cg_dev(arena, cig + 8u + (uint32_t)((l_seq + 1) / 2) + (uint32_t)l_seq, r + (uint32_t)bs, &cnt);
-                    if (cg) { ops = cg; n_ops = cnt; }
-                }
-            }
-            long long cur = (long long)pos;                 // the reference cursor where the tile starts, 0-based
-            for (int32_t t0 = 0; t0 < n_ops && cur < b3; t0 += 64) {
-                const int32_t t = t0 + (int32_t)lane;
-                const uint32_t o = t < n_ops ? rd32u(arena + ops + 4u * (uint32_t)t) : 15u;
-                const uint32_t code = o & 15u;
-                const long long n = (long long)(o >> 4);
-                const bool covers = code == 0u || code == 7u || code == 8u;
-                const long long adv = (covers || code == 2u || code == 3u) ? n : 0;
-                const long long A = wave_scan64(adv, lane);
-                if (covers) {
-                    const long long e = cur + A, sb = e - n;
-                    c0 += depth_overlap(sb, e, b0, b1);
-                    c1 += depth_overlap(sb, e, b1, b2);
-                    c2 += depth_overlap(sb, e, b2, b3);
-                }
-                cur += __shfl(A, 63);
-            }
+            cur += __shfl(A, 63);
         }
-    }
+        return (int)REG_OK;
+    });
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) {
         c0 += __shfl_down(c0, (unsigned)d);
@@ -1251,17 +1326,13 @@ __global__ __launch_bounds__(64) void bam_depth_kernel(const uint8_t* __restrict
 }
 
 // Split-read and CIGAR evidence per region (`--signatures`; vapor_bam.cpp bam_signature_impl is the host's
-// statement, vapor_amd/signature.py answer the rule): one wavefront a region, bam_depth_kernel's record walk with its checks,
-// statuses and filter test, and behind it the events of a record.  The operations go 64 a step to the record's end (RCLIP needs
-// the reference end): one wave_scan64 of the reference advance gives every lane the cursor where its operation starts, and a D
-// or N (GAP) or an I (INSOP) is tested on the lane that holds it.  The leading clip is operations 0 and 1 of the first tile; the
-// trailing clip the last two operations, of which n - 2 may be lane 63 of the tile before (carried in `prev63`).  Lanes 0 to 3
-// own the four clip bits (bit k: the leading clip for even k, the trailing for odd; target x0 below 2, x1 above), so a record's
-// clip events cost one comparison on four lanes.  Counts are per-lane registers, reduced once; the two histograms are
-// 2 * (2 * tol + 1) words of LDS, updated with LDS atomics by the lane that owns the event; the mode of each is one wave
-// maximum over a key that orders (count, smaller |offset|, negative offset) exactly.
-__device__ __forceinline__ bool sig_is_clip(uint32_t o) { return (o & 15u) == 4u || (o & 15u) == 5u; }
-
+// statement, vapor_amd/signature.py answer the rule): one wavefront a region, walk_records to w3, and behind it the events of
+// a record.  The operations go 64 a step to the record's end (RCLIP needs the reference end): one wave_scan64 of the reference
+// advance gives every lane the cursor where its operation starts, and a D or N (GAP) or an I (INSOP) is tested on the lane
+// that holds it; ClipEnds keeps the two clips.  Lanes 0 to 3 own the four clip bits (bit k: the leading clip for even k, the
+// trailing for odd; target x0 below 2, x1 above), so a record's clip events cost one comparison on four lanes.  Counts are
+// per-lane registers, reduced once; the two histograms are 2 * (2 * tol + 1) words of LDS, updated with LDS atomics by the lane
+// that owns the event; the mode of each is hist_mode's.
 __global__ __launch_bounds__(64) void bam_signature_kernel(const uint8_t* __restrict__ arena, const SigRegion* __restrict__ regs,
                                                           const BamSpan* __restrict__ spans, const int32_t* __restrict__ blk_status, int n_regs,
                                                           uint32_t* __restrict__ ans, int32_t* __restrict__ reg_status)
@@ -1277,7 +1348,6 @@ __global__ __launch_bounds__(64) void bam_signature_kernel(const uint8_t* __rest
     const uint32_t width = 2u * (uint32_t)tol + 1u;
     const long long nmin = R.nmin, nmax = R.nmax, min_clip = R.min_clip;
     const uint32_t mask = R.mask;
-    const uint32_t flt_excl = R.filter & 0xFFFFu, flt_mapq = (R.filter >> 16) & 0xFFu;
     for (uint32_t i = lane; i < 2u * width; i += 64) hist[i] = 0u;
     __syncthreads();
     // this lane's clip bit, for lanes 0 to 3: which end of the record, which target, which histogram
@@ -1285,95 +1355,47 @@ __global__ __launch_bounds__(64) void bam_signature_kernel(const uint8_t* __rest
     const long long my_x = (lane & 2u) ? x1 : x0;
     const uint32_t my_hist = (lane & 2u) ? width : 0u;
     uint32_t c_clip = 0, c_gap = 0, c_ins = 0;
-    int st = REG_OK;
-    const int span_n = w3 > R.w0 ? R.span_n : 0;            // (an empty window has no records, whatever chunks came with it)
-    for (int s = 0; s < span_n && st == REG_OK; ++s) {
-        const BamSpan SP = spans[R.span_first + s];
-        int bad = 0;
-        for (uint32_t i = lane; i < SP.blk_n; i += 64) bad |= blk_status[SP.blk_first + i] != 0;
-        if (__any(bad)) { st = REG_BLOCK; break; }
-        uint32_t pos_u = SP.u_begin;
-        // (a record is 36 bytes at least: pos_u grows every turn and the loop ends at u_end)
-        while (pos_u < SP.u_end) {
-            if ((unsigned long long)pos_u + 36ull > SP.u_limit) { st = REG_BEYOND; break; }
-            uint32_t w = 0;
-            if (lane < 6) w = rd32u(arena + pos_u + 4u * lane);
-            const int32_t bs = (int32_t)__shfl(w, 0), ref_id = (int32_t)__shfl(w, 1), pos = (int32_t)__shfl(w, 2);
-            const uint32_t wd3 = __shfl(w, 3), wd4 = __shfl(w, 4);
-            const int32_t l_seq = (int32_t)__shfl(w, 5);
-            if (bs < 32 || bs > (1 << 29)) { st = REG_MALFORMED; break; }
-            if ((unsigned long long)pos_u + 4ull + (unsigned long long)bs > SP.u_limit) { st = REG_BEYOND; break; }
-            const uint32_t r = pos_u + 4u;
-            pos_u += 4u + (uint32_t)bs;
-            const int l_name = (int)(wd3 & 0xFFu), n_cig = (int)(wd4 & 0xFFFFu);
-            if (l_seq < 0 || 32ll + l_name + 4ll * n_cig + ((long long)l_seq + 1) / 2 + (long long)l_seq > (long long)bs) { st = REG_MALFORMED; break; }
-            if (ref_id != R.tid || (long long)pos >= w3) {
-                if (ref_id > R.tid || (ref_id == R.tid && (long long)pos >= w3)) break;
-                continue;
-            }
-            // the read filter, DEPTH_EXCLUDE among its flags: both fields came with the record's header
-            if (((wd3 >> 8) & 0xFFu) < flt_mapq || ((wd4 >> 16) & flt_excl)) continue;
-            const uint32_t cig = r + 32u + (uint32_t)l_name;
-            uint32_t ops = cig;
-            int32_t n_ops = n_cig;
-            if (n_cig == 2) {
-                const uint32_t o0 = rd32u(arena + cig), o1 = rd32u(arena + cig + 4);
-                if ((o0 & 15u) == 4u && (int32_t)(o0 >> 4) == l_seq && (o1 & 15u) == 3u) {
-                    int32_t cnt = 0;
-                    const uint32_t cg = find_cg_dev(arena, cig + 8u + (uint32_t)((l_seq + 1) / 2) + (uint32_t)l_seq, r + (uint32_t)bs, &cnt);
-                    if (cg) { ops = cg; n_ops = cnt; }
+    // (an empty window has no records, whatever chunks came with it)
+    const int st = walk_records(arena, spans, blk_status, lane, R.tid, w3, R.span_first, w3 > R.w0 ? R.span_n : 0, R.filter, [&](const RecView rec) {
+        const int32_t n_ops = rec.n_ops;
+        if (n_ops <= 0) return (int)REG_OK;             // no CIGAR: nothing, and no error
+        long long cur = (long long)rec.pos;             // the reference cursor where the tile starts, 0-based
+        ClipEnds clip;
+        for (int32_t t0 = 0; t0 < n_ops; t0 += 64) {
+            const int32_t t = t0 + (int32_t)lane;
+            const uint32_t o = t < n_ops ? rd32u(arena + rec.ops + 4u * (uint32_t)t) : 15u;
+            const uint32_t code = o & 15u;
+            const long long n = (long long)(o >> 4);
+            const long long adv = (code == 0u || code == 2u || code == 3u || code == 7u || code == 8u) ? n : 0;
+            const long long A = wave_scan64(adv, lane);
+            const long long a = cur + A - adv;          // where this lane's operation starts
+            if ((code == 2u || code == 3u) && (mask & SIG_GAP) && n >= nmin && n <= nmax) {
+                const long long d0 = a - x0, d1 = a + n - x1;
+                if (d0 >= -tol && d0 <= tol && d1 >= -tol && d1 <= tol) {
+                    ++c_gap;
+                    atomicAdd(&hist[(uint32_t)(d0 + tol)], 1u);
+                    atomicAdd(&hist[width + (uint32_t)(d1 + tol)], 1u);
                 }
             }
-            if (n_ops <= 0) continue;                       // no CIGAR: nothing, and no error
-            long long cur = (long long)pos;                 // the reference cursor where the tile starts, 0-based
-            long long lead = 0, trail = 0;                  // the clipped bases at the record's two ends
-            uint32_t prev63 = 15u;                          // operation t0 - 1, for a trailing clip that starts on the tile before
-            for (int32_t t0 = 0; t0 < n_ops; t0 += 64) {
-                const int32_t t = t0 + (int32_t)lane;
-                const uint32_t o = t < n_ops ? rd32u(arena + ops + 4u * (uint32_t)t) : 15u;
-                const uint32_t code = o & 15u;
-                const long long n = (long long)(o >> 4);
-                const long long adv = (code == 0u || code == 2u || code == 3u || code == 7u || code == 8u) ? n : 0;
-                const long long A = wave_scan64(adv, lane);
-                const long long a = cur + A - adv;          // where this lane's operation starts
-                if ((code == 2u || code == 3u) && (mask & SIG_GAP) && n >= nmin && n <= nmax) {
-                    const long long d0 = a - x0, d1 = a + n - x1;
-                    if (d0 >= -tol && d0 <= tol && d1 >= -tol && d1 <= tol) {
-                        ++c_gap;
-                        atomicAdd(&hist[(uint32_t)(d0 + tol)], 1u);
-                        atomicAdd(&hist[width + (uint32_t)(d1 + tol)], 1u);
-                    }
-                }
-                if (code == 1u && (mask & SIG_INSOP) && n >= nmin && n <= nmax && a >= x0 - tol && a <= x1 + tol) {
-                    ++c_ins;
-                    const long long d0 = a - x0;
-                    if (d0 >= -tol && d0 <= tol) atomicAdd(&hist[(uint32_t)(d0 + tol)], 1u);
-                }
-                if (t0 == 0) {
-                    const uint32_t o0 = __shfl(o, 0), o1 = __shfl(o, 1);
-                    if (sig_is_clip(o0)) lead = (long long)(o0 >> 4) + ((n_ops >= 2 && sig_is_clip(o1)) ? (long long)(o1 >> 4) : 0);
-                    // (a record of at most two operations that are all clips has neither event)
-                    if (sig_is_clip(o0) && (n_ops == 1 || (n_ops == 2 && sig_is_clip(o1)))) lead = -1;
-                }
-                if (t0 + 64 >= n_ops) {
-                    const int32_t l = n_ops - 1 - t0;       // the lane of the last operation, 0..63
-                    const uint32_t ol = __shfl(o, l), op = l > 0 ? __shfl(o, l - 1) : prev63;
-                    if (sig_is_clip(ol)) trail = (long long)(ol >> 4) + ((n_ops >= 2 && sig_is_clip(op)) ? (long long)(op >> 4) : 0);
-                }
-                prev63 = __shfl(o, 63);
-                cur += __shfl(A, 63);
+            if (code == 1u && (mask & SIG_INSOP) && n >= nmin && n <= nmax && a >= x0 - tol && a <= x1 + tol) {
+                ++c_ins;
+                const long long d0 = a - x0;
+                if (d0 >= -tol && d0 <= tol) atomicAdd(&hist[(uint32_t)(d0 + tol)], 1u);
             }
-            if (lead < 0) continue;
-            if (my_clip) {
-                const long long have = (lane & 1u) ? trail : lead;
-                const long long d = ((lane & 1u) ? cur : (long long)pos) - my_x;
-                if (have >= min_clip && d >= -tol && d <= tol) {
-                    ++c_clip;
-                    atomicAdd(&hist[my_hist + (uint32_t)(d + tol)], 1u);
-                }
+            clip.tile(o, t0, n_ops);
+            cur += __shfl(A, 63);
+        }
+        if (clip.lead < 0) return (int)REG_OK;
+        if (my_clip) {
+            const long long have = (lane & 1u) ? clip.trail : clip.lead;
+            const long long d = ((lane & 1u) ? cur : (long long)rec.pos) - my_x;
+            if (have >= min_clip && d >= -tol && d <= tol) {
+                ++c_clip;
+                atomicAdd(&hist[my_hist + (uint32_t)(d + tol)], 1u);
             }
         }
-    }
+        return (int)REG_OK;
+    });
     __syncthreads();
     // the six counts: lanes 0 to 3 hold the clip bits', the GAP and INSOP counts are sums over the wavefront
 #pragma unroll
@@ -1382,35 +1404,11 @@ __global__ __launch_bounds__(64) void bam_signature_kernel(const uint8_t* __rest
         c_ins += __shfl_down(c_ins, (unsigned)d);
     }
     const uint32_t k0 = __shfl(c_clip, 0), k1 = __shfl(c_clip, 1), k2 = __shfl(c_clip, 2), k3 = __shfl(c_clip, 3);
-    // the modes: key = count << 10 | 1023 - rank, rank = 2 |offset| + (offset > 0) - the largest key is the largest count, then
-    // the smallest |offset|, then the negative one
-    unsigned long long best[2];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        unsigned long long key = 0;
-        for (uint32_t i = lane; i < width; i += 64) {
-            const long long off = (long long)i - tol;
-            const uint32_t rank = (uint32_t)(off < 0 ? -2 * off : 2 * off + 1);
-            const unsigned long long k = ((unsigned long long)hist[(uint32_t)h * width + i] << 10) | (unsigned long long)(1023u - rank);
-            key = k > key ? k : key;
-        }
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            const unsigned long long o = __shfl_xor(key, d);
-            key = o > key ? o : key;
-        }
-        best[h] = key;
-    }
+    const HistMode m0 = hist_mode(hist, width, tol, lane), m1 = hist_mode(hist + width, width, tol, lane);
     if (lane == 0) {
         uint32_t* o = ans + (size_t)SIG_ANSWER_WORDS * (size_t)g;
         o[0] = k0; o[1] = k1; o[2] = k2; o[3] = k3; o[4] = c_gap; o[5] = c_ins;
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const uint32_t cnt = (uint32_t)(best[h] >> 10), rank = 1023u - (uint32_t)(best[h] & 1023u);
-            const int32_t off = cnt ? ((rank & 1u) ? (int32_t)(rank >> 1) : -(int32_t)(rank >> 1)) : 0;
-            o[6 + 2 * h] = (uint32_t)off;
-            o[7 + 2 * h] = cnt;
-        }
+        o[6] = (uint32_t)m0.off; o[7] = m0.cnt; o[8] = (uint32_t)m1.off; o[9] = m1.cnt;
         reg_status[g] = st;
     }
 }
@@ -1591,12 +1589,13 @@ __device__ __forceinline__ uint32_t link_scan_sa(const uint8_t* arena, uint32_t 
 }
 
 // Split reads joined through their SA tags, per region (`--links`; vapor_bam.cpp bam_links_impl is the host's
-// statement, vapor_amd/links.py answer the rule): one wavefront a region; the header checks, statuses, filter test, CG
-// replacement and clip test are bam_signature_kernel's.  A region asks for one clip event.  LCLIP needs the first two operations
-// only; RCLIP the last two and the reference end, a wave sum per 64 operations.  Only a clip record - the event within tol of x -
-// pays for the aux walk to SA (find_sa_dev) and the scan of its value (link_scan_sa).  Everything about a record is
-// wave-uniform here: the three counts are scalars, the histogram - 2 * tol + 1 words of LDS - takes one LDS atomic from lane 0
-// per linked record, and the mode is bam_signature_kernel's wave maximum over the same key.
+// statement, vapor_amd/links.py answer the rule): one wavefront a region; the name check, then walk_records to w3.  A region asks
+// for one clip event.  LCLIP needs the first two operations only; RCLIP the last two and the reference end, a wave sum per 64
+// operations: the four operations are loaded directly, not through ClipEnds, so that a record without the event costs no tile.
+// Only a clip record - the event within tol of x - pays for the aux walk to SA (find_sa_dev) and the scan of its value
+// (link_scan_sa); a damaged aux area ends the region.  Everything about a record is wave-uniform here: the three counts are
+// scalars, the histogram - 2 * tol + 1 words of LDS - takes one LDS atomic from lane 0 per linked record, and the mode is
+// hist_mode's.
 __global__ __launch_bounds__(64) void bam_link_kernel(const uint8_t* __restrict__ arena, const LinkRegion* __restrict__ regs,
                                                      const BamSpan* __restrict__ spans, const int32_t* __restrict__ blk_status,
                                                      const uint8_t* __restrict__ names, uint32_t names_len, int n_regs,
@@ -1613,7 +1612,6 @@ __global__ __launch_bounds__(64) void bam_link_kernel(const uint8_t* __restrict_
     const uint32_t width = 2u * (uint32_t)tol + 1u;
     const long long min_clip = R.min_clip;
     const bool want_r = R.bits & LINK_EV, use_b = R.bits & LINK_PEND, differ = R.bits & LINK_REL;
-    const uint32_t flt_excl = R.filter & 0xFFFFu, flt_mapq = (R.filter >> 16) & 0xFFu;
     for (uint32_t i = lane; i < width; i += 64) hist[i] = 0u;
     __syncthreads();
     uint32_t n_clip = 0, n_split = 0, n_link = 0;
@@ -1621,108 +1619,58 @@ __global__ __launch_bounds__(64) void bam_link_kernel(const uint8_t* __restrict_
     // (the host checked the name against the blob; a table that says otherwise is the host route's to refuse)
     if (R.name_len == 0u || R.name_off > names_len || R.name_len > names_len - R.name_off) st = REG_MALFORMED;
     const uint8_t* pname = names + R.name_off;
-    const int span_n = w3 > R.w0 ? R.span_n : 0;            // (an empty window has no records, whatever chunks came with it)
-    for (int s = 0; s < span_n && st == REG_OK; ++s) {
-        const BamSpan SP = spans[R.span_first + s];
-        int bad = 0;
-        for (uint32_t i = lane; i < SP.blk_n; i += 64) bad |= blk_status[SP.blk_first + i] != 0;
-        if (__any(bad)) { st = REG_BLOCK; break; }
-        uint32_t pos_u = SP.u_begin;
-        // (a record is 36 bytes at least: pos_u grows every turn and the loop ends at u_end)
-        while (pos_u < SP.u_end) {
-            if ((unsigned long long)pos_u + 36ull > SP.u_limit) { st = REG_BEYOND; break; }
-            uint32_t w = 0;
-            if (lane < 6) w = rd32u(arena + pos_u + 4u * lane);
-            const int32_t bs = (int32_t)__shfl(w, 0), ref_id = (int32_t)__shfl(w, 1), pos = (int32_t)__shfl(w, 2);
-            const uint32_t wd3 = __shfl(w, 3), wd4 = __shfl(w, 4);
-            const int32_t l_seq = (int32_t)__shfl(w, 5);
-            if (bs < 32 || bs > (1 << 29)) { st = REG_MALFORMED; break; }
-            if ((unsigned long long)pos_u + 4ull + (unsigned long long)bs > SP.u_limit) { st = REG_BEYOND; break; }
-            const uint32_t r = pos_u + 4u;
-            pos_u += 4u + (uint32_t)bs;
-            const int l_name = (int)(wd3 & 0xFFu), n_cig = (int)(wd4 & 0xFFFFu);
-            if (l_seq < 0 || 32ll + l_name + 4ll * n_cig + ((long long)l_seq + 1) / 2 + (long long)l_seq > (long long)bs) { st = REG_MALFORMED; break; }
-            if (ref_id != R.tid || (long long)pos >= w3) {
-                if (ref_id > R.tid || (ref_id == R.tid && (long long)pos >= w3)) break;
-                continue;
-            }
-            // the read filter, DEPTH_EXCLUDE among its flags: both fields came with the record's header
-            if (((wd3 >> 8) & 0xFFu) < flt_mapq || ((wd4 >> 16) & flt_excl)) continue;
-            const uint32_t cig = r + 32u + (uint32_t)l_name;
-            const uint32_t aux = cig + 4u * (uint32_t)n_cig + (uint32_t)((l_seq + 1) / 2) + (uint32_t)l_seq, rec_end = r + (uint32_t)bs;
-            uint32_t ops = cig;
-            int32_t n_ops = n_cig;
-            if (n_cig == 2) {
-                const uint32_t o0 = rd32u(arena + cig), o1 = rd32u(arena + cig + 4);
-                if ((o0 & 15u) == 4u && (int32_t)(o0 >> 4) == l_seq && (o1 & 15u) == 3u) {
-                    int32_t cnt = 0;
-                    const uint32_t cg = find_cg_dev(arena, aux, rec_end, &cnt);
-                    if (cg) { ops = cg; n_ops = cnt; }
-                }
-            }
-            if (n_ops <= 0) continue;                       // no CIGAR: nothing, and no error
-            const uint32_t o0 = rd32u(arena + ops), o1 = n_ops >= 2 ? rd32u(arena + ops + 4u) : 15u;
-            // (a record of at most two operations that are all clips has neither event)
-            if (sig_is_clip(o0) && (n_ops == 1 || (n_ops == 2 && sig_is_clip(o1)))) continue;
-            long long have = 0, at = (long long)pos;
-            if (!want_r) {
-                // LCLIP: the operations behind the first two are not walked
-                if (sig_is_clip(o0)) have = (long long)(o0 >> 4) + (sig_is_clip(o1) ? (long long)(o1 >> 4) : 0);
-            } else {
-                const uint32_t ol = rd32u(arena + ops + 4u * (uint32_t)(n_ops - 1)), op = n_ops >= 2 ? rd32u(arena + ops + 4u * (uint32_t)(n_ops - 2)) : 15u;
-                if (sig_is_clip(ol)) have = (long long)(ol >> 4) + (sig_is_clip(op) ? (long long)(op >> 4) : 0);
-                if (have < min_clip) continue;              // (no event: its reference end is not needed)
-                for (int32_t t0 = 0; t0 < n_ops; t0 += 64) {
-                    const int32_t t = t0 + (int32_t)lane;
-                    const uint32_t o = t < n_ops ? rd32u(arena + ops + 4u * (uint32_t)t) : 15u;
-                    const uint32_t code = o & 15u;
-                    at += wave_sum64((code == 0u || code == 2u || code == 3u || code == 7u || code == 8u) ? (long long)(o >> 4) : 0);
-                }
-            }
-            const long long d = at - x;
-            if (have < min_clip || d < -tol || d > tol) continue;
-            ++n_clip;
-            uint32_t value = 0, len = 0;
-            const int found = find_sa_dev(arena, aux, rec_end, lane, &value, &len);
-            if (found == 2) { st = REG_MALFORMED; break; }
-            if (found != 1) continue;
-            long long off = 0;
-            const uint32_t got = link_scan_sa(arena, value, value + len, lane, pname, R.name_len, ((wd4 >> 16) & 0x10u) != 0u, differ, use_b, y, tol,
-                                              flt_mapq, &off);
-            if (got & 1u) ++n_split;
-            if (got & 2u) {
-                ++n_link;
-                if (lane == 0) atomicAdd(&hist[(uint32_t)(off + tol)], 1u);
+    // (an empty window has no records, whatever chunks came with it)
+    if (st == REG_OK) st = walk_records(arena, spans, blk_status, lane, R.tid, w3, R.span_first, w3 > R.w0 ? R.span_n : 0, R.filter, [&](const RecView rec) {
+        const uint32_t ops = rec.ops;
+        const int32_t n_ops = rec.n_ops;
+        if (n_ops <= 0) return (int)REG_OK;             // no CIGAR: nothing, and no error
+        const uint32_t o0 = rd32u(arena + ops), o1 = n_ops >= 2 ? rd32u(arena + ops + 4u) : 15u;
+        // (a record of at most two operations that are all clips has neither event)
+        if (sig_is_clip(o0) && (n_ops == 1 || (n_ops == 2 && sig_is_clip(o1)))) return (int)REG_OK;
+        long long have = 0, at = (long long)rec.pos;
+        if (!want_r) {
+            // LCLIP: the operations behind the first two are not walked
+            if (sig_is_clip(o0)) have = (long long)(o0 >> 4) + (sig_is_clip(o1) ? (long long)(o1 >> 4) : 0);
+        } else {
+            const uint32_t ol = rd32u(arena + ops + 4u * (uint32_t)(n_ops - 1)), op = n_ops >= 2 ? rd32u(arena + ops + 4u * (uint32_t)(n_ops - 2)) : 15u;
+            if (sig_is_clip(ol)) have = (long long)(ol >> 4) + (sig_is_clip(op) ? (long long)(op >> 4) : 0);
+            if (have < min_clip) return (int)REG_OK;    // (no event: its reference end is not needed)
+            for (int32_t t0 = 0; t0 < n_ops; t0 += 64) {
+                const int32_t t = t0 + (int32_t)lane;
+                const uint32_t o = t < n_ops ? rd32u(arena + ops + 4u * (uint32_t)t) : 15u;
+                const uint32_t code = o & 15u;
+                at += wave_sum64((code == 0u || code == 2u || code == 3u || code == 7u || code == 8u) ? (long long)(o >> 4) : 0);
             }
         }
-    }
+        const long long d = at - x;
+        if (have < min_clip || d < -tol || d > tol) return (int)REG_OK;
+        ++n_clip;
+        uint32_t value = 0, len = 0;
+        const int found = find_sa_dev(arena, rec.aux, rec.end, lane, &value, &len);
+        if (found == 2) return (int)REG_MALFORMED;
+        if (found != 1) return (int)REG_OK;
+        long long off = 0;
+        const uint32_t got = link_scan_sa(arena, value, value + len, lane, pname, R.name_len, ((rec.flag_word >> 16) & 0x10u) != 0u, differ, use_b, y, tol,
+                                          (R.filter >> 16) & 0xFFu, &off);
+        if (got & 1u) ++n_split;
+        if (got & 2u) {
+            ++n_link;
+            if (lane == 0) atomicAdd(&hist[(uint32_t)(off + tol)], 1u);
+        }
+        return (int)REG_OK;
+    });
     __syncthreads();
-    // the mode: key = count << 10 | 1023 - rank, rank = 2 |offset| + (offset > 0) - bam_signature_kernel's
-    unsigned long long key = 0;
-    for (uint32_t i = lane; i < width; i += 64) {
-        const long long off = (long long)i - tol;
-        const uint32_t rank = (uint32_t)(off < 0 ? -2 * off : 2 * off + 1);
-        const unsigned long long k = ((unsigned long long)hist[i] << 10) | (unsigned long long)(1023u - rank);
-        key = k > key ? k : key;
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const unsigned long long o = __shfl_xor(key, d);
-        key = o > key ? o : key;
-    }
+    const HistMode m = hist_mode(hist, width, tol, lane);
     if (lane == 0) {
         uint32_t* o = ans + (size_t)LINK_ANSWER_WORDS * (size_t)g;
-        const uint32_t cnt = (uint32_t)(key >> 10), rank = 1023u - (uint32_t)(key & 1023u);
-        o[0] = n_clip; o[1] = n_split; o[2] = n_link;
-        o[3] = (uint32_t)(cnt ? ((rank & 1u) ? (int32_t)(rank >> 1) : -(int32_t)(rank >> 1)) : 0);
-        o[4] = cnt;
+        o[0] = n_clip; o[1] = n_split; o[2] = n_link; o[3] = (uint32_t)m.off; o[4] = m.cnt;
         reg_status[g] = st;
     }
 }
 
 // Alt and ref alignments per region (`--support`; vapor_bam.cpp bam_support_impl is the host's statement,
-// vapor_amd/support.py answer the rule): one wavefront a region, bam_signature_kernel's record walk with its checks, statuses,
-// filter test, tiles of 64 operations and `prev63` carry.  The question is per record, not per event: each lane tests its own
+// vapor_amd/support.py answer the rule): one wavefront a region, walk_records to w3, and per record the signature kernel's tiles
+// of 64 operations with ClipEnds.  The question is per record, not per event: each lane tests its own
 // operation for "a GAP or INSOP that 4.20 counts", "blocks target 0" and "blocks target 1", __any makes the three answers
 // wave-uniform and they are OR-ed over the record's tiles.  Behind the last tile the reference end, the two clips and the three
 // flags are uniform, so the record's class and its coverage are a few uniform comparisons, and the seven counts are uniform
@@ -1739,104 +1687,55 @@ __global__ __launch_bounds__(64) void bam_support_kernel(const uint8_t* __restri
     const long long tol = R.tol, nmin = R.nmin, nmax = R.nmax, min_clip = R.min_clip;
     const long long F = R.flank, gmin = R.gmin;
     const uint32_t mask = R.mask;
-    const uint32_t flt_excl = R.filter & 0xFFFFu, flt_mapq = (R.filter >> 16) & 0xFFu;
     uint32_t n_cg = 0, n_l = 0, n_r = 0, n_ref0 = 0, n_ref1 = 0, n_cov0 = 0, n_cov1 = 0;
-    int st = REG_OK;
-    const int span_n = w3 > R.w0 ? R.span_n : 0;            // (an empty window has no records, whatever chunks came with it)
-    for (int s = 0; s < span_n && st == REG_OK; ++s) {
-        const BamSpan SP = spans[R.span_first + s];
-        int bad = 0;
-        for (uint32_t i = lane; i < SP.blk_n; i += 64) bad |= blk_status[SP.blk_first + i] != 0;
-        if (__any(bad)) { st = REG_BLOCK; break; }
-        uint32_t pos_u = SP.u_begin;
-        // (a record is 36 bytes at least: pos_u grows every turn and the loop ends at u_end)
-        while (pos_u < SP.u_end) {
-            if ((unsigned long long)pos_u + 36ull > SP.u_limit) { st = REG_BEYOND; break; }
-            uint32_t w = 0;
-            if (lane < 6) w = rd32u(arena + pos_u + 4u * lane);
-            const int32_t bs = (int32_t)__shfl(w, 0), ref_id = (int32_t)__shfl(w, 1), pos = (int32_t)__shfl(w, 2);
-            const uint32_t wd3 = __shfl(w, 3), wd4 = __shfl(w, 4);
-            const int32_t l_seq = (int32_t)__shfl(w, 5);
-            if (bs < 32 || bs > (1 << 29)) { st = REG_MALFORMED; break; }
-            if ((unsigned long long)pos_u + 4ull + (unsigned long long)bs > SP.u_limit) { st = REG_BEYOND; break; }
-            const uint32_t r = pos_u + 4u;
-            pos_u += 4u + (uint32_t)bs;
-            const int l_name = (int)(wd3 & 0xFFu), n_cig = (int)(wd4 & 0xFFFFu);
-            if (l_seq < 0 || 32ll + l_name + 4ll * n_cig + ((long long)l_seq + 1) / 2 + (long long)l_seq > (long long)bs) { st = REG_MALFORMED; break; }
-            if (ref_id != R.tid || (long long)pos >= w3) {
-                if (ref_id > R.tid || (ref_id == R.tid && (long long)pos >= w3)) break;
-                continue;
+    // (an empty window has no records, whatever chunks came with it)
+    const int st = walk_records(arena, spans, blk_status, lane, R.tid, w3, R.span_first, w3 > R.w0 ? R.span_n : 0, R.filter, [&](const RecView rec) {
+        const int32_t n_ops = rec.n_ops;
+        if (n_ops <= 0) return (int)REG_OK;             // no CIGAR: nothing, and no error
+        long long cur = (long long)rec.pos;             // the reference cursor where the tile starts, 0-based
+        ClipEnds clip;
+        bool cg = false, blk0 = false, blk1 = false;    // the record's three flags, wave-uniform, OR-ed over its tiles
+        for (int32_t t0 = 0; t0 < n_ops; t0 += 64) {
+            const int32_t t = t0 + (int32_t)lane;
+            const uint32_t o = t < n_ops ? rd32u(arena + rec.ops + 4u * (uint32_t)t) : 15u;
+            const uint32_t code = o & 15u;
+            const long long n = (long long)(o >> 4);
+            const long long adv = (code == 0u || code == 2u || code == 3u || code == 7u || code == 8u) ? n : 0;
+            const long long A = wave_scan64(adv, lane);
+            const long long a = cur + A - adv;          // where this lane's operation starts
+            const bool gap = code == 2u || code == 3u, ins = code == 1u;
+            bool my_cg = false;
+            if (gap && (mask & SIG_GAP) && n >= nmin && n <= nmax) {
+                const long long d0 = a - x0, d1 = a + n - x1;
+                my_cg = d0 >= -tol && d0 <= tol && d1 >= -tol && d1 <= tol;
             }
-            // the read filter, DEPTH_EXCLUDE among its flags: both fields came with the record's header
-            if (((wd3 >> 8) & 0xFFu) < flt_mapq || ((wd4 >> 16) & flt_excl)) continue;
-            const uint32_t cig = r + 32u + (uint32_t)l_name;
-            uint32_t ops = cig;
-            int32_t n_ops = n_cig;
-            if (n_cig == 2) {
-                const uint32_t o0 = rd32u(arena + cig), o1 = rd32u(arena + cig + 4);
-                if ((o0 & 15u) == 4u && (int32_t)(o0 >> 4) == l_seq && (o1 & 15u) == 3u) {
-                    int32_t cnt = 0;
-                    const uint32_t cg = find_cg_dev(arena, cig + 8u + (uint32_t)((l_seq + 1) / 2) + (uint32_t)l_seq, r + (uint32_t)bs, &cnt);
-                    if (cg) { ops = cg; n_ops = cnt; }
-                }
-            }
-            if (n_ops <= 0) continue;                       // no CIGAR: nothing, and no error
-            long long cur = (long long)pos;                 // the reference cursor where the tile starts, 0-based
-            long long lead = 0, trail = 0;                  // the clipped bases at the record's two ends
-            uint32_t prev63 = 15u;                          // operation t0 - 1, for a trailing clip that starts on the tile before
-            bool cg = false, blk0 = false, blk1 = false;    // the record's three flags, wave-uniform, OR-ed over its tiles
-            for (int32_t t0 = 0; t0 < n_ops; t0 += 64) {
-                const int32_t t = t0 + (int32_t)lane;
-                const uint32_t o = t < n_ops ? rd32u(arena + ops + 4u * (uint32_t)t) : 15u;
-                const uint32_t code = o & 15u;
-                const long long n = (long long)(o >> 4);
-                const long long adv = (code == 0u || code == 2u || code == 3u || code == 7u || code == 8u) ? n : 0;
-                const long long A = wave_scan64(adv, lane);
-                const long long a = cur + A - adv;          // where this lane's operation starts
-                const bool gap = code == 2u || code == 3u, ins = code == 1u;
-                bool my_cg = false;
-                if (gap && (mask & SIG_GAP) && n >= nmin && n <= nmax) {
-                    const long long d0 = a - x0, d1 = a + n - x1;
-                    my_cg = d0 >= -tol && d0 <= tol && d1 >= -tol && d1 <= tol;
-                }
-                if (ins && (mask & SIG_INSOP) && n >= nmin && n <= nmax && a >= x0 - tol && a <= x1 + tol) my_cg = true;
-                const bool big = n >= gmin;
-                const bool my_b0 = big && ((gap && a < x0 + F && a + n > x0 - F) || (ins && a >= x0 - F && a <= x0 + F));
-                const bool my_b1 = big && ((gap && a < x1 + F && a + n > x1 - F) || (ins && a >= x1 - F && a <= x1 + F));
-                cg = cg || __any(my_cg);
-                blk0 = blk0 || __any(my_b0);
-                blk1 = blk1 || __any(my_b1);
-                if (t0 == 0) {
-                    const uint32_t o0 = __shfl(o, 0), o1 = __shfl(o, 1);
-                    if (sig_is_clip(o0)) lead = (long long)(o0 >> 4) + ((n_ops >= 2 && sig_is_clip(o1)) ? (long long)(o1 >> 4) : 0);
-                    // (a record of at most two operations that are all clips has neither event)
-                    if (sig_is_clip(o0) && (n_ops == 1 || (n_ops == 2 && sig_is_clip(o1)))) lead = -1;
-                }
-                if (t0 + 64 >= n_ops) {
-                    const int32_t l = n_ops - 1 - t0;       // the lane of the last operation, 0..63
-                    const uint32_t ol = __shfl(o, l), op = l > 0 ? __shfl(o, l - 1) : prev63;
-                    if (sig_is_clip(ol)) trail = (long long)(ol >> 4) + ((n_ops >= 2 && sig_is_clip(op)) ? (long long)(op >> 4) : 0);
-                }
-                prev63 = __shfl(o, 63);
-                cur += __shfl(A, 63);
-            }
-            if (lead < 0) continue;                         // (it covers no base either: nothing of the rule holds for it)
-            // the record: [pos, q) on the reference, every value below is the same on all lanes
-            const long long p = (long long)pos, q = cur;
-            const bool lc = lead >= min_clip, tc = trail >= min_clip;
-            const long long dp0 = p - x0, dq0 = q - x0, dp1 = p - x1, dq1 = q - x1;
-            const bool clip0 = ((mask & SIG_LCLIP0) && lc && dp0 >= -tol && dp0 <= tol) || ((mask & SIG_RCLIP0) && tc && dq0 >= -tol && dq0 <= tol);
-            const bool clip1 = ((mask & SIG_LCLIP1) && lc && dp1 >= -tol && dp1 <= tol) || ((mask & SIG_RCLIP1) && tc && dq1 >= -tol && dq1 <= tol);
-            const bool span0 = p <= x0 - F && q >= x0 + F && !blk0, span1 = p <= x1 - F && q >= x1 + F && !blk1;
-            n_cg += cg ? 1u : 0u;
-            n_l += (clip0 && !cg) ? 1u : 0u;
-            n_r += (clip1 && !cg) ? 1u : 0u;
-            n_ref0 += ((mask & SUP_REF0) && span0 && !cg && !clip0) ? 1u : 0u;
-            n_ref1 += ((mask & SUP_REF1) && span1 && !cg && !clip1) ? 1u : 0u;
-            n_cov0 += (p <= x0 && x0 < q) ? 1u : 0u;
-            n_cov1 += (p <= x1 && x1 < q) ? 1u : 0u;
+            if (ins && (mask & SIG_INSOP) && n >= nmin && n <= nmax && a >= x0 - tol && a <= x1 + tol) my_cg = true;
+            const bool big = n >= gmin;
+            const bool my_b0 = big && ((gap && a < x0 + F && a + n > x0 - F) || (ins && a >= x0 - F && a <= x0 + F));
+            const bool my_b1 = big && ((gap && a < x1 + F && a + n > x1 - F) || (ins && a >= x1 - F && a <= x1 + F));
+            cg = cg || __any(my_cg);
+            blk0 = blk0 || __any(my_b0);
+            blk1 = blk1 || __any(my_b1);
+            clip.tile(o, t0, n_ops);
+            cur += __shfl(A, 63);
         }
-    }
+        if (clip.lead < 0) return (int)REG_OK;          // (it covers no base either: nothing of the rule holds for it)
+        // the record: [pos, q) on the reference, every value below is the same on all lanes
+        const long long p = (long long)rec.pos, q = cur;
+        const bool lc = clip.lead >= min_clip, tc = clip.trail >= min_clip;
+        const long long dp0 = p - x0, dq0 = q - x0, dp1 = p - x1, dq1 = q - x1;
+        const bool clip0 = ((mask & SIG_LCLIP0) && lc && dp0 >= -tol && dp0 <= tol) || ((mask & SIG_RCLIP0) && tc && dq0 >= -tol && dq0 <= tol);
+        const bool clip1 = ((mask & SIG_LCLIP1) && lc && dp1 >= -tol && dp1 <= tol) || ((mask & SIG_RCLIP1) && tc && dq1 >= -tol && dq1 <= tol);
+        const bool span0 = p <= x0 - F && q >= x0 + F && !blk0, span1 = p <= x1 - F && q >= x1 + F && !blk1;
+        n_cg += cg ? 1u : 0u;
+        n_l += (clip0 && !cg) ? 1u : 0u;
+        n_r += (clip1 && !cg) ? 1u : 0u;
+        n_ref0 += ((mask & SUP_REF0) && span0 && !cg && !clip0) ? 1u : 0u;
+        n_ref1 += ((mask & SUP_REF1) && span1 && !cg && !clip1) ? 1u : 0u;
+        n_cov0 += (p <= x0 && x0 < q) ? 1u : 0u;
+        n_cov1 += (p <= x1 && x1 < q) ? 1u : 0u;
+        return (int)REG_OK;
+    });
     if (lane == 0) {
         uint32_t* o = ans + (size_t)SUP_ANSWER_WORDS * (size_t)g;
         o[0] = n_cg; o[1] = n_l; o[2] = n_r; o[3] = n_ref0; o[4] = n_ref1; o[5] = n_cov0; o[6] = n_cov1;

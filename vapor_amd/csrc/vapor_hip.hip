@@ -1166,194 +1166,104 @@ extern "C" int vapor_bam_chop_device_haplotag(vapor_ctx* ctx, vapor_bam* bam, in
     return bam_chop_device_impl(ctx, bam, c, ChopOut{kept_first, sq_addr, q0, miss, status, member, phase_set, tagged}, out);
 }
 
-// Read depth of many regions of an open BAM file (`--depth`; vapor_readplan.h DepthCall): what
+// The evidence of many regions of an open BAM file (`--depth`, `--signatures`, `--links`, `--support`): what
 // bam_chop_device_impl does up to the inflate launch - the regions' chunks staged, scanned, laid out in the arena, inflated with
-// CRC - then bam_depth_kernel, one wavefront a region, and one copy back.  The arena is a block of the call: nothing stays on the
-// device, and there is no batch.  The statistics of the chop call (vapor_bam_last_stats) are left alone.
+// CRC - then the call's kernel, one wavefront a region (launch(stream, arena, meta, the device's block)), and one copy back.  The
+// arena is a block of the call: nothing stays on the device, and there is no batch.  The statistics of the chop call
+// (vapor_bam_last_stats) are left alone.  `who` is the entry's name in its errors; the plan is the call's in vapor_readplan.h.
+template <typename Layout, typename Call, typename Out, typename Launch>
+static int bam_evidence_device(vapor_ctx* ctx, vapor_bam* bam, const char* who, Call& call, Out* out, int32_t* status, Launch launch)
+{
+    using namespace vapor_readplan;
+    if (!ctx || !bam) return fail(VAPOR_E_ARG, std::string(who) + ": bad argument");
+    if (const Refusal r = check_args(call, out, status)) return fail(r.code, r.msg);
+    const int fd = vapor_bam_fileno(bam);
+    if (fd < 0) return fail(VAPOR_E_ARG, std::string(who) + ": the file is not open");
+    call.filter_word = depth_filter_word(vapor_bam_filter_word(bam));
+    HIPCHK(hipSetDevice(ctx->device));
+    return guarded(who, [&]() -> int {
+        SpanPlan plan;
+        if (const Refusal r = plan_spans(call, status, plan)) return fail(r.code, r.msg);
+        CallScope sc(ctx, ctx->stream);
+        InflateStage stage(sc);
+        Block<> d_arena(sc);
+        HIPCHK(stage.begin(plan.stage_bytes));
+        read_and_scan(stage, fd, bam, plan.spans);
+        Layout L;
+        if (const Refusal r = layout(call, plan, status, L)) return fail(r.code, r.msg);
+        const typename Layout::Meta& M = L.meta;
+        if (const int rc = stage.alloc(M.bytes, M.bytes)) return rc;
+        HIPCHK(d_arena.ensure(L.arena + 64));
+        uint8_t *const h_meta = stage.h_meta, *const d_meta = stage.d_meta;
+        L.fill(h_meta);
+        const hipStream_t st = sc.st = bam_stream_of(ctx);
+        if (const int rc = stage.run(L.blks.size(), M.in_bytes, M.blks.in(d_meta), M.blk_status.in(d_meta), d_arena, ctx->bam_ev)) return rc;
+        if (call.n_regions) {
+            launch(st, (const uint8_t*)d_arena, M, d_meta);
+            HIPCHK(hipGetLastError());
+        }
+        HIPCHK(hipMemcpyAsync(M.back(h_meta), M.back(d_meta), M.back_bytes(), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        sc.settled();
+        collect(call, M, h_meta, out, status);
+        return VAPOR_OK;
+    });
+}
+
+// bam_depth_kernel: three 64-bit sums a region
 extern "C" int vapor_bam_depth_device(vapor_ctx* ctx, vapor_bam* bam, int32_t n_regions, const int32_t* tid, const int64_t* bounds,
                                       const int32_t* chunk_first, const uint64_t* chunks, uint64_t* cov, int32_t* status)
 {
     using namespace vapor_bamdev;
-    using namespace vapor_readplan;
-    if (!ctx || !bam) return fail(VAPOR_E_ARG, "vapor_bam_depth_device: bad argument");
-    DepthCall call;
+    vapor_readplan::DepthCall call;
     call.n_regions = n_regions; call.tid = tid; call.bounds = bounds; call.chunk_first = chunk_first; call.chunks = chunks;
-    if (const Refusal r = check_args(call, cov, status)) return fail(r.code, r.msg);
-    const int fd = vapor_bam_fileno(bam);
-    if (fd < 0) return fail(VAPOR_E_ARG, "vapor_bam_depth_device: the file is not open");
-    call.filter_word = depth_filter_word(vapor_bam_filter_word(bam));
-    HIPCHK(hipSetDevice(ctx->device));
-    return guarded("vapor_bam_depth_device", [&]() -> int {
-        SpanPlan plan;
-        if (const Refusal r = plan_spans(call, status, plan)) return fail(r.code, r.msg);
-        std::vector<HostSpan>& spans = plan.spans;
-        CallScope sc(ctx, ctx->stream);
-        InflateStage stage(sc);
-        Block<> d_arena(sc);
-        HIPCHK(stage.begin(plan.stage_bytes));
-        read_and_scan(stage, fd, bam, spans);
-        DepthLayout L;
-        if (const Refusal r = layout(call, plan, status, L)) return fail(r.code, r.msg);
-        const DepthMeta& M = L.meta;
-        const size_t n_blks = L.blks.size();
-        if (const int rc = stage.alloc(M.bytes, M.bytes)) return rc;
-        HIPCHK(d_arena.ensure(L.arena + 64));
-        uint8_t *const h_meta = stage.h_meta, *const d_meta = stage.d_meta;
-        L.fill(h_meta);
-        const hipStream_t st = sc.st = bam_stream_of(ctx);
-        if (const int rc = stage.run(n_blks, M.in_bytes, M.blks.in(d_meta), M.blk_status.in(d_meta), d_arena, ctx->bam_ev)) return rc;
-        if (n_regions) {
-            hipLaunchKernelGGL(bam_depth_kernel, dim3((unsigned)n_regions), dim3(64), 0, st, d_arena, M.regs.in(d_meta), M.spans.in(d_meta), M.blk_status.in(d_meta),
-                               (int)n_regions, reinterpret_cast<unsigned long long*>(M.cov.in(d_meta)), M.reg_status.in(d_meta));
-            HIPCHK(hipGetLastError());
-        }
-        HIPCHK(hipMemcpyAsync(M.back(h_meta), M.back(d_meta), M.back_bytes(), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        sc.settled();
-        collect(call, M, h_meta, cov, status);
-        return VAPOR_OK;
+    return bam_evidence_device<vapor_readplan::DepthLayout>(ctx, bam, "vapor_bam_depth_device", call, cov, status,
+                                                            [&](hipStream_t st, const uint8_t* arena, const auto& M, uint8_t* d_meta) {
+        hipLaunchKernelGGL(bam_depth_kernel, dim3((unsigned)n_regions), dim3(64), 0, st, arena, M.regs.in(d_meta), M.spans.in(d_meta), M.blk_status.in(d_meta),
+                           (int)n_regions, reinterpret_cast<unsigned long long*>(M.ans.in(d_meta)), M.reg_status.in(d_meta));
     });
 }
 
-// Split-read and CIGAR evidence of many regions of an open BAM file (`--signatures`; vapor_readplan.h SigCall):
-// vapor_bam_depth_device's steps with another plan and another kernel - the regions' chunks staged, scanned, laid out, inflated
-// with CRC, then bam_signature_kernel, one wavefront a region, and one copy back.  Nothing stays on the device.
+// bam_signature_kernel: SIG_ANSWER_WORDS words a region
 extern "C" int vapor_bam_signature_device(vapor_ctx* ctx, vapor_bam* bam, int32_t n_regions, const int32_t* tid, const int64_t* regions,
                                           const int32_t* chunk_first, const uint64_t* chunks, int64_t* out, int32_t* status)
 {
     using namespace vapor_bamdev;
-    using namespace vapor_readplan;
-    if (!ctx || !bam) return fail(VAPOR_E_ARG, "vapor_bam_signature_device: bad argument");
-    SigCall call;
+    vapor_readplan::SigCall call;
     call.n_regions = n_regions; call.tid = tid; call.regions = regions; call.chunk_first = chunk_first; call.chunks = chunks;
-    if (const Refusal r = check_args(call, out, status)) return fail(r.code, r.msg);
-    const int fd = vapor_bam_fileno(bam);
-    if (fd < 0) return fail(VAPOR_E_ARG, "vapor_bam_signature_device: the file is not open");
-    call.filter_word = depth_filter_word(vapor_bam_filter_word(bam));
-    HIPCHK(hipSetDevice(ctx->device));
-    return guarded("vapor_bam_signature_device", [&]() -> int {
-        SpanPlan plan;
-        if (const Refusal r = plan_spans(call, status, plan)) return fail(r.code, r.msg);
-        CallScope sc(ctx, ctx->stream);
-        InflateStage stage(sc);
-        Block<> d_arena(sc);
-        HIPCHK(stage.begin(plan.stage_bytes));
-        read_and_scan(stage, fd, bam, plan.spans);
-        SigLayout L;
-        if (const Refusal r = layout(call, plan, status, L)) return fail(r.code, r.msg);
-        const SigMeta& M = L.meta;
-        const size_t n_blks = L.blks.size();
-        if (const int rc = stage.alloc(M.bytes, M.bytes)) return rc;
-        HIPCHK(d_arena.ensure(L.arena + 64));
-        uint8_t *const h_meta = stage.h_meta, *const d_meta = stage.d_meta;
-        L.fill(h_meta);
-        const hipStream_t st = sc.st = bam_stream_of(ctx);
-        if (const int rc = stage.run(n_blks, M.in_bytes, M.blks.in(d_meta), M.blk_status.in(d_meta), d_arena, ctx->bam_ev)) return rc;
-        if (n_regions) {
-            hipLaunchKernelGGL(bam_signature_kernel, dim3((unsigned)n_regions), dim3(64), 0, st, d_arena, M.regs.in(d_meta), M.spans.in(d_meta), M.blk_status.in(d_meta),
-                               (int)n_regions, M.ans.in(d_meta), M.reg_status.in(d_meta));
-            HIPCHK(hipGetLastError());
-        }
-        HIPCHK(hipMemcpyAsync(M.back(h_meta), M.back(d_meta), M.back_bytes(), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        sc.settled();
-        collect(call, M, h_meta, out, status);
-        return VAPOR_OK;
+    return bam_evidence_device<vapor_readplan::SigLayout>(ctx, bam, "vapor_bam_signature_device", call, out, status,
+                                                          [&](hipStream_t st, const uint8_t* arena, const auto& M, uint8_t* d_meta) {
+        hipLaunchKernelGGL(bam_signature_kernel, dim3((unsigned)n_regions), dim3(64), 0, st, arena, M.regs.in(d_meta), M.spans.in(d_meta), M.blk_status.in(d_meta),
+                           (int)n_regions, M.ans.in(d_meta), M.reg_status.in(d_meta));
     });
 }
 
-// Split reads joined through their SA tags, many regions of an open BAM file (`--links`; vapor_readplan.h
-// LinkCall): vapor_bam_signature_device's steps with another plan and another kernel - the partner names go up once, inside the
-// call's metadata block - then bam_link_kernel, one wavefront a region, and one copy back.  Nothing stays on the device.
+// bam_link_kernel: LINK_ANSWER_WORDS words a region; the partner names go up once, inside the call's metadata block
 extern "C" int vapor_bam_links_device(vapor_ctx* ctx, vapor_bam* bam, int32_t n_regions, const int32_t* tid, const int64_t* regions, const uint8_t* names,
                                       int64_t names_len, const int32_t* chunk_first, const uint64_t* chunks, int64_t* out, int32_t* status)
 {
     using namespace vapor_bamdev;
-    using namespace vapor_readplan;
-    if (!ctx || !bam) return fail(VAPOR_E_ARG, "vapor_bam_links_device: bad argument");
-    LinkCall call;
+    vapor_readplan::LinkCall call;
     call.n_regions = n_regions; call.tid = tid; call.regions = regions; call.names = names; call.names_len = names_len;
     call.chunk_first = chunk_first; call.chunks = chunks;
-    if (const Refusal r = check_args(call, out, status)) return fail(r.code, r.msg);
-    const int fd = vapor_bam_fileno(bam);
-    if (fd < 0) return fail(VAPOR_E_ARG, "vapor_bam_links_device: the file is not open");
-    call.filter_word = depth_filter_word(vapor_bam_filter_word(bam));
-    HIPCHK(hipSetDevice(ctx->device));
-    return guarded("vapor_bam_links_device", [&]() -> int {
-        SpanPlan plan;
-        if (const Refusal r = plan_spans(call, status, plan)) return fail(r.code, r.msg);
-        CallScope sc(ctx, ctx->stream);
-        InflateStage stage(sc);
-        Block<> d_arena(sc);
-        HIPCHK(stage.begin(plan.stage_bytes));
-        read_and_scan(stage, fd, bam, plan.spans);
-        LinkLayout L;
-        if (const Refusal r = layout(call, plan, status, L)) return fail(r.code, r.msg);
-        const LinkMeta& M = L.meta;
-        const size_t n_blks = L.blks.size();
-        if (const int rc = stage.alloc(M.bytes, M.bytes)) return rc;
-        HIPCHK(d_arena.ensure(L.arena + 64));
-        uint8_t *const h_meta = stage.h_meta, *const d_meta = stage.d_meta;
-        L.fill(h_meta);
-        const hipStream_t st = sc.st = bam_stream_of(ctx);
-        if (const int rc = stage.run(n_blks, M.in_bytes, M.blks.in(d_meta), M.blk_status.in(d_meta), d_arena, ctx->bam_ev)) return rc;
-        if (n_regions) {
-            hipLaunchKernelGGL(bam_link_kernel, dim3((unsigned)n_regions), dim3(64), 0, st, d_arena, M.regs.in(d_meta), M.spans.in(d_meta), M.blk_status.in(d_meta),
-                               M.names.in(d_meta), (uint32_t)names_len, (int)n_regions, M.ans.in(d_meta), M.reg_status.in(d_meta));
-            HIPCHK(hipGetLastError());
-        }
-        HIPCHK(hipMemcpyAsync(M.back(h_meta), M.back(d_meta), M.back_bytes(), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        sc.settled();
-        collect(call, M, h_meta, out, status);
-        return VAPOR_OK;
+    return bam_evidence_device<vapor_readplan::LinkLayout>(ctx, bam, "vapor_bam_links_device", call, out, status,
+                                                           [&](hipStream_t st, const uint8_t* arena, const auto& M, uint8_t* d_meta) {
+        hipLaunchKernelGGL(bam_link_kernel, dim3((unsigned)n_regions), dim3(64), 0, st, arena, M.regs.in(d_meta), M.spans.in(d_meta), M.blk_status.in(d_meta),
+                           M.names.in(d_meta), (uint32_t)names_len, (int)n_regions, M.ans.in(d_meta), M.reg_status.in(d_meta));
     });
 }
 
-// Alt and ref alignments of many regions of an open BAM file (`--support`; vapor_readplan.h SupCall):
-// vapor_bam_signature_device's steps with another plan and another kernel - bam_support_kernel, one wavefront a region, and one
-// copy back.  Nothing stays on the device.
+// bam_support_kernel: SUP_ANSWER_WORDS counts a region
 extern "C" int vapor_bam_support_device(vapor_ctx* ctx, vapor_bam* bam, int32_t n_regions, const int32_t* tid, const int64_t* regions,
                                         const int32_t* chunk_first, const uint64_t* chunks, int64_t* out, int32_t* status)
 {
     using namespace vapor_bamdev;
-    using namespace vapor_readplan;
-    if (!ctx || !bam) return fail(VAPOR_E_ARG, "vapor_bam_support_device: bad argument");
-    SupCall call;
+    vapor_readplan::SupCall call;
     call.n_regions = n_regions; call.tid = tid; call.regions = regions; call.chunk_first = chunk_first; call.chunks = chunks;
-    if (const Refusal r = check_args(call, out, status)) return fail(r.code, r.msg);
-    const int fd = vapor_bam_fileno(bam);
-    if (fd < 0) return fail(VAPOR_E_ARG, "vapor_bam_support_device: the file is not open");
-    call.filter_word = depth_filter_word(vapor_bam_filter_word(bam));
-    HIPCHK(hipSetDevice(ctx->device));
-    return guarded("vapor_bam_support_device", [&]() -> int {
-        SpanPlan plan;
-        if (const Refusal r = plan_spans(call, status, plan)) return fail(r.code, r.msg);
-        CallScope sc(ctx, ctx->stream);
-        InflateStage stage(sc);
-        Block<> d_arena(sc);
-        HIPCHK(stage.begin(plan.stage_bytes));
-        read_and_scan(stage, fd, bam, plan.spans);
-        SupLayout L;
-        if (const Refusal r = layout(call, plan, status, L)) return fail(r.code, r.msg);
-        const SupMeta& M = L.meta;
-        const size_t n_blks = L.blks.size();
-        if (const int rc = stage.alloc(M.bytes, M.bytes)) return rc;
-        HIPCHK(d_arena.ensure(L.arena + 64));
-        uint8_t *const h_meta = stage.h_meta, *const d_meta = stage.d_meta;
-        L.fill(h_meta);
-        const hipStream_t st = sc.st = bam_stream_of(ctx);
-        if (const int rc = stage.run(n_blks, M.in_bytes, M.blks.in(d_meta), M.blk_status.in(d_meta), d_arena, ctx->bam_ev)) return rc;
-        if (n_regions) {
-            hipLaunchKernelGGL(bam_support_kernel, dim3((unsigned)n_regions), dim3(64), 0, st, d_arena, M.regs.in(d_meta), M.spans.in(d_meta), M.blk_status.in(d_meta),
-                               (int)n_regions, M.ans.in(d_meta), M.reg_status.in(d_meta));
-            HIPCHK(hipGetLastError());
-        }
-        HIPCHK(hipMemcpyAsync(M.back(h_meta), M.back(d_meta), M.back_bytes(), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        sc.settled();
-        collect(call, M, h_meta, out, status);
-        return VAPOR_OK;
+    return bam_evidence_device<vapor_readplan::SupLayout>(ctx, bam, "vapor_bam_support_device", call, out, status,
+                                                          [&](hipStream_t st, const uint8_t* arena, const auto& M, uint8_t* d_meta) {
+        hipLaunchKernelGGL(bam_support_kernel, dim3((unsigned)n_regions), dim3(64), 0, st, arena, M.regs.in(d_meta), M.spans.in(d_meta), M.blk_status.in(d_meta),
+                           (int)n_regions, M.ans.in(d_meta), M.reg_status.in(d_meta));
     });
 }
 

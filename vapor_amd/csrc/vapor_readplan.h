@@ -1,5 +1,5 @@
 // vapor_readplan.h - the plan of a device reader call (the planning is host arithmetic without HIP), for
-// vapor_bam_chop_device*, vapor_bam_depth_device and vapor_fasta_windows_device in vapor_hip.hip.  Plain C++17 over vapor_readrec.h and vapor_bgzf.h: which
+// vapor_bam_chop_device*, the four evidence calls and vapor_fasta_windows_device in vapor_hip.hip.  Plain C++17 over vapor_readrec.h and vapor_bgzf.h: which
 // regions are refused and why, which file ranges are read and where they go in the staging block, where every span, stretch and
 // block lands in the arena, where the tables lie in the call's metadata block, what the host reads back and how that becomes the
 // caller's arrays.  The .hip keeps the reads, the allocations, the copies and the launches.  tools/readplan_check.cpp holds all of
@@ -370,6 +370,96 @@ inline void collect(const ChopCall& c, const ChopMeta& M, const uint8_t* h_meta,
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
+// The evidence calls: vapor_bam_depth_device, _signature_device, _links_device, _support_device.  One plan
+// shape over (the region record the kernel reads, the answer word it writes, the words a region, which of them are signed); a
+// call's own rules - *_region_ok, *_region_set, plan_spans, the texts of its refusals - stand in its section below.
+// ------------------------------------------------------------------------------------------------------------------------------
+// Where each table of an evidence call lies in its metadata block: blocks, spans, regions and - a call that has one - the name
+// blob go in; block status, WORDS answer words a region and the region status come back.  The host's block is the device's.
+template <typename Region, typename Word, int WORDS, uint32_t SIGNED = 0>
+struct EvidenceMeta {
+    Table<BgzfBlk> blks;
+    Table<BamSpan> spans;
+    Table<Region> regs;
+    Table<uint8_t> names;                  // links: the partner contigs' names, once, whatever number of regions name a contig
+    Table<int32_t> blk_status;
+    Table<Word> ans;                       // WORDS a region; bit k of SIGNED: word k is an int32
+    Table<int32_t> reg_status;
+    size_t in_bytes = 0, bytes = 0;
+
+    EvidenceMeta() = default;
+    EvidenceMeta(int32_t n_regions, size_t n_blks, size_t n_spans, size_t names_room)      // names_room 0: the call has no blob
+    {
+        const size_t nr = (size_t)std::max(n_regions, 1);
+        Carve m;
+        m.take(blks, std::max<size_t>(n_blks, 1));
+        m.take(spans, std::max<size_t>(n_spans, 1));
+        m.take(regs, nr);
+        m.take(names, names_room);
+        in_bytes = m.off;
+        m.take(blk_status, std::max<size_t>(n_blks, 1));
+        m.take(ans, (size_t)WORDS * nr);
+        m.take(reg_status, nr);
+        bytes = m.off;
+    }
+    size_t back_bytes() const { return bytes - blk_status.off; }       // [blk_status.off, bytes) comes back
+    template <typename B> B* back(B* block) const { return block + blk_status.off; }
+};
+
+template <typename Region, typename Word, int WORDS, uint32_t SIGNED = 0>
+struct EvidenceLayout {
+    using Meta = EvidenceMeta<Region, Word, WORDS, SIGNED>;
+    std::vector<BgzfBlk> blks;
+    std::vector<BamSpan> spans;
+    std::vector<Region> regs;
+    const uint8_t* names = nullptr;        // links
+    size_t names_len = 0;
+    size_t arena = 0;
+    Meta meta;
+    void fill(uint8_t* h_meta) const       // the tables that go in, into the host's block
+    {
+        if (!blks.empty()) memcpy(meta.blks.in(h_meta), blks.data(), sizeof(BgzfBlk) * blks.size());
+        if (!spans.empty()) memcpy(meta.spans.in(h_meta), spans.data(), sizeof(BamSpan) * spans.size());
+        memcpy(meta.regs.in(h_meta), regs.data(), sizeof(Region) * regs.size());
+        if (names_len) memcpy(meta.names.in(h_meta), names, names_len);
+    }
+};
+
+// layout_of with the call's region records, then the metadata block.  (set(R, g) as layout_of takes it; names_room as EvidenceMeta)
+template <typename Call, typename Layout, typename SetRegion>
+inline Refusal layout_evidence(const Call& c, const SpanPlan& p, int32_t* status, Layout& L, const char* too_big, SetRegion set, size_t names_room = 0)
+{
+    if (const Refusal r = layout_of(c.n_regions, p, status, L.blks, L.spans, L.regs, &L.arena, too_big, set)) return r;
+    L.meta = typename Layout::Meta(c.n_regions, L.blks.size(), L.spans.size(), names_room);
+    return {};
+}
+
+// The read-back block into the caller's arrays: a region the host refused keeps its status and zeros, one the device refused
+// takes the device's status (its answer is then the host route's to make), the others their WORDS words.
+template <typename Call, typename Region, typename Word, int WORDS, uint32_t SIGNED, typename Out>
+inline void collect(const Call& c, const EvidenceMeta<Region, Word, WORDS, SIGNED>& M, const uint8_t* h_meta, Out* out, int32_t* status)
+{
+    const Word* da = M.ans.in(h_meta);
+    const int32_t* rst = M.reg_status.in(h_meta);
+    for (int32_t g = 0; g < c.n_regions; ++g) {
+        Out* o = out + (size_t)WORDS * (size_t)g;
+        for (int k = 0; k < WORDS; ++k) o[k] = 0;
+        if (status[g]) continue;
+        if (rst[g] != REG_OK) { status[g] = rst[g]; continue; }
+        const Word* a = da + (size_t)WORDS * (size_t)g;
+        for (int k = 0; k < WORDS; ++k) o[k] = ((SIGNED >> k) & 1u) ? (Out)(int32_t)a[k] : (Out)a[k];
+    }
+}
+
+// the argument rules: what must hold before a region is looked at (fields: the call's bounds or regions; more_ok: its own conditions)
+template <typename Call>
+inline Refusal check_evidence_args(const Call& c, const int64_t* fields, const void* out, const int32_t* status, const char* msg, bool more_ok = true)
+{
+    if (c.n_regions < 0 || !more_ok || (c.n_regions && (!c.tid || !fields || !c.chunk_first || !out || !status))) return {VAPOR_E_ARG, msg};
+    return {};
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
 // vapor_bam_depth_device (`--depth`)
 // ------------------------------------------------------------------------------------------------------------------------------
 struct DepthCall {
@@ -386,9 +476,7 @@ inline uint32_t depth_filter_word(uint32_t handle_word) { return handle_word | D
 
 inline Refusal check_args(const DepthCall& c, const uint64_t* cov, const int32_t* status)
 {
-    if (c.n_regions < 0 || (c.n_regions && (!c.tid || !c.bounds || !c.chunk_first || !cov || !status)))
-        return {VAPOR_E_ARG, "vapor_bam_depth_device: bad argument"};
-    return {};
+    return check_evidence_args(c, c.bounds, cov, status, "vapor_bam_depth_device: bad argument");
 }
 
 // The region rules: the bounds ascend from 0, b3 is a BAM position, the contig is one - else REG_MALFORMED and the host route's
@@ -402,74 +490,16 @@ inline Refusal plan_spans(const DepthCall& c, int32_t* status, SpanPlan& p)
     });
 }
 
-// Where each table of a depth call lies in its metadata block: blocks, spans and regions go in; block status, the three sums a
-// region and the region status come back.
-struct DepthMeta {
-    Table<BgzfBlk> blks;
-    Table<BamSpan> spans;
-    Table<DepthRegion> regs;
-    Table<int32_t> blk_status;
-    Table<uint64_t> cov;                   // three a region
-    Table<int32_t> reg_status;
-    size_t in_bytes = 0, bytes = 0;
-
-    DepthMeta() = default;
-    DepthMeta(int32_t n_regions, size_t n_blks, size_t n_spans)
-    {
-        const size_t nr = (size_t)std::max(n_regions, 1);
-        Carve m;
-        m.take(blks, std::max<size_t>(n_blks, 1));
-        m.take(spans, std::max<size_t>(n_spans, 1));
-        m.take(regs, nr);
-        in_bytes = m.off;
-        m.take(blk_status, std::max<size_t>(n_blks, 1));
-        m.take(cov, 3 * nr);
-        m.take(reg_status, nr);
-        bytes = m.off;
-    }
-    size_t back_bytes() const { return bytes - blk_status.off; }       // the host's block is the device's: [blk_status.off, bytes) comes back
-    template <typename B> B* back(B* block) const { return block + blk_status.off; }
-};
-
-struct DepthLayout {
-    std::vector<BgzfBlk> blks;
-    std::vector<BamSpan> spans;
-    std::vector<DepthRegion> regs;
-    size_t arena = 0;
-    DepthMeta meta;
-    void fill(uint8_t* h_meta) const
-    {
-        if (!blks.empty()) memcpy(meta.blks.in(h_meta), blks.data(), sizeof(BgzfBlk) * blks.size());
-        if (!spans.empty()) memcpy(meta.spans.in(h_meta), spans.data(), sizeof(BamSpan) * spans.size());
-        memcpy(meta.regs.in(h_meta), regs.data(), sizeof(DepthRegion) * regs.size());
-    }
-};
+// three sums a region, 64-bit.  A refused region's record carries its fields all the same.
+using DepthLayout = EvidenceLayout<DepthRegion, uint64_t, 3>;
+using DepthMeta = DepthLayout::Meta;
 
 inline Refusal layout(const DepthCall& c, const SpanPlan& p, int32_t* status, DepthLayout& L)
 {
-    if (const Refusal r = layout_of(c.n_regions, p, status, L.blks, L.spans, L.regs, &L.arena,
-                                    "vapor_bam_depth_device: more than 2 GB of block data in one call (use smaller batches)", [&](DepthRegion& R, int32_t g) {
-            for (int k = 0; k < 4; ++k) R.b[k] = c.bounds[4 * (size_t)g + (size_t)k];
-            R.tid = c.tid[g]; R.filter = c.filter_word;
-        }))
-        return r;
-    L.meta = DepthMeta(c.n_regions, L.blks.size(), L.spans.size());
-    return {};
-}
-
-// The read-back block into the caller's arrays: a region the host refused keeps its status and zeros, one the device refused
-// takes the device's status (its sums are then the host route's to make), the others their three sums.
-inline void collect(const DepthCall& c, const DepthMeta& M, const uint8_t* h_meta, uint64_t* cov, int32_t* status)
-{
-    const uint64_t* dc = M.cov.in(h_meta);
-    const int32_t* rst = M.reg_status.in(h_meta);
-    for (int32_t g = 0; g < c.n_regions; ++g) {
-        uint64_t* o = cov + 3 * (size_t)g;
-        o[0] = o[1] = o[2] = 0;
-        if (status[g]) continue;
-        if (rst[g] != REG_OK) { status[g] = rst[g]; continue; }
-        for (int k = 0; k < 3; ++k) o[k] = dc[3 * (size_t)g + (size_t)k];
-    }
+    return layout_evidence(c, p, status, L, "vapor_bam_depth_device: more than 2 GB of block data in one call (use smaller batches)", [&](DepthRegion& R, int32_t g) {
+        for (int k = 0; k < 4; ++k) R.b[k] = c.bounds[4 * (size_t)g + (size_t)k];
+        R.tid = c.tid[g]; R.filter = c.filter_word;
+    });
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
@@ -487,9 +517,7 @@ struct SigCall {
 
 inline Refusal check_args(const SigCall& c, const int64_t* out, const int32_t* status)
 {
-    if (c.n_regions < 0 || (c.n_regions && (!c.tid || !c.regions || !c.chunk_first || !out || !status)))
-        return {VAPOR_E_ARG, "vapor_bam_signature_device: bad argument"};
-    return {};
+    return check_evidence_args(c, c.regions, out, status, "vapor_bam_signature_device: bad argument");
 }
 
 // Whether a region's own fields are a question the readers answer: the window ascends from 0 and ends at a BAM position, the
@@ -525,77 +553,17 @@ inline Refusal plan_spans(const SigCall& c, int32_t* status, SpanPlan& p)
                          [&](int32_t g, int*) { return sig_region_ok(c.tid[g], c.regions + SIG_FIELDS * (size_t)g); });
 }
 
-// Where each table of a signature call lies in its metadata block: blocks, spans and regions go in; block status, the
-// SIG_ANSWER_WORDS words a region and the region status come back.
-struct SigMeta {
-    Table<BgzfBlk> blks;
-    Table<BamSpan> spans;
-    Table<SigRegion> regs;
-    Table<int32_t> blk_status;
-    Table<uint32_t> ans;                   // SIG_ANSWER_WORDS a region: six counts, then (offset, count) of each mode - the offsets are int32
-    Table<int32_t> reg_status;
-    size_t in_bytes = 0, bytes = 0;
-
-    SigMeta() = default;
-    SigMeta(int32_t n_regions, size_t n_blks, size_t n_spans)
-    {
-        const size_t nr = (size_t)std::max(n_regions, 1);
-        Carve m;
-        m.take(blks, std::max<size_t>(n_blks, 1));
-        m.take(spans, std::max<size_t>(n_spans, 1));
-        m.take(regs, nr);
-        in_bytes = m.off;
-        m.take(blk_status, std::max<size_t>(n_blks, 1));
-        m.take(ans, (size_t)SIG_ANSWER_WORDS * nr);
-        m.take(reg_status, nr);
-        bytes = m.off;
-    }
-    size_t back_bytes() const { return bytes - blk_status.off; }       // the host's block is the device's: [blk_status.off, bytes) comes back
-    template <typename B> B* back(B* block) const { return block + blk_status.off; }
-};
-
-struct SigLayout {
-    std::vector<BgzfBlk> blks;
-    std::vector<BamSpan> spans;
-    std::vector<SigRegion> regs;
-    size_t arena = 0;
-    SigMeta meta;
-    void fill(uint8_t* h_meta) const
-    {
-        if (!blks.empty()) memcpy(meta.blks.in(h_meta), blks.data(), sizeof(BgzfBlk) * blks.size());
-        if (!spans.empty()) memcpy(meta.spans.in(h_meta), spans.data(), sizeof(BamSpan) * spans.size());
-        memcpy(meta.regs.in(h_meta), regs.data(), sizeof(SigRegion) * regs.size());
-    }
-};
+// SIG_ANSWER_WORDS words a region: six counts, then (offset, count) of each mode - the two offsets are int32
+using SigLayout = EvidenceLayout<SigRegion, uint32_t, SIG_ANSWER_WORDS, (1u << 6) | (1u << 8)>;
+using SigMeta = SigLayout::Meta;
 
 inline Refusal layout(const SigCall& c, const SpanPlan& p, int32_t* status, SigLayout& L)
 {
-    if (const Refusal r = layout_of(c.n_regions, p, status, L.blks, L.spans, L.regs, &L.arena,
-                                    "vapor_bam_signature_device: more than 2 GB of block data in one call (use smaller batches)", [&](SigRegion& R, int32_t g) {
-            const int64_t* f = c.regions + SIG_FIELDS * (size_t)g;
-            // (a region the plan refused keeps a record that asks nothing: no kernel reads it, its span_n is 0)
-            if (status[g]) { R = SigRegion(); return; }
-            sig_region_set(R, c.tid[g], f, c.filter_word);
-        }))
-        return r;
-    L.meta = SigMeta(c.n_regions, L.blks.size(), L.spans.size());
-    return {};
-}
-
-// The read-back block into the caller's arrays: a region the host refused keeps its status and zeros, one the device refused
-// takes the device's status (its answer is then the host route's to make), the others their ten words - the offsets signed.
-inline void collect(const SigCall& c, const SigMeta& M, const uint8_t* h_meta, int64_t* out, int32_t* status)
-{
-    const uint32_t* da = M.ans.in(h_meta);
-    const int32_t* rst = M.reg_status.in(h_meta);
-    for (int32_t g = 0; g < c.n_regions; ++g) {
-        int64_t* o = out + (size_t)SIG_ANSWER_WORDS * (size_t)g;
-        for (int k = 0; k < SIG_ANSWER_WORDS; ++k) o[k] = 0;
-        if (status[g]) continue;
-        if (rst[g] != REG_OK) { status[g] = rst[g]; continue; }
-        const uint32_t* a = da + (size_t)SIG_ANSWER_WORDS * (size_t)g;
-        for (int k = 0; k < SIG_ANSWER_WORDS; ++k) o[k] = (k == 6 || k == 8) ? (int64_t)(int32_t)a[k] : (int64_t)a[k];
-    }
+    return layout_evidence(c, p, status, L, "vapor_bam_signature_device: more than 2 GB of block data in one call (use smaller batches)", [&](SigRegion& R, int32_t g) {
+        // (a region the plan refused keeps a record that asks nothing: no kernel reads it, its span_n is 0)
+        if (status[g]) { R = SigRegion(); return; }
+        sig_region_set(R, c.tid[g], c.regions + SIG_FIELDS * (size_t)g, c.filter_word);
+    });
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
@@ -615,10 +583,8 @@ struct LinkCall {
 
 inline Refusal check_args(const LinkCall& c, const int64_t* out, const int32_t* status)
 {
-    if (c.n_regions < 0 || c.names_len < 0 || c.names_len >= ((int64_t)1 << 30) || (c.names_len && !c.names) ||
-        (c.n_regions && (!c.tid || !c.regions || !c.chunk_first || !out || !status)))
-        return {VAPOR_E_ARG, "vapor_bam_links_device: bad argument"};
-    return {};
+    return check_evidence_args(c, c.regions, out, status, "vapor_bam_links_device: bad argument",
+                               c.names_len >= 0 && c.names_len < ((int64_t)1 << 30) && (!c.names_len || c.names));
 }
 
 // Whether a region's own fields are a question the readers answer: the window ascends from 0 and ends at a BAM position, the
@@ -652,83 +618,20 @@ inline Refusal plan_spans(const LinkCall& c, int32_t* status, SpanPlan& p)
                          [&](int32_t g, int*) { return link_region_ok(c.tid[g], c.regions + LINK_FIELDS * (size_t)g, c.names_len); });
 }
 
-// Where each table of a links call lies in its metadata block: blocks, spans, regions and the name blob go in - the blob once,
-// whatever number of regions name a contig; block status, the LINK_ANSWER_WORDS words a region and the region status come back.
-struct LinkMeta {
-    Table<BgzfBlk> blks;
-    Table<BamSpan> spans;
-    Table<LinkRegion> regs;
-    Table<uint8_t> names;
-    Table<int32_t> blk_status;
-    Table<uint32_t> ans;                   // LINK_ANSWER_WORDS a region: n_clip, n_split, n_link, the mode's offset (int32) and count
-    Table<int32_t> reg_status;
-    size_t in_bytes = 0, bytes = 0;
-
-    LinkMeta() = default;
-    LinkMeta(int32_t n_regions, size_t n_blks, size_t n_spans, size_t names_len)
-    {
-        const size_t nr = (size_t)std::max(n_regions, 1);
-        Carve m;
-        m.take(blks, std::max<size_t>(n_blks, 1));
-        m.take(spans, std::max<size_t>(n_spans, 1));
-        m.take(regs, nr);
-        m.take(names, std::max<size_t>(names_len, 1));
-        in_bytes = m.off;
-        m.take(blk_status, std::max<size_t>(n_blks, 1));
-        m.take(ans, (size_t)LINK_ANSWER_WORDS * nr);
-        m.take(reg_status, nr);
-        bytes = m.off;
-    }
-    size_t back_bytes() const { return bytes - blk_status.off; }       // the host's block is the device's: [blk_status.off, bytes) comes back
-    template <typename B> B* back(B* block) const { return block + blk_status.off; }
-};
-
-struct LinkLayout {
-    std::vector<BgzfBlk> blks;
-    std::vector<BamSpan> spans;
-    std::vector<LinkRegion> regs;
-    const uint8_t* names = nullptr;
-    size_t names_len = 0;
-    size_t arena = 0;
-    LinkMeta meta;
-    void fill(uint8_t* h_meta) const
-    {
-        if (!blks.empty()) memcpy(meta.blks.in(h_meta), blks.data(), sizeof(BgzfBlk) * blks.size());
-        if (!spans.empty()) memcpy(meta.spans.in(h_meta), spans.data(), sizeof(BamSpan) * spans.size());
-        memcpy(meta.regs.in(h_meta), regs.data(), sizeof(LinkRegion) * regs.size());
-        if (names_len) memcpy(meta.names.in(h_meta), names, names_len);
-    }
-};
+// LINK_ANSWER_WORDS words a region: n_clip, n_split, n_link, the mode's offset (int32) and count.  The name blob goes up inside
+// the metadata block, a byte of room at least.
+using LinkLayout = EvidenceLayout<LinkRegion, uint32_t, LINK_ANSWER_WORDS, 1u << 3>;
+using LinkMeta = LinkLayout::Meta;
 
 inline Refusal layout(const LinkCall& c, const SpanPlan& p, int32_t* status, LinkLayout& L)
 {
-    if (const Refusal r = layout_of(c.n_regions, p, status, L.blks, L.spans, L.regs, &L.arena,
-                                    "vapor_bam_links_device: more than 2 GB of block data in one call (use smaller batches)", [&](LinkRegion& R, int32_t g) {
-            const int64_t* f = c.regions + LINK_FIELDS * (size_t)g;
-            // (a region the plan refused keeps a record that asks nothing: no kernel reads it, its span_n is 0)
-            if (status[g]) { R = LinkRegion(); return; }
-            link_region_set(R, c.tid[g], f, c.filter_word);
-        }))
-        return r;
     L.names = c.names;
     L.names_len = (size_t)c.names_len;
-    L.meta = LinkMeta(c.n_regions, L.blks.size(), L.spans.size(), L.names_len);
-    return {};
-}
-
-// The read-back block into the caller's arrays, as collect(SigCall) does it: five words, the fourth signed.
-inline void collect(const LinkCall& c, const LinkMeta& M, const uint8_t* h_meta, int64_t* out, int32_t* status)
-{
-    const uint32_t* da = M.ans.in(h_meta);
-    const int32_t* rst = M.reg_status.in(h_meta);
-    for (int32_t g = 0; g < c.n_regions; ++g) {
-        int64_t* o = out + (size_t)LINK_ANSWER_WORDS * (size_t)g;
-        for (int k = 0; k < LINK_ANSWER_WORDS; ++k) o[k] = 0;
-        if (status[g]) continue;
-        if (rst[g] != REG_OK) { status[g] = rst[g]; continue; }
-        const uint32_t* a = da + (size_t)LINK_ANSWER_WORDS * (size_t)g;
-        for (int k = 0; k < LINK_ANSWER_WORDS; ++k) o[k] = k == 3 ? (int64_t)(int32_t)a[k] : (int64_t)a[k];
-    }
+    return layout_evidence(c, p, status, L, "vapor_bam_links_device: more than 2 GB of block data in one call (use smaller batches)", [&](LinkRegion& R, int32_t g) {
+        // (a region the plan refused keeps a record that asks nothing: no kernel reads it, its span_n is 0)
+        if (status[g]) { R = LinkRegion(); return; }
+        link_region_set(R, c.tid[g], c.regions + LINK_FIELDS * (size_t)g, c.filter_word);
+    }, std::max<size_t>(L.names_len, 1));
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
@@ -746,9 +649,7 @@ struct SupCall {
 
 inline Refusal check_args(const SupCall& c, const int64_t* out, const int32_t* status)
 {
-    if (c.n_regions < 0 || (c.n_regions && (!c.tid || !c.regions || !c.chunk_first || !out || !status)))
-        return {VAPOR_E_ARG, "vapor_bam_support_device: bad argument"};
-    return {};
+    return check_evidence_args(c, c.regions, out, status, "vapor_bam_support_device: bad argument");
 }
 
 // Whether a region's own fields are a question the readers answer: sig_region_ok of its first nine, a flank of 1..65535 and a
@@ -783,76 +684,17 @@ inline Refusal plan_spans(const SupCall& c, int32_t* status, SpanPlan& p)
                          [&](int32_t g, int*) { return sup_region_ok(c.tid[g], c.regions + SUP_FIELDS * (size_t)g); });
 }
 
-// Where each table of a support call lies in its metadata block: blocks, spans and regions go in; block status, the
-// SUP_ANSWER_WORDS words a region and the region status come back.
-struct SupMeta {
-    Table<BgzfBlk> blks;
-    Table<BamSpan> spans;
-    Table<SupRegion> regs;
-    Table<int32_t> blk_status;
-    Table<uint32_t> ans;                   // SUP_ANSWER_WORDS a region: alt_cg, alt_l, alt_r, ref_0, ref_1, cov_0, cov_1
-    Table<int32_t> reg_status;
-    size_t in_bytes = 0, bytes = 0;
-
-    SupMeta() = default;
-    SupMeta(int32_t n_regions, size_t n_blks, size_t n_spans)
-    {
-        const size_t nr = (size_t)std::max(n_regions, 1);
-        Carve m;
-        m.take(blks, std::max<size_t>(n_blks, 1));
-        m.take(spans, std::max<size_t>(n_spans, 1));
-        m.take(regs, nr);
-        in_bytes = m.off;
-        m.take(blk_status, std::max<size_t>(n_blks, 1));
-        m.take(ans, (size_t)SUP_ANSWER_WORDS * nr);
-        m.take(reg_status, nr);
-        bytes = m.off;
-    }
-    size_t back_bytes() const { return bytes - blk_status.off; }       // the host's block is the device's: [blk_status.off, bytes) comes back
-    template <typename B> B* back(B* block) const { return block + blk_status.off; }
-};
-
-struct SupLayout {
-    std::vector<BgzfBlk> blks;
-    std::vector<BamSpan> spans;
-    std::vector<SupRegion> regs;
-    size_t arena = 0;
-    SupMeta meta;
-    void fill(uint8_t* h_meta) const
-    {
-        if (!blks.empty()) memcpy(meta.blks.in(h_meta), blks.data(), sizeof(BgzfBlk) * blks.size());
-        if (!spans.empty()) memcpy(meta.spans.in(h_meta), spans.data(), sizeof(BamSpan) * spans.size());
-        memcpy(meta.regs.in(h_meta), regs.data(), sizeof(SupRegion) * regs.size());
-    }
-};
+// SUP_ANSWER_WORDS counts a region: alt_cg, alt_l, alt_r, ref_0, ref_1, cov_0, cov_1
+using SupLayout = EvidenceLayout<SupRegion, uint32_t, SUP_ANSWER_WORDS>;
+using SupMeta = SupLayout::Meta;
 
 inline Refusal layout(const SupCall& c, const SpanPlan& p, int32_t* status, SupLayout& L)
 {
-    if (const Refusal r = layout_of(c.n_regions, p, status, L.blks, L.spans, L.regs, &L.arena,
-                                    "vapor_bam_support_device: more than 2 GB of block data in one call (use smaller batches)", [&](SupRegion& R, int32_t g) {
-            const int64_t* f = c.regions + SUP_FIELDS * (size_t)g;
-            // (a region the plan refused keeps a record that asks nothing: no kernel reads it, its span_n is 0)
-            if (status[g]) { R = SupRegion(); return; }
-            sup_region_set(R, c.tid[g], f, c.filter_word);
-        }))
-        return r;
-    L.meta = SupMeta(c.n_regions, L.blks.size(), L.spans.size());
-    return {};
-}
-
-// The read-back block into the caller's arrays, as collect(SigCall) does it: seven counts.
-inline void collect(const SupCall& c, const SupMeta& M, const uint8_t* h_meta, int64_t* out, int32_t* status)
-{
-    const uint32_t* da = M.ans.in(h_meta);
-    const int32_t* rst = M.reg_status.in(h_meta);
-    for (int32_t g = 0; g < c.n_regions; ++g) {
-        int64_t* o = out + (size_t)SUP_ANSWER_WORDS * (size_t)g;
-        for (int k = 0; k < SUP_ANSWER_WORDS; ++k) o[k] = 0;
-        if (status[g]) continue;
-        if (rst[g] != REG_OK) { status[g] = rst[g]; continue; }
-        const uint32_t* a = da + (size_t)SUP_ANSWER_WORDS * (size_t)g;
-        for (int k = 0; k < SUP_ANSWER_WORDS; ++k) o[k] = (int64_t)a[k];
-    }
+    return layout_evidence(c, p, status, L, "vapor_bam_support_device: more than 2 GB of block data in one call (use smaller batches)", [&](SupRegion& R, int32_t g) {
+        // (a region the plan refused keeps a record that asks nothing: no kernel reads it, its span_n is 0)
+        if (status[g]) { R = SupRegion(); return; }
+        sup_region_set(R, c.tid[g], c.regions + SUP_FIELDS * (size_t)g, c.filter_word);
+    });
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------

@@ -479,25 +479,32 @@ class Engine:
             batch.name_keys = batch.read_name_keys(w)
         return kept_first, addr[:w], q0[:w], miss[:w], status[:n], batch
 
+    def _bam_evidence_device(self, entry, what, native_bam, tids, rows, width, out_words, out_dtype, chunk_first, chunks, names=None, label="regions"):
+        """One call of an evidence entry (vapor_bam_depth_device, _signature_device, _links_device, _support_device): rows is
+        (n, width) int64, the answer (n, out_words) of out_dtype; names, for the entry that takes one, the call's byte blob."""
+        fn = Engine._wide_entry(entry, what)
+        n = len(tids)
+        tids = np.ascontiguousarray(tids, dtype=np.int32)
+        rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        chunk_first = np.ascontiguousarray(chunk_first, dtype=np.int32)
+        chunks = np.ascontiguousarray(chunks, dtype=np.uint64).reshape(-1)
+        if len(rows) != width * n or len(chunk_first) != n + 1 or len(chunks) != 2 * int(chunk_first[-1]):
+            raise ValueError("%s / chunk_first / chunks do not describe %d regions" % (label, n))
+        out = np.zeros(out_words * max(n, 1), dtype=out_dtype)
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        vp = ctypes.c_void_p
+        blob = () if names is None else (ctypes.c_char_p(bytes(names)), len(bytes(names)))
+        L.check(fn(self._ctx, native_bam, n, tids.ctypes.data_as(vp), rows.ctypes.data_as(vp), *blob, chunk_first.ctypes.data_as(vp),
+                   chunks.ctypes.data_as(vp) if len(chunks) else None, out.ctypes.data_as(vp), status.ctypes.data_as(vp)))
+        return out[:out_words * n].reshape(n, out_words), status[:n]
+
     def bam_depth_device(self, native_bam, tids, bounds, chunk_first, chunks):
         """vapor_bam_depth_device (`--depth`): the read depth of many depth regions of an open BAM file on the
         device.  bounds: (n, 4) int64, chunk_first / chunks as in bam_chop_device.  Returns (cov, status): cov (n, 3) uint64,
         status per region - 0, or the code of a region that is the host route's (its sums are 0 then).  Nothing stays on the
         device.  NotImplementedError where the library has no such entry."""
-        fn = Engine._wide_entry("vapor_bam_depth_device", "device depth reader")
-        n = len(tids)
-        tids = np.ascontiguousarray(tids, dtype=np.int32)
-        bounds = np.ascontiguousarray(bounds, dtype=np.int64).reshape(-1)
-        chunk_first = np.ascontiguousarray(chunk_first, dtype=np.int32)
-        chunks = np.ascontiguousarray(chunks, dtype=np.uint64).reshape(-1)
-        if len(bounds) != 4 * n or len(chunk_first) != n + 1 or len(chunks) != 2 * int(chunk_first[-1]):
-            raise ValueError("bounds / chunk_first / chunks do not describe %d regions" % n)
-        cov = np.zeros(3 * max(n, 1), dtype=np.uint64)
-        status = np.zeros(max(n, 1), dtype=np.int32)
-        vp = ctypes.c_void_p
-        L.check(fn(self._ctx, native_bam, n, tids.ctypes.data_as(vp), bounds.ctypes.data_as(vp), chunk_first.ctypes.data_as(vp),
-                   chunks.ctypes.data_as(vp) if len(chunks) else None, cov.ctypes.data_as(vp), status.ctypes.data_as(vp)))
-        return cov[:3 * n].reshape(n, 3), status[:n]
+        return self._bam_evidence_device("vapor_bam_depth_device", "device depth reader", native_bam, tids, bounds, 4, 3, np.uint64, chunk_first, chunks,
+                                         label="bounds")
 
     def bam_signature_device(self, native_bam, tids, regions, chunk_first, chunks):
         """vapor_bam_signature_device (`--signatures`): split-read and CIGAR evidence of many signature regions
@@ -505,20 +512,7 @@ class Engine:
         (signature.FIELDS); chunk_first / chunks as in bam_chop_device.  Returns (out, status): out (n, 10) int64 - the six
         counts, then offset and count of each target's mode - and status per region: 0, or the code of a region that is the host
         route's (its words are 0 then).  Nothing stays on the device.  NotImplementedError where the library has no such entry."""
-        fn = Engine._wide_entry("vapor_bam_signature_device", "device signature reader")
-        n = len(tids)
-        tids = np.ascontiguousarray(tids, dtype=np.int32)
-        regions = np.ascontiguousarray(regions, dtype=np.int64).reshape(-1)
-        chunk_first = np.ascontiguousarray(chunk_first, dtype=np.int32)
-        chunks = np.ascontiguousarray(chunks, dtype=np.uint64).reshape(-1)
-        if len(regions) != 9 * n or len(chunk_first) != n + 1 or len(chunks) != 2 * int(chunk_first[-1]):
-            raise ValueError("regions / chunk_first / chunks do not describe %d regions" % n)
-        out = np.zeros(10 * max(n, 1), dtype=np.int64)
-        status = np.zeros(max(n, 1), dtype=np.int32)
-        vp = ctypes.c_void_p
-        L.check(fn(self._ctx, native_bam, n, tids.ctypes.data_as(vp), regions.ctypes.data_as(vp), chunk_first.ctypes.data_as(vp),
-                   chunks.ctypes.data_as(vp) if len(chunks) else None, out.ctypes.data_as(vp), status.ctypes.data_as(vp)))
-        return out[:10 * n].reshape(n, 10), status[:n]
+        return self._bam_evidence_device("vapor_bam_signature_device", "device signature reader", native_bam, tids, regions, 9, 10, np.int64, chunk_first, chunks)
 
     def bam_links_device(self, native_bam, tids, regions, chunk_first, chunks, names=b""):
         """vapor_bam_links_device (`--links`): split reads joined through their SA tags, many link regions of an
@@ -527,22 +521,8 @@ class Engine:
         bam_chop_device.  Returns (out, status): out (n, 5) int64 - n_clip, n_split, n_link, offset and count of the mode - and
         status per region: 0, or the code of a region that is the host route's (its words are 0 then).  Nothing stays on the
         device.  NotImplementedError where the library has no such entry."""
-        fn = Engine._wide_entry("vapor_bam_links_device", "device links reader")
-        n = len(tids)
-        tids = np.ascontiguousarray(tids, dtype=np.int32)
-        regions = np.ascontiguousarray(regions, dtype=np.int64).reshape(-1)
-        chunk_first = np.ascontiguousarray(chunk_first, dtype=np.int32)
-        chunks = np.ascontiguousarray(chunks, dtype=np.uint64).reshape(-1)
-        if len(regions) != 11 * n or len(chunk_first) != n + 1 or len(chunks) != 2 * int(chunk_first[-1]):
-            raise ValueError("regions / chunk_first / chunks do not describe %d regions" % n)
-        names = bytes(names)
-        out = np.zeros(5 * max(n, 1), dtype=np.int64)
-        status = np.zeros(max(n, 1), dtype=np.int32)
-        vp = ctypes.c_void_p
-        L.check(fn(self._ctx, native_bam, n, tids.ctypes.data_as(vp), regions.ctypes.data_as(vp), ctypes.c_char_p(names), len(names),
-                   chunk_first.ctypes.data_as(vp), chunks.ctypes.data_as(vp) if len(chunks) else None, out.ctypes.data_as(vp),
-                   status.ctypes.data_as(vp)))
-        return out[:5 * n].reshape(n, 5), status[:n]
+        return self._bam_evidence_device("vapor_bam_links_device", "device links reader", native_bam, tids, regions, 11, 5, np.int64, chunk_first, chunks,
+                                         names=names)
 
     def bam_support_device(self, native_bam, tids, regions, chunk_first, chunks):
         """vapor_bam_support_device (`--support`): alt and ref alignments of many support regions of an open BAM
@@ -550,20 +530,7 @@ class Engine:
         chunks as in bam_chop_device.  Returns (out, status): out (n, 7) int64 - alt_cg, alt_l, alt_r, ref_0, ref_1, cov_0,
         cov_1 - and status per region: 0, or the code of a region that is the host route's (its words are 0 then).  Nothing
         stays on the device.  NotImplementedError where the library has no such entry."""
-        fn = Engine._wide_entry("vapor_bam_support_device", "device support reader")
-        n = len(tids)
-        tids = np.ascontiguousarray(tids, dtype=np.int32)
-        regions = np.ascontiguousarray(regions, dtype=np.int64).reshape(-1)
-        chunk_first = np.ascontiguousarray(chunk_first, dtype=np.int32)
-        chunks = np.ascontiguousarray(chunks, dtype=np.uint64).reshape(-1)
-        if len(regions) != 11 * n or len(chunk_first) != n + 1 or len(chunks) != 2 * int(chunk_first[-1]):
-            raise ValueError("regions / chunk_first / chunks do not describe %d regions" % n)
-        out = np.zeros(7 * max(n, 1), dtype=np.int64)
-        status = np.zeros(max(n, 1), dtype=np.int32)
-        vp = ctypes.c_void_p
-        L.check(fn(self._ctx, native_bam, n, tids.ctypes.data_as(vp), regions.ctypes.data_as(vp), chunk_first.ctypes.data_as(vp),
-                   chunks.ctypes.data_as(vp) if len(chunks) else None, out.ctypes.data_as(vp), status.ctypes.data_as(vp)))
-        return out[:7 * n].reshape(n, 7), status[:n]
+        return self._bam_evidence_device("vapor_bam_support_device", "device support reader", native_bam, tids, regions, 11, 7, np.int64, chunk_first, chunks)
 
     def bam_last_stats(self) -> dict:
         """What this engine's last bam_chop_device did (vapor_bam_last_stats)."""
