@@ -13,6 +13,7 @@ import pytest
 
 import links_cases as LC
 import test_bamio as TB
+import test_modes_cpu as TM
 import test_signature_cpu as SC
 from vapor_amd import _lib as L
 from vapor_amd import bamio, cli, links, modes, pipeline, seqio, signature, synth
@@ -30,7 +31,8 @@ def test_the_parser_takes_links_on_bed_and_vcf():
     assert cli.build_parser().parse_args(BASE + ["--links"]).links is True
     assert cli.build_parser().parse_args(BASE + ["--links", "--min-mapq", "20", "--exclude-flags", "0x800", "--dedup-qname", "--bnd", "--no-figures"]).links is True
     m = modes.LINKS
-    assert m.name == "links" and m.chunk_payloads is cli._links_payloads and m.chunk_gens is None
+    assert m.name == "links" and m.chunk_payloads is not None and m.chunk_gens is None
+    assert tuple(TM.hook_payloads(m)) == links.TYPES          # the hook answers for the module's types
     assert (links.C, links.T, links.TOL_MAX, links.EXCLUDE) == (30, 50, 255, 0x704) and links.EXCLUDE is signature.EXCLUDE
     assert links.events is signature.events                  # the clip events are not stated a second time
 

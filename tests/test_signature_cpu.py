@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import test_bamio as TB
+import test_modes_cpu as TM
 from fake_engine import FakeEngine
 from vapor_amd import _lib as L
 from vapor_amd import bamio, cli, modes, pipeline, seqio, signature, synth
@@ -34,7 +35,8 @@ def test_the_parser_takes_signatures_on_bed_and_vcf():
     assert cli.build_parser().parse_args(BASE + ["--signatures", "--min-mapq", "20", "--exclude-flags", "0x800", "--dedup-qname", "--bnd",
                                                  "--no-figures"]).signatures is True
     m = modes.SIGNATURES
-    assert m.name == "signatures" and m.chunk_payloads is cli._signature_payloads and m.chunk_gens is None
+    assert m.name == "signatures" and m.chunk_payloads is not None and m.chunk_gens is None
+    assert tuple(TM.hook_payloads(m)) == signature.TYPES          # the hook answers for the module's types
     assert (signature.C, signature.T, signature.P, signature.EXCLUDE) == (C, T, P, 0x704)
 
 

@@ -38,7 +38,8 @@ def test_the_parser_takes_support_on_bed_and_vcf():
     assert cli.build_parser().parse_args(BASE + ["--support", "--min-mapq", "20", "--exclude-flags", "0x800", "--dedup-qname", "--bnd",
                                                  "--no-figures"]).support is True
     m = modes.SUPPORT
-    assert m.name == "support" and m.chunk_payloads is cli._support_payloads and m.chunk_gens is None
+    assert m.name == "support" and m.chunk_payloads is not None and m.chunk_gens is None
+    assert tuple(TM.hook_payloads(m)) == support.TYPES          # the hook answers for the module's types
     assert (support.F, support.G, support.T, support.C, support.P, support.EXCLUDE, support.ERR) == (F, G, T, C, P, 0x704, 0.05)
     assert support.FIELDS == signature.FIELDS + ("flank", "gmin") and len(support.FIELDS) == 11 and len(support.WORDS) == 7
     assert support.TYPES == signature.TYPES == ("DEL", "TANDUP", "INV", "INS") and (support.REF0, support.REF1) == (REF0, REF1)

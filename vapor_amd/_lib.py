@@ -262,22 +262,14 @@ def bind(L: ctypes.CDLL) -> ctypes.CDLL:
         L.vapor_bam_set_dedup.argtypes = [vp, ctypes.c_int32]
     if hasattr(L, "vapor_bam_batch_name_keys"):
         L.vapor_bam_batch_name_keys.argtypes = [vp, ctypes.c_int64, vp]
-    if hasattr(L, "vapor_bam_depth"):
-        L.vapor_bam_depth.argtypes = [vp, ctypes.c_int32, vp, ctypes.c_int32, vp, vp]
-    if hasattr(L, "vapor_bam_depth_device"):
-        L.vapor_bam_depth_device.argtypes = [vp, vp, ctypes.c_int32, vp, vp, vp, vp, vp, vp]
-    if hasattr(L, "vapor_bam_signature"):
-        L.vapor_bam_signature.argtypes = [vp, ctypes.c_int32, vp, ctypes.c_int32, vp, vp]
-    if hasattr(L, "vapor_bam_signature_device"):
-        L.vapor_bam_signature_device.argtypes = [vp, vp, ctypes.c_int32, vp, vp, vp, vp, vp, vp]
-    if hasattr(L, "vapor_bam_support"):
-        L.vapor_bam_support.argtypes = [vp, ctypes.c_int32, vp, ctypes.c_int32, vp, vp]
-    if hasattr(L, "vapor_bam_support_device"):
-        L.vapor_bam_support_device.argtypes = [vp, vp, ctypes.c_int32, vp, vp, vp, vp, vp, vp]
-    if hasattr(L, "vapor_bam_links"):
-        L.vapor_bam_links.argtypes = [vp, ctypes.c_int32, vp, vp, ctypes.c_int64, ctypes.c_int32, vp, vp]
-    if hasattr(L, "vapor_bam_links_device"):
-        L.vapor_bam_links_device.argtypes = [vp, vp, ctypes.c_int32, vp, vp, vp, ctypes.c_int64, vp, vp, vp, vp]
+    # the evidence readers: two signatures, the host entry's and the device entry's; the links entries take the
+    # blob of partner names and its length behind the rows
+    for kind in ("depth", "signature", "support", "links"):
+        names = [vp, ctypes.c_int64] if kind == "links" else []
+        for entry, head, tail in (("vapor_bam_" + kind, [vp, ctypes.c_int32, vp], [ctypes.c_int32, vp, vp]),
+                                  ("vapor_bam_%s_device" % kind, [vp, vp, ctypes.c_int32, vp, vp], [vp, vp, vp, vp])):
+            if hasattr(L, entry):
+                getattr(L, entry).argtypes = head + names + tail
     if hasattr(L, "vapor_plan_run_grid"):
         L.vapor_plan_run_grid.argtypes = [vp, i32p, f64p, f64p, i64p]
     for name in EXPORTS:

@@ -472,81 +472,48 @@ class BamFile:
         except Exception:       # noqa: BLE001
             pass
 
+    # The native host readers of the evidence modes: one region's words through the library's host
+    # entry; the .bai lookup stays here.  ValueError with the reader's message for a file that breaks a rule or a region the
+    # reader refuses.  region: the module's FIELDS (depth: the four bounds); links: then offset and length of the partner
+    # contig's name in `names`.
     def depth_native(self, tid: int, bounds, chunks=None):
-        """[cov0, cov1, cov2] of one depth region (`--depth`, DESIGN.md 4.19) through the library's host reader (vapor_bam_depth);
-        the .bai lookup stays here.  ValueError with the reader's message for a file that breaks a rule."""
-        from . import _lib
-        lib = _lib.load()
-        b = np.ascontiguousarray(bounds, dtype=np.int64)
-        ch = self.index.chunks(tid, int(b[0]), int(b[3])) if chunks is None else chunks
-        cov = np.zeros(3, dtype=np.uint64)
-        if not len(ch):
-            return [0, 0, 0]
-        flat = np.asarray(ch, dtype=np.uint64).reshape(-1)
-        tl = self._take_handle(lib)
-        try:
-            if lib.vapor_bam_depth(tl["native"], int(tid), b.ctypes.data, len(flat) // 2, flat.ctypes.data, cov.ctypes.data) != 0:
-                raise ValueError(lib.vapor_bam_last_error().decode())
-        finally:
-            with self._lock:
-                self._free.append(tl)
-        return [int(x) for x in cov]
+        from . import depth
+        return self._evidence_native(depth, tid, bounds, chunks)
 
     def signature_native(self, tid: int, region, chunks=None):
-        """The ten words of one signature region (`--signatures`; region: signature.FIELDS) through the library's
-        host reader (vapor_bam_signature); the .bai lookup stays here.  ValueError with the reader's message for a file that
-        breaks a rule or a region the reader refuses."""
-        from . import _lib
-        lib = _lib.load()
-        r = np.ascontiguousarray(region, dtype=np.int64)
-        ch = self.index.chunks(tid, int(r[0]), int(r[1])) if chunks is None and tid >= 0 and 0 <= r[0] <= r[1] else (chunks or [])
-        out = np.zeros(10, dtype=np.int64)
-        flat = np.asarray(ch, dtype=np.uint64).reshape(-1)
-        tl = self._take_handle(lib)
-        try:
-            if lib.vapor_bam_signature(tl["native"], int(tid), r.ctypes.data, len(flat) // 2, flat.ctypes.data if len(flat) else None,
-                                       out.ctypes.data) != 0:
-                raise ValueError(lib.vapor_bam_last_error().decode())
-        finally:
-            with self._lock:
-                self._free.append(tl)
-        return [int(x) for x in out]
+        from . import signature
+        return self._evidence_native(signature, tid, region, chunks)
 
     def support_native(self, tid: int, region, chunks=None):
-        """The seven words of one support region (`--support`; region: support.FIELDS) through the library's host
-        reader (vapor_bam_support); the .bai lookup stays here.  ValueError with the reader's message for a file that breaks a
-        rule or a region the reader refuses."""
-        from . import _lib
-        lib = _lib.load()
-        r = np.ascontiguousarray(region, dtype=np.int64)
-        ch = self.index.chunks(tid, int(r[0]), int(r[1])) if chunks is None and tid >= 0 and 0 <= r[0] <= r[1] else (chunks or [])
-        out = np.zeros(7, dtype=np.int64)
-        flat = np.asarray(ch, dtype=np.uint64).reshape(-1)
-        tl = self._take_handle(lib)
-        try:
-            if lib.vapor_bam_support(tl["native"], int(tid), r.ctypes.data, len(flat) // 2, flat.ctypes.data if len(flat) else None,
-                                     out.ctypes.data) != 0:
-                raise ValueError(lib.vapor_bam_last_error().decode())
-        finally:
-            with self._lock:
-                self._free.append(tl)
-        return [int(x) for x in out]
+        from . import support
+        return self._evidence_native(support, tid, region, chunks)
 
     def links_native(self, tid: int, region, chunks=None, names: bytes = b""):
-        """The five words of one link region (`--links`; region: links.FIELDS, then offset and length of the
-        partner contig's name in `names`) through the library's host reader (vapor_bam_links); the .bai lookup stays here.
-        ValueError with the reader's message for a file that breaks a rule or a region the reader refuses."""
+        from . import links
+        return self._evidence_native(links, tid, region, chunks, bytes(names))
+
+    def _evidence_native(self, module, tid: int, row, chunks=None, names=None):
+        """The four above from the module's reader surface (its ENTRIES, WINDOW, ZERO and DTYPE)."""
         from . import _lib
         lib = _lib.load()
-        r = np.ascontiguousarray(region, dtype=np.int64)
-        ch = self.index.chunks(tid, int(r[0]), int(r[1])) if chunks is None and tid >= 0 and 0 <= r[0] <= r[1] else (chunks or [])
-        out = np.zeros(5, dtype=np.int64)
+        r = np.ascontiguousarray(row, dtype=np.int64)
+        lo, hi = r[module.WINDOW[0]], r[module.WINDOW[1]]
+        if module.ASKED_WITHOUT_CHUNKS:
+            # the library refuses a region in its own words, so it is asked also when no chunk overlaps the region (a null
+            # pointer); the index only about a window it can look up
+            ch = self.index.chunks(tid, int(lo), int(hi)) if chunks is None and tid >= 0 and 0 <= lo <= hi else (chunks or [])
+        else:
+            # depth: the index is asked whatever the bounds, and a region it lists no chunk for is zeros without the library
+            ch = self.index.chunks(tid, int(lo), int(hi)) if chunks is None else chunks
+            if not len(ch):
+                return list(module.ZERO)
+        out = np.zeros(len(module.ZERO), dtype=module.DTYPE)
         flat = np.asarray(ch, dtype=np.uint64).reshape(-1)
-        names = bytes(names)
+        more = () if names is None else (names, len(names))
         tl = self._take_handle(lib)
         try:
-            if lib.vapor_bam_links(tl["native"], int(tid), r.ctypes.data, names, len(names), len(flat) // 2,
-                                   flat.ctypes.data if len(flat) else None, out.ctypes.data) != 0:
+            if getattr(lib, module.ENTRIES[0])(tl["native"], int(tid), r.ctypes.data, *more, len(flat) // 2,
+                                               flat.ctypes.data if len(flat) else None, out.ctypes.data) != 0:
                 raise ValueError(lib.vapor_bam_last_error().decode())
         finally:
             with self._lock:

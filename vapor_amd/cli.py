@@ -43,6 +43,9 @@ mode (vapor_amd.modes) or none, built once in _main and handed
 driver a locus takes), score_jobs (the payload gathered into Job.extra), the table writer and SF.vcf_vapor_modify.  An option
 that adds columns is a module with INFO, COLUMNS, pack, unpack and columns_many, a Mode made of it, and its branch in _simple_job.
 """
+# (The text above is also `vapor --help`'s description.)  The four evidence modes - --depth, --signatures, --links, --support - have
+# one chunk hook between them, _evidence_payloads, which reads a chunk's regions through the rule module's reader surface
+# (DESIGN.md 4.16), and the parser refuses every pair of mode options from one list and one table (MODE_OPTIONS, PAIR_REASONS).
 from __future__ import annotations
 
 import argparse
@@ -51,7 +54,7 @@ import sys
 from typing import List, Optional
 
 from . import dist as vdist
-from . import drivers, modes, pipeline
+from . import depth, drivers, links, modes, pipeline, signature, support
 from . import simple_function as SF
 from .finish import result_organize_ins, row_tail
 
@@ -703,152 +706,51 @@ def _both_ends_gens(jobs, rest, gens, engine):
 modes.BOTH_ENDS.chunk_gens = _both_ends_gens          # (the only mode that replaces a chunk's generators)
 
 
-def _depth_payloads(jobs, todo, engine):
-    """`--depth`: depth is not a property of a driver's result but of the chunk - the depth regions of all
-    its DEL and TANDUP loci (depth.regions of Job.spec, clipped to the backend's contig length), array route and drivers' route
-    alike, go to the read backend in one depth_many call per BAM file (a per-chromosome pattern: per file, summed).  Returns
-    {t: depth.Payload}; a locus of another type has none."""
-    from . import depth, seqio
-    be = seqio.get_backend()
-    by_bam = {}
-    for t in todo:
-        j = jobs[t]
-        if j.spec is not None and j.ctx is not None and j.spec[0] in depth.TYPES:
-            by_bam.setdefault((j.ctx[1], j.ctx[2]), []).append(t)
-    out = {}
-    for (bam, ref), ts in by_bam.items():
-        files = seqio.bam_in_decide(bam, None)
-        where, chroms, bounds = [], [], []
-        for t in ts:
-            name, chrom, s, e = jobs[t].spec[:4]
-            regs = depth.regions(name, [chrom, s, e], be.contig_length(files[0], ref, chrom) if files else 0)
-            where.append((len(bounds), regs))
-            chroms += [chrom] * len(regs)
-            bounds += regs
-        covs = [[0, 0, 0] for _ in bounds]
-        for f in files:
-            for k, c in enumerate(be.depth_many(engine, f, chroms, bounds)):
-                covs[k] = [x + int(y) for x, y in zip(covs[k], c)]
-        for t, (at, regs) in zip(ts, where):
-            p = depth.payload(jobs[t].spec[0], regs, covs[at:at + len(regs)])
-            out[t] = depth.Payload(p, jobs[t].spec[0]) if p is not None else None
-    return out
+def _evidence_payloads(module):
+    """The chunk hook of an evidence mode - `--depth`, `--signatures`, `--links`, `--support` (4.19 to 4.22) -
+    from its rule module's reader surface.  The evidence is not a property of a driver's result but of the chunk: the regions
+    of all its loci of module.TYPES (module.locus_regions of Job.spec - an INS is spelled [chrom, pos, length] - and, where
+    "BND" is among the types, of a breakend's scored view, Job.bnd), array route and drivers' route alike, every window clipped
+    to the backend's contig length, go to the read backend in one call of its module.MANY per BAM file; a per-chromosome
+    pattern: per file, merged by module.merge_words, the lengths asked of its first file (a pattern that matches none: length
+    0, zero answers).  The hook returns {t: module.Payload}; a locus of another type has none."""
+    def hook(jobs, todo, engine):
+        from . import seqio
+        be = seqio.get_backend()
+        by_bam = {}
+        for t in todo:
+            j = jobs[t]
+            if j.bnd is not None:
+                if "BND" in module.TYPES:
+                    by_bam.setdefault((j.bnd[1][1], j.bnd[1][2]), []).append((t, "BND", list(j.bnd[0])))
+            elif j.spec is not None and j.ctx is not None and j.spec[0] in module.TYPES:
+                name, chrom, s, e, ins_seq = j.spec[:5]
+                by_bam.setdefault((j.ctx[1], j.ctx[2]), []).append((t, name, [chrom, s, len(ins_seq)] if name == 'INS' else [chrom, s, e]))
+        out = {}
+        for (bam, ref), loci in by_bam.items():
+            files = seqio.bam_in_decide(bam, None)
+
+            def length_of(chrom):
+                return be.contig_length(files[0], ref, chrom) if files else 0
+            where, sent = [], []
+            for _t, name, locus in loci:
+                regs = module.locus_regions(name, locus, length_of)
+                where.append((len(sent), regs))
+                sent += regs
+            chroms, rows = [c for c, _f, _p in sent], [f for _c, f, _p in sent]
+            partners = ([p for _c, _f, p in sent],) if module.LINKED else ()
+            got = [list(module.ZERO) for _ in sent]
+            for f in files:
+                for k, a in enumerate(getattr(be, module.MANY)(engine, f, chroms, rows, *partners)):
+                    got[k] = module.merge_words(got[k], a)
+            for (t, name, locus), (at, regs) in zip(loci, where):
+                out[t] = module.locus_payload(name, locus, regs, got[at:at + len(regs)])
+        return out
+    return hook
 
 
-modes.DEPTH.chunk_payloads = _depth_payloads
-
-
-def _signature_payloads(jobs, todo, engine):
-    """`--signatures`: like depth, the evidence is the chunk's - the signature regions of all its DEL, TANDUP,
-    INV and INS loci (signature.regions of Job.spec, clipped to the backend's contig length) go to the read backend in one
-    signature_many call per BAM file (a per-chromosome pattern: per file, merged by signature.merge_words).  Returns
-    {t: signature.Payload}; a locus of another type has none."""
-    from . import seqio, signature
-    be = seqio.get_backend()
-    by_bam = {}
-    for t in todo:
-        j = jobs[t]
-        if j.spec is not None and j.ctx is not None and j.spec[0] in signature.TYPES:
-            by_bam.setdefault((j.ctx[1], j.ctx[2]), []).append(t)
-    out = {}
-    for (bam, ref), ts in by_bam.items():
-        files = seqio.bam_in_decide(bam, None)
-        where, chroms, regs_all, loci = [], [], [], []
-        for t in ts:
-            name, chrom, s, e, ins_seq = jobs[t].spec[:5]
-            locus = [chrom, s, len(ins_seq)] if name == 'INS' else [chrom, s, e]
-            regs = signature.regions(name, locus, be.contig_length(files[0], ref, chrom) if files else 0)
-            where.append((len(regs_all), regs))
-            loci.append(locus)
-            chroms += [chrom] * len(regs)
-            regs_all += regs
-        got = [[0] * 10 for _ in regs_all]
-        for f in files:
-            for k, a in enumerate(be.signature_many(engine, f, chroms, regs_all)):
-                got[k] = signature.merge_words(got[k], a)
-        for t, locus, (at, regs) in zip(ts, loci, where):
-            out[t] = signature.payload(jobs[t].spec[0], locus, regs, got[at:at + len(regs)])
-    return out
-
-
-modes.SIGNATURES.chunk_payloads = _signature_payloads
-
-
-def _links_payloads(jobs, todo, engine):
-    """`--links`: like the signatures, the evidence is the chunk's - the link regions of all its DEL, TANDUP and
-    INV loci (links.regions of Job.spec) and of its breakends (of Job.bnd's view), every window clipped to the backend's contig
-    length, go to the read backend in one links_many call per BAM file (a per-chromosome pattern: per file, merged by
-    links.merge_words; a region on a contig that a file lacks is zero there).  Returns {t: links.Payload}; a locus of another
-    type has none."""
-    from . import links, seqio
-    be = seqio.get_backend()
-    by_bam = {}
-    for t in todo:
-        j = jobs[t]
-        if j.bnd is not None:
-            by_bam.setdefault((j.bnd[1][1], j.bnd[1][2]), []).append((t, 'BND', list(j.bnd[0])))
-        elif j.spec is not None and j.ctx is not None and j.spec[0] in links.TYPES:
-            by_bam.setdefault((j.ctx[1], j.ctx[2]), []).append((t, j.spec[0], [j.spec[1], j.spec[2], j.spec[3]]))
-    out = {}
-    for (bam, ref), loci in by_bam.items():
-        files = seqio.bam_in_decide(bam, None)
-
-        def length_of(chrom):
-            return be.contig_length(files[0], ref, chrom) if files else 0
-        where, chroms, regs_all, partners = [], [], [], []
-        for _t, name, locus in loci:
-            left, right = links.regions(name, locus, length_of)
-            where.append((len(regs_all), len(left), len(right)))
-            for c, fields, pc in left + right:
-                chroms.append(c)
-                regs_all.append(fields)
-                partners.append(pc)
-        got = [[0] * 5 for _ in regs_all]
-        for f in files:
-            for k, a in enumerate(be.links_many(engine, f, chroms, regs_all, partners)):
-                got[k] = links.merge_words(got[k], a)
-        for (t, name, locus), (at, nl, nr) in zip(loci, where):
-            out[t] = links.payload(name, locus, got[at:at + nl], got[at + nl:at + nl + nr])
-    return out
-
-
-modes.LINKS.chunk_payloads = _links_payloads
-
-
-def _support_payloads(jobs, todo, engine):
-    """`--support`: like the signatures, the evidence is the chunk's - the support regions of all its DEL,
-    TANDUP, INV and INS loci (support.regions of Job.spec, clipped to the backend's contig length) go to the read backend in one
-    support_many call per BAM file (a per-chromosome pattern: per file, the words summed).  Returns {t: support.Payload}; a
-    locus of another type has none."""
-    from . import seqio, support
-    be = seqio.get_backend()
-    by_bam = {}
-    for t in todo:
-        j = jobs[t]
-        if j.spec is not None and j.ctx is not None and j.spec[0] in support.TYPES:
-            by_bam.setdefault((j.ctx[1], j.ctx[2]), []).append(t)
-    out = {}
-    for (bam, ref), ts in by_bam.items():
-        files = seqio.bam_in_decide(bam, None)
-        where, chroms, regs_all, loci = [], [], [], []
-        for t in ts:
-            name, chrom, s, e, ins_seq = jobs[t].spec[:5]
-            locus = [chrom, s, len(ins_seq)] if name == 'INS' else [chrom, s, e]
-            regs = support.regions(name, locus, be.contig_length(files[0], ref, chrom) if files else 0)
-            where.append((len(regs_all), regs))
-            loci.append(locus)
-            chroms += [chrom] * len(regs)
-            regs_all += regs
-        got = [[0] * 7 for _ in regs_all]
-        for f in files:
-            for k, a in enumerate(be.support_many(engine, f, chroms, regs_all)):
-                got[k] = support.merge_words(got[k], a)
-        for t, locus, (at, regs) in zip(ts, loci, where):
-            out[t] = support.payload(jobs[t].spec[0], locus, regs, got[at:at + len(regs)])
-    return out
-
-
-modes.SUPPORT.chunk_payloads = _support_payloads
+for _mode, _module in ((modes.DEPTH, depth), (modes.SIGNATURES, signature), (modes.LINKS, links), (modes.SUPPORT, support)):
+    _mode.chunk_payloads = _evidence_payloads(_module)
 
 
 last_timing: dict = {}          # of the most recent score_jobs: seconds scoring this rank's share, seconds in the gather
@@ -1058,6 +960,26 @@ def _int_in(name, lo, hi):
     return parse
 
 
+# "A run has one mode" (vapor_amd/modes.py), as the parser says it: the options that make a mode, in the order their refusals are
+# checked, and what a pair is told where that is more than the rule.  `--phase-vcf` is `--phased` with another source of tags:
+# the three older modes refuse it under that name (None: not under its own).
+MODE_OPTIONS = ('--refine', '--phase-vcf', '--phased', '--both-ends', '--depth', '--signatures', '--links', '--support')
+PAIR_REASONS = {
+    ('--phased', '--refine'): 'refinement per haplotype is not implemented',
+    ('--phased', '--phase-vcf'): None,
+    ('--both-ends', '--refine'): 'refined candidates are scored from one side',
+    ('--both-ends', '--phase-vcf'): None,
+    ('--both-ends', '--phased'): 'right-anchored reads are not read with their tags',
+    ('--depth', '--refine'): 'depth is measured over the called breakpoints',
+    ('--depth', '--phase-vcf'): 'depth is not measured per haplotype',
+    ('--depth', '--phased'): 'depth is not measured per haplotype',
+    ('--signatures', '--phase-vcf'): 'signatures are not counted per haplotype',
+    ('--signatures', '--phased'): 'signatures are not counted per haplotype',
+    ('--links', '--phase-vcf'): 'links are not counted per haplotype',
+    ('--links', '--phased'): 'links are not counted per haplotype',
+}
+
+
 def main(argv: Optional[List[str]] = None) -> int:
     held: list = []                      # (`--phase-vcf`, the read filter: the backend that carries the run's sites and its (Q, F), for as long as the run lasts)
     try:
@@ -1108,65 +1030,18 @@ def _main(argv, held) -> int:
         parser.error('--phase-sample names a sample of --phase-vcf: give that option too')
     if args.phase_vcf is not None:
         args.phased = True               # (the groups, the scoring and the columns are --phased's: only the tags' source differs)
-    if args.phased:
+    # a run has one mode: every later option of MODE_OPTIONS refuses the sub-commands it does not apply to, then each earlier one
+    given = dict(zip(MODE_OPTIONS, (refine is not None, args.phase_vcf is not None, args.phased, args.both_ends, args.depth, args.signatures,
+                                    args.links, args.support)))
+    for k, opt in enumerate(MODE_OPTIONS[2:], 2):           # (--refine's block stands above, --phase-vcf is --phased here)
+        if not given[opt]:
+            continue
         if cmd not in ('bed', 'vcf'):
-            parser.error('--phased applies to `vapor bed` and `vapor vcf`')
-        if refine is not None:
-            parser.error('--phased and --refine cannot be combined (refinement per haplotype is not implemented)')
-    if args.both_ends:
-        if cmd not in ('bed', 'vcf'):
-            parser.error('--both-ends applies to `vapor bed` and `vapor vcf`')
-        if refine is not None:
-            parser.error('--both-ends and --refine cannot be combined (refined candidates are scored from one side)')
-        if args.phased:
-            parser.error('--both-ends and --phased cannot be combined (right-anchored reads are not read with their tags)')
-    if args.depth:
-        if cmd not in ('bed', 'vcf'):
-            parser.error('--depth applies to `vapor bed` and `vapor vcf`')
-        if refine is not None:
-            parser.error('--depth and --refine cannot be combined (depth is measured over the called breakpoints)')
-        if args.phase_vcf is not None:
-            parser.error('--depth and --phase-vcf cannot be combined (depth is not measured per haplotype)')
-        if args.phased:
-            parser.error('--depth and --phased cannot be combined (depth is not measured per haplotype)')
-        if args.both_ends:
-            parser.error('--depth and --both-ends cannot be combined (a run has one mode)')
-    if args.signatures:
-        if cmd not in ('bed', 'vcf'):
-            parser.error('--signatures applies to `vapor bed` and `vapor vcf`')
-        if refine is not None:
-            parser.error('--signatures and --refine cannot be combined (a run has one mode)')
-        if args.phase_vcf is not None:
-            parser.error('--signatures and --phase-vcf cannot be combined (signatures are not counted per haplotype)')
-        if args.phased:
-            parser.error('--signatures and --phased cannot be combined (signatures are not counted per haplotype)')
-        if args.both_ends:
-            parser.error('--signatures and --both-ends cannot be combined (a run has one mode)')
-        if args.depth:
-            parser.error('--signatures and --depth cannot be combined (a run has one mode)')
-    if args.links:
-        if cmd not in ('bed', 'vcf'):
-            parser.error('--links applies to `vapor bed` and `vapor vcf`')
-        if refine is not None:
-            parser.error('--links and --refine cannot be combined (a run has one mode)')
-        if args.phase_vcf is not None:
-            parser.error('--links and --phase-vcf cannot be combined (links are not counted per haplotype)')
-        if args.phased:
-            parser.error('--links and --phased cannot be combined (links are not counted per haplotype)')
-        if args.both_ends:
-            parser.error('--links and --both-ends cannot be combined (a run has one mode)')
-        if args.depth:
-            parser.error('--links and --depth cannot be combined (a run has one mode)')
-        if args.signatures:
-            parser.error('--links and --signatures cannot be combined (a run has one mode)')
-    if args.support:
-        if cmd not in ('bed', 'vcf'):
-            parser.error('--support applies to `vapor bed` and `vapor vcf`')
-        for on, what in ((refine is not None, '--refine'), (args.phase_vcf is not None, '--phase-vcf'), (args.phased, '--phased'),
-                         (args.both_ends, '--both-ends'), (args.depth, '--depth'), (args.signatures, '--signatures'),
-                         (args.links, '--links')):
-            if on:
-                parser.error('--support and %s cannot be combined (a run has one mode)' % what)
+            parser.error('%s applies to `vapor bed` and `vapor vcf`' % opt)
+        for other in MODE_OPTIONS[:k]:
+            why = PAIR_REASONS.get((opt, other), 'a run has one mode')
+            if given[other] and why is not None:
+                parser.error('%s and %s cannot be combined (%s)' % (opt, other, why))
     if args.phase_vcf is not None:
         # (every rank reads the VCF itself; the sites ride on the backend the reads are taken through)
         from . import phase as ph

@@ -2,7 +2,8 @@
 line of evidence beside the dot plots of the reads that cross a breakpoint.  This module is the rule - the intervals of a locus
 (`regions`), what a record covers (`cover`), the fold change and its verdict (`fold`) - and the mode's surface for cli.py and
 the VCF writer (INFO, COLUMNS, pack, unpack, columns_many).  The readers that apply the rule to a BAM file are
-seqio.*.depth_many: bam_depth_kernel on the device, vapor_bam_depth on the host, `cover` over bamio's records."""
+seqio.*.depth_many: bam_depth_kernel on the device, vapor_bam_depth on the host, `cover` over bamio's records; what they need to
+know of this module is its reader surface (ROW_WIDTH .. locus_payload below)."""
 from __future__ import annotations
 
 from typing import List, Optional
@@ -20,6 +21,14 @@ INFO = (
     ("VaPoR_DSUP", "Integer", "1", "1 if the fold change supports the call, below 0.7 for DEL and above 1.3 for TANDUP, else 0 (--depth)"),
 )
 COLUMNS = tuple(i[0] for i in INFO)
+
+# The reader surface: a region's row as the readers take it - its integers, the indices of its walk window -, the answer of a
+# region without records and the answer's type; the library's host and device entry, the Engine's method, the BamFile's and the
+# backends'.  LINKED: whether a region has a partner contig and its records carry FLAG and the SA value.  ASKED_WITHOUT_CHUNKS:
+# whether the native reader asks the library about a region no chunk overlaps - here it does not: such a region is zeros.
+ROW_WIDTH, WINDOW, ZERO, DTYPE = 4, (0, 3), (0, 0, 0), "uint64"
+ENTRIES, DEVICE, NATIVE, MANY = ("vapor_bam_depth", "vapor_bam_depth_device"), "bam_depth_device", "depth_native", "depth_many"
+LINKED = ASKED_WITHOUT_CHUNKS = False
 
 _COVERS = (1, 0, 0, 0, 0, 0, 0, 1, 1)        # M I D N S H P = X: covers the reference bases it spans
 _ADVANCES = (1, 0, 1, 1, 0, 0, 0, 1, 1)      # ... moves the reference cursor
@@ -69,6 +78,27 @@ def cover(records, bounds) -> list:
             if _ADVANCES[code]:
                 cur += n
     return cov
+
+
+def statement(records, row, partner=None, min_mapq=0) -> list:
+    """The Python statement the readers are held to: a region's words from its records (pos, ops)."""
+    return cover(records, row)
+
+
+def merge_words(a, b) -> list:
+    """The answers of one region from two files of a per-chromosome pattern: summed."""
+    return [int(x) + int(y) for x, y in zip(a, b)]
+
+
+def locus_regions(svtype: str, locus, length_of) -> list:
+    """A locus's regions as the chunk hook sends them: [(contig, bounds, None)]; length_of(contig): the contig's length."""
+    return [(locus[0], b, None) for b in regions(svtype, locus, length_of(locus[0]))] if svtype in TYPES else []
+
+
+def locus_payload(svtype: str, locus, regs, answers) -> Optional["Payload"]:
+    """The locus's Payload from locus_regions' list and the regions' words; None for a locus that is not measured."""
+    p = payload(svtype, [b for _c, b, _p in regs], answers)
+    return Payload(p, svtype) if p is not None else None
 
 
 def parse_cigar(text: str) -> list:

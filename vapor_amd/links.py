@@ -32,6 +32,13 @@ INFO = (
 )
 COLUMNS = tuple(i[0] for i in INFO)
 
+# The reader surface (as depth.py's).  A row is FIELDS, then offset and length of the partner contig's name in the call's blob of
+# names.  LINKED: a region has a partner contig, and its records carry FLAG and the SA value (bamio's fetch_links, sa_of_sam of a
+# SAM line).  ASKED_WITHOUT_CHUNKS: the library refuses a region in its own words, also one no chunk overlaps.
+ROW_WIDTH, WINDOW, ZERO, DTYPE = len(FIELDS) + 2, (0, 1), (0,) * 5, "int64"
+ENTRIES, DEVICE, NATIVE, MANY = ("vapor_bam_links", "vapor_bam_links_device"), "bam_links_device", "links_native", "links_many"
+LINKED = ASKED_WITHOUT_CHUNKS = True
+
 _OPS = b"MIDNSHP=X"
 _ADVANCE = (1, 0, 1, 1, 0, 0, 0, 1, 1)
 
@@ -176,6 +183,24 @@ def answer(records, fields, partner, min_mapq: int = 0):
 def words(ans) -> list:
     """An answer as the native readers give it: n_clip, n_split, n_link, then offset and count of the mode."""
     return [ans[0], ans[1], ans[2], ans[4][0], ans[4][1]]
+
+
+def statement(records, row, partner, min_mapq=0) -> list:
+    """The Python statement the readers are held to: a region's words from its records (pos, ops, flag, sa); row: FIELDS, and
+    whatever a reader keeps behind them."""
+    return words(answer(records, row[:len(FIELDS)], partner, min_mapq))
+
+
+def locus_regions(svtype: str, locus, length_of) -> list:
+    """A locus's regions as the chunk hook sends them: `regions`' left side, then its right - as many each."""
+    left, right = regions(svtype, locus, length_of)
+    return left + right
+
+
+def locus_payload(svtype: str, locus, regs, answers) -> Optional["Payload"]:
+    """The locus's Payload from locus_regions' list and the regions' words: the first half is the left side's."""
+    half = len(regs) // 2
+    return payload(svtype, locus, answers[:half], answers[half:])
 
 
 def merge_words(a, b) -> list:

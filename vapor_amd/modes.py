@@ -1,7 +1,8 @@
 """The run modes of `vapor bed | vcf` that append columns to every row: `--refine`, `--phased` (and `--phase-vcf`, the same mode
 with another source of tags), `--both-ends`, `--depth`, `--signatures`, `--links` and `--support`.  At most one holds for a run (the parser refuses every pair); None is the plain
 run.  A Mode is everything cli.py and the VCF writer need to know about one; what the option computes stays in
-its own module - refine.py, phase.py, bothends.py, depth.py, signature.py, links.py, support.py - which gives the mode its columns and the way they travel between ranks."""
+its own module - refine.py, phase.py, bothends.py, depth.py, signature.py, links.py, support.py - which gives the mode its columns and the way they travel between ranks;
+the last four also say how their regions are read (their reader surface), and the parser states the rule once (cli.MODE_OPTIONS)."""
 from __future__ import annotations
 
 from . import bothends, depth, links, phase, signature, support
@@ -16,7 +17,8 @@ class Mode:
     payloads.  `phased`: the drivers and the array route run with phased=True.  `chunk_gens`: None, or a hook
     (jobs, rest, gens, engine) -> (gens, held) that may replace a chunk's generators before they run (cli._both_ends_gens).
     `chunk_payloads`: None, or a hook (jobs, todo, engine) -> {t: payload} for a mode whose payload is not a property of a
-    driver's result but of the chunk: called once for all of a chunk's loci, whatever route scores them (cli._depth_payloads, cli._signature_payloads, cli._links_payloads, cli._support_payloads).
+    driver's result but of the chunk: called once for all of a chunk's loci, whatever route scores them - the four evidence modes'
+    is one function over their module's reader surface (cli._evidence_payloads).
     `--refine`'s own: `margin_step` = (M, T), and `ci_of` (cli.vcf_ci_readin: the bounds of a VCF record's candidates)."""
     chunk_gens = None
     chunk_payloads = None

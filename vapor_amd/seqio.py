@@ -24,7 +24,41 @@ from typing import Iterable, List, Optional
 _backend = None
 
 
-class SamtoolsCLI:
+class _EvidenceMany:
+    """The four evidence readers of a backend (`--depth`, `--signatures`, `--links`, `--support`) by
+    their public names: per region (chroms[g], rows[g]: the module's FIELDS; depth: the four bounds; links: partners[g] the
+    partner contig's name) the module's words - depth [cov0, cov1, cov2], signatures ten, links five, support seven.  Each
+    hands its rule module to the backend's one _evidence_many(module, engine, bam, chroms, rows, partners=None), which reads
+    the regions as the module's reader surface says and holds them to module.statement."""
+
+    def depth_many(self, engine, bam: str, chroms, bounds):
+        from . import depth
+        return self._evidence_many(depth, engine, bam, chroms, bounds)
+
+    def signature_many(self, engine, bam: str, chroms, regions):
+        from . import signature
+        return self._evidence_many(signature, engine, bam, chroms, regions)
+
+    def links_many(self, engine, bam: str, chroms, regions, partners):
+        from . import links
+        return self._evidence_many(links, engine, bam, chroms, regions, partners)
+
+    def support_many(self, engine, bam: str, chroms, regions):
+        from . import support
+        return self._evidence_many(support, engine, bam, chroms, regions)
+
+
+def _sam_records(module, fields_of_lines) -> list:
+    """The alignment lines of `view` as module.statement's records: (POS, operations), with FLAG and the SA field for a module
+    whose records are LINKED."""
+    from .depth import parse_cigar
+    if not module.LINKED:
+        return [(int(f[3]), parse_cigar(f[5])) for f in fields_of_lines]
+    from .links import sa_of_sam
+    return [(int(f[3]), parse_cigar(f[5]), int(f[1]), sa_of_sam(f[11:])) for f in fields_of_lines]
+
+
+class SamtoolsCLI(_EvidenceMany):
     """Runs the samtools binary; raises if it is missing instead of yielding nothing."""
 
     # `--min-mapq`, `--exclude-flags` (DESIGN.md 4.17): (min_mapq, exclude_flags) - a record is filtered iff MAPQ < min_mapq or
@@ -64,61 +98,17 @@ class SamtoolsCLI:
             cache[ref] = {f[0]: int(f[1]) for f in (ln.split("\t") for ln in self.fai_lines(ref)) if len(f) > 1}
         return cache[ref].get(chrom, 0)
 
-    def depth_many(self, engine, bam: str, chroms, bounds):
-        """[cov0, cov1, cov2] per depth region (chroms[g], bounds[g] = (b0, b1, b2, b3)): depth.cover over POS and CIGAR of the
-        alignment lines of `view`, filtered where they are read (_sam_fields) with depth.EXCLUDE among the excluded flags."""
-        from . import depth
+    def _evidence_many(self, module, engine, bam: str, chroms, rows, partners=None):
+        """module.statement over the alignment lines of `view`, filtered where they are read (_sam_fields) with module.EXCLUDE
+        among the excluded flags; the entries' mapQ (links) meets the filter's minimum MAPQ."""
+        lo, hi = module.WINDOW
         out = []
-        for chrom, b in zip(chroms, bounds):
-            if not b[3] > b[0]:
-                out.append([0, 0, 0])
+        for g, (chrom, row) in enumerate(zip(chroms, rows)):
+            if not row[hi] > row[lo]:
+                out.append(list(module.ZERO))
                 continue
-            recs = [(int(f[3]), depth.parse_cigar(f[5])) for f in _sam_fields(self, bam, chrom, int(b[0]) + 1, int(b[3]), depth.EXCLUDE)]
-            out.append(depth.cover(recs, b))
-        return out
-
-    def signature_many(self, engine, bam: str, chroms, regions):
-        """The ten words per signature region (`--signatures`; chroms[g], regions[g] = signature.FIELDS):
-        signature.answer over POS and CIGAR of the alignment lines of `view`, filtered where they are read (_sam_fields) with
-        signature.EXCLUDE among the excluded flags."""
-        from . import signature
-        out = []
-        for chrom, rg in zip(chroms, regions):
-            if not rg[1] > rg[0]:
-                out.append([0] * 10)
-                continue
-            recs = [(int(f[3]), signature.parse_cigar(f[5])) for f in _sam_fields(self, bam, chrom, int(rg[0]) + 1, int(rg[1]), signature.EXCLUDE)]
-            out.append(signature.words(signature.answer(recs, rg)))
-        return out
-
-    def support_many(self, engine, bam: str, chroms, regions):
-        """The seven words per support region (`--support`; chroms[g], regions[g] = support.FIELDS):
-        support.answer over POS and CIGAR of the alignment lines of `view`, filtered where they are read (_sam_fields) with
-        support.EXCLUDE among the excluded flags."""
-        from . import support
-        out = []
-        for chrom, rg in zip(chroms, regions):
-            if not rg[1] > rg[0]:
-                out.append([0] * 7)
-                continue
-            recs = [(int(f[3]), support.parse_cigar(f[5])) for f in _sam_fields(self, bam, chrom, int(rg[0]) + 1, int(rg[1]), support.EXCLUDE)]
-            out.append(support.answer(recs, rg))
-        return out
-
-    def links_many(self, engine, bam: str, chroms, regions, partners):
-        """The five words per link region (`--links`; chroms[g], regions[g] = links.FIELDS, partners[g] the
-        partner contig's name): links.answer over POS, CIGAR, FLAG and the SA field of the alignment lines of `view`, filtered
-        where they are read (_sam_fields) with links.EXCLUDE among the excluded flags; the entries' mapQ meets the filter's
-        minimum MAPQ."""
-        from . import links, signature
-        out = []
-        for chrom, rg, pc in zip(chroms, regions, partners):
-            if not rg[1] > rg[0]:
-                out.append([0] * 5)
-                continue
-            recs = [(int(f[3]), signature.parse_cigar(f[5]), int(f[1]), links.sa_of_sam(f[11:]))
-                    for f in _sam_fields(self, bam, chrom, int(rg[0]) + 1, int(rg[1]), links.EXCLUDE)]
-            out.append(links.words(links.answer(recs, rg, pc, getattr(self, "read_filter", (0, 0))[0])))
+            recs = _sam_records(module, _sam_fields(self, bam, chrom, int(row[lo]) + 1, int(row[hi]), module.EXCLUDE))
+            out.append(module.statement(recs, row, partners[g] if partners is not None else None, getattr(self, "read_filter", (0, 0))[0]))
         return out
 
 
@@ -656,81 +646,38 @@ class InProcessBam(SamtoolsHybrid):
         t = b.tid.get(chrom)
         return int(b.refs[t][1]) if t is not None else 0
 
-    def depth_many(self, engine, bam: str, chroms, bounds):
-        """[cov0, cov1, cov2] per depth region (`--depth`; chroms[g], bounds[g] = (b0, b1, b2, b3)) of a BAM
-        file.  The regions go to the device in groups by compressed size, like chop_many_device's, a group the library refuses
-        for its size ("in one call") in halves (vapor_bam_depth_device: bam_depth_kernel, one wavefront a region); a region the
-        device hands back with a status, and every region with VAPOR_BAM_DEVICE=0 or without a device reader, goes to the native
-        host reader (vapor_bam_depth).  A library without the entries, one without the read filter the file carries, or
-        VAPOR_BAM_NATIVE=0: the Python statement, depth.cover over fetch_raw with depth.EXCLUDE added to the excluded flags.
-        `engine`: an Engine, or None for the one of pipeline.get_engine() when the device is asked."""
-        from . import depth
-
-        def python(b, chrom, bd):
-            recs = [(r[1], r[2]) for r in b.fetch_raw(chrom, int(bd[0]) + 1, int(bd[3]), exclude_more=depth.EXCLUDE)]
-            return depth.cover(recs, bd)
-        return self._regions_many(engine, bam, chroms, bounds, 4, 0, 3, [0, 0, 0], ("vapor_bam_depth", "vapor_bam_depth_device"),
-                                  "bam_depth_device", "depth_native", python)
-
-    def signature_many(self, engine, bam: str, chroms, regions):
-        """The ten words per signature region (`--signatures`; chroms[g], regions[g] = signature.FIELDS) of a BAM
-        file: the six counts, then offset and count of each target's mode.  The routes are depth_many's: the device in groups
-        (vapor_bam_signature_device: bam_signature_kernel, one wavefront a region), a region it hands back and every region with
-        VAPOR_BAM_DEVICE=0 to the native host reader (vapor_bam_signature), and the Python statement - signature.answer over
-        fetch_raw with signature.EXCLUDE added to the excluded flags - for a library without the entries or VAPOR_BAM_NATIVE=0."""
-        from . import signature
-
-        def python(b, chrom, rg):
-            recs = [(r[1], r[2]) for r in b.fetch_raw(chrom, int(rg[0]) + 1, int(rg[1]), exclude_more=signature.EXCLUDE)]
-            return signature.words(signature.answer(recs, rg))
-        return self._regions_many(engine, bam, chroms, regions, len(signature.FIELDS), 0, 1, [0] * 10,
-                                  ("vapor_bam_signature", "vapor_bam_signature_device"), "bam_signature_device", "signature_native", python)
-
-    def links_many(self, engine, bam: str, chroms, regions, partners):
-        """The five words per link region (`--links`; chroms[g], regions[g] = links.FIELDS, partners[g] the
-        partner contig's name) of a BAM file: n_clip, n_split, n_link, then offset and count of the mode.  The routes are
-        depth_many's: the device in groups (vapor_bam_links_device: bam_link_kernel, one wavefront a region), a region it hands
-        back - one with a record whose aux area is malformed among them - and every region with VAPOR_BAM_DEVICE=0 to the native
-        host reader (vapor_bam_links), and the Python statement - links.answer over fetch_links with links.EXCLUDE added to the
-        excluded flags - for a library without the entries or VAPOR_BAM_NATIVE=0.  The native readers do not know contig names:
-        the partners' go as one byte blob, every name once, and each region's row ends in its name's offset and length."""
-        from . import links
-        where, blob, rows = {}, bytearray(), []
-        for rg, pc in zip(regions, partners):
-            name = pc.encode("latin-1") if isinstance(pc, str) else bytes(pc)
-            if name not in where:
-                where[name] = len(blob)
-                blob += name
-            rows.append([int(v) for v in rg] + [where[name], len(name)])
-        names = bytes(blob)
+    def _evidence_many(self, module, engine, bam: str, chroms, rows, partners=None):
+        """The routes of the evidence readers over a BAM file.  The regions go to the device in groups by compressed size, like
+        chop_many_device's, a group the library refuses for its size ("in one call") in halves (module.ENTRIES[1] through the
+        Engine's module.DEVICE: one wavefront a region); a region the device hands back with a status - for links one with a
+        record whose aux area is malformed among them -, and every region with VAPOR_BAM_DEVICE=0 or without a device reader,
+        goes to the native host reader (the BamFile's module.NATIVE).  A library without the entries, one without the read
+        filter the file carries, or VAPOR_BAM_NATIVE=0: the Python statement, module.statement over fetch_raw (LINKED:
+        fetch_links) with module.EXCLUDE added to the excluded flags.  A region on an unknown contig or with an empty walk
+        window [row[lo], row[hi]) is module.ZERO.  `engine`: an Engine, or None for the one of pipeline.get_engine() when the
+        device is asked.  partners (links): the native readers do not know contig names - the partners' go as one byte blob,
+        every name once, handed to the device and the native entry as their `names`, and each region's row ends in its
+        name's offset and length."""
+        width, (lo, hi) = module.ROW_WIDTH, module.WINDOW
+        more = {}
+        if partners is not None:
+            where, blob, rows = {}, bytearray(), [list(r) for r in rows]
+            for row, pc in zip(rows, partners):
+                name = pc.encode("latin-1") if isinstance(pc, str) else bytes(pc)
+                if name not in where:
+                    where[name] = len(blob)
+                    blob += name
+                row += [where[name], len(name)]
+            more["names"] = names = bytes(blob)
 
         def python(b, chrom, row):
-            recs = b.fetch_links(chrom, int(row[0]) + 1, int(row[1]), exclude_more=links.EXCLUDE)
-            return links.words(links.answer(recs, row[:9], names[int(row[9]):int(row[9]) + int(row[10])], b.read_filter[0]))
-        return self._regions_many(engine, bam, chroms, rows, len(links.FIELDS) + 2, 0, 1, [0] * 5, ("vapor_bam_links", "vapor_bam_links_device"),
-                                  "bam_links_device", "links_native", python, names=names)
-
-    def support_many(self, engine, bam: str, chroms, regions):
-        """The seven words per support region (`--support`; chroms[g], regions[g] = support.FIELDS) of a BAM
-        file: alt_cg, alt_l, alt_r, ref_0, ref_1, cov_0, cov_1.  The routes are depth_many's: the device in groups
-        (vapor_bam_support_device: bam_support_kernel, one wavefront a region), a region it hands back and every region with
-        VAPOR_BAM_DEVICE=0 to the native host reader (vapor_bam_support), and the Python statement - support.answer over
-        fetch_raw with support.EXCLUDE added to the excluded flags - for a library without the entries or VAPOR_BAM_NATIVE=0."""
-        from . import support
-
-        def python(b, chrom, rg):
-            recs = [(r[1], r[2]) for r in b.fetch_raw(chrom, int(rg[0]) + 1, int(rg[1]), exclude_more=support.EXCLUDE)]
-            return support.answer(recs, rg)
-        return self._regions_many(engine, bam, chroms, regions, len(support.FIELDS), 0, 1, [0] * 7,
-                                  ("vapor_bam_support", "vapor_bam_support_device"), "bam_support_device", "support_native", python)
-
-    def _regions_many(self, engine, bam, chroms, rows, width, lo, hi, zero, entries, device, native, python, names=None):
-        """The routes of depth_many, signature_many, links_many and support_many.  rows[g]: the `width` integers of region g, its walk window
-        [rows[g][lo], rows[g][hi]); zero: the answer of a region without records (an unknown contig, an empty window);
-        entries: the library's host and device entry; device: the Engine's method, native: the BamFile's, python(b, chrom, row)
-        the Python statement.  names (links_many): a byte blob the rows point into, handed to the device and the native entry
-        as their `names`."""
-        more = {} if names is None else {"names": names}
+            if module.LINKED:
+                recs = b.fetch_links(chrom, int(row[lo]) + 1, int(row[hi]), exclude_more=module.EXCLUDE)
+            else:
+                recs = [(r[1], r[2]) for r in b.fetch_raw(chrom, int(row[lo]) + 1, int(row[hi]), exclude_more=module.EXCLUDE)]
+            partner = names[int(row[-2]):int(row[-2]) + int(row[-1])] if partners is not None else None
+            return module.statement(recs, row, partner, b.read_filter[0])
+        zero, entries, device, native = module.ZERO, module.ENTRIES, module.DEVICE, module.NATIVE
         import numpy as np
         from . import _lib
         n = len(chroms)
@@ -859,7 +806,7 @@ class InProcessBam(SamtoolsHybrid):
         return self._fasta(ref).fetch(chrom, start, end)
 
 
-class MemorySamtools:
+class MemorySamtools(_EvidenceMany):
     # cli.score_jobs may score several chunks at once, a thread each: the native chop writes to arrays of the call's own
     # (not with VAPOR_MEMORY_CHOP=records: that path's CIGAR walk answers into one module-level array, see cli._chunk_threads_ok)
     chunk_threads_ok = True
@@ -1148,103 +1095,38 @@ class MemorySamtools:
         """(`--depth`) the world's contig; 0 for one it does not have."""
         return len(self.world.contigs[chrom]) if chrom in self.world.contigs else 0
 
-    def depth_many(self, engine, bam: str, chroms, bounds):
-        """[cov0, cov1, cov2] per depth region (`--depth`) from the world's records that pass the read filter
-        with depth.EXCLUDE among its flags: depth.cover over (POS, operations), every CIGAR text parsed once per record list."""
-        from . import depth
-        from .bamio import record_passes
-        q, f = self.read_filter
-        f |= depth.EXCLUDE
-        cache = self.__dict__.setdefault("_depth_cache", {})
-        out = []
-        for chrom, b in zip(chroms, bounds):
-            recs = self.world.reads.get(chrom, ())
-            got = cache.get(id(recs))
-            if got is None or got[0] is not recs or got[1] != len(recs):
-                got = (recs, len(recs), [depth.parse_cigar(r.cigar) for r in recs])
-                if getattr(self.world, "cache_ok", True):
-                    if len(cache) > 200000:
-                        cache.clear()
-                    cache[id(recs)] = got
-            b0, b3 = int(b[0]), int(b[3])
-            out.append(depth.cover([(r.pos, ops) for r, ops in zip(recs, got[2])
-                                    if b0 < b3 and r.pos - 1 < b3 and record_passes(r.mapq, r.flag, q, f)], b))
-        return out
+    def _cigar_ops(self, recs) -> list:
+        """The operations of every record of one of the world's record lists, each CIGAR text parsed once per list."""
+        from .depth import parse_cigar
+        cache = self.__dict__.setdefault("_cigar_cache", {})
+        got = cache.get(id(recs))
+        if got is None or got[0] is not recs or got[1] != len(recs):
+            got = (recs, len(recs), [parse_cigar(r.cigar) for r in recs])
+            if getattr(self.world, "cache_ok", True):
+                if len(cache) > 200000:
+                    cache.clear()
+                cache[id(recs)] = got
+        return got[2]
 
-    def signature_many(self, engine, bam: str, chroms, regions):
-        """The ten words per signature region (`--signatures`) from the world's records that pass the read filter
-        with signature.EXCLUDE among its flags: signature.answer over (POS, operations) of the records that start before w3 and
-        do not end before w0, every CIGAR text parsed once per record list."""
-        from . import signature
+    def _evidence_many(self, module, engine, bam: str, chroms, rows, partners=None):
+        """module.statement over the world's records that pass the read filter with module.EXCLUDE among its flags and start
+        before the end of the region's walk window: (POS, operations), and for a module whose records are LINKED FLAG and the
+        SA value - the record's `SA` tag when that is a string."""
         from .bamio import record_passes
         q, f = self.read_filter
-        f |= signature.EXCLUDE
-        cache = self.__dict__.setdefault("_depth_cache", {})
+        f |= module.EXCLUDE
+        lo, hi = module.WINDOW
         out = []
-        for chrom, rg in zip(chroms, regions):
+        for g, (chrom, row) in enumerate(zip(chroms, rows)):
             recs = self.world.reads.get(chrom, ())
-            got = cache.get(id(recs))
-            if got is None or got[0] is not recs or got[1] != len(recs):
-                got = (recs, len(recs), [signature.parse_cigar(r.cigar) for r in recs])
-                if getattr(self.world, "cache_ok", True):
-                    if len(cache) > 200000:
-                        cache.clear()
-                    cache[id(recs)] = got
-            w0, w3 = int(rg[0]), int(rg[1])
-            out.append(signature.words(signature.answer([(r.pos, ops) for r, ops in zip(recs, got[2])
-                                                         if w0 < w3 and r.pos - 1 < w3 and record_passes(r.mapq, r.flag, q, f)], rg)))
-        return out
-
-    def links_many(self, engine, bam: str, chroms, regions, partners):
-        """The five words per link region (`--links`) from the world's records that pass the read filter with
-        links.EXCLUDE among its flags: links.answer over (POS, operations, FLAG, SA) of the records that start before w3, the SA
-        value the record's `SA` tag when that is a string."""
-        from . import links, signature
-        from .bamio import record_passes
-        q, f = self.read_filter
-        f |= links.EXCLUDE
-        cache = self.__dict__.setdefault("_depth_cache", {})
-        out = []
-        for chrom, rg, pc in zip(chroms, regions, partners):
-            recs = self.world.reads.get(chrom, ())
-            got = cache.get(id(recs))
-            if got is None or got[0] is not recs or got[1] != len(recs):
-                got = (recs, len(recs), [signature.parse_cigar(r.cigar) for r in recs])
-                if getattr(self.world, "cache_ok", True):
-                    if len(cache) > 200000:
-                        cache.clear()
-                    cache[id(recs)] = got
-            w0, w3 = int(rg[0]), int(rg[1])
-            rows = []
-            for r, ops in zip(recs, got[2]):
-                if w0 < w3 and r.pos - 1 < w3 and record_passes(r.mapq, r.flag, q, f):
-                    sa = (r.tags or {}).get("SA")
-                    rows.append((r.pos, ops, r.flag, sa.encode("latin-1") if isinstance(sa, str) else None))
-            out.append(links.words(links.answer(rows, rg, pc, q)))
-        return out
-
-    def support_many(self, engine, bam: str, chroms, regions):
-        """The seven words per support region (`--support`) from the world's records that pass the read filter
-        with support.EXCLUDE among its flags: support.answer over (POS, operations) of the records that start before w3, every
-        CIGAR text parsed once per record list."""
-        from . import support
-        from .bamio import record_passes
-        q, f = self.read_filter
-        f |= support.EXCLUDE
-        cache = self.__dict__.setdefault("_depth_cache", {})
-        out = []
-        for chrom, rg in zip(chroms, regions):
-            recs = self.world.reads.get(chrom, ())
-            got = cache.get(id(recs))
-            if got is None or got[0] is not recs or got[1] != len(recs):
-                got = (recs, len(recs), [support.parse_cigar(r.cigar) for r in recs])
-                if getattr(self.world, "cache_ok", True):
-                    if len(cache) > 200000:
-                        cache.clear()
-                    cache[id(recs)] = got
-            w0, w3 = int(rg[0]), int(rg[1])
-            out.append(support.answer([(r.pos, ops) for r, ops in zip(recs, got[2])
-                                       if w0 < w3 and r.pos - 1 < w3 and record_passes(r.mapq, r.flag, q, f)], rg))
+            w0, w3 = int(row[lo]), int(row[hi])
+            kept = [(r, ops) for r, ops in zip(recs, self._cigar_ops(recs)) if w0 < w3 and r.pos - 1 < w3 and record_passes(r.mapq, r.flag, q, f)]
+            if module.LINKED:
+                sas = [(r.tags or {}).get("SA") for r, _ops in kept]
+                records = [(r.pos, ops, r.flag, sa.encode("latin-1") if isinstance(sa, str) else None) for (r, ops), sa in zip(kept, sas)]
+            else:
+                records = [(r.pos, ops) for r, ops in kept]
+            out.append(module.statement(records, row, partners[g] if partners is not None else None, q))
         return out
 
     def fai_lines(self, ref: str) -> Iterable[str]:

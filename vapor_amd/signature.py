@@ -30,6 +30,11 @@ INFO = (
 )
 COLUMNS = tuple(i[0] for i in INFO)
 
+# The reader surface (as depth.py's).  ASKED_WITHOUT_CHUNKS: the library refuses a region in its own words, also one no chunk overlaps.
+ROW_WIDTH, WINDOW, ZERO, DTYPE = len(FIELDS), (0, 1), (0,) * 10, "int64"
+ENTRIES, DEVICE, NATIVE, MANY = ("vapor_bam_signature", "vapor_bam_signature_device"), "bam_signature_device", "signature_native", "signature_many"
+LINKED, ASKED_WITHOUT_CHUNKS = False, True
+
 _ADVANCES = (1, 0, 1, 1, 0, 0, 0, 1, 1)      # M I D N S H P = X: moves the reference cursor
 
 
@@ -160,6 +165,16 @@ def words(ans) -> list:
     return list(counts) + [modes[0][0], modes[0][1], modes[1][0], modes[1][1]]
 
 
+def statement(records, row, partner=None, min_mapq=0) -> list:
+    """The Python statement the readers are held to: a region's words from its records (pos, ops)."""
+    return words(answer(records, row))
+
+
+def locus_regions(svtype: str, locus, length_of) -> list:
+    """A locus's regions as the chunk hook sends them: [(contig, FIELDS tuple, None)]; length_of(contig): the contig's length."""
+    return [(locus[0], f, None) for f in regions(svtype, locus, length_of(locus[0]))] if svtype in TYPES else []
+
+
 def merge_words(a, b) -> list:
     """The answers of one region from two files of a per-chromosome pattern: the counts summed, of each mode the better of the
     two by the tie rule (the histograms do not leave the readers)."""
@@ -206,6 +221,9 @@ def payload(svtype: str, locus, regs, answers) -> Optional[Payload]:
     else:
         s, e = int(locus[1]), int(locus[2])
     return Payload([l, r, cg, m0[0], m0[1], m1[0], m1[1]], svtype, s, e)
+
+
+locus_payload = payload              # (of locus_regions' list only its length is read)
 
 
 def columns(p) -> List[str]:

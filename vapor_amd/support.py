@@ -34,6 +34,11 @@ INFO = (
 )
 COLUMNS = tuple(i[0] for i in INFO)
 
+# The reader surface (as depth.py's).  ASKED_WITHOUT_CHUNKS: the library refuses a region in its own words, also one no chunk overlaps.
+ROW_WIDTH, WINDOW, ZERO, DTYPE = len(FIELDS), (0, 1), (0,) * 7, "int64"
+ENTRIES, DEVICE, NATIVE, MANY = ("vapor_bam_support", "vapor_bam_support_device"), "bam_support_device", "support_native", "support_many"
+LINKED, ASKED_WITHOUT_CHUNKS = False, True
+
 
 def regions(svtype: str, locus, contig_len: int) -> list:
     """The support regions of a locus: signature.regions' (the same windows, the same split at P) with F and G behind each and
@@ -114,6 +119,16 @@ def answer(records, region) -> list:
     return [int(v) for v in out]
 
 
+def statement(records, row, partner=None, min_mapq=0) -> list:
+    """The Python statement the readers are held to: a region's words from its records (pos, ops)."""
+    return answer(records, row)
+
+
+def locus_regions(svtype: str, locus, length_of) -> list:
+    """A locus's regions as the chunk hook sends them: [(contig, FIELDS tuple, None)]; length_of(contig): the contig's length."""
+    return [(locus[0], f, None) for f in regions(svtype, locus, length_of(locus[0]))] if svtype in TYPES else []
+
+
 def merge_words(a, b) -> list:
     """The answers of one region from two files of a per-chromosome pattern: summed."""
     return [int(x) + int(y) for x, y in zip(a, b)]
@@ -158,6 +173,9 @@ def payload(svtype: str, locus, regs, answers) -> Optional[Payload]:
     else:
         s, e = int(locus[1]), int(locus[2])
     return Payload(vals, svtype, s, e)
+
+
+locus_payload = payload              # (of locus_regions' list only its length is read)
 
 
 def columns(p) -> List[str]:
