@@ -242,7 +242,8 @@ def test_device_extraction_in_groups_and_a_region_too_large_for_a_call(eng, tmp_
     got = be.chop_many_device(eng, bam, chroms, st, en, fl)
     for bt in got[5]:
         bt.close()
-    assert max(calls) == 9 and calls.count(1) >= 2
+    # (all nine, refused; 0..3 in two pairs; 4..8: 4 and 5 refused for locus 4, locus 4 alone refused, 5 alone; 6..8: 6, then 7 and 8)
+    assert calls == [9, 4, 2, 2, 5, 2, 1, 1, 3, 1, 2]
     status = got[4].tolist()
     assert status[4] != 0 and [s for t, s in enumerate(status) if t != 4] == [0] * 8
     n_want, n_got = np.diff(want[0]), np.diff(got[0])
@@ -250,3 +251,43 @@ def test_device_extraction_in_groups_and_a_region_too_large_for_a_call(eng, tmp_
     keep = np.ones(len(want[3]), dtype=bool)
     keep[int(want[0][4]):int(want[0][5])] = False
     assert np.array_equal(got[3], want[3][keep]) and np.array_equal(got[2], want[2][keep])
+
+
+@pytest.mark.parametrize("err", [ValueError("not the library's error"), KeyboardInterrupt()])
+def test_device_extraction_closes_its_batches_on_any_error(eng, tmp_path, monkeypatch, err):
+    """An error that is not the library's in a later group of chop_many_device: the batches of the groups before it are closed
+    there and then, the error arrives as it was raised, and the native handle is back on the free list."""
+    from vapor_amd import engine, seqio, synth
+    w = synth.make_world(seed=54, n_loci=4, svtypes=("DEL", "INS"), span_range=(100, 900), read_len=3000, n_reads=22)
+    for c in w.reads:
+        w.reads[c] = sorted(w.reads[c], key=lambda r: r.pos)
+    fa, bam = synth.write_world_files(w, str(tmp_path), block_size=0xFF00)
+    be = seqio.InProcessBam()
+    chroms = [l.chrom for l in w.loci]
+    st = np.asarray([l.start - 200 for l in w.loci], dtype=np.int64)
+    fl = np.full(len(chroms), 200, dtype=np.int64)
+    for bt in be.chop_many_device(eng, bam, chroms, st, st + 700, fl)[5]:
+        bt.close()
+    b = be._open(bam)
+    n_free = len(b._free)
+    assert n_free >= 1
+    real, real_close = eng.bam_chop_device, engine.BamBatch.close
+    made, closed = [], []
+
+    def second_fails(*a, **k):
+        if made:
+            raise err
+        made.append(real(*a, **k)[5])
+        return (None,) * 5 + (made[0],) + (None,) * 3
+
+    def close(self):
+        closed.append(self)
+        real_close(self)
+    monkeypatch.setattr(eng, "bam_chop_device", second_fails)
+    monkeypatch.setattr(engine.BamBatch, "close", close)
+    monkeypatch.setenv("VAPOR_BAM_DEVICE_BATCH_MB", "0")            # (every region a group of its own)
+    with pytest.raises(type(err)) as info:
+        be.chop_many_device(eng, bam, chroms, st, st + 700, fl)
+    assert info.value is err
+    assert len(made) == 1 and closed == made and made[0]._h is None
+    assert len(b._free) == n_free

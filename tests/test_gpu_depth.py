@@ -40,12 +40,8 @@ def device(eng, b, chroms, bounds):
         for c in ch:
             flat += [c[0], c[1]]
         chunk_first.append(len(flat) // 2)
-    tl = b._take_handle(L.load())
-    try:
+    with b.handle(L.load()) as tl:
         cov, status = eng.bam_depth_device(tl["native"], tids, np.asarray(bounds, dtype=np.int64).reshape(-1, 4), chunk_first, np.asarray(flat, dtype=np.uint64))
-    finally:
-        with b._lock:
-            b._free.append(tl)
     return [[int(x) for x in c] for c in cov], status.tolist(), per
 
 
@@ -213,16 +209,14 @@ def test_with_the_handles_filter(eng, designed):
 def test_refused_regions_and_arguments(eng, designed):
     path, _, _block = designed
     b = bamio.BamFile(path)
-    tl = b._take_handle(L.load())
-    ch = np.asarray(b.index.chunks(0, 0, 5000), dtype=np.uint64).reshape(-1)
-    bounds = np.asarray([(0, 100, 200, 300), (5, 4, 6, 9), (0, 5, 9, 1 << 31), (-1, 5, 9, 12), (0, 100, 200, 300)], dtype=np.int64)
-    first = np.arange(6, dtype=np.int32) * (len(ch) // 2)
-    cov, status = eng.bam_depth_device(tl["native"], [0, 0, 0, 0, -1], bounds, first, np.tile(ch, 5))
-    assert status.tolist() == [0, 2, 2, 2, 2] and cov[1:].tolist() == [[0, 0, 0]] * 4 and cov[0].tolist() == b.depth_native(0, bounds[0])
-    cov, status = eng.bam_depth_device(tl["native"], [], np.zeros((0, 4), dtype=np.int64), [0], [])
-    assert len(cov) == 0 and len(status) == 0
-    with b._lock:
-        b._free.append(tl)
+    with b.handle(L.load()) as tl:
+        ch = np.asarray(b.index.chunks(0, 0, 5000), dtype=np.uint64).reshape(-1)
+        bounds = np.asarray([(0, 100, 200, 300), (5, 4, 6, 9), (0, 5, 9, 1 << 31), (-1, 5, 9, 12), (0, 100, 200, 300)], dtype=np.int64)
+        first = np.arange(6, dtype=np.int32) * (len(ch) // 2)
+        cov, status = eng.bam_depth_device(tl["native"], [0, 0, 0, 0, -1], bounds, first, np.tile(ch, 5))
+        assert status.tolist() == [0, 2, 2, 2, 2] and cov[1:].tolist() == [[0, 0, 0]] * 4 and cov[0].tolist() == b.depth_native(0, bounds[0])
+        cov, status = eng.bam_depth_device(tl["native"], [], np.zeros((0, 4), dtype=np.int64), [0], [])
+        assert len(cov) == 0 and len(status) == 0
     b.close()
 
 
@@ -276,6 +270,12 @@ def test_300_regions_in_one_call_and_split_and_halved(eng, many, monkeypatch):
     assert be.depth_many(Refusing(), path, ["c"] * 300, bounds) == host
     big, small = [c for c in calls if c > 8], [c for c in calls if c <= 8]
     assert len(big) >= 10 and sum(small) == 300 and max(calls) < 100
+    # the calls themselves, in order: the groups of 8 MB as the index gives them, a refused one followed at once by its halves
+    # (and a half that is refused again by its own)
+    assert calls == [
+        10, 5, 5, 10, 5, 5, 11, 5, 6, 15, 7, 8, 12, 6, 6, 10, 5, 5, 13, 6, 7, 8, 11, 5, 6, 8, 11, 5, 6, 10, 5, 5, 12, 6, 6,
+        11, 5, 6, 12, 6, 6, 8, 9, 4, 5, 11, 5, 6, 11, 5, 6, 12, 6, 6, 10, 5, 5, 11, 5, 6, 12, 6, 6, 11, 5, 6, 10, 5, 5, 11, 5,
+        6, 9, 4, 5, 10, 5, 5, 1]
     calls.clear()
     monkeypatch.setenv("VAPOR_BAM_DEVICE_BATCH_MB", "192")
     assert be.depth_many(eng, path, ["c"] * 300 + ["nowhere"], bounds + [(0, 1, 2, 3)]) == host + [[0, 0, 0]]

@@ -35,12 +35,8 @@ def eng():
 def device(eng, b, cases):
     """engine.bam_links_device over the cases' .bai chunks: (five words per region, status per region, chunks per region)."""
     tids, rows, names, chunk_first, flat, per = LC.device_rows(b, cases)
-    tl = b._take_handle(L.load())
-    try:
+    with b.handle(L.load()) as tl:
         out, status = eng.bam_links_device(tl["native"], tids, rows, chunk_first, flat, names)
-    finally:
-        with b._lock:
-            b._free.append(tl)
     return [[int(x) for x in o] for o in out], status.tolist(), per
 
 
@@ -115,25 +111,23 @@ def test_with_the_handles_filter(eng, designed):
 def test_refused_regions_and_arguments(eng, designed):
     path, d, _block = designed
     b = bamio.BamFile(path)
-    tl = b._take_handle(L.load())
-    case = d.cases[0]
-    f = case[2]
-    ch = np.asarray(b.index.chunks(0, f[0], f[1]), dtype=np.uint64).reshape(-1)
-    names = b"xx" + case[3]
-    good = tuple(f) + (2, len(case[3]))
-    bad = [good[:k] + (v,) + good[k + 1:] for k, v in ((0, f[1] + 1), (1, 1 << 31), (4, -1), (4, 256), (6, 2), (7, -1), (8, 2), (10, 0), (10, len(names)), (9, -1), (0, -1))]
-    regions = np.asarray([good] + bad + [good], dtype=np.int64)
-    n = len(regions)
-    first = np.arange(n + 1, dtype=np.int32) * (len(ch) // 2)
-    out, status = eng.bam_links_device(tl["native"], [0] * (n - 1) + [-1], regions, first, np.tile(ch, n), names)
-    assert status.tolist() == [0] + [REG_MALFORMED] * (n - 1) and out[1:].tolist() == [[0] * 5] * (n - 1) and out[0].tolist() == case[4] == [1, 1, 1, 0, 1]
-    out, status = eng.bam_links_device(tl["native"], [], np.zeros((0, 11), dtype=np.int64), [0], [], b"")
-    assert len(out) == 0 and len(status) == 0
-    # a call without names: every region is refused by status, nothing is read
-    out, status = eng.bam_links_device(tl["native"], [0], np.asarray([good], dtype=np.int64), first[:2], ch, b"")
-    assert status.tolist() == [REG_MALFORMED] and out.tolist() == [[0] * 5]
-    with b._lock:
-        b._free.append(tl)
+    with b.handle(L.load()) as tl:
+        case = d.cases[0]
+        f = case[2]
+        ch = np.asarray(b.index.chunks(0, f[0], f[1]), dtype=np.uint64).reshape(-1)
+        names = b"xx" + case[3]
+        good = tuple(f) + (2, len(case[3]))
+        bad = [good[:k] + (v,) + good[k + 1:] for k, v in ((0, f[1] + 1), (1, 1 << 31), (4, -1), (4, 256), (6, 2), (7, -1), (8, 2), (10, 0), (10, len(names)), (9, -1), (0, -1))]
+        regions = np.asarray([good] + bad + [good], dtype=np.int64)
+        n = len(regions)
+        first = np.arange(n + 1, dtype=np.int32) * (len(ch) // 2)
+        out, status = eng.bam_links_device(tl["native"], [0] * (n - 1) + [-1], regions, first, np.tile(ch, n), names)
+        assert status.tolist() == [0] + [REG_MALFORMED] * (n - 1) and out[1:].tolist() == [[0] * 5] * (n - 1) and out[0].tolist() == case[4] == [1, 1, 1, 0, 1]
+        out, status = eng.bam_links_device(tl["native"], [], np.zeros((0, 11), dtype=np.int64), [0], [], b"")
+        assert len(out) == 0 and len(status) == 0
+        # a call without names: every region is refused by status, nothing is read
+        out, status = eng.bam_links_device(tl["native"], [0], np.asarray([good], dtype=np.int64), first[:2], ch, b"")
+        assert status.tolist() == [REG_MALFORMED] and out.tolist() == [[0] * 5]
     b.close()
 
 
@@ -178,6 +172,12 @@ def test_300_regions_in_one_call_and_split_and_halved(eng, many, monkeypatch):
     assert be.links_many(Refusing(), path, *args_of(cases)) == want
     big, small = [c for c in calls if c > 8], [c for c in calls if c <= 8]
     assert len(big) >= 3 and sum(small) == 300 and max(calls) < 300
+    # the calls themselves, in order: the groups of 8 MB as the index gives them, a refused one followed at once by its halves
+    # (and a half that is refused again by its own)
+    assert calls == [
+        15, 7, 8, 18, 9, 4, 5, 9, 4, 5, 18, 9, 4, 5, 9, 4, 5, 19, 9, 4, 5, 10, 5, 5, 19, 9, 4, 5, 10, 5, 5, 18, 9, 4, 5, 9, 4,
+        5, 18, 9, 4, 5, 9, 4, 5, 16, 8, 8, 17, 8, 9, 4, 5, 17, 8, 9, 4, 5, 19, 9, 4, 5, 10, 5, 5, 16, 8, 8, 16, 8, 8, 17, 8,
+        9, 4, 5, 17, 8, 9, 4, 5, 17, 8, 9, 4, 5, 16, 8, 8, 7]
     calls.clear()
     monkeypatch.setenv("VAPOR_BAM_DEVICE_BATCH_MB", "192")
     more = cases + [("nowhere", "nowhere", (0, 30, 10, 20, 5, C, 0, 0, 0), b"c", None, 0)]

@@ -36,10 +36,8 @@ def handle(world):
     """(the open file, its native handle): what seqio.chop_many_device hands Engine.bam_chop_device."""
     be = seqio.InProcessBam()
     b = be._open(world[1])
-    tl = b._take_handle(L.load())
-    yield b, tl["native"]
-    with b._lock:
-        b._free.append(tl)
+    with b.handle(L.load()) as tl:
+        yield b, tl["native"]
     b.close()
 
 

@@ -45,13 +45,9 @@ def device(eng, b, chroms, regions):
         for c in ch:
             flat += [c[0], c[1]]
         chunk_first.append(len(flat) // 2)
-    tl = b._take_handle(L.load())
-    try:
+    with b.handle(L.load()) as tl:
         out, status = eng.bam_support_device(tl["native"], tids, np.asarray(regions, dtype=np.int64).reshape(-1, 11), chunk_first,
                                              np.asarray(flat, dtype=np.uint64))
-    finally:
-        with b._lock:
-            b._free.append(tl)
     return [[int(x) for x in o] for o in out], status.tolist(), per
 
 
@@ -291,20 +287,18 @@ def test_with_the_handles_filter(eng, designed):
 def test_refused_regions_and_arguments(eng, designed):
     path, _, _block = designed
     b = bamio.BamFile(path)
-    tl = b._take_handle(L.load())
-    ch = np.asarray(b.index.chunks(0, 0, 5000), dtype=np.uint64).reshape(-1)
-    good = (0, 400, 100, 100, T, C, 0, 10, ALL, F, G)
-    bad = [good[:k] + (v,) + good[k + 1:] for k, v in ((0, 401), (1, 1 << 31), (4, -1), (4, 256), (6, 11), (0, -1), (9, 0), (9, 65536), (10, 0))]
-    regions = np.asarray([good] + bad + [good], dtype=np.int64)
-    n = len(regions)
-    first = np.arange(n + 1, dtype=np.int32) * (len(ch) // 2)
-    out, status = eng.bam_support_device(tl["native"], [0] * (n - 1) + [-1], regions, first, np.tile(ch, n))
-    assert status.tolist() == [0] + [2] * (n - 1) and out[1:].tolist() == [[0] * 7] * (n - 1) and out[0].tolist() == b.support_native(0, good)
-    assert out[0].tolist() == [0, 0, 0, 1, 1, 1, 1]
-    out, status = eng.bam_support_device(tl["native"], [], np.zeros((0, 11), dtype=np.int64), [0], [])
-    assert len(out) == 0 and len(status) == 0
-    with b._lock:
-        b._free.append(tl)
+    with b.handle(L.load()) as tl:
+        ch = np.asarray(b.index.chunks(0, 0, 5000), dtype=np.uint64).reshape(-1)
+        good = (0, 400, 100, 100, T, C, 0, 10, ALL, F, G)
+        bad = [good[:k] + (v,) + good[k + 1:] for k, v in ((0, 401), (1, 1 << 31), (4, -1), (4, 256), (6, 11), (0, -1), (9, 0), (9, 65536), (10, 0))]
+        regions = np.asarray([good] + bad + [good], dtype=np.int64)
+        n = len(regions)
+        first = np.arange(n + 1, dtype=np.int32) * (len(ch) // 2)
+        out, status = eng.bam_support_device(tl["native"], [0] * (n - 1) + [-1], regions, first, np.tile(ch, n))
+        assert status.tolist() == [0] + [2] * (n - 1) and out[1:].tolist() == [[0] * 7] * (n - 1) and out[0].tolist() == b.support_native(0, good)
+        assert out[0].tolist() == [0, 0, 0, 1, 1, 1, 1]
+        out, status = eng.bam_support_device(tl["native"], [], np.zeros((0, 11), dtype=np.int64), [0], [])
+        assert len(out) == 0 and len(status) == 0
     b.close()
 
 

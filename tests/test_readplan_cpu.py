@@ -9,23 +9,14 @@ minimize_pacbio_read_list by brute force, the windows' bytes against an arena la
 caps, a text buffer one byte short.  Every buffer is a heap allocation of exactly the bytes the header asks for.  The kernels
 behind these plans are what tests/test_gpu_bamdev.py, test_gpu_phase.py, test_gpu_haplotag.py, test_gpu_both_ends.py,
 test_gpu_dedup.py and test_gpu_bgzf_fasta.py check, and tests/test_gpu_reader_plan.py the refusals on the real entries."""
-import os
-import subprocess
-
 import pytest
 
-from conftest import ROOT
+import readplan_program
 
 
 @pytest.fixture(scope="module")
-def output(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("readplan") / "readplan_check")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-DVBD_EMU",
-                           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "vapor_amd", "csrc"),
-                           os.path.join(ROOT, "tools", "readplan_check.cpp"), "-o", exe])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
-    return r.stdout
+def output():
+    return readplan_program.output()
 
 
 @pytest.mark.parametrize("line", [

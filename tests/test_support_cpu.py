@@ -14,6 +14,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import readplan_program
 import test_bamio as TB
 import test_modes_cpu as TM
 import test_signature_cpu as TS
@@ -588,14 +589,8 @@ def test_sup_pass_under_sanitizers_on_good_and_damaged_files(designed, tmp_path)
     assert n_err >= 7, n_err              # (a file cut between two blocks may end like one without EOF marker)
 
 
-def test_the_plan_of_the_device_call_under_sanitizers(tmp_path):
-    exe = str(tmp_path / "readplan_check")
-    r = subprocess.run(["g++", "-std=c++17", "-DVBD_EMU"] + SAN + [os.path.join(ROOT, "tools", "readplan_check.cpp"), "-o", exe], capture_output=True, text=True,
-                       timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    p = subprocess.run([exe], env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"), capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0 and "Sanitizer" not in p.stderr and "runtime error" not in p.stderr, p.stderr[-2000:]
-    lines = p.stdout.splitlines()
+def test_the_plan_of_the_device_call_under_sanitizers():
+    lines = readplan_program.output().splitlines()
     assert lines[-1] == "readplan_check: all equal"
     sup = [ln for ln in lines if ln.startswith("support plan: ")]
     assert len(sup) == 1 and "clamped fields and collected words equal the rule" in sup[0] and 'both size refusals say "in one call"' in sup[0]

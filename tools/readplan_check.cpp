@@ -1,9 +1,10 @@
 // readplan_check.cpp - the plan of a device reader call (vapor_amd/csrc/vapor_readplan.h: check_args, plan_spans, layout, ChopMeta,
-// collect for vapor_bam_chop_device*; the same five over DepthCall, DepthMeta, DepthLayout for vapor_bam_depth_device and over SigCall, SigMeta, SigLayout for vapor_bam_signature_device, LinkCall's for vapor_bam_links_device and SupCall's for vapor_bam_support_device; plan_stretches, stage_stretches, layout_arena, place_windows, FastaMeta, gather_texts for
+// collect for vapor_bam_chop_device*; the same five over the one EvidenceMeta / EvidenceLayout of the four evidence calls, vapor_bam_depth_device,
+// _signature_device, _links_device and _support_device (check_evidence<Mode>); plan_stretches, stage_stretches, layout_arena, place_windows, FastaMeta, gather_texts for
 // vapor_fasta_windows_device) on a CPU, against direct statements of its rules.  It needs neither zlib nor files: the spans and
 // stretches are block tables the program fills in itself, the calls come from fixed seeds, and every buffer is a heap allocation
 // of exactly the bytes the header says it needs.  Nothing here is compared with recorded plans.
-// Built and run by tests/test_readplan_cpu.py:
+// Built and run once for the tests that quote it (tests/readplan_program.py):
 //   g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -DVBD_EMU -Iinclude -Ivapor_amd/csrc tools/readplan_check.cpp
 #include "vapor_readplan.h"
 
@@ -924,186 +925,79 @@ static void check_fasta_caps()
 }
 
 // ================================================================================================================================
-// vapor_bam_depth_device: DepthCall's plan over the same plan_spans_of / layout_of the chop's goes through
+// The evidence calls: vapor_bam_depth_device, _signature_device, _links_device, _support_device.  The header
+// has one plan shape for the four (EvidenceMeta, EvidenceLayout, collect over plan_spans_of / layout_of), and so has the check:
+// check_evidence<Mode> states the spans, the staging block, the arena, the block table, the metadata block, fill, collect and the
+// two size refusals once.  A Mode below holds what is a call's own: how it is drawn, its argument rules, the rule of a region's
+// record, its sizes and which of its words are signed.
 // ================================================================================================================================
-struct DRegion {
+typedef std::vector<std::pair<uint64_t, uint64_t>> Chunks;
+
+struct EvRegion {
     int32_t tid = 0;
-    int64_t b[4] = {0, 0, 0, 0};
-    std::vector<std::pair<uint64_t, uint64_t>> chunks;
+    int64_t f[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};      // the call's fields, FIELDS of them
+    Chunks chunks;
     bool bad = false;
 };
 
-static DRegion depth_region(int bad)       // bad: 0 good; 1 b0 < 0; 2..4 bounds descend; 5 b3 = 2^31; 6 tid < 0; 7 ce < cs; 8 a chunk wider than 2^27
+// the arrays of a call as they were drawn
+struct EvDrawn {
+    int n = 0;
+    std::vector<int32_t> tid, chunk_first = {0};
+    std::vector<int64_t> fields;
+    std::vector<uint64_t> chunks;
+    std::vector<char> bad;
+    std::vector<uint8_t> names;       // links
+    void push(const EvRegion& r, int n_fields)
+    {
+        tid.push_back(r.tid);
+        fields.insert(fields.end(), r.f, r.f + n_fields);
+        for (auto& c : r.chunks) { chunks.push_back(c.first); chunks.push_back(c.second); }
+        chunk_first.push_back((int32_t)(chunks.size() / 2));
+        bad.push_back(r.bad);
+    }
+};
+
+static Chunks evidence_chunks()
 {
-    DRegion r;
-    r.tid = rnd(0, 30);
-    int64_t x = one_in(6) ? 0 : rnd(0, 1 << 30);
-    for (int k = 0; k < 4; ++k) { r.b[k] = x; x += one_in(3) ? 0 : rnd(0, 20000); }
-    if (one_in(10)) r.b[3] = ((int64_t)1 << 31) - 1;
+    Chunks out;
     for (int k = rnd(0, 3); k > 0; --k) {
         const uint64_t c0 = (uint64_t)rnd(0, 1 << 28), len = one_in(4) ? 0 : (uint64_t)rnd(0, 300000);
         const uint64_t u0 = (uint64_t)rnd(0, 65535), u1 = len == 0 ? (uint64_t)rnd((int)u0, 65535) : (uint64_t)rnd(0, 65535);
-        r.chunks.push_back({c0 << 16 | u0, (c0 + len) << 16 | u1});
+        out.push_back({c0 << 16 | u0, (c0 + len) << 16 | u1});
     }
+    return out;
+}
+
+// a chunk of the region that ends before it starts, or one wider than 2^27
+static void spoil_chunk(Chunks& chunks, bool wide)
+{
+    if (chunks.empty()) chunks.push_back({(uint64_t)5 << 16, (uint64_t)9 << 16});
+    auto& c = chunks[(size_t)rnd(0, (int)chunks.size() - 1)];
+    if (wide) c.second = ((c.first >> 16) + ((uint64_t)1 << 27) + 1) << 16;
+    else c.second = c.first - 1 - (c.first > 1 ? (uint64_t)rnd(0, 1) : 0);
+}
+
+static EvRegion depth_region(int bad)       // bad: 0 good; 1 b0 < 0; 2..4 bounds descend; 5 b3 = 2^31; 6 tid < 0; 7 ce < cs; 8 a chunk wider than 2^27
+{
+    EvRegion r;
+    r.tid = rnd(0, 30);
+    int64_t x = one_in(6) ? 0 : rnd(0, 1 << 30);
+    for (int k = 0; k < 4; ++k) { r.f[k] = x; x += one_in(3) ? 0 : rnd(0, 20000); }
+    if (one_in(10)) r.f[3] = ((int64_t)1 << 31) - 1;
+    r.chunks = evidence_chunks();
     r.bad = bad != 0;
-    if (bad == 1) { r.b[0] = -1 - rnd(0, 5); }
-    if (bad >= 2 && bad <= 4) { r.b[bad - 1] = r.b[bad - 2] - 1 - rnd(0, 9); if (bad == 2 && r.b[1] < 0) r.b[0] = 0, r.b[1] = -1; }
-    if (bad == 5) r.b[3] = (int64_t)1 << 31;
+    if (bad == 1) { r.f[0] = -1 - rnd(0, 5); }
+    if (bad >= 2 && bad <= 4) { r.f[bad - 1] = r.f[bad - 2] - 1 - rnd(0, 9); if (bad == 2 && r.f[1] < 0) r.f[0] = 0, r.f[1] = -1; }
+    if (bad == 5) r.f[3] = (int64_t)1 << 31;
     if (bad == 6) r.tid = -1 - rnd(0, 3);
-    if (bad == 7 || bad == 8) {
-        if (r.chunks.empty()) r.chunks.push_back({(uint64_t)5 << 16, (uint64_t)9 << 16});
-        auto& c = r.chunks[(size_t)rnd(0, (int)r.chunks.size() - 1)];
-        if (bad == 7) c.second = c.first - 1 - (c.first > 1 ? (uint64_t)rnd(0, 1) : 0);
-        else c.second = ((c.first >> 16) + ((uint64_t)1 << 27) + 1) << 16;
-    }
+    if (bad == 7 || bad == 8) spoil_chunk(r.chunks, bad == 8);
     return r;
 }
 
-static void check_depth()
+static EvRegion sig_region(int bad)       // bad: 0 good; 1 w0 < 0; 2 w0 > w3; 3 w3 = 2^31; 4 tol < 0; 5 tol > 255; 6 nmin > nmax; 7 tid < 0; 8 ce < cs
 {
-    long n_calls = 0, n_refused = 0, n_regions_seen = 0;
-    for (int it = 0; it < 1500; ++it) {
-        g_case = it;
-        const int n = one_in(15) ? 0 : rnd(1, 12);
-        std::vector<DRegion> regs;
-        for (int g = 0; g < n; ++g) regs.push_back(depth_region(one_in(4) ? rnd(1, 8) : 0));
-        std::vector<int32_t> tid((size_t)n), chunk_first((size_t)n + 1, 0);
-        std::vector<int64_t> bounds(4 * (size_t)n);
-        std::vector<uint64_t> chunks;
-        for (int g = 0; g < n; ++g) {
-            tid[(size_t)g] = regs[(size_t)g].tid;
-            for (int k = 0; k < 4; ++k) bounds[4 * (size_t)g + (size_t)k] = regs[(size_t)g].b[k];
-            for (auto& c : regs[(size_t)g].chunks) { chunks.push_back(c.first); chunks.push_back(c.second); }
-            chunk_first[(size_t)g + 1] = (int32_t)(chunks.size() / 2);
-        }
-        DepthCall c;
-        c.n_regions = n; c.tid = tid.data(); c.bounds = bounds.data(); c.chunk_first = chunk_first.data();
-        c.chunks = chunks.empty() ? nullptr : chunks.data();
-        const uint32_t handle_word = (uint32_t)rnd(0, 65535) | ((uint32_t)rnd(0, 255) << 16);
-        c.filter_word = depth_filter_word(handle_word);
-        CHECK((c.filter_word & 0x704u) == 0x704u && (c.filter_word | 0x704u) == (handle_word | 0x704u), "filter word %x of %x", c.filter_word, handle_word);
-        std::vector<uint64_t> cov(3 * (size_t)std::max(n, 1), 77);
-        std::vector<int32_t> status((size_t)std::max(n, 1), -9);
-        CHECK(!check_args(c, cov.data(), status.data()), "a good call is refused");
-        if (n) {
-            CHECK(check_args(c, nullptr, status.data()).code == VAPOR_E_ARG && check_args(c, cov.data(), nullptr).code == VAPOR_E_ARG, "null outputs pass");
-            DepthCall d = c; d.bounds = nullptr;
-            CHECK(check_args(d, cov.data(), status.data()).code == VAPOR_E_ARG, "null bounds pass");
-        }
-        SpanPlan p;
-        CHECK(!plan_spans(c, status.data(), p), "a call below the size limit is refused");
-        // the statuses and the spans, against the rule stated per region
-        size_t si = 0, stage = 0;
-        for (int g = 0; g < n; ++g) {
-            const DRegion& r = regs[(size_t)g];
-            CHECK(status[(size_t)g] == (r.bad ? REG_MALFORMED : 0), "region %d: status %d, bad %d", g, status[(size_t)g], (int)r.bad);
-            CHECK(p.span_first[(size_t)g] == (int32_t)si, "region %d: span_first", g);
-            if (r.bad) { ++n_refused; continue; }
-            for (auto& ch : r.chunks) {
-                CHECK(si < p.spans.size(), "region %d: a span is missing", g);
-                const HostSpan& sp = p.spans[si++];
-                const size_t want = (size_t)((ch.second >> 16) - (ch.first >> 16)) + ((ch.second & 0xFFFFu) ? 65536 + 64 : 0);
-                CHECK(sp.region == g && sp.cs == ch.first && sp.ce == ch.second && sp.file_off == (int64_t)(ch.first >> 16) && sp.want == want && sp.stage_off == stage,
-                      "region %d: span fields", g);
-                stage += up64(want);
-            }
-        }
-        CHECK(si == p.spans.size() && p.span_first[(size_t)n] == (int32_t)si && p.stage_bytes == stage, "spans %zu of %zu, stage %zu of %zu", si, p.spans.size(), stage, p.stage_bytes);
-        // the layout after a made-up scan
-        for (HostSpan& sp : p.spans) fake_scan(sp);
-        std::vector<int32_t> before = status;
-        DepthLayout L;
-        CHECK(!layout(c, p, status.data(), L), "a layout below the size limit is refused");
-        size_t arena = 0, n_blk = 0, n_sp = 0;
-        CHECK((int)L.regs.size() == std::max(n, 1), "regions in the layout");
-        for (int g = 0; g < n; ++g) {
-            bool scan_bad = false;
-            for (int32_t s = p.span_first[(size_t)g]; s < p.span_first[(size_t)g + 1]; ++s) scan_bad |= p.spans[(size_t)s].bad;
-            CHECK(status[(size_t)g] == (scan_bad ? REG_MALFORMED : before[(size_t)g]), "region %d: status after the scan", g);
-            const DepthRegion& R = L.regs[(size_t)g];
-            CHECK(R.tid == tid[(size_t)g] && R.filter == c.filter_word && !memcmp(R.b, &bounds[4 * (size_t)g], 32), "region %d: its record", g);
-            CHECK(R.span_first == (int32_t)n_sp, "region %d: span_first in the layout", g);
-            if (status[(size_t)g]) { CHECK(R.span_n == 0, "a refused region has spans"); continue; }
-            CHECK(R.span_n == p.span_first[(size_t)g + 1] - p.span_first[(size_t)g], "region %d: span_n", g);
-            for (int32_t s = p.span_first[(size_t)g]; s < p.span_first[(size_t)g + 1]; ++s) {
-                const HostSpan& sp = p.spans[(size_t)s];
-                const BamSpan& d = L.spans[n_sp++];
-                CHECK(d.u_begin == arena + sp.u_begin && d.u_end == arena + sp.u_end && d.u_limit == arena + sp.u_total && d.blk_first == n_blk && d.blk_n == sp.blks.size(),
-                      "region %d: a span in the arena", g);
-                for (const Block& k : sp.blks) {
-                    const BgzfBlk& B = L.blks[n_blk++];
-                    CHECK(B.c_off == sp.stage_off + k.payload() && B.c_len == k.c_len() && B.u_off == arena + k.u && B.u_len == k.isize && B.crc == k.crc, "a block of region %d", g);
-                }
-                arena += up64(sp.u_total);
-            }
-        }
-        CHECK(L.arena == arena && L.blks.size() == n_blk && L.spans.size() == n_sp, "arena %zu of %zu", arena, L.arena);
-        // the metadata block: the tables in order, on multiples of 64, without overlap; what goes in first, what comes back last
-        const DepthMeta& M = L.meta;
-        const size_t nr = (size_t)std::max(n, 1), nb = std::max<size_t>(n_blk, 1), ns = std::max<size_t>(n_sp, 1);
-        const size_t offs[6] = {M.blks.off, M.spans.off, M.regs.off, M.blk_status.off, M.ans.off, M.reg_status.off};
-        const size_t sizes[6] = {24 * nb, 24 * ns, 48 * nr, 4 * nb, 24 * nr, 4 * nr};
-        size_t at = 0;
-        for (int t = 0; t < 6; ++t) { CHECK(offs[t] == at && at % 64 == 0, "table %d at %zu, not %zu", t, offs[t], at); at += up64(sizes[t]); }
-        CHECK(M.bytes == at && M.in_bytes == M.blk_status.off && M.back_bytes() == M.bytes - M.blk_status.off, "the block's sizes");
-        // fill and collect on heap blocks of exactly those bytes
-        std::vector<uint8_t> h(M.bytes, 0xEE);
-        L.fill(h.data());
-        CHECK(!memcmp(M.regs.in(h.data()), L.regs.data(), 48 * nr) && (!n_blk || !memcmp(M.blks.in(h.data()), L.blks.data(), 24 * n_blk)) &&
-              (!n_sp || !memcmp(M.spans.in(h.data()), L.spans.data(), 24 * n_sp)), "fill");
-        uint64_t* dc = M.ans.in(h.data());
-        int32_t* rs = M.reg_status.in(h.data());
-        for (size_t g = 0; g < nr; ++g) { for (int k = 0; k < 3; ++k) dc[3 * g + (size_t)k] = rng(); rs[g] = one_in(5) ? rnd(1, 5) : 0; }
-        std::vector<int32_t> st2 = status;
-        collect(c, M, h.data(), cov.data(), st2.data());
-        for (int g = 0; g < n; ++g) {
-            const bool host_refused = status[(size_t)g] != 0, dev_refused = rs[(size_t)g] != 0;
-            CHECK(st2[(size_t)g] == (host_refused ? status[(size_t)g] : rs[(size_t)g]), "region %d: collected status", g);
-            for (int k = 0; k < 3; ++k)
-                CHECK(cov[3 * (size_t)g + (size_t)k] == (host_refused || dev_refused ? 0 : dc[3 * (size_t)g + (size_t)k]), "region %d: sum %d", g, k);
-        }
-        ++n_calls;
-        n_regions_seen += n;
-    }
-    // the two "in one call" refusals the Python side halves a group on
-    {
-        std::vector<int32_t> tid(40, 0), chunk_first(41), status(40);
-        std::vector<int64_t> bounds;
-        std::vector<uint64_t> chunks;
-        for (int g = 0; g < 40; ++g) {
-            for (int64_t v : {0, 10, 20, 30}) bounds.push_back(v);
-            chunks.push_back((uint64_t)g << 44); chunks.push_back(((uint64_t)g << 44) + (((uint64_t)1 << 26) << 16));
-            chunk_first[(size_t)g + 1] = g + 1;
-        }
-        DepthCall c;
-        c.n_regions = 40; c.tid = tid.data(); c.bounds = bounds.data(); c.chunk_first = chunk_first.data(); c.chunks = chunks.data();
-        SpanPlan p;
-        const Refusal r = plan_spans(c, status.data(), p);
-        CHECK(r.code == VAPOR_E_ARG && strstr(r.msg, "vapor_bam_depth_device") && strstr(r.msg, "in one call"), "2.5 GB of blocks pass");
-        c.n_regions = 20;
-        CHECK(!plan_spans(c, status.data(), p), "1.25 GB of blocks are refused");
-        for (HostSpan& sp : p.spans) { sp.blks.push_back(Block{0, 6, 100, 0, 65536, 0}); sp.u_total = (uint64_t)120 << 20; sp.u_begin = 0; sp.u_end = 100; sp.got = sp.want; }
-        DepthLayout L;
-        const Refusal r2 = layout(c, p, status.data(), L);
-        CHECK(r2.code == VAPOR_E_ARG && strstr(r2.msg, "vapor_bam_depth_device") && strstr(r2.msg, "in one call"), "2.4 GB of block data pass");
-    }
-    printf("depth plan: %ld calls with %ld regions (%ld refused): statuses, spans, arena, tables and collected sums equal the rule; both size refusals say \"in one call\"\n",
-           n_calls, n_regions_seen, n_refused);
-}
-
-// ================================================================================================================================
-// vapor_bam_signature_device: SigCall's plan over the same plan_spans_of / layout_of
-// ================================================================================================================================
-struct SRegion {
-    int32_t tid = 0;
-    int64_t f[SIG_FIELDS] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    std::vector<std::pair<uint64_t, uint64_t>> chunks;
-    bool bad = false;
-};
-
-static SRegion sig_region(int bad)       // bad: 0 good; 1 w0 < 0; 2 w0 > w3; 3 w3 = 2^31; 4 tol < 0; 5 tol > 255; 6 nmin > nmax; 7 tid < 0; 8 ce < cs
-{
-    SRegion r;
+    EvRegion r;
     r.tid = rnd(0, 30);
     r.f[0] = one_in(6) ? 0 : rnd(0, 1 << 30);
     r.f[1] = r.f[0] + (one_in(5) ? 0 : rnd(0, 20000));
@@ -1115,11 +1009,7 @@ static SRegion sig_region(int bad)       // bad: 0 good; 1 w0 < 0; 2 w0 > w3; 3 
     r.f[6] = one_in(6) ? -(int64_t)rnd(0, 1 << 30) : rnd(0, 5000);
     r.f[7] = r.f[6] + (one_in(6) ? ((int64_t)1 << 40) : rnd(0, 9000));
     r.f[8] = one_in(8) ? 0xFFFF : rnd(0, 63);
-    for (int k = rnd(0, 3); k > 0; --k) {
-        const uint64_t c0 = (uint64_t)rnd(0, 1 << 28), len = one_in(4) ? 0 : (uint64_t)rnd(0, 300000);
-        const uint64_t u0 = (uint64_t)rnd(0, 65535), u1 = len == 0 ? (uint64_t)rnd((int)u0, 65535) : (uint64_t)rnd(0, 65535);
-        r.chunks.push_back({c0 << 16 | u0, (c0 + len) << 16 | u1});
-    }
+    r.chunks = evidence_chunks();
     r.bad = bad != 0;
     if (bad == 1) { r.f[0] = -1 - rnd(0, 5); }
     if (bad == 2) { r.f[0] = r.f[1] + 1 + rnd(0, 9); }
@@ -1128,179 +1018,86 @@ static SRegion sig_region(int bad)       // bad: 0 good; 1 w0 < 0; 2 w0 > w3; 3 
     if (bad == 5) r.f[4] = 256 + rnd(0, 1000);
     if (bad == 6) r.f[6] = r.f[7] + 1 + rnd(0, 9);
     if (bad == 7) r.tid = -1 - rnd(0, 3);
-    if (bad == 8) {
-        if (r.chunks.empty()) r.chunks.push_back({(uint64_t)5 << 16, (uint64_t)9 << 16});
-        auto& c = r.chunks[(size_t)rnd(0, (int)r.chunks.size() - 1)];
-        c.second = c.first - 1 - (c.first > 1 ? (uint64_t)rnd(0, 1) : 0);
-    }
+    if (bad == 8) spoil_chunk(r.chunks, false);
     return r;
 }
 
-static void check_signature()
+// the length bounds of a signature or support region as its record carries them
+static int64_t clamped_len(int64_t v) { return v < -1 ? (int64_t)-1 : (v > ((int64_t)1 << 28) ? ((int64_t)1 << 28) : v); }
+
+// the first nine fields of a signature or support record: as given where they are in range, clamped where a clamp admits the same operations
+template <typename Region>
+static void sig_fields_rule(const Region& R, const int64_t* f, uint32_t mask_bits, int g)
 {
-    long n_calls = 0, n_refused = 0, n_regions_seen = 0;
-    for (int it = 0; it < 1500; ++it) {
-        g_case = it;
-        const int n = one_in(15) ? 0 : rnd(1, 12);
-        std::vector<SRegion> regs;
-        for (int g = 0; g < n; ++g) regs.push_back(sig_region(one_in(4) ? rnd(1, 8) : 0));
-        std::vector<int32_t> tid((size_t)n), chunk_first((size_t)n + 1, 0);
-        std::vector<int64_t> fields((size_t)SIG_FIELDS * (size_t)n);
-        std::vector<uint64_t> chunks;
-        for (int g = 0; g < n; ++g) {
-            tid[(size_t)g] = regs[(size_t)g].tid;
-            for (int k = 0; k < SIG_FIELDS; ++k) fields[(size_t)SIG_FIELDS * (size_t)g + (size_t)k] = regs[(size_t)g].f[k];
-            for (auto& c : regs[(size_t)g].chunks) { chunks.push_back(c.first); chunks.push_back(c.second); }
-            chunk_first[(size_t)g + 1] = (int32_t)(chunks.size() / 2);
-        }
-        SigCall c;
-        c.n_regions = n; c.tid = tid.data(); c.regions = fields.data(); c.chunk_first = chunk_first.data();
-        c.chunks = chunks.empty() ? nullptr : chunks.data();
-        c.filter_word = depth_filter_word((uint32_t)rnd(0, 65535) | ((uint32_t)rnd(0, 255) << 16));
-        std::vector<int64_t> out((size_t)SIG_ANSWER_WORDS * (size_t)std::max(n, 1), 77);
-        std::vector<int32_t> status((size_t)std::max(n, 1), -9);
-        CHECK(!check_args(c, out.data(), status.data()), "a good call is refused");
-        if (n) {
-            CHECK(check_args(c, nullptr, status.data()).code == VAPOR_E_ARG && check_args(c, out.data(), nullptr).code == VAPOR_E_ARG, "null outputs pass");
-            SigCall d = c; d.regions = nullptr;
-            CHECK(check_args(d, out.data(), status.data()).code == VAPOR_E_ARG, "null regions pass");
-        }
-        SpanPlan p;
-        CHECK(!plan_spans(c, status.data(), p), "a call below the size limit is refused");
-        size_t si = 0, stage = 0;
-        for (int g = 0; g < n; ++g) {
-            const SRegion& r = regs[(size_t)g];
-            CHECK(status[(size_t)g] == (r.bad ? REG_MALFORMED : 0), "region %d: status %d, bad %d", g, status[(size_t)g], (int)r.bad);
-            CHECK(p.span_first[(size_t)g] == (int32_t)si, "region %d: span_first", g);
-            if (r.bad) { ++n_refused; continue; }
-            for (auto& ch : r.chunks) {
-                CHECK(si < p.spans.size(), "region %d: a span is missing", g);
-                const HostSpan& sp = p.spans[si++];
-                const size_t want = (size_t)((ch.second >> 16) - (ch.first >> 16)) + ((ch.second & 0xFFFFu) ? 65536 + 64 : 0);
-                CHECK(sp.region == g && sp.cs == ch.first && sp.ce == ch.second && sp.file_off == (int64_t)(ch.first >> 16) && sp.want == want && sp.stage_off == stage,
-                      "region %d: span fields", g);
-                stage += up64(want);
-            }
-        }
-        CHECK(si == p.spans.size() && p.span_first[(size_t)n] == (int32_t)si && p.stage_bytes == stage, "spans %zu of %zu, stage %zu of %zu", si, p.spans.size(), stage, p.stage_bytes);
-        for (HostSpan& sp : p.spans) fake_scan(sp);
-        std::vector<int32_t> before = status;
-        SigLayout L;
-        CHECK(!layout(c, p, status.data(), L), "a layout below the size limit is refused");
-        size_t arena = 0, n_blk = 0, n_sp = 0;
-        CHECK((int)L.regs.size() == std::max(n, 1), "regions in the layout");
-        for (int g = 0; g < n; ++g) {
-            bool scan_bad = false;
-            for (int32_t s = p.span_first[(size_t)g]; s < p.span_first[(size_t)g + 1]; ++s) scan_bad |= p.spans[(size_t)s].bad;
-            CHECK(status[(size_t)g] == (scan_bad ? REG_MALFORMED : before[(size_t)g]), "region %d: status after the scan", g);
-            const SigRegion& R = L.regs[(size_t)g];
-            const int64_t* f = regs[(size_t)g].f;
-            CHECK(R.span_first == (int32_t)n_sp, "region %d: span_first in the layout", g);
-            if (status[(size_t)g]) {
-                // a region the plan or the scan refused carries a record that asks nothing
-                CHECK(R.span_n == 0 && R.mask == 0 && R.tol == 0 && R.w0 == 0 && R.w3 == 0, "region %d: a refused region's record", g);
-                continue;
-            }
-            // the record: the fields as given where they are in range, clamped where a clamp admits the same operations
-            CHECK(R.tid == tid[(size_t)g] && R.filter == c.filter_word && R.w0 == f[0] && R.w3 == f[1] && R.x0 == f[2] && R.x1 == f[3] && R.tol == f[4], "region %d: its record", g);
-            CHECK(R.min_clip == (f[5] < 1 ? 1 : f[5]) && R.mask == ((uint32_t)f[8] & 63u), "region %d: min_clip %d of %lld, mask %u", g, R.min_clip, (long long)f[5], R.mask);
-            auto clamped = [](int64_t v) { return v < -1 ? (int64_t)-1 : (v > ((int64_t)1 << 28) ? ((int64_t)1 << 28) : v); };
-            CHECK(R.nmin == clamped(f[6]) && R.nmax == clamped(f[7]) && R.nmin <= R.nmax, "region %d: length bounds", g);
-            for (int64_t len : {(int64_t)0, (int64_t)1, f[6] - 1, f[6], f[7], f[7] + 1, ((int64_t)1 << 28) - 1})
-                if (len >= 0 && len < ((int64_t)1 << 28))
-                    CHECK((len >= f[6] && len <= f[7]) == (len >= R.nmin && len <= R.nmax), "region %d: the clamped bounds admit other operations at %lld", g, (long long)len);
-            CHECK(R.span_n == p.span_first[(size_t)g + 1] - p.span_first[(size_t)g], "region %d: span_n", g);
-            for (int32_t s = p.span_first[(size_t)g]; s < p.span_first[(size_t)g + 1]; ++s) {
-                const HostSpan& sp = p.spans[(size_t)s];
-                const BamSpan& d = L.spans[n_sp++];
-                CHECK(d.u_begin == arena + sp.u_begin && d.u_end == arena + sp.u_end && d.u_limit == arena + sp.u_total && d.blk_first == n_blk && d.blk_n == sp.blks.size(),
-                      "region %d: a span in the arena", g);
-                for (const Block& k : sp.blks) {
-                    const BgzfBlk& B = L.blks[n_blk++];
-                    CHECK(B.c_off == sp.stage_off + k.payload() && B.c_len == k.c_len() && B.u_off == arena + k.u && B.u_len == k.isize && B.crc == k.crc, "a block of region %d", g);
-                }
-                arena += up64(sp.u_total);
-            }
-        }
-        CHECK(L.arena == arena && L.blks.size() == n_blk && L.spans.size() == n_sp, "arena %zu of %zu", arena, L.arena);
-        const SigMeta& M = L.meta;
-        const size_t nr = (size_t)std::max(n, 1), nb = std::max<size_t>(n_blk, 1), ns = std::max<size_t>(n_sp, 1);
-        const size_t offs[6] = {M.blks.off, M.spans.off, M.regs.off, M.blk_status.off, M.ans.off, M.reg_status.off};
-        const size_t sizes[6] = {24 * nb, 24 * ns, 72 * nr, 4 * nb, 40 * nr, 4 * nr};
-        size_t at = 0;
-        for (int t = 0; t < 6; ++t) { CHECK(offs[t] == at && at % 64 == 0, "table %d at %zu, not %zu", t, offs[t], at); at += up64(sizes[t]); }
-        CHECK(M.bytes == at && M.in_bytes == M.blk_status.off && M.back_bytes() == M.bytes - M.blk_status.off, "the block's sizes");
-        std::vector<uint8_t> h(M.bytes, 0xEE);
-        L.fill(h.data());
-        CHECK(!memcmp(M.regs.in(h.data()), L.regs.data(), 72 * nr) && (!n_blk || !memcmp(M.blks.in(h.data()), L.blks.data(), 24 * n_blk)) &&
-              (!n_sp || !memcmp(M.spans.in(h.data()), L.spans.data(), 24 * n_sp)), "fill");
-        uint32_t* da = M.ans.in(h.data());
-        int32_t* rs = M.reg_status.in(h.data());
-        for (size_t g = 0; g < nr; ++g) {
-            for (int k = 0; k < SIG_ANSWER_WORDS; ++k) da[(size_t)SIG_ANSWER_WORDS * g + (size_t)k] = (uint32_t)rng();
-            da[(size_t)SIG_ANSWER_WORDS * g + 6] = (uint32_t)(int32_t)rnd(-255, 255);
-            da[(size_t)SIG_ANSWER_WORDS * g + 8] = (uint32_t)(int32_t)rnd(-255, 255);
-            rs[g] = one_in(5) ? rnd(1, 5) : 0;
-        }
-        std::vector<int32_t> st2 = status;
-        collect(c, M, h.data(), out.data(), st2.data());
-        for (int g = 0; g < n; ++g) {
-            const bool host_refused = status[(size_t)g] != 0, dev_refused = rs[(size_t)g] != 0;
-            CHECK(st2[(size_t)g] == (host_refused ? status[(size_t)g] : rs[(size_t)g]), "region %d: collected status", g);
-            for (int k = 0; k < SIG_ANSWER_WORDS; ++k) {
-                const uint32_t wd = da[(size_t)SIG_ANSWER_WORDS * (size_t)g + (size_t)k];
-                const int64_t want = host_refused || dev_refused ? 0 : ((k == 6 || k == 8) ? (int64_t)(int32_t)wd : (int64_t)wd);
-                CHECK(out[(size_t)SIG_ANSWER_WORDS * (size_t)g + (size_t)k] == want, "region %d: word %d", g, k);
-            }
-        }
-        ++n_calls;
-        n_regions_seen += n;
-    }
-    // the two "in one call" refusals the Python side halves a group on
-    {
-        std::vector<int32_t> tid(40, 0), chunk_first(41), status(40);
-        std::vector<int64_t> fields;
-        std::vector<uint64_t> chunks;
-        for (int g = 0; g < 40; ++g) {
-            for (int64_t v : {0, 100, 40, 60, 50, 30, 30, 200, 63}) fields.push_back(v);
-            chunks.push_back((uint64_t)g << 44); chunks.push_back(((uint64_t)g << 44) + (((uint64_t)1 << 26) << 16));
-            chunk_first[(size_t)g + 1] = g + 1;
-        }
-        SigCall c;
-        c.n_regions = 40; c.tid = tid.data(); c.regions = fields.data(); c.chunk_first = chunk_first.data(); c.chunks = chunks.data();
-        SpanPlan p;
-        const Refusal r = plan_spans(c, status.data(), p);
-        CHECK(r.code == VAPOR_E_ARG && strstr(r.msg, "vapor_bam_signature_device") && strstr(r.msg, "in one call"), "2.5 GB of blocks pass");
-        c.n_regions = 20;
-        CHECK(!plan_spans(c, status.data(), p), "1.25 GB of blocks are refused");
-        for (HostSpan& sp : p.spans) { sp.blks.push_back(Block{0, 6, 100, 0, 65536, 0}); sp.u_total = (uint64_t)120 << 20; sp.u_begin = 0; sp.u_end = 100; sp.got = sp.want; }
-        SigLayout L;
-        const Refusal r2 = layout(c, p, status.data(), L);
-        CHECK(r2.code == VAPOR_E_ARG && strstr(r2.msg, "vapor_bam_signature_device") && strstr(r2.msg, "in one call"), "2.4 GB of block data pass");
-    }
-    printf("signature plan: %ld calls with %ld regions (%ld refused): statuses, spans, arena, tables, clamped fields and collected words equal the rule; both size refusals say \"in one call\"\n",
-           n_calls, n_regions_seen, n_refused);
+    CHECK(R.w0 == f[0] && R.w3 == f[1] && R.x0 == f[2] && R.x1 == f[3] && R.tol == f[4], "region %d: its record", g);
+    CHECK(R.min_clip == (f[5] < 1 ? 1 : f[5]) && R.mask == ((uint32_t)f[8] & mask_bits), "region %d: min_clip %d of %lld, mask %u", g, R.min_clip, (long long)f[5], R.mask);
+    CHECK(R.nmin == clamped_len(f[6]) && R.nmax == clamped_len(f[7]) && R.nmin <= R.nmax, "region %d: length bounds", g);
 }
 
-// ================================================================================================================================
-// vapor_bam_links_device: LinkCall's plan over the same plan_spans_of / layout_of, with the name blob
-// ================================================================================================================================
-static void check_links()
-{
-    long n_calls = 0, n_refused = 0, n_regions_seen = 0;
-    for (int it = 0; it < 1000; ++it) {
-        g_case = it;
-        const int n = one_in(15) ? 0 : rnd(1, 12);
+struct DepthMode {
+    using Call = DepthCall; using Layout = DepthLayout; using Word = uint64_t; using Out = uint64_t;
+    static constexpr int FIELDS = 4, WORDS = 3, ITERS = 1500;
+    static constexpr size_t REG_BYTES = 48, ANS_BYTES = 24;
+    static constexpr uint32_t SIGNED = 0;
+    static constexpr bool NAMES = false;
+    static constexpr const char* ENTRY = "vapor_bam_depth_device";
+    static constexpr const char* NAME = "depth";
+    static constexpr const char* EQUAL = "statuses, spans, arena, tables and collected sums";
+    static constexpr int64_t EXAMPLE[FIELDS] = {0, 10, 20, 30};
+    static void draw(EvDrawn& d) { for (int g = 0; g < d.n; ++g) d.push(depth_region(one_in(4) ? rnd(1, 8) : 0), FIELDS); }
+    static void bind(Call& c, const int64_t* fields, const EvDrawn&) { c.bounds = fields; }
+    static void more_args(const Call&, Out*, int32_t*) {}
+    // a refused region's record carries its fields all the same
+    static void record(const DepthRegion& R, const Call& c, int g, bool)
+    {
+        CHECK(R.tid == c.tid[g] && R.filter == c.filter_word && !memcmp(R.b, c.bounds + 4 * (size_t)g, 32), "region %d: its record", g);
+    }
+};
+
+struct SigMode {
+    using Call = SigCall; using Layout = SigLayout; using Word = uint32_t; using Out = int64_t;
+    static constexpr int FIELDS = SIG_FIELDS, WORDS = SIG_ANSWER_WORDS, ITERS = 1500;
+    static constexpr size_t REG_BYTES = 72, ANS_BYTES = 40;
+    static constexpr uint32_t SIGNED = (1u << 6) | (1u << 8);
+    static constexpr bool NAMES = false;
+    static constexpr const char* ENTRY = "vapor_bam_signature_device";
+    static constexpr const char* NAME = "signature";
+    static constexpr const char* EQUAL = "statuses, spans, arena, tables, clamped fields and collected words";
+    static constexpr int64_t EXAMPLE[FIELDS] = {0, 100, 40, 60, 50, 30, 30, 200, 63};
+    static void draw(EvDrawn& d) { for (int g = 0; g < d.n; ++g) d.push(sig_region(one_in(4) ? rnd(1, 8) : 0), FIELDS); }
+    static void bind(Call& c, const int64_t* fields, const EvDrawn&) { c.regions = fields; }
+    static void more_args(const Call&, Out*, int32_t*) {}
+    static void record(const SigRegion& R, const Call& c, int g, bool refused)
+    {
+        const int64_t* f = c.regions + (size_t)FIELDS * (size_t)g;
+        // a region the plan or the scan refused carries a record that asks nothing
+        if (refused) { CHECK(R.mask == 0 && R.tol == 0 && R.w0 == 0 && R.w3 == 0, "region %d: a refused region's record", g); return; }
+        sig_fields_rule(R, f, 63u, g);
+        for (int64_t len : {(int64_t)0, (int64_t)1, f[6] - 1, f[6], f[7], f[7] + 1, ((int64_t)1 << 28) - 1})
+            if (len >= 0 && len < ((int64_t)1 << 28))
+                CHECK((len >= f[6] && len <= f[7]) == (len >= R.nmin && len <= R.nmax), "region %d: the clamped bounds admit other operations at %lld", g, (long long)len);
+    }
+};
+
+struct LinkMode {
+    using Call = LinkCall; using Layout = LinkLayout; using Word = uint32_t; using Out = int64_t;
+    static constexpr int FIELDS = LINK_FIELDS, WORDS = LINK_ANSWER_WORDS, ITERS = 1000;
+    static constexpr size_t REG_BYTES = 72, ANS_BYTES = 20;
+    static constexpr uint32_t SIGNED = 1u << 3;
+    static constexpr bool NAMES = true;
+    static constexpr const char* ENTRY = "vapor_bam_links_device";
+    static constexpr const char* NAME = "links";
+    static constexpr const char* EQUAL = "statuses, tables, the name blob, clamped fields and collected words";
+    static constexpr int64_t EXAMPLE[FIELDS] = {0, 100, 40, 60, 50, 30, 1, 0, 0, 0, 2};
+    static void draw(EvDrawn& d)
+    {
         const int64_t names_len = one_in(10) ? 0 : rnd(1, 400);
-        std::vector<uint8_t> names((size_t)names_len);
-        for (auto& ch : names) ch = (uint8_t)rnd(33, 126);
-        std::vector<int32_t> tid((size_t)n), chunk_first((size_t)n + 1, 0);
-        std::vector<int64_t> fields((size_t)LINK_FIELDS * (size_t)n);
-        std::vector<uint64_t> chunks;
-        std::vector<char> bad((size_t)n, 0);
-        for (int g = 0; g < n; ++g) {
-            int64_t* f = fields.data() + (size_t)LINK_FIELDS * (size_t)g;
-            tid[(size_t)g] = rnd(0, 30);
+        d.names.resize((size_t)names_len);
+        for (auto& ch : d.names) ch = (uint8_t)rnd(33, 126);
+        for (int g = 0; g < d.n; ++g) {
+            EvRegion r;
+            int64_t* f = r.f;
+            r.tid = rnd(0, 30);
             f[0] = one_in(6) ? 0 : rnd(0, 1 << 30);
             f[1] = f[0] + (one_in(5) ? 0 : rnd(0, 200));
             if (one_in(10)) f[1] = ((int64_t)1 << 31) - 1;
@@ -1311,12 +1108,7 @@ static void check_links()
             f[6] = rnd(0, 1); f[7] = rnd(0, 1); f[8] = rnd(0, 1);
             f[10] = names_len ? rnd(1, (int)names_len) : 1;
             f[9] = names_len ? rnd(0, (int)(names_len - f[10])) : 0;
-            for (int k = rnd(0, 3); k > 0; --k) {
-                const uint64_t c0 = (uint64_t)rnd(0, 1 << 28), len = one_in(4) ? 0 : (uint64_t)rnd(0, 300000);
-                const uint64_t u0 = (uint64_t)rnd(0, 65535), u1 = len == 0 ? (uint64_t)rnd((int)u0, 65535) : (uint64_t)rnd(0, 65535);
-                chunks.push_back(c0 << 16 | u0); chunks.push_back((c0 + len) << 16 | u1);
-            }
-            chunk_first[(size_t)g + 1] = (int32_t)(chunks.size() / 2);
+            r.chunks = evidence_chunks();
             // 1 w0 < 0; 2 w0 > w3; 3 w3 = 2^31; 4 tol < 0; 5 tol > 255; 6 ev; 7 pend; 8 rel; 9 an empty name; 10 a name past the blob;
             // 11 a negative offset; 12 tid < 0
             const int how = one_in(3) ? rnd(1, 12) : 0;
@@ -1329,227 +1121,181 @@ static void check_links()
             if (how == 9) f[10] = 0;
             if (how == 10) f[10] = names_len - f[9] + 1 + rnd(0, 5);
             if (how == 11) f[9] = -1 - rnd(0, 5);
-            if (how == 12) tid[(size_t)g] = -1 - rnd(0, 3);
-            bad[(size_t)g] = how != 0 || names_len == 0;
+            if (how == 12) r.tid = -1 - rnd(0, 3);
+            r.bad = how != 0 || names_len == 0;
             // the one statement, against the rule spelled out
-            CHECK(link_region_ok(tid[(size_t)g], f, names_len) == !bad[(size_t)g], "region %d: link_region_ok, how %d", g, how);
+            CHECK(link_region_ok(r.tid, f, names_len) == !r.bad, "region %d: link_region_ok, how %d", g, how);
+            d.push(r, FIELDS);
         }
-        LinkCall c;
-        c.n_regions = n; c.tid = tid.data(); c.regions = fields.data(); c.names = names_len ? names.data() : nullptr; c.names_len = names_len;
-        c.chunk_first = chunk_first.data(); c.chunks = chunks.empty() ? nullptr : chunks.data();
-        c.filter_word = depth_filter_word((uint32_t)rnd(0, 65535) | ((uint32_t)rnd(0, 255) << 16));
-        std::vector<int64_t> out((size_t)LINK_ANSWER_WORDS * (size_t)std::max(n, 1), 77);
-        std::vector<int32_t> status((size_t)std::max(n, 1), -9);
-        CHECK(!check_args(c, out.data(), status.data()), "a good call is refused");
-        if (n) {
-            CHECK(check_args(c, nullptr, status.data()).code == VAPOR_E_ARG && check_args(c, out.data(), nullptr).code == VAPOR_E_ARG, "null outputs pass");
-            LinkCall d = c; d.names_len = -1;
-            CHECK(check_args(d, out.data(), status.data()).code == VAPOR_E_ARG, "a negative blob passes");
-            if (names_len) { d = c; d.names = nullptr; CHECK(check_args(d, out.data(), status.data()).code == VAPOR_E_ARG, "a null blob passes"); }
-        }
-        SpanPlan p;
-        CHECK(!plan_spans(c, status.data(), p), "a call below the size limit is refused");
-        for (int g = 0; g < n; ++g) {
-            CHECK(status[(size_t)g] == (bad[(size_t)g] ? REG_MALFORMED : 0), "region %d: status %d, bad %d", g, status[(size_t)g], (int)bad[(size_t)g]);
-            n_refused += bad[(size_t)g];
-        }
-        for (HostSpan& sp : p.spans) fake_scan(sp);
-        LinkLayout L;
-        CHECK(!layout(c, p, status.data(), L), "a layout below the size limit is refused");
-        CHECK((int)L.regs.size() == std::max(n, 1), "regions in the layout");
-        size_t n_sp = 0;
-        for (int g = 0; g < n; ++g) {
-            const LinkRegion& R = L.regs[(size_t)g];
-            const int64_t* f = fields.data() + (size_t)LINK_FIELDS * (size_t)g;
-            CHECK(R.span_first == (int32_t)n_sp, "region %d: span_first in the layout", g);
-            if (status[(size_t)g]) {
-                CHECK(R.span_n == 0 && R.name_len == 0 && R.tol == 0 && R.w0 == 0 && R.w3 == 0 && R.bits == 0, "region %d: a refused region's record", g);
-                continue;
-            }
-            const int64_t far = (int64_t)1 << 40;
-            CHECK(R.tid == tid[(size_t)g] && R.filter == c.filter_word && R.w0 == f[0] && R.w3 == f[1] && R.tol == f[4], "region %d: its record", g);
-            CHECK(R.x == (f[2] > far ? far : f[2]) && R.y == (f[3] < -far ? -far : f[3]) && R.min_clip == (f[5] < 1 ? 1 : f[5]), "region %d: clamped fields", g);
-            CHECK(R.bits == ((uint32_t)f[6] | (uint32_t)f[7] << 1 | (uint32_t)f[8] << 2) && R.name_off == (uint32_t)f[9] && R.name_len == (uint32_t)f[10], "region %d: bits and name", g);
-            CHECK((uint64_t)R.name_off + R.name_len <= (uint64_t)names_len, "region %d: its name leaves the blob", g);
-            CHECK(R.span_n == p.span_first[(size_t)g + 1] - p.span_first[(size_t)g], "region %d: span_n", g);
-            n_sp += (size_t)R.span_n;
-        }
-        const LinkMeta& M = L.meta;
-        const size_t nr = (size_t)std::max(n, 1), nb = std::max<size_t>(L.blks.size(), 1), ns = std::max<size_t>(L.spans.size(), 1);
-        const size_t offs[7] = {M.blks.off, M.spans.off, M.regs.off, M.names.off, M.blk_status.off, M.ans.off, M.reg_status.off};
-        const size_t sizes[7] = {24 * nb, 24 * ns, 72 * nr, std::max<size_t>((size_t)names_len, 1), 4 * nb, 20 * nr, 4 * nr};
-        size_t at = 0;
-        for (int t = 0; t < 7; ++t) { CHECK(offs[t] == at && at % 64 == 0, "table %d at %zu, not %zu", t, offs[t], at); at += up64(sizes[t]); }
-        CHECK(M.bytes == at && M.in_bytes == M.blk_status.off && M.back_bytes() == M.bytes - M.blk_status.off, "the block's sizes");
-        std::vector<uint8_t> h(M.bytes, 0xEE);
-        L.fill(h.data());
-        CHECK(!memcmp(M.regs.in(h.data()), L.regs.data(), 72 * nr) && (!names_len || !memcmp(M.names.in(h.data()), names.data(), (size_t)names_len)), "fill");
-        uint32_t* da = M.ans.in(h.data());
-        int32_t* rs = M.reg_status.in(h.data());
-        for (size_t g = 0; g < nr; ++g) {
-            for (int k = 0; k < LINK_ANSWER_WORDS; ++k) da[(size_t)LINK_ANSWER_WORDS * g + (size_t)k] = (uint32_t)rng();
-            da[(size_t)LINK_ANSWER_WORDS * g + 3] = (uint32_t)(int32_t)rnd(-255, 255);
-            rs[g] = one_in(5) ? rnd(1, 5) : 0;
-        }
-        std::vector<int32_t> st2 = status;
-        collect(c, M, h.data(), out.data(), st2.data());
-        for (int g = 0; g < n; ++g) {
-            const bool host_refused = status[(size_t)g] != 0, dev_refused = rs[(size_t)g] != 0;
-            CHECK(st2[(size_t)g] == (host_refused ? status[(size_t)g] : rs[(size_t)g]), "region %d: collected status", g);
-            for (int k = 0; k < LINK_ANSWER_WORDS; ++k) {
-                const uint32_t wd = da[(size_t)LINK_ANSWER_WORDS * (size_t)g + (size_t)k];
-                const int64_t want = host_refused || dev_refused ? 0 : (k == 3 ? (int64_t)(int32_t)wd : (int64_t)wd);
-                CHECK(out[(size_t)LINK_ANSWER_WORDS * (size_t)g + (size_t)k] == want, "region %d: word %d", g, k);
-            }
-        }
-        ++n_calls;
-        n_regions_seen += n;
     }
-    // the two "in one call" refusals the Python side halves a group on
+    static void bind(Call& c, const int64_t* fields, const EvDrawn& d)
     {
-        std::vector<int32_t> tid(40, 0), chunk_first(41), status(40);
-        std::vector<int64_t> fields;
-        std::vector<uint64_t> chunks;
-        const uint8_t names[2] = {'c', '1'};
-        for (int g = 0; g < 40; ++g) {
-            for (int64_t v : {0, 100, 40, 60, 50, 30, 1, 0, 0, 0, 2}) fields.push_back(v);
-            chunks.push_back((uint64_t)g << 44); chunks.push_back(((uint64_t)g << 44) + (((uint64_t)1 << 26) << 16));
-            chunk_first[(size_t)g + 1] = g + 1;
-        }
-        LinkCall c;
-        c.n_regions = 40; c.tid = tid.data(); c.regions = fields.data(); c.names = names; c.names_len = 2; c.chunk_first = chunk_first.data(); c.chunks = chunks.data();
-        SpanPlan p;
-        const Refusal r = plan_spans(c, status.data(), p);
-        CHECK(r.code == VAPOR_E_ARG && strstr(r.msg, "vapor_bam_links_device") && strstr(r.msg, "in one call"), "2.5 GB of blocks pass");
-        c.n_regions = 20;
-        CHECK(!plan_spans(c, status.data(), p), "1.25 GB of blocks are refused");
-        for (HostSpan& sp : p.spans) { sp.blks.push_back(Block{0, 6, 100, 0, 65536, 0}); sp.u_total = (uint64_t)120 << 20; sp.u_begin = 0; sp.u_end = 100; sp.got = sp.want; }
-        LinkLayout L;
-        const Refusal r2 = layout(c, p, status.data(), L);
-        CHECK(r2.code == VAPOR_E_ARG && strstr(r2.msg, "vapor_bam_links_device") && strstr(r2.msg, "in one call"), "2.4 GB of block data pass");
+        c.regions = fields; c.names = d.names.empty() ? nullptr : d.names.data(); c.names_len = (int64_t)d.names.size();
     }
-    printf("links plan: %ld calls with %ld regions (%ld refused): statuses, tables, the name blob, clamped fields and collected words equal the rule; both size refusals say \"in one call\"\n",
-           n_calls, n_regions_seen, n_refused);
-}
+    static void more_args(const Call& c, Out* out, int32_t* status)
+    {
+        Call d = c; d.names_len = -1;
+        CHECK(check_args(d, out, status).code == VAPOR_E_ARG, "a negative blob passes");
+        if (c.names_len) { d = c; d.names = nullptr; CHECK(check_args(d, out, status).code == VAPOR_E_ARG, "a null blob passes"); }
+    }
+    static void record(const LinkRegion& R, const Call& c, int g, bool refused)
+    {
+        const int64_t* f = c.regions + (size_t)FIELDS * (size_t)g;
+        if (refused) { CHECK(R.name_len == 0 && R.tol == 0 && R.w0 == 0 && R.w3 == 0 && R.bits == 0, "region %d: a refused region's record", g); return; }
+        const int64_t far = (int64_t)1 << 40;
+        CHECK(R.w0 == f[0] && R.w3 == f[1] && R.tol == f[4], "region %d: its record", g);
+        CHECK(R.x == (f[2] > far ? far : f[2]) && R.y == (f[3] < -far ? -far : f[3]) && R.min_clip == (f[5] < 1 ? 1 : f[5]), "region %d: clamped fields", g);
+        CHECK(R.bits == ((uint32_t)f[6] | (uint32_t)f[7] << 1 | (uint32_t)f[8] << 2) && R.name_off == (uint32_t)f[9] && R.name_len == (uint32_t)f[10], "region %d: bits and name", g);
+        CHECK((uint64_t)R.name_off + R.name_len <= (uint64_t)c.names_len, "region %d: its name leaves the blob", g);
+    }
+};
 
-// ================================================================================================================================
-// vapor_bam_support_device: SupCall's plan over the same plan_spans_of / layout_of
-// ================================================================================================================================
-static void check_support()
-{
-    long n_calls = 0, n_refused = 0, n_regions_seen = 0;
-    for (int it = 0; it < 1000; ++it) {
-        g_case = it;
-        const int n = one_in(15) ? 0 : rnd(1, 12);
-        std::vector<SRegion> regs;
-        std::vector<int32_t> tid((size_t)n), chunk_first((size_t)n + 1, 0);
-        std::vector<int64_t> fields((size_t)SUP_FIELDS * (size_t)n);
-        std::vector<uint64_t> chunks;
-        std::vector<char> bad((size_t)n, 0);
-        for (int g = 0; g < n; ++g) {
+struct SupMode {
+    using Call = SupCall; using Layout = SupLayout; using Word = uint32_t; using Out = int64_t;
+    static constexpr int FIELDS = SUP_FIELDS, WORDS = SUP_ANSWER_WORDS, ITERS = 1000;
+    static constexpr size_t REG_BYTES = 80, ANS_BYTES = 28;
+    static constexpr uint32_t SIGNED = 0;
+    static constexpr bool NAMES = false;
+    static constexpr const char* ENTRY = "vapor_bam_support_device";
+    static constexpr const char* NAME = "support";
+    static constexpr const char* EQUAL = "statuses, spans, arena, tables, clamped fields and collected words";
+    static constexpr int64_t EXAMPLE[FIELDS] = {0, 100, 40, 60, 50, 30, 30, 200, 255, 51, 30};
+    static void draw(EvDrawn& d)
+    {
+        for (int g = 0; g < d.n; ++g) {
             // the nine signature fields with their eight ways to be bad, then 9 flank < 1; 10 flank > 65535; 11 gmin < 1
             const int how = one_in(3) ? rnd(1, 11) : 0;
-            regs.push_back(sig_region(how <= 8 ? how : 0));
-            SRegion& r = regs.back();
-            int64_t* f = fields.data() + (size_t)SUP_FIELDS * (size_t)g;
-            for (int k = 0; k < SIG_FIELDS; ++k) f[k] = r.f[k];
+            EvRegion r = sig_region(how <= 8 ? how : 0);
+            int64_t* f = r.f;
             if (one_in(8)) f[8] = rnd(0, 255);
             f[9] = one_in(4) ? (one_in(2) ? 1 : 65535) : rnd(1, 65535);
             f[10] = one_in(6) ? ((int64_t)1 << rnd(28, 40)) : rnd(1, 5000);
             if (how == 9) f[9] = -(int64_t)rnd(0, 9);
             if (how == 10) f[9] = 65536 + rnd(0, 1 << 20);
             if (how == 11) f[10] = -(int64_t)rnd(0, 9);
-            bad[(size_t)g] = how != 0;
-            tid[(size_t)g] = r.tid;
-            for (auto& c : r.chunks) { chunks.push_back(c.first); chunks.push_back(c.second); }
-            chunk_first[(size_t)g + 1] = (int32_t)(chunks.size() / 2);
+            r.bad = how != 0;
             // the one statement, against the rule spelled out (how 8 is a chunk that descends: the fields are good)
             const bool fields_bad = how != 0 && how != 8;
-            CHECK(sup_region_ok(tid[(size_t)g], f) == !fields_bad, "region %d: sup_region_ok, how %d", g, how);
-            CHECK(!sup_region_ok(tid[(size_t)g], f) || sig_region_ok(tid[(size_t)g], f), "region %d: a support region is a signature region", g);
+            CHECK(sup_region_ok(r.tid, f) == !fields_bad, "region %d: sup_region_ok, how %d", g, how);
+            CHECK(!sup_region_ok(r.tid, f) || sig_region_ok(r.tid, f), "region %d: a support region is a signature region", g);
+            d.push(r, FIELDS);
         }
-        SupCall c;
-        c.n_regions = n; c.tid = tid.data(); c.regions = fields.data(); c.chunk_first = chunk_first.data();
-        c.chunks = chunks.empty() ? nullptr : chunks.data();
-        c.filter_word = depth_filter_word((uint32_t)rnd(0, 65535) | ((uint32_t)rnd(0, 255) << 16));
-        std::vector<int64_t> out((size_t)SUP_ANSWER_WORDS * (size_t)std::max(n, 1), 77);
+    }
+    static void bind(Call& c, const int64_t* fields, const EvDrawn&) { c.regions = fields; }
+    static void more_args(const Call&, Out*, int32_t*) {}
+    static void record(const SupRegion& R, const Call& c, int g, bool refused)
+    {
+        const int64_t* f = c.regions + (size_t)FIELDS * (size_t)g;
+        if (refused) { CHECK(R.mask == 0 && R.tol == 0 && R.w0 == 0 && R.w3 == 0 && R.flank == 0 && R.gmin == 0, "region %d: a refused region's record", g); return; }
+        sig_fields_rule(R, f, 255u, g);
+        CHECK(R.flank == f[9], "region %d: flank %d", g, R.flank);
+        CHECK(R.gmin == (f[10] > ((int64_t)1 << 28) ? ((int64_t)1 << 28) : f[10]) && R.gmin >= 1, "region %d: gmin %d of %lld", g, R.gmin, (long long)f[10]);
+        for (int64_t len : {(int64_t)0, (int64_t)1, f[10] - 1, f[10], f[10] + 1, ((int64_t)1 << 28) - 1})
+            if (len >= 0 && len < ((int64_t)1 << 28))
+                CHECK((len >= f[10]) == (len >= R.gmin), "region %d: the clamped blocking length admits other operations at %lld", g, (long long)len);
+    }
+};
+
+template <typename Mode>
+static void check_evidence()
+{
+    using Call = typename Mode::Call;
+    using Layout = typename Mode::Layout;
+    using Word = typename Mode::Word;
+    using Out = typename Mode::Out;
+    constexpr size_t F = (size_t)Mode::FIELDS, W = (size_t)Mode::WORDS;
+    long n_calls = 0, n_refused = 0, n_regions_seen = 0;
+    for (int it = 0; it < Mode::ITERS; ++it) {
+        g_case = it;
+        EvDrawn d;
+        d.n = one_in(15) ? 0 : rnd(1, 12);
+        Mode::draw(d);
+        const int n = d.n;
+        Call c;
+        c.n_regions = n; c.tid = d.tid.data(); c.chunk_first = d.chunk_first.data(); c.chunks = d.chunks.empty() ? nullptr : d.chunks.data();
+        Mode::bind(c, d.fields.data(), d);
+        const uint32_t low = (uint32_t)rnd(0, 65535), handle_word = low | ((uint32_t)rnd(0, 255) << 16);
+        c.filter_word = depth_filter_word(handle_word);
+        CHECK((c.filter_word & 0x704u) == 0x704u && (c.filter_word | 0x704u) == (handle_word | 0x704u), "filter word %x of %x", c.filter_word, handle_word);
+        std::vector<Out> out(W * (size_t)std::max(n, 1), 77);
         std::vector<int32_t> status((size_t)std::max(n, 1), -9);
         CHECK(!check_args(c, out.data(), status.data()), "a good call is refused");
         if (n) {
             CHECK(check_args(c, nullptr, status.data()).code == VAPOR_E_ARG && check_args(c, out.data(), nullptr).code == VAPOR_E_ARG, "null outputs pass");
-            SupCall d = c; d.regions = nullptr;
-            CHECK(check_args(d, out.data(), status.data()).code == VAPOR_E_ARG, "null regions pass");
-            d = c; d.n_regions = -1;
-            CHECK(check_args(d, out.data(), status.data()).code == VAPOR_E_ARG, "a negative count passes");
+            Call e = c; Mode::bind(e, nullptr, d);
+            CHECK(check_args(e, out.data(), status.data()).code == VAPOR_E_ARG, "null bounds or regions pass");
+            e = c; e.n_regions = -1;
+            CHECK(check_args(e, out.data(), status.data()).code == VAPOR_E_ARG, "a negative count passes");
+            Mode::more_args(c, out.data(), status.data());
         }
         SpanPlan p;
         CHECK(!plan_spans(c, status.data(), p), "a call below the size limit is refused");
+        // the statuses and the spans, against the rule stated per region
         size_t si = 0, stage = 0;
         for (int g = 0; g < n; ++g) {
-            CHECK(status[(size_t)g] == (bad[(size_t)g] ? REG_MALFORMED : 0), "region %d: status %d, bad %d", g, status[(size_t)g], (int)bad[(size_t)g]);
+            CHECK(status[(size_t)g] == (d.bad[(size_t)g] ? REG_MALFORMED : 0), "region %d: status %d, bad %d", g, status[(size_t)g], (int)d.bad[(size_t)g]);
             CHECK(p.span_first[(size_t)g] == (int32_t)si, "region %d: span_first", g);
-            if (bad[(size_t)g]) { ++n_refused; continue; }
-            for (auto& ch : regs[(size_t)g].chunks) {
+            if (d.bad[(size_t)g]) { ++n_refused; continue; }
+            for (int32_t k = d.chunk_first[(size_t)g]; k < d.chunk_first[(size_t)g + 1]; ++k) {
+                const uint64_t cs = d.chunks[2 * (size_t)k], ce = d.chunks[2 * (size_t)k + 1];
                 CHECK(si < p.spans.size(), "region %d: a span is missing", g);
                 const HostSpan& sp = p.spans[si++];
-                const size_t want = (size_t)((ch.second >> 16) - (ch.first >> 16)) + ((ch.second & 0xFFFFu) ? 65536 + 64 : 0);
-                CHECK(sp.region == g && sp.cs == ch.first && sp.ce == ch.second && sp.want == want && sp.stage_off == stage, "region %d: span fields", g);
+                const size_t want = (size_t)((ce >> 16) - (cs >> 16)) + ((ce & 0xFFFFu) ? 65536 + 64 : 0);
+                CHECK(sp.region == g && sp.cs == cs && sp.ce == ce && sp.file_off == (int64_t)(cs >> 16) && sp.want == want && sp.stage_off == stage, "region %d: span fields", g);
                 stage += up64(want);
             }
         }
         CHECK(si == p.spans.size() && p.span_first[(size_t)n] == (int32_t)si && p.stage_bytes == stage, "spans %zu of %zu, stage %zu of %zu", si, p.spans.size(), stage, p.stage_bytes);
+        // the layout after a made-up scan
         for (HostSpan& sp : p.spans) fake_scan(sp);
-        std::vector<int32_t> before = status;
-        SupLayout L;
+        const std::vector<int32_t> before = status;
+        Layout L;
         CHECK(!layout(c, p, status.data(), L), "a layout below the size limit is refused");
+        size_t arena = 0, n_blk = 0, n_sp = 0;
         CHECK((int)L.regs.size() == std::max(n, 1), "regions in the layout");
-        size_t n_sp = 0, arena = 0, n_blk = 0;
         for (int g = 0; g < n; ++g) {
             bool scan_bad = false;
             for (int32_t s = p.span_first[(size_t)g]; s < p.span_first[(size_t)g + 1]; ++s) scan_bad |= p.spans[(size_t)s].bad;
             CHECK(status[(size_t)g] == (scan_bad ? REG_MALFORMED : before[(size_t)g]), "region %d: status after the scan", g);
-            const SupRegion& R = L.regs[(size_t)g];
-            const int64_t* f = fields.data() + (size_t)SUP_FIELDS * (size_t)g;
+            const auto& R = L.regs[(size_t)g];
+            const bool refused = status[(size_t)g] != 0;
             CHECK(R.span_first == (int32_t)n_sp, "region %d: span_first in the layout", g);
-            if (status[(size_t)g]) {
-                CHECK(R.span_n == 0 && R.mask == 0 && R.tol == 0 && R.w0 == 0 && R.w3 == 0 && R.flank == 0 && R.gmin == 0, "region %d: a refused region's record", g);
-                continue;
-            }
-            // the record: the fields as given where they are in range, clamped where a clamp admits the same records
-            CHECK(R.tid == tid[(size_t)g] && R.filter == c.filter_word && R.w0 == f[0] && R.w3 == f[1] && R.x0 == f[2] && R.x1 == f[3] && R.tol == f[4], "region %d: its record", g);
-            CHECK(R.min_clip == (f[5] < 1 ? 1 : f[5]) && R.mask == ((uint32_t)f[8] & 255u) && R.flank == f[9], "region %d: min_clip, mask %u, flank %d", g, R.mask, R.flank);
-            auto clamped = [](int64_t v) { return v < -1 ? (int64_t)-1 : (v > ((int64_t)1 << 28) ? ((int64_t)1 << 28) : v); };
-            CHECK(R.nmin == clamped(f[6]) && R.nmax == clamped(f[7]) && R.nmin <= R.nmax, "region %d: length bounds", g);
-            CHECK(R.gmin == (f[10] > ((int64_t)1 << 28) ? ((int64_t)1 << 28) : f[10]) && R.gmin >= 1, "region %d: gmin %d of %lld", g, R.gmin, (long long)f[10]);
-            for (int64_t len : {(int64_t)0, (int64_t)1, f[10] - 1, f[10], f[10] + 1, ((int64_t)1 << 28) - 1})
-                if (len >= 0 && len < ((int64_t)1 << 28))
-                    CHECK((len >= f[10]) == (len >= R.gmin), "region %d: the clamped blocking length admits other operations at %lld", g, (long long)len);
+            Mode::record(R, c, g, refused);
+            if (refused) { CHECK(R.span_n == 0, "a refused region has spans"); continue; }
+            CHECK(R.tid == d.tid[(size_t)g] && R.filter == c.filter_word, "region %d: contig and filter", g);
             CHECK(R.span_n == p.span_first[(size_t)g + 1] - p.span_first[(size_t)g], "region %d: span_n", g);
             for (int32_t s = p.span_first[(size_t)g]; s < p.span_first[(size_t)g + 1]; ++s) {
                 const HostSpan& sp = p.spans[(size_t)s];
-                const BamSpan& d = L.spans[n_sp++];
-                CHECK(d.u_begin == arena + sp.u_begin && d.u_end == arena + sp.u_end && d.u_limit == arena + sp.u_total && d.blk_first == n_blk && d.blk_n == sp.blks.size(),
+                const BamSpan& b = L.spans[n_sp++];
+                CHECK(b.u_begin == arena + sp.u_begin && b.u_end == arena + sp.u_end && b.u_limit == arena + sp.u_total && b.blk_first == n_blk && b.blk_n == sp.blks.size(),
                       "region %d: a span in the arena", g);
-                n_blk += sp.blks.size();
+                for (const Block& k : sp.blks) {
+                    const BgzfBlk& B = L.blks[n_blk++];
+                    CHECK(B.c_off == sp.stage_off + k.payload() && B.c_len == k.c_len() && B.u_off == arena + k.u && B.u_len == k.isize && B.crc == k.crc, "a block of region %d", g);
+                }
                 arena += up64(sp.u_total);
             }
         }
         CHECK(L.arena == arena && L.blks.size() == n_blk && L.spans.size() == n_sp, "arena %zu of %zu", arena, L.arena);
-        const SupMeta& M = L.meta;
+        // the metadata block: the tables in order, on multiples of 64, without overlap (a call without a blob has a names table of
+        // no bytes); what goes in first, what comes back last
+        const auto& M = L.meta;
         const size_t nr = (size_t)std::max(n, 1), nb = std::max<size_t>(n_blk, 1), ns = std::max<size_t>(n_sp, 1);
-        const size_t offs[6] = {M.blks.off, M.spans.off, M.regs.off, M.blk_status.off, M.ans.off, M.reg_status.off};
-        const size_t sizes[6] = {24 * nb, 24 * ns, 80 * nr, 4 * nb, 28 * nr, 4 * nr};
+        const size_t offs[7] = {M.blks.off, M.spans.off, M.regs.off, M.names.off, M.blk_status.off, M.ans.off, M.reg_status.off};
+        const size_t sizes[7] = {24 * nb, 24 * ns, Mode::REG_BYTES * nr, Mode::NAMES ? std::max<size_t>(d.names.size(), 1) : 0, 4 * nb, Mode::ANS_BYTES * nr, 4 * nr};
         size_t at = 0;
-        for (int t = 0; t < 6; ++t) { CHECK(offs[t] == at && at % 64 == 0, "table %d at %zu, not %zu", t, offs[t], at); at += up64(sizes[t]); }
+        for (int t = 0; t < 7; ++t) { CHECK(offs[t] == at && at % 64 == 0, "table %d at %zu, not %zu", t, offs[t], at); at += up64(sizes[t]); }
         CHECK(M.bytes == at && M.in_bytes == M.blk_status.off && M.back_bytes() == M.bytes - M.blk_status.off, "the block's sizes");
+        // fill and collect on a heap block of exactly those bytes
         std::vector<uint8_t> h(M.bytes, 0xEE);
         L.fill(h.data());
-        CHECK(!memcmp(M.regs.in(h.data()), L.regs.data(), 80 * nr) && (!n_blk || !memcmp(M.blks.in(h.data()), L.blks.data(), 24 * n_blk)) &&
-              (!n_sp || !memcmp(M.spans.in(h.data()), L.spans.data(), 24 * n_sp)), "fill");
-        uint32_t* da = M.ans.in(h.data());
+        CHECK(!memcmp(M.regs.in(h.data()), L.regs.data(), Mode::REG_BYTES * nr) && (!n_blk || !memcmp(M.blks.in(h.data()), L.blks.data(), 24 * n_blk)) &&
+              (!n_sp || !memcmp(M.spans.in(h.data()), L.spans.data(), 24 * n_sp)) && (d.names.empty() || !memcmp(M.names.in(h.data()), d.names.data(), d.names.size())), "fill");
+        Word* da = M.ans.in(h.data());
         int32_t* rs = M.reg_status.in(h.data());
         for (size_t g = 0; g < nr; ++g) {
-            for (int k = 0; k < SUP_ANSWER_WORDS; ++k) da[(size_t)SUP_ANSWER_WORDS * g + (size_t)k] = (uint32_t)rng();
+            for (size_t k = 0; k < W; ++k) da[W * g + k] = (Word)rng();
+            for (size_t k = 0; k < W; ++k) if ((Mode::SIGNED >> k) & 1u) da[W * g + k] = (Word)(uint32_t)(int32_t)rnd(-255, 255);
             rs[g] = one_in(5) ? rnd(1, 5) : 0;
         }
         std::vector<int32_t> st2 = status;
@@ -1557,9 +1303,10 @@ static void check_support()
         for (int g = 0; g < n; ++g) {
             const bool host_refused = status[(size_t)g] != 0, dev_refused = rs[(size_t)g] != 0;
             CHECK(st2[(size_t)g] == (host_refused ? status[(size_t)g] : rs[(size_t)g]), "region %d: collected status", g);
-            for (int k = 0; k < SUP_ANSWER_WORDS; ++k) {
-                const int64_t want = host_refused || dev_refused ? 0 : (int64_t)da[(size_t)SUP_ANSWER_WORDS * (size_t)g + (size_t)k];
-                CHECK(out[(size_t)SUP_ANSWER_WORDS * (size_t)g + (size_t)k] == want, "region %d: word %d", g, k);
+            for (size_t k = 0; k < W; ++k) {
+                const Word wd = da[W * (size_t)g + k];
+                const Out want = host_refused || dev_refused ? (Out)0 : ((Mode::SIGNED >> k) & 1u) ? (Out)(int32_t)wd : (Out)wd;
+                CHECK(out[W * (size_t)g + k] == want, "region %d: word %zu", g, k);
             }
         }
         ++n_calls;
@@ -1571,24 +1318,27 @@ static void check_support()
         std::vector<int64_t> fields;
         std::vector<uint64_t> chunks;
         for (int g = 0; g < 40; ++g) {
-            for (int64_t v : {0, 100, 40, 60, 50, 30, 30, 200, 255, 51, 30}) fields.push_back(v);
+            fields.insert(fields.end(), Mode::EXAMPLE, Mode::EXAMPLE + F);
             chunks.push_back((uint64_t)g << 44); chunks.push_back(((uint64_t)g << 44) + (((uint64_t)1 << 26) << 16));
             chunk_first[(size_t)g + 1] = g + 1;
         }
-        SupCall c;
-        c.n_regions = 40; c.tid = tid.data(); c.regions = fields.data(); c.chunk_first = chunk_first.data(); c.chunks = chunks.data();
+        EvDrawn d;
+        d.names = {'c', '1'};
+        Call c;
+        c.n_regions = 40; c.tid = tid.data(); c.chunk_first = chunk_first.data(); c.chunks = chunks.data();
+        Mode::bind(c, fields.data(), d);
         SpanPlan p;
         const Refusal r = plan_spans(c, status.data(), p);
-        CHECK(r.code == VAPOR_E_ARG && strstr(r.msg, "vapor_bam_support_device") && strstr(r.msg, "in one call"), "2.5 GB of blocks pass");
+        CHECK(r.code == VAPOR_E_ARG && strstr(r.msg, Mode::ENTRY) && strstr(r.msg, "in one call"), "2.5 GB of blocks pass");
         c.n_regions = 20;
         CHECK(!plan_spans(c, status.data(), p), "1.25 GB of blocks are refused");
         for (HostSpan& sp : p.spans) { sp.blks.push_back(Block{0, 6, 100, 0, 65536, 0}); sp.u_total = (uint64_t)120 << 20; sp.u_begin = 0; sp.u_end = 100; sp.got = sp.want; }
-        SupLayout L;
+        Layout L;
         const Refusal r2 = layout(c, p, status.data(), L);
-        CHECK(r2.code == VAPOR_E_ARG && strstr(r2.msg, "vapor_bam_support_device") && strstr(r2.msg, "in one call"), "2.4 GB of block data pass");
+        CHECK(r2.code == VAPOR_E_ARG && strstr(r2.msg, Mode::ENTRY) && strstr(r2.msg, "in one call"), "2.4 GB of block data pass");
     }
-    printf("support plan: %ld calls with %ld regions (%ld refused): statuses, spans, arena, tables, clamped fields and collected words equal the rule; both size refusals say \"in one call\"\n",
-           n_calls, n_regions_seen, n_refused);
+    printf("%s plan: %ld calls with %ld regions (%ld refused): %s equal the rule; both size refusals say \"in one call\"\n", Mode::NAME, n_calls, n_regions_seen, n_refused,
+           Mode::EQUAL);
 }
 
 // ================================================================================================================================
@@ -1662,10 +1412,10 @@ int main()
     check_collect();
     check_fasta();
     check_fasta_caps();
-    check_depth();          // (behind the others: the calls above draw from the one seeded stream, and their counts are quoted)
-    check_signature();
-    check_links();
-    check_support();
+    check_evidence<DepthMode>();          // (behind the others: the calls above draw from the one seeded stream, and their counts are quoted)
+    check_evidence<SigMode>();
+    check_evidence<LinkMode>();
+    check_evidence<SupMode>();
     printf("readplan_check: all equal\n");
     return 0;
 }

@@ -14,6 +14,7 @@ environment (the reference bundles none), so it has not been run on one.
 """
 from __future__ import annotations
 
+import contextlib
 import struct
 import threading
 import zlib
@@ -327,22 +328,22 @@ class BamFile:
         (vapor_bam_chop_tagged) every entry also carries the record's hap and ps; with `right` (vapor_bam_chop_right, `--both-ends`)
         the right-anchored reads of the window, reverse complemented (seqio._chop_records).  sites (`--phase-vcf`, with tagged: a
         phase.Sites): hap and ps come from the locus's phased sites instead (vapor_bam_chop_haplotag)."""
-        import ctypes
+        return self._chop_native(chrom, start, end, flank_length, False, tagged, right, sites) or []
+
+    def _chop_native(self, chrom, start, end, flank_length, raw, tagged, right, sites):
+        """chop_native (raw false) and chop_native_raw (raw true): the .bai lookup, then _chop_with on a leased handle.  None for
+        an unknown contig or a window no chunk overlaps (and from _chop_with's raw form without a kept read)."""
         from . import _lib
         lib = _lib.load()
         tid = self.tid.get(chrom)
         if tid is None:
-            return []
+            return None
         ch = self.index.chunks(tid, max(int(start) - 1, 0), int(end))
         if not ch:
-            return []
-        tl = self._take_handle(lib)
-        try:
-            return self._chop_with(lib, tl, tid, ch, start, end, flank_length, tagged=tagged, right=right,
+            return None
+        with self.handle(lib) as tl:
+            return self._chop_with(lib, tl, tid, ch, start, end, flank_length, raw=raw, tagged=tagged, right=right,
                                    sites=self._locus_sites(sites, chrom, start, end) if tagged else None)
-        finally:
-            with self._lock:
-                self._free.append(tl)
 
     @staticmethod
     def _locus_sites(sites, chrom, start, end):
@@ -359,18 +360,15 @@ class BamFile:
         """chop_native's answer as numbers: (text, offsets, lengths, miss_bp) - read r is text[offsets[r] : offsets[r] + lengths[r]]
         - for callers that hand the reads on by address (vapor_amd.fastpath) instead of making a string per read; with `tagged`
         also hap and ps per read (ps: phase.PS_NONE for none)."""
-        from . import _lib
-        lib = _lib.load()
-        tid = self.tid.get(chrom)
-        if tid is None:
-            return None
-        ch = self.index.chunks(tid, max(int(start) - 1, 0), int(end))
-        if not ch:
-            return None
+        return self._chop_native(chrom, start, end, flank_length, True, tagged, right, sites)
+
+    @contextlib.contextmanager
+    def handle(self, lib):
+        """The lease of a native handle: `with b.handle(lib) as tl:` takes one as _take_handle does and puts it back on the free
+        list on every way out of the block, an exception included.  Every native and device call of the file runs inside one."""
         tl = self._take_handle(lib)
         try:
-            return self._chop_with(lib, tl, tid, ch, start, end, flank_length, raw=True, tagged=tagged, right=right,
-                                   sites=self._locus_sites(sites, chrom, start, end) if tagged else None)
+            yield tl
         finally:
             with self._lock:
                 self._free.append(tl)
@@ -510,14 +508,10 @@ class BamFile:
         out = np.zeros(len(module.ZERO), dtype=module.DTYPE)
         flat = np.asarray(ch, dtype=np.uint64).reshape(-1)
         more = () if names is None else (names, len(names))
-        tl = self._take_handle(lib)
-        try:
+        with self.handle(lib) as tl:
             if getattr(lib, module.ENTRIES[0])(tl["native"], int(tid), r.ctypes.data, *more, len(flat) // 2,
                                                flat.ctypes.data if len(flat) else None, out.ctypes.data) != 0:
                 raise ValueError(lib.vapor_bam_last_error().decode())
-        finally:
-            with self._lock:
-                self._free.append(tl)
         return [int(x) for x in out]
 
     @staticmethod

@@ -391,6 +391,70 @@ class SamtoolsHybrid(SamtoolsCLI):
         return fa.lines(region)
 
 
+# The scheduler of the device readers' calls: InProcessBam.chop_many_device and ._evidence_many hand their
+# regions' .bai chunks to the three functions below and keep only what is theirs - the windows, the arguments of a call, and
+# what becomes of an answer and of a region no call takes.
+def _flat_chunks(chunk_lists):
+    """The regions' chunk lists as the arrays a device reader takes: (chunk_first, flat_a) - chunk_first int32 of len + 1, region
+    k's chunks are flat_a[chunk_first[k]:chunk_first[k + 1]]; flat_a uint64 of shape (m, 2), a chunk's two virtual offsets a
+    row.  A region without chunks is an empty range; no region at all is ([0], shape (0, 2))."""
+    import numpy as np
+    chunk_first = np.zeros(len(chunk_lists) + 1, dtype=np.int32)
+    flat = []
+    for k, chunks in enumerate(chunk_lists):
+        for c in chunks:
+            flat.append(c[0])
+            flat.append(c[1])
+        chunk_first[k + 1] = len(flat) >> 1
+    return chunk_first, np.asarray(flat, dtype=np.uint64).reshape(-1, 2)
+
+
+def _size_groups(chunk_first, flat_a):
+    """The regions cut into the groups [(a, e), ...] of one call each, in order and without a gap.  One call holds the blocks of
+    all its regions on the device at once, compressed and inflated: a region counts (end >> 16) - (begin >> 16) + 65600
+    compressed bytes a chunk (the file range and a last block), and a group always takes its first region and a further one
+    only while the sum stays within VAPOR_BAM_DEVICE_BATCH_MB (default 192, read at every call; in MB of 2^20 bytes) - the
+    inflated data of such a group stays far below the library's 2 GB a call."""
+    import numpy as np
+    n = len(chunk_first) - 1
+    comp = np.zeros(n, dtype=np.int64)
+    if len(flat_a):
+        per_chunk = ((flat_a[:, 1] >> np.uint64(16)) - (flat_a[:, 0] >> np.uint64(16))).astype(np.int64) + 65600
+        np.add.at(comp, np.repeat(np.arange(n), np.diff(chunk_first)), per_chunk)
+    cap = int(os.environ.get("VAPOR_BAM_DEVICE_BATCH_MB", "192")) << 20
+    groups = []
+    a = 0
+    while a < n:
+        e, tot = a, 0
+        while e < n and (e == a or tot + int(comp[e]) <= cap):
+            tot += int(comp[e])
+            e += 1
+        groups.append((a, e))
+        a = e
+    return groups
+
+
+def _run_groups(groups, call):
+    """call(a, e) for every group, from the front: yields (a, e, what the call returned).  A group the library refuses for its
+    size (a VaporHipError that says "in one call") goes back to the front as its halves [a, (a + e) // 2) and [(a + e) // 2, e);
+    a single region refused so - its blocks alone are more than a call takes - is yielded as (a, a + 1, None), the host
+    route's.  Every other error passes through."""
+    from . import _lib
+    groups = list(groups)
+    while groups:
+        a, e = groups.pop(0)
+        try:
+            got = call(a, e)
+        except _lib.VaporHipError as err:
+            if "in one call" not in str(err):
+                raise
+            if e - a >= 2:
+                groups[:0] = [(a, (a + e) // 2), ((a + e) // 2, e)]
+                continue
+            got = None
+        yield a, e, got
+
+
 class InProcessBam(SamtoolsHybrid):
     """BAM and BAI read in-process as well (vapor_amd.bamio): no process per locus at all, and the records reach
     the trimming code as fields, not as text to be split again.  The default backend."""
@@ -566,67 +630,37 @@ class InProcessBam(SamtoolsHybrid):
                 raise NotImplementedError("no haplotagging device reader")
             from . import phase
             tables = phase.device_site_tables(sites, chroms, starts, ends)
-        tids = np.zeros(n, dtype=np.int32)
-        chunk_first = np.zeros(n + 1, dtype=np.int32)
-        flat = []
+        # (a region on a contig the file does not have: tid 0 and no chunk)
+        tid_of = [b.tid.get(c) for c in chroms]
+        tids = np.asarray([t or 0 for t in tid_of], dtype=np.int32)
         index_chunks = b.index.chunks
-        tid_of = b.tid
-        for g in range(n):
-            t = tid_of.get(chroms[g])
-            if t is not None:
-                tids[g] = t
-                for c in index_chunks(t, max(int(starts[g]) - 1, 0), int(ends[g])):
-                    flat.append(c[0])
-                    flat.append(c[1])
-            chunk_first[g + 1] = len(flat) >> 1
-        # One call holds the blocks of all its regions on the device at once (compressed and inflated): regions in groups of
-        # at most ~192 MB of compressed blocks (their inflated data stays far below the library's 2 GB a call), a group that the
-        # library still refuses for its size in halves.
-        flat_a = np.asarray(flat, dtype=np.uint64).reshape(-1, 2)
-        comp = np.zeros(n, dtype=np.int64)
-        if len(flat_a):
-            per_chunk = ((flat_a[:, 1] >> np.uint64(16)) - (flat_a[:, 0] >> np.uint64(16))).astype(np.int64) + 65600
-            np.add.at(comp, np.repeat(np.arange(n), np.diff(chunk_first)), per_chunk)
-        cap = int(os.environ.get("VAPOR_BAM_DEVICE_BATCH_MB", "192")) << 20
-        groups = []
-        a = 0
-        while a < n:
-            e, tot = a, 0
-            while e < n and (e == a or tot + int(comp[e]) <= cap):
-                tot += int(comp[e])
-                e += 1
-            groups.append((a, e))
-            a = e
-        tl = b._take_handle(lib)
+        chunk_first, flat_a = _flat_chunks([index_chunks(t, max(int(starts[g]) - 1, 0), int(ends[g])) if t is not None else ()
+                                            for g, t in enumerate(tid_of)])
+
+        def call(a, e):
+            c0, c1 = int(chunk_first[a]), int(chunk_first[e])
+            if tables is not None:                  # (the batch's slice of the site tables, its offsets from zero)
+                sf, ent, pf, psv = tables
+                more["sites"] = (sf[a:e + 1] - sf[a], ent[int(sf[a]):int(sf[e])], pf[a:e + 1] - pf[a], psv[int(pf[a]):int(pf[e])])
+            return engine.bam_chop_device(tl["native"], tids[a:e], starts[a:e], ends[a:e], flanks[a:e], chunk_first[a:e + 1] - c0,
+                                          flat_a[c0:c1].reshape(-1), max_keep, **more)
         parts, batches = [], []
-        try:
-            while groups:
-                a, e = groups.pop(0)
-                c0, c1 = int(chunk_first[a]), int(chunk_first[e])
-                if tables is not None:                  # (the batch's slice of the site tables, its offsets from zero)
-                    sf, ent, pf, psv = tables
-                    more["sites"] = (sf[a:e + 1] - sf[a], ent[int(sf[a]):int(sf[e])], pf[a:e + 1] - pf[a], psv[int(pf[a]):int(pf[e])])
-                try:
-                    got = engine.bam_chop_device(tl["native"], tids[a:e], starts[a:e], ends[a:e], flanks[a:e], chunk_first[a:e + 1] - c0,
-                                                 flat_a[c0:c1].reshape(-1), max_keep, **more)
-                except _lib.VaporHipError as err:
-                    if "in one call" in str(err) and e - a >= 2:
-                        groups[:0] = [(a, (a + e) // 2), ((a + e) // 2, e)]
-                        continue
-                    if "in one call" in str(err):
+        with b.handle(lib) as tl:
+            try:
+                for a, e, got in _run_groups(_size_groups(chunk_first, flat_a), call):
+                    if got is None:
                         # one region whose blocks alone are more than a call takes: the host route's (it streams them)
                         parts.append((np.zeros(2, dtype=np.int32), np.zeros(0, dtype=np.uint64), np.zeros(0, dtype=np.int64),
                                       np.zeros(0, dtype=np.int64), np.ones(1, dtype=np.int32), np.zeros(0, dtype=np.uint32),
                                       np.zeros(1, dtype=np.int64), np.zeros(1, dtype=np.int32)))
                         continue
-                    for bt in batches:
-                        bt.close()
-                    raise
-                parts.append(got[:5] + got[6:])
-                batches.append(got[5])
-        finally:
-            with b._lock:
-                b._free.append(tl)
+                    parts.append(got[:5] + got[6:])
+                    batches.append(got[5])
+            except BaseException:
+                # (whatever ends the run early: the batches so far are closed here, on the thread that made them)
+                for bt in batches:
+                    bt.close()
+                raise
         kf = np.zeros(n + 1, dtype=np.int32)
         w = 0
         g = 0
@@ -647,8 +681,8 @@ class InProcessBam(SamtoolsHybrid):
         return int(b.refs[t][1]) if t is not None else 0
 
     def _evidence_many(self, module, engine, bam: str, chroms, rows, partners=None):
-        """The routes of the evidence readers over a BAM file.  The regions go to the device in groups by compressed size, like
-        chop_many_device's, a group the library refuses for its size ("in one call") in halves (module.ENTRIES[1] through the
+        """The routes of the evidence readers over a BAM file.  The regions go to the device in groups by compressed size
+        (_size_groups), a group the library refuses for its size ("in one call") in halves (_run_groups; module.ENTRIES[1] through the
         Engine's module.DEVICE: one wavefront a region); a region the device hands back with a status - for links one with a
         record whose aux area is malformed among them -, and every region with VAPOR_BAM_DEVICE=0 or without a device reader,
         goes to the native host reader (the BamFile's module.NATIVE).  A library without the entries, one without the read
@@ -703,54 +737,24 @@ class InProcessBam(SamtoolsHybrid):
             engine = None
         if engine is not None and hasattr(engine, device):
             host = []
-            m = len(todo)
             tids = np.asarray([tid_of[chroms[g]] for g in todo], dtype=np.int32)
-            chunk_first = np.zeros(m + 1, dtype=np.int32)
-            flat = []
-            for k, g in enumerate(todo):
-                for c in chunks_of[g]:
-                    flat.append(c[0])
-                    flat.append(c[1])
-                chunk_first[k + 1] = len(flat) >> 1
-            flat_a = np.asarray(flat, dtype=np.uint64).reshape(-1, 2)
-            comp = np.zeros(m, dtype=np.int64)
-            if len(flat_a):
-                per_chunk = ((flat_a[:, 1] >> np.uint64(16)) - (flat_a[:, 0] >> np.uint64(16))).astype(np.int64) + 65600
-                np.add.at(comp, np.repeat(np.arange(m), np.diff(chunk_first)), per_chunk)
-            cap = int(os.environ.get("VAPOR_BAM_DEVICE_BATCH_MB", "192")) << 20
-            groups = []
-            a = 0
-            while a < m:
-                e, tot = a, 0
-                while e < m and (e == a or tot + int(comp[e]) <= cap):
-                    tot += int(comp[e])
-                    e += 1
-                groups.append((a, e))
-                a = e
+            chunk_first, flat_a = _flat_chunks([chunks_of[g] for g in todo])
             bt = bounds[todo]
-            tl = b._take_handle(lib)
-            try:
-                while groups:
-                    a, e = groups.pop(0)
-                    c0, c1 = int(chunk_first[a]), int(chunk_first[e])
-                    try:
-                        cov, status = getattr(engine, device)(tl["native"], tids[a:e], bt[a:e], chunk_first[a:e + 1] - c0, flat_a[c0:c1].reshape(-1), **more)
-                    except _lib.VaporHipError as err:
-                        if "in one call" in str(err) and e - a >= 2:
-                            groups[:0] = [(a, (a + e) // 2), ((a + e) // 2, e)]
-                            continue
-                        if "in one call" in str(err):
-                            host.append(todo[a])          # (one region whose blocks alone are more than a call takes)
-                            continue
-                        raise
+
+            def call(a, e):
+                c0, c1 = int(chunk_first[a]), int(chunk_first[e])
+                return getattr(engine, device)(tl["native"], tids[a:e], bt[a:e], chunk_first[a:e + 1] - c0, flat_a[c0:c1].reshape(-1), **more)
+            with b.handle(lib) as tl:
+                for a, e, got in _run_groups(_size_groups(chunk_first, flat_a), call):
+                    if got is None:
+                        host.append(todo[a])              # (one region whose blocks alone are more than a call takes)
+                        continue
+                    cov, status = got
                     for k in range(a, e):
                         if status[k - a]:
                             host.append(todo[k])
                         else:
                             out[todo[k]] = [int(x) for x in cov[k - a]]
-            finally:
-                with b._lock:
-                    b._free.append(tl)
         for g in host:
             out[g] = getattr(b, native)(tid_of[chroms[g]], bounds[g], chunks_of[g], **more)
         return out
