@@ -206,7 +206,9 @@ int vapor_plan_fetch_hits(vapor_plan* plan, int64_t n_sel, const int64_t* pair_i
  * (ref_a, alt_a); 2: within_10Perc_m1b (SF:277-294); 3: directed_dis_m1b_redefine_diagnal
  * (SF:241-257); 0: a deletion read - abs_dis_m1b on (ref_a, alt_a) and within_10Perc_m1b on
  * (ref_b, alt_b), the smaller score wins (SF:1718-1726).  len_ref / len_alt are the full allele
- * lengths the gates divide by.  Reads must be sorted by locus.
+ * lengths the gates divide by, taken as given (they are not compared with the sequences) and at least 1: the
+ * reference divides by zero at 0.  A scorer whose pair failed (word 15 of its record is not 0) scores nothing, so
+ * the read is skipped - a deletion read keeps the score of its other scorer.  Reads must be sorted by locus.
  */
 typedef struct vapor_read {
     int32_t ref_a, alt_a, ref_b, alt_b;
