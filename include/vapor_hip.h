@@ -333,6 +333,26 @@ int vapor_clean_hits_wide(vapor_ctx* ctx, int64_t n_lists, const int32_t* hits_j
 int vapor_anyk_batch(vapor_ctx* ctx, vapor_seqset* set, int64_t n_pairs, const vapor_pair* pairs, int64_t* stats,
                      int32_t* hits_ji, int64_t hits_capacity, int64_t* hit_off);
 
+/* ---- `--realign`: the banded edit distance of a read against an allele ------ */
+/*
+ * For every pair, with a = seq1 (n symbols) and b = seq2 from symbol off2 on (m symbols): the edit distance of a against b inside
+ * the band |i - j| <= band, the start anchored at (0, 0), both ends free.  D[0][0] = 0; a cell (i, j) exists iff 0 <= i <= n,
+ * 0 <= j <= m and |i - j| <= band; D[i][j] is the minimum over its existing predecessors of D[i-1][j-1] + (0 if a[i-1] matches
+ * b[j-1] else 1), D[i-1][j] + 1 and D[i][j-1] + 1; d is the minimum of D over the existing cells of the last row (i = n) and of
+ * the last column (j = m).  Symbols are the codes of the 4-bit plane: two match iff both are A, C, G or T in either case and the
+ * same base - case never matters; N, an IUPAC code and any other byte match nothing, not even themselves.
+ * out[2t] = d, out[2t + 1] = 0 for pair t; its k and flags are ignored.  A pair with a bad index, off2 outside 0 .. len(seq2)
+ * or a sequence longer than VAPOR_MAX_SEQ_LEN gets out[2t] = -1 and out[2t + 1] = VAPOR_E_ARG, and the call still returns
+ * VAPOR_OK.  The call itself returns VAPOR_E_ARG for a band outside 1 .. VAPOR_MAX_BAND or n_pairs < 0; n_pairs == 0 is
+ * VAPOR_OK.  Any sequence set will do - bytes, derived sequences, the device-held BAM bases of vapor_seqset_create_mixed - since
+ * only the 4-bit plane and the lengths are read.  One upload of the pair table, one launch (realign_kernel: one wavefront a
+ * pair), one copy back, on the context's stream; the call returns when out is filled.  A library without a device (the CPU twin
+ * of the tests, whose oracle/ sources do not get the entry) exports the name and refuses every call with VAPOR_E_ARG; there is no
+ * host route: a caller without the kernel has no `--realign`.
+ */
+#define VAPOR_MAX_BAND 512
+int vapor_realign_batch(vapor_ctx* ctx, vapor_seqset* set, int64_t n_pairs, const vapor_pair* pairs, int32_t band, int32_t* out);
+
 /*
  * Host helper of the read extraction (cigar2alignstart_by_pos, SF:309-337; no device involved): walks the CIGAR of
  * an alignment starting at align_start until the reference cursor passes start-1; out[0] = offset into the read,

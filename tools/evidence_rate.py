@@ -1,4 +1,4 @@
-"""What an evidence mode (`--depth`, `--signatures`, `--links`, `--support`) costs on the files path (FASTA + BAM through the
+"""What an evidence mode (`--depth`, `--signatures`, `--links`, `--support`; `--realign` through tools/realign_rate.py) costs on the files path (FASTA + BAM through the
 product CLI): one synthetic world of the mode (MODES below: its maker in vapor_amd/synth.py, its flag, the columns it appends to a
 row) written to files, and runs alternating, each in a warm process of its own: with --parent DIR the plain run and the run with
 the mode on of another checkout (the parent commit, built), then this tree's plain run and its run with the mode on.  The spread
@@ -6,7 +6,7 @@ between one build's own repeats can then be read beside the difference between t
 must be the plain run's, and the tables of the two trees' mode runs must be equal.
   python tools/evidence_rate.py MODE [n_loci] [--repeats R] [--parent DIR] [--bed-repeat K] [--layers N] [--reads N]
                                 [--mode-repeats F] [--plain-repeats F] [--timeout S] [--kernel-only]
-(MODE: depth, sig, links or sup; --bed-repeat K: the same loci K times over in the BED file; --mode-repeats / --plain-repeats F:
+(MODE: depth, sig, links, sup or ra - `--realign`, which a parent checkout from before the option does not run: its plain run only; --bed-repeat K: the same loci K times over in the BED file; --mode-repeats / --plain-repeats F:
 those runs only in the first F repeats; --timeout S: the limit of one process; --kernel-only: this tree's mode run once, in this
 process - for a kernel trace of the mode's kernel)
 A child (`--child ROOT MODE ON FA BAM BED`) is one such process, importing vapor_amd from ROOT."""
@@ -56,10 +56,10 @@ def _count(label, col):
     return lambda rows: "%s %d" % (label, sum(1 for r in rows if r[col] not in (".", "0")))
 
 
-def _genotypes(rows):
+def _genotypes(rows, col=-2):
     gts = {}
     for r in rows:
-        gts[r[-2]] = gts.get(r[-2], 0) + 1
+        gts[r[col]] = gts.get(r[col], 0) + 1
     return "genotypes " + " ".join("%s: %d" % kv for kv in sorted(gts.items()))
 
 
@@ -67,7 +67,9 @@ def _genotypes(rows):
 MODES = {"depth": (_depth_world, "--depth", 4, lambda rows: "supported %d" % sum(1 for r in rows if r[-1] == "1")),
          "sig": (_sig_world, "--signatures", 6, _count("with signature reads", -3)),
          "links": (_links_world, "--links", 7, _count("with linked reads", -5)),
-         "sup": (_sup_world, "--support", 9, _genotypes)}
+         "sup": (_sup_world, "--support", 9, _genotypes),
+         "ra": (_sup_world, "--realign", 7, lambda rows: _genotypes(rows, -3))}
+NOT_IN_PARENT = ("ra",)          # modes a parent checkout does not have: only its plain run is taken
 
 
 def child(root, mode, on, fa, bam, bed, runs=4):
@@ -138,7 +140,8 @@ def main():
             raise SystemExit("child %s %s failed:\n%s" % (root, mode if on else "plain", r.stderr[-3000:]))
         return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     res = {}
-    order = ([("parent", parent, False), ("parent", parent, True)] if parent else []) + [("this", HERE, False), ("this", HERE, True)]
+    order = ([("parent", parent, False)] + ([("parent", parent, True)] if mode not in NOT_IN_PARENT else []) if parent else [])
+    order += [("this", HERE, False), ("this", HERE, True)]
     for rep in range(repeats):
         for who, root, on in order:
             if rep >= only_first[on]:
@@ -159,14 +162,17 @@ def main():
     print("%s / plain: rate %.2f (medians); the rows' own columns equal: %s" % (flag, med(md) / med(pl), {g["table"] for g in md} == {g["table"] for g in pl}))
     if parent:
         for on, mine in ((False, pl), (True, md)):
+            if ("parent", on) not in res:
+                continue
             pa = res[("parent", on)]
             rp = rates(pa)
             inside = sum(1 for g in mine if rp[0] <= g["loci"] / g["best_s"] <= rp[-1])
             below = sum(1 for g in mine if g["loci"] / g["best_s"] < rp[0])
             print("this / parent, %s: %.3f (medians); tables equal: %s; %d of this tree's %d runs lie inside the parent's own spread (%.0f .. %.0f), %d below its minimum"
                   % (mode if on else "plain", med(mine) / med(pa), {g["answers"] for g in mine} == {g["answers"] for g in pa}, inside, len(mine), rp[0], rp[-1], below))
-        print("%s: this tree's median %.0f loci/s, the parent's minimum %.0f: %s"
-              % (flag, med(md), rates(res[("parent", True)])[0], "not below" if med(md) >= rates(res[("parent", True)])[0] else "BELOW"))
+        if ("parent", True) in res:
+            print("%s: this tree's median %.0f loci/s, the parent's minimum %.0f: %s"
+                  % (flag, med(md), rates(res[("parent", True)])[0], "not below" if med(md) >= rates(res[("parent", True)])[0] else "BELOW"))
 
 
 if __name__ == "__main__":

@@ -37,6 +37,7 @@ E_HIP, E_OVERFLOW, E_KEYERROR, E_ARG, E_NOMEM = -1, -2, -3, -4, -5
 MAX_SEQ_LEN = 65535
 MAX_WIDE_SEQ_LEN = 1048575     # the wide route: vapor_wide_batch / vapor_clean_hits_wide
 MAX_ANY_K = 64                 # the any-k route: vapor_anyk_batch takes k from 1 to this
+MAX_BAND = 512                 # vapor_realign_batch: the band, from 1 to this
 FASTA_BLOCK, FASTA_RANGE, FASTA_NON_ASCII, FASTA_ROOM = 1, 2, 3, 4                    # vapor_fasta_windows_device: status of a window
 FASTA_TR_LOWER, FASTA_TR_NOT_ACGTN, FASTA_TR_NOT_ACGTN_ANY_CASE, FASTA_TR_HIGH = 1, 2, 4, 8    # ... and its traits
 ABI_VERSION = 3
@@ -63,6 +64,7 @@ EXPORTS = [
     "vapor_bam_signature", "vapor_bam_signature_device",
     "vapor_bam_links", "vapor_bam_links_device",
     "vapor_bam_support", "vapor_bam_support_device",
+    "vapor_realign_batch",
 ]
 # entry points a library may lack (the CPU twin of the C ABI has no wide or any-k route and no refinement kernel): bound when
 # present, and the engine's wide, any-k and grid methods raise NotImplementedError when they are not
@@ -82,7 +84,9 @@ OPTIONAL_EXPORTS = ("vapor_wide_batch", "vapor_clean_hits_wide", "vapor_anyk_bat
                     # (`--links`, DESIGN.md 4.21: without them a run takes links.answer over bamio's records)
                     "vapor_bam_links", "vapor_bam_links_device",
                     # (`--support`, DESIGN.md 4.22: without them a run takes support.answer over bamio's records)
-                    "vapor_bam_support", "vapor_bam_support_device")
+                    "vapor_bam_support", "vapor_bam_support_device",
+                    # (`--realign`, DESIGN.md 4.23: there is no other route - without it Engine.realign raises)
+                    "vapor_realign_batch")
 MAX_CANDIDATES = 128           # breakpoint refinement: candidates per locus (VAPOR_MAX_CANDIDATES)
 
 _lib = None
@@ -238,6 +242,8 @@ def bind(L: ctypes.CDLL) -> ctypes.CDLL:
         L.vapor_clean_hits_wide.argtypes = [vp, ctypes.c_int64, i32p, i64p, u32p, i64p, u8p]
     if hasattr(L, "vapor_anyk_batch"):
         L.vapor_anyk_batch.argtypes = [vp, vp, ctypes.c_int64, vp, i64p, i32p, ctypes.c_int64, i64p]
+    if hasattr(L, "vapor_realign_batch"):
+        L.vapor_realign_batch.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_int32, i32p]
     if hasattr(L, "vapor_plan_set_grid"):
         L.vapor_plan_set_grid.argtypes = [vp, ctypes.c_int64, i32p]
     if hasattr(L, "vapor_grid_pick"):

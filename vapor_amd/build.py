@@ -15,11 +15,13 @@ SOURCES = [os.path.join(CSRC, "vapor_hip.hip"), os.path.join(CSRC, "vapor_bam.cp
 # The csrc headers, once, in the order both lists below keep.  The ones that hold device code are part of kernel_source_id();
 # vapor_records.h holds the records the kernels read, vapor_names.h the name key and drop rule bam_dedup_kernel shares with the host reader.  vapor_inflate.h, vapor_bgzf.h (the BGZF block parser and scans of the host and
 # device readers), vapor_planner.h (share groups, plan layout, clean order) and vapor_readplan.h (the plan of a device reader call, over the
-# records of vapor_readrec.h that the readers' kernels read) are host-only.  A new route's header goes here.
+# records of vapor_readrec.h that the readers' kernels read) are host-only; vapor_realign_plan.h is host arithmetic too, but realign_kernel reads its
+# constants and functions, so it counts as device code.  A new route's header goes here.
 _HEADERS = [("vapor_kernels.h", True), ("vapor_wide.h", True), ("vapor_anyk.h", True), ("vapor_inflate.h", False),
             ("vapor_bamdev.h", True), ("vapor_fasta.h", True), ("vapor_refine.h", True), ("vapor_bgzf.h", False),
             ("vapor_records.h", True), ("vapor_planner.h", False), ("vapor_names.h", True),
-            ("vapor_readrec.h", True), ("vapor_readplan.h", False), ("vapor_sa.h", False)]
+            ("vapor_readrec.h", True), ("vapor_readplan.h", False), ("vapor_sa.h", False),
+            ("vapor_realign.h", True), ("vapor_realign_plan.h", True)]
 DEPS = SOURCES + [os.path.join(CSRC, h) for h, _dev in _HEADERS] + [os.path.join(ROOT, "include", "vapor_hip.h")]
 KERNEL_FILES = [os.path.join(CSRC, h) for h, dev in _HEADERS if dev] + [SOURCES[0], os.path.abspath(__file__)]
 

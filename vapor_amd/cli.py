@@ -407,8 +407,9 @@ _SIMPLE = {'DEL': drivers.vapor_simple_del, 'INV': drivers.vapor_simple_inv, 'TA
 def _simple_job(name, info, key, fig, row_prefix, label, plt_li, ctx, mode, with_mode=True) -> Job:
     """The job of a DEL / INV / TANDUP record `info` = [chrom, start, end].  Plain and `--phased`: the type's own driver, with
     its array-route description.  `--refine`: drivers.vapor_refine (which leaves a locus it cannot refine to the type's own
-    driver), within the record's CIPOS / CIEND where the mode has them.  `--both-ends`: drivers.vapor_both_ends.  `with_mode`
-    False: a record that these two drivers do not take goes the plain way."""
+    driver), within the record's CIPOS / CIEND where the mode has them.  `--both-ends`: drivers.vapor_both_ends.  `--realign`:
+    drivers.vapor_realign around the type's own driver, on the drivers' route.  `with_mode` False: a record that these drivers do
+    not take goes the plain way."""
     n_cff, bam_in, ref = ctx
     span = info[2] - info[1]
     spec = (name, info[0], info[1], info[2], None)       # (None below: the locus is not for the array route)
@@ -425,10 +426,22 @@ def _simple_job(name, info, key, fig, row_prefix, label, plt_li, ctx, mode, with
             spec = None
         call = (drivers.vapor_both_ends, name, n_cff, plt_li, bam_in, ref, info, fig)
         cost = job_cost(name, span, views=_views_n(name, span))
+    elif kind == 'realign':
+        # (every read meets both alleles once more, in a band: about the cost of the locus again; the array route has no second pass)
+        call = (drivers.vapor_realign, _SIMPLE[name], n_cff, plt_li, bam_in, ref, info, fig, False)
+        cost, spec = 2 * job_cost(name, span), None
     else:
         call = (_SIMPLE[name], n_cff, plt_li, bam_in, ref, info, fig, mode is not None and mode.phased)
         cost = job_cost(name, span)
     return Job(key, None, None, row_prefix, label, cost, spec, ctx, call)
+
+
+def _ins_job(call, cost, spec, mode):
+    """(call, cost, array-route description) of an INS locus: as given, and under `--realign` drivers.vapor_realign around the
+    call, about twice its cost, on the drivers' route (no description), as _simple_job has it for the other three types."""
+    if mode is modes.REALIGN:
+        return (drivers.vapor_realign,) + call, 2 * cost, None
+    return call, cost, spec
 
 
 def bed_jobs(bed_info, num_reads_cff, bam_in, ref, out_path, sample_name, mode=None) -> List[Job]:
@@ -451,9 +464,9 @@ def bed_jobs(bed_info, num_reads_cff, bam_in, ref, out_path, sample_name, mode=N
             ins_pos = '_'.join([str(i) for i in x[:2]])
             ins_seq = ''.join(['X' for _ in range(x[4])]) if type(x[4]) == type(4) else x[4]
             fig = out_path + sample_name + '.INS.' + key.replace(':', '__') + '.png'
-            jobs.append(Job(key, call=(drivers.vapor_simple_ins, num_reads_cff, plt_li, bam_in, ref, ins_pos, ins_seq, fig, '+', phased),
-                            row_prefix=x[3], label=x, cost=job_cost('INS', len(ins_seq)),
-                            spec=('INS', x[0], x[1], None, ins_seq), ctx=ctx))
+            call, cost, spec = _ins_job((drivers.vapor_simple_ins, num_reads_cff, plt_li, bam_in, ref, ins_pos, ins_seq, fig, '+', phased),
+                                        job_cost('INS', len(ins_seq)), ('INS', x[0], x[1], None, ins_seq), mode)
+            jobs.append(Job(key, call=call, row_prefix=x[3], label=x, cost=cost, spec=spec, ctx=ctx))
             continue
         elif tag in ['a/aa', 'aa/a', 'aa/aa', 'DUP', 'TANDUP']:
             name = 'TANDUP'
@@ -531,8 +544,9 @@ def vcf_jobs(vcf_list, num_reads_cff, bam_in, ref, out_path, sample_name, mode=N
                 ins_pos = '_'.join([str(i) for i in y[:2]])
                 ins_seq = y[-1] if len(y) == 4 else ''.join(['X' for _ in range(y[2])])
                 fig = out_path + sample_name + '.INS.' + key.replace(':', '__') + '.png'
-                jobs.append(Job(key, call=(drivers.vapor_simple_ins, num_reads_cff, plt_li, bam_in, ref, ins_pos, ins_seq, fig, '+', phased),
-                                cost=job_cost('INS', len(ins_seq)), spec=('INS', y[0], y[1], None, ins_seq), ctx=ctx))
+                call, cost, spec = _ins_job((drivers.vapor_simple_ins, num_reads_cff, plt_li, bam_in, ref, ins_pos, ins_seq, fig, '+', phased),
+                                            job_cost('INS', len(ins_seq)), ('INS', y[0], y[1], None, ins_seq), mode)
+                jobs.append(Job(key, call=call, cost=cost, spec=spec, ctx=ctx))
             elif x == 'DISDUP':
                 key = ':'.join([str(i) for i in y + ['DISDUP']])
                 fig = out_path + sample_name + '.DISDUP.' + key.replace(':', '__') + '.png'
@@ -933,6 +947,9 @@ def build_parser() -> argparse.ArgumentParser:
                         'VaPoR_SUP_REF, VaPoR_SUP_REFL, VaPoR_SUP_REFR, VaPoR_SUP_COVL, VaPoR_SUP_COVR, VaPoR_SUP_VAF, VaPoR_SUP_GT and '
                         'VaPoR_SUP_GQ (vcf: to INFO; no VAF, GT or GQ for a TANDUP); not together with --refine, --phased, '
                         '--phase-vcf, --both-ends, --depth, --signatures or --links')
+    # (`--realign`, DESIGN.md 4.23: every read aligned to both alleles on the device, VaPoR_RA_* behind the row.  Its paragraph is
+    # README.md's until the recording of this help text is made again: SUPPRESS keeps the option out of the usage line and the list)
+    p.add_argument('--realign', action='store_true', help=argparse.SUPPRESS)
     p.add_argument('--min-mapq', metavar='Q', type=_int_in('--min-mapq', 0, 255), default=0,
                    help='every sub-command: skip records with MAPQ below Q (0..255, default 0), as `samtools view -q Q` does; a '
                         'filtered record is treated as if it were not in the file')
@@ -963,7 +980,7 @@ def _int_in(name, lo, hi):
 # "A run has one mode" (vapor_amd/modes.py), as the parser says it: the options that make a mode, in the order their refusals are
 # checked, and what a pair is told where that is more than the rule.  `--phase-vcf` is `--phased` with another source of tags:
 # the three older modes refuse it under that name (None: not under its own).
-MODE_OPTIONS = ('--refine', '--phase-vcf', '--phased', '--both-ends', '--depth', '--signatures', '--links', '--support')
+MODE_OPTIONS = ('--refine', '--phase-vcf', '--phased', '--both-ends', '--depth', '--signatures', '--links', '--support', '--realign')
 PAIR_REASONS = {
     ('--phased', '--refine'): 'refinement per haplotype is not implemented',
     ('--phased', '--phase-vcf'): None,
@@ -1032,7 +1049,7 @@ def _main(argv, held) -> int:
         args.phased = True               # (the groups, the scoring and the columns are --phased's: only the tags' source differs)
     # a run has one mode: every later option of MODE_OPTIONS refuses the sub-commands it does not apply to, then each earlier one
     given = dict(zip(MODE_OPTIONS, (refine is not None, args.phase_vcf is not None, args.phased, args.both_ends, args.depth, args.signatures,
-                                    args.links, args.support)))
+                                    args.links, args.support, args.realign)))
     for k, opt in enumerate(MODE_OPTIONS[2:], 2):           # (--refine's block stands above, --phase-vcf is --phased here)
         if not given[opt]:
             continue
@@ -1082,6 +1099,8 @@ def _main(argv, held) -> int:
         mode = modes.LINKS
     elif args.support:
         mode = modes.SUPPORT
+    elif args.realign:
+        mode = modes.REALIGN
     figure_fn = None
     if not args.no_figures:
         from . import figures

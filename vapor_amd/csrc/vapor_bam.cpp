@@ -1376,6 +1376,13 @@ extern "C" __attribute__((weak)) int vapor_anyk_batch(vapor_ctx*, vapor_seqset*,
     return bfail(VAPOR_E_ARG, "vapor_anyk_batch: this build has no any-k route");
 }
 
+// `--realign`'s distances (vapor_realign_batch: realign_kernel) are device code in vapor_hip.hip as well and have no host route;
+// the CPU twin exports the name and refuses every call, and Engine.realign does not call it there.
+extern "C" __attribute__((weak)) int vapor_realign_batch(vapor_ctx*, vapor_seqset*, int64_t, const vapor_pair*, int32_t, int32_t*)
+{
+    return bfail(VAPOR_E_ARG, "vapor_realign_batch: this build has no realignment kernel");
+}
+
 // The reference windows of a bgzipped FASTA on the device (vapor_fasta_windows_device, vapor_fasta_last_stats) are device code in
 // vapor_hip.hip as well; the CPU twin answers them with VAPOR_E_ARG, and the caller reads the windows on the host.
 extern "C" __attribute__((weak)) int vapor_fasta_windows_device(vapor_ctx*, int, int32_t, const uint64_t*, const uint64_t*, uint8_t*, int64_t,

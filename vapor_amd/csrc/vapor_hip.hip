@@ -8,6 +8,7 @@
 #include "vapor_kernels.h"
 #include "vapor_wide.h"
 #include "vapor_anyk.h"
+#include "vapor_realign.h"
 #include "vapor_bamdev.h"
 #include "vapor_bgzf.h"
 #include "vapor_fasta.h"
@@ -2453,6 +2454,50 @@ extern "C" int vapor_anyk_batch(vapor_ctx* ctx, vapor_seqset* set, int64_t n_pai
                                 int32_t* hits_ji, int64_t hits_capacity, int64_t* hit_off)
 {
     return dot_pairs<AnykRoute>("vapor_anyk_batch", ctx, set, n_pairs, pairs, stats, hits_ji, hits_capacity, hit_off);
+}
+
+// ------------------------------------------------------------------------------------------
+// `--realign` (vapor_realign.h): the banded edit distance of every pair, one wavefront a pair.  The checks, the pair records and
+// the geometry are vapor_realign_plan.h's; here: one upload of the records, one launch, one copy back.
+template <int S>
+static void realign_launch(hipStream_t st, const uint32_t* x4, const vapor_realign::RPair* d_pairs, int64_t n_pairs, int32_t band, int32_t* d_out)
+{
+    hipLaunchKernelGGL((realign_kernel<S>), dim3((unsigned)vapor_realign::grid_of(n_pairs)), dim3(64 * vapor_realign::WAVES), 0, st, x4, d_pairs,
+                       (long long)n_pairs, (int)band, d_out);
+}
+
+extern "C" int vapor_realign_batch(vapor_ctx* ctx, vapor_seqset* set, int64_t n_pairs, const vapor_pair* pairs, int32_t band, int32_t* out)
+{
+    namespace ra = vapor_realign;
+    if (!ctx || !set || n_pairs < 0 || n_pairs > ra::MAX_PAIRS || (n_pairs && (!pairs || !out)))
+        return fail(VAPOR_E_ARG, "vapor_realign_batch: null argument or a pair count outside 0 .. 2^26");
+    if (!ra::band_ok(band)) return fail(VAPOR_E_ARG, "vapor_realign_batch: band outside 1 .. VAPOR_MAX_BAND");
+    if (n_pairs == 0) return VAPOR_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    std::vector<ra::RPair> recs((size_t)n_pairs);          // (the upload reads it: declared before the owners, which unwind first)
+    CallScope sc(ctx, st);
+    Block<ra::RPair> d_pairs(sc);
+    Block<int32_t> d_out(sc);
+    for (int64_t t = 0; t < n_pairs; ++t)
+        recs[(size_t)t] = ra::pair_record(pairs[t], set->n, [&](int32_t s) { return set->h[(size_t)s].len; },
+                                          [&](int32_t s) { return set->h[(size_t)s].chunk0; });
+    HIPCHK(d_pairs.ensure(sizeof(ra::RPair) * (size_t)n_pairs));
+    HIPCHK(d_out.ensure(sizeof(int32_t) * 2 * (size_t)n_pairs));
+    HIPCHK(hipMemcpyAsync(d_pairs.p, recs.data(), sizeof(ra::RPair) * (size_t)n_pairs, hipMemcpyHostToDevice, st));
+    switch (ra::lane_width(band)) {
+    case 1: realign_launch<1>(st, set->d_x4, d_pairs, n_pairs, band, d_out); break;
+    case 2: realign_launch<2>(st, set->d_x4, d_pairs, n_pairs, band, d_out); break;
+    case 3: realign_launch<3>(st, set->d_x4, d_pairs, n_pairs, band, d_out); break;
+    case 5: realign_launch<5>(st, set->d_x4, d_pairs, n_pairs, band, d_out); break;
+    case 9: realign_launch<9>(st, set->d_x4, d_pairs, n_pairs, band, d_out); break;
+    default: realign_launch<ra::MAX_SLOTS>(st, set->d_x4, d_pairs, n_pairs, band, d_out); break;
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, d_out.p, sizeof(int32_t) * 2 * (size_t)n_pairs, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    sc.settled();
+    return VAPOR_OK;
 }
 
 // ------------------------------------------------------------------------------------------

@@ -596,6 +596,46 @@ def vapor_refine(svtype, num_reads_cff, plt_li, bam_in, ref, sv_info, out_figure
     return scores
 
 
+class Realign:
+    """`--realign`: the reads of a Score request against its two alleles.  Result: a realign.Payload - per read
+    its edit distance to ref_seq[miss_bp:] minus that to alt_seq[miss_bp:] - or None when a pair came back with a status."""
+    __slots__ = ("ref_seq", "alt_seq", "reads")
+
+    def __init__(self, ref_seq, alt_seq, reads):
+        self.ref_seq, self.alt_seq, self.reads = ref_seq, alt_seq, reads
+
+
+class Realigned(list):
+    """The score list of a locus under `--realign` - the type's own driver's, as without the option - with `realign`: the payload
+    of the last Score request the driver made whose answer was a list, None for a locus without one."""
+    realign = None
+
+
+def vapor_realign(driver, *args):
+    """`--realign` for a DEL, INV, TANDUP or INS locus: the type's own driver runs as it is - its requests, its figure, its
+    scores: the row's own columns - and the last Score request whose answer was a list is asked once more as a Realign request,
+    whichever branch made it (the short window and the junction window are both just a Score request)."""
+    gen = driver(*args)
+    last = None
+    try:
+        req = next(gen)
+        while True:
+            try:
+                ans = yield req
+            except Exception as e:           # noqa: BLE001 - the executor's answer to a request may be an exception: the driver's to handle
+                req = gen.throw(e)
+                continue
+            if isinstance(req, Score) and isinstance(ans, list):
+                last = req
+            req = gen.send(ans)
+    except StopIteration as fin:
+        scores = fin.value
+    out = Realigned(scores if scores is not None else [])
+    if last is not None:
+        out.realign = yield Realign(last.ref_seq, last.alt_seq, last.reads)
+    return out
+
+
 def vapor_simple_ins(num_reads_cff, plt_li, bam_in, ref, ins_pos, ins_seq, out_figure_name, POLARITY, phased=False):
     """vapor_simple_ins_Vapor, SF:1856-1893.  ins_pos is 'chrom_pos'."""
     if POLARITY == "+":

@@ -710,6 +710,22 @@ class Engine:
         kmerhits(..., inversions=False)); with want_hits also, per pair, the (n,2) [j,i] hit array in the reference's order."""
         return self._score_dots("vapor_anyk_batch", seqset, pairs, want_hits, sort=False)
 
+    # ---- `--realign`: the banded edit distance of every pair (DESIGN.md 4.23) ----
+    def realign_available(self) -> bool:
+        """Whether the loaded library has vapor_realign_batch (the CPU twin of the C ABI has not)."""
+        return self._available("vapor_realign_batch")
+
+    def realign(self, seqset: SeqSet, pairs: np.ndarray, band: int):
+        """(d, status) of every pair, two int32 arrays (vapor_realign_batch): d the edit distance of seq1 against seq2[off2:]
+        inside the band, start anchored, both ends free - -1 where status is E_ARG.  A pair's k and flags are ignored.
+        NotImplementedError where the library has no such entry: there is no other route."""
+        fn = self._wide_entry("vapor_realign_batch", "realignment kernel (--realign)")
+        pairs = np.ascontiguousarray(pairs, dtype=L.PAIR_DTYPE)
+        n = len(pairs)
+        out = np.zeros((max(n, 1), 2), dtype=np.int32)
+        L.check(fn(self._ctx, seqset._h, n, pairs.ctypes.data if n else None, int(band), L.ptr(out, ctypes.c_int32)))
+        return out[:n, 0].copy(), out[:n, 1].copy()
+
     def clean_hits_wide(self, lists: Sequence[np.ndarray], flags: Optional[Sequence[int]] = None):
         """clean_hits for lists with coordinates up to MAX_WIDE_SEQ_LEN (vapor_clean_hits_wide)."""
         return self._clean_lists(self._wide_entry("vapor_clean_hits_wide"), lists, flags)

@@ -1,11 +1,11 @@
 """The run modes of `vapor bed | vcf` that append columns to every row: `--refine`, `--phased` (and `--phase-vcf`, the same mode
-with another source of tags), `--both-ends`, `--depth`, `--signatures`, `--links` and `--support`.  At most one holds for a run (the parser refuses every pair); None is the plain
+with another source of tags), `--both-ends`, `--depth`, `--signatures`, `--links`, `--support` and `--realign`.  At most one holds for a run (the parser refuses every pair); None is the plain
 run.  A Mode is everything cli.py and the VCF writer need to know about one; what the option computes stays in
-its own module - refine.py, phase.py, bothends.py, depth.py, signature.py, links.py, support.py - which gives the mode its columns and the way they travel between ranks;
-the last four also say how their regions are read (their reader surface), and the parser states the rule once (cli.MODE_OPTIONS)."""
+its own module - refine.py, phase.py, bothends.py, depth.py, signature.py, links.py, support.py, realign.py - which gives the mode its columns and the way they travel between ranks;
+depth.py to support.py also say how their regions are read (their reader surface), and the parser states the rule once (cli.MODE_OPTIONS)."""
 from __future__ import annotations
 
-from . import bothends, depth, links, phase, signature, support
+from . import bothends, depth, links, phase, realign, signature, support
 from . import refine as _refine
 
 
@@ -42,3 +42,4 @@ DEPTH = Mode("depth", depth, "depth")
 SIGNATURES = Mode("signatures", signature, "signatures")
 LINKS = Mode("links", links, "links")
 SUPPORT = Mode("support", support, "support")
+REALIGN = Mode("realign", realign, "realign")

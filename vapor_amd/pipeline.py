@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _lib as L
 from . import repeat_qc
-from .drivers import Figure, Score, ScoreGrid, Window
+from .drivers import Figure, Realign, Score, ScoreGrid, Window
 
 import threading
 
@@ -532,6 +532,44 @@ def _score_requests_narrow(engine, reqs: Sequence[Score]) -> List[object]:
 
 
 # ------------------------------------------------------------------------------------------
+# `--realign`: every read against both alleles (drivers.Realign)
+# ------------------------------------------------------------------------------------------
+def realign_requests(engine, reqs: Sequence[object]) -> List[object]:
+    """Evaluates every Realign request of a batch: one sequence set (reads as literals, alleles described where they are
+    drivers.Alleles: nothing of a derived allele crosses the link), two pairs a read - the read against the reference allele and
+    against the alt allele, both from miss_bp on - and one engine.realign call.  Per request a realign.Payload, or None when one
+    of its pairs came back with a status.  An engine without the kernel raises (Engine.realign): there is no other route."""
+    from . import realign
+    sb = _SetBuilder()
+    rows = []                         # (read, allele, miss_bp), the reference allele's pair before the alt allele's
+    first = []
+    for r in reqs:
+        first.append(len(rows))
+        if not r.reads:
+            continue
+        ri, ai = sb.describe(r.ref_seq, False), sb.describe(r.alt_seq, False)
+        for x in r.reads:
+            q = len(sb.seqs)
+            sb.seqs.append(x[0])                             # (reads are never shared between requests: no look-up)
+            rows += [(q, ri, int(x[1])), (q, ai, int(x[1]))]
+    first.append(len(rows))
+    if not rows:
+        return [realign.Payload() for _ in reqs]
+    n_lit = len(sb.seqs)
+    pairs = np.zeros(len(rows), dtype=L.PAIR_DTYPE)
+    tab = np.asarray(rows, dtype=np.int64)
+    pairs["seq1"] = tab[:, 0]
+    pairs["seq2"] = np.where(tab[:, 1] < 0, n_lit - 1 - tab[:, 1], tab[:, 1])       # derived sequence d: behind the literals
+    pairs["off2"] = tab[:, 2]
+    ss = engine.seqset(sb.seqs, None, sb.derived) if sb.derived else engine.seqset(sb.seqs)
+    try:
+        d, st = engine.realign(ss, pairs, realign.BAND)
+    finally:
+        ss.close()
+    return [realign.payload(d[a:b:2], d[a + 1:b:2], st[a:b:2], st[a + 1:b:2]) for a, b in zip(first[:-1], first[1:])]
+
+
+# ------------------------------------------------------------------------------------------
 # breakpoint refinement: grids of candidate alleles (drivers.ScoreGrid)
 # ------------------------------------------------------------------------------------------
 GRID_PAIRS_PER_PLAN = 150000      # a plan of grids is sized by pairs, not by loci (121 candidates x 20 reads: some 5 000 pairs a locus;
@@ -748,6 +786,10 @@ def _answer(engine, reqs: Sequence[object], figure_fn) -> List[object]:
     gi = [t for t, r in enumerate(reqs) if isinstance(r, ScoreGrid)]
     if gi:
         for t, v in zip(gi, score_grids(engine, [reqs[t] for t in gi])):
+            res[t] = v
+    ri = [t for t, r in enumerate(reqs) if isinstance(r, Realign)]
+    if ri:
+        for t, v in zip(ri, realign_requests(engine, [reqs[t] for t in ri])):
             res[t] = v
     if figure_fn is not None:
         figs = [r for r in reqs if isinstance(r, Figure)]
