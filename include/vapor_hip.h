@@ -353,6 +353,30 @@ int vapor_anyk_batch(vapor_ctx* ctx, vapor_seqset* set, int64_t n_pairs, const v
 #define VAPOR_MAX_BAND 512
 int vapor_realign_batch(vapor_ctx* ctx, vapor_seqset* set, int64_t n_pairs, const vapor_pair* pairs, int32_t band, int32_t* out);
 
+/* ---- `--realign-out`: the alignment behind the distance --------------------- */
+/*
+ * For every pair, with a, n, b, m, the matrix D and d as vapor_realign_batch has them: one alignment of cost d, by a rule.
+ * End cell: of the existing cells of the last row and of the last column whose D equals d, the one with the largest i, among
+ * those the one with the largest j.  Walk from it back to (0, 0); at (i, j) take the diagonal predecessor if it exists and
+ * D[i-1][j-1] + sub == D[i][j] (op '=' where the symbols match, 'X' where not), otherwise the vertical one if it exists and
+ * D[i-1][j] + 1 == D[i][j] (op 'I': a read symbol against nothing), otherwise the horizontal one (op 'D': an allele symbol
+ * skipped); row 0 is all horizontal.  The path reversed and run-length encoded is the pair's trace; the n - i_end read symbols
+ * behind the end cell are soft-clipped and are no run.
+ * head[8t ..] = {d, status, i_end, j_end, n_runs, 0, 0, 0}.  runs holds cap_runs words a pair; a run is len << 2 | op with op
+ * 0 '=', 1 'X', 2 'I', 3 'D'; the runs of pair t are the LAST n_runs words of runs[t * cap_runs .. (t + 1) * cap_runs), in path
+ * order, and what stands in front of them is unspecified.  A pair whose trace needs more than cap_runs runs gets status
+ * VAPOR_E_OVERFLOW: its d, i_end and j_end are right, n_runs is the count it needs, its words are unspecified.  A pair that
+ * vapor_realign_batch refuses gets d = -1 and status VAPOR_E_ARG here too, and the call still returns VAPOR_OK; d of every pair
+ * is vapor_realign_batch's.  The call returns VAPOR_E_ARG where vapor_realign_batch does and for cap_runs < 1; n_pairs == 0 is
+ * VAPOR_OK.  The forward pass keeps two bits a cell of the band: rows_walked * 256 bytes a pair up to band 288, twice that
+ * above.  The pairs run in consecutive groups whose workspaces fit vapor_set_param(ctx, "trace_budget", bytes) - 512 MiB unless
+ * set, never below the 64 MiB that hold the largest pair; a lower value is raised to that.  One upload, per group two kernels
+ * (realign_trace_kernel, traceback_kernel: one wavefront a pair each), the copies back and one synchronisation, on the
+ * context's stream.  A library without a device exports the name and refuses every call with VAPOR_E_ARG; there is no host route.
+ */
+int vapor_realign_trace(vapor_ctx* ctx, vapor_seqset* set, int64_t n_pairs, const vapor_pair* pairs, int32_t band,
+                        int32_t cap_runs, int32_t* head, uint32_t* runs);
+
 /*
  * Host helper of the read extraction (cigar2alignstart_by_pos, SF:309-337; no device involved): walks the CIGAR of
  * an alignment starting at align_start until the reference cursor passes start-1; out[0] = offset into the read,

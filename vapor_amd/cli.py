@@ -429,6 +429,8 @@ def _simple_job(name, info, key, fig, row_prefix, label, plt_li, ctx, mode, with
     elif kind == 'realign':
         # (every read meets both alleles once more, in a band: about the cost of the locus again; the array route has no second pass)
         call = (drivers.vapor_realign, _SIMPLE[name], n_cff, plt_li, bam_in, ref, info, fig, False)
+        if mode.sink is not None:            # (`--realign-out`: the same wrapper, its Realign request named and asking for traces)
+            call = (drivers.vapor_realign_out, key) + call[1:]
         cost, spec = 2 * job_cost(name, span), None
     else:
         call = (_SIMPLE[name], n_cff, plt_li, bam_in, ref, info, fig, mode is not None and mode.phased)
@@ -436,10 +438,13 @@ def _simple_job(name, info, key, fig, row_prefix, label, plt_li, ctx, mode, with
     return Job(key, None, None, row_prefix, label, cost, spec, ctx, call)
 
 
-def _ins_job(call, cost, spec, mode):
+def _ins_job(call, cost, spec, mode, key=None):
     """(call, cost, array-route description) of an INS locus: as given, and under `--realign` drivers.vapor_realign around the
-    call, about twice its cost, on the drivers' route (no description), as _simple_job has it for the other three types."""
-    if mode is modes.REALIGN:
+    call, about twice its cost, on the drivers' route (no description), as _simple_job has it for the other three types
+    (under `--realign-out` drivers.vapor_realign_out, named `key`)."""
+    if mode is not None and mode.name == 'realign':
+        if mode.sink is not None:
+            return (drivers.vapor_realign_out, key) + call, 2 * cost, None
         return (drivers.vapor_realign,) + call, 2 * cost, None
     return call, cost, spec
 
@@ -465,7 +470,7 @@ def bed_jobs(bed_info, num_reads_cff, bam_in, ref, out_path, sample_name, mode=N
             ins_seq = ''.join(['X' for _ in range(x[4])]) if type(x[4]) == type(4) else x[4]
             fig = out_path + sample_name + '.INS.' + key.replace(':', '__') + '.png'
             call, cost, spec = _ins_job((drivers.vapor_simple_ins, num_reads_cff, plt_li, bam_in, ref, ins_pos, ins_seq, fig, '+', phased),
-                                        job_cost('INS', len(ins_seq)), ('INS', x[0], x[1], None, ins_seq), mode)
+                                        job_cost('INS', len(ins_seq)), ('INS', x[0], x[1], None, ins_seq), mode, key)
             jobs.append(Job(key, call=call, row_prefix=x[3], label=x, cost=cost, spec=spec, ctx=ctx))
             continue
         elif tag in ['a/aa', 'aa/a', 'aa/aa', 'DUP', 'TANDUP']:
@@ -545,7 +550,7 @@ def vcf_jobs(vcf_list, num_reads_cff, bam_in, ref, out_path, sample_name, mode=N
                 ins_seq = y[-1] if len(y) == 4 else ''.join(['X' for _ in range(y[2])])
                 fig = out_path + sample_name + '.INS.' + key.replace(':', '__') + '.png'
                 call, cost, spec = _ins_job((drivers.vapor_simple_ins, num_reads_cff, plt_li, bam_in, ref, ins_pos, ins_seq, fig, '+', phased),
-                                            job_cost('INS', len(ins_seq)), ('INS', y[0], y[1], None, ins_seq), mode)
+                                            job_cost('INS', len(ins_seq)), ('INS', y[0], y[1], None, ins_seq), mode, key)
                 jobs.append(Job(key, call=call, cost=cost, spec=spec, ctx=ctx))
             elif x == 'DISDUP':
                 key = ':'.join([str(i) for i in y + ['DISDUP']])
@@ -814,6 +819,11 @@ def _score_jobs(jobs, chunk, figure_fn, t0, mode=None):
         if mode is not None and mode.chunk_payloads is not None and todo:
             # (a payload of the chunk, not of a driver's result: one call for all its loci, whichever route scored them)
             payloads.update(mode.chunk_payloads(jobs, todo, engine))
+        if mode is not None and mode.sink is not None:
+            # (`--realign-out`: the rank that scored a locus writes it, as figures are written; the sink orders by job)
+            for t in todo:
+                if not isinstance(done[t], BaseException) and done[t] is not None:
+                    mode.sink.take(t, jobs[t].key, getattr(done[t], mode.attr, None))
         return part, todo, [done[t] for t in todo]
 
     in_flight = max(1, int(os.environ.get("VAPOR_CHUNKS_IN_FLIGHT", "3")))
@@ -950,6 +960,9 @@ def build_parser() -> argparse.ArgumentParser:
     # (`--realign`, DESIGN.md 4.23: every read aligned to both alleles on the device, VaPoR_RA_* behind the row.  Its paragraph is
     # README.md's until the recording of this help text is made again: SUPPRESS keeps the option out of the usage line and the list)
     p.add_argument('--realign', action='store_true', help=argparse.SUPPRESS)
+    # (`--realign-out PREFIX`, DESIGN.md 4.24: every read's alignment to the allele it fits, PREFIX.sam over PREFIX.fa; no mode
+    # of its own - it needs --realign - and suppressed for the same reason)
+    p.add_argument('--realign-out', metavar='PREFIX', default=None, help=argparse.SUPPRESS)
     p.add_argument('--min-mapq', metavar='Q', type=_int_in('--min-mapq', 0, 255), default=0,
                    help='every sub-command: skip records with MAPQ below Q (0..255, default 0), as `samtools view -q Q` does; a '
                         'filtered record is treated as if it were not in the file')
@@ -1045,6 +1058,8 @@ def _main(argv, held) -> int:
             parser.error(str(e))
     if args.phase_sample is not None and args.phase_vcf is None:
         parser.error('--phase-sample names a sample of --phase-vcf: give that option too')
+    if args.realign_out is not None and not args.realign:
+        parser.error('--realign-out needs --realign')
     if args.phase_vcf is not None:
         args.phased = True               # (the groups, the scoring and the columns are --phased's: only the tags' source differs)
     # a run has one mode: every later option of MODE_OPTIONS refuses the sub-commands it does not apply to, then each earlier one
@@ -1107,6 +1122,9 @@ def _main(argv, held) -> int:
         figure_fn = figures.make_event_figure_1
         figures.warm()                  # (the drawing processes start while the input is parsed and the first batch scored)
     vdist.init_from_env()
+    if mode is modes.REALIGN and args.realign_out is not None:
+        from . import realign
+        mode = modes.realign_out(realign.TraceWriter(args.realign_out, vdist.rank(), vdist.world()))
     out_path = SF.path_modify(args.output_path)
     SF.path_mkdir(out_path)
     sample_name = '.'.join(args.sv_input.split('/')[-1].split('.')[:-1])
@@ -1138,6 +1156,8 @@ def _main(argv, held) -> int:
         melt.run(args.sv_input, out_path, sample_name.split('.')[0], bam_in, ref, num_reads_cff, args.chunk, figure_fn)
     else:
         raise SystemExit("vapor: unknown mode %r (bed | vcf | svelter | ins)" % cmd)
+    if mode is not None and mode.sink is not None:
+        mode.sink.close()
     vdist.finalize()
     return 0
 

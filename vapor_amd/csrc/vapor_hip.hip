@@ -9,6 +9,7 @@
 #include "vapor_wide.h"
 #include "vapor_anyk.h"
 #include "vapor_realign.h"
+#include "vapor_realign_trace.h"
 #include "vapor_bamdev.h"
 #include "vapor_bgzf.h"
 #include "vapor_fasta.h"
@@ -101,6 +102,7 @@ struct vapor_ctx {
     int remap_in_clean = 1;                    // ... and the clean workgroup of a target cuts its records out of the shared plot (0: remap_kernel)
     int clean_order = 1;                       // 1: the clean workgroups are dealt out longest pair first (clean_order); 0: in pair order
     int clean_fit = 1;                         // 1: after a blocking run the clean kernel's LDS copy is sized for the records the pairs really hold
+    int64_t trace_budget = vapor_trace::BUDGET_DEFAULT;      // bytes of vapor_realign_trace's workspace (never below BUDGET_FLOOR)
     int stage_threads = 3;                     // host threads that copy a large upload into the pinned staging buffer (measured:
                                                // two to four are as fast as it gets, more are slower - tools/upload_sweep.py)
     bool attrs_set = false;
@@ -455,6 +457,10 @@ extern "C" int vapor_set_param(vapor_ctx* c, const char* name, int64_t v)
     }
     if (!strcmp(name, "clean_fit")) {
         c->clean_fit = v != 0;
+        return VAPOR_OK;
+    }
+    if (!strcmp(name, "trace_budget")) {
+        c->trace_budget = vapor_trace::budget_of(v);       // (a lower value is raised to the floor that always holds one pair)
         return VAPOR_OK;
     }
     if (!strcmp(name, "stage_threads")) {
@@ -2495,6 +2501,75 @@ extern "C" int vapor_realign_batch(vapor_ctx* ctx, vapor_seqset* set, int64_t n_
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, d_out.p, sizeof(int32_t) * 2 * (size_t)n_pairs, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    sc.settled();
+    return VAPOR_OK;
+}
+
+// `--realign-out` (vapor_realign_trace.h): the alignment behind every pair's distance.  The pair records are
+// vapor_realign_plan.h's, the groups, the workspace and the head vapor_trace_plan.h's; here: one upload (records and workspace
+// offsets), per group the forward pass and the traceback back to back on one workspace, the copies back and one synchronisation.
+template <int S>
+static void realign_trace_launch(hipStream_t st, const uint32_t* x4, const vapor_realign::RPair* d_pairs, const uint64_t* d_off, int64_t t0,
+                                 int64_t count, int32_t band, uint32_t* d_ws, int32_t cap_runs, int32_t* d_head, uint32_t* d_runs)
+{
+    const dim3 grid((unsigned)vapor_realign::grid_of(count)), block(64 * vapor_realign::WAVES);
+    hipLaunchKernelGGL((realign_trace_kernel<S>), grid, block, 0, st, x4, d_pairs, d_off, (long long)t0, (long long)count, (int)band, d_ws, d_head);
+    hipLaunchKernelGGL((traceback_kernel<S>), grid, block, 0, st, d_pairs, d_off, (long long)t0, (long long)count, (int)band,
+                       (const uint32_t*)d_ws, (int)cap_runs, d_head, d_runs);
+}
+
+extern "C" int vapor_realign_trace(vapor_ctx* ctx, vapor_seqset* set, int64_t n_pairs, const vapor_pair* pairs, int32_t band, int32_t cap_runs,
+                                   int32_t* head, uint32_t* runs)
+{
+    namespace ra = vapor_realign;
+    namespace tr = vapor_trace;
+    if (!ctx || !set || n_pairs < 0 || n_pairs > ra::MAX_PAIRS || (n_pairs && (!pairs || !head || !runs)))
+        return fail(VAPOR_E_ARG, "vapor_realign_trace: null argument or a pair count outside 0 .. 2^26");
+    if (!ra::band_ok(band)) return fail(VAPOR_E_ARG, "vapor_realign_trace: band outside 1 .. VAPOR_MAX_BAND");
+    if (!tr::cap_ok(cap_runs)) return fail(VAPOR_E_ARG, "vapor_realign_trace: cap_runs below 1");
+    if (n_pairs == 0) return VAPOR_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const int S = ra::lane_width(band);
+    const size_t np = (size_t)n_pairs, rec_bytes = sizeof(ra::RPair) * np;
+    std::vector<ra::RPair> recs(np);
+    std::vector<int64_t> first;
+    std::vector<uint64_t> off;
+    std::vector<uint8_t> up(rec_bytes + sizeof(uint64_t) * np);        // (the upload reads it: declared before the owners)
+    CallScope sc(ctx, st);
+    Block<uint8_t> d_up(sc);
+    Block<uint32_t> d_ws(sc);
+    Block<int32_t> d_head(sc);
+    Block<uint32_t> d_runs(sc);
+    for (int64_t t = 0; t < n_pairs; ++t)
+        recs[(size_t)t] = ra::pair_record(pairs[t], set->n, [&](int32_t s) { return set->h[(size_t)s].len; },
+                                          [&](int32_t s) { return set->h[(size_t)s].chunk0; });
+    const int64_t ws_words = tr::plan_groups(recs.data(), n_pairs, band, S, ctx->trace_budget, first, off);
+    memcpy(up.data(), recs.data(), rec_bytes);
+    memcpy(up.data() + rec_bytes, off.data(), sizeof(uint64_t) * np);
+    HIPCHK(d_up.ensure(up.size()));
+    HIPCHK(d_ws.ensure(sizeof(uint32_t) * (size_t)std::max<int64_t>(ws_words, 64)));
+    HIPCHK(d_head.ensure(sizeof(int32_t) * tr::HEAD * np));
+    HIPCHK(d_runs.ensure(sizeof(uint32_t) * np * (size_t)cap_runs));
+    HIPCHK(hipMemcpyAsync(d_up.p, up.data(), up.size(), hipMemcpyHostToDevice, st));
+    const ra::RPair* d_pairs = reinterpret_cast<const ra::RPair*>(d_up.p);
+    const uint64_t* d_off = reinterpret_cast<const uint64_t*>(d_up.p + rec_bytes);
+    for (size_t g = 0; g + 1 < first.size(); ++g) {
+        const int64_t t0 = first[g], count = first[g + 1] - t0;
+        if (count == 0) continue;
+        switch (S) {
+        case 1: realign_trace_launch<1>(st, set->d_x4, d_pairs, d_off, t0, count, band, d_ws, cap_runs, d_head, d_runs); break;
+        case 2: realign_trace_launch<2>(st, set->d_x4, d_pairs, d_off, t0, count, band, d_ws, cap_runs, d_head, d_runs); break;
+        case 3: realign_trace_launch<3>(st, set->d_x4, d_pairs, d_off, t0, count, band, d_ws, cap_runs, d_head, d_runs); break;
+        case 5: realign_trace_launch<5>(st, set->d_x4, d_pairs, d_off, t0, count, band, d_ws, cap_runs, d_head, d_runs); break;
+        case 9: realign_trace_launch<9>(st, set->d_x4, d_pairs, d_off, t0, count, band, d_ws, cap_runs, d_head, d_runs); break;
+        default: realign_trace_launch<ra::MAX_SLOTS>(st, set->d_x4, d_pairs, d_off, t0, count, band, d_ws, cap_runs, d_head, d_runs); break;
+        }
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipMemcpyAsync(head, d_head.p, sizeof(int32_t) * tr::HEAD * np, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(runs, d_runs.p, sizeof(uint32_t) * np * (size_t)cap_runs, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     sc.settled();
     return VAPOR_OK;

@@ -598,11 +598,13 @@ def vapor_refine(svtype, num_reads_cff, plt_li, bam_in, ref, sv_info, out_figure
 
 class Realign:
     """`--realign`: the reads of a Score request against its two alleles.  Result: a realign.Payload - per read
-    its edit distance to ref_seq[miss_bp:] minus that to alt_seq[miss_bp:] - or None when a pair came back with a status."""
-    __slots__ = ("ref_seq", "alt_seq", "reads")
+    its edit distance to ref_seq[miss_bp:] minus that to alt_seq[miss_bp:] - or None when a pair came back with a status.
+    `trace` (`--realign-out`; off unless asked): the payload also carries `.traces`, every read's alignment to the
+    allele it fits; `name`: the locus as the files spell it."""
+    __slots__ = ("ref_seq", "alt_seq", "reads", "name", "trace")
 
-    def __init__(self, ref_seq, alt_seq, reads):
-        self.ref_seq, self.alt_seq, self.reads = ref_seq, alt_seq, reads
+    def __init__(self, ref_seq, alt_seq, reads, name=None, trace=False):
+        self.ref_seq, self.alt_seq, self.reads, self.name, self.trace = ref_seq, alt_seq, reads, name, bool(trace)
 
 
 class Realigned(list):
@@ -615,6 +617,15 @@ def vapor_realign(driver, *args):
     """`--realign` for a DEL, INV, TANDUP or INS locus: the type's own driver runs as it is - its requests, its figure, its
     scores: the row's own columns - and the last Score request whose answer was a list is asked once more as a Realign request,
     whichever branch made it (the short window and the junction window are both just a Score request)."""
+    return (yield from _realign(None, False, driver, args))
+
+
+def vapor_realign_out(name, driver, *args):
+    """`--realign --realign-out`: vapor_realign whose Realign request carries the locus's name and asks for the traces."""
+    return (yield from _realign(name, True, driver, args))
+
+
+def _realign(name, trace, driver, args):
     gen = driver(*args)
     last = None
     try:
@@ -632,7 +643,8 @@ def vapor_realign(driver, *args):
         scores = fin.value
     out = Realigned(scores if scores is not None else [])
     if last is not None:
-        out.realign = yield Realign(last.ref_seq, last.alt_seq, last.reads)
+        out.realign = yield (Realign(last.ref_seq, last.alt_seq, last.reads, name, True) if trace else
+                             Realign(last.ref_seq, last.alt_seq, last.reads))
     return out
 
 

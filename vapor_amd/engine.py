@@ -726,6 +726,26 @@ class Engine:
         L.check(fn(self._ctx, seqset._h, n, pairs.ctypes.data if n else None, int(band), L.ptr(out, ctypes.c_int32)))
         return out[:n, 0].copy(), out[:n, 1].copy()
 
+    # ---- `--realign-out`: the alignment behind the distance ----
+    def realign_trace_available(self) -> bool:
+        """Whether the loaded library has vapor_realign_trace (the CPU twin of the C ABI has not)."""
+        return self._available("vapor_realign_trace")
+
+    def realign_trace(self, seqset: SeqSet, pairs: np.ndarray, band: int, cap_runs: int):
+        """(head, runs) of every pair (vapor_realign_trace): head an (n, 8) int32 array, a row {d, status, i_end, j_end, n_runs,
+        0, 0, 0}; runs an (n, cap_runs) uint32 array, a pair's runs (len << 2 | op; 0 '=', 1 'X', 2 'I', 3 'D') the last n_runs
+        words of its row, in path order (realign.runs_of reads them).  status is E_OVERFLOW for a pair that needs more than
+        cap_runs runs - n_runs says how many - and E_ARG, with d = -1, for a pair the entry refuses.
+        NotImplementedError where the library has no such entry: there is no other route."""
+        fn = self._wide_entry("vapor_realign_trace", "traceback kernel (--realign-out)")
+        pairs = np.ascontiguousarray(pairs, dtype=L.PAIR_DTYPE)
+        n, cap = len(pairs), int(cap_runs)
+        head = np.zeros((max(n, 1), 8), dtype=np.int32)
+        runs = np.zeros((max(n, 1), max(cap, 1)), dtype=np.uint32)
+        L.check(fn(self._ctx, seqset._h, n, pairs.ctypes.data if n else None, int(band), cap, L.ptr(head, ctypes.c_int32),
+                   L.ptr(runs, ctypes.c_uint32)))
+        return head[:n], runs[:n]
+
     def clean_hits_wide(self, lists: Sequence[np.ndarray], flags: Optional[Sequence[int]] = None):
         """clean_hits for lists with coordinates up to MAX_WIDE_SEQ_LEN (vapor_clean_hits_wide)."""
         return self._clean_lists(self._wide_entry("vapor_clean_hits_wide"), lists, flags)

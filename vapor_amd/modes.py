@@ -19,9 +19,12 @@ class Mode:
     `chunk_payloads`: None, or a hook (jobs, todo, engine) -> {t: payload} for a mode whose payload is not a property of a
     driver's result but of the chunk: called once for all of a chunk's loci, whatever route scores them - the four evidence modes'
     is one function over their module's reader surface (cli._evidence_payloads).
-    `--refine`'s own: `margin_step` = (M, T), and `ci_of` (cli.vcf_ci_readin: the bounds of a VCF record's candidates)."""
+    `--refine`'s own: `margin_step` = (M, T), and `ci_of` (cli.vcf_ci_readin: the bounds of a VCF record's candidates).
+    `sink`: None, or an object with take(job index, key, payload) that is shown every locus a rank scores, from the chunk's
+    thread (`--realign-out`: realign.TraceWriter)."""
     chunk_gens = None
     chunk_payloads = None
+    sink = None
 
     def __init__(self, name, src, attr, keys=None, skip_dot=True, phased=False, margin_step=None, ci_of=None):
         self.name, self.attr, self.skip_dot, self.phased = name, attr, skip_dot, phased
@@ -43,3 +46,10 @@ SIGNATURES = Mode("signatures", signature, "signatures")
 LINKS = Mode("links", links, "links")
 SUPPORT = Mode("support", support, "support")
 REALIGN = Mode("realign", realign, "realign")
+
+
+def realign_out(sink) -> Mode:
+    """`--realign --realign-out PREFIX`: REALIGN's columns, with the sink the loci's traces go to."""
+    m = Mode("realign", realign, "realign")
+    m.sink = sink
+    return m

@@ -564,9 +564,52 @@ def realign_requests(engine, reqs: Sequence[object]) -> List[object]:
     ss = engine.seqset(sb.seqs, None, sb.derived) if sb.derived else engine.seqset(sb.seqs)
     try:
         d, st = engine.realign(ss, pairs, realign.BAND)
+        out = [realign.payload(d[a:b:2], d[a + 1:b:2], st[a:b:2], st[a + 1:b:2]) for a, b in zip(first[:-1], first[1:])]
+        if any(r.trace for r in reqs):
+            _realign_traces(engine, ss, reqs, out, pairs, d, first)
     finally:
         ss.close()
-    return [realign.payload(d[a:b:2], d[a + 1:b:2], st[a:b:2], st[a + 1:b:2]) for a, b in zip(first[:-1], first[1:])]
+    return out
+
+
+def _realign_traces(engine, ss, reqs, out, pairs, d, first) -> None:
+    """`--realign-out`: one engine.realign_trace call over the set of the distances' call, one pair a read of
+    every request that asks for traces and has a payload - the read against the allele it fits (realign.fits_alt) - at a modest
+    cap_runs, and one more call for the pairs that overflowed, at n + m + 1, which always holds.  The traces ride on the
+    payload (`.traces`)."""
+    from . import realign
+    pick, where = [], []                      # the pair of the distances' table a read is traced on; (request, read)
+    for t, (r, a) in enumerate(zip(reqs, first[:-1])):
+        if not r.trace or out[t] is None:
+            continue
+        for k, diff in enumerate(out[t]):
+            pick.append(a + 2 * k + (1 if realign.fits_alt(diff) else 0))
+            where.append((t, k))
+    got = {}
+    todo, cap = list(range(len(pick))), realign.FIRST_CAP_RUNS
+    for attempt in (0, 1):
+        if not todo:
+            break
+        tp = pairs[np.asarray([pick[q] for q in todo], dtype=np.int64)]
+        head, runs = engine.realign_trace(ss, tp, realign.BAND, cap)
+        over = []
+        for q, h, w in zip(todo, head, runs):
+            if int(h[1]) == L.E_OVERFLOW and attempt == 0:
+                over.append(q)
+            else:
+                got[q] = (int(h[1]), int(h[2]), int(h[3]), realign.runs_of(h, w) if int(h[1]) == 0 else [])
+        todo, cap = over, 2 * L.MAX_SEQ_LEN + 1
+        if over:                              # (a path has at most n + m steps)
+            cap = min(cap, 1 + max(len(reqs[t].reads[k][0]) + max(len(reqs[t].ref_seq), len(reqs[t].alt_seq))
+                                   for t, k in (where[q] for q in over)))
+    for t, r in enumerate(reqs):
+        if r.trace and out[t] is not None:
+            out[t].traces = realign.Traces(r.ref_seq, r.alt_seq, [])
+    for q, (t, k) in enumerate(where):
+        status, i_end, j_end, rr = got[q]
+        x = reqs[t].reads[k]
+        a = first[t]
+        out[t].traces.reads.append((x[0], int(x[1]), int(d[a + 2 * k]), int(d[a + 2 * k + 1]), i_end, j_end, rr if status == 0 else []))
 
 
 # ------------------------------------------------------------------------------------------

@@ -77,6 +77,180 @@ def statement(read, allele, off2: int, band: int) -> int:
     return d
 
 
+# ---- `--realign-out`: the alignment behind d ----
+OPS = "=XID"                   # the op codes of a run word (len << 2 | op), as vapor_realign_trace writes them
+FIRST_CAP_RUNS = 64            # runs a pair of the first Engine.realign_trace call of a batch; an overflow is asked again at n + m + 1
+
+
+def trace_statement(read, allele, off2: int, band: int):
+    """(d, i_end, j_end, runs) of the pair: d as `statement` has it and the alignment 4.24's rule picks.  End cell: of the
+    existing cells of the last row and of the last column whose D equals d, the one with the largest i, among those the one
+    with the largest j.  From there back to (0, 0), at every cell: the diagonal predecessor if it exists and
+    D[i-1][j-1] + sub == D[i][j] ('=' where the symbols match, 'X' where not), otherwise the vertical one if it exists and
+    D[i-1][j] + 1 == D[i][j] ('I'), otherwise the horizontal one ('D'); row 0 is all horizontal.  runs: the path reversed and
+    run-length encoded, [(length, op)]; the n - i_end read symbols behind the end cell are soft-clipped and are no run.
+    `statement`'s rows with one byte kept per slot and row (the move out of that cell), so 65 535 rows fit."""
+    band, off2 = int(band), int(off2)
+    if not 1 <= band <= MAX_BAND:
+        raise ValueError("realign: band %d outside 1 .. %d" % (band, MAX_BAND))
+    if not 0 <= off2 <= len(allele):
+        raise ValueError("realign: off2 %d outside 0 .. %d" % (off2, len(allele)))
+    a = _bases(read, _NEVER_A)
+    b = _bases(allele, _NEVER_B)[off2:]
+    n, m, w = len(a), len(b), 2 * band + 1
+    c = np.arange(w, dtype=np.int64)
+    bpad = np.full(n + m + 2 * w + 2, _NEVER_B, dtype=np.int64)
+    bpad[band:band + m] = b
+    j = c - band
+    row = np.where((j >= 0) & (j <= m), j, _BIG)
+    col = m + band
+    moves = np.zeros((n + 1, w), dtype=np.uint8)
+    last_col = np.full(n + 1, _BIG, dtype=np.int64)                  # D[i][m], _BIG where the cell does not exist
+    if 0 <= col < w:
+        last_col[0] = row[col]
+    for i in range(1, n + 1):
+        j = c + (i - band)
+        sub = (bpad[i - 1:i - 1 + w] != a[i - 1]).astype(np.int64)
+        diag = row + sub
+        vert = np.append(row[1:], _BIG) + 1
+        t = np.where((j >= 0) & (j <= m), np.minimum(diag, vert), _BIG)
+        row = np.minimum(np.minimum.accumulate(t - c) + c, _BIG)
+        moves[i] = np.where(row == diag, sub, np.where(row == vert, 2, 3))
+        s = col - i
+        if 0 <= s < w:
+            last_col[i] = row[s]
+    jn = c + (n - band)
+    last_row = np.where((jn >= 0) & (jn <= m), row, _BIG)            # D[n][j] at slot j - n + band
+    d = int(min(last_row.min(), last_col.min()))
+    on_row = np.nonzero(last_row == d)[0]
+    if len(on_row):
+        i_end, j_end = n, int(jn[on_row[-1]])
+    else:
+        i_end, j_end = int(np.nonzero(last_col == d)[0][-1]), m
+    i, j, runs = i_end, j_end, []
+
+    def step(op):
+        if runs and runs[-1][1] == op:
+            runs[-1][0] += 1
+        else:
+            runs.append([1, op])
+    while i > 0:
+        mv = int(moves[i, j - i + band])
+        step(OPS[mv])
+        if mv < 2:
+            i, j = i - 1, j - 1
+        elif mv == 2:
+            i -= 1
+        else:
+            j -= 1
+    if j > 0:
+        if runs and runs[-1][1] == "D":
+            runs[-1][0] += j
+        else:
+            runs.append([j, "D"])
+    return d, i_end, j_end, [(k, op) for k, op in reversed(runs)]
+
+
+def runs_of(head, words):
+    """[(length, op)] of a pair from its head row and its row of run words (Engine.realign_trace): the last n_runs words."""
+    k = int(head[4])
+    return [(int(v) >> 2, OPS[int(v) & 3]) for v in words[len(words) - k:]] if k else []
+
+
+def fold_leading_d(runs):
+    """(lead, rest): a leading 'D' run's length - the read starts that far behind the allele's start, which a SAM record says
+    with POS - and the runs behind it; (0, runs) without one."""
+    if runs and runs[0][1] == "D":
+        return int(runs[0][0]), list(runs[1:])
+    return 0, list(runs)
+
+
+def cigar_text(runs, clip: int = 0) -> str:
+    """The runs as CIGAR text with a trailing soft clip of `clip` read symbols; '*' for nothing at all."""
+    return ("".join("%d%s" % (k, op) for k, op in runs) + ("%dS" % clip if clip else "")) or "*"
+
+
+def aligned(runs) -> bool:
+    """Whether a trace holds an '=' or 'X' run: a read without one is not written."""
+    return any(op in "=X" for _k, op in runs)
+
+
+def fits_alt(diff: int) -> bool:
+    """The allele a read's alignment is shown on: an ALT voter against alt, a REF voter against ref, a no-call against the
+    smaller distance, a tie against ref - alt iff d_ref - d_alt > 0."""
+    return int(diff) > 0
+
+
+def vote_text(diff: int) -> str:
+    return "ALT" if diff >= MARGIN else "REF" if diff <= -MARGIN else "NC"
+
+
+class Traces:
+    """What `--realign-out` writes of a locus: its two alleles as text and, per read in request order, (text, miss_bp, d_ref,
+    d_alt, i_end, j_end, runs) - the alignment against the allele the read fits (fits_alt of d_ref - d_alt).  Rides on the
+    locus's Payload as `.traces`, on the rank that scored it; pack / unpack never see it."""
+    __slots__ = ("ref", "alt", "reads")
+
+    def __init__(self, ref, alt, reads):
+        self.ref, self.alt, self.reads = str(ref), str(alt), list(reads)
+
+
+def sam_record(key: str, index: int, read) -> Optional[str]:
+    """The SAM line of read `index` of locus `key`; None for a read whose trace holds no '=' or 'X'."""
+    text, miss, d_ref, d_alt, i_end, _j_end, runs = read
+    if not aligned(runs):
+        return None
+    diff = int(d_ref) - int(d_alt)
+    on_alt = fits_alt(diff)
+    lead, rest = fold_leading_d(runs)
+    fields = ["%s/%d" % (key, index), "0", "%s|%s" % (key, "ALT" if on_alt else "REF"), str(int(miss) + 1 + lead), "255",
+              cigar_text(rest, len(text) - int(i_end)), "*", "0", "0", str(text), "*", "NM:i:%d" % (d_alt if on_alt else d_ref),
+              "rd:i:%d" % d_ref, "ad:i:%d" % d_alt, "vt:Z:%s" % vote_text(diff)]
+    return "\t".join(fields)
+
+
+class TraceWriter:
+    """The sink of `--realign-out PREFIX`: takes the loci a rank scores from any chunk thread, under a lock, and at close writes
+    PREFIX.fa and PREFIX.sam (PREFIX.rank<k>.* on rank k of several) in job order, so that the files depend neither on the
+    threads nor on the chunking.  PREFIX.fa: per locus with a payload `>KEY|REF` and `>KEY|ALT`, the whole allele on one line,
+    KEY the job's key as the table spells it, a repeated key with #2, #3, ..  PREFIX.sam: `@HD VN:1.6 SO:unknown`, one @SQ per
+    FASTA entry in that order, then the records (sam_record).  A locus without a payload writes nothing."""
+
+    def __init__(self, prefix: str, rank: int = 0, world: int = 1):
+        import threading
+        self.stem = prefix if world <= 1 else "%s.rank%d" % (prefix, rank)
+        self._lock = threading.Lock()
+        self._spool = {}
+
+    def take(self, order: int, key: str, payload) -> None:
+        traces = getattr(payload, "traces", None)
+        if traces is None:
+            return
+        with self._lock:
+            self._spool[int(order)] = (key, traces)
+
+    def close(self):
+        seen, names, fasta, records = {}, [], [], []
+        for order in sorted(self._spool):
+            key, tr = self._spool[order]
+            seen[key] = seen.get(key, 0) + 1
+            if seen[key] > 1:
+                key = "%s#%d" % (key, seen[key])
+            for tag, allele in (("REF", tr.ref), ("ALT", tr.alt)):
+                names.append(("%s|%s" % (key, tag), len(allele)))
+                fasta.append(">%s|%s\n%s\n" % (key, tag, allele))
+            for k, read in enumerate(tr.reads):
+                line = sam_record(key, k, read)
+                if line is not None:
+                    records.append(line + "\n")
+        with open(self.stem + ".fa", "w") as f:
+            f.write("".join(fasta))
+        with open(self.stem + ".sam", "w") as f:
+            f.write("@HD\tVN:1.6\tSO:unknown\n" + "".join("@SQ\tSN:%s\tLN:%d\n" % nl for nl in names) + "".join(records))
+        self._spool = {}
+        return self.stem + ".sam", self.stem + ".fa"
+
+
 def votes(d_ref, d_alt) -> List[int]:
     """Per read its diff = d_ref - d_alt: the read votes ALT iff diff >= MARGIN, REF iff diff <= -MARGIN, else it makes no call."""
     return [int(r) - int(a) for r, a in zip(d_ref, d_alt)]
