@@ -105,7 +105,11 @@ const char* vapor_last_error(void);
 int vapor_init(int device_ordinal, vapor_ctx** ctx);
 int vapor_destroy(vapor_ctx* ctx);
 /* tuning knobs: "reads_per_task" (at most this many pairs per join workgroup, <= 64), "join_tasks" (number of
- * join workgroups a launch is cut into; default = number of CUs), "max_pair_cap" (largest record slot a pair may
+ * join workgroups a launch is cut into; default = number of CUs), "join_align" (read at vapor_plan_create.  0: every run
+ * takes the cost-balanced task table; 2: every run takes the window-aligned one - every task the reads of ONE allele, no table
+ * built again by a neighbouring task, the tasks less even; 1, the default: blocking runs take the balanced table, an asynchronous
+ * step the aligned one while a step of another plan of the context is in flight beside it and the planner's cost model sees
+ * enough builds saved - the aligned table is made by the plan's first asynchronous step), "max_pair_cap" (largest record slot a pair may
  * grow to on an overflow rerun; beyond it the pair keeps VAPOR_E_OVERFLOW), "shared_join" (1, the default: a read scored
  * against a window and alleles derived from it - vapor_seqset_create_derived - is joined once for all of them; 0: one join per
  * pair), "remap_in_clean" (who cuts a served pair's records out of a shared dot plot.  1, the default: the workgroup that cleans
@@ -183,7 +187,9 @@ int vapor_plan_run(vapor_plan* plan, int64_t* stats);
  * library's stream: ms[0] = join kernels (and remap_kernel where the plan runs it), ms[1] = clean kernels, ms[2] = whole run incl.
  * copies, ms[3] = number of join launches, ms[4] = number of retried pairs, ms[5] = finish kernel, ms[6] = pairs served by a shared
  * join, ms[7] = joins that serve them, ms[8] = clean workgroups per CU (what the staged records leave room for), ms[9] = 1 when
- * the clean workgroups cut the served pairs' records out of the shared dot plots themselves ("remap_in_clean") */
+ * the clean workgroups cut the served pairs' records out of the shared dot plots themselves ("remap_in_clean"), ms[10] = join
+ * tasks (workgroups) of the task table the last run took, ms[11] = allele tables that run built (per task: alleles x tiles;
+ * "join_align").  n = how many of the twelve the caller wants. */
 int vapor_plan_timings(vapor_plan* plan, double* ms, int32_t n);
 /* run records the join of the last run wrote per pair (n_pairs int64): the device keeps runs of consecutive
  * dots (j+t, i+t) / (j-t, i+t) as one record; stats[0] stays the number of dots */

@@ -86,6 +86,7 @@ struct vapor_ctx {
     hipStream_t lane[2] = {nullptr, nullptr};
     hipStream_t fin[2] = {nullptr, nullptr};   // per lane: the stream its plans' finish kernels go to (highest priority)
     unsigned lane_rr = 0;
+    vapor_plan* lane_plan[2] = {nullptr, nullptr};   // per lane: the plan whose asynchronous step was enqueued last (join_table_for_async)
     bool user_stream = false;
     // staging for vapor_seqset_create*, kept between calls (pinned allocations are slow): ASCII chunks + chunk map
     uint8_t* h_stage = nullptr;
@@ -97,6 +98,7 @@ struct vapor_ctx {
     int reads_per_task = MAX_READS_PER_TASK;   // upper bound on pairs per join task
     int n_cus = 256;
     int join_tasks = 256;                      // join tasks aimed for per launch (cost-balanced ranges): one per CU
+    int join_align = 1;                        // which task table a run takes: 0 the cost-balanced one, 2 the window-aligned one, 1 by run (join_table_for_async)
     int64_t max_pair_cap = (int64_t)1 << 28;
     bool shared_join = true;                   // reads scored against a window and alleles derived from it: one join for all
     int remap_in_clean = 1;                    // ... and the clean workgroup of a target cuts its records out of the shared plot (0: remap_kernel)
@@ -263,6 +265,11 @@ struct vapor_plan : PlanLayout {   // the layout the planner made (vapor_planner
     int64_t total_cap = 0;
     DPair* d_pairs = nullptr;
     DTask* d_tasks = nullptr;
+    DTask* d_atasks = nullptr;              // the window-aligned table (`atasks`), NULL when the plan was made with join_align 0
+    int join_align = 0;                     // the context's parameter when the plan was made
+    PlanParams params{};                    // ... and what the planner read of the context then
+    bool aligned_made = false;              // join_align 1: `atasks` exists (made and uploaded by the first asynchronous step)
+    int last_table = 0;                     // the table the last run took: 0 `tasks`, 1 `atasks`
     int32_t* d_task_pairs = nullptr;
     unsigned long long* d_hits = nullptr;   // run records (VREC_*), hp[].cap slots per pair
     uint8_t* d_hflags = nullptr;            // one flag byte per record
@@ -280,6 +287,7 @@ struct vapor_plan : PlanLayout {   // the layout the planner made (vapor_planner
     double* h_loci = nullptr;                  // pinned copy of the per-locus records of the last async step
     hipEvent_t ev_t0 = nullptr;
     hipStream_t lane = nullptr;                // the stream this plan's asynchronous steps are enqueued on
+    int lane_ix = -1;                          // ... as an index into the context's lanes
     hipStream_t fin = nullptr;                 // ... and the one their finish kernels go to (NULL: the lane itself)
     hipEvent_t ev_clean = nullptr;             // the clean kernels of the last enqueued step are done (lane -> fin)
     hipEvent_t ev_fin = nullptr;               // its finish kernel is done (fin -> lane: the next step's clean kernels wait for it)
@@ -435,6 +443,11 @@ extern "C" int vapor_set_param(vapor_ctx* c, const char* name, int64_t v)
     if (!strcmp(name, "join_tasks")) {
         if (v < 1) return fail(VAPOR_E_ARG, "join_tasks out of range");
         c->join_tasks = (int)v;
+        return VAPOR_OK;
+    }
+    if (!strcmp(name, "join_align")) {
+        if (v < 0 || v > 2) return fail(VAPOR_E_ARG, "vapor_set_param: join_align is 0, 1 or 2");
+        c->join_align = (int)v;
         return VAPOR_OK;
     }
     if (!strcmp(name, "max_pair_cap")) {
@@ -1419,6 +1432,7 @@ static void plan_free_device(vapor_plan* p)
 {
     dfree(p->ctx, p->d_pairs); p->d_pairs = nullptr;
     dfree(p->ctx, p->d_tasks); p->d_tasks = nullptr;
+    dfree(p->ctx, p->d_atasks); p->d_atasks = nullptr;
     dfree(p->ctx, p->d_task_pairs); p->d_task_pairs = nullptr;
     dfree(p->ctx, p->d_hits); p->d_hits = nullptr;
     dfree(p->ctx, p->d_hflags); p->d_hflags = nullptr;
@@ -1440,6 +1454,9 @@ extern "C" int vapor_plan_destroy(vapor_plan* p)
         (void)hipStreamSynchronize(p->lane);
         if (p->fin) (void)hipStreamSynchronize(p->fin);
     }
+    if (ctx_alive(p->ctx))
+        for (auto& q : p->ctx->lane_plan)
+            if (q == p) q = nullptr;
     plan_free_device(p);
     hfree(p->ctx, p->h_stats);
     hfree(p->ctx, p->h_overflow);
@@ -1502,10 +1519,16 @@ extern "C" int vapor_plan_create(vapor_ctx* ctx, vapor_seqset* set, int64_t n_pa
     p->device = ctx->device;
     p->set = set;
     p->n_pairs = n_pairs;
-    static_cast<PlanLayout&>(*p) = plan_layout(PlanParams{ctx->reads_per_task, ctx->join_tasks, ctx->max_pair_cap, ctx->shared_join,
-                                                          tile_pos<JoinCfg, 2>(), tile_pos<JoinCfg, 4>()},
+    // (join_align 1: the aligned table is made by the plan's first asynchronous step, join_table_for_async - a plan that is only ever
+    // run blocking, a pipeline chunk's, does not pay for it: 2.8 ms of host time on 40 000 joins)
+    p->params = PlanParams{ctx->reads_per_task, ctx->join_tasks, ctx->max_pair_cap, ctx->shared_join,
+                           tile_pos<JoinCfg, 2>(), tile_pos<JoinCfg, 4>(), ctx->join_align == 2};
+    static_cast<PlanLayout&>(*p) = plan_layout(p->params,
                                                SetView{set->h, set->n, set->n_lit, set->derived, set->groups, set->group_of, set->slot_of},
                                                n_pairs, pairs);
+    p->join_align = ctx->join_align;
+    // (join_align 2: the aligned table is the plan's only one - blocking runs, asynchronous steps and vapor_debug_plan_tasks see it)
+    if (p->join_align == 2) { p->tasks = p->atasks; p->launches = p->alaunches; p->model[0] = p->model[1]; }
     p->hcap_want = (int)std::min<int64_t>(p->hwant, CLEAN_HCAP_MAX);
     p->n_dpairs = (int64_t)p->shares.size();
     HIPCHK(dmalloc(ctx, (void**)&p->d_pairs, sizeof(DPair) * p->hp.size()));
@@ -1550,20 +1573,20 @@ extern "C" int vapor_plan_create(vapor_ctx* ctx, vapor_seqset* set, int64_t n_pa
 }
 
 template <int BPS, int K>
-static void launch_join(vapor_plan* p, const Launch& L, bool first, hipStream_t st)
+static void launch_join(vapor_plan* p, const Launch& L, const DTask* d_tasks, bool first, hipStream_t st)
 {
     const vapor_seqset* s = p->set;
     if (BPS == 2 && L.exc == 1)
         hipLaunchKernelGGL((join_kernel<JoinCfg, BPS, K, (BPS == 2 ? 1 : 0)>), dim3((unsigned)L.n_tasks), dim3(JoinCfg::THREADS), JOIN_DYN_LDS(BPS),
-                           st, s->d_seqs, s->d_p2, s->d_e1, s->d_x4, p->d_pairs, p->d_tasks + L.task_begin,
+                           st, s->d_seqs, s->d_p2, s->d_e1, s->d_x4, p->d_pairs, d_tasks + L.task_begin,
                            p->d_task_pairs, p->d_hits, p->d_nhits, first ? p->d_overflow : (unsigned int*)nullptr);
     else if (BPS == 2 && L.exc == 2)
         hipLaunchKernelGGL((join_kernel<JoinCfg, BPS, K, (BPS == 2 ? 2 : 0)>), dim3((unsigned)L.n_tasks), dim3(JoinCfg::THREADS), JOIN_DYN_LDS(BPS),
-                           st, s->d_seqs, s->d_p2, s->d_e1, s->d_x4, p->d_pairs, p->d_tasks + L.task_begin,
+                           st, s->d_seqs, s->d_p2, s->d_e1, s->d_x4, p->d_pairs, d_tasks + L.task_begin,
                            p->d_task_pairs, p->d_hits, p->d_nhits, first ? p->d_overflow : (unsigned int*)nullptr);
     else
         hipLaunchKernelGGL((join_kernel<JoinCfg, BPS, K, 0>), dim3((unsigned)L.n_tasks), dim3(JoinCfg::THREADS), JOIN_DYN_LDS(BPS),
-                           st, s->d_seqs, s->d_p2, s->d_e1, s->d_x4, p->d_pairs, p->d_tasks + L.task_begin,
+                           st, s->d_seqs, s->d_p2, s->d_e1, s->d_x4, p->d_pairs, d_tasks + L.task_begin,
                            p->d_task_pairs, p->d_hits, p->d_nhits, first ? p->d_overflow : (unsigned int*)nullptr);
 }
 
@@ -1657,30 +1680,83 @@ static bool remap_in_clean(const vapor_plan* p)
     return p->n_pairs <= 4 * (int64_t)cg.per_cu * p->ctx->n_cus;
 }
 
+// Which task table an asynchronous step takes under join_align 1.  Blocking runs always take the cost-balanced table: there one
+// plan's latency is what the caller waits for, and the aligned table's dearer tasks are that latency.  The same holds for the
+// asynchronous steps of ONE plan, which lie behind each other on its stream (cfg2, one plan: 0.1679-0.1694 -> 0.1733-0.1744 ms a
+// pass with the aligned table, join 0.079 -> 0.084), so a step takes the aligned table only while a step of another plan is in
+// flight on the context's other lane (by the host's books: it has enqueued steps nobody has waited for yet) - then the CUs the
+// fewer or shorter join tasks leave go to that plan's clean workgroups.
+// Measured with two plans in flight, join_align 0 against 2, five alternating runs each on one box, no two ranges overlapping
+// (profiles/join_align.txt), beside what the planner's cost units (TableModel) say of the two tables:
+//   cfg2   0.1241-0.1248 -> 0.1223-0.1230 ms   300 -> 250 builds   sum of the tasks -3.0 %   dearest task +9.5 %
+//   cfg3   3.210-3.219   -> 3.172-3.178        1700 -> 1000        -1.7 %                    -25 %  (1 000 tasks of 40 reads for 768 of 52)
+//   small  0.7772-0.7795 -> 0.7670-0.7695      2671 -> 2000        -2.5 %                    -57 %  (2 000 tasks)
+// The aligned table won on all three, so the sweep gives no shape where it loses with two plans in flight; the two thresholds
+// are the edges of what was measured, not of what wins: a saving of at least 1.5 % of the tasks' sum (cfg3's 1.7 % is the
+// smallest that was seen to pay; below it the model sees less than a run can tell from noise) and a dearest task at most 10 %
+// dearer than the balanced table's (cfg2's 9.5 % is the dearest that was seen to pay).  Between and beyond these shapes the rule
+// is a guess - a plan whose aligned tasks are 20 % dearer for 5 % fewer builds may well win and is turned down.
+constexpr int JOIN_ALIGN_MIN_SAVING_PM = 15;       // per mille of the balanced table's sum
+constexpr int JOIN_ALIGN_MAX_DEARER_PCT = 10;
+static bool join_align_pays(const TableModel& bal, const TableModel& ali)
+{
+    return ali.n_tasks > 0 && (bal.sum - ali.sum) * 1000 >= bal.sum * JOIN_ALIGN_MIN_SAVING_PM && ali.path * 100 <= bal.path * (100 + JOIN_ALIGN_MAX_DEARER_PCT);
+}
+static int join_table_for_async(vapor_plan* p, hipStream_t st, int* table)
+{
+    *table = 0;
+    if (p->join_align != 1) return VAPOR_OK;                   // (0 and 2: the plan has one table)
+    const vapor_ctx* c = p->ctx;
+    if (c->user_stream || p->lane_ix < 0) return VAPOR_OK;     // (one stream for every plan: nothing runs beside this step)
+    // a step of another plan in flight beside this one, by the host's own books: the plan enqueued last on the other lane has
+    // steps that no vapor_plan_sync or blocking run has waited for yet (no question to the device: the same calls take the same tables)
+    const vapor_plan* o = c->lane_plan[1 - p->lane_ix];
+    if (!o || o == p || o->ring_n <= 0) return VAPOR_OK;
+    if (!p->aligned_made) {
+        const vapor_seqset* s = p->set;
+        plan_aligned(p->params, SetView{s->h, s->n, s->n_lit, s->derived, s->groups, s->group_of, s->slot_of}, p);
+        p->aligned_made = true;
+        if (!p->atasks.empty() && join_align_pays(p->model[0], p->model[1])) {
+            // (on the step's own stream, in front of its join; `atasks` lives as long as the plan)
+            HIPCHK(dmalloc(p->ctx, (void**)&p->d_atasks, sizeof(DTask) * p->atasks.size()));
+            HIPCHK(hipMemcpyAsync(p->d_atasks, p->atasks.data(), sizeof(DTask) * p->atasks.size(), hipMemcpyHostToDevice, st));
+        }
+    }
+    if (p->d_atasks) *table = 1;                               // (else: the model does not see the aligned table pay)
+    return VAPOR_OK;
+}
+
 // keep_flags: the clean kernel writes the per-record flag bytes beside the pairs' records - what vapor_plan_fetch_hits hands out;
 // the device-finished path (vapor_plan_run_loci*) needs the statistics only and leaves that pass out.
-static int plan_run_once(vapor_plan* p, bool fetch_stats = true, hipEvent_t* evs = nullptr, hipStream_t on = nullptr, bool skip_big = false,
+// `table`: the join's task table, 0 the plan's own (`tasks`), 1 the window-aligned one beside it (`atasks`, join_align 1).  The
+// tables cut the same sorted pair list and a pair lies whole inside one task of either, so what a pair's records are does not
+// depend on the table (tests/test_gpu_join_align.py holds the library to that).
+static int plan_run_once(vapor_plan* p, int table, bool fetch_stats = true, hipEvent_t* evs = nullptr, hipStream_t on = nullptr, bool skip_big = false,
                          hipEvent_t before_clean = nullptr, bool keep_flags = true)
 {
     vapor_ctx* c = p->ctx;
     hipStream_t st = on ? on : c->stream;
     hipEvent_t* ev = evs ? evs : p->ev;
+    if (table == 1 && !p->d_atasks) table = 0;
+    const std::vector<Launch>& launches = table == 1 ? p->alaunches : p->launches;
+    const DTask* d_tasks = table == 1 ? p->d_atasks : p->d_tasks;
+    p->last_table = table;
     // no memsets in the steady state: the pair counts are stored whole by the join, the clean kernels' two
     // counters are cleared by the first join launch
-    if (p->launches.empty()) HIPCHK(hipMemsetAsync(p->d_overflow, 0, 2 * sizeof(unsigned int), st));
+    if (launches.empty()) HIPCHK(hipMemsetAsync(p->d_overflow, 0, 2 * sizeof(unsigned int), st));
     HIPCHK(hipEventRecord(ev[0], st));       // start of the run and of the join
     bool first = true;
-    for (const Launch& L : p->launches) {
+    for (const Launch& L : launches) {
         if (L.bps == 2) {
-            if (L.k == 10) launch_join<2, 10>(p, L, first, st);
-            else if (L.k == 20) launch_join<2, 20>(p, L, first, st);
-            else if (L.k == 30) launch_join<2, 30>(p, L, first, st);
-            else launch_join<2, 40>(p, L, first, st);
+            if (L.k == 10) launch_join<2, 10>(p, L, d_tasks, first, st);
+            else if (L.k == 20) launch_join<2, 20>(p, L, d_tasks, first, st);
+            else if (L.k == 30) launch_join<2, 30>(p, L, d_tasks, first, st);
+            else launch_join<2, 40>(p, L, d_tasks, first, st);
         } else {
-            if (L.k == 10) launch_join<4, 10>(p, L, first, st);
-            else if (L.k == 20) launch_join<4, 20>(p, L, first, st);
-            else if (L.k == 30) launch_join<4, 30>(p, L, first, st);
-            else launch_join<4, 40>(p, L, first, st);
+            if (L.k == 10) launch_join<4, 10>(p, L, d_tasks, first, st);
+            else if (L.k == 20) launch_join<4, 20>(p, L, d_tasks, first, st);
+            else if (L.k == 30) launch_join<4, 30>(p, L, d_tasks, first, st);
+            else launch_join<4, 40>(p, L, d_tasks, first, st);
         }
         first = false;
         HIPCHK(hipGetLastError());
@@ -1746,7 +1822,7 @@ extern "C" int vapor_plan_run(vapor_plan* p, int64_t* stats)
     }
     p->n_retried = 0;
     for (int attempt = 0; attempt < 3; ++attempt) {
-        int rc = plan_run_once(p);
+        int rc = plan_run_once(p, 0);
         if (rc != VAPOR_OK) return rc;
         // pairs whose hit count exceeded their slot: enlarge to the exact count and rerun
         int64_t grow = 0;
@@ -1818,9 +1894,11 @@ extern "C" int vapor_plan_timings(vapor_plan* p, double* ms, int32_t n)
 {
     if (!p || !ms) return fail(VAPOR_E_ARG, "vapor_plan_timings: null argument");
     const CleanGeom cg = clean_geom(p->range_words_cap, p->hcap_want, p->hcap_measured);
-    double v[10] = {p->t_join, p->t_clean, p->t_total, (double)p->launches.size(), (double)p->n_retried, p->t_finish,
-                    (double)p->n_served, (double)p->n_dpairs, (double)cg.per_cu, remap_in_clean(p) ? 1.0 : 0.0};
-    for (int i = 0; i < n && i < 10; ++i) ms[i] = v[i];
+    const TableModel& tm = p->model[p->last_table];
+    double v[12] = {p->t_join, p->t_clean, p->t_total, (double)p->launches.size(), (double)p->n_retried, p->t_finish,
+                    (double)p->n_served, (double)p->n_dpairs, (double)cg.per_cu, remap_in_clean(p) ? 1.0 : 0.0,
+                    (double)tm.n_tasks, (double)tm.builds};
+    for (int i = 0; i < n && i < 12; ++i) ms[i] = v[i];
     return VAPOR_OK;
 }
 
@@ -2708,7 +2786,7 @@ extern "C" int vapor_plan_run_loci(vapor_plan* p, void* d_loci_out, double* loci
         if (host_status)
             HIPCHK(hipMemcpyAsync(p->d_stats, p->h_stats, sizeof(long long) * 16 * (size_t)p->n_pairs, hipMemcpyHostToDevice, st));
     } else {
-        rc = plan_run_once(p, false, nullptr, nullptr, false, nullptr, false);
+        rc = plan_run_once(p, 0, false, nullptr, nullptr, false, nullptr, false);
         if (rc != VAPOR_OK) return rc;
     }
     hipEvent_t e1 = p->ev_f[1];                  // the finish kernel starts where the clean kernels end (ev[2])
@@ -2906,6 +2984,7 @@ static int plan_lane(vapor_plan* p, hipStream_t* out)
             }
         }
         p->lane = c->lane[l];
+        p->lane_ix = (int)l;
         p->fin = c->fin[l];
     }
     *out = p->lane;
@@ -2972,7 +3051,10 @@ extern "C" int vapor_plan_run_loci_async(vapor_plan* p, void* d_loci_out)
     // run counted before it resized the slots is not theirs
     if (p->ring_n == 0 && p->acc_n == 0) HIPCHK(hipMemsetAsync(p->d_overflow + 2, 0, sizeof(unsigned int), st));
     hipEvent_t* ev = p->ring[(size_t)p->ring_n].data();
-    rc = plan_run_once(p, false, ev, st, p->big_known && p->n_big == 0, (fs != st && p->have_fin) ? p->ev_fin : nullptr, false);
+    int table = 0;
+    rc = join_table_for_async(p, st, &table);
+    if (rc != VAPOR_OK) return rc;
+    rc = plan_run_once(p, table, false, ev, st, p->big_known && p->n_big == 0, (fs != st && p->have_fin) ? p->ev_fin : nullptr, false);
     if (rc != VAPOR_OK) return rc;
     double* d_out = d_loci_out ? static_cast<double*>(d_loci_out) : p->d_loci;
     if (fs != st) {
@@ -2992,6 +3074,7 @@ extern "C" int vapor_plan_run_loci_async(vapor_plan* p, void* d_loci_out)
         p->have_fin = true;
     }
     p->have_last = true;
+    if (!p->ctx->user_stream && p->lane_ix >= 0) p->ctx->lane_plan[p->lane_ix] = p;
     ++p->ring_n;
     return VAPOR_OK;
 }

@@ -1,8 +1,8 @@
 // vapor_planner.h - the host arithmetic that decides what the kernels are told to do, without HIP: the share groups of a
 // sequence set (share_layout), the plan of a list of pairs - validation, shared joins and their remap tables, launches and
-// cost-balanced join tasks (plan_layout) - and the order of the clean workgroups (clean_order).  vapor_hip.hip calls these and
-// does the allocations and uploads; tools/planner_check.cpp runs them on a CPU under the sanitizers, against direct statements
-// of their rules.
+// cost-balanced join tasks (plan_layout), the window-aligned task table beside them (plan_aligned) - and the order of the clean
+// workgroups (clean_order).  vapor_hip.hip calls these and does the allocations and uploads; tools/planner_check.cpp and
+// tools/planner_align_check.cpp run them on a CPU under the sanitizers, against direct statements of their rules.
 #pragma once
 #include "vapor_records.h"
 #include "vapor_hip.h"
@@ -142,6 +142,7 @@ struct PlanParams {
     int64_t max_pair_cap;
     bool shared_join;
     int tile2, tile4;              // allele positions per join tile on the 2-bit and on the 4-bit planes (tile_pos<JoinCfg, BPS>())
+    bool align_tasks = false;      // also make the window-aligned task table (PlanLayout::atasks); `tasks` is the same either way
 };
 // ... and of the sequence set: its host view.
 struct SetView {
@@ -153,6 +154,10 @@ struct SetView {
     const std::vector<int32_t>& slot_of;
 };
 
+// A task table in the planner's own cost units (plan_launch_tasks): every task's probes and table builds summed, the dearest
+// task of every launch summed over the launches (they run one behind the other), and the tables built (per task: alleles x tiles).
+struct TableModel { int64_t sum = 0, path = 0, builds = 0, n_tasks = 0; };
+
 // What a plan is before anything of it is on the device.
 struct PlanLayout {
     std::vector<DPair> hp;                     // the caller's pairs, then the (read, shared sequence) pairs the shared joins run
@@ -160,6 +165,11 @@ struct PlanLayout {
     std::vector<DTask> tasks;
     std::vector<int32_t> task_pairs;
     std::vector<Launch> launches;
+    // the window-aligned table (PlanParams::align_tasks): the same launches over the same task_pairs, every task the pairs of ONE
+    // allele (plan_launch_aligned)
+    std::vector<DTask> atasks;
+    std::vector<Launch> alaunches;
+    TableModel model[2];                       // what the planner's cost units say of `tasks` [0] and of `atasks` [1]
     // shared joins (remap_kernel): pairs n_pairs .. n_pairs + shares.size() - 1 of hp are the (read, shared sequence) pairs the
     // join runs instead of the pairs they serve
     std::vector<DShare> shares;
@@ -369,6 +379,13 @@ inline void plan_shared_joins(const PlanParams& P, const SetView& S, int64_t n_p
     }
 }
 
+// The planner's cost units: probing a read against the tiles of an allele, and building an allele's table
+inline int64_t probe_cost(const PlanParams& P, const SetView& S, const DPair& d, int k, int m)
+{
+    return (int64_t)S.h[d.seq1].len * allele_tiles(P, S.h[d.seq2].len, k, m) + 256;
+}
+inline int64_t build_cost(const SetView& S, const DPair& d) { return (VAPOR_BUILD_COST_X8 * (int64_t)S.h[d.seq2].len) / 8; }
+
 // The tasks of one launch: pairs task_pairs[q, e), all of mode m and one k, sorted by allele.
 // Cost of a range of consecutive pairs = its probe passes + one table build for its first allele + one for
 // every further allele it reaches into.  The ranges are the contiguous partition into at most `want`
@@ -382,8 +399,8 @@ inline void plan_launch_tasks(const PlanParams& P, const SetView& S, size_t q, s
     int64_t total = 0, biggest = 0;
     for (size_t t = q; t < e; ++t) {
         const DPair& d = L->hp[order[t]];
-        probe[t - q] = (int64_t)S.h[d.seq1].len * allele_tiles(P, S.h[d.seq2].len, k, m) + 256;
-        build[t - q] = (VAPOR_BUILD_COST_X8 * (int64_t)S.h[d.seq2].len) / 8;
+        probe[t - q] = probe_cost(P, S, d, k, m);
+        build[t - q] = build_cost(S, d);
         total += probe[t - q] + build[t - q];
         biggest = std::max(biggest, probe[t - q] + build[t - q]);
     }
@@ -442,6 +459,134 @@ inline void plan_launch_tasks(const PlanParams& P, const SetView& S, size_t q, s
     }
 }
 
+// The same launch cut at allele boundaries: every task holds pairs of ONE allele, so that a workgroup builds one table (per tile)
+// and no table is built again by the neighbour that a cost-balanced range reaches into.  A group is the pairs of one allele; a
+// range of it costs its probes plus one build.  Under a bound a group needs the fewest ranges greedy packing gives (reads are
+// indivisible, at most reads_per_task a range); the launch takes the smallest bound whose groups need at most `join_tasks`
+// ranges together (bisection, as above) - or, when the groups' fewest ranges are more than that already (more windows than CUs),
+// those fewest - and every group is then cut into exactly the ranges that bound needs, as evenly as that many ranges allow:
+// ranges beyond them would be builds for nothing.
+// "No table built twice" therefore holds between windows, not inside one: the smallest bound uses the tasks `join_tasks` offers,
+// so a launch of fewer groups than that cuts its groups further - down to one read a task when the tasks suffice (a launch of
+// four reads of one window and join_tasks 7: four tasks, four builds of the one table, where one task would build it once; cfg2's
+// 250 tasks for 100 windows are the same rule).  Those builds run side by side on CUs that would stand idle, so they shorten the
+// launch and cost CU-time; the table's model carries them (TableModel::sum), and the library takes the aligned table only where
+// that sum still comes out below the balanced table's (join_align_pays).
+inline void plan_launch_aligned(const PlanParams& P, const SetView& S, size_t q, size_t e, int m, PlanLayout* L)
+{
+    const std::vector<int32_t>& order = L->task_pairs;
+    const int k = L->hp[order[q]].k;
+    const size_t n = e - q;
+    std::vector<int64_t> probe(n);
+    std::vector<size_t> group{0};                     // first pair of every group, then n
+    int64_t total = 0, biggest = 0;
+    for (size_t t = 0; t < n; ++t) {
+        const DPair& d = L->hp[order[q + t]];
+        probe[t] = probe_cost(P, S, d, k, m);
+        if (t > 0 && d.seq2 != L->hp[order[q + t - 1]].seq2) group.push_back(t);
+        total += probe[t] + build_cost(S, d);
+        biggest = std::max(biggest, probe[t] + build_cost(S, d));
+    }
+    group.push_back(n);
+    const size_t n_g = group.size() - 1;
+    // ranges group g needs under a bound (cuts[] = first pair of every range when asked for)
+    auto pack = [&](size_t g, int64_t bound, std::vector<size_t>* cuts) {
+        const int64_t build = build_cost(S, L->hp[order[q + group[g]]]);
+        int64_t ranges = 0, acc = 0;
+        size_t t0 = group[g];
+        for (size_t t = group[g]; t < group[g + 1]; ++t) {
+            if (t > t0 && (acc + probe[t] > bound || (int)(t - t0) >= P.reads_per_task)) {
+                ++ranges;
+                if (cuts) cuts->push_back(t0);
+                t0 = t;
+                acc = 0;
+            }
+            if (t == t0) acc = build;
+            acc += probe[t];
+        }
+        if (cuts) cuts->push_back(t0);
+        return ranges + 1;
+    };
+    auto pack_all = [&](int64_t bound) {
+        int64_t ranges = 0;
+        for (size_t g = 0; g < n_g; ++g) ranges += pack(g, bound, nullptr);
+        return ranges;
+    };
+    const int64_t want = std::max(1, P.join_tasks);
+    int64_t lo = biggest, hi = total;                 // (under `total` only reads_per_task cuts a group)
+    if (pack_all(hi) <= want)
+        while (lo < hi) {
+            const int64_t mid = lo + (hi - lo) / 2;
+            if (pack_all(mid) <= want) hi = mid; else lo = mid + 1;
+        }
+    const int64_t bound = hi;
+    L->alaunches.push_back(launch_of_mode(m, k, (int)L->atasks.size()));
+    std::vector<size_t> cuts;
+    for (size_t g = 0; g < n_g; ++g) {
+        // the group's own smallest bound for the ranges the launch's bound gives it
+        const int64_t m_g = pack(g, bound, nullptr);
+        int64_t glo = 0, ghi = bound;
+        for (size_t t = group[g]; t < group[g + 1]; ++t) glo = std::max(glo, probe[t]);
+        glo += build_cost(S, L->hp[order[q + group[g]]]);
+        while (glo < ghi) {
+            const int64_t mid = glo + (ghi - glo) / 2;
+            if (pack(g, mid, nullptr) <= m_g) ghi = mid; else glo = mid + 1;
+        }
+        cuts.clear();
+        pack(g, ghi, &cuts);
+        for (size_t c = 0; c < cuts.size(); ++c) {
+            const size_t t0 = q + cuts[c], t1 = q + (c + 1 < cuts.size() ? cuts[c + 1] : group[g + 1]);
+            DTask tk;
+            tk.seq2 = L->hp[order[t0]].seq2; tk.k = k; tk.n_reads = (int32_t)(t1 - t0); tk.first = (int32_t)t0;
+            L->atasks.push_back(tk);
+            L->alaunches.back().n_tasks++;
+        }
+    }
+}
+
+inline int mode_of_launch(const Launch& la) { return la.bps == 4 ? 4 : (la.exc == 1 ? 3 : la.exc == 2 ? 5 : 2); }
+
+// A task table of the layout in the planner's cost units
+inline TableModel table_model(const PlanParams& P, const SetView& S, const PlanLayout& L, const std::vector<DTask>& tasks,
+                              const std::vector<Launch>& launches)
+{
+    TableModel M;
+    for (const Launch& la : launches) {
+        const int m = mode_of_launch(la);
+        int64_t dearest = 0;
+        for (int x = 0; x < la.n_tasks; ++x) {
+            const DTask& tk = tasks[(size_t)(la.task_begin + x)];
+            int64_t cost = 0;
+            for (int32_t t = tk.first; t < tk.first + tk.n_reads; ++t) {
+                const DPair& d = L.hp[(size_t)L.task_pairs[(size_t)t]];
+                cost += probe_cost(P, S, d, la.k, m);
+                if (t == tk.first || d.seq2 != L.hp[(size_t)L.task_pairs[(size_t)t - 1]].seq2) {
+                    cost += build_cost(S, d);
+                    M.builds += allele_tiles(P, S.h[d.seq2].len, la.k, m);
+                }
+            }
+            M.sum += cost;
+            dearest = std::max(dearest, cost);
+        }
+        M.path += dearest;
+        M.n_tasks += la.n_tasks;
+    }
+    return M;
+}
+
+// The window-aligned table of a layout beside its cost-balanced one: launch by launch over the same pairs.  plan_layout makes it
+// when PlanParams::align_tasks asks for it; a caller that may never need it makes it later, with the parameters of the layout.
+inline void plan_aligned(const PlanParams& P, const SetView& S, PlanLayout* L)
+{
+    L->atasks.clear();
+    L->alaunches.clear();
+    for (const Launch& la : L->launches) {
+        const DTask &t0 = L->tasks[(size_t)la.task_begin], &t1 = L->tasks[(size_t)(la.task_begin + la.n_tasks - 1)];
+        plan_launch_aligned(P, S, (size_t)t0.first, (size_t)(t1.first + t1.n_reads), mode_of_launch(la), L);
+    }
+    L->model[1] = table_model(P, S, *L, L->atasks, L->alaunches);
+}
+
 // The plan of `pairs` over a sequence set, everything but its device blocks.
 inline PlanLayout plan_layout(const PlanParams& P, const SetView& S, int64_t n_pairs, const vapor_pair* pairs)
 {
@@ -472,6 +617,8 @@ inline PlanLayout plan_layout(const PlanParams& P, const SetView& S, int64_t n_p
         plan_launch_tasks(P, S, q, e, m, &L);
         q = e;
     }
+    L.model[0] = table_model(P, S, L, L.tasks, L.launches);
+    if (P.align_tasks) plan_aligned(P, S, &L);
     return L;
 }
 

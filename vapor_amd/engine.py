@@ -279,11 +279,13 @@ class Plan:
         return self.stats[:self.n]
 
     def timings(self) -> dict:
-        ms = np.zeros(10, dtype=np.float64)
-        L.check(L.load().vapor_plan_timings(self._h, L.ptr(ms, ctypes.c_double), 10))
+        ms = np.zeros(12, dtype=np.float64)
+        L.check(L.load().vapor_plan_timings(self._h, L.ptr(ms, ctypes.c_double), 12))
         return {"join_ms": ms[0], "clean_ms": ms[1], "total_ms": ms[2], "join_launches": int(ms[3]),
                 "retried_pairs": int(ms[4]), "finish_ms": ms[5], "pairs_served_by_shared_joins": int(ms[6]), "shared_joins": int(ms[7]),
-                "clean_workgroups_per_cu": int(ms[8]), "remap_in_clean": int(ms[9])}
+                "clean_workgroups_per_cu": int(ms[8]), "remap_in_clean": int(ms[9]),
+                # (of the task table the last run took, parameter join_align)
+                "join_tasks": int(ms[10]), "table_builds": int(ms[11])}
 
     def record_counts(self) -> np.ndarray:
         """Run records per pair of the last run (the device stores runs of consecutive dots as one record)."""
