@@ -383,6 +383,36 @@ int vapor_realign_batch(vapor_ctx* ctx, vapor_seqset* set, int64_t n_pairs, cons
 int vapor_realign_trace(vapor_ctx* ctx, vapor_seqset* set, int64_t n_pairs, const vapor_pair* pairs, int32_t band,
                         int32_t cap_runs, int32_t* head, uint32_t* runs);
 
+/* ---- `--realign-polish`: the consensus of a locus's reads on its allele ------ */
+/*
+ * The pairs of locus g are first[g] .. first[g + 1] (n_loci + 1 ascending int64 from 0 to n_pairs); all of them name the same
+ * seq2, the locus's allele of len symbols, whose columns 0 .. len - 1 are col_off[g] .. col_off[g + 1] of the call's columns
+ * (n_loci + 1 ascending int64 from 0).  Every pair's trace (vapor_realign_trace's, with slots that always hold it) is walked
+ * from (0, 0), the column of allele symbol j being off2 + j: a leading 'D' run is no coverage; an '=' or 'X' step adds 1 to the
+ * column's counter A, C, G or T by the read symbol's base, O for a read symbol that is none; a later 'D' step adds 1 to Dl;
+ * every covered column but the pair's first adds 1 to bcov; an 'I' run strictly inside the pair's coverage adds 1 to ins of
+ * the column it lies before.  A column with cov = A + C + G + T + O + Dl >= 3 whose largest of A, C, G, T, Dl holds a strict
+ * majority of cov is called as that (a base equal to the allele's is KEEP); a column q >= 1 with bcov >= 3 and 2 * ins > bcov is
+ * an insertion site, the first 256 of a locus are kept, and position r < 64 of a site's text is the base most inserted there
+ * (the smallest code on a tie) while more than half of bcov insert one.
+ * stats[8g ..] = {status, pairs piled, columns with cov >= 3, substitutions, deletions, sites kept, inserted bases, sites
+ * dropped}.  calls: one byte a column, 0 .. 3 a substituted base, 4 KEEP, 5 DELETE, bit 3 set when a kept site lies before the
+ * column.  sites: 256 slots a locus of {column, bases}; ins: 64 bytes a slot, the inserted text in upper case, 0 behind it.
+ * counts (may be NULL): eight uint32 a column, A C G T O Dl bcov ins.
+ * A locus whose pairs name different seq2, whose columns are not its allele's length or one of whose pairs vapor_realign_batch
+ * refuses gets status VAPOR_E_ARG; one whose trace workspace alone exceeds "trace_budget" VAPOR_E_NOMEM: zero statistics, every
+ * column KEEP, the other loci are served.  A locus without pairs has status 0 and every column KEEP.  The call returns
+ * VAPOR_E_ARG where vapor_realign_batch does, for tables that do not ascend from 0, a `first` that does not end at n_pairs and a
+ * locus of more than VAPOR_MAX_SEQ_LEN columns; n_loci == 0 is VAPOR_OK.  Consecutive whole loci run in groups whose device
+ * buffer - trace rows, run slots, counters and site tables - fits "trace_budget"; per group one clear and six kernels
+ * (realign_trace_kernel, traceback_kernel, pileup_kernel, consensus_kernel, pileup_ins_kernel, insert_kernel) back to back, then
+ * the copies back; one synchronisation a call.  Neither the trace rows nor the runs cross the link.  A library without a device
+ * exports the name and refuses every call with VAPOR_E_ARG; there is no host route.
+ */
+int vapor_realign_polish(vapor_ctx* ctx, vapor_seqset* set, int64_t n_pairs, const vapor_pair* pairs, int32_t band, int64_t n_loci,
+                         const int64_t* first, const int64_t* col_off, int32_t* stats, uint8_t* calls, int32_t* sites, uint8_t* ins,
+                         uint32_t* counts);
+
 /*
  * Host helper of the read extraction (cigar2alignstart_by_pos, SF:309-337; no device involved): walks the CIGAR of
  * an alignment starting at align_start until the reference cursor passes start-1; out[0] = offset into the read,

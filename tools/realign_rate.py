@@ -13,7 +13,14 @@ the plain run and the `--realign` run of the parent checkout (which has `--reali
 `--realign --realign-out` run, alternating, each in a warm process of its own: the two trees' tables must be equal leg for leg,
 the `--realign-out` run's table the `--realign` run's; its rate is printed relative to `--realign` alone, with the seconds the
 writer's close takes.  --kernel-only: the `--realign-out` run once, in this process, for a kernel trace of its own; --kernels DIR
-prints the two trace kernels beside realign_kernel when the trace holds them."""
+prints the two trace kernels beside realign_kernel when the trace holds them.
+`--realign-polish` likewise:
+  python tools/realign_rate.py --polish [n_loci] [--repeats R] [--parent DIR] [--bed-repeat K] [--layers N] [--timeout S]
+                               [--kernel-only [--kernel-leg plain|ra|pol]]
+the same legs with this tree's `--realign --realign-polish` run in place of the `--realign-out` run; its table must be the
+`--realign` run's in the leading columns.  --kernel-only runs one leg once (`pol` unless --kernel-leg names another), and
+--kernels DIR also prints the four polish kernels and a digest of (kernel, launches) over the whole trace, by which two trees'
+`--realign` runs are seen to launch the same kernels."""
 import contextlib
 import csv
 import glob
@@ -48,7 +55,9 @@ def kernels(d):
     t = sum(float(r["TotalDurationNs"]) for r in mine)
     n = sum(int(r["Calls"]) for r in mine)
     print("realign_kernel: %d launches, %.1f us a launch, %.1f %% of the run's kernel time" % (n, t / n / 1e3, 100.0 * t / total))
-    for name in ("realign_trace_kernel", "traceback_kernel"):
+    digest = hashlib.sha256("\n".join(sorted("%s %d" % (r["Name"], int(r["Calls"])) for r in rows)).encode()).hexdigest()[:16]
+    print("launches: %d in all, digest of (kernel, launches) %s" % (sum(int(r["Calls"]) for r in rows), digest))
+    for name in ("realign_trace_kernel", "traceback_kernel", "pileup_kernel", "consensus_kernel", "pileup_ins_kernel", "insert_kernel"):
         mine = [r for r in rows if name in r["Name"]]
         if mine:
             t = sum(float(r["TotalDurationNs"]) for r in mine)
@@ -56,7 +65,7 @@ def kernels(d):
             print("%s: %d launches, %.1f us a launch, %.1f %% of the run's kernel time" % (name, n, t / n / 1e3, 100.0 * t / total))
 
 
-LEGS = {"plain": [], "ra": ["--realign"], "out": ["--realign", "--realign-out"]}
+LEGS = {"plain": [], "ra": ["--realign"], "out": ["--realign", "--realign-out"], "pol": ["--realign", "--realign-polish"]}
 
 
 def trace_child(root, leg, fa, bam, bed, runs=4):
@@ -88,6 +97,9 @@ def trace_child(root, leg, fa, bam, bed, runs=4):
         assert rc in (0, None), rc
     got = {"loci": sum(1 for _ in open(bed)), "best_s": min(times[1:] or times), "runs_s": times[1:] or times,
            "table": hashlib.sha256(open(out, "rb").read()).hexdigest()[:16]}
+    if leg == "pol":                       # (the table without its last six columns: --realign's, byte for byte)
+        lead = "".join("\t".join(ln.rstrip("\n").split("\t")[:-6]) + "\n" for ln in open(out))
+        got["lead"] = hashlib.sha256(lead.encode()).hexdigest()[:16]
     if leg == "out":
         sam = os.path.join(tmp, "traces.sam")
         got.update(close_s=min(close_s[1:] or close_s), sam_mb=os.path.getsize(sam) / 1e6,
@@ -95,7 +107,7 @@ def trace_child(root, leg, fa, bam, bed, runs=4):
     print(json.dumps(got), flush=True)
 
 
-def trace_main(argv):
+def trace_main(argv, last="out"):
     def opt(name, default=None):
         if name in argv:
             k = argv.index(name)
@@ -105,7 +117,7 @@ def trace_main(argv):
         return default
     repeats, bed_repeat, layers = int(opt("--repeats", "4")), int(opt("--bed-repeat", "1")), int(opt("--layers", "4"))
     limit, parent = float(opt("--timeout", "240")), opt("--parent")
-    kernel_only = "--kernel-only" in argv
+    kernel_only, kernel_leg = "--kernel-only" in argv, opt("--kernel-leg", last)
     pos = [a for a in argv if not a.startswith("--")]
     n = int(pos[0]) if pos else 120
     here = evidence_rate.HERE
@@ -119,7 +131,7 @@ def trace_main(argv):
     print("source %s; files of %d %s, the BED file %d times over: %.1f MB BAM" % (_lib.load().vapor_source_id().decode(), n, what, bed_repeat,
                                                                                  os.path.getsize(bam) / 1e6), flush=True)
     if kernel_only:
-        trace_child(here, "out", fa, bam, bed, runs=1)
+        trace_child(here, kernel_leg, fa, bam, bed, runs=1)
         return
 
     def run(root, leg):
@@ -130,7 +142,7 @@ def trace_main(argv):
         if r.returncode != 0:
             raise SystemExit("child %s %s failed:\n%s" % (root, leg, r.stderr[-3000:]))
         return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
-    order = ([("parent", parent, "plain"), ("parent", parent, "ra")] if parent else []) + [("this", here, leg) for leg in ("plain", "ra", "out")]
+    order = ([("parent", parent, "plain"), ("parent", parent, "ra")] if parent else []) + [("this", here, leg) for leg in ("plain", "ra", last)]
     res = {}
     for rep in range(repeats):
         for who, root, leg in order:
@@ -145,10 +157,14 @@ def trace_main(argv):
     for (who, leg), runs in res.items():
         r = rates(runs)
         print("%-6s %-5s loci/s over %d processes: min %.0f  median %.0f  max %.0f" % (who, leg, len(runs), r[0], med(runs), r[-1]))
-    ra, out = res[("this", "ra")], res[("this", "out")]
-    print("--realign-out / --realign: rate %.3f (medians); tables equal: %s; the writer's close is %.1f %% of the run"
-          % (med(out) / med(ra), {g["table"] for g in out} == {g["table"] for g in ra},
-             100.0 * min(g["close_s"] for g in out) / min(g["best_s"] for g in out)))
+    ra, out = res[("this", "ra")], res[("this", last)]
+    if last == "out":
+        print("--realign-out / --realign: rate %.3f (medians); tables equal: %s; the writer's close is %.1f %% of the run"
+              % (med(out) / med(ra), {g["table"] for g in out} == {g["table"] for g in ra},
+                 100.0 * min(g["close_s"] for g in out) / min(g["best_s"] for g in out)))
+    else:
+        print("--realign-polish / --realign: rate %.3f (medians); the leading columns equal --realign's table: %s"
+              % (med(out) / med(ra), {g["lead"] for g in out} == {g["table"] for g in ra}))
     if parent:
         for leg in ("plain", "ra"):
             pa, mine = res[("parent", leg)], res[("this", leg)]
@@ -156,7 +172,7 @@ def trace_main(argv):
             print("this / parent, %-5s: %.3f (medians); tables equal: %s; %d of this tree's %d runs below the parent's minimum (%.0f)"
                   % (leg, med(mine) / med(pa), {g["table"] for g in mine} == {g["table"] for g in pa},
                      sum(1 for v in rates(mine) if v < rp[0]), len(mine), rp[0]))
-        print("--realign-out against the parent's --realign: rate %.3f (medians)" % (med(out) / med(res[("parent", "ra")])))
+        print("%s against the parent's --realign: rate %.3f (medians)" % (" ".join(LEGS[last][1:]), med(out) / med(res[("parent", "ra")])))
 
 
 if __name__ == "__main__":
@@ -166,6 +182,8 @@ if __name__ == "__main__":
         trace_child(*sys.argv[2:7])
     elif len(sys.argv) > 1 and sys.argv[1] == "--trace":
         trace_main(sys.argv[2:])
+    elif len(sys.argv) > 1 and sys.argv[1] == "--polish":
+        trace_main(sys.argv[2:], "pol")
     else:
         sys.argv.insert(1, "ra")
         evidence_rate.main()

@@ -23,7 +23,9 @@ _HEADERS = [("vapor_kernels.h", True), ("vapor_wide.h", True), ("vapor_anyk.h", 
             ("vapor_readrec.h", True), ("vapor_readplan.h", False), ("vapor_sa.h", False),
             ("vapor_realign.h", True), ("vapor_realign_plan.h", True),
             # (`--realign-out`, DESIGN.md 4.24: the trace kernels, and their host arithmetic, which they read as well)
-            ("vapor_realign_trace.h", True), ("vapor_trace_plan.h", True)]
+            ("vapor_realign_trace.h", True), ("vapor_trace_plan.h", True),
+            # (`--realign-polish`, DESIGN.md 4.25: the pileup and consensus kernels and the plan they read)
+            ("vapor_polish.h", True), ("vapor_polish_plan.h", True)]
 DEPS = SOURCES + [os.path.join(CSRC, h) for h, _dev in _HEADERS] + [os.path.join(ROOT, "include", "vapor_hip.h")]
 KERNEL_FILES = [os.path.join(CSRC, h) for h, dev in _HEADERS if dev] + [SOURCES[0], os.path.abspath(__file__)]
 

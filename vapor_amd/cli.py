@@ -429,7 +429,9 @@ def _simple_job(name, info, key, fig, row_prefix, label, plt_li, ctx, mode, with
     elif kind == 'realign':
         # (every read meets both alleles once more, in a band: about the cost of the locus again; the array route has no second pass)
         call = (drivers.vapor_realign, _SIMPLE[name], n_cff, plt_li, bam_in, ref, info, fig, False)
-        if mode.sink is not None:            # (`--realign-out`: the same wrapper, its Realign request named and asking for traces)
+        if mode.polish:                      # (`--realign-polish`: the request asks for the consensus too, with a sink for the traces as well)
+            call = (drivers.vapor_realign_polish, key, mode.sink is not None) + call[1:]
+        elif mode.sink is not None:          # (`--realign-out`: the same wrapper, its Realign request named and asking for traces)
             call = (drivers.vapor_realign_out, key) + call[1:]
         cost, spec = 2 * job_cost(name, span), None
     else:
@@ -443,6 +445,8 @@ def _ins_job(call, cost, spec, mode, key=None):
     call, about twice its cost, on the drivers' route (no description), as _simple_job has it for the other three types
     (under `--realign-out` drivers.vapor_realign_out, named `key`)."""
     if mode is not None and mode.name == 'realign':
+        if mode.polish:
+            return (drivers.vapor_realign_polish, key, mode.sink is not None) + call, 2 * cost, None
         if mode.sink is not None:
             return (drivers.vapor_realign_out, key) + call, 2 * cost, None
         return (drivers.vapor_realign,) + call, 2 * cost, None
@@ -963,6 +967,9 @@ def build_parser() -> argparse.ArgumentParser:
     # (`--realign-out PREFIX`, DESIGN.md 4.24: every read's alignment to the allele it fits, PREFIX.sam over PREFIX.fa; no mode
     # of its own - it needs --realign - and suppressed for the same reason)
     p.add_argument('--realign-out', metavar='PREFIX', default=None, help=argparse.SUPPRESS)
+    # (`--realign-polish`, DESIGN.md 4.25: the ALT voters piled on the alt allele, six columns behind --realign's and, with
+    # --realign-out, PREFIX.pol.fa; no mode of its own - it needs --realign - and suppressed for the same reason)
+    p.add_argument('--realign-polish', action='store_true', help=argparse.SUPPRESS)
     p.add_argument('--min-mapq', metavar='Q', type=_int_in('--min-mapq', 0, 255), default=0,
                    help='every sub-command: skip records with MAPQ below Q (0..255, default 0), as `samtools view -q Q` does; a '
                         'filtered record is treated as if it were not in the file')
@@ -1060,6 +1067,8 @@ def _main(argv, held) -> int:
         parser.error('--phase-sample names a sample of --phase-vcf: give that option too')
     if args.realign_out is not None and not args.realign:
         parser.error('--realign-out needs --realign')
+    if args.realign_polish and not args.realign:
+        parser.error('--realign-polish needs --realign')
     if args.phase_vcf is not None:
         args.phased = True               # (the groups, the scoring and the columns are --phased's: only the tags' source differs)
     # a run has one mode: every later option of MODE_OPTIONS refuses the sub-commands it does not apply to, then each earlier one
@@ -1122,7 +1131,10 @@ def _main(argv, held) -> int:
         figure_fn = figures.make_event_figure_1
         figures.warm()                  # (the drawing processes start while the input is parsed and the first batch scored)
     vdist.init_from_env()
-    if mode is modes.REALIGN and args.realign_out is not None:
+    if mode is modes.REALIGN and args.realign_polish:
+        from . import polish
+        mode = modes.realign_polish(polish.PolishWriter(args.realign_out, vdist.rank(), vdist.world()) if args.realign_out is not None else None)
+    elif mode is modes.REALIGN and args.realign_out is not None:
         from . import realign
         mode = modes.realign_out(realign.TraceWriter(args.realign_out, vdist.rank(), vdist.world()))
     out_path = SF.path_modify(args.output_path)

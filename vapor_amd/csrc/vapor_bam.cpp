@@ -1390,6 +1390,13 @@ extern "C" __attribute__((weak)) int vapor_realign_trace(vapor_ctx*, vapor_seqse
     return bfail(VAPOR_E_ARG, "vapor_realign_trace: this build has no traceback kernel");
 }
 
+// ... and `--realign-polish`'s consensus (vapor_realign_polish: the four kernels of vapor_polish.h behind those two).
+extern "C" __attribute__((weak)) int vapor_realign_polish(vapor_ctx*, vapor_seqset*, int64_t, const vapor_pair*, int32_t, int64_t, const int64_t*,
+                                                          const int64_t*, int32_t*, uint8_t*, int32_t*, uint8_t*, uint32_t*)
+{
+    return bfail(VAPOR_E_ARG, "vapor_realign_polish: this build has no pileup kernels");
+}
+
 // The reference windows of a bgzipped FASTA on the device (vapor_fasta_windows_device, vapor_fasta_last_stats) are device code in
 // vapor_hip.hip as well; the CPU twin answers them with VAPOR_E_ARG, and the caller reads the windows on the host.
 extern "C" __attribute__((weak)) int vapor_fasta_windows_device(vapor_ctx*, int, int32_t, const uint64_t*, const uint64_t*, uint8_t*, int64_t,

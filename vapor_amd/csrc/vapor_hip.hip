@@ -10,6 +10,7 @@
 #include "vapor_anyk.h"
 #include "vapor_realign.h"
 #include "vapor_realign_trace.h"
+#include "vapor_polish.h"
 #include "vapor_bamdev.h"
 #include "vapor_bgzf.h"
 #include "vapor_fasta.h"
@@ -2648,6 +2649,149 @@ extern "C" int vapor_realign_trace(vapor_ctx* ctx, vapor_seqset* set, int64_t n_
     }
     HIPCHK(hipMemcpyAsync(head, d_head.p, sizeof(int32_t) * tr::HEAD * np, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(runs, d_runs.p, sizeof(uint32_t) * np * (size_t)cap_runs, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    sc.settled();
+    return VAPOR_OK;
+}
+
+// `--realign-polish` (vapor_polish.h): the consensus of every locus's pairs on its allele.  The checks, the groups
+// and the layout of a group's buffer are vapor_polish_plan.h's; here: one upload (pair records, workspace offsets, the pairs' loci,
+// the locus records), per group one clear of its tables, the forward pass, the traceback into run slots that stay on the device,
+// the four kernels and the copies back; one synchronisation at the end.
+extern "C" int vapor_realign_polish(vapor_ctx* ctx, vapor_seqset* set, int64_t n_pairs, const vapor_pair* pairs, int32_t band, int64_t n_loci,
+                                    const int64_t* first, const int64_t* col_off, int32_t* stats, uint8_t* calls, int32_t* sites, uint8_t* ins,
+                                    uint32_t* counts)
+{
+    namespace ra = vapor_realign;
+    namespace tr = vapor_trace;
+    namespace pp = vapor_polish;
+    if (!ctx || !set || n_pairs < 0 || n_pairs > ra::MAX_PAIRS || (n_pairs && !pairs))
+        return fail(VAPOR_E_ARG, "vapor_realign_polish: null argument or a pair count outside 0 .. 2^26");
+    if (!ra::band_ok(band)) return fail(VAPOR_E_ARG, "vapor_realign_polish: band outside 1 .. VAPOR_MAX_BAND");
+    if (n_loci < 0 || n_loci > ra::MAX_PAIRS) return fail(VAPOR_E_ARG, "vapor_realign_polish: a locus count outside 0 .. 2^26");
+    if (n_loci == 0 && n_pairs == 0) return VAPOR_OK;
+    if (!pp::tables_ok(n_pairs, n_loci, first, col_off))
+        return fail(VAPOR_E_ARG, "vapor_realign_polish: first / col_off must ascend from 0, first must end at n_pairs, a locus has at most "
+                                 "VAPOR_MAX_SEQ_LEN columns");
+    if (n_loci == 0) return VAPOR_OK;
+    if (!stats || !sites || !ins || (col_off[n_loci] && !calls)) return fail(VAPOR_E_ARG, "vapor_realign_polish: null output");
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const int S = ra::lane_width(band);
+    const size_t np = (size_t)n_pairs, nl = (size_t)n_loci;
+    std::vector<ra::RPair> recs(np);
+    for (int64_t t = 0; t < n_pairs; ++t)
+        recs[(size_t)t] = ra::pair_record(pairs[t], set->n, [&](int32_t s) { return set->h[(size_t)s].len; },
+                                          [&](int32_t s) { return set->h[(size_t)s].chunk0; });
+    // the loci: status, trace words, run cap
+    std::vector<pp::PLocus> loci(nl);
+    std::vector<int64_t> twords(nl), cap(nl);
+    std::vector<int32_t> pair_locus(np);
+    for (int64_t g = 0; g < n_loci; ++g) {
+        const int64_t a = first[g], b = first[g + 1], span = col_off[g + 1] - col_off[g];
+        const int status = pp::locus_status(recs.data(), a, b, span, band, S, ctx->trace_budget, [&](int64_t t) { return pairs[t].seq2; },
+                                            [&](int64_t t) { return (int64_t)set->h[(size_t)pairs[t].seq2].len; }, twords[(size_t)g]);
+        pp::PLocus& lc = loci[(size_t)g];
+        lc = pp::PLocus{};
+        lc.len = (int32_t)span;
+        lc.n_pairs = (int32_t)(status ? 0 : b - a);
+        lc.status = status;
+        lc.word2 = (!status && b > a) ? recs[(size_t)a].word2 : 0;
+        cap[(size_t)g] = 1;
+        for (int64_t t = a; t < b; ++t) {
+            if (status) recs[(size_t)t].status = recs[(size_t)t].status ? recs[(size_t)t].status : status;     // (no pair of a refused locus runs)
+            cap[(size_t)g] = std::max(cap[(size_t)g], pp::run_cap(recs[(size_t)t]));
+        }
+    }
+    std::vector<pp::Group> groups;
+    const int64_t most = pp::plan_groups(n_loci, first, col_off, twords.data(), cap.data(), ctx->trace_budget, groups);
+    // the pairs' workspace offsets, their loci and the loci's columns, relative to their group (the two trace kernels are launched
+    // with the group's pointers and t0 = 0)
+    std::vector<uint64_t> off(np, 0);
+    for (const pp::Group& gr : groups) {
+        uint64_t used = 0;
+        for (int64_t t = gr.pair0; t < gr.pair1; ++t) {
+            const ra::RPair& r = recs[(size_t)t];
+            off[(size_t)t] = used;
+            if (!r.status) used += (uint64_t)tr::pair_words(ra::rows_walked(r.n, r.m, band), S);
+        }
+        for (int64_t g = gr.locus0; g < gr.locus1; ++g) {
+            loci[(size_t)g].col0 = col_off[g] - col_off[gr.locus0];
+            for (int64_t t = first[g]; t < first[g + 1]; ++t) pair_locus[(size_t)t] = (int32_t)(g - gr.locus0);
+        }
+    }
+    const size_t b_rec = sizeof(ra::RPair) * np, b_off = sizeof(uint64_t) * np, b_loc = sizeof(pp::PLocus) * nl, b_pl = sizeof(int32_t) * np;
+    std::vector<uint8_t> up(b_rec + b_off + b_loc + b_pl);              // (the upload reads it: declared before the owners)
+    memcpy(up.data(), recs.data(), b_rec);
+    memcpy(up.data() + b_rec, off.data(), b_off);
+    memcpy(up.data() + b_rec + b_off, loci.data(), b_loc);
+    memcpy(up.data() + b_rec + b_off + b_loc, pair_locus.data(), b_pl);
+    CallScope sc(ctx, st);
+    Block<uint8_t> d_up(sc);
+    Block<uint32_t> d_buf(sc);
+    Block<int32_t> d_head(sc);
+    HIPCHK(d_up.ensure(up.size()));
+    HIPCHK(d_buf.ensure(sizeof(uint32_t) * (size_t)std::max<int64_t>(most, 64)));
+    HIPCHK(d_head.ensure(sizeof(int32_t) * tr::HEAD * std::max<size_t>(np, 1)));
+    HIPCHK(hipMemcpyAsync(d_up.p, up.data(), up.size(), hipMemcpyHostToDevice, st));
+    const ra::RPair* d_pairs = reinterpret_cast<const ra::RPair*>(d_up.p);
+    const uint64_t* d_off = reinterpret_cast<const uint64_t*>(d_up.p + b_rec);
+    const pp::PLocus* d_loci = reinterpret_cast<const pp::PLocus*>(d_up.p + b_rec + b_off);
+    const int32_t* d_pl = reinterpret_cast<const int32_t*>(d_up.p + b_rec + b_off + b_loc);
+    for (const pp::Group& gr : groups) {
+        const int64_t count = gr.pair1 - gr.pair0, gl = gr.locus1 - gr.locus0;
+        uint32_t* const b = d_buf.p;
+        uint32_t* const g_counts = b + gr.counts_off;
+        uint32_t* const g_slot = b + gr.slot_off;
+        uint8_t* const g_calls = reinterpret_cast<uint8_t*>(b + gr.calls_off);
+        int32_t* const g_stats = reinterpret_cast<int32_t*>(b + gr.stats_off);
+        int32_t* const g_sites = reinterpret_cast<int32_t*>(b + gr.sites_off);
+        uint8_t* const g_ins = reinterpret_cast<uint8_t*>(b + gr.ins_off);
+        uint32_t* const g_insb = b + gr.insb_off;
+        HIPCHK(hipMemsetAsync(b + gr.zero_off, 0, sizeof(uint32_t) * (size_t)(gr.words - gr.zero_off), st));
+        const ra::RPair* gp = d_pairs + gr.pair0;
+        const pp::PLocus* gloc = d_loci + gr.locus0;
+        const int32_t* gpl = d_pl + gr.pair0;
+        int32_t* ghead = d_head.p + tr::HEAD * gr.pair0;
+        const int32_t cap_runs = (int32_t)gr.cap_runs;
+        if (count > 0) {
+            const uint64_t* goff = d_off + gr.pair0;
+            uint32_t* g_runs = b + gr.runs_off;
+            switch (S) {
+            case 1: realign_trace_launch<1>(st, set->d_x4, gp, goff, 0, count, band, b, cap_runs, ghead, g_runs); break;
+            case 2: realign_trace_launch<2>(st, set->d_x4, gp, goff, 0, count, band, b, cap_runs, ghead, g_runs); break;
+            case 3: realign_trace_launch<3>(st, set->d_x4, gp, goff, 0, count, band, b, cap_runs, ghead, g_runs); break;
+            case 5: realign_trace_launch<5>(st, set->d_x4, gp, goff, 0, count, band, b, cap_runs, ghead, g_runs); break;
+            case 9: realign_trace_launch<9>(st, set->d_x4, gp, goff, 0, count, band, b, cap_runs, ghead, g_runs); break;
+            default: realign_trace_launch<ra::MAX_SLOTS>(st, set->d_x4, gp, goff, 0, count, band, b, cap_runs, ghead, g_runs); break;
+            }
+            HIPCHK(hipGetLastError());
+            const dim3 grid((unsigned)ra::grid_of(count)), block(64 * ra::WAVES);
+            hipLaunchKernelGGL(pileup_kernel, grid, block, 0, st, (const uint32_t*)set->d_x4, gp, gpl, gloc, (long long)count, (const int32_t*)ghead,
+                               (const uint32_t*)g_runs, (int)cap_runs, g_counts);
+            HIPCHK(hipGetLastError());
+        }
+        hipLaunchKernelGGL(consensus_kernel, dim3((unsigned)gl), dim3(CONSENSUS_THREADS), 0, st, (const uint32_t*)set->d_x4, gloc,
+                           (const uint32_t*)g_counts, g_slot, g_calls, g_stats, g_sites);
+        HIPCHK(hipGetLastError());
+        if (count > 0) {
+            const dim3 grid((unsigned)ra::grid_of(count)), block(64 * ra::WAVES);
+            hipLaunchKernelGGL(pileup_ins_kernel, grid, block, 0, st, (const uint32_t*)set->d_x4, gp, gpl, gloc, (long long)count,
+                               (const int32_t*)ghead, (const uint32_t*)(b + gr.runs_off), (int)cap_runs, (const uint32_t*)g_slot, g_insb);
+            HIPCHK(hipGetLastError());
+            const long long n_slots = (long long)gl * pp::MAX_SITES;
+            hipLaunchKernelGGL(insert_kernel, dim3((unsigned)ra::grid_of(n_slots)), block, 0, st, gloc, n_slots, (const uint32_t*)g_counts,
+                               (const uint32_t*)g_insb, g_stats, g_sites, g_ins);
+            HIPCHK(hipGetLastError());
+        }
+        const size_t c0 = (size_t)col_off[gr.locus0], l0 = (size_t)gr.locus0;
+        if (gr.cols) HIPCHK(hipMemcpyAsync(calls + c0, g_calls, (size_t)gr.cols, hipMemcpyDeviceToHost, st));
+        if (gr.cols && counts)
+            HIPCHK(hipMemcpyAsync(counts + pp::COUNTERS * c0, g_counts, sizeof(uint32_t) * pp::COUNTERS * (size_t)gr.cols, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(stats + pp::STATS * l0, g_stats, sizeof(int32_t) * pp::STATS * (size_t)gl, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(sites + pp::SITE_WORDS * l0, g_sites, sizeof(int32_t) * pp::SITE_WORDS * (size_t)gl, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(ins + 4 * pp::INS_WORDS * l0, g_ins, 4 * (size_t)pp::INS_WORDS * (size_t)gl, hipMemcpyDeviceToHost, st));
+    }
     HIPCHK(hipStreamSynchronize(st));
     sc.settled();
     return VAPOR_OK;

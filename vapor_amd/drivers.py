@@ -600,11 +600,13 @@ class Realign:
     """`--realign`: the reads of a Score request against its two alleles.  Result: a realign.Payload - per read
     its edit distance to ref_seq[miss_bp:] minus that to alt_seq[miss_bp:] - or None when a pair came back with a status.
     `trace` (`--realign-out`; off unless asked): the payload also carries `.traces`, every read's alignment to the
-    allele it fits; `name`: the locus as the files spell it."""
-    __slots__ = ("ref_seq", "alt_seq", "reads", "name", "trace")
+    allele it fits; `name`: the locus as the files spell it.  `polish` (`--realign-polish`; off unless asked): the
+    payload also carries `.polish`, the consensus of the ALT voters on the alt allele."""
+    __slots__ = ("ref_seq", "alt_seq", "reads", "name", "trace", "polish")
 
-    def __init__(self, ref_seq, alt_seq, reads, name=None, trace=False):
+    def __init__(self, ref_seq, alt_seq, reads, name=None, trace=False, polish=False):
         self.ref_seq, self.alt_seq, self.reads, self.name, self.trace = ref_seq, alt_seq, reads, name, bool(trace)
+        self.polish = bool(polish)
 
 
 class Realigned(list):
@@ -625,7 +627,13 @@ def vapor_realign_out(name, driver, *args):
     return (yield from _realign(name, True, driver, args))
 
 
-def _realign(name, trace, driver, args):
+def vapor_realign_polish(name, trace, driver, *args):
+    """`--realign --realign-polish`: vapor_realign whose Realign request asks for the polish; with `trace` (`--realign-out` as
+    well) it carries the locus's name and asks for the traces too."""
+    return (yield from _realign(name if trace else None, bool(trace), driver, args, True))
+
+
+def _realign(name, trace, driver, args, polish=False):
     gen = driver(*args)
     last = None
     try:
@@ -643,8 +651,8 @@ def _realign(name, trace, driver, args):
         scores = fin.value
     out = Realigned(scores if scores is not None else [])
     if last is not None:
-        out.realign = yield (Realign(last.ref_seq, last.alt_seq, last.reads, name, True) if trace else
-                             Realign(last.ref_seq, last.alt_seq, last.reads))
+        out.realign = yield (Realign(last.ref_seq, last.alt_seq, last.reads, name, True, polish) if trace else
+                             Realign(last.ref_seq, last.alt_seq, last.reads, polish=polish))
     return out
 
 

@@ -748,6 +748,38 @@ class Engine:
                    L.ptr(runs, ctypes.c_uint32)))
         return head[:n], runs[:n]
 
+    # ---- `--realign-polish`: the consensus of a locus's pairs on its allele ----
+    def realign_polish_available(self) -> bool:
+        """Whether the loaded library has vapor_realign_polish (the CPU twin of the C ABI has not)."""
+        return self._available("vapor_realign_polish")
+
+    def realign_polish(self, seqset: SeqSet, pairs: np.ndarray, band: int, first, col_off, want_counts: bool = False):
+        """(stats, calls, sites, ins, counts) of every locus (vapor_realign_polish): the pairs of locus g are first[g] ..
+        first[g + 1], all against the locus's allele, whose columns are col_off[g] .. col_off[g + 1].  stats (n_loci, 8) int32,
+        a row {status, pairs piled, PCOV, PSUB, PDEL, sites kept, PINS, sites dropped}; calls one uint8 a column; sites
+        (n_loci, 256, 2) int32, a kept site's (column, bases); ins (n_loci, 256, 64) uint8, its text; counts (columns, 8) uint32
+        with want_counts, else None (polish.statement says what they hold).  A locus the entry refuses has status E_ARG or
+        E_NOMEM, zero statistics and every column KEEP.
+        NotImplementedError where the library has no such entry: there is no other route."""
+        from . import polish
+        fn = self._wide_entry("vapor_realign_polish", "pileup kernels (--realign-polish)")
+        pairs = np.ascontiguousarray(pairs, dtype=L.PAIR_DTYPE)
+        fl = np.ascontiguousarray(first, dtype=np.int64)
+        co = np.ascontiguousarray(col_off, dtype=np.int64)
+        if len(fl) != len(co) or len(fl) < 1:
+            raise ValueError("realign_polish: first and col_off hold one entry a locus and one more")
+        n, ng = len(pairs), len(fl) - 1
+        cols = max(int(co[-1]), 0)
+        stats = np.zeros((max(ng, 1), 8), dtype=np.int32)
+        calls = np.zeros(max(cols, 1), dtype=np.uint8)
+        sites = np.zeros((max(ng, 1), polish.MAX_SITES, 2), dtype=np.int32)
+        ins = np.zeros((max(ng, 1), polish.MAX_SITES, polish.RMAX), dtype=np.uint8)
+        counts = np.zeros((max(cols, 1), 8), dtype=np.uint32) if want_counts else None
+        L.check(fn(self._ctx, seqset._h, n, pairs.ctypes.data if n else None, int(band), ng, L.ptr(fl, ctypes.c_int64), L.ptr(co, ctypes.c_int64),
+                   L.ptr(stats, ctypes.c_int32), L.ptr(calls, ctypes.c_uint8), L.ptr(sites, ctypes.c_int32), L.ptr(ins, ctypes.c_uint8),
+                   L.ptr(counts, ctypes.c_uint32) if want_counts else None))
+        return stats[:ng], calls[:cols], sites[:ng], ins[:ng], counts[:cols] if want_counts else None
+
     def clean_hits_wide(self, lists: Sequence[np.ndarray], flags: Optional[Sequence[int]] = None):
         """clean_hits for lists with coordinates up to MAX_WIDE_SEQ_LEN (vapor_clean_hits_wide)."""
         return self._clean_lists(self._wide_entry("vapor_clean_hits_wide"), lists, flags)

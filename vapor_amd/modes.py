@@ -5,7 +5,7 @@ its own module - refine.py, phase.py, bothends.py, depth.py, signature.py, links
 depth.py to support.py also say how their regions are read (their reader surface), and the parser states the rule once (cli.MODE_OPTIONS)."""
 from __future__ import annotations
 
-from . import bothends, depth, links, phase, realign, signature, support
+from . import bothends, depth, links, phase, polish, realign, signature, support
 from . import refine as _refine
 
 
@@ -25,6 +25,7 @@ class Mode:
     chunk_gens = None
     chunk_payloads = None
     sink = None
+    polish = False                             # (`--realign-polish`: the Realign requests ask for the consensus too)
 
     def __init__(self, name, src, attr, keys=None, skip_dot=True, phased=False, margin_step=None, ci_of=None):
         self.name, self.attr, self.skip_dot, self.phased = name, attr, skip_dot, phased
@@ -52,4 +53,13 @@ def realign_out(sink) -> Mode:
     """`--realign --realign-out PREFIX`: REALIGN's columns, with the sink the loci's traces go to."""
     m = Mode("realign", realign, "realign")
     m.sink = sink
+    return m
+
+
+def realign_polish(sink=None) -> Mode:
+    """`--realign --realign-polish`: REALIGN's columns followed by polish's six; with `--realign-out` the sink
+    the loci's traces and polished alleles go to (polish.PolishWriter)."""
+    m = Mode("realign", polish, "realign")
+    m.sink = sink
+    m.polish = True
     return m

@@ -554,7 +554,10 @@ def realign_requests(engine, reqs: Sequence[object]) -> List[object]:
             rows += [(q, ri, int(x[1])), (q, ai, int(x[1]))]
     first.append(len(rows))
     if not rows:
-        return [realign.Payload() for _ in reqs]
+        out = [realign.Payload() for _ in reqs]
+        if any(r.polish for r in reqs):
+            _realign_polish(engine, None, reqs, out, None, first)
+        return out
     n_lit = len(sb.seqs)
     pairs = np.zeros(len(rows), dtype=L.PAIR_DTYPE)
     tab = np.asarray(rows, dtype=np.int64)
@@ -567,6 +570,8 @@ def realign_requests(engine, reqs: Sequence[object]) -> List[object]:
         out = [realign.payload(d[a:b:2], d[a + 1:b:2], st[a:b:2], st[a + 1:b:2]) for a, b in zip(first[:-1], first[1:])]
         if any(r.trace for r in reqs):
             _realign_traces(engine, ss, reqs, out, pairs, d, first)
+        if any(r.polish for r in reqs):
+            _realign_polish(engine, ss, reqs, out, pairs, first)
     finally:
         ss.close()
     return out
@@ -610,6 +615,35 @@ def _realign_traces(engine, ss, reqs, out, pairs, d, first) -> None:
         x = reqs[t].reads[k]
         a = first[t]
         out[t].traces.reads.append((x[0], int(x[1]), int(d[a + 2 * k]), int(d[a + 2 * k + 1]), i_end, j_end, rr if status == 0 else []))
+
+
+def _realign_polish(engine, ss, reqs, out, pairs, first) -> None:
+    """`--realign-polish`: one engine.realign_polish call over the set of the distances' call for the requests
+    that ask and have a payload - per request one locus, its pairs the alt pair of every read that votes ALT.  The statistics
+    ride on the payload (`.polish`); the polished allele is spelt only where a sink takes it (the request asks for traces and
+    has them).  A request without reads has nothing in the set: its pile is empty, which needs no call."""
+    from . import polish, realign
+    pick, pfirst, col_off, who = [], [0], [0], []
+    for t, (r, a) in enumerate(zip(reqs, first[:-1])):
+        if not r.polish or out[t] is None:
+            continue
+        if not r.reads:
+            out[t].polish = polish.Polish([0] * 8, str(r.alt_seq) if getattr(out[t], "traces", None) is not None else None)
+            continue
+        pick += [a + 2 * k + 1 for k, diff in enumerate(out[t]) if diff >= realign.MARGIN]
+        pfirst.append(len(pick))
+        col_off.append(col_off[-1] + len(r.alt_seq))
+        who.append(t)
+    if not who:
+        return
+    stats, calls, sites, ins, _counts = engine.realign_polish(ss, pairs[np.asarray(pick, dtype=np.int64)], realign.BAND, pfirst, col_off)
+    for g, t in enumerate(who):
+        text = None
+        if reqs[t].trace:             # (a locus the entry refuses keeps its allele: the columns say '.')
+            text = str(reqs[t].alt_seq)
+            if int(stats[g][0]) == 0:
+                text = polish.apply(text, calls[col_off[g]:col_off[g + 1]], sites[g], ins[g])
+        out[t].polish = polish.Polish(stats[g], text)
 
 
 # ------------------------------------------------------------------------------------------
