@@ -413,6 +413,28 @@ int vapor_realign_polish(vapor_ctx* ctx, vapor_seqset* set, int64_t n_pairs, con
                          const int64_t* first, const int64_t* col_off, int32_t* stats, uint8_t* calls, int32_t* sites, uint8_t* ins,
                          uint32_t* counts);
 
+/* ---- `--realign-junction`: the one jump between two sequences --------------- */
+/*
+ * Per pair: s = seq1 (ns symbols) and l = seq2 (nl symbols), ns <= nl, off2 == 0; symbols, matching, the band and D are
+ * vapor_realign_batch's.  The row table T(s, l) has rows i = 0 .. ns: f(i) the minimum of D[i][j] over the existing cells of
+ * row i (|i - j| <= band, 0 <= j <= nl; D of s[0:i] against l[0:j], anchored at (0, 0)), jf(i) the smallest j that attains it.
+ * With F = T(s, l) and R = T(reversed s, reversed l), split row i has j1 = jf_F(i), j2 = nl - jf_R(ns - i) and
+ * cost = f_F(i) + f_R(ns - i); it is valid iff j2 >= j1 (row 0 always is).  The junction is the valid row with the smallest
+ * (cost, i): s is l with l[j1 : j2) skipped at row i, at `cost` further edits.
+ * out[8 t ..] = {status, cost, i, j1, j2, f_F(i), f_R(ns - i), 0}.  rows may be NULL; otherwise row_off holds n_pairs + 1
+ * ascending int64 from 0, and the ns + 1 rows of pair t are written from row row_off[t] on, four int32 a row:
+ * {f_F, jf_F, f_R, jf_R}, each pass's two indexed by that pass's own row.  The rows of a refused pair are not written.
+ * A bad index, a sequence longer than VAPOR_MAX_SEQ_LEN, off2 != 0, len(seq1) > len(seq2) or (rows given) a slot of fewer than
+ * ns + 1 rows gives the pair status VAPOR_E_ARG and a record that is zero behind it; the other pairs are served.  The call
+ * returns VAPOR_E_ARG where vapor_realign_batch does and for a row_off that does not ascend from 0, VAPOR_E_NOMEM when the pairs'
+ * tables (16 (ns + 1) bytes each) exceed "trace_budget", VAPOR_OK for n_pairs == 0.  One upload, two launches
+ * (junction_rows_kernel: a wavefront per pair and direction, the backward one reading both sequences from their last symbol;
+ * junction_pick_kernel: a wavefront per pair), the copies back, one synchronisation.  A library without a device exports the
+ * name and refuses every call with VAPOR_E_ARG; there is no host route.
+ */
+int vapor_realign_junction(vapor_ctx* ctx, vapor_seqset* set, int64_t n_pairs, const vapor_pair* pairs, int32_t band, int32_t* out,
+                           const int64_t* row_off, int32_t* rows);
+
 /*
  * Host helper of the read extraction (cigar2alignstart_by_pos, SF:309-337; no device involved): walks the CIGAR of
  * an alignment starting at align_start until the reference cursor passes start-1; out[0] = offset into the read,

@@ -20,7 +20,16 @@ prints the two trace kernels beside realign_kernel when the trace holds them.
 the same legs with this tree's `--realign --realign-polish` run in place of the `--realign-out` run; its table must be the
 `--realign` run's in the leading columns.  --kernel-only runs one leg once (`pol` unless --kernel-leg names another), and
 --kernels DIR also prints the four polish kernels and a digest of (kernel, launches) over the whole trace, by which two trees'
-`--realign` runs are seen to launch the same kernels."""
+`--realign` runs are seen to launch the same kernels.
+`--realign-junction` likewise:
+  python tools/realign_rate.py --junction [n_loci] [--repeats R] [--parent DIR] [--bed-repeat K] [--layers N] [--timeout S]
+                                 [--kernel-only [--kernel-leg plain|ra|pol|jun]]
+the plain, `--realign` and `--realign --realign-polish` runs of the parent checkout (which has all three) and of this tree, and
+this tree's `--realign --realign-polish --realign-junction` run; its table must be the `--realign-polish` run's in the leading
+columns.  --kernels DIR also prints the two junction kernels.
+  python tools/realign_rate.py --junction-call [pairs] [rows] [band]
+one Engine.realign_junction call (wall time with its copies, best of three) of `pairs` pairs of `rows` rows, the longer
+sequence carrying a jump of 300 symbols, beside DESIGN.md 4.23's arithmetic for its 2 * pairs wavefronts."""
 import contextlib
 import csv
 import glob
@@ -57,7 +66,8 @@ def kernels(d):
     print("realign_kernel: %d launches, %.1f us a launch, %.1f %% of the run's kernel time" % (n, t / n / 1e3, 100.0 * t / total))
     digest = hashlib.sha256("\n".join(sorted("%s %d" % (r["Name"], int(r["Calls"])) for r in rows)).encode()).hexdigest()[:16]
     print("launches: %d in all, digest of (kernel, launches) %s" % (sum(int(r["Calls"]) for r in rows), digest))
-    for name in ("realign_trace_kernel", "traceback_kernel", "pileup_kernel", "consensus_kernel", "pileup_ins_kernel", "insert_kernel"):
+    for name in ("realign_trace_kernel", "traceback_kernel", "pileup_kernel", "consensus_kernel", "pileup_ins_kernel", "insert_kernel", "junction_rows_kernel",
+                 "junction_pick_kernel"):
         mine = [r for r in rows if name in r["Name"]]
         if mine:
             t = sum(float(r["TotalDurationNs"]) for r in mine)
@@ -65,7 +75,8 @@ def kernels(d):
             print("%s: %d launches, %.1f us a launch, %.1f %% of the run's kernel time" % (name, n, t / n / 1e3, 100.0 * t / total))
 
 
-LEGS = {"plain": [], "ra": ["--realign"], "out": ["--realign", "--realign-out"], "pol": ["--realign", "--realign-polish"]}
+LEGS = {"plain": [], "ra": ["--realign"], "out": ["--realign", "--realign-out"], "pol": ["--realign", "--realign-polish"],
+        "jun": ["--realign", "--realign-polish", "--realign-junction"]}
 
 
 def trace_child(root, leg, fa, bam, bed, runs=4):
@@ -97,7 +108,7 @@ def trace_child(root, leg, fa, bam, bed, runs=4):
         assert rc in (0, None), rc
     got = {"loci": sum(1 for _ in open(bed)), "best_s": min(times[1:] or times), "runs_s": times[1:] or times,
            "table": hashlib.sha256(open(out, "rb").read()).hexdigest()[:16]}
-    if leg == "pol":                       # (the table without its last six columns: --realign's, byte for byte)
+    if leg in ("pol", "jun"):              # (the table without its last six columns: the run's before it, byte for byte)
         lead = "".join("\t".join(ln.rstrip("\n").split("\t")[:-6]) + "\n" for ln in open(out))
         got["lead"] = hashlib.sha256(lead.encode()).hexdigest()[:16]
     if leg == "out":
@@ -142,7 +153,8 @@ def trace_main(argv, last="out"):
         if r.returncode != 0:
             raise SystemExit("child %s %s failed:\n%s" % (root, leg, r.stderr[-3000:]))
         return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
-    order = ([("parent", parent, "plain"), ("parent", parent, "ra")] if parent else []) + [("this", here, leg) for leg in ("plain", "ra", last)]
+    shared = ("plain", "ra", "pol") if last == "jun" else ("plain", "ra")      # (the legs the parent has too)
+    order = ([("parent", parent, leg) for leg in shared] if parent else []) + [("this", here, leg) for leg in shared + (last,)]
     res = {}
     for rep in range(repeats):
         for who, root, leg in order:
@@ -162,17 +174,54 @@ def trace_main(argv, last="out"):
         print("--realign-out / --realign: rate %.3f (medians); tables equal: %s; the writer's close is %.1f %% of the run"
               % (med(out) / med(ra), {g["table"] for g in out} == {g["table"] for g in ra},
                  100.0 * min(g["close_s"] for g in out) / min(g["best_s"] for g in out)))
+    elif last == "jun":
+        pol = res[("this", "pol")]
+        print("--realign-junction / --realign-polish: rate %.3f (medians); the leading columns equal --realign-polish's table: %s"
+              % (med(out) / med(pol), {g["lead"] for g in out} == {g["table"] for g in pol}))
     else:
         print("--realign-polish / --realign: rate %.3f (medians); the leading columns equal --realign's table: %s"
               % (med(out) / med(ra), {g["lead"] for g in out} == {g["table"] for g in ra}))
     if parent:
-        for leg in ("plain", "ra"):
+        for leg in shared:
             pa, mine = res[("parent", leg)], res[("this", leg)]
             rp = rates(pa)
             print("this / parent, %-5s: %.3f (medians); tables equal: %s; %d of this tree's %d runs below the parent's minimum (%.0f)"
                   % (leg, med(mine) / med(pa), {g["table"] for g in mine} == {g["table"] for g in pa},
                      sum(1 for v in rates(mine) if v < rp[0]), len(mine), rp[0]))
         print("%s against the parent's --realign: rate %.3f (medians)" % (" ".join(LEGS[last][1:]), med(out) / med(res[("parent", "ra")])))
+
+
+def junction_call(argv):
+    """One Engine.realign_junction call of P pairs of r rows at a band, best of three, beside 2 P r 4 (5 S + 45) SIMD cycles."""
+    import numpy as np
+    sys.path.insert(0, evidence_rate.HERE)
+    from vapor_amd.engine import Engine
+    pairs, rows, band = (int(v) for v in (argv + ["4096", "10000", "256"][len(argv):])[:3])
+    rng = np.random.default_rng(1)
+    n_seq = 64                                                     # (distinct sequences; the pairs go round them)
+    seqs = []
+    for _ in range(n_seq):
+        l = "".join("ACGT"[j] for j in rng.integers(0, 4, rows + 300))
+        seqs += [l[:rows // 2] + l[rows // 2 + 300:], l]
+    S = next(w for w in (1, 2, 3, 5, 9, 17) if 64 * w >= 2 * band + 1)
+    e = Engine(0)
+    try:
+        e.set_param("trace_budget", 16 * (rows + 1) * pairs + (1 << 20))      # (the tables of the call: 655 MB at the default shape)
+        ss = e.seqset(seqs)
+        tab = e.make_pairs([(2 * (t % n_seq), 2 * (t % n_seq) + 1, 0, 0, 0) for t in range(pairs)])
+        times = []
+        for _ in range(4):
+            t0 = time.perf_counter()
+            out, _o, _r = e.realign_junction(ss, tab, band)
+            times.append(time.perf_counter() - t0)
+        assert out[:, 0].tolist() == [0] * pairs and set((out[:, 4] - out[:, 3]).tolist()) == {300} and not out[:, 1].any()
+        ss.close()
+    finally:
+        e.close()
+    stated = 2.0 * pairs * rows * 4 * (5 * S + 45) / (1024 * 2.4e9)
+    best = min(times[1:])
+    print("realign_junction: %d pairs of %d rows at band %d (S = %d): %.2f ms (best of three; %s), stated %.2f ms, measured / stated %.2f"
+          % (pairs, rows, band, S, best * 1e3, " ".join("%.2f" % (t * 1e3) for t in times[1:]), stated * 1e3, best / stated), flush=True)
 
 
 if __name__ == "__main__":
@@ -184,6 +233,10 @@ if __name__ == "__main__":
         trace_main(sys.argv[2:])
     elif len(sys.argv) > 1 and sys.argv[1] == "--polish":
         trace_main(sys.argv[2:], "pol")
+    elif len(sys.argv) > 1 and sys.argv[1] == "--junction":
+        trace_main(sys.argv[2:], "jun")
+    elif len(sys.argv) > 1 and sys.argv[1] == "--junction-call":
+        junction_call(sys.argv[2:])
     else:
         sys.argv.insert(1, "ra")
         evidence_rate.main()

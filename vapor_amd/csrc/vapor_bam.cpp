@@ -1397,6 +1397,13 @@ extern "C" __attribute__((weak)) int vapor_realign_polish(vapor_ctx*, vapor_seqs
     return bfail(VAPOR_E_ARG, "vapor_realign_polish: this build has no pileup kernels");
 }
 
+// ... and `--realign-junction`'s one-jump reading of a pair (vapor_realign_junction: the two kernels of vapor_junction.h).
+extern "C" __attribute__((weak)) int vapor_realign_junction(vapor_ctx*, vapor_seqset*, int64_t, const vapor_pair*, int32_t, int32_t*, const int64_t*,
+                                                            int32_t*)
+{
+    return bfail(VAPOR_E_ARG, "vapor_realign_junction: this build has no junction kernels");
+}
+
 // The reference windows of a bgzipped FASTA on the device (vapor_fasta_windows_device, vapor_fasta_last_stats) are device code in
 // vapor_hip.hip as well; the CPU twin answers them with VAPOR_E_ARG, and the caller reads the windows on the host.
 extern "C" __attribute__((weak)) int vapor_fasta_windows_device(vapor_ctx*, int, int32_t, const uint64_t*, const uint64_t*, uint8_t*, int64_t,

@@ -11,6 +11,7 @@
 #include "vapor_realign.h"
 #include "vapor_realign_trace.h"
 #include "vapor_polish.h"
+#include "vapor_junction.h"
 #include "vapor_bamdev.h"
 #include "vapor_bgzf.h"
 #include "vapor_fasta.h"
@@ -2794,6 +2795,74 @@ extern "C" int vapor_realign_polish(vapor_ctx* ctx, vapor_seqset* set, int64_t n
     }
     HIPCHK(hipStreamSynchronize(st));
     sc.settled();
+    return VAPOR_OK;
+}
+
+// `--realign-junction` (vapor_junction.h): the one jump between the two sequences of every pair.  The checks, the
+// pair records and the workspace are vapor_junction_plan.h's; here: one upload of the records, the two launches back to back, the
+// copies back - the rows through one staging buffer, dealt to the caller's slots on the host - and one synchronisation.
+template <int S>
+static void junction_launch(hipStream_t st, const uint32_t* x4, const vapor_junction::JPair* d_pairs, int64_t n_pairs, int32_t band, int32_t* d_ws,
+                            int32_t* d_out)
+{
+    namespace vj = vapor_junction;
+    const dim3 block(64 * vapor_realign::WAVES);
+    hipLaunchKernelGGL((junction_rows_kernel<S>), dim3((unsigned)vj::rows_grid(n_pairs)), block, 0, st, x4, d_pairs, (long long)vj::tasks_of(n_pairs),
+                       (int)band, d_ws);
+    hipLaunchKernelGGL(junction_pick_kernel, dim3((unsigned)vj::pick_grid(n_pairs)), block, 0, st, d_pairs, (long long)n_pairs, (const int32_t*)d_ws,
+                       d_out);
+}
+
+extern "C" int vapor_realign_junction(vapor_ctx* ctx, vapor_seqset* set, int64_t n_pairs, const vapor_pair* pairs, int32_t band, int32_t* out,
+                                      const int64_t* row_off, int32_t* rows)
+{
+    namespace ra = vapor_realign;
+    namespace vj = vapor_junction;
+    if (!ctx || !set || n_pairs < 0 || n_pairs > ra::MAX_PAIRS || (n_pairs && (!pairs || !out)))
+        return fail(VAPOR_E_ARG, "vapor_realign_junction: null argument or a pair count outside 0 .. 2^26");
+    if (!ra::band_ok(band)) return fail(VAPOR_E_ARG, "vapor_realign_junction: band outside 1 .. VAPOR_MAX_BAND");
+    if (rows && !vj::row_off_ok(n_pairs, row_off)) return fail(VAPOR_E_ARG, "vapor_realign_junction: row_off must ascend from 0");
+    if (n_pairs == 0) return VAPOR_OK;
+    const size_t np = (size_t)n_pairs;
+    std::vector<vj::JPair> recs(np);                       // (the upload reads it: declared before the owners, which unwind first)
+    for (int64_t t = 0; t < n_pairs; ++t) {
+        vj::JPair& r = recs[(size_t)t];
+        r = vj::pair_record(pairs[t], set->n, [&](int32_t s) { return set->h[(size_t)s].len; }, [&](int32_t s) { return set->h[(size_t)s].chunk0; });
+        if (rows && !vj::slot_holds(r, row_off, t)) r = vj::JPair{0, 0, 0, 0, VAPOR_E_ARG, 0, 0};
+    }
+    const int64_t n_rows = vj::lay_out(recs.data(), n_pairs);
+    if (!vj::fits(n_rows, ctx->trace_budget)) return fail(VAPOR_E_NOMEM, "vapor_realign_junction: the pairs' row tables exceed trace_budget");
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const size_t ws_bytes = sizeof(int32_t) * vj::ROW * (size_t)n_rows;
+    std::vector<int32_t> staged(rows ? vj::ROW * (size_t)n_rows : 0);
+    CallScope sc(ctx, st);
+    Block<vj::JPair> d_pairs(sc);
+    Block<int32_t> d_ws(sc);
+    Block<int32_t> d_out(sc);
+    HIPCHK(d_pairs.ensure(sizeof(vj::JPair) * np));
+    HIPCHK(d_ws.ensure(std::max<size_t>(ws_bytes, 64)));
+    HIPCHK(d_out.ensure(sizeof(int32_t) * vj::OUT * np));
+    HIPCHK(hipMemcpyAsync(d_pairs.p, recs.data(), sizeof(vj::JPair) * np, hipMemcpyHostToDevice, st));
+    switch (ra::lane_width(band)) {
+    case 1: junction_launch<1>(st, set->d_x4, d_pairs, n_pairs, band, d_ws, d_out); break;
+    case 2: junction_launch<2>(st, set->d_x4, d_pairs, n_pairs, band, d_ws, d_out); break;
+    case 3: junction_launch<3>(st, set->d_x4, d_pairs, n_pairs, band, d_ws, d_out); break;
+    case 5: junction_launch<5>(st, set->d_x4, d_pairs, n_pairs, band, d_ws, d_out); break;
+    case 9: junction_launch<9>(st, set->d_x4, d_pairs, n_pairs, band, d_ws, d_out); break;
+    default: junction_launch<ra::MAX_SLOTS>(st, set->d_x4, d_pairs, n_pairs, band, d_ws, d_out); break;
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, d_out.p, sizeof(int32_t) * vj::OUT * np, hipMemcpyDeviceToHost, st));
+    if (rows && n_rows) HIPCHK(hipMemcpyAsync(staged.data(), d_ws.p, ws_bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    sc.settled();
+    if (rows)
+        for (int64_t t = 0; t < n_pairs; ++t) {
+            const vj::JPair& r = recs[(size_t)t];
+            if (!r.status)
+                memcpy(rows + vj::ROW * row_off[t], staged.data() + vj::ROW * r.row0, sizeof(int32_t) * vj::ROW * (size_t)vj::pair_rows(r.ns));
+        }
     return VAPOR_OK;
 }
 

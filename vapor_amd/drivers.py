@@ -601,12 +601,15 @@ class Realign:
     its edit distance to ref_seq[miss_bp:] minus that to alt_seq[miss_bp:] - or None when a pair came back with a status.
     `trace` (`--realign-out`; off unless asked): the payload also carries `.traces`, every read's alignment to the
     allele it fits; `name`: the locus as the files spell it.  `polish` (`--realign-polish`; off unless asked): the
-    payload also carries `.polish`, the consensus of the ALT voters on the alt allele."""
-    __slots__ = ("ref_seq", "alt_seq", "reads", "name", "trace", "polish")
+    payload also carries `.polish`, the consensus of the ALT voters on the alt allele.  `junction` (`--realign-junction`, DESIGN.md
+    4.26; off unless asked, and only with `polish`): the payload also carries `.junction`, the one jump of the polished allele
+    beside that of the call's."""
+    __slots__ = ("ref_seq", "alt_seq", "reads", "name", "trace", "polish", "junction")
 
-    def __init__(self, ref_seq, alt_seq, reads, name=None, trace=False, polish=False):
+    def __init__(self, ref_seq, alt_seq, reads, name=None, trace=False, polish=False, junction=False):
         self.ref_seq, self.alt_seq, self.reads, self.name, self.trace = ref_seq, alt_seq, reads, name, bool(trace)
         self.polish = bool(polish)
+        self.junction = bool(junction)
 
 
 class Realigned(list):
@@ -633,7 +636,12 @@ def vapor_realign_polish(name, trace, driver, *args):
     return (yield from _realign(name if trace else None, bool(trace), driver, args, True))
 
 
-def _realign(name, trace, driver, args, polish=False):
+def vapor_realign_junction(name, trace, driver, *args):
+    """`--realign --realign-polish --realign-junction`: vapor_realign_polish whose Realign request asks for the junction too."""
+    return (yield from _realign(name if trace else None, bool(trace), driver, args, True, True))
+
+
+def _realign(name, trace, driver, args, polish=False, junction=False):
     gen = driver(*args)
     last = None
     try:
@@ -651,8 +659,8 @@ def _realign(name, trace, driver, args, polish=False):
         scores = fin.value
     out = Realigned(scores if scores is not None else [])
     if last is not None:
-        out.realign = yield (Realign(last.ref_seq, last.alt_seq, last.reads, name, True, polish) if trace else
-                             Realign(last.ref_seq, last.alt_seq, last.reads, polish=polish))
+        out.realign = yield (Realign(last.ref_seq, last.alt_seq, last.reads, name, True, polish, junction) if trace else
+                             Realign(last.ref_seq, last.alt_seq, last.reads, polish=polish, junction=junction))
     return out
 
 

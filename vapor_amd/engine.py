@@ -780,6 +780,34 @@ class Engine:
                    L.ptr(counts, ctypes.c_uint32) if want_counts else None))
         return stats[:ng], calls[:cols], sites[:ng], ins[:ng], counts[:cols] if want_counts else None
 
+    # ---- `--realign-junction`: the one jump between the two sequences of a pair ----
+    def realign_junction_available(self) -> bool:
+        """Whether the loaded library has vapor_realign_junction (the CPU twin of the C ABI has not)."""
+        return self._available("vapor_realign_junction")
+
+    def realign_junction(self, seqset: SeqSet, pairs: np.ndarray, band: int, want_rows: bool = False):
+        """(out, row_off, rows) of every pair (vapor_realign_junction): seq1 the shorter sequence, seq2 the longer, off2 0.  out an
+        (n, 8) int32 array, a row {status, cost, i, j1, j2, f_F(i), f_R(ns - i), 0}: seq1 is seq2 with seq2[j1:j2] skipped at
+        row i, at `cost` further edits (junction.junction says it in numpy); status E_ARG and zeros for a pair the entry refuses.
+        With want_rows, rows is a (row_off[-1], 4) int32 array whose rows row_off[t] .. row_off[t + 1] are pair t's
+        {f_F, jf_F, f_R, jf_R} (junction.row_table), len(seq1) + 1 of them; else row_off and rows are None.
+        NotImplementedError where the library has no such entry: there is no other route."""
+        fn = self._wide_entry("vapor_realign_junction", "junction kernels (--realign-junction)")
+        pairs = np.ascontiguousarray(pairs, dtype=L.PAIR_DTYPE)
+        n = len(pairs)
+        out = np.zeros((max(n, 1), 8), dtype=np.int32)
+        row_off = rows = None
+        if want_rows:
+            lens = np.asarray(seqset.lens, dtype=np.int64)
+            s1 = np.asarray(pairs["seq1"], dtype=np.int64)
+            ok = (s1 >= 0) & (s1 < len(lens))
+            need = np.where(ok, lens[np.where(ok, s1, 0)] + 1, 0) if n else np.zeros(0, dtype=np.int64)
+            row_off = np.concatenate(([0], np.cumsum(need))).astype(np.int64)
+            rows = np.zeros((max(int(row_off[-1]), 1), 4), dtype=np.int32)
+        L.check(fn(self._ctx, seqset._h, n, pairs.ctypes.data if n else None, int(band), L.ptr(out, ctypes.c_int32),
+                   L.ptr(row_off, ctypes.c_int64) if want_rows else None, L.ptr(rows, ctypes.c_int32) if want_rows else None))
+        return out[:n], row_off, rows[:int(row_off[-1])] if want_rows else None
+
     def clean_hits_wide(self, lists: Sequence[np.ndarray], flags: Optional[Sequence[int]] = None):
         """clean_hits for lists with coordinates up to MAX_WIDE_SEQ_LEN (vapor_clean_hits_wide)."""
         return self._clean_lists(self._wide_entry("vapor_clean_hits_wide"), lists, flags)

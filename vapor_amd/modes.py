@@ -5,7 +5,7 @@ its own module - refine.py, phase.py, bothends.py, depth.py, signature.py, links
 depth.py to support.py also say how their regions are read (their reader surface), and the parser states the rule once (cli.MODE_OPTIONS)."""
 from __future__ import annotations
 
-from . import bothends, depth, links, phase, polish, realign, signature, support
+from . import bothends, depth, junction, links, phase, polish, realign, signature, support
 from . import refine as _refine
 
 
@@ -26,6 +26,7 @@ class Mode:
     chunk_payloads = None
     sink = None
     polish = False                             # (`--realign-polish`: the Realign requests ask for the consensus too)
+    junction = False                           # (`--realign-junction`: ... and for the one jump of the polished allele)
 
     def __init__(self, name, src, attr, keys=None, skip_dot=True, phased=False, margin_step=None, ci_of=None):
         self.name, self.attr, self.skip_dot, self.phased = name, attr, skip_dot, phased
@@ -62,4 +63,14 @@ def realign_polish(sink=None) -> Mode:
     m = Mode("realign", polish, "realign")
     m.sink = sink
     m.polish = True
+    return m
+
+
+def realign_junction(sink=None) -> Mode:
+    """`--realign --realign-polish --realign-junction`: realign_polish's columns followed by junction's six,
+    with realign_polish's sink."""
+    m = Mode("realign", junction, "realign")
+    m.sink = sink
+    m.polish = True
+    m.junction = True
     return m

@@ -557,7 +557,7 @@ def realign_requests(engine, reqs: Sequence[object]) -> List[object]:
         out = [realign.Payload() for _ in reqs]
         if any(r.polish for r in reqs):
             _realign_polish(engine, None, reqs, out, None, first)
-        return out
+        return out                            # (an empty pile has fewer than MIN_COV reads: no junction applies)
     n_lit = len(sb.seqs)
     pairs = np.zeros(len(rows), dtype=L.PAIR_DTYPE)
     tab = np.asarray(rows, dtype=np.int64)
@@ -574,6 +574,8 @@ def realign_requests(engine, reqs: Sequence[object]) -> List[object]:
             _realign_polish(engine, ss, reqs, out, pairs, first)
     finally:
         ss.close()
+    if any(r.junction for r in reqs):
+        _realign_junction(engine, reqs, out)
     return out
 
 
@@ -639,11 +641,73 @@ def _realign_polish(engine, ss, reqs, out, pairs, first) -> None:
     stats, calls, sites, ins, _counts = engine.realign_polish(ss, pairs[np.asarray(pick, dtype=np.int64)], realign.BAND, pfirst, col_off)
     for g, t in enumerate(who):
         text = None
-        if reqs[t].trace:             # (a locus the entry refuses keeps its allele: the columns say '.')
+        # (the text is spelt for a sink, and for the junction where the polish applies; a locus the entry refuses keeps its
+        # allele: the columns say '.')
+        if reqs[t].trace or (reqs[t].junction and int(stats[g][0]) == 0 and int(stats[g][1]) >= polish.MIN_COV):
             text = str(reqs[t].alt_seq)
             if int(stats[g][0]) == 0:
                 text = polish.apply(text, calls[col_off[g]:col_off[g + 1]], sites[g], ins[g])
         out[t].polish = polish.Polish(stats[g], text)
+
+
+def _lens_window(r):
+    """(first, symbols) of the stretch of r.ref_seq that the called allele spans: from the start of its first segment to the end
+    of its last, where both are forward slices of r.ref_seq; otherwise all of it.  Only an INS call below 5 000 bases differs
+    from the whole window: vapor_simple_ins reads that window len(ins) bases past the right flank."""
+    segs = getattr(r.alt_seq, "segs", None)
+    if segs and all(par is r.ref_seq and not rc for par, _o, _n, rc in (segs[0], segs[-1])):
+        lo, hi = int(segs[0][1]), int(segs[-1][1]) + int(segs[-1][2])
+        if 0 <= lo < hi <= len(r.ref_seq):
+            return lo, hi - lo
+    return 0, len(r.ref_seq)
+
+
+def _realign_junction(engine, reqs, out) -> None:
+    """`--realign-junction`: one engine.realign_junction call for the requests that ask and whose polish applies
+    (status 0, at least MIN_COV reads piled) - per request two pairs, the call's own alt allele and the polished one, each
+    against the window the called allele spans (_lens_window), the shorter sequence first - over one small sequence set:
+    windows and called alleles described as for the distances, polished alleles as literals.  The nine integers ride on the
+    payload (`.junction`), left and right in r.ref_seq's coordinates; where a pair comes back with a status there is none."""
+    from . import junction, polish, realign
+    from .drivers import Allele
+    sb = _SetBuilder()
+    rows, who, cut = [], [], []              # (`cut`: the described windows, alive while the builder keys them by id)
+    for t, r in enumerate(reqs):
+        po = getattr(out[t], "polish", None) if out[t] is not None else None
+        if not r.junction or po is None or po.text is None or po.stats[polish.STATUS] != 0 or po.stats[polish.PAIRS] < polish.MIN_COV:
+            continue
+        lo, n_win = _lens_window(r)
+        win = r.ref_seq
+        if (lo, n_win) != (0, len(r.ref_seq)):
+            win = Allele(r.ref_seq[lo:lo + n_win])
+            win.segs = [(r.ref_seq, lo, n_win, False)]
+            cut.append(win)
+        wi, ai = sb.describe(win, False), sb.describe(r.alt_seq, False)
+        pi = len(sb.seqs)
+        sb.seqs.append(po.text)                          # (a polished allele belongs to one request: no look-up)
+        forms = (junction.deletion_form(len(r.alt_seq), n_win), junction.deletion_form(len(po.text), n_win))
+        rows += [(ai, wi) if forms[0] else (wi, ai), (pi, wi) if forms[1] else (wi, pi)]
+        who.append((t, forms, lo))
+    if not who:
+        return
+    n_lit = len(sb.seqs)
+    tab = np.asarray(rows, dtype=np.int64)
+    tab = np.where(tab < 0, n_lit - 1 - tab, tab)        # derived sequence d: behind the literals
+    pairs = np.zeros(len(rows), dtype=L.PAIR_DTYPE)
+    pairs["seq1"], pairs["seq2"] = tab[:, 0], tab[:, 1]
+    ss = engine.seqset(sb.seqs, None, sb.derived) if sb.derived else engine.seqset(sb.seqs)
+    try:
+        recs, _row_off, _rows = engine.realign_junction(ss, pairs, realign.BAND)
+    finally:
+        ss.close()
+    for g, (t, forms, lo) in enumerate(who):
+        called, polished = recs[2 * g], recs[2 * g + 1]
+        if int(called[0]) == 0 and int(polished[0]) == 0:
+            c0, l0, r0, g0, _k0 = junction.of_record(called, forms[0])
+            c1, l1, r1, g1, k1 = junction.of_record(polished, forms[1])
+            out[t].junction = junction.Junction((c0, l0 + lo, r0 + lo, g0, c1, l1 + lo, r1 + lo, g1, k1))
+        if not reqs[t].trace:
+            out[t].polish.text = None                    # (no sink takes it)
 
 
 # ------------------------------------------------------------------------------------------
