@@ -190,6 +190,27 @@ def designed_expected():
     return _expected
 
 
+# the bands on both sides of every step of the compiled lane widths 1, 2, 3, 5, 9, 17: ceil((2 B + 1) / 64) slots a lane
+EDGE_BANDS = (31, 32, 63, 64, 95, 96, 159, 160, 287, 288, 512)
+EDGE_WIDTHS = (1, 2, 2, 3, 3, 5, 5, 9, 9, 17, 17)
+
+
+def edge_band_cases():
+    """[(name, read, allele, off2, band)] at every EDGE_BANDS: the insertion and the deletion of B and of B + 1 of designed_cases()
+    (every slot of the band carries a live cell), and one pair with a few substitutions behind off2 = 5."""
+    rng = random.Random(20231)
+    out = []
+    for band in EDGE_BANDS:
+        left, right = bytes(rng.choice(b"ACG") for _ in range(8)), bytes(rng.choice(b"ACG") for _ in range(band + 20))
+        for extra in (band, band + 1):
+            mid = b"T" * extra
+            out.append(("insertion of %d B=%d" % (extra, band), left + mid + right, left + right, 0, band))
+            out.append(("deletion of %d B=%d" % (extra, band), left + right, left + mid + right, 0, band))
+        s = _dna(rng, band + 40)
+        out.append(("substitutions off2=5 B=%d" % band, _with_subs(rng, s, 4), _dna(rng, 5) + s, 5, band))
+    return out
+
+
 def planted(rng, n, subs, indels, max_indel=6):
     """(read, allele): an allele of n random bases and a read made of it with planted substitutions and short indels."""
     allele = _dna(rng, n)

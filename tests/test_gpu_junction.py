@@ -61,6 +61,19 @@ def test_designed_pairs_equal_the_model_at_every_band(eng, band):
     assert not bad, (band, len(bad), bad[:5])
 
 
+def test_bands_on_both_sides_of_every_lane_width_equal_the_model(eng):
+    """A jump of B and of B + 1 in the longer sequence at the bands around every step of the compiled lane widths, rows asked for."""
+    bands = (31, 32, 63, 64, 95, 96, 159, 160, 287, 288, 512)
+    widths = [min(w for w in (1, 2, 3, 5, 9, 17) if 64 * w >= 2 * band + 1) for band in bands]       # 2 B + 1 slots over 64 lanes
+    assert widths == [1, 2, 2, 3, 3, 5, 5, 9, 9, 17, 17] and set(widths) == {1, 2, 3, 5, 9, 17}
+    rng = np.random.default_rng(26)
+    for band in bands:
+        left, right = bytes(rng.choice(list(b"ACG"), 8).tolist()), bytes(rng.choice(list(b"ACG"), band + 20).tolist())
+        pairs = [("jump of %d B=%d" % (extra, band), left + right, left + b"T" * extra + right, band) for extra in (band, band + 1)]
+        bad = wrong(pairs, device(eng, pairs, band), [M.junction(s, l, band) for _n, s, l, _b in pairs])
+        assert not bad, (band, len(bad), bad[:5])
+
+
 def test_designed_pairs_at_their_own_band_and_without_rows(eng):
     pairs, expect = M.designed_pairs(), M.expected_pairs()
     got = {}

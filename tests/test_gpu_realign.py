@@ -51,6 +51,20 @@ def test_designed_pairs_equal_the_model(eng):
     assert not wrong, wrong[:10]
 
 
+def lane_widths(bands):
+    """The compiled lane width each band runs at: the smallest of 1, 2, 3, 5, 9, 17 that deals its 2 B + 1 slots to 64 lanes."""
+    return [min(w for w in (1, 2, 3, 5, 9, 17) if 64 * w >= 2 * band + 1) for band in bands]
+
+
+def test_bands_on_both_sides_of_every_lane_width_equal_the_model(eng):
+    cases = M.edge_band_cases()
+    bands = sorted({c[4] for c in cases})
+    assert bands == list(M.EDGE_BANDS) and lane_widths(bands) == list(M.EDGE_WIDTHS) and set(lane_widths(bands)) == {1, 2, 3, 5, 9, 17}
+    got = device(eng, cases)
+    wrong = [(c[0], g, M.distance(*c[1:])) for c, g in zip(cases, got) if g != M.distance(*c[1:])]
+    assert not wrong, wrong[:10]
+
+
 def test_seeded_fuzz_equals_the_model(eng):
     cases = M.fuzz_cases()
     assert len(cases) == 60 and all(len(c[1]) <= 300 and len(c[2]) <= 300 for c in cases)

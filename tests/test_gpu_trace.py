@@ -63,6 +63,17 @@ def test_designed_pairs_equal_the_model_run_for_run(eng):
     assert not wrong, (len(wrong), wrong[:5])
 
 
+def test_bands_on_both_sides_of_every_lane_width_equal_the_model_run_for_run(eng):
+    cases = RM.edge_band_cases()
+    bands = sorted({c[4] for c in cases})
+    widths = [min(w for w in (1, 2, 3, 5, 9, 17) if 64 * w >= 2 * band + 1) for band in bands]       # 2 B + 1 slots over 64 lanes
+    assert bands == list(RM.EDGE_BANDS) and widths == list(RM.EDGE_WIDTHS) and set(widths) == {1, 2, 3, 5, 9, 17}
+    got = device(eng, cases)
+    expect = [tuple(M.trace(*c[1:])[:4]) for c in cases]
+    wrong = [(c[0], g, e) for c, g, e in zip(cases, got, expect) if g != e]
+    assert not wrong, (len(wrong), wrong[:5])
+
+
 def test_seeded_fuzz_equals_the_model(eng):
     cases = RM.fuzz_cases()
     assert len(cases) == 60

@@ -22,6 +22,8 @@ _HEADERS = [("vapor_kernels.h", True), ("vapor_wide.h", True), ("vapor_anyk.h", 
             ("vapor_records.h", True), ("vapor_planner.h", False), ("vapor_names.h", True),
             ("vapor_readrec.h", True), ("vapor_readplan.h", False), ("vapor_sa.h", False),
             ("vapor_realign.h", True), ("vapor_realign_plan.h", True),
+            # (the band row the realign, trace and junction kernels walk)
+            ("vapor_band_row.h", True),
             # (`--realign-out`, DESIGN.md 4.24: the trace kernels, and their host arithmetic, which they read as well)
             ("vapor_realign_trace.h", True), ("vapor_trace_plan.h", True),
             # (`--realign-polish`, DESIGN.md 4.25: the pileup and consensus kernels and the plan they read)

@@ -34,6 +34,7 @@
 #include <set>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <array>
 #include <atomic>
 #include <chrono>
@@ -2545,6 +2546,42 @@ extern "C" int vapor_anyk_batch(vapor_ctx* ctx, vapor_seqset* set, int64_t n_pai
 // ------------------------------------------------------------------------------------------
 // `--realign` (vapor_realign.h): the banded edit distance of every pair, one wavefront a pair.  The checks, the pair records and
 // the geometry are vapor_realign_plan.h's; here: one upload of the records, one launch, one copy back.
+//
+// What the four realign entries share.  The compiled lane width of a band, as a constant: f(std::integral_constant<int, S>) for
+// the S of vapor_realign::WIDTHS the band takes (a band out of range, which every entry has refused, would take the widest).
+template <int K = 0, typename F>
+static void with_lane_width(int32_t band, F&& f)
+{
+    namespace ra = vapor_realign;
+    if constexpr (K + 1 < ra::N_WIDTHS) {
+        if (ra::lane_width(band) != ra::WIDTHS[K]) return with_lane_width<K + 1>(band, f);
+    }
+    f(std::integral_constant<int, ra::WIDTHS[K]>{});
+}
+
+// the records of a call's pairs over the set: vapor_realign::RPair, or vapor_junction::JPair
+template <typename Rec>
+static std::vector<Rec> pair_records(const vapor_seqset* set, const vapor_pair* pairs, int64_t n_pairs)
+{
+    const auto len_of = [&](int32_t s) { return set->h[(size_t)s].len; };
+    const auto chunk_of = [&](int32_t s) { return set->h[(size_t)s].chunk0; };
+    std::vector<Rec> recs((size_t)n_pairs);
+    for (int64_t t = 0; t < n_pairs; ++t) {
+        if constexpr (std::is_same_v<Rec, vapor_junction::JPair>) recs[(size_t)t] = vapor_junction::pair_record(pairs[t], set->n, len_of, chunk_of);
+        else recs[(size_t)t] = vapor_realign::pair_record(pairs[t], set->n, len_of, chunk_of);
+    }
+    return recs;
+}
+
+// the refusals of every entry, in their order; args_ok: the pointers a call with pairs needs are there
+static int realign_refusal(const char* entry, const vapor_ctx* ctx, const vapor_seqset* set, int64_t n_pairs, bool args_ok, int32_t band)
+{
+    if (!ctx || !set || n_pairs < 0 || n_pairs > vapor_realign::MAX_PAIRS || (n_pairs && !args_ok))
+        return fail(VAPOR_E_ARG, std::string(entry) + ": null argument or a pair count outside 0 .. 2^26");
+    if (!vapor_realign::band_ok(band)) return fail(VAPOR_E_ARG, std::string(entry) + ": band outside 1 .. VAPOR_MAX_BAND");
+    return VAPOR_OK;
+}
+
 template <int S>
 static void realign_launch(hipStream_t st, const uint32_t* x4, const vapor_realign::RPair* d_pairs, int64_t n_pairs, int32_t band, int32_t* d_out)
 {
@@ -2555,30 +2592,18 @@ static void realign_launch(hipStream_t st, const uint32_t* x4, const vapor_reali
 extern "C" int vapor_realign_batch(vapor_ctx* ctx, vapor_seqset* set, int64_t n_pairs, const vapor_pair* pairs, int32_t band, int32_t* out)
 {
     namespace ra = vapor_realign;
-    if (!ctx || !set || n_pairs < 0 || n_pairs > ra::MAX_PAIRS || (n_pairs && (!pairs || !out)))
-        return fail(VAPOR_E_ARG, "vapor_realign_batch: null argument or a pair count outside 0 .. 2^26");
-    if (!ra::band_ok(band)) return fail(VAPOR_E_ARG, "vapor_realign_batch: band outside 1 .. VAPOR_MAX_BAND");
+    if (const int no = realign_refusal("vapor_realign_batch", ctx, set, n_pairs, pairs && out, band)) return no;
     if (n_pairs == 0) return VAPOR_OK;
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    std::vector<ra::RPair> recs((size_t)n_pairs);          // (the upload reads it: declared before the owners, which unwind first)
+    const std::vector<ra::RPair> recs = pair_records<ra::RPair>(set, pairs, n_pairs);      // (the upload reads it: declared before the owners, which unwind first)
     CallScope sc(ctx, st);
     Block<ra::RPair> d_pairs(sc);
     Block<int32_t> d_out(sc);
-    for (int64_t t = 0; t < n_pairs; ++t)
-        recs[(size_t)t] = ra::pair_record(pairs[t], set->n, [&](int32_t s) { return set->h[(size_t)s].len; },
-                                          [&](int32_t s) { return set->h[(size_t)s].chunk0; });
     HIPCHK(d_pairs.ensure(sizeof(ra::RPair) * (size_t)n_pairs));
     HIPCHK(d_out.ensure(sizeof(int32_t) * 2 * (size_t)n_pairs));
     HIPCHK(hipMemcpyAsync(d_pairs.p, recs.data(), sizeof(ra::RPair) * (size_t)n_pairs, hipMemcpyHostToDevice, st));
-    switch (ra::lane_width(band)) {
-    case 1: realign_launch<1>(st, set->d_x4, d_pairs, n_pairs, band, d_out); break;
-    case 2: realign_launch<2>(st, set->d_x4, d_pairs, n_pairs, band, d_out); break;
-    case 3: realign_launch<3>(st, set->d_x4, d_pairs, n_pairs, band, d_out); break;
-    case 5: realign_launch<5>(st, set->d_x4, d_pairs, n_pairs, band, d_out); break;
-    case 9: realign_launch<9>(st, set->d_x4, d_pairs, n_pairs, band, d_out); break;
-    default: realign_launch<ra::MAX_SLOTS>(st, set->d_x4, d_pairs, n_pairs, band, d_out); break;
-    }
+    with_lane_width(band, [&](auto S) { realign_launch<S()>(st, set->d_x4, d_pairs, n_pairs, band, d_out); });
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, d_out.p, sizeof(int32_t) * 2 * (size_t)n_pairs, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
@@ -2604,16 +2629,14 @@ extern "C" int vapor_realign_trace(vapor_ctx* ctx, vapor_seqset* set, int64_t n_
 {
     namespace ra = vapor_realign;
     namespace tr = vapor_trace;
-    if (!ctx || !set || n_pairs < 0 || n_pairs > ra::MAX_PAIRS || (n_pairs && (!pairs || !head || !runs)))
-        return fail(VAPOR_E_ARG, "vapor_realign_trace: null argument or a pair count outside 0 .. 2^26");
-    if (!ra::band_ok(band)) return fail(VAPOR_E_ARG, "vapor_realign_trace: band outside 1 .. VAPOR_MAX_BAND");
+    if (const int no = realign_refusal("vapor_realign_trace", ctx, set, n_pairs, pairs && head && runs, band)) return no;
     if (!tr::cap_ok(cap_runs)) return fail(VAPOR_E_ARG, "vapor_realign_trace: cap_runs below 1");
     if (n_pairs == 0) return VAPOR_OK;
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     const int S = ra::lane_width(band);
     const size_t np = (size_t)n_pairs, rec_bytes = sizeof(ra::RPair) * np;
-    std::vector<ra::RPair> recs(np);
+    const std::vector<ra::RPair> recs = pair_records<ra::RPair>(set, pairs, n_pairs);
     std::vector<int64_t> first;
     std::vector<uint64_t> off;
     std::vector<uint8_t> up(rec_bytes + sizeof(uint64_t) * np);        // (the upload reads it: declared before the owners)
@@ -2622,9 +2645,6 @@ extern "C" int vapor_realign_trace(vapor_ctx* ctx, vapor_seqset* set, int64_t n_
     Block<uint32_t> d_ws(sc);
     Block<int32_t> d_head(sc);
     Block<uint32_t> d_runs(sc);
-    for (int64_t t = 0; t < n_pairs; ++t)
-        recs[(size_t)t] = ra::pair_record(pairs[t], set->n, [&](int32_t s) { return set->h[(size_t)s].len; },
-                                          [&](int32_t s) { return set->h[(size_t)s].chunk0; });
     const int64_t ws_words = tr::plan_groups(recs.data(), n_pairs, band, S, ctx->trace_budget, first, off);
     memcpy(up.data(), recs.data(), rec_bytes);
     memcpy(up.data() + rec_bytes, off.data(), sizeof(uint64_t) * np);
@@ -2638,14 +2658,7 @@ extern "C" int vapor_realign_trace(vapor_ctx* ctx, vapor_seqset* set, int64_t n_
     for (size_t g = 0; g + 1 < first.size(); ++g) {
         const int64_t t0 = first[g], count = first[g + 1] - t0;
         if (count == 0) continue;
-        switch (S) {
-        case 1: realign_trace_launch<1>(st, set->d_x4, d_pairs, d_off, t0, count, band, d_ws, cap_runs, d_head, d_runs); break;
-        case 2: realign_trace_launch<2>(st, set->d_x4, d_pairs, d_off, t0, count, band, d_ws, cap_runs, d_head, d_runs); break;
-        case 3: realign_trace_launch<3>(st, set->d_x4, d_pairs, d_off, t0, count, band, d_ws, cap_runs, d_head, d_runs); break;
-        case 5: realign_trace_launch<5>(st, set->d_x4, d_pairs, d_off, t0, count, band, d_ws, cap_runs, d_head, d_runs); break;
-        case 9: realign_trace_launch<9>(st, set->d_x4, d_pairs, d_off, t0, count, band, d_ws, cap_runs, d_head, d_runs); break;
-        default: realign_trace_launch<ra::MAX_SLOTS>(st, set->d_x4, d_pairs, d_off, t0, count, band, d_ws, cap_runs, d_head, d_runs); break;
-        }
+        with_lane_width(band, [&](auto W) { realign_trace_launch<W()>(st, set->d_x4, d_pairs, d_off, t0, count, band, d_ws, cap_runs, d_head, d_runs); });
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipMemcpyAsync(head, d_head.p, sizeof(int32_t) * tr::HEAD * np, hipMemcpyDeviceToHost, st));
@@ -2666,9 +2679,7 @@ extern "C" int vapor_realign_polish(vapor_ctx* ctx, vapor_seqset* set, int64_t n
     namespace ra = vapor_realign;
     namespace tr = vapor_trace;
     namespace pp = vapor_polish;
-    if (!ctx || !set || n_pairs < 0 || n_pairs > ra::MAX_PAIRS || (n_pairs && !pairs))
-        return fail(VAPOR_E_ARG, "vapor_realign_polish: null argument or a pair count outside 0 .. 2^26");
-    if (!ra::band_ok(band)) return fail(VAPOR_E_ARG, "vapor_realign_polish: band outside 1 .. VAPOR_MAX_BAND");
+    if (const int no = realign_refusal("vapor_realign_polish", ctx, set, n_pairs, pairs != nullptr, band)) return no;
     if (n_loci < 0 || n_loci > ra::MAX_PAIRS) return fail(VAPOR_E_ARG, "vapor_realign_polish: a locus count outside 0 .. 2^26");
     if (n_loci == 0 && n_pairs == 0) return VAPOR_OK;
     if (!pp::tables_ok(n_pairs, n_loci, first, col_off))
@@ -2680,10 +2691,7 @@ extern "C" int vapor_realign_polish(vapor_ctx* ctx, vapor_seqset* set, int64_t n
     hipStream_t st = ctx->stream;
     const int S = ra::lane_width(band);
     const size_t np = (size_t)n_pairs, nl = (size_t)n_loci;
-    std::vector<ra::RPair> recs(np);
-    for (int64_t t = 0; t < n_pairs; ++t)
-        recs[(size_t)t] = ra::pair_record(pairs[t], set->n, [&](int32_t s) { return set->h[(size_t)s].len; },
-                                          [&](int32_t s) { return set->h[(size_t)s].chunk0; });
+    std::vector<ra::RPair> recs = pair_records<ra::RPair>(set, pairs, n_pairs);
     // the loci: status, trace words, run cap
     std::vector<pp::PLocus> loci(nl);
     std::vector<int64_t> twords(nl), cap(nl);
@@ -2758,14 +2766,7 @@ extern "C" int vapor_realign_polish(vapor_ctx* ctx, vapor_seqset* set, int64_t n
         if (count > 0) {
             const uint64_t* goff = d_off + gr.pair0;
             uint32_t* g_runs = b + gr.runs_off;
-            switch (S) {
-            case 1: realign_trace_launch<1>(st, set->d_x4, gp, goff, 0, count, band, b, cap_runs, ghead, g_runs); break;
-            case 2: realign_trace_launch<2>(st, set->d_x4, gp, goff, 0, count, band, b, cap_runs, ghead, g_runs); break;
-            case 3: realign_trace_launch<3>(st, set->d_x4, gp, goff, 0, count, band, b, cap_runs, ghead, g_runs); break;
-            case 5: realign_trace_launch<5>(st, set->d_x4, gp, goff, 0, count, band, b, cap_runs, ghead, g_runs); break;
-            case 9: realign_trace_launch<9>(st, set->d_x4, gp, goff, 0, count, band, b, cap_runs, ghead, g_runs); break;
-            default: realign_trace_launch<ra::MAX_SLOTS>(st, set->d_x4, gp, goff, 0, count, band, b, cap_runs, ghead, g_runs); break;
-            }
+            with_lane_width(band, [&](auto W) { realign_trace_launch<W()>(st, set->d_x4, gp, goff, 0, count, band, b, cap_runs, ghead, g_runs); });
             HIPCHK(hipGetLastError());
             const dim3 grid((unsigned)ra::grid_of(count)), block(64 * ra::WAVES);
             hipLaunchKernelGGL(pileup_kernel, grid, block, 0, st, (const uint32_t*)set->d_x4, gp, gpl, gloc, (long long)count, (const int32_t*)ghead,
@@ -2818,18 +2819,13 @@ extern "C" int vapor_realign_junction(vapor_ctx* ctx, vapor_seqset* set, int64_t
 {
     namespace ra = vapor_realign;
     namespace vj = vapor_junction;
-    if (!ctx || !set || n_pairs < 0 || n_pairs > ra::MAX_PAIRS || (n_pairs && (!pairs || !out)))
-        return fail(VAPOR_E_ARG, "vapor_realign_junction: null argument or a pair count outside 0 .. 2^26");
-    if (!ra::band_ok(band)) return fail(VAPOR_E_ARG, "vapor_realign_junction: band outside 1 .. VAPOR_MAX_BAND");
+    if (const int no = realign_refusal("vapor_realign_junction", ctx, set, n_pairs, pairs && out, band)) return no;
     if (rows && !vj::row_off_ok(n_pairs, row_off)) return fail(VAPOR_E_ARG, "vapor_realign_junction: row_off must ascend from 0");
     if (n_pairs == 0) return VAPOR_OK;
     const size_t np = (size_t)n_pairs;
-    std::vector<vj::JPair> recs(np);                       // (the upload reads it: declared before the owners, which unwind first)
-    for (int64_t t = 0; t < n_pairs; ++t) {
-        vj::JPair& r = recs[(size_t)t];
-        r = vj::pair_record(pairs[t], set->n, [&](int32_t s) { return set->h[(size_t)s].len; }, [&](int32_t s) { return set->h[(size_t)s].chunk0; });
-        if (rows && !vj::slot_holds(r, row_off, t)) r = vj::JPair{0, 0, 0, 0, VAPOR_E_ARG, 0, 0};
-    }
+    std::vector<vj::JPair> recs = pair_records<vj::JPair>(set, pairs, n_pairs);    // (the upload reads it: declared before the owners, which unwind first)
+    for (int64_t t = 0; rows && t < n_pairs; ++t)
+        if (!vj::slot_holds(recs[(size_t)t], row_off, t)) recs[(size_t)t] = vj::JPair{0, 0, 0, 0, VAPOR_E_ARG, 0, 0};
     const int64_t n_rows = vj::lay_out(recs.data(), n_pairs);
     if (!vj::fits(n_rows, ctx->trace_budget)) return fail(VAPOR_E_NOMEM, "vapor_realign_junction: the pairs' row tables exceed trace_budget");
     HIPCHK(hipSetDevice(ctx->device));
@@ -2844,14 +2840,7 @@ extern "C" int vapor_realign_junction(vapor_ctx* ctx, vapor_seqset* set, int64_t
     HIPCHK(d_ws.ensure(std::max<size_t>(ws_bytes, 64)));
     HIPCHK(d_out.ensure(sizeof(int32_t) * vj::OUT * np));
     HIPCHK(hipMemcpyAsync(d_pairs.p, recs.data(), sizeof(vj::JPair) * np, hipMemcpyHostToDevice, st));
-    switch (ra::lane_width(band)) {
-    case 1: junction_launch<1>(st, set->d_x4, d_pairs, n_pairs, band, d_ws, d_out); break;
-    case 2: junction_launch<2>(st, set->d_x4, d_pairs, n_pairs, band, d_ws, d_out); break;
-    case 3: junction_launch<3>(st, set->d_x4, d_pairs, n_pairs, band, d_ws, d_out); break;
-    case 5: junction_launch<5>(st, set->d_x4, d_pairs, n_pairs, band, d_ws, d_out); break;
-    case 9: junction_launch<9>(st, set->d_x4, d_pairs, n_pairs, band, d_ws, d_out); break;
-    default: junction_launch<ra::MAX_SLOTS>(st, set->d_x4, d_pairs, n_pairs, band, d_ws, d_out); break;
-    }
+    with_lane_width(band, [&](auto S) { junction_launch<S()>(st, set->d_x4, d_pairs, n_pairs, band, d_ws, d_out); });
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, d_out.p, sizeof(int32_t) * vj::OUT * np, hipMemcpyDeviceToHost, st));
     if (rows && n_rows) HIPCHK(hipMemcpyAsync(staged.data(), d_ws.p, ws_bytes, hipMemcpyDeviceToHost, st));

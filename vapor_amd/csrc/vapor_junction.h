@@ -1,19 +1,18 @@
 // vapor_junction.h - junction_rows_kernel and junction_pick_kernel: the one jump that turns the longer of two
 // sequences into the shorter, from a forward pass anchored at the common start and a backward pass anchored at the common end.
 //
-// junction_rows_kernel<S>: one wavefront a task, a task a pair in one direction.  The row is vapor_realign.h's - slot c = j - i + B
-// of row i is cell (i, j), lane l owns the S slots c = l S + s, the kernel keeps E = D - c, the allele's symbols are one-hot nibbles
-// in a shift register - with off2 = 0, and behind every row, row 0 included, the minimum of D = E + c over the slots that are cells
-// (c <= 2B and 0 <= j = i + c - B <= nl) with the smallest slot on a tie: one wave minimum of D << 11 | c, stored by one lane as
-// (f, jf).  The cells behind column nl are the wildcard continuation of the row and are masked here only: they feed no cell at or
-// before column nl.  The backward task reads both sequences from their last symbol towards their first: symbol k of a pass is
+// junction_rows_kernel<S>: one wavefront a task, a task a pair in one direction.  It walks the band row of vapor_band_row.h with
+// off2 = 0, and behind every row, row 0 included, takes the minimum of D = E + c over the slots that are cells
+// (c <= 2B and 0 <= j = i + c - B <= nl) with the smallest slot on a tie: one wave minimum of vapor_realign::row_key(D, c), stored
+// by one lane as (f, jf).  The cells behind column nl are the wildcard continuation of the row and are masked here only: they
+// feed no cell at or before column nl.  The backward task reads both sequences from their last symbol towards their first: symbol k of a pass is
 // symbol len - 1 - k, the words of the 4-bit plane loaded descending, one ahead; no reversed copy exists.
 // junction_pick_kernel: one wavefront a pair, 64 split rows a step: cost = f_F(i) + f_R(ns - i), j1 = jf_F(i),
 // j2 = nl - jf_R(ns - i), valid iff j2 >= j1, the smallest (cost, i) wins; one lane writes the pair's eight words.
 #pragma once
 
 #include "vapor_junction_plan.h"
-#include "vapor_realign.h"
+#include "vapor_band_row.h"
 
 namespace vapor {
 
@@ -79,7 +78,6 @@ template <int S>
 __global__ __launch_bounds__(64 * vapor_realign::WAVES) void junction_rows_kernel(const uint32_t* __restrict__ x4, const JPair* __restrict__ pairs,
                                                                                   long long n_tasks, int band, int32_t* __restrict__ ws)
 {
-    constexpr int NW = (4 * S + 31) / 32;                  // words of a lane's nibbles
     const int lane = (int)(threadIdx.x & 63u);
     const long long task = (long long)blockIdx.x * vapor_realign::WAVES + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     if (task >= n_tasks) return;                           // (a whole wavefront: the cross-lane steps below need all 64 lanes)
@@ -89,22 +87,13 @@ __global__ __launch_bounds__(64 * vapor_realign::WAVES) void junction_rows_kerne
     const uint32_t* __restrict__ x1 = x4 + p.word1;
     const uint32_t* __restrict__ x2 = x4 + p.word2;
     const int ns = p.ns, nl = p.nl, B = band, W = vapor_realign::row_slots(band);
-    const int c0 = lane * S;
     // row i of this pass: words 4 (row0 + i) + (backward ? 2 : 0) and the one behind it
     int32_t* __restrict__ mine = ws + p.row0 * vapor_junction::ROW + (back ? vapor_junction::R_F_BWD : vapor_junction::R_F_FWD);
 
-    // row 0: D[0][j] = j for 0 <= j <= B, so E = -B at the slots c = B .. 2B; the nibbles of row 1: slot c meets symbol c - B
+    const int c0 = lane * S;
     int E[S], vadd[S];
-    uint32_t w[NW];
-#pragma unroll
-    for (int k = 0; k < NW; ++k) w[k] = 0u;
-#pragma unroll
-    for (int s = 0; s < S; ++s) {
-        const int c = c0 + s;
-        E[s] = (c >= B && c < W) ? -B : RA_INF;
-        vadd[s] = (c + 1 < W) ? 2 : RA_INF;
-        w[s >> 3] |= jn_nibble(x2, nl, back, c - B) << ((s & 7) * 4);
-    }
+    uint32_t w[ra_words(S)];
+    ra_row_start<S>(E, vadd, w, c0, B, W, [&](int jb) { return jn_nibble(x2, nl, back, jb); });
     jn_store_row<S>(E, c0, 0, B, W, nl, lane, mine);
 
     // the shorter sequence's symbol i - 1 for row i; the longer one's symbol that enters at lane 63's last slot for row i + 1,
@@ -113,41 +102,13 @@ __global__ __launch_bounds__(64 * vapor_realign::WAVES) void junction_rows_kerne
     const int q0 = 64 * S - B;
     r1.start(x1, ns, back, 0);
     r2.start(x2, nl, back, q0);
-
+    RaNoHooks none;
     for (int i = 1; i <= ns; ++i) {
         const int ia = i - 1;
-        const uint32_t ca = r1.take(ia);
-        // mismatch bits: bit 4 s of x[s / 8] is set iff slot s does not match (a symbol outside ACGT matches the wildcard only)
-        uint32_t x[NW];
-        if (ca < 8u) {
-#pragma unroll
-            for (int k = 0; k < NW; ++k) x[k] = ~(w[k] >> (ca & 3u));
-        } else {
-#pragma unroll
-            for (int k = 0; k < NW; ++k) x[k] = ~(w[k] & (w[k] >> 1) & (w[k] >> 2) & (w[k] >> 3));
-        }
-        // t = min(diagonal, vertical) and its prefix minimum inside the lane
-        const int vin = dpp_from<0x130, 0xF>(RA_INF, E[0]);              // wave_shl:1 - lane l + 1's first slot (lane 63: none)
-        int run = RA_INF;
-#pragma unroll
-        for (int s = 0; s < S; ++s) {
-            const int d = E[s] + (int)((x[s >> 3] >> ((s & 7) * 4)) & 1u);
-            const int v = (s + 1 < S ? E[s + 1] : vin) + vadd[s];
-            run = min(run, min(d, v));
-            E[s] = run;
-        }
-        // ... and across the lanes: what the lanes before this one end with
-        const int before = dpp_from<0x138, 0xF>(RA_INF, wave_scan<OpMin>(run, RA_INF));     // wave_shr:1 (lane 0: none)
-#pragma unroll
-        for (int s = 0; s < S; ++s) E[s] = min(E[s], before);
+        ra_row_step<S>(E, vadd, w, r1.take(ia), none);
         jn_store_row<S>(E, c0, i, B, W, nl, lane, mine + (long long)i * vapor_junction::ROW);
-        // the nibbles move one slot down; lane 63 takes the longer sequence's next symbol
         const uint32_t cb = r2.take(q0 + ia);
-        const uint32_t nb = cb < 16u ? ra_onehot(cb) : 15u;
-        const uint32_t in = (uint32_t)dpp_from<0x130, 0xF>((int)nb, (int)(w[0] & 15u));
-#pragma unroll
-        for (int k = 0; k < NW; ++k) w[k] = (w[k] >> 4) | (k + 1 < NW ? w[k + 1] << 28 : 0u);
-        w[(S - 1) >> 3] |= in << (((S - 1) & 7) * 4);
+        ra_row_shift<S>(w, cb < 16u ? ra_onehot(cb) : 15u);
     }
 }
 

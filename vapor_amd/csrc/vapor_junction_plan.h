@@ -21,14 +21,12 @@ enum OutField { O_STATUS = 0, O_COST = 1, O_I = 2, O_J1 = 3, O_J2 = 4, O_FF = 5,
 constexpr int ROW = 4;
 enum RowField { R_F_FWD = 0, R_JF_FWD = 1, R_F_BWD = 2, R_JF_BWD = 3 };
 
-// the row's reduction key is D << KEY_SHIFT | c: a slot is below 2^11 (2 * VAPOR_MAX_BAND + 1 slots), D at most ns + nl < 2^17
-constexpr int KEY_SHIFT = 11;
+// the row's reduction key is vapor_realign's, of D (at most ns + nl) and the slot; NO_CELL lies above every key
+using vapor_realign::KEY_SHIFT;
+using vapor_realign::key_c;
+using vapor_realign::key_d;
+using vapor_realign::row_key;
 constexpr int NO_CELL = 0x7FFFFFFF;
-static_assert(2 * VAPOR_MAX_BAND + 1 <= (1 << KEY_SHIFT), "a slot fits the key");
-static_assert(2 * (int64_t)VAPOR_MAX_SEQ_LEN < ((int64_t)1 << (31 - KEY_SHIFT)), "a distance fits the key");
-VAPOR_RA_HD inline int row_key(int d, int c) { return d << KEY_SHIFT | c; }
-VAPOR_RA_HD inline int key_d(int key) { return key >> KEY_SHIFT; }
-VAPOR_RA_HD inline int key_c(int key) { return key & ((1 << KEY_SHIFT) - 1); }
 
 // A pair as the kernels take it (40 B): the sequences' first words in the 4-bit plane, ns = len(seq1) <= nl = len(seq2), and the
 // first row of its tables in the workspace.

@@ -48,6 +48,15 @@ inline int lane_width(int band)
     return 0;
 }
 
+// The key a wave minimum picks a slot of a row by is rank << KEY_SHIFT | c: a slot is below 2^11 (2 * VAPOR_MAX_BAND + 1 slots); the
+// rank is a distance (at most the two sequences' lengths, < 2^17) or vapor_trace::end_key (a slot, or at most m + band)
+constexpr int KEY_SHIFT = 11;
+static_assert(2 * VAPOR_MAX_BAND + 1 <= (1 << KEY_SHIFT), "a slot fits the key");
+static_assert(2 * (int64_t)VAPOR_MAX_SEQ_LEN < ((int64_t)1 << (31 - KEY_SHIFT)), "a distance fits the key");
+VAPOR_RA_HD inline int row_key(int d, int c) { return d << KEY_SHIFT | c; }
+VAPOR_RA_HD inline int key_d(int key) { return key >> KEY_SHIFT; }
+VAPOR_RA_HD inline int key_c(int key) { return key & ((1 << KEY_SHIFT) - 1); }
+
 // Rows the kernel walks: behind row m + band + 1 every cell of the band lies past the allele's end, where the free end makes
 // every step along a diagonal cost nothing - the row's minimum is the answer and does not change any more.
 VAPOR_RA_HD inline int rows_walked(int n, int m, int band)

@@ -1,7 +1,7 @@
 // vapor_realign_trace.h - the two kernels of vapor_realign_trace: the alignment behind realign_kernel's distance.
 //
-// realign_trace_kernel<S> is realign_kernel<S>'s row (vapor_realign.h: the band row in E = D - c, the nibble shift register, the
-// scalar sequence loads) with two bits kept per slot and row, the move the rule takes out of that cell:
+// realign_trace_kernel<S> walks realign_kernel<S>'s rows (vapor_band_row.h) and keeps two bits per slot and row through the row's
+// hooks, the move the rule takes out of that cell:
 //   0 '='  1 'X'   the diagonal predecessor, E' == E[c] + sub of the row before (the sub bit tells the two apart)
 //   2 'I'          otherwise the vertical predecessor, E' == E[c + 1] + 2 of the row before
 //   3 'D'          otherwise the horizontal predecessor: E' came out of the prefix minimum
@@ -18,16 +18,28 @@
 // (ballots and scalar arithmetic); lane 0 stores them from the back of the pair's slot, and n_runs counts on past cap_runs.
 #pragma once
 
+#include "vapor_band_row.h"
 #include "vapor_trace_plan.h"
 
 namespace vapor {
+
+// the hooks of a row that records its moves: TW words of 2-bit codes, slot s at bits 2 (s & 15) of word s / 16
+template <int TW>
+struct TraceMoves {
+    uint32_t mv[TW] = {};
+    __device__ __forceinline__ void slot(int s, int run, int d, int v, uint32_t sub)
+    {
+        const uint32_t code = run == d ? sub : run == v ? (uint32_t)vapor_trace::OP_I : (uint32_t)vapor_trace::OP_D;
+        mv[s >> 4] |= code << ((s & 15) * 2);
+    }
+    __device__ __forceinline__ void carried(int s) { mv[s >> 4] |= 3u << ((s & 15) * 2); }
+};
 
 template <int S>
 __global__ __launch_bounds__(64 * vapor_realign::WAVES) void realign_trace_kernel(const uint32_t* __restrict__ x4, const RPair* __restrict__ pairs,
                                                                                   const uint64_t* __restrict__ ws_off, long long t0, long long count,
                                                                                   int band, uint32_t* __restrict__ ws, int32_t* __restrict__ head)
 {
-    constexpr int NW = (4 * S + 31) / 32;                  // words of a lane's nibbles
     constexpr int TW = vapor_trace::words_of(S);           // words of a lane's moves
     const int lane = (int)(threadIdx.x & 63u);
     const long long g = (long long)blockIdx.x * vapor_realign::WAVES + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -42,100 +54,39 @@ __global__ __launch_bounds__(64 * vapor_realign::WAVES) void realign_trace_kerne
     const uint32_t* __restrict__ x1 = x4 + p.word1;
     const uint32_t* __restrict__ x2 = x4 + p.word2;
     const int n = p.n, m = p.m, off2 = p.off2, B = band, W = vapor_realign::row_slots(band);
-    const int len2 = off2 + m;
     const int rows = vapor_realign::rows_walked(n, m, B);
-    const int c0 = lane * S;
     uint32_t* __restrict__ tr = ws + ws_off[t] + (size_t)lane * TW;      // this lane's words of row 1
 
+    const int c0 = lane * S;
     int E[S], vadd[S];
-    uint32_t w[NW];
-#pragma unroll
-    for (int k = 0; k < NW; ++k) w[k] = 0u;
-#pragma unroll
-    for (int s = 0; s < S; ++s) {
-        const int c = c0 + s;
-        E[s] = (c >= B && c < W) ? -B : RA_INF;
-        vadd[s] = (c + 1 < W) ? 2 : RA_INF;
-        w[s >> 3] |= ra_allele_nibble(x2, off2, m, c - B) << ((s & 7) * 4);
-    }
-
-    uint32_t rw = 0u, rnext = n > 0 ? x1[0] : 0u;
+    uint32_t w[ra_words(S)];
+    ra_row_start<S>(E, vadd, w, c0, B, W, [&](int jb) { return ra_allele_nibble(x2, off2, m, jb); });
+    RaReader r1, r2;                                       // (as realign_kernel feeds the row)
     const int q0 = off2 + 64 * S - B;
-    uint32_t bw = (q0 >> 3) * 8 < len2 ? x2[q0 >> 3] : 0u;
-    uint32_t bnext = ((q0 >> 3) + 1) * 8 < len2 ? x2[(q0 >> 3) + 1] : 0u;
-
-    for (int i = 1; i <= rows; ++i) {
-        const int ia = i - 1;
-        if ((ia & 7) == 0) {
-            rw = rnext;
-            const int nx = (ia >> 3) + 1;
-            rnext = nx * 8 < n ? x1[nx] : 0u;
-        }
-        const uint32_t ca = (rw >> ((ia & 7) * 4)) & 15u;
-        uint32_t x[NW];
-        if (ca < 8u) {
-#pragma unroll
-            for (int k = 0; k < NW; ++k) x[k] = ~(w[k] >> (ca & 3u));
-        } else {
-#pragma unroll
-            for (int k = 0; k < NW; ++k) x[k] = ~(w[k] & (w[k] >> 1) & (w[k] >> 2) & (w[k] >> 3));
-        }
-        const int vin = dpp_from<0x130, 0xF>(RA_INF, E[0]);              // wave_shl:1
-        int run = RA_INF;
-        uint32_t mv[TW];
-#pragma unroll
-        for (int k = 0; k < TW; ++k) mv[k] = 0u;
-#pragma unroll
-        for (int s = 0; s < S; ++s) {
-            const uint32_t sub = (x[s >> 3] >> ((s & 7) * 4)) & 1u;
-            const int d = E[s] + (int)sub;
-            const int v = (s + 1 < S ? E[s + 1] : vin) + vadd[s];
-            run = min(run, min(d, v));
-            E[s] = run;
-            const uint32_t code = run == d ? sub : run == v ? (uint32_t)vapor_trace::OP_I : (uint32_t)vapor_trace::OP_D;
-            mv[s >> 4] |= code << ((s & 15) * 2);
-        }
-        const int before = dpp_from<0x138, 0xF>(RA_INF, wave_scan<OpMin>(run, RA_INF));     // wave_shr:1
-#pragma unroll
-        for (int s = 0; s < S; ++s) {
-            if (before < E[s]) mv[s >> 4] |= 3u << ((s & 15) * 2);
-            E[s] = min(E[s], before);
-        }
-        if constexpr (TW == 1) tr[0] = mv[0];
-        else *reinterpret_cast<uint2*>(tr) = make_uint2(mv[0], mv[1]);
+    r1.start(x1, n, 0);
+    r2.start(x2, off2 + m, q0);
+    for (int ia = 0; ia < rows; ++ia) {
+        TraceMoves<TW> moves;
+        ra_row_step<S>(E, vadd, w, r1.take(ia), moves);
+        if constexpr (TW == 1) tr[0] = moves.mv[0];
+        else *reinterpret_cast<uint2*>(tr) = make_uint2(moves.mv[0], moves.mv[1]);
         tr += vapor_trace::row_words(S);
-        const int q = q0 + ia;
-        const uint32_t nb = q - off2 < m ? ra_onehot((bw >> ((q & 7) * 4)) & 15u) : 15u;
-        if ((q & 7) == 7) {
-            bw = bnext;
-            const int nx = (q >> 3) + 2;
-            bnext = nx * 8 < len2 ? x2[nx] : 0u;
-        }
-        const uint32_t in = (uint32_t)dpp_from<0x130, 0xF>((int)nb, (int)(w[0] & 15u));
-#pragma unroll
-        for (int k = 0; k < NW; ++k) w[k] = (w[k] >> 4) | (k + 1 < NW ? w[k + 1] << 28 : 0u);
-        w[(S - 1) >> 3] |= in << (((S - 1) & 7) * 4);
+        ra_row_shift<S>(w, r2.nibble(q0 + ia));
     }
 
-    // d as realign_kernel has it, then the slot the rule prefers among those that hold d (key << 11 | slot: a slot is below 2048)
-    int best = RA_INF;
-#pragma unroll
-    for (int s = 0; s < S; ++s) {
-        const int c = c0 + s;
-        if (c < W && rows + c - B >= 0) best = min(best, E[s] + c);
-    }
-    best = wave_min_i32(best);
+    // d as realign_kernel has it, then the slot the rule prefers among those that hold d
+    const int best = wave_min_i32(ra_row_best<S>(E, c0, rows, B, W));
     int pick = 0x7FFFFFFF;
 #pragma unroll
     for (int s = 0; s < S; ++s) {
         const int c = c0 + s;
         const int key = vapor_trace::end_key(c, n, m, B, rows);
-        if (key != vapor_trace::NO_SLOT && E[s] + c == best) pick = min(pick, key << 11 | c);
+        if (key != vapor_trace::NO_SLOT && E[s] + c == best) pick = min(pick, vapor_realign::row_key(key, c));
     }
     pick = wave_min_i32(pick);
     int i_end = 0, j_end = 0, status = 0;
     if (pick == 0x7FFFFFFF) status = VAPOR_E_HIP;          // (no slot holds d: cannot be; the traceback leaves such a pair alone)
-    else vapor_trace::end_cell(pick & 2047, n, m, B, rows, i_end, j_end);
+    else vapor_trace::end_cell(vapor_realign::key_c(pick), n, m, B, rows, i_end, j_end);
     if (lane < vapor_trace::HEAD)
         h[lane] = lane == vapor_trace::H_D ? best : lane == vapor_trace::H_STATUS ? status : lane == vapor_trace::H_I_END ? i_end
                   : lane == vapor_trace::H_J_END ? j_end : 0;
