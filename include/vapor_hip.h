@@ -413,6 +413,38 @@ int vapor_realign_polish(vapor_ctx* ctx, vapor_seqset* set, int64_t n_pairs, con
                          const int64_t* first, const int64_t* col_off, int32_t* stats, uint8_t* calls, int32_t* sites, uint8_t* ins,
                          uint32_t* counts);
 
+/* ---- `--realign-revote`: every read against the polished allele ------------- */
+/*
+ * vapor_realign_polish, and behind it, without a round trip, a second alignment.  The arguments up to `counts`, their results,
+ * refusals and groups are vapor_realign_polish's, bit for bit.
+ * Spelling, on plane codes (A C G T 0..3, a c g t 4..7, N / IUPAC 8, their lower case 9, other 15): the flagged columns of a locus
+ * (call bit 3) are numbered k = 0, 1, .. in column order; for q ascending a flagged column emits the sites[k][1] bases of ins[k]
+ * as codes 0..3, then every column emits its own symbol - KEEP the allele's code unchanged, a call 0..3 that code, DELETE nothing.
+ * start(q) counts the symbols emitted before column q's inserted text, own(q) = start(q) + (sites[k][1] if q is flagged else 0),
+ * own(len) = plen.
+ * The vote pairs of locus g are votes[vfirst[g] .. vfirst[g + 1]) (n_loci + 1 ascending int64 from 0 to n_votes): seq1 the read,
+ * seq2 the locus's allele (its pairs' seq2; for a locus without pairs that of its first vote pair vapor_realign_batch accepts
+ * whose seq2 has the locus's columns), off2 in the called allele's columns.  A read starts in the polished allele at
+ * off2' = own(off2); d_pol is vapor_realign_batch's d of the read against the polished symbols from off2' on, m' = plen - off2'.
+ * vout[4 t ..] = {d_pol, status, off2', m'}; lout[4 g ..] = {vstatus, plen, 0, 0}.  vstatus is the polish status where that is
+ * not 0 (and VAPOR_E_ARG for a locus that has no allele), with plen 0; VAPOR_E_ARG for plen > VAPOR_MAX_SEQ_LEN.  The vote pairs of
+ * a locus whose vstatus is not 0 get {-1, vstatus, 0, 0}; a vote pair vapor_realign_batch would refuse, or whose seq2 is not the
+ * locus's allele, gets {-1, VAPOR_E_ARG, 0, 0} while the others are served (off2 == len is legal: m' = 0).  A locus without vote
+ * pairs is spelt all the same; n_votes == 0 is legal.
+ * spelt (may be NULL): spelt_off holds n_loci + 1 ascending int64 from 0, and the plen codes of locus g are written one a byte
+ * from spelt_off[g] on; a slot of fewer than len + 64 * min(256, len) bytes gives the locus vstatus VAPOR_E_ARG and writes
+ * nothing, its polish part is served.
+ * The call returns VAPOR_E_ARG where vapor_realign_polish does, for n_votes outside 0 .. 2^26, a vfirst that does not ascend from
+ * 0 to n_votes and a spelt_off that does not ascend from 0.  Per locus the group's buffer also holds own[], one byte a spelt
+ * symbol and the polished 4-bit plane, charged to "trace_budget"; per group three more kernels behind insert_kernel
+ * (spell_kernel, spell_pack_kernel, realign_onto_kernel), still one synchronisation a call.  The polished allele never crosses
+ * the link.  A library without a device exports the name and refuses every call with VAPOR_E_ARG; there is no host route.
+ */
+int vapor_realign_revote(vapor_ctx* ctx, vapor_seqset* set, int64_t n_pairs, const vapor_pair* pairs, int32_t band, int64_t n_loci,
+                         const int64_t* first, const int64_t* col_off, int32_t* stats, uint8_t* calls, int32_t* sites, uint8_t* ins,
+                         uint32_t* counts, int64_t n_votes, const vapor_pair* votes, const int64_t* vfirst, int32_t* vout, int32_t* lout,
+                         const int64_t* spelt_off, uint8_t* spelt);
+
 /* ---- `--realign-junction`: the one jump between two sequences --------------- */
 /*
  * Per pair: s = seq1 (ns symbols) and l = seq2 (nl symbols), ns <= nl, off2 == 0; symbols, matching, the band and D are

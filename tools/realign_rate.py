@@ -27,6 +27,13 @@ the same legs with this tree's `--realign --realign-polish` run in place of the 
 the plain, `--realign` and `--realign --realign-polish` runs of the parent checkout (which has all three) and of this tree, and
 this tree's `--realign --realign-polish --realign-junction` run; its table must be the `--realign-polish` run's in the leading
 columns.  --kernels DIR also prints the two junction kernels.
+`--realign-revote` likewise:
+  python tools/realign_rate.py --revote [n_loci] [--repeats R] [--parent DIR] [--bed-repeat K] [--layers N] [--timeout S]
+                               [--kernel-only [--kernel-leg plain|ra|pol|rev]]
+the same three shared legs and this tree's `--realign --realign-polish --realign-revote` run; its table must be the
+`--realign-polish` run's in the leading columns.  The run's process also times polish.apply - the host's spelling, which the
+device's replaces - over the loci of its last run, on the calls the device gave.  --kernels DIR also prints the three re-vote
+kernels.
   python tools/realign_rate.py --junction-call [pairs] [rows] [band]
 one Engine.realign_junction call (wall time with its copies, best of three) of `pairs` pairs of `rows` rows, the longer
 sequence carrying a jump of 300 symbols, beside DESIGN.md 4.23's arithmetic for its 2 * pairs wavefronts."""
@@ -67,7 +74,7 @@ def kernels(d):
     digest = hashlib.sha256("\n".join(sorted("%s %d" % (r["Name"], int(r["Calls"])) for r in rows)).encode()).hexdigest()[:16]
     print("launches: %d in all, digest of (kernel, launches) %s" % (sum(int(r["Calls"]) for r in rows), digest))
     for name in ("realign_trace_kernel", "traceback_kernel", "pileup_kernel", "consensus_kernel", "pileup_ins_kernel", "insert_kernel", "junction_rows_kernel",
-                 "junction_pick_kernel"):
+                 "junction_pick_kernel", "spell_kernel", "spell_pack_kernel", "realign_onto_kernel"):
         mine = [r for r in rows if name in r["Name"]]
         if mine:
             t = sum(float(r["TotalDurationNs"]) for r in mine)
@@ -76,7 +83,8 @@ def kernels(d):
 
 
 LEGS = {"plain": [], "ra": ["--realign"], "out": ["--realign", "--realign-out"], "pol": ["--realign", "--realign-polish"],
-        "jun": ["--realign", "--realign-polish", "--realign-junction"]}
+        "jun": ["--realign", "--realign-polish", "--realign-junction"], "rev": ["--realign", "--realign-polish", "--realign-revote"]}
+TAIL = {"pol": 6, "jun": 6, "rev": 8}      # the columns a leg appends to the table of the leg before it
 
 
 def trace_child(root, leg, fa, bam, bed, runs=4):
@@ -99,8 +107,19 @@ def trace_child(root, leg, fa, bam, bed, runs=4):
             finally:
                 close_s.append(time.perf_counter() - t0)
         realign.TraceWriter.close = timed
+    spelt = []                             # (`rev`: what every Engine.realign_revote call of a run gave, for the host's spelling below)
+    if leg == "rev":
+        from vapor_amd.engine import Engine
+        orig_revote = Engine.realign_revote
+
+        def kept(self, ss, pairs, band, first, col_off, *more, **kw):
+            got = orig_revote(self, ss, pairs, band, first, col_off, *more, **kw)
+            spelt.append((list(col_off), got[1], got[2], got[3]))
+            return got
+        Engine.realign_revote = kept
     times = []
     for _ in range(int(runs)):
+        del spelt[:]
         with contextlib.redirect_stdout(io.StringIO()):
             t0 = time.perf_counter()
             rc = cli.main(args)
@@ -108,9 +127,23 @@ def trace_child(root, leg, fa, bam, bed, runs=4):
         assert rc in (0, None), rc
     got = {"loci": sum(1 for _ in open(bed)), "best_s": min(times[1:] or times), "runs_s": times[1:] or times,
            "table": hashlib.sha256(open(out, "rb").read()).hexdigest()[:16]}
-    if leg in ("pol", "jun"):              # (the table without its last six columns: the run's before it, byte for byte)
-        lead = "".join("\t".join(ln.rstrip("\n").split("\t")[:-6]) + "\n" for ln in open(out))
+    if leg in TAIL:                        # (the table without the leg's own columns: the run's before it, byte for byte)
+        lead = "".join("\t".join(ln.rstrip("\n").split("\t")[:-TAIL[leg]]) + "\n" for ln in open(out))
         got["lead"] = hashlib.sha256(lead.encode()).hexdigest()[:16]
+    if leg == "rev":                       # (polish.apply over the last run's loci, on texts of the alleles' lengths: best of three)
+        from vapor_amd import polish
+        best, n_loci, n_cols = None, 0, 0
+        for _ in range(3):
+            t0 = time.perf_counter()
+            n_loci = n_cols = 0
+            for col_off, calls, sites, ins in spelt:
+                for g in range(len(col_off) - 1):
+                    polish.apply("A" * (col_off[g + 1] - col_off[g]), calls[col_off[g]:col_off[g + 1]], sites[g], ins[g])
+                    n_loci += 1
+                    n_cols += col_off[g + 1] - col_off[g]
+            dt = time.perf_counter() - t0
+            best = dt if best is None else min(best, dt)
+        got.update(apply_s=best, apply_loci=n_loci, apply_cols=n_cols)
     if leg == "out":
         sam = os.path.join(tmp, "traces.sam")
         got.update(close_s=min(close_s[1:] or close_s), sam_mb=os.path.getsize(sam) / 1e6,
@@ -153,7 +186,7 @@ def trace_main(argv, last="out"):
         if r.returncode != 0:
             raise SystemExit("child %s %s failed:\n%s" % (root, leg, r.stderr[-3000:]))
         return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
-    shared = ("plain", "ra", "pol") if last == "jun" else ("plain", "ra")      # (the legs the parent has too)
+    shared = ("plain", "ra", "pol") if last in ("jun", "rev") else ("plain", "ra")      # (the legs the parent has too)
     order = ([("parent", parent, leg) for leg in shared] if parent else []) + [("this", here, leg) for leg in shared + (last,)]
     res = {}
     for rep in range(repeats):
@@ -174,6 +207,13 @@ def trace_main(argv, last="out"):
         print("--realign-out / --realign: rate %.3f (medians); tables equal: %s; the writer's close is %.1f %% of the run"
               % (med(out) / med(ra), {g["table"] for g in out} == {g["table"] for g in ra},
                  100.0 * min(g["close_s"] for g in out) / min(g["best_s"] for g in out)))
+    elif last == "rev":
+        pol = res[("this", "pol")]
+        print("--realign-revote / --realign-polish: rate %.3f (medians); the leading columns equal --realign-polish's table: %s"
+              % (med(out) / med(pol), {g["lead"] for g in out} == {g["table"] for g in pol}))
+        g = min(out, key=lambda g: g["apply_s"])
+        print("polish.apply on this host over the run's %d loci (%d columns): %.4f s, %.3f ms a locus - %.1f %% of the --realign-revote run"
+              % (g["apply_loci"], g["apply_cols"], g["apply_s"], 1e3 * g["apply_s"] / max(g["apply_loci"], 1), 100.0 * g["apply_s"] / g["best_s"]))
     elif last == "jun":
         pol = res[("this", "pol")]
         print("--realign-junction / --realign-polish: rate %.3f (medians); the leading columns equal --realign-polish's table: %s"
@@ -235,6 +275,8 @@ if __name__ == "__main__":
         trace_main(sys.argv[2:], "pol")
     elif len(sys.argv) > 1 and sys.argv[1] == "--junction":
         trace_main(sys.argv[2:], "jun")
+    elif len(sys.argv) > 1 and sys.argv[1] == "--revote":
+        trace_main(sys.argv[2:], "rev")
     elif len(sys.argv) > 1 and sys.argv[1] == "--junction-call":
         junction_call(sys.argv[2:])
     else:

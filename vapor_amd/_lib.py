@@ -64,7 +64,7 @@ EXPORTS = [
     "vapor_bam_signature", "vapor_bam_signature_device",
     "vapor_bam_links", "vapor_bam_links_device",
     "vapor_bam_support", "vapor_bam_support_device",
-    "vapor_realign_batch", "vapor_realign_trace", "vapor_realign_polish", "vapor_realign_junction",
+    "vapor_realign_batch", "vapor_realign_trace", "vapor_realign_polish", "vapor_realign_junction", "vapor_realign_revote",
 ]
 # entry points a library may lack (the CPU twin of the C ABI has no wide or any-k route and no refinement kernel): bound when
 # present, and the engine's wide, any-k and grid methods raise NotImplementedError when they are not
@@ -92,7 +92,9 @@ OPTIONAL_EXPORTS = ("vapor_wide_batch", "vapor_clean_hits_wide", "vapor_anyk_bat
                     # (`--realign-polish`, DESIGN.md 4.25: no other route either - without it Engine.realign_polish raises)
                     "vapor_realign_polish",
                     # (`--realign-junction`, DESIGN.md 4.26: no other route either - without it Engine.realign_junction raises)
-                    "vapor_realign_junction")
+                    "vapor_realign_junction",
+                    # (`--realign-revote`, DESIGN.md 4.27: no other route either - without it Engine.realign_revote raises)
+                    "vapor_realign_revote")
 MAX_CANDIDATES = 128           # breakpoint refinement: candidates per locus (VAPOR_MAX_CANDIDATES)
 
 _lib = None
@@ -254,6 +256,9 @@ def bind(L: ctypes.CDLL) -> ctypes.CDLL:
         L.vapor_realign_trace.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_int32, ctypes.c_int32, i32p, u32p]
     if hasattr(L, "vapor_realign_polish"):
         L.vapor_realign_polish.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_int32, ctypes.c_int64, i64p, i64p, i32p, u8p, i32p, u8p, u32p]
+    if hasattr(L, "vapor_realign_revote"):
+        L.vapor_realign_revote.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_int32, ctypes.c_int64, i64p, i64p, i32p, u8p, i32p, u8p, u32p,
+                                           ctypes.c_int64, vp, i64p, i32p, i32p, i64p, u8p]
     if hasattr(L, "vapor_realign_junction"):
         L.vapor_realign_junction.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_int32, i32p, i64p, i32p]
     if hasattr(L, "vapor_plan_set_grid"):

@@ -429,7 +429,9 @@ def _simple_job(name, info, key, fig, row_prefix, label, plt_li, ctx, mode, with
     elif kind == 'realign':
         # (every read meets both alleles once more, in a band: about the cost of the locus again; the array route has no second pass)
         call = (drivers.vapor_realign, _SIMPLE[name], n_cff, plt_li, bam_in, ref, info, fig, False)
-        if mode.junction:                    # (`--realign-junction`: the polish's request, asking for the junction as well)
+        if mode.revote:                      # (`--realign-revote`: the polish's request, asking for the second vote as well)
+            call = (drivers.vapor_realign_revote, key, mode.sink is not None, mode.junction) + call[1:]
+        elif mode.junction:                  # (`--realign-junction`: the polish's request, asking for the junction as well)
             call = (drivers.vapor_realign_junction, key, mode.sink is not None) + call[1:]
         elif mode.polish:                    # (`--realign-polish`: the request asks for the consensus too, with a sink for the traces as well)
             call = (drivers.vapor_realign_polish, key, mode.sink is not None) + call[1:]
@@ -447,6 +449,8 @@ def _ins_job(call, cost, spec, mode, key=None):
     call, about twice its cost, on the drivers' route (no description), as _simple_job has it for the other three types
     (under `--realign-out` drivers.vapor_realign_out, named `key`)."""
     if mode is not None and mode.name == 'realign':
+        if mode.revote:
+            return (drivers.vapor_realign_revote, key, mode.sink is not None, mode.junction) + call, 2 * cost, None
         if mode.junction:
             return (drivers.vapor_realign_junction, key, mode.sink is not None) + call, 2 * cost, None
         if mode.polish:
@@ -977,6 +981,9 @@ def build_parser() -> argparse.ArgumentParser:
     # (`--realign-junction`, DESIGN.md 4.26: the polished allele read as one jump of its window, six columns behind
     # --realign-polish's; no mode of its own - it needs --realign-polish - and suppressed for the same reason)
     p.add_argument('--realign-junction', action='store_true', help=argparse.SUPPRESS)
+    # (`--realign-revote`, DESIGN.md 4.27: every read aligned once more, against the polished allele, eight columns behind
+    # everything else the run appends; no mode of its own - it needs --realign-polish - and suppressed for the same reason)
+    p.add_argument('--realign-revote', action='store_true', help=argparse.SUPPRESS)
     p.add_argument('--min-mapq', metavar='Q', type=_int_in('--min-mapq', 0, 255), default=0,
                    help='every sub-command: skip records with MAPQ below Q (0..255, default 0), as `samtools view -q Q` does; a '
                         'filtered record is treated as if it were not in the file')
@@ -1078,6 +1085,8 @@ def _main(argv, held) -> int:
         parser.error('--realign-polish needs --realign')
     if args.realign_junction and not args.realign_polish:
         parser.error('--realign-junction needs --realign-polish')
+    if args.realign_revote and not args.realign_polish:
+        parser.error('--realign-revote needs --realign-polish')
     if args.phase_vcf is not None:
         args.phased = True               # (the groups, the scoring and the columns are --phased's: only the tags' source differs)
     # a run has one mode: every later option of MODE_OPTIONS refuses the sub-commands it does not apply to, then each earlier one
@@ -1143,7 +1152,8 @@ def _main(argv, held) -> int:
     if mode is modes.REALIGN and args.realign_polish:
         from . import polish
         sink = polish.PolishWriter(args.realign_out, vdist.rank(), vdist.world()) if args.realign_out is not None else None
-        mode = modes.realign_junction(sink) if args.realign_junction else modes.realign_polish(sink)
+        mode = (modes.realign_revote(sink, args.realign_junction) if args.realign_revote else
+                modes.realign_junction(sink) if args.realign_junction else modes.realign_polish(sink))
     elif mode is modes.REALIGN and args.realign_out is not None:
         from . import realign
         mode = modes.realign_out(realign.TraceWriter(args.realign_out, vdist.rank(), vdist.world()))

@@ -1397,6 +1397,15 @@ extern "C" __attribute__((weak)) int vapor_realign_polish(vapor_ctx*, vapor_seqs
     return bfail(VAPOR_E_ARG, "vapor_realign_polish: this build has no pileup kernels");
 }
 
+// ... and `--realign-revote`'s second vote on the polished allele (vapor_realign_revote: the three kernels of vapor_revote.h behind
+// the polish's).
+extern "C" __attribute__((weak)) int vapor_realign_revote(vapor_ctx*, vapor_seqset*, int64_t, const vapor_pair*, int32_t, int64_t, const int64_t*,
+                                                          const int64_t*, int32_t*, uint8_t*, int32_t*, uint8_t*, uint32_t*, int64_t,
+                                                          const vapor_pair*, const int64_t*, int32_t*, int32_t*, const int64_t*, uint8_t*)
+{
+    return bfail(VAPOR_E_ARG, "vapor_realign_revote: this build has no re-vote kernels");
+}
+
 // ... and `--realign-junction`'s one-jump reading of a pair (vapor_realign_junction: the two kernels of vapor_junction.h).
 extern "C" __attribute__((weak)) int vapor_realign_junction(vapor_ctx*, vapor_seqset*, int64_t, const vapor_pair*, int32_t, int32_t*, const int64_t*,
                                                             int32_t*)

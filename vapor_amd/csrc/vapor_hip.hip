@@ -11,6 +11,7 @@
 #include "vapor_realign.h"
 #include "vapor_realign_trace.h"
 #include "vapor_polish.h"
+#include "vapor_revote.h"
 #include "vapor_junction.h"
 #include "vapor_bamdev.h"
 #include "vapor_bgzf.h"
@@ -2672,21 +2673,47 @@ extern "C" int vapor_realign_trace(vapor_ctx* ctx, vapor_seqset* set, int64_t n_
 // and the layout of a group's buffer are vapor_polish_plan.h's; here: one upload (pair records, workspace offsets, the pairs' loci,
 // the locus records), per group one clear of its tables, the forward pass, the traceback into run slots that stay on the device,
 // the four kernels and the copies back; one synchronisation at the end.
-extern "C" int vapor_realign_polish(vapor_ctx* ctx, vapor_seqset* set, int64_t n_pairs, const vapor_pair* pairs, int32_t band, int64_t n_loci,
-                                    const int64_t* first, const int64_t* col_off, int32_t* stats, uint8_t* calls, int32_t* sites, uint8_t* ins,
-                                    uint32_t* counts)
+//
+// `--realign-revote` (vapor_revote.h) is the same call with three more kernels a group behind insert_kernel: `rv`
+// names the vote pairs and the outputs of vapor_realign_revote, null for the polish alone, which launches what it always did.
+// The extra checks, the vote pair's record and the pieces a locus adds to its group's buffer are vapor_revote_plan.h's.
+struct RevoteArgs {
+    int64_t n_votes;
+    const vapor_pair* votes;
+    const int64_t* vfirst;
+    int32_t *vout, *lout;
+    const int64_t* spelt_off;
+    uint8_t* spelt;
+};
+
+template <int S>
+static void realign_onto_launch(hipStream_t st, const uint32_t* x4, const vapor_revote::VPair* d_votes, const vapor_revote::VLocus* d_vloci,
+                                const uint32_t* d_buf, const int32_t* d_lout, int64_t n_votes, int32_t band, int32_t* d_vout)
+{
+    hipLaunchKernelGGL((realign_onto_kernel<S>), dim3((unsigned)vapor_realign::grid_of(n_votes)), dim3(64 * vapor_realign::WAVES), 0, st, x4,
+                       d_votes, d_vloci, d_buf, d_lout, (long long)n_votes, (int)band, d_vout);
+}
+
+static int polish_call(const std::string& entry, vapor_ctx* ctx, vapor_seqset* set, int64_t n_pairs, const vapor_pair* pairs, int32_t band,
+                       int64_t n_loci, const int64_t* first, const int64_t* col_off, int32_t* stats, uint8_t* calls, int32_t* sites, uint8_t* ins,
+                       uint32_t* counts, const RevoteArgs* rv)
 {
     namespace ra = vapor_realign;
     namespace tr = vapor_trace;
     namespace pp = vapor_polish;
-    if (const int no = realign_refusal("vapor_realign_polish", ctx, set, n_pairs, pairs != nullptr, band)) return no;
-    if (n_loci < 0 || n_loci > ra::MAX_PAIRS) return fail(VAPOR_E_ARG, "vapor_realign_polish: a locus count outside 0 .. 2^26");
-    if (n_loci == 0 && n_pairs == 0) return VAPOR_OK;
+    namespace vr = vapor_revote;
+    if (const int no = realign_refusal(entry.c_str(), ctx, set, n_pairs, pairs != nullptr, band)) return no;
+    if (n_loci < 0 || n_loci > ra::MAX_PAIRS) return fail(VAPOR_E_ARG, entry + ": a locus count outside 0 .. 2^26");
+    if (rv && (rv->n_votes < 0 || rv->n_votes > ra::MAX_PAIRS)) return fail(VAPOR_E_ARG, entry + ": a vote pair count outside 0 .. 2^26");
+    if (n_loci == 0 && n_pairs == 0 && (!rv || rv->n_votes == 0)) return VAPOR_OK;
     if (!pp::tables_ok(n_pairs, n_loci, first, col_off))
-        return fail(VAPOR_E_ARG, "vapor_realign_polish: first / col_off must ascend from 0, first must end at n_pairs, a locus has at most "
-                                 "VAPOR_MAX_SEQ_LEN columns");
+        return fail(VAPOR_E_ARG, entry + ": first / col_off must ascend from 0, first must end at n_pairs, a locus has at most "
+                                         "VAPOR_MAX_SEQ_LEN columns");
+    if (rv && !vr::vfirst_ok(rv->n_votes, n_loci, rv->vfirst)) return fail(VAPOR_E_ARG, entry + ": vfirst must ascend from 0 to n_votes");
+    if (rv && rv->spelt && !vr::spelt_off_ok(n_loci, rv->spelt_off)) return fail(VAPOR_E_ARG, entry + ": spelt_off must ascend from 0");
     if (n_loci == 0) return VAPOR_OK;
-    if (!stats || !sites || !ins || (col_off[n_loci] && !calls)) return fail(VAPOR_E_ARG, "vapor_realign_polish: null output");
+    if (!stats || !sites || !ins || (col_off[n_loci] && !calls)) return fail(VAPOR_E_ARG, entry + ": null output");
+    if (rv && (!rv->lout || (rv->n_votes && (!rv->votes || !rv->vout)))) return fail(VAPOR_E_ARG, entry + ": null output");
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     const int S = ra::lane_width(band);
@@ -2712,8 +2739,39 @@ extern "C" int vapor_realign_polish(vapor_ctx* ctx, vapor_seqset* set, int64_t n
             cap[(size_t)g] = std::max(cap[(size_t)g], pp::run_cap(recs[(size_t)t]));
         }
     }
+    // the re-vote's loci and vote pairs: a locus's allele is its pairs' seq2, else that of its first vote pair that fits its columns
+    const size_t nv = rv ? (size_t)rv->n_votes : 0;
+    std::vector<vr::VLocus> vloci(rv ? nl : 0);
+    std::vector<vr::VPair> vrecs(nv);
+    std::vector<int64_t> extra(rv ? nl : 0), spans(rv ? nl : 0);
+    if (rv) {
+        const auto len_of = [&](int32_t s) { return set->h[(size_t)s].len; };
+        const auto chunk_of = [&](int32_t s) { return set->h[(size_t)s].chunk0; };
+        for (int64_t g = 0; g < n_loci; ++g) {
+            const int64_t a = first[g], b = first[g + 1], va = rv->vfirst[g], vb = rv->vfirst[g + 1], span = col_off[g + 1] - col_off[g];
+            vr::VLocus& vl = vloci[(size_t)g];
+            vl = vr::VLocus{};
+            vl.status = loci[(size_t)g].status;
+            int64_t allele = -1;
+            if (!vl.status && b > a) allele = pairs[a].seq2;
+            for (int64_t t = va; t < vb && !vl.status && allele < 0; ++t)
+                if (!ra::pair_status(rv->votes[t], set->n, len_of) && (int64_t)len_of(rv->votes[t].seq2) == span) allele = rv->votes[t].seq2;
+            if (!vl.status && allele < 0) vl.status = VAPOR_E_ARG;
+            if (!vl.status) {
+                vl.word2 = (uint64_t)chunk_of((int32_t)allele) * 4u;
+                vl.cap = (int32_t)vr::spelt_cap(span);
+                vl.short_slot = rv->spelt && !vr::slot_ok(rv->spelt_off[g + 1] - rv->spelt_off[g], span);
+                extra[(size_t)g] = vr::locus_extra(span);
+            }
+            spans[(size_t)g] = span;
+            for (int64_t t = va; t < vb; ++t) {
+                vrecs[(size_t)t] = vr::vote_record(rv->votes[t], set->n, allele, 0, len_of, chunk_of);
+                if (vl.status) vrecs[(size_t)t].status = vl.status;       // (the pairs of a refused locus say why)
+            }
+        }
+    }
     std::vector<pp::Group> groups;
-    const int64_t most = pp::plan_groups(n_loci, first, col_off, twords.data(), cap.data(), ctx->trace_budget, groups);
+    const int64_t most = pp::plan_groups(n_loci, first, col_off, twords.data(), cap.data(), ctx->trace_budget, groups, rv ? extra.data() : nullptr);
     // the pairs' workspace offsets, their loci and the loci's columns, relative to their group (the two trace kernels are launched
     // with the group's pointers and t0 = 0)
     std::vector<uint64_t> off(np, 0);
@@ -2727,18 +2785,41 @@ extern "C" int vapor_realign_polish(vapor_ctx* ctx, vapor_seqset* set, int64_t n
         for (int64_t g = gr.locus0; g < gr.locus1; ++g) {
             loci[(size_t)g].col0 = col_off[g] - col_off[gr.locus0];
             for (int64_t t = first[g]; t < first[g + 1]; ++t) pair_locus[(size_t)t] = (int32_t)(g - gr.locus0);
+            if (rv)
+                for (int64_t t = rv->vfirst[g]; t < rv->vfirst[g + 1]; ++t) vrecs[(size_t)t].locus = (int32_t)(g - gr.locus0);
         }
     }
-    const size_t b_rec = sizeof(ra::RPair) * np, b_off = sizeof(uint64_t) * np, b_loc = sizeof(pp::PLocus) * nl, b_pl = sizeof(int32_t) * np;
-    std::vector<uint8_t> up(b_rec + b_off + b_loc + b_pl);              // (the upload reads it: declared before the owners)
+    // the re-vote's pieces inside every group's buffer, and where a group's stagings land in the host copy the spelt output is dealt from
+    std::vector<int64_t> stage_base(rv ? groups.size() : 0), stage_words(rv ? groups.size() : 0), stage_host(rv ? groups.size() : 0);
+    int64_t staged_words = 0;
+    for (size_t k = 0; rv && k < groups.size(); ++k) {
+        const pp::Group& gr = groups[k];
+        const size_t l0 = (size_t)gr.locus0;
+        const int64_t gl = gr.locus1 - gr.locus0;
+        vr::place(gr.extra_off, gl, spans.data() + l0, extra.data() + l0, vloci.data() + l0, stage_base[k]);
+        stage_words[k] = gl ? vloci[l0].plane_off - stage_base[k] : 0;
+        stage_host[k] = staged_words;
+        if (rv->spelt) staged_words += stage_words[k];
+    }
+    std::vector<uint32_t> staged((size_t)staged_words);                 // (the copies back write it: declared before the owners)
+    const size_t b_rec = sizeof(ra::RPair) * np, b_off = sizeof(uint64_t) * np, b_loc = sizeof(pp::PLocus) * nl, b_pl = (sizeof(int32_t) * np + 7) / 8 * 8;
+    const size_t b_vl = sizeof(vr::VLocus) * vloci.size(), b_vp = sizeof(vr::VPair) * nv;
+    std::vector<uint8_t> up(b_rec + b_off + b_loc + b_pl + b_vl + b_vp);     // (the upload reads it: declared before the owners)
     memcpy(up.data(), recs.data(), b_rec);
     memcpy(up.data() + b_rec, off.data(), b_off);
     memcpy(up.data() + b_rec + b_off, loci.data(), b_loc);
-    memcpy(up.data() + b_rec + b_off + b_loc, pair_locus.data(), b_pl);
+    memcpy(up.data() + b_rec + b_off + b_loc, pair_locus.data(), sizeof(int32_t) * np);
+    if (b_vl) memcpy(up.data() + b_rec + b_off + b_loc + b_pl, vloci.data(), b_vl);
+    if (b_vp) memcpy(up.data() + b_rec + b_off + b_loc + b_pl + b_vl, vrecs.data(), b_vp);
     CallScope sc(ctx, st);
     Block<uint8_t> d_up(sc);
     Block<uint32_t> d_buf(sc);
     Block<int32_t> d_head(sc);
+    Block<int32_t> d_vout(sc), d_lout(sc);
+    if (rv) {
+        HIPCHK(d_vout.ensure(sizeof(int32_t) * vr::VOUT * std::max<size_t>(nv, 1)));
+        HIPCHK(d_lout.ensure(sizeof(int32_t) * vr::LOUT * nl));
+    }
     HIPCHK(d_up.ensure(up.size()));
     HIPCHK(d_buf.ensure(sizeof(uint32_t) * (size_t)std::max<int64_t>(most, 64)));
     HIPCHK(d_head.ensure(sizeof(int32_t) * tr::HEAD * std::max<size_t>(np, 1)));
@@ -2747,6 +2828,8 @@ extern "C" int vapor_realign_polish(vapor_ctx* ctx, vapor_seqset* set, int64_t n
     const uint64_t* d_off = reinterpret_cast<const uint64_t*>(d_up.p + b_rec);
     const pp::PLocus* d_loci = reinterpret_cast<const pp::PLocus*>(d_up.p + b_rec + b_off);
     const int32_t* d_pl = reinterpret_cast<const int32_t*>(d_up.p + b_rec + b_off + b_loc);
+    const vr::VLocus* d_vloci = reinterpret_cast<const vr::VLocus*>(d_up.p + b_rec + b_off + b_loc + b_pl);
+    const vr::VPair* d_votes = reinterpret_cast<const vr::VPair*>(d_up.p + b_rec + b_off + b_loc + b_pl + b_vl);
     for (const pp::Group& gr : groups) {
         const int64_t count = gr.pair1 - gr.pair0, gl = gr.locus1 - gr.locus0;
         uint32_t* const b = d_buf.p;
@@ -2786,6 +2869,26 @@ extern "C" int vapor_realign_polish(vapor_ctx* ctx, vapor_seqset* set, int64_t n
                                (const uint32_t*)g_insb, g_stats, g_sites, g_ins);
             HIPCHK(hipGetLastError());
         }
+        if (rv) {
+            const size_t k = (size_t)(&gr - groups.data());
+            const vr::VLocus* gvl = d_vloci + gr.locus0;
+            int32_t* glout = d_lout.p + vr::LOUT * gr.locus0;
+            hipLaunchKernelGGL(spell_kernel, dim3((unsigned)gl), dim3(CONSENSUS_THREADS), 0, st, (const uint32_t*)set->d_x4, gloc, gvl,
+                               (const uint8_t*)g_calls, (const int32_t*)g_sites, (const uint8_t*)g_ins, b, glout);
+            HIPCHK(hipGetLastError());
+            hipLaunchKernelGGL(spell_pack_kernel, dim3((unsigned)gl), dim3(CONSENSUS_THREADS), 0, st, gvl, b, (const int32_t*)glout);
+            HIPCHK(hipGetLastError());
+            const int64_t v0 = rv->vfirst[gr.locus0], n_gv = rv->vfirst[gr.locus1] - v0;
+            if (n_gv > 0) {
+                with_lane_width(band, [&](auto W) {
+                    realign_onto_launch<W()>(st, set->d_x4, d_votes + v0, gvl, b, glout, n_gv, band, d_vout.p + vr::VOUT * v0);
+                });
+                HIPCHK(hipGetLastError());
+            }
+            if (rv->spelt && stage_words[k])
+                HIPCHK(hipMemcpyAsync(staged.data() + stage_host[k], b + stage_base[k], sizeof(uint32_t) * (size_t)stage_words[k],
+                                      hipMemcpyDeviceToHost, st));
+        }
         const size_t c0 = (size_t)col_off[gr.locus0], l0 = (size_t)gr.locus0;
         if (gr.cols) HIPCHK(hipMemcpyAsync(calls + c0, g_calls, (size_t)gr.cols, hipMemcpyDeviceToHost, st));
         if (gr.cols && counts)
@@ -2794,9 +2897,39 @@ extern "C" int vapor_realign_polish(vapor_ctx* ctx, vapor_seqset* set, int64_t n
         HIPCHK(hipMemcpyAsync(sites + pp::SITE_WORDS * l0, g_sites, sizeof(int32_t) * pp::SITE_WORDS * (size_t)gl, hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(ins + 4 * pp::INS_WORDS * l0, g_ins, 4 * (size_t)pp::INS_WORDS * (size_t)gl, hipMemcpyDeviceToHost, st));
     }
+    if (rv) {
+        if (nv) HIPCHK(hipMemcpyAsync(rv->vout, d_vout.p, sizeof(int32_t) * vr::VOUT * nv, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(rv->lout, d_lout.p, sizeof(int32_t) * vr::LOUT * nl, hipMemcpyDeviceToHost, st));
+    }
     HIPCHK(hipStreamSynchronize(st));
     sc.settled();
+    // the spelt codes, dealt to the caller's slots: plen bytes of every locus that was spelt and whose slot holds them
+    for (size_t k = 0; rv && rv->spelt && k < groups.size(); ++k) {
+        const pp::Group& gr = groups[k];
+        for (int64_t g = gr.locus0; g < gr.locus1; ++g) {
+            const vr::VLocus& vl = vloci[(size_t)g];
+            if (vl.status || vl.short_slot) continue;
+            const int64_t plen = std::min<int64_t>(rv->lout[vr::LOUT * g + vr::L_PLEN], vl.cap);
+            if (plen > 0) memcpy(rv->spelt + rv->spelt_off[g], reinterpret_cast<const uint8_t*>(staged.data() + stage_host[k] + (vl.stage_off - stage_base[k])), (size_t)plen);
+        }
+    }
     return VAPOR_OK;
+}
+
+extern "C" int vapor_realign_polish(vapor_ctx* ctx, vapor_seqset* set, int64_t n_pairs, const vapor_pair* pairs, int32_t band, int64_t n_loci,
+                                    const int64_t* first, const int64_t* col_off, int32_t* stats, uint8_t* calls, int32_t* sites, uint8_t* ins,
+                                    uint32_t* counts)
+{
+    return polish_call("vapor_realign_polish", ctx, set, n_pairs, pairs, band, n_loci, first, col_off, stats, calls, sites, ins, counts, nullptr);
+}
+
+extern "C" int vapor_realign_revote(vapor_ctx* ctx, vapor_seqset* set, int64_t n_pairs, const vapor_pair* pairs, int32_t band, int64_t n_loci,
+                                    const int64_t* first, const int64_t* col_off, int32_t* stats, uint8_t* calls, int32_t* sites, uint8_t* ins,
+                                    uint32_t* counts, int64_t n_votes, const vapor_pair* votes, const int64_t* vfirst, int32_t* vout, int32_t* lout,
+                                    const int64_t* spelt_off, uint8_t* spelt)
+{
+    const RevoteArgs rv{n_votes, votes, vfirst, vout, lout, spelt_off, spelt};
+    return polish_call("vapor_realign_revote", ctx, set, n_pairs, pairs, band, n_loci, first, col_off, stats, calls, sites, ins, counts, &rv);
 }
 
 // `--realign-junction` (vapor_junction.h): the one jump between the two sequences of every pair.  The checks, the

@@ -85,7 +85,8 @@ inline int locus_status(const vapor_realign::RPair* recs, int64_t a, int64_t b, 
 // A group: consecutive whole loci, and where its pieces stand in the group's buffer, in dwords.  The trace rows come first (the
 // pairs' offsets are relative to it), then the run slots - traceback_kernel's slots are one size a launch, so every pair of the
 // group gets the group's largest n + m + 1 -, then everything that starts at zero (`zero_off` .. `words`): the columns' counters,
-// their site slots and call bytes, and the loci's tables.
+// their site slots and call bytes, and the loci's tables, and behind those `extra` dwords that a caller adds for its own pieces
+// (vapor_realign_revote's, vapor_revote_plan.h; none for the polish alone).
 struct Group {
     int64_t locus0, locus1;    // loci of the group
     int64_t pair0, pair1;      // their pairs
@@ -93,6 +94,7 @@ struct Group {
     int64_t cap_runs;          // words of a run slot
     int64_t trace_words;
     int64_t runs_off, zero_off, counts_off, slot_off, calls_off, stats_off, sites_off, ins_off, insb_off, words;
+    int64_t extra, extra_off;  // the caller's own dwords (a multiple of four) and where they start
 };
 
 inline int64_t calls_words(int64_t cols) { return (cols + 3) / 4; }
@@ -111,16 +113,18 @@ inline void lay_out(Group& g)
     g.sites_off = g.stats_off + STATS * nl;
     g.ins_off = g.sites_off + SITE_WORDS * nl;
     g.insb_off = g.ins_off + INS_WORDS * nl;
-    g.words = g.insb_off + INSB_WORDS * nl;
+    g.extra_off = g.insb_off + INSB_WORDS * nl;
+    g.words = g.extra_off + g.extra;
 }
 
 // The groups of a call.  trace_words[g] (0 for a refused locus) and cap[g] (the largest run_cap of the locus's pairs, 1 without
 // one that is served) describe locus g; first / col_off are the call's tables.  A locus joins the open group while the group's
 // buffer stays inside the budget; a group always takes at least one locus, so a single locus whose tables go past the budget
 // (its rows alone do not: locus_status) still runs.  ws_off[t]: the first trace dword of pair t inside its group (the caller
-// fills it from the pairs' own words).  Returns the dwords of the largest group.
+// fills it from the pairs' own words).  extra[g] (may be null: none): the dwords locus g adds to its group's buffer beside the
+// polish's own, charged to the budget like them.  Returns the dwords of the largest group.
 inline int64_t plan_groups(int64_t n_loci, const int64_t* first, const int64_t* col_off, const int64_t* trace_words, const int64_t* cap,
-                           int64_t budget, std::vector<Group>& groups)
+                           int64_t budget, std::vector<Group>& groups, const int64_t* extra = nullptr)
 {
     const int64_t limit = vapor_trace::budget_of(budget) / 4;
     groups.clear();
@@ -137,6 +141,7 @@ inline int64_t plan_groups(int64_t n_loci, const int64_t* first, const int64_t* 
             next.cols = col_off[h + 1] - col_off[g];
             next.trace_words = cur.trace_words + trace_words[h];
             next.cap_runs = cap[h] > cur.cap_runs ? cap[h] : cur.cap_runs;
+            next.extra = cur.extra + (extra ? extra[h] : 0);
             lay_out(next);
             if (next.words > limit && h > g) break;
             cur = next;

@@ -603,13 +603,16 @@ class Realign:
     allele it fits; `name`: the locus as the files spell it.  `polish` (`--realign-polish`; off unless asked): the
     payload also carries `.polish`, the consensus of the ALT voters on the alt allele.  `junction` (`--realign-junction`, DESIGN.md
     4.26; off unless asked, and only with `polish`): the payload also carries `.junction`, the one jump of the polished allele
-    beside that of the call's."""
-    __slots__ = ("ref_seq", "alt_seq", "reads", "name", "trace", "polish", "junction")
+    beside that of the call's.  `revote` (`--realign-revote`; off, and only with `polish`): an attribute the
+    wrapper sets on the request it makes, not an argument - the constructor's parameters stay the seven they were -; the payload
+    then also carries `.revote`, every read's distance to the polished allele."""
+    __slots__ = ("ref_seq", "alt_seq", "reads", "name", "trace", "polish", "junction", "revote")
 
     def __init__(self, ref_seq, alt_seq, reads, name=None, trace=False, polish=False, junction=False):
         self.ref_seq, self.alt_seq, self.reads, self.name, self.trace = ref_seq, alt_seq, reads, name, bool(trace)
         self.polish = bool(polish)
         self.junction = bool(junction)
+        self.revote = False
 
 
 class Realigned(list):
@@ -641,7 +644,13 @@ def vapor_realign_junction(name, trace, driver, *args):
     return (yield from _realign(name if trace else None, bool(trace), driver, args, True, True))
 
 
-def _realign(name, trace, driver, args, polish=False, junction=False):
+def vapor_realign_revote(name, trace, junction, driver, *args):
+    """`--realign --realign-polish --realign-revote`: vapor_realign_polish whose Realign request asks for the second vote too,
+    and with `junction` (`--realign-junction` as well) for the junction."""
+    return (yield from _realign(name if trace else None, bool(trace), driver, args, True, bool(junction), True))
+
+
+def _realign(name, trace, driver, args, polish=False, junction=False, revote=False):
     gen = driver(*args)
     last = None
     try:
@@ -659,8 +668,10 @@ def _realign(name, trace, driver, args, polish=False, junction=False):
         scores = fin.value
     out = Realigned(scores if scores is not None else [])
     if last is not None:
-        out.realign = yield (Realign(last.ref_seq, last.alt_seq, last.reads, name, True, polish, junction) if trace else
-                             Realign(last.ref_seq, last.alt_seq, last.reads, polish=polish, junction=junction))
+        req = (Realign(last.ref_seq, last.alt_seq, last.reads, name, True, polish, junction) if trace else
+               Realign(last.ref_seq, last.alt_seq, last.reads, polish=polish, junction=junction))
+        req.revote = bool(revote)
+        out.realign = yield req
     return out
 
 

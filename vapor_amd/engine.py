@@ -780,6 +780,54 @@ class Engine:
                    L.ptr(counts, ctypes.c_uint32) if want_counts else None))
         return stats[:ng], calls[:cols], sites[:ng], ins[:ng], counts[:cols] if want_counts else None
 
+    # ---- `--realign-revote`: every read against the polished allele ----
+    def realign_revote_available(self) -> bool:
+        """Whether the loaded library has vapor_realign_revote (the CPU twin of the C ABI has not)."""
+        return self._available("vapor_realign_revote")
+
+    def realign_revote(self, seqset: SeqSet, pairs: np.ndarray, band: int, first, col_off, votes: np.ndarray, vfirst,
+                       want_counts: bool = False, want_spelt: bool = False, spelt_off=None):
+        """(stats, calls, sites, ins, counts, vout, lout, spelt_off, spelt) of every locus (vapor_realign_revote): realign_polish's
+        five, bit for bit, and the second alignment behind them.  The vote pairs of locus g are votes[vfirst[g] .. vfirst[g + 1]),
+        seq1 the read, seq2 the locus's allele, off2 in the called allele's columns.  vout (n_votes, 4) int32, a row {d_pol,
+        status, off2', m'}; lout (n_loci, 4) int32, a row {vstatus, plen, 0, 0} (revote.statement says what they hold).  With
+        want_spelt, spelt is a uint8 array that holds the plen codes of locus g from spelt_off[g] on - slots of the largest
+        polished allele a locus can have unless `spelt_off` gives others -; else both are None.
+        NotImplementedError where the library has no such entry: there is no other route."""
+        from . import polish
+        fn = self._wide_entry("vapor_realign_revote", "re-vote kernels (--realign-revote)")
+        pairs = np.ascontiguousarray(pairs, dtype=L.PAIR_DTYPE)
+        votes = np.ascontiguousarray(votes, dtype=L.PAIR_DTYPE)
+        fl = np.ascontiguousarray(first, dtype=np.int64)
+        co = np.ascontiguousarray(col_off, dtype=np.int64)
+        vf = np.ascontiguousarray(vfirst, dtype=np.int64)
+        if len(fl) != len(co) or len(fl) != len(vf) or len(fl) < 1:
+            raise ValueError("realign_revote: first, col_off and vfirst hold one entry a locus and one more")
+        n, nv, ng = len(pairs), len(votes), len(fl) - 1
+        cols = max(int(co[-1]), 0)
+        stats = np.zeros((max(ng, 1), 8), dtype=np.int32)
+        calls = np.zeros(max(cols, 1), dtype=np.uint8)
+        sites = np.zeros((max(ng, 1), polish.MAX_SITES, 2), dtype=np.int32)
+        ins = np.zeros((max(ng, 1), polish.MAX_SITES, polish.RMAX), dtype=np.uint8)
+        counts = np.zeros((max(cols, 1), 8), dtype=np.uint32) if want_counts else None
+        vout = np.zeros((max(nv, 1), 4), dtype=np.int32)
+        lout = np.zeros((max(ng, 1), 4), dtype=np.int32)
+        so = spelt = None
+        if want_spelt:
+            if spelt_off is None:
+                span = np.diff(co)
+                spelt_off = np.concatenate(([0], np.cumsum(span + polish.RMAX * np.minimum(span, polish.MAX_SITES))))
+            so = np.ascontiguousarray(spelt_off, dtype=np.int64)
+            if len(so) != len(fl):
+                raise ValueError("realign_revote: spelt_off holds one entry a locus and one more")
+            spelt = np.zeros(max(int(so.max()), 1), dtype=np.uint8)
+        L.check(fn(self._ctx, seqset._h, n, pairs.ctypes.data if n else None, int(band), ng, L.ptr(fl, ctypes.c_int64), L.ptr(co, ctypes.c_int64),
+                   L.ptr(stats, ctypes.c_int32), L.ptr(calls, ctypes.c_uint8), L.ptr(sites, ctypes.c_int32), L.ptr(ins, ctypes.c_uint8),
+                   L.ptr(counts, ctypes.c_uint32) if want_counts else None, nv, votes.ctypes.data if nv else None, L.ptr(vf, ctypes.c_int64),
+                   L.ptr(vout, ctypes.c_int32), L.ptr(lout, ctypes.c_int32), L.ptr(so, ctypes.c_int64) if want_spelt else None,
+                   L.ptr(spelt, ctypes.c_uint8) if want_spelt else None))
+        return (stats[:ng], calls[:cols], sites[:ng], ins[:ng], counts[:cols] if want_counts else None, vout[:nv], lout[:ng], so, spelt)
+
     # ---- `--realign-junction`: the one jump between the two sequences of a pair (DESIGN.md 4.26) ----
     def realign_junction_available(self) -> bool:
         """Whether the loaded library has vapor_realign_junction (the CPU twin of the C ABI has not)."""

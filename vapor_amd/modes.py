@@ -5,7 +5,8 @@ its own module - refine.py, phase.py, bothends.py, depth.py, signature.py, links
 depth.py to support.py also say how their regions are read (their reader surface), and the parser states the rule once (cli.MODE_OPTIONS)."""
 from __future__ import annotations
 
-from . import bothends, depth, junction, links, phase, polish, realign, signature, support
+from . import bothends, depth, junction, links, phase, polish, realign, revote, signature, support
+from . import junction as _junction            # (realign_revote's `junction` argument hides the module's name)
 from . import refine as _refine
 
 
@@ -27,6 +28,7 @@ class Mode:
     sink = None
     polish = False                             # (`--realign-polish`: the Realign requests ask for the consensus too)
     junction = False                           # (`--realign-junction`: ... and for the one jump of the polished allele)
+    revote = False                             # (`--realign-revote`: ... and for every read's distance to the polished allele)
 
     def __init__(self, name, src, attr, keys=None, skip_dot=True, phased=False, margin_step=None, ci_of=None):
         self.name, self.attr, self.skip_dot, self.phased = name, attr, skip_dot, phased
@@ -73,4 +75,15 @@ def realign_junction(sink=None) -> Mode:
     m.sink = sink
     m.polish = True
     m.junction = True
+    return m
+
+
+def realign_revote(sink=None, junction=False) -> Mode:
+    """`--realign --realign-polish --realign-revote`: realign_polish's columns - with `junction`
+    (`--realign-junction` as well) realign_junction's - followed by revote's eight, with realign_polish's sink."""
+    m = Mode("realign", revote.over(_junction if junction else polish), "realign")
+    m.sink = sink
+    m.polish = True
+    m.junction = bool(junction)
+    m.revote = True
     return m

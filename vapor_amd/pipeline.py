@@ -571,7 +571,7 @@ def realign_requests(engine, reqs: Sequence[object]) -> List[object]:
         if any(r.trace for r in reqs):
             _realign_traces(engine, ss, reqs, out, pairs, d, first)
         if any(r.polish for r in reqs):
-            _realign_polish(engine, ss, reqs, out, pairs, first)
+            _realign_polish(engine, ss, reqs, out, pairs, first, d)
     finally:
         ss.close()
     if any(r.junction for r in reqs):
@@ -619,26 +619,45 @@ def _realign_traces(engine, ss, reqs, out, pairs, d, first) -> None:
         out[t].traces.reads.append((x[0], int(x[1]), int(d[a + 2 * k]), int(d[a + 2 * k + 1]), i_end, j_end, rr if status == 0 else []))
 
 
-def _realign_polish(engine, ss, reqs, out, pairs, first) -> None:
+def _realign_polish(engine, ss, reqs, out, pairs, first, d=None) -> None:
     """`--realign-polish`: one engine.realign_polish call over the set of the distances' call for the requests
     that ask and have a payload - per request one locus, its pairs the alt pair of every read that votes ALT.  The statistics
     ride on the payload (`.polish`); the polished allele is spelt only where a sink takes it (the request asks for traces and
-    has them).  A request without reads has nothing in the set: its pile is empty, which needs no call."""
-    from . import polish, realign
+    has them).  A request without reads has nothing in the set: its pile is empty, which needs no call.
+    `--realign-revote`: where a request of the batch asks, the one call is engine.realign_revote instead - the
+    same loci and pairs, and as vote pairs the alt pair of every read of a request that asks and has at least MIN_COV voters.
+    What comes back rides on the payload (`.revote`) beside d_ref of the first call (`d`, the distances of `pairs`)."""
+    from . import polish, realign, revote
     pick, pfirst, col_off, who = [], [0], [0], []
+    votes, vfirst = [], [0]
     for t, (r, a) in enumerate(zip(reqs, first[:-1])):
         if not r.polish or out[t] is None:
             continue
         if not r.reads:
             out[t].polish = polish.Polish([0] * 8, str(r.alt_seq) if getattr(out[t], "traces", None) is not None else None)
             continue
-        pick += [a + 2 * k + 1 for k, diff in enumerate(out[t]) if diff >= realign.MARGIN]
+        mine = [a + 2 * k + 1 for k, diff in enumerate(out[t]) if diff >= realign.MARGIN]
+        pick += mine
         pfirst.append(len(pick))
+        if r.revote and len(mine) >= polish.MIN_COV:
+            votes += [a + 2 * k + 1 for k in range(len(out[t]))]
+        vfirst.append(len(votes))
         col_off.append(col_off[-1] + len(r.alt_seq))
         who.append(t)
     if not who:
         return
-    stats, calls, sites, ins, _counts = engine.realign_polish(ss, pairs[np.asarray(pick, dtype=np.int64)], realign.BAND, pfirst, col_off)
+    if any(reqs[t].revote for t in who):
+        stats, calls, sites, ins, _counts, vout, lout, _so, _spelt = engine.realign_revote(
+            ss, pairs[np.asarray(pick, dtype=np.int64)], realign.BAND, pfirst, col_off, pairs[np.asarray(votes, dtype=np.int64)], vfirst)
+        for g, t in enumerate(who):
+            mine = vout[vfirst[g]:vfirst[g + 1]]
+            if reqs[t].revote and len(mine):
+                bad = [int(v[1]) for v in mine if int(v[1]) != 0]
+                a = first[t]
+                out[t].revote = revote.Revote(int(lout[g][0]) or (bad[0] if bad else 0), [int(d[a + 2 * k]) for k in range(len(mine))],
+                                              [int(v[0]) for v in mine])
+    else:
+        stats, calls, sites, ins, _counts = engine.realign_polish(ss, pairs[np.asarray(pick, dtype=np.int64)], realign.BAND, pfirst, col_off)
     for g, t in enumerate(who):
         text = None
         # (the text is spelt for a sink, and for the junction where the polish applies; a locus the entry refuses keeps its
