@@ -222,6 +222,7 @@ def check_output(tmp_path_factory):
     "tables: 2000 calls, refused ones among them",
     "locus status: 3000 loci, every status met",
     "groups: 400 calls, many in several groups",
+    "call plan: 66 calls, every kind of locus, many in several groups; check_args: 172 cases",
     "polish_check: all equal",
 ])
 def test_the_calls_host_plan_against_direct_statements_under_sanitizers(check_output, line):

@@ -283,6 +283,8 @@ def check_output(tmp_path_factory):
     "tables: 2000 calls, refused ones among them",
     "vote pairs: 20000 cases, served and refused ones",
     "groups: 300 calls, many in several groups, the pieces move some cuts",
+    "call plan: 65 calls, every kind of locus and slot, spelt bytes dealt past group 0 and clamped, the polish's share unchanged; "
+    "check_args: 154 cases",
     "revote_check: all equal",
 ])
 def test_the_calls_host_plan_against_direct_statements_under_sanitizers(check_output, line):

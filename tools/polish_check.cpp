@@ -1,9 +1,10 @@
 // polish_check.cpp - the host plan of vapor_realign_polish (vapor_amd/csrc/vapor_polish_plan.h) held to direct statements of its
-// rules, as a program of its own under the address and undefined-behaviour sanitizers (tests/test_polish_cpu.py builds and runs
-// it; no HIP, no device):
+// rules, and the plan of a whole call that vapor_amd/csrc/vapor_polish_call.h puts together from them (the polish alone; the
+// re-vote's share is tools/revote_check.cpp's), as a program of its own under the address and undefined-behaviour sanitizers
+// (tests/test_polish_cpu.py builds and runs it; no HIP, no device):
 //   g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -Iinclude -Ivapor_amd/csrc
 //       tools/polish_check.cpp -o polish_check && ./polish_check
-#include "vapor_polish_plan.h"
+#include "polish_call_world.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -14,18 +15,6 @@
 namespace ra = vapor_realign;
 namespace tr = vapor_trace;
 namespace pp = vapor_polish;
-
-static int g_bad = 0;
-#define CHECK(cond, ...)                                    \
-    do {                                                    \
-        if (!(cond)) {                                      \
-            if (++g_bad <= 20) {                            \
-                std::printf("FAILED %s: ", #cond);          \
-                std::printf(__VA_ARGS__);                   \
-                std::printf("\n");                          \
-            }                                               \
-        }                                                   \
-    } while (0)
 
 int main()
 {
@@ -169,6 +158,93 @@ int main()
             ++n_cases;
         }
         std::printf("groups: %d calls, %s in several groups\n", n_cases, many > 20 ? "many" : "few");
+    }
+    // the plan of a whole call, the polish alone (vapor_polish_call.h): designed loci, then drawn ones at the floor budget - small
+    // calls, and calls large enough for several groups - and at the default
+    {
+        namespace pc = vapor_polish_call;
+        using world::pair_of;
+        world::Met met;
+        {
+            world::World w;
+            const int32_t allele = w.seq(300), other = w.seq(300), read = w.seq(120), wide = w.seq(65535), wide_read = w.seq(65535);
+            w.locus(300, {}, {}, 0);                                                                        // without pairs: served
+            w.locus(300, {pair_of(read, allele, 0), pair_of(-1, allele, 0), pair_of(read, allele, 10)}, {}, 0);      // a refused pair inside
+            w.locus(300, {pair_of(read, allele, 0), pair_of(read, other, 0)}, {}, 0);                       // two seq2
+            w.locus(299, {pair_of(read, allele, 0)}, {}, 0);                                                // columns that are not the allele's length
+            // rows alone past the floor: five pairs of 65 535 rows, 64 dwords a row at band 100 - 84 MB
+            w.locus(65535, std::vector<vapor_pair>(5, pair_of(wide_read, wide, 0)), {}, 0);
+            w.locus(300, {pair_of(read, allele, 0), pair_of(read, allele, 300), pair_of(read, allele, 7)}, {}, 0);
+            const int at_floor[6] = {0, VAPOR_E_ARG, VAPOR_E_ARG, VAPOR_E_ARG, VAPOR_E_NOMEM, 0}, n_served[6] = {0, 0, 0, 0, 0, 3};
+            for (const int64_t budget : {(int64_t)0, tr::BUDGET_DEFAULT}) {
+                const pc::Plan p(w.call(nullptr), w.seqs(), budget);
+                for (int g = 0; g < 6; ++g) {
+                    const int want = budget && g == 4 ? 0 : at_floor[g];
+                    CHECK(p.loci[(size_t)g].status == want && p.loci[(size_t)g].n_pairs == (want ? 0 : g == 4 ? 5 : n_served[g]), "designed locus %d", g);
+                    for (int64_t t = w.first[(size_t)g]; t < w.first[(size_t)g + 1]; ++t)
+                        CHECK(p.recs[(size_t)t].status == want, "pair %lld of designed locus %d", (long long)t, g);
+                }
+                CHECK(p.loci[5].word2 == (uint64_t)(5 * allele + 3) * 4 && p.recs[(size_t)w.first[5] + 1].m == 0, "the served locus");
+                world::hold(w, nullptr, budget, p, met, "designed loci");
+            }
+        }
+        for (int t = 0; t < 64; ++t) {
+            world::World w;
+            const int bands[6] = {1, 31, 100, 256, 300, 512};
+            w.band = bands[t % 6];
+            const bool big = t % 2 == 1;
+            if (t == 5) {                                                                                   // loci, and no pair at all
+                for (int g = 0; g < 9; ++g) w.locus(100 * g, {}, {}, 0);
+            } else
+                world::draw(w, rng, big ? 60 + (int64_t)(rng() % 60) : 1 + (int64_t)(rng() % 30), big);
+            const int64_t budget = t % 8 == 7 ? tr::BUDGET_DEFAULT : (int64_t)(rng() % 2) * tr::BUDGET_FLOOR;
+            const pc::Plan p(w.call(nullptr), w.seqs(), budget);
+            world::hold(w, nullptr, budget, p, met, "a drawn call");
+        }
+        // check_args, the polish's: every way alone, and the earlier of every two
+        const auto fresh = [] {
+            world::World w;
+            const int32_t allele = w.seq(40), read = w.seq(30);
+            w.locus(40, {pair_of(read, allele, 0), pair_of(read, allele, 3)}, {}, 0);
+            w.locus(40, {pair_of(read, allele, 1)}, {}, 0);
+            return w;
+        };
+        const char *null_or_count = "null argument or a pair count outside 0 .. 2^26", *band = "band outside 1 .. VAPOR_MAX_BAND";
+        const char *loci = "a locus count outside 0 .. 2^26", *null_out = "null output";
+        const char* tables = "first / col_off must ascend from 0, first must end at n_pairs, a locus has at most VAPOR_MAX_SEQ_LEN columns";
+        const std::vector<world::Way> ways = {
+            {null_or_count, [](world::World&, pc::Call& c, pc::RevoteArgs&) { c.handles = false; }},
+            {null_or_count, [](world::World&, pc::Call& c, pc::RevoteArgs&) { c.n_pairs = -1; }},
+            {null_or_count, [](world::World&, pc::Call& c, pc::RevoteArgs&) { c.n_pairs = ra::MAX_PAIRS + 1; }},
+            {null_or_count, [](world::World&, pc::Call& c, pc::RevoteArgs&) { c.pairs = nullptr; }},
+            {band, [](world::World&, pc::Call& c, pc::RevoteArgs&) { c.band = 0; }},
+            {band, [](world::World&, pc::Call& c, pc::RevoteArgs&) { c.band = VAPOR_MAX_BAND + 1; }},
+            {loci, [](world::World&, pc::Call& c, pc::RevoteArgs&) { c.n_loci = -1; }},
+            {loci, [](world::World&, pc::Call& c, pc::RevoteArgs&) { c.n_loci = ra::MAX_PAIRS + 1; }},
+            {tables, [](world::World&, pc::Call& c, pc::RevoteArgs&) { c.first = nullptr; }},
+            {tables, [](world::World&, pc::Call& c, pc::RevoteArgs&) { c.col_off = nullptr; }},
+            {tables, [](world::World& w, pc::Call&, pc::RevoteArgs&) { w.first[0] = 1; }},
+            {tables, [](world::World& w, pc::Call&, pc::RevoteArgs&) { w.col_off[1] = w.col_off[2] + 1; }},
+            {tables, [](world::World& w, pc::Call&, pc::RevoteArgs&) { w.first[2] = 4; }},
+            {tables, [](world::World& w, pc::Call&, pc::RevoteArgs&) { w.col_off[2] = 40 + VAPOR_MAX_SEQ_LEN + 1; }},
+            {null_out, [](world::World&, pc::Call& c, pc::RevoteArgs&) { c.stats = nullptr; }},
+            {null_out, [](world::World&, pc::Call& c, pc::RevoteArgs&) { c.sites = nullptr; }},
+            {null_out, [](world::World&, pc::Call& c, pc::RevoteArgs&) { c.ins = nullptr; }},
+            {null_out, [](world::World&, pc::Call& c, pc::RevoteArgs&) { c.calls = nullptr; }},
+        };
+        const int n_args = world::hold_check_args(fresh, ways, false);
+        {
+            bool nothing = false;
+            const pc::Call empty{true, 0, nullptr, 100, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+            CHECK(!pc::check_args(empty, nothing) && nothing, "a call of nothing is in order and has nothing to run");
+            world::World w = fresh();
+            pc::Call c = w.call(nullptr);
+            c.calls = nullptr;                                   // (no columns: no call bytes to write)
+            w.col_off.assign(3, 0);
+            CHECK(!pc::check_args(c, nothing) && !nothing, "loci without columns need no calls");
+        }
+        const bool all_met = met.served > 100 && met.arg > 50 && met.nomem >= 1 && met.no_pairs > 20 && met.several > 10;
+        std::printf("call plan: %d calls, %s; check_args: %d cases\n", met.calls, all_met ? "every kind of locus, many in several groups" : "a kind not met", n_args);
     }
     if (g_bad) {
         std::printf("polish_check: %d FAILED\n", g_bad);

@@ -12,6 +12,7 @@
 #include "vapor_realign_trace.h"
 #include "vapor_polish.h"
 #include "vapor_revote.h"
+#include "vapor_polish_call.h"
 #include "vapor_junction.h"
 #include "vapor_bamdev.h"
 #include "vapor_bgzf.h"
@@ -2560,26 +2561,32 @@ static void with_lane_width(int32_t band, F&& f)
     f(std::integral_constant<int, ra::WIDTHS[K]>{});
 }
 
+// the set as the plan headers take it: its sequences, and the length and first chunk of sequence s
+static auto seqs_of(const vapor_seqset* set)
+{
+    return vapor_polish_call::seqs(set->n, [set](int32_t s) { return set->h[(size_t)s].len; }, [set](int32_t s) { return set->h[(size_t)s].chunk0; });
+}
+
 // the records of a call's pairs over the set: vapor_realign::RPair, or vapor_junction::JPair
 template <typename Rec>
 static std::vector<Rec> pair_records(const vapor_seqset* set, const vapor_pair* pairs, int64_t n_pairs)
 {
-    const auto len_of = [&](int32_t s) { return set->h[(size_t)s].len; };
-    const auto chunk_of = [&](int32_t s) { return set->h[(size_t)s].chunk0; };
+    const auto s = seqs_of(set);
     std::vector<Rec> recs((size_t)n_pairs);
     for (int64_t t = 0; t < n_pairs; ++t) {
-        if constexpr (std::is_same_v<Rec, vapor_junction::JPair>) recs[(size_t)t] = vapor_junction::pair_record(pairs[t], set->n, len_of, chunk_of);
-        else recs[(size_t)t] = vapor_realign::pair_record(pairs[t], set->n, len_of, chunk_of);
+        if constexpr (std::is_same_v<Rec, vapor_junction::JPair>) recs[(size_t)t] = vapor_junction::pair_record(pairs[t], s.n, s.len_of, s.chunk_of);
+        else recs[(size_t)t] = vapor_realign::pair_record(pairs[t], s.n, s.len_of, s.chunk_of);
     }
     return recs;
 }
 
+// a refusal of the plan headers (a code, and the message without the entry's name) as the entry's status
+static int refused(const std::string& entry, const vapor_polish_call::Refusal& no) { return fail(no.code, entry + ": " + no.msg); }
+
 // the refusals of every entry, in their order; args_ok: the pointers a call with pairs needs are there
 static int realign_refusal(const char* entry, const vapor_ctx* ctx, const vapor_seqset* set, int64_t n_pairs, bool args_ok, int32_t band)
 {
-    if (!ctx || !set || n_pairs < 0 || n_pairs > vapor_realign::MAX_PAIRS || (n_pairs && !args_ok))
-        return fail(VAPOR_E_ARG, std::string(entry) + ": null argument or a pair count outside 0 .. 2^26");
-    if (!vapor_realign::band_ok(band)) return fail(VAPOR_E_ARG, std::string(entry) + ": band outside 1 .. VAPOR_MAX_BAND");
+    if (const auto no = vapor_polish_call::realign_args(ctx && set, n_pairs, args_ok, band)) return refused(entry, no);
     return VAPOR_OK;
 }
 
@@ -2636,26 +2643,31 @@ extern "C" int vapor_realign_trace(vapor_ctx* ctx, vapor_seqset* set, int64_t n_
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     const int S = ra::lane_width(band);
-    const size_t np = (size_t)n_pairs, rec_bytes = sizeof(ra::RPair) * np;
+    const size_t np = (size_t)n_pairs;
     const std::vector<ra::RPair> recs = pair_records<ra::RPair>(set, pairs, n_pairs);
     std::vector<int64_t> first;
     std::vector<uint64_t> off;
-    std::vector<uint8_t> up(rec_bytes + sizeof(uint64_t) * np);        // (the upload reads it: declared before the owners)
+    vapor_polish_call::Table<ra::RPair> t_recs;                        // the upload image: the records, then the workspace offsets
+    vapor_polish_call::Table<uint64_t> t_off;
+    vapor_polish_call::Carve carve;
+    carve.take(t_recs, np);
+    carve.take(t_off, np);
+    std::vector<uint8_t> up(carve.off);                                // (the upload reads it: declared before the owners)
     CallScope sc(ctx, st);
     Block<uint8_t> d_up(sc);
     Block<uint32_t> d_ws(sc);
     Block<int32_t> d_head(sc);
     Block<uint32_t> d_runs(sc);
     const int64_t ws_words = tr::plan_groups(recs.data(), n_pairs, band, S, ctx->trace_budget, first, off);
-    memcpy(up.data(), recs.data(), rec_bytes);
-    memcpy(up.data() + rec_bytes, off.data(), sizeof(uint64_t) * np);
+    t_recs.fill(up, recs);
+    t_off.fill(up, off);
     HIPCHK(d_up.ensure(up.size()));
     HIPCHK(d_ws.ensure(sizeof(uint32_t) * (size_t)std::max<int64_t>(ws_words, 64)));
     HIPCHK(d_head.ensure(sizeof(int32_t) * tr::HEAD * np));
     HIPCHK(d_runs.ensure(sizeof(uint32_t) * np * (size_t)cap_runs));
     HIPCHK(hipMemcpyAsync(d_up.p, up.data(), up.size(), hipMemcpyHostToDevice, st));
-    const ra::RPair* d_pairs = reinterpret_cast<const ra::RPair*>(d_up.p);
-    const uint64_t* d_off = reinterpret_cast<const uint64_t*>(d_up.p + rec_bytes);
+    const ra::RPair* d_pairs = t_recs.in(d_up.p);
+    const uint64_t* d_off = t_off.in(d_up.p);
     for (size_t g = 0; g + 1 < first.size(); ++g) {
         const int64_t t0 = first[g], count = first[g + 1] - t0;
         if (count == 0) continue;
@@ -2670,21 +2682,15 @@ extern "C" int vapor_realign_trace(vapor_ctx* ctx, vapor_seqset* set, int64_t n_
 }
 
 // `--realign-polish` (vapor_polish.h): the consensus of every locus's pairs on its allele.  The checks, the groups
-// and the layout of a group's buffer are vapor_polish_plan.h's; here: one upload (pair records, workspace offsets, the pairs' loci,
-// the locus records), per group one clear of its tables, the forward pass, the traceback into run slots that stay on the device,
-// the four kernels and the copies back; one synchronisation at the end.
+// and the layout of a group's buffer are vapor_polish_plan.h's, and the call's plan - every record, every offset, the upload image
+// and the dealing of the spelt bytes - is vapor_polish_call.h's; here: one upload (pair records, workspace offsets, the locus
+// records, the pairs' loci), per group one clear of its tables, the forward pass, the traceback into run slots that stay on the
+// device, the four kernels and the copies back; one synchronisation at the end.
 //
 // `--realign-revote` (vapor_revote.h) is the same call with three more kernels a group behind insert_kernel: `rv`
 // names the vote pairs and the outputs of vapor_realign_revote, null for the polish alone, which launches what it always did.
 // The extra checks, the vote pair's record and the pieces a locus adds to its group's buffer are vapor_revote_plan.h's.
-struct RevoteArgs {
-    int64_t n_votes;
-    const vapor_pair* votes;
-    const int64_t* vfirst;
-    int32_t *vout, *lout;
-    const int64_t* spelt_off;
-    uint8_t* spelt;
-};
+using vapor_polish_call::RevoteArgs;
 
 template <int S>
 static void realign_onto_launch(hipStream_t st, const uint32_t* x4, const vapor_revote::VPair* d_votes, const vapor_revote::VLocus* d_vloci,
@@ -2694,123 +2700,24 @@ static void realign_onto_launch(hipStream_t st, const uint32_t* x4, const vapor_
                        d_votes, d_vloci, d_buf, d_lout, (long long)n_votes, (int)band, d_vout);
 }
 
-static int polish_call(const std::string& entry, vapor_ctx* ctx, vapor_seqset* set, int64_t n_pairs, const vapor_pair* pairs, int32_t band,
-                       int64_t n_loci, const int64_t* first, const int64_t* col_off, int32_t* stats, uint8_t* calls, int32_t* sites, uint8_t* ins,
-                       uint32_t* counts, const RevoteArgs* rv)
+static int polish_call(const std::string& entry, vapor_ctx* ctx, vapor_seqset* set, const vapor_polish_call::Call& c)
 {
     namespace ra = vapor_realign;
     namespace tr = vapor_trace;
     namespace pp = vapor_polish;
     namespace vr = vapor_revote;
-    if (const int no = realign_refusal(entry.c_str(), ctx, set, n_pairs, pairs != nullptr, band)) return no;
-    if (n_loci < 0 || n_loci > ra::MAX_PAIRS) return fail(VAPOR_E_ARG, entry + ": a locus count outside 0 .. 2^26");
-    if (rv && (rv->n_votes < 0 || rv->n_votes > ra::MAX_PAIRS)) return fail(VAPOR_E_ARG, entry + ": a vote pair count outside 0 .. 2^26");
-    if (n_loci == 0 && n_pairs == 0 && (!rv || rv->n_votes == 0)) return VAPOR_OK;
-    if (!pp::tables_ok(n_pairs, n_loci, first, col_off))
-        return fail(VAPOR_E_ARG, entry + ": first / col_off must ascend from 0, first must end at n_pairs, a locus has at most "
-                                         "VAPOR_MAX_SEQ_LEN columns");
-    if (rv && !vr::vfirst_ok(rv->n_votes, n_loci, rv->vfirst)) return fail(VAPOR_E_ARG, entry + ": vfirst must ascend from 0 to n_votes");
-    if (rv && rv->spelt && !vr::spelt_off_ok(n_loci, rv->spelt_off)) return fail(VAPOR_E_ARG, entry + ": spelt_off must ascend from 0");
-    if (n_loci == 0) return VAPOR_OK;
-    if (!stats || !sites || !ins || (col_off[n_loci] && !calls)) return fail(VAPOR_E_ARG, entry + ": null output");
-    if (rv && (!rv->lout || (rv->n_votes && (!rv->votes || !rv->vout)))) return fail(VAPOR_E_ARG, entry + ": null output");
+    bool nothing = false;
+    if (const auto no = vapor_polish_call::check_args(c, nothing)) return refused(entry, no);
+    if (nothing) return VAPOR_OK;
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    const int S = ra::lane_width(band);
-    const size_t np = (size_t)n_pairs, nl = (size_t)n_loci;
-    std::vector<ra::RPair> recs = pair_records<ra::RPair>(set, pairs, n_pairs);
-    // the loci: status, trace words, run cap
-    std::vector<pp::PLocus> loci(nl);
-    std::vector<int64_t> twords(nl), cap(nl);
-    std::vector<int32_t> pair_locus(np);
-    for (int64_t g = 0; g < n_loci; ++g) {
-        const int64_t a = first[g], b = first[g + 1], span = col_off[g + 1] - col_off[g];
-        const int status = pp::locus_status(recs.data(), a, b, span, band, S, ctx->trace_budget, [&](int64_t t) { return pairs[t].seq2; },
-                                            [&](int64_t t) { return (int64_t)set->h[(size_t)pairs[t].seq2].len; }, twords[(size_t)g]);
-        pp::PLocus& lc = loci[(size_t)g];
-        lc = pp::PLocus{};
-        lc.len = (int32_t)span;
-        lc.n_pairs = (int32_t)(status ? 0 : b - a);
-        lc.status = status;
-        lc.word2 = (!status && b > a) ? recs[(size_t)a].word2 : 0;
-        cap[(size_t)g] = 1;
-        for (int64_t t = a; t < b; ++t) {
-            if (status) recs[(size_t)t].status = recs[(size_t)t].status ? recs[(size_t)t].status : status;     // (no pair of a refused locus runs)
-            cap[(size_t)g] = std::max(cap[(size_t)g], pp::run_cap(recs[(size_t)t]));
-        }
-    }
-    // the re-vote's loci and vote pairs: a locus's allele is its pairs' seq2, else that of its first vote pair that fits its columns
-    const size_t nv = rv ? (size_t)rv->n_votes : 0;
-    std::vector<vr::VLocus> vloci(rv ? nl : 0);
-    std::vector<vr::VPair> vrecs(nv);
-    std::vector<int64_t> extra(rv ? nl : 0), spans(rv ? nl : 0);
-    if (rv) {
-        const auto len_of = [&](int32_t s) { return set->h[(size_t)s].len; };
-        const auto chunk_of = [&](int32_t s) { return set->h[(size_t)s].chunk0; };
-        for (int64_t g = 0; g < n_loci; ++g) {
-            const int64_t a = first[g], b = first[g + 1], va = rv->vfirst[g], vb = rv->vfirst[g + 1], span = col_off[g + 1] - col_off[g];
-            vr::VLocus& vl = vloci[(size_t)g];
-            vl = vr::VLocus{};
-            vl.status = loci[(size_t)g].status;
-            int64_t allele = -1;
-            if (!vl.status && b > a) allele = pairs[a].seq2;
-            for (int64_t t = va; t < vb && !vl.status && allele < 0; ++t)
-                if (!ra::pair_status(rv->votes[t], set->n, len_of) && (int64_t)len_of(rv->votes[t].seq2) == span) allele = rv->votes[t].seq2;
-            if (!vl.status && allele < 0) vl.status = VAPOR_E_ARG;
-            if (!vl.status) {
-                vl.word2 = (uint64_t)chunk_of((int32_t)allele) * 4u;
-                vl.cap = (int32_t)vr::spelt_cap(span);
-                vl.short_slot = rv->spelt && !vr::slot_ok(rv->spelt_off[g + 1] - rv->spelt_off[g], span);
-                extra[(size_t)g] = vr::locus_extra(span);
-            }
-            spans[(size_t)g] = span;
-            for (int64_t t = va; t < vb; ++t) {
-                vrecs[(size_t)t] = vr::vote_record(rv->votes[t], set->n, allele, 0, len_of, chunk_of);
-                if (vl.status) vrecs[(size_t)t].status = vl.status;       // (the pairs of a refused locus say why)
-            }
-        }
-    }
-    std::vector<pp::Group> groups;
-    const int64_t most = pp::plan_groups(n_loci, first, col_off, twords.data(), cap.data(), ctx->trace_budget, groups, rv ? extra.data() : nullptr);
-    // the pairs' workspace offsets, their loci and the loci's columns, relative to their group (the two trace kernels are launched
-    // with the group's pointers and t0 = 0)
-    std::vector<uint64_t> off(np, 0);
-    for (const pp::Group& gr : groups) {
-        uint64_t used = 0;
-        for (int64_t t = gr.pair0; t < gr.pair1; ++t) {
-            const ra::RPair& r = recs[(size_t)t];
-            off[(size_t)t] = used;
-            if (!r.status) used += (uint64_t)tr::pair_words(ra::rows_walked(r.n, r.m, band), S);
-        }
-        for (int64_t g = gr.locus0; g < gr.locus1; ++g) {
-            loci[(size_t)g].col0 = col_off[g] - col_off[gr.locus0];
-            for (int64_t t = first[g]; t < first[g + 1]; ++t) pair_locus[(size_t)t] = (int32_t)(g - gr.locus0);
-            if (rv)
-                for (int64_t t = rv->vfirst[g]; t < rv->vfirst[g + 1]; ++t) vrecs[(size_t)t].locus = (int32_t)(g - gr.locus0);
-        }
-    }
-    // the re-vote's pieces inside every group's buffer, and where a group's stagings land in the host copy the spelt output is dealt from
-    std::vector<int64_t> stage_base(rv ? groups.size() : 0), stage_words(rv ? groups.size() : 0), stage_host(rv ? groups.size() : 0);
-    int64_t staged_words = 0;
-    for (size_t k = 0; rv && k < groups.size(); ++k) {
-        const pp::Group& gr = groups[k];
-        const size_t l0 = (size_t)gr.locus0;
-        const int64_t gl = gr.locus1 - gr.locus0;
-        vr::place(gr.extra_off, gl, spans.data() + l0, extra.data() + l0, vloci.data() + l0, stage_base[k]);
-        stage_words[k] = gl ? vloci[l0].plane_off - stage_base[k] : 0;
-        stage_host[k] = staged_words;
-        if (rv->spelt) staged_words += stage_words[k];
-    }
-    std::vector<uint32_t> staged((size_t)staged_words);                 // (the copies back write it: declared before the owners)
-    const size_t b_rec = sizeof(ra::RPair) * np, b_off = sizeof(uint64_t) * np, b_loc = sizeof(pp::PLocus) * nl, b_pl = (sizeof(int32_t) * np + 7) / 8 * 8;
-    const size_t b_vl = sizeof(vr::VLocus) * vloci.size(), b_vp = sizeof(vr::VPair) * nv;
-    std::vector<uint8_t> up(b_rec + b_off + b_loc + b_pl + b_vl + b_vp);     // (the upload reads it: declared before the owners)
-    memcpy(up.data(), recs.data(), b_rec);
-    memcpy(up.data() + b_rec, off.data(), b_off);
-    memcpy(up.data() + b_rec + b_off, loci.data(), b_loc);
-    memcpy(up.data() + b_rec + b_off + b_loc, pair_locus.data(), sizeof(int32_t) * np);
-    if (b_vl) memcpy(up.data() + b_rec + b_off + b_loc + b_pl, vloci.data(), b_vl);
-    if (b_vp) memcpy(up.data() + b_rec + b_off + b_loc + b_pl + b_vl, vrecs.data(), b_vp);
+    const RevoteArgs* rv = c.rv;
+    const int64_t* col_off = c.col_off;
+    const int32_t band = c.band;
+    const size_t np = (size_t)c.n_pairs, nl = (size_t)c.n_loci, nv = rv ? (size_t)rv->n_votes : 0;
+    const vapor_polish_call::Plan plan(c, seqs_of(set), ctx->trace_budget);     // (the upload reads its image: declared before the owners)
+    std::vector<uint32_t> staged((size_t)plan.staged_words);                   // (the copies back write it: declared before the owners)
+    const std::vector<pp::Group>& groups = plan.groups;
     CallScope sc(ctx, st);
     Block<uint8_t> d_up(sc);
     Block<uint32_t> d_buf(sc);
@@ -2820,16 +2727,16 @@ static int polish_call(const std::string& entry, vapor_ctx* ctx, vapor_seqset* s
         HIPCHK(d_vout.ensure(sizeof(int32_t) * vr::VOUT * std::max<size_t>(nv, 1)));
         HIPCHK(d_lout.ensure(sizeof(int32_t) * vr::LOUT * nl));
     }
-    HIPCHK(d_up.ensure(up.size()));
-    HIPCHK(d_buf.ensure(sizeof(uint32_t) * (size_t)std::max<int64_t>(most, 64)));
+    HIPCHK(d_up.ensure(plan.image.size()));
+    HIPCHK(d_buf.ensure(sizeof(uint32_t) * (size_t)std::max<int64_t>(plan.most, 64)));
     HIPCHK(d_head.ensure(sizeof(int32_t) * tr::HEAD * std::max<size_t>(np, 1)));
-    HIPCHK(hipMemcpyAsync(d_up.p, up.data(), up.size(), hipMemcpyHostToDevice, st));
-    const ra::RPair* d_pairs = reinterpret_cast<const ra::RPair*>(d_up.p);
-    const uint64_t* d_off = reinterpret_cast<const uint64_t*>(d_up.p + b_rec);
-    const pp::PLocus* d_loci = reinterpret_cast<const pp::PLocus*>(d_up.p + b_rec + b_off);
-    const int32_t* d_pl = reinterpret_cast<const int32_t*>(d_up.p + b_rec + b_off + b_loc);
-    const vr::VLocus* d_vloci = reinterpret_cast<const vr::VLocus*>(d_up.p + b_rec + b_off + b_loc + b_pl);
-    const vr::VPair* d_votes = reinterpret_cast<const vr::VPair*>(d_up.p + b_rec + b_off + b_loc + b_pl + b_vl);
+    HIPCHK(hipMemcpyAsync(d_up.p, plan.image.data(), plan.image.size(), hipMemcpyHostToDevice, st));
+    const ra::RPair* d_pairs = plan.t_recs.in(d_up.p);
+    const uint64_t* d_off = plan.t_off.in(d_up.p);
+    const pp::PLocus* d_loci = plan.t_loci.in(d_up.p);
+    const int32_t* d_pl = plan.t_pair_locus.in(d_up.p);
+    const vr::VLocus* d_vloci = plan.t_vloci.in(d_up.p);
+    const vr::VPair* d_votes = plan.t_vrecs.in(d_up.p);
     for (const pp::Group& gr : groups) {
         const int64_t count = gr.pair1 - gr.pair0, gl = gr.locus1 - gr.locus0;
         uint32_t* const b = d_buf.p;
@@ -2885,17 +2792,17 @@ static int polish_call(const std::string& entry, vapor_ctx* ctx, vapor_seqset* s
                 });
                 HIPCHK(hipGetLastError());
             }
-            if (rv->spelt && stage_words[k])
-                HIPCHK(hipMemcpyAsync(staged.data() + stage_host[k], b + stage_base[k], sizeof(uint32_t) * (size_t)stage_words[k],
+            if (rv->spelt && plan.stage_words[k])
+                HIPCHK(hipMemcpyAsync(staged.data() + plan.stage_host[k], b + plan.stage_base[k], sizeof(uint32_t) * (size_t)plan.stage_words[k],
                                       hipMemcpyDeviceToHost, st));
         }
         const size_t c0 = (size_t)col_off[gr.locus0], l0 = (size_t)gr.locus0;
-        if (gr.cols) HIPCHK(hipMemcpyAsync(calls + c0, g_calls, (size_t)gr.cols, hipMemcpyDeviceToHost, st));
-        if (gr.cols && counts)
-            HIPCHK(hipMemcpyAsync(counts + pp::COUNTERS * c0, g_counts, sizeof(uint32_t) * pp::COUNTERS * (size_t)gr.cols, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(stats + pp::STATS * l0, g_stats, sizeof(int32_t) * pp::STATS * (size_t)gl, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(sites + pp::SITE_WORDS * l0, g_sites, sizeof(int32_t) * pp::SITE_WORDS * (size_t)gl, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(ins + 4 * pp::INS_WORDS * l0, g_ins, 4 * (size_t)pp::INS_WORDS * (size_t)gl, hipMemcpyDeviceToHost, st));
+        if (gr.cols) HIPCHK(hipMemcpyAsync(c.calls + c0, g_calls, (size_t)gr.cols, hipMemcpyDeviceToHost, st));
+        if (gr.cols && c.counts)
+            HIPCHK(hipMemcpyAsync(c.counts + pp::COUNTERS * c0, g_counts, sizeof(uint32_t) * pp::COUNTERS * (size_t)gr.cols, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(c.stats + pp::STATS * l0, g_stats, sizeof(int32_t) * pp::STATS * (size_t)gl, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(c.sites + pp::SITE_WORDS * l0, g_sites, sizeof(int32_t) * pp::SITE_WORDS * (size_t)gl, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(c.ins + 4 * pp::INS_WORDS * l0, g_ins, 4 * (size_t)pp::INS_WORDS * (size_t)gl, hipMemcpyDeviceToHost, st));
     }
     if (rv) {
         if (nv) HIPCHK(hipMemcpyAsync(rv->vout, d_vout.p, sizeof(int32_t) * vr::VOUT * nv, hipMemcpyDeviceToHost, st));
@@ -2903,16 +2810,7 @@ static int polish_call(const std::string& entry, vapor_ctx* ctx, vapor_seqset* s
     }
     HIPCHK(hipStreamSynchronize(st));
     sc.settled();
-    // the spelt codes, dealt to the caller's slots: plen bytes of every locus that was spelt and whose slot holds them
-    for (size_t k = 0; rv && rv->spelt && k < groups.size(); ++k) {
-        const pp::Group& gr = groups[k];
-        for (int64_t g = gr.locus0; g < gr.locus1; ++g) {
-            const vr::VLocus& vl = vloci[(size_t)g];
-            if (vl.status || vl.short_slot) continue;
-            const int64_t plen = std::min<int64_t>(rv->lout[vr::LOUT * g + vr::L_PLEN], vl.cap);
-            if (plen > 0) memcpy(rv->spelt + rv->spelt_off[g], reinterpret_cast<const uint8_t*>(staged.data() + stage_host[k] + (vl.stage_off - stage_base[k])), (size_t)plen);
-        }
-    }
+    if (rv) plan.deal_spelt(staged.data(), rv->lout, rv->spelt_off, rv->spelt);
     return VAPOR_OK;
 }
 
@@ -2920,7 +2818,7 @@ extern "C" int vapor_realign_polish(vapor_ctx* ctx, vapor_seqset* set, int64_t n
                                     const int64_t* first, const int64_t* col_off, int32_t* stats, uint8_t* calls, int32_t* sites, uint8_t* ins,
                                     uint32_t* counts)
 {
-    return polish_call("vapor_realign_polish", ctx, set, n_pairs, pairs, band, n_loci, first, col_off, stats, calls, sites, ins, counts, nullptr);
+    return polish_call("vapor_realign_polish", ctx, set, {ctx && set, n_pairs, pairs, band, n_loci, first, col_off, stats, calls, sites, ins, counts, nullptr});
 }
 
 extern "C" int vapor_realign_revote(vapor_ctx* ctx, vapor_seqset* set, int64_t n_pairs, const vapor_pair* pairs, int32_t band, int64_t n_loci,
@@ -2929,7 +2827,7 @@ extern "C" int vapor_realign_revote(vapor_ctx* ctx, vapor_seqset* set, int64_t n
                                     const int64_t* spelt_off, uint8_t* spelt)
 {
     const RevoteArgs rv{n_votes, votes, vfirst, vout, lout, spelt_off, spelt};
-    return polish_call("vapor_realign_revote", ctx, set, n_pairs, pairs, band, n_loci, first, col_off, stats, calls, sites, ins, counts, &rv);
+    return polish_call("vapor_realign_revote", ctx, set, {ctx && set, n_pairs, pairs, band, n_loci, first, col_off, stats, calls, sites, ins, counts, &rv});
 }
 
 // `--realign-junction` (vapor_junction.h): the one jump between the two sequences of every pair.  The checks, the
