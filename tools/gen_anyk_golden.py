@@ -7,6 +7,12 @@ for the small cases, the count and sha256 of the (j, i) int32 rows for the large
 edit-distance branch (about a minute and a half each at ~110 bp), so the cases run in parallel processes.
 
     python tools/gen_anyk_golden.py [--jobs N]
+
+--designs leaves every case of the file as it is and adds, under names of their own: every k from 1 to 40 that EXACT_K lacks
+(both modes, the same ~200-symbol shape), the last_symbol designs of tests/anyk_designs.py and its eight golden_rounds() pairs
+(k = 41 and 64, D = 64 and 65; a few minutes each in the reference).  A case whose name the file already holds is not run again.
+
+    python tools/gen_anyk_golden.py --designs [--jobs N]
 """
 from __future__ import annotations
 
@@ -139,6 +145,41 @@ def kmerhits_specs():
     return out
 
 
+def design_specs():
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import anyk_designs as ad
+    rng = np.random.default_rng(4343)
+    out = []
+    for k in range(1, 41):
+        if k in EXACT_K:
+            continue
+        a = synth.random_dna(rng, int(rng.integers(120, 220)))
+        b = _mut(rng, a[10:]) + synth.revcomp(a[:60])
+        for inv in (True, False):
+            out.append(("exact_k%d_%s" % (k, "inv" if inv else "fwd"), k, a, b, inv))
+    for p in ad.last_symbol():
+        out.append(("last_symbol_%s" % p.name, p.k, p.s1, p.s2, not p.forward))
+    for p in ad.golden_rounds():
+        assert len(p.s1) <= 200 and len(p.s2) <= 200, p.name
+        out.append((p.name, p.k, p.s1, p.s2, not p.forward))
+    return out
+
+
+def add_designs(n_jobs):
+    import gzip
+    import json
+    with gzip.open(os.path.join(ROOT, "tests", "golden", NAME), "rt") as f:
+        gold = json.load(f)
+    have = {c["name"] for c in gold["cases"]}
+    specs = sorted((s for s in design_specs() if s[0] not in have), key=lambda s: -s[1])      # the slow ones (k > 40) first
+    with mp.get_context("fork").Pool(n_jobs) as pool:
+        res = pool.map(job_kmerhits, specs, chunksize=1)
+    order = {s[0]: t for t, s in enumerate(design_specs())}
+    gold["cases"] += sorted(res, key=lambda c: order[c["name"]])
+    gg.dump(NAME, gold)
+    print("added %d cases" % len(res))
+
+
 def scorer_specs():
     rng = np.random.default_rng(5151)
     out = []
@@ -174,7 +215,10 @@ def subkeys_cases():
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--jobs", type=int, default=min(8, os.cpu_count() or 1))
+    ap.add_argument("--designs", action="store_true", help="add the designed cases to the file, leaving its cases as they are")
     a = ap.parse_args()
+    if a.designs:
+        return add_designs(a.jobs)
     jobs = [(job_kmerhits, s) for s in kmerhits_specs()] + [(job_scorer, s) for s in scorer_specs()]
     # the slow ones (k > 40) first, so that the pool's tail is short
     order = sorted(range(len(jobs)), key=lambda t: -(jobs[t][1][1] if jobs[t][0] is job_kmerhits else

@@ -236,7 +236,8 @@ __device__ __forceinline__ int anyk_lev(const unsigned long long* peq, const uin
 // One wave per allele k-mer j (4 per workgroup; this launch: j0 .. j1 - 1): the keys within distance k / 10 of it, 64 at a time
 // in rank order.  EMIT = false: cnt[j] = dots of j; EMIT = true: the dots at off[j], in order (a wave prefix of the lanes' list
 // lengths).  The host cuts a pair into launches of at most ANYK_EDIT_PAIRS (query, key) distance computations (~0.1 s each), so
-// that a long pair does not hold the device in one kernel.
+// that a long pair does not hold the device in one kernel; vapor_set_param(ctx, "anyk_edit_pairs", v) puts another number in its
+// place (the tests' way to the launches behind the first at small sizes).
 constexpr int ANYK_EDIT_WAVES = 4;
 constexpr long long ANYK_EDIT_PAIRS = 1ll << 31;
 template <bool EMIT>

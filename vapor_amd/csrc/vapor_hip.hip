@@ -110,6 +110,7 @@ struct vapor_ctx {
     int clean_order = 1;                       // 1: the clean workgroups are dealt out longest pair first (clean_order); 0: in pair order
     int clean_fit = 1;                         // 1: after a blocking run the clean kernel's LDS copy is sized for the records the pairs really hold
     int64_t trace_budget = vapor_trace::BUDGET_DEFAULT;      // bytes of vapor_realign_trace's workspace (never below BUDGET_FLOOR)
+    int64_t anyk_edit_pairs = ANYK_EDIT_PAIRS;  // (query, key) distances one launch of the any-k route's edit pass may hold (anyk_edit_launch)
     int stage_threads = 3;                     // host threads that copy a large upload into the pinned staging buffer (measured:
                                                // two to four are as fast as it gets, more are slower - tools/upload_sweep.py)
     bool attrs_set = false;
@@ -479,6 +480,11 @@ extern "C" int vapor_set_param(vapor_ctx* c, const char* name, int64_t v)
     }
     if (!strcmp(name, "trace_budget")) {
         c->trace_budget = vapor_trace::budget_of(v);       // (a lower value is raised to the floor that always holds one pair)
+        return VAPOR_OK;
+    }
+    if (!strcmp(name, "anyk_edit_pairs")) {
+        if (v < 1) return fail(VAPOR_E_ARG, "anyk_edit_pairs out of range");
+        c->anyk_edit_pairs = v;
         return VAPOR_OK;
     }
     if (!strcmp(name, "stage_threads")) {
@@ -2414,16 +2420,17 @@ namespace {
 struct AnykBufs : WideBufs {
     using WideBufs::WideBufs;
     enum { SYM, IDX, CNT, FIRST, OFF, ISF, RUN, RANK, KEYS };
+    long long edit_pairs = ANYK_EDIT_PAIRS;        // the context's "anyk_edit_pairs"
 };
 
 inline size_t anyk_pad(int n) { return ((size_t)n + 16 + 15) & ~(size_t)15; }
 
-// the edit-distance pass over allele k-mers 0 .. nk2 - 1, in launches of at most ANYK_EDIT_PAIRS distances (n entries bound the
-// number of keys)
+// the edit-distance pass over allele k-mers 0 .. nk2 - 1, in launches of at most edit_pairs distances ("anyk_edit_pairs",
+// ANYK_EDIT_PAIRS unless set; n entries bound the number of keys)
 template <bool EMIT>
 void anyk_edit_launch(AnykBufs& x, hipStream_t st, const AnykSrc& src, int n, int nk2, uint32_t* cnt, const long long* off, int2* dots)
 {
-    const long long per = std::max<long long>(ANYK_EDIT_WAVES, ANYK_EDIT_PAIRS / std::max(n, 1) / ANYK_EDIT_WAVES * ANYK_EDIT_WAVES);
+    const long long per = std::max<long long>(ANYK_EDIT_WAVES, x.edit_pairs / std::max(n, 1) / ANYK_EDIT_WAVES * ANYK_EDIT_WAVES);
     for (long long j0 = 0; j0 < nk2; j0 += per) {
         const int j1 = (int)std::min<long long>(nk2, j0 + per);
         hipLaunchKernelGGL((anyk_edit_kernel<EMIT>), dim3((unsigned)((j1 - j0 + ANYK_EDIT_WAVES - 1) / ANYK_EDIT_WAVES)), dim3(64 * ANYK_EDIT_WAVES), 0,
@@ -2493,7 +2500,7 @@ struct AnykRoute {
     hipStream_t st;
     const vapor_seqset* set;
     AnykSrc src{};                                 // of the pair being counted, for its emit pass
-    AnykRoute(CallScope& sc, WideBufs& bufs, const vapor_seqset* s) : b(bufs), x(sc), st(sc.st), set(s) {}
+    AnykRoute(CallScope& sc, WideBufs& bufs, const vapor_seqset* s) : b(bufs), x(sc), st(sc.st), set(s) { x.edit_pairs = sc.ctx->anyk_edit_pairs; }
     hipError_t prepare() { return hipSuccess; }
     bool no_bytes(int32_t q) const                 // a symbol outside the alphabet whose byte was not kept
     {
