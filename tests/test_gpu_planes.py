@@ -16,8 +16,9 @@ pytestmark = pytest.mark.gpu
 
 LENGTHS = (0, 1, 15, 16, 17, 31, 32, 33, 63, 64, 65, 8191, 8192, 8193)
 ALPHABET = b"ACGTacgtNnRrYyKkMmXx-=*"
-# vapor_hip.hip stages an upload on several host threads when its ASCII layout (every sequence in whole 32-byte chunks) holds
-# STAGE_SWITCH_BYTES or more and the set STAGE_SWITCH_SEQS sequences or more
+# the library stages an upload on several host threads when its ASCII layout (every sequence in whole 32-byte chunks) holds
+# STAGE_SWITCH_BYTES or more and the set STAGE_SWITCH_SEQS sequences or more (the constants of these names in
+# vapor_amd/csrc/vapor_seqset_plan.h)
 STAGE_SWITCH_BYTES = 4 << 20
 STAGE_SWITCH_SEQS = 8
 STAGE_THREADS = (1, 2, 3, 5, 12, 13, 64)

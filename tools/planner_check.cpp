@@ -6,7 +6,9 @@
 // are built on purpose.  Nothing here is compared with recorded output of the planner: the tuning constants are free to move.
 // Built and run by tests/test_planner_cpu.py:
 //   g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -Iinclude -Ivapor_amd/csrc tools/planner_check.cpp
+#include "seq_spell.h"
 #include "vapor_planner.h"
+#include "vapor_seqset_plan.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -23,26 +25,9 @@ static long g_case = 0;
 static int rnd(int lo, int hi) { return lo + (int)(rng() % (uint64_t)(hi - lo + 1)); }      // lo .. hi
 static bool one_in(int n) { return rng() % (uint64_t)n == 0; }
 
-// ---- texts ----
-static char comp(char c)
-{
-    switch (c) {
-    case 'A': return 'T'; case 'T': return 'A'; case 'C': return 'G'; case 'G': return 'C';
-    case 'a': return 't'; case 't': return 'a'; case 'c': return 'g'; case 'g': return 'c';
-    default: return c;
-    }
-}
-static std::string revcomp(const std::string& s)
-{
-    std::string r(s.rbegin(), s.rend());
-    for (char& c : r) c = comp(c);
-    return r;
-}
-static std::string upper(std::string s)
-{
-    for (char& c : s) if (c >= 'a' && c <= 'z') c = (char)(c - 32);
-    return s;
-}
+// ---- texts (what segments spell: tools/seq_spell.h) ----
+using seq_spell::revcomp;
+using seq_spell::upper;
 // `lower`, `odd`: one symbol in that many is lower-case / an N or an X (0: none)
 static std::string dna(int n, int lower, int odd)
 {
@@ -55,7 +40,8 @@ static std::string dna(int n, int lower, int odd)
     return s;
 }
 
-// A sequence set as vapor_seqset_create_derived lays it out on the host, with the texts its sequences spell.
+// A sequence set as vapor_seqset_create_derived lays it out on the host (vapor_seqset_plan.h's Layout, from the lengths and the
+// segments), with the texts its sequences spell.
 struct World {
     std::vector<std::string> text;             // per sequence, the hidden ones behind the caller's ("" for the too-long literal)
     std::vector<SeqDesc> h;
@@ -71,30 +57,31 @@ struct World {
     SetView view() const { return SetView{h, n, n_lit, derived, groups, group_of, slot_of}; }
 };
 
+// the symbols a text holds outside upper-case ACGT and outside invert_base's alphabet: the counts the kernels would send back
+static void count(SeqDesc& d, const std::string& t)
+{
+    d.n_exc = d.n_invalid = 0;
+    for (char c : t) {
+        if (!strchr("ACGT", c)) ++d.n_exc;
+        if (!strchr("ACGTNacgtn", c)) ++d.n_invalid;
+    }
+}
+
 static SeqDesc describe(const std::string& t, uint32_t flags)
 {
     SeqDesc d;
     memset(&d, 0, sizeof d);
     d.len = (int32_t)t.size();
     d.flags = flags;
-    for (char c : t) {
-        if (!strchr("ACGT", c)) ++d.n_exc;
-        if (!strchr("ACGTNacgtn", c)) ++d.n_invalid;
-    }
+    count(d, t);
     return d;
 }
 
 static std::string spell(const World& w, const std::vector<HSeg>& segs, bool up)
 {
-    std::string s;
-    for (const HSeg& x : segs) {
-        CHECK(x.parent >= 0 && x.parent < w.n_lit && x.off >= 0 && x.len > 0 && (size_t)x.off + (size_t)x.len <= w.text[(size_t)x.parent].size(),
-              "segment %d+%d outside literal %d", x.off, x.len, x.parent);
-        CHECK(x.dst == (int32_t)s.size(), "segment at %d, %zu symbols before it", x.dst, s.size());
-        const std::string cut = w.text[(size_t)x.parent].substr((size_t)x.off, (size_t)x.len);
-        s += x.rc ? revcomp(cut) : cut;
-    }
-    return up ? upper(s) : s;
+    std::string s, why;
+    CHECK(seq_spell::spell(w.text, w.n_lit, segs, up, s, why), "%s", why.c_str());
+    return s;
 }
 
 static void add_seg(std::vector<HSeg>& a, int32_t parent, int off, int len, bool rc)
@@ -198,16 +185,29 @@ static World make_world(Kind kind, bool shared_join)
         for (size_t d = 0; d < w.derived.size(); ++d)
             for (HSeg& x : w.derived[d]) x.off += (int32_t)d;
     w.n = w.n_lit + (int32_t)w.derived.size();
-    for (size_t d = 0; d < w.derived.size(); ++d) {
-        w.text.push_back(spell(w, w.derived[d], w.dflags[d] & VAPOR_SEQ_UPPER));
-        w.h.push_back(describe(w.text.back(), w.dflags[d]));
+    // the descriptors of the derived and the hidden sequences and the share groups: as the library lays the set out, from the
+    // lengths and the segments (vapor_seqset_plan.h); the counts are the texts'
+    std::vector<int32_t> len, seg_first(1, 0);
+    std::vector<uint8_t> flags;
+    std::vector<vapor_segment> segs;
+    for (const SeqDesc& d : w.h) { len.push_back(d.len); flags.push_back((uint8_t)d.flags); }
+    for (const auto& v : w.derived) {
+        for (const HSeg& x : v) segs.push_back(vapor_segment{x.parent, x.off, x.len, x.rc ? VAPOR_SEG_REVCOMP : 0u});
+        seg_first.push_back((int32_t)segs.size());
     }
-    if (shared_join) w.hidden = share_layout(w.h, w.n, w.n_lit, w.derived, w.dflags, &w.groups, &w.group_of, &w.slot_of);
-    for (size_t t = 0; t < w.hidden.size(); ++t) {
-        bool up = false;
-        for (const ShareGroup& g : w.groups) if (g.t_seq == w.n + (int32_t)t) up = g.upper;
-        w.text.push_back(spell(w, w.hidden[t], up));
-        w.h.push_back(describe(w.text.back(), up ? VAPOR_SEQ_UPPER : 0u));
+    vapor_seqset_plan::Layout L;
+    const vapor_seqset_plan::Refusal no = L.build(vapor_seqset_plan::Call{vapor_seqset_plan::DERIVED, true, w.n_lit, nullptr, nullptr, nullptr, len.data(), flags.data(), nullptr,
+                                                                          nullptr, (int32_t)w.derived.size(), seg_first.data(), segs.data(), w.dflags.data()}, shared_join);
+    CHECK(!no && L.n == w.n && L.derived.size() == w.derived.size(), "the set is refused: %s", no.msg ? no.msg : "");
+    for (size_t i = 0; i < (size_t)w.n_lit; ++i) { L.h[i].n_exc = w.h[i].n_exc; L.h[i].n_invalid = w.h[i].n_invalid; }
+    w.h = L.h;
+    w.hidden = L.hidden;
+    w.groups = L.groups;
+    w.group_of = L.group_of;
+    w.slot_of = L.slot_of;
+    for (size_t i = (size_t)w.n_lit; i < w.h.size(); ++i) {
+        w.text.push_back(spell(w, L.segments(i - (size_t)w.n_lit), w.h[i].flags & VAPOR_SEQ_UPPER));
+        count(w.h[i], w.text.back());
     }
     return w;
 }

@@ -33,7 +33,9 @@ _HEADERS = [("vapor_kernels.h", True), ("vapor_wide.h", True), ("vapor_anyk.h", 
             # (`--realign-revote`, DESIGN.md 4.27: the spelling and re-vote kernels and the plan they read)
             ("vapor_revote.h", True), ("vapor_revote_plan.h", True),
             # (the host plan of one polish / re-vote call, put together from the two plans above: host-only, no kernel reads it)
-            ("vapor_polish_call.h", False)]
+            ("vapor_polish_call.h", False),
+            # (the host plan of one vapor_seqset_create* call, and the refusal and image tables the host plans share: host-only)
+            ("vapor_seqset_plan.h", False), ("vapor_image.h", False)]
 DEPS = SOURCES + [os.path.join(CSRC, h) for h, _dev in _HEADERS] + [os.path.join(ROOT, "include", "vapor_hip.h")]
 KERNEL_FILES = [os.path.join(CSRC, h) for h, dev in _HEADERS if dev] + [SOURCES[0], os.path.abspath(__file__)]
 

@@ -13,6 +13,7 @@
 #include "vapor_polish.h"
 #include "vapor_revote.h"
 #include "vapor_polish_call.h"
+#include "vapor_seqset_plan.h"
 #include "vapor_junction.h"
 #include "vapor_bamdev.h"
 #include "vapor_bgzf.h"
@@ -509,270 +510,120 @@ extern "C" int vapor_seqset_destroy(vapor_seqset* s)
     return VAPOR_OK;
 }
 
-// Shared by the two entry points: sequence i starts at src(i).
-template <typename SRC>
-static int seqset_create_impl(vapor_ctx* ctx, int32_t n_seqs, SRC src, const int32_t* len, const uint8_t* flags,
-                              int32_t* seq_info, vapor_seqset** out, int32_t n_derived = 0, const int32_t* seg_first = nullptr,
-                              const vapor_segment* segs = nullptr, const uint8_t* derived_flags = nullptr,
-                              const uint8_t* src_kind = nullptr, const int64_t* src_first = nullptr)
+static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+// vapor_seqset_create*: the four entries state their call, and everything that is arithmetic - the refusals in their order, where
+// every sequence lies in the planes, the staging buffer's tables and what is written into them, the threaded staging, what follows
+// the counts - is vapor_seqset_plan.h's.  Here: the staging buffer kept in the context and grown on demand, the set's blocks, the
+// copies, bam_expand_kernel / pack_kernel / derive_kernel, the copy back and the synchronisation.
+static int seqset_create_impl(vapor_ctx* ctx, const vapor_seqset_plan::Call& call, int32_t* seq_info, vapor_seqset** out)
 {
+    namespace sp = vapor_seqset_plan;
+    // (vapor_seqset_create_mixed takes packed bases by device address: only addresses inside the arena of a live batch are followed)
+    const auto in_live_batch = [ctx](const uint8_t* a, const uint8_t* b) {
+        auto it = ctx->arenas.upper_bound(a);
+        if (it == ctx->arenas.begin()) return false;
+        --it;
+        return b < it->first + it->second;
+    };
+    if (const sp::Refusal no = sp::check_args(call, in_live_batch)) return fail(no.code, no.msg);
     HIPCHK(hipSetDevice(ctx->device));
     const bool dbg_t = getenv("VAPOR_DEBUG_UPLOAD") != nullptr;
-    auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    double tq[8] = {now(), 0, 0, 0, 0, 0, 0, 0};
+    double tq[6] = {now_ms(), 0, 0, 0, 0, 0};
+    sp::Layout L;                              // (the copies read and fill its descriptors: declared before the owners)
     CallScope sc(ctx, ctx->stream);
     std::unique_ptr<vapor_seqset, Building<vapor_seqset, vapor_seqset_destroy>> s(new (std::nothrow) vapor_seqset(), {&sc});
     if (!s) return fail(VAPOR_E_NOMEM, "out of memory");
     s->ctx = ctx;
     s->device = ctx->device;
-    s->n = n_seqs + n_derived;
-    s->n_lit = n_seqs;
-    s->h.resize((size_t)std::max(n_seqs + n_derived, 1));
-    size_t asc = 0, pl = 0;
-    for (int32_t i = 0; i < n_seqs; ++i) {
-        if (len[i] < 0) return fail(VAPOR_E_ARG, "negative sequence length");
-        SeqDesc& d = s->h[i];
-        memset(&d, 0, sizeof d);
-        size_t ch = ((size_t)len[i] + 31) / 32;
-        d.asc0 = (uint32_t)asc;
-        d.chunk0 = (uint32_t)pl;
-        d.len = len[i];
-        d.flags = flags ? flags[i] : 0;
-        asc += ch;
-        pl += ch + VP_PAD_CHUNKS;
-        if (pl > 0xFFFFFFF0ull) return fail(VAPOR_E_ARG, "sequence set too large");
-    }
-    // derived sequences (the caller's, then the hidden shared ones): planes behind the literals', assembled by derive_kernel
-    std::vector<std::vector<HSeg>> hidden;
-    std::vector<uint8_t> dfl((size_t)n_derived, 0);
-    size_t der_chunks = 0;
-    if (n_derived > 0) {
-        s->derived.resize((size_t)n_derived);
-        for (int32_t d = 0; d < n_derived; ++d) {
-            const int32_t g0 = seg_first[d], g1 = seg_first[d + 1];
-            if (g1 < g0 || g1 - g0 > VAPOR_MAX_SEGMENTS) return fail(VAPOR_E_ARG, "vapor_seqset_create_derived: bad segment count");
-            int64_t tot = 0;
-            for (int32_t g = g0; g < g1; ++g) {
-                const vapor_segment& x = segs[g];
-                if (x.parent < 0 || x.parent >= n_seqs || x.off < 0 || x.len < 0 || (int64_t)x.off + x.len > len[x.parent])
-                    return fail(VAPOR_E_ARG, "vapor_seqset_create_derived: segment outside its parent");
-                if (x.len == 0) continue;
-                // (a derived sequence is slices of its parents' BYTES: one that is not upper-cased itself cannot be cut from a
-                // parent that was upper-cased at upload - its planes hold the upper-cased text)
-                if (flags && (flags[x.parent] & VAPOR_SEQ_UPPER) && !(derived_flags && (derived_flags[d] & VAPOR_SEQ_UPPER)))
-                    return fail(VAPOR_E_ARG, "vapor_seqset_create_derived: a derived sequence without VAPOR_SEQ_UPPER over a parent uploaded with it");
-                s->derived[(size_t)d].push_back(HSeg{x.parent, x.off, x.len, (int32_t)tot, (x.flags & VAPOR_SEG_REVCOMP) != 0});
-                tot += x.len;
-                if (tot > 0x7FFFFFF0LL) return fail(VAPOR_E_ARG, "vapor_seqset_create_derived: sequence too long");
-            }
-            dfl[(size_t)d] = derived_flags ? derived_flags[d] : 0;
-            SeqDesc& dd = s->h[(size_t)(n_seqs + d)];
-            memset(&dd, 0, sizeof dd);
-            dd.len = (int32_t)tot;
-            dd.flags = dfl[(size_t)d];
-        }
-        if (ctx->shared_join) hidden = share_layout(s->h, s->n, n_seqs, s->derived, dfl, &s->groups, &s->group_of, &s->slot_of);
-        s->h.resize((size_t)(n_seqs + n_derived) + hidden.size());
-        for (size_t t = 0; t < hidden.size(); ++t) {
-            SeqDesc& dd = s->h[(size_t)(n_seqs + n_derived) + t];
-            memset(&dd, 0, sizeof dd);
-            int64_t tot = 0;
-            for (const HSeg& x : hidden[t]) tot += x.len;
-            dd.len = (int32_t)tot;
-        }
-        for (const ShareGroup& g : s->groups)
-            if (g.t_seq >= 0 && g.upper) s->h[(size_t)g.t_seq].flags = VAPOR_SEQ_UPPER;
-        for (size_t i = (size_t)n_seqs; i < s->h.size(); ++i) {
-            SeqDesc& dd = s->h[i];
-            const size_t ch = ((size_t)dd.len + 31) / 32;
-            dd.asc0 = (uint32_t)der_chunks;             // (first chunk among the derived sequences' chunks)
-            dd.chunk0 = (uint32_t)pl;
-            der_chunks += ch;
-            pl += ch + VP_PAD_CHUNKS;
-            if (pl > 0xFFFFFFF0ull) return fail(VAPOR_E_ARG, "sequence set too large");
-        }
-    }
-    pl += VP_PAD_CHUNKS + 1;
-    s->plane_chunks = pl;
-    const size_t n_asc = asc;
-    tq[1] = now();
-    {
-        // staging (ASCII at 32-byte chunks, then the chunk -> sequence map, then what derive_kernel reads: segment lists, their
-        // offsets, the chunk -> sequence map of the derived sequences), kept in the context and grown on demand
-        const size_t n_dseq = s->h.size() - (size_t)n_seqs;
-        size_t n_seg = 0;
-        for (auto& v : s->derived) n_seg += v.size();
-        for (auto& v : hidden) n_seg += v.size();
-        // (a mixed set - vapor_seqset_create_mixed - has sequences whose bases are on the device already, 4 bits each: their
-        // addresses and first bases travel instead of their bytes, bam_expand_kernel writes their part of the ASCII layout)
-        const bool mixed = src_kind != nullptr;
-        const size_t mix_off = (n_asc * 36 + 7) & ~(size_t)7;
-        const size_t mix_bytes = mixed ? (size_t)n_seqs * 12 : 0;
-        const size_t der_off = (mix_off + mix_bytes + 63) & ~(size_t)63;
-        const size_t der_bytes = der_chunks ? sizeof(DSeg) * std::max<size_t>(n_seg, 1) + sizeof(int32_t) * (n_dseq + 1) + sizeof(uint32_t) * der_chunks : 0;
-        const size_t need = std::max<size_t>(der_off + der_bytes, 64);
-        if (need > ctx->stage_cap) {
-            HIPCHK(hipStreamSynchronize(ctx->stream));
-            if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
-            if (ctx->d_stage) (void)hipFree(ctx->d_stage);
-            ctx->h_stage = nullptr; ctx->d_stage = nullptr; ctx->stage_cap = 0;
-            const size_t cap = need + need / 4;
-            HIPCHK(hipHostMalloc((void**)&ctx->h_stage, cap));
-            HIPCHK(hipMalloc((void**)&ctx->d_stage, cap));
-            ctx->stage_cap = cap;
-        }
-        uint8_t* h_asc = ctx->h_stage;
-        uint32_t* h_map = reinterpret_cast<uint32_t*>(ctx->h_stage + n_asc * 32);
-        uint8_t* d_asc = ctx->d_stage;
-        uint32_t* d_map = reinterpret_cast<uint32_t*>(ctx->d_stage + n_asc * 32);
-        // the copy into the pinned staging buffer is the largest part of an upload (a core moves ~8 GB/s, the link
-        // 50): split the sequences over a few host threads when there is enough to copy
-        auto stage_range = [&](int32_t i0, int32_t i1) {
-            for (int32_t i = i0; i < i1; ++i) {
-                const SeqDesc& d = s->h[i];
-                size_t ch = ((size_t)d.len + 31) / 32;
-                for (size_t c = 0; c < ch; ++c) h_map[d.asc0 + c] = (uint32_t)i;
-                if (mixed && src_kind[i]) continue;
-                uint8_t* dst = h_asc + (size_t)d.asc0 * 32;
-                if (d.len) memcpy(dst, src(i), (size_t)d.len);
-                memset(dst + d.len, 0, ch * 32 - (size_t)d.len);
-            }
-        };
-        // the chunks the host has bytes for end here (the reads of a chunk of loci lie behind its windows: the usual mixed set
-        // sends the windows alone over the link)
-        size_t host_end = n_asc;
-        if (mixed) {
-            host_end = 0;
-            for (int32_t i = 0; i < n_seqs; ++i)
-                if (!src_kind[i] && s->h[i].len > 0) host_end = std::max(host_end, (size_t)s->h[i].asc0 + ((size_t)s->h[i].len + 31) / 32);
-        }
-        HIPCHK(dmalloc(ctx, (void**)&s->d_seqs, sizeof(SeqDesc) * s->h.size()));
-        HIPCHK(dmalloc(ctx, (void**)&s->d_p2, pl * 2 * sizeof(uint32_t)));
-        HIPCHK(dmalloc(ctx, (void**)&s->d_e1, pl * sizeof(uint32_t)));
-        HIPCHK(dmalloc(ctx, (void**)&s->d_x4, pl * 4 * sizeof(uint32_t)));
-        HIPCHK(hipMemsetAsync(s->d_p2, 0, pl * 2 * sizeof(uint32_t), ctx->stream));
-        HIPCHK(hipMemsetAsync(s->d_e1, 0, pl * sizeof(uint32_t), ctx->stream));
-        HIPCHK(hipMemsetAsync(s->d_x4, 0, pl * 4 * sizeof(uint32_t), ctx->stream));
-        HIPCHK(hipMemcpyAsync(s->d_seqs, s->h.data(), sizeof(SeqDesc) * s->h.size(), hipMemcpyHostToDevice, ctx->stream));
-        tq[2] = now();
-        const int n_thr = (!mixed && n_asc * 32 >= ((size_t)4 << 20) && n_seqs >= 8) ? ctx->stage_threads : 1;
-        if (mixed) {
-            stage_range(0, n_seqs);
-            unsigned long long* h_src = reinterpret_cast<unsigned long long*>(ctx->h_stage + mix_off);
-            int32_t* h_first = reinterpret_cast<int32_t*>(ctx->h_stage + mix_off + (size_t)n_seqs * 8);
-            for (int32_t i = 0; i < n_seqs; ++i) {
-                // (src_kind 2: the source reverse complemented from base src_first downwards - bit 63 tells bam_expand_kernel)
-                h_src[i] = src_kind[i] ? (unsigned long long)reinterpret_cast<uintptr_t>(src(i)) | (src_kind[i] == 2 ? 1ull << 63 : 0ull) : 0ull;
-                h_first[i] = src_kind[i] ? (int32_t)src_first[i] : 0;
-            }
-            if (host_end) HIPCHK(hipMemcpyAsync(d_asc, h_asc, host_end * 32, hipMemcpyHostToDevice, ctx->stream));
-            if (n_asc) HIPCHK(hipMemcpyAsync(d_map, h_map, n_asc * 4, hipMemcpyHostToDevice, ctx->stream));
-            HIPCHK(hipMemcpyAsync(ctx->d_stage + mix_off, ctx->h_stage + mix_off, mix_bytes, hipMemcpyHostToDevice, ctx->stream));
-            if (n_asc) {
-                hipLaunchKernelGGL(vapor_bamdev::bam_expand_kernel, dim3((unsigned)((n_asc + 255) / 256)), dim3(256), 0, ctx->stream, d_asc, d_map,
-                                   (uint32_t)n_asc, reinterpret_cast<const uint32_t*>(s->d_seqs),
-                                   reinterpret_cast<const unsigned long long*>(ctx->d_stage + mix_off),
-                                   reinterpret_cast<const int32_t*>(ctx->d_stage + mix_off + (size_t)n_seqs * 8));
-                HIPCHK(hipGetLastError());
-            }
-        } else if (n_thr == 1) {
-            stage_range(0, n_seqs);
-            if (n_asc) HIPCHK(hipMemcpyAsync(d_asc, h_asc, n_asc * 36, hipMemcpyHostToDevice, ctx->stream));
-        } else {
-            // slices of equal shares of the bytes, staged by the threads in order; this thread sends a slice to the device
-            // as soon as it is staged, so that the link works while the cores still copy
-            constexpr int SLICES = 12;
-            std::vector<int32_t> cut(1, 0);
-            for (int t = 1; t < SLICES; ++t) {
-                const uint32_t want = (uint32_t)(n_asc * (size_t)t / (size_t)SLICES);
-                int32_t i = cut.back();
-                while (i < n_seqs && s->h[i].asc0 < want) ++i;
-                cut.push_back(i);
-            }
-            cut.push_back(n_seqs);
-            std::atomic<int> staged[SLICES];
-            for (auto& f : staged) f.store(0, std::memory_order_relaxed);
-            std::vector<std::thread> th;
-            for (int t = 0; t < n_thr; ++t)
-                th.emplace_back([&, t] {
-                    for (int k = t; k < SLICES; k += n_thr) {
-                        stage_range(cut[(size_t)k], cut[(size_t)k + 1]);
-                        staged[k].store(1, std::memory_order_release);
-                    }
-                });
-            hipError_t err = hipSuccess;
-            for (int k = 0; k < SLICES; ++k) {
-                while (!staged[k].load(std::memory_order_acquire)) std::this_thread::yield();
-                const size_t c0 = cut[(size_t)k] < n_seqs ? s->h[(size_t)cut[(size_t)k]].asc0 : n_asc;
-                const size_t c1 = cut[(size_t)k + 1] < n_seqs ? s->h[(size_t)cut[(size_t)k + 1]].asc0 : n_asc;
-                if (c1 > c0 && err == hipSuccess)
-                    err = hipMemcpyAsync(d_asc + c0 * 32, h_asc + c0 * 32, (c1 - c0) * 32, hipMemcpyHostToDevice, ctx->stream);
-            }
-            for (auto& x : th) x.join();
-            HIPCHK(err);
-            HIPCHK(hipMemcpyAsync(d_map, h_map, n_asc * 4, hipMemcpyHostToDevice, ctx->stream));
-        }
-        tq[3] = now();
-        if (n_asc) {
-            unsigned grid = (unsigned)((n_asc + 255) / 256);
-            hipLaunchKernelGGL(pack_kernel, dim3(grid), dim3(256), 0, ctx->stream, d_asc, s->d_seqs, n_seqs, d_map,
-                               (uint32_t)n_asc, s->d_p2, s->d_e1, s->d_x4);
-            HIPCHK(hipGetLastError());
-        }
-        if (der_chunks) {
-            uint8_t* blk = ctx->h_stage + der_off;
-            DSeg* hs = reinterpret_cast<DSeg*>(blk);
-            int32_t* hf = reinterpret_cast<int32_t*>(blk + sizeof(DSeg) * std::max<size_t>(n_seg, 1));
-            uint32_t* hc = reinterpret_cast<uint32_t*>(hf + n_dseq + 1);
-            size_t w = 0;
-            for (size_t t = 0; t < n_dseq; ++t) {
-                const auto& v = t < s->derived.size() ? s->derived[t] : hidden[t - s->derived.size()];
-                hf[t] = (int32_t)w;
-                for (const HSeg& x : v) hs[w++] = DSeg{s->h[(size_t)x.parent].chunk0, x.off, x.len, x.dst, x.rc ? 1u : 0u};
-                const SeqDesc& dd = s->h[(size_t)n_seqs + t];
-                for (size_t c = 0; c < ((size_t)dd.len + 31) / 32; ++c) hc[dd.asc0 + c] = (uint32_t)((size_t)n_seqs + t);
-            }
-            hf[n_dseq] = (int32_t)w;
-            uint8_t* d_blk = ctx->d_stage + der_off;
-            HIPCHK(hipMemcpyAsync(d_blk, blk, der_bytes, hipMemcpyHostToDevice, ctx->stream));
-            const DSeg* dsg = reinterpret_cast<const DSeg*>(d_blk);
-            const int32_t* dsf = reinterpret_cast<const int32_t*>(d_blk + sizeof(DSeg) * std::max<size_t>(n_seg, 1));
-            const uint32_t* dsc = reinterpret_cast<const uint32_t*>(dsf + n_dseq + 1);
-            hipLaunchKernelGGL(derive_kernel, dim3((unsigned)((der_chunks + 255) / 256)), dim3(256), 0, ctx->stream, s->d_seqs, dsc,
-                               (uint32_t)der_chunks, dsf, dsg, n_seqs, s->d_p2, s->d_e1, s->d_x4);
-            HIPCHK(hipGetLastError());
-        }
-        tq[4] = now();
-        HIPCHK(hipMemcpyAsync(s->h.data(), s->d_seqs, sizeof(SeqDesc) * s->h.size(), hipMemcpyDeviceToHost, ctx->stream));
+    if (const sp::Refusal no = L.build(call, ctx->shared_join)) return fail(no.code, no.msg);
+    s->n = L.n;
+    s->n_lit = L.n_lit;
+    s->plane_chunks = L.plane_chunks;
+    const int32_t n_seqs = L.n_lit;
+    const size_t n_asc = L.n_asc, pl = L.plane_chunks, desc_bytes = sizeof(SeqDesc) * L.h.size();
+    tq[1] = now_ms();
+    const sp::Staging st(call, L);
+    if (st.need > ctx->stage_cap) {
         HIPCHK(hipStreamSynchronize(ctx->stream));
-        tq[5] = now();
-        if (dbg_t) fprintf(stderr, "seqset: layout+groups %.3f  alloc+memset %.3f  stage+h2d %.3f  launches %.3f  sync %.3f ms\n", tq[1] - tq[0], tq[2] - tq[1], tq[3] - tq[2], tq[4] - tq[3], tq[5] - tq[4]);
-        // complementary() drops what is not ATGCN / atgcn (SF:471-478): a reversed slice of a window that holds such a
-        // character is not what the reference would have built
-        for (const auto& v : s->derived)
-            for (const HSeg& x : v)
-                if (x.rc && s->h[(size_t)x.parent].n_nocomp > 0)
-                    return fail(VAPOR_E_ARG, "vapor_seqset_create_derived: a reverse-complemented segment's parent holds characters complementary() drops "
-                                             "(outside ATGCN/atgcn, SF:471-478); upload that allele as bytes");
-        // keep the bytes of the sequences with symbols outside the alphabet (rare) before the staging buffer is reused
-        s->raw_off.assign(s->h.size(), -1);
-        size_t raw_bytes = 0;
-        for (int32_t i = 0; i < n_seqs; ++i)
-            if (s->h[i].n_invalid > 0) { s->raw_off[i] = (int64_t)raw_bytes; raw_bytes += ((size_t)s->h[i].len + 15) & ~(size_t)15; }
-        if (raw_bytes) {
-            HIPCHK(dmalloc(ctx, (void**)&s->d_raw, raw_bytes));
-            for (int32_t i = 0; i < n_seqs; ++i)
-                if (s->raw_off[i] >= 0 && s->h[i].len)
-                    HIPCHK(hipMemcpyAsync(s->d_raw + s->raw_off[i], d_asc + (size_t)s->h[i].asc0 * 32, (size_t)s->h[i].len,
-                                          hipMemcpyDeviceToDevice, ctx->stream));
-            HIPCHK(hipStreamSynchronize(ctx->stream));
-        }
-        if (seq_info)
-            for (int32_t i = 0; i < s->n; ++i) {
-                seq_info[2 * i] = s->h[i].n_exc;
-                seq_info[2 * i + 1] = s->h[i].n_invalid;
-            }
+        if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
+        if (ctx->d_stage) (void)hipFree(ctx->d_stage);
+        ctx->h_stage = nullptr; ctx->d_stage = nullptr; ctx->stage_cap = 0;
+        const size_t cap = st.need + st.need / 4;
+        HIPCHK(hipHostMalloc((void**)&ctx->h_stage, cap));
+        HIPCHK(hipMalloc((void**)&ctx->d_stage, cap));
+        ctx->stage_cap = cap;
     }
+    uint8_t *const h_stage = ctx->h_stage, *const d_stage = ctx->d_stage;
+    HIPCHK(dmalloc(ctx, (void**)&s->d_seqs, desc_bytes));
+    HIPCHK(dmalloc(ctx, (void**)&s->d_p2, pl * 2 * sizeof(uint32_t)));
+    HIPCHK(dmalloc(ctx, (void**)&s->d_e1, pl * sizeof(uint32_t)));
+    HIPCHK(dmalloc(ctx, (void**)&s->d_x4, pl * 4 * sizeof(uint32_t)));
+    HIPCHK(hipMemsetAsync(s->d_p2, 0, pl * 2 * sizeof(uint32_t), ctx->stream));
+    HIPCHK(hipMemsetAsync(s->d_e1, 0, pl * sizeof(uint32_t), ctx->stream));
+    HIPCHK(hipMemsetAsync(s->d_x4, 0, pl * 4 * sizeof(uint32_t), ctx->stream));
+    HIPCHK(hipMemcpyAsync(s->d_seqs, L.h.data(), desc_bytes, hipMemcpyHostToDevice, ctx->stream));
+    tq[2] = now_ms();
+    // the copy into the pinned staging buffer is the largest part of an upload (a core moves ~8 GB/s, the link 50): the literals
+    // are split over a few host threads when there is enough to copy
+    const int n_thr = st.sliced ? ctx->stage_threads : 1;
+    if (L.mixed) {
+        // (the device holds some literals already, 4 bits a base: bam_expand_kernel writes their part of the ASCII layout)
+        sp::stage_range(call, L, st, h_stage, 0, n_seqs);
+        sp::fill_sources(call, st, h_stage);
+        if (st.host_end) HIPCHK(hipMemcpyAsync(d_stage, h_stage, st.host_end * 32, hipMemcpyHostToDevice, ctx->stream));
+        if (n_asc) HIPCHK(hipMemcpyAsync(st.map.in(d_stage), st.map.in(h_stage), st.map.bytes(), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(hipMemcpyAsync(st.src.in(d_stage), st.src.in(h_stage), st.mix_bytes, hipMemcpyHostToDevice, ctx->stream));
+        if (n_asc) {
+            hipLaunchKernelGGL(vapor_bamdev::bam_expand_kernel, dim3((unsigned)((n_asc + 255) / 256)), dim3(256), 0, ctx->stream, st.asc.in(d_stage),
+                               st.map.in(d_stage), (uint32_t)n_asc, reinterpret_cast<const uint32_t*>(s->d_seqs), st.src.in(d_stage), st.first.in(d_stage));
+            HIPCHK(hipGetLastError());
+        }
+    } else if (n_thr == 1) {
+        sp::stage_range(call, L, st, h_stage, 0, n_seqs);
+        if (n_asc) HIPCHK(hipMemcpyAsync(d_stage, h_stage, st.asc.bytes() + st.map.bytes(), hipMemcpyHostToDevice, ctx->stream));
+    } else {
+        hipError_t err = hipSuccess;
+        sp::stage_sliced(call, L, st, h_stage, n_thr, [&](size_t c0, size_t c1) {
+            if (err == hipSuccess) err = hipMemcpyAsync(d_stage + c0 * 32, h_stage + c0 * 32, (c1 - c0) * 32, hipMemcpyHostToDevice, ctx->stream);
+        });
+        HIPCHK(err);
+        HIPCHK(hipMemcpyAsync(st.map.in(d_stage), st.map.in(h_stage), st.map.bytes(), hipMemcpyHostToDevice, ctx->stream));
+    }
+    tq[3] = now_ms();
+    if (n_asc) {
+        hipLaunchKernelGGL(pack_kernel, dim3((unsigned)((n_asc + 255) / 256)), dim3(256), 0, ctx->stream, st.asc.in(d_stage), s->d_seqs, n_seqs,
+                           st.map.in(d_stage), (uint32_t)n_asc, s->d_p2, s->d_e1, s->d_x4);
+        HIPCHK(hipGetLastError());
+    }
+    if (L.der_chunks) {
+        sp::fill_derived(L, st, h_stage);
+        HIPCHK(hipMemcpyAsync(st.segs.in(d_stage), st.segs.in(h_stage), st.der_bytes, hipMemcpyHostToDevice, ctx->stream));
+        hipLaunchKernelGGL(derive_kernel, dim3((unsigned)((L.der_chunks + 255) / 256)), dim3(256), 0, ctx->stream, s->d_seqs, st.der_map.in(d_stage),
+                           (uint32_t)L.der_chunks, st.seg_first.in(d_stage), st.segs.in(d_stage), n_seqs, s->d_p2, s->d_e1, s->d_x4);
+        HIPCHK(hipGetLastError());
+    }
+    tq[4] = now_ms();
+    HIPCHK(hipMemcpyAsync(L.h.data(), s->d_seqs, desc_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    tq[5] = now_ms();
+    if (dbg_t) fprintf(stderr, "seqset: layout+groups %.3f  alloc+memset %.3f  stage+h2d %.3f  launches %.3f  sync %.3f ms\n", tq[1] - tq[0], tq[2] - tq[1], tq[3] - tq[2], tq[4] - tq[3], tq[5] - tq[4]);
+    if (const sp::Refusal no = sp::revcomp_refusal(L)) return fail(no.code, no.msg);
+    // keep the bytes of the sequences with symbols outside the alphabet (rare) before the staging buffer is reused
+    if (const size_t raw_bytes = sp::raw_layout(L, s->raw_off)) {
+        HIPCHK(dmalloc(ctx, (void**)&s->d_raw, raw_bytes));
+        for (int32_t i = 0; i < n_seqs; ++i)
+            if (s->raw_off[i] >= 0 && L.h[i].len)
+                HIPCHK(hipMemcpyAsync(s->d_raw + s->raw_off[i], st.asc.in(d_stage) + (size_t)L.h[i].asc0 * 32, (size_t)L.h[i].len,
+                                      hipMemcpyDeviceToDevice, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+    }
+    sp::fill_seq_info(L, seq_info);
+    s->h = std::move(L.h);
+    s->derived = std::move(L.derived);
+    s->groups = std::move(L.groups);
+    s->group_of = std::move(L.group_of);
+    s->slot_of = std::move(L.slot_of);
     *out = s.release();
     return VAPOR_OK;
 }
@@ -780,19 +631,15 @@ static int seqset_create_impl(vapor_ctx* ctx, int32_t n_seqs, SRC src, const int
 extern "C" int vapor_seqset_create(vapor_ctx* ctx, int32_t n_seqs, const uint8_t* blob, const int64_t* off,
                                    const int32_t* len, const uint8_t* flags, int32_t* seq_info, vapor_seqset** out)
 {
-    if (!ctx || !out || n_seqs < 0 || (n_seqs && (!blob || !off || !len)))
-        return fail(VAPOR_E_ARG, "vapor_seqset_create: null argument");
-    return seqset_create_impl(ctx, n_seqs, [&](int32_t i) { return blob + off[i]; }, len, flags, seq_info, out);
+    return seqset_create_impl(ctx, {vapor_seqset_plan::BLOB, ctx && out, n_seqs, blob, off, nullptr, len, flags, nullptr, nullptr, 0, nullptr, nullptr, nullptr},
+                              seq_info, out);
 }
 
 extern "C" int vapor_seqset_create_ptrs(vapor_ctx* ctx, int32_t n_seqs, const uint8_t* const* seq, const int32_t* len,
                                         const uint8_t* flags, int32_t* seq_info, vapor_seqset** out)
 {
-    if (!ctx || !out || n_seqs < 0 || (n_seqs && (!seq || !len)))
-        return fail(VAPOR_E_ARG, "vapor_seqset_create_ptrs: null argument");
-    for (int32_t i = 0; i < n_seqs; ++i)
-        if (len[i] > 0 && !seq[i]) return fail(VAPOR_E_ARG, "vapor_seqset_create_ptrs: null sequence");
-    return seqset_create_impl(ctx, n_seqs, [&](int32_t i) { return seq[i]; }, len, flags, seq_info, out);
+    return seqset_create_impl(ctx, {vapor_seqset_plan::PTRS, ctx && out, n_seqs, nullptr, nullptr, seq, len, flags, nullptr, nullptr, 0, nullptr, nullptr, nullptr},
+                              seq_info, out);
 }
 
 extern "C" int vapor_seqset_create_derived(vapor_ctx* ctx, int32_t n_seqs, const uint8_t* const* seq, const int32_t* len,
@@ -800,13 +647,20 @@ extern "C" int vapor_seqset_create_derived(vapor_ctx* ctx, int32_t n_seqs, const
                                            const vapor_segment* segs, const uint8_t* derived_flags, int32_t* seq_info,
                                            vapor_seqset** out)
 {
-    if (!ctx || !out || n_seqs < 0 || n_derived < 0 || (n_seqs && (!seq || !len)) || (n_derived && (!seg_first || !segs)))
-        return fail(VAPOR_E_ARG, "vapor_seqset_create_derived: null argument");
-    if ((int64_t)n_seqs + n_derived > 0x7FFFFFF0LL) return fail(VAPOR_E_ARG, "vapor_seqset_create_derived: too many sequences");
-    for (int32_t i = 0; i < n_seqs; ++i)
-        if (len[i] > 0 && !seq[i]) return fail(VAPOR_E_ARG, "vapor_seqset_create_derived: null sequence");
-    return seqset_create_impl(ctx, n_seqs, [&](int32_t i) { return seq[i]; }, len, flags, seq_info, out, n_derived, seg_first, segs,
-                              derived_flags);
+    return seqset_create_impl(ctx, {vapor_seqset_plan::DERIVED, ctx && out, n_seqs, nullptr, nullptr, seq, len, flags, nullptr, nullptr, n_derived, seg_first, segs,
+                                    derived_flags}, seq_info, out);
+}
+
+// vapor_seqset_create_derived with sequences whose bases are on the device already (vapor_bam_chop_device's reads): src_kind[i] = 1
+// says seq[i] is the DEVICE address of BAM-packed bases (4 bits each, high nibble first) inside the arena of a live batch of this
+// context and src_first[i] the first base; len[i] bases from there are the sequence.  0: bytes on the host, as ever.
+extern "C" int vapor_seqset_create_mixed(vapor_ctx* ctx, int32_t n_seqs, const uint8_t* const* seq, const int32_t* len,
+                                         const uint8_t* flags, const uint8_t* src_kind, const int64_t* src_first,
+                                         int32_t n_derived, const int32_t* seg_first, const vapor_segment* segs,
+                                         const uint8_t* derived_flags, int32_t* seq_info, vapor_seqset** out)
+{
+    return seqset_create_impl(ctx, {vapor_seqset_plan::MIXED, ctx && out, n_seqs, nullptr, nullptr, seq, len, flags, src_kind, src_first, n_derived, seg_first, segs,
+                                    derived_flags}, seq_info, out);
 }
 
 extern "C" int vapor_seqset_planes(vapor_seqset* s, int32_t seq, uint32_t* p2, uint32_t* e1, uint32_t* x4)
@@ -882,8 +736,6 @@ static hipError_t crc_pow_on_device(vapor_ctx* ctx)
     ctx->d_crc_pow = d;
     return hipSuccess;
 }
-
-static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // The inflate stage of the two device readers (vapor_bam_chop_device*, vapor_fasta_windows_device): the file's bytes read into a
 // pinned block, one metadata block (vapor_readplan.h carves it) that holds the BgzfBlk list, both sent on the call's stream, bgzf_inflate_kernel.
@@ -1384,40 +1236,6 @@ extern "C" int vapor_fasta_last_stats(vapor_ctx* ctx, double* out, int32_t n)
     if (!ctx || !out || n < 0) return fail(VAPOR_E_ARG, "vapor_fasta_last_stats: null argument");
     for (int32_t i = 0; i < n && i < 6; ++i) out[i] = ctx->fasta_stats[i];
     return VAPOR_OK;
-}
-
-// vapor_seqset_create_derived with sequences whose bases are on the device already (vapor_bam_chop_device's reads): src_kind[i] = 1
-// says seq[i] is the DEVICE address of BAM-packed bases (4 bits each, high nibble first) inside the arena of a live batch of this
-// context and src_first[i] the first base; len[i] bases from there are the sequence.  0: bytes on the host, as ever.
-extern "C" int vapor_seqset_create_mixed(vapor_ctx* ctx, int32_t n_seqs, const uint8_t* const* seq, const int32_t* len,
-                                         const uint8_t* flags, const uint8_t* src_kind, const int64_t* src_first,
-                                         int32_t n_derived, const int32_t* seg_first, const vapor_segment* segs,
-                                         const uint8_t* derived_flags, int32_t* seq_info, vapor_seqset** out)
-{
-    if (!ctx || !out || n_seqs < 0 || n_derived < 0 || (n_seqs && (!seq || !len)) || (n_derived && (!seg_first || !segs)))
-        return fail(VAPOR_E_ARG, "vapor_seqset_create_mixed: null argument");
-    if ((int64_t)n_seqs + n_derived > 0x7FFFFFF0LL) return fail(VAPOR_E_ARG, "vapor_seqset_create_mixed: too many sequences");
-    bool any_dev = false;
-    for (int32_t i = 0; i < n_seqs; ++i) {
-        if (len[i] < 0) return fail(VAPOR_E_ARG, "negative sequence length");
-        if (len[i] > 0 && !seq[i]) return fail(VAPOR_E_ARG, "vapor_seqset_create_mixed: null sequence");
-        if (!src_kind || !src_kind[i]) continue;
-        if ((src_kind[i] != 1 && src_kind[i] != 2) || !src_first || src_first[i] < 0 || src_first[i] > 0x7FFFFFF0LL ||
-            (src_kind[i] == 2 && (int64_t)len[i] > src_first[i] + 1))
-            return fail(VAPOR_E_ARG, "vapor_seqset_create_mixed: bad source description");
-        any_dev = true;
-        if (len[i] == 0) continue;
-        // the bytes that will be read must lie inside the arena of a batch that is alive
-        const int64_t lo = src_kind[i] == 2 ? src_first[i] - len[i] + 1 : src_first[i];        // (kind 2 reads downwards)
-        const uint8_t* a = seq[i] + (lo >> 1);
-        const uint8_t* b = seq[i] + ((lo + len[i] - 1) >> 1);
-        auto it = ctx->arenas.upper_bound(a);
-        if (it == ctx->arenas.begin()) return fail(VAPOR_E_ARG, "vapor_seqset_create_mixed: a device source outside every live batch");
-        --it;
-        if (b >= it->first + it->second) return fail(VAPOR_E_ARG, "vapor_seqset_create_mixed: a device source outside every live batch");
-    }
-    return seqset_create_impl(ctx, n_seqs, [&](int32_t i) { return seq[i]; }, len, flags, seq_info, out, n_derived, seg_first, segs,
-                              derived_flags, any_dev ? src_kind : nullptr, src_first);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2654,9 +2472,9 @@ extern "C" int vapor_realign_trace(vapor_ctx* ctx, vapor_seqset* set, int64_t n_
     const std::vector<ra::RPair> recs = pair_records<ra::RPair>(set, pairs, n_pairs);
     std::vector<int64_t> first;
     std::vector<uint64_t> off;
-    vapor_polish_call::Table<ra::RPair> t_recs;                        // the upload image: the records, then the workspace offsets
-    vapor_polish_call::Table<uint64_t> t_off;
-    vapor_polish_call::Carve carve;
+    vapor_image::Table<ra::RPair> t_recs;                        // the upload image: the records, then the workspace offsets
+    vapor_image::Table<uint64_t> t_off;
+    vapor_image::Carve carve;
     carve.take(t_recs, np);
     carve.take(t_off, np);
     std::vector<uint8_t> up(carve.off);                                // (the upload reads it: declared before the owners)

@@ -36,7 +36,7 @@ namespace vapor {
 // plane, 1 word of the exception plane, 4 words of the 4-bit plane.
 #define VP_P2_WORDS_PER_CHUNK 2
 #define VP_X4_WORDS_PER_CHUNK 4
-#define VP_PAD_CHUNKS 3  // zeroed chunks after each sequence: window reads may run this far
+// (VP_PAD_CHUNKS, the zeroed chunks after each sequence, is vapor_records.h's: the host lays the planes out with it)
 
 #ifndef VAPOR_CLEAN_THREADS
 #define VAPOR_CLEAN_THREADS 256
@@ -126,11 +126,7 @@ __global__ __launch_bounds__(256) void pack_kernel(const uint8_t* __restrict__ a
 // + ref[-f:] (SF:1755), ref[:f] + reverse(complementary(mid)) + ref[-f:] (SF:1907), flank + ins_seq + flank (SF:1872), the
 // str.upper() twins of abs_dis_m1b (SF:183-184) - travels as a list of segments; this kernel writes its three planes from the
 // parents' 4-bit plane (which holds everything: case, N, folded IUPAC, invalid).  One thread per 32-symbol chunk.
-struct DSeg {          // 20 B: dst symbols [dst, dst + len) of the derived sequence = parent[off .. off + len), reversed and
-    uint32_t chunk0;   // complemented when rc; chunk0 = the parent's first plane chunk
-    int32_t off, len, dst;
-    uint32_t rc;
-};
+// (the segment record, DSeg, is vapor_records.h's: the host writes the list this kernel reads)
 
 __device__ __forceinline__ uint32_t comp_code(uint32_t c)
 {

@@ -8,6 +8,7 @@
 // copies back and one synchronisation.
 #pragma once
 
+#include "vapor_image.h"
 #include "vapor_revote_plan.h"
 
 #include <algorithm>
@@ -23,32 +24,11 @@ namespace tr = vapor_trace;
 namespace pp = vapor_polish;
 namespace vr = vapor_revote;
 
-// why a call is refused: the code, and the message without the entry's name (the entry prepends "<name>: ")
-struct Refusal {
-    int code = 0;
-    const char* msg = nullptr;
-    explicit operator bool() const { return code != 0; }
-};
-
-// A table of an upload image: n entries of T from byte `off` on, every table starting on 8 bytes.  The image is carved once; the
-// host fills a table and the launches take its entries through in(), given the host's or the device's copy of the image.  A table
-// the call does not have takes no room.  (vapor_realign_trace carves its two tables the same way.)
-template <typename T>
-struct Table {
-    size_t off = 0, n = 0;
-    T* in(uint8_t* image) const { return reinterpret_cast<T*>(image + off); }
-    const T* in(const uint8_t* image) const { return reinterpret_cast<const T*>(image + off); }
-    size_t end() const { return off + (sizeof(T) * n + 7) / 8 * 8; }
-    void fill(std::vector<uint8_t>& image, const std::vector<T>& from) const
-    {
-        if (n) memcpy(image.data() + off, from.data(), sizeof(T) * n);
-    }
-};
-struct Carve {                     // a running offset; `off` is the image's size once every table is taken
-    size_t off = 0;
-    template <typename T>
-    void take(Table<T>& t, size_t n) { t.off = off; t.n = n; off = t.end(); }
-};
+// why a call is refused (here: the message without the entry's name, the entry prepends "<name>: "), and the upload image's tables,
+// every one starting on 8 bytes (vapor_image.h; vapor_realign_trace carves its two tables the same way)
+using vapor_image::Carve;
+using vapor_image::Refusal;
+using vapor_image::Table;
 
 // the set as the plan headers' helpers take it: sequences, the length and the first 32-symbol chunk of sequence s
 template <typename LenOf, typename ChunkOf>

@@ -19,6 +19,15 @@ struct SeqDesc {       // 32 B
     uint32_t pad;
 };
 
+#define VP_PAD_CHUNKS 3  // zeroed chunks after each sequence: window reads may run this far
+
+// a segment of a derived sequence as derive_kernel reads it (vapor_kernels.h); vapor_seqset_plan.h writes the list
+struct DSeg {          // 20 B: dst symbols [dst, dst + len) of the derived sequence = parent[off .. off + len), reversed and
+    uint32_t chunk0;   // complemented when rc; chunk0 = the parent's first plane chunk
+    int32_t off, len, dst;
+    uint32_t rc;
+};
+
 struct DPair {         // 40 B
     int32_t seq1, seq2, off2, k;
     uint32_t flags, cap;
@@ -64,7 +73,7 @@ struct DServe {        // 32 B per pair: what the clean workgroup of a pair serv
     int32_t pad;
 };
 
-static_assert(sizeof(SeqDesc) == 32 && sizeof(DPair) == 40 && sizeof(DTask) == 16 && sizeof(DMap) == 16 && sizeof(DShare) == 32 &&
+static_assert(sizeof(SeqDesc) == 32 && sizeof(DSeg) == 20 && sizeof(DPair) == 40 && sizeof(DTask) == 16 && sizeof(DMap) == 16 && sizeof(DShare) == 32 &&
               sizeof(DServe) == 32, "the sizes the comments state: the kernels index arrays of these");
 
 }  // namespace vapor
