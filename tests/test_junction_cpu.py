@@ -137,12 +137,7 @@ def test_the_flag_parses_and_the_help_text_is_unchanged(monkeypatch):
     with open(os.path.join(ROOT, "tests", "golden", "cli_help.txt")) as f:
         assert p.format_help() == f.read()
     assert "--realign-junction" not in p.format_help() and "--realign-junction" not in p.format_usage()
-    m = modes.realign_junction()
-    assert m.name == "realign" and m.sink is None and m.polish and m.junction and m.COLUMNS == junction.COLUMNS
-    assert m.COLUMNS[:13] == modes.realign_polish().COLUMNS and not modes.realign_polish().junction
-    assert not modes.REALIGN.junction and not modes.realign_out(object()).junction and modes.REALIGN.COLUMNS == realign.COLUMNS
-    sink = object()
-    assert modes.realign_junction(sink).sink is sink
+    assert modes.REALIGN.COLUMNS == realign.COLUMNS
 
 
 def test_refused_without_realign_polish(capsys):
@@ -150,19 +145,6 @@ def test_refused_without_realign_polish(capsys):
         TR._refused([cmd] + TR.BASE + ["--realign-junction"], "--realign-junction needs --realign-polish", capsys)
     TR._refused(["bed"] + TR.BASE + ["--realign", "--realign-junction"], "--realign-junction needs --realign-polish", capsys)
     TR._refused(["vcf"] + TR.BASE + ["--realign", "--realign-out", "pre", "--realign-junction"], "--realign-junction needs --realign-polish", capsys)
-
-
-def test_the_request_and_the_wrappers_keep_their_signatures():
-    import inspect
-
-    from vapor_amd import drivers
-    assert list(inspect.signature(drivers.Realign.__init__).parameters)[1:] == ["ref_seq", "alt_seq", "reads", "name", "trace", "polish", "junction"]
-    r = drivers.Realign("A", "C", [])
-    assert (r.trace, r.polish, r.junction) == (False, False, False) and drivers.Realign("A", "C", [], None, False, True, True).junction
-    assert list(inspect.signature(drivers.vapor_realign).parameters) == ["driver", "args"]
-    assert list(inspect.signature(drivers.vapor_realign_out).parameters) == ["name", "driver", "args"]
-    assert list(inspect.signature(drivers.vapor_realign_polish).parameters) == ["name", "trace", "driver", "args"]
-    assert list(inspect.signature(drivers.vapor_realign_junction).parameters) == ["name", "trace", "driver", "args"]
 
 
 # ------------------------------------------------------------------------------------------------------------------------------

@@ -165,9 +165,7 @@ def test_the_flag_parses_and_the_help_text_is_unchanged(monkeypatch):
     with open(os.path.join(ROOT, "tests", "golden", "cli_help.txt")) as f:
         assert p.format_help() == f.read()
     assert "--realign-polish" not in p.format_help() and "--realign-polish" not in p.format_usage()
-    m = modes.realign_polish()
-    assert m.name == "realign" and m.sink is None and m.polish and m.COLUMNS == polish.COLUMNS and m.COLUMNS[:7] == modes.REALIGN.COLUMNS
-    assert not modes.REALIGN.polish and not modes.realign_out(object()).polish and modes.REALIGN.COLUMNS == realign.COLUMNS
+    assert modes.REALIGN.COLUMNS == realign.COLUMNS
 
 
 def test_refused_without_realign(capsys):

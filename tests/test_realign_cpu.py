@@ -317,7 +317,7 @@ def test_the_wrapper_forwards_everything_and_asks_once():
         yield drivers.Figure([], "", 10, "R", "A", "name")
         return [0.5]
 
-    gen = drivers.vapor_realign(driver, 1, 2)
+    gen = drivers.vapor_realign(realign.Options(), "key", driver, 1, 2)
     req = next(gen)
     assert isinstance(req, drivers.Window)
     req = gen.send([10])
@@ -329,6 +329,7 @@ def test_the_wrapper_forwards_everything_and_asks_once():
     assert isinstance(req, drivers.Figure)
     req = gen.send(None)
     assert isinstance(req, drivers.Realign) and (req.ref_seq, req.alt_seq, req.reads) == ("REF1", "ALT1", [["r", 0, "q"]])
+    assert req.name is None and req.options == realign.Options()
     with pytest.raises(StopIteration) as fin:
         gen.send(realign.Payload([12]))
     out = fin.value.value
@@ -337,7 +338,7 @@ def test_the_wrapper_forwards_everything_and_asks_once():
     def none(_a):
         yield drivers.Window("W")
         return []
-    gen = drivers.vapor_realign(none, 0)
+    gen = drivers.vapor_realign(realign.Options(), "key", none, 0)
     next(gen)
     with pytest.raises(StopIteration) as fin:
         gen.send([10])

@@ -3,7 +3,6 @@
 nine mutants every one of which is told from the rule at least three times, the columns, their gate and their round trip, the
 parser, the header's prototype and the export lists, the host plan of the call under the sanitizers as a program of its own
 (tools/revote_check.cpp), and cli.main on an engine whose entries are the statements."""
-import inspect
 import os
 import re
 import subprocess
@@ -20,7 +19,7 @@ import test_realign_cpu as TR
 import test_signature_cpu as TS
 from conftest import ROOT
 from vapor_amd import _lib as L
-from vapor_amd import cli, drivers, junction, modes, pipeline, polish, realign, revote, seqio, synth
+from vapor_amd import cli, junction, pipeline, polish, realign, revote, seqio, synth
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -191,13 +190,6 @@ def test_the_flag_parses_and_the_help_text_is_unchanged(monkeypatch):
     with open(os.path.join(ROOT, "tests", "golden", "cli_help.txt")) as f:
         assert p.format_help() == f.read()
     assert "--realign-revote" not in p.format_help() and "--realign-revote" not in p.format_usage()
-    m = modes.realign_revote()
-    assert m.name == "realign" and m.sink is None and m.polish and m.revote and not m.junction and m.COLUMNS == polish.COLUMNS + revote.COLUMNS
-    sink = object()
-    m = modes.realign_revote(sink, True)
-    assert m.sink is sink and m.polish and m.junction and m.revote and m.COLUMNS == junction.COLUMNS + revote.COLUMNS and m.keys == m.COLUMNS
-    assert not modes.REALIGN.revote and not modes.realign_polish().revote and not modes.realign_junction().revote
-    assert list(inspect.signature(modes.realign_revote).parameters) == ["sink", "junction"]
 
 
 def test_refused_without_realign_polish(capsys):
@@ -205,31 +197,6 @@ def test_refused_without_realign_polish(capsys):
         TR._refused([cmd] + TR.BASE + ["--realign-revote"], "--realign-revote needs --realign-polish", capsys)
     TR._refused(["bed"] + TR.BASE + ["--realign", "--realign-revote"], "--realign-revote needs --realign-polish", capsys)
     TR._refused(["vcf"] + TR.BASE + ["--realign", "--realign-out", "pre", "--realign-revote"], "--realign-revote needs --realign-polish", capsys)
-
-
-def test_the_request_and_the_wrappers():
-    # (the constructor's parameters are pinned by tests/test_junction_cpu.py: `revote` is an attribute, off until the wrapper sets it)
-    assert list(inspect.signature(drivers.Realign.__init__).parameters)[1:] == ["ref_seq", "alt_seq", "reads", "name", "trace", "polish", "junction"]
-    r = drivers.Realign("A", "C", [])
-    assert (r.trace, r.polish, r.junction, r.revote) == (False, False, False, False) and "revote" in drivers.Realign.__slots__
-
-    def _one_score():
-        got = yield drivers.Score("s1", "ACGT", "ACT", [("ACGT", 0)], 10)
-        return got
-    for wrapper, args, want in ((drivers.vapor_realign_revote, ("k", False, False), (True, False, True)),
-                                (drivers.vapor_realign_revote, ("k", True, True), (True, True, True)),
-                                (drivers.vapor_realign_junction, ("k", False), (True, True, False)),
-                                (drivers.vapor_realign_polish, ("k", False), (True, False, False))):
-        gen = wrapper(*args, _one_score)
-        req = next(gen)
-        assert isinstance(req, drivers.Score)
-        req = gen.send([0.5])
-        assert isinstance(req, drivers.Realign) and (req.polish, req.junction, req.revote) == want and req.trace == bool(args[1])
-    assert list(inspect.signature(drivers.vapor_realign).parameters) == ["driver", "args"]
-    assert list(inspect.signature(drivers.vapor_realign_out).parameters) == ["name", "driver", "args"]
-    assert list(inspect.signature(drivers.vapor_realign_polish).parameters) == ["name", "trace", "driver", "args"]
-    assert list(inspect.signature(drivers.vapor_realign_junction).parameters) == ["name", "trace", "driver", "args"]
-    assert list(inspect.signature(drivers.vapor_realign_revote).parameters) == ["name", "trace", "junction", "driver", "args"]
 
 
 # ------------------------------------------------------------------------------------------------------------------------------

@@ -428,15 +428,7 @@ def _simple_job(name, info, key, fig, row_prefix, label, plt_li, ctx, mode, with
         cost = job_cost(name, span, views=_views_n(name, span))
     elif kind == 'realign':
         # (every read meets both alleles once more, in a band: about the cost of the locus again; the array route has no second pass)
-        call = (drivers.vapor_realign, _SIMPLE[name], n_cff, plt_li, bam_in, ref, info, fig, False)
-        if mode.revote:                      # (`--realign-revote`: the polish's request, asking for the second vote as well)
-            call = (drivers.vapor_realign_revote, key, mode.sink is not None, mode.junction) + call[1:]
-        elif mode.junction:                  # (`--realign-junction`: the polish's request, asking for the junction as well)
-            call = (drivers.vapor_realign_junction, key, mode.sink is not None) + call[1:]
-        elif mode.polish:                    # (`--realign-polish`: the request asks for the consensus too, with a sink for the traces as well)
-            call = (drivers.vapor_realign_polish, key, mode.sink is not None) + call[1:]
-        elif mode.sink is not None:          # (`--realign-out`: the same wrapper, its Realign request named and asking for traces)
-            call = (drivers.vapor_realign_out, key) + call[1:]
+        call = _realign_call(mode, key, (_SIMPLE[name], n_cff, plt_li, bam_in, ref, info, fig, False))
         cost, spec = 2 * job_cost(name, span), None
     else:
         call = (_SIMPLE[name], n_cff, plt_li, bam_in, ref, info, fig, mode is not None and mode.phased)
@@ -444,20 +436,17 @@ def _simple_job(name, info, key, fig, row_prefix, label, plt_li, ctx, mode, with
     return Job(key, None, None, row_prefix, label, cost, spec, ctx, call)
 
 
+def _realign_call(mode, key, call):
+    """`call` = (driver, *args) under `--realign`: drivers.vapor_realign around it, with the mode's options and the locus's key -
+    the name of its Realign request where the options ask for traces."""
+    return (drivers.vapor_realign, mode.options, key) + call
+
+
 def _ins_job(call, cost, spec, mode, key=None):
     """(call, cost, array-route description) of an INS locus: as given, and under `--realign` drivers.vapor_realign around the
-    call, about twice its cost, on the drivers' route (no description), as _simple_job has it for the other three types
-    (under `--realign-out` drivers.vapor_realign_out, named `key`)."""
+    call, about twice its cost, on the drivers' route (no description), as _simple_job has it for the other three types."""
     if mode is not None and mode.name == 'realign':
-        if mode.revote:
-            return (drivers.vapor_realign_revote, key, mode.sink is not None, mode.junction) + call, 2 * cost, None
-        if mode.junction:
-            return (drivers.vapor_realign_junction, key, mode.sink is not None) + call, 2 * cost, None
-        if mode.polish:
-            return (drivers.vapor_realign_polish, key, mode.sink is not None) + call, 2 * cost, None
-        if mode.sink is not None:
-            return (drivers.vapor_realign_out, key) + call, 2 * cost, None
-        return (drivers.vapor_realign,) + call, 2 * cost, None
+        return _realign_call(mode, key, call), 2 * cost, None
     return call, cost, spec
 
 
@@ -1141,22 +1130,18 @@ def _main(argv, held) -> int:
         mode = modes.LINKS
     elif args.support:
         mode = modes.SUPPORT
-    elif args.realign:
-        mode = modes.REALIGN
     figure_fn = None
     if not args.no_figures:
         from . import figures
         figure_fn = figures.make_event_figure_1
         figures.warm()                  # (the drawing processes start while the input is parsed and the first batch scored)
     vdist.init_from_env()
-    if mode is modes.REALIGN and args.realign_polish:
-        from . import polish
-        sink = polish.PolishWriter(args.realign_out, vdist.rank(), vdist.world()) if args.realign_out is not None else None
-        mode = (modes.realign_revote(sink, args.realign_junction) if args.realign_revote else
-                modes.realign_junction(sink) if args.realign_junction else modes.realign_polish(sink))
-    elif mode is modes.REALIGN and args.realign_out is not None:
-        from . import realign
-        mode = modes.realign_out(realign.TraceWriter(args.realign_out, vdist.rank(), vdist.world()))
+    if args.realign:
+        # (what the run asks beside the votes, and with `--realign-out` the sink of the rank's traces)
+        from . import polish, realign
+        options = realign.Options(args.realign_out is not None, args.realign_polish, args.realign_junction, args.realign_revote)
+        writer = polish.PolishWriter if options.polish else realign.TraceWriter
+        mode = modes.realign(options, writer(args.realign_out, vdist.rank(), vdist.world()) if options.trace else None)
     out_path = SF.path_modify(args.output_path)
     SF.path_mkdir(out_path)
     sample_name = '.'.join(args.sv_input.split('/')[-1].split('.')[:-1])

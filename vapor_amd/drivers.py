@@ -21,7 +21,7 @@ from __future__ import annotations
 
 from typing import List
 
-from . import seqio
+from . import realign, seqio
 
 default_flank_length = 500       # SF:21-22
 default_max_sv_test = 10000      # SF:25-26
@@ -599,20 +599,20 @@ def vapor_refine(svtype, num_reads_cff, plt_li, bam_in, ref, sv_info, out_figure
 class Realign:
     """`--realign`: the reads of a Score request against its two alleles.  Result: a realign.Payload - per read
     its edit distance to ref_seq[miss_bp:] minus that to alt_seq[miss_bp:] - or None when a pair came back with a status.
-    `trace` (`--realign-out`; off unless asked): the payload also carries `.traces`, every read's alignment to the
-    allele it fits; `name`: the locus as the files spell it.  `polish` (`--realign-polish`; off unless asked): the
-    payload also carries `.polish`, the consensus of the ALT voters on the alt allele.  `junction` (`--realign-junction`, DESIGN.md
-    4.26; off unless asked, and only with `polish`): the payload also carries `.junction`, the one jump of the polished allele
-    beside that of the call's.  `revote` (`--realign-revote`; off, and only with `polish`): an attribute the
-    wrapper sets on the request it makes, not an argument - the constructor's parameters stay the seven they were -; the payload
-    then also carries `.revote`, every read's distance to the polished allele."""
-    __slots__ = ("ref_seq", "alt_seq", "reads", "name", "trace", "polish", "junction", "revote")
+    `options` (a realign.Options; nothing asked by default) says what else the payload is to carry, each on the attribute of the
+    flag's name: `trace` (`--realign-out`) every read's alignment to the allele it fits, as `.traces`, with
+    `name` the locus as the files spell it; `polish` (`--realign-polish`, 4.25) the consensus of the ALT voters on the alt
+    allele; `junction` (`--realign-junction`, 4.26) the one jump of the polished allele beside that of the call's; `revote`
+    (`--realign-revote`, 4.27) every read's distance to the polished allele.  The four flags read through the request."""
+    __slots__ = ("ref_seq", "alt_seq", "reads", "name", "options")
 
-    def __init__(self, ref_seq, alt_seq, reads, name=None, trace=False, polish=False, junction=False):
-        self.ref_seq, self.alt_seq, self.reads, self.name, self.trace = ref_seq, alt_seq, reads, name, bool(trace)
-        self.polish = bool(polish)
-        self.junction = bool(junction)
-        self.revote = False
+    def __init__(self, ref_seq, alt_seq, reads, name=None, options=realign.Options()):
+        self.ref_seq, self.alt_seq, self.reads, self.name, self.options = ref_seq, alt_seq, reads, name, options
+
+    trace = property(lambda self: self.options.trace)
+    polish = property(lambda self: self.options.polish)
+    junction = property(lambda self: self.options.junction)
+    revote = property(lambda self: self.options.revote)
 
 
 class Realigned(list):
@@ -621,36 +621,11 @@ class Realigned(list):
     realign = None
 
 
-def vapor_realign(driver, *args):
+def vapor_realign(options, name, driver, *args):
     """`--realign` for a DEL, INV, TANDUP or INS locus: the type's own driver runs as it is - its requests, its figure, its
-    scores: the row's own columns - and the last Score request whose answer was a list is asked once more as a Realign request,
-    whichever branch made it (the short window and the junction window are both just a Score request)."""
-    return (yield from _realign(None, False, driver, args))
-
-
-def vapor_realign_out(name, driver, *args):
-    """`--realign --realign-out`: vapor_realign whose Realign request carries the locus's name and asks for the traces."""
-    return (yield from _realign(name, True, driver, args))
-
-
-def vapor_realign_polish(name, trace, driver, *args):
-    """`--realign --realign-polish`: vapor_realign whose Realign request asks for the polish; with `trace` (`--realign-out` as
-    well) it carries the locus's name and asks for the traces too."""
-    return (yield from _realign(name if trace else None, bool(trace), driver, args, True))
-
-
-def vapor_realign_junction(name, trace, driver, *args):
-    """`--realign --realign-polish --realign-junction`: vapor_realign_polish whose Realign request asks for the junction too."""
-    return (yield from _realign(name if trace else None, bool(trace), driver, args, True, True))
-
-
-def vapor_realign_revote(name, trace, junction, driver, *args):
-    """`--realign --realign-polish --realign-revote`: vapor_realign_polish whose Realign request asks for the second vote too,
-    and with `junction` (`--realign-junction` as well) for the junction."""
-    return (yield from _realign(name if trace else None, bool(trace), driver, args, True, bool(junction), True))
-
-
-def _realign(name, trace, driver, args, polish=False, junction=False, revote=False):
+    scores: the row's own columns - and the last Score request whose answer was a list is asked once more as a Realign request
+    with the run's `options`, whichever branch made it (the short window and the junction window are both just a Score request).
+    The request carries the locus's `name` where the options ask for traces."""
     gen = driver(*args)
     last = None
     try:
@@ -668,10 +643,7 @@ def _realign(name, trace, driver, args, polish=False, junction=False, revote=Fal
         scores = fin.value
     out = Realigned(scores if scores is not None else [])
     if last is not None:
-        req = (Realign(last.ref_seq, last.alt_seq, last.reads, name, True, polish, junction) if trace else
-               Realign(last.ref_seq, last.alt_seq, last.reads, polish=polish, junction=junction))
-        req.revote = bool(revote)
-        out.realign = yield req
+        out.realign = yield Realign(last.ref_seq, last.alt_seq, last.reads, name if options.trace else None, options)
     return out
 
 

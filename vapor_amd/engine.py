@@ -753,6 +753,27 @@ class Engine:
         """Whether the loaded library has vapor_realign_polish (the CPU twin of the C ABI has not)."""
         return self._available("vapor_realign_polish")
 
+    def _polish_marshal(self, who, seqset, pairs, band, tables, want_counts):
+        """What the calls of vapor_realign_polish and vapor_realign_revote share: (args, outs, tabs, pairs) - the entries' thirteen
+        leading arguments; the five outputs behind them, cut to the call's loci and columns; `tables` (first, col_off and what
+        the entry has beside them, one entry a locus and one more each) as int64 arrays; and the pair table `args` points into."""
+        from . import polish
+        pairs = np.ascontiguousarray(pairs, dtype=L.PAIR_DTYPE)
+        tabs = [np.ascontiguousarray(t, dtype=np.int64) for t in tables]
+        if any(len(t) != len(tabs[0]) for t in tabs) or len(tabs[0]) < 1:
+            raise ValueError("%s hold one entry a locus and one more" % who)
+        n, ng = len(pairs), len(tabs[0]) - 1
+        cols = max(int(tabs[1][-1]), 0)
+        stats = np.zeros((max(ng, 1), 8), dtype=np.int32)
+        calls = np.zeros(max(cols, 1), dtype=np.uint8)
+        sites = np.zeros((max(ng, 1), polish.MAX_SITES, 2), dtype=np.int32)
+        ins = np.zeros((max(ng, 1), polish.MAX_SITES, polish.RMAX), dtype=np.uint8)
+        counts = np.zeros((max(cols, 1), 8), dtype=np.uint32) if want_counts else None
+        args = (self._ctx, seqset._h, n, pairs.ctypes.data if n else None, int(band), ng, L.ptr(tabs[0], ctypes.c_int64),
+                L.ptr(tabs[1], ctypes.c_int64), L.ptr(stats, ctypes.c_int32), L.ptr(calls, ctypes.c_uint8), L.ptr(sites, ctypes.c_int32),
+                L.ptr(ins, ctypes.c_uint8), L.ptr(counts, ctypes.c_uint32) if want_counts else None)
+        return args, (stats[:ng], calls[:cols], sites[:ng], ins[:ng], counts[:cols] if want_counts else None), tabs, pairs
+
     def realign_polish(self, seqset: SeqSet, pairs: np.ndarray, band: int, first, col_off, want_counts: bool = False):
         """(stats, calls, sites, ins, counts) of every locus (vapor_realign_polish): the pairs of locus g are first[g] ..
         first[g + 1], all against the locus's allele, whose columns are col_off[g] .. col_off[g + 1].  stats (n_loci, 8) int32,
@@ -761,24 +782,10 @@ class Engine:
         with want_counts, else None (polish.statement says what they hold).  A locus the entry refuses has status E_ARG or
         E_NOMEM, zero statistics and every column KEEP.
         NotImplementedError where the library has no such entry: there is no other route."""
-        from . import polish
         fn = self._wide_entry("vapor_realign_polish", "pileup kernels (--realign-polish)")
-        pairs = np.ascontiguousarray(pairs, dtype=L.PAIR_DTYPE)
-        fl = np.ascontiguousarray(first, dtype=np.int64)
-        co = np.ascontiguousarray(col_off, dtype=np.int64)
-        if len(fl) != len(co) or len(fl) < 1:
-            raise ValueError("realign_polish: first and col_off hold one entry a locus and one more")
-        n, ng = len(pairs), len(fl) - 1
-        cols = max(int(co[-1]), 0)
-        stats = np.zeros((max(ng, 1), 8), dtype=np.int32)
-        calls = np.zeros(max(cols, 1), dtype=np.uint8)
-        sites = np.zeros((max(ng, 1), polish.MAX_SITES, 2), dtype=np.int32)
-        ins = np.zeros((max(ng, 1), polish.MAX_SITES, polish.RMAX), dtype=np.uint8)
-        counts = np.zeros((max(cols, 1), 8), dtype=np.uint32) if want_counts else None
-        L.check(fn(self._ctx, seqset._h, n, pairs.ctypes.data if n else None, int(band), ng, L.ptr(fl, ctypes.c_int64), L.ptr(co, ctypes.c_int64),
-                   L.ptr(stats, ctypes.c_int32), L.ptr(calls, ctypes.c_uint8), L.ptr(sites, ctypes.c_int32), L.ptr(ins, ctypes.c_uint8),
-                   L.ptr(counts, ctypes.c_uint32) if want_counts else None))
-        return stats[:ng], calls[:cols], sites[:ng], ins[:ng], counts[:cols] if want_counts else None
+        args, outs, _tabs, _pairs = self._polish_marshal("realign_polish: first and col_off", seqset, pairs, band, (first, col_off), want_counts)
+        L.check(fn(*args))
+        return outs
 
     # ---- `--realign-revote`: every read against the polished allele (DESIGN.md 4.27) ----
     def realign_revote_available(self) -> bool:
@@ -796,20 +803,10 @@ class Engine:
         NotImplementedError where the library has no such entry: there is no other route."""
         from . import polish
         fn = self._wide_entry("vapor_realign_revote", "re-vote kernels (--realign-revote)")
-        pairs = np.ascontiguousarray(pairs, dtype=L.PAIR_DTYPE)
+        args, outs, (_fl, co, vf), _pairs = self._polish_marshal("realign_revote: first, col_off and vfirst", seqset, pairs, band,
+                                                                 (first, col_off, vfirst), want_counts)
         votes = np.ascontiguousarray(votes, dtype=L.PAIR_DTYPE)
-        fl = np.ascontiguousarray(first, dtype=np.int64)
-        co = np.ascontiguousarray(col_off, dtype=np.int64)
-        vf = np.ascontiguousarray(vfirst, dtype=np.int64)
-        if len(fl) != len(co) or len(fl) != len(vf) or len(fl) < 1:
-            raise ValueError("realign_revote: first, col_off and vfirst hold one entry a locus and one more")
-        n, nv, ng = len(pairs), len(votes), len(fl) - 1
-        cols = max(int(co[-1]), 0)
-        stats = np.zeros((max(ng, 1), 8), dtype=np.int32)
-        calls = np.zeros(max(cols, 1), dtype=np.uint8)
-        sites = np.zeros((max(ng, 1), polish.MAX_SITES, 2), dtype=np.int32)
-        ins = np.zeros((max(ng, 1), polish.MAX_SITES, polish.RMAX), dtype=np.uint8)
-        counts = np.zeros((max(cols, 1), 8), dtype=np.uint32) if want_counts else None
+        nv, ng = len(votes), len(vf) - 1
         vout = np.zeros((max(nv, 1), 4), dtype=np.int32)
         lout = np.zeros((max(ng, 1), 4), dtype=np.int32)
         so = spelt = None
@@ -818,15 +815,13 @@ class Engine:
                 span = np.diff(co)
                 spelt_off = np.concatenate(([0], np.cumsum(span + polish.RMAX * np.minimum(span, polish.MAX_SITES))))
             so = np.ascontiguousarray(spelt_off, dtype=np.int64)
-            if len(so) != len(fl):
+            if len(so) != len(vf):
                 raise ValueError("realign_revote: spelt_off holds one entry a locus and one more")
             spelt = np.zeros(max(int(so.max()), 1), dtype=np.uint8)
-        L.check(fn(self._ctx, seqset._h, n, pairs.ctypes.data if n else None, int(band), ng, L.ptr(fl, ctypes.c_int64), L.ptr(co, ctypes.c_int64),
-                   L.ptr(stats, ctypes.c_int32), L.ptr(calls, ctypes.c_uint8), L.ptr(sites, ctypes.c_int32), L.ptr(ins, ctypes.c_uint8),
-                   L.ptr(counts, ctypes.c_uint32) if want_counts else None, nv, votes.ctypes.data if nv else None, L.ptr(vf, ctypes.c_int64),
-                   L.ptr(vout, ctypes.c_int32), L.ptr(lout, ctypes.c_int32), L.ptr(so, ctypes.c_int64) if want_spelt else None,
+        L.check(fn(*args, nv, votes.ctypes.data if nv else None, L.ptr(vf, ctypes.c_int64), L.ptr(vout, ctypes.c_int32),
+                   L.ptr(lout, ctypes.c_int32), L.ptr(so, ctypes.c_int64) if want_spelt else None,
                    L.ptr(spelt, ctypes.c_uint8) if want_spelt else None))
-        return (stats[:ng], calls[:cols], sites[:ng], ins[:ng], counts[:cols] if want_counts else None, vout[:nv], lout[:ng], so, spelt)
+        return outs + (vout[:nv], lout[:ng], so, spelt)
 
     # ---- `--realign-junction`: the one jump between the two sequences of a pair ----
     def realign_junction_available(self) -> bool:

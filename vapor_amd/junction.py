@@ -17,7 +17,7 @@ NONE, DEL, INS = range(3)                                            # the type 
 TYPES = ("NONE", "DEL", "INS")
 COST0, LEFT0, RIGHT0, GLEN0, COST, LEFT, RIGHT, GLEN, TYPE = range(9)  # what a locus's Junction holds
 
-INFO = polish.INFO + (
+_INFO = (
     ("VaPoR_RA_JT", "String", "1", "The event the polished alt allele carries against its window: DEL, INS or NONE (--realign-junction)"),
     ("VaPoR_RA_JLEN", "Integer", "1", "Length of that event (--realign-junction)"),
     ("VaPoR_RA_JLEN0", "Integer", "1", "Length of the event of the call's own alt allele, by the same rule (--realign-junction)"),
@@ -25,7 +25,6 @@ INFO = polish.INFO + (
     ("VaPoR_RA_JDR", "Integer", "1", "Right end of the polished allele's event minus that of the call's, in bases (--realign-junction)"),
     ("VaPoR_RA_JCOST", "Integer", "1", "Edits the polished allele still has against its best one-jump reading (--realign-junction)"),
 )
-COLUMNS = tuple(i[0] for i in INFO)
 
 _BIG = 1 << 28                 # a cell that does not exist
 
@@ -119,10 +118,9 @@ class Junction:
 def applies(p) -> bool:
     """Whether the lens applies to a payload: it has a pile of status 0 with at least MIN_COV reads, both pairs came back (it
     carries a Junction) and the call's own allele is exactly one jump of its window (cost0 == 0)."""
-    po = getattr(p, "polish", None) if p is not None else None
-    jn = getattr(p, "junction", None) if p is not None else None
-    return (po is not None and jn is not None and po.stats[polish.STATUS] == 0 and po.stats[polish.PAIRS] >= polish.MIN_COV and
-            jn.vals[COST0] == 0)
+    if p is None or p.polish is None or p.junction is None:
+        return False
+    return p.polish.stats[polish.STATUS] == 0 and p.polish.stats[polish.PAIRS] >= polish.MIN_COV and p.junction.vals[COST0] == 0
 
 
 def six(p) -> List[str]:
@@ -133,27 +131,9 @@ def six(p) -> List[str]:
     return [TYPES[v[TYPE]], str(v[GLEN]), str(v[GLEN0]), str(v[LEFT] - v[LEFT0]), str(v[RIGHT] - v[RIGHT0]), str(v[COST])]
 
 
-def columns(p) -> List[str]:
-    return polish.columns(p) + six(p)
-
-
-def pack(p) -> List[float]:
-    """polish.pack's floats, then 1 and the nine integers where the payload carries a Junction, 0 where not."""
-    if p is None:
-        return []
-    jn = getattr(p, "junction", None)
-    return polish.pack(p) + ([1.0] + [float(v) for v in jn.vals] if jn is not None else [0.0])
-
-
-def unpack(flat):
-    p = polish.unpack(flat)
-    if p is None:
-        return None
-    at = 1 + int(flat[0])                                                 # polish's flag, eight statistics behind a 1
-    at += 1 + (8 if len(flat) > at and int(flat[at]) == 1 else 0)
-    p.junction = Junction(flat[at + 1:at + 10]) if len(flat) > at and int(flat[at]) == 1 else None
-    return p
-
-
-def columns_many(payloads) -> List[List[str]]:
-    return [columns(p) for p in payloads]
+# (the section: the nine integers travel; and the surface of a run with `--realign-junction`, polish's columns then the six)
+SECTION = realign.Section("junction", _INFO, six, lambda jn: jn.vals, lambda flat, at: (Junction(flat[at:at + 9]), at + 9))
+SECTIONS = polish.SECTIONS + (SECTION,)
+_CHAIN = realign.Chain(SECTIONS)
+INFO, COLUMNS = _CHAIN.INFO, _CHAIN.COLUMNS
+columns, pack, unpack, columns_many = _CHAIN.columns, _CHAIN.pack, _CHAIN.unpack, _CHAIN.columns_many

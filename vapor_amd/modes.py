@@ -5,8 +5,8 @@ its own module - refine.py, phase.py, bothends.py, depth.py, signature.py, links
 depth.py to support.py also say how their regions are read (their reader surface), and the parser states the rule once (cli.MODE_OPTIONS)."""
 from __future__ import annotations
 
-from . import bothends, depth, junction, links, phase, polish, realign, revote, signature, support
-from . import junction as _junction            # (realign_revote's `junction` argument hides the module's name)
+from . import bothends, depth, junction, links, phase, polish, revote, signature, support
+from . import realign as _realign
 from . import refine as _refine
 
 
@@ -22,13 +22,12 @@ class Mode:
     is one function over their module's reader surface (cli._evidence_payloads).
     `--refine`'s own: `margin_step` = (M, T), and `ci_of` (cli.vcf_ci_readin: the bounds of a VCF record's candidates).
     `sink`: None, or an object with take(job index, key, payload) that is shown every locus a rank scores, from the chunk's
-    thread (`--realign-out`: realign.TraceWriter)."""
+    thread (`--realign-out`: realign.TraceWriter).  `options`: `--realign`'s realign.Options, what its Realign requests ask for;
+    None for every other mode."""
     chunk_gens = None
     chunk_payloads = None
     sink = None
-    polish = False                             # (`--realign-polish`: the Realign requests ask for the consensus too)
-    junction = False                           # (`--realign-junction`: ... and for the one jump of the polished allele)
-    revote = False                             # (`--realign-revote`: ... and for every read's distance to the polished allele)
+    options = None
 
     def __init__(self, name, src, attr, keys=None, skip_dot=True, phased=False, margin_step=None, ci_of=None):
         self.name, self.attr, self.skip_dot, self.phased = name, attr, skip_dot, phased
@@ -49,41 +48,15 @@ DEPTH = Mode("depth", depth, "depth")
 SIGNATURES = Mode("signatures", signature, "signatures")
 LINKS = Mode("links", links, "links")
 SUPPORT = Mode("support", support, "support")
-REALIGN = Mode("realign", realign, "realign")
 
 
-def realign_out(sink) -> Mode:
-    """`--realign --realign-out PREFIX`: REALIGN's columns, with the sink the loci's traces go to."""
-    m = Mode("realign", realign, "realign")
-    m.sink = sink
+def realign(options=_realign.Options(), sink=None) -> Mode:
+    """`--realign` with what the run asks beside it: realign's seven columns, then those of the sections the
+    options name, in the order polish, junction, revote (4.25 - 4.27); `sink`, where the loci's traces go (`--realign-out`, 4.24:
+    realign.TraceWriter, polish.PolishWriter with `--realign-polish`)."""
+    m = Mode("realign", _realign.Chain(x.SECTION for x in (polish, junction, revote) if getattr(options, x.SECTION.attr)), "realign")
+    m.options, m.sink = options, sink
     return m
 
 
-def realign_polish(sink=None) -> Mode:
-    """`--realign --realign-polish`: REALIGN's columns followed by polish's six; with `--realign-out` the sink
-    the loci's traces and polished alleles go to (polish.PolishWriter)."""
-    m = Mode("realign", polish, "realign")
-    m.sink = sink
-    m.polish = True
-    return m
-
-
-def realign_junction(sink=None) -> Mode:
-    """`--realign --realign-polish --realign-junction`: realign_polish's columns followed by junction's six,
-    with realign_polish's sink."""
-    m = Mode("realign", junction, "realign")
-    m.sink = sink
-    m.polish = True
-    m.junction = True
-    return m
-
-
-def realign_revote(sink=None, junction=False) -> Mode:
-    """`--realign --realign-polish --realign-revote`: realign_polish's columns - with `junction`
-    (`--realign-junction` as well) realign_junction's - followed by revote's eight, with realign_polish's sink."""
-    m = Mode("realign", revote.over(_junction if junction else polish), "realign")
-    m.sink = sink
-    m.polish = True
-    m.junction = bool(junction)
-    m.revote = True
-    return m
+REALIGN = realign()

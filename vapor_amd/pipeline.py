@@ -553,29 +553,30 @@ def realign_requests(engine, reqs: Sequence[object]) -> List[object]:
             sb.seqs.append(x[0])                             # (reads are never shared between requests: no look-up)
             rows += [(q, ri, int(x[1])), (q, ai, int(x[1]))]
     first.append(len(rows))
-    if not rows:
-        out = [realign.Payload() for _ in reqs]
-        if any(r.polish for r in reqs):
-            _realign_polish(engine, None, reqs, out, None, first)
-        return out                            # (an empty pile has fewer than MIN_COV reads: no junction applies)
-    n_lit = len(sb.seqs)
-    pairs = np.zeros(len(rows), dtype=L.PAIR_DTYPE)
-    tab = np.asarray(rows, dtype=np.int64)
-    pairs["seq1"] = tab[:, 0]
-    pairs["seq2"] = np.where(tab[:, 1] < 0, n_lit - 1 - tab[:, 1], tab[:, 1])       # derived sequence d: behind the literals
-    pairs["off2"] = tab[:, 2]
-    ss = engine.seqset(sb.seqs, None, sb.derived) if sb.derived else engine.seqset(sb.seqs)
+    ss = pairs = d = None                  # (a batch without a read has no set, no table and nothing to trace)
     try:
-        d, st = engine.realign(ss, pairs, realign.BAND)
-        out = [realign.payload(d[a:b:2], d[a + 1:b:2], st[a:b:2], st[a + 1:b:2]) for a, b in zip(first[:-1], first[1:])]
-        if any(r.trace for r in reqs):
+        if rows:
+            n_lit = len(sb.seqs)
+            pairs = np.zeros(len(rows), dtype=L.PAIR_DTYPE)
+            tab = np.asarray(rows, dtype=np.int64)
+            pairs["seq1"] = tab[:, 0]
+            pairs["seq2"] = np.where(tab[:, 1] < 0, n_lit - 1 - tab[:, 1], tab[:, 1])       # derived sequence d: behind the literals
+            pairs["off2"] = tab[:, 2]
+            ss = engine.seqset(sb.seqs, None, sb.derived) if sb.derived else engine.seqset(sb.seqs)
+            d, st = engine.realign(ss, pairs, realign.BAND)
+            out = [realign.payload(d[a:b:2], d[a + 1:b:2], st[a:b:2], st[a + 1:b:2]) for a, b in zip(first[:-1], first[1:])]
+        else:
+            out = [realign.Payload() for _ in reqs]
+        # the steps the requests' options ask for, in their order; the junction's call has a set of its own
+        if ss is not None and any(r.trace for r in reqs):
             _realign_traces(engine, ss, reqs, out, pairs, d, first)
         if any(r.polish for r in reqs):
             _realign_polish(engine, ss, reqs, out, pairs, first, d)
     finally:
-        ss.close()
+        if ss is not None:
+            ss.close()
     if any(r.junction for r in reqs):
-        _realign_junction(engine, reqs, out)
+        _realign_junction(engine, reqs, out)     # (an empty pile has fewer than MIN_COV reads: no junction applies)
     return out
 
 
@@ -634,7 +635,7 @@ def _realign_polish(engine, ss, reqs, out, pairs, first, d=None) -> None:
         if not r.polish or out[t] is None:
             continue
         if not r.reads:
-            out[t].polish = polish.Polish([0] * 8, str(r.alt_seq) if getattr(out[t], "traces", None) is not None else None)
+            out[t].polish = polish.Polish([0] * 8, str(r.alt_seq) if out[t].traces is not None else None)
             continue
         mine = [a + 2 * k + 1 for k, diff in enumerate(out[t]) if diff >= realign.MARGIN]
         pick += mine
@@ -692,7 +693,7 @@ def _realign_junction(engine, reqs, out) -> None:
     sb = _SetBuilder()
     rows, who, cut = [], [], []              # (`cut`: the described windows, alive while the builder keys them by id)
     for t, r in enumerate(reqs):
-        po = getattr(out[t], "polish", None) if out[t] is not None else None
+        po = out[t].polish if out[t] is not None else None
         if not r.junction or po is None or po.text is None or po.stats[polish.STATUS] != 0 or po.stats[polish.PAIRS] < polish.MIN_COV:
             continue
         lo, n_win = _lens_window(r)

@@ -20,7 +20,7 @@ KEEP, DELETE, SITE_BIT = 4, 5, 8                                     # the call 
 A, C, G, T, O, DL, BCOV, INS = range(8)                              # a column's counters
 STATUS, PAIRS, PCOV, PSUB, PDEL, SITES, PINS, DROPPED = range(8)     # a locus's statistics
 
-INFO = realign.INFO + (
+_INFO = (
     ("VaPoR_RA_PN", "Integer", "1", "Reads that vote for the alt allele and are piled on it (--realign-polish)"),
     ("VaPoR_RA_PCOV", "Integer", "1", "Columns of the alt allele that at least 3 piled reads cover (--realign-polish)"),
     ("VaPoR_RA_PSUB", "Integer", "1", "Columns where a strict majority of the piled reads holds another base (--realign-polish)"),
@@ -28,7 +28,6 @@ INFO = realign.INFO + (
     ("VaPoR_RA_PINS", "Integer", "1", "Bases that a strict majority of the piled reads inserts (--realign-polish)"),
     ("VaPoR_RA_PID", "Float", "1", "Identity of the alt allele to the piled reads, 1 - (PSUB + PDEL + PINS) / PCOV (--realign-polish)"),
 )
-COLUMNS = tuple(i[0] for i in INFO)
 
 
 def statement(reads_with_off2, allele, band: int):
@@ -151,36 +150,18 @@ def identity(stats) -> Optional[str]:
 
 def six(p) -> List[str]:
     """The six columns behind realign's: '.' without a payload, without a pile, or for a locus whose status is not 0."""
-    po = getattr(p, "polish", None) if p is not None else None
-    if po is None or po.stats[STATUS] != 0:
+    if p is None or p.polish is None or p.polish.stats[STATUS] != 0:
         return ["."] * 6
-    s = po.stats
+    s = p.polish.stats
     return [str(s[PAIRS]), str(s[PCOV]), str(s[PSUB]), str(s[PDEL]), str(s[PINS]), identity(s) or "."]
 
 
-def columns(p) -> List[str]:
-    return realign.columns(p) + six(p)
-
-
-def pack(p) -> List[float]:
-    """realign.pack's floats, then 1 and the eight statistics where the payload carries a pile, 0 where not."""
-    if p is None:
-        return []
-    po = getattr(p, "polish", None)
-    return realign.pack(p) + ([1.0] + [float(v) for v in po.stats] if po is not None else [0.0])
-
-
-def unpack(flat):
-    p = realign.unpack(flat)
-    if p is None:
-        return None
-    at = 1 + int(flat[0])
-    p.polish = Polish(flat[at + 1:at + 9]) if len(flat) > at and int(flat[at]) == 1 else None
-    return p
-
-
-def columns_many(payloads) -> List[List[str]]:
-    return [columns(p) for p in payloads]
+# (the section: the eight statistics travel; and the surface of a run with `--realign-polish` alone, realign's columns then the six)
+SECTION = realign.Section("polish", _INFO, six, lambda po: po.stats, lambda flat, at: (Polish(flat[at:at + 8]), at + 8))
+SECTIONS = (SECTION,)
+_CHAIN = realign.Chain(SECTIONS)
+INFO, COLUMNS = _CHAIN.INFO, _CHAIN.COLUMNS
+columns, pack, unpack, columns_many = _CHAIN.columns, _CHAIN.pack, _CHAIN.unpack, _CHAIN.columns_many
 
 
 class PolishWriter(realign.TraceWriter):
@@ -194,21 +175,14 @@ class PolishWriter(realign.TraceWriter):
 
     def take(self, order: int, key: str, payload) -> None:
         super().take(order, key, payload)
-        po = getattr(payload, "polish", None)
+        po = payload.polish if payload is not None else None
         if po is not None and po.text is not None:
             with self._lock:
                 self._polished[int(order)] = (key, po.text)
 
     def close(self):
         names = super().close()
-        seen, out = {}, []
-        for order in sorted(self._polished):
-            key, text = self._polished[order]
-            seen[key] = seen.get(key, 0) + 1
-            if seen[key] > 1:
-                key = "%s#%d" % (key, seen[key])
-            out.append(">%s|POL\n%s\n" % (key, text))
         with open(self.stem + ".pol.fa", "w") as f:
-            f.write("".join(out))
+            f.write("".join(">%s|POL\n%s\n" % kt for kt in realign.numbered(self._polished)))
         self._polished = {}
         return names + (self.stem + ".pol.fa",)

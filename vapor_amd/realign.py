@@ -7,6 +7,7 @@ call); there is no other route.  The genotype of the two counts is support.genot
 comparable."""
 from __future__ import annotations
 
+import collections
 from typing import List, Optional
 
 import numpy as np
@@ -17,6 +18,20 @@ BAND = 256                     # the band of the command line: a cell (i, j) exi
 MAX_BAND = 512                 # the widest band the kernel takes (VAPOR_MAX_BAND)
 MARGIN = 10                    # a read votes when its two distances differ by at least this (the smallest event the drivers take is
                                # 50 bp, whose expected difference is about the event's length): a rule, not a tolerance
+
+class Options(collections.namedtuple("Options", "trace polish junction revote")):
+    """What a `--realign` run asks beside the votes, the one place that spells the four: `trace` (`--realign-out`),
+    `polish` (`--realign-polish`, 4.25), `junction` (`--realign-junction`, 4.26) and `revote` (`--realign-revote`, 4.27); the last
+    two read the polished allele and need `polish`.  A flag beside `trace` names the section of its module (polish.SECTION, ..)
+    and the attribute of the Payload its object rides on."""
+    __slots__ = ()
+
+    def __new__(cls, trace=False, polish=False, junction=False, revote=False):
+        self = super().__new__(cls, bool(trace), bool(polish), bool(junction), bool(revote))
+        if (self.junction or self.revote) and not self.polish:
+            raise ValueError("realign: junction and revote need polish")
+        return self
+
 
 INFO = (
     ("VaPoR_RA_ALT", "Integer", "1", "Reads that align better to the alt allele, by at least 10 edits (--realign)"),
@@ -209,6 +224,15 @@ def sam_record(key: str, index: int, read) -> Optional[str]:
     return "\t".join(fields)
 
 
+def numbered(spool):
+    """The (key, value) entries of a writer's spool {job index: (key, value)} in job order, a repeated key with #2, #3, .."""
+    seen = {}
+    for order in sorted(spool):
+        key, value = spool[order]
+        seen[key] = seen.get(key, 0) + 1
+        yield (key if seen[key] == 1 else "%s#%d" % (key, seen[key])), value
+
+
 class TraceWriter:
     """The sink of `--realign-out PREFIX`: takes the loci a rank scores from any chunk thread, under a lock, and at close writes
     PREFIX.fa and PREFIX.sam (PREFIX.rank<k>.* on rank k of several) in job order, so that the files depend neither on the
@@ -223,19 +247,14 @@ class TraceWriter:
         self._spool = {}
 
     def take(self, order: int, key: str, payload) -> None:
-        traces = getattr(payload, "traces", None)
-        if traces is None:
+        if payload is None or payload.traces is None:
             return
         with self._lock:
-            self._spool[int(order)] = (key, traces)
+            self._spool[int(order)] = (key, payload.traces)
 
     def close(self):
-        seen, names, fasta, records = {}, [], [], []
-        for order in sorted(self._spool):
-            key, tr = self._spool[order]
-            seen[key] = seen.get(key, 0) + 1
-            if seen[key] > 1:
-                key = "%s#%d" % (key, seen[key])
+        names, fasta, records = [], [], []
+        for key, tr in numbered(self._spool):
             for tag, allele in (("REF", tr.ref), ("ALT", tr.alt)):
                 names.append(("%s|%s" % (key, tag), len(allele)))
                 fasta.append(">%s|%s\n%s\n" % (key, tag, allele))
@@ -264,7 +283,9 @@ def counts(diffs):
 
 
 class Payload(list):
-    """The reads' diffs, in read order."""
+    """The reads' diffs, in read order.  What the run's other options know of the locus rides on it, None unless set: `traces`
+    (a Traces, on the rank that scored it) and, one a section, `polish`, `junction` and `revote`."""
+    traces = polish = junction = revote = None
 
     def __init__(self, diffs=()):
         super().__init__(int(v) for v in diffs)
@@ -304,3 +325,48 @@ def unpack(flat) -> Optional[Payload]:
 
 def columns_many(payloads) -> List[List[str]]:
     return [columns(p) for p in payloads]
+
+
+class Section:
+    """What one `--realign-*` option adds behind the seven columns (polish.SECTION, junction.SECTION, revote.SECTION): `attr`,
+    the flag of Options that asks for it and the attribute of the Payload its object rides on; `INFO`, its own ##INFO tuples, and
+    `COLUMNS`; `columns(p)`, its own fields of a payload or of None, gate included; `floats(obj)`, its object as floats for the
+    gather, and `read(flat, at)` -> (obj, next), the object back from the floats that start at `at`."""
+
+    def __init__(self, attr, info, columns, floats, read):
+        self.attr, self.INFO, self.columns, self.floats, self.read = attr, tuple(info), columns, floats, read
+        self.COLUMNS = tuple(i[0] for i in self.INFO)
+
+
+class Chain:
+    """The surface of a `--realign` run for modes.Mode and the VCF writer: the seven columns, then those of `sections`, in order.
+    pack: `pack`'s floats, then per section 0 where the payload carries none of it, or 1 and the section's floats; unpack walks
+    that list once, every section reading its own floats from where the one before it stopped."""
+
+    def __init__(self, sections=()):
+        self.SECTIONS = tuple(sections)
+        self.INFO = INFO + tuple(i for s in self.SECTIONS for i in s.INFO)
+        self.COLUMNS = tuple(i[0] for i in self.INFO)
+
+    def columns(self, p) -> List[str]:
+        return columns(p) + [c for s in self.SECTIONS for c in s.columns(p)]
+
+    def pack(self, p) -> List[float]:
+        flat = pack(p)
+        for s in self.SECTIONS if p is not None else ():
+            obj = getattr(p, s.attr)
+            flat += [0.0] if obj is None else [1.0] + [float(v) for v in s.floats(obj)]
+        return flat
+
+    def unpack(self, flat) -> Optional[Payload]:
+        p = unpack(flat)
+        at = 1 + len(p) if p is not None else 0
+        for s in self.SECTIONS if p is not None else ():
+            at += 1
+            if len(flat) >= at and int(flat[at - 1]) == 1:
+                obj, at = s.read(flat, at)
+                setattr(p, s.attr, obj)
+        return p
+
+    def columns_many(self, payloads) -> List[List[str]]:
+        return [self.columns(p) for p in payloads]

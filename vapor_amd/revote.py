@@ -107,10 +107,10 @@ class Revote:
 def applies(p) -> bool:
     """The gate: the locus has a payload, its polish status is 0, at least MIN_COV reads were piled, its re-vote status is 0 and
     every vote pair came back with status 0 (a Revote of status 0 with a d_pol for every read)."""
-    po = getattr(p, "polish", None) if p is not None else None
-    rv = getattr(p, "revote", None) if p is not None else None
-    return (po is not None and rv is not None and po.stats[polish.STATUS] == 0 and po.stats[polish.PAIRS] >= polish.MIN_COV and
-            rv.status == 0 and len(rv.d_pol) == len(p))
+    if p is None or p.polish is None or p.revote is None:
+        return False
+    return (p.polish.stats[polish.STATUS] == 0 and p.polish.stats[polish.PAIRS] >= polish.MIN_COV and p.revote.status == 0 and
+            len(p.revote.d_pol) == len(p))
 
 
 def eight(p) -> List[str]:
@@ -124,44 +124,21 @@ def eight(p) -> List[str]:
     return realign.columns(realign.Payload(diff2)) + [str(gain)]
 
 
-class Source:
-    """The surface of a run with `--realign-revote` for modes.Mode: the source the columns follow - polish, or junction -, then
-    the eight.  pack: the source's floats, then 1, the status and the reads' d_pol and d_ref where the payload carries a Revote,
-    0 where not."""
-
-    def __init__(self, src):
-        self.src = src
-        self.INFO = src.INFO + INFO
-        self.COLUMNS = tuple(i[0] for i in self.INFO)
-
-    def columns(self, p) -> List[str]:
-        return self.src.columns(p) + eight(p)
-
-    def pack(self, p) -> List[float]:
-        if p is None:
-            return []
-        rv = getattr(p, "revote", None)
-        return self.src.pack(p) + ([1.0, float(rv.status), float(len(rv.d_pol))] + [float(v) for v in rv.d_pol + rv.d_ref] if rv is not None else [0.0])
-
-    def unpack(self, flat):
-        p = self.src.unpack(flat)
-        if p is None:
-            return None
-        at = len(self.src.pack(p))                                            # (what the source wrote, and reads back)
-        p.revote = None
-        if len(flat) > at and int(flat[at]) == 1:
-            n = int(flat[at + 2])
-            p.revote = Revote(flat[at + 1], flat[at + 3 + n:at + 3 + 2 * n], flat[at + 3:at + 3 + n])
-        return p
-
-    def columns_many(self, payloads) -> List[List[str]]:
-        return [self.columns(p) for p in payloads]
+def _read(flat, at):
+    """A Revote from its floats {status, n, d_pol x n, d_ref x n} at `at`, and where they end."""
+    n = int(flat[at + 1])
+    return Revote(flat[at], flat[at + 2 + n:at + 2 + 2 * n], flat[at + 2:at + 2 + n]), at + 2 + 2 * n
 
 
-def over(src) -> Source:
-    return Source(src)
+SECTION = realign.Section("revote", INFO, eight, lambda rv: (rv.status, len(rv.d_pol)) + rv.d_pol + rv.d_ref, _read)
+
+
+def over(src) -> realign.Chain:
+    """The surface of a run with `--realign-revote`: the sections of the source the columns follow - polish, or junction -, then
+    this one."""
+    return realign.Chain(src.SECTIONS + (SECTION,))
 
 
 # (the run without `--realign-junction`: polish's columns, then the eight)
-_PLAIN = Source(polish)
+_PLAIN = over(polish)
 columns, pack, unpack, columns_many = _PLAIN.columns, _PLAIN.pack, _PLAIN.unpack, _PLAIN.columns_many
