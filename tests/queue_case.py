@@ -21,9 +21,10 @@ def _rc(s):
 
 
 def bucket(kmer, nb_log2=15):
-    """join_kernel's bucket of a k = 10 k-mer (2-bit keys, one word): canon_hash of min(key, revcomp)."""
+    """join_kernel's bucket of a k = 10 k-mer (2-bit keys, one word of 20 bits): canon_hash of min(key, revcomp), which for a
+    key of at most 24 bits is the 24-bit multiply by 0xC2B2AF."""
     c = min(_key(kmer), _key(_rc(kmer)))
-    return ((c * 0x9E3779B1) & 0xFFFFFFFF) >> (32 - nb_log2)
+    return ((c * 0xC2B2AF) & 0xFFFFFFFF) >> (32 - nb_log2)
 
 
 def build(seed=5):

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import dot_designs
+import join_designs
 from conftest import load_golden
 
 pytestmark = pytest.mark.gpu
@@ -314,8 +315,9 @@ def test_run_records_expand_to_the_oracle_dots(eng, oracle):
         got = got[np.lexsort((got[:, 1], got[:, 0]))]
         assert st[t, 0] == len(exp) and got.tolist() == exp.tolist(), (t, rows[t])
         assert 0 < rec[t] <= st[t, 0]
-    assert rec[0] * 20 < st[0, 0]                 # an exact copy: 32 dots per record
-    assert rec[4] * 8 < st[4, 0]                  # a read with an N forms runs as well (they end before it)
+    for t in (0, 4):                              # an exact copy: 32 dots per record; a read with an N forms runs as well (they end before it)
+        s1, s2, off2, k, fl = rows[t]
+        assert rec[t] == join_designs.records(join_designs.Pair("row%d" % t, "parity", seqs[s1], seqs[s2], k, "", off2=off2, flags=fl)), t
     plan.close()
     _check_stats_vs_oracle(eng, oracle, seqs, [False] * len(seqs), rows, "runs")
 
