@@ -106,12 +106,12 @@ def own_groups(n, one_sided=False):
     return [(int(x), int(y)) for x, y in zip((a - d) // 2, (a + d) // 2)]
 
 
-# How many dots an LDS-staged list may hold, and what cluster_dual's counters then do (vapor_hip.hip):
-#   vapor_clean_hits asks clean_geom(rw, 4096) for the staged records, rw = ceil((max i + max j + 4) / 32) bitmap words for the
-#   batch; clean_geom_for starts from min(4096, CLEAN_HCAP_MAX = 8192) and only shrinks it while the LDS share of a workgroup is
-#   too small, so hcap <= 4096, and the share at one to three workgroups per CU holds all 4096 at every rw.  A list of more
+# How many dots an LDS-staged list may hold, and what cluster_dual's counters then do (vapor_clean_plan.h, namespace clean_plan):
+#   vapor_clean_hits asks geom(rw, LISTS_WANT = 4096) for the staged records, rw = ListPack's ceil((max i + max j + 4) / 32) bitmap
+#   words for the batch; geom_for starts from min(4096, CLEAN_HCAP_MAX = 8192) and only shrinks it while the LDS share of a workgroup
+#   is too small, so hcap <= 4096, and the share at one to three workgroups per CU holds all 4096 at every rw.  A list of more
 #   records goes to clean_big_kernel; 4096 is the most a staged list holds.
-#   clean_groups_lds(rw, hcap) = 2 * max((g + 1) / 2, rw * 32 / 100 + 8) with g = min(rw * 32 / 10 + 8, hcap) 16-bit counters;
+#   groups_lds(rw, hcap) = 2 * max((g + 1) / 2, rw * 32 / 100 + 8) with g = min(rw * 32 / 10 + 8, hcap) 16-bit counters;
 #   cluster_dual declines a list with groups_D + groups_A + 2 > that and leaves it to two cluster_axis passes.
 #   * rw = 1024 (clean_kernel<4>; both layouts fit three workgroups per CU there, so the dual one is used): i + j < 32 768 has
 #     room for 3 277 values 10 apart; g = 3 284 counters.  OWN_3270 has 3 270 + 3 270 groups: more than the counters hold.
@@ -510,7 +510,7 @@ def rw_of(cases):
 def small_cases(band=None, n_random=200):
     """Small lists (clean_kernel, one-dot records).  band None: the named and random designs; band 0 / 1 / 2: those plus the
     lists that put the batch's largest i + j into the band of clean_kernel<4> / <8> / <CLEAN_PER_MAX>.
-    launch_clean picks the instantiation by per = ceil(rw / 256) (<= 4, <= 8, else), rw = rw_of(batch): max i + max j <= 32 764
+    clean_plan::width picks the instantiation by per = ceil(rw / 256) (<= 4, <= 8, else), rw = rw_of(batch): max i + max j <= 32 764
     gives rw <= 1024, <= 65 532 gives rw <= 2048, and the corner 65 535 + 65 535 = 131 070 gives the cap, 4096."""
     base = [_case(d) for d in narrow_named()] + [_case(d) for d in random_designs(n_random)]
     if band is None:

@@ -52,6 +52,8 @@ static int fail(int code, const std::string& msg)
     g_err = msg;
     return code;
 }
+// a refusal of the plan headers (a code, and the message without the entry's name) as the entry's status
+static int refused(const std::string& entry, const vapor_image::Refusal& no) { return fail(no.code, entry + ": " + no.msg); }
 
 #define HIPCHK(expr)                                                                          \
     do {                                                                                      \
@@ -396,11 +398,9 @@ extern "C" int vapor_init(int device_ordinal, vapor_ctx** out)
     }
     hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     if (e != hipSuccess) { delete c; return fail(VAPOR_E_HIP, hipGetErrorString(e)); }
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&clean_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&clean_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&clean_kernel<CLEAN_PER_MAX>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&clean_big_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096);
+    for (const void* k : {reinterpret_cast<const void*>(&clean_kernel<4>), reinterpret_cast<const void*>(&clean_kernel<8>),
+                          reinterpret_cast<const void*>(&clean_kernel<CLEAN_PER_MAX>), reinterpret_cast<const void*>(&clean_big_kernel)})
+        if (e == hipSuccess) e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CLEAN_LDS_DYNAMIC_MAX);
     if (e != hipSuccess) { (void)hipStreamDestroy(c->stream); delete c; return fail(VAPOR_E_HIP, std::string("hipFuncSetAttribute(clean): ") + hipGetErrorString(e)); }
     c->own_stream = c->stream;
     { std::lock_guard<std::mutex> g(g_live_m); g_live_ctx.insert(c); }
@@ -1308,17 +1308,10 @@ extern "C" int vapor_plan_destroy(vapor_plan* p)
     return VAPOR_OK;
 }
 
-static_assert((2 * VAPOR_MAX_SEQ_LEN + 2 + 31) / 32 <= CLEAN_RANGE_WORDS_MAX, "cluster_axis sizes its per-thread word list for this");
-
-// lays out the hit workspace from hp[].cap and (re)allocates it
+// lays out the hit workspace from hp[].cap (clean_plan::lay_slots) and (re)allocates it
 static int plan_alloc_hits(vapor_plan* p)
 {
-    int64_t tot = 0;
-    for (auto& d : p->hp) {
-        d.hit_off = tot;
-        tot += (int64_t)((d.cap + 3u) & ~3u);
-    }
-    tot += 4;
+    const int64_t tot = clean_plan::lay_slots(p->hp, p->serve);
     HIPCHK(hipStreamSynchronize(p->ctx->stream));      // (a rerun: nothing may still read the old slots when they are reused)
     dfree(p->ctx, p->d_hits); p->d_hits = nullptr;
     dfree(p->ctx, p->d_hflags); p->d_hflags = nullptr;
@@ -1326,11 +1319,8 @@ static int plan_alloc_hits(vapor_plan* p)
     HIPCHK(dmalloc(p->ctx, (void**)&p->d_hflags, (size_t)tot));
     p->total_cap = tot;
     HIPCHK(hipMemcpyAsync(p->d_pairs, p->hp.data(), sizeof(DPair) * p->hp.size(), hipMemcpyHostToDevice, p->ctx->stream));
-    if (p->n_dpairs) {                                  // the served pairs' view of the shared dot plots' slots
-        for (auto& sv : p->serve)
-            if (sv.dpair >= 0) { sv.hit_off = p->hp[(size_t)sv.dpair].hit_off; sv.cap = p->hp[(size_t)sv.dpair].cap; }
+    if (p->n_dpairs)                                    // the served pairs' view of the shared dot plots' slots
         HIPCHK(hipMemcpyAsync(p->d_serve, p->serve.data(), sizeof(DServe) * p->serve.size(), hipMemcpyHostToDevice, p->ctx->stream));
-    }
     return VAPOR_OK;
 }
 
@@ -1381,7 +1371,7 @@ extern "C" int vapor_plan_create(vapor_ctx* ctx, vapor_seqset* set, int64_t n_pa
     }
     // (a plan of many rounds of clean workgroups has no tail worth ordering for - cfg3's 62 rounds gain nothing - and sorting
     // 80 000 pairs costs a pipeline chunk's plan 3-4 ms: the order is made for plans of up to eight rounds)
-    if (ctx->clean_order && n_pairs > 1 && n_pairs <= (int64_t)8 * (2048 / CLEAN_THREADS) * ctx->n_cus) {
+    if (ctx->clean_order && n_pairs > 1 && n_pairs <= (int64_t)8 * CLEAN_PER_CU_MAX * ctx->n_cus) {
         HIPCHK(dmalloc(ctx, (void**)&p->d_clean_order, sizeof(int32_t) * (size_t)n_pairs));
         const std::vector<int32_t> ord = clean_order(*p, n_pairs);
         HIPCHK(hipMemcpy(p->d_clean_order, ord.data(), sizeof(int32_t) * (size_t)n_pairs, hipMemcpyHostToDevice));
@@ -1419,95 +1409,43 @@ static void launch_join(vapor_plan* p, const Launch& L, const DTask* d_tasks, bo
                            p->d_task_pairs, p->d_hits, p->d_nhits, first ? p->d_overflow : (unsigned int*)nullptr);
 }
 
-static int clean_groups_cap(int range_words_cap) { return range_words_cap * 32 / 10 + 8; }
-
-// clean_kernel is instantiated for 4, 8 and CLEAN_PER_MAX bitmap words per thread: the smallest that covers the value range
+// The clean launch: vapor_clean_plan.h says how many records a workgroup stages, how its LDS is carved, which compiled width the
+// value range takes and who cuts the served pairs' records; here are the launches and a developer build's overrides.
 template <typename... A>
 static void launch_clean(int range_words_cap, unsigned grid, size_t lds, hipStream_t st, A... a)
 {
-    const int per = (range_words_cap + CLEAN_THREADS - 1) / CLEAN_THREADS;
-    if (per <= 4) hipLaunchKernelGGL(clean_kernel<4>, dim3(grid), dim3(CLEAN_THREADS), lds, st, a...);
-    else if (per <= 8) hipLaunchKernelGGL(clean_kernel<8>, dim3(grid), dim3(CLEAN_THREADS), lds, st, a...);
+    const int per = clean_plan::width(range_words_cap);
+    if (per == 4) hipLaunchKernelGGL(clean_kernel<4>, dim3(grid), dim3(CLEAN_THREADS), lds, st, a...);
+    else if (per == 8) hipLaunchKernelGGL(clean_kernel<8>, dim3(grid), dim3(CLEAN_THREADS), lds, st, a...);
     else hipLaunchKernelGGL(clean_kernel<CLEAN_PER_MAX>, dim3(grid), dim3(CLEAN_THREADS), lds, st, a...);
 }
 
-// clean_kernel's LDS: bitmap + 16-bit ranks + group sizes (+ staged hits).  Pairs cleaned out of LDS use
-// 16-bit group counters; pairs that stream their hits need 32-bit ones, which must fit as well.
-constexpr int CLEAN_BIG_GRID = 1024;      // clean_big_kernel walks its list with at most this many workgroups
-
-// clean_big_kernel: bitmap + 16-bit ranks + 32-bit group sizes (as many groups as the value range can hold)
-static size_t clean_fixed_bytes(int rw, bool wide)
+static clean_plan::Geom clean_geom(int range_words_cap, int want, bool exact = false)
 {
-    const size_t g = (size_t)clean_groups_cap(rw);
-    return sizeof(uint32_t) * ((size_t)rw + ((size_t)rw + 1) / 2 + (wide ? g : (g + 1) / 2)) + 64;
-}
-
-// clean_kernel: 16-bit group sizes.  A pair staged in LDS has at most hcap records and every group holds at least
-// one, so hcap counters do; the same region later holds the per-value counters of the median (value span / 100).
-static int clean_groups_lds(int rw, int hcap)
-{
-    const int g = std::min(clean_groups_cap(rw), std::max(hcap, 1));
-    return 2 * std::max((g + 1) / 2, rw * 32 / 100 + 8);
-}
-
-// clean_pair's layout: bitmap and ranks of one axis, or of both (`dual`: cluster_dual works on the two axes of C1 at
-// once), one region of 16-bit group counters, then the staged records, 8 bytes each with their flag byte inside
-static size_t clean_lds_bytes(int rw, int hcap, bool dual)
-{
-    const size_t bw = (size_t)rw + ((size_t)rw + 1) / 2;
-    const size_t rec_word = ((dual ? 2 : 1) * bw + ((size_t)clean_groups_lds(rw, hcap) + 1) / 2 + 1) & ~(size_t)1;
-    return sizeof(uint32_t) * rec_word + 64 + (size_t)hcap * 8 + 8;
-}
-
-// The kernel waits for memory and barriers more than it computes, so residency matters: take the largest number
-// of workgroups per CU (32 waves at most) whose share of the 160 KB still stages ~90 % of the expected records.
-struct CleanGeom { int hcap, per_cu; bool dual; };
-static CleanGeom clean_geom_for(int range_words_cap, int want, bool dual, bool exact = false)
-{
-    CleanGeom g{0, 1, dual};
+    clean_plan::Geom g = clean_plan::geom(range_words_cap, want, exact);
 #ifdef VAPOR_DEV_BUILD
-    if (const char* e = getenv("VAPOR_DEV_HCAP")) { g.hcap = atoi(e) & ~3; return g; }      // experiment: records staged per pair
+    const char* dual = getenv("VAPOR_DEV_CLEAN_DUAL");               // experiment: the layout, whatever it costs in residency
+    if (dual) g = clean_plan::geom_for(range_words_cap, want, atoi(dual) != 0, exact);
+    if (const char* e = getenv("VAPOR_DEV_HCAP")) g = clean_plan::Geom{atoi(e) & ~3, 1, dual ? g.dual : true};   // experiment: records staged per pair
 #endif
-    for (int per_cu = 2048 / CLEAN_THREADS; per_cu >= 1; --per_cu) {
-        const size_t share = (size_t)(160 * 1024) / per_cu - 512;
-        int cap = std::min(want, CLEAN_HCAP_MAX) & ~3;
-        while (cap > 0 && clean_lds_bytes(range_words_cap, cap, dual) + 512 > share) cap -= 4;
-        // (an estimated `want`: nine tenths of it staged is enough; a measured one - the largest record count of the plan's
-        // pairs - is staged whole, so that no pair is left to clean_big_kernel for the sake of residency)
-        if (cap >= (exact ? want : want * 9 / 10) || per_cu == 1) { g.hcap = std::max(cap, 0); g.per_cu = per_cu; break; }
-    }
     return g;
 }
-// Both axes of C1 in one sweep (cluster_dual) need a second bitmap and rank array per workgroup.  Measured (tools/clean_sweep.py,
-// profiles/r03_clean_variants.txt): the sweep wins where the extra LDS costs no residency (30 kb x 40 kb pairs, two workgroups
-// per CU either way: clean 1.87 -> 1.70 ms) and loses where it does (10 kb x 20 kb: 7 -> 6 per CU, 0.075 vs 0.078 ms; 15 kb x
-// 20 kb: 5 -> 4, 1.32 vs 1.42 ms) - so it is used exactly when it is free.
-static CleanGeom clean_geom(int range_words_cap, int want, bool exact = false)
+static clean_plan::Geom clean_geom(const vapor_plan* p) { return clean_geom(p->range_words_cap, p->hcap_want, p->hcap_measured); }
+
+static bool remap_in_clean(const vapor_plan* p, const clean_plan::Geom& cg)
 {
-    const CleanGeom seq = clean_geom_for(range_words_cap, want, false, exact), dual = clean_geom_for(range_words_cap, want, true, exact);
-#ifdef VAPOR_DEV_BUILD
-    if (const char* e = getenv("VAPOR_DEV_CLEAN_DUAL")) return atoi(e) ? dual : seq;
-#endif
-    return dual.per_cu >= seq.per_cu ? dual : seq;      // (either stages at least nine tenths of the expected records)
+    return clean_plan::remap_in_clean(p->ctx->remap_in_clean, p->n_dpairs, p->n_pairs, cg.per_cu, p->ctx->n_cus);
+}
+
+static void launch_clean_big(int64_t n_pairs, int rw, hipStream_t st, const DPair* pairs, const unsigned long long* n_hits,
+                             const unsigned long long* hits, uint8_t* hflags, long long* stats, const unsigned int* overflow, const int32_t* big_list)
+{
+    const clean_plan::Layout big = clean_plan::big_layout(rw);
+    hipLaunchKernelGGL(clean_big_kernel, dim3((unsigned)std::min<int64_t>(n_pairs, CLEAN_BIG_GRID)), dim3(CLEAN_THREADS), big.big_bytes(), st,
+                       pairs, n_hits, hits, hflags, stats, rw, big.groups_cap, overflow, big_list);
 }
 
 static int async_fold(vapor_plan* p);
-
-// Who cuts the served pairs' records out of the shared dot plots: the clean workgroup of each pair, or remap_kernel before the
-// cleaning.  Measured (profiles/r04_remap_experiments.txt): the clean workgroups win when the plan is a couple of rounds of them
-// - a resident batch of the 10 kb shape, 4 000 pairs at seven workgroups per CU: such a launch is bound by its start, its tail
-// and the chains of loads in between, and a kernel boundary and a trip of the records through HBM is what the kernel of its own
-// adds (+3 % loci/s) - and lose when it is many rounds (cfg3, 15 kb reads: 80 000 pairs at five per CU, 62 rounds: a launch bound by
-// what its workgroups execute, and every target reads the shared plot and searches the interval table again; -3 %).  Between
-// the two measured shapes the rule is a guess: the clean workgroups up to four rounds.
-// "remap_in_clean": 1 = that rule, 0 = always the kernel, 2 = always the clean workgroups.
-static bool remap_in_clean(const vapor_plan* p)
-{
-    if (p->n_dpairs <= 0 || p->ctx->remap_in_clean == 0) return false;
-    if (p->ctx->remap_in_clean == 2) return true;
-    const CleanGeom cg = clean_geom(p->range_words_cap, p->hcap_want, p->hcap_measured);
-    return p->n_pairs <= 4 * (int64_t)cg.per_cu * p->ctx->n_cus;
-}
 
 // Which task table an asynchronous step takes under join_align 1.  Blocking runs always take the cost-balanced table: there one
 // plan's latency is what the caller waits for, and the aligned table's dearer tasks are that latency.  The same holds for the
@@ -1590,10 +1528,12 @@ static int plan_run_once(vapor_plan* p, int table, bool fetch_stats = true, hipE
         first = false;
         HIPCHK(hipGetLastError());
     }
+    const clean_plan::Geom cg = clean_geom(p);
+    const bool in_clean = remap_in_clean(p, cg);
 #if defined(VAPOR_AB) && VAPOR_AB == 3               /* (developer variant 3: the shared joins without their remap) */
     if (false) {
 #else
-    if (p->n_dpairs && !remap_in_clean(p)) {
+    if (p->n_dpairs && !in_clean) {
 #endif
         hipLaunchKernelGGL(remap_kernel, dim3((unsigned)p->n_dpairs), dim3(256), 0, st, (const DPair*)p->d_pairs, (const DShare*)p->d_shares,
                            (const int32_t*)p->d_maps, p->d_hits, p->d_nhits, p->d_overflow);
@@ -1603,17 +1543,15 @@ static int plan_run_once(vapor_plan* p, int table, bool fetch_stats = true, hipE
     // (the clean kernels overwrite the statistics the previous step's finish kernel reads on its own stream)
     if (before_clean) HIPCHK(hipStreamWaitEvent(st, before_clean, 0));
     if (p->n_pairs > 0) {
-        const CleanGeom cg = clean_geom(p->range_words_cap, p->hcap_want, p->hcap_measured);
-        const int hcap = cg.hcap;
-        size_t lds = clean_lds_bytes(p->range_words_cap, hcap, cg.dual);
+        const clean_plan::Layout lay = clean_plan::staged_layout(p->range_words_cap, cg.hcap, cg.dual);
+        size_t lds = clean_plan::launch_bytes(lay, in_clean);
 #ifdef VAPOR_DEV_BUILD
         if (const char* e = getenv("VAPOR_DEV_CLEAN_PAD")) lds += (size_t)atoi(e);   // experiment: fewer workgroups per CU
 #endif
-        const bool in_clean = remap_in_clean(p);
         launch_clean(p->range_words_cap, (unsigned)p->n_pairs, lds, st,
                      (const DPair*)p->d_pairs, (const int32_t*)p->d_clean_order, p->d_nhits,
                      p->d_hits, p->d_hflags, p->d_stats, p->range_words_cap,
-                     clean_groups_lds(p->range_words_cap, hcap), hcap, p->d_overflow, p->d_big_list, skip_big ? 0 : 1, cg.dual ? 1 : 0,
+                     lay.groups_cap, lay.hcap, p->d_overflow, p->d_big_list, skip_big ? 0 : 1, cg.dual ? 1 : 0,
                      in_clean ? (const DServe*)p->d_serve : (const DServe*)nullptr, (const int32_t*)p->d_maps, keep_flags ? 1 : 0);
         HIPCHK(hipGetLastError());
         p->flags_valid = keep_flags;
@@ -1621,9 +1559,7 @@ static int plan_run_once(vapor_plan* p, int table, bool fetch_stats = true, hipE
         // on the stream until that join is over even with nothing to do, and holds back the finish kernel and the
         // plan's next step with it - so an asynchronous step leaves it out when the plan's blocking run left it no pair)
         if (!skip_big) {
-            hipLaunchKernelGGL(clean_big_kernel, dim3((unsigned)std::min<int64_t>(p->n_pairs, CLEAN_BIG_GRID)), dim3(CLEAN_THREADS),
-                               clean_fixed_bytes(p->range_words_cap, true), st, p->d_pairs, p->d_nhits, p->d_hits, p->d_hflags,
-                               p->d_stats, p->range_words_cap, clean_groups_cap(p->range_words_cap), p->d_overflow, p->d_big_list);
+            launch_clean_big(p->n_pairs, p->range_words_cap, st, p->d_pairs, p->d_nhits, p->d_hits, p->d_hflags, p->d_stats, p->d_overflow, p->d_big_list);
             HIPCHK(hipGetLastError());
         }
     }
@@ -1650,69 +1586,33 @@ extern "C" int vapor_plan_run(vapor_plan* p, int64_t* stats)
         if (rc0 != VAPOR_OK) return rc0;
     }
     p->n_retried = 0;
+    // The shared dot plots' packed counters, fetched after every run.  The copy of the LAST run serves what follows the loop too:
+    // the loop ends either where nothing grew, or after the third run's plan_alloc_hits, which allocates the record slots anew and
+    // uploads pair records - no kernel runs and nothing writes d_nhits between that copy and the end of the loop.
+    std::vector<unsigned long long> plots((size_t)p->n_dpairs);
     for (int attempt = 0; attempt < 3; ++attempt) {
         int rc = plan_run_once(p, 0);
         if (rc != VAPOR_OK) return rc;
-        // pairs whose hit count exceeded their slot: enlarge to the exact count and rerun
-        int64_t grow = 0;
-        for (int64_t i = 0; i < p->n_pairs; ++i) {
-            const long long* s = p->h_stats + 16 * i;
-            if (s[15] == VAPOR_E_OVERFLOW && s[14] <= p->ctx->max_pair_cap && (uint32_t)s[14] > p->hp[i].cap) {
-                p->hp[i].cap = (uint32_t)s[14];     // records the pair produced
-                ++grow;
-            }
-        }
-        if (p->n_dpairs) {
-            // the shared dot plots: their record counts are the low halves of the join's packed counters
-            std::vector<unsigned long long> dc((size_t)p->n_dpairs);
-            HIPCHK(hipMemcpy(dc.data(), p->d_nhits + p->n_pairs, sizeof(unsigned long long) * dc.size(), hipMemcpyDeviceToHost));
-            for (int64_t t = 0; t < p->n_dpairs; ++t) {
-                DPair& d = p->hp[(size_t)(p->n_pairs + t)];
-                const uint32_t need = (uint32_t)dc[(size_t)t];
-                if (need > d.cap && (int64_t)need <= p->ctx->max_pair_cap) { d.cap = need; ++grow; }
-            }
-        }
+        if (p->n_dpairs)
+            HIPCHK(hipMemcpy(plots.data(), p->d_nhits + p->n_pairs, sizeof(unsigned long long) * plots.size(), hipMemcpyDeviceToHost));
+        // pairs and plots whose record count exceeded their slot: enlarge to the exact count and rerun
+        const int64_t grow = clean_plan::grow_slots(p->h_stats, p->n_pairs, plots, p->ctx->max_pair_cap, p->hp);
         if (!grow) break;
         p->n_retried += (int)grow;
         rc = plan_alloc_hits(p);
         if (rc != VAPOR_OK) return rc;
     }
     if (p->ctx->clean_fit && p->n_pairs > 0) {
-        // The clean kernel's geometry from what the pairs really hold: a plan is created with an ESTIMATE of the records a pair
-        // will have (a tenth of the shorter sequence plus the chance dots), which sizes the LDS copy and with it the workgroups a
-        // CU holds; the join is deterministic, so after one blocking run the largest record count is known exactly and the copy
-        // is sized for that.  On the 10 kb x 20 kb shape that is eight workgroups per CU instead of seven - and 4 000 pairs are
-        // 1.95 rounds of 2 048 workgroups instead of 2.2 rounds of 1 792, i.e. two rounds instead of three.
+        // the clean kernel's geometry from what the pairs really hold (clean_plan::measured_want)
         std::vector<unsigned long long> cnt((size_t)p->n_pairs);
         HIPCHK(hipMemcpy(cnt.data(), p->d_nhits, sizeof(unsigned long long) * cnt.size(), hipMemcpyDeviceToHost));
-        uint32_t most = 0;
-        for (int64_t i = 0; i < p->n_pairs; ++i)
-            if (p->status[(size_t)i] == 0 && (uint32_t)(cnt[(size_t)i] >> 32) <= 65535u) most = std::max(most, (uint32_t)cnt[(size_t)i]);
-        if (most > 0 && most <= (uint32_t)CLEAN_HCAP_MAX) {
-            p->hcap_want = (int)((most + 3u) & ~3u);
+        if (const int want = clean_plan::measured_want(cnt, p->status)) {
+            p->hcap_want = want;
             p->hcap_measured = true;
         }
     }
-    if (p->n_dpairs) {
-        // A shared dot plot that needs more than max_pair_cap cannot grow: the records its targets were cut from are a
-        // truncated plot, although the targets' own slots did not overflow.  Every pair it serves keeps VAPOR_E_OVERFLOW
-        // (include/vapor_hip.h, "max_pair_cap") - as a host-side status, so that every later run reports it as well and
-        // vapor_plan_run_loci takes the path that hands the statuses to the finish kernel.
-        std::vector<unsigned long long> dc((size_t)p->n_dpairs);
-        HIPCHK(hipMemcpy(dc.data(), p->d_nhits + p->n_pairs, sizeof(unsigned long long) * dc.size(), hipMemcpyDeviceToHost));
-        for (int64_t t = 0; t < p->n_dpairs; ++t)
-            if ((uint32_t)dc[(size_t)t] > p->hp[(size_t)(p->n_pairs + t)].cap)
-                for (int32_t tg : p->shares[(size_t)t].target)
-                    if (tg >= 0 && p->status[(size_t)tg] == 0) p->status[(size_t)tg] = VAPOR_E_OVERFLOW;
-    }
-    for (int64_t i = 0; i < p->n_pairs; ++i) {
-        long long* s = p->h_stats + 16 * i;
-        if (p->status[i] != 0) {
-            for (int t = 0; t < 16; ++t) s[t] = 0;
-            s[1] = s[2] = -1;
-            s[15] = p->status[i];
-        }
-    }
+    clean_plan::refuse_truncated_plots(plots, p->hp, p->n_pairs, p->shares, p->status);
+    clean_plan::mask_refused(p->h_stats, p->status, p->n_pairs);
     memcpy(p->last_stats.data(), p->h_stats, sizeof(int64_t) * 16 * (size_t)p->n_pairs);
     memcpy(stats, p->h_stats, sizeof(int64_t) * 16 * (size_t)p->n_pairs);
     p->ran = true;
@@ -1722,10 +1622,10 @@ extern "C" int vapor_plan_run(vapor_plan* p, int64_t* stats)
 extern "C" int vapor_plan_timings(vapor_plan* p, double* ms, int32_t n)
 {
     if (!p || !ms) return fail(VAPOR_E_ARG, "vapor_plan_timings: null argument");
-    const CleanGeom cg = clean_geom(p->range_words_cap, p->hcap_want, p->hcap_measured);
+    const clean_plan::Geom cg = clean_geom(p);
     const TableModel& tm = p->model[p->last_table];
     double v[12] = {p->t_join, p->t_clean, p->t_total, (double)p->launches.size(), (double)p->n_retried, p->t_finish,
-                    (double)p->n_served, (double)p->n_dpairs, (double)cg.per_cu, remap_in_clean(p) ? 1.0 : 0.0,
+                    (double)p->n_served, (double)p->n_dpairs, (double)cg.per_cu, remap_in_clean(p, cg) ? 1.0 : 0.0,
                     (double)tm.n_tasks, (double)tm.builds};
     for (int i = 0; i < n && i < 12; ++i) ms[i] = v[i];
     return VAPOR_OK;
@@ -1864,58 +1764,17 @@ extern "C" int vapor_selfplot_qc(vapor_ctx* ctx, vapor_seqset* set, int32_t n, c
 // Cleaning and reductions on caller-supplied hit lists: what clean_dotdata_diagnal_and_anti_diagnal
 // (SF:432-448), clean_dotdata_diagnal_m1b / clean_dotdata_anti_diagnal_m1b (SF:404-430) and the
 // eu_dis_* reductions do when handed an explicit dot list instead of a fresh dotdata() result.
-// The lists of vapor_clean_hits and vapor_clean_hits_wide: coordinates in 0 .. coord_max.  Only the wide entry point has ever
-// checked the offsets themselves (list_cap >= 0: they do not decrease, no list longer than that); the narrow one (list_cap < 0)
-// takes them as given.  Each entry point keeps its own set of refusals here; aligning them is a change of behaviour.
-static int clean_lists_check(const std::string& who, vapor_ctx* ctx, int64_t n_lists, const int32_t* hits_ji, const int64_t* off,
-                             const int64_t* stats, int coord_max, int64_t list_cap)
-{
-    if (!ctx || n_lists < 0 || (n_lists && (!off || !stats))) return fail(VAPOR_E_ARG, who + ": null argument");
-    if (n_lists == 0) return VAPOR_OK;
-    if (off[n_lists] && !hits_ji) return fail(VAPOR_E_ARG, who + ": null hit list");
-    for (int64_t t = 0; t < n_lists; ++t) {
-        if (list_cap >= 0 && (off[t + 1] < off[t] || off[t + 1] - off[t] > list_cap)) return fail(VAPOR_E_ARG, who + ": bad list offsets");
-        for (int64_t h = off[t]; h < off[t + 1]; ++h) {
-            const int j = hits_ji[2 * h], i = hits_ji[2 * h + 1];
-            if (j < 0 || i < 0 || j > coord_max || i > coord_max) return fail(VAPOR_E_ARG, who + ": coordinate out of range");
-        }
-    }
-    return VAPOR_OK;
-}
-
+// (the refusals of the two list entries and the packing of the narrow one: clean_plan::lists_check, clean_plan::ListPack)
 extern "C" int vapor_clean_hits(vapor_ctx* ctx, int64_t n_lists, const int32_t* hits_ji, const int64_t* off,
                                 const uint32_t* flags, int64_t* stats, uint8_t* hit_flags)
 {
-    if (const int rc = clean_lists_check("vapor_clean_hits", ctx, n_lists, hits_ji, off, stats, VAPOR_MAX_SEQ_LEN, -1)) return rc;
+    if (const auto no = clean_plan::lists_check(ctx != nullptr, n_lists, hits_ji, off, stats, VAPOR_MAX_SEQ_LEN, -1)) return refused("vapor_clean_hits", no);
     if (n_lists == 0) return VAPOR_OK;
     HIPCHK(hipSetDevice(ctx->device));
     const int64_t tot = off[n_lists];
-    std::vector<DPair> dp((size_t)n_lists);
-    std::vector<unsigned long long> nh((size_t)n_lists);
-    // device layout: one record per dot, every list's slot padded to a multiple of four records (the kernels
-    // store flag bytes four at a time)
-    std::vector<int64_t> poff((size_t)n_lists + 1, 0);
-    for (int64_t t = 0; t < n_lists; ++t) poff[t + 1] = poff[t] + ((off[t + 1] - off[t] + 3) & ~(int64_t)3);
-    std::vector<unsigned long long> packed((size_t)std::max<int64_t>(poff[n_lists], 4), 0ull);
-    int rw = 1;
-    for (int64_t t = 0; t < n_lists; ++t) {
-        int mi = 0, mj = 0;
-        for (int64_t h = off[t]; h < off[t + 1]; ++h) {
-            int j = hits_ji[2 * h], i = hits_ji[2 * h + 1];
-            mi = std::max(mi, i); mj = std::max(mj, j);
-            packed[poff[t] + (h - off[t])] = (unsigned long long)(((uint32_t)j << 16) | (uint32_t)i) | (1ull << 32);
-        }
-        DPair& d = dp[t];
-        d.seq1 = (int32_t)(2 * t); d.seq2 = (int32_t)(2 * t + 1); d.off2 = 0; d.k = 10;
-        d.len1 = mi + 1; d.len2 = mj + 1;
-        d.flags = flags ? flags[t] : 3u;
-        d.cap = (uint32_t)(off[t + 1] - off[t]);
-        d.hit_off = poff[t];
-        nh[t] = (unsigned long long)(off[t + 1] - off[t]) * 0x100000001ull;   // records | dots << 32
-        // the largest values, i + j = 131070 and i - j + len2 = 131071, still fall into word 4095
-        rw = std::min(std::max(rw, (mi + mj + 4 + 31) / 32), CLEAN_RANGE_WORDS_MAX);
-    }
-    std::vector<uint8_t> fl(hit_flags && tot ? packed.size() : 0);
+    const clean_plan::ListPack L(n_lists, hits_ji, off, flags);
+    const int rw = L.rw;
+    std::vector<uint8_t> fl(hit_flags && tot ? L.packed.size() : 0);
     hipStream_t st = ctx->stream;
     CallScope sc(ctx, st);
     Block<DPair> d_dp(sc);
@@ -1925,31 +1784,30 @@ extern "C" int vapor_clean_hits(vapor_ctx* ctx, int64_t n_lists, const int32_t* 
     Block<uint8_t> d_fl(sc);
     Block<long long> d_st(sc);
     HIPCHK(d_ov.ensure(4 * sizeof(unsigned int)));
-    HIPCHK(d_big.ensure(sizeof(int32_t) * dp.size()));
-    HIPCHK(d_dp.ensure(sizeof(DPair) * dp.size()));
-    HIPCHK(d_nh.ensure(sizeof(unsigned long long) * nh.size()));
-    HIPCHK(d_hits.ensure(sizeof(unsigned long long) * packed.size()));
-    HIPCHK(d_fl.ensure(packed.size()));
+    HIPCHK(d_big.ensure(sizeof(int32_t) * L.dp.size()));
+    HIPCHK(d_dp.ensure(sizeof(DPair) * L.dp.size()));
+    HIPCHK(d_nh.ensure(sizeof(unsigned long long) * L.counts.size()));
+    HIPCHK(d_hits.ensure(sizeof(unsigned long long) * L.packed.size()));
+    HIPCHK(d_fl.ensure(L.packed.size()));
     HIPCHK(d_st.ensure(sizeof(long long) * 16 * (size_t)n_lists));
     HIPCHK(hipMemsetAsync(d_ov, 0, 4 * sizeof(unsigned int), st));
-    HIPCHK(hipMemcpyAsync(d_dp, dp.data(), sizeof(DPair) * dp.size(), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_nh, nh.data(), sizeof(unsigned long long) * nh.size(), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_hits, packed.data(), sizeof(unsigned long long) * packed.size(), hipMemcpyHostToDevice, st));
-    const CleanGeom cg = clean_geom(rw, 4096);
-    const int hcap = cg.hcap;
-    launch_clean(rw, (unsigned)n_lists, clean_lds_bytes(rw, hcap, cg.dual), st, (const DPair*)d_dp, (const int32_t*)nullptr,
+    HIPCHK(hipMemcpyAsync(d_dp, L.dp.data(), sizeof(DPair) * L.dp.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_nh, L.counts.data(), sizeof(unsigned long long) * L.counts.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_hits, L.packed.data(), sizeof(unsigned long long) * L.packed.size(), hipMemcpyHostToDevice, st));
+    const clean_plan::Geom cg = clean_geom(rw, clean_plan::LISTS_WANT);
+    const clean_plan::Layout lay = clean_plan::staged_layout(rw, cg.hcap, cg.dual);
+    launch_clean(rw, (unsigned)n_lists, clean_plan::launch_bytes(lay, false), st, (const DPair*)d_dp, (const int32_t*)nullptr,
                  d_nh.p, d_hits.p, d_fl.p, d_st.p, rw,
-                 clean_groups_lds(rw, hcap), hcap, d_ov.p, d_big.p, 1, cg.dual ? 1 : 0,
+                 lay.groups_cap, lay.hcap, d_ov.p, d_big.p, 1, cg.dual ? 1 : 0,
                  (const DServe*)nullptr, (const int32_t*)nullptr, 1);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(clean_big_kernel, dim3((unsigned)std::min<int64_t>(n_lists, CLEAN_BIG_GRID)), dim3(CLEAN_THREADS),
-                       clean_fixed_bytes(rw, true), st, d_dp.p, d_nh.p, d_hits.p, d_fl.p, d_st.p, rw, clean_groups_cap(rw), d_ov.p, d_big.p);
+    launch_clean_big(n_lists, rw, st, d_dp.p, d_nh.p, d_hits.p, d_fl.p, d_st.p, d_ov.p, d_big.p);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(stats, d_st, sizeof(long long) * 16 * (size_t)n_lists, hipMemcpyDeviceToHost, st));
     if (!fl.empty()) HIPCHK(hipMemcpyAsync(fl.data(), d_fl, fl.size(), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     sc.settled();
-    for (int64_t t = 0; !fl.empty() && t < n_lists; ++t) memcpy(hit_flags + off[t], fl.data() + poff[t], (size_t)(off[t + 1] - off[t]));
+    for (int64_t t = 0; !fl.empty() && t < n_lists; ++t) memcpy(hit_flags + off[t], fl.data() + L.poff[t], (size_t)(off[t + 1] - off[t]));
     return VAPOR_OK;
 }
 
@@ -2197,9 +2055,8 @@ extern "C" int vapor_wide_batch(vapor_ctx* ctx, vapor_seqset* set, int64_t n_pai
 extern "C" int vapor_clean_hits_wide(vapor_ctx* ctx, int64_t n_lists, const int32_t* hits_ji, const int64_t* off,
                                      const uint32_t* flags, int64_t* stats, uint8_t* hit_flags)
 {
-    if (const int rc = clean_lists_check("vapor_clean_hits_wide", ctx, n_lists, hits_ji, off, stats, VAPOR_MAX_WIDE_SEQ_LEN,
-                                         ctx ? ctx->max_pair_cap : 0))
-        return rc;
+    if (const auto no = clean_plan::lists_check(ctx != nullptr, n_lists, hits_ji, off, stats, VAPOR_MAX_WIDE_SEQ_LEN, ctx ? ctx->max_pair_cap : 0))
+        return refused("vapor_clean_hits_wide", no);
     if (n_lists == 0) return VAPOR_OK;
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
@@ -2404,9 +2261,6 @@ static std::vector<Rec> pair_records(const vapor_seqset* set, const vapor_pair* 
     }
     return recs;
 }
-
-// a refusal of the plan headers (a code, and the message without the entry's name) as the entry's status
-static int refused(const std::string& entry, const vapor_polish_call::Refusal& no) { return fail(no.code, entry + ": " + no.msg); }
 
 // the refusals of every entry, in their order; args_ok: the pointers a call with pairs needs are there
 static int realign_refusal(const char* entry, const vapor_ctx* ctx, const vapor_seqset* set, int64_t n_pairs, bool args_ok, int32_t band)

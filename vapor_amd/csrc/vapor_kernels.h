@@ -30,6 +30,8 @@
 #error "developer switch without -DVAPOR_DEV_BUILD: a product library cannot be an experimental one"
 #endif
 
+#include "vapor_clean_plan.h"   // the clean kernels' constants and the layout of their dynamic LDS, shared with the host (behind the guard: it gives VAPOR_CLEAN_THREADS its default)
+
 namespace vapor {
 
 // plane geometry: every sequence starts on a 32-base chunk; a chunk is 2 words of the 2-bit
@@ -38,14 +40,7 @@ namespace vapor {
 #define VP_X4_WORDS_PER_CHUNK 4
 // (VP_PAD_CHUNKS, the zeroed chunks after each sequence, is vapor_records.h's: the host lays the planes out with it)
 
-#ifndef VAPOR_CLEAN_THREADS
-#define VAPOR_CLEAN_THREADS 256
-#endif
-constexpr int CLEAN_THREADS = VAPOR_CLEAN_THREADS;
-constexpr int CLEAN_WAVES = CLEAN_THREADS / 64;
-// words of the clean kernels' value bitmap: values i + j and i - j + len2 stay below 2 * 65536 (positions are 16 bit)
-constexpr int CLEAN_RANGE_WORDS_MAX = 4096;
-constexpr int CLEAN_PER_MAX = (CLEAN_RANGE_WORDS_MAX + CLEAN_THREADS - 1) / CLEAN_THREADS;   // bitmap words per thread at the largest value range
+// (CLEAN_THREADS, CLEAN_WAVES, CLEAN_RANGE_WORDS_MAX, CLEAN_PER_MAX and CLEAN_HCAP_MAX are vapor_clean_plan.h's)
 
 // per-hit working flags inside clean_kernel (upper nibble) and the public ones (lower)
 #define HF_C1 1u
@@ -1320,7 +1315,6 @@ struct RecV {
 // group-size pass, read by the flag pass: a pair staged in LDS has at most CLEAN_HCAP_MAX = 8192 records and every group
 // holds at least one, so 13 bits do); a single-axis pass uses bits 38.. for its one group.  The lower word is i0 | j0 << 16
 // in both formats.
-constexpr int CLEAN_HCAP_MAX = 8192;
 template <bool LFMT>
 __device__ __forceinline__ RecV rec_decode(unsigned long long r)
 {
@@ -1933,8 +1927,7 @@ __device__ __forceinline__ void clean_body(HP recs, FP hflags, int n, int n_dots
     }
 }
 
-// One pair of n records / n_dots dots.  Dynamic LDS: bitmap (range_words_cap words) | wrank (u16 each) | group
-// sizes | (IN_LDS: record copy (hcap x 8 B, 8-byte aligned) | flag bytes (hcap)).
+// One pair of n records / n_dots dots.  Dynamic LDS: clean_plan::Layout (vapor_clean_plan.h), which the host sizes it by.
 template <bool IN_LDS, int PER_MAX>
 __device__ __forceinline__ void clean_pair(int p, uint32_t* lds, CleanShared& sh, const DPair& pr, int n, int n_dots, int len2,
                                            int range_words, const unsigned long long* __restrict__ recs_all,
@@ -1957,14 +1950,13 @@ __device__ __forceinline__ void clean_pair(int p, uint32_t* lds, CleanShared& sh
     }
     // clean_kernel (IN_LDS): bitmap and ranks of i - j | bitmap and ranks of i + j (cluster_dual) | group counters | records;
     // clean_big_kernel: bitmap | ranks | group counters
-    const int bw = range_words_cap + (range_words_cap + 1) / 2;
-    uint32_t* bm = lds;
-    uint16_t* wrank = reinterpret_cast<uint16_t*>(bm + range_words_cap);
-    uint32_t* bm2 = lds + bw;
-    uint16_t* wrank2 = reinterpret_cast<uint16_t*>(bm2 + range_words_cap);
-    uint32_t* gcnt = lds + (dual_layout ? 2 * bw : bw);
-    const int rec_word = ((dual_layout ? 2 : 1) * bw + (groups_cap + 1) / 2 + 1) & ~1;
-    unsigned long long* lrecs = reinterpret_cast<unsigned long long*>(lds + rec_word);
+    const clean_plan::Layout L{range_words_cap, groups_cap, hcap, dual_layout};
+    uint32_t* bm = lds + L.bitmap();
+    uint16_t* wrank = reinterpret_cast<uint16_t*>(bm + L.ranks_behind_bitmap());
+    uint32_t* bm2 = lds + L.bitmap2();
+    uint16_t* wrank2 = reinterpret_cast<uint16_t*>(bm2 + L.ranks_behind_bitmap());
+    uint32_t* gcnt = lds + L.counters();
+    unsigned long long* lrecs = reinterpret_cast<unsigned long long*>(lds + L.records());
 
     if (tid == 0) {
         sh.min_j = 0x7FFFFFFF; sh.max_j = -1; sh.n_diag = 0; sh.n_lower = 0;
@@ -2044,7 +2036,7 @@ __device__ __forceinline__ void clean_pair(int p, uint32_t* lds, CleanShared& sh
 // about to clean pair p first cuts p's records out of the shared dot plot - the arithmetic of remap_kernel for one slot - writes
 // them to p's slot and goes on to read them back: through the L2 of its own XCD instead of through HBM and a kernel boundary.
 // Returns p's packed count (records | dots << 32), which it also stores for the host.  `w`: the start of the workgroup's dynamic
-// LDS (free until the cleaning proper begins).
+// LDS (free until the cleaning proper begins; REMAP_SCRATCH_BYTES of it, which the host's launch_bytes holds every serving launch to).
 #ifndef VAPOR_REMAP_CLEAN_PER
 #define VAPOR_REMAP_CLEAN_PER 4
 #endif
@@ -2059,8 +2051,8 @@ __device__ __forceinline__ unsigned long long remap_for_target(int p, const DPai
     const int n_iv = min(sv.n_iv, REMAP_MAX_IV);
     const int32_t* tb = tables + sv.iv_first;
     uint32_t* c = w;                                               // [0] records, [1] dots
-    int* s_B = reinterpret_cast<int*>(w + 4);                      // n_iv + 2 boundaries
-    uint32_t* s_ops = w + 64;                                      // two op words per interval: this slot's
+    int* s_B = reinterpret_cast<int*>(w + REMAP_BOUNDS_WORD);      // n_iv + 2 boundaries
+    uint32_t* s_ops = w + REMAP_OPS_WORD;                          // two op words per interval: this slot's
     if (tid <= n_iv) s_B[tid] = tb[tid];
     if (tid == n_iv + 1) s_B[tid] = 0x7FFFFFFF;
     if (tid < 2 * n_iv) s_ops[tid] = (uint32_t)tb[n_iv + 1 + (tid >> 1) * REMAP_OPS + slot * 2 + (tid & 1)];
