@@ -7,7 +7,8 @@ A plain helper module (no pytest hooks).  It holds
     anyk_model (the restatement of kmerhits' two match rules), its statistics words 0-13 from dot_designs.expected();
   * the groups: sort_sizes(), every_k(), last_symbol(), edit_rounds(), edit_split(), batch_state() - built once per process;
   * the numbers of the route that the designs are aimed at, restated: entries() / padded() (n and np of the sort), per_of() /
-    launches() (anyk_edit_launch), comparator_key() (anyk_cmp's order);
+    launches() (dots_plan::edit_cut; tools/dots_plan_check.cpp holds vapor_dots_plan.h to the same numbers), comparator_key()
+    (anyk_cmp's order);
   * MUTANTS and mutant_hits(): deliberately wrong variants of the statement, each one way the kernels can be wrong, used only
     to show that the designs can tell them from the right one.
 
@@ -52,7 +53,7 @@ def padded(n):
 
 
 def per_of(n, edit_pairs=None):
-    """Allele k-mers per launch of the edit pass (anyk_edit_launch)."""
+    """Allele k-mers per launch of the edit pass (dots_plan::edit_cut)."""
     return max(WAVES, (edit_pairs or EDIT_PAIRS_DEFAULT) // max(n, 1) // WAVES * WAVES)
 
 

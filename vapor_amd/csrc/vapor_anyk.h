@@ -22,9 +22,8 @@
 
 namespace vapor {
 
-constexpr int ANYK_EXACT_MAX_K = 40;
+// (ANYK_EXACT_MAX_K, ANYK_TILE, ANYK_EDIT_WAVES and ANYK_EDIT_PAIRS: vapor_dots_plan.h, where the host's arithmetic reads them too)
 constexpr uint32_t ANYK_NONE = 0xFFFFFFFFu;     // padding entry of the sort (after every real one)
-constexpr int ANYK_TILE = 512;                  // elements sorted in LDS by one 256-thread workgroup
 
 // the symbol bytes of one pair's sequences and how entry e maps to a k-mer of them
 struct AnykSrc {
@@ -238,8 +237,6 @@ __device__ __forceinline__ int anyk_lev(const unsigned long long* peq, const uin
 // lengths).  The host cuts a pair into launches of at most ANYK_EDIT_PAIRS (query, key) distance computations (~0.1 s each), so
 // that a long pair does not hold the device in one kernel; vapor_set_param(ctx, "anyk_edit_pairs", v) puts another number in its
 // place (the tests' way to the launches behind the first at small sizes).
-constexpr int ANYK_EDIT_WAVES = 4;
-constexpr long long ANYK_EDIT_PAIRS = 1ll << 31;
 template <bool EMIT>
 __global__ __launch_bounds__(64 * ANYK_EDIT_WAVES) void anyk_edit_kernel(AnykSrc s, const uint32_t* __restrict__ idx, const int4* __restrict__ keys,
                                                                          const long long* __restrict__ n_keys, int j0, int j1,

@@ -113,7 +113,7 @@ struct vapor_ctx {
     int clean_order = 1;                       // 1: the clean workgroups are dealt out longest pair first (clean_order); 0: in pair order
     int clean_fit = 1;                         // 1: after a blocking run the clean kernel's LDS copy is sized for the records the pairs really hold
     int64_t trace_budget = vapor_trace::BUDGET_DEFAULT;      // bytes of vapor_realign_trace's workspace (never below BUDGET_FLOOR)
-    int64_t anyk_edit_pairs = ANYK_EDIT_PAIRS;  // (query, key) distances one launch of the any-k route's edit pass may hold (anyk_edit_launch)
+    int64_t anyk_edit_pairs = ANYK_EDIT_PAIRS;  // (query, key) distances one launch of the any-k route's edit pass may hold (dots_plan::edit_cut)
     int stage_threads = 3;                     // host threads that copy a large upload into the pinned staging buffer (measured:
                                                // two to four are as fast as it gets, more are slower - tools/upload_sweep.py)
     bool attrs_set = false;
@@ -1812,237 +1812,185 @@ extern "C" int vapor_clean_hits(vapor_ctx* ctx, int64_t n_lists, const int32_t* 
 }
 
 // ------------------------------------------------------------------------------------------
-// The wide route (vapor_wide.h): sequences up to VAPOR_MAX_WIDE_SEQ_LEN, one pair at a time, explicit dots with 32-bit
-// positions.  The narrow entry points above keep their limit and their refusals.
+// The explicit-dot routes: the wide route (vapor_wide.h; sequences up to VAPOR_MAX_WIDE_SEQ_LEN, explicit dots with 32-bit
+// positions) and the any-k route (vapor_anyk.h), one pair at a time.  Their host plan - refusals, sizes, schedules, records - is
+// vapor_dots_plan.h's; here: ensure, memset, the launches, the copies and the synchronisations.  The narrow
+// entry points above keep their limit and their refusals.
+namespace dp = vapor::dots_plan;
+static_assert(dp::SKIP_C2D == HF_C2D && sizeof(int2) == 8 && sizeof(int4) == 16, "what vapor_dots_plan.h states without HIP");
+
 namespace {
 
-struct WideBufs {                  // a route's blocks by slot, each grown to the largest pair so far (Block::ensure)
-    Block<> p[10];
-    enum { KEYS, HEAD, NEXT, CNT, OFF, DOTS, FL, SCR, ACC, BOOK };
-    explicit WideBufs(CallScope& sc) { for (auto& q : p) q.sc = &sc; }
-    hipError_t ensure(int b, size_t bytes) { return p[b].ensure(std::max<size_t>(bytes, 256)); }
-    template <typename T> T* at(int b) const { return reinterpret_cast<T*>(p[b].p); }
+template <typename Slot, int N>
+struct DotBufs {                   // an owner's blocks by slot (vapor_dots_plan.h), each grown to the largest pair so far (Block::ensure)
+    Block<> p[N];
+    explicit DotBufs(CallScope& sc) { for (auto& q : p) q.sc = &sc; }
+    hipError_t ensure(Slot b, size_t bytes) { return p[b].ensure(std::max(bytes, dp::BLOCK_FLOOR)); }
+    template <typename T> T* at(Slot b) const { return reinterpret_cast<T*>(p[b].p); }
 };
+using SharedBufs = DotBufs<dp::SharedSlot, dp::N_SHARED>;
+using WideBufs = DotBufs<dp::WideSlot, dp::N_WIDE>;
+using AnykBufs = DotBufs<dp::AnykSlot, dp::N_ANYK>;
 
-inline unsigned wide_grid(int64_t n) { return (unsigned)((n + 255) / 256); }
-
-// Cleaning and reductions of the n dots in b.DOTS (coordinates i <= maxi, j <= maxj), enqueued on st; the results land in
+// Cleaning and reductions of the n > 0 dots in b.DOTS (coordinates i <= maxi, j <= maxj), enqueued on st; the results land in
 // b.ACC, which the caller has initialised.
-hipError_t wide_clean(WideBufs& b, hipStream_t st, int n, int maxi, int maxj, uint32_t flags)
+hipError_t wide_clean(SharedBufs& b, hipStream_t st, int n, int maxi, int maxj, uint32_t flags)
 {
-    const int2* dots = b.at<int2>(WideBufs::DOTS);
-    uint8_t* fl = b.at<uint8_t>(WideBufs::FL);
-    WideAcc* acc = b.at<WideAcc>(WideBufs::ACC);
-    const bool c1 = flags & 1u, c2 = flags & 2u, s3 = c1 && (flags & 4u);
-    const int R = maxi + maxj + 1, shift = maxj;
-    hipError_t e = b.ensure(WideBufs::SCR, sizeof(uint32_t) * 3 * (size_t)R);
+    const dp::Cleaning c = dp::cleaning(flags);
+    const dp::Scratch s = dp::scratch(maxi, maxj);
+    hipError_t e = b.ensure(dp::SCR, s.bytes);
     if (e != hipSuccess) return e;
-    uint32_t* cnt = b.at<uint32_t>(WideBufs::SCR);
-    uint32_t* gid = cnt + R;
-    uint32_t* gsize = gid + R;
-    auto cluster = [&](int axis, uint32_t skip, int slot, int mode) -> hipError_t {
-        hipError_t e2 = hipMemsetAsync(cnt, 0, sizeof(uint32_t) * (size_t)R, st);
-        if (e2 == hipSuccess) e2 = hipMemsetAsync(gsize, 0, sizeof(uint32_t) * (size_t)R, st);
-        if (e2 != hipSuccess) return e2;
-        hipLaunchKernelGGL(wide_hist_kernel, dim3(wide_grid(n)), dim3(256), 0, st, dots, (const uint8_t*)fl, n, axis, shift, skip, cnt);
-        hipLaunchKernelGGL(wide_group_kernel, dim3(1), dim3(WIDE_SCAN_THREADS), 0, st, (const uint32_t*)cnt, R, gid, gsize, acc, slot);
-        hipLaunchKernelGGL(wide_flag_kernel, dim3(wide_grid(n)), dim3(256), 0, st, dots, fl, n, mode, shift, flags,
-                           (const uint32_t*)gid, (const uint32_t*)gsize, (const WideAcc*)acc);
-        return hipGetLastError();
-    };
-    if (n <= 0) return hipSuccess;
-    if (c1 || c2) {
-        if ((e = cluster(0, 0u, 0, 0)) != hipSuccess) return e;
-        if (c1 && (e = cluster(1, 0u, 1, 1)) != hipSuccess) return e;
-        if (c2 && (e = cluster(1, HF_C2D, 2, 2)) != hipSuccess) return e;
-    } else if ((e = hipMemsetAsync(fl, 0, (size_t)n, st)) != hipSuccess) {
-        return e;
+    const int2* dots = b.at<int2>(dp::DOTS);
+    uint8_t* fl = b.at<uint8_t>(dp::FL);
+    WideAcc* acc = b.at<WideAcc>(dp::ACC);
+    uint32_t *cnt = b.at<uint32_t>(dp::SCR), *gid = cnt + s.R, *gsize = gid + s.R;
+    const dim3 grid(dp::grid(n)), block(dp::THREADS);
+    for (int t = 0; t < c.n_passes; ++t) {
+        const dp::ClusterPass& q = c.pass[t];
+        if ((e = hipMemsetAsync(cnt, 0, s.axis_bytes(), st)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(gsize, 0, s.axis_bytes(), st)) != hipSuccess) return e;
+        hipLaunchKernelGGL(wide_hist_kernel, grid, block, 0, st, dots, (const uint8_t*)fl, n, q.axis, s.shift, q.skip, cnt);
+        hipLaunchKernelGGL(wide_group_kernel, dim3(1), dim3(WIDE_SCAN_THREADS), 0, st, (const uint32_t*)cnt, s.R, gid, gsize, acc, q.slot);
+        hipLaunchKernelGGL(wide_flag_kernel, grid, block, 0, st, dots, fl, n, q.mode, s.shift, flags, (const uint32_t*)gid, (const uint32_t*)gsize,
+                           (const WideAcc*)acc);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(wide_reduce_kernel, dim3(wide_grid(n)), dim3(256), 0, st, dots, fl, n, acc);
+    if (c.zero_flags && (e = hipMemsetAsync(fl, 0, (size_t)n, st)) != hipSuccess) return e;
+    hipLaunchKernelGGL(wide_reduce_kernel, grid, block, 0, st, dots, fl, n, acc);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    if (s3) {
-        if ((e = hipMemsetAsync(cnt, 0, sizeof(uint32_t) * (size_t)R, st)) != hipSuccess) return e;
+    if (c.dir) {
+        if ((e = hipMemsetAsync(cnt, 0, s.axis_bytes(), st)) != hipSuccess) return e;
         hipLaunchKernelGGL(wide_dir_kernel, dim3(1), dim3(WIDE_SCAN_THREADS), 0, st, dots, (const uint8_t*)fl, n, acc, cnt);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     return hipSuccess;
 }
 
-WideAcc wide_acc_init()
-{
-    WideAcc a;
-    memset(&a, 0, sizeof(a));
-    a.min_j = 0x7FFFFFFF; a.max_j = -1; a.kd_lo = 0x7FFFFFFF; a.kd_hi = -0x7FFFFFFF;
-    return a;
-}
-
-void wide_stats(const WideAcc& a, int64_t n, uint32_t flags, int64_t* st)
-{
-    const bool s3 = (flags & 1u) && (flags & 4u);
-    for (int t = 0; t < 16; ++t) st[t] = 0;
-    st[0] = n;
-    st[1] = n ? a.min_j : -1;
-    st[2] = n ? a.max_j : -1;
-    if (!n) return;
-    st[3] = (int64_t)a.c1_kept; st[4] = (int64_t)a.c1_sum_abs; st[5] = (int64_t)a.c2_kept; st[6] = (int64_t)a.c2_count10;
-    st[7] = (int64_t)a.n_diag; st[8] = (int64_t)a.n_lower; st[9] = (int64_t)a.c2_kept_diag;
-    if (s3) { st[10] = a.dir_c2x; st[11] = a.dir_n; st[12] = a.dir_sum2; st[13] = a.dir_lists; }
-}
-
-template <int K>
-void wide_join_launch(WideBufs& b, hipStream_t st, const uint32_t* x4_1, int nk1, const uint32_t* x4_2, int off2, int nk2,
-                      uint32_t hmask, bool emit, unsigned long long cap)
-{
-    const WKey<K>* keys = b.at<const WKey<K>>(WideBufs::KEYS);
-    if (!emit) {
-        hipLaunchKernelGGL(wide_table_kernel<K>, dim3(wide_grid(2 * (int64_t)nk1)), dim3(256), 0, st, x4_1, nk1, b.at<WKey<K>>(WideBufs::KEYS),
-                           b.at<int32_t>(WideBufs::HEAD), b.at<int32_t>(WideBufs::NEXT), hmask);
-        hipLaunchKernelGGL((wide_probe_kernel<K, false>), dim3(wide_grid(nk2)), dim3(256), 0, st, x4_2, off2, nk2, keys,
-                           (const int32_t*)b.at<int32_t>(WideBufs::HEAD), (const int32_t*)b.at<int32_t>(WideBufs::NEXT), hmask,
-                           b.at<uint32_t>(WideBufs::CNT), (const long long*)nullptr, (int2*)nullptr,
-                           b.at<unsigned long long>(WideBufs::BOOK), cap);
-        hipLaunchKernelGGL(wide_scan_kernel, dim3(1), dim3(WIDE_SCAN_THREADS), 0, st, (const uint32_t*)b.at<uint32_t>(WideBufs::CNT), nk2,
-                           b.at<long long>(WideBufs::OFF));
-    } else {
-        hipLaunchKernelGGL((wide_probe_kernel<K, true>), dim3(wide_grid(nk2)), dim3(256), 0, st, x4_2, off2, nk2, keys,
-                           (const int32_t*)b.at<int32_t>(WideBufs::HEAD), (const int32_t*)b.at<int32_t>(WideBufs::NEXT), hmask,
-                           (uint32_t*)nullptr, (const long long*)b.at<long long>(WideBufs::OFF), b.at<int2>(WideBufs::DOTS),
-                           (unsigned long long*)nullptr, cap);
-    }
-}
-
-void wide_join(int k, WideBufs& b, hipStream_t st, const uint32_t* x4_1, int nk1, const uint32_t* x4_2, int off2, int nk2,
-               uint32_t hmask, bool emit, unsigned long long cap)
-{
-    switch (k) {
-    case 10: wide_join_launch<10>(b, st, x4_1, nk1, x4_2, off2, nk2, hmask, emit, cap); break;
-    case 20: wide_join_launch<20>(b, st, x4_1, nk1, x4_2, off2, nk2, hmask, emit, cap); break;
-    case 30: wide_join_launch<30>(b, st, x4_1, nk1, x4_2, off2, nk2, hmask, emit, cap); break;
-    default: wide_join_launch<40>(b, st, x4_1, nk1, x4_2, off2, nk2, hmask, emit, cap); break;
-    }
-}
-
 }  // namespace
 
 // The per-pair loop of the explicit-dot routes (vapor_wide_batch, vapor_anyk_batch).  A Route supplies three things:
-//   admit(a)                         the status the pair gets before any device work, 0 to go on (the order of a route's
-//                                    refusals is part of its contract);
-//   count(a, s1, s2, nk1, nk2, &at)  enqueues the count pass and says where on the device the number of dots will stand;
-//   emit(a, nk1, nk2)                enqueues the dots into b.DOTS.
-// The loop owns everything else: the accumulator, the read-back of the total, the pair that outgrows max_pair_cap, DOTS / FL,
+//   admit(view, a)                   the status the pair gets before any device work, 0 to go on (dots_plan::admit_wide / admit_anyk);
+//   count(a, s1, s2, shape, &at)     enqueues the count pass and says where on the device the number of dots will stand;
+//   emit(a, shape)                   enqueues the dots into b.DOTS.
+// The loop owns everything else: the accumulator, the read-back of the total, the pair that outgrows the dot bound, DOTS / FL,
 // the cleaning, the copies out and hit_off.  Two synchronisations per scored pair, one for a pair without k-mers.
 template <typename Route>
 static int dot_pairs(const std::string& who, vapor_ctx* ctx, vapor_seqset* set, int64_t n_pairs, const vapor_pair* pairs, int64_t* stats,
               int32_t* hits_ji, int64_t hits_capacity, int64_t* hit_off)
 {
-    if (!ctx || !set || n_pairs < 0 || (n_pairs && (!pairs || !stats)) || (hits_ji && !hit_off) || hits_capacity < 0)
-        return fail(VAPOR_E_ARG, who + ": null argument");
+    if (const auto no = dp::call_refusal(dp::Call{dp::BATCH, ctx && set, n_pairs, stats, hits_ji, hit_off, pairs, hits_capacity, 0})) return refused(who, no);
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     CallScope sc(ctx, st);
-    const WideAcc init = wide_acc_init();
+    const WideAcc init = dp::acc_init();
     WideAcc res;
     long long total = 0;
-    WideBufs b(sc);
-    Route route(sc, b, set);
-    HIPCHK(b.ensure(WideBufs::ACC, sizeof(WideAcc)));
+    const int64_t cap = dp::dots_cap(ctx->max_pair_cap);
+    const dp::SetView view{set->n, set->h.data(), set->raw_off.data(), set->raw_off.size()};
+    SharedBufs b(sc);
+    Route route(sc, b, set, cap);
+    HIPCHK(b.ensure(dp::ACC, sizeof(WideAcc)));
     HIPCHK(route.prepare());
-    int64_t running = 0;
-    if (hit_off) hit_off[0] = 0;
+    dp::Capacity room(hits_ji != nullptr, hits_capacity, hit_off);
     for (int64_t t = 0; t < n_pairs; ++t) {
         const vapor_pair& a = pairs[t];
         int64_t* s = stats + 16 * t;
-        auto refuse = [&](int code) {
-            for (int q = 0; q < 16; ++q) s[q] = 0;
-            s[1] = s[2] = -1;
-            s[15] = code;
-        };
         int64_t n = 0;
-        if (const int code = route.admit(a)) {
-            refuse(code);
+        if (const int code = Route::admit(view, a)) {
+            dp::record_refused(code, s);
         } else {
             const SeqDesc& s1 = set->h[a.seq1];
             const SeqDesc& s2 = set->h[a.seq2];
-            const int nk1 = s1.len - a.k + 1, nk2 = std::max(0, s2.len - a.off2) - a.k + 1;
-            HIPCHK(hipMemcpyAsync(b.p[WideBufs::ACC], &init, sizeof(WideAcc), hipMemcpyHostToDevice, st));
-            if (nk1 > 0 && nk2 > 0) {
+            const dp::Shape sh = dp::shape(s1, s2, a);
+            HIPCHK(hipMemcpyAsync(b.p[dp::ACC], &init, sizeof(WideAcc), hipMemcpyHostToDevice, st));
+            if (sh.kmers()) {
                 const long long* d_total = nullptr;
-                HIPCHK(route.count(a, s1, s2, nk1, nk2, &d_total));
+                HIPCHK(route.count(a, s1, s2, sh, &d_total));
                 HIPCHK(hipMemcpyAsync(&total, d_total, sizeof(long long), hipMemcpyDeviceToHost, st));
                 HIPCHK(hipStreamSynchronize(st));
-                if (total > ctx->max_pair_cap) {
-                    // more dots than a pair may hold ("max_pair_cap"): the pair keeps VAPOR_E_OVERFLOW with the dots counted
-                    // (the wide route's count pass stops early: more than max_pair_cap, not necessarily all of them)
-                    refuse(VAPOR_E_OVERFLOW);
-                    s[0] = total;
-                    s[14] = total;
-                    if (hit_off) hit_off[t + 1] = running;
+                if (total > cap) {
+                    dp::record_overflowed(total, s);
+                    room.close(t, 0);
                     continue;
                 }
                 n = total;
-                HIPCHK(b.ensure(WideBufs::DOTS, sizeof(int2) * (size_t)n));
-                HIPCHK(b.ensure(WideBufs::FL, (size_t)n));
+                HIPCHK(b.ensure(dp::DOTS, sizeof(int2) * (size_t)n));
+                HIPCHK(b.ensure(dp::FL, (size_t)n));
                 if (n) {
-                    HIPCHK(route.emit(a, nk1, nk2));
-                    HIPCHK(wide_clean(b, st, (int)n, nk1 - 1, nk2 - 1, a.flags));
+                    HIPCHK(route.emit(a, sh));
+                    HIPCHK(wide_clean(b, st, (int)n, sh.nk1 - 1, sh.nk2 - 1, a.flags));
                 }
             }
-            HIPCHK(hipMemcpyAsync(&res, b.p[WideBufs::ACC], sizeof(WideAcc), hipMemcpyDeviceToHost, st));
-            if (hits_ji && n && running + n <= hits_capacity)
-                HIPCHK(hipMemcpyAsync(hits_ji + 2 * running, b.p[WideBufs::DOTS], sizeof(int2) * (size_t)n, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(&res, b.p[dp::ACC], sizeof(WideAcc), hipMemcpyDeviceToHost, st));
+            if (room.fits(n)) HIPCHK(hipMemcpyAsync(hits_ji + 2 * room.running, b.p[dp::DOTS], sizeof(int2) * (size_t)n, hipMemcpyDeviceToHost, st));
             HIPCHK(hipStreamSynchronize(st));
-            wide_stats(res, n, a.flags, s);
+            dp::record_folded(res, n, a.flags, s);
         }
-        running += n;
-        if (hit_off) hit_off[t + 1] = running;
+        room.close(t, n);
     }
     sc.settled();              // (every pair ended in a synchronisation, a refused one enqueued nothing)
-    if (hits_ji && running > hits_capacity)
-        return fail(VAPOR_E_OVERFLOW, who + ": hits_capacity too small (hit_off[n_pairs] holds the count needed)");
+    if (room.overflowed()) return fail(VAPOR_E_OVERFLOW, who + ": hits_capacity too small (hit_off[n_pairs] holds the count needed)");
     return VAPOR_OK;
 }
 
 namespace {
 struct WideRoute {
-    WideBufs& b;
+    SharedBufs& b;
+    WideBufs w;
     hipStream_t st;
     const vapor_seqset* set;
-    const unsigned long long cap;
+    const unsigned long long cap;                          // the dot bound: the count pass stops booking beyond it
     const uint32_t *x4_1 = nullptr, *x4_2 = nullptr;       // of the pair being counted, for its emit pass
-    uint32_t H = 1;
-    WideRoute(CallScope& sc, WideBufs& bufs, const vapor_seqset* s)
-        : b(bufs), st(sc.st), set(s), cap((unsigned long long)std::max<int64_t>(sc.ctx->max_pair_cap, 0)) {}
-    hipError_t prepare() { return b.ensure(WideBufs::BOOK, sizeof(unsigned long long)); }
-    int admit(const vapor_pair& a) const
+    dp::WideJoin j{};
+    WideRoute(CallScope& sc, SharedBufs& bufs, const vapor_seqset* s, int64_t dots_cap)
+        : b(bufs), w(sc), st(sc.st), set(s), cap((unsigned long long)dots_cap) {}
+    hipError_t prepare() { return w.ensure(dp::WIDE_BOOKED, sizeof(unsigned long long)); }
+    static int admit(const dp::SetView& v, const vapor_pair& a) { return dp::admit_wide(v, a); }
+    template <int K>
+    void join(const vapor_pair& a, const dp::Shape& sh, bool emit)
     {
-        if (a.seq1 < 0 || a.seq1 >= set->n || a.seq2 < 0 || a.seq2 >= set->n || a.off2 < 0 || !k_supported(a.k)) return VAPOR_E_ARG;
-        if (set->h[a.seq1].len > VAPOR_MAX_WIDE_SEQ_LEN || set->h[a.seq2].len > VAPOR_MAX_WIDE_SEQ_LEN) return VAPOR_E_ARG;
-        if (set->h[a.seq1].len - a.k + 1 > 0 && set->h[a.seq1].n_invalid > 0) return VAPOR_E_KEYERROR;
-        return 0;
+        const WKey<K>* keys = w.at<const WKey<K>>(dp::WIDE_KEYS);
+        const int32_t *head = w.at<int32_t>(dp::WIDE_HEAD), *next = w.at<int32_t>(dp::WIDE_NEXT);
+        const dim3 block(dp::THREADS);
+        if (!emit) {
+            hipLaunchKernelGGL(wide_table_kernel<K>, dim3(j.table_grid), block, 0, st, x4_1, sh.nk1, w.at<WKey<K>>(dp::WIDE_KEYS),
+                               w.at<int32_t>(dp::WIDE_HEAD), w.at<int32_t>(dp::WIDE_NEXT), j.mask);
+            hipLaunchKernelGGL((wide_probe_kernel<K, false>), dim3(j.probe_grid), block, 0, st, x4_2, a.off2, sh.nk2, keys, head, next, j.mask,
+                               w.at<uint32_t>(dp::WIDE_CNT), (const long long*)nullptr, (int2*)nullptr, w.at<unsigned long long>(dp::WIDE_BOOKED), cap);
+            hipLaunchKernelGGL(wide_scan_kernel, dim3(j.scan_grid), dim3(WIDE_SCAN_THREADS), 0, st, (const uint32_t*)w.at<uint32_t>(dp::WIDE_CNT), sh.nk2,
+                               w.at<long long>(dp::WIDE_OFF));
+        } else {
+            hipLaunchKernelGGL((wide_probe_kernel<K, true>), dim3(j.probe_grid), block, 0, st, x4_2, a.off2, sh.nk2, keys, head, next, j.mask,
+                               (uint32_t*)nullptr, (const long long*)w.at<long long>(dp::WIDE_OFF), b.at<int2>(dp::DOTS), (unsigned long long*)nullptr, cap);
+        }
     }
-    hipError_t count(const vapor_pair& a, const SeqDesc& s1, const SeqDesc& s2, int nk1, int nk2, const long long** d_total)
+    hipError_t join(const vapor_pair& a, const dp::Shape& sh, bool emit)
     {
-        const int64_t ne = 2 * (int64_t)nk1;
-        for (H = 1; (int64_t)H < 2 * ne;) H <<= 1;
+        switch (a.k) {
+        case 10: join<10>(a, sh, emit); break;
+        case 20: join<20>(a, sh, emit); break;
+        case 30: join<30>(a, sh, emit); break;
+        default: join<40>(a, sh, emit); break;
+        }
+        return hipGetLastError();
+    }
+    hipError_t count(const vapor_pair& a, const SeqDesc& s1, const SeqDesc& s2, const dp::Shape& sh, const long long** d_total)
+    {
+        j = dp::wide_join(a.k, sh.nk1, sh.nk2);
         hipError_t e;
-        if ((e = b.ensure(WideBufs::KEYS, (size_t)ne * sizeof(uint32_t) * ((4 * a.k + 31) / 32))) != hipSuccess) return e;
-        if ((e = b.ensure(WideBufs::HEAD, sizeof(int32_t) * (size_t)H)) != hipSuccess) return e;
-        if ((e = b.ensure(WideBufs::NEXT, sizeof(int32_t) * (size_t)ne)) != hipSuccess) return e;
-        if ((e = b.ensure(WideBufs::CNT, sizeof(uint32_t) * (size_t)nk2)) != hipSuccess) return e;
-        if ((e = b.ensure(WideBufs::OFF, sizeof(long long) * ((size_t)nk2 + 1))) != hipSuccess) return e;
-        if ((e = hipMemsetAsync(b.p[WideBufs::HEAD], 0xFF, sizeof(int32_t) * (size_t)H, st)) != hipSuccess) return e;
-        if ((e = hipMemsetAsync(b.p[WideBufs::BOOK], 0, sizeof(unsigned long long), st)) != hipSuccess) return e;
+        if ((e = w.ensure(dp::WIDE_KEYS, j.keys)) != hipSuccess) return e;
+        if ((e = w.ensure(dp::WIDE_HEAD, j.heads)) != hipSuccess) return e;
+        if ((e = w.ensure(dp::WIDE_NEXT, j.nexts)) != hipSuccess) return e;
+        if ((e = w.ensure(dp::WIDE_CNT, j.counts)) != hipSuccess) return e;
+        if ((e = w.ensure(dp::WIDE_OFF, j.offsets)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(w.p[dp::WIDE_HEAD], 0xFF, j.heads, st)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(w.p[dp::WIDE_BOOKED], 0, sizeof(unsigned long long), st)) != hipSuccess) return e;
         x4_1 = set->d_x4 + (size_t)s1.chunk0 * 4;
         x4_2 = set->d_x4 + (size_t)s2.chunk0 * 4;
-        wide_join(a.k, b, st, x4_1, nk1, x4_2, a.off2, nk2, H - 1, false, cap);
-        *d_total = b.at<long long>(WideBufs::OFF) + nk2;
-        return hipGetLastError();
+        *d_total = w.at<long long>(dp::WIDE_OFF) + sh.nk2;
+        return join(a, sh, false);
     }
-    hipError_t emit(const vapor_pair& a, int nk1, int nk2)
-    {
-        wide_join(a.k, b, st, x4_1, nk1, x4_2, a.off2, nk2, H - 1, true, cap);
-        return hipGetLastError();
-    }
+    hipError_t emit(const vapor_pair& a, const dp::Shape& sh) { return join(a, sh, true); }
 };
 }  // namespace
 
@@ -2055,32 +2003,31 @@ extern "C" int vapor_wide_batch(vapor_ctx* ctx, vapor_seqset* set, int64_t n_pai
 extern "C" int vapor_clean_hits_wide(vapor_ctx* ctx, int64_t n_lists, const int32_t* hits_ji, const int64_t* off,
                                      const uint32_t* flags, int64_t* stats, uint8_t* hit_flags)
 {
-    if (const auto no = clean_plan::lists_check(ctx != nullptr, n_lists, hits_ji, off, stats, VAPOR_MAX_WIDE_SEQ_LEN, ctx ? ctx->max_pair_cap : 0))
+    if (const auto no = dp::call_refusal(dp::Call{dp::LISTS, ctx != nullptr, n_lists, stats, hits_ji, off, nullptr, 0, ctx ? ctx->max_pair_cap : 0}))
         return refused("vapor_clean_hits_wide", no);
     if (n_lists == 0) return VAPOR_OK;
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     CallScope sc(ctx, st);
-    const WideAcc init = wide_acc_init();
+    const WideAcc init = dp::acc_init();
     WideAcc res;
-    WideBufs b(sc);
-    HIPCHK(b.ensure(WideBufs::ACC, sizeof(WideAcc)));
+    SharedBufs b(sc);
+    HIPCHK(b.ensure(dp::ACC, sizeof(WideAcc)));
     for (int64_t t = 0; t < n_lists; ++t) {
         const int64_t n = off[t + 1] - off[t];
-        const uint32_t f = flags ? flags[t] : 3u;
-        int mi = 0, mj = 0;
-        for (int64_t h = off[t]; h < off[t + 1]; ++h) { mj = std::max(mj, hits_ji[2 * h]); mi = std::max(mi, hits_ji[2 * h + 1]); }
-        HIPCHK(hipMemcpyAsync(b.p[WideBufs::ACC], &init, sizeof(WideAcc), hipMemcpyHostToDevice, st));
+        const uint32_t f = flags ? flags[t] : dp::LIST_FLAGS;
+        const dp::Extent x = dp::extent(hits_ji, off[t], off[t + 1]);
+        HIPCHK(hipMemcpyAsync(b.p[dp::ACC], &init, sizeof(WideAcc), hipMemcpyHostToDevice, st));
         if (n) {
-            HIPCHK(b.ensure(WideBufs::DOTS, sizeof(int2) * (size_t)n));
-            HIPCHK(b.ensure(WideBufs::FL, (size_t)n));
-            HIPCHK(hipMemcpyAsync(b.p[WideBufs::DOTS], hits_ji + 2 * off[t], sizeof(int2) * (size_t)n, hipMemcpyHostToDevice, st));
-            HIPCHK(wide_clean(b, st, (int)n, mi, mj, f));
+            HIPCHK(b.ensure(dp::DOTS, sizeof(int2) * (size_t)n));
+            HIPCHK(b.ensure(dp::FL, (size_t)n));
+            HIPCHK(hipMemcpyAsync(b.p[dp::DOTS], hits_ji + 2 * off[t], sizeof(int2) * (size_t)n, hipMemcpyHostToDevice, st));
+            HIPCHK(wide_clean(b, st, (int)n, x.mi, x.mj, f));
         }
-        HIPCHK(hipMemcpyAsync(&res, b.p[WideBufs::ACC], sizeof(WideAcc), hipMemcpyDeviceToHost, st));
-        if (hit_flags && n) HIPCHK(hipMemcpyAsync(hit_flags + off[t], b.p[WideBufs::FL], (size_t)n, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(&res, b.p[dp::ACC], sizeof(WideAcc), hipMemcpyDeviceToHost, st));
+        if (hit_flags && n) HIPCHK(hipMemcpyAsync(hit_flags + off[t], b.p[dp::FL], (size_t)n, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
-        wide_stats(res, n, f, stats + 16 * t);
+        dp::record_folded(res, n, f, stats + 16 * t);
     }
     sc.settled();
     return VAPOR_OK;
@@ -2090,132 +2037,83 @@ extern "C" int vapor_clean_hits_wide(vapor_ctx* ctx, int64_t n_lists, const int3
 // The any-k route (vapor_anyk.h): kmerhits at every k from 1 to VAPOR_MAX_ANY_K, dots in the reference's order, the statistics
 // from the wide route's cleaning.
 namespace {
-
-// the pair's symbol bytes, sorted entries and per-j counts: enqueued on st, the number of dots at b.OFF[nk2]
-struct AnykBufs : WideBufs {
-    using WideBufs::WideBufs;
-    enum { SYM, IDX, CNT, FIRST, OFF, ISF, RUN, RANK, KEYS };
-    long long edit_pairs = ANYK_EDIT_PAIRS;        // the context's "anyk_edit_pairs"
-};
-
-inline size_t anyk_pad(int n) { return ((size_t)n + 16 + 15) & ~(size_t)15; }
-
-// the edit-distance pass over allele k-mers 0 .. nk2 - 1, in launches of at most edit_pairs distances ("anyk_edit_pairs",
-// ANYK_EDIT_PAIRS unless set; n entries bound the number of keys)
-template <bool EMIT>
-void anyk_edit_launch(AnykBufs& x, hipStream_t st, const AnykSrc& src, int n, int nk2, uint32_t* cnt, const long long* off, int2* dots)
-{
-    const long long per = std::max<long long>(ANYK_EDIT_WAVES, x.edit_pairs / std::max(n, 1) / ANYK_EDIT_WAVES * ANYK_EDIT_WAVES);
-    for (long long j0 = 0; j0 < nk2; j0 += per) {
-        const int j1 = (int)std::min<long long>(nk2, j0 + per);
-        hipLaunchKernelGGL((anyk_edit_kernel<EMIT>), dim3((unsigned)((j1 - j0 + ANYK_EDIT_WAVES - 1) / ANYK_EDIT_WAVES)), dim3(64 * ANYK_EDIT_WAVES), 0,
-                           st, src, x.at<const uint32_t>(AnykBufs::IDX), (const int4*)x.at<int4>(AnykBufs::KEYS),
-                           (const long long*)(x.at<long long>(AnykBufs::RANK) + n), (int)j0, j1, cnt, off, dots);
-    }
-}
-
-hipError_t anyk_count(AnykBufs& x, hipStream_t st, const AnykSrc& src, int nk1, int nk2)
-{
-    const int n = src.inv ? 2 * nk1 : nk1;
-    int np = ANYK_TILE;
-    while (np < n) np <<= 1;
-    hipError_t e;
-    if ((e = x.ensure(AnykBufs::IDX, sizeof(uint32_t) * (size_t)np)) != hipSuccess) return e;
-    uint32_t* idx = x.at<uint32_t>(AnykBufs::IDX);
-    hipLaunchKernelGGL(anyk_iota_kernel, dim3(wide_grid(np)), dim3(256), 0, st, idx, n, np);
-    hipLaunchKernelGGL(anyk_sort_local_kernel, dim3(np / ANYK_TILE), dim3(256), 0, st, src, idx, 1, 0);
-    for (int kk = 2 * ANYK_TILE; kk <= np; kk <<= 1) {
-        for (int jj = kk >> 1; jj >= ANYK_TILE; jj >>= 1)
-            hipLaunchKernelGGL(anyk_sort_global_kernel, dim3(wide_grid(np / 2)), dim3(256), 0, st, src, idx, np, kk, jj);
-        hipLaunchKernelGGL(anyk_sort_local_kernel, dim3(np / ANYK_TILE), dim3(256), 0, st, src, idx, 0, kk);
-    }
-    if ((e = x.ensure(AnykBufs::CNT, sizeof(uint32_t) * (size_t)nk2)) != hipSuccess) return e;
-    if ((e = x.ensure(AnykBufs::OFF, sizeof(long long) * ((size_t)nk2 + 1))) != hipSuccess) return e;
-    uint32_t* cnt = x.at<uint32_t>(AnykBufs::CNT);
-    if (src.k <= ANYK_EXACT_MAX_K) {
-        if ((e = x.ensure(AnykBufs::FIRST, sizeof(uint32_t) * (size_t)nk2)) != hipSuccess) return e;
-        hipLaunchKernelGGL(anyk_probe_kernel, dim3(wide_grid(nk2)), dim3(256), 0, st, src, (const uint32_t*)idx, n, nk2, cnt,
-                           x.at<uint32_t>(AnykBufs::FIRST));
-    } else {
-        if ((e = x.ensure(AnykBufs::ISF, sizeof(uint32_t) * (size_t)n)) != hipSuccess) return e;
-        if ((e = x.ensure(AnykBufs::RUN, sizeof(int2) * (size_t)n)) != hipSuccess) return e;
-        if ((e = x.ensure(AnykBufs::RANK, sizeof(long long) * ((size_t)n + 1))) != hipSuccess) return e;
-        if ((e = x.ensure(AnykBufs::KEYS, sizeof(int4) * (size_t)n)) != hipSuccess) return e;
-        if ((e = hipMemsetAsync(x.p[AnykBufs::ISF], 0, sizeof(uint32_t) * (size_t)n, st)) != hipSuccess) return e;
-        hipLaunchKernelGGL(anyk_group_kernel, dim3(wide_grid(n)), dim3(256), 0, st, src, (const uint32_t*)idx, n,
-                           x.at<uint32_t>(AnykBufs::ISF), x.at<int2>(AnykBufs::RUN));
-        hipLaunchKernelGGL(wide_scan_kernel, dim3(1), dim3(WIDE_SCAN_THREADS), 0, st, (const uint32_t*)x.at<uint32_t>(AnykBufs::ISF), n,
-                           x.at<long long>(AnykBufs::RANK));
-        hipLaunchKernelGGL(anyk_rank_kernel, dim3(wide_grid(n)), dim3(256), 0, st, n, (const uint32_t*)x.at<uint32_t>(AnykBufs::ISF),
-                           (const long long*)x.at<long long>(AnykBufs::RANK), (const int2*)x.at<int2>(AnykBufs::RUN), x.at<int4>(AnykBufs::KEYS));
-        anyk_edit_launch<false>(x, st, src, n, nk2, cnt, nullptr, nullptr);
-    }
-    hipLaunchKernelGGL(wide_scan_kernel, dim3(1), dim3(WIDE_SCAN_THREADS), 0, st, (const uint32_t*)cnt, nk2, x.at<long long>(AnykBufs::OFF));
-    return hipGetLastError();
-}
-
-void anyk_emit(AnykBufs& x, hipStream_t st, const AnykSrc& src, int nk1, int nk2, int2* dots)
-{
-    const int n = src.inv ? 2 * nk1 : nk1;
-    const uint32_t* idx = x.at<const uint32_t>(AnykBufs::IDX);
-    const long long* off = x.at<const long long>(AnykBufs::OFF);
-    if (src.k <= ANYK_EXACT_MAX_K)
-        hipLaunchKernelGGL(anyk_emit_kernel, dim3(wide_grid(nk2)), dim3(256), 0, st, src, idx, nk2, (const uint32_t*)x.at<uint32_t>(AnykBufs::CNT),
-                           (const uint32_t*)x.at<uint32_t>(AnykBufs::FIRST), off, dots);
-    else
-        anyk_edit_launch<true>(x, st, src, n, nk2, nullptr, off, dots);
-}
-
-}  // namespace
-
-namespace {
 struct AnykRoute {
-    WideBufs& b;
+    SharedBufs& b;
     AnykBufs x;
     hipStream_t st;
     const vapor_seqset* set;
+    const long long edit_pairs;                    // the context's "anyk_edit_pairs"
     AnykSrc src{};                                 // of the pair being counted, for its emit pass
-    AnykRoute(CallScope& sc, WideBufs& bufs, const vapor_seqset* s) : b(bufs), x(sc), st(sc.st), set(s) { x.edit_pairs = sc.ctx->anyk_edit_pairs; }
+    dp::AnykPass p{};
+    AnykRoute(CallScope& sc, SharedBufs& bufs, const vapor_seqset* s, int64_t) : b(bufs), x(sc), st(sc.st), set(s), edit_pairs(sc.ctx->anyk_edit_pairs) {}
     hipError_t prepare() { return hipSuccess; }
-    bool no_bytes(int32_t q) const                 // a symbol outside the alphabet whose byte was not kept
+    static int admit(const dp::SetView& v, const vapor_pair& a) { return dp::admit_anyk(v, a); }
+    // the bytes the set kept of sequence q (it holds a symbol outside the alphabet), or null
+    const uint8_t* raw(int32_t q) const
     {
-        return set->h[q].n_invalid > 0 && (q >= (int32_t)set->raw_off.size() || set->raw_off[q] < 0);
+        return set->h[q].n_invalid > 0 && (size_t)q < set->raw_off.size() && set->raw_off[q] >= 0 ? set->d_raw + set->raw_off[q] : nullptr;
     }
-    int admit(const vapor_pair& a) const
+    // the edit-distance pass over the allele k-mers, one launch per range of the cut
+    template <bool EMIT>
+    void edit(int nk2, uint32_t* cnt, const long long* off, int2* dots)
     {
-        const bool inv = !(a.flags & VAPOR_PF_FORWARD);
-        if (a.seq1 < 0 || a.seq1 >= set->n || a.seq2 < 0 || a.seq2 >= set->n || a.off2 < 0 || a.k < 1 || a.k > VAPOR_MAX_ANY_K) return VAPOR_E_ARG;
-        if (set->h[a.seq1].len > VAPOR_MAX_WIDE_SEQ_LEN || set->h[a.seq2].len > VAPOR_MAX_WIDE_SEQ_LEN) return VAPOR_E_ARG;
-        if (inv && set->h[a.seq1].len - a.k + 1 > 0 && set->h[a.seq1].n_invalid > 0) return VAPOR_E_KEYERROR;
-        if (!inv && (no_bytes(a.seq1) || no_bytes(a.seq2))) return VAPOR_E_ARG;
-        return 0;
+        const dp::EditCut c = dp::edit_cut(p.n, nk2, edit_pairs);
+        for (int t = 0; t < c.launches(); ++t)
+            hipLaunchKernelGGL((anyk_edit_kernel<EMIT>), dim3(c.grid(t)), dim3(64 * ANYK_EDIT_WAVES), 0, st, src, x.at<const uint32_t>(dp::ANYK_IDX),
+                               (const int4*)x.at<int4>(dp::ANYK_KEYS), (const long long*)(x.at<long long>(dp::ANYK_RANK) + p.n), c.j0(t), c.j1(t), cnt, off, dots);
     }
-    hipError_t count(const vapor_pair& a, const SeqDesc& s1, const SeqDesc& s2, int nk1, int nk2, const long long** d_total)
+    // the pair's symbol bytes, sorted entries and per-j counts: enqueued on st, the number of dots at x.OFF[nk2]
+    hipError_t count(const vapor_pair& a, const SeqDesc& s1, const SeqDesc& s2, const dp::Shape& sh, const long long** d_total)
     {
-        const bool inv = !(a.flags & VAPOR_PF_FORWARD);
-        const int n2 = std::max(0, s2.len - a.off2);
-        const size_t o_r1 = anyk_pad(s1.len), o_s2 = o_r1 + (inv ? anyk_pad(s1.len) : 0);
-        hipError_t e = x.ensure(AnykBufs::SYM, o_s2 + anyk_pad(n2));
-        if (e != hipSuccess) return e;
-        uint8_t* sym = x.at<uint8_t>(AnykBufs::SYM);
+        const bool inv = !dp::forward_only(a);
+        p = dp::anyk_pass(a.k, inv, s1.len, sh);
+        const dp::Symbols& y = p.sym;
+        hipError_t e;
+        for (int q = 0; q < dp::N_ANYK; ++q)
+            if (p.bytes[q] && (e = x.ensure((dp::AnykSlot)q, p.bytes[q])) != hipSuccess) return e;
+        uint8_t* sym = x.at<uint8_t>(dp::ANYK_SYM);
         const uint32_t* x4_1 = set->d_x4 + (size_t)s1.chunk0 * 4;
         const uint32_t* x4_2 = set->d_x4 + (size_t)s2.chunk0 * 4;
-        const uint8_t* raw1 = !inv && s1.n_invalid > 0 ? set->d_raw + set->raw_off[a.seq1] : nullptr;
-        const uint8_t* raw2 = s2.n_invalid > 0 && a.seq2 < (int32_t)set->raw_off.size() && set->raw_off[a.seq2] >= 0
-                                  ? set->d_raw + set->raw_off[a.seq2] : nullptr;
-        hipLaunchKernelGGL(anyk_sym_kernel, dim3(wide_grid(s1.len)), dim3(256), 0, st, x4_1, raw1, (int)(s1.flags & 1u), 0, s1.len,
-                           sym, inv ? sym + o_r1 : (uint8_t*)nullptr);
-        // (with inversions a symbol of seq2 outside the alphabet matches nothing: it stays 0xFF)
-        hipLaunchKernelGGL(anyk_sym_kernel, dim3(wide_grid(n2)), dim3(256), 0, st, x4_2, inv ? (const uint8_t*)nullptr : raw2,
-                           (int)(s2.flags & 1u), a.off2, n2, sym + o_s2, (uint8_t*)nullptr);
-        src = AnykSrc{sym, sym + o_r1, sym + o_s2, s1.len, a.k, inv ? 1 : 0};
-        if ((e = anyk_count(x, st, src, nk1, nk2)) != hipSuccess) return e;
-        *d_total = x.at<long long>(AnykBufs::OFF) + nk2;
-        return hipSuccess;
+        const dim3 block(dp::THREADS);
+        // (without inversions a symbol outside the alphabet is compared byte for byte; with them one of seq1 is refused, and one of
+        // seq2 matches nothing: it stays 0xFF)
+        hipLaunchKernelGGL(anyk_sym_kernel, dim3(dp::grid(s1.len)), block, 0, st, x4_1, inv ? (const uint8_t*)nullptr : raw(a.seq1), (int)(s1.flags & 1u), 0,
+                           s1.len, sym + y.s1, inv ? sym + y.r1 : (uint8_t*)nullptr);
+        hipLaunchKernelGGL(anyk_sym_kernel, dim3(dp::grid(sh.n2)), block, 0, st, x4_2, inv ? (const uint8_t*)nullptr : raw(a.seq2), (int)(s2.flags & 1u), a.off2,
+                           sh.n2, sym + y.s2, (uint8_t*)nullptr);
+        src = AnykSrc{sym + y.s1, sym + y.r1, sym + y.s2, s1.len, a.k, inv ? 1 : 0};
+        uint32_t* idx = x.at<uint32_t>(dp::ANYK_IDX);
+        hipLaunchKernelGGL(anyk_iota_kernel, dim3(p.iota_grid), block, 0, st, idx, p.n, p.np);
+        for (const dp::SortStep& s : dp::sort_schedule(p.np)) {
+            if (s.local) hipLaunchKernelGGL(anyk_sort_local_kernel, dim3(p.tile_grid), block, 0, st, src, idx, s.full, s.kk);
+            else hipLaunchKernelGGL(anyk_sort_global_kernel, dim3(p.stride_grid), block, 0, st, src, idx, p.np, s.kk, s.jj);
+        }
+        uint32_t* cnt = x.at<uint32_t>(dp::ANYK_CNT);
+        if (p.exact) {
+            hipLaunchKernelGGL(anyk_probe_kernel, dim3(p.allele_grid), block, 0, st, src, (const uint32_t*)idx, p.n, sh.nk2, cnt, x.at<uint32_t>(dp::ANYK_FIRST));
+        } else {
+            uint32_t* isf = x.at<uint32_t>(dp::ANYK_ISF);
+            long long* rank = x.at<long long>(dp::ANYK_RANK);
+            if ((e = hipMemsetAsync(isf, 0, p.bytes[dp::ANYK_ISF], st)) != hipSuccess) return e;
+            hipLaunchKernelGGL(anyk_group_kernel, dim3(p.entry_grid), block, 0, st, src, (const uint32_t*)idx, p.n, isf, x.at<int2>(dp::ANYK_RUN));
+            hipLaunchKernelGGL(wide_scan_kernel, dim3(1), dim3(WIDE_SCAN_THREADS), 0, st, (const uint32_t*)isf, p.n, rank);
+            hipLaunchKernelGGL(anyk_rank_kernel, dim3(p.entry_grid), block, 0, st, p.n, (const uint32_t*)isf, (const long long*)rank,
+                               (const int2*)x.at<int2>(dp::ANYK_RUN), x.at<int4>(dp::ANYK_KEYS));
+            edit<false>(sh.nk2, cnt, nullptr, nullptr);
+        }
+        hipLaunchKernelGGL(wide_scan_kernel, dim3(1), dim3(WIDE_SCAN_THREADS), 0, st, (const uint32_t*)cnt, sh.nk2, x.at<long long>(dp::ANYK_OFF));
+        *d_total = x.at<long long>(dp::ANYK_OFF) + sh.nk2;
+        return hipGetLastError();
     }
-    hipError_t emit(const vapor_pair&, int nk1, int nk2)
+    hipError_t emit(const vapor_pair&, const dp::Shape& sh)
     {
-        anyk_emit(x, st, src, nk1, nk2, b.at<int2>(WideBufs::DOTS));
+        const long long* off = x.at<const long long>(dp::ANYK_OFF);
+        int2* dots = b.at<int2>(dp::DOTS);
+        if (p.exact)
+            hipLaunchKernelGGL(anyk_emit_kernel, dim3(p.allele_grid), dim3(dp::THREADS), 0, st, src, x.at<const uint32_t>(dp::ANYK_IDX), sh.nk2,
+                               (const uint32_t*)x.at<uint32_t>(dp::ANYK_CNT), (const uint32_t*)x.at<uint32_t>(dp::ANYK_FIRST), off, dots);
+        else
+            edit<true>(sh.nk2, nullptr, off, dots);
         return hipGetLastError();
     }
 };

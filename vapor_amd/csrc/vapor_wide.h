@@ -18,6 +18,8 @@
 // Every value is exact: counts and sums that can pass 2^31 are 64-bit.
 #pragma once
 
+#include "vapor_dots_plan.h"   // WideAcc, shared with the host (no HIP)
+
 namespace vapor {
 
 constexpr int WIDE_SCAN_THREADS = 1024;
@@ -113,14 +115,7 @@ __global__ __launch_bounds__(WIDE_SCAN_THREADS) void wide_scan_kernel(const uint
     if (tid == WIDE_SCAN_THREADS - 1) off[n] = incl;
 }
 
-// per-pair results of the cleaning (device side; the host turns them into the statistics record)
-struct WideAcc {
-    unsigned long long n_diag, n_lower, c1_kept, c1_sum_abs, c2_kept, c2_count10, c2_kept_diag;
-    long long dir_sum2;
-    int min_j, max_j, kd_lo, kd_hi;
-    int dir_c2x, dir_n, dir_lists, pad;
-    uint32_t max_group[4];      // largest group of each clustering pass (0: i - j over all dots, 1: i + j for C1, 2: i + j for C2)
-};
+// (the per-pair results of the cleaning, WideAcc: vapor_dots_plan.h, which turns them into the statistics record)
 
 __device__ __forceinline__ uint32_t wide_value(int2 d, int axis, int shift)
 {
