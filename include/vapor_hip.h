@@ -123,7 +123,11 @@ int vapor_destroy(vapor_ctx* ctx);
  * key) distances one launch of vapor_anyk_batch's k > 40 pass may hold - a pair of n lookup entries is cut into launches of
  * max(4, anyk_edit_pairs / n rounded down to a multiple of 4) allele k-mers), "bam_cu_share" (0 .. 8: vapor_bam_chop_device's copies and kernels
  * go to a stream masked to that many eighths of the CUs - 0 and 8: the context's own stream, all CUs; a caller that scores several
- * batches at once on several contexts leaves CUs to the other contexts' kernels this way).  Results do not depend on any of them. */
+ * batches at once on several contexts leaves CUs to the other contexts' kernels this way).  Results do not depend on any of them.
+ * A test parameter: "pool_fill" (-1, the default: off; 0 .. 255: from now on every device or pinned block the context's pool hands
+ * out, fresh or recycled, is filled with that byte over its whole capacity before the call that asked for it goes on, and so are
+ * the staging buffers of vapor_seqset_create* - each fill ends in a host-side wait for the device, so calls are slow; any other
+ * value is VAPOR_E_ARG).  No answer may depend on what a block held before: tests/test_gpu_pool_fill.py. */
 int vapor_set_param(vapor_ctx* ctx, const char* name, int64_t value);
 
 /* ---- sequences: ASCII in, packed bit planes resident in HBM ------------------------------ */

@@ -90,10 +90,14 @@ def _device(eng, bz, wins):
 
 @pytest.mark.parametrize("line_width,block_size,crlf", [(60, 65280, False), (70, 1000, False), (80, 1000, True), (60, 1000, True), (80, 65280, False)])
 def test_device_windows_equal_the_host_reader(eng, tmp_path, line_width, block_size, crlf):
+    assert check_device_windows(eng, tmp_path, line_width, block_size, crlf, 700) >= 900
+
+
+def check_device_windows(eng, tmp_path, line_width, block_size, crlf, n_draws):
+    """The body of the test above at n_draws random windows (and the block-boundary windows of chr1); returns how many windows there were."""
     gz = seqio.write_bgzf_fasta(str(tmp_path / "ref.fa.gz"), _contigs(line_width + block_size), line_width, block_size, crlf)
     bz = seqio.BgzfFasta(gz)
-    wins = _windows(bz, random.Random(block_size + line_width), 700)
-    assert len(wins) >= 900
+    wins = _windows(bz, random.Random(block_size + line_width), n_draws)
     keep, texts, traits, status, blocks = _device(eng, bz, wins)
     assert status.tolist() == [0] * len(keep)
     for q, i in enumerate(keep):
@@ -111,6 +115,7 @@ def test_device_windows_equal_the_host_reader(eng, tmp_path, line_width, block_s
         assert nocomp == bool(t & L.FASTA_TR_NOT_ACGTN_ANY_CASE)
         if not t & L.FASTA_TR_NOT_ACGTN:
             assert up
+    return len(wins)
 
 
 def test_a_foreign_subfield_in_front_of_bc_in_every_block(eng, tmp_path, monkeypatch):

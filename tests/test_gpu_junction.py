@@ -202,11 +202,11 @@ def test_call_shapes_refused_pairs_and_refusals(eng):
         ss.close()
 
 
-def test_tables_beyond_the_budget_refuse_the_call():
+def check_tables_beyond_the_budget_refuse_the_call(make_engine):
     """16 (ns + 1) bytes a pair: 65 pairs of 65 535 rows are 68 MB, above the floor of trace_budget (64 MiB) and below its default."""
     rng = np.random.default_rng(4)
     s = "".join("ACGT"[j] for j in rng.integers(0, 4, 65535))
-    e = Engine(0)
+    e = make_engine()
     try:
         ss = e.seqset([s[:40], s[:60], s])
         try:
@@ -221,6 +221,10 @@ def test_tables_beyond_the_budget_refuse_the_call():
             ss.close()
     finally:
         e.close()
+
+
+def test_tables_beyond_the_budget_refuse_the_call():
+    check_tables_beyond_the_budget_refuse_the_call(lambda: Engine(0))
 
 
 def test_one_pair_of_65535_against_65535_symbols(eng):

@@ -225,7 +225,7 @@ def test_call_shapes_empty_and_refused_loci_and_refusals(eng):
         ss.close()
 
 
-def test_the_budget_at_its_floor():
+def check_budget_at_its_floor(make_engine):
     """At the floor of trace_budget: 60 small loci, answered as at the default budget and as the model has them; twelve loci of
     six pairs of 4 000 rows at band 512 (2 MB of rows a pair) fall into several groups and one locus of seventy such pairs
     (140 MB of rows) is refused with E_NOMEM while its neighbours are served - all of it the default budget's answer, where the
@@ -248,7 +248,7 @@ def test_the_budget_at_its_floor():
     mixed = tiny[:2] + [long_locus] * 6 + [huge] + [long_locus] * 6 + tiny[2:]
     results = {}
     for budget in (None, 1):
-        e = Engine(0)
+        e = make_engine()
         try:
             if budget is not None:
                 e.set_param("trace_budget", budget)          # (below the floor: raised to it)
@@ -262,6 +262,10 @@ def test_the_budget_at_its_floor():
     assert all(g == d[2] for g in d[2:8] + d[9:15]) and d[2][4][:2] == [0, 6]
     assert d[2][4][polish.PSUB] >= 1 and d[2][4][polish.PDEL] >= 3 and d[2][4][polish.PINS] >= 7
     assert d[:2] + d[15:] == [tuple(M.polish(*l[1:])) for l in tiny]
+
+
+def test_the_budget_at_its_floor():
+    check_budget_at_its_floor(lambda: Engine(0))
 
 
 # ------------------------------------------------------------------------------------------------------------------------------

@@ -270,7 +270,7 @@ def test_call_shapes_bad_pairs_short_slots_and_refusals(eng):
         ss.close()
 
 
-def test_the_budget_at_its_floor():
+def check_budget_at_its_floor(make_engine):
     """At the floor of trace_budget sixty small loci and, between small ones, twelve loci of six pairs of 4 000 rows at band 512,
     which fall into several groups: the default budget's answers, in the polish part and in the second vote."""
     rng = np.random.default_rng(21)
@@ -285,7 +285,7 @@ def test_the_budget_at_its_floor():
     mixed = tiny[:2] + [long_locus] * 12 + tiny[2:]
     results = {}
     for budget in (None, 1):
-        e = Engine(0)
+        e = make_engine()
         try:
             if budget is not None:
                 e.set_param("trace_budget", budget)          # (below the floor: raised to it)
@@ -297,6 +297,10 @@ def test_the_budget_at_its_floor():
     d = results[None][1]
     want = _stated([(r.decode(), o) for r, o in reads], [(r.decode(), o) for r, o in votes], allele.tobytes().decode(), 512)
     assert all(g == want for g in d[2:14]) and want[0] == [0, 4040 - 3 + 7, 0, 0] and want[1][6][2:] == [2000, 4044 - 2000]
+
+
+def test_the_budget_at_its_floor():
+    check_budget_at_its_floor(lambda: Engine(0))
 
 
 def test_a_polished_allele_one_symbol_too_long(eng):

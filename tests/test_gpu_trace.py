@@ -161,7 +161,7 @@ def test_call_shapes_bad_pairs_and_refusals(eng):
         ss.close()
 
 
-def test_the_budget_at_its_floor_and_several_groups():
+def check_budget_at_its_floor_and_several_groups(make_engine):
     """300 small pairs run in one group at the floor; forty pairs of 4 000 rows at band 512 (2 MB of workspace each) among them
     make several.  Both answers equal the default budget's, and the small pairs' the model's."""
     rng = np.random.default_rng(21)
@@ -180,7 +180,7 @@ def test_the_budget_at_its_floor_and_several_groups():
     want_small = [M.trace(c[1], c[2], c[3], band) for c in cases]
     results = {}
     for budget in (None, 1):
-        e = Engine(0)
+        e = make_engine()
         try:
             if budget is not None:
                 e.set_param("trace_budget", budget)          # (below the floor: raised to it)
@@ -200,6 +200,10 @@ def test_the_budget_at_its_floor_and_several_groups():
         assert g[1] == 0 and g[2] == 4000 and sum(k for k, op in g[4] if op == "D") >= 40, g[:4]
         assert sum(k for k, op in g[4] if op in "=XI") == 4000 and sum(k for k, op in g[4] if op in "=XD") == g[3]
         assert g == got_big[row[0] - 60]                     # (the same pair gives the same trace wherever it stands)
+
+
+def test_the_budget_at_its_floor_and_several_groups():
+    check_budget_at_its_floor_and_several_groups(lambda: Engine(0))
 
 
 def test_one_long_pair(eng):

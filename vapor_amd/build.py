@@ -39,7 +39,9 @@ _HEADERS = [("vapor_kernels.h", True), ("vapor_wide.h", True), ("vapor_anyk.h", 
             # (the host side of a clean launch; the clean kernels take their constants and their LDS layout from it: device code)
             ("vapor_clean_plan.h", True),
             # (the host side of the explicit-dot routes; vapor_wide.h takes WideAcc and vapor_anyk.h its constants from it: device code)
-            ("vapor_dots_plan.h", True)]
+            ("vapor_dots_plan.h", True),
+            # (the block pool's policy, DESIGN.md 4.12: host-only)
+            ("vapor_pool.h", False)]
 DEPS = SOURCES + [os.path.join(CSRC, h) for h, _dev in _HEADERS] + [os.path.join(ROOT, "include", "vapor_hip.h")]
 KERNEL_FILES = [os.path.join(CSRC, h) for h, dev in _HEADERS if dev] + [SOURCES[0], os.path.abspath(__file__)]
 

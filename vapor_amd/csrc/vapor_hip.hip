@@ -21,6 +21,7 @@
 #include "vapor_refine.h"
 #include "vapor_planner.h"
 #include "vapor_readplan.h"
+#include "vapor_pool.h"
 #include "vapor_hip.h"
 
 #include <unistd.h>
@@ -68,20 +69,10 @@ static int refused(const std::string& entry, const vapor_image::Refusal& no) { r
 // batch cost more than the batch's kernels.  Freed blocks go to a per-context free list (by capacity) and are handed
 // out again to requests of similar size; vapor_destroy releases them.  A set or plan that outlives its context
 // frees its blocks directly.  Who gives a block back, and when it may: see CallScope / Block below the pool's functions.
-struct BlockPool {
-    std::multimap<size_t, void*> free_dev, free_host;
-    std::map<const void*, size_t> cap_of;               // capacity of every block this pool has handed out or holds
-    size_t cached_dev = 0, cached_host = 0;
-};
+// The pool's policy - rounding, the window a free block serves, the caching limits, the test fill - is vapor_pool.h's.
+using vapor_pool::BlockPool;
 static std::mutex g_live_m;
 static std::set<const void*> g_live_ctx;
-
-static size_t pool_round(size_t bytes)
-{
-    if (bytes <= 256) return 256;
-    if (bytes < ((size_t)1 << 16)) { size_t c = 256; while (c < bytes) c <<= 1; return c; }
-    return (bytes + 0xFFFF) & ~(size_t)0xFFFF;          // 64 KB steps above that
-}
 
 struct vapor_ctx {
     int device = 0;
@@ -144,18 +135,16 @@ static bool ctx_alive(const vapor_ctx* c)
 // one host thread per context (include/vapor_hip.h), so the lists themselves need no lock
 static hipError_t pool_alloc(vapor_ctx* c, void** out, size_t bytes, bool host)
 {
-    const size_t cap = pool_round(bytes);
-    auto& fl = host ? c->pool.free_host : c->pool.free_dev;
-    auto it = fl.lower_bound(cap);
-    if (it != fl.end() && it->first <= 2 * cap + ((size_t)1 << 20)) {
-        *out = it->second;
-        (host ? c->pool.cached_host : c->pool.cached_dev) -= it->first;
-        fl.erase(it);
-        return hipSuccess;
-    }
-    hipError_t e = host ? hipHostMalloc(out, cap) : hipMalloc(out, cap);
-    if (e == hipSuccess) c->pool.cap_of[*out] = cap;
-    return e;
+    return (hipError_t)vapor_pool::take(
+        c->pool, out, bytes, host,
+        [](void** o, size_t cap, bool h) { return (int)(h ? hipHostMalloc(o, cap) : hipMalloc(o, cap)); },
+        // (parameter pool_fill: the library's streams do not wait for the null stream, and the block may be used on any of them -
+        // the fill is over when the device is idle)
+        [](void* p, size_t cap, bool h, int byte) {
+            if (h) { memset(p, byte, cap); return 0; }
+            const hipError_t e = hipMemset(p, byte, cap);
+            return (int)(e != hipSuccess ? e : hipDeviceSynchronize());
+        });
 }
 static hipError_t dmalloc(vapor_ctx* c, void** out, size_t bytes) { return pool_alloc(c, out, bytes, false); }
 static hipError_t hmalloc(vapor_ctx* c, void** out, size_t bytes) { return pool_alloc(c, out, bytes, true); }
@@ -163,19 +152,9 @@ static hipError_t hmalloc(vapor_ctx* c, void** out, size_t bytes) { return pool_
 static void pool_free(vapor_ctx* c, void* p, bool host)
 {
     if (!p) return;
-    if (c && ctx_alive(c)) {
-        auto it = c->pool.cap_of.find(p);
-        if (it != c->pool.cap_of.end()) {
-            size_t& cached = host ? c->pool.cached_host : c->pool.cached_dev;
-            if (cached + it->second <= (host ? ((size_t)2 << 30) : ((size_t)16 << 30))) {
-                (host ? c->pool.free_host : c->pool.free_dev).emplace(it->second, p);
-                cached += it->second;
-                return;
-            }
-            c->pool.cap_of.erase(it);
-        }
-    }
-    if (host) (void)hipHostFree(p); else (void)hipFree(p);
+    vapor_pool::give(c && ctx_alive(c) ? &c->pool : nullptr, p, host, [](void* q, bool h) {
+        if (h) (void)hipHostFree(q); else (void)hipFree(q);
+    });
 }
 static void dfree(vapor_ctx* c, void* p) { pool_free(c, p, false); }
 static void hfree(vapor_ctx* c, void* p) { pool_free(c, p, true); }
@@ -493,6 +472,11 @@ extern "C" int vapor_set_param(vapor_ctx* c, const char* name, int64_t v)
         c->stage_threads = (int)v;
         return VAPOR_OK;
     }
+    if (!strcmp(name, "pool_fill")) {
+        if (!vapor_pool::valid_fill(v)) return fail(VAPOR_E_ARG, "vapor_set_param: pool_fill is -1 (off) or a byte, 0 .. 255");
+        c->pool.fill = (int)v;
+        return VAPOR_OK;
+    }
     return fail(VAPOR_E_ARG, std::string("unknown parameter ") + name);
 }
 
@@ -555,6 +539,13 @@ static int seqset_create_impl(vapor_ctx* ctx, const vapor_seqset_plan::Call& cal
         ctx->stage_cap = cap;
     }
     uint8_t *const h_stage = ctx->h_stage, *const d_stage = ctx->d_stage;
+    if (ctx->pool.fill != vapor_pool::FILL_OFF && ctx->stage_cap) {
+        // (parameter pool_fill: the staging buffers are no pool blocks and are never fresh after the first upload)
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        memset(h_stage, ctx->pool.fill, ctx->stage_cap);
+        HIPCHK(hipMemset(d_stage, ctx->pool.fill, ctx->stage_cap));
+        HIPCHK(hipDeviceSynchronize());
+    }
     HIPCHK(dmalloc(ctx, (void**)&s->d_seqs, desc_bytes));
     HIPCHK(dmalloc(ctx, (void**)&s->d_p2, pl * 2 * sizeof(uint32_t)));
     HIPCHK(dmalloc(ctx, (void**)&s->d_e1, pl * sizeof(uint32_t)));
