@@ -231,12 +231,14 @@ typedef struct vapor_read {
 #define VAPOR_LOCUS_STRIDE 8 /* doubles per locus: QS, GS, GT (0 = 0/0, 1 = 0/1, 2 = 1/1), GQ, reads scored,
                                 positive scores, scores that round to <= 0, reserved; all NaN but [4] = 0 for an 'NA' locus */
 /* gt_table[(k * 65 + l) * 2 + {0,1}] = genotype index and quality for k scored reads of which l round to
- * <= 0 (gt_estimate_log_likelihood SF:2054-2069, evaluated by the host with the reference's float64 steps). */
+ * <= 0 (gt_estimate_log_likelihood SF:2054-2069, evaluated by the host with the reference's float64 steps).
+ * What a read is refused for and in which order, and what the device is handed: DESIGN.md 4.11-host (csrc/vapor_finish_plan.h). */
 int vapor_plan_set_reads(vapor_plan* plan, int64_t n_reads, const vapor_read* reads, int64_t n_loci,
                          const double* gt_table);
 /* join -> clean -> per-read scores (SF:1718-1726 etc.) -> result_organize_ins (SF:1219-1231) ->
  * genotype, all on the device.  d_loci_out: device buffer (may be NULL) filled on the library's stream
- * before it is synchronised; loci_out / read_scores: host copies (may be NULL; a skipped read is NaN). */
+ * before it is synchronised; loci_out / read_scores: host copies (may be NULL; a skipped read is NaN).
+ * Which path a run takes and when it is repeated: DESIGN.md 4.11-host. */
 int vapor_plan_run_loci(vapor_plan* plan, void* d_loci_out, double* loci_out, double* read_scores);
 /*
  * The same run without a host round trip per step.  vapor_plan_run_loci_async only enqueues join -> clean -> finish
@@ -253,6 +255,7 @@ int vapor_plan_run_loci(vapor_plan* plan, void* d_loci_out, double* loci_out, do
  * collective that reads d_loci_out); vapor_plan_after makes the plan's next step wait for what the caller has
  * enqueued on its stream so far (before d_loci_out is overwritten).  vapor_set_stream makes the library enqueue
  * everything on the caller's HIP stream instead (NULL: back to its own streams).
+ * What vapor_plan_run_loci_async refuses before it enqueues anything: DESIGN.md 4.11-host.
  */
 int vapor_set_stream(vapor_ctx* ctx, void* hip_stream);
 int vapor_plan_run_loci_async(vapor_plan* plan, void* d_loci_out);
@@ -275,6 +278,8 @@ int vapor_plan_sync(vapor_plan* plan, double* loci_out);
  * VAPOR_LOCUS_STRIDE doubles, then those of the group's first candidate; winner_scores[score_off[g] .. score_off[g + 1]) = the
  * winner's per-read scores (NaN: a skipped read); score_off (n_groups + 1 entries) is filled by the call.  Any of the four may
  * be NULL.  Only these cross the link, not the candidates' records and scores.
+ * What vapor_plan_set_grid and vapor_grid_pick refuse a grid for and in which order, and the block the device is handed:
+ * DESIGN.md 4.11-host (csrc/vapor_finish_plan.h).
  */
 #define VAPOR_MAX_CANDIDATES 128 /* per group: one wavefront holds a group with two candidates per lane */
 int vapor_plan_set_grid(vapor_plan* plan, int64_t n_groups, const int32_t* first_locus);

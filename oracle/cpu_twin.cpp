@@ -13,6 +13,7 @@
  * Build: oracle/oracle.py build_twin()  (g++ -O2 -shared cpu_twin.cpp vapor_oracle.c)
  */
 #include "../include/vapor_hip.h"
+#include "vapor_finish_plan.h"      // what a read of vapor_plan_set_reads is refused for: the library's own statement
 
 #include <algorithm>
 #include <cmath>
@@ -457,11 +458,7 @@ extern "C" int vapor_plan_set_reads(vapor_plan* p, int64_t n_reads, const vapor_
     int32_t prev = -1;
     for (int64_t r = 0; r < n_reads; ++r) {
         const vapor_read& x = reads[r];
-        if (x.locus < prev || x.locus >= n_loci) return fail(VAPOR_E_ARG, "reads must be sorted by locus");
-        if (x.kind < 0 || x.kind > 3) return fail(VAPOR_E_ARG, "unknown scorer kind");
-        const int32_t q[4] = {x.ref_a, x.alt_a, x.kind == 0 ? x.ref_b : x.ref_a, x.kind == 0 ? x.alt_b : x.alt_a};
-        for (int32_t v : q)
-            if (v < 0 || v >= (int32_t)p->pairs.size()) return fail(VAPOR_E_ARG, "read refers to a pair outside the plan");
+        if (const auto no = vapor::finish_plan::read_refusal(x, prev, n_loci, (int64_t)p->pairs.size())) return fail(no.code, no.msg);
         prev = x.locus;
     }
     p->reads.assign(reads, reads + n_reads);

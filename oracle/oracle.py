@@ -40,13 +40,16 @@ def build_twin(force: bool = False) -> str:
     bam = os.path.join(os.path.dirname(_HERE), "vapor_amd", "csrc", "vapor_bam.cpp")
     srcs = [os.path.join(_HERE, "cpu_twin.cpp"), os.path.join(_HERE, "vapor_oracle.c"),
             os.path.join(os.path.dirname(_HERE), "include", "vapor_hip.h"), bam,
-            os.path.join(os.path.dirname(bam), "vapor_bgzf.h"), os.path.join(os.path.dirname(bam), "vapor_inflate.h")]
+            os.path.join(os.path.dirname(bam), "vapor_bgzf.h"), os.path.join(os.path.dirname(bam), "vapor_inflate.h"),
+            # (what vapor_plan_set_reads refuses a read for is the library's statement: HIP-free headers)
+            os.path.join(os.path.dirname(bam), "vapor_finish_plan.h"), os.path.join(os.path.dirname(bam), "vapor_image.h")]
     if force or not os.path.exists(_TWIN) or any(os.path.getmtime(_TWIN) < os.path.getmtime(x) for x in srcs):
         os.makedirs(os.path.dirname(_TWIN), exist_ok=True)
         obj = os.path.join(_HERE, "_build", "vapor_oracle_twin.o")
         subprocess.check_call(["gcc", "-O2", "-std=c11", "-fPIC", "-c", "-o", obj, srcs[1]])
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-pthread",
-                               "-I" + os.path.join(os.path.dirname(_HERE), "include"), "-o", _TWIN, srcs[0], bam, obj, "-lz"])
+                               "-I" + os.path.join(os.path.dirname(_HERE), "include"), "-I" + os.path.dirname(bam),
+                               "-o", _TWIN, srcs[0], bam, obj, "-lz"])
     return _TWIN
 
 

@@ -40,6 +40,8 @@ _HEADERS = [("vapor_kernels.h", True), ("vapor_wide.h", True), ("vapor_anyk.h", 
             ("vapor_clean_plan.h", True),
             # (the host side of the explicit-dot routes; vapor_wide.h takes WideAcc and vapor_anyk.h its constants from it: device code)
             ("vapor_dots_plan.h", True),
+            # (the host side of the finishing and grid calls; oracle/cpu_twin.cpp reads it too: host-only)
+            ("vapor_finish_plan.h", False),
             # (the block pool's policy, DESIGN.md 4.12: host-only)
             ("vapor_pool.h", False)]
 DEPS = SOURCES + [os.path.join(CSRC, h) for h, _dev in _HEADERS] + [os.path.join(ROOT, "include", "vapor_hip.h")]

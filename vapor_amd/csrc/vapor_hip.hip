@@ -19,6 +19,7 @@
 #include "vapor_bgzf.h"
 #include "vapor_fasta.h"
 #include "vapor_refine.h"
+#include "vapor_finish_plan.h"
 #include "vapor_planner.h"
 #include "vapor_readplan.h"
 #include "vapor_pool.h"
@@ -242,6 +243,48 @@ struct vapor_seqset {
     std::vector<int64_t> raw_off;
 };
 
+namespace fp = vapor::finish_plan;
+
+// A plan's finishing state (vapor_finish_plan.h): the read table and the grid described over it, each the
+// device's copy of its upload image, the blocks the kernels write, the counts and what the host keeps.  Members of the plan:
+// release() gives the blocks back when a new table comes and in the plan's destroy function.
+struct ReadTables {
+    fp::ReadImage im;
+    int64_t n_reads = 0, n_loci = 0;
+    uint8_t* d_image = nullptr;           // reads | locus_first
+    double* d_gt = nullptr;
+    bool own_gt = false;                  // false: the context's cached table
+    double* d_read_scores = nullptr;
+    double* d_loci = nullptr;
+    std::vector<int32_t> h_locus_first;   // host copy of d_locus_first()
+    bool set() const { return d_image != nullptr; }
+    const DRead* d_reads() const { return reinterpret_cast<const DRead*>(im.reads.in(d_image)); }
+    const int32_t* d_locus_first() const { return im.locus_first.in(d_image); }
+    void release(vapor_ctx* ctx)
+    {
+        dfree(ctx, d_image);
+        if (own_gt) dfree(ctx, d_gt);
+        dfree(ctx, d_read_scores);
+        dfree(ctx, d_loci);
+        *this = ReadTables();
+    }
+};
+struct GridTables {                       // groups of consecutive loci, each one locus's candidates (grid_pick_kernel)
+    fp::GridImage im;
+    int64_t n_groups = 0, n_scores = 0;
+    uint8_t* d_image = nullptr;           // first_locus | score_off | winner_idx
+    double* d_group_out = nullptr;        // a group record a group
+    double* d_winner_scores = nullptr;
+    std::vector<int32_t> score_off;       // per group: its first slot among the winners' scores
+    void release(vapor_ctx* ctx)
+    {
+        dfree(ctx, d_image);
+        dfree(ctx, d_group_out);
+        dfree(ctx, d_winner_scores);
+        *this = GridTables();
+    }
+};
+
 struct vapor_plan : PlanLayout {   // the layout the planner made (vapor_planner.h) and what the device holds of it
     vapor_ctx* ctx = nullptr;
     int device = 0;                // kept here: the plan may be destroyed after its context
@@ -287,14 +330,8 @@ struct vapor_plan : PlanLayout {   // the layout the planner made (vapor_planner
     int n_retried = 0;
     bool ran = false;
     bool flags_valid = false;                  // the last run wrote the per-record flag bytes (vapor_plan_fetch_hits hands them out)
-    // optional per-read / per-locus finishing on the device
-    int64_t n_reads = 0, n_loci = 0;
-    DRead* d_reads = nullptr;
-    int32_t* d_locus_first = nullptr;
-    double* d_gt = nullptr;
-    bool own_gt = false;              // false: the context's cached table
-    double* d_read_scores = nullptr;
-    double* d_loci = nullptr;
+    ReadTables reads;                     // optional per-read / per-locus finishing on the device (vapor_plan_set_reads)
+    GridTables grid;                      // breakpoint refinement (vapor_plan_set_grid)
     unsigned int* d_overflow = nullptr;   // [0] pairs whose slot overflowed, [1] length of d_big_list
     int32_t* d_big_list = nullptr;        // pairs with more dots than clean_kernel stages in LDS
     unsigned int* h_overflow = nullptr;   // pinned, two counters: pairs that overflowed their slot, pairs left to clean_big_kernel
@@ -308,16 +345,6 @@ struct vapor_plan : PlanLayout {   // the layout the planner made (vapor_planner
     int32_t* d_maps = nullptr;                 // `tables`
     DServe* d_serve = nullptr;
     int32_t* d_clean_order = nullptr;          // the pairs in the order their clean workgroups are dealt out (longest first)
-    // breakpoint refinement (vapor_plan_set_grid): groups of consecutive loci, each one locus's candidates (grid_pick_kernel)
-    std::vector<int32_t> h_locus_first;        // host copy of d_locus_first
-    int64_t n_groups = 0, n_grid_scores = 0;
-    std::vector<int32_t> grid_score_off;       // per group: its first slot among the winners' scores
-    int32_t* d_grid = nullptr;                 // one block: first_locus[n_groups + 1], score_off[n_groups + 1], winner_idx[n_groups]
-    double* d_group_out = nullptr;             // 16 doubles a group: the winner's record, candidate 0's record
-    double* d_winner_scores = nullptr;
-    int32_t* grid_idx_out = nullptr;           // host buffers of the vapor_plan_run_grid in progress
-    double* grid_rec_out = nullptr;
-    double* grid_scores_out = nullptr;
 };
 
 // ------------------------------------------------------------------------------------------
@@ -1230,24 +1257,6 @@ extern "C" int vapor_fasta_last_stats(vapor_ctx* ctx, double* out, int32_t n)
 }
 
 // ------------------------------------------------------------------------------------------
-static void plan_free_grid(vapor_plan* p)
-{
-    dfree(p->ctx, p->d_grid); p->d_grid = nullptr;
-    dfree(p->ctx, p->d_group_out); p->d_group_out = nullptr;
-    dfree(p->ctx, p->d_winner_scores); p->d_winner_scores = nullptr;
-    p->n_groups = 0;
-}
-
-static void plan_free_reads(vapor_plan* p)
-{
-    dfree(p->ctx, p->d_reads); p->d_reads = nullptr;
-    p->d_locus_first = nullptr;           // (inside d_reads' block)
-    if (p->own_gt) dfree(p->ctx, p->d_gt);
-    p->d_gt = nullptr; p->own_gt = false;
-    dfree(p->ctx, p->d_read_scores); p->d_read_scores = nullptr;
-    dfree(p->ctx, p->d_loci); p->d_loci = nullptr;
-}
-
 static void plan_free_device(vapor_plan* p)
 {
     dfree(p->ctx, p->d_pairs); p->d_pairs = nullptr;
@@ -1258,12 +1267,12 @@ static void plan_free_device(vapor_plan* p)
     dfree(p->ctx, p->d_hflags); p->d_hflags = nullptr;
     dfree(p->ctx, p->d_nhits); p->d_nhits = nullptr;
     dfree(p->ctx, p->d_stats); p->d_stats = nullptr;
-    plan_free_reads(p);
+    p->reads.release(p->ctx);
     dfree(p->ctx, p->d_shares); p->d_shares = nullptr;
     dfree(p->ctx, p->d_maps); p->d_maps = nullptr;
     dfree(p->ctx, p->d_serve); p->d_serve = nullptr;
     dfree(p->ctx, p->d_clean_order); p->d_clean_order = nullptr;
-    plan_free_grid(p);
+    p->grid.release(p->ctx);
 }
 
 extern "C" int vapor_plan_destroy(vapor_plan* p)
@@ -2455,7 +2464,8 @@ extern "C" int vapor_realign_junction(vapor_ctx* ctx, vapor_seqset* set, int64_t
 }
 
 // ------------------------------------------------------------------------------------------
-// per-read scores and per-locus summaries on the device
+// per-read scores and per-locus summaries on the device, and the breakpoint grid over them.  What a call is refused for, the
+// upload images and every size are vapor_finish_plan.h's.
 extern "C" int vapor_plan_set_reads(vapor_plan* p, int64_t n_reads, const vapor_read* reads, int64_t n_loci,
                                     const double* gt_table)
 {
@@ -2463,195 +2473,183 @@ extern "C" int vapor_plan_set_reads(vapor_plan* p, int64_t n_reads, const vapor_
         return fail(VAPOR_E_ARG, "vapor_plan_set_reads: null argument");
     static_assert(sizeof(vapor_read) == sizeof(DRead), "vapor_read layout");
     HIPCHK(hipSetDevice(p->ctx->device));
-    std::vector<int32_t> first((size_t)n_loci + 1, 0);
-    int32_t prev = -1;
-    for (int64_t r = 0; r < n_reads; ++r) {
-        const vapor_read& x = reads[r];
-        if (x.locus < prev || x.locus >= n_loci) return fail(VAPOR_E_ARG, "reads must be sorted by locus");
-        const int32_t idx[4] = {x.ref_a, x.alt_a, x.kind == 0 ? x.ref_b : x.ref_a, x.kind == 0 ? x.alt_b : x.alt_a};
-        for (int32_t q : idx)
-            if (q < 0 || q >= p->n_pairs) return fail(VAPOR_E_ARG, "read refers to a pair outside the plan");
-        if (x.kind < 0 || x.kind > 3) return fail(VAPOR_E_ARG, "unknown scorer kind");
-        prev = x.locus;
-        first[(size_t)x.locus + 1]++;
-    }
-    for (int64_t l = 0; l < n_loci; ++l) first[l + 1] += first[l];
-    plan_free_reads(p);
-    // the read table and the locus offsets travel as one block (one blocking copy out of caller memory instead of two)
-    const size_t reads_bytes = (sizeof(DRead) * (size_t)std::max<int64_t>(n_reads, 1) + 15) & ~(size_t)15;
-    const size_t first_bytes = sizeof(int32_t) * first.size();
-    std::vector<uint8_t> blockv(reads_bytes + first_bytes, 0);
-    if (n_reads) memcpy(blockv.data(), reads, sizeof(DRead) * (size_t)n_reads);
-    memcpy(blockv.data() + reads_bytes, first.data(), first_bytes);
-    HIPCHK(dmalloc(p->ctx, (void**)&p->d_reads, blockv.size()));
-    p->d_locus_first = reinterpret_cast<int32_t*>(reinterpret_cast<uint8_t*>(p->d_reads) + reads_bytes);
-    HIPCHK(dmalloc(p->ctx, (void**)&p->d_read_scores, sizeof(double) * std::max<int64_t>(n_reads, 1)));
-    HIPCHK(dmalloc(p->ctx, (void**)&p->d_loci, sizeof(double) * 8 * std::max<int64_t>(n_loci, 1)));
-    HIPCHK(hipMemcpy(p->d_reads, blockv.data(), blockv.size(), hipMemcpyHostToDevice));
+    std::vector<int32_t> first;
+    std::vector<uint8_t> image;
+    fp::ReadImage im;
+    if (const fp::Refusal no = fp::read_table(n_reads, reads, n_loci, p->n_pairs, first, im, image)) return fail(no.code, no.msg);
+    ReadTables& t = p->reads;
+    t.release(p->ctx);
+    t.im = im;
+    HIPCHK(dmalloc(p->ctx, (void**)&t.d_image, im.bytes));
+    HIPCHK(dmalloc(p->ctx, (void**)&t.d_read_scores, im.score_bytes));
+    HIPCHK(dmalloc(p->ctx, (void**)&t.d_loci, im.loci_bytes));
+    HIPCHK(hipMemcpy(t.d_image, image.data(), image.size(), hipMemcpyHostToDevice));
     // the genotype table is the same for every plan of a run: uploaded once per context, again only for a different one
     {
         vapor_ctx* c = p->ctx;
-        const size_t gt_n = (size_t)2 * VAPOR_GT_TABLE_N * VAPOR_GT_TABLE_N;
+        const size_t gt_bytes = sizeof(double) * fp::GT_ENTRIES;
         if (!c->d_gt) {
-            HIPCHK(hipMalloc((void**)&c->d_gt, sizeof(double) * gt_n));
-            HIPCHK(hipMemcpy(c->d_gt, gt_table, sizeof(double) * gt_n, hipMemcpyHostToDevice));
-            c->h_gt.assign(gt_table, gt_table + gt_n);
+            HIPCHK(hipMalloc((void**)&c->d_gt, gt_bytes));
+            HIPCHK(hipMemcpy(c->d_gt, gt_table, gt_bytes, hipMemcpyHostToDevice));
+            c->h_gt.assign(gt_table, gt_table + fp::GT_ENTRIES);
         }
-        if (memcmp(c->h_gt.data(), gt_table, sizeof(double) * gt_n) == 0) {
-            p->d_gt = c->d_gt;
+        if (memcmp(c->h_gt.data(), gt_table, gt_bytes) == 0) {
+            t.d_gt = c->d_gt;
         } else {
-            HIPCHK(dmalloc(c, (void**)&p->d_gt, sizeof(double) * gt_n));
-            p->own_gt = true;
-            HIPCHK(hipMemcpy(p->d_gt, gt_table, sizeof(double) * gt_n, hipMemcpyHostToDevice));
+            HIPCHK(dmalloc(c, (void**)&t.d_gt, gt_bytes));
+            t.own_gt = true;
+            HIPCHK(hipMemcpy(t.d_gt, gt_table, gt_bytes, hipMemcpyHostToDevice));
         }
     }
-    p->n_reads = n_reads;
-    p->n_loci = n_loci;
-    p->h_locus_first = first;
+    t.n_reads = n_reads;
+    t.n_loci = n_loci;
+    t.h_locus_first = std::move(first);
     // (a grid described for an earlier read table does not describe this one)
-    plan_free_grid(p);
-    return VAPOR_OK;
-}
-
-// Breakpoint refinement: the loci are the candidates of n_groups refined loci, group g the loci first_locus[g] ..
-// first_locus[g + 1].  Every candidate of a group scores the group's reads, so all of them have one read count (lf: the loci's
-// read ranges); off[g] .. off[g + 1]: the group's slots among the winners' scores.  Everything grid_pick_kernel indexes with
-// is checked here.
-static int grid_check(int64_t n_groups, const int32_t* first_locus, int64_t n_loci, const int32_t* lf, std::vector<int32_t>* off)
-{
-    if (first_locus[0] != 0 || first_locus[n_groups] != n_loci) return fail(VAPOR_E_ARG, "grid: the groups must cover the loci");
-    off->assign((size_t)n_groups + 1, 0);
-    for (int64_t g = 0; g < n_groups; ++g) {
-        const int32_t a = first_locus[g], b = first_locus[g + 1];
-        if (a < 0 || b <= a || b - a > VAPOR_MAX_CANDIDATES || b > n_loci)
-            return fail(VAPOR_E_ARG, "grid: a group holds 1 .. VAPOR_MAX_CANDIDATES consecutive loci");
-        const int32_t nr = lf[(size_t)a + 1] - lf[a];
-        if (nr < 0) return fail(VAPOR_E_ARG, "grid: read ranges must not decrease");
-        for (int32_t c = a; c < b; ++c)
-            if (lf[(size_t)c + 1] - lf[c] != nr) return fail(VAPOR_E_ARG, "grid: the candidates of a group score the same reads");
-        if ((int64_t)(*off)[g] + nr > INT32_MAX) return fail(VAPOR_E_ARG, "grid: too many reads");
-        (*off)[g + 1] = (*off)[g] + nr;
-    }
+    p->grid.release(p->ctx);
     return VAPOR_OK;
 }
 
 extern "C" int vapor_plan_set_grid(vapor_plan* p, int64_t n_groups, const int32_t* first_locus)
 {
     if (!p || n_groups < 0 || !first_locus) return fail(VAPOR_E_ARG, "vapor_plan_set_grid: null argument");
-    if (!p->d_reads) return fail(VAPOR_E_ARG, "vapor_plan_set_grid: call vapor_plan_set_reads first");
+    if (!p->reads.set()) return fail(VAPOR_E_ARG, "vapor_plan_set_grid: call vapor_plan_set_reads first");
     HIPCHK(hipSetDevice(p->ctx->device));
     std::vector<int32_t> off;
-    const int rc = grid_check(n_groups, first_locus, p->n_loci, p->h_locus_first.data(), &off);
-    if (rc != VAPOR_OK) return rc;
-    plan_free_grid(p);
+    if (const fp::Refusal no = fp::grid_check(n_groups, first_locus, p->reads.n_loci, p->reads.h_locus_first.data(), off))
+        return fail(no.code, no.msg);
+    GridTables& g = p->grid;
+    g.release(p->ctx);
     if (n_groups == 0) return VAPOR_OK;
-    const size_t ng = (size_t)n_groups;
-    std::vector<int32_t> block(3 * ng + 2, 0);
-    memcpy(block.data(), first_locus, sizeof(int32_t) * (ng + 1));
-    memcpy(block.data() + ng + 1, off.data(), sizeof(int32_t) * (ng + 1));
-    HIPCHK(dmalloc(p->ctx, (void**)&p->d_grid, sizeof(int32_t) * block.size()));
-    HIPCHK(dmalloc(p->ctx, (void**)&p->d_group_out, sizeof(double) * 16 * ng));
-    HIPCHK(dmalloc(p->ctx, (void**)&p->d_winner_scores, sizeof(double) * (size_t)std::max<int32_t>(off[ng], 1)));
-    HIPCHK(hipMemcpy(p->d_grid, block.data(), sizeof(int32_t) * block.size(), hipMemcpyHostToDevice));
-    p->grid_score_off = off;
-    p->n_grid_scores = off[ng];
-    p->n_groups = n_groups;
+    g.im = fp::GridImage((size_t)n_groups, off.back(), 0);
+    const std::vector<uint8_t> image = g.im.filled(first_locus, off, nullptr);
+    HIPCHK(dmalloc(p->ctx, (void**)&g.d_image, g.im.bytes));
+    HIPCHK(dmalloc(p->ctx, (void**)&g.d_group_out, g.im.group_bytes));
+    HIPCHK(dmalloc(p->ctx, (void**)&g.d_winner_scores, g.im.winner_bytes));
+    HIPCHK(hipMemcpy(g.d_image, image.data(), image.size(), hipMemcpyHostToDevice));
+    g.n_scores = off.back();
+    g.score_off = std::move(off);
+    g.n_groups = n_groups;
     return VAPOR_OK;
 }
 
-// join -> clean -> finish on the device; the per-pair statistics stay in HBM.  d_loci_out (device
-// pointer, n_loci * 8 doubles, may be NULL) receives a copy on the library's stream before it is
-// synchronised; loci_out / read_scores (host, may be NULL) receive host copies.
-extern "C" int vapor_plan_run_loci(vapor_plan* p, void* d_loci_out, double* loci_out, double* read_scores)
+// finish_kernel over a read table, a workgroup a locus: the per-read scores into the table's block, the locus records to d_out and,
+// where h_copy is given (pinned host memory), there as well
+static int launch_finish(hipStream_t st, const ReadTables& t, const long long* d_stats, double* d_out, double* h_copy)
 {
-    if (!p) return fail(VAPOR_E_ARG, "vapor_plan_run_loci: null plan");
-    if (!p->d_reads) return fail(VAPOR_E_ARG, "vapor_plan_run_loci: call vapor_plan_set_reads first");
+    if (t.n_loci <= 0) return VAPOR_OK;
+    hipLaunchKernelGGL(finish_kernel, dim3((unsigned)t.n_loci), dim3(64), 0, st, t.d_reads(), t.d_locus_first(), d_stats, t.d_gt,
+                       t.d_read_scores, d_out, h_copy);
+    HIPCHK(hipGetLastError());
+    return VAPOR_OK;
+}
+
+// grid_pick_kernel, a workgroup a group, and what of its answers the caller wants on the host
+struct GridOut { int32_t* winner_idx; double* group_out; double* winner_scores; };     // host arrays, each may be null
+struct GridView {
+    const fp::GridImage& im;
+    uint8_t* d_image;
+    size_t n_scores;
+    const double* d_records;                   // the candidates' locus records
+    const int32_t* d_read_first;               // ... and read ranges
+    const double* d_read_scores;
+    double *d_group_out, *d_winner_scores;
+};
+static int launch_grid_pick(hipStream_t st, const GridView& v, const GridOut& o)
+{
+    int32_t* d_idx = v.im.winner_idx.in(v.d_image);
+    hipLaunchKernelGGL(grid_pick_kernel, dim3((unsigned)v.im.winner_idx.n), dim3(64), 0, st, v.d_records, v.im.first_locus.in(v.d_image),
+                       v.d_read_first, v.d_read_scores, v.im.score_off.in(v.d_image), d_idx, v.d_group_out, v.d_winner_scores);
+    HIPCHK(hipGetLastError());
+    if (o.winner_idx) HIPCHK(hipMemcpyAsync(o.winner_idx, d_idx, v.im.winner_idx.bytes(), hipMemcpyDeviceToHost, st));
+    if (o.group_out) HIPCHK(hipMemcpyAsync(o.group_out, v.d_group_out, v.im.group_bytes, hipMemcpyDeviceToHost, st));
+    if (o.winner_scores && v.n_scores)
+        HIPCHK(hipMemcpyAsync(o.winner_scores, v.d_winner_scores, sizeof(double) * v.n_scores, hipMemcpyDeviceToHost, st));
+    return VAPOR_OK;
+}
+
+// join -> clean -> finish (-> the choice among each group's candidates when the plan has a grid) on the device; the per-pair
+// statistics stay in HBM.  grid_out: where vapor_plan_run_grid wants the choice, or null.
+static int run_loci_impl(vapor_plan* p, void* d_loci_out, double* loci_out, double* read_scores, const GridOut* grid_out)
+{
     HIPCHK(hipSetDevice(p->ctx->device));
     if (p->ring_n > 0) {
         int rc0 = async_fold(p);
         if (rc0 != VAPOR_OK) return rc0;
     }
     hipStream_t st = p->ctx->stream;
-    bool host_status = false;
-    for (int64_t i = 0; i < p->n_pairs; ++i)
-        if (p->status[i] != 0) { host_status = true; break; }
+    const ReadTables& t = p->reads;
+    bool host_status = fp::any_status(p->status.data(), p->n_pairs);
     int rc;
-    const bool light = !(host_status || !p->ran);
+    const bool light = fp::light_run(p->ran, host_status);
     if (!light) {
         // first run, or pairs the host marked as failed: full path once (statistics to the host, slots grown)
         rc = vapor_plan_run(p, p->last_stats.data());
         if (rc != VAPOR_OK) return rc;
         // (the run itself may have given pairs a host-side status: the targets of a shared dot plot beyond max_pair_cap)
-        for (int64_t i = 0; i < p->n_pairs && !host_status; ++i)
-            if (p->status[i] != 0) host_status = true;
-        if (host_status)
-            HIPCHK(hipMemcpyAsync(p->d_stats, p->h_stats, sizeof(long long) * 16 * (size_t)p->n_pairs, hipMemcpyHostToDevice, st));
+        host_status = host_status || fp::any_status(p->status.data(), p->n_pairs);
     } else {
         rc = plan_run_once(p, 0, false, nullptr, nullptr, false, nullptr, false);
         if (rc != VAPOR_OK) return rc;
     }
+    if (fp::reupload_statuses(light, host_status))
+        HIPCHK(hipMemcpyAsync(p->d_stats, p->h_stats, sizeof(long long) * fp::STATS_WORDS * (size_t)p->n_pairs, hipMemcpyHostToDevice, st));
     hipEvent_t e1 = p->ev_f[1];                  // the finish kernel starts where the clean kernels end (ev[2])
-    double* d_out = d_loci_out ? static_cast<double*>(d_loci_out) : p->d_loci;
-    if (p->n_loci > 0) {
-        hipLaunchKernelGGL(finish_kernel, dim3((unsigned)p->n_loci), dim3(64), 0, st, p->d_reads, p->d_locus_first, p->d_stats,
-                           p->d_gt, p->d_read_scores, d_out, (double*)nullptr);
-        HIPCHK(hipGetLastError());
-    }
+    double* d_out = d_loci_out ? static_cast<double*>(d_loci_out) : t.d_loci;
+    if ((rc = launch_finish(st, t, p->d_stats, d_out, nullptr)) != VAPOR_OK) return rc;
     HIPCHK(hipEventRecord(e1, st));
-    if (p->n_groups > 0 && p->n_loci > 0) {
-        // the choice among each group's candidates, behind the finish kernel on its stream (no host step in between)
-        const size_t ng = (size_t)p->n_groups;
-        int32_t* d_idx = p->d_grid + 2 * ng + 2;
-        hipLaunchKernelGGL(grid_pick_kernel, dim3((unsigned)ng), dim3(64), 0, st, d_out, p->d_grid, p->d_locus_first, p->d_read_scores,
-                           p->d_grid + ng + 1, d_idx, p->d_group_out, p->d_winner_scores);
-        HIPCHK(hipGetLastError());
-        if (p->grid_idx_out) HIPCHK(hipMemcpyAsync(p->grid_idx_out, d_idx, sizeof(int32_t) * ng, hipMemcpyDeviceToHost, st));
-        if (p->grid_rec_out) HIPCHK(hipMemcpyAsync(p->grid_rec_out, p->d_group_out, sizeof(double) * 16 * ng, hipMemcpyDeviceToHost, st));
-        if (p->grid_scores_out && p->n_grid_scores)
-            HIPCHK(hipMemcpyAsync(p->grid_scores_out, p->d_winner_scores, sizeof(double) * (size_t)p->n_grid_scores, hipMemcpyDeviceToHost, st));
+    const GridTables& g = p->grid;
+    if (g.n_groups > 0 && t.n_loci > 0) {
+        // behind the finish kernel on its stream (no host step in between)
+        const GridView v{g.im, g.d_image, (size_t)g.n_scores, d_out, t.d_locus_first(), t.d_read_scores,
+                         g.d_group_out, g.d_winner_scores};
+        if ((rc = launch_grid_pick(st, v, grid_out ? *grid_out : GridOut{})) != VAPOR_OK) return rc;
     }
     // only the overflow count has to come back (after the finish kernel, so that nothing sits between the kernels)
     HIPCHK(hipMemcpyAsync(p->h_overflow, p->d_overflow, 2 * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
-    if (loci_out && p->n_loci)
-        HIPCHK(hipMemcpyAsync(loci_out, d_out, sizeof(double) * 8 * (size_t)p->n_loci, hipMemcpyDeviceToHost, st));
-    if (read_scores && p->n_reads)
-        HIPCHK(hipMemcpyAsync(read_scores, p->d_read_scores, sizeof(double) * (size_t)p->n_reads, hipMemcpyDeviceToHost, st));
+    if (loci_out && t.n_loci)
+        HIPCHK(hipMemcpyAsync(loci_out, d_out, sizeof(double) * fp::LOCUS_DOUBLES * (size_t)t.n_loci, hipMemcpyDeviceToHost, st));
+    if (read_scores && t.n_reads)
+        HIPCHK(hipMemcpyAsync(read_scores, t.d_read_scores, sizeof(double) * (size_t)t.n_reads, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    if (light && *p->h_overflow != 0 && !p->overflow_final) {
-        // some pair outgrew its record slot on this run: redo through the full path, which resizes.  Pairs that
-        // still overflow after that (their slot would exceed max_pair_cap) keep VAPOR_E_OVERFLOW in their
-        // statistics and are scored as reads without a usable plot; nothing is retried for them again.
+    if (fp::repeat_full(light, *p->h_overflow != 0, p->overflow_final)) {
+        // some pair outgrew its record slot on this run: the full path resizes, then the whole run once more.  A pair that still
+        // overflows (its slot would pass max_pair_cap) keeps VAPOR_E_OVERFLOW in its statistics: overflow_final, no further repeat
         rc = vapor_plan_run(p, p->last_stats.data());
         if (rc != VAPOR_OK) return rc;
-        for (int64_t i = 0; i < p->n_pairs; ++i)
-            if (p->last_stats[16 * (size_t)i + 15] == VAPOR_E_OVERFLOW) { p->overflow_final = true; break; }
-        return vapor_plan_run_loci(p, d_loci_out, loci_out, read_scores);
+        if (fp::still_overflows(p->last_stats.data(), p->n_pairs)) p->overflow_final = true;
+        return run_loci_impl(p, d_loci_out, loci_out, read_scores, grid_out);
     }
     p->big_known = true;
     p->n_big = p->h_overflow[1];
-    float f = 0, a = 0, b = 0, t = 0;
+    float f = 0, a = 0, b = 0, tt = 0;
     HIPCHK(hipEventElapsedTime(&f, p->ev[2], e1));
     p->t_finish = f;
     if (hipEventElapsedTime(&a, p->ev[0], p->ev[1]) == hipSuccess && hipEventElapsedTime(&b, p->ev[1], p->ev[2]) == hipSuccess &&
-        hipEventElapsedTime(&t, p->ev[0], e1) == hipSuccess) {
-        p->t_join = a; p->t_clean = b; p->t_total = t;
+        hipEventElapsedTime(&tt, p->ev[0], e1) == hipSuccess) {
+        p->t_join = a; p->t_clean = b; p->t_total = tt;
     }
     return VAPOR_OK;
 }
 
-// vapor_plan_run_loci with the choice among each group's candidates behind it (grid_pick_kernel): per group the winner's index
-// among its candidates, 16 doubles (the winner's record, candidate 0's), and the winner's per-read scores (group g's at
-// score_off[g] .. score_off[g + 1]; a skipped read is NaN).  Only these cross the link.
+// d_loci_out (device pointer, n_loci * VAPOR_LOCUS_STRIDE doubles, may be NULL) receives a copy on the library's stream before it
+// is synchronised; loci_out / read_scores (host, may be NULL) receive host copies.
+extern "C" int vapor_plan_run_loci(vapor_plan* p, void* d_loci_out, double* loci_out, double* read_scores)
+{
+    if (!p) return fail(VAPOR_E_ARG, "vapor_plan_run_loci: null plan");
+    if (!p->reads.set()) return fail(VAPOR_E_ARG, "vapor_plan_run_loci: call vapor_plan_set_reads first");
+    return run_loci_impl(p, d_loci_out, loci_out, read_scores, nullptr);
+}
+
+// vapor_plan_run_loci with the choice among each group's candidates handed out: per group the winner's index among its candidates,
+// a group record (the winner's locus record, candidate 0's), and the winner's per-read scores (group g's at score_off[g] ..
+// score_off[g + 1]; a skipped read is NaN).  Only these cross the link.
 extern "C" int vapor_plan_run_grid(vapor_plan* p, int32_t* winner_idx, double* group_out, double* winner_scores, int64_t* score_off)
 {
     if (!p) return fail(VAPOR_E_ARG, "vapor_plan_run_grid: null plan");
-    if (p->n_groups <= 0 || !p->d_grid) return fail(VAPOR_E_ARG, "vapor_plan_run_grid: call vapor_plan_set_grid first");
-    if (score_off)
-        for (int64_t g = 0; g <= p->n_groups; ++g) score_off[g] = p->grid_score_off[(size_t)g];
-    p->grid_idx_out = winner_idx; p->grid_rec_out = group_out; p->grid_scores_out = winner_scores;
-    const int rc = vapor_plan_run_loci(p, nullptr, nullptr, nullptr);
-    p->grid_idx_out = nullptr; p->grid_rec_out = nullptr; p->grid_scores_out = nullptr;
-    return rc;
+    if (p->grid.n_groups <= 0 || !p->grid.d_image) return fail(VAPOR_E_ARG, "vapor_plan_run_grid: call vapor_plan_set_grid first");
+    if (score_off) std::copy(p->grid.score_off.begin(), p->grid.score_off.end(), score_off);
+    const GridOut out{winner_idx, group_out, winner_scores};
+    return run_loci_impl(p, nullptr, nullptr, nullptr, &out);
 }
 
 // grid_pick_kernel on the caller's tables (records and scores computed elsewhere; the tests' hand-made ones): one call, host
@@ -2662,41 +2660,29 @@ extern "C" int vapor_grid_pick(vapor_ctx* ctx, int64_t n_groups, const int32_t* 
 {
     if (!ctx || n_groups < 0 || !first_locus || !records || !read_first) return fail(VAPOR_E_ARG, "vapor_grid_pick: null argument");
     HIPCHK(hipSetDevice(ctx->device));
-    const int64_t n_loci = first_locus[n_groups];
-    if (n_loci < 0 || n_loci > INT32_MAX || read_first[0] != 0) return fail(VAPOR_E_ARG, "vapor_grid_pick: bad ranges");
-    for (int64_t c = 0; c < n_loci; ++c)
-        if (read_first[c + 1] < read_first[c]) return fail(VAPOR_E_ARG, "vapor_grid_pick: read ranges must not decrease");
     std::vector<int32_t> off;
-    const int rc = grid_check(n_groups, first_locus, n_loci, read_first, &off);
-    if (rc != VAPOR_OK) return rc;
-    if (score_off)
-        for (int64_t g = 0; g <= n_groups; ++g) score_off[g] = off[(size_t)g];
+    if (const fp::Refusal no = fp::pick_check(n_groups, first_locus, read_first, off)) return fail(no.code, no.msg);
+    if (score_off) std::copy(off.begin(), off.end(), score_off);
     if (n_groups == 0) return VAPOR_OK;
-    const size_t ng = (size_t)n_groups, nl = (size_t)n_loci, nr = (size_t)read_first[n_loci], nw = (size_t)off[ng];
-    if (nr && !read_scores) return fail(VAPOR_E_ARG, "vapor_grid_pick: null argument");
-    std::vector<int32_t> block(3 * ng + 2 + nl + 1, 0);
-    memcpy(block.data(), first_locus, sizeof(int32_t) * (ng + 1));
-    memcpy(block.data() + ng + 1, off.data(), sizeof(int32_t) * (ng + 1));
-    memcpy(block.data() + 3 * ng + 2, read_first, sizeof(int32_t) * (nl + 1));
+    const size_t nl = (size_t)first_locus[n_groups], nr = (size_t)read_first[nl], nw = (size_t)off.back();
+    if (const fp::Refusal no = fp::pick_scores_check(nr, read_scores)) return fail(no.code, no.msg);
+    const fp::GridImage im((size_t)n_groups, off.back(), nl + 1);
+    const std::vector<uint8_t> image = im.filled(first_locus, off, read_first);
+    const size_t rec_bytes = sizeof(double) * fp::LOCUS_DOUBLES * nl;
     hipStream_t st = ctx->stream;
     CallScope sc(ctx, st);
-    Block<int32_t> d_block(sc);
+    Block<uint8_t> d_image(sc);
     Block<double> d_rec(sc), d_sc(sc), d_out(sc), d_win(sc);
-    HIPCHK(d_block.ensure(sizeof(int32_t) * block.size()));
-    HIPCHK(d_rec.ensure(sizeof(double) * 8 * nl));
+    HIPCHK(d_image.ensure(im.bytes));
+    HIPCHK(d_rec.ensure(rec_bytes));
     HIPCHK(d_sc.ensure(sizeof(double) * std::max<size_t>(nr, 1)));
-    HIPCHK(d_out.ensure(sizeof(double) * 16 * ng));
-    HIPCHK(d_win.ensure(sizeof(double) * std::max<size_t>(nw, 1)));
-    HIPCHK(hipMemcpyAsync(d_block, block.data(), sizeof(int32_t) * block.size(), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_rec, records, sizeof(double) * 8 * nl, hipMemcpyHostToDevice, st));
+    HIPCHK(d_out.ensure(im.group_bytes));
+    HIPCHK(d_win.ensure(im.winner_bytes));
+    HIPCHK(hipMemcpyAsync(d_image, image.data(), image.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_rec, records, rec_bytes, hipMemcpyHostToDevice, st));
     if (nr) HIPCHK(hipMemcpyAsync(d_sc, read_scores, sizeof(double) * nr, hipMemcpyHostToDevice, st));
-    int32_t* d_idx = d_block + 2 * ng + 2;
-    hipLaunchKernelGGL(grid_pick_kernel, dim3((unsigned)ng), dim3(64), 0, st, d_rec.p, d_block.p, d_block + 3 * ng + 2, d_sc.p,
-                       d_block + ng + 1, d_idx, d_out.p, d_win.p);
-    HIPCHK(hipGetLastError());
-    if (winner_idx) HIPCHK(hipMemcpyAsync(winner_idx, d_idx, sizeof(int32_t) * ng, hipMemcpyDeviceToHost, st));
-    if (group_out) HIPCHK(hipMemcpyAsync(group_out, d_out, sizeof(double) * 16 * ng, hipMemcpyDeviceToHost, st));
-    if (winner_scores && nw) HIPCHK(hipMemcpyAsync(winner_scores, d_win, sizeof(double) * nw, hipMemcpyDeviceToHost, st));
+    const GridView v{im, d_image.p, nw, d_rec.p, im.read_first.in(d_image.p), d_sc.p, d_out.p, d_win.p};
+    if (const int rc = launch_grid_pick(st, v, GridOut{winner_idx, group_out, winner_scores})) return rc;
     HIPCHK(hipStreamSynchronize(st));
     sc.settled();
     return VAPOR_OK;
@@ -2818,10 +2804,7 @@ static int async_fold(vapor_plan* p)
 extern "C" int vapor_plan_run_loci_async(vapor_plan* p, void* d_loci_out)
 {
     if (!p) return fail(VAPOR_E_ARG, "vapor_plan_run_loci_async: null plan");
-    if (!p->d_reads) return fail(VAPOR_E_ARG, "vapor_plan_run_loci_async: call vapor_plan_set_reads first");
-    if (!p->ran) return fail(VAPOR_E_ARG, "vapor_plan_run_loci_async: run the plan once with vapor_plan_run_loci first (it sizes the slots)");
-    for (int64_t i = 0; i < p->n_pairs; ++i)
-        if (p->status[i] != 0) return fail(VAPOR_E_ARG, "vapor_plan_run_loci_async: the plan holds pairs the host rejected; use vapor_plan_run_loci");
+    if (const fp::Refusal no = fp::async_refusal(p->reads.set(), p->ran, p->status.data(), p->n_pairs)) return fail(no.code, no.msg);
     HIPCHK(hipSetDevice(p->ctx->device));
     if (p->ring_n >= ASYNC_RING) {              // every event set is in use: wait for those steps, keep their times
         int rc0 = async_fold(p);
@@ -2834,7 +2817,7 @@ extern "C" int vapor_plan_run_loci_async(vapor_plan* p, void* d_loci_out)
         p->ring.resize(ASYNC_RING);
         for (auto& r : p->ring)
             for (auto& e : r) { e = nullptr; HIPCHK(hipEventCreate(&e)); }
-        HIPCHK(hmalloc(p->ctx, (void**)&p->h_loci, sizeof(double) * 8 * (size_t)std::max<int64_t>(p->n_loci, 1)));
+        HIPCHK(hmalloc(p->ctx, (void**)&p->h_loci, p->reads.im.loci_bytes));
         HIPCHK(hipEventCreateWithFlags(&p->ev_last, hipEventDisableTiming));
         HIPCHK(hipEventCreateWithFlags(&p->ev_clean, hipEventDisableTiming));
         HIPCHK(hipEventCreateWithFlags(&p->ev_fin, hipEventDisableTiming));
@@ -2857,17 +2840,13 @@ extern "C" int vapor_plan_run_loci_async(vapor_plan* p, void* d_loci_out)
     if (rc != VAPOR_OK) return rc;
     rc = plan_run_once(p, table, false, ev, st, p->big_known && p->n_big == 0, (fs != st && p->have_fin) ? p->ev_fin : nullptr, false);
     if (rc != VAPOR_OK) return rc;
-    double* d_out = d_loci_out ? static_cast<double*>(d_loci_out) : p->d_loci;
+    double* d_out = d_loci_out ? static_cast<double*>(d_loci_out) : p->reads.d_loci;
     if (fs != st) {
         HIPCHK(hipEventRecord(p->ev_clean, st));
         HIPCHK(hipStreamWaitEvent(fs, p->ev_clean, 0));
     }
-    if (p->n_loci > 0) {
-        // (the finish kernel writes the pinned host copy itself: no copy kernel behind it)
-        hipLaunchKernelGGL(finish_kernel, dim3((unsigned)p->n_loci), dim3(64), 0, fs, p->d_reads, p->d_locus_first, p->d_stats,
-                           p->d_gt, p->d_read_scores, d_out, p->h_loci);
-        HIPCHK(hipGetLastError());
-    }
+    // (the finish kernel writes the pinned host copy itself: no copy kernel behind it)
+    if ((rc = launch_finish(fs, p->reads, p->d_stats, d_out, p->h_loci)) != VAPOR_OK) return rc;
     HIPCHK(hipEventRecord(ev[3], fs));
     HIPCHK(hipEventRecord(p->ev_last, fs));
     if (fs != st) {
@@ -2915,7 +2894,8 @@ extern "C" int vapor_plan_sync(vapor_plan* p, double* loci_out)
     if (p->acc_n > 0) {
         p->t_join = (float)(p->acc_ms[0] / p->acc_n); p->t_clean = (float)(p->acc_ms[1] / p->acc_n);
         p->t_finish = (float)(p->acc_ms[2] / p->acc_n); p->t_total = (float)(p->acc_ms[3] / p->acc_n);
-        if (loci_out && p->n_loci && (had > 0 || p->h_loci)) memcpy(loci_out, p->h_loci, sizeof(double) * 8 * (size_t)p->n_loci);
+        if (loci_out && p->reads.n_loci && (had > 0 || p->h_loci))
+            memcpy(loci_out, p->h_loci, sizeof(double) * fp::LOCUS_DOUBLES * (size_t)p->reads.n_loci);
     }
     p->acc_ms[0] = p->acc_ms[1] = p->acc_ms[2] = p->acc_ms[3] = 0;
     p->acc_n = 0;
